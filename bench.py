@@ -25,6 +25,7 @@ Rank 0 prints ONE JSON line with the contract fields plus
   chain         the receive chain behind one handle (include/tetra_rx.h) on coded downlinks: steady-state ms per second of 4096
                 channels on two streams / one stream, stage times with rooflines, CRC-good and exact-block counters (informational;
                 also --chain-only).
+--dump-outputs DIR writes what the last timed step returned (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +52,10 @@ HBM_PEAK_GBS = 8000.0
 FLOP_PER_SAMPLE = 935.0
 VALU_PEAK_TFLOPS = 157.3          # MI355X FP32 vector peak (MI355X_MICROARCH.md)
 RAMP_STEPS = 8                    # untimed passes that bring the shader clock up before warm-up (see main)
+DUMP_CHANNELS = 256               # --dump-outputs: bit rows of at most this many channels (a fixed, seeded sample), every channel's count
+DUMP_SEED = 20260001
+DUMP_BUDGET = 64 << 20            # --dump-outputs: bytes on disk in all
+NPY_HEADER = 4096                 # room left for each .npy file's header (numpy writes 128 bytes for these shapes)
 
 
 def make_input(torch, pkg, device, n_channels, n_samples, seed):
@@ -476,6 +481,56 @@ def receive_chain(args, torch, pkg, device, local_rank, C=CHANNELS_PER_GPU, N=SA
     return res
 
 
+def dump_plan(world, n_channels, stride):
+    """Bit rows per rank that --dump-outputs writes: as many as fit DUMP_BUDGET beside every channel's count (float64) -- a row is
+    `stride` float32 plus its channel number (float64) -- at most DUMP_CHANNELS over all ranks, the same number on every rank."""
+    free = DUMP_BUDGET - 3 * NPY_HEADER - 8 * world * n_channels
+    rows = min(DUMP_CHANNELS, world * n_channels, max(0, free) // (4 * stride + 8)) // world
+    if rows < 1:
+        raise SystemExit("--dump-outputs: %d channel counts and one bit row of %d bits per rank do not fit %d MB"
+                         % (world * n_channels, stride, DUMP_BUDGET >> 20))
+    return rows
+
+
+def dump_channels(n_channels, rows):
+    """The channels of one rank whose bit rows --dump-outputs writes: all of them up to `rows`, else a sorted sample drawn with a
+    fixed seed, so that two runs with the same arguments dump the same rows."""
+    if n_channels <= rows:
+        return np.arange(n_channels, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_channels, rows, replace=False)).astype(np.int64)
+
+
+def write_dump(out_dir, rows, counts, channels):
+    """The files of --dump-outputs: n_bits.npy every channel's bit count (float64); bits.npy the bit rows (one byte per bit in the
+    call's output) of the channels in bits_channels.npy as float32, -1 past a row's count, where the call wrote nothing.  Returns
+    what the result line reports: the array names (DIR/<name>.npy) and the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    bits = rows.astype(np.float32)
+    bits[np.arange(bits.shape[1])[None, :] >= counts[channels][:, None]] = -1.0
+    out = {"bits": bits, "n_bits": counts.astype(np.float64), "bits_channels": channels.astype(np.float64)}
+    size = 0
+    for name, a in out.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        size += os.path.getsize(path)
+    return {"dir": out_dir, "arrays": sorted(out), "bytes": size, "rows": int(bits.shape[0])}
+
+
+def dump_outputs(pkg, out_dir, bits, nbits, rows, ch_lo=0, world=1, dist=None, device=None):
+    """--dump-outputs: what the timed step returned to its caller, bit rows [C][stride] and counts [C] of this rank's channels
+    [ch_lo, ch_lo + C), with `rows` (dump_plan) sampled rows per rank.  With N > 1 every rank's part is gathered (device: where the
+    collective's tensors live, None for gloo) and rank 0 writes ONE set for the whole bank in global channel numbers; the other ranks
+    return None."""
+    import torch
+    sel = dump_channels(bits.shape[0], rows)
+    parts = [bits[torch.as_tensor(sel, device=bits.device)], nbits, torch.as_tensor(sel + ch_lo)]
+    if world > 1:
+        parts = [pkg.shard.gather_channel_rows(dist, t.to(device or "cpu"), t.shape[0] * world, world, device=device) for t in parts]
+    if dist is not None and dist.get_rank() != 0:
+        return None
+    return write_dump(out_dir, *(t.cpu().numpy() for t in parts))
+
+
 def informational(leg, *a):
     """An informational leg of the default line (config 5, the receive chain) must not take the metric line down with it: a leg that
     fails -- its own known-answer check included -- is reported as {"error": ...} in its place (run alone, --config5 / --chain-only,
@@ -536,9 +591,16 @@ def main():
                          "N > 1 path on a one-GPU box (RCCL refuses several ranks on one device, so this is how its half is exercised there)")
     ap.add_argument("--no-time-major", action="store_true",
                     help="skip the informational leg that hands the same workload over time-major (iq[n][c], field time_major)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (bit rows of a fixed sample of channels, every "
+                         "channel's bit count) as DIR/<name>.npy, to compare two builds output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.config5 or args.chain_only):
+        raise SystemExit("--dump-outputs writes the headline workload's outputs; it does not combine with --config5 / --chain-only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -598,6 +660,7 @@ def main():
     assert ch_hi - ch_lo == C
     iq, seeds = make_input(torch, pkg, device, C, N, seed=20260000 + ch_lo)
     stride = pkg.binding.bits_stride(N)
+    dump_rows = dump_plan(world, C, stride) if args.dump_outputs else 0
     bits = torch.zeros((C, stride), dtype=torch.uint8, device=device)
     nbits = torch.zeros(C, dtype=torch.int32, device=device)
     dem = pkg.Demodulator(C, N, device=local_rank, flags=0)
@@ -630,6 +693,10 @@ def main():
     elapsed = time.perf_counter() - t0
     if dist is not None:
         elapsed = pkg.shard.max_over_ranks(dist, elapsed, device=device if args.backend == "nccl" else None)
+    dumped = None
+    if args.dump_outputs:          # the last timed step's outputs, before anything below runs the handle again
+        dumped = dump_outputs(pkg, args.dump_outputs, bits, nbits, dump_rows, ch_lo, world, dist,
+                              device if args.backend == "nccl" else None)
 
     # per-launch kernel durations of the timed region (HIP events on the launch stream)
     nh = min(args.steps, 64)
@@ -819,6 +886,8 @@ def main():
             out["value_functional"] = round(value, 3)
             out["functional_note"] = ("%d ranks shared %d GPU(s): a functional run of the N > 1 path, NOT an %d-GPU measurement"
                                       % (world, gpus_physical, world))
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if tmaj is not None:
             out["time_major"] = tmaj
         out.update(host)

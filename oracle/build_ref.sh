@@ -33,3 +33,22 @@ gcc -O2 -std=gnu11 -fPIC -shared -w -I"$SRC" -o "$HERE/_ref/libtetra_lmac_ref.so
     "$LM/tetra_scramb.c" "$LM/tetra_interleave.c" "$LM/tetra_conv_enc.c" "$LM/crc_simple.c" \
     "$LM/viterbi.c" "$LM/viterbi_cch.c" "$LM/osmo_conv.c"
 echo "built $HERE/_ref/libtetra_lmac_ref.so from $LM/{tetra_scramb,tetra_interleave,tetra_conv_enc,crc_simple,viterbi,viterbi_cch,osmo_conv}.c"
+# The reference's per-sample DSP objects (src/dsp/pi4dqpsk, fll, complex_fd, pi4dqpsk_costas, dqpsk_sym_extr, bit_unpacker), again
+# compiled where they lie, against OUR stand-in SDR++ core headers (tests/refshim/, see its README.md) and the test-side driver
+# tests/refshim/ref_driver.cpp: libref_shim.so with pi spelt as the double constant, libref_shim_fpi.so with the float macro
+# (-DREFSHIM_FLOAT_PI).  Loaded by tests/test_reference_shim.py and tests/test_sdrpp_tables.py.
+# -ffp-contract=off: the reference's expressions as written (an x86 build never fuses them);
+# -fno-access-control: ref_driver.cpp reads the objects' protected / private loop state (ref_get_state).
+DSP="$REF/src/dsp"
+SHIM="$HERE/../tests/refshim"
+shim() {
+    g++ -std=c++17 -O2 -ffp-contract=off -fno-access-control -fPIC -shared -w "$@" -I"$SHIM" -I"$REF/src" "$SHIM/ref_driver.cpp" \
+        "$DSP/pi4dqpsk.cpp" "$DSP/fll.cpp" "$DSP/complex_fd.cpp" "$DSP/pi4dqpsk_costas.cpp" "$DSP/dqpsk_sym_extr.cpp" "$DSP/bit_unpacker.cpp"
+}
+if [ -f "$DSP/pi4dqpsk.cpp" ]; then
+    shim -o "$HERE/_ref/libref_shim.so" & p0=$!
+    shim -DREFSHIM_FLOAT_PI -o "$HERE/_ref/libref_shim_fpi.so" & p1=$!
+    wait $p0
+    wait $p1
+    echo "built $HERE/_ref/libref_shim.so, libref_shim_fpi.so from $DSP/{pi4dqpsk,fll,complex_fd,pi4dqpsk_costas,dqpsk_sym_extr,bit_unpacker}.cpp"
+fi

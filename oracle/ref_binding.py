@@ -213,6 +213,24 @@ RCPC_PUNCT_2_3 = 0         # enum tetra_rcpc_puncturer, first entry (lower_mac/t
 _lmac = None
 
 
+SHIM_DIR = os.path.join(_HERE, "..", "tests", "refshim")
+
+
+def shim_path(float_pi=False):
+    """oracle/_ref/libref_shim.so (libref_shim_fpi.so with float_pi): the reference's src/dsp objects against the stand-in core headers
+    of tests/refshim (build_ref.sh).  Rebuilt when what it is compiled from (ref_driver.cpp, the dsp/ headers) is newer; None when it
+    is not built and the reference is not present to build it."""
+    path = os.path.join(_HERE, "_ref", "libref_shim_fpi.so" if float_pi else "libref_shim.so")
+    deps = [os.path.join(SHIM_DIR, "ref_driver.cpp")] + [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(SHIM_DIR, "dsp"))
+                                                         for f in fs]
+    if not os.path.exists(path) or any(os.path.getmtime(d) > os.path.getmtime(path) for d in deps):
+        try:
+            build()
+        except Exception:
+            pass
+    return path if os.path.exists(path) else None
+
+
 def lmac_available():
     if not os.path.exists(LMAC_LIB_PATH):
         try:

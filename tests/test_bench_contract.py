@@ -3,6 +3,8 @@ import json
 import os
 import shutil
 
+import pytest
+
 import bench
 
 
@@ -114,3 +116,47 @@ def test_hashed_channel_streams_are_the_same_on_cpu_and_in_torch():
     b = pkg.synth_gpu.hash_bits(torch, dev, seeds, 300).numpy()
     assert all(np.array_equal(b[c], pkg.synth.hash_bits(int(seeds[c]), 300)) for c in range(6))
     assert not np.array_equal(b[0], b[1])
+
+
+def test_dump_outputs_writes_the_callers_arrays_within_budget(pkg, tmp_path):
+    """--dump-outputs: the bit rows of a fixed channel sample (float32, -1 past each row's count), their channel numbers and every
+    channel's count (float64), the same sample on every run, and never more than 64 MB on disk: one rank at the headline size and at
+    twice the samples, eight ranks (one set for the whole bank, written by rank 0)."""
+    import numpy as np
+    import torch
+    C, stride = 1000, 704
+    g = torch.Generator().manual_seed(3)
+    bits = torch.randint(0, 2, (C, stride), dtype=torch.uint8, generator=g)
+    nbits = torch.randint(600, stride + 1, (C,), dtype=torch.int32, generator=g)
+    line = bench.dump_outputs(None, str(tmp_path / "d"), bits, nbits, bench.dump_plan(1, C, stride))
+    assert line["arrays"] == ["bits", "bits_channels", "n_bits"] and line["rows"] == bench.DUMP_CHANNELS
+    rows, sel, nb = (np.load(tmp_path / "d" / (n + ".npy")) for n in line["arrays"])
+    assert line["bytes"] == sum(os.path.getsize(tmp_path / "d" / (n + ".npy")) for n in line["arrays"])
+    assert rows.dtype == np.float32 and sel.dtype == np.float64 and nb.dtype == np.float64
+    assert np.array_equal(nb, nbits.numpy()) and rows.shape == (bench.DUMP_CHANNELS, stride)
+    assert np.array_equal(sel, bench.dump_channels(C, bench.DUMP_CHANNELS)) and np.array_equal(sel, np.unique(sel)) and sel.max() < C
+    for j, c in enumerate(sel.astype(np.int64)):
+        n = int(nbits[c])
+        assert np.array_equal(rows[j, :n], bits[c, :n].numpy()) and (rows[j, n:] == -1).all()
+    assert np.array_equal(bench.dump_channels(10, 256), np.arange(10))
+    # on-disk totals at full size: the headline workload, twice its samples, eight ranks (what rank 0 writes after the gather)
+    for world, samples in ((1, bench.SAMPLES), (1, 2 * bench.SAMPLES), (8, bench.SAMPLES), (8, 2 * bench.SAMPLES)):
+        C, stride = bench.CHANNELS_PER_GPU, pkg.binding.bits_stride(samples)
+        k = bench.dump_plan(world, C, stride)
+        assert 1 <= k and world * k <= bench.DUMP_CHANNELS
+        sel = np.concatenate([bench.dump_channels(C, k) + r * C for r in range(world)])
+        rows = np.ones((world * k, stride), np.uint8)
+        line = bench.write_dump(str(tmp_path / ("w%d_%d" % (world, samples))), rows, np.full(world * C, stride // 2), sel)
+        assert line["rows"] == world * k and line["bytes"] <= 64 << 20, (world, samples, line)
+    assert bench.dump_plan(1, bench.CHANNELS_PER_GPU, pkg.binding.bits_stride(2 * bench.SAMPLES)) < bench.DUMP_CHANNELS
+    with pytest.raises(SystemExit):
+        bench.dump_plan(1, 4096, 64 << 20)          # not one row fits
+
+
+def test_dump_outputs_flag_and_steps_are_checked():
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.abspath(bench.__file__))
+    for extra, msg in ((["--steps", "0"], "--steps must be >= 1"), (["--chain-only", "--dump-outputs", "x"], "--dump-outputs writes")):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr[-500:]

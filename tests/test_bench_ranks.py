@@ -53,29 +53,41 @@ def test_bench_gpus_2_runs_two_ranks(backend):
     assert abs(value - 2 * 4096 * 36000 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * value
 
 
-def test_bench_gpus_8_folded_onto_the_box(tmp_path):
+def test_bench_gpus_4_folded_onto_the_box(tmp_path):
     """the driver's SCALE run is `bench.py --gpus 8` on an 8-GPU node that no round has had.  Here the same
-    command starts EIGHT ranks (512 channels each so that eight handles, inputs and bit rows fit beside each other on one GPU),
-    folded onto the GPUs the box has: rendezvous, eight communicators' worth of barriers and the MAX / SUM reductions, eight
-    known-answer checks -- every rank's own channel range against its own transmitted bits -- and a line nobody can mistake for
-    an 8-GPU measurement."""
+    command starts FOUR ranks (512 channels each so that the handles, inputs and bit rows fit beside each other on one GPU), folded
+    onto the GPUs the box has: rendezvous, several ranks' worth of barriers and the MAX / SUM reductions, a known-answer check on
+    every rank -- its own channel range against its own transmitted bits -- and a line nobody can mistake for a 4-GPU measurement.
+    Four ranks, not eight: with this test's own process that keeps five processes at most with the GPU open at once."""
     import torch
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--channels", "512",
-           "--no-cpu-baseline"]
+    import numpy as np
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--channels", "512",
+           "--no-cpu-baseline", "--dump-outputs", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     d = _line(r)
     os.makedirs(OUT, exist_ok=True)
-    json.dump(d, open(os.path.join(OUT, "bench_gpus8_folded.json"), "w"))
+    json.dump(d, open(os.path.join(OUT, "bench_gpus4_folded.json"), "w"))
     ngpu = torch.cuda.device_count()
-    assert d["n_ranks"] == 8 and d["gpus_physical"] == ngpu and d["n_gpus"] == min(8, ngpu) and d["scaling"] == "weak"
-    assert d["functional_only"] == (ngpu < 8)
-    if ngpu < 8:
-        assert d["value"] is None and d["value_functional"] > 0 and "NOT an 8-GPU measurement" in d["functional_note"]
+    assert d["n_ranks"] == 4 and d["gpus_physical"] == ngpu and d["n_gpus"] == min(4, ngpu) and d["scaling"] == "weak"
+    assert d["functional_only"] == (ngpu < 4)
+    if ngpu < 4:
+        assert d["value"] is None and d["value_functional"] > 0 and "NOT an 4-GPU measurement" in d["functional_note"]
         assert d["dist_backend"] == "gloo" and "RCCL needs one GPU per rank" in d["dist_backend_note"]
     ck = d["check"]
-    assert ck["ranks_checked"] == 8 and ck["ranks_green"] == 8 and ck["channels_checked"] == 8 * 256          # bench.CHECK_CHANNELS of every rank
-    assert ck["bit_errors"] <= 1e-3 * ck["bits_compared_last_quarter"] and ck["bits_compared_last_quarter"] > 8 * 32 * 8000
+    assert ck["ranks_checked"] == 4 and ck["ranks_green"] == 4 and ck["channels_checked"] == 4 * 256          # bench.CHECK_CHANNELS of every rank
+    assert ck["bit_errors"] <= 1e-3 * ck["bits_compared_last_quarter"] and ck["bits_compared_last_quarter"] > 4 * 32 * 8000
     assert d["config"]["channels_per_gpu"] == 512
+    # --dump-outputs with N > 1: every rank's part gathered, ONE set for the whole bank (global channel numbers) under the names the
+    # line reports, within 64 MB
+    dd = d["dump_outputs"]
+    assert sorted(os.listdir(dump)) == [n + ".npy" for n in dd["arrays"]] == ["bits.npy", "bits_channels.npy", "n_bits.npy"]
+    assert dd["bytes"] == sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 << 20
+    rows, sel, nb = (np.load(dump / (n + ".npy")) for n in dd["arrays"])
+    assert nb.shape == (4 * 512,) and (np.abs(nb - 36000) < 360).all() and rows.shape[0] == dd["rows"] == 256
+    assert [int((sel // 512 == q).sum()) for q in range(4)] == [64] * 4 and np.array_equal(sel, np.unique(sel))
+    for j, c in enumerate(sel.astype(np.int64)):
+        assert (rows[j, : int(nb[c])] >= 0).all() and (rows[j, int(nb[c]):] == -1).all()
 
 
 def test_bench_rccl_half_of_the_rank_path_on_one_gpu():
@@ -132,3 +144,26 @@ def test_chain_leg_known_answer_at_full_size():
     assert total > 600000 and d["rows_per_kind"]["schf"] == ck["blocks"]["schf"]["rows"]
     assert 3.5 < d["two_streams_ms_per_second"] < d["one_stream_ms_per_second"] * 1.02 < 6.0        # sanity: not a timing claim
     assert set(d["stages_one_stream"]) == {"demodulator", "burst_sync", "frame_lists_sb1_decode_track", "other_kinds_decode_label"}
+
+
+def test_bench_dump_outputs_are_the_same_on_a_second_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments dump the same arrays (same inputs, same last timed step), and
+    what is dumped is the call's output -- the counts are those of two demodulated seconds at 36 ksps.  At twice the headline samples a
+    row is twice as long: fewer rows are sampled, the files stay within 64 MB."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--channels", "512",
+            "--samples", "72000", "--no-cpu-baseline", "--no-host-path", "--no-large-batch", "--no-config5", "--no-time-major", "--no-chain"]
+    got = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        r = subprocess.run(base + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        line = _line(r)
+        dd = line["dump_outputs"]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and dd["arrays"] == ["bits", "bits_channels", "n_bits"]
+        assert dd["bytes"] == sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20 and 128 < dd["rows"] < 256
+        got.append({n: np.load(d / (n + ".npy")) for n in dd["arrays"]})
+    for n in got[0]:
+        assert got[0][n].dtype == got[1][n].dtype and np.array_equal(got[0][n], got[1][n]), n
+    nb, rows = got[0]["n_bits"], got[0]["bits"]
+    assert nb.shape == (512,) and rows.shape[0] == got[0]["bits_channels"].shape[0] and (np.abs(nb - 72000) < 720).all()
+    assert set(np.unique(rows)) <= {-1.0, 0.0, 1.0} and 0.4 < (rows == 1).sum() / (rows >= 0).sum() < 0.6

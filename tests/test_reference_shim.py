@@ -1,6 +1,7 @@
 """The reference's OWN src/dsp/*.cpp, compiled where they lie against stand-in core headers, versus the oracle.
 
-Container only: needs /root/reference (absent on the GPU box -> the module is skipped there).  The reference's
+Needs oracle/_ref/libref_shim*.so, which build() compiles from the reference sources (oracle/build_ref.sh); skipped where neither
+is there.  The reference's
 PI4DQPSK / FLL / COMPLEX_FD / PI4DQPSK_COSTAS / DQPSKSymbolExtractor / BitUnpacker sources include SDR++ core headers
 and VOLK, which are NOT under /root/reference; tests/refshim/ holds our own restatement of those primitives
 (SURVEY.md Appendix A).  So this is EVIDENCE, NOT A PIN: it shows the reference's per-sample loop code, fed the
@@ -17,36 +18,22 @@ between the two oracle modes is exactly the documented recipe (polynomial sincos
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "refshim")
-REF = os.environ.get("TETRA_REFERENCE_DIR", "/root/reference")
-REF_DSP = os.path.join(REF, "src", "dsp")
-SOURCES = ["pi4dqpsk.cpp", "fll.cpp", "complex_fd.cpp", "pi4dqpsk_costas.cpp", "dqpsk_sym_extr.cpp", "bit_unpacker.cpp"]
+from oracle import ref_binding
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF_DSP, "pi4dqpsk.cpp")),
-                                reason="reference sources not present (container-only evidence test)")
+pytestmark = pytest.mark.skipif(ref_binding.shim_path() is None,
+                                reason="oracle/_ref/libref_shim.so not built and the reference sources not present")
 
 RMS_TOL = 3e-3
 MAX_TOL = 3e-2
 
 
 def load_reference_build():
-    out_dir = os.path.join(SHIM, "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libref_shim.so")
-    srcs = [os.path.join(SHIM, "ref_driver.cpp")] + [os.path.join(REF_DSP, s) for s in SOURCES]
-    deps = srcs + [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(SHIM, "dsp")) for f in fs]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        # -ffp-contract=off: the reference's expressions as written (an x86 build never fuses them)
-        # -fno-access-control: ref_driver.cpp reads the objects' protected / private loop state (ref_get_state)
-        subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-access-control", "-fPIC", "-shared", "-w", "-I", SHIM,
-                        "-I", os.path.join(REF, "src"), "-o", so] + srcs, check=True)
-    L = C.CDLL(so)
+    # built by oracle/build_ref.sh (flags and sources there)
+    L = C.CDLL(ref_binding.shim_path())
     L.ref_create.restype = C.c_void_p
     L.ref_create.argtypes = [C.c_double, C.c_double, C.c_int] + [C.c_double] * 7
     L.ref_destroy.argtypes = [C.c_void_p]
@@ -295,15 +282,7 @@ def test_exact_with_the_float_pi_header_variant(oracle, synth):
     interpolator taps differ), and the oracle's reference-float mode handed those tables -- read out of the reference's objects --
     reproduces every symbol float, bit and the loop state bit for bit: the per-sample transcription does not lean on the tables,
     and the tables are data."""
-    out_dir = os.path.join(SHIM, "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libref_shim_fpi.so")
-    srcs = [os.path.join(SHIM, "ref_driver.cpp")] + [os.path.join(REF_DSP, s) for s in SOURCES]
-    deps = srcs + [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(SHIM, "dsp")) for f in fs]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-access-control", "-fPIC", "-shared", "-w", "-DREFSHIM_FLOAT_PI",
-                        "-I", SHIM, "-I", os.path.join(REF, "src"), "-o", so] + srcs, check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(ref_binding.shim_path(float_pi=True))
     L.ref_create.restype = C.c_void_p
     L.ref_create.argtypes = [C.c_double, C.c_double, C.c_int] + [C.c_double] * 7
     L.ref_destroy.argtypes = [C.c_void_p]

@@ -16,6 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from oracle import ref_binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PK = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
 SHIM = os.path.join(ROOT, "tests", "refshim")
@@ -122,10 +124,7 @@ def test_float_pi_variant_changes_most_taps_and_no_bit_after_lock(pkg, oracle, s
           "channels settle on another one); %d bits differ before lock" % (n_rrc, n_bank, worst_rms, worst_max, other_quadrant, differing_before_lock))
 
 
-REF = os.environ.get("TETRA_REFERENCE_DIR", "/root/reference")
-
-
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "src", "dsp", "pi4dqpsk.cpp")), reason="reference sources not present (container-only)")
+@pytest.mark.skipif(ref_binding.shim_path() is None, reason="oracle/_ref/libref_shim.so not built and the reference sources not present")
 @pytest.mark.parametrize("float_pi", [False, True])
 def test_sdrpp_route_hands_over_what_the_reference_objects_design_for_themselves(pkg, tmp_path, float_pi):
     """The closure itself (container only): the REFERENCE's own objects, compiled where they lie against a header variant, design
@@ -135,16 +134,7 @@ def test_sdrpp_route_hands_over_what_the_reference_objects_design_for_themselves
     setSamplerate / setRRCParams / setRRCTapCount / setRRCBeta(int).  Together with test_handle_runs_the_included_headers_tables
     (GPU: handle tables == sdrpp_tables output) this says: in an SDR++ build the kernels run the tables the reference would."""
     import ctypes as C
-    out_dir = os.path.join(SHIM, "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libref_shim_fpi.so" if float_pi else "libref_shim_tables.so")
-    srcs = [os.path.join(SHIM, "ref_driver.cpp")] + [os.path.join(REF, "src", "dsp", f) for f in
-                                                     ("pi4dqpsk.cpp", "fll.cpp", "complex_fd.cpp", "pi4dqpsk_costas.cpp", "dqpsk_sym_extr.cpp", "bit_unpacker.cpp")]
-    deps = srcs + [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(SHIM, "dsp")) for f in fs]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-access-control", "-fPIC", "-shared", "-w", "-I", SHIM, "-I",
-                        os.path.join(REF, "src")] + (["-DREFSHIM_FLOAT_PI"] if float_pi else []) + ["-o", so] + srcs, check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(ref_binding.shim_path(float_pi))          # the reference's objects against the same header variant (oracle/build_ref.sh)
     L.ref_create.restype = C.c_void_p
     L.ref_create.argtypes = [C.c_double, C.c_double, C.c_int] + [C.c_double] * 7
     L.ref_destroy.argtypes = [C.c_void_p]
