@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/tetra_burst_scan.h"
+#include "hip_host.hpp"
 
 namespace {
 
@@ -242,51 +243,31 @@ int tetra_find_train_seq_batch(const uint8_t* bits, int n_channels, int bits_str
     if (!bits || !end_of_in || !type || !offset || n_channels < 1 || bits_stride < 4) return TETRA_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (device >= 0) {
-        if (device >= ndev || hipSetDevice(device) != hipSuccess) return TETRA_ERR_NO_DEVICE;
-    }
-    uint8_t* d_bits = nullptr;
-    int *d_end = nullptr, *d_t = nullptr, *d_o = nullptr;
+    if (device >= ndev) return TETRA_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    DevMem<uint8_t> d_bits;
+    DevMem<int> d_end, d_t, d_o;
     const size_t nb = (size_t)n_channels * (size_t)bits_stride;
-    int rc = TETRA_OK;
-    if (hipMalloc((void**)&d_bits, nb) != hipSuccess || hipMalloc((void**)&d_end, sizeof(int) * n_channels) != hipSuccess ||
-        hipMalloc((void**)&d_t, sizeof(int) * n_channels) != hipSuccess || hipMalloc((void**)&d_o, sizeof(int) * n_channels) != hipSuccess)
-        rc = TETRA_ERR_NOMEM;
-    if (rc == TETRA_OK && (hipMemcpy(d_bits, bits, nb, hipMemcpyHostToDevice) != hipSuccess ||
-                           hipMemcpy(d_end, end_of_in, sizeof(int) * n_channels, hipMemcpyHostToDevice) != hipSuccess))
-        rc = TETRA_ERR_HIP;
-    if (rc == TETRA_OK) rc = tetra_find_train_seq_batch_device(d_bits, n_channels, bits_stride, d_end, mask, d_t, d_o, nullptr);
-    if (rc == TETRA_OK && (hipStreamSynchronize(0) != hipSuccess ||
-                           hipMemcpy(type, d_t, sizeof(int) * n_channels, hipMemcpyDeviceToHost) != hipSuccess ||
-                           hipMemcpy(offset, d_o, sizeof(int) * n_channels, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = TETRA_ERR_HIP;
-    if (d_bits) (void)hipFree(d_bits);
-    if (d_end) (void)hipFree(d_end);
-    if (d_t) (void)hipFree(d_t);
-    if (d_o) (void)hipFree(d_o);
-    if (prev >= 0) (void)hipSetDevice(prev);
-    return rc;
+    if (d_bits.reserve(nb) != hipSuccess || d_end.reserve(sizeof(int) * n_channels) != hipSuccess ||
+        d_t.reserve(sizeof(int) * n_channels) != hipSuccess || d_o.reserve(sizeof(int) * n_channels) != hipSuccess)
+        return TETRA_ERR_NOMEM;
+    if (hipMemcpy(d_bits, bits, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_end, end_of_in, sizeof(int) * n_channels, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int rc = tetra_find_train_seq_batch_device(d_bits, n_channels, bits_stride, d_end, mask, d_t, d_o, nullptr);
+    if (rc != TETRA_OK) return rc;
+    if (hipStreamSynchronize(0) != hipSuccess || hipMemcpy(type, d_t, sizeof(int) * n_channels, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(offset, d_o, sizeof(int) * n_channels, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    return TETRA_OK;
 }
 
 struct tetra_ts_indicator {
     int C = 0, device = 0;
-    uint8_t* tail = nullptr;      // [C][44]
-    int* expire = nullptr;        // [C]
+    DevMem<uint8_t> tail;         // [C][44]
+    DevMem<int> expire;           // [C]
 };
-
-namespace {
-struct IndDeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit IndDeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev != prev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~IndDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-}  // namespace
 
 int tetra_ts_indicator_create(int n_channels, int device, tetra_ts_indicator_t** out) {
     if (!out) return TETRA_ERR_ARG;
@@ -296,34 +277,31 @@ int tetra_ts_indicator_create(int n_channels, int device, tetra_ts_indicator_t**
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
     if (device < 0 && hipGetDevice(&device) != hipSuccess) return TETRA_ERR_NO_DEVICE;
     if (device >= ndev) return TETRA_ERR_NO_DEVICE;
-    IndDeviceGuard g(device);
+    DeviceGuard g(device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     tetra_ts_indicator* h = new (std::nothrow) tetra_ts_indicator;
     if (!h) return TETRA_ERR_NOMEM;
     h->C = n_channels;
     h->device = device;
-    if (hipMalloc((void**)&h->tail, (size_t)n_channels * kIndTail) != hipSuccess ||
-        hipMalloc((void**)&h->expire, sizeof(int) * (size_t)n_channels) != hipSuccess) {
-        tetra_ts_indicator_destroy(h);
+    if (h->tail.reserve((size_t)n_channels * kIndTail) != hipSuccess || h->expire.reserve(sizeof(int) * (size_t)n_channels) != hipSuccess) {
+        delete h;
         return TETRA_ERR_NOMEM;
     }
     const int rc = tetra_ts_indicator_reset(h, -1);
-    if (rc != TETRA_OK) { tetra_ts_indicator_destroy(h); return rc; }
+    if (rc != TETRA_OK) { delete h; return rc; }
     *out = h;
     return TETRA_OK;
 }
 
 void tetra_ts_indicator_destroy(tetra_ts_indicator_t* h) {
     if (!h) return;
-    IndDeviceGuard g(h->device);
-    if (h->tail) (void)hipFree(h->tail);
-    if (h->expire) (void)hipFree(h->expire);
+    DeviceGuard g(h->device);
     delete h;
 }
 
 int tetra_ts_indicator_reset(tetra_ts_indicator_t* h, int channel) {
     if (!h || channel < -1 || channel >= h->C) return TETRA_ERR_ARG;
-    IndDeviceGuard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     const size_t first = channel < 0 ? 0 : (size_t)channel, count = channel < 0 ? (size_t)h->C : 1;
     if (hipMemset(h->tail + first * kIndTail, 0, count * kIndTail) != hipSuccess ||
@@ -336,7 +314,7 @@ int tetra_ts_indicator_process_device(tetra_ts_indicator_t* h, const uint8_t* d_
                                       uint8_t* d_found, int32_t* d_expire, void* hip_stream) {
     if (!h || !d_bits || !d_n_bits || !d_found || bits_stride < 4) return TETRA_ERR_ARG;
     if ((bits_stride & 3) || (reinterpret_cast<uintptr_t>(d_bits) & 3)) return TETRA_ERR_ALIGN;
-    IndDeviceGuard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipLaunchKernelGGL(k_ts_indicator, dim3(h->C), dim3(kThreads), 0, (hipStream_t)hip_stream, d_bits, bits_stride, d_n_bits,
                        h->tail, h->expire, d_found, d_expire);
@@ -347,28 +325,23 @@ int tetra_ts_indicator_process(tetra_ts_indicator_t* h, const uint8_t* bits, int
                                uint8_t* found, int32_t* expire) {
     if (!h || !bits || !n_bits || !found || bits_stride < 4) return TETRA_ERR_ARG;
     if (bits_stride & 3) return TETRA_ERR_ALIGN;
-    IndDeviceGuard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    uint8_t *d_bits = nullptr, *d_found = nullptr;
-    int *d_n = nullptr, *d_e = nullptr;
+    DevMem<uint8_t> d_bits, d_found;
+    DevMem<int> d_n, d_e;
     const size_t nb = (size_t)h->C * (size_t)bits_stride;
-    int rc = TETRA_OK;
-    if (hipMalloc((void**)&d_bits, nb) != hipSuccess || hipMalloc((void**)&d_n, sizeof(int) * h->C) != hipSuccess ||
-        hipMalloc((void**)&d_found, (size_t)h->C) != hipSuccess || hipMalloc((void**)&d_e, sizeof(int) * h->C) != hipSuccess)
-        rc = TETRA_ERR_NOMEM;
-    if (rc == TETRA_OK && (hipMemcpy(d_bits, bits, nb, hipMemcpyHostToDevice) != hipSuccess ||
-                           hipMemcpy(d_n, n_bits, sizeof(int) * h->C, hipMemcpyHostToDevice) != hipSuccess))
-        rc = TETRA_ERR_HIP;
-    if (rc == TETRA_OK) rc = tetra_ts_indicator_process_device(h, d_bits, bits_stride, d_n, d_found, d_e, nullptr);
-    if (rc == TETRA_OK && (hipStreamSynchronize(0) != hipSuccess ||
-                           hipMemcpy(found, d_found, (size_t)h->C, hipMemcpyDeviceToHost) != hipSuccess ||
-                           (expire && hipMemcpy(expire, d_e, sizeof(int) * h->C, hipMemcpyDeviceToHost) != hipSuccess)))
-        rc = TETRA_ERR_HIP;
-    if (d_bits) (void)hipFree(d_bits);
-    if (d_n) (void)hipFree(d_n);
-    if (d_found) (void)hipFree(d_found);
-    if (d_e) (void)hipFree(d_e);
-    return rc;
+    if (d_bits.reserve(nb) != hipSuccess || d_n.reserve(sizeof(int) * h->C) != hipSuccess || d_found.reserve((size_t)h->C) != hipSuccess ||
+        d_e.reserve(sizeof(int) * h->C) != hipSuccess)
+        return TETRA_ERR_NOMEM;
+    if (hipMemcpy(d_bits, bits, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_n, n_bits, sizeof(int) * h->C, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int rc = tetra_ts_indicator_process_device(h, d_bits, bits_stride, d_n, d_found, d_e, nullptr);
+    if (rc != TETRA_OK) return rc;
+    if (hipStreamSynchronize(0) != hipSuccess || hipMemcpy(found, d_found, (size_t)h->C, hipMemcpyDeviceToHost) != hipSuccess ||
+        (expire && hipMemcpy(expire, d_e, sizeof(int) * h->C, hipMemcpyDeviceToHost) != hipSuccess))
+        return TETRA_ERR_HIP;
+    return TETRA_OK;
 }
 
 }  // extern "C"

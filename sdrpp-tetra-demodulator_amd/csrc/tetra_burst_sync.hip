@@ -17,6 +17,7 @@
 #include "../../include/tetra_burst_sync.h"
 #include "bsync_core.hpp"
 #include "demux_core.hpp"
+#include "hip_host.hpp"
 
 namespace {
 
@@ -324,8 +325,8 @@ size_t lds_bytes(int max_bits, int max_frames) { return (size_t)stream_words(max
 
 struct tetra_bsync {
     int n_channels, max_bits, max_frames, device;
-    State* d_state;
-    uint8_t* d_carry;
+    DevMem<State> d_state;
+    DevMem<uint8_t> d_carry;
 };
 
 extern "C" {
@@ -335,13 +336,12 @@ int tetra_bsync_create(int n_channels, int max_bits, int device, tetra_bsync_t**
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
     if (device >= ndev) return TETRA_ERR_NO_DEVICE;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return TETRA_ERR_HIP;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_HIP;
     if (device < 0 && hipGetDevice(&device) != hipSuccess) return TETRA_ERR_HIP;
-    tetra_bsync* h = new tetra_bsync{ n_channels, max_bits, (kBuf + max_bits) / kTs + 2, device, nullptr, nullptr };
+    tetra_bsync* h = new tetra_bsync{ n_channels, max_bits, (kBuf + max_bits) / kTs + 2, device };
     if (lds_bytes(max_bits, h->max_frames) > 160 * 1024 - 64) { delete h; return TETRA_ERR_UNSUPPORTED; }
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_state), sizeof(State) * n_channels) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->d_carry), (size_t)kBuf * n_channels) != hipSuccess) {
-        (void)hipFree(h->d_state);
+    if (h->d_state.reserve(sizeof(State) * n_channels) != hipSuccess || h->d_carry.reserve((size_t)kBuf * n_channels) != hipSuccess) {
         delete h;
         return TETRA_ERR_NOMEM;
     }
@@ -351,7 +351,7 @@ int tetra_bsync_create(int n_channels, int max_bits, int device, tetra_bsync_t**
                             160 * 1024 - 64) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 64) != hipSuccess) {
-        tetra_bsync_destroy(h);
+        delete h;
         return TETRA_ERR_HIP;
     }
     *out = h;
@@ -360,15 +360,14 @@ int tetra_bsync_create(int n_channels, int max_bits, int device, tetra_bsync_t**
 
 int tetra_bsync_destroy(tetra_bsync_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    (void)hipFree(h->d_state);
-    (void)hipFree(h->d_carry);
     delete h;
     return TETRA_OK;
 }
 
 int tetra_bsync_reset(tetra_bsync_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    if (hipSetDevice(h->device) != hipSuccess) return TETRA_ERR_HIP;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_HIP;
     if (hipMemset(h->d_state, 0, sizeof(State) * h->n_channels) != hipSuccess ||
         hipMemset(h->d_carry, 0, (size_t)kBuf * h->n_channels) != hipSuccess)
         return TETRA_ERR_HIP;
@@ -410,42 +409,34 @@ int tetra_bsync_process(tetra_bsync_t* h, const uint8_t* bits, int bits_stride, 
                         int32_t* frame_type, uint32_t* frame_bitnum, int32_t* n_frames) {
     if (!h || !bits || !n_bits || !frames || !frame_type || !frame_bitnum || !n_frames) return TETRA_ERR_ARG;
     if (bits_stride < 4 || (bits_stride & 3)) return TETRA_ERR_ALIGN;
-    if (hipSetDevice(h->device) != hipSuccess) return TETRA_ERR_HIP;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_HIP;
     const int C = h->n_channels, F = h->max_frames;
-    uint8_t *d_bits = nullptr, *d_frames = nullptr;
-    int32_t *d_n = nullptr, *d_ft = nullptr, *d_nf = nullptr;
-    uint32_t* d_fb = nullptr;
-    int rc = TETRA_ERR_HIP;
-    do {
-        if (hipMalloc(reinterpret_cast<void**>(&d_bits), (size_t)C * bits_stride) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_frames), (size_t)C * F * TETRA_FRAME_STRIDE) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_n), sizeof(int32_t) * C) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_ft), sizeof(int32_t) * C * F) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_fb), sizeof(uint32_t) * C * F) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d_nf), sizeof(int32_t) * C) != hipSuccess) { rc = TETRA_ERR_NOMEM; break; }
-        if (hipMemcpy(d_bits, bits, (size_t)C * bits_stride, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_n, n_bits, sizeof(int32_t) * C, hipMemcpyHostToDevice) != hipSuccess) break;
-        const int krc = tetra_bsync_process_device(h, d_bits, bits_stride, d_n, d_frames, d_ft, d_fb, d_nf, nullptr);
-        if (krc != TETRA_OK) { rc = krc; break; }
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(frames, d_frames, (size_t)C * F * TETRA_FRAME_STRIDE, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(frame_type, d_ft, sizeof(int32_t) * C * F, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(frame_bitnum, d_fb, sizeof(uint32_t) * C * F, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(n_frames, d_nf, sizeof(int32_t) * C, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = TETRA_OK;
-    } while (false);
-    (void)hipFree(d_bits);
-    (void)hipFree(d_frames);
-    (void)hipFree(d_n);
-    (void)hipFree(d_ft);
-    (void)hipFree(d_fb);
-    (void)hipFree(d_nf);
-    return rc;
+    DevMem<uint8_t> d_bits, d_frames;
+    DevMem<int32_t> d_n, d_ft, d_nf;
+    DevMem<uint32_t> d_fb;
+    if (d_bits.reserve((size_t)C * bits_stride) != hipSuccess || d_frames.reserve((size_t)C * F * TETRA_FRAME_STRIDE) != hipSuccess ||
+        d_n.reserve(sizeof(int32_t) * C) != hipSuccess || d_ft.reserve(sizeof(int32_t) * C * F) != hipSuccess ||
+        d_fb.reserve(sizeof(uint32_t) * C * F) != hipSuccess || d_nf.reserve(sizeof(int32_t) * C) != hipSuccess)
+        return TETRA_ERR_NOMEM;
+    if (hipMemcpy(d_bits, bits, (size_t)C * bits_stride, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_n, n_bits, sizeof(int32_t) * C, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int rc = tetra_bsync_process_device(h, d_bits, bits_stride, d_n, d_frames, d_ft, d_fb, d_nf, nullptr);
+    if (rc != TETRA_OK) return rc;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(frames, d_frames, (size_t)C * F * TETRA_FRAME_STRIDE, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(frame_type, d_ft, sizeof(int32_t) * C * F, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(frame_bitnum, d_fb, sizeof(uint32_t) * C * F, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(n_frames, d_nf, sizeof(int32_t) * C, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    return TETRA_OK;
 }
 
 int tetra_bsync_get_state(tetra_bsync_t* h, int first, int count, tetra_bsync_state_t* out) {
     if (!h || !out || first < 0 || count < 0 || first + count > h->n_channels) return TETRA_ERR_ARG;
-    if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    DeviceGuard g(h->device);
+    if (!g.ok || hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
     static_assert(sizeof(State) == sizeof(tetra_bsync_state_t), "state layout");
     if (count && hipMemcpy(out, h->d_state + first, sizeof(State) * count, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;

@@ -18,10 +18,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/tetra_chan.h"
 #include "chan_fft_core.hpp"
+#include "hip_host.hpp"
 
 namespace {
 
@@ -329,32 +331,22 @@ struct tetra_chan {
     int device = 0, last_hip = 0;
     int M = 0, P = 0, D = 0, L = 0, N1 = 0, N2 = 0, max_in = 0;
     std::vector<float> proto;
-    float2* xbuf = nullptr;     // [L-1 + max_in]: [history | new samples] of the call in flight
-    float2* xalt = nullptr;     // same size: receives the next call's history (one copy, then the two swap roles)
-    float* d_h = nullptr;
-    float2 *d_w1 = nullptr, *d_w2 = nullptr, *d_wm = nullptr;
-    float *d_bc = nullptr, *d_ac = nullptr;   // matrix-pipe form: the two constant block-twiddle operands (k_channelise_mfma)
+    DevMem<float2> xbuf;        // [L-1 + max_in]: [history | new samples] of the call in flight
+    DevMem<float2> xalt;        // same size: receives the next call's history (one copy, then the two swap roles)
+    DevMem<float> d_h;
+    DevMem<float2> d_w1, d_w2, d_wm;
+    DevMem<float> d_bc, d_ac;   // matrix-pipe form: the two constant block-twiddle operands (k_channelise_mfma)
     bool mfma = false;
     bool fft = false;           // M = 800, D = 400: the mixed-radix FFT kernel (k_channelise_fft)
-    float2* d_tw = nullptr;     // its [25][32] inter-stage twiddles
-    float* d_ht = nullptr;      // and the prototype re-ordered for its fold [800][2][P]
+    DevMem<float2> d_tw;        // its [25][32] inter-stage twiddles
+    DevMem<float> d_ht;         // and the prototype re-ordered for its fold [800][2][P]
     int cus = 256;
-    float2* st_out = nullptr;   // host-path staging
-    size_t st_out_frames = 0;
+    DevMem<float2> st_out;      // host-path staging
     int phase = 0;              // samples consumed towards the next frame
     long long consumed = 0;     // absolute index of the next input sample
-    hipEvent_t ev[2] = { nullptr, nullptr };
+    Event ev[2];
     bool ev_valid = false;
 };
-
-#define CH_TRY(h, expr)                                   \
-    do {                                                  \
-        hipError_t e__ = (expr);                          \
-        if (e__ != hipSuccess) {                          \
-            (h)->last_hip = (int)e__;                     \
-            return TETRA_ERR_HIP;                         \
-        }                                                 \
-    } while (0)
 
 namespace {
 
@@ -399,13 +391,6 @@ bool factor(int M, int& n1, int& n2) {
     return true;
 }
 
-struct Guard {
-    int prev = -1;
-    bool ok;
-    explicit Guard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; ok = hipSetDevice(d) == hipSuccess; }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 int upload_twiddles(tetra_chan* h) {
     const double pi = 3.14159265358979323846;
     auto tw = [&](int n) {
@@ -414,10 +399,10 @@ int upload_twiddles(tetra_chan* h) {
         return w;
     };
     auto w1 = tw(h->N1), w2 = tw(h->N2), wm = tw(h->M);
-    CH_TRY(h, hipMemcpy(h->d_w1, w1.data(), sizeof(float2) * w1.size(), hipMemcpyHostToDevice));
-    CH_TRY(h, hipMemcpy(h->d_w2, w2.data(), sizeof(float2) * w2.size(), hipMemcpyHostToDevice));
-    CH_TRY(h, hipMemcpy(h->d_wm, wm.data(), sizeof(float2) * wm.size(), hipMemcpyHostToDevice));
-    CH_TRY(h, hipMemcpy(h->d_h, h->proto.data(), sizeof(float) * h->proto.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_w1, w1.data(), sizeof(float2) * w1.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_w2, w2.data(), sizeof(float2) * w2.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_wm, wm.data(), sizeof(float2) * wm.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_h, h->proto.data(), sizeof(float) * h->proto.size(), hipMemcpyHostToDevice));
     if (h->fft) {
         std::vector<float2> t((size_t)chanfft::kN1 * chanfft::kN2);
         for (int n1 = 0; n1 < chanfft::kN1; n1++)
@@ -425,10 +410,10 @@ int upload_twiddles(tetra_chan* h) {
                 const double a = -2.0 * pi * (double)((n1 * k2) % chanfft::kM) / chanfft::kM;
                 t[(size_t)n1 * chanfft::kN2 + k2] = make_float2((float)std::cos(a), (float)std::sin(a));
             }
-        CH_TRY(h, hipMemcpy(h->d_tw, t.data(), sizeof(float2) * t.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_tw, t.data(), sizeof(float2) * t.size(), hipMemcpyHostToDevice));
         std::vector<float> ht((size_t)2 * chanfft::kM * h->P);
         chanfft::fold_transpose_prototype(h->proto.data(), h->P, ht.data());
-        CH_TRY(h, hipMemcpy(h->d_ht, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_ht, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice));
     }
     if (h->mfma) {
         // stage 1: Bc[k][col], k = n1 | N1 + n1, col = k1 | 32 + k1:  re = Vr Wr - Vi Wi, im = Vr Wi + Vi Wr, W = W_N1^(n1 k1)
@@ -448,16 +433,10 @@ int upload_twiddles(tetra_chan* h) {
                 ac[(size_t)k2 * 64 + n2] = wr;            ac[(size_t)k2 * 64 + 32 + n2] = -wi;
                 ac[(size_t)(32 + k2) * 64 + n2] = wi;     ac[(size_t)(32 + k2) * 64 + 32 + n2] = wr;
             }
-        CH_TRY(h, hipMemcpy(h->d_bc, bc.data(), sizeof(float) * bc.size(), hipMemcpyHostToDevice));
-        CH_TRY(h, hipMemcpy(h->d_ac, ac.data(), sizeof(float) * ac.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_bc, bc.data(), sizeof(float) * bc.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_ac, ac.data(), sizeof(float) * ac.size(), hipMemcpyHostToDevice));
     }
     return TETRA_OK;
-}
-
-void free_all(tetra_chan* h) {
-    void* ptrs[] = { h->xbuf, h->xalt, h->d_h, h->d_w1, h->d_w2, h->d_wm, h->d_bc, h->d_ac, h->d_tw, h->d_ht, h->st_out };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
 }
 
 }  // namespace
@@ -509,34 +488,33 @@ int tetra_chan_create(const tetra_chan_config_t* cfg, tetra_chan_t** out) {
     h->mfma = !h->fft && n1 == kMN1 && n2 == kMN2 && p_ok && !(cfg->reserved & TETRA_CHAN_FLAG_VALU_DFT);
     if (cfg->prototype) h->proto.assign(cfg->prototype, cfg->prototype + h->L);
     else design_prototype(h->M, h->P, cfg->cutoff_rel, h->proto);
-    Guard g(dev);
+    DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     // (the FFT kernel reads the caller's samples in place: its handles keep only the L - 1 samples of delay line, twice)
     const size_t xelems = (size_t)h->L - 1 + (h->fft ? 0 : (size_t)h->max_in);
-    bool ok = hipMalloc((void**)&h->xbuf, sizeof(float2) * xelems) == hipSuccess &&
-              hipMalloc((void**)&h->xalt, sizeof(float2) * xelems) == hipSuccess &&
-              hipMalloc((void**)&h->d_h, sizeof(float) * h->L) == hipSuccess &&
-              hipMalloc((void**)&h->d_w1, sizeof(float2) * h->N1) == hipSuccess &&
-              hipMalloc((void**)&h->d_w2, sizeof(float2) * h->N2) == hipSuccess &&
-              hipMalloc((void**)&h->d_wm, sizeof(float2) * h->M) == hipSuccess &&
-              (!h->fft || (hipMalloc((void**)&h->d_tw, sizeof(float2) * chanfft::kN1 * chanfft::kN2) == hipSuccess &&
-                           hipMalloc((void**)&h->d_ht, sizeof(float) * 2 * chanfft::kM * h->P) == hipSuccess)) &&
-              (!h->mfma || (hipMalloc((void**)&h->d_bc, sizeof(float) * 4 * kMK1 * 64) == hipSuccess &&
-                            hipMalloc((void**)&h->d_ac, sizeof(float) * 64 * 64) == hipSuccess)) &&
-              hipEventCreate(&h->ev[0]) == hipSuccess && hipEventCreate(&h->ev[1]) == hipSuccess;
+    bool ok = h->xbuf.reserve(sizeof(float2) * xelems) == hipSuccess &&
+              h->xalt.reserve(sizeof(float2) * xelems) == hipSuccess &&
+              h->d_h.reserve(sizeof(float) * h->L) == hipSuccess &&
+              h->d_w1.reserve(sizeof(float2) * h->N1) == hipSuccess &&
+              h->d_w2.reserve(sizeof(float2) * h->N2) == hipSuccess &&
+              h->d_wm.reserve(sizeof(float2) * h->M) == hipSuccess &&
+              (!h->fft || (h->d_tw.reserve(sizeof(float2) * chanfft::kN1 * chanfft::kN2) == hipSuccess &&
+                           h->d_ht.reserve(sizeof(float) * 2 * chanfft::kM * h->P) == hipSuccess)) &&
+              (!h->mfma || (h->d_bc.reserve(sizeof(float) * 4 * kMK1 * 64) == hipSuccess &&
+                            h->d_ac.reserve(sizeof(float) * 64 * 64) == hipSuccess)) &&
+              hipEventCreate(h->ev[0].put()) == hipSuccess && hipEventCreate(h->ev[1].put()) == hipSuccess;
     if (ok && hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) h->cus = 256;
     int rc = ok ? upload_twiddles(h) : TETRA_ERR_NOMEM;
     if (rc == TETRA_OK && hipMemset(h->xbuf, 0, sizeof(float2) * ((size_t)h->L - 1)) != hipSuccess) rc = TETRA_ERR_HIP;
-    if (rc != TETRA_OK) { free_all(h); delete h; return rc; }
+    if (rc != TETRA_OK) { delete h; return rc; }
     *out = h;
     return TETRA_OK;
 }
 
 int tetra_chan_destroy(tetra_chan_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     (void)hipDeviceSynchronize();
-    free_all(h);
     delete h;
     return TETRA_OK;
 }
@@ -554,13 +532,13 @@ constexpr int kFmtBytes[3] = { 8, 4, 2 };
 int copy_samples(tetra_chan* h, int fmt, const void* d_x, size_t first, size_t n, float2* dst, hipStream_t s) {
     if (n == 0) return TETRA_OK;
     if (fmt == chanfft::kFmtC32) {
-        CH_TRY(h, hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
         return TETRA_OK;
     }
     const dim3 grid((unsigned)((n + 255) / 256));
     if (fmt == chanfft::kFmtCs16) hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs16>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
     else hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs8>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
-    CH_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipGetLastError());
     return TETRA_OK;
 }
 template <int FMT> void launch_fft(tetra_chan* h, const ChanFftParams& p, dim3 grid, hipStream_t s);
@@ -570,7 +548,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
     // samples are moved as whole units (the FFT kernel reads d_x in place with 8- / 4- / 2-byte loads; every kernel stores 8-byte units)
     if (((uintptr_t)d_x & (kFmtBytes[fmt] - 1)) || ((uintptr_t)d_out & 7)) return TETRA_ERR_ALIGN;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)hip_stream;
     const int frames = (h->phase + n_in) / h->D;
@@ -582,7 +560,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         const int rc = copy_samples(h, fmt, d_x, 0, (size_t)n_in, h->xbuf + hist, s);
         if (rc != TETRA_OK) return rc;
     }
-    CH_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
     if (frames > 0 && h->fft) {
         ChanFftParams p;
         p.x = d_x; p.hist = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_ht; p.tw = h->d_tw;
@@ -608,7 +586,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         if (fmt == chanfft::kFmtCs16) launch_fft<chanfft::kFmtCs16>(h, p, grid, s);
         else if (fmt == chanfft::kFmtCs8) launch_fft<chanfft::kFmtCs8>(h, p, grid, s);
         else launch_fft<chanfft::kFmtC32>(h, p, grid, s);
-        CH_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
     } else if (frames > 0 && h->mfma) {
         ChanMfmaParams p;
         p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h; p.bc = h->d_bc; p.ac = h->d_ac; p.wm = h->d_wm;
@@ -619,7 +597,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         if (h->P == 8) hipLaunchKernelGGL(k_channelise_mfma<8>, dim3(grid), dim3(kThreads), 0, s, p);
         else if (h->P == 6) hipLaunchKernelGGL(k_channelise_mfma<6>, dim3(grid), dim3(kThreads), 0, s, p);
         else hipLaunchKernelGGL(k_channelise_mfma<4>, dim3(grid), dim3(kThreads), 0, s, p);
-        CH_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
     } else if (frames > 0) {
         ChanParams p;
         p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h;
@@ -627,9 +605,9 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         p.M = h->M; p.P = h->P; p.D = h->D; p.N1 = h->N1; p.N2 = h->N2;
         p.ph0 = h->phase; p.abs0 = h->consumed;
         hipLaunchKernelGGL(k_channelise, dim3(frames), dim3(kThreads), sizeof(float2) * ((size_t)h->M + (size_t)h->N1 * (h->N2 + 1)), s, p);
-        CH_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
     }
-    CH_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
     h->ev_valid = true;
     // carry: the last L-1 samples of [history | new] become the next call's history -- ONE copy into the other buffer
     // (whatever n_in is; an in-place move would overlap for n_in < L-1), then the buffers swap roles.  Stream order keeps the
@@ -637,13 +615,13 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     if (n_in > 0 && h->fft) {
         // the same from the two places the samples live in: what is left of the old delay line, then the tail of the caller's buffer
         const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
-        if (keep) CH_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * keep, hipMemcpyDeviceToDevice, s));
+        if (keep) HIP_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * keep, hipMemcpyDeviceToDevice, s));
         const int rc = copy_samples(h, fmt, d_x, (size_t)n_in - from_x, from_x, h->xalt + keep, s);
         if (rc != TETRA_OK) return rc;
-        float2* t = h->xbuf; h->xbuf = h->xalt; h->xalt = t;
+        std::swap(h->xbuf, h->xalt);
     } else if (n_in > 0) {
-        CH_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
-        float2* t = h->xbuf; h->xbuf = h->xalt; h->xalt = t;
+        HIP_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
+        std::swap(h->xbuf, h->xalt);
     }
     h->phase = (h->phase + n_in) % h->D;
     h->consumed += n_in;
@@ -671,26 +649,18 @@ int tetra_chan_process_device_cs8(tetra_chan_t* h, const int8_t* d_x, int n_in, 
 int tetra_chan_process(tetra_chan_t* h, const float* x, int n_in, float* out, int* n_frames) {
     if (!h || (!x && n_in > 0) || !out || !n_frames) return TETRA_ERR_ARG;
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     const size_t frames = (size_t)((h->phase + n_in) / h->D);
-    if (frames > h->st_out_frames) {
-        if (h->st_out) (void)hipFree(h->st_out);
-        h->st_out = nullptr; h->st_out_frames = 0;
-        CH_TRY(h, hipMalloc((void**)&h->st_out, sizeof(float2) * frames * (size_t)h->M));
-        h->st_out_frames = frames;
-    }
-    struct Tmp {                      // freed on every return path
-        float2* p = nullptr;
-        ~Tmp() { if (p) (void)hipFree(p); }
-    } d_x, d_dummy;
+    HIP_TRY(h, h->st_out.reserve(sizeof(float2) * frames * (size_t)h->M));
+    DevMem<float2> d_x, d_dummy;      // freed on every return path
     if (n_in > 0) {
-        CH_TRY(h, hipMalloc((void**)&d_x.p, sizeof(float2) * (size_t)n_in));
-        CH_TRY(h, hipMemcpy(d_x.p, x, sizeof(float2) * (size_t)n_in, hipMemcpyHostToDevice));
+        HIP_TRY(h, d_x.reserve(sizeof(float2) * (size_t)n_in));
+        HIP_TRY(h, hipMemcpy(d_x, x, sizeof(float2) * (size_t)n_in, hipMemcpyHostToDevice));
     }
-    if (!h->st_out) CH_TRY(h, hipMalloc((void**)&d_dummy.p, sizeof(float2)));
-    int rc = tetra_chan_process_device(h, reinterpret_cast<const float*>(d_x.p), n_in,
-                                       reinterpret_cast<float*>(h->st_out ? h->st_out : d_dummy.p), n_frames, nullptr);
+    if (!h->st_out) HIP_TRY(h, d_dummy.reserve(sizeof(float2)));
+    int rc = tetra_chan_process_device(h, reinterpret_cast<const float*>(d_x.get()), n_in,
+                                       reinterpret_cast<float*>(h->st_out ? h->st_out.get() : d_dummy.get()), n_frames, nullptr);
     if (rc == TETRA_OK) {
         hipError_t e = hipStreamSynchronize(0);
         if (e == hipSuccess && frames) e = hipMemcpy(out, h->st_out, sizeof(float2) * frames * (size_t)h->M, hipMemcpyDeviceToHost);
@@ -701,10 +671,10 @@ int tetra_chan_process(tetra_chan_t* h, const float* x, int n_in, float* out, in
 
 int tetra_chan_reset(tetra_chan_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    CH_TRY(h, hipDeviceSynchronize());
-    CH_TRY(h, hipMemset(h->xbuf, 0, sizeof(float2) * ((size_t)h->L - 1)));
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemset(h->xbuf, 0, sizeof(float2) * ((size_t)h->L - 1)));
     h->phase = 0;
     h->consumed = 0;
     return TETRA_OK;
@@ -718,10 +688,10 @@ int tetra_chan_get_prototype(tetra_chan_t* h, float* proto) {
 
 int tetra_chan_last_kernel_ms(tetra_chan_t* h, float* ms) {
     if (!h || !ms || !h->ev_valid) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    CH_TRY(h, hipEventSynchronize(h->ev[1]));
-    CH_TRY(h, hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
+    HIP_TRY(h, hipEventSynchronize(h->ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
     return TETRA_OK;
 }
 

@@ -19,12 +19,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/tetra_demod.h"
 #include "constellation_core.hpp"
 #include "demod_core.hpp"
 #include "design.hpp"
+#include "hip_host.hpp"
 
 using namespace tdm;
 
@@ -215,96 +217,74 @@ struct tetra_demod {
     int C = 0;
     int max_samples = 0;
     // device memory
-    float *agc_g = nullptr, *fll_ph = nullptr, *fll_fr = nullptr;
-    float2* hist = nullptr;
-    float2* hist_far = nullptr;     // [C][48]: the delay-line samples before hist's 80 (the fused kernel's long rows and the generic kernel)
+    DevMem<float> agc_g, fll_ph, fll_fr;
+    DevMem<float2> hist;
+    DevMem<float2> hist_far;        // [C][48]: the delay-line samples before hist's 80 (the fused kernel's long rows and the generic kernel)
     bool far_valid = true;          // false once the fused kernel has run since hist_far was written: it then reads as zeros
-    float2 *g_xs = nullptr, *g_ys = nullptr;      // generic kernel's scratch: [C][128 + max_samples] FLL outputs, [C][7 + max_samples] RRC outputs
-    float *d_g_be_a = nullptr, *d_g_be_b = nullptr, *d_g_rrc = nullptr;   // un-padded tap tables for it, [kGenMaxTaps] each
-    float *mu = nullptr, *omega = nullptr, *cph = nullptr, *cfr = nullptr, *ph2 = nullptr;
-    int *offset = nullptr, *prev = nullptr;
+    DevMem<float2> g_xs, g_ys;      // generic kernel's scratch: [C][128 + max_samples] FLL outputs, [C][7 + max_samples] RRC outputs
+    DevMem<float> d_g_be_a, d_g_be_b, d_g_rrc;   // un-padded tap tables for it, [kGenMaxTaps] each
+    DevMem<float> mu, omega, cph, cfr, ph2;
+    DevMem<int> offset, prev;
     int n_wide = 0;             // channels [0, n_wide) run in 32-channel workgroups, [n_wide, C) in 16-channel ones ...
     bool small = false;         // ... or, when they are at most 4 per CU (or the flag forces it), in 4-channel ones
     bool force_small = false;   // TETRA_FLAG_SMALL_WORKGROUPS
     bool force_generic = false; // TETRA_FLAG_GENERIC_KERNEL
     bool force_shape = false;   // TETRA_FLAG_WIDE_WORKGROUPS / _NARROW_: the caller chose
     int cus = 256;
-    int* rrc_valid = nullptr;   // [C] delay-line samples the RRC may see (tetra_demod.h: tetra_demod_channel_state.rrc_valid)
-    float2* y = nullptr;        // TETRA_FLAG_KEEP_RRC_OUT: time-major RRC output scratch [(7 + max_samples)][C]
-    float2* ybuf = nullptr;     // COMPLEX_FD delay buffer [C][7]
-    int* d_overruns = nullptr;  // [1] channels cut off at their row capacity, counted by the kernels since create
+    DevMem<int> rrc_valid;      // [C] delay-line samples the RRC may see (tetra_demod.h: tetra_demod_channel_state.rrc_valid)
+    DevMem<float2> y;           // TETRA_FLAG_KEEP_RRC_OUT: time-major RRC output scratch [(7 + max_samples)][C]
+    DevMem<float2> ybuf;        // COMPLEX_FD delay buffer [C][7]
+    DevMem<int> d_overruns;     // [1] channels cut off at their row capacity, counted by the kernels since create
     long long overruns_seen = 0;   // ... and what the host entry points have already reported of it
     int* cut_flag = nullptr;    // set around an in-place call's launch: a cut-off channel also stores 1 here (mapped host memory)
     bool tn_disabled = false;   // the platform refused the mapped, coherent host blocks: short calls keep the copy-engine path
-    float* q_ring = nullptr;    // TETRA_FLAG_QUALITY: [C][4096] distance ring + per-channel state (k_quality)
-    int *q_ptr = nullptr, *q_disp = nullptr, *q_sync = nullptr;
-    float* q_err = nullptr;
-    float2* q_sym = nullptr;    // [C][q_sym_stride] symbols of the last launch when the caller did not ask for them
-    float2 *cd_blk = nullptr, *cd_part = nullptr;   // TETRA_FLAG_CONSTELLATION: [C][1024] last complete / partial block (k_constellation)
-    int *cd_fill = nullptr, *cd_blocks = nullptr;   // [C] symbols in the partial block, blocks completed
+    DevMem<float> q_ring;       // TETRA_FLAG_QUALITY: [C][4096] distance ring + per-channel state (k_quality)
+    DevMem<int> q_ptr, q_disp, q_sync;
+    DevMem<float> q_err;
+    DevMem<float2> q_sym;       // [C][q_sym_stride] symbols of the last launch when the caller did not ask for them
+    DevMem<float2> cd_blk, cd_part;   // TETRA_FLAG_CONSTELLATION: [C][1024] last complete / partial block (k_constellation)
+    DevMem<int> cd_fill, cd_blocks;   // [C] symbols in the partial block, blocks completed
     bool taps_sym() const { return q_ring || cd_blk; }      // a post-launch kernel reads the launch's symbols
     long long q_sym_stride = 0;
     bool user_rrc = false, user_be = false;   // caller-supplied FIR tables (cfg.rrc_taps / cfg.bandedge_taps)
     bool quirks = false;        // TETRA_FLAG_REFERENCE_QUIRKS
     bool keep_y = false;        // y scratch allocated
-    float* d_bank = nullptr;
-    float *d_be_re80 = nullptr, *d_be_im80 = nullptr, *d_rrc_ext = nullptr;   // band-edge taps zero-padded (old end) to 80, RRC zero-extended
+    DevMem<float> d_bank;
+    DevMem<float> d_be_re80, d_be_im80, d_rrc_ext;   // band-edge taps zero-padded (old end) to 80, RRC zero-extended
     // host-path staging
-    float* st_iq = nullptr;
-    uint8_t* st_bits = nullptr;
-    int* st_nbits = nullptr;
-    float* st_sym = nullptr;
-    size_t st_iq_bytes = 0, st_bits_bytes = 0, st_sym_bytes = 0;
+    DevMem<float> st_iq;
+    DevMem<uint8_t> st_bits;
+    DevMem<int> st_nbits;
+    DevMem<float> st_sym;
     // small synchronous calls (the single-channel drop-in's 180-sample chunks): page-locked host staging, one packed output
-    uint8_t *pk_dev = nullptr, *pk_host = nullptr, *pk_in = nullptr;
-    size_t pk_bytes = 0, pk_in_bytes = 0;
+    DevMem<uint8_t> pk_dev;
+    HostMem<uint8_t> pk_host, pk_in;
     // the smallest synchronous calls: page-locked, mapped, coherent blocks the kernels read / write in place (no copy engine)
-    uint8_t *tn_out = nullptr, *tn_in = nullptr, *tn_out_dev = nullptr, *tn_in_dev = nullptr;
+    HostMem<uint8_t> tn_out, tn_in;
+    uint8_t *tn_out_dev = nullptr, *tn_in_dev = nullptr;
     // ring of HIP-event pairs (before / after the call's launches), one slot per process call
     static constexpr int kEvSlots = 64;
-    hipEvent_t ev[kEvSlots][2] = {};
+    Event ev[kEvSlots][2];
     long long n_calls = 0;      // process calls that launched kernels
-    hipStream_t own_stream = nullptr;   // tetra_demod_process_resident: the handle's own (non-blocking) stream
-    long long* d_prof = nullptr;   // TETRA_DEMOD_PROFILE scratch
+    Stream own_stream;          // tetra_demod_process_resident: the handle's own (non-blocking) stream
+    DevMem<long long> d_prof;   // TETRA_DEMOD_PROFILE scratch
     int last_n = 0;
     // tetra_demod_process_async: three streams, time chunks double-buffered in HBM (see the function)
     struct Async {
         bool ready = false;
-        hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
-        hipEvent_t ev_in[2] = {}, ev_free[2] = {}, ev_done[2] = {}, ev_out[2] = {};
-        void* d_raw[2] = {};        // int16 input only: the chunk as it came
-        float* d_iq[2] = {};        // the chunk as complex float [C][chunk] (or [chunk][C])
-        uint8_t* d_cbits[2] = {};   // the chunk's bits [C][chunk_stride]
-        int* d_cnb[2] = {};
-        uint8_t* d_out[2] = {};     // a call's bits [C][bits_stride]; two calls may be in flight
-        int* d_onb[2] = {};
-        size_t raw_bytes = 0, iq_bytes = 0, cbits_bytes = 0, out_bytes = 0;
+        Stream s_in, s_k, s_out;
+        Event ev_in[2], ev_free[2], ev_done[2], ev_out[2];
+        DevMem<void> d_raw[2];      // int16 input only: the chunk as it came
+        DevMem<float> d_iq[2];      // the chunk as complex float [C][chunk] (or [chunk][C])
+        DevMem<uint8_t> d_cbits[2]; // the chunk's bits [C][chunk_stride]
+        DevMem<int> d_cnb[2];
+        DevMem<uint8_t> d_out[2];   // a call's bits [C][bits_stride]; two calls may be in flight
+        DevMem<int> d_onb[2];
         long long chunks = 0, calls = 0;
     } as;
 };
 
-#define HIP_TRY(h, expr)                                  \
-    do {                                                  \
-        hipError_t e__ = (expr);                          \
-        if (e__ != hipSuccess) {                          \
-            (h)->last_hip = (int)e__;                     \
-            return TETRA_ERR_HIP;                         \
-        }                                                 \
-    } while (0)
-
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 int upload_tables(tetra_demod* h) {
     HIP_TRY(h, hipMemcpy(h->d_bank, h->design.bank.data(), sizeof(float) * kInterpPhases * kInterpTaps,
@@ -408,37 +388,6 @@ int reset_range(tetra_demod* h, int first, int count, bool fresh) {
     return TETRA_OK;
 }
 
-void free_all(tetra_demod* h) {
-    void* gen[] = { h->hist_far, h->g_xs, h->g_ys, h->d_g_be_a, h->d_g_be_b, h->d_g_rrc };
-    for (void* p : gen)
-        if (p) (void)hipFree(p);
-    void* ptrs[] = { h->agc_g, h->fll_ph, h->fll_fr, h->hist, h->mu, h->omega, h->cph, h->cfr, h->ph2, h->offset,
-                     h->prev, h->rrc_valid, h->y, h->ybuf, h->q_ring, h->q_sym, h->q_ptr, h->q_disp, h->q_sync, h->q_err, h->cd_blk, h->cd_part, h->cd_fill, h->cd_blocks, h->d_overruns, h->d_bank, h->d_be_re80, h->d_be_im80,
-                     h->d_rrc_ext, h->st_iq, h->st_bits, h->st_nbits, h->st_sym, h->d_prof };
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto& slot : h->ev)
-        for (auto& e : slot)
-            if (e) (void)hipEventDestroy(e);
-    auto& a = h->as;
-    for (int i = 0; i < 2; i++) {
-        void* bufs[] = { a.d_raw[i], a.d_iq[i], a.d_cbits[i], a.d_cnb[i], a.d_out[i], a.d_onb[i] };
-        for (void* p : bufs)
-            if (p) (void)hipFree(p);
-        hipEvent_t evs[] = { a.ev_in[i], a.ev_free[i], a.ev_done[i], a.ev_out[i] };
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
-    }
-    if (h->pk_dev) (void)hipFree(h->pk_dev);
-    if (h->pk_host) (void)hipHostFree(h->pk_host);
-    if (h->pk_in) (void)hipHostFree(h->pk_in);
-    if (h->tn_out) (void)hipHostFree(h->tn_out);
-    if (h->tn_in) (void)hipHostFree(h->tn_in);
-    hipStream_t ss[] = { a.s_in, a.s_k, a.s_out, h->own_stream };
-    for (hipStream_t st : ss)
-        if (st) (void)hipStreamDestroy(st);
-}
-
 // Reads the kernels' overrun counter (the device must be idle for this handle's work) and tells whether it moved since the
 // last report: > 0 = channels newly cut off, 0 = none, < 0 = a TETRA_ERR_* status.
 int new_overruns(tetra_demod* h) {
@@ -447,11 +396,6 @@ int new_overruns(tetra_demod* h) {
     const long long fresh = (long long)total - h->overruns_seen;
     h->overruns_seen = total;
     return fresh > 0 ? (int)(fresh > 0x7fffffff ? 0x7fffffff : fresh) : 0;
-}
-
-template <class T> int dalloc(tetra_demod* h, T** p, size_t count) {
-    HIP_TRY(h, hipMalloc((void**)p, sizeof(T) * count));
-    return TETRA_OK;
 }
 
 // Can a launch of this handle take the generic kernel (kernel_generic.hpp)?  Its parameters, or TETRA_FLAG_GENERIC_KERNEL, decide.
@@ -464,15 +408,13 @@ bool generic_applies(const tetra_demod* h) { return generic_applies(h, h->design
 // point never allocates or synchronises), released by the setter that moves it away.  The device is idle when this runs.
 int sync_generic_scratch(tetra_demod* h, const host::Design& d) {
     if (!generic_applies(h, d)) {
-        if (h->g_xs) (void)hipFree(h->g_xs);
-        if (h->g_ys) (void)hipFree(h->g_ys);
-        h->g_xs = h->g_ys = nullptr;
+        h->g_xs.reset();
+        h->g_ys.reset();
         return TETRA_OK;
     }
     const size_t xs_stride = (size_t)kGenHist + (size_t)h->max_samples, ys_stride = (size_t)kYHist + (size_t)h->max_samples;
-    hipError_t e = hipSuccess;
-    if (!h->g_xs) e = hipMalloc((void**)&h->g_xs, sizeof(float2) * xs_stride * (size_t)h->C);
-    if (e == hipSuccess && !h->g_ys) e = hipMalloc((void**)&h->g_ys, sizeof(float2) * ys_stride * (size_t)h->C);
+    hipError_t e = h->g_xs.reserve(sizeof(float2) * xs_stride * (size_t)h->C);
+    if (e == hipSuccess) e = h->g_ys.reserve(sizeof(float2) * ys_stride * (size_t)h->C);
     if (e != hipSuccess) {
         h->last_hip = (int)e;
         (void)hipGetLastError();
@@ -618,14 +560,17 @@ int tetra_demod_create(const tetra_demod_config_t* cfg, tetra_demod_t** out) {
     }
     const size_t C = (size_t)h->C;
     int rc = TETRA_OK;
-    auto A = [&](int r) { if (rc == TETRA_OK) rc = r; };
-    A(dalloc(h, &h->agc_g, C)); A(dalloc(h, &h->fll_ph, C)); A(dalloc(h, &h->fll_fr, C));
-    A(dalloc(h, &h->hist, C * kHist));
-    A(dalloc(h, &h->hist_far, C * (size_t)(kGenHist - kHist)));
-    A(dalloc(h, &h->d_g_be_a, (size_t)kGenMaxTaps)); A(dalloc(h, &h->d_g_be_b, (size_t)kGenMaxTaps)); A(dalloc(h, &h->d_g_rrc, (size_t)kGenMaxTaps));
-    A(dalloc(h, &h->mu, C)); A(dalloc(h, &h->omega, C)); A(dalloc(h, &h->cph, C)); A(dalloc(h, &h->cfr, C));
-    A(dalloc(h, &h->ph2, C)); A(dalloc(h, &h->offset, C)); A(dalloc(h, &h->prev, C));
-    A(dalloc(h, &h->rrc_valid, C));
+    auto A = [&](auto& buf, size_t count) {      // every allocation is attempted; the first failure is the status
+        const hipError_t e = buf.reserve(sizeof(*buf.get()) * count);
+        if (e != hipSuccess) { h->last_hip = (int)e; if (rc == TETRA_OK) rc = TETRA_ERR_HIP; }
+    };
+    A(h->agc_g, C); A(h->fll_ph, C); A(h->fll_fr, C);
+    A(h->hist, C * kHist);
+    A(h->hist_far, C * (size_t)(kGenHist - kHist));
+    A(h->d_g_be_a, (size_t)kGenMaxTaps); A(h->d_g_be_b, (size_t)kGenMaxTaps); A(h->d_g_rrc, (size_t)kGenMaxTaps);
+    A(h->mu, C); A(h->omega, C); A(h->cph, C); A(h->cfr, C);
+    A(h->ph2, C); A(h->offset, C); A(h->prev, C);
+    A(h->rrc_valid, C);
     h->user_rrc = cfg->rrc_taps != nullptr;
     h->user_be = cfg->bandedge_taps != nullptr;
     h->quirks = (cfg->flags & TETRA_FLAG_REFERENCE_QUIRKS) != 0;
@@ -656,34 +601,33 @@ int tetra_demod_create(const tetra_demod_config_t* cfg, tetra_demod_t** out) {
         if (cfg->flags & TETRA_FLAG_SMALL_WORKGROUPS) { h->n_wide = 0; h->small = h->force_small = true; }
         h->force_generic = (cfg->flags & TETRA_FLAG_GENERIC_KERNEL) != 0;
     }
-    if (h->keep_y) A(dalloc(h, &h->y, C * ((size_t)h->max_samples + kYHist)));
-    A(dalloc(h, &h->ybuf, C * kYHist));
+    if (h->keep_y) A(h->y, C * ((size_t)h->max_samples + kYHist));
+    A(h->ybuf, C * kYHist);
     if (cfg->flags & TETRA_FLAG_QUALITY) {
-        A(dalloc(h, &h->q_ring, C * 4096)); A(dalloc(h, &h->q_ptr, C));
-        A(dalloc(h, &h->q_disp, C)); A(dalloc(h, &h->q_sync, C)); A(dalloc(h, &h->q_err, C));
+        A(h->q_ring, C * 4096); A(h->q_ptr, C);
+        A(h->q_disp, C); A(h->q_sync, C); A(h->q_err, C);
     }
     if (cfg->flags & TETRA_FLAG_CONSTELLATION) {
-        A(dalloc(h, &h->cd_blk, C * (size_t)kCdSyms)); A(dalloc(h, &h->cd_part, C * (size_t)kCdSyms));
-        A(dalloc(h, &h->cd_fill, C)); A(dalloc(h, &h->cd_blocks, C));
+        A(h->cd_blk, C * (size_t)kCdSyms); A(h->cd_part, C * (size_t)kCdSyms);
+        A(h->cd_fill, C); A(h->cd_blocks, C);
     }
     if (cfg->flags & (TETRA_FLAG_QUALITY | TETRA_FLAG_CONSTELLATION)) {
         h->q_sym_stride = stride_for(h->design, h->max_samples) / 2;
-        A(dalloc(h, &h->q_sym, C * (size_t)h->q_sym_stride));
+        A(h->q_sym, C * (size_t)h->q_sym_stride);
     }
-    A(dalloc(h, &h->d_overruns, (size_t)1));
-    A(dalloc(h, &h->d_be_re80, (size_t)kBePadLong)); A(dalloc(h, &h->d_be_im80, (size_t)kBePadLong));   // (sized for the long rows' tables)
-    A(dalloc(h, &h->d_rrc_ext, (size_t)kRrcExtLong));
-    A(dalloc(h, &h->d_bank, (size_t)kInterpPhases * kInterpTaps));
+    A(h->d_overruns, (size_t)1);
+    A(h->d_be_re80, (size_t)kBePadLong); A(h->d_be_im80, (size_t)kBePadLong);   // (sized for the long rows' tables)
+    A(h->d_rrc_ext, (size_t)kRrcExtLong);
+    A(h->d_bank, (size_t)kInterpPhases * kInterpTaps);
     if (rc == TETRA_OK && hipMemset(h->d_overruns, 0, sizeof(int)) != hipSuccess) rc = TETRA_ERR_HIP;
     for (auto& slot : h->ev)
         for (auto& e : slot)
-            if (rc == TETRA_OK && hipEventCreate(&e) != hipSuccess) rc = TETRA_ERR_HIP;
+            if (rc == TETRA_OK && hipEventCreate(e.put()) != hipSuccess) rc = TETRA_ERR_HIP;
     if (rc == TETRA_OK) rc = upload_tables(h);
     if (rc == TETRA_OK) rc = reset_range(h, 0, h->C, true);
     if (rc == TETRA_OK) rc = sync_generic_scratch(h);
     if (rc != TETRA_OK) {
         int st = (h->last_hip == (int)hipErrorOutOfMemory) ? TETRA_ERR_NOMEM : rc;
-        free_all(h);
         delete h;
         return st;
     }
@@ -695,7 +639,6 @@ int tetra_demod_destroy(tetra_demod_t* h) {
     if (!h) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     (void)hipDeviceSynchronize();
-    free_all(h);
     delete h;
     return TETRA_OK;
 }
@@ -715,7 +658,7 @@ int tetra_demod_process_device(tetra_demod_t* h, const float* d_iq, int n_sample
         HIP_TRY(h, hipMemsetAsync(d_n_bits, 0, sizeof(int32_t) * (size_t)h->C, s));
         return TETRA_OK;
     }
-    hipEvent_t* ev = h->ev[h->n_calls % tetra_demod::kEvSlots];
+    const Event* ev = h->ev[h->n_calls % tetra_demod::kEvSlots];
     const bool long_rows = host::needs_long(h->design) && !h->force_generic;
     if (generic_applies(h)) {
         // timing loops slower than 0.07 samples per symbol (and, with TETRA_FLAG_GENERIC_KERNEL, those below 0.27 and filters of more than 72 taps): one
@@ -802,7 +745,7 @@ int tetra_demod_process_device(tetra_demod_t* h, const float* d_iq, int n_sample
         const char* prof_path = std::getenv("TETRA_DEMOD_PROFILE");
         if (prof_path && n_wide == 0 && !rest_small && !long_rows) {      // (the instrumented instantiation exists for the regular rows only)
             const size_t nwg = (size_t)gf.x;
-            if (!h->d_prof) HIP_TRY(h, hipMalloc((void**)&h->d_prof, sizeof(long long) * 8 * nwg));
+            if (!h->d_prof) HIP_TRY(h, h->d_prof.reserve(sizeof(long long) * 8 * nwg));
             HIP_TRY(h, hipMemsetAsync(h->d_prof, 0, sizeof(long long) * 8 * nwg, s));
             pf.prof = h->d_prof;
             profiling = true;
@@ -893,7 +836,7 @@ int tetra_demod_process_resident(tetra_demod_t* h, const float* d_iq, int n_samp
         HIP_TRY(h, hipStreamSynchronize(h->as.s_k));
         HIP_TRY(h, hipStreamSynchronize(h->as.s_out));
     }
-    if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
     const int rc = tetra_demod_process_device(h, d_iq, n_samples, d_bits, bits_stride, d_n_bits, d_sym, h->own_stream);
     if (rc != TETRA_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
@@ -941,17 +884,18 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         // that is cut off additionally leaves a plain store in the host block, and only then is the counter read back.
         // A platform that refuses mapped + coherent host memory (or its device pointer) loses nothing but this shortcut: the
         // blocks are only kept once BOTH calls succeeded, otherwise the path is switched off and the call continues below.
-        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        auto mapped_block = [&](uint8_t** host_p, uint8_t** dev_p) {
-            if (*host_p) return true;
-            uint8_t *hp = nullptr, *dp = nullptr;
-            if (hipHostMalloc((void**)&hp, kSmallCall, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if (hipHostGetDevicePointer((void**)&dp, hp, 0) != hipSuccess || !dp) { (void)hipGetLastError(); (void)hipHostFree(hp); return false; }
+        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
+        auto mapped_block = [&](HostMem<uint8_t>& host_p, uint8_t** dev_p) {
+            if (host_p) return true;
+            HostMem<uint8_t> hp;
+            uint8_t* dp = nullptr;
+            if (hp.reserve(kSmallCall, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return false; }
+            if (hipHostGetDevicePointer((void**)&dp, hp, 0) != hipSuccess || !dp) { (void)hipGetLastError(); return false; }
             std::memset(hp, 0, kSmallCall);
-            *host_p = hp; *dev_p = dp;
+            host_p = std::move(hp); *dev_p = dp;
             return true;
         };
-        if (!mapped_block(&h->tn_out, &h->tn_out_dev) || !mapped_block(&h->tn_in, &h->tn_in_dev)) h->tn_disabled = true;
+        if (!mapped_block(h->tn_out, &h->tn_out_dev) || !mapped_block(h->tn_in, &h->tn_in_dev)) h->tn_disabled = true;
     }
     if (n_samples > 0 && n_samples <= kTiny && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall && !h->tn_disabled) {
         std::memcpy(h->tn_in, iq, iq_bytes);
@@ -973,28 +917,14 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         return cut < 0 ? cut : TETRA_ERR_OVERRUN;
     }
     if (n_samples > 0 && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall) {
-        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        if (pack_bytes > h->pk_bytes) {
-            if (h->pk_dev) (void)hipFree(h->pk_dev);
-            if (h->pk_host) (void)hipHostFree(h->pk_host);
-            h->pk_dev = h->pk_host = nullptr; h->pk_bytes = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->pk_dev, kSmallCall));
+        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
+        if (!h->pk_host) {      // once, both at kSmallCall; the packed output starts zero-filled
+            HIP_TRY(h, h->pk_dev.reserve(kSmallCall));
             HIP_TRY(h, hipMemset(h->pk_dev, 0, kSmallCall));
-            HIP_TRY(h, hipHostMalloc((void**)&h->pk_host, kSmallCall, hipHostMallocDefault));
-            h->pk_bytes = kSmallCall;
+            HIP_TRY(h, h->pk_host.reserve(kSmallCall));
         }
-        if (iq_bytes > h->pk_in_bytes) {
-            if (h->pk_in) (void)hipHostFree(h->pk_in);
-            h->pk_in = nullptr; h->pk_in_bytes = 0;
-            HIP_TRY(h, hipHostMalloc((void**)&h->pk_in, kSmallCall, hipHostMallocDefault));
-            h->pk_in_bytes = kSmallCall;
-        }
-        if (iq_bytes > h->st_iq_bytes) {
-            if (h->st_iq) (void)hipFree(h->st_iq);
-            h->st_iq = nullptr; h->st_iq_bytes = 0;
-            HIP_TRY(h, hipMalloc((void**)&h->st_iq, iq_bytes));
-            h->st_iq_bytes = iq_bytes;
-        }
+        HIP_TRY(h, h->pk_in.reserve(kSmallCall));
+        HIP_TRY(h, h->st_iq.reserve(iq_bytes));
         std::memcpy(h->pk_in, iq, iq_bytes);
         HIP_TRY(h, hipMemcpyAsync(h->st_iq, h->pk_in, iq_bytes, hipMemcpyHostToDevice, h->own_stream));
         uint8_t* d_nb = h->pk_dev;
@@ -1015,32 +945,21 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         h->overruns_seen = total;
         return fresh > 0 ? TETRA_ERR_OVERRUN : TETRA_OK;
     }
-    if (iq_bytes > h->st_iq_bytes) {
-        if (h->st_iq) (void)hipFree(h->st_iq);
-        h->st_iq = nullptr; h->st_iq_bytes = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->st_iq, iq_bytes));
-        h->st_iq_bytes = iq_bytes;
+    HIP_TRY(h, h->st_iq.reserve(iq_bytes));
+    if (bits_bytes > h->st_bits.bytes()) {      // once per size: the kernels define bits[c][0 .. n_bits[c]) per call, the rest stays as it is
+        HIP_TRY(h, h->st_bits.reserve(bits_bytes));
+        const hipError_t e = hipMemset(h->st_bits, 0, bits_bytes);
+        if (e != hipSuccess) h->st_bits.reset();      // (kept only zero-filled)
+        HIP_TRY(h, e);
     }
-    if (bits_bytes > h->st_bits_bytes) {
-        if (h->st_bits) (void)hipFree(h->st_bits);
-        h->st_bits = nullptr; h->st_bits_bytes = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->st_bits, bits_bytes));
-        HIP_TRY(h, hipMemset(h->st_bits, 0, bits_bytes));      // once: the kernels define bits[c][0 .. n_bits[c]) per call, the rest stays as it is
-        h->st_bits_bytes = bits_bytes;
-    }
-    if (!h->st_nbits) HIP_TRY(h, hipMalloc((void**)&h->st_nbits, sizeof(int) * C));
-    if (sym_bytes > h->st_sym_bytes) {
-        if (h->st_sym) (void)hipFree(h->st_sym);
-        h->st_sym = nullptr; h->st_sym_bytes = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->st_sym, sym_bytes));
-        h->st_sym_bytes = sym_bytes;
-    }
+    HIP_TRY(h, h->st_nbits.reserve(sizeof(int) * C));
+    HIP_TRY(h, h->st_sym.reserve(sym_bytes));
     if (iq_bytes) HIP_TRY(h, hipMemcpy(h->st_iq, iq, iq_bytes, hipMemcpyHostToDevice));
 #ifdef TETRA_DEMOD_DEBUG
     HIP_TRY(h, hipMemset(h->st_bits, 0, bits_bytes));      // release builds: only bits[c][0 .. n_bits[c]) are defined
 #endif
-    int rc = tetra_demod_process_device(h, h->st_iq ? h->st_iq : reinterpret_cast<const float*>(h->agc_g), n_samples,
-                                        h->st_bits, bits_stride, h->st_nbits, sym ? h->st_sym : nullptr, nullptr);
+    int rc = tetra_demod_process_device(h, h->st_iq ? h->st_iq : h->agc_g, n_samples, h->st_bits, bits_stride, h->st_nbits,
+                                        sym ? h->st_sym.get() : nullptr, nullptr);
     if (rc != TETRA_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(0));
     HIP_TRY(h, hipMemcpy(bits, h->st_bits, bits_bytes, hipMemcpyDeviceToHost));
@@ -1059,14 +978,6 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
 // Two calls may be in flight (two output slots), so call j+1's input copy overlaps call j's output copy.
 // ------------------------------------------------------------------------------------------------
 namespace {
-int grow(tetra_demod* h, void** p, size_t* have, size_t want) {
-    if (want <= *have && *p) return TETRA_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    HIP_TRY(h, hipMalloc(p, want));
-    return TETRA_OK;
-}
-
 int async_chunk_len(int n_samples) {
     int k = n_samples / 4096;
     k = k < 1 ? 1 : (k > 8 ? 8 : k);
@@ -1085,28 +996,22 @@ int async_enqueue(tetra_demod* h, const void* iq, int iq_format, int n_samples, 
     const size_t in_elem = iq_format == TETRA_IQ_CS16 ? sizeof(short) * 2 : iq_format == TETRA_IQ_CS8 ? 2 : sizeof(float) * 2;
     const size_t want_iq = sizeof(float) * 2 * C * (size_t)chunk, want_raw = iq_format != TETRA_IQ_CF32 ? in_elem * C * (size_t)chunk : 0;
     const size_t want_cbits = C * (size_t)cstride, want_out = C * (size_t)bits_stride;
-    if (want_iq > a.iq_bytes || want_raw > a.raw_bytes || want_cbits > a.cbits_bytes || want_out > a.out_bytes) {
+    auto fits = [&](int i) {
+        return a.d_iq[i].bytes() >= want_iq && a.d_raw[i].bytes() >= want_raw && a.d_cbits[i].bytes() >= want_cbits && a.d_out[i].bytes() >= want_out;
+    };
+    if (!fits(0) || !fits(1)) {
         HIP_TRY(h, hipDeviceSynchronize());          // buffers may be in use by calls still in flight
         for (int i = 0; i < 2; i++) {
-            int rc = TETRA_OK;
-            size_t t;
-            t = a.iq_bytes; rc = grow(h, (void**)&a.d_iq[i], &t, want_iq);
-            if (rc == TETRA_OK && want_raw) { t = a.raw_bytes; rc = grow(h, &a.d_raw[i], &t, want_raw); }
-            if (rc == TETRA_OK) { t = a.cbits_bytes; rc = grow(h, (void**)&a.d_cbits[i], &t, want_cbits); }
-            if (rc == TETRA_OK) { t = a.out_bytes; rc = grow(h, (void**)&a.d_out[i], &t, want_out); }
-            if (rc == TETRA_OK && want_out > a.out_bytes) {      // once; a call defines bits[c][0 .. n_bits[c])
+            HIP_TRY(h, a.d_iq[i].reserve(want_iq));
+            HIP_TRY(h, a.d_raw[i].reserve(want_raw));
+            HIP_TRY(h, a.d_cbits[i].reserve(want_cbits));
+            if (want_out > a.d_out[i].bytes()) {     // once per size; a call defines bits[c][0 .. n_bits[c])
+                HIP_TRY(h, a.d_out[i].reserve(want_out));
                 const hipError_t e = hipMemset(a.d_out[i], 0, want_out);
-                if (e != hipSuccess) { h->last_hip = (int)e; rc = TETRA_ERR_HIP; }
-            }
-            if (rc != TETRA_OK) {      // a buffer may be gone: forget every size, the next call allocates all of them again
-                a.iq_bytes = a.raw_bytes = a.cbits_bytes = a.out_bytes = 0;
-                return rc;
+                if (e != hipSuccess) a.d_out[i].reset();      // (kept only zero-filled)
+                HIP_TRY(h, e);
             }
         }
-        a.iq_bytes = a.iq_bytes > want_iq ? a.iq_bytes : want_iq;
-        if (want_raw) a.raw_bytes = a.raw_bytes > want_raw ? a.raw_bytes : want_raw;
-        a.cbits_bytes = a.cbits_bytes > want_cbits ? a.cbits_bytes : want_cbits;
-        a.out_bytes = a.out_bytes > want_out ? a.out_bytes : want_out;
     }
     const int os = (int)(a.calls & 1);               // output slot of this call
     if (a.calls >= 2) HIP_TRY(h, hipStreamWaitEvent(a.s_k, a.ev_out[os], 0));     // its previous user's D2H is done
@@ -1117,7 +1022,7 @@ int async_enqueue(tetra_demod* h, const void* iq, int iq_format, int n_samples, 
         const int len = n_samples - pos < chunk ? n_samples - pos : chunk;
         const int sl = (int)(a.chunks & 1);
         if (a.chunks >= 2) HIP_TRY(h, hipStreamWaitEvent(a.s_in, a.ev_free[sl], 0));
-        void* dst = iq_format != TETRA_IQ_CF32 ? a.d_raw[sl] : (void*)a.d_iq[sl];
+        void* dst = iq_format != TETRA_IQ_CF32 ? a.d_raw[sl].get() : (void*)a.d_iq[sl].get();
         if (time_major) {      // iq[n][c]: a time chunk is contiguous
             HIP_TRY(h, hipMemcpyAsync(dst, src + in_elem * C * (size_t)pos, in_elem * C * (size_t)len, hipMemcpyHostToDevice, a.s_in));
         } else {               // iq[c][n]: one row piece per channel, packed to [C][len] on the device
@@ -1128,13 +1033,13 @@ int async_enqueue(tetra_demod* h, const void* iq, int iq_format, int n_samples, 
         HIP_TRY(h, hipStreamWaitEvent(a.s_k, a.ev_in[sl], 0));
         if (iq_format == TETRA_IQ_CS16) {
             const long long n = (long long)C * len;
-            hipLaunchKernelGGL(k_cs16_to_cf32, dim3(2048), dim3(256), 0, a.s_k, static_cast<const short2*>(a.d_raw[sl]),
-                               reinterpret_cast<float2*>(a.d_iq[sl]), n);
+            hipLaunchKernelGGL(k_cs16_to_cf32, dim3(2048), dim3(256), 0, a.s_k, static_cast<const short2*>(a.d_raw[sl].get()),
+                               reinterpret_cast<float2*>(a.d_iq[sl].get()), n);
             HIP_TRY(h, hipGetLastError());
         } else if (iq_format == TETRA_IQ_CS8) {
             const long long n = (long long)C * len;
-            hipLaunchKernelGGL(k_cs8_to_cf32, dim3(2048), dim3(256), 0, a.s_k, static_cast<const char2*>(a.d_raw[sl]),
-                               reinterpret_cast<float2*>(a.d_iq[sl]), n);
+            hipLaunchKernelGGL(k_cs8_to_cf32, dim3(2048), dim3(256), 0, a.s_k, static_cast<const char2*>(a.d_raw[sl].get()),
+                               reinterpret_cast<float2*>(a.d_iq[sl].get()), n);
             HIP_TRY(h, hipGetLastError());
         }
         const int rc = tetra_demod_process_device(h, a.d_iq[sl], len, a.d_cbits[sl], cstride, a.d_cnb[sl], nullptr, a.s_k);
@@ -1173,16 +1078,13 @@ int tetra_demod_process_async(tetra_demod_t* h, const void* iq, int iq_format, i
     if (!a.ready) {
         // every resource is created only where it is still missing, so a call after a failed set-up neither leaks nor
         // re-creates what already exists
-        if (!a.s_in) HIP_TRY(h, hipStreamCreateWithFlags(&a.s_in, hipStreamNonBlocking));
-        if (!a.s_k) HIP_TRY(h, hipStreamCreateWithFlags(&a.s_k, hipStreamNonBlocking));
-        if (!a.s_out) HIP_TRY(h, hipStreamCreateWithFlags(&a.s_out, hipStreamNonBlocking));
+        for (Stream* st : { &a.s_in, &a.s_k, &a.s_out })
+            if (!*st) HIP_TRY(h, hipStreamCreateWithFlags(st->put(), hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) {
-            if (!a.ev_in[i]) HIP_TRY(h, hipEventCreateWithFlags(&a.ev_in[i], hipEventDisableTiming));
-            if (!a.ev_free[i]) HIP_TRY(h, hipEventCreateWithFlags(&a.ev_free[i], hipEventDisableTiming));
-            if (!a.ev_done[i]) HIP_TRY(h, hipEventCreateWithFlags(&a.ev_done[i], hipEventDisableTiming));
-            if (!a.ev_out[i]) HIP_TRY(h, hipEventCreateWithFlags(&a.ev_out[i], hipEventDisableTiming));
-            if (!a.d_cnb[i]) HIP_TRY(h, hipMalloc((void**)&a.d_cnb[i], sizeof(int) * C));
-            if (!a.d_onb[i]) HIP_TRY(h, hipMalloc((void**)&a.d_onb[i], sizeof(int) * C));
+            for (Event* e : { &a.ev_in[i], &a.ev_free[i], &a.ev_done[i], &a.ev_out[i] })
+                if (!*e) HIP_TRY(h, hipEventCreateWithFlags(e->put(), hipEventDisableTiming));
+            HIP_TRY(h, a.d_cnb[i].reserve(sizeof(int) * C));
+            HIP_TRY(h, a.d_onb[i].reserve(sizeof(int) * C));
         }
         a.ready = true;
     }
@@ -1267,10 +1169,9 @@ int apply_params(tetra_demod* h, const host::DesignParams& np, bool tables, bool
     if (h->taps_sym() && stride_for(nd, h->max_samples) / 2 > h->q_sym_stride) {
         // a slower timing loop emits more symbols per sample: the statistic's symbol scratch grows with it
         const long long want = stride_for(nd, h->max_samples) / 2;
-        float2* q = nullptr;
-        HIP_TRY(h, hipMalloc((void**)&q, sizeof(float2) * (size_t)h->C * (size_t)want));
-        (void)hipFree(h->q_sym);
-        h->q_sym = q;
+        DevMem<float2> q;
+        HIP_TRY(h, q.reserve(sizeof(float2) * (size_t)h->C * (size_t)want));
+        h->q_sym = std::move(q);
         h->q_sym_stride = want;
     }
     if (generic_applies(h, nd)) {      // the generic kernel's scratch first: a failure leaves the handle as it was
@@ -1485,7 +1386,7 @@ int tetra_demod_kernel_ms_history(tetra_demod_t* h, int n, float* ms) {
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     for (int i = 0; i < n; i++) {
-        hipEvent_t* ev = h->ev[(h->n_calls - n + i) % tetra_demod::kEvSlots];
+        const Event* ev = h->ev[(h->n_calls - n + i) % tetra_demod::kEvSlots];
         HIP_TRY(h, hipEventSynchronize(ev[1]));
         HIP_TRY(h, hipEventElapsedTime(&ms[i], ev[0], ev[1]));
     }
@@ -1529,16 +1430,13 @@ int tetra_demod_debug_selftest(tetra_demod_t* h, const float* in128, float* out3
     if (!h || !in128 || !out320) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    struct Tmp {                      // freed on every return path
-        float* p = nullptr;
-        ~Tmp() { if (p) (void)hipFree(p); }
-    } din, dout;
-    HIP_TRY(h, hipMalloc((void**)&din.p, sizeof(float) * 128));
-    HIP_TRY(h, hipMalloc((void**)&dout.p, sizeof(float) * 320));
-    HIP_TRY(h, hipMemcpy(din.p, in128, sizeof(float) * 128, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest, dim3(1), dim3(64), 0, 0, din.p, dout.p);
+    DevMem<float> din, dout;          // freed on every return path
+    HIP_TRY(h, din.reserve(sizeof(float) * 128));
+    HIP_TRY(h, dout.reserve(sizeof(float) * 320));
+    HIP_TRY(h, hipMemcpy(din, in128, sizeof(float) * 128, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_selftest, dim3(1), dim3(64), 0, 0, din, dout);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpy(out320, dout.p, sizeof(float) * 320, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out320, dout, sizeof(float) * 320, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
 
@@ -1546,19 +1444,16 @@ int tetra_demod_debug_mfma_selftest(tetra_demod_t* h, int shape, int k, const fl
     if (!h || !a || !b || !d || (shape != 16 && shape != 32) || k < 4 || (k & 3) || k > 4096) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    struct Tmp {
-        float* p = nullptr;
-        ~Tmp() { if (p) (void)hipFree(p); }
-    } da, db, dd;
+    DevMem<float> da, db, dd;
     const size_t na = (size_t)shape * k, nd = (size_t)shape * shape;
-    HIP_TRY(h, hipMalloc((void**)&da.p, sizeof(float) * na));
-    HIP_TRY(h, hipMalloc((void**)&db.p, sizeof(float) * na));
-    HIP_TRY(h, hipMalloc((void**)&dd.p, sizeof(float) * nd));
-    HIP_TRY(h, hipMemcpy(da.p, a, sizeof(float) * na, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(db.p, b, sizeof(float) * na, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mfma_selftest, dim3(1), dim3(64), 0, 0, shape, k, da.p, db.p, dd.p);
+    HIP_TRY(h, da.reserve(sizeof(float) * na));
+    HIP_TRY(h, db.reserve(sizeof(float) * na));
+    HIP_TRY(h, dd.reserve(sizeof(float) * nd));
+    HIP_TRY(h, hipMemcpy(da, a, sizeof(float) * na, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(db, b, sizeof(float) * na, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_mfma_selftest, dim3(1), dim3(64), 0, 0, shape, k, da, db, dd);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpy(d, dd.p, sizeof(float) * nd, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(d, dd, sizeof(float) * nd, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
 

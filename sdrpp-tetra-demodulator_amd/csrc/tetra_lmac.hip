@@ -28,6 +28,7 @@
 
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
+#include "hip_host.hpp"
 #include "lmac_core.hpp"
 
 namespace {
@@ -345,14 +346,13 @@ const uint32_t* seq_table() {
         const size_t seq_words = (size_t)4 * 256 * kSeqStride;
         std::vector<uint32_t> host(seq_words);
         scramb_sequence_table(host.data());
-        uint32_t* d_seq = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d_seq), sizeof(uint32_t) * seq_words) != hipSuccess ||
+        DevMem<uint32_t> d_seq;
+        if (d_seq.reserve(sizeof(uint32_t) * seq_words) != hipSuccess ||
             hipMemcpy(d_seq, host.data(), sizeof(uint32_t) * seq_words, hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
-            if (d_seq) (void)hipFree(d_seq);
             return nullptr;
         }
-        g_seq_tab[dev] = d_seq;
+        g_seq_tab[dev] = d_seq.release();
     }
     return g_seq_tab[dev];
 }
@@ -796,35 +796,29 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
     if (rc != TETRA_OK || n_blocks == 0) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return TETRA_ERR_HIP;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    uint32_t* d_init = nullptr;
-    int32_t* d_ok = nullptr;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_HIP;
+    DevMem<uint8_t> d_in, d_out;
+    DevMem<uint32_t> d_init;
+    DevMem<int32_t> d_ok;
     const size_t in_bytes = (size_t)n_blocks * in_stride, out_bytes = (size_t)n_blocks * out_stride;
-    rc = TETRA_ERR_HIP;
-    do {
-        if (hipMalloc(&d_in, in_bytes) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess ||
-            hipMalloc(&d_ok, sizeof(int32_t) * n_blocks) != hipSuccess) { rc = TETRA_ERR_NOMEM; break; }
-        if (scramb_init) {
-            if (hipMalloc(&d_init, sizeof(uint32_t) * n_blocks) != hipSuccess) { rc = TETRA_ERR_NOMEM; break; }
-            if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess) break;
-        }
-        if (hipMemcpy(d_in, type5, in_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        const int krc = tetra_lmac_decode_batch_device(type, d_in, n_blocks, in_stride, d_init, d_out, out_stride, d_ok, nullptr);
-        if (krc != TETRA_OK) { rc = krc; break; }
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        // only the type2_bits columns: the caller's row padding is left alone
-        // (rows without padding: one contiguous copy -- a strided device-to-host copy of many narrow rows crawls)
-        if (out_stride == kBlk[type].type2 ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
-                                           : hipMemcpy2D(type2, out_stride, d_out, out_stride, kBlk[type].type2, n_blocks, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (hipMemcpy(crc_ok, d_ok, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = TETRA_OK;
-    } while (false);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_init);
-    (void)hipFree(d_ok);
-    return rc;
+    if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_ok.reserve(sizeof(int32_t) * n_blocks) != hipSuccess)
+        return TETRA_ERR_NOMEM;
+    if (scramb_init) {
+        if (d_init.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess) return TETRA_ERR_NOMEM;
+        if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
+    }
+    if (hipMemcpy(d_in, type5, in_bytes, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
+    rc = tetra_lmac_decode_batch_device(type, d_in, n_blocks, in_stride, d_init, d_out, out_stride, d_ok, nullptr);
+    if (rc != TETRA_OK) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    // only the type2_bits columns: the caller's row padding is left alone
+    // (rows without padding: one contiguous copy -- a strided device-to-host copy of many narrow rows crawls)
+    if (out_stride == kBlk[type].type2 ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
+                                       : hipMemcpy2D(type2, out_stride, d_out, out_stride, kBlk[type].type2, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    if (hipMemcpy(crc_ok, d_ok, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    return TETRA_OK;
 }
 
 }  // extern "C"

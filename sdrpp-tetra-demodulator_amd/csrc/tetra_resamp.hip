@@ -9,9 +9,11 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/tetra_chan.h"
+#include "hip_host.hpp"
 #include "resamp_core.hpp"
 
 namespace {
@@ -87,13 +89,6 @@ void design_prototype(int I, int DN, int T, double cutoff_rel, double beta, std:
     for (int l = 0; l < L; l++) h[l] = (float)(t[l] / sum * (double)I);
 }
 
-struct Guard {
-    int prev = -1;
-    bool ok;
-    explicit Guard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; ok = hipSetDevice(d) == hipSuccess; }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct tetra_resamp {
@@ -102,34 +97,18 @@ struct tetra_resamp {
     int C = 0, I = 0, DN = 0, T = 0, W = 4, units = 0, max_in = 0;
     std::vector<float> proto;
     fixed_kernel_t fixed = nullptr;
-    float* d_coef = nullptr;     // [I][T] phase table (fixed kernel) or the prototype (generic)
-    float* hist = nullptr;       // [T - 1][2 C]: the frames before the next call's first
-    float* halt = nullptr;       // same size: receives the next call's delay line, then the two swap roles
+    DevMem<float> d_coef;        // [I][T] phase table (fixed kernel) or the prototype (generic)
+    DevMem<float> hist;          // [T - 1][2 C]: the frames before the next call's first
+    DevMem<float> halt;          // same size: receives the next call's delay line, then the two swap roles
     long long n_total = 0;       // frames consumed so far
     long long m_next = 0;        // outputs emitted so far
-    float* st_in = nullptr;      // host-path staging
-    float* st_out = nullptr;
-    size_t st_in_frames = 0, st_out_frames = 0;
-    hipEvent_t ev[2] = { nullptr, nullptr };
+    DevMem<float> st_in;         // host-path staging
+    DevMem<float> st_out;
+    Event ev[2];
     bool ev_valid = false;
 };
 
-#define RS_TRY(h, expr)                                   \
-    do {                                                  \
-        hipError_t e__ = (expr);                          \
-        if (e__ != hipSuccess) {                          \
-            (h)->last_hip = (int)e__;                     \
-            return TETRA_ERR_HIP;                         \
-        }                                                 \
-    } while (0)
-
 namespace {
-
-void free_all(tetra_resamp* h) {
-    void* ptrs[] = { h->d_coef, h->hist, h->halt, h->st_in, h->st_out };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
-}
 
 size_t hist_bytes(const tetra_resamp* h) { return sizeof(float) * 2 * (size_t)h->C * (size_t)(h->T - 1); }
 
@@ -176,28 +155,27 @@ int tetra_resamp_create(const tetra_resamp_config_t* cfg, tetra_resamp_t** out) 
     if (cfg->prototype) h->proto.assign(cfg->prototype, cfg->prototype + (size_t)h->I * h->T);
     else design_prototype(h->I, h->DN, h->T, cfg->cutoff_rel, cfg->kaiser_beta, h->proto);
     h->fixed = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_fixed(h->I, h->DN, h->T, h->W);
-    Guard g(dev);
+    DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     std::vector<float> coef((size_t)h->I * h->T);
     if (h->fixed) resamp::phase_table(h->proto.data(), h->I, h->DN, h->T, coef.data());
     else coef = h->proto;
-    bool ok = hipMalloc((void**)&h->d_coef, sizeof(float) * coef.size()) == hipSuccess &&
-              hipMalloc((void**)&h->hist, hist_bytes(h)) == hipSuccess && hipMalloc((void**)&h->halt, hist_bytes(h)) == hipSuccess &&
-              hipEventCreate(&h->ev[0]) == hipSuccess && hipEventCreate(&h->ev[1]) == hipSuccess;
+    bool ok = h->d_coef.reserve(sizeof(float) * coef.size()) == hipSuccess &&
+              h->hist.reserve(hist_bytes(h)) == hipSuccess && h->halt.reserve(hist_bytes(h)) == hipSuccess &&
+              hipEventCreate(h->ev[0].put()) == hipSuccess && hipEventCreate(h->ev[1].put()) == hipSuccess;
     int rc = ok ? TETRA_OK : TETRA_ERR_NOMEM;
     if (rc == TETRA_OK && (hipMemcpy(h->d_coef, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice) != hipSuccess ||
                            hipMemset(h->hist, 0, hist_bytes(h)) != hipSuccess))
         rc = TETRA_ERR_HIP;
-    if (rc != TETRA_OK) { free_all(h); delete h; return rc; }
+    if (rc != TETRA_OK) { delete h; return rc; }
     *out = h;
     return TETRA_OK;
 }
 
 int tetra_resamp_destroy(tetra_resamp_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     (void)hipDeviceSynchronize();
-    free_all(h);
     delete h;
     return TETRA_OK;
 }
@@ -212,13 +190,13 @@ int tetra_resamp_process_device(tetra_resamp_t* h, const float* d_in, int n_in, 
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
     const size_t amask = h->W == 4 ? 15 : 7;
     if (((uintptr_t)d_in & amask) || ((uintptr_t)d_out & amask)) return TETRA_ERR_ALIGN;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)hip_stream;
     const long long m1 = resamp::outputs_after(h->n_total + n_in, h->I, h->DN);
     const long long n_new = m1 - h->m_next;
     *n_out = (int)n_new;
-    RS_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
     if (n_new > 0) {
         resamp::Ctx c;
         c.x = d_in; c.hist = h->hist; c.out = d_out; c.coef = h->d_coef;
@@ -232,19 +210,19 @@ int tetra_resamp_process_device(tetra_resamp_t* h, const float* d_in, int n_in, 
         if (h->fixed) hipLaunchKernelGGL(h->fixed, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
         else if (h->W == 4) hipLaunchKernelGGL(k_resample_generic<4>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
         else hipLaunchKernelGGL(k_resample_generic<2>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
-        RS_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
     }
-    RS_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
     h->ev_valid = true;
     // carry: the last T - 1 frames of [delay line | new] become the next call's delay line -- into the OTHER buffer (an in-place
     // move would overlap for n_in < T - 1), then the two swap roles.  Stream order keeps the kernel ahead of the copies.
     if (n_in > 0) {
         const size_t row = sizeof(float) * 2 * (size_t)h->C, hist = (size_t)h->T - 1;
         const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
-        if (keep) RS_TRY(h, hipMemcpyAsync(h->halt, (const char*)h->hist + row * (size_t)n_in, row * keep, hipMemcpyDeviceToDevice, s));
-        RS_TRY(h, hipMemcpyAsync((char*)h->halt + row * keep, (const char*)d_in + row * ((size_t)n_in - from_x), row * from_x,
+        if (keep) HIP_TRY(h, hipMemcpyAsync(h->halt, (const char*)h->hist.get() + row * (size_t)n_in, row * keep, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync((char*)h->halt.get() + row * keep, (const char*)d_in + row * ((size_t)n_in - from_x), row * from_x,
                                  hipMemcpyDeviceToDevice, s));
-        float* t = h->hist; h->hist = h->halt; h->halt = t;
+        std::swap(h->hist, h->halt);
     }
     h->n_total += n_in;
     h->m_next = m1;
@@ -254,23 +232,14 @@ int tetra_resamp_process_device(tetra_resamp_t* h, const float* d_in, int n_in, 
 int tetra_resamp_process(tetra_resamp_t* h, const float* in, int n_in, float* out, int* n_out) {
     if (!h || (!in && n_in > 0) || !out || !n_out) return TETRA_ERR_ARG;
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     const size_t row = sizeof(float) * 2 * (size_t)h->C;
     const size_t frames = (size_t)(resamp::outputs_after(h->n_total + n_in, h->I, h->DN) - h->m_next);
-    auto grow = [&](float*& p, size_t& have, size_t want) -> int {
-        if (want <= have && p) return TETRA_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; have = 0;
-        RS_TRY(h, hipMalloc((void**)&p, row * (want ? want : 1)));
-        have = want ? want : 1;
-        return TETRA_OK;
-    };
-    int rc = grow(h->st_in, h->st_in_frames, (size_t)n_in);
-    if (rc == TETRA_OK) rc = grow(h->st_out, h->st_out_frames, frames);
-    if (rc != TETRA_OK) return rc;
-    if (n_in > 0) RS_TRY(h, hipMemcpy(h->st_in, in, row * (size_t)n_in, hipMemcpyHostToDevice));
-    rc = tetra_resamp_process_device(h, h->st_in, n_in, h->st_out, n_out, nullptr);
+    HIP_TRY(h, h->st_in.reserve(row * (n_in ? (size_t)n_in : 1)));
+    HIP_TRY(h, h->st_out.reserve(row * (frames ? frames : 1)));
+    if (n_in > 0) HIP_TRY(h, hipMemcpy(h->st_in, in, row * (size_t)n_in, hipMemcpyHostToDevice));
+    int rc = tetra_resamp_process_device(h, h->st_in, n_in, h->st_out, n_out, nullptr);
     if (rc == TETRA_OK) {
         hipError_t e = hipStreamSynchronize(0);
         if (e == hipSuccess && frames) e = hipMemcpy(out, h->st_out, row * frames, hipMemcpyDeviceToHost);
@@ -281,10 +250,10 @@ int tetra_resamp_process(tetra_resamp_t* h, const float* in, int n_in, float* ou
 
 int tetra_resamp_reset(tetra_resamp_t* h) {
     if (!h) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    RS_TRY(h, hipDeviceSynchronize());
-    RS_TRY(h, hipMemset(h->hist, 0, hist_bytes(h)));
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemset(h->hist, 0, hist_bytes(h)));
     h->n_total = 0;
     h->m_next = 0;
     return TETRA_OK;
@@ -298,10 +267,10 @@ int tetra_resamp_get_prototype(tetra_resamp_t* h, float* proto) {
 
 int tetra_resamp_last_kernel_ms(tetra_resamp_t* h, float* ms) {
     if (!h || !ms || !h->ev_valid) return TETRA_ERR_ARG;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    RS_TRY(h, hipEventSynchronize(h->ev[1]));
-    RS_TRY(h, hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
+    HIP_TRY(h, hipEventSynchronize(h->ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
     return TETRA_OK;
 }
 
