@@ -1,0 +1,81 @@
+// rx_handle.hpp -- the receive-chain handle (include/tetra_rx.h) as its C ABI sources share it: tetra_rx.hip runs the chain,
+// tetra_rx_out.hip delivers a call's results to the host (include/tetra_rx_out.h).  Host-side definitions only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/tetra_rx.h"
+#include "hip_host.hpp"
+
+namespace tetra_rx_impl {
+
+struct KindInfo {
+    int tpsap, blk, list, out_stride, type1_bits;
+};
+// rows as the decoder writes them (tetra_lower_mac.c:58-105: type2 / type1 bits) and the frame list a kind's rows come from
+constexpr KindInfo kKinds[TETRA_RX_N_KINDS] = {
+    { TETRA_TPSAP_T_SB1, 1, TETRA_LIST_SYNC, 80, 60 },       // SB1
+    { TETRA_TPSAP_T_BBK, 0, TETRA_LIST_ANY, 32, 30 },        // BBK
+    { TETRA_TPSAP_T_SB2, 2, TETRA_LIST_SYNC, 144, 124 },     // SB2
+    { TETRA_TPSAP_T_NDB, 1, TETRA_LIST_NORM_2, 144, 124 },   // NDB blk 1
+    { TETRA_TPSAP_T_NDB, 2, TETRA_LIST_NORM_2, 144, 124 },   // NDB blk 2
+    { TETRA_TPSAP_T_SCH_F, 0, TETRA_LIST_NORM_1, 288, 268 }, // SCH/F
+};
+// the second decode launch's job order: long blocks first, so that the short ones fill the machine while the long ones finish
+constexpr int kJobOrder[] = { TETRA_RX_KIND_SCH_F, TETRA_RX_KIND_SB2, TETRA_RX_KIND_NDB1, TETRA_RX_KIND_NDB2, TETRA_RX_KIND_BBK };
+
+static_assert(sizeof(tetra_rx_block_t) == sizeof(tetra_lmac_label_t), "tetra_rx_block_t is the decoder's row label");
+
+struct KindBufs {                 // one parity's results of one kind
+    DevMem<uint8_t> t2;           // [rows][out_stride]
+    DevMem<int32_t> ok;           // [rows]
+    DevMem<tetra_rx_block_t> blocks;      // [rows]
+    // into the parity's frame lists (not owned): the kind's rows are the frames row_frame[0 .. *n_rows)
+    const int32_t* row_frame = nullptr;
+    const int32_t* n_rows = nullptr;
+};
+
+}  // namespace tetra_rx_impl
+
+using namespace tetra_rx_impl;
+
+struct tetra_rx {
+    tetra_rx_config_t cfg;
+    int device = 0, last_hip = 0;
+    int C = 0, F = 0, rows = 0, stride = 0, kinds = 0;
+    bool one_stream = false;
+    Handle<tetra_demod_t*, tetra_demod_destroy> dem;
+    Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
+    Stream tail;
+    Stream fetch_s;                       // tetra_rx_fetch's pack + copy (never behind a queued tail)
+    // per call parity
+    DevMem<uint8_t> bits[2];
+    DevMem<int32_t> nbits[2];
+    KindBufs res[2][TETRA_RX_N_KINDS];
+    DevMem<int32_t> lists[2];             // [TETRA_N_LISTS][rows] frame lists
+    DevMem<int32_t> counts[2];            // [TETRA_N_LISTS]
+    Event ev_demod[2], ev_tail[2];
+    // the tail's working set (one: tails run one after the other on one stream)
+    DevMem<uint32_t> frames;              // [rows][16] packed frames
+    DevMem<int32_t> ft;                   // [rows] frame types
+    DevMem<uint32_t> fb;                  // [rows] frame bit numbers
+    DevMem<int32_t> nf;                   // [C]
+    DevMem<int32_t> chan_first;           // [TETRA_N_LISTS][C] position in each list of a channel's first entry
+    DevMem<int32_t> index_work;           // tetra_burst_index_device's scratch
+    DevMem<void> lmac_ws;                 // the decoder's decision scratch for the launch of every other kind
+    DevMem<uint8_t> fetch_stage;          // tetra_rx_fetch: a kind's type-1 bits packed row after row (allocated on first use)
+    DevMem<uint32_t> row_scramb, row_time_rx, row_time;
+    DevMem<tetra_lmac_cell_state_t> cell; // [C]
+    DevMem<float> st_iq;                  // host-path staging
+    Event ev_stage[4];
+    long long calls = 0;
+    bool stage_valid = false;
+    // deliveries (tetra_rx_out.hip), on fetch_s behind the tail of the call they read
+    Event ev_out[2];                      // per call parity: the latest delivery of that parity's results ...
+    bool out_pending[2] = { false, false };   // ... still to be waited for by the tail that overwrites those results
+    static constexpr int kOutRing = 8;    // the latest deliveries, for tetra_rx_out_query / _wait (created on first use)
+    Event ring_ev[kOutRing];
+    long long ring_call[kOutRing] = { -1, -1, -1, -1, -1, -1, -1, -1 }, ring_seq[kOutRing] = {}, out_seq = 0;
+    DevMem<int32_t> out_tiles;            // [2][TETRA_RX_N_KINDS][tiles]: kept rows per tile, then their first output row
+    DevMem<uint8_t> out_layout;           // the layout the write launch reads (rx_out::Layout)
+};

@@ -22,26 +22,9 @@
 #include <new>
 
 #include "../../include/tetra_rx.h"
-#include "hip_host.hpp"
+#include "rx_handle.hpp"
 
 namespace {
-
-struct KindInfo {
-    int tpsap, blk, list, out_stride, type1_bits;
-};
-// rows as the decoder writes them (tetra_lower_mac.c:58-105: type2 / type1 bits) and the frame list a kind's rows come from
-constexpr KindInfo kKinds[TETRA_RX_N_KINDS] = {
-    { TETRA_TPSAP_T_SB1, 1, TETRA_LIST_SYNC, 80, 60 },       // SB1
-    { TETRA_TPSAP_T_BBK, 0, TETRA_LIST_ANY, 32, 30 },        // BBK
-    { TETRA_TPSAP_T_SB2, 2, TETRA_LIST_SYNC, 144, 124 },     // SB2
-    { TETRA_TPSAP_T_NDB, 1, TETRA_LIST_NORM_2, 144, 124 },   // NDB blk 1
-    { TETRA_TPSAP_T_NDB, 2, TETRA_LIST_NORM_2, 144, 124 },   // NDB blk 2
-    { TETRA_TPSAP_T_SCH_F, 0, TETRA_LIST_NORM_1, 288, 268 }, // SCH/F
-};
-// the second decode launch's job order: long blocks first, so that the short ones fill the machine while the long ones finish
-constexpr int kJobOrder[] = { TETRA_RX_KIND_SCH_F, TETRA_RX_KIND_SB2, TETRA_RX_KIND_NDB1, TETRA_RX_KIND_NDB2, TETRA_RX_KIND_BBK };
-
-static_assert(sizeof(tetra_rx_block_t) == sizeof(tetra_lmac_label_t), "tetra_rx_block_t is the decoder's row label");
 
 // the type-1 bits of the first n rows, packed: out[j][0 .. nb) = t2[j][0 .. nb) (two bytes per thread: every kind's count is even)
 __global__ __launch_bounds__(256) void k_rx_pack_type1(const uint8_t* __restrict__ t2, int in_stride, int nb, int n, uint8_t* __restrict__ out) {
@@ -51,52 +34,6 @@ __global__ __launch_bounds__(256) void k_rx_pack_type1(const uint8_t* __restrict
     const int j = (int)(i / half), u = (int)(i - (long long)j * half);
     reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(t2 + (size_t)j * in_stride)[u];
 }
-
-struct KindBufs {                 // one parity's results of one kind
-    DevMem<uint8_t> t2;           // [rows][out_stride]
-    DevMem<int32_t> ok;           // [rows]
-    DevMem<tetra_rx_block_t> blocks;      // [rows]
-    // into the parity's frame lists (not owned): the kind's rows are the frames row_frame[0 .. *n_rows)
-    const int32_t* row_frame = nullptr;
-    const int32_t* n_rows = nullptr;
-};
-
-}  // namespace
-
-struct tetra_rx {
-    tetra_rx_config_t cfg;
-    int device = 0, last_hip = 0;
-    int C = 0, F = 0, rows = 0, stride = 0, kinds = 0;
-    bool one_stream = false;
-    Handle<tetra_demod_t*, tetra_demod_destroy> dem;
-    Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
-    Stream tail;
-    Stream fetch_s;                       // tetra_rx_fetch's pack + copy (never behind a queued tail)
-    // per call parity
-    DevMem<uint8_t> bits[2];
-    DevMem<int32_t> nbits[2];
-    KindBufs res[2][TETRA_RX_N_KINDS];
-    DevMem<int32_t> lists[2];             // [TETRA_N_LISTS][rows] frame lists
-    DevMem<int32_t> counts[2];            // [TETRA_N_LISTS]
-    Event ev_demod[2], ev_tail[2];
-    // the tail's working set (one: tails run one after the other on one stream)
-    DevMem<uint32_t> frames;              // [rows][16] packed frames
-    DevMem<int32_t> ft;                   // [rows] frame types
-    DevMem<uint32_t> fb;                  // [rows] frame bit numbers
-    DevMem<int32_t> nf;                   // [C]
-    DevMem<int32_t> chan_first;           // [TETRA_N_LISTS][C] position in each list of a channel's first entry
-    DevMem<int32_t> index_work;           // tetra_burst_index_device's scratch
-    DevMem<void> lmac_ws;                 // the decoder's decision scratch for the launch of every other kind
-    DevMem<uint8_t> fetch_stage;          // tetra_rx_fetch: a kind's type-1 bits packed row after row (allocated on first use)
-    DevMem<uint32_t> row_scramb, row_time_rx, row_time;
-    DevMem<tetra_lmac_cell_state_t> cell; // [C]
-    DevMem<float> st_iq;                  // host-path staging
-    Event ev_stage[4];
-    long long calls = 0;
-    bool stage_valid = false;
-};
-
-namespace {
 
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
 
@@ -208,7 +145,8 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     for (int b = 0; b < 2 && ok; b++) {
         ok = dalloc(h->bits[b], (size_t)h->C * h->stride) && dalloc(h->nbits[b], (size_t)h->C) && dalloc(h->lists[b], (size_t)TETRA_N_LISTS * n) &&
              dalloc(h->counts[b], (size_t)TETRA_N_LISTS) && hipEventCreateWithFlags(h->ev_demod[b].put(), hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(h->ev_tail[b].put(), hipEventDisableTiming) == hipSuccess;
+             hipEventCreateWithFlags(h->ev_tail[b].put(), hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(h->ev_out[b].put(), hipEventDisableTiming) == hipSuccess;
         for (int k = 0; k < TETRA_RX_N_KINDS && ok; k++) {
             if (!(h->kinds & (1 << k))) continue;
             KindBufs& r = h->res[b][k];
@@ -256,6 +194,8 @@ int tetra_rx_reset(tetra_rx_t* h) {
     TETRA_TRY(zero_results(h));
     h->calls = 0;
     h->stage_valid = false;
+    for (bool& p : h->out_pending) p = false;          // (the device is idle: every delivery has completed)
+    for (long long& c : h->ring_call) c = -1;
     return TETRA_OK;
 }
 
@@ -274,6 +214,11 @@ int tetra_rx_process_device(tetra_rx_t* h, const float* d_iq, int n_samples, voi
     if (!h->one_stream) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_demod[b], 0));
     h->calls++;                     // the call exists from here on: a failing tail leaves its rows undefined, not the bookkeeping
     h->stage_valid = false;
+    // a delivery of call k - 2 (tetra_rx_out.h) still reads this parity's results: this tail waits for it on the device
+    if (h->out_pending[b]) {
+        HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_out[b], 0));
+        h->out_pending[b] = false;
+    }
     TETRA_TRY(enqueue_tail(h, b, sb));
     HIP_TRY(h, hipEventRecord(h->ev_tail[b], sb));
     h->stage_valid = true;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "tetra_rx.h"
+#include "tetra_rx_out.h"
 
 namespace dsp {
 namespace demod {
@@ -24,13 +25,18 @@ public:
     };
 
     TetraRxBank() {}
-    ~TetraRxBank() { if (h_) tetra_rx_destroy(h_); }
+    ~TetraRxBank() {
+        if (h_) tetra_rx_destroy(h_);          // synchronises the device: no delivery still writes into out_
+        for (auto& o : out_) tetra_rx_out_host_free(o.buf);
+    }
     TetraRxBank(const TetraRxBank&) = delete;
     TetraRxBank& operator=(const TetraRxBank&) = delete;
 
     // cfg: tetra_rx_default_config() + demod.n_channels / max_samples / layout / device (+ kinds, flags).  Returns a TETRA_* status.
     int init(const tetra_rx_config_t& cfg) {
         if (h_) { tetra_rx_destroy(h_); h_ = nullptr; }
+        for (auto& o : out_) { tetra_rx_out_host_free(o.buf); o = OutBuf(); }
+        next_ = 0;
         channels_ = cfg.demod.n_channels;
         return tetra_rx_create(&cfg, &h_);
     }
@@ -40,7 +46,10 @@ public:
     // the same with the samples already on the GPU (what a channeliser leaves there), enqueued on the caller's stream
     int processDevice(int count, const float* dIq, void* hipStream) { return tetra_rx_process_device(h_, dIq, count, hipStream); }
     int wait() { return tetra_rx_wait(h_); }
-    int reset() { return tetra_rx_reset(h_); }
+    int reset() {
+        out_[0].call = out_[1].call = -1;
+        return tetra_rx_reset(h_);
+    }
     // Decoded blocks of one kind (TETRA_RX_KIND_*) of the latest call (which = 0) or the one before it (1).
     int fetch(int kind, Blocks& out, int which = 0) {
         const int nb = tetra_rx_type1_bits(kind);
@@ -53,6 +62,58 @@ public:
         out.type1.resize((size_t)n * (size_t)nb);
         if (n == 0) return TETRA_OK;
         return tetra_rx_fetch(h_, which, kind, out.info.data(), out.type1.data(), nb, n, &n);
+    }
+    // One-step hand-off (include/tetra_rx_out.h): every kind of `kinds` (0 = every configured kind) of the latest (which = 0) or
+    // previous (1) call, gathered by the GPU into one of this bank's two page-locked buffers without waiting; *call names the delivered
+    // call for collect(), which must come before the second deliver() after this one.  flags: TETRA_RX_OUT_*.
+    int deliver(int64_t* call, int which = 0, int kinds = 0, int flags = 0) {
+        if (!h_ || !call) return TETRA_ERR_ARG;
+        // two buffers, taken in turn, each sized once for the largest delivery the handle can make (every kind, byte per bit); the
+        // delivery stream runs them in order, so a buffer is only rewritten after the delivery before it has completed
+        OutBuf& o = out_[next_];
+        if (!o.buf) {
+            uint64_t need = 0;
+            const int rc = tetra_rx_out_bound(h_, 0, 0, &need);
+            if (rc != TETRA_OK) return rc;
+            if (!(o.buf = tetra_rx_out_host_alloc((size_t)need))) return TETRA_ERR_NOMEM;
+            o.bytes = need;
+        }
+        const int rc = tetra_rx_out_enqueue(h_, which, kinds, flags, o.buf, o.bytes, call);
+        if (rc != TETRA_OK) return rc;
+        o.call = *call;
+        next_ ^= 1;
+        return TETRA_OK;
+    }
+    // Waits for the delivery of `call` and copies its blocks out: out[kind] for every kind it holds (type-1 rows one bit per byte,
+    // unpacked if the delivery was packed); the other entries are left empty.
+    int collect(int64_t call, Blocks out[TETRA_RX_N_KINDS]) {
+        if (!h_ || call < 0) return TETRA_ERR_ARG;
+        int rc = tetra_rx_out_wait(h_, call);
+        if (rc != TETRA_OK) return rc;
+        const OutBuf* ob = out_[0].call == call ? &out_[0] : out_[1].call == call ? &out_[1] : nullptr;
+        if (!ob) return TETRA_ERR_ARG;
+        const OutBuf& o = *ob;
+        for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
+            Blocks& b = out[k];
+            b.info.clear();
+            b.type1.clear();
+            b.bitsPerBlock = tetra_rx_type1_bits(k);
+            const tetra_rx_block_t* blk = nullptr;
+            const uint8_t* bits = nullptr;
+            int n = 0, rb = 0;
+            rc = tetra_rx_out_view(o.buf, o.bytes, k, &blk, &bits, &n, &rb);
+            if (rc == TETRA_ERR_UNSUPPORTED) continue;             // a kind the delivery does not hold
+            if (rc != TETRA_OK) return rc;
+            b.info.assign(blk, blk + n);
+            if (rb == b.bitsPerBlock) {
+                b.type1.assign(bits, bits + (size_t)n * (size_t)rb);
+                continue;
+            }
+            b.type1.resize((size_t)n * (size_t)b.bitsPerBlock);
+            rc = tetra_rx_unpack_bits(bits, n, rb, b.bitsPerBlock, b.type1.data(), b.bitsPerBlock);
+            if (rc != TETRA_OK) return rc;
+        }
+        return TETRA_OK;
     }
     // tcd / t_phy_state of every channel (tetra_lower_mac.c:116, tetra_burst_sync.c:34 -- one per channel here)
     int cells(std::vector<tetra_lmac_cell_state_t>& out) {
@@ -73,8 +134,15 @@ public:
     tetra_rx_t* handle() { return h_; }
 
 private:
+    struct OutBuf {
+        void* buf = nullptr;
+        uint64_t bytes = 0;
+        int64_t call = -1;                // the call last delivered into it
+    };
     tetra_rx_t* h_ = nullptr;
     int channels_ = 0;
+    OutBuf out_[2];
+    int next_ = 0;
 };
 
 // The chain over several GPUs of a node, beside PI4DQPSKMultiBank: channels are independent receivers, so GPU g takes the channel
@@ -143,6 +211,28 @@ public:
             for (auto& b : part.info) b.channel += s->first;
             out.info.insert(out.info.end(), part.info.begin(), part.info.end());
             out.type1.insert(out.type1.end(), part.type1.begin(), part.type1.end());
+        }
+        return TETRA_OK;
+    }
+    // Every kind of `kinds` (0 = all configured) in one step per shard: every shard's delivery is enqueued first, then each is
+    // collected, so the GPUs' transfers run side by side.  out[kind] as fetch() returns it (bank channel numbers, (channel, frame)
+    // order, one bit per byte); kinds outside the delivery come back empty.
+    int fetchAll(TetraRxBank::Blocks out[TETRA_RX_N_KINDS], int which = 0, int kinds = 0, int flags = 0) {
+        for (int k = 0; k < TETRA_RX_N_KINDS; k++) { out[k].info.clear(); out[k].type1.clear(); out[k].bitsPerBlock = tetra_rx_type1_bits(k); }
+        std::vector<int64_t> calls(shards_.size(), -1);
+        for (size_t s = 0; s < shards_.size(); s++) {
+            const int rc = shards_[s]->bank.deliver(&calls[s], which, kinds, flags);
+            if (rc != TETRA_OK) return rc;
+        }
+        TetraRxBank::Blocks part[TETRA_RX_N_KINDS];
+        for (size_t s = 0; s < shards_.size(); s++) {
+            const int rc = shards_[s]->bank.collect(calls[s], part);
+            if (rc != TETRA_OK) return rc;
+            for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
+                for (auto& b : part[k].info) b.channel += shards_[s]->first;
+                out[k].info.insert(out[k].info.end(), part[k].info.begin(), part[k].info.end());
+                out[k].type1.insert(out[k].type1.end(), part[k].type1.begin(), part[k].type1.end());
+            }
         }
         return TETRA_OK;
     }

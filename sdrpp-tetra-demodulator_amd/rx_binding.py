@@ -102,8 +102,9 @@ class RxChain:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.tetra_rx_destroy(self._h)
+            self._lib.tetra_rx_destroy(self._h)          # synchronises the device: no delivery still writes into the pool
             self._h = None
+        self._close_pool()
 
     def __del__(self):
         try:
@@ -178,3 +179,166 @@ class RxChain:
 
     def demod_handle(self):
         return self._lib.tetra_rx_demod(self._h)
+
+    def deliver(self, which=0, kinds=0, packed=False, crc_good_only=False, buf=None):
+        """Enqueue a delivery of the latest (which = 0) or previous (1) call's blocks of `kinds` (bit mask, 0 = every configured kind)
+        and return a Delivery without waiting.  buf = None: the next of two page-locked buffers of this handle (sized for the worst case),
+        so the arrays a Delivery returns stay valid until the second delivery after it is enqueued; else a HostBuffer, a torch tensor on
+        the handle's GPU, or any object with a .ctypes pointer (pageable memory is refused: TETRA_ERR_ARG)."""
+        self._out = _out_lib()
+        flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
+        if buf is None:
+            if getattr(self, "_pool", None) is None:
+                nb = C.c_uint64(0)
+                self._chk(self._out.tetra_rx_out_bound(self._h, 0, 0, C.byref(nb)), "tetra_rx_out_bound")
+                self._pool, self._pool_next = [HostBuffer(nb.value) for _ in range(2)], 0
+            buf = self._pool[self._pool_next]
+            self._pool_next ^= 1
+        if isinstance(buf, HostBuffer):
+            ptr, cap = buf.ptr, buf.nbytes
+        elif hasattr(buf, "data_ptr"):
+            ptr, cap = buf.data_ptr(), buf.numel() * buf.element_size()
+        else:
+            ptr, cap = buf.ctypes.data, buf.nbytes
+        call = C.c_int64(-1)
+        self._chk(self._out.tetra_rx_out_enqueue(self._h, which, kinds, flags, C.c_void_p(ptr), cap, C.byref(call)), "tetra_rx_out_enqueue")
+        return Delivery(self, call.value, buf, cap)
+
+    def out_bound(self, kinds=0, packed=False, crc_good_only=False):
+        nb = C.c_uint64(0)
+        flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
+        self._chk(_out_lib().tetra_rx_out_bound(self._h, kinds, flags, C.byref(nb)), "tetra_rx_out_bound")
+        return nb.value
+
+    def _close_pool(self):
+        for b in getattr(self, "_pool", None) or []:
+            b.close()
+        self._pool = None
+
+
+# ---- one-step hand-off of a call's blocks (include/tetra_rx_out.h) ----
+
+RX_OUT_EXPORTS = ["tetra_rx_out_bound", "tetra_rx_out_enqueue", "tetra_rx_out_query", "tetra_rx_out_wait", "tetra_rx_out_host_alloc",
+                  "tetra_rx_out_host_free", "tetra_rx_out_view", "tetra_rx_unpack_bits"]
+OUT_PACKED, OUT_CRC_GOOD = 1, 2
+OUT_MAGIC = 0x4f585254
+
+
+class OutKind(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("n_rows_decoded", C.c_int32), ("row_bytes", C.c_int32),
+                ("blocks_offset", C.c_uint64), ("bits_offset", C.c_uint64)]
+
+
+class OutHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint32), ("status", C.c_int32), ("flags", C.c_int32), ("n_kinds", C.c_int32), ("call", C.c_int64),
+                ("bytes", C.c_uint64), ("kinds", OutKind * N_KINDS)]
+
+
+_out_ready = False
+
+
+def _out_lib():
+    global _out_ready
+    L = _lib()
+    if not _out_ready:
+        vp, i32 = C.c_void_p, C.c_int
+        L.tetra_rx_out_bound.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
+        L.tetra_rx_out_enqueue.argtypes = [vp, i32, i32, i32, vp, C.c_uint64, C.POINTER(C.c_int64)]
+        L.tetra_rx_out_query.argtypes = [vp, C.c_int64]
+        L.tetra_rx_out_wait.argtypes = [vp, C.c_int64]
+        L.tetra_rx_out_host_alloc.argtypes = [C.c_size_t]
+        L.tetra_rx_out_host_alloc.restype = vp
+        L.tetra_rx_out_host_free.argtypes = [vp]
+        L.tetra_rx_out_host_free.restype = None
+        L.tetra_rx_out_view.argtypes = [vp, C.c_uint64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
+        L.tetra_rx_unpack_bits.argtypes = [vp, i32, i32, i32, vp, i32]
+        for n in ("tetra_rx_out_bound", "tetra_rx_out_enqueue", "tetra_rx_out_query", "tetra_rx_out_wait", "tetra_rx_out_view",
+                  "tetra_rx_unpack_bits"):
+            getattr(L, n).restype = i32
+        _out_ready = True
+    return L
+
+
+class HostBuffer:
+    """Page-locked, coherent host memory mapped for the GPUs (tetra_rx_out_host_alloc); .array is a uint8 numpy view of it."""
+
+    def __init__(self, nbytes):
+        self._lib = _out_lib()
+        self.nbytes = int(nbytes)
+        self.ptr = self._lib.tetra_rx_out_host_alloc(self.nbytes)
+        if not self.ptr:
+            raise TetraDemodError(-5, "tetra_rx_out_host_alloc")
+        self.array = np.ctypeslib.as_array((C.c_uint8 * self.nbytes).from_address(self.ptr))
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.array = None
+            self._lib.tetra_rx_out_host_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def view_delivery(buf, nbytes=None):
+    """A completed delivery in host memory (numpy uint8 array, or HostBuffer) -> (header, {kind: (blocks, type1)}): numpy views into
+    the buffer; type1 is [n][row_bytes] (packed rows when the header's flags say so).  A header status other than TETRA_OK raises."""
+    L = _out_lib()
+    arr = buf.array if isinstance(buf, HostBuffer) else buf
+    nbytes = arr.nbytes if nbytes is None else int(nbytes)
+    base = arr.ctypes.data
+    hd = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+    out = {}
+    for i in range(max(0, min(hd.n_kinds, N_KINDS))):
+        k = hd.kinds[i].kind
+        pb, pt, n, rb = C.c_void_p(), C.c_void_p(), C.c_int(0), C.c_int(0)
+        rc = L.tetra_rx_out_view(C.c_void_p(base), nbytes, k, C.byref(pb), C.byref(pt), C.byref(n), C.byref(rb))
+        if rc:
+            raise TetraDemodError(rc, "tetra_rx_out_view")
+        ob, ot = pb.value - base, pt.value - base
+        blocks = arr[ob: ob + n.value * BLOCK_DTYPE.itemsize].view(BLOCK_DTYPE)
+        out[k] = (blocks, arr[ot: ot + n.value * rb.value].reshape(n.value, rb.value))
+    return hd, out
+
+
+def unpack_bits(packed, n_bits):
+    """Packed rows [n][row_bytes] (first bit in bit 7) -> uint8 [n][n_bits], one bit per byte (tetra_rx_unpack_bits)."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    n, rb = packed.shape
+    out = np.zeros((n, n_bits), np.uint8)
+    rc = _out_lib().tetra_rx_unpack_bits(packed.ctypes.data_as(C.c_void_p), n, rb, n_bits, out.ctypes.data_as(C.c_void_p), n_bits)
+    if rc:
+        raise TetraDemodError(rc, "tetra_rx_unpack_bits")
+    return out
+
+
+class Delivery:
+    """One enqueued delivery (RxChain.deliver).  ready() polls; wait() blocks and returns {kind: (blocks, type1)}."""
+
+    def __init__(self, chain, call, buf, capacity):
+        self.chain, self.call, self.buf, self.capacity = chain, call, buf, capacity
+        self.header = None
+
+    def ready(self):
+        rc = self.chain._out.tetra_rx_out_query(self.chain._h, self.call)
+        if rc < 0:
+            raise TetraDemodError(rc, "tetra_rx_out_query")
+        return rc == 0
+
+    def wait(self):
+        self.chain._chk(self.chain._out.tetra_rx_out_wait(self.chain._h, self.call), "tetra_rx_out_wait")
+        buf = self.buf
+        if hasattr(buf, "data_ptr"):              # a device tensor: the header says how much to bring over
+            head = buf[:C.sizeof(OutHeader)].cpu().numpy()
+            need = int(OutHeader.from_buffer_copy(head.tobytes()).bytes)
+            buf = buf[:min(need, self.capacity)].cpu().numpy() if need <= self.capacity else head
+            self.host_copy = buf
+        arr = buf.array if isinstance(buf, HostBuffer) else buf
+        self.header = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+        if self.header.status:
+            raise TetraDemodError(self.header.status, "tetra_rx delivery (needs %d bytes)" % self.header.bytes)
+        return view_delivery(buf, min(arr.nbytes, self.capacity))[1]
+
