@@ -1,7 +1,9 @@
 """Time-bounded fuzz of tetra_burst_index_device + tetra_lmac_decode_frames_device + tetra_lmac_track_sync_lists_device on the GPU
 against (a) the decoder's lane code built for the host (tests/emul/lmac_emul.cpp, itself pinned on the reference's primitives by the
-CPU suite) for every listed frame of every kind, and (b) the slot-layout tracker tetra_lmac_track_sync_device (pinned on the
-reference's field read-out and TDMA arithmetic) for cell state / codes / times / SB1 labels.  Random frame types (incl. slots that
+CPU suite) for every listed frame of every kind, and (b) tetra_lmac_track_sync_device for cell state / codes / times / SB1 labels.
+Both trackers run the same kernel (k_track), so (b) compares its two row layouts -- compact list rows read as words against one row
+per frame slot read as bytes -- not two independent implementations; the rule itself is pinned on the reference by
+tests/test_lmac.py.  Random frame types (incl. slots that
 carry nothing), random payload with a share of reference-encoded blocks under the frame's own code, random codes, ragged frame
 counts, carried cell state over several calls.  Usage: python profiles/fuzz_lmac_frames_gpu.py [seconds] [out.json]"""
 import json

@@ -26,6 +26,7 @@
 //                      g3 = 1+D+D^2+D^4, g4 = 1+D+D^3+D^4.  With i = (d0 d1 d2) the three newer delay bits of the even
 //                      predecessor and input 0: g1 = d0, g2 = d1^d2 (g3, g4 only ever meet erasures here).
 //   * CRC              crc_simple.c:59-77, :103-106: CRC16-CCITT (0x1021) over the bits, start 0xffff, good = 0x1d0f.
+// The SB1 tracker's scalar pieces (SYNC-PDU fields, scrambling code, TDMA clock) are at the end.
 #pragma once
 
 #include <stdint.h>
@@ -449,5 +450,60 @@ LM_FN bool viterbi_traceback(int n2, Ld ld, St st, Tinv tinv) {
 
 // 4 decoded bits -> 4 bytes (one bit per byte, little endian)
 LM_FN uint32_t spread4(uint32_t nib) { return (nib * 0x00204081u) & 0x01010101u; }
+
+// ---- SB1 tracking (tetra_lmac_track_*_device): the SYNC PDU, the scrambling code and the TDMA clock -------------------------------
+// Host and device: tetra_lmac_scramb_init and the tracker kernel use the same source.
+#if defined(__HIPCC__) && !defined(TETRA_HOST_EMUL)
+#define LM_HD __host__ __device__ __forceinline__
+#else
+#define LM_HD inline
+#endif
+
+// tetra_scramb.c:87-99: colour (6 bits) | MNC (14) << 6 | MCC (10) << 20, then two 1 bits shifted in below
+LM_HD uint32_t scramb_code(uint32_t colour, uint32_t mcc, uint32_t mnc) {
+    return (((colour & 0x3f) | ((mnc & 0x3fff) << 6) | ((mcc & 0x3ff) << 20)) << 2) | kScrambInitSb1;
+}
+
+// The fields tp_sap_udata_ind's SB1 case reads from a SYNC PDU (tetra_lower_mac.c:246-275), read from v = type-2 bits 0..55 of the
+// SB1 block, bit 0 at bit 63.
+struct SyncPdu {
+    uint64_t v;
+    LM_HD uint32_t field(int first, int len) const { return (uint32_t)(v >> (64 - first - len)) & ((1u << len) - 1u); }
+    LM_HD uint32_t colour() const { return field(4, 6); }
+    LM_HD uint32_t tn() const { return field(10, 2) + 1u; }          // as tcd->time holds it: the PDU's timeslot field + 1
+    LM_HD uint32_t fn() const { return field(12, 5); }
+    LM_HD uint32_t mn() const { return field(17, 6); }
+    LM_HD uint32_t mcc() const { return field(31, 10); }
+    LM_HD uint32_t mnc() const { return field(41, 14); }
+};
+
+// The PHY's TDMA clock (tetra_tdma.c:28-78).  One tetra_tdma_time_add_tn(t, 1), wrap thresholds to the letter: any state lands in
+// tn 0..4, fn 0..18, mn 0..60.
+struct Tdma { uint32_t tn, fn, mn; };
+LM_HD void tdma_add_tn(Tdma& t) {
+    t.tn += 1;
+    if (t.tn > 4) { const uint32_t d = t.tn / 4; t.tn = t.tn % 4; t.fn += d; }
+    if (t.fn > 18) { const uint32_t d = t.fn / 18; t.fn = t.fn % 18; t.mn += d; }
+    if (t.mn > 60) t.mn = t.mn % 60;
+}
+// k >= 1 calls of tetra_tdma_time_add_tn(t, 1): one literal step, then k - 1 in closed form (from there on the three counters run
+// 1..4, 1..18, 1..60, a zero taking one step to become 1)
+LM_HD Tdma tdma_advance(Tdma t, uint32_t k) {
+    tdma_add_tn(t);
+    k -= 1;
+    if (k) {
+        const uint32_t p1 = t.tn + k - 1u;                                // t.tn in 0..4: a zero needs one step to become 1
+        const uint32_t c1 = p1 >> 2;
+        t.tn = (p1 & 3u) + 1u;
+        if (c1) {
+            const uint32_t p2 = t.fn + c1 - 1u, c2 = p2 / 18u;
+            t.fn = p2 - 18u * c2 + 1u;
+            if (c2) t.mn = (t.mn + c2 - 1u) % 60u + 1u;
+        }
+    }
+    return t;
+}
+// the packed time of the tracker's outputs: tn | fn << 8 | mn << 16
+LM_HD uint32_t tdma_pack(Tdma t) { return t.tn | (t.fn << 8) | (t.mn << 16); }
 
 }  // namespace tetra_lmac

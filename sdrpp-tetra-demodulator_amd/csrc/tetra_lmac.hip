@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tetra_lmac.h"
@@ -396,124 +397,61 @@ __global__ __launch_bounds__(256) void k_lmac_bbk(const uint8_t* __restrict__ ty
     crc_ok[blk] = 1;
 }
 
-// tetra_lower_mac.c:258-266 per channel: walk the frame slots in time order, a good SB1 replaces the scrambling code
-__global__ __launch_bounds__(256) void k_track_scramb(const uint8_t* __restrict__ sb1, int stride, const int* __restrict__ crc_ok,
-                                                      const int* __restrict__ valid, int n_channels, int frames,
-                                                      uint32_t* __restrict__ chan_scramb, uint32_t* __restrict__ row_scramb) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_channels) return;
-    uint32_t cur = chan_scramb[c];
-    for (int f = 0; f < frames; ++f) {
-        const size_t r = (size_t)c * frames + f;
-        if (valid[r] && crc_ok[r]) {
-            const uint8_t* t2 = sb1 + r * stride;
-            auto field = [&](int first, int len) { uint32_t v = 0; for (int i = 0; i < len; ++i) v = (v << 1) | (t2[first + i] & 1u); return v; };
-            const uint32_t cc = field(4, 6), mcc = field(31, 10), mnc = field(41, 14);
-            cur = (((cc & 0x3f) | ((mnc & 0x3fff) << 6) | ((mcc & 0x3ff) << 20)) << 2) | kScrambInitSb1;   // tetra_scramb.c:87-99
-        }
-        row_scramb[r] = cur;
-    }
-    chan_scramb[c] = cur;
-}
-
-// The whole SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) plus the PHY's TDMA clock
-// (tetra_burst_sync.c:113, tetra_tdma.c:28-78), per channel, frame slots in time order:
+// The SB1 tracking rule, every entry point's: the SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) plus
+// the PHY's TDMA clock (tetra_burst_sync.c:113, tetra_tdma.c:28-78), per channel, frame slots in time order:
 //   every frame the LOCKED receiver consumes      t_phy_state.time += one timeslot (tetra_tdma_time_add_tn, before the callback)
 //   a SYNC burst's SB1 block, good CRC            tcd-> colour code, time (tn = bits + 1, fn, mn), mcc, mnc, scramb_init
 //   a SYNC burst's SB1 block, any CRC             t_phy_state.time = tcd->time   (:268-269: copied whatever the CRC said)
 // Outputs per frame slot: the scrambling code in force for the slot's other blocks, the TDMA time tetra_burst_rx_cb sees on
 // entry (t_display_st->curr_multiframe / curr_frame, tetra_burst.c:349-350) and the time after the slot's SB1 (what every
-// later block of the burst and the next slot's increment start from).  Times are packed tn | fn << 8 | mn << 16.
-__device__ __forceinline__ void tdma_add_tn(uint32_t& tn, uint32_t& fn, uint32_t& mn) {
-    tn += 1;                                                  // tetra_tdma_time_add_tn(tm, 1) -> normalize_tn -> _fn -> _mn
-    if (tn > 4) { const uint32_t d = tn / 4; tn = tn % 4; fn += d; }
-    if (fn > 18) { const uint32_t d = fn / 18; fn = fn % 18; mn += d; }
-    if (mn > 60) mn = mn % 60;
+// later block of the burst and the next slot's increment start from).  Times are packed tn | fn << 8 | mn << 16 (tdma_pack).
+//
+// No walk over the slots: one wavefront per channel, 64 frame slots at a time, a slot per lane.  What a slot needs from its past is
+// (1) the last SYNC frame before it -- the PHY clock was set to tcd's time there -- and how many slots ago that was, (2) the last
+// SYNC frame with a good CRC up to there / up to the slot itself -- that is what tcd holds.  Both are "highest set bit below my
+// lane" of two ballots; the fields travel with two lane shuffles; and the clock k slots after a reset is tdma_advance.  Nothing is
+// serial but the carry from one 64-slot group to the next.  (A walk on the scalar unit: 2577 scalar instructions per wave, 29 us.)
+//
+// Two compile-time choices:
+//   ROWS   kRowsList: the SB1 rows are compact, one per SYNC-list entry (tetra_lmac_track_sync_lists_device): a slot holds a SYNC
+//                     burst where `present` (the frame types) says TETRA_TRAIN_SYNC, its row is chan_first[c] + the channel's SYNC
+//                     slots before it, read as words (4-byte aligned rows);
+//          kRowsSlot: one row per frame slot (tetra_lmac_track_sync_device / _scramb_device): the row of slot r is r, a slot holds
+//                     one where `present` (d_valid) is non-zero, read as bytes (any stride, any row alignment)
+//   State  tetra_lmac_cell_state_t (both times, labels) or uint32_t (tetra_lmac_track_scramb_device: the code alone, every slot live)
+enum { kRowsList, kRowsSlot };
+__device__ __forceinline__ tetra_lmac_cell_state_t load_state(const tetra_lmac_cell_state_t& s) { return s; }
+__device__ __forceinline__ tetra_lmac_cell_state_t load_state(uint32_t code) {
+    tetra_lmac_cell_state_t s = {};
+    s.scramb_init = code;
+    return s;
 }
-__global__ __launch_bounds__(256) void k_track_sync(const uint8_t* __restrict__ sb1, int stride, const int* __restrict__ crc_ok,
-                                                    const int* __restrict__ valid, const int* __restrict__ n_frames, int n_channels,
-                                                    int frames, tetra_lmac_cell_state_t* __restrict__ cell,
-                                                    uint32_t* __restrict__ row_scramb, uint32_t* __restrict__ row_time_rx,
-                                                    uint32_t* __restrict__ row_time) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_channels) return;
-    tetra_lmac_cell_state_t st = cell[c];
-    const int nf = n_frames ? (n_frames[c] < frames ? n_frames[c] : frames) : frames;
-    for (int f = 0; f < frames; ++f) {
-        const size_t r = (size_t)c * frames + f;
-        if (f < nf) {
-            tdma_add_tn(st.phy_tn, st.phy_fn, st.phy_mn);
-            if (row_time_rx) row_time_rx[r] = st.phy_tn | (st.phy_fn << 8) | (st.phy_mn << 16);
-            if (valid[r]) {
-                if (crc_ok[r]) {
-                    const uint8_t* t2 = sb1 + r * stride;
-                    auto field = [&](int first, int len) { uint32_t v = 0; for (int i = 0; i < len; ++i) v = (v << 1) | (t2[first + i] & 1u); return v; };
-                    st.colour_code = field(4, 6);
-                    st.tcd_tn = field(10, 2) + 1;
-                    st.tcd_fn = field(12, 5);
-                    st.tcd_mn = field(17, 6);
-                    st.mcc = field(31, 10);
-                    st.mnc = field(41, 14);
-                    st.scramb_init = (((st.colour_code & 0x3f) | ((st.mnc & 0x3fff) << 6) | ((st.mcc & 0x3ff) << 20)) << 2) | kScrambInitSb1;
-                }
-                st.phy_tn = st.tcd_tn; st.phy_fn = st.tcd_fn; st.phy_mn = st.tcd_mn;
-            }
-        } else if (row_time_rx) {
-            row_time_rx[r] = 0;
-        }
-        row_scramb[r] = st.scramb_init;
-        if (row_time) row_time[r] = f < nf ? (st.phy_tn | (st.phy_fn << 8) | (st.phy_mn << 16)) : 0u;
-    }
-    cell[c] = st;
-}
-
-// tetra_lmac_track_sync_lists_device: k_track_sync's walk with the channel's SB1 rows compact, WITHOUT the walk.  One wavefront per
-// channel, 64 frame slots at a time, a slot per lane.  What a slot needs from its past is (1) the last SYNC frame before it -- the
-// PHY clock was set to tcd's time there -- and how many slots ago that was, (2) the last SYNC frame with a good CRC up to there /
-// up to the slot itself -- that is what tcd holds.  Both are "highest set bit below my lane" of two ballots; the fields travel
-// with two lane shuffles; and the clock k slots after a reset is one literal tetra_tdma_time_add_tn step (tetra_tdma.c:28-78: any
-// state lands in tn 0..4, fn 0..18, mn 0..60 -- the wrap tests run on every call) followed by k - 1 steps in closed form
-// (three counters that run 1..4, 1..18, 1..60, a zero taking one step to become 1).  Nothing is serial but the carry from one
-// 64-slot group to the next.  (The first version walked the slots on the scalar unit: 2577 scalar instructions per wave, 29 us.)
-struct Tdma { uint32_t tn, fn, mn; };
-__device__ __forceinline__ Tdma tdma_advance(Tdma t, uint32_t k) {       // k >= 1 calls of tetra_tdma_time_add_tn(t, 1)
-    tdma_add_tn(t.tn, t.fn, t.mn);
-    k -= 1;
-    if (k) {
-        const uint32_t p1 = t.tn + k - 1u;                                // t.tn in 0..4: a zero needs one step to become 1
-        const uint32_t c1 = p1 >> 2;
-        t.tn = (p1 & 3u) + 1u;
-        if (c1) {
-            const uint32_t p2 = t.fn + c1 - 1u, c2 = p2 / 18u;
-            t.fn = p2 - 18u * c2 + 1u;
-            if (c2) t.mn = (t.mn + c2 - 1u) % 60u + 1u;
-        }
-    }
-    return t;
-}
-__device__ __forceinline__ uint32_t tdma_pack(Tdma t) { return t.tn | (t.fn << 8) | (t.mn << 16); }
+__device__ __forceinline__ void store_state(tetra_lmac_cell_state_t& d, const tetra_lmac_cell_state_t& s) { d = s; }
+__device__ __forceinline__ void store_state(uint32_t& d, const tetra_lmac_cell_state_t& s) { d = s.scramb_init; }
 // highest set bit of m at or below position `upto` (-1: none; upto = -1: none)
 __device__ __forceinline__ int last_set_upto(unsigned long long m, int upto) {
     if (upto < 0) return -1;
     const unsigned long long x = m & (upto >= 63 ? ~0ull : ((2ull << upto) - 1ull));
     return x ? 63 - __clzll((long long)x) : -1;
 }
-__global__ __launch_bounds__(kLanes) void k_track_sync_lists(const uint8_t* __restrict__ sb1, int stride, const int* __restrict__ crc_ok,
-                                                             const int* __restrict__ frame_type, const int* __restrict__ n_frames,
-                                                             const int* __restrict__ chan_first, int frames,
-                                                             tetra_lmac_cell_state_t* __restrict__ cell, uint32_t* __restrict__ row_scramb,
-                                                             uint32_t* __restrict__ row_time_rx, uint32_t* __restrict__ row_time,
-                                                             const uint32_t* __restrict__ frame_bitnum, tetra_lmac_label_t* __restrict__ labels) {
+template <int ROWS, class State>
+__global__ __launch_bounds__(kLanes) void k_track(const uint8_t* __restrict__ sb1, int stride, const int* __restrict__ crc_ok,
+                                                  const int* __restrict__ present, const int* __restrict__ n_frames,
+                                                  const int* __restrict__ chan_first, int frames, State* __restrict__ state,
+                                                  uint32_t* __restrict__ row_scramb, uint32_t* __restrict__ row_time_rx,
+                                                  uint32_t* __restrict__ row_time, const uint32_t* __restrict__ frame_bitnum,
+                                                  tetra_lmac_label_t* __restrict__ labels) {
+    using Row = typename std::conditional<ROWS == kRowsList, int, size_t>::type;      // a list position, or the slot
     const int c = blockIdx.x, lane = threadIdx.x;
     const int nf = n_frames ? min(n_frames[c], frames) : frames;
-    int base = chan_first[c];
-    tetra_lmac_cell_state_t st = cell[c];                 // wave-uniform; carried from group to group
+    int base = ROWS == kRowsList ? chan_first[c] : 0;
+    tetra_lmac_cell_state_t st = load_state(state[c]);    // wave-uniform; carried from group to group
     for (int f0 = 0; f0 < frames; f0 += kLanes) {
         const int f = f0 + lane;
         const size_t r = (size_t)c * frames + f;
-        const bool is_sync = f < frames && frame_type[r] == TETRA_TRAIN_SYNC;
+        const bool is_sync = f < frames && (ROWS == kRowsList ? present[r] == TETRA_TRAIN_SYNC : present[r] != 0);
         const unsigned long long m = __ballot(is_sync);
-        const int j = base + __popcll(m & ((1ull << lane) - 1ull));
+        const Row j = ROWS == kRowsList ? (Row)(base + __popcll(m & ((1ull << lane) - 1ull))) : (Row)r;      // the slot's SB1 row
         base += __popcll(m);
         // a: colour << 2, tn << 8, fn << 11, mn << 16;  b: mcc | mnc << 10  (of a SYNC frame with a good CRC)
         const bool valid = is_sync && f < nf;
@@ -521,13 +459,17 @@ __global__ __launch_bounds__(kLanes) void k_track_sync_lists(const uint8_t* __re
         uint32_t a = 0, b = 0;
         if (valid && crc_ok[j]) {
             good = true;
-            const uint32_t* t2 = reinterpret_cast<const uint32_t*>(sb1 + (size_t)j * stride);
+            const uint8_t* t2 = sb1 + (size_t)j * stride;
+            auto word = [&](int k) -> uint32_t {                 // bytes 4k .. 4k+3 of the row, little endian
+                if (ROWS == kRowsList) return reinterpret_cast<const uint32_t*>(t2)[k];
+                return t2[4 * k] | (t2[4 * k + 1] << 8) | (t2[4 * k + 2] << 16) | ((uint32_t)t2[4 * k + 3] << 24);
+            };
             uint64_t v = 0;                               // type-2 bits 0..55, first bit most significant
 #pragma unroll
-            for (int k = 0; k < 14; ++k) v |= (uint64_t)pack4(t2[k] & 0x01010101u) << (60 - 4 * k);
-            auto field = [&](int first, int len) { return (uint32_t)(v >> (64 - first - len)) & ((1u << len) - 1u); };
-            a = (field(4, 6) << 2) | ((field(10, 2) + 1u) << 8) | (field(12, 5) << 11) | (field(17, 6) << 16);
-            b = field(31, 10) | (field(41, 14) << 10);
+            for (int k = 0; k < 14; ++k) v |= (uint64_t)pack4(word(k) & 0x01010101u) << (60 - 4 * k);
+            const SyncPdu p = { v };
+            a = (p.colour() << 2) | (p.tn() << 8) | (p.fn() << 11) | (p.mn() << 16);
+            b = p.mcc() | (p.mnc() << 10);
         }
         const unsigned long long mv = __ballot(valid), mg = __ballot(good);
         // tcd as a slot sees it: the fields of good frame h (ah, bh = its words, fetched by every lane: a shuffle reads active lanes
@@ -554,7 +496,8 @@ __global__ __launch_bounds__(kLanes) void k_track_sync_lists(const uint8_t* __re
         // after the slot's SB1: tcd as of this slot if it is a SYNC frame, else unchanged
         const Tdma tcd_now = tcd_of(hs, as, bs, cc, mcc, mnc);
         const Tdma t_after = valid ? tcd_now : t_rx;
-        const uint32_t scramb = hs >= 0 ? ((((cc & 0x3f) | ((mnc & 0x3fff) << 6) | ((mcc & 0x3ff) << 20)) << 2) | kScrambInitSb1) : st.scramb_init;
+        uint32_t scramb = st.scramb_init;                                     // (an if, not ?:, compiles the list form to the same code
+        if (hs >= 0) scramb = scramb_code(cc, mcc, mnc);                     //  as the formula written out in place)
         const bool live = f < nf;
         // the group's last live slot is the state the next group (and the next call) starts from; slots past the channel's frame
         // count carry the code in force at its end
@@ -587,7 +530,7 @@ __global__ __launch_bounds__(kLanes) void k_track_sync_lists(const uint8_t* __re
             st.scramb_init = code_end;
         }
     }
-    if (lane == 0) cell[c] = st;
+    if (lane == 0) store_state(state[c], st);
 }
 
 int check_args(int type, const void* in, int n_blocks, int in_stride, const void* init, const void* out, int out_stride,
@@ -617,11 +560,7 @@ int tetra_lmac_blk_param(int type, tetra_lmac_blk_param_t* out) {
     return TETRA_OK;
 }
 
-uint32_t tetra_lmac_scramb_init(uint16_t mcc, uint16_t mnc, uint8_t colour) {
-    // tetra_scramb.c:87-99: colour (6 bits) | MNC (14) << 6 | MCC (10) << 20, then two 1 bits shifted in below
-    const uint32_t v = (uint32_t)(colour & 0x3f) | ((uint32_t)(mnc & 0x3fff) << 6) | ((uint32_t)(mcc & 0x3ff) << 20);
-    return (v << 2) | kScrambInitSb1;
-}
+uint32_t tetra_lmac_scramb_init(uint16_t mcc, uint16_t mnc, uint8_t colour) { return scramb_code(colour, mcc, mnc); }
 
 int tetra_lmac_decode_batch_device(int type, const uint8_t* d_type5, int n_blocks, int in_stride, const uint32_t* d_scramb_init,
                                    uint8_t* d_type2, int out_stride, int32_t* d_crc_ok, void* hip_stream) {
@@ -756,13 +695,17 @@ int tetra_lmac_debug_force_byte_route(int on) {
     return was;
 }
 
+// The three tracking entry points: one kernel (k_track), one wavefront per channel.  The slot layout reads its rows as bytes, so it
+// takes any stride and row alignment; the compact rows are read as words.
 int tetra_lmac_track_scramb_device(const uint8_t* d_sb1_type2, int type2_stride, const int32_t* d_crc_ok, const int32_t* d_valid,
                                    int n_channels, int frames_per_channel, uint32_t* d_chan_scramb, uint32_t* d_row_scramb,
                                    void* hip_stream) {
     if (!d_sb1_type2 || !d_crc_ok || !d_valid || !d_chan_scramb || !d_row_scramb) return TETRA_ERR_ARG;
     if (n_channels < 1 || frames_per_channel < 0 || type2_stride < 60) return TETRA_ERR_ARG;
-    hipLaunchKernelGGL(k_track_scramb, dim3((n_channels + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_sb1_type2,
-                       type2_stride, d_crc_ok, d_valid, n_channels, frames_per_channel, d_chan_scramb, d_row_scramb);
+    if (frames_per_channel == 0) return TETRA_OK;
+    hipLaunchKernelGGL((k_track<kRowsSlot, uint32_t>), dim3(n_channels), dim3(kLanes), 0, static_cast<hipStream_t>(hip_stream), d_sb1_type2,
+                       type2_stride, d_crc_ok, d_valid, nullptr, nullptr, frames_per_channel, d_chan_scramb, d_row_scramb, nullptr, nullptr,
+                       nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
@@ -771,9 +714,10 @@ int tetra_lmac_track_sync_device(const uint8_t* d_sb1_type2, int type2_stride, c
                                  uint32_t* d_row_scramb, uint32_t* d_row_time_rx, uint32_t* d_row_time, void* hip_stream) {
     if (!d_sb1_type2 || !d_crc_ok || !d_valid || !d_cell || !d_row_scramb) return TETRA_ERR_ARG;
     if (n_channels < 1 || frames_per_channel < 0 || type2_stride < 60) return TETRA_ERR_ARG;
-    hipLaunchKernelGGL(k_track_sync, dim3((n_channels + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_sb1_type2,
-                       type2_stride, d_crc_ok, d_valid, d_n_frames, n_channels, frames_per_channel, d_cell, d_row_scramb, d_row_time_rx,
-                       d_row_time);
+    if (frames_per_channel == 0) return TETRA_OK;
+    hipLaunchKernelGGL((k_track<kRowsSlot, tetra_lmac_cell_state_t>), dim3(n_channels), dim3(kLanes), 0, static_cast<hipStream_t>(hip_stream),
+                       d_sb1_type2, type2_stride, d_crc_ok, d_valid, d_n_frames, nullptr, frames_per_channel, d_cell, d_row_scramb,
+                       d_row_time_rx, d_row_time, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
@@ -785,8 +729,9 @@ int tetra_lmac_track_sync_lists_device(const uint8_t* d_sb1_type2, int type2_str
     if (n_channels < 1 || frames_per_channel < 0 || type2_stride < 60 || (d_sb1_labels && !d_frame_bitnum)) return TETRA_ERR_ARG;
     if ((type2_stride & 3) || ((uintptr_t)d_sb1_type2 & 3)) return TETRA_ERR_ALIGN;
     if (frames_per_channel == 0) return TETRA_OK;
-    hipLaunchKernelGGL(k_track_sync_lists, dim3(n_channels), dim3(kLanes), 0, static_cast<hipStream_t>(hip_stream), d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync,
-                       frames_per_channel, d_cell, d_row_scramb, d_row_time_rx, d_row_time, d_frame_bitnum, d_sb1_labels);
+    hipLaunchKernelGGL((k_track<kRowsList, tetra_lmac_cell_state_t>), dim3(n_channels), dim3(kLanes), 0, static_cast<hipStream_t>(hip_stream),
+                       d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync, frames_per_channel, d_cell,
+                       d_row_scramb, d_row_time_rx, d_row_time, d_frame_bitnum, d_sb1_labels);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 

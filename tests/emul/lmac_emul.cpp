@@ -138,3 +138,11 @@ extern "C" int lmac_emul_decode_frames(int tpsap, int blk_num, const uint32_t* f
     }
     return 0;
 }
+
+// tdma_advance (the SB1 tracker's closed-form TDMA clock, lmac_core.hpp) for n start states (tn, fn, mn) and every k = 1..kmax:
+// out[i][k - 1] = tdma_pack(tdma_advance(start i, k))
+extern "C" void lmac_emul_tdma_advance(const uint32_t* start, int n, int kmax, uint32_t* out) {
+    for (int i = 0; i < n; ++i)
+        for (int k = 1; k <= kmax; ++k)
+            out[(size_t)i * kmax + k - 1] = tdma_pack(tdma_advance(Tdma{ start[3 * i], start[3 * i + 1], start[3 * i + 2] }, (uint32_t)k));
+}

@@ -60,3 +60,16 @@ def decode_frames(tpsap, blk_num, frames_packed, frame_type, row_frame, frame_sc
     if rc:
         raise ValueError("refused")
     return out, ok
+
+
+def tdma_advance(start, kmax):
+    """tdma_advance (lmac_core.hpp) built for the host: start [n][3] (tn, fn, mn) -> [n][kmax] packed times after k = 1..kmax steps."""
+    global _lib
+    if _lib is None:
+        build()
+        _lib = C.CDLL(LIB)
+    st = np.ascontiguousarray(start, np.uint32)
+    out = np.zeros((len(st), kmax), np.uint32)
+    vp = C.c_void_p
+    _lib.lmac_emul_tdma_advance(st.ctypes.data_as(vp), len(st), int(kmax), out.ctypes.data_as(vp))
+    return out

@@ -372,105 +372,141 @@ def test_gpu_lmac_full_size_round_trip(pkg, lref):
         assert np.array_equal(out[r, :288], t2) and okr == ok[r]
 
 
-@pytest.mark.gpu
-def test_gpu_track_scramb_equals_reference_rule(pkg, lref):
-    """tetra_lmac_track_scramb_device == the reference's rule (tetra_lower_mac.c:258-266 with tetra_scramb_get_init from the
-    reference build): per channel in time order, a valid SB1 row with a good CRC replaces the code; carried across calls."""
-    import torch
-    rng = np.random.default_rng(8)
-    Cn, F = 37, 23
-    dev = torch.device("cuda", 0)
-    chan = rng.integers(0, 2 ** 32, Cn, dtype=np.uint64).astype(np.uint32)
-    chan[:5] = 0
-    want_chan = chan.copy()
-    d_chan = torch.from_numpy(chan.view(np.int32).copy()).to(dev)
-    for call in range(3):
-        t2 = rng.integers(0, 2, (Cn * F, 80), dtype=np.uint8)
-        ok = (rng.random(Cn * F) < 0.3).astype(np.int32)
-        valid = (rng.random(Cn * F) < 0.4).astype(np.int32)
-        want_rows = np.zeros(Cn * F, np.uint32)
-        for c in range(Cn):
-            cur = want_chan[c]
-            for f in range(F):
-                r = c * F + f
-                if valid[r] and ok[r]:
-                    bits = t2[r]
-                    val = lambda a, n: int("".join(map(str, bits[a:a + n])), 2)
-                    cur = np.uint32(lref.scramb_get_init(val(31, 10), val(41, 14), val(4, 6)))
-                want_rows[r] = cur
-            want_chan[c] = cur
-        d_rows = torch.zeros(Cn * F, dtype=torch.int32, device=dev)
-        pkg.lmac_binding.track_scramb_device(torch.from_numpy(t2).to(dev), 80, torch.from_numpy(ok).to(dev), torch.from_numpy(valid).to(dev),
-                                             Cn, F, d_chan, d_rows)
-        torch.cuda.synchronize()
-        assert np.array_equal(d_rows.cpu().numpy().view(np.uint32), want_rows), call
-        assert np.array_equal(d_chan.cpu().numpy().view(np.uint32), want_chan), call
-
-
 class _TdmaTime(__import__("ctypes").Structure):
     """struct tetra_tdma_time (src/decoder/src/tetra_tdma.h:6-12)"""
     import ctypes as _C
     _fields_ = [("hn", _C.c_uint16), ("sn", _C.c_uint32), ("tn", _C.c_uint32), ("fn", _C.c_uint32), ("mn", _C.c_uint32)]
 
 
-@pytest.mark.gpu
-def test_gpu_track_sync_equals_the_reference_rule_and_clock(pkg, lref, ref):
-    """tetra_lmac_track_sync_device == tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) + the LOCKED receiver's clock
-    (tetra_burst_sync.c:113), walked per channel in frame order with the REFERENCE'S OWN tetra_tdma_time_add_tn
-    (oracle/_ref: src/decoder/src/tetra_tdma.c compiled where it lies) and tetra_scramb_get_init: a SYNC PDU with a good CRC
-    sets colour code / TN / FN / MN / MCC / MNC and the scrambling code; the PHY time takes tcd's after EVERY SB1, good CRC or
-    not; every consumed frame advances it by one timeslot with the reference's wrap thresholds.  Three calls, state carried,
-    ragged frame counts; arbitrary field values (FN up to 31, MN up to 63 as the bit fields allow) exercise the normalisation."""
+def _ref_add_tn(ref):
+    """The reference's own tetra_tdma_time_add_tn (oracle/_ref: src/decoder/src/tetra_tdma.c compiled where it lies)."""
     import ctypes as C
+    add_tn = ref.lib().tetra_tdma_time_add_tn
+    add_tn.argtypes = [C.POINTER(_TdmaTime), C.c_uint32]
+    add_tn.restype = None
+    return add_tn
+
+
+def walk_slots(lref, cell, t2, ok, valid, nfr=None):
+    """The SB1 tracking rule walked on the host, per channel in frame-slot order, with the REFERENCE'S OWN tetra_tdma_time_add_tn
+    and tetra_scramb_get_init: tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) + the LOCKED receiver's clock
+    (tetra_burst_sync.c:113).  Every consumed frame (slot f < nfr[c]; nfr None: all) advances the PHY time by one timeslot; a valid
+    SB1 with a good CRC sets colour code / TN / FN / MN / MCC / MNC and the scrambling code; the PHY time takes tcd's after EVERY
+    valid SB1, good CRC or not.  cell [C][10] uint32 (tetra_lmac_cell_state_t) is updated in place; t2 / ok / valid are per frame
+    slot [C * F].  Returns the slot outputs (code, time on entry, time after the SB1), as the tracker packs them."""
+    import ctypes as C
+    add_tn = _ref_add_tn(lref)
+    n_ch = len(cell)
+    F = len(ok) // n_ch
+    scr, t_rx, t_af = (np.zeros(n_ch * F, np.uint32) for _ in range(3))
+    pack = lambda t: t.tn | (t.fn << 8) | (t.mn << 16)
+    for c in range(n_ch):
+        code, cc, mcc, mnc, *tcd = (int(x) for x in cell[c][:7])
+        phy = _TdmaTime(tn=int(cell[c][7]), fn=int(cell[c][8]), mn=int(cell[c][9]))
+        nf = F if nfr is None else min(int(nfr[c]), F)
+        for f in range(F):
+            r = c * F + f
+            if f < nf:
+                add_tn(C.byref(phy), 1)
+                t_rx[r] = pack(phy)
+                if valid[r]:
+                    if ok[r]:
+                        val = lambda a, n: int("".join(str(int(x)) for x in t2[r][a:a + n]), 2)
+                        cc, mcc, mnc = val(4, 6), val(31, 10), val(41, 14)
+                        tcd = [val(10, 2) + 1, val(12, 5), val(17, 6)]
+                        code = lref.scramb_get_init(mcc, mnc, cc)
+                    phy.tn, phy.fn, phy.mn = tcd
+                t_af[r] = pack(phy)
+            scr[r] = code
+        cell[c] = [code, cc, mcc, mnc, *tcd, phy.tn, phy.fn, phy.mn]
+    return scr, t_rx, t_af
+
+
+def test_tdma_advance_equals_the_reference_clock(ref):
+    """The tracker's closed-form TDMA clock (lmac_core.hpp tdma_advance, built for the host through tests/emul/lmac_emul.cpp) ==
+    k calls of the reference's tetra_tdma_time_add_tn, for every start state tn < 8, fn < 32, mn < 64 (the SYNC PDU's field widths,
+    out-of-range digits included) and every k = 1..200."""
+    import ctypes as C
+    from tests.emul import lmac_emul_bind
+    add_tn = _ref_add_tn(ref)
+    K = 200
+    start = np.array([(tn, fn, mn) for tn in range(8) for fn in range(32) for mn in range(64)], np.uint32)
+    got = lmac_emul_bind.tdma_advance(start, K)
+    want = np.zeros_like(got)
+    for i, (tn, fn, mn) in enumerate(start):
+        t = _TdmaTime(tn=int(tn), fn=int(fn), mn=int(mn))
+        p = C.byref(t)
+        row = []
+        for _ in range(K):
+            add_tn(p, 1)
+            row.append(t.tn | (t.fn << 8) | (t.mn << 16))
+        want[i] = row
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, [(tuple(start[i]), k + 1, hex(got[i, k]), hex(want[i, k])) for i, k in bad[:5]]
+
+
+def _rows_on_device(t2, stride, offset, rng):
+    """t2 [n][w] as device rows of `stride` bytes starting `offset` bytes into a buffer; the padding bytes are garbage."""
+    import torch
+    buf = rng.integers(0, 256, len(t2) * stride + offset, dtype=np.uint8)
+    buf[offset:].reshape(len(t2), stride)[:, :t2.shape[1]] = t2
+    return torch.from_numpy(buf).to(torch.device("cuda", 0))[offset:]
+
+
+LAYOUTS = ((80, 0), (83, 1), (80, 0))       # (row stride, byte offset of the first row) per call: a tight one, an odd stride unaligned
+
+
+@pytest.mark.gpu
+def test_gpu_track_scramb_equals_reference_rule(pkg, lref):
+    """tetra_lmac_track_scramb_device == the host walk (walk_slots, every slot live): per channel in time order, a valid SB1 row with
+    a good CRC replaces the code; carried across calls; rows 4-byte aligned or not."""
+    import torch
+    rng = np.random.default_rng(8)
+    Cn, F = 37, 23
+    dev = torch.device("cuda", 0)
+    chan = rng.integers(0, 2 ** 32, Cn, dtype=np.uint64).astype(np.uint32)
+    chan[:5] = 0
+    want_cell = np.zeros((Cn, 10), np.uint32)
+    want_cell[:, 0] = chan
+    d_chan = torch.from_numpy(chan.view(np.int32).copy()).to(dev)
+    for call, (stride, offset) in enumerate(LAYOUTS):
+        t2 = rng.integers(0, 2, (Cn * F, 80), dtype=np.uint8)
+        ok = (rng.random(Cn * F) < 0.3).astype(np.int32)
+        valid = (rng.random(Cn * F) < 0.4).astype(np.int32)
+        want_rows, _, _ = walk_slots(lref, want_cell, t2, ok, valid)
+        d_rows = torch.zeros(Cn * F, dtype=torch.int32, device=dev)
+        pkg.lmac_binding.track_scramb_device(_rows_on_device(t2, stride, offset, rng), stride, torch.from_numpy(ok).to(dev),
+                                             torch.from_numpy(valid).to(dev), Cn, F, d_chan, d_rows)
+        torch.cuda.synchronize()
+        assert np.array_equal(d_rows.cpu().numpy().view(np.uint32), want_rows), call
+        assert np.array_equal(d_chan.cpu().numpy().view(np.uint32), want_cell[:, 0]), call
+
+
+@pytest.mark.gpu
+def test_gpu_track_sync_equals_the_reference_rule_and_clock(pkg, lref):
+    """tetra_lmac_track_sync_device == the host walk (walk_slots: the reference's own clock and scrambling code): cell state, per-slot
+    codes and both times.  Three calls, state carried, ragged frame counts, rows 4-byte aligned or not; arbitrary field values
+    (FN up to 31, MN up to 63 as the bit fields allow) exercise the normalisation."""
     import torch
     rng = np.random.default_rng(9)
     Cn, F = 41, 29
     dev = torch.device("cuda", 0)
-    add_tn = ref.lib().tetra_tdma_time_add_tn
-    add_tn.argtypes = [C.POINTER(_TdmaTime), C.c_uint32]
-    add_tn.restype = None
-    cell = np.zeros((Cn, 10), np.uint32)
-    d_cell = torch.from_numpy(cell.view(np.int32).copy()).to(dev)
-    want = [dict(scr=0, cc=0, mcc=0, mnc=0, tcd=(0, 0, 0), phy=_TdmaTime()) for _ in range(Cn)]
-    for call in range(3):
+    want_cell = np.zeros((Cn, 10), np.uint32)
+    d_cell = torch.from_numpy(want_cell.view(np.int32).copy()).to(dev)
+    for call, (stride, offset) in enumerate(LAYOUTS):
         t2 = rng.integers(0, 2, (Cn * F, 80), dtype=np.uint8)
         ok = (rng.random(Cn * F) < 0.5).astype(np.int32)
         valid = (rng.random(Cn * F) < 0.3).astype(np.int32)
         nfr = rng.integers(0, F + 1, Cn).astype(np.int32)
-        w_scr = np.zeros(Cn * F, np.uint32)
-        w_rx = np.zeros(Cn * F, np.uint32)
-        w_t = np.zeros(Cn * F, np.uint32)
-        for c in range(Cn):
-            w = want[c]
-            for f in range(F):
-                r = c * F + f
-                if f < nfr[c]:
-                    add_tn(C.byref(w["phy"]), 1)
-                    w_rx[r] = w["phy"].tn | (w["phy"].fn << 8) | (w["phy"].mn << 16)
-                    if valid[r]:
-                        bits = t2[r]
-                        val = lambda a, n: int("".join(map(str, bits[a:a + n])), 2)
-                        if ok[r]:
-                            w["cc"], w["mcc"], w["mnc"] = val(4, 6), val(31, 10), val(41, 14)
-                            w["tcd"] = (val(10, 2) + 1, val(12, 5), val(17, 6))
-                            w["scr"] = int(lref.scramb_get_init(w["mcc"], w["mnc"], w["cc"]))
-                        w["phy"].tn, w["phy"].fn, w["phy"].mn = w["tcd"]
-                    w_t[r] = w["phy"].tn | (w["phy"].fn << 8) | (w["phy"].mn << 16)
-                w_scr[r] = w["scr"]
-        d_scr = torch.zeros(Cn * F, dtype=torch.int32, device=dev)
-        d_rx = torch.zeros(Cn * F, dtype=torch.int32, device=dev)
-        d_t = torch.zeros(Cn * F, dtype=torch.int32, device=dev)
-        pkg.lmac_binding.track_sync_device(torch.from_numpy(t2).to(dev), 80, torch.from_numpy(ok).to(dev), torch.from_numpy(valid).to(dev),
-                                           torch.from_numpy(nfr).to(dev), Cn, F, d_cell, d_scr, d_rx, d_t)
+        w_scr, w_rx, w_t = walk_slots(lref, want_cell, t2, ok, valid, nfr)
+        outs = [torch.zeros(Cn * F, dtype=torch.int32, device=dev) for _ in range(3)]
+        pkg.lmac_binding.track_sync_device(_rows_on_device(t2, stride, offset, rng), stride, torch.from_numpy(ok).to(dev),
+                                           torch.from_numpy(valid).to(dev), torch.from_numpy(nfr).to(dev), Cn, F, d_cell, *outs)
         torch.cuda.synchronize()
-        assert np.array_equal(d_scr.cpu().numpy().view(np.uint32), w_scr), call
-        assert np.array_equal(d_rx.cpu().numpy().view(np.uint32), w_rx), call
-        assert np.array_equal(d_t.cpu().numpy().view(np.uint32), w_t), call
-        got = d_cell.cpu().numpy().view(np.uint32)
-        for c in range(Cn):
-            w = want[c]
-            assert list(got[c]) == [w["scr"], w["cc"], w["mcc"], w["mnc"], *w["tcd"], w["phy"].tn, w["phy"].fn, w["phy"].mn], (call, c)
-    assert max(w["phy"].mn for w in want) > 0 and any(w["scr"] for w in want)
+        for got, want in zip(outs, (w_scr, w_rx, w_t)):
+            assert np.array_equal(got.cpu().numpy().view(np.uint32), want), call
+        assert np.array_equal(d_cell.cpu().numpy().view(np.uint32), want_cell), call
+    assert want_cell[:, 9].max() > 0 and want_cell[:, 0].any()
 
 
 @pytest.mark.gpu
@@ -585,10 +621,10 @@ def test_gpu_decode_frames_all_kinds_in_one_launch(pkg, lref, oracle):
 
 @pytest.mark.gpu
 def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
-    """tetra_lmac_track_sync_lists_device (compact SB1 rows, a wavefront per channel) == tetra_lmac_track_sync_device (slot layout,
-    itself checked against the reference's field read-out and TDMA arithmetic in tests/test_burst_sync.py): cell state, per-slot
-    codes and times, over two calls with carried state, channels without any SYNC burst, bad CRCs, short frame counts; plus the
-    SB1 rows' labels."""
+    """tetra_lmac_track_sync_lists_device (compact SB1 rows) == the host walk (walk_slots) on the same frames in the slot layout, and
+    tetra_lmac_track_sync_device (the same kernel on the slot layout) == the list form: cell state, per-slot codes and times, over
+    two calls with carried state (clock digits out of range), channels without any SYNC burst, bad CRCs, short frame counts, three
+    64-slot groups per channel; plus the SB1 rows' labels."""
     import torch
     lb, bb = pkg.lmac_binding, pkg.bsync_binding
     dev = torch.device("cuda", 0)
@@ -600,6 +636,7 @@ def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
     cell0[20, 4:] = [100, 200, 500, 7, 36, 121]
     cell_a = torch.from_numpy(cell0).to(dev)
     cell_b = torch.from_numpy(cell0.copy()).to(dev)
+    want_cell = cell0.view(np.uint32).copy()
     for call in range(2):
         types = rng.choice(np.array([0, 1, 3, 3, -1, -2], np.int32), n)
         types.reshape(C_, F)[5] = 0                                     # a channel without SYNC bursts
@@ -608,7 +645,7 @@ def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
         sync = np.flatnonzero(types == 3)
         t2c = rng.integers(0, 2, (sync.size, 80), dtype=np.uint8)
         okc = (rng.random(sync.size) < 0.8).astype(np.int32)
-        # slot layout for the old tracker
+        # the same frames in the slot layout
         slot_t2 = np.zeros((n, 80), np.uint8)
         slot_ok = np.zeros(n, np.int32)
         slot_valid = np.zeros(n, np.int32)
@@ -626,6 +663,10 @@ def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
         labels = torch.full((n, 6), -1, dtype=torch.int32, device=dev)
         lb.track_sync_lists_device(d(t2c), 80, d(okc), d_ft, d(nf), chan_first[0], C_, F, cell_b, *outs_b, d_frame_bitnum=bitnum, d_sb1_labels=labels)
         torch.cuda.synchronize()
+        want = walk_slots(lref, want_cell, slot_t2, slot_ok, slot_valid, nf)
+        assert np.array_equal(cell_b.cpu().numpy().view(np.uint32), want_cell), call
+        for b, w in zip(outs_b, want):
+            assert np.array_equal(b.cpu().numpy().view(np.uint32), w), call
         assert torch.equal(cell_a, cell_b)
         for a, b in zip(outs_a, outs_b):
             assert torch.equal(a, b)
@@ -657,4 +698,7 @@ def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
     lb.track_sync_device(d(slot_t2), 80, d(slot_ok), d(slot_valid), None, C_, F, cell_a, *oa)
     lb.track_sync_lists_device(d(t2c), 80, d(okc), d_ft, None, chan_first[0], C_, F, cell_b, *ob)
     torch.cuda.synchronize()
+    want = walk_slots(lref, want_cell, slot_t2, slot_ok, slot_valid)
+    assert np.array_equal(cell_b.cpu().numpy().view(np.uint32), want_cell)
+    assert all(np.array_equal(b.cpu().numpy().view(np.uint32), w) for b, w in zip(ob, want))
     assert torch.equal(cell_a, cell_b) and all(torch.equal(a, b) for a, b in zip(oa, ob))
