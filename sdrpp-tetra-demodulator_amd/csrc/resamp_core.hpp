@@ -13,7 +13,12 @@
 // sit in SGPRs), and of the DN + T - 1 input rows a group reads every one is loaded once and used from registers.  Consecutive lanes
 // = consecutive units: every load / store instruction of a wavefront covers one contiguous 1 KB run of a row.
 //
-// Compiles for the host as well (tests/emul/resamp_emul.cpp runs every thread of a launch against the double-precision definition).
+// The wideband receiver (tetra_wbrx.hip) runs the same thread code over a channeliser's full rows and keeps only the carriers' bins
+// (PickColumns below): every output float is the same fma chain over the same coefficients as the full resampler's, so a picked
+// column equals that column of the full resampler bit for bit.
+//
+// Compiles for the host as well (tests/emul/resamp_emul.cpp runs every thread of a launch against the double-precision definition,
+// tests/emul/resamp_select_emul.cpp the picking variant against the full one).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -62,8 +67,38 @@ template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row_at(const 
     return reinterpret_cast<const V*>(c.x)[(rel < c.n_in ? rel : c.n_in - 1) * stride + u];
 }
 
+// Which input column a lane unit reads.  A column map hands each lane a `lane` object whose row() reads the lane's unit of a row.
+// AllColumns (the resampler, tetra_resamp.hip): unit u of rows of c.units units, in the new frames, the delay line and the output.
+struct AllColumns {
+    RESAMP_HD AllColumns lane(const Ctx&, int) const { return *this; }
+    template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row(const Ctx& c, long long rel, int u, int T) const {
+        return row_at<W, CAREFUL>(c, rel, u, T);
+    }
+};
+// PickColumns (the wideband receiver, tetra_wbrx.hip): the new frames are a channeliser's rows of in_units units, of which unit u
+// reads column col[u] (one channel per unit: W = 2); the delay line and the output hold the picked columns only (rows of c.units =
+// the number of picked columns), unit u.
+struct PickedLane {
+    long long stride;      // units per row of the new frames
+    int col;               // the lane's column in them
+    template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row(const Ctx& c, long long rel, int u, int T) const {
+        using V = typename unit_of<W>::type;
+        if (!CAREFUL) return reinterpret_cast<const V*>(c.x)[rel * stride + col];
+        if (rel < 0) {
+            const long long k = (T - 1) + rel;
+            return reinterpret_cast<const V*>(c.hist)[(k < 0 ? 0 : k) * (long long)c.units + u];
+        }
+        return reinterpret_cast<const V*>(c.x)[(rel < c.n_in ? rel : c.n_in - 1) * stride + col];
+    }
+};
+struct PickColumns {
+    const int* col;        // [c.units], each in [0, in_units)
+    int in_units;
+    RESAMP_HD PickedLane lane(const Ctx&, int u) const { return PickedLane{(long long)in_units, col[u]}; }
+};
+
 // One group of I outputs (absolute group G, i.e. outputs I G .. I G + I - 1) for lane unit u.
-template <int I, int DN, int T, int W, bool CAREFUL> RESAMP_HD void group_t(const Ctx& c, long long G, int u) {
+template <int I, int DN, int T, int W, bool CAREFUL, class Lane> RESAMP_HD void group_t(const Ctx& c, long long G, int u, const Lane& lane) {
     RESAMP_FP_FAST
     using V = typename unit_of<W>::type;
     constexpr int kQmax = (DN * (I - 1)) / I;            // newest row the group's last output reads
@@ -71,7 +106,7 @@ template <int I, int DN, int T, int W, bool CAREFUL> RESAMP_HD void group_t(cons
     const long long base = (long long)DN * G - c.n0;      // row DN G counted from the call's first new frame
     V rows[kRows];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) rows[k] = row_at<W, CAREFUL>(c, base + (k - (T - 1)), u, T);
+    for (int k = 0; k < kRows; k++) rows[k] = lane.template row<W, CAREFUL>(c, base + (k - (T - 1)), u, T);
     V* const out = reinterpret_cast<V*>(c.out);
 #pragma unroll
     for (int i = 0; i < I; i++) {
@@ -105,18 +140,19 @@ template <int I, int DN, int T> RESAMP_HD bool group_is_careful(const Ctx& c, lo
 
 // Thread t of the launch: groups G0 .. of the call x units, flattened (a wavefront may straddle two groups: the coefficients do not
 // depend on the group, so they stay wave-uniform).
-template <int I, int DN, int T, int W> RESAMP_HD void thread_fixed(const Ctx& c, long long t) {
+template <int I, int DN, int T, int W, class Cols = AllColumns> RESAMP_HD void thread_fixed(const Ctx& c, long long t, const Cols& cols = Cols()) {
     const long long G0 = c.m0 / I, G1 = (c.m1 + I - 1) / I;         // groups [G0, G1) hold the call's outputs
     const long long g = t / c.units;
     const int u = (int)(t - g * c.units);
     const long long G = G0 + g;
     if (G >= G1) return;
-    if (group_is_careful<I, DN, T>(c, G)) group_t<I, DN, T, W, true>(c, G, u);
-    else group_t<I, DN, T, W, false>(c, G, u);
+    const auto lane = cols.lane(c, u);
+    if (group_is_careful<I, DN, T>(c, G)) group_t<I, DN, T, W, true>(c, G, u, lane);
+    else group_t<I, DN, T, W, false>(c, G, u, lane);
 }
 
 // Any ratio, any length (run-time I, DN, T): one output per (thread, unit); coefficients from the prototype in memory.
-template <int W> RESAMP_HD void thread_generic(const Ctx& c, long long t) {
+template <int W, class Cols = AllColumns> RESAMP_HD void thread_generic(const Ctx& c, long long t, const Cols& cols = Cols()) {
     RESAMP_FP_FAST
     using V = typename unit_of<W>::type;
     const long long k = t / c.units;
@@ -125,12 +161,13 @@ template <int W> RESAMP_HD void thread_generic(const Ctx& c, long long t) {
     if (m >= c.m1) return;
     const long long q = ((long long)c.DN * m) / c.I;
     const int r = (int)((long long)c.DN * m - q * c.I);
+    const auto lane = cols.lane(c, u);
     float acc[W];
 #pragma unroll
     for (int w = 0; w < W; w++) acc[w] = 0.f;
     for (int j = c.T - 1; j >= 0; j--) {
         const float h = c.coef[r + c.I * j];
-        const V xv = row_at<W, true>(c, q - j - c.n0, u, c.T);
+        const V xv = lane.template row<W, true>(c, q - j - c.n0, u, c.T);
 #pragma unroll
         for (int w = 0; w < W; w++) acc[w] += h * xv.v[w];
     }

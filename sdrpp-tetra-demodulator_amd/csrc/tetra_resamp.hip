@@ -15,6 +15,7 @@
 #include "../../include/tetra_chan.h"
 #include "hip_host.hpp"
 #include "resamp_core.hpp"
+#include "resamp_handle.hpp"
 
 namespace {
 
@@ -39,26 +40,55 @@ template <int W> __global__ __launch_bounds__(kThreads) void k_resample_generic(
     resamp::thread_generic<W>(c, b * kThreads + threadIdx.x);
 }
 
-typedef void (*fixed_kernel_t)(resamp::Ctx, int, long long);
-
-template <int I, int DN, int T> fixed_kernel_t pick_w(int W) {
-    return W == 4 ? (fixed_kernel_t)k_resample<I, DN, T, 4> : (fixed_kernel_t)k_resample<I, DN, T, 2>;
+// The same two kernels over picked columns (the wideband receiver's carriers): one channel per lane unit, read from column
+// cols.col[u] of the channeliser's rows.
+template <int I, int DN, int T> __global__ __launch_bounds__(kThreads) void k_resample_pick(resamp::Ctx c, resamp::PickColumns cols, int span,
+                                                                                         long long blocks) {
+    const long long b = remapped_block(span);
+    if (b >= blocks) return;
+    resamp::thread_fixed<I, DN, T, 2>(c, b * kThreads + threadIdx.x, cols);
 }
 
-fixed_kernel_t pick_fixed(int I, int DN, int T, int W) {
+__global__ __launch_bounds__(kThreads) void k_resample_pick_generic(resamp::Ctx c, resamp::PickColumns cols, int span, long long blocks) {
+    const long long b = remapped_block(span);
+    if (b >= blocks) return;
+    resamp::thread_generic<2>(c, b * kThreads + threadIdx.x, cols);
+}
+
+// rows [first, first + rows) of frames [*][in_ch], columns cols[0 .. n) -> out [rows][n] (the picked delay line)
+__global__ __launch_bounds__(256) void k_pick_rows(const float2* __restrict__ in, int in_ch, const int32_t* __restrict__ cols, int n,
+                                                   long long first, int rows, float2* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)rows * n) return;
+    const long long r = i / n;
+    const int j = (int)(i - r * n);
+    out[i] = in[(first + r) * in_ch + cols[j]];
+}
+
+template <int I, int DN, int T> struct FullKernel {
+    static fixed_kernel_t get(int W) { return W == 4 ? (fixed_kernel_t)k_resample<I, DN, T, 4> : (fixed_kernel_t)k_resample<I, DN, T, 2>; }
+};
+template <int I, int DN, int T> struct PickKernel {
+    static pick_kernel_t get() { return (pick_kernel_t)k_resample_pick<I, DN, T>; }
+};
+
+// K<I, DN, T>::get(a...) for the ratios and lengths that have a kernel specialised at compile time, nullptr for any other
+template <template <int, int, int> class K, class... A> auto pick_ratio(int I, int DN, int T, A... a) -> decltype(K<18, 25, 8>::get(a...)) {
     if (I == 18 && DN == 25) {
-        if (T == 8) return pick_w<18, 25, 8>(W);
-        if (T == 12) return pick_w<18, 25, 12>(W);
-        if (T == 16) return pick_w<18, 25, 16>(W);
-        if (T == 24) return pick_w<18, 25, 24>(W);
+        if (T == 8) return K<18, 25, 8>::get(a...);
+        if (T == 12) return K<18, 25, 12>::get(a...);
+        if (T == 16) return K<18, 25, 16>::get(a...);
+        if (T == 24) return K<18, 25, 24>::get(a...);
     }
     if (T == 8) {
-        if (I == 2 && DN == 3) return pick_w<2, 3, 8>(W);
-        if (I == 3 && DN == 2) return pick_w<3, 2, 8>(W);
-        if (I == 1 && DN == 2) return pick_w<1, 2, 8>(W);
+        if (I == 2 && DN == 3) return K<2, 3, 8>::get(a...);
+        if (I == 3 && DN == 2) return K<3, 2, 8>::get(a...);
+        if (I == 1 && DN == 2) return K<1, 2, 8>::get(a...);
     }
     return nullptr;
 }
+
+fixed_kernel_t pick_fixed(int I, int DN, int T, int W) { return pick_ratio<FullKernel>(I, DN, T, W); }
 
 double bessel_i0(double x) {
     double s = 1.0, t = 1.0;
@@ -91,28 +121,76 @@ void design_prototype(int I, int DN, int T, double cutoff_rel, double beta, std:
 
 }  // namespace
 
-struct tetra_resamp {
-    tetra_resamp_config_t cfg;
-    int device = 0, last_hip = 0;
-    int C = 0, I = 0, DN = 0, T = 0, W = 4, units = 0, max_in = 0;
-    std::vector<float> proto;
-    fixed_kernel_t fixed = nullptr;
-    DevMem<float> d_coef;        // [I][T] phase table (fixed kernel) or the prototype (generic)
-    DevMem<float> hist;          // [T - 1][2 C]: the frames before the next call's first
-    DevMem<float> halt;          // same size: receives the next call's delay line, then the two swap roles
-    long long n_total = 0;       // frames consumed so far
-    long long m_next = 0;        // outputs emitted so far
-    DevMem<float> st_in;         // host-path staging
-    DevMem<float> st_out;
-    Event ev[2];
-    bool ev_valid = false;
-};
 
 namespace {
 
 size_t hist_bytes(const tetra_resamp* h) { return sizeof(float) * 2 * (size_t)h->C * (size_t)(h->T - 1); }
 
+// One call's kernel and delay-line carry.  d_cols = nullptr: every column in place (in_ch = C); else the C picked columns of rows of
+// in_ch channels.  The arguments are checked by the caller.
+int process_any(tetra_resamp* h, const int32_t* d_cols, int in_ch, const float* d_in, int n_in, float* d_out, int* n_out, hipStream_t s) {
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    const long long m1 = resamp::outputs_after(h->n_total + n_in, h->I, h->DN);
+    const long long n_new = m1 - h->m_next;
+    *n_out = (int)n_new;
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    if (n_new > 0) {
+        resamp::Ctx c;
+        c.x = d_in; c.hist = h->hist; c.out = d_out; c.coef = h->d_coef;
+        c.n0 = h->n_total; c.m0 = h->m_next; c.m1 = m1; c.n_in = n_in; c.units = h->units;
+        c.I = h->I; c.DN = h->DN; c.T = h->T;
+        long long threads;
+        if (d_cols ? h->pick != nullptr : h->fixed != nullptr) threads = ((m1 + h->I - 1) / h->I - h->m_next / h->I) * (long long)h->units;
+        else threads = n_new * (long long)h->units;
+        const long long blocks = (threads + kThreads - 1) / kThreads;
+        const int span = (int)((blocks + 7) / 8);
+        if (d_cols) {
+            resamp::PickColumns cols;
+            cols.col = d_cols; cols.in_units = in_ch;
+            if (h->pick) hipLaunchKernelGGL(h->pick, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
+            else hipLaunchKernelGGL(k_resample_pick_generic, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
+        } else if (h->fixed) hipLaunchKernelGGL(h->fixed, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
+        else if (h->W == 4) hipLaunchKernelGGL(k_resample_generic<4>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
+        else hipLaunchKernelGGL(k_resample_generic<2>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    h->ev_valid = true;
+    // carry: the last T - 1 frames of [delay line | new] (their picked columns) become the next call's delay line -- into the OTHER
+    // buffer (an in-place move would overlap for n_in < T - 1), then the two swap roles.  Stream order keeps the kernel ahead of the copies.
+    if (n_in > 0) {
+        const size_t row = sizeof(float) * 2 * (size_t)h->C, hist = (size_t)h->T - 1;
+        const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
+        if (keep) HIP_TRY(h, hipMemcpyAsync(h->halt, (const char*)h->hist.get() + row * (size_t)n_in, row * keep, hipMemcpyDeviceToDevice, s));
+        if (d_cols) {
+            const long long n = (long long)from_x * h->C;
+            hipLaunchKernelGGL(k_pick_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float2*>(d_in), in_ch, d_cols, h->C,
+                               (long long)n_in - (long long)from_x, (int)from_x, reinterpret_cast<float2*>(h->halt.get() + 2 * (size_t)h->C * keep));
+            HIP_TRY(h, hipGetLastError());
+        } else {
+            HIP_TRY(h, hipMemcpyAsync((char*)h->halt.get() + row * keep, (const char*)d_in + row * ((size_t)n_in - from_x), row * from_x,
+                                     hipMemcpyDeviceToDevice, s));
+        }
+        std::swap(h->hist, h->halt);
+    }
+    h->n_total += n_in;
+    h->m_next = m1;
+    return TETRA_OK;
+}
+
 }  // namespace
+
+namespace resamp_impl {
+
+int process_pick_device(tetra_resamp_t* h, const int32_t* d_cols, int in_ch, const float* d_in, int n_in, float* d_out, int* n_out, hipStream_t s) {
+    if (!h || !d_cols || in_ch < 1 || (!d_in && n_in > 0) || !d_out || !n_out || h->W != 2) return TETRA_ERR_ARG;
+    if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
+    if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 7)) return TETRA_ERR_ALIGN;
+    return process_any(h, d_cols, in_ch, d_in, n_in, d_out, n_out, s);
+}
+
+}  // namespace resamp_impl
 
 extern "C" {
 
@@ -155,6 +233,7 @@ int tetra_resamp_create(const tetra_resamp_config_t* cfg, tetra_resamp_t** out) 
     if (cfg->prototype) h->proto.assign(cfg->prototype, cfg->prototype + (size_t)h->I * h->T);
     else design_prototype(h->I, h->DN, h->T, cfg->cutoff_rel, cfg->kaiser_beta, h->proto);
     h->fixed = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_fixed(h->I, h->DN, h->T, h->W);
+    h->pick = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_ratio<PickKernel>(h->I, h->DN, h->T);
     DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     std::vector<float> coef((size_t)h->I * h->T);
@@ -190,43 +269,7 @@ int tetra_resamp_process_device(tetra_resamp_t* h, const float* d_in, int n_in, 
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
     const size_t amask = h->W == 4 ? 15 : 7;
     if (((uintptr_t)d_in & amask) || ((uintptr_t)d_out & amask)) return TETRA_ERR_ALIGN;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)hip_stream;
-    const long long m1 = resamp::outputs_after(h->n_total + n_in, h->I, h->DN);
-    const long long n_new = m1 - h->m_next;
-    *n_out = (int)n_new;
-    HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    if (n_new > 0) {
-        resamp::Ctx c;
-        c.x = d_in; c.hist = h->hist; c.out = d_out; c.coef = h->d_coef;
-        c.n0 = h->n_total; c.m0 = h->m_next; c.m1 = m1; c.n_in = n_in; c.units = h->units;
-        c.I = h->I; c.DN = h->DN; c.T = h->T;
-        long long threads;
-        if (h->fixed) threads = ((m1 + h->I - 1) / h->I - h->m_next / h->I) * (long long)h->units;
-        else threads = n_new * (long long)h->units;
-        const long long blocks = (threads + kThreads - 1) / kThreads;
-        const int span = (int)((blocks + 7) / 8);
-        if (h->fixed) hipLaunchKernelGGL(h->fixed, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
-        else if (h->W == 4) hipLaunchKernelGGL(k_resample_generic<4>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
-        else hipLaunchKernelGGL(k_resample_generic<2>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    h->ev_valid = true;
-    // carry: the last T - 1 frames of [delay line | new] become the next call's delay line -- into the OTHER buffer (an in-place
-    // move would overlap for n_in < T - 1), then the two swap roles.  Stream order keeps the kernel ahead of the copies.
-    if (n_in > 0) {
-        const size_t row = sizeof(float) * 2 * (size_t)h->C, hist = (size_t)h->T - 1;
-        const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
-        if (keep) HIP_TRY(h, hipMemcpyAsync(h->halt, (const char*)h->hist.get() + row * (size_t)n_in, row * keep, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync((char*)h->halt.get() + row * keep, (const char*)d_in + row * ((size_t)n_in - from_x), row * from_x,
-                                 hipMemcpyDeviceToDevice, s));
-        std::swap(h->hist, h->halt);
-    }
-    h->n_total += n_in;
-    h->m_next = m1;
-    return TETRA_OK;
+    return process_any(h, nullptr, h->C, d_in, n_in, d_out, n_out, (hipStream_t)hip_stream);
 }
 
 int tetra_resamp_process(tetra_resamp_t* h, const float* in, int n_in, float* out, int* n_out) {

@@ -1,0 +1,301 @@
+// tetra_wbrx.hip -- the wideband receiver behind one handle (include/tetra_wbrx.h): one capture in, the receive chain's blocks per
+// carrier out.  Per call k, all on the caller's stream:
+//
+//   [wait: call k - 1 is through]  channeliser (tetra_chan) -> chan_out [nf][M]                                   (event C_k)
+//                                  selecting resampler: the carriers' columns of chan_out -> res[k & 1] [n][n_bins]  (event R_k)
+//                                  tetra_rx_process_device(res[k & 1], n): demodulator here, the chain's tail on its own stream
+//
+// The resampler's state (delay line of the picked columns, positions) is a tetra_resamp handle created for n_bins channels with
+// one channel per lane unit; resamp_impl::process_pick_device runs its kernels over picked columns (resamp_core.hpp, PickColumns).
+// A bin list 0 .. M - 1 in order runs the resampler in place on the full rows instead.  The resampled frames are double buffered by
+// call parity like the chain's bit rows, so tetra_wbrx_frames_device can hand out the previous call's too.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "../../include/tetra_wbrx.h"
+#include "hip_host.hpp"
+#include "resamp_handle.hpp"
+
+namespace {
+
+constexpr int kPowerSplits = 4096;      // at most this many frame ranges per bin in the first pass of the bin power
+constexpr int kPowerMinFrames = 64;     // and at least this many frames in each
+
+// Partial sums of |X_k|^2 over frames [y F, y F + F) of x [nf][M]: one lane per bin (a row's reads are coalesced), float64 sums.
+__global__ __launch_bounds__(256) void k_bin_power_part(const float2* __restrict__ x, int M, int nf, int F, double* __restrict__ part) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= M) return;
+    const int f0 = blockIdx.y * F, f1 = f0 + F < nf ? f0 + F : nf;
+    double s = 0.0;
+    for (int f = f0; f < f1; f++) {
+        const float2 v = x[(size_t)f * M + k];
+        s += (double)v.x * v.x + (double)v.y * v.y;
+    }
+    part[(size_t)blockIdx.y * M + k] = s;
+}
+
+// out[k] = (sum of the partial sums of bin k) / nf
+__global__ __launch_bounds__(256) void k_bin_power_sum(const double* __restrict__ part, int M, int splits, int nf, float* __restrict__ out) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= M) return;
+    double s = 0.0;
+    for (int j = 0; j < splits; j++) s += part[(size_t)j * M + k];
+    out[k] = (float)(s / (double)nf);
+}
+
+template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
+
+enum { kFmtC32 = 0, kFmtCs16 = 1, kFmtCs8 = 2 };
+constexpr size_t kFmtBytes[3] = { 8, 4, 2 };
+
+}  // namespace
+
+struct tetra_wbrx {
+    tetra_wbrx_config_t cfg;
+    int device = 0, last_hip = 0;
+    int M = 0, n_bins = 0, max_in = 0, max_chan = 0, max_res = 0;
+    bool all = false;                       // bins = 0 .. M - 1 in order: the resampler runs in place on the full rows
+    std::vector<int32_t> bins;
+    Handle<tetra_chan_t*, tetra_chan_destroy> chan;
+    Handle<tetra_resamp_t*, tetra_resamp_destroy> rs;
+    Handle<tetra_rx_t*, tetra_rx_destroy> rx;
+    DevMem<int32_t> d_bins;                 // [n_bins]
+    DevMem<float> chan_out;                 // [max_chan][M] complex64: the latest call's channeliser frames
+    DevMem<float> res[2];                   // per call parity: [max_res][n_bins] complex64, the resampled carriers
+    int n_res[2] = { 0, 0 };
+    int n_chan = 0;                         // channeliser frames of the latest call
+    Event ev_chan, ev_res[2], ev_done;
+    long long calls = 0;
+    Stream aux;                             // tetra_wbrx_bin_power (created on first use, with its buffers)
+    DevMem<double> pw_part;
+    DevMem<float> pw_out;
+    DevMem<uint8_t> st_x;                   // host-path staging
+};
+
+namespace {
+
+int process_any(tetra_wbrx* h, int fmt, const void* d_x, int n_in, void* hip_stream) {
+    if (!h || (!d_x && n_in > 0)) return TETRA_ERR_ARG;
+    if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
+    if ((uintptr_t)d_x & (kFmtBytes[fmt] - 1)) return TETRA_ERR_ALIGN;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int b = (int)(h->calls & 1);
+    // chan_out was read by the previous call's resampler and res[b] by the demodulator two calls back (which the previous call
+    // waited for in turn): on another stream, wait for them
+    if (h->calls > 0) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+    int nf = 0, nr = 0;
+    if (fmt == kFmtCs16) TETRA_TRY(tetra_chan_process_device_cs16(h->chan, static_cast<const int16_t*>(d_x), n_in, h->chan_out, &nf, s));
+    else if (fmt == kFmtCs8) TETRA_TRY(tetra_chan_process_device_cs8(h->chan, static_cast<const int8_t*>(d_x), n_in, h->chan_out, &nf, s));
+    else TETRA_TRY(tetra_chan_process_device(h->chan, static_cast<const float*>(d_x), n_in, h->chan_out, &nf, s));
+    HIP_TRY(h, hipEventRecord(h->ev_chan, s));
+    if (h->all) TETRA_TRY(tetra_resamp_process_device(h->rs, h->chan_out, nf, h->res[b], &nr, s));
+    else TETRA_TRY(resamp_impl::process_pick_device(h->rs, h->d_bins, h->M, h->chan_out, nf, h->res[b], &nr, s));
+    HIP_TRY(h, hipEventRecord(h->ev_res[b], s));
+    h->n_chan = nf;
+    h->n_res[b] = nr;
+    h->calls++;
+    TETRA_TRY(tetra_rx_process_device(h->rx, h->res[b], nr, s));
+    HIP_TRY(h, hipEventRecord(h->ev_done, s));
+    return TETRA_OK;
+}
+
+int process_host(tetra_wbrx* h, int fmt, const void* x, int n_in) {
+    if (!h || (!x && n_in > 0)) return TETRA_ERR_ARG;
+    if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    if (h->st_x.reserve(kFmtBytes[fmt] * (size_t)h->max_in) != hipSuccess) return TETRA_ERR_NOMEM;
+    // the staging buffer is read by the previous call's channeliser (and its delay-line copy): wait for it before overwriting
+    HIP_TRY(h, hipStreamSynchronize(nullptr));
+    if (n_in > 0) HIP_TRY(h, hipMemcpy(h->st_x, x, kFmtBytes[fmt] * (size_t)n_in, hipMemcpyHostToDevice));
+    return process_any(h, fmt, h->st_x, n_in, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tetra_wbrx_default_config(tetra_wbrx_config_t* cfg) {
+    if (!cfg) return TETRA_ERR_ARG;
+    std::memset(cfg, 0, sizeof(*cfg));
+    TETRA_TRY(tetra_chan_default_config(&cfg->chan));
+    tetra_resamp_config_t rc;
+    TETRA_TRY(tetra_resamp_default_config(&rc));
+    cfg->interp = rc.interp;
+    cfg->decim = rc.decim;
+    cfg->taps_per_phase = rc.taps_per_phase;
+    cfg->resamp_cutoff_rel = rc.cutoff_rel;
+    cfg->resamp_kaiser_beta = rc.kaiser_beta;
+    TETRA_TRY(tetra_rx_default_config(&cfg->rx));
+    cfg->rx.demod.n_channels = 0;             // filled in by the handle
+    cfg->rx.demod.max_samples = 0;
+    cfg->rx.demod.layout = TETRA_LAYOUT_TIME_MAJOR;
+    return TETRA_OK;
+}
+
+int tetra_wbrx_create(const tetra_wbrx_config_t* cfg, tetra_wbrx_t** out) {
+    if (!cfg || !out) return TETRA_ERR_ARG;
+    *out = nullptr;
+    const int M = cfg->chan.n_channels, D = cfg->chan.decimation, nb = cfg->n_bins;
+    if (M < 1 || D < 1 || cfg->chan.max_in < 1 || nb < 1 || nb > M || !cfg->bins || cfg->interp < 1 || cfg->decim < 1) return TETRA_ERR_ARG;
+    std::vector<char> seen((size_t)M, 0);
+    for (int j = 0; j < nb; j++) {
+        const int k = cfg->bins[j];
+        if (k < 0 || k >= M || seen[(size_t)k]) return TETRA_ERR_ARG;
+        seen[(size_t)k] = 1;
+    }
+    // the most frames one call can bring: channeliser (its sub-frame phase carries up to D - 1 samples), then the resampler
+    const long long max_chan = ((long long)D - 1 + cfg->chan.max_in) / D;
+    const long long max_res = max_chan * cfg->interp / cfg->decim + 1;
+    if (max_res > 0x7fffffffLL) return TETRA_ERR_SIZE;
+    const tetra_demod_config_t& dc = cfg->rx.demod;
+    if ((dc.n_channels != 0 && dc.n_channels != nb) || (dc.layout != 0 && dc.layout != TETRA_LAYOUT_TIME_MAJOR) ||
+        (dc.max_samples != 0 && dc.max_samples != (int32_t)max_res))
+        return TETRA_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
+    int dev = cfg->chan.device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return TETRA_ERR_NO_DEVICE;
+    if (dev >= ndev) return TETRA_ERR_NO_DEVICE;
+    if (dc.device >= 0 && dc.device != dev) return TETRA_ERR_ARG;
+    std::unique_ptr<tetra_wbrx> h(new (std::nothrow) tetra_wbrx());      // everything it holds is released on every failure below
+    if (!h) return TETRA_ERR_NOMEM;
+    h->cfg = *cfg;
+    h->bins.assign(cfg->bins, cfg->bins + nb);
+    h->cfg.bins = nullptr;
+    h->cfg.chan.prototype = nullptr;
+    h->device = dev;
+    h->M = M; h->n_bins = nb; h->max_in = cfg->chan.max_in; h->max_chan = (int)max_chan; h->max_res = (int)max_res;
+    h->all = nb == M;
+    for (int j = 0; j < nb && h->all; j++) h->all = h->bins[(size_t)j] == j;
+    DeviceGuard g(dev);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+
+    tetra_chan_config_t cc = cfg->chan;
+    cc.device = dev;
+    TETRA_TRY(tetra_chan_create(&cc, h->chan.put()));
+    tetra_resamp_config_t rc;
+    TETRA_TRY(tetra_resamp_default_config(&rc));
+    rc.n_channels = h->all ? M : nb;
+    rc.interp = cfg->interp; rc.decim = cfg->decim; rc.taps_per_phase = cfg->taps_per_phase;
+    rc.max_in = h->max_chan > 0 ? h->max_chan : 1;
+    rc.device = dev;
+    rc.flags = h->all ? 0 : TETRA_RESAMP_FLAG_NARROW_UNITS;          // picked columns: one channel per lane unit
+    rc.cutoff_rel = cfg->resamp_cutoff_rel; rc.kaiser_beta = cfg->resamp_kaiser_beta;
+    TETRA_TRY(tetra_resamp_create(&rc, h->rs.put()));
+    tetra_rx_config_t xc = cfg->rx;
+    xc.demod.n_channels = nb;
+    xc.demod.layout = TETRA_LAYOUT_TIME_MAJOR;
+    xc.demod.max_samples = h->max_res;
+    xc.demod.device = dev;
+    TETRA_TRY(tetra_rx_create(&xc, h->rx.put()));
+
+    const size_t row = 2 * (size_t)nb;
+    bool ok = dalloc(h->d_bins, (size_t)nb) && dalloc(h->chan_out, 2 * (size_t)M * (size_t)h->max_chan) &&
+              dalloc(h->res[0], row * (size_t)h->max_res) && dalloc(h->res[1], row * (size_t)h->max_res) &&
+              hipEventCreateWithFlags(h->ev_chan.put(), hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(h->ev_res[0].put(), hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(h->ev_res[1].put(), hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(h->ev_done.put(), hipEventDisableTiming) == hipSuccess;
+    if (!ok) return TETRA_ERR_NOMEM;
+    HIP_TRY(h.get(), hipMemcpy(h->d_bins, h->bins.data(), sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice));
+    *out = h.release();
+    return TETRA_OK;
+}
+
+int tetra_wbrx_destroy(tetra_wbrx_t* h) {
+    if (!h) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    (void)hipDeviceSynchronize();
+    delete h;
+    return TETRA_OK;
+}
+
+int tetra_wbrx_reset(tetra_wbrx_t* h) {
+    if (!h) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipDeviceSynchronize());
+    TETRA_TRY(tetra_chan_reset(h->chan));
+    TETRA_TRY(tetra_resamp_reset(h->rs));
+    TETRA_TRY(tetra_rx_reset(h->rx));
+    h->calls = 0;
+    h->n_chan = 0;
+    h->n_res[0] = h->n_res[1] = 0;
+    return TETRA_OK;
+}
+
+int tetra_wbrx_process_device(tetra_wbrx_t* h, const float* d_x, int n_in, void* hip_stream) {
+    return process_any(h, kFmtC32, d_x, n_in, hip_stream);
+}
+int tetra_wbrx_process_device_cs16(tetra_wbrx_t* h, const int16_t* d_x, int n_in, void* hip_stream) {
+    return process_any(h, kFmtCs16, d_x, n_in, hip_stream);
+}
+int tetra_wbrx_process_device_cs8(tetra_wbrx_t* h, const int8_t* d_x, int n_in, void* hip_stream) {
+    return process_any(h, kFmtCs8, d_x, n_in, hip_stream);
+}
+int tetra_wbrx_process(tetra_wbrx_t* h, const float* x, int n_in) { return process_host(h, kFmtC32, x, n_in); }
+int tetra_wbrx_process_cs16(tetra_wbrx_t* h, const int16_t* x, int n_in) { return process_host(h, kFmtCs16, x, n_in); }
+
+tetra_rx_t* tetra_wbrx_rx(tetra_wbrx_t* h) { return h ? (tetra_rx_t*)h->rx : nullptr; }
+
+int tetra_wbrx_bins(tetra_wbrx_t* h, int32_t* out) {
+    if (!h || !out) return TETRA_ERR_ARG;
+    std::memcpy(out, h->bins.data(), sizeof(int32_t) * h->bins.size());
+    return TETRA_OK;
+}
+
+int tetra_wbrx_frames_device(tetra_wbrx_t* h, int which, const float** d_frames, int* n_frames, void* hip_stream) {
+    if (!h || !d_frames || !n_frames || which < 0 || which > 1) return TETRA_ERR_ARG;
+    *d_frames = nullptr;
+    *n_frames = 0;
+    if (h->calls <= which) return TETRA_OK;
+    const int b = (int)((h->calls - 1 - which) & 1);
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_res[b], 0));
+    *d_frames = h->res[b];
+    *n_frames = h->n_res[b];
+    return TETRA_OK;
+}
+
+int tetra_wbrx_bin_power(tetra_wbrx_t* h, float* out) {
+    if (!h || !out) return TETRA_ERR_ARG;
+    const int nf = h->calls > 0 ? h->n_chan : 0, M = h->M;
+    if (nf == 0) {
+        std::memset(out, 0, sizeof(float) * (size_t)M);
+        return TETRA_OK;
+    }
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    int F = (nf + kPowerSplits - 1) / kPowerSplits;
+    if (F < kPowerMinFrames) F = kPowerMinFrames;
+    const int splits = (nf + F - 1) / F;
+    if (!h->aux) HIP_TRY(h, hipStreamCreateWithFlags(h->aux.put(), hipStreamNonBlocking));
+    HIP_TRY(h, h->pw_part.reserve(sizeof(double) * (size_t)splits * (size_t)M));
+    HIP_TRY(h, h->pw_out.reserve(sizeof(float) * (size_t)M));
+    HIP_TRY(h, hipStreamWaitEvent(h->aux, h->ev_chan, 0));
+    const unsigned gx = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(k_bin_power_part, dim3(gx, (unsigned)splits), dim3(256), 0, h->aux, reinterpret_cast<const float2*>(h->chan_out.get()), M,
+                       nf, F, h->pw_part);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_bin_power_sum, dim3(gx), dim3(256), 0, h->aux, h->pw_part, M, splits, nf, h->pw_out);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->pw_out, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, h->aux));
+    HIP_TRY(h, hipStreamSynchronize(h->aux));
+    return TETRA_OK;
+}
+
+int tetra_wbrx_stage_ms(tetra_wbrx_t* h, float ms[2]) {
+    if (!h || !ms || h->calls == 0) return TETRA_ERR_ARG;
+    TETRA_TRY(tetra_chan_last_kernel_ms(h->chan, &ms[0]));
+    return tetra_resamp_last_kernel_ms(h->rs, &ms[1]);
+}
+
+}  // extern "C"

@@ -1,0 +1,190 @@
+"""ctypes binding of the wideband receiver (include/tetra_wbrx.h): one SDR capture in, the receive chain's blocks per carrier out."""
+import ctypes as C
+
+import numpy as np
+
+from . import binding as B
+from .binding import TetraDemodError, load_library
+from .chan_binding import ChanConfig
+from .rx_binding import RxChain, RxConfig, _stream_ptr
+from .rx_binding import _lib as _rx_lib
+
+WBRX_EXPORTS = ["tetra_wbrx_default_config", "tetra_wbrx_create", "tetra_wbrx_destroy", "tetra_wbrx_reset", "tetra_wbrx_process_device",
+                "tetra_wbrx_process_device_cs16", "tetra_wbrx_process_device_cs8", "tetra_wbrx_process", "tetra_wbrx_process_cs16",
+                "tetra_wbrx_rx", "tetra_wbrx_bins", "tetra_wbrx_frames_device", "tetra_wbrx_bin_power", "tetra_wbrx_stage_ms"]
+
+
+class WbrxConfig(C.Structure):
+    _fields_ = [("chan", ChanConfig), ("interp", C.c_int32), ("decim", C.c_int32), ("taps_per_phase", C.c_int32), ("n_bins", C.c_int32),
+                ("resamp_cutoff_rel", C.c_double), ("resamp_kaiser_beta", C.c_double), ("bins", C.c_void_p), ("rx", RxConfig)]
+
+
+_ready = False
+
+
+def _lib():
+    global _ready
+    L = load_library()
+    if not _ready:
+        vp, i32 = C.c_void_p, C.c_int
+        L.tetra_wbrx_default_config.argtypes = [C.POINTER(WbrxConfig)]
+        L.tetra_wbrx_create.argtypes = [C.POINTER(WbrxConfig), C.POINTER(vp)]
+        L.tetra_wbrx_destroy.argtypes = [vp]
+        L.tetra_wbrx_reset.argtypes = [vp]
+        for n in ("tetra_wbrx_process_device", "tetra_wbrx_process_device_cs16", "tetra_wbrx_process_device_cs8"):
+            getattr(L, n).argtypes = [vp, vp, i32, vp]
+        L.tetra_wbrx_process.argtypes = [vp, vp, i32]
+        L.tetra_wbrx_process_cs16.argtypes = [vp, vp, i32]
+        L.tetra_wbrx_rx.argtypes = [vp]
+        L.tetra_wbrx_rx.restype = vp
+        L.tetra_wbrx_bins.argtypes = [vp, vp]
+        L.tetra_wbrx_frames_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), vp]
+        L.tetra_wbrx_bin_power.argtypes = [vp, vp]
+        L.tetra_wbrx_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 2)]
+        for n in WBRX_EXPORTS:
+            if n != "tetra_wbrx_rx":
+                getattr(L, n).restype = i32
+        _ready = True
+    return L
+
+
+def default_config():
+    cfg = WbrxConfig()
+    rc = _lib().tetra_wbrx_default_config(C.byref(cfg))
+    if rc:
+        raise TetraDemodError(rc, "tetra_wbrx_default_config")
+    return cfg
+
+
+class _ChainView(RxChain):
+    """The chain inside a WidebandRx (tetra_wbrx_rx): every RxChain reader (fetch, cells, sync_states, stage_ms, rows_device,
+    bits_device, deliver ...) as it is.  It does not own the handle: close() only detaches it, and process / reset are refused --
+    the wideband handle feeds and resets its chain."""
+
+    def __init__(self, handle, n_channels, max_samples):          # (RxChain's owning constructor is not run)
+        self._lib = _rx_lib()
+        self._h = C.c_void_p(handle)
+        self.n_channels, self.max_samples = n_channels, max_samples
+        self.max_rows = int(self._lib.tetra_rx_max_rows(self._h))
+
+    def close(self):
+        self._h = None
+        self._close_pool()
+
+    def reset(self):
+        raise TypeError("the wideband receiver's chain is reset through WidebandRx.reset()")
+
+    def process(self, iq):
+        raise TypeError("the wideband receiver's chain is fed through WidebandRx.process*()")
+
+    process_device = process
+
+
+class _DeviceArray:
+    """A device buffer as __cuda_array_interface__, for torch.as_tensor (no copy)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class WidebandRx:
+    """An SDR capture in, the decoded blocks of the carriers on `bins` out: channeliser (M bins) -> selecting 18 / 25 resampler ->
+    receive chain on one GPU.  `.rx` is the chain (an RxChain view); a block's channel is the carrier's index into `bins`."""
+
+    def __init__(self, bins, n_channels=800, taps_per_channel=8, decimation=None, max_in=1 << 20, device=-1, chan_cutoff_rel=1.2,
+                 chan_flags=0, interp=18, decim=25, taps_per_phase=16, resamp_cutoff_rel=1.0, resamp_kaiser_beta=6.0, kinds=0, flags=0,
+                 demod_flags=0, **params):
+        self._lib = _lib()
+        cfg = default_config()
+        cfg.chan.n_channels, cfg.chan.taps_per_channel = n_channels, taps_per_channel
+        cfg.chan.decimation = decimation if decimation is not None else n_channels // 2
+        cfg.chan.max_in, cfg.chan.device, cfg.chan.cutoff_rel, cfg.chan.reserved = max_in, device, chan_cutoff_rel, chan_flags
+        cfg.interp, cfg.decim, cfg.taps_per_phase = interp, decim, taps_per_phase
+        cfg.resamp_cutoff_rel, cfg.resamp_kaiser_beta = resamp_cutoff_rel, resamp_kaiser_beta
+        keep = np.ascontiguousarray(np.asarray(bins, np.int64).astype(np.int32).reshape(-1))
+        cfg.n_bins = keep.size
+        cfg.bins = keep.ctypes.data if keep.size else None
+        cfg.rx.kinds, cfg.rx.flags, cfg.rx.demod.flags = kinds, flags, demod_flags
+        for k, v in params.items():
+            if k not in B.PARAMS:
+                raise TypeError("unknown parameter %r" % k)
+            setattr(cfg.rx.demod, k, v)
+        self.M, self.D, self.max_in, self.n_bins = n_channels, cfg.chan.decimation, max_in, int(keep.size)
+        h = C.c_void_p()
+        rc = self._lib.tetra_wbrx_create(C.byref(cfg), C.byref(h))
+        if rc:
+            raise TetraDemodError(rc, "tetra_wbrx_create")
+        self._h = h
+        max_samples = int(((self.D - 1 + max_in) // self.D) * interp // decim + 1)
+        self.rx = _ChainView(self._lib.tetra_wbrx_rx(h), self.n_bins, max_samples)
+
+    def close(self):
+        if getattr(self, "rx", None) is not None:
+            self.rx.close()
+        if getattr(self, "_h", None):
+            self._lib.tetra_wbrx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc:
+            raise TetraDemodError(rc, what)
+
+    def reset(self):
+        self._chk(self._lib.tetra_wbrx_reset(self._h), "tetra_wbrx_reset")
+
+    def process(self, x):
+        """Host capture: complex64 [n], or int16 interleaved I / Q ([n][2] or [2 n]) -> tetra_wbrx_process / _process_cs16."""
+        x = np.asarray(x)
+        if x.dtype == np.int16:
+            x = np.ascontiguousarray(x).reshape(-1)
+            self._chk(self._lib.tetra_wbrx_process_cs16(self._h, x.ctypes.data_as(C.c_void_p), x.size // 2), "tetra_wbrx_process_cs16")
+        else:
+            x = np.ascontiguousarray(x, np.complex64).reshape(-1)
+            self._chk(self._lib.tetra_wbrx_process(self._h, x.ctypes.data_as(C.c_void_p), x.size), "tetra_wbrx_process")
+
+    def process_device(self, d_x, n_in=None, stream=None):
+        """Device capture: the entry point follows the tensor's dtype (complex64, or interleaved I / Q pairs int16 / int8, as
+        Channeliser.process_device).  n_in: samples (default: all of the tensor)."""
+        dt = str(getattr(d_x, "dtype", ""))
+        name = {"torch.int16": "tetra_wbrx_process_device_cs16", "torch.int8": "tetra_wbrx_process_device_cs8"}.get(dt, "tetra_wbrx_process_device")
+        if n_in is None:
+            n_in = d_x.numel() // 2 if name != "tetra_wbrx_process_device" else d_x.numel()
+        p = C.c_void_p(d_x.data_ptr() if hasattr(d_x, "data_ptr") else int(d_x))
+        self._chk(getattr(self._lib, name)(self._h, p, int(n_in), _stream_ptr(stream)), name)
+
+    def bins(self):
+        out = np.zeros(max(self.n_bins, 1), np.int32)
+        self._chk(self._lib.tetra_wbrx_bins(self._h, out.ctypes.data_as(C.c_void_p)), "tetra_wbrx_bins")
+        return out[:self.n_bins]
+
+    def frames_device(self, which=0, stream=None):
+        """-> (device pointer, n_frames) of the resampled carrier IQ [n_frames][n_bins] complex64 of the latest (0) / previous (1) call."""
+        p, n = C.c_void_p(), C.c_int(0)
+        self._chk(self._lib.tetra_wbrx_frames_device(self._h, int(which), C.byref(p), C.byref(n), _stream_ptr(stream)), "tetra_wbrx_frames_device")
+        return p.value, n.value
+
+    def frames(self, which=0, stream=None):
+        """The same as a torch tensor [n_frames][n_bins] complex64 on the handle's GPU: a view, valid until the next-but-one call."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        p, n = self.frames_device(which, stream)
+        if n == 0:
+            return torch.zeros((0, self.n_bins), dtype=torch.complex64, device=stream.device)
+        return torch.as_tensor(_DeviceArray(p, (n, self.n_bins), "<c8"), device=stream.device)
+
+    def bin_power(self):
+        out = np.zeros(self.M, np.float32)
+        self._chk(self._lib.tetra_wbrx_bin_power(self._h, out.ctypes.data_as(C.c_void_p)), "tetra_wbrx_bin_power")
+        return out
+
+    def stage_ms(self):
+        ms = (C.c_float * 2)()
+        self._chk(self._lib.tetra_wbrx_stage_ms(self._h, C.byref(ms)), "tetra_wbrx_stage_ms")
+        return [float(v) for v in ms]

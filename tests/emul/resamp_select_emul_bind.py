@@ -1,0 +1,58 @@
+"""ctypes binding of tests/emul/resamp_select_emul.cpp (host emulation of the wideband receiver's selecting resampler; TEST TOOL)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(os.path.dirname(_HERE))
+_SO = os.path.join(_HERE, "libresamp_select_emul.so")
+_lib = None
+
+
+def build():
+    deps = [os.path.join(_HERE, "resamp_select_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "resamp_core.hpp")]
+    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", deps[0], "-o", _SO], check=True)
+    return _SO
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = C.CDLL(build())
+        vp = C.c_void_p
+        L.resamp_select_emul.argtypes = [C.c_int] * 5 + [vp, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong, vp]
+        L.resamp_select_emul.restype = C.c_int
+        _lib = L
+    return _lib
+
+
+class ResampSelectEmul:
+    """The selecting resampler's arithmetic and index maps with the carried state of the C ABI (delay line of the T - 1 newest frames'
+    picked columns, positions): input rows of in_ch channels, output column j = input column cols[j]."""
+
+    def __init__(self, in_ch, cols, I, DN, T, proto, generic=False):
+        self.in_ch, self.I, self.DN, self.T = in_ch, I, DN, T
+        self.cols = np.ascontiguousarray(cols, np.int32)
+        self.h = np.ascontiguousarray(proto, np.float32)
+        self.generic = generic
+        self.hist = np.zeros((T - 1, self.cols.size), np.complex64)
+        self.n_total, self.m_next = 0, 0
+
+    def process(self, x):
+        x = np.ascontiguousarray(x, np.complex64).reshape(-1, self.in_ch)
+        n_in, n = x.shape[0], self.cols.size
+        m1 = ((self.n_total + n_in) * self.I + self.DN - 1) // self.DN
+        n_out = m1 - self.m_next
+        # NaN-poisoned output: every stored element must be written
+        out = np.full((max(n_out, 1), n), np.nan + 0j, np.complex64)
+        xs = x.copy() if n_in else np.zeros((1, self.in_ch), np.complex64)
+        got = lib().resamp_select_emul(self.I, self.DN, self.T, self.in_ch, n, self.cols.ctypes.data, int(self.generic), self.h.ctypes.data,
+                                       self.hist.ctypes.data, xs.ctypes.data, n_in, self.n_total, self.m_next, out.ctypes.data)
+        assert got == n_out, (got, n_out)
+        self.hist = np.concatenate([self.hist, x[:, self.cols]])[n_in:].copy()
+        self.n_total += n_in
+        self.m_next = m1
+        return out[:n_out]
