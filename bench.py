@@ -9,11 +9,15 @@ samples (1 s @ 36 ksps) per GPU, 65-tap RRC, loop state carried from step to ste
 range -- channels are independent, so there is no data-path collective; RCCL is only used for the
 barrier and the max-over-ranks of the elapsed time ("weak" scaling).
 
+A plain run sets up, ramps the clock, warms up, times the K steps, writes --dump-outputs and prints the line -- nothing else.
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline      dominant kernel (k_fused, the whole chain in one launch):
                 algorithmic bytes (9 B per input sample: 8 B IQ read + 1 B bit written, SURVEY.md section
                 8(d)) / its mean launch duration from HIP events recorded on the launch stream inside the
                 timed region, against 8 TB/s HBM peak;
+and, with --full only (each leg after the timed region, each skippable with its --no-* option):
+  check         the known-answer check: every rank demodulates its bank once more from fresh loops and compares a sample of 256
+                channels with their transmitted bits (a failure ends the run);
   cpu_baseline  the CPU oracle (oracle/, "port") timed on this host's cores on a bounded sample of the
                 same workload.  The oracle is only the baseline/checker here, never the measured path.
   time_major    the same workload handed over as iq[n][c] (TETRA_LAYOUT_TIME_MAJOR, what a channeliser emits), A/B beside the
@@ -532,7 +536,7 @@ def dump_outputs(pkg, out_dir, bits, nbits, rows, ch_lo=0, world=1, dist=None, d
 
 
 def informational(leg, *a):
-    """An informational leg of the default line (config 5, the receive chain) must not take the metric line down with it: a leg that
+    """An informational leg of the --full line (config 5, the receive chain) must not take the metric line down with it: a leg that
     fails -- its own known-answer check included -- is reported as {"error": ...} in its place (run alone, --config5 / --chain-only,
     the same failure ends the run with a non-zero status)."""
     try:
@@ -563,6 +567,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--channels", type=int, default=CHANNELS_PER_GPU, help="channels per GPU")
     ap.add_argument("--samples", type=int, default=SAMPLES, help="samples per channel per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the known-answer check, the CPU baselines and the "
+                         "informational legs (time-major, host path, large batch, config 5, receive chain); each one can still be "
+                         "skipped with its --no-* option")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
@@ -576,12 +584,12 @@ def main():
     ap.add_argument("--no-host-path", action="store_true",
                     help="skip the PCIe-inclusive host-path legs (tetra_demod_process / tetra_demod_process_async on page-locked "
                          "buffers; informational fields host_path_*, never the metric value)")
-    ap.add_argument("--host-path", action="store_true", help="(default now; kept for old command lines)")
+    ap.add_argument("--host-path", action="store_true", help="(part of --full now; kept for old command lines)")
     ap.add_argument("--no-config5", action="store_true",
                     help="skip the informational BASELINE config 5 leg (wideband -> channeliser -> 800-channel demod, field config5)")
     ap.add_argument("--no-large-batch", action="store_true",
                     help="skip the informational leg with twice the channels per GPU (32-channel workgroup shape, field large_batch)")
-    ap.add_argument("--chain", action="store_true", help="(default now; kept for old command lines)")
+    ap.add_argument("--chain", action="store_true", help="(part of --full now; kept for old command lines)")
     ap.add_argument("--no-chain", action="store_true",
                     help="skip the informational receive-chain leg (include/tetra_rx.h: demodulator || synchroniser -> demultiplexer -> "
                          "lower-MAC decoder -> SYNC-PDU tracker on coded downlinks; field chain)")
@@ -705,7 +713,7 @@ def main():
     # size-independent property at full size: after lock every channel returns its transmitted bits -- on EVERY rank (each has its
     # own channel range and input); the counters are summed over the ranks after the timed region, one failing rank fails the job
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         dem.reset()
         step()
         torch.cuda.synchronize(device)
@@ -731,7 +739,7 @@ def main():
     # The same workload handed over time-major, iq[n][c] (what a channeliser emits; the AGC wave's loads then coalesce across
     # the channel axis as north_star words it): a second handle on the transposed samples, informational A/B.
     tmaj = None
-    if not args.no_time_major and rank == 0 and world == 1:
+    if args.full and not args.no_time_major and rank == 0 and world == 1:
         iq_t = iq.transpose(0, 1).contiguous()
         dem_t = pkg.Demodulator(C, N, device=local_rank, flags=0, layout=pkg.binding.LAYOUT_TIME_MAJOR)
         bits_t = torch.zeros_like(bits)
@@ -767,7 +775,7 @@ def main():
     # included.  Page-locked caller buffers throughout.  sync = tetra_demod_process (copy, kernel, copy);
     # async = tetra_demod_process_async (time chunks double-buffered, two calls in flight), float and int16 input.
     host = {}
-    if not args.no_host_path and rank == 0 and world == 1:
+    if args.full and not args.no_host_path and rank == 0 and world == 1:
         import ctypes
         B = pkg.binding
         lib = B.load_library()
@@ -815,7 +823,7 @@ def main():
     # Twice the channels on the same GPU (informational, never the metric): above one 16-channel workgroup per CU the library
     # launches 32-channel workgroups whose FLL rows carry 16 channels per wave.
     large = None
-    if not args.no_large_batch and rank == 0 and world == 1 and C == CHANNELS_PER_GPU:
+    if args.full and not args.no_large_batch and rank == 0 and world == 1 and C == CHANNELS_PER_GPU:
         iq2 = torch.cat([iq, iq])
         bits2 = torch.zeros((2 * C, stride), dtype=torch.uint8, device=device)
         nb2 = torch.zeros(2 * C, dtype=torch.int32, device=device)
@@ -862,7 +870,7 @@ def main():
             "n_ranks": world, "gpus_physical": gpus_physical, "functional_only": folded, "steps": args.steps,
             "warmup": args.warmup, "ramp_steps": RAMP_STEPS, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": "%d channels/GPU x %d complex64 samples (1 s @ 36 ksps), 65-tap RRC, pi/4-DQPSK Es/N0 25 dB, every "
                                    "channel from its own seed (bits, carrier / timing offset, amplitude, phase), state carried" % (C, N),
                        "channels_per_gpu": C, "samples_per_channel": N, "sharding": "channel ranges, no collective",
@@ -893,7 +901,7 @@ def main():
         out.update(host)
         if large is not None:
             out["large_batch"] = large
-        if not args.no_config5 and world == 1 and C == CHANNELS_PER_GPU:
+        if args.full and not args.no_config5 and world == 1 and C == CHANNELS_PER_GPU:
             dem.close()
             dem = None
             out["config5"] = informational(wideband_config5, args, torch, pkg, device, local_rank)      # after the timed region
@@ -902,9 +910,9 @@ def main():
             out["dist_backend"] = args.backend
             if backend_note:
                 out["dist_backend_note"] = backend_note
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["cpu_baseline_fast"] = cpu_baseline(pkg.synth, N)
-        if not args.no_chain and world == 1 and C == CHANNELS_PER_GPU:
+        if args.full and not args.no_chain and world == 1 and C == CHANNELS_PER_GPU:
             if dem is not None:
                 dem.close()
             dem = None

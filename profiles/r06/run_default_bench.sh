@@ -3,7 +3,7 @@ TAG=${1:-r06q}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-T0=$(date +%s.%N); python bench.py > $O/bench_default.json 2> $O/bench_default.err; T1=$(date +%s.%N); echo "default bench wall seconds: $(echo "$T1 - $T0" | bc)" | tee $O/time.txt
+T0=$(date +%s.%N); python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; T1=$(date +%s.%N); echo "default bench wall seconds: $(echo "$T1 - $T0" | bc)" | tee $O/time.txt
 python -c "
 import json
 d=json.load(open('$O/bench_default.json'))

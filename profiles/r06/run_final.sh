@@ -2,7 +2,7 @@
 TAG=${1:-r06_final}; O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O; cd $GRAFT_REPO_ROOT
 timeout 2400 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-T0=$(date +%s); python bench.py > $O/bench_default.json 2> $O/bench_default.err; T1=$(date +%s); echo "default bench wall seconds: $((T1 - T0))" | tee $O/time.txt
+T0=$(date +%s); python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; T1=$(date +%s); echo "default bench wall seconds: $((T1 - T0))" | tee $O/time.txt
 python -c "
 import json
 d=json.load(open('$O/bench_default.json'))

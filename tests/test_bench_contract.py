@@ -77,13 +77,17 @@ def test_rank_count_must_equal_gpus_flag():
     assert r.returncode != 0 and "is running as one of 2 rank(s)" in r.stderr
 
 
-def test_default_line_carries_config5_at_the_plugins_rate_and_the_receive_chain():
-    """What the driver's plain `python bench.py` run reports beside the metric: config 5 through the 18/25
-    resampler at the plugin's 36 ksps by default, the receive chain (include/tetra_rx.h) unless --no-chain, per-channel seeds and a
-    known-answer check over >= 256 channels.  (Source-level pins: the line itself needs the GPU; tests/test_bench_ranks.py runs it.)"""
+def test_full_line_carries_config5_at_the_plugins_rate_and_the_receive_chain():
+    """What `bench.py --full` reports beside the metric: config 5 through the 18/25 resampler at the plugin's
+    36 ksps by default, the receive chain (include/tetra_rx.h) unless --no-chain, per-channel seeds and a known-answer check over
+    >= 256 channels.  A plain run leaves all of them, and every other leg that the headline does not need, to --full.  (Source-level
+    pins: the line itself needs the GPU; tests/test_bench_ranks.py runs it.)"""
     import inspect
     src = inspect.getsource(bench.main)
     assert 'out["chain"] = informational(receive_chain, ' in src and "args.no_chain" in src and 'out["config5"] = informational(wideband_config5, ' in src
+    for leg in ("check", "time_major", "host_path", "large_batch", "config5", "cpu_baseline", "chain"):
+        assert src.count("if args.full and not args.no_%s and " % leg) + src.count("if args.full and not args.no_%s:" % leg) == 1, leg
+    assert '"--full", action="store_true"' in src
     # an informational leg that fails (its own check included) is reported in place, the metric line still comes out
     assert bench.informational(lambda: (_ for _ in ()).throw(SystemExit("check failed"))) == {"error": "SystemExit: check failed"}
     assert bench.informational(lambda x: {"ok": x}, 3) == {"ok": 3}

@@ -1,6 +1,7 @@
 """bench.py's N > 1 path on real hardware: `python bench.py --gpus 2` by itself starts two ranks (here both mapped onto the
 one GPU of the box), once over gloo and once over RCCL; on a box with fewer GPUs than ranks the line is marked functional_only
-(value null, n_gpus = the GPUs that ran) and the known-answer check is green."""
+(value null, n_gpus = the GPUs that ran) and the known-answer check (a --full leg) is green.  Beside them, a plain one-rank run
+carries the headline alone."""
 import json
 import os
 import subprocess
@@ -15,7 +16,7 @@ OUT = os.path.join(ROOT, "gpurun_out")
 
 
 def _run(backend):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--backend", backend]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
 
@@ -63,7 +64,7 @@ def test_bench_gpus_4_folded_onto_the_box(tmp_path):
     import numpy as np
     dump = tmp_path / "dump"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--channels", "512",
-           "--no-cpu-baseline", "--dump-outputs", str(dump)]
+           "--full", "--no-cpu-baseline", "--dump-outputs", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     d = _line(r)
     os.makedirs(OUT, exist_ok=True)
@@ -94,7 +95,7 @@ def test_bench_rccl_half_of_the_rank_path_on_one_gpu():
     """RCCL refuses several ranks on one device, so on a one-GPU box its half of bench.py's N > 1 path -- communicator set-up
     with device_id, barrier, MAX all-reduce of the elapsed time on a device tensor, tear-down -- runs as a ONE-rank group
     (--force-dist); the two-rank half runs over gloo above."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-host-path", "--no-large-batch", "--no-config5", "--no-time-major", "--force-dist", "--backend", "nccl"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     d = _line(r)
@@ -113,7 +114,7 @@ def test_bench_under_the_driver_s_own_launcher():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--backend", "gloo"]
+           "--full", "--no-cpu-baseline", "--backend", "gloo"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     d = _line(r)
     import torch
@@ -152,7 +153,8 @@ def test_bench_dump_outputs_are_the_same_on_a_second_run(tmp_path):
     row is twice as long: fewer rows are sampled, the files stay within 64 MB."""
     import numpy as np
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--channels", "512",
-            "--samples", "72000", "--no-cpu-baseline", "--no-host-path", "--no-large-batch", "--no-config5", "--no-time-major", "--no-chain"]
+            "--samples", "72000", "--full", "--no-cpu-baseline", "--no-host-path", "--no-large-batch", "--no-config5", "--no-time-major",
+            "--no-chain"]
     got = []
     for k in range(2):
         d = tmp_path / ("d%d" % k)
@@ -167,3 +169,24 @@ def test_bench_dump_outputs_are_the_same_on_a_second_run(tmp_path):
     nb, rows = got[0]["n_bits"], got[0]["bits"]
     assert nb.shape == (512,) and rows.shape[0] == got[0]["bits_channels"].shape[0] and (np.abs(nb - 72000) < 720).all()
     assert set(np.unique(rows)) <= {-1.0, 0.0, 1.0} and 0.4 < (rows == 1).sum() / (rows >= 0).sum() < 0.6
+
+
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set-up, ramp, warm-up, the K timed steps, --dump-outputs and the line --
+    the contract fields and the roofline of the timed launches, but no known-answer check, CPU baseline or informational leg (those
+    are --full's)."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    d = _line(r)
+    assert d["full"] is False and d["check"] is None and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["metric"] == "IQ Msamples/s demodulated to bits, batched TETRA channels" and d["unit"] == "Msamples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["roofline"]["kernel_ms"] > 0
+    assert abs(d["value"] - 4096 * 36000 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * d["value"]
+    legs = {"cpu_baseline", "cpu_baseline_fast", "time_major", "large_batch", "config5", "chain"}
+    assert not legs & set(d) and not [k for k in d if k.startswith("host_path")], sorted(d)
+    dd = d["dump_outputs"]
+    assert dd["arrays"] == ["bits", "bits_channels", "n_bits"] and dd["rows"] == 256
+    nb = np.load(dump / "n_bits.npy")
+    assert nb.shape == (4096,) and (np.abs(nb - 36000) < 360).all()
