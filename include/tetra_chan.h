@@ -12,6 +12,8 @@
  * M channels at spacing Fs/M (channel k centred at k*Fs/M; k > M/2 are the negative frequencies), prototype low-pass
  * h of L = P*M taps, decimation D (output rate Fs/D per channel; D = M/2 = 2x oversampled is the intended use:
  * 20 MHz / 800 channels = 25 kHz spacing, 50 ksps per channel, demodulator run with samplerate 50000).
+ * Carriers that lie off the centres k*Fs/M by one common offset: the frequency shift of tetra_shift.h (tetra_chan_set_shift)
+ * moves the whole bank by a fraction of a bin, inside the same kernels.
  * Floating point throughout (float32 DFT): results are held to a tolerance against the double-precision definition
  * (oracle/chan_oracle.c), see tests/test_chan.py.  Same conventions as tetra_demod.h: extern "C", int status
  * (TETRA_OK / TETRA_ERR_*), no exceptions, one thread per handle, GPU only.

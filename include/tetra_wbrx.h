@@ -10,7 +10,10 @@
  *
  * so that everything behind the channeliser's FFT costs in proportion to the carriers, not to the M bins.  The resampled IQ of
  * carrier j is column bins[j] of tetra_resamp run on all M bins, bit for bit; the chain's output is then what tetra_rx gives for
- * those columns.  Carriers must sit on the bins' centres (k Fs / M): the handle has no per-carrier mixer.
+ * those columns.  The handle has no per-carrier mixer: the carriers must share ONE offset from the bins' centres (k Fs / M).  That
+ * offset -- zero, or the fraction of a bin that the band's raster and the SDR's tuning leave, typically half a bin -- goes into the
+ * channeliser's frequency shift (tetra_wbrx_set_shift, tetra_shift.h), which costs no extra pass over the capture; a residual of a
+ * few hundred hertz is the demodulator FLL's business, as before.
  *
  * Same conventions as the other headers: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, one thread per handle,
  * GPU only; every mis-sized or misaligned buffer is a status.

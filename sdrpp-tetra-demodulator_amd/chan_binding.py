@@ -8,6 +8,8 @@ from .binding import TetraDemodError, load_library
 CHAN_EXPORTS = ["tetra_chan_default_config", "tetra_chan_create", "tetra_chan_destroy", "tetra_chan_frames_for",
                 "tetra_chan_process_device", "tetra_chan_process", "tetra_chan_reset", "tetra_chan_get_prototype",
                 "tetra_chan_last_kernel_ms", "tetra_chan_process_device_cs16", "tetra_chan_process_device_cs8"]
+# include/tetra_shift.h (the frequency-shifted bank): the channeliser's share
+CHAN_SHIFT_EXPORTS = ["tetra_chan_set_shift", "tetra_chan_get_shift", "tetra_chan_shift_from_hz"]
 RESAMP_EXPORTS = ["tetra_resamp_default_config", "tetra_resamp_create", "tetra_resamp_destroy", "tetra_resamp_frames_for",
                   "tetra_resamp_process_device", "tetra_resamp_process", "tetra_resamp_reset", "tetra_resamp_get_prototype",
                   "tetra_resamp_last_kernel_ms"]
@@ -55,18 +57,31 @@ def _lib():
         L.tetra_resamp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         for n in CHAN_EXPORTS + RESAMP_EXPORTS:
             getattr(L, n).restype = i32
+        if hasattr(L, "tetra_chan_set_shift"):       # (a TETRA_DEMOD_LIB override may be an older build without the shift)
+            L.tetra_chan_set_shift.argtypes = [vp, C.c_uint32]
+            L.tetra_chan_set_shift.restype = i32
+            L.tetra_chan_get_shift.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.tetra_chan_get_shift.restype = i32
+            L.tetra_chan_shift_from_hz.argtypes = [C.c_double, C.c_double]
+            L.tetra_chan_shift_from_hz.restype = C.c_uint32
         _ready = True
     return L
 
 
+def shift_from_hz(shift_hz, sample_rate_hz):
+    """tetra_chan_shift_from_hz: the increment (2^-32 cycles per input sample) of a shift in hertz; negative shifts wrap."""
+    return int(_lib().tetra_chan_shift_from_hz(float(shift_hz), float(sample_rate_hz)))
+
+
 class Channeliser:
-    """M-channel analysis filter bank on one GPU; emits time-major frames [frames][M] complex64."""
+    """M-channel analysis filter bank on one GPU; emits time-major frames [frames][M] complex64.  shift: the frequency shift of
+    include/tetra_shift.h in 2^-32 cycles per input sample (0 = off), for carriers off the bins' centres by one common offset."""
 
     FLAG_VALU_DFT = 1      # TETRA_CHAN_FLAG_VALU_DFT: keep the direct-sum DFT kernel where a faster form exists (M = 800)
     FLAG_MATRIX_DFT = 2    # TETRA_CHAN_FLAG_MATRIX_DFT: M = 800 at D = M / 2 as 25 x 32 matrix products (round 4's kernel) instead of the mixed-radix FFT
 
     def __init__(self, n_channels=800, taps_per_channel=8, decimation=None, max_in=1 << 20, device=-1, cutoff_rel=1.2,
-                 prototype=None, flags=0):
+                 prototype=None, flags=0, shift=0):
         self._lib = _lib()
         cfg = ChanConfig()
         self._lib.tetra_chan_default_config(C.byref(cfg))
@@ -87,6 +102,21 @@ class Channeliser:
         if rc:
             raise TetraDemodError(rc, "tetra_chan_create")
         self._h = h
+        if shift:
+            self.set_shift(shift)
+
+    def set_shift(self, inc):
+        """tetra_chan_set_shift: between process calls; takes effect from the next call's first frame, keeps the phase reference."""
+        rc = self._lib.tetra_chan_set_shift(self._h, int(inc) & 0xffffffff)
+        if rc:
+            raise TetraDemodError(rc, "tetra_chan_set_shift")
+
+    def get_shift(self):
+        v = C.c_uint32(0)
+        rc = self._lib.tetra_chan_get_shift(self._h, C.byref(v))
+        if rc:
+            raise TetraDemodError(rc, "tetra_chan_get_shift")
+        return int(v.value)
 
     def close(self):
         if getattr(self, "_h", None):

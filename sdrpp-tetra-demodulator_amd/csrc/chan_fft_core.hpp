@@ -19,6 +19,9 @@
 // thread against the double-precision definition, oracle/chan_oracle.c), so everything here is plain C++ on float pairs.
 #pragma once
 
+#include <cmath>
+#include <cstdint>
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define CHAN_HD __host__ __device__ __forceinline__
 #else
@@ -168,6 +171,57 @@ template <int P> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoef<P>
         k.c[1][q] = ht[(2 * u + 1) * P + q];
     }
 }
+// ---- the frequency-shifted bank (tetra_chan_set_shift): complex taps and one phasor per frame ----------------------------
+// Shifting the input by delta = inc / 2^32 cycles per sample, x'[n] = x[n] exp(-j 2 pi delta n), folds into the bank exactly:
+//     out'[m][k] = exp(-j 2 pi delta n_m) . sum_l hc[l] x[n_m - l] exp(-j 2 pi k (n_m - l) / M),    hc[l] = h[l] exp(+j 2 pi delta l)
+// = the same fold with a complex (modulated) prototype, and one phasor per output frame that is the same for every bin.  Both
+// phases are taken in INTEGER arithmetic mod 2^32 (inc . l for the taps, inc . n_m for the frame, n_m = the absolute index of the
+// frame's newest sample): exact at any stream position, whatever the chunking.  Everything here is selected at compile time
+// (SHIFT = true); the SHIFT = false instantiations are the code above, untouched.
+template <int P> struct FoldCoefC {
+    c32 c[2][P];
+};
+// hc in double on the host, re-ordered like fold_transpose_prototype: htc[u][parity][q] complex (16 P bytes per slot)
+inline void fold_transpose_prototype_shifted(const float* h, int P, uint32_t inc, c32* htc) {
+    const double two_pi = 6.283185307179586476925286766559;
+    auto hc = [&](int l) {
+        const double a = two_pi * (double)(uint32_t)(inc * (uint32_t)l) / 4294967296.0;
+        return mk((float)((double)h[l] * std::cos(a)), (float)((double)h[l] * std::sin(a)));
+    };
+    for (int u = 0; u < kM; u++) {
+        const int uo = u < kM / 2 ? u + kM / 2 : u - kM / 2;
+        for (int q = 0; q < P; q++) {
+            htc[(2 * u + 0) * P + q] = hc(u + kM * q);
+            htc[(2 * u + 1) * P + q] = hc(uo + kM * q);
+        }
+    }
+}
+template <int P> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoefC<P>& k) {
+    const c32* htc = reinterpret_cast<const c32*>(ht);
+#pragma unroll
+    for (int q = 0; q < P; q++) {
+        k.c[0][q] = htc[(2 * u + 0) * P + q];
+        k.c[1][q] = htc[(2 * u + 1) * P + q];
+    }
+}
+template <int P, bool SHIFT> struct FoldCoefOf { typedef FoldCoef<P> type; };
+template <int P> struct FoldCoefOf<P, true> { typedef FoldCoefC<P> type; };
+// exp(-j 2 pi ph / 2^32).  The phase goes to binary32 as a signed fraction of a turn (24 significant bits: 1.9e-7 rad at worst).
+CHAN_HD c32 shift_phasor(uint32_t ph) {
+    const float t = (float)(int32_t)ph * (1.0f / 2147483648.0f);      // half-turns in [-1, 1)
+    float sn, cs;
+#if defined(__HIP_DEVICE_COMPILE__)
+    sincospif(t, &sn, &cs);
+#else
+    sn = (float)std::sin(3.14159265358979323846 * (double)t);
+    cs = (float)std::cos(3.14159265358979323846 * (double)t);
+#endif
+    return mk(cs, -sn);
+}
+// The phasor of frame t of a block lives in the one element of the frame's LDS region that no phase touches: the pad of the last
+// row of the transposed block (33 . 24 + 32 = 824: past the fold's linear v[0 .. 800), and column 32 of a row is never written).
+constexpr int kPhasorSlot = kFrameLds - 1;
+
 // ---- one block of kBlockFrames frames on a workgroup of 256 threads: three phases, a barrier after each ------------------
 // Sample formats of the wideband input (round 6): complex64, or what an SDR's DMA delivers -- interleaved int16 / int8 I, Q pairs,
 // converted in the fold's load (value / 32768, value / 128: exact in binary32), so that an integer capture crosses HBM once at 4 or
@@ -198,6 +252,7 @@ struct BlockCtx {
     int ph0;              // samples already consumed towards the call's first frame
     long long abs0;       // absolute time of the first new sample
     int L;                // 800 P
+    uint32_t inc;         // frequency shift in 2^-32 cycles per input sample (SHIFT instantiations only; h then holds the complex taps)
 };
 
 // Sample s of the stream, s counted from the call's first new sample.  Blocks in the middle of a call read only new samples and
@@ -236,16 +291,40 @@ template <int P, int CLS, bool CAREFUL, int FMT> CHAN_HD void fold_slot(const Bl
     }
 }
 
+// the same with complex taps: 4 fma per tap instead of 2
+template <int P, int CLS, bool CAREFUL, int FMT> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoefC<P>& k, c32 out[kBlockFrames]) {
+    CHAN_FP_FAST
+    constexpr int kS = P + 3 + CLS;
+    c32 S[kS];
+#pragma unroll
+    for (int j = 0; j < kS; j++) S[j] = sample_at<CAREFUL, FMT>(c, s0 + kM * (j - (P - 1)));
+#pragma unroll
+    for (int t = 0; t < kBlockFrames; t++) {
+        const int s = (t + CLS) >> 1;
+        float ar = 0.f, ai = 0.f;
+#pragma unroll
+        for (int q = 0; q < P; q++) {
+            const c32 xv = S[s - q + (P - 1)];
+            const c32 hv = k.c[t & 1][q];
+            ar += hv.x * xv.x;
+            ar -= hv.y * xv.y;
+            ai += hv.x * xv.y;
+            ai += hv.y * xv.x;
+        }
+        out[t] = mk(ar, ai);
+    }
+}
+
 // phase 1 (threads < kFoldThreads): fold the block's 8 frames, v_t[r] -> lds[t][r].  Slot after slot: a slot's 2 P coefficients and
 // P + 4 samples live only while its 8 frames are summed.
-template <int P, bool CAREFUL, int FMT> CHAN_HD void phase_fold_t(const BlockCtx& c, int blk, int tid, c32* lds) {
+template <int P, bool CAREFUL, int FMT, bool SHIFT = false> CHAN_HD void phase_fold_t(const BlockCtx& c, int blk, int tid, c32* lds) {
     if (tid >= kFoldThreads) return;
     const long long newest0 = (long long)(kBlockFrames * blk + 1) * (kM / 2) - 1 - c.ph0;     // index of the block's first frame's newest sample among the new samples
     const int a = (int)((c.abs0 + newest0) % kM);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int u = kFoldThreads * i + tid;
-        FoldCoef<P> k;
+        typename FoldCoefOf<P, SHIFT>::type k;
         fold_load_coef<P>(c.h, u, k);
         c32 v[kBlockFrames];
         if (i < 2) fold_slot<P, 0, CAREFUL, FMT>(c, newest0 - u, k, v);
@@ -261,10 +340,22 @@ template <int P, bool CAREFUL, int FMT> CHAN_HD void phase_fold_t(const BlockCtx
 #endif
     }
 }
-template <int P, int FMT = kFmtC32> CHAN_HD void phase_fold(const BlockCtx& c, int blk, int tid, c32* lds) {
+template <int P, int FMT = kFmtC32, bool SHIFT = false> CHAN_HD void phase_fold(const BlockCtx& c, int blk, int tid, c32* lds) {
     const long long newest0 = (long long)(kBlockFrames * blk + 1) * (kM / 2) - 1 - c.ph0;
-    if (block_is_careful(c, newest0)) phase_fold_t<P, true, FMT>(c, blk, tid, lds);      // (uniform over the workgroup)
-    else phase_fold_t<P, false, FMT>(c, blk, tid, lds);
+    if (block_is_careful(c, newest0)) phase_fold_t<P, true, FMT, SHIFT>(c, blk, tid, lds);      // (uniform over the workgroup)
+    else phase_fold_t<P, false, FMT, SHIFT>(c, blk, tid, lds);
+}
+// phase 1, shifted bank only: the block's 8 frame phasors, ONE thread per frame (threads 200 .. 207: they fold nothing, though their wave 3 does for its first 8 lanes), into
+// kPhasorSlot of the frame's region; phase 3 reads them behind the two barriers.  Frame j of the call has its newest sample at
+// absolute index n = abs0 + 400 (j + 1) - 1 - ph0; its phase is inc . n mod 2^32 -- unsigned 32-bit arithmetic IS that.
+CHAN_HD uint32_t frame_phase(const BlockCtx& c, long long j) {
+    const uint32_t n = (uint32_t)(c.abs0 + (j + 1) * (kM / 2) - 1 - c.ph0);
+    return c.inc * n;
+}
+CHAN_HD void phase_phasor(const BlockCtx& c, int blk, int tid, c32* lds) {
+    const int t = tid - kFoldThreads;
+    if (t < 0 || t >= kBlockFrames) return;
+    lds[t * kFrameLds + kPhasorSlot] = shift_phasor(frame_phase(c, (long long)kBlockFrames * blk + t));
 }
 
 // phase 2 (lanes n1 < 25 of each half-wave; wave w, half f -> frame 2 w + f): 32-point FFT over n2, result transposed IN PLACE:
@@ -296,7 +387,7 @@ CHAN_HD void load_twiddles(const BlockCtx& c, int tid, c32 tw[kN1 - 1]) {
 #pragma unroll
     for (int n1 = 1; n1 < kN1; n1++) tw[n1 - 1] = c.tw[n1 * kN2 + k2];
 }
-template <int EXP = 0> CHAN_HD void phase_dft25_store(const BlockCtx& c, long long j0, int tid, const c32* lds, const c32 tw[kN1 - 1]) {
+template <int EXP = 0, bool SHIFT = false> CHAN_HD void phase_dft25_store(const BlockCtx& c, long long j0, int tid, const c32* lds, const c32 tw[kN1 - 1]) {
     CHAN_FP_FAST
     const int k2 = tid & 31, t = tid >> 5;
     const long long j = j0 + t;               // j0 = the first frame of the block (of the pair)
@@ -318,6 +409,12 @@ template <int EXP = 0> CHAN_HD void phase_dft25_store(const BlockCtx& c, long lo
         return;
     }
     // (16-byte stores through a lane-pair exchange were measured: no gain, 38.2 vs 37.7 us -- profiles/r05/README.md)
+    if (SHIFT) {                              // the frame's phasor (phase_phasor): the same for the 32 lanes and the 25 bins of each
+        const c32 ph = f[kPhasorSlot];
+#pragma unroll
+        for (int k1 = 0; k1 < kN1; k1++) dst[kN2 * k1] = cmul(x[k1], ph);
+        return;
+    }
 #pragma unroll
     for (int k1 = 0; k1 < kN1; k1++) dst[kN2 * k1] = x[k1];
 }

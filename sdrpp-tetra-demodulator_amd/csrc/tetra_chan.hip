@@ -21,7 +21,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/tetra_chan.h"
+#include "../../include/tetra_shift.h"
 #include "chan_fft_core.hpp"
 #include "hip_host.hpp"
 
@@ -40,12 +40,17 @@ struct ChanParams {
     int M, P, D, N1, N2;
     int ph0;               // samples already consumed towards the first frame of this call
     long long abs0;        // absolute index of xbuf[L-1] (the first new sample)
+    const float2* hc;      // SHIFT: the modulated prototype hc[l] = h[l] exp(+j 2 pi inc l / 2^32), [L]
+    uint32_t inc;          // SHIFT: frequency shift in 2^-32 cycles per input sample (tetra_chan_set_shift)
 };
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
-__global__ __launch_bounds__(kThreads) void k_channelise(ChanParams p) {
-    extern __shared__ float2 lds[];          // v[M] | b[N1][N2 + 1]
+// SHIFT (all three kernels): the frequency-shifted bank of tetra_chan_set_shift -- complex taps hc in the fold and the frame's phasor
+// exp(-j 2 pi inc n_m / 2^32) on every stored bin (the identity is in chan_fft_core.hpp).  A template parameter: SHIFT = false is the
+// kernel as it was.
+template <bool SHIFT> __global__ __launch_bounds__(kThreads) void k_channelise(ChanParams p) {
+    extern __shared__ float2 lds[];          // v[M] | b[N1][N2 + 1] (| SHIFT: the frame's phasor)
     float2* v = lds;
     __shared__ float2 tw1[kMaxFactor], tw2[kMaxFactor];     // the two short twiddle tables: few distinct entries per wave
     if (threadIdx.x < p.N1) tw1[threadIdx.x] = p.w1[threadIdx.x];
@@ -65,12 +70,23 @@ __global__ __launch_bounds__(kThreads) void k_channelise(ChanParams p) {
         float2 acc = make_float2(0.f, 0.f);
         for (int q = 0; q < p.P; q++) {
             const int l = l0 + q * M;
+            if (SHIFT) {
+                const float2 hv = p.hc[l];
+                const float2 xv = xn[-l];
+                acc.x = fmaf(-hv.y, xv.y, fmaf(hv.x, xv.x, acc.x));
+                acc.y = fmaf(hv.y, xv.x, fmaf(hv.x, xv.y, acc.y));
+                continue;
+            }
             const float hv = p.h[l];
             const float2 xv = xn[-l];
             acc.x = fmaf(hv, xv.x, acc.x);
             acc.y = fmaf(hv, xv.y, acc.y);
         }
         v[r] = acc;
+    }
+    if (SHIFT && threadIdx.x == 0) {      // one frame per workgroup: its phasor once, into LDS behind b, read behind the barriers
+        const chanfft::c32 w = chanfft::shift_phasor(p.inc * (uint32_t)n_abs);
+        lds[p.M + p.N1 * (p.N2 + 1)] = make_float2(w.x, w.y);
     }
     __syncthreads();
     // column DFTs + twiddle: b[k1][n2] = W_M^{n2 k1} * sum_{n1} v[n1*N2 + n2] * W_N1^{n1 k1}
@@ -102,6 +118,7 @@ __global__ __launch_bounds__(kThreads) void k_channelise(ChanParams p) {
             idx += k2;
             if (idx >= N2) idx -= N2;
         }
+        if (SHIFT) acc = cmul(acc, lds[M + N1 * (N2 + 1)]);
         dst[o] = acc;
     }
 }
@@ -130,24 +147,27 @@ constexpr int kMBoStride = 36;                    // floats per Bo row (32 used)
 struct ChanMfmaParams {
     const float2* xbuf;
     float2* out;
-    const float* h;
+    const float* h;        // prototype [L]; SHIFT: the modulated prototype hc, [L] complex
     const float* bc;       // [4 kMK1][64] stage-1 constant operand
     const float* ac;       // [64][64]     stage-2 constant operand
     const float2* wm;      // exp(-j 2 pi i / M)
     int P, D, frames;
     int ph0;
     long long abs0;
+    uint32_t inc;          // SHIFT: frequency shift in 2^-32 cycles per input sample
 };
 
-template <int P> __global__ __launch_bounds__(kThreads, 3) void k_channelise_mfma(ChanMfmaParams p) {      // 3 waves per SIMD: <= 168 VGPRs
+template <int P, bool SHIFT = false> __global__ __launch_bounds__(kThreads, SHIFT ? 2 : 3) void k_channelise_mfma(ChanMfmaParams p) {      // 3 waves per SIMD: <= 168 VGPRs (SHIFT: 2, its LDS allows no more)
     constexpr int M = kMN1 * kMN2, L = M * P;
     __shared__ float At[4 * kMK1][kMAtStride];
     __shared__ float Bo[2 * kMN2][kMBoStride];
-    __shared__ float hs[L];              // the prototype: every frame reads all of it (rotated by the frame's time mod M)
+    __shared__ float hs[SHIFT ? 2 * L : L];   // the prototype: every frame reads all of it (rotated by the frame's time mod M); SHIFT: the
+                                              // complex taps, re / im interleaved (P = 8: 51 KB -- two workgroups per CU instead of three)
+    __shared__ float2 phs;                    // SHIFT: the phasor of the frame in flight (thread 0 in the fold -> every lane in stage 2)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
     const int wlo = w & 1, whi = w >> 1;
-    for (int i = tid; i < L; i += kThreads) hs[i] = p.h[i];
+    for (int i = tid; i < (SHIFT ? 2 * L : L); i += kThreads) hs[i] = p.h[i];
     // constant operands of this wave's tiles (registers for the workgroup's life)
     float b1re[kMK1], b1im[kMK1], a2re[kMK2], a2im[kMK2];
 #pragma unroll
@@ -200,6 +220,12 @@ template <int P> __global__ __launch_bounds__(kThreads, 3) void k_channelise_mfm
             float2 acc = make_float2(0.f, 0.f);
 #pragma unroll
             for (int q = 0; q < P; q++) {
+                if (SHIFT) {
+                    const float hr = hs[2 * (l0s[i] + q * M)], hi = hs[2 * (l0s[i] + q * M) + 1];
+                    acc.x = fmaf(-hi, xv[i][q].y, fmaf(hr, xv[i][q].x, acc.x));
+                    acc.y = fmaf(hi, xv[i][q].x, fmaf(hr, xv[i][q].y, acc.y));
+                    continue;
+                }
                 const float hv = hs[l0s[i] + q * M];
                 acc.x = fmaf(hv, xv[i][q].x, acc.x);
                 acc.y = fmaf(hv, xv[i][q].y, acc.y);
@@ -209,6 +235,10 @@ template <int P> __global__ __launch_bounds__(kThreads, 3) void k_channelise_mfm
                 At[n1][n2] = acc.x;
                 At[kMN1 + n1][n2] = acc.y;
             }
+        }
+        if (SHIFT && tid == 0) {      // the frame's phasor, once: phase inc . n_m mod 2^32 from the absolute index of its newest sample
+            const chanfft::c32 w = chanfft::shift_phasor(p.inc * (uint32_t)(p.abs0 + (long long)(j + 1) * p.D - 1 - p.ph0));
+            phs = make_float2(w.x, w.y);
         }
         if (j + (int)gridDim.x < p.frames) request(j + gridDim.x);
         __syncthreads();
@@ -241,7 +271,8 @@ template <int P> __global__ __launch_bounds__(kThreads, 3) void k_channelise_mfm
             if (k1 < kMN1) {
                 float2* dst = p.out + (long long)j * M + k1;
 #pragma unroll
-                for (int r = 0; r < 4; r++) dst[kMN1 * (16 * wlo + 4 * g + r)] = make_float2(xre[r], xim[r]);
+                for (int r = 0; r < 4; r++)
+                    dst[kMN1 * (16 * wlo + 4 * g + r)] = SHIFT ? cmul(make_float2(xre[r], xim[r]), phs) : make_float2(xre[r], xim[r]);
             }
         }
         __syncthreads();      // the next frame's fold rewrites At (read in stage 1, behind the barrier above) -- and its stage 1 rewrites
@@ -271,9 +302,12 @@ struct ChanFftParams {
     int xcd_span;          // blocks per XCD (ceil(blocks / 8)); 0 = no remap
     int exp;               // ablation switches (profiles/measure_chan_fft.py; compile-time variants of the P = 8 kernel): 1 = one store per lane, 2 = no inter-stage twiddles
     long long abs0;
+    uint32_t inc;          // frequency shift (tetra_chan_set_shift); read by the SHIFT instantiations only, for which h holds the complex taps [800][2][P]
 };
 
-template <int P, int EXP = 0, int FMT = chanfft::kFmtC32> __global__ __launch_bounds__(kThreads, 2) void k_channelise_fft(ChanFftParams p) {
+// SHIFT = true: the frequency-shifted bank (complex taps in the fold, one phasor per frame in the store: chan_fft_core.hpp).  SHIFT =
+// false is the kernel as it was: the shift is a template parameter so that it costs the un-shifted bank no instruction.
+template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false> __global__ __launch_bounds__(kThreads, 2) void k_channelise_fft(ChanFftParams p) {
     using namespace chanfft;
     __shared__ c32 lds[kBlockFrames * kFrameLds];          // 52.8 KB: three workgroups per CU
     const int tid = threadIdx.x;
@@ -286,6 +320,7 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32> __global__ __launch_bo
     c.h = p.h;
     c.tw = reinterpret_cast<const c32*>(p.tw);
     c.frames = p.frames; c.ph0 = p.ph0; c.abs0 = p.abs0;
+    c.inc = SHIFT ? p.inc : 0u;
     // One block of 8 frames per workgroup, no loop over blocks: nothing is carried from block to block, and a loop makes the compiler
     // keep the transforms' ~100 literal twiddles in VGPRs across it (256 VGPRs + spills instead of 147: three workgroups per CU).
     // Consecutive blocks share two thirds of their samples (a block reads 9600, 3200 of them new).  Workgroups are dealt to the 8 XCDs
@@ -297,7 +332,8 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32> __global__ __launch_bo
         blk = (int)(blockIdx.x & 7) * p.xcd_span + (int)(blockIdx.x >> 3);
         if (blk >= p.blocks || (int)(blockIdx.x >> 3) >= p.xcd_span) return;
     }
-    phase_fold<P, FMT>(c, blk, tid, lds);
+    phase_fold<P, FMT, SHIFT>(c, blk, tid, lds);
+    if (SHIFT) phase_phasor(c, blk, tid, lds);
     __syncthreads();
     c32 tw[kN1 - 1];
     load_twiddles(c, tid, tw);
@@ -313,7 +349,7 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32> __global__ __launch_bo
         if (live) phase_fft32_store(tid, lds, x);
     }
     __syncthreads();
-    phase_dft25_store<EXP>(c, (long long)kBlockFrames * blk, tid, lds, tw);
+    phase_dft25_store<EXP, SHIFT>(c, (long long)kBlockFrames * blk, tid, lds, tw);
 }
 
 // integer samples -> complex64 (the staging buffer of the kernels that read [history | new] contiguously, and the delay line)
@@ -342,6 +378,12 @@ struct tetra_chan {
     DevMem<float> d_ht;         // and the prototype re-ordered for its fold [800][2][P]
     int cus = 256;
     DevMem<float2> st_out;      // host-path staging
+    uint32_t inc = 0;           // frequency shift in 2^-32 cycles per input sample (tetra_chan_set_shift); 0 = the un-shifted kernels
+    DevMem<float2> d_hc;        // inc != 0: the modulated prototype hc -- FFT kernel: re-ordered for its fold [800][2][P]; the others: [L]
+    HostMem<float2> hc_host;    // its page-locked upload staging: rebuilt by set_shift, copied at the head of the next process call
+    bool hc_dirty = false;      // hc_host is newer than d_hc
+    Event ev_hc;                // behind the latest upload: set_shift waits for it before it rewrites hc_host
+    bool hc_in_flight = false;
     int phase = 0;              // samples consumed towards the next frame
     long long consumed = 0;     // absolute index of the next input sample
     Event ev[2];
@@ -542,6 +584,8 @@ int copy_samples(tetra_chan* h, int fmt, const void* d_x, size_t first, size_t n
     return TETRA_OK;
 }
 template <int FMT> void launch_fft(tetra_chan* h, const ChanFftParams& p, dim3 grid, hipStream_t s);
+// complex elements of the modulated prototype: the FFT kernel's fold layout holds every tap twice ([800][2][P], as d_ht), the others [L]
+size_t hc_elems(const tetra_chan* h) { return h->fft ? (size_t)2 * chanfft::kM * h->P : (size_t)h->L; }
 
 int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_out, int* n_frames, void* hip_stream) {
     if (!h || (!d_x && n_in > 0) || !d_out || !n_frames) return TETRA_ERR_ARG;
@@ -560,10 +604,20 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         const int rc = copy_samples(h, fmt, d_x, 0, (size_t)n_in, h->xbuf + hist, s);
         if (rc != TETRA_OK) return rc;
     }
+    // a new shift's taps go up here, in stream order behind everything enqueued before this call and ahead of its kernel
+    if (h->hc_dirty) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_hc, h->hc_host, sizeof(float2) * hc_elems(h), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(h->ev_hc, s));
+        h->hc_dirty = false;
+        h->hc_in_flight = true;
+    }
+    const bool shift = h->inc != 0;
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
     if (frames > 0 && h->fft) {
         ChanFftParams p;
-        p.x = d_x; p.hist = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_ht; p.tw = h->d_tw;
+        p.x = d_x; p.hist = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.tw = h->d_tw;
+        p.h = shift ? reinterpret_cast<const float*>(h->d_hc.get()) : h->d_ht.get();
+        p.inc = h->inc;
         p.frames = frames; p.blocks = (frames + chanfft::kBlockFrames - 1) / chanfft::kBlockFrames; p.n_in = n_in;
         p.ph0 = h->phase; p.abs0 = h->consumed;
         // one block of 8 frames per workgroup: the hardware hands the next block to whichever CU is through first
@@ -590,11 +644,18 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     } else if (frames > 0 && h->mfma) {
         ChanMfmaParams p;
         p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h; p.bc = h->d_bc; p.ac = h->d_ac; p.wm = h->d_wm;
-        p.P = h->P; p.D = h->D; p.frames = frames; p.ph0 = h->phase; p.abs0 = h->consumed;
+        p.P = h->P; p.D = h->D; p.frames = frames; p.ph0 = h->phase; p.abs0 = h->consumed; p.inc = h->inc;
+        if (shift) p.h = reinterpret_cast<const float*>(h->d_hc.get());
         // workgroups loop over frames (the constant operands are loaded once per workgroup): a few per CU keep the matrix pipe,
         // the fold's loads and the stores of different frames overlapping
-        const int grid = frames < 3 * h->cus ? frames : 3 * h->cus;      // three workgroups fit a CU (registers, LDS); each loops over its frames
-        if (h->P == 8) hipLaunchKernelGGL(k_channelise_mfma<8>, dim3(grid), dim3(kThreads), 0, s, p);
+        const int per_cu = shift ? 2 : 3;                                 // workgroups that fit a CU (registers, LDS; the shifted form's complex taps double hs)
+        const int grid = frames < per_cu * h->cus ? frames : per_cu * h->cus;      // each loops over its frames
+        if (shift) {
+            if (h->P == 8) hipLaunchKernelGGL((k_channelise_mfma<8, true>), dim3(grid), dim3(kThreads), 0, s, p);
+            else if (h->P == 6) hipLaunchKernelGGL((k_channelise_mfma<6, true>), dim3(grid), dim3(kThreads), 0, s, p);
+            else hipLaunchKernelGGL((k_channelise_mfma<4, true>), dim3(grid), dim3(kThreads), 0, s, p);
+        }
+        else if (h->P == 8) hipLaunchKernelGGL(k_channelise_mfma<8>, dim3(grid), dim3(kThreads), 0, s, p);
         else if (h->P == 6) hipLaunchKernelGGL(k_channelise_mfma<6>, dim3(grid), dim3(kThreads), 0, s, p);
         else hipLaunchKernelGGL(k_channelise_mfma<4>, dim3(grid), dim3(kThreads), 0, s, p);
         HIP_TRY(h, hipGetLastError());
@@ -603,8 +664,10 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h;
         p.w1 = h->d_w1; p.w2 = h->d_w2; p.wm = h->d_wm;
         p.M = h->M; p.P = h->P; p.D = h->D; p.N1 = h->N1; p.N2 = h->N2;
-        p.ph0 = h->phase; p.abs0 = h->consumed;
-        hipLaunchKernelGGL(k_channelise, dim3(frames), dim3(kThreads), sizeof(float2) * ((size_t)h->M + (size_t)h->N1 * (h->N2 + 1)), s, p);
+        p.ph0 = h->phase; p.abs0 = h->consumed; p.hc = h->d_hc; p.inc = h->inc;
+        const size_t lds_bytes = sizeof(float2) * ((size_t)h->M + (size_t)h->N1 * (h->N2 + 1));
+        if (shift) hipLaunchKernelGGL(k_channelise<true>, dim3(frames), dim3(kThreads), lds_bytes + sizeof(float2), s, p);
+        else hipLaunchKernelGGL(k_channelise<false>, dim3(frames), dim3(kThreads), lds_bytes, s, p);
         HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
@@ -628,6 +691,12 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     return TETRA_OK;
 }
 template <int FMT> void launch_fft(tetra_chan* h, const ChanFftParams& p, dim3 grid, hipStream_t s) {
+    if (h->inc != 0) {
+        if (h->P == 8) hipLaunchKernelGGL((k_channelise_fft<8, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
+        else if (h->P == 6) hipLaunchKernelGGL((k_channelise_fft<6, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
+        else hipLaunchKernelGGL((k_channelise_fft<4, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
+        return;
+    }
     if (h->P == 8) hipLaunchKernelGGL((k_channelise_fft<8, 0, FMT>), grid, dim3(kThreads), 0, s, p);
     else if (h->P == 6) hipLaunchKernelGGL((k_channelise_fft<6, 0, FMT>), grid, dim3(kThreads), 0, s, p);
     else hipLaunchKernelGGL((k_channelise_fft<4, 0, FMT>), grid, dim3(kThreads), 0, s, p);
@@ -678,6 +747,53 @@ int tetra_chan_reset(tetra_chan_t* h) {
     h->phase = 0;
     h->consumed = 0;
     return TETRA_OK;
+}
+
+int tetra_chan_set_shift(tetra_chan_t* h, uint32_t inc) {
+    if (!h) return TETRA_ERR_ARG;
+    if (inc == h->inc) return TETRA_OK;
+    if (inc == 0) {             // back to the un-shifted kernels; nothing to upload.  Phase and position stay: the reference n runs on
+        h->inc = 0;
+        h->hc_dirty = false;
+        return TETRA_OK;
+    }
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    // (a failure below leaves the handle on its old shift: inc is committed last)
+    HIP_TRY(h, h->d_hc.reserve(sizeof(float2) * hc_elems(h)));
+    HIP_TRY(h, h->hc_host.reserve(sizeof(float2) * hc_elems(h)));
+    if (!h->ev_hc) HIP_TRY(h, hipEventCreateWithFlags(h->ev_hc.put(), hipEventDisableTiming));
+    if (h->hc_in_flight) {      // the staging buffer may still be waiting for an earlier upload behind enqueued work
+        HIP_TRY(h, hipEventSynchronize(h->ev_hc));
+        h->hc_in_flight = false;
+    }
+    // hc[l] = h[l] exp(+j 2 pi inc l / 2^32): the phase inc l mod 2^32 in integers, cos / sin in double
+    if (h->fft) {
+        chanfft::fold_transpose_prototype_shifted(h->proto.data(), h->P, inc, reinterpret_cast<chanfft::c32*>(h->hc_host.get()));
+    } else {
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int l = 0; l < h->L; l++) {
+            const double a = two_pi * (double)(uint32_t)(inc * (uint32_t)l) / 4294967296.0;
+            h->hc_host.get()[l] = make_float2((float)((double)h->proto[l] * std::cos(a)), (float)((double)h->proto[l] * std::sin(a)));
+        }
+    }
+    h->inc = inc;
+    h->hc_dirty = true;         // uploaded at the head of the next process call, on its stream
+    return TETRA_OK;
+}
+
+int tetra_chan_get_shift(tetra_chan_t* h, uint32_t* inc) {
+    if (!h || !inc) return TETRA_ERR_ARG;
+    *inc = h->inc;
+    return TETRA_OK;
+}
+
+uint32_t tetra_chan_shift_from_hz(double shift_hz, double sample_rate_hz) {
+    if (!(sample_rate_hz > 0) || !std::isfinite(shift_hz)) return 0;
+    double f = shift_hz / sample_rate_hz;
+    f -= std::floor(f);                                      // cycles per sample in [0, 1): negative shifts wrap
+    const double v = std::nearbyint(f * 4294967296.0);       // (round to nearest; 2^32 itself wraps to 0)
+    return (uint32_t)(unsigned long long)v;
 }
 
 int tetra_chan_get_prototype(tetra_chan_t* h, float* proto) {

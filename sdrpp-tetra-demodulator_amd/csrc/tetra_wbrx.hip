@@ -16,7 +16,7 @@
 #include <new>
 #include <vector>
 
-#include "../../include/tetra_wbrx.h"
+#include "../../include/tetra_shift.h"
 #include "hip_host.hpp"
 #include "resamp_handle.hpp"
 
@@ -290,6 +290,17 @@ int tetra_wbrx_bin_power(tetra_wbrx_t* h, float* out) {
     HIP_TRY(h, hipMemcpyAsync(out, h->pw_out, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, h->aux));
     HIP_TRY(h, hipStreamSynchronize(h->aux));
     return TETRA_OK;
+}
+
+// The frequency shift (include/tetra_shift.h) is the channeliser's: every stage behind it sees the shifted bins.
+int tetra_wbrx_set_shift(tetra_wbrx_t* h, uint32_t inc) {
+    if (!h) return TETRA_ERR_ARG;
+    return tetra_chan_set_shift(h->chan, inc);
+}
+
+int tetra_wbrx_get_shift(tetra_wbrx_t* h, uint32_t* inc) {
+    if (!h) return TETRA_ERR_ARG;
+    return tetra_chan_get_shift(h->chan, inc);
 }
 
 int tetra_wbrx_stage_ms(tetra_wbrx_t* h, float ms[2]) {

@@ -12,6 +12,8 @@ from .rx_binding import _lib as _rx_lib
 WBRX_EXPORTS = ["tetra_wbrx_default_config", "tetra_wbrx_create", "tetra_wbrx_destroy", "tetra_wbrx_reset", "tetra_wbrx_process_device",
                 "tetra_wbrx_process_device_cs16", "tetra_wbrx_process_device_cs8", "tetra_wbrx_process", "tetra_wbrx_process_cs16",
                 "tetra_wbrx_rx", "tetra_wbrx_bins", "tetra_wbrx_frames_device", "tetra_wbrx_bin_power", "tetra_wbrx_stage_ms"]
+# include/tetra_shift.h (the frequency-shifted bank): the wideband receiver's share
+WBRX_SHIFT_EXPORTS = ["tetra_wbrx_set_shift", "tetra_wbrx_get_shift"]
 
 
 class WbrxConfig(C.Structure):
@@ -44,6 +46,11 @@ def _lib():
         for n in WBRX_EXPORTS:
             if n != "tetra_wbrx_rx":
                 getattr(L, n).restype = i32
+        if hasattr(L, "tetra_wbrx_set_shift"):       # (a TETRA_DEMOD_LIB override may be an older build without the shift)
+            L.tetra_wbrx_set_shift.argtypes = [vp, C.c_uint32]
+            L.tetra_wbrx_set_shift.restype = i32
+            L.tetra_wbrx_get_shift.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.tetra_wbrx_get_shift.restype = i32
         _ready = True
     return L
 
@@ -89,11 +96,13 @@ class _DeviceArray:
 
 class WidebandRx:
     """An SDR capture in, the decoded blocks of the carriers on `bins` out: channeliser (M bins) -> selecting 18 / 25 resampler ->
-    receive chain on one GPU.  `.rx` is the chain (an RxChain view); a block's channel is the carrier's index into `bins`."""
+    receive chain on one GPU.  `.rx` is the chain (an RxChain view); a block's channel is the carrier's index into `bins`.  shift:
+    the channeliser's frequency shift (include/tetra_shift.h, 2^-32 cycles per input sample) for carriers that share one offset from
+    the bins' centres, e.g. chan_binding.shift_from_hz(12500, 20e6) for half a bin."""
 
     def __init__(self, bins, n_channels=800, taps_per_channel=8, decimation=None, max_in=1 << 20, device=-1, chan_cutoff_rel=1.2,
                  chan_flags=0, interp=18, decim=25, taps_per_phase=16, resamp_cutoff_rel=1.0, resamp_kaiser_beta=6.0, kinds=0, flags=0,
-                 demod_flags=0, **params):
+                 demod_flags=0, shift=0, **params):
         self._lib = _lib()
         cfg = default_config()
         cfg.chan.n_channels, cfg.chan.taps_per_channel = n_channels, taps_per_channel
@@ -117,6 +126,17 @@ class WidebandRx:
         self._h = h
         max_samples = int(((self.D - 1 + max_in) // self.D) * interp // decim + 1)
         self.rx = _ChainView(self._lib.tetra_wbrx_rx(h), self.n_bins, max_samples)
+        if shift:
+            self.set_shift(shift)
+
+    def set_shift(self, inc):
+        """tetra_wbrx_set_shift: forwards to the channeliser; between process calls, from the next call's first frame."""
+        self._chk(self._lib.tetra_wbrx_set_shift(self._h, int(inc) & 0xffffffff), "tetra_wbrx_set_shift")
+
+    def get_shift(self):
+        v = C.c_uint32(0)
+        self._chk(self._lib.tetra_wbrx_get_shift(self._h, C.byref(v)), "tetra_wbrx_get_shift")
+        return int(v.value)
 
     def close(self):
         if getattr(self, "rx", None) is not None:

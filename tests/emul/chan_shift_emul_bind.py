@@ -1,0 +1,76 @@
+"""ctypes binding of tests/emul/chan_shift_emul.cpp (host emulation of the frequency-shifted FFT channeliser kernel; TEST TOOL).
+Compiles on first use."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(os.path.dirname(_HERE))
+_SO = os.path.join(_HERE, "libchan_shift_emul.so")
+_lib = None
+
+
+def build():
+    deps = [os.path.join(_HERE, "chan_shift_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "chan_fft_core.hpp")]
+    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
+        tmp = _SO + ".tmp.%d" % os.getpid()
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", deps[0], "-o", tmp], check=True)
+        os.replace(tmp, _SO)
+    return _SO
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = C.CDLL(build())
+        L.chan_fft_shift_emul_fmt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_uint,
+                                              C.c_int, C.c_void_p]
+        L.chan_fft_shift_emul_fmt.restype = C.c_int
+        L.chan_shift_phasor.argtypes = [C.c_uint, C.c_void_p]
+        _lib = L
+    return _lib
+
+
+def phasor(ph):
+    out = np.zeros(2, np.float32)
+    lib().chan_shift_phasor(int(ph) & 0xffffffff, out.ctypes.data)
+    return complex(out[0], out[1])
+
+
+class ChanFftShiftEmul:
+    """The shifted FFT kernel's arithmetic for M = 800, D = 400, P taps per channel, with the handle's carried state: delay line,
+    sub-frame phase, absolute position (the phase reference) and the shift.  force_shift_code: run the SHIFT = true lane code even
+    for inc == 0 (the library dispatches inc == 0 to the un-shifted kernels)."""
+
+    def __init__(self, P, proto, inc=0, force_shift_code=False):
+        self.P, self.L = P, 800 * P
+        self.h = np.ascontiguousarray(proto, np.float32)
+        self.hist = np.zeros(self.L - 1, np.complex64)
+        self.phase, self.consumed = 0, 0
+        self.inc, self.mode = int(inc) & 0xffffffff, int(bool(force_shift_code))
+
+    def set_shift(self, inc):
+        self.inc = int(inc) & 0xffffffff
+
+    def process(self, x):
+        """x: complex64 samples, or integer I / Q pairs [n][2] int16 / int8."""
+        x = np.ascontiguousarray(x)
+        if x.dtype == np.int16 or x.dtype == np.int8:
+            fmt = 1 if x.dtype == np.int16 else 2
+            xc = (x[:, 0].astype(np.float32) + 1j * x[:, 1].astype(np.float32)).astype(np.complex64) / np.float32(32768 if fmt == 1 else 128)
+        else:
+            fmt, x = 0, np.ascontiguousarray(x, np.complex64)
+            xc = x
+        frames = (self.phase + len(x)) // 400
+        out = np.full((max(frames, 1), 800), np.nan + 0j, np.complex64)      # every stored element must be written
+        # exact-size buffers in their own allocations (no slack behind the new samples: the kernel must not read past them)
+        xs = x.copy() if len(x) else np.zeros((1, 2), x.dtype) if fmt else np.zeros(1, np.complex64)
+        got = lib().chan_fft_shift_emul_fmt(self.hist.ctypes.data, xs.ctypes.data, fmt, len(x), self.P, self.phase, self.consumed,
+                                            self.h.ctypes.data, self.inc, self.mode, out.ctypes.data)
+        assert got == frames
+        self.hist = np.concatenate([self.hist, xc])[len(xc):].copy()
+        self.phase = (self.phase + len(x)) % 400
+        self.consumed += len(x)
+        return out[:frames]
