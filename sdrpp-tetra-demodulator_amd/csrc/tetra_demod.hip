@@ -3,8 +3,9 @@
 // The whole chain runs in ONE kernel, k_fused (kernel_fused.hpp): AGC -> band-edge FLL -> RRC matched filter -> ML timing
 // recovery -> pi/4 Costas -> slicer -> differential decoder -> bit unpacker, as specialised waves connected by LDS rings.  Three
 // workgroup shapes of the one template: 16 channels in six waves (one workgroup per CU up to 4096 channels), 32 channels in
-// eight waves (more than 16 channels per CU) and 4 channels (at most 4 channels per CU); tetra_demod_create plans which
-// channels take which shape, the results are identical bit for bit.  Filters of 73 .. 129 taps take the LONG variant of the 4- or
+// eight waves (more than 16 channels per CU) and 4 channels (at most 4 channels per CU); host::plan_launch (launch_plan.hpp) says
+// which channels take which shape -- computed wherever a design is committed (create, the setters), read by every process call --
+// and the results are identical bit for bit.  Filters of 73 .. 129 taps take the LONG variant of the 4- or
 // the 16-channel shape (FLL rows of 16 x 9 / 8 x 17 taps, 128 delay-line samples); timing loops below 0.07 samples per symbol -- and, on request, the
 // long filters -- run in k_generic (kernel_generic.hpp): one lane per channel, same arithmetic.  (The two-kernel pipeline of
 // round 1 -- k1_agc_fll_rrc / k2_sync_slice with an HBM scratch in between -- was retired in ABI 2; `git log` has it.)
@@ -27,6 +28,7 @@
 #include "demod_core.hpp"
 #include "design.hpp"
 #include "hip_host.hpp"
+#include "launch_plan.hpp"
 
 using namespace tdm;
 
@@ -34,9 +36,6 @@ namespace {
 
 constexpr int kTinyCallSamples = 768;           // tetra_demod_process: calls of at most this many samples per channel run in place (below)
 constexpr int kYHist = kInterpTaps - 1;         // COMPLEX_FD's delay buffer: 7 RRC outputs in front of the new ones
-constexpr int kWg16ClocksPerSample = 258;       // measured shader clocks per sample of one workgroup round: 3.86 ms per 36000 samples (profiles/r03)
-constexpr int kWg32ClocksPerSample = 348;       // 32-channel workgroup: 5.21 ms per 36000 samples
-constexpr int kWg4ClocksPerSample = 223;        // 4-channel workgroup: 3.33 ms per 36000 samples
 
 __device__ __forceinline__ Pair<float> ld_pair(const float2* p) {
     float2 v = *p;
@@ -225,12 +224,8 @@ struct tetra_demod {
     DevMem<float> d_g_be_a, d_g_be_b, d_g_rrc;   // un-padded tap tables for it, [kGenMaxTaps] each
     DevMem<float> mu, omega, cph, cfr, ph2;
     DevMem<int> offset, prev;
-    int n_wide = 0;             // channels [0, n_wide) run in 32-channel workgroups, [n_wide, C) in 16-channel ones ...
-    bool small = false;         // ... or, when they are at most 4 per CU (or the flag forces it), in 4-channel ones
-    bool force_small = false;   // TETRA_FLAG_SMALL_WORKGROUPS
-    bool force_generic = false; // TETRA_FLAG_GENERIC_KERNEL
-    bool force_shape = false;   // TETRA_FLAG_WIDE_WORKGROUPS / _NARROW_: the caller chose
     int cus = 256;
+    host::LaunchPlan plan;      // what a process call launches under `design` (launch_plan.hpp): set wherever a design is committed
     DevMem<int> rrc_valid;      // [C] delay-line samples the RRC may see (tetra_demod.h: tetra_demod_channel_state.rrc_valid)
     DevMem<float2> y;           // TETRA_FLAG_KEEP_RRC_OUT: time-major RRC output scratch [(7 + max_samples)][C]
     DevMem<float2> ybuf;        // COMPLEX_FD delay buffer [C][7]
@@ -297,32 +292,20 @@ int upload_tables(tetra_demod* h) {
         HIP_TRY(h, hipMemcpy(h->d_g_be_b, b.data(), sizeof(float) * kGenMaxTaps, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->d_g_rrc, r.data(), sizeof(float) * kGenMaxTaps, hipMemcpyHostToDevice));
     }
-    if (h->design.ntaps <= kF8Pad && h->design.ntaps_be <= kF8Pad) {
-        std::vector<float> re72(kBePad, 0.f), im72(kBePad, 0.f), rrx(kRrcExt, 0.f);
-        const int o72 = kBePad - h->design.ntaps_be;
-        const int rpad = (8 - ((h->design.ntaps - 1) & 7)) & 7;     // RRC windows start on a multiple of 8, see kernel_fused.hpp
-        for (int k = 0; k < h->design.ntaps_be; k++) {
-            re72[o72 + k] = h->design.be_re[k];
-            im72[o72 + k] = h->design.be_im[k];
-        }
-        for (int k = 0; k < h->design.ntaps; k++) rrx[7 + rpad + k] = h->design.rrc[k];
-        HIP_TRY(h, hipMemcpy(h->d_be_re80, re72.data(), sizeof(float) * kBePad, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_be_im80, im72.data(), sizeof(float) * kBePad, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_rrc_ext, rrx.data(), sizeof(float) * kRrcExt, hipMemcpyHostToDevice));
-    } else {
-        // filters of 73 .. 129 taps: the same tables in the long rows' sizes (kernel_fused.hpp: LONG)
-        std::vector<float> re(kBePadLong, 0.f), im(kBePadLong, 0.f), rrx(kRrcExtLong, 0.f);
-        const int o = kBePadLong - h->design.ntaps_be;
-        const int rpad = (8 - ((h->design.ntaps - 1) & 7)) & 7;
-        for (int k = 0; k < h->design.ntaps_be; k++) {
-            re[o + k] = h->design.be_re[k];
-            im[o + k] = h->design.be_im[k];
-        }
-        for (int k = 0; k < h->design.ntaps; k++) rrx[7 + rpad + k] = h->design.rrc[k];
-        HIP_TRY(h, hipMemcpy(h->d_be_re80, re.data(), sizeof(float) * kBePadLong, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_be_im80, im.data(), sizeof(float) * kBePadLong, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_rrc_ext, rrx.data(), sizeof(float) * kRrcExtLong, hipMemcpyHostToDevice));
+    // the fused kernel's padded tables; filters of 73 .. 129 taps: the same tables in the long rows' sizes (kernel_fused.hpp: LONG)
+    const bool long_tables = h->design.ntaps > kF8Pad || h->design.ntaps_be > kF8Pad;
+    const int be_pad = long_tables ? kBePadLong : kBePad, rrc_ext = long_tables ? kRrcExtLong : kRrcExt;
+    std::vector<float> re(be_pad, 0.f), im(be_pad, 0.f), rrx(rrc_ext, 0.f);
+    const int o = be_pad - h->design.ntaps_be;
+    const int rpad = (8 - ((h->design.ntaps - 1) & 7)) & 7;     // RRC windows start on a multiple of 8, see kernel_fused.hpp
+    for (int k = 0; k < h->design.ntaps_be; k++) {
+        re[o + k] = h->design.be_re[k];
+        im[o + k] = h->design.be_im[k];
     }
+    for (int k = 0; k < h->design.ntaps; k++) rrx[7 + rpad + k] = h->design.rrc[k];
+    HIP_TRY(h, hipMemcpy(h->d_be_re80, re.data(), sizeof(float) * be_pad, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_be_im80, im.data(), sizeof(float) * be_pad, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_rrc_ext, rrx.data(), sizeof(float) * rrc_ext, hipMemcpyHostToDevice));
     return TETRA_OK;
 }
 
@@ -398,16 +381,11 @@ int new_overruns(tetra_demod* h) {
     return fresh > 0 ? (int)(fresh > 0x7fffffff ? 0x7fffffff : fresh) : 0;
 }
 
-// Can a launch of this handle take the generic kernel (kernel_generic.hpp)?  Its parameters, or TETRA_FLAG_GENERIC_KERNEL, decide.
-bool generic_applies(const tetra_demod* h, const host::Design& d) {
-    return host::needs_generic(d) || ((host::needs_long(d) || host::deep_level(d) == 2) && h->force_generic);
-}
-bool generic_applies(const tetra_demod* h) { return generic_applies(h, h->design); }
 // The generic kernel's HBM scratch -- 2 x 8 B x C x (max_samples + 128), the delay lines of a whole call -- is held exactly while
-// generic_applies(): allocated by create / the setter that moves the handle there (so that the stream-asynchronous process entry
-// point never allocates or synchronises), released by the setter that moves it away.  The device is idle when this runs.
-int sync_generic_scratch(tetra_demod* h, const host::Design& d) {
-    if (!generic_applies(h, d)) {
+// the plan says k_generic: allocated by create / the setter that moves the handle there (so that the stream-asynchronous process
+// entry point never allocates or synchronises), released by the setter that moves it away.  The device is idle when this runs.
+int sync_generic_scratch(tetra_demod* h, const host::LaunchPlan& plan) {
+    if (!plan.generic) {
         h->g_xs.reset();
         h->g_ys.reset();
         return TETRA_OK;
@@ -422,7 +400,99 @@ int sync_generic_scratch(tetra_demod* h, const host::Design& d) {
     }
     return TETRA_OK;
 }
-int sync_generic_scratch(tetra_demod* h) { return sync_generic_scratch(h, h->design); }
+
+// Commits a design: the handle's parameters and its launch plan follow it, the generic kernel's scratch is allocated (a failure leaves
+// the handle as it was) or, when the parameters have left that kernel's domain, released.
+int commit_design(tetra_demod* h, const host::DesignParams& np, const host::Design& nd) {
+    const host::LaunchPlan plan = host::plan_launch(h->C, h->cus, h->cfg.flags, nd);
+    const int rc = sync_generic_scratch(h, plan);
+    if (rc != TETRA_OK) return rc;
+    h->dp = np;
+    h->design = nd;
+    h->plan = plan;
+    return TETRA_OK;
+}
+
+// FIR::setTaps with more taps keeps the RRC's old taps-1 history samples and zero-fills the newly visible part (quirks handles)
+int shrink_rrc_valid(tetra_demod* h, int old_ntaps) {
+    if (!h->quirks || h->design.ntaps <= old_ntaps) return TETRA_OK;
+    hipLaunchKernelGGL(k_min_i32, dim3((h->C + 255) / 256), dim3(256), 0, 0, h->rrc_valid, old_ntaps - 1, h->C);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(0));
+    return TETRA_OK;
+}
+
+// "Let the asynchronous calls still in flight finish" (they run on their own three streams; state order)
+int drain_async(tetra_demod* h) {
+    if (!h->as.ready) return TETRA_OK;
+    for (Stream* st : { &h->as.s_in, &h->as.s_k, &h->as.s_out }) HIP_TRY(h, hipStreamSynchronize(*st));
+    return TETRA_OK;
+}
+
+// the handle's own (non-blocking) stream, created on first use
+int ensure_own_stream(tetra_demod* h) {
+    if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
+    return TETRA_OK;
+}
+
+static_assert(host::kPlanCh == kFCh && host::kPlanChWide == kFChWide && host::kPlanChSmall == kFChSmall,
+              "launch_plan.hpp plans the workgroup shapes kernel_fused.hpp has");
+
+// What GenericParams and FusedParams have in common (same members, same names): the call's input and outputs, the channels' state,
+// the loop constants.  Each kernel's own tables and extras are its caller's.
+template <class P> void fill_common_params(P& p, const tetra_demod* h, const float* d_iq, int n_samples, uint8_t* d_bits, int bits_stride,
+                                           int32_t* d_n_bits, float* d_sym) {
+    p.iq = reinterpret_cast<const float2*>(d_iq);
+    if (h->cfg.layout == TETRA_LAYOUT_CHANNEL_MAJOR) { p.in_ch_stride = n_samples; p.in_t_stride = 1; }
+    else { p.in_ch_stride = 1; p.in_t_stride = h->C; }
+    p.n = n_samples; p.n_channels = h->C;
+    p.agc_g = h->agc_g; p.fll_ph = h->fll_ph; p.fll_fr = h->fll_fr; p.hist = h->hist;
+    p.rrc_valid = h->rrc_valid;
+    p.mu = h->mu; p.omega = h->omega; p.offset = h->offset;
+    p.cph = h->cph; p.cfr = h->cfr; p.ph2 = h->ph2; p.prev = h->prev; p.ybuf = h->ybuf;
+    p.ntaps = h->design.ntaps;
+    p.bank = h->d_bank;
+    p.bits = d_bits; p.bits_stride = bits_stride; p.n_bits = d_n_bits;
+    p.sym = reinterpret_cast<float2*>(d_sym); p.sym_stride = bits_stride / 2;
+    if (h->taps_sym() && !p.sym) { p.sym = h->q_sym; p.sym_stride = h->q_sym_stride; }      // a post-launch kernel reads the symbols
+    p.y_dbg = h->keep_y ? h->y : nullptr;
+    p.overruns = h->d_overruns;
+    p.k1 = h->design.k1; p.k2 = h->design.k2;
+}
+
+// One launch of k_fused<true, false, CH, DEEP, LONG> over channels [first, first + count).
+template <int CH, int DEEP, bool LONG>
+void launch_fused(const tetra_demod* h, const FusedParams& pf, int first, int count, bool far_was_valid, hipStream_t s) {
+    typename FusedArgs<CH, LONG>::type p;
+    static_cast<FusedParams&>(p) = pf;
+    p.ch_base = first;
+    if constexpr (CH == kFChSmall) p.cut_flag4 = h->cut_flag;
+    if constexpr (LONG) {      // the long rows also carry the 48 delay-line samples in front of hist's 80
+        p.hist_far = h->hist_far;
+        p.far_valid = far_was_valid ? 1 : 0;
+    }
+    hipLaunchKernelGGL((k_fused<true, false, CH, DEEP, LONG>), dim3((count + CH - 1) / CH), dim3(fused_threads(CH)), 0, s, p);
+}
+
+// The launches of a fused call as the plan says: channels [0, n_wide) in 32-channel workgroups, the rest in 16- or 4-channel ones -- at
+// most two, back to back on the stream.  Exactly the instantiations that exist: the deep symbol ring's first level for the 16- and
+// 4-channel shapes, its second for the 4-channel shape, none for the 32-channel shape (plan_launch never asks for another).
+bool launch_fused_plan(const tetra_demod* h, const FusedParams& pf, hipStream_t s) {
+    const host::LaunchPlan& plan = h->plan;
+    const int first = plan.n_wide, count = h->C - first;
+    if (first > 0) launch_fused<kFChWide, 0, false>(h, pf, 0, first, h->far_valid, s);
+    if (count == 0) return true;
+    constexpr auto key = [](int ch, int deep, bool long_rows) { return ch * 8 + deep * 2 + (long_rows ? 1 : 0); };
+#define TETRA_REST(CH, DEEP, LONG) case key(CH, DEEP, LONG): launch_fused<CH, DEEP, LONG>(h, pf, first, count, h->far_valid, s); return true
+    switch (key(plan.rest_ch, plan.deep, plan.long_rows)) {
+    TETRA_REST(kFChSmall, 2, true); TETRA_REST(kFChSmall, 1, true); TETRA_REST(kFChSmall, 0, true);
+    TETRA_REST(kFChSmall, 2, false); TETRA_REST(kFChSmall, 1, false); TETRA_REST(kFChSmall, 0, false);
+    TETRA_REST(kFCh, 1, true); TETRA_REST(kFCh, 0, true);
+    TETRA_REST(kFCh, 1, false); TETRA_REST(kFCh, 0, false);
+    default: return false;
+    }
+#undef TETRA_REST
+}
 
 }  // namespace
 
@@ -575,32 +645,9 @@ int tetra_demod_create(const tetra_demod_config_t* cfg, tetra_demod_t** out) {
     h->user_be = cfg->bandedge_taps != nullptr;
     h->quirks = (cfg->flags & TETRA_FLAG_REFERENCE_QUIRKS) != 0;
     h->keep_y = (cfg->flags & TETRA_FLAG_KEEP_RRC_OUT) != 0;
-    {
-        // Workgroup shapes.  16 channels per workgroup is the fastest way through ONE workgroup (kWg16 clocks per sample) and
-        // right while there is at most one per CU; the 32-channel workgroup (FLL rows of 4 lanes per channel: the loop code
-        // of an FLL wave serves twice the channels; kWg32 clocks per sample) gets a CU through 32 channels in 1.3x that time.
-        // Plan: whole rounds of 32-channel workgroups, then the rest in whichever shape is through first (rounds of
-        // workgroups per CU x clocks per round) -- at most two launches per call; the flags force one shape for everything.
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        cus = cus > 0 ? cus : 256;
-        // whole rounds of 32-channel workgroups first; what is left takes whichever shape gets it through in less time: one
-        // round of 4-channel workgroups (each has a CU to itself and the shortest FLL step: kWg4 clocks per sample) if there
-        // are at most 4 channels per CU, else rounds of 16-channel ones, or one more round of 32-channel ones
-        h->cus = cus;
-        const long long per_round32 = (long long)kFChWide * cus;
-        const long long full = (h->C / per_round32) * per_round32, rest = h->C - full;
-        const long long r16 = ((rest + kFCh - 1) / kFCh + cus - 1) / cus, r32 = ((rest + kFChWide - 1) / kFChWide + cus - 1) / cus;
-        const long long t16 = r16 * kWg16ClocksPerSample, t32 = r32 * kWg32ClocksPerSample;
-        const long long t4 = rest <= (long long)kFChSmall * cus ? (long long)kWg4ClocksPerSample : t16 + t32 + 1;
-        const bool rest_wide = rest > 0 && t32 < t16 && t32 < t4;
-        h->n_wide = (int)(rest_wide ? h->C : full);
-        h->small = rest > 0 && !rest_wide && t4 < t16;
-        if (cfg->flags & TETRA_FLAG_WIDE_WORKGROUPS) { h->n_wide = h->C; h->small = false; h->force_shape = true; }
-        if (cfg->flags & TETRA_FLAG_NARROW_WORKGROUPS) { h->n_wide = 0; h->small = false; h->force_shape = true; }
-        if (cfg->flags & TETRA_FLAG_SMALL_WORKGROUPS) { h->n_wide = 0; h->small = h->force_small = true; }
-        h->force_generic = (cfg->flags & TETRA_FLAG_GENERIC_KERNEL) != 0;
-    }
+    (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (h->cus <= 0) h->cus = 256;
+    h->plan = host::plan_launch(h->C, h->cus, cfg->flags, h->design);
     if (h->keep_y) A(h->y, C * ((size_t)h->max_samples + kYHist));
     A(h->ybuf, C * kYHist);
     if (cfg->flags & TETRA_FLAG_QUALITY) {
@@ -625,7 +672,7 @@ int tetra_demod_create(const tetra_demod_config_t* cfg, tetra_demod_t** out) {
             if (rc == TETRA_OK && hipEventCreate(e.put()) != hipSuccess) rc = TETRA_ERR_HIP;
     if (rc == TETRA_OK) rc = upload_tables(h);
     if (rc == TETRA_OK) rc = reset_range(h, 0, h->C, true);
-    if (rc == TETRA_OK) rc = sync_generic_scratch(h);
+    if (rc == TETRA_OK) rc = sync_generic_scratch(h, h->plan);
     if (rc != TETRA_OK) {
         int st = (h->last_hip == (int)hipErrorOutOfMemory) ? TETRA_ERR_NOMEM : rc;
         delete h;
@@ -658,172 +705,86 @@ int tetra_demod_process_device(tetra_demod_t* h, const float* d_iq, int n_sample
         HIP_TRY(h, hipMemsetAsync(d_n_bits, 0, sizeof(int32_t) * (size_t)h->C, s));
         return TETRA_OK;
     }
+    const host::LaunchPlan& plan = h->plan;
     const Event* ev = h->ev[h->n_calls % tetra_demod::kEvSlots];
-    const bool long_rows = host::needs_long(h->design) && !h->force_generic;
-    if (generic_applies(h)) {
-        // timing loops slower than 0.07 samples per symbol (and, with TETRA_FLAG_GENERIC_KERNEL, those below 0.27 and filters of more than 72 taps): one
-        // lane per channel, delay lines in an HBM scratch (kernel_generic.hpp) that create / the setters hold ready (sync_generic_scratch)
-        const size_t xs_stride = (size_t)kGenHist + (size_t)h->max_samples, ys_stride = (size_t)kYHist + (size_t)h->max_samples;
+    GenericParams pg;
+    FusedParams pf;
+#ifdef TETRA_DEMOD_DEBUG
+    // Debug builds only (profiles/build_debug.sh): TETRA_DEMOD_PROFILE=<file> appends the per-role busy clocks of every
+    // launch to <file>.  The release library has neither the getenv nor the instrumented instantiation.
+    const char* prof_path = std::getenv("TETRA_DEMOD_PROFILE");
+    const size_t prof_wgs = (size_t)(h->C + kFCh - 1) / kFCh;
+    bool profiling = false;
+#endif
+    if (plan.generic) {
+        // one lane per channel, delay lines in an HBM scratch (kernel_generic.hpp) that create / the setters hold ready (sync_generic_scratch)
         if (!h->g_xs || !h->g_ys) return TETRA_ERR_NOMEM;
-        GenericParams pg;
-        pg.iq = reinterpret_cast<const float2*>(d_iq);
-        if (h->cfg.layout == TETRA_LAYOUT_CHANNEL_MAJOR) { pg.in_ch_stride = n_samples; pg.in_t_stride = 1; }
-        else { pg.in_ch_stride = 1; pg.in_t_stride = h->C; }
-        pg.n = n_samples; pg.n_channels = h->C;
-        pg.agc_g = h->agc_g; pg.fll_ph = h->fll_ph; pg.fll_fr = h->fll_fr; pg.hist = h->hist; pg.hist_far = h->hist_far;
-        pg.far_valid = h->far_valid ? 1 : 0;
-        pg.rrc_valid = h->rrc_valid; pg.mu = h->mu; pg.omega = h->omega; pg.offset = h->offset;
-        pg.cph = h->cph; pg.cfr = h->cfr; pg.ph2 = h->ph2; pg.prev = h->prev; pg.ybuf = h->ybuf;
-        pg.be_a = h->d_g_be_a; pg.be_b = h->d_g_be_b; pg.rrc = h->d_g_rrc; pg.ntaps = h->design.ntaps; pg.ntaps_be = h->design.ntaps_be;
-        pg.bank = h->d_bank;
-        pg.xs = h->g_xs; pg.ys = h->g_ys; pg.xs_stride = (long long)xs_stride; pg.ys_stride = (long long)ys_stride;
-        pg.bits = d_bits; pg.bits_stride = bits_stride; pg.n_bits = d_n_bits;
-        pg.sym = reinterpret_cast<float2*>(d_sym); pg.sym_stride = bits_stride / 2;
-        if (h->taps_sym() && !pg.sym) { pg.sym = h->q_sym; pg.sym_stride = h->q_sym_stride; }
-        pg.overruns = h->d_overruns; pg.cut_flag = h->cut_flag;
-        pg.y_dbg = h->keep_y ? h->y : nullptr;
-        pg.k1 = h->design.k1; pg.k2 = h->design.k2;
-        HIP_TRY(h, hipEventRecord(ev[0], s));
-        {   // about eight waves per CU when there are enough channels, never more than 64 channels per wave
-            int lanes = h->C / (8 * h->cus);
-            lanes = lanes < 1 ? 1 : lanes > 64 ? 64 : lanes;
-            pg.lanes = lanes;
-            hipLaunchKernelGGL(k_generic, dim3((h->C + lanes - 1) / lanes), dim3(64), 0, s, pg);
-        }
-        if (h->q_ring)
-            hipLaunchKernelGGL(k_quality, dim3(h->C), dim3(64), 0, s, pg.sym, pg.sym_stride, d_n_bits, h->q_ring, h->q_ptr, h->q_disp,
-                               h->q_err, h->q_sync);
-        if (h->cd_blk)
-            hipLaunchKernelGGL(k_constellation, dim3(h->C), dim3(256), 0, s, pg.sym, pg.sym_stride, d_n_bits, h->cd_blk, h->cd_part,
-                               h->cd_fill, h->cd_blocks);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(ev[1], s));
-        h->n_calls++;
-        h->far_valid = true;
-        return TETRA_OK;
-    }
-    const bool far_was_valid = h->far_valid;
-    {
-        FusedParams pf;
-        pf.iq = reinterpret_cast<const float2*>(d_iq);
-        if (h->cfg.layout == TETRA_LAYOUT_CHANNEL_MAJOR) { pf.in_ch_stride = n_samples; pf.in_t_stride = 1; }
-        else { pf.in_ch_stride = 1; pf.in_t_stride = h->C; }
-        pf.n = n_samples; pf.n_channels = h->C; pf.ch_base = 0;
-        pf.agc_g = h->agc_g; pf.fll_ph = h->fll_ph; pf.fll_fr = h->fll_fr; pf.hist = h->hist;
-        pf.rrc_valid = h->rrc_valid;
-        pf.mu = h->mu; pf.omega = h->omega; pf.offset = h->offset;
-        pf.cph = h->cph; pf.cfr = h->cfr; pf.ph2 = h->ph2; pf.prev = h->prev; pf.ybuf = h->ybuf;
-        pf.be_re80 = h->d_be_re80; pf.be_im80 = h->d_be_im80; pf.rrc_ext = h->d_rrc_ext; pf.ntaps = h->design.ntaps;
-        pf.bank = h->d_bank;
-        pf.bits = d_bits; pf.bits_stride = bits_stride; pf.n_bits = d_n_bits; pf.sym = reinterpret_cast<float2*>(d_sym);
-        pf.y_dbg = h->keep_y ? h->y : nullptr;
-        pf.overruns = h->d_overruns;
-        pf.sym_stride = bits_stride / 2;
-        if (h->taps_sym() && !pf.sym) { pf.sym = h->q_sym; pf.sym_stride = h->q_sym_stride; }   // the statistic reads the symbols
-        pf.k1 = h->design.k1; pf.k2 = h->design.k2;
+        fill_common_params(pg, h, d_iq, n_samples, d_bits, bits_stride, d_n_bits, d_sym);
+        pg.hist_far = h->hist_far; pg.far_valid = h->far_valid ? 1 : 0;
+        pg.be_a = h->d_g_be_a; pg.be_b = h->d_g_be_b; pg.rrc = h->d_g_rrc; pg.ntaps_be = h->design.ntaps_be;
+        pg.xs = h->g_xs; pg.ys = h->g_ys;
+        pg.xs_stride = (long long)kGenHist + h->max_samples; pg.ys_stride = (long long)kYHist + h->max_samples;
+        pg.cut_flag = h->cut_flag;
+        pg.lanes = host::generic_lanes(h->C, h->cus);
+    } else {
+        fill_common_params(pf, h, d_iq, n_samples, d_bits, bits_stride, d_n_bits, d_sym);
+        pf.ch_base = 0;
+        pf.be_re80 = h->d_be_re80; pf.be_im80 = h->d_be_im80; pf.rrc_ext = h->d_rrc_ext;
         pf.prof = reinterpret_cast<long long*>(h->cut_flag);      // the non-instrumented 16- / 32-channel kernels read it as the cut flag (kernel_fused.hpp)
-        // channels [0, n_wide) in 32-channel workgroups (see tetra_demod_create; their FLL rows hold 4 x 17 taps), the rest in
-        // 16-channel ones: at most two launches, back to back on the stream
-        // (band-edge filters of more than 68 taps do not fit the 32-channel shape's rows: then everything is "the rest")
-        // (the same for a timing loop that may emit several symbols from one offset: the deep symbol ring exists for the 16-
-        // and 4-channel shapes)
-        const bool deep = host::needs_deep(h->design);
-        const bool deeper = host::deep_level(h->design) == 2;      // more than 3.7 symbols per sample: the 4-channel shape's 1024-deep ring
-        const int n_wide = h->design.ntaps_be <= kF4Pad && !deep && !long_rows ? h->n_wide : 0;
-        // (long rows: 4-channel workgroups while every one of them has a CU to itself, 16-channel ones beyond -- or as the flags say)
-        const bool rest_small = deeper || h->force_small || (long_rows ? !h->force_shape && h->C <= kFChSmall * h->cus
-                                                             : h->small && h->C - n_wide <= kFChSmall * h->cus);
-        const dim3 gw((n_wide + kFChWide - 1) / kFChWide), gf((h->C - n_wide + kFCh - 1) / kFCh),
-            gs((h->C - n_wide + kFChSmall - 1) / kFChSmall);
         // the FLL's loop filter runs with alpha = 0 (fll.cpp:25; design.hpp never produces anything else): only those kernels exist
         if (pf.k1.fll_alpha != 0.0f) return TETRA_ERR_UNSUPPORTED;
-        bool profiling = false;
-        (void)profiling;
 #ifdef TETRA_DEMOD_DEBUG
-        // Debug builds only (profiles/build_debug.sh): TETRA_DEMOD_PROFILE=<file> appends the per-role busy clocks of every
-        // launch to <file>.  The release library has neither the getenv nor the instrumented instantiation.
-        const char* prof_path = std::getenv("TETRA_DEMOD_PROFILE");
-        if (prof_path && n_wide == 0 && !rest_small && !long_rows) {      // (the instrumented instantiation exists for the regular rows only)
-            const size_t nwg = (size_t)gf.x;
-            if (!h->d_prof) HIP_TRY(h, h->d_prof.reserve(sizeof(long long) * 8 * nwg));
-            HIP_TRY(h, hipMemsetAsync(h->d_prof, 0, sizeof(long long) * 8 * nwg, s));
+        if (prof_path && plan.n_wide == 0 && plan.rest_ch == kFCh && !plan.long_rows) {      // (the instrumented instantiation exists for the regular rows only)
+            if (!h->d_prof) HIP_TRY(h, h->d_prof.reserve(sizeof(long long) * 8 * prof_wgs));
+            HIP_TRY(h, hipMemsetAsync(h->d_prof, 0, sizeof(long long) * 8 * prof_wgs, s));
             pf.prof = h->d_prof;
             profiling = true;
         }
 #endif
-        HIP_TRY(h, hipEventRecord(ev[0], s));
-#ifdef TETRA_DEMOD_DEBUG
-        if (profiling && !deep) { FusedParamsT<kFCh> pp; static_cast<FusedParams&>(pp) = pf; hipLaunchKernelGGL((k_fused<true, true>), gf, dim3(kFThreads), 0, s, pp); }
-        else
-#endif
-        {
-            if (n_wide > 0) {
-                const dim3 tw(fused_threads(kFChWide));
-                pf.ch_base = 0;
-                { FusedParamsT<kFChWide> pw; static_cast<FusedParams&>(pw) = pf; hipLaunchKernelGGL((k_fused<true, false, kFChWide>), gw, tw, 0, s, pw); }
-            }
-            if (n_wide < h->C && rest_small) {
-                const dim3 ts(fused_threads(kFChSmall));
-                pf.ch_base = n_wide;
-                FusedParamsT<kFChSmall> ps;
-                static_cast<FusedParams&>(ps) = pf;
-                ps.cut_flag4 = h->cut_flag;
-                if (long_rows) {
-                    // filters of 73 .. 129 taps: FLL rows of 16 x 9 taps, 4 channels per workgroup whatever the channel count
-                    FusedParamsLongT<kFChSmall> pl;
-                    static_cast<FusedParamsT<kFChSmall>&>(pl) = ps;
-                    pl.hist_far = h->hist_far;
-                    pl.far_valid = far_was_valid ? 1 : 0;
-                    if (deeper) hipLaunchKernelGGL((k_fused<true, false, kFChSmall, 2, true>), gs, ts, 0, s, pl);
-                    else if (deep) hipLaunchKernelGGL((k_fused<true, false, kFChSmall, 1, true>), gs, ts, 0, s, pl);
-                    else hipLaunchKernelGGL((k_fused<true, false, kFChSmall, 0, true>), gs, ts, 0, s, pl);
-                } else if (deeper) hipLaunchKernelGGL((k_fused<true, false, kFChSmall, 2>), gs, ts, 0, s, ps);
-                else if (deep) hipLaunchKernelGGL((k_fused<true, false, kFChSmall, 1>), gs, ts, 0, s, ps);
-                else hipLaunchKernelGGL((k_fused<true, false, kFChSmall>), gs, ts, 0, s, ps);
-            } else if (n_wide < h->C) {
-                pf.ch_base = n_wide;
-                FusedParamsT<kFCh> pn;
-                static_cast<FusedParams&>(pn) = pf;
-                if (long_rows) {
-                    // filters of 73 .. 129 taps on more than 1024 channels: FLL rows of 8 x 17 taps
-                    FusedParamsLongT<kFCh> pl;
-                    static_cast<FusedParamsT<kFCh>&>(pl) = pn;
-                    pl.hist_far = h->hist_far;
-                    pl.far_valid = far_was_valid ? 1 : 0;
-                    if (deep) hipLaunchKernelGGL((k_fused<true, false, kFCh, 1, true>), gf, dim3(kFThreads), 0, s, pl);
-                    else hipLaunchKernelGGL((k_fused<true, false, kFCh, 0, true>), gf, dim3(kFThreads), 0, s, pl);
-                } else if (deep) hipLaunchKernelGGL((k_fused<true, false, kFCh, 1>), gf, dim3(kFThreads), 0, s, pn);
-                else hipLaunchKernelGGL((k_fused<true>), gf, dim3(kFThreads), 0, s, pn);
-            }
-        }
-        if (h->q_ring)
-            hipLaunchKernelGGL(k_quality, dim3(h->C), dim3(64), 0, s, pf.sym, pf.sym_stride, d_n_bits, h->q_ring, h->q_ptr, h->q_disp,
-                               h->q_err, h->q_sync);
-        if (h->cd_blk)
-            hipLaunchKernelGGL(k_constellation, dim3(h->C), dim3(256), 0, s, pf.sym, pf.sym_stride, d_n_bits, h->cd_blk, h->cd_part,
-                               h->cd_fill, h->cd_blocks);
-        HIP_TRY(h, hipGetLastError());
-        h->far_valid = long_rows;      // the fused kernel carries the newest 80 delay-line samples only -- its long rows all 128
-        HIP_TRY(h, hipEventRecord(ev[1], s));
-        h->n_calls++;
-#ifdef TETRA_DEMOD_DEBUG
-        if (profiling) {
-            const size_t nwg = (size_t)gf.x;
-            std::vector<long long> host(8 * nwg);
-            HIP_TRY(h, hipStreamSynchronize(s));
-            HIP_TRY(h, hipMemcpy(host.data(), h->d_prof, sizeof(long long) * host.size(), hipMemcpyDeviceToHost));
-            if (FILE* f = std::fopen(prof_path, "a")) {
-                double sum[8] = { 0 };
-                for (size_t w = 0; w < nwg; w++)
-                    for (int r = 0; r < 8; r++) sum[r] += (double)host[8 * w + r];
-                std::fprintf(f, "{\"n\": %d, \"workgroups\": %zu, \"mean_busy_clocks\": {\"E\": %.0f, \"D\": %.0f, \"F0\": %.0f, \"F1\": %.0f, \"A\": %.0f, \"C\": %.0f}, \"mean_total_clocks\": %.0f}\n",
-                             n_samples, nwg, sum[0] / nwg, sum[1] / nwg, sum[2] / nwg, sum[3] / nwg, sum[4] / nwg, sum[5] / nwg, sum[7] / nwg);
-                std::fclose(f);
-            }
-        }
-#endif
-        return TETRA_OK;
     }
+    HIP_TRY(h, hipEventRecord(ev[0], s));
+    if (plan.generic) {
+        hipLaunchKernelGGL(k_generic, dim3((h->C + pg.lanes - 1) / pg.lanes), dim3(64), 0, s, pg);
+    } else {
+#ifdef TETRA_DEMOD_DEBUG
+        if (profiling && !plan.deep) {
+            FusedParamsT<kFCh> pp;
+            static_cast<FusedParams&>(pp) = pf;
+            hipLaunchKernelGGL((k_fused<true, true>), dim3(prof_wgs), dim3(kFThreads), 0, s, pp);
+        } else
+#endif
+        if (!launch_fused_plan(h, pf, s)) return TETRA_ERR_UNSUPPORTED;
+    }
+    const float2* sym = plan.generic ? pg.sym : pf.sym;      // where the launch leaves its symbols: the taps behind it read them
+    const long long sym_stride = plan.generic ? pg.sym_stride : pf.sym_stride;
+    if (h->q_ring)
+        hipLaunchKernelGGL(k_quality, dim3(h->C), dim3(64), 0, s, sym, sym_stride, d_n_bits, h->q_ring, h->q_ptr, h->q_disp,
+                           h->q_err, h->q_sync);
+    if (h->cd_blk)
+        hipLaunchKernelGGL(k_constellation, dim3(h->C), dim3(256), 0, s, sym, sym_stride, d_n_bits, h->cd_blk, h->cd_part,
+                           h->cd_fill, h->cd_blocks);
+    HIP_TRY(h, hipGetLastError());
+    // the generic kernel carries all 128 delay-line samples, the fused kernel the newest 80 only -- its long rows all 128
+    h->far_valid = plan.generic || plan.long_rows;
+    HIP_TRY(h, hipEventRecord(ev[1], s));
+    h->n_calls++;
+#ifdef TETRA_DEMOD_DEBUG
+    if (profiling) {
+        const size_t nwg = prof_wgs;
+        std::vector<long long> host(8 * nwg);
+        HIP_TRY(h, hipStreamSynchronize(s));
+        HIP_TRY(h, hipMemcpy(host.data(), h->d_prof, sizeof(long long) * host.size(), hipMemcpyDeviceToHost));
+        if (FILE* f = std::fopen(prof_path, "a")) {
+            double sum[8] = { 0 };
+            for (size_t w = 0; w < nwg; w++)
+                for (int r = 0; r < 8; r++) sum[r] += (double)host[8 * w + r];
+            std::fprintf(f, "{\"n\": %d, \"workgroups\": %zu, \"mean_busy_clocks\": {\"E\": %.0f, \"D\": %.0f, \"F0\": %.0f, \"F1\": %.0f, \"A\": %.0f, \"C\": %.0f}, \"mean_total_clocks\": %.0f}\n",
+                         n_samples, nwg, sum[0] / nwg, sum[1] / nwg, sum[2] / nwg, sum[3] / nwg, sum[4] / nwg, sum[5] / nwg, sum[7] / nwg);
+            std::fclose(f);
+        }
+    }
+#endif
+    return TETRA_OK;
 }
 
 int tetra_demod_process_resident(tetra_demod_t* h, const float* d_iq, int n_samples, uint8_t* d_bits, int bits_stride,
@@ -831,13 +792,9 @@ int tetra_demod_process_resident(tetra_demod_t* h, const float* d_iq, int n_samp
     if (!h) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->as.ready) {      // like tetra_demod_process: asynchronous calls still in flight finish first (state order)
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_in));
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_k));
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_out));
-    }
-    if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
-    const int rc = tetra_demod_process_device(h, d_iq, n_samples, d_bits, bits_stride, d_n_bits, d_sym, h->own_stream);
+    int rc;
+    if ((rc = drain_async(h)) || (rc = ensure_own_stream(h))) return rc;
+    rc = tetra_demod_process_device(h, d_iq, n_samples, d_bits, bits_stride, d_n_bits, d_sym, h->own_stream);
     if (rc != TETRA_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
     const int cut = new_overruns(h);
@@ -852,11 +809,8 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
     if (bits_stride & 7) return TETRA_ERR_ALIGN;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->as.ready) {      // asynchronous calls still in flight run on their own streams: let them finish first (state order)
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_in));
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_k));
-        HIP_TRY(h, hipStreamSynchronize(h->as.s_out));
-    }
+    int rc;
+    if ((rc = drain_async(h))) return rc;
     const size_t C = (size_t)h->C;
     const size_t iq_bytes = sizeof(float) * 2 * C * (size_t)n_samples;
     const size_t bits_bytes = C * (size_t)bits_stride;
@@ -873,7 +827,10 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
 #else
     constexpr int kTiny = kTinyCallSamples;
 #endif
-    if (n_samples > 0 && n_samples <= kTiny && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall && !h->tn_disabled) {
+    const bool small_call = n_samples > 0 && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall;
+    if (small_call && (rc = ensure_own_stream(h))) return rc;
+    bool tiny = small_call && n_samples <= kTiny && !h->tn_disabled;
+    if (tiny) {
         // The shortest calls use no copy engine at all: the CPU copies the samples into a page-locked, mapped, coherent block
         // that the AGC wave reads in place over PCIe (a tile ahead, as always), the kernels write n_bits | bits | symbols | a
         // "some channel was cut off" flag straight into a second such block, ONE synchronisation, plain memcpys out.  Measured
@@ -884,7 +841,6 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         // that is cut off additionally leaves a plain store in the host block, and only then is the counter read back.
         // A platform that refuses mapped + coherent host memory (or its device pointer) loses nothing but this shortcut: the
         // blocks are only kept once BOTH calls succeeded, otherwise the path is switched off and the call continues below.
-        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
         auto mapped_block = [&](HostMem<uint8_t>& host_p, uint8_t** dev_p) {
             if (host_p) return true;
             HostMem<uint8_t> hp;
@@ -896,16 +852,17 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
             return true;
         };
         if (!mapped_block(h->tn_out, &h->tn_out_dev) || !mapped_block(h->tn_in, &h->tn_in_dev)) h->tn_disabled = true;
+        tiny = !h->tn_disabled;
     }
-    if (n_samples > 0 && n_samples <= kTiny && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall && !h->tn_disabled) {
+    if (tiny) {
         std::memcpy(h->tn_in, iq, iq_bytes);
         volatile int* flag = reinterpret_cast<volatile int*>(h->tn_out + pack_bytes - 16);
         *flag = 0;
         uint8_t* d_bits = h->tn_out_dev + nb_bytes;
         h->cut_flag = reinterpret_cast<int*>(h->tn_out_dev + pack_bytes - 16);
-        const int rc = tetra_demod_process_device(h, reinterpret_cast<const float*>(h->tn_in_dev), n_samples, d_bits, bits_stride,
-                                                  reinterpret_cast<int32_t*>(h->tn_out_dev),
-                                                  sym ? reinterpret_cast<float*>(d_bits + bits_bytes) : nullptr, h->own_stream);
+        rc = tetra_demod_process_device(h, reinterpret_cast<const float*>(h->tn_in_dev), n_samples, d_bits, bits_stride,
+                                        reinterpret_cast<int32_t*>(h->tn_out_dev), sym ? reinterpret_cast<float*>(d_bits + bits_bytes) : nullptr,
+                                        h->own_stream);
         h->cut_flag = nullptr;
         if (rc != TETRA_OK) return rc;
         HIP_TRY(h, hipStreamSynchronize(h->own_stream));
@@ -916,8 +873,7 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         const int cut = new_overruns(h);          // rare: a poisoned channel filled its row
         return cut < 0 ? cut : TETRA_ERR_OVERRUN;
     }
-    if (n_samples > 0 && iq_bytes <= kSmallCall && pack_bytes <= kSmallCall) {
-        if (!h->own_stream) HIP_TRY(h, hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
+    if (small_call) {
         if (!h->pk_host) {      // once, both at kSmallCall; the packed output starts zero-filled
             HIP_TRY(h, h->pk_dev.reserve(kSmallCall));
             HIP_TRY(h, hipMemset(h->pk_dev, 0, kSmallCall));
@@ -930,8 +886,8 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
         uint8_t* d_nb = h->pk_dev;
         uint8_t* d_bits = h->pk_dev + nb_bytes;
         uint8_t* d_sym = d_bits + bits_bytes;
-        int rc = tetra_demod_process_device(h, h->st_iq, n_samples, d_bits, bits_stride, reinterpret_cast<int32_t*>(d_nb),
-                                            sym ? reinterpret_cast<float*>(d_sym) : nullptr, h->own_stream);
+        rc = tetra_demod_process_device(h, h->st_iq, n_samples, d_bits, bits_stride, reinterpret_cast<int32_t*>(d_nb),
+                                        sym ? reinterpret_cast<float*>(d_sym) : nullptr, h->own_stream);
         if (rc != TETRA_OK) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->pk_dev + pack_bytes - 16, h->d_overruns, sizeof(int), hipMemcpyDeviceToDevice, h->own_stream));
         HIP_TRY(h, hipMemcpyAsync(h->pk_host, h->pk_dev, pack_bytes, hipMemcpyDeviceToHost, h->own_stream));
@@ -958,8 +914,8 @@ int tetra_demod_process(tetra_demod_t* h, const float* iq, int n_samples, uint8_
 #ifdef TETRA_DEMOD_DEBUG
     HIP_TRY(h, hipMemset(h->st_bits, 0, bits_bytes));      // release builds: only bits[c][0 .. n_bits[c]) are defined
 #endif
-    int rc = tetra_demod_process_device(h, h->st_iq ? h->st_iq : h->agc_g, n_samples, h->st_bits, bits_stride, h->st_nbits,
-                                        sym ? h->st_sym.get() : nullptr, nullptr);
+    rc = tetra_demod_process_device(h, h->st_iq ? h->st_iq : h->agc_g, n_samples, h->st_bits, bits_stride, h->st_nbits,
+                                    sym ? h->st_sym.get() : nullptr, nullptr);
     if (rc != TETRA_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(0));
     HIP_TRY(h, hipMemcpy(bits, h->st_bits, bits_bytes, hipMemcpyDeviceToHost));
@@ -1092,9 +1048,7 @@ int tetra_demod_process_async(tetra_demod_t* h, const void* iq, int iq_format, i
     if (rc != TETRA_OK) {
         // part of the call may be enqueued: let it drain, then start the slot / event bookkeeping afresh (no wait of a later
         // call refers to an event this call did not get to record)
-        (void)hipStreamSynchronize(a.s_in);
-        (void)hipStreamSynchronize(a.s_k);
-        (void)hipStreamSynchronize(a.s_out);
+        (void)drain_async(h);
         a.chunks = 0;
         a.calls = 0;
     }
@@ -1106,9 +1060,8 @@ int tetra_demod_wait(tetra_demod_t* h) {
     if (!h->as.ready) return TETRA_OK;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipStreamSynchronize(h->as.s_in));
-    HIP_TRY(h, hipStreamSynchronize(h->as.s_k));
-    HIP_TRY(h, hipStreamSynchronize(h->as.s_out));
+    const int rc = drain_async(h);
+    if (rc != TETRA_OK) return rc;
     const int cut = new_overruns(h);
     return cut > 0 ? TETRA_ERR_OVERRUN : cut;
 }
@@ -1174,27 +1127,12 @@ int apply_params(tetra_demod* h, const host::DesignParams& np, bool tables, bool
         h->q_sym = std::move(q);
         h->q_sym_stride = want;
     }
-    if (generic_applies(h, nd)) {      // the generic kernel's scratch first: a failure leaves the handle as it was
-        const int rc = sync_generic_scratch(h, nd);
-        if (rc != TETRA_OK) return rc;
-    }
     const int old_ntaps = h->design.ntaps;
-    h->dp = np;
-    h->design = nd;
-    (void)sync_generic_scratch(h);        // (releases it when the parameters have left the generic kernel's domain)
-    if (tables) {
-        int rc = upload_tables(h);
-        if (rc != TETRA_OK) return rc;
-        if (h->quirks && nd.ntaps > old_ntaps) {
-            // FIR::setTaps with more taps keeps the RRC's old taps-1 history samples and zero-fills the newly visible part
-            hipLaunchKernelGGL(k_min_i32, dim3((h->C + 255) / 256), dim3(256), 0, 0, h->rrc_valid, old_ntaps - 1, h->C);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(0));
-        }
-    }
+    int rc = commit_design(h, np, nd);
+    if (rc != TETRA_OK) return rc;
+    if (tables && ((rc = upload_tables(h)) || (rc = shrink_rrc_valid(h, old_ntaps)))) return rc;
     if (timing_reset) {
-        int rc = reset_timing(h, 0, h->C);
-        if (rc != TETRA_OK) return rc;
+        if ((rc = reset_timing(h, 0, h->C))) return rc;
         HIP_TRY(h, hipStreamSynchronize(0));
     }
     return TETRA_OK;
@@ -1261,38 +1199,24 @@ int tetra_demod_set_tables(tetra_demod_t* h, const float* rrc_taps, int n_rrc, c
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     HIP_TRY(h, hipDeviceSynchronize());
-    if (generic_applies(h, nd)) {
-        const int rc = sync_generic_scratch(h, nd);
-        if (rc != TETRA_OK) return rc;
-    }
     const int old_ntaps = h->design.ntaps;
     // commit, upload -- and take the commit back if the upload fails: the handle never stays half-updated (its host-side design is
     // what the next setter re-designs from and what get_tables reports)
     const host::Design old_design = h->design;
     const host::DesignParams old_dp = h->dp;
     const bool old_user_rrc = h->user_rrc, old_user_be = h->user_be;
-    h->dp = np;
-    h->design = nd;
+    int rc = commit_design(h, np, nd);
+    if (rc != TETRA_OK) return rc;
     if (rrc_taps) h->user_rrc = true;
     if (bandedge_taps) h->user_be = true;
-    (void)sync_generic_scratch(h);
-    int rc = upload_tables(h);
-    if (rc != TETRA_OK) {
-        h->dp = old_dp;
-        h->design = old_design;
+    if ((rc = upload_tables(h)) != TETRA_OK) {
+        (void)commit_design(h, old_dp, old_design);
         h->user_rrc = old_user_rrc;
         h->user_be = old_user_be;
-        (void)sync_generic_scratch(h);
         (void)upload_tables(h);
         return rc;
     }
-    if (h->quirks && nd.ntaps > old_ntaps) {
-        // FIR::setTaps with more taps keeps the RRC's old taps-1 history samples and zero-fills the newly visible part
-        hipLaunchKernelGGL(k_min_i32, dim3((h->C + 255) / 256), dim3(256), 0, 0, h->rrc_valid, old_ntaps - 1, h->C);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipStreamSynchronize(0));
-    }
-    return TETRA_OK;
+    return shrink_rrc_valid(h, old_ntaps);
 }
 
 int tetra_demod_get_state(tetra_demod_t* h, int channel, tetra_demod_channel_state_t* out) {
