@@ -6,6 +6,7 @@
 
 #include "../../include/tetra_rx.h"
 #include "hip_host.hpp"
+#include "retune_list.hpp"
 
 namespace tetra_rx_impl {
 
@@ -78,4 +79,9 @@ struct tetra_rx {
     long long ring_call[kOutRing] = { -1, -1, -1, -1, -1, -1, -1, -1 }, ring_seq[kOutRing] = {}, out_seq = 0;
     DevMem<int32_t> out_tiles;            // [2][TETRA_RX_N_KINDS][tiles]: kept rows per tile, then their first output row
     DevMem<uint8_t> out_layout;           // the layout the write launch reads (rx_out::Layout)
+    // resets of single channels (include/tetra_retune.h, tetra_retune.hip)
+    ListRing to_device;                       // the channel lists on their way to the device
+    Event ev_reset;                       // the latest reset's work on the stream it was given ...
+    bool reset_pending = false;           // ... which the next process call waits for on ITS stream
+    bool owned = false;                   // inside a wideband handle (tetra_wbrx_rx): that handle restarts its channels, the entry point refuses
 };

@@ -18,6 +18,7 @@
 #include "bsync_core.hpp"
 #include "demux_core.hpp"
 #include "hip_host.hpp"
+#include "retune_impl.hpp"
 
 namespace {
 
@@ -377,6 +378,15 @@ int tetra_bsync_reset(tetra_bsync_t* h) {
 int tetra_bsync_max_frames(tetra_bsync_t* h) { return h ? h->max_frames : TETRA_ERR_ARG; }
 
 }  // extern "C"
+
+// The state and the bit buffer tetra_bsync_reset clears, for the stream-ordered reset of listed channels (tetra_retune.hip)
+int retune_impl::bsync_view(tetra_bsync_t* h, retune::BsyncView* v) {
+    if (!h || !v) return TETRA_ERR_ARG;
+    static_assert(sizeof(State) % 4 == 0 && kBuf % 4 == 0, "reset in 32-bit words");
+    v->state = reinterpret_cast<uint32_t*>(h->d_state.get()); v->state_words = (int32_t)(sizeof(State) / 4);
+    v->carry = reinterpret_cast<uint32_t*>(h->d_carry.get()); v->carry_words = kBuf / 4;
+    return TETRA_OK;
+}
 
 namespace {
 template <bool PACKED> int bsync_launch(tetra_bsync_t* h, const uint8_t* d_bits, int bits_stride, const int32_t* d_n_bits, void* d_frames,

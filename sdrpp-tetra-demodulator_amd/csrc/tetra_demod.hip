@@ -29,6 +29,7 @@
 #include "design.hpp"
 #include "hip_host.hpp"
 #include "launch_plan.hpp"
+#include "retune_impl.hpp"
 
 using namespace tdm;
 
@@ -1094,6 +1095,27 @@ int tetra_demod_reset(tetra_demod_t* h, int channel) {
     HIP_TRY(h, hipDeviceSynchronize());
     return channel < 0 ? reset_range(h, 0, h->C, !h->quirks) : reset_range(h, channel, 1, !h->quirks);
 }
+
+}  // extern "C"
+
+// The per-channel state that reset_range writes, for the stream-ordered reset of listed channels (tetra_retune.hip, retune_core.hpp)
+int retune_impl::demod_view(tetra_demod_t* h, retune::DemodView* v) {
+    if (!h || !v) return TETRA_ERR_ARG;
+    *v = retune::DemodView{};
+    v->agc_g = h->agc_g; v->fll_ph = h->fll_ph; v->fll_fr = h->fll_fr; v->mu = h->mu; v->omega = h->omega;
+    v->cph = h->cph; v->cfr = h->cfr; v->ph2 = h->ph2; v->offset = h->offset; v->prev = h->prev; v->rrc_valid = h->rrc_valid;
+    v->hist = reinterpret_cast<float*>(h->hist.get()); v->n_hist = kHist;
+    v->hist_far = reinterpret_cast<float*>(h->hist_far.get()); v->n_hist_far = kGenHist - kHist;
+    v->ybuf = reinterpret_cast<float*>(h->ybuf.get()); v->n_ybuf = kYHist;
+    v->q_ring = h->q_ring; v->q_ptr = h->q_ptr; v->q_disp = h->q_disp; v->q_sync = h->q_sync; v->q_err = h->q_err; v->n_q_ring = 4096;
+    v->cd_blk = reinterpret_cast<float*>(h->cd_blk.get()); v->cd_fill = h->cd_fill; v->cd_blocks = h->cd_blocks; v->n_cd = kCdSyms;
+    v->rrc_all = kGenHist;
+    v->tr_omega = h->design.tr_omega;
+    v->fresh = h->quirks ? 0 : 1;
+    return TETRA_OK;
+}
+
+extern "C" {
 
 namespace {
 // What every setter ends in: validate the new parameter set, re-design what `tables` / `with_tap_count` ask for, then commit

@@ -16,6 +16,7 @@
 #include "hip_host.hpp"
 #include "resamp_core.hpp"
 #include "resamp_handle.hpp"
+#include "retune_impl.hpp"
 
 namespace {
 
@@ -191,6 +192,15 @@ int process_pick_device(tetra_resamp_t* h, const int32_t* d_cols, int in_ch, con
 }
 
 }  // namespace resamp_impl
+
+int retune_impl::resamp_narrow_units(tetra_resamp_t* h) {
+    if (!h) return TETRA_ERR_ARG;
+    h->W = 2;
+    h->units = h->C;
+    h->fixed = (h->cfg.flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_fixed(h->I, h->DN, h->T, h->W);
+    h->cfg.flags |= TETRA_RESAMP_FLAG_NARROW_UNITS;
+    return TETRA_OK;
+}
 
 extern "C" {
 

@@ -1,0 +1,192 @@
+// tetra_retune.hip -- retuning while the stream runs (include/tetra_retune.h): the stream-ordered reset of listed channels of the
+// receive chain, and the wideband receiver's retune of carrier slots on top of it.
+//
+// Nothing here waits on the host.  Two calls may be in flight (the demodulator of call k + 1 runs beside the tail of call k), so a
+// reset between call k and call k + 1 is split by stream:
+//
+//   caller's stream  [wait: demodulator k]  (wideband: bin list, delay-line columns)  k_reset_demod           (event ev_reset)
+//   tail stream      [behind tail k, wait ev_reset]  k_reset_tail: synchroniser state + bit buffer, cell state
+//
+// and call k + 1 is ordered behind both: its demodulator waits for ev_reset, its tail runs on the tail stream.  The events of call k
+// (ev_demod, ev_tail, the wideband ev_done) are recorded again behind the reset, so whoever waits for that call -- tetra_rx_wait,
+// the state readers, the call after next -- also waits for the reset.  Call k's results are not touched: they stay fetchable.
+//
+// The kernels are a launch of one 64-lane workgroup per listed channel (lane code: retune_core.hpp): not a hot path.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "../../include/tetra_retune.h"
+#include "hip_host.hpp"
+#include "resamp_handle.hpp"
+#include "retune_core.hpp"
+#include "retune_impl.hpp"
+#include "rx_handle.hpp"
+#include "wbrx_handle.hpp"
+
+namespace {
+
+constexpr int kLanes = 64;
+
+__global__ __launch_bounds__(kLanes) void k_reset_demod(retune::DemodView v, const int32_t* __restrict__ channels, int n_channels) {
+    const int c = channels[blockIdx.x];
+    if (c < 0 || c >= n_channels) return;          // (the host has checked the list)
+    retune::reset_demod_channel(v, c, threadIdx.x, kLanes);
+}
+
+__global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retune::CellView cell, const int32_t* __restrict__ channels, int n_channels) {
+    const int c = channels[blockIdx.x];
+    if (c < 0 || c >= n_channels) return;
+    retune::reset_bsync_channel(b, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(cell, c, threadIdx.x, kLanes);
+}
+
+// list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
+// history ring [hist][M] (a sibling of tetra_resamp.hip's k_pick_rows: same rows, one column each, out of the ring)
+__global__ __launch_bounds__(256) void k_retune_columns(const float* __restrict__ ring, int M, int hist, long long n_total, const int32_t* __restrict__ list,
+                                                        int n, int C, float* __restrict__ line, int32_t* __restrict__ bins) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= hist * n) return;
+    const int r = i / n, j = i - r * n;
+    const int slot = list[j], bin = list[n + j];
+    if (slot < 0 || slot >= C || bin < 0 || bin >= M) return;
+    retune::rebuild_element(ring, M, hist, n_total, r, bin, slot, C, line);
+    if (r == 0) bins[slot] = bin;
+}
+
+bool no_device() {
+    int n = 0;
+    return hipGetDeviceCount(&n) != hipSuccess || n <= 0;
+}
+
+// false: an index outside [0, limit) or twice in the list
+bool distinct_in_range(const int32_t* v, int n, int limit) {
+    std::vector<char> seen((size_t)limit, 0);
+    for (int i = 0; i < n; i++) {
+        if (v[i] < 0 || v[i] >= limit || seen[(size_t)v[i]]) return false;
+        seen[(size_t)v[i]] = 1;
+    }
+    return true;
+}
+
+// The chain's part, for n > 0 channels listed on the device at d_channels (uploaded on s).  The caller marks the list's readers:
+// s, and *tail_reader (the tail stream when the chain has one of its own, else null).
+int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader) {
+    retune::DemodView dv;
+    retune::BsyncView bv;
+    TETRA_TRY(retune_impl::demod_view(h->dem, &dv));
+    TETRA_TRY(retune_impl::bsync_view(h->bs, &bv));
+    static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0, "reset in 32-bit words");
+    retune::CellView cv = { reinterpret_cast<uint32_t*>(h->cell.get()), (int32_t)(sizeof(tetra_lmac_cell_state_t) / 4) };
+    if (!h->ev_reset) HIP_TRY(h, hipEventCreateWithFlags(h->ev_reset.put(), hipEventDisableTiming));
+    const int last = (int)((h->calls - 1) & 1);
+    hipStream_t st = h->one_stream ? s : static_cast<hipStream_t>(h->tail);
+    if (h->reset_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_reset, 0));        // an earlier reset, possibly given another stream
+    if (h->calls > 0) {
+        HIP_TRY(h, hipStreamWaitEvent(s, h->ev_demod[last], 0));
+        if (h->one_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[last], 0));
+    }
+    hipLaunchKernelGGL(k_reset_demod, dim3((unsigned)n), dim3(kLanes), 0, s, dv, d_channels, h->C);
+    HIP_TRY(h, hipGetLastError());
+    if (!h->one_stream) {
+        HIP_TRY(h, hipEventRecord(h->ev_reset, s));
+        HIP_TRY(h, hipStreamWaitEvent(st, h->ev_reset, 0));
+    }
+    hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, d_channels, h->C);
+    HIP_TRY(h, hipGetLastError());
+    if (h->one_stream) HIP_TRY(h, hipEventRecord(h->ev_reset, s));
+    h->reset_pending = true;
+    if (h->calls > 0) {      // who waits for the last call waits for the reset too
+        HIP_TRY(h, hipEventRecord(h->ev_demod[last], s));
+        HIP_TRY(h, hipEventRecord(h->ev_tail[last], st));
+    }
+    *tail_reader = h->one_stream ? nullptr : st;
+    return TETRA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tetra_rx_reset_channels_device(tetra_rx_t* h, const int32_t* channels, int n, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
+    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune restarts its slots
+    if (!distinct_in_range(channels, n, h->C)) return TETRA_ERR_ARG;
+    if (n == 0) return TETRA_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    int32_t* d_list = nullptr;
+    hipError_t e = hipSuccess;
+    const int k = h->to_device.push(channels, n, h->C, s, &d_list, &e);
+    if (k < 0) HIP_TRY(h, e);
+    hipStream_t tail = nullptr;
+    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail));
+    HIP_TRY(h, h->to_device.done(k, 0, s));
+    if (tail) HIP_TRY(h, h->to_device.done(k, 1, tail));
+    return TETRA_OK;
+}
+
+int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || !bins) return TETRA_ERR_ARG;
+    const int S = h->n_bins;
+    if (!distinct_in_range(bins, S, h->M)) return TETRA_ERR_ARG;
+    std::vector<int32_t> list;               // [n slots | n bins] of the slots that move
+    for (int j = 0; j < S; j++)
+        if (bins[j] != h->bins[(size_t)j]) list.push_back(j);
+    const int n = (int)list.size();
+    for (int i = 0; i < n; i++) list.push_back(bins[list[(size_t)i]]);
+    if (n == 0) {
+        h->retunes++;
+        return TETRA_OK;
+    }
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    tetra_resamp* rs = h->rs;
+    tetra_rx* rx = h->rx;
+    // chan_out's rows are in the ring and the delay line is the last call's once that call's work on its stream is through
+    if (h->done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+    int32_t* d_list = nullptr;
+    hipError_t e = hipSuccess;
+    const int k = h->to_device.push(list.data(), 2 * n, 2 * S, s, &d_list, &e);
+    if (k < 0) HIP_TRY(h, e);
+    const int hist = rs->T - 1, cells = hist * n;      // (the delay line's layout does not depend on the resampler's lane-unit width)
+    hipLaunchKernelGGL(k_retune_columns, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->ring.get(), h->M, hist, rs->n_total, d_list, n, rs->C,
+                       rs->hist.get(), h->d_bins.get());
+    const hipError_t launched = hipGetLastError();
+    (void)h->to_device.done(k, 0, s);
+    HIP_TRY(h, launched);              // nothing has changed so far, on the device or here
+    // The device's bin list and delay line move with that launch, so from here on the host state is committed whatever becomes
+    // of the rest; a failure below is reported, and leaves the moved slots' chain state undefined until tetra_wbrx_reset.
+    if (h->all) {      // from now on the selecting resampler, over a delay line that already holds every bin in order
+        (void)retune_impl::resamp_narrow_units(rs);
+        h->all = false;
+    }
+    for (int i = 0; i < n; i++) h->bins[(size_t)list[(size_t)i]] = list[(size_t)(n + i)];
+    h->retunes++;
+    h->slots_changed += n;
+    hipStream_t tail = nullptr;
+    int rc = reset_enqueue(rx, d_list, n, s, &tail);
+    hipError_t late = h->to_device.done(k, 0, s);
+    if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
+    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
+    if (late == hipSuccess) h->done_recorded = true;
+    else if (rc == TETRA_OK) {
+        h->last_hip = (int)late;
+        rc = TETRA_ERR_HIP;
+    }
+    return rc;
+}
+
+int tetra_wbrx_retune_count(tetra_wbrx_t* h, int64_t* retunes, int64_t* slots_changed) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h) return TETRA_ERR_ARG;
+    if (retunes) *retunes = h->retunes;
+    if (slots_changed) *slots_changed = h->slots_changed;
+    return TETRA_OK;
+}
+
+}  // extern "C"

@@ -196,6 +196,7 @@ int tetra_rx_reset(tetra_rx_t* h) {
     h->stage_valid = false;
     for (bool& p : h->out_pending) p = false;          // (the device is idle: every delivery has completed)
     for (long long& c : h->ring_call) c = -1;
+    h->reset_pending = false;
     return TETRA_OK;
 }
 
@@ -209,6 +210,10 @@ int tetra_rx_process_device(tetra_rx_t* h, const float* d_iq, int n_samples, voi
     const int b = (int)(h->calls & 1);
     // the bit rows of this parity were last read by the tail of call k - 2
     if (h->calls >= 2 && !h->one_stream) HIP_TRY(h, hipStreamWaitEvent(sa, h->ev_tail[b], 0));
+    if (h->reset_pending) {         // channels reset since the last call (tetra_retune.h): the demodulator starts behind that
+        HIP_TRY(h, hipStreamWaitEvent(sa, h->ev_reset, 0));
+        h->reset_pending = false;
+    }
     TETRA_TRY(tetra_demod_process_device(h->dem, d_iq, n_samples, h->bits[b], h->stride, h->nbits[b], nullptr, sa));
     HIP_TRY(h, hipEventRecord(h->ev_demod[b], sa));
     if (!h->one_stream) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_demod[b], 0));

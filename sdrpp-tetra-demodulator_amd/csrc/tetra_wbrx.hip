@@ -19,6 +19,9 @@
 #include "../../include/tetra_shift.h"
 #include "hip_host.hpp"
 #include "resamp_handle.hpp"
+#include "retune_core.hpp"
+#include "rx_handle.hpp"
+#include "wbrx_handle.hpp"
 
 namespace {
 
@@ -47,36 +50,16 @@ __global__ __launch_bounds__(256) void k_bin_power_sum(const double* __restrict_
     out[k] = (float)(s / (double)nf);
 }
 
+// The `rows` newest of the n_in frames x [n_in][M] that follow n0 earlier ones -> the history ring (retune_core.hpp)
+__global__ __launch_bounds__(256) void k_keep_rows(const float* __restrict__ x, int M, long long n0, int n_in, int rows, int hist, float* __restrict__ ring) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < (long long)rows * M) retune::keep_element(x, M, n0, n_in, rows, hist, i, ring);
+}
+
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
 
 enum { kFmtC32 = 0, kFmtCs16 = 1, kFmtCs8 = 2 };
 constexpr size_t kFmtBytes[3] = { 8, 4, 2 };
-
-}  // namespace
-
-struct tetra_wbrx {
-    tetra_wbrx_config_t cfg;
-    int device = 0, last_hip = 0;
-    int M = 0, n_bins = 0, max_in = 0, max_chan = 0, max_res = 0;
-    bool all = false;                       // bins = 0 .. M - 1 in order: the resampler runs in place on the full rows
-    std::vector<int32_t> bins;
-    Handle<tetra_chan_t*, tetra_chan_destroy> chan;
-    Handle<tetra_resamp_t*, tetra_resamp_destroy> rs;
-    Handle<tetra_rx_t*, tetra_rx_destroy> rx;
-    DevMem<int32_t> d_bins;                 // [n_bins]
-    DevMem<float> chan_out;                 // [max_chan][M] complex64: the latest call's channeliser frames
-    DevMem<float> res[2];                   // per call parity: [max_res][n_bins] complex64, the resampled carriers
-    int n_res[2] = { 0, 0 };
-    int n_chan = 0;                         // channeliser frames of the latest call
-    Event ev_chan, ev_res[2], ev_done;
-    long long calls = 0;
-    Stream aux;                             // tetra_wbrx_bin_power (created on first use, with its buffers)
-    DevMem<double> pw_part;
-    DevMem<float> pw_out;
-    DevMem<uint8_t> st_x;                   // host-path staging
-};
-
-namespace {
 
 int process_any(tetra_wbrx* h, int fmt, const void* d_x, int n_in, void* hip_stream) {
     if (!h || (!d_x && n_in > 0)) return TETRA_ERR_ARG;
@@ -88,7 +71,7 @@ int process_any(tetra_wbrx* h, int fmt, const void* d_x, int n_in, void* hip_str
     const int b = (int)(h->calls & 1);
     // chan_out was read by the previous call's resampler and res[b] by the demodulator two calls back (which the previous call
     // waited for in turn): on another stream, wait for them
-    if (h->calls > 0) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+    if (h->done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));      // (a retune records it too)
     int nf = 0, nr = 0;
     if (fmt == kFmtCs16) TETRA_TRY(tetra_chan_process_device_cs16(h->chan, static_cast<const int16_t*>(d_x), n_in, h->chan_out, &nf, s));
     else if (fmt == kFmtCs8) TETRA_TRY(tetra_chan_process_device_cs8(h->chan, static_cast<const int8_t*>(d_x), n_in, h->chan_out, &nf, s));
@@ -101,7 +84,16 @@ int process_any(tetra_wbrx* h, int fmt, const void* d_x, int n_in, void* hip_str
     h->n_res[b] = nr;
     h->calls++;
     TETRA_TRY(tetra_rx_process_device(h->rx, h->res[b], nr, s));
+    if (nf > 0) {      // the newest T - 1 channeliser frames of ALL bins, for the slots a retune moves (tetra_retune.hip); off the chain's path
+        const tetra_resamp* rs = h->rs;
+        const int hist = rs->T - 1, rows = nf < hist ? nf : hist;
+        const long long n = (long long)rows * h->M;
+        hipLaunchKernelGGL(k_keep_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->chan_out.get(), h->M, rs->n_total - nf, nf, rows, hist,
+                           h->ring.get());
+        HIP_TRY(h, hipGetLastError());
+    }
     HIP_TRY(h, hipEventRecord(h->ev_done, s));
+    h->done_recorded = true;
     return TETRA_OK;
 }
 
@@ -195,9 +187,11 @@ int tetra_wbrx_create(const tetra_wbrx_config_t* cfg, tetra_wbrx_t** out) {
     xc.demod.max_samples = h->max_res;
     xc.demod.device = dev;
     TETRA_TRY(tetra_rx_create(&xc, h->rx.put()));
+    static_cast<tetra_rx*>(h->rx)->owned = true;
 
     const size_t row = 2 * (size_t)nb;
     bool ok = dalloc(h->d_bins, (size_t)nb) && dalloc(h->chan_out, 2 * (size_t)M * (size_t)h->max_chan) &&
+              dalloc(h->ring, 2 * (size_t)M * (size_t)(cfg->taps_per_phase - 1)) &&
               dalloc(h->res[0], row * (size_t)h->max_res) && dalloc(h->res[1], row * (size_t)h->max_res) &&
               hipEventCreateWithFlags(h->ev_chan.put(), hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(h->ev_res[0].put(), hipEventDisableTiming) == hipSuccess &&

@@ -10,6 +10,8 @@ from .bsync_binding import BsyncState
 RX_EXPORTS = ["tetra_rx_default_config", "tetra_rx_create", "tetra_rx_destroy", "tetra_rx_reset", "tetra_rx_process_device",
               "tetra_rx_process", "tetra_rx_wait", "tetra_rx_max_rows", "tetra_rx_type1_bits", "tetra_rx_fetch", "tetra_rx_rows_device",
               "tetra_rx_get_cell", "tetra_rx_get_sync_state", "tetra_rx_bits_device", "tetra_rx_demod", "tetra_rx_stage_ms"]
+# include/tetra_retune.h (resets of single channels while the stream runs): the chain's share
+RX_RETUNE_EXPORTS = ["tetra_rx_reset_channels_device"]
 KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
 N_KINDS = 6
 FLAG_ONE_STREAM = 1
@@ -61,6 +63,9 @@ def _lib():
         for n in RX_EXPORTS:
             if n != "tetra_rx_demod":
                 getattr(L, n).restype = i32
+        if hasattr(L, "tetra_rx_reset_channels_device"):       # (a TETRA_DEMOD_LIB override may be an older build without it)
+            L.tetra_rx_reset_channels_device.argtypes = [vp, vp, i32, vp]
+            L.tetra_rx_reset_channels_device.restype = i32
         _ready = True
     return L
 
@@ -118,6 +123,13 @@ class RxChain:
 
     def reset(self):
         self._chk(self._lib.tetra_rx_reset(self._h), "tetra_rx_reset")
+
+    def reset_channels(self, channels, stream=None):
+        """tetra_rx_reset_channels_device: the listed channels start afresh from the next process call on, everything else stays;
+        enqueued on `stream`, not waited for."""
+        ch = np.ascontiguousarray(np.asarray(channels, np.int64).astype(np.int32).reshape(-1))
+        self._chk(self._lib.tetra_rx_reset_channels_device(self._h, ch.ctypes.data_as(C.c_void_p) if ch.size else None, int(ch.size),
+                                                           _stream_ptr(stream)), "tetra_rx_reset_channels_device")
 
     def process(self, iq):
         iq = np.ascontiguousarray(iq, np.complex64)

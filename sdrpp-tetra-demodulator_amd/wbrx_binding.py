@@ -14,6 +14,8 @@ WBRX_EXPORTS = ["tetra_wbrx_default_config", "tetra_wbrx_create", "tetra_wbrx_de
                 "tetra_wbrx_rx", "tetra_wbrx_bins", "tetra_wbrx_frames_device", "tetra_wbrx_bin_power", "tetra_wbrx_stage_ms"]
 # include/tetra_shift.h (the frequency-shifted bank): the wideband receiver's share
 WBRX_SHIFT_EXPORTS = ["tetra_wbrx_set_shift", "tetra_wbrx_get_shift"]
+# include/tetra_retune.h (carrier slots that move while the stream runs): the wideband receiver's share
+WBRX_RETUNE_EXPORTS = ["tetra_wbrx_retune", "tetra_wbrx_retune_count"]
 
 
 class WbrxConfig(C.Structure):
@@ -51,6 +53,11 @@ def _lib():
             L.tetra_wbrx_set_shift.restype = i32
             L.tetra_wbrx_get_shift.argtypes = [vp, C.POINTER(C.c_uint32)]
             L.tetra_wbrx_get_shift.restype = i32
+        if hasattr(L, "tetra_wbrx_retune"):
+            L.tetra_wbrx_retune.argtypes = [vp, vp, vp]
+            L.tetra_wbrx_retune.restype = i32
+            L.tetra_wbrx_retune_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.tetra_wbrx_retune_count.restype = i32
         _ready = True
     return L
 
@@ -80,6 +87,9 @@ class _ChainView(RxChain):
 
     def reset(self):
         raise TypeError("the wideband receiver's chain is reset through WidebandRx.reset()")
+
+    def reset_channels(self, channels, stream=None):
+        raise TypeError("the wideband receiver's slots are restarted through WidebandRx.retune()")
 
     def process(self, iq):
         raise TypeError("the wideband receiver's chain is fed through WidebandRx.process*()")
@@ -137,6 +147,20 @@ class WidebandRx:
         v = C.c_uint32(0)
         self._chk(self._lib.tetra_wbrx_get_shift(self._h, C.byref(v)), "tetra_wbrx_get_shift")
         return int(v.value)
+
+    def retune(self, bins, stream=None):
+        """tetra_wbrx_retune: slot j receives bins[j] from the next process call on.  Slots whose bin stays are untouched; every other
+        slot starts afresh on its new bin.  Enqueued on `stream` (the one the process calls use), not waited for."""
+        new = np.ascontiguousarray(np.asarray(bins, np.int64).astype(np.int32).reshape(-1))
+        if new.size != self.n_bins:
+            raise ValueError("retune takes exactly %d bins" % self.n_bins)
+        self._chk(self._lib.tetra_wbrx_retune(self._h, new.ctypes.data_as(C.c_void_p), _stream_ptr(stream)), "tetra_wbrx_retune")
+
+    def retune_count(self):
+        """-> (accepted retunes, slots they moved) since create."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.tetra_wbrx_retune_count(self._h, C.byref(a), C.byref(b)), "tetra_wbrx_retune_count")
+        return int(a.value), int(b.value)
 
     def close(self):
         if getattr(self, "rx", None) is not None:
