@@ -175,7 +175,9 @@ int tetra_lmac_track_scramb_device(const uint8_t* d_sb1_type2, int type2_stride,
 /*
  * The whole SYNC-PDU read-out and the PHY's TDMA clock for every channel at once -- what labels a frame with its TDMA time.
  * Reference: tp_sap_udata_ind's SB1 case (src/decoder/src/lower_mac/tetra_lower_mac.c:246-275: colour code, TN/FN/MN, MCC,
- * MNC of a SYNC PDU with a good CRC go to tcd; tcd->time is then copied to t_phy_state.time WHATEVER the CRC was, :268-269),
+ * MNC of a SYNC PDU with a good CRC go to tcd, and tcd->time is copied to t_phy_state.time, :268-269.  tcd->time is the PHY time
+ * itself on entry of every tp_sap_udata_ind call, :172, so an SB1 with a BAD CRC leaves the clock where it was: only a SYNC PDU
+ * with a good CRC sets it.  tests/test_sync_track.py holds this to the reference's own tp_sap_udata_ind.),
  * the per-frame increment of the LOCKED receiver (src/decoder/src/phy/tetra_burst_sync.c:113: tetra_tdma_time_add_tn before
  * the callback) and its normalisation (src/decoder/src/tetra_tdma.c:28-78, reproduced to the letter including the wrap
  * thresholds tn > 4, fn > 18, mn > 60).  The reference keeps ONE process-global tcd / t_phy_state (tetra_lower_mac.c:116,
@@ -184,7 +186,8 @@ int tetra_lmac_track_scramb_device(const uint8_t* d_sb1_type2, int type2_stride,
 typedef struct tetra_lmac_cell_state {
     uint32_t scramb_init;              /* tcd->scramb_init (0 for a fresh receiver) */
     uint32_t colour_code, mcc, mnc;    /* tcd->colour_code / mcc / mnc of the last SYNC PDU with a good CRC */
-    uint32_t tcd_tn, tcd_fn, tcd_mn;   /* tcd->time */
+    uint32_t tcd_tn, tcd_fn, tcd_mn;   /* TN / FN / MN of the last SYNC PDU with a good CRC, as tcd->time took them (tn = the field + 1); 0 before
+                                          the first.  (The reference's tcd->time itself is overwritten with the PHY time by every later block.) */
     uint32_t phy_tn, phy_fn, phy_mn;   /* t_phy_state.time */
 } tetra_lmac_cell_state_t;
 /*
@@ -196,8 +199,9 @@ typedef struct tetra_lmac_cell_state {
  * d_row_scramb  [n_channels * frames_per_channel] uint32 out: the code in force for the slot's non-SB1 blocks
  * d_row_time_rx [..] uint32 out, may be NULL: t_phy_state.time when tetra_burst_rx_cb is entered for the slot's frame
  *               (t_display_st->curr_multiframe / curr_frame, tetra_burst.c:349-350), packed tn | fn << 8 | mn << 16
- * d_row_time    [..] uint32 out, may be NULL: t_phy_state.time after the slot's SB1 block (if it has one), i.e. the time
- *               every later block of the burst is handled under; unused slots get 0 in both.
+ * d_row_time    [..] uint32 out, may be NULL: t_phy_state.time after the slot's SB1 block (if it has one: the SYNC PDU's time if
+ *               its CRC is good, else the time on entry), i.e. the time every later block of the burst is handled under
+ *               (tup->tdma_time); unused slots get 0 in both.
  */
 int tetra_lmac_track_sync_device(const uint8_t* d_sb1_type2, int type2_stride, const int32_t* d_crc_ok, const int32_t* d_valid,
                                  const int32_t* d_n_frames, int n_channels, int frames_per_channel, tetra_lmac_cell_state_t* d_cell,
@@ -210,7 +214,7 @@ int tetra_lmac_track_sync_device(const uint8_t* d_sb1_type2, int type2_stride, c
  * pointer; TETRA_ERR_ALIGN otherwise).  Outputs as above; with d_sb1_labels != NULL (needs d_frame_bitnum) also the label of every
  * SB1 row, which the decode launch cannot write because the times come from here.
  * All three tracking entry points run one kernel: one wavefront per channel, a frame slot per lane, no walk over the slots (the
- * last SYNC frame before a slot and the last one with a good CRC are found with two ballots, their fields fetched by lane
+ * last SYNC frame with a good CRC before a slot -- the one that set the clock -- is found with a ballot, its fields fetched by lane
  * shuffle, and the clock k slots after it was set is one literal tetra_tdma_time_add_tn step plus k - 1 in closed form); they
  * differ only in where a slot's SB1 row is and in the state they carry.  Any frames_per_channel (64 slots at a time, the state
  * carried in between); frames_per_channel == 0 changes nothing.

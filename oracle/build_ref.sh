@@ -25,14 +25,26 @@ gcc -O2 -std=gnu11 -fPIC -shared -Wall -I"$SRC" -o "$HERE/_ref/libtetra_tpsap_re
 echo "built $HERE/_ref/libtetra_tpsap_recorder.so (test-side recorder for tp_sap_udata_ind)"
 # Lower-MAC channel-coding primitives, again the reference's own files compiled in place:
 # scrambler, block (de)interleaver, RCPC (de)puncturer + mother-code encoder, CRC16, and the K=5 rate-1/4 Viterbi decoder
-# (viterbi_dec_sb1_wrapper -> conv_cch_decode -> osmo_conv_decode).  tetra_lower_mac.c itself (tp_sap_udata_ind) is NOT
-# built: it needs the upper MAC / crypto / codec objects; the checker chains the primitives in the order its lines
-# :181-227 call them (oracle/ref_binding.py: lmac_decode).
+# (viterbi_dec_sb1_wrapper -> conv_cch_decode -> osmo_conv_decode).  tetra_lower_mac.c itself (tp_sap_udata_ind) is not in THIS
+# library (it is in libtetra_rxchain_ref.so, below); the checker chains the primitives in the order its lines :181-227 call them
+# (oracle/ref_binding.py: lmac_decode).
 LM="$SRC/lower_mac"
 gcc -O2 -std=gnu11 -fPIC -shared -w -I"$SRC" -o "$HERE/_ref/libtetra_lmac_ref.so" \
     "$LM/tetra_scramb.c" "$LM/tetra_interleave.c" "$LM/tetra_conv_enc.c" "$LM/crc_simple.c" \
     "$LM/viterbi.c" "$LM/viterbi_cch.c" "$LM/osmo_conv.c"
 echo "built $HERE/_ref/libtetra_lmac_ref.so from $LM/{tetra_scramb,tetra_interleave,tetra_conv_enc,crc_simple,viterbi,viterbi_cch,osmo_conv}.c"
+# The reference's lower MAC itself, tp_sap_udata_ind (lower_mac/tetra_lower_mac.c), behind its own tetra_burst_sync_in / tetra_burst_rx_cb:
+# libtetra_rxchain_ref.so.  The reference's files are compiled where they lie; what tetra_lower_mac.c needs from downstream (the upper
+# MAC's upper_mac_prim_recv, update_current_network, the ETSI codec's five entry points) is the TEST-SIDE recorder
+# tests/refrec/tmv_sap_recorder.c, and the two codec headers it includes are our stand-ins under tests/refrec/standin/c-code/.
+# -Wl,-Bsymbolic: the library's tetra_burst_rx_cb calls its OWN tp_sap_udata_ind and uses its OWN t_phy_state, even with the recorder
+# above loaded RTLD_GLOBAL in the same process.  Pins the SYNC tracker (tests/test_sync_track.py).
+gcc -O2 -std=gnu11 -fPIC -shared -w -I"$SRC" -I"$SRC/lower_mac" -I"$HERE/../tests/refrec/standin" -Wl,-Bsymbolic -Wl,--no-undefined \
+    -o "$HERE/_ref/libtetra_rxchain_ref.so" "$HERE/../tests/refrec/tmv_sap_recorder.c" \
+    "$LM/tetra_lower_mac.c" "$SRC/tetra_common.c" "$SRC/phy/tetra_burst.c" "$SRC/phy/tetra_burst_sync.c" "$SRC/tetra_tdma.c" \
+    "$LM/tetra_scramb.c" "$LM/tetra_interleave.c" "$LM/tetra_conv_enc.c" "$LM/crc_simple.c" \
+    "$LM/viterbi.c" "$LM/viterbi_cch.c" "$LM/osmo_conv.c"
+echo "built $HERE/_ref/libtetra_rxchain_ref.so from $LM/tetra_lower_mac.c, tetra_common.c, phy/tetra_burst{,_sync}.c, tetra_tdma.c, the lower-MAC primitives + tests/refrec/tmv_sap_recorder.c"
 # The reference's per-sample DSP objects (src/dsp/pi4dqpsk, fll, complex_fd, pi4dqpsk_costas, dqpsk_sym_extr, bit_unpacker), again
 # compiled where they lie, against OUR stand-in SDR++ core headers (tests/refshim/, see its README.md) and the test-side driver
 # tests/refshim/ref_driver.cpp: libref_shim.so with pi spelt as the double constant, libref_shim_fpi.so with the float macro

@@ -4,6 +4,7 @@ compiled from /root/reference where they lie by oracle/build_ref.sh (test infras
 Gives the tests the reference's real tetra_find_train_seq() (tetra_burst.c:271-341) and its burst builders
 build_sync_c_d_burst() / build_norm_c_d_burst() (tetra_burst.c:171-269).  The library keeps undefined references into
 the lower MAC (tetra_burst_rx_cb -> tp_sap_udata_ind); they are never called, so it is loaded with lazy binding."""
+import _ctypes
 import ctypes as C
 import os
 import subprocess
@@ -317,3 +318,162 @@ def lmac_encode(blk_type, type1, scramb_init):
     L.block_interleave(n345, a, _p(type3), _p(type4))
     L.tetra_scramb_bits(SCRAMB_INIT if blk_type == TPSAP_T_SB1 else int(scramb_init) & 0xffffffff, _p(type4), n345)
     return type4
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The reference's WHOLE receive chain below the demodulator: oracle/_ref/libtetra_rxchain_ref.so = its tetra_burst_sync_in ->
+# tetra_burst_rx_cb -> tp_sap_udata_ind (lower_mac/tetra_lower_mac.c, the real one) -> upper_mac_prim_recv, the last being the
+# test-side recorder tests/refrec/tmv_sap_recorder.c.  tcd is a static of tetra_lower_mac.c and t_phy_state a process global, so a
+# fresh receiver is a fresh PRIVATE COPY of the library: the file is copied to a temporary name and loaded from there (the dynamic
+# loader keeps one image per file), RTLD_LOCAL; the library is linked -Bsymbolic, so nothing else in the process -- the RTLD_GLOBAL
+# recorder above defines tp_sap_udata_ind too -- gets between its functions.
+# ---------------------------------------------------------------------------------------------------------------------
+RXCHAIN_LIB_PATH = os.path.join(_HERE, "_ref", "libtetra_rxchain_ref.so")
+RX_S_UNLOCKED, RX_S_KNOW_FSTART, RX_S_LOCKED = 0, 1, 2      # enum rx_state, phy/tetra_burst_sync.h
+# enum tetra_log_chan (tetra_common.h:241-): what tp_sap_udata_ind labels a block with
+TETRA_LC_UNKNOWN, TETRA_LC_SCH_F, TETRA_LC_AACH, TETRA_LC_BSCH, TETRA_LC_BNCH = 0, 1, 8, 10, 11
+
+
+class RxChainEvent(C.Structure):
+    _fields_ = [("lchan", C.c_int32), ("blk_num", C.c_int32), ("crc_ok", C.c_int32), ("n_bits", C.c_int32),
+                ("scrambling_code", C.c_uint32), ("tup_tn", C.c_uint32), ("tup_fn", C.c_uint32), ("tup_mn", C.c_uint32),
+                ("phy_tn", C.c_uint32), ("phy_fn", C.c_uint32), ("phy_mn", C.c_uint32), ("bitbuf_start_bitnum", C.c_uint32),
+                ("rx_state", C.c_int32), ("curr_frame", C.c_int32), ("curr_multiframe", C.c_int32), ("bits", C.c_uint8 * 268)]
+
+
+def rxchain_available():
+    if not os.path.exists(RXCHAIN_LIB_PATH):
+        try:
+            build()
+        except Exception:
+            return False
+    return os.path.exists(RXCHAIN_LIB_PATH)
+
+
+def tdma_pack(tn, fn, mn):
+    """A TDMA time as the product's tracker packs it: tn | fn << 8 | mn << 16."""
+    return int(tn) | (int(fn) << 8) | (int(mn) << 16)
+
+
+class ReferenceRxChain:
+    """One receiver of the reference with zeroed tcd / t_phy_state: a private copy of libtetra_rxchain_ref.so.
+    feed(bits)                 bits -> tetra_burst_sync_in
+    udata_ind(type, blk, bits) one block -> tp_sap_udata_ind, as tetra_burst_rx_cb hands it over
+    add_tn(n)                  tetra_tdma_time_add_tn(&t_phy_state.time, n): the LOCKED receiver's step per consumed frame
+    events()                   the TMV-SAP indications recorded since the last call, as dicts: lchan, blk_num, crc_ok, scramb (tup->
+                               scrambling_code), time (tup->tdma_time, packed), phy (t_phy_state.time at that moment, packed), bitnum,
+                               rx_state, curr_frame / curr_multiframe (stored by tetra_burst_rx_cb on entry), bits (type-1)
+    phy_time() / set_phy_time  t_phy_state.time as (tn, fn, mn)"""
+
+    def __init__(self):
+        import shutil
+        import tempfile
+        if not rxchain_available():
+            raise RuntimeError("oracle/_ref/libtetra_rxchain_ref.so is not built and /root/reference is not present")
+        fd, path = tempfile.mkstemp(prefix="rxchain_", suffix=".so")
+        os.close(fd)
+        try:
+            shutil.copyfile(RXCHAIN_LIB_PATH, path)
+            L = C.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_NOW)
+        finally:
+            os.unlink(path)              # the mapping stays
+        vp = C.c_void_p
+        L.rxc_new.restype = vp
+        L.rxc_free.argtypes = [vp]
+        L.rxc_feed.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.rxc_udata_ind.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
+        L.rxc_add_tn.argtypes = [C.c_int]
+        L.rxc_get_phy_time.argtypes = [vp]
+        L.rxc_set_phy_time.argtypes = [C.c_uint32] * 3
+        L.rxc_own_udata_ind.restype = vp
+        L.rxc_own_phy_state.restype = vp
+        L.rxc_network.argtypes = [vp, vp]
+        L.rxc_rx_state.argtypes = [vp, vp]
+        L.rxc_event_count.argtypes = [vp]
+        L.rxc_events.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.rxc_clear_events.argtypes = [vp]
+        assert L.rxc_event_size() == C.sizeof(RxChainEvent)
+        self._L = L
+        self._h = L.rxc_new()
+
+    def close(self):
+        if self._h:
+            self._L.rxc_free(self._h)
+            self._h = None
+            handle, self._L = self._L._handle, None
+            _ctypes.dlclose(handle)      # last reference: the copy's image (and its tcd / t_phy_state) goes away
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def feed(self, bits, chunk=510):
+        b = np.ascontiguousarray(bits, np.uint8)
+        self._L.rxc_feed(self._h, b.ctypes.data_as(C.c_void_p), int(b.size), int(chunk))
+
+    def feed_bitwise(self, bits):
+        """A bit per tetra_burst_sync_in call.  Yields, per call that consumed a frame (the PHY clock stepped) or changed the receiver's
+        state: (t_phy_state.time before the call, the receiver's state after it, the indications the call made)."""
+        b = np.ascontiguousarray(bits, np.uint8)
+        L, h, base = self._L, self._h, b.ctypes.data
+        w, st = (C.c_uint32 * 3)(), (C.c_uint32 * 4)()
+        L.rxc_get_phy_time(w)
+        L.rxc_rx_state(h, st)
+        before, state = (int(w[0]), int(w[1]), int(w[2])), int(st[0])
+        for i in range(b.size):
+            L.rxc_feed(h, base + i, 1, 1)
+            L.rxc_get_phy_time(w)
+            L.rxc_rx_state(h, st)
+            now = (int(w[0]), int(w[1]), int(w[2]))
+            n = L.rxc_event_count(h)
+            if n or now != before or int(st[0]) != state:
+                yield before, int(st[0]), self.events()
+                L.rxc_get_phy_time(w)
+                before, state = (int(w[0]), int(w[1]), int(w[2])), int(st[0])
+
+    def udata_ind(self, blk_type, blk_num, bits):
+        b = np.ascontiguousarray(bits, np.uint8)
+        assert b.size >= BLK_PARAM[blk_type][0]
+        self._L.rxc_udata_ind(self._h, int(blk_type), int(blk_num), b.ctypes.data_as(C.c_void_p), int(BLK_PARAM[blk_type][0]))
+
+    def add_tn(self, count=1):
+        self._L.rxc_add_tn(int(count))
+
+    def phy_time(self):
+        w = (C.c_uint32 * 3)()
+        self._L.rxc_get_phy_time(w)
+        return int(w[0]), int(w[1]), int(w[2])
+
+    def set_phy_time(self, tn, fn, mn):
+        self._L.rxc_set_phy_time(int(tn), int(fn), int(mn))
+
+    def network(self):
+        """(mcc, mnc) as update_current_network last stored them, tcs->cc, and how often it was called"""
+        w = (C.c_int32 * 4)()
+        self._L.rxc_network(self._h, w)
+        return tuple(int(x) for x in w)
+
+    @property
+    def state(self):
+        """(state, bits_in_buf, bitbuf_start_bitnum, next_frame_start_bitnum)"""
+        w = (C.c_uint32 * 4)()
+        self._L.rxc_rx_state(self._h, w)
+        return tuple(int(x) for x in w)
+
+    def own_addresses(self):
+        """Where this copy's tp_sap_udata_ind and t_phy_state live, as the library's own code sees them."""
+        return int(self._L.rxc_own_udata_ind()), int(self._L.rxc_own_phy_state())
+
+    def events(self):
+        n = self._L.rxc_event_count(self._h)
+        ev = (RxChainEvent * max(n, 1))()
+        if n:
+            self._L.rxc_events(self._h, 0, n, ev)
+        self._L.rxc_clear_events(self._h)
+        return [dict(lchan=int(e.lchan), blk_num=int(e.blk_num), crc_ok=int(e.crc_ok), scramb=int(e.scrambling_code),
+                     time=tdma_pack(e.tup_tn, e.tup_fn, e.tup_mn), phy=tdma_pack(e.phy_tn, e.phy_fn, e.phy_mn),
+                     bitnum=int(e.bitbuf_start_bitnum), rx_state=int(e.rx_state), curr_frame=int(e.curr_frame),
+                     curr_multiframe=int(e.curr_multiframe), bits=np.frombuffer(bytes(e.bits), np.uint8)[: e.n_bits].copy())
+                for e in ev[:n]]

@@ -506,4 +506,88 @@ LM_HD Tdma tdma_advance(Tdma t, uint32_t k) {
 // the packed time of the tracker's outputs: tn | fn << 8 | mn << 16
 LM_HD uint32_t tdma_pack(Tdma t) { return t.tn | (t.fn << 8) | (t.mn << 16); }
 
+// ---- The SB1 tracking rule of one frame slot (k_track in tetra_lmac.hip; tests/emul/lmac_emul.cpp runs the same functions on the host) ----
+// tp_sap_udata_ind (tetra_lower_mac.c) copies t_phy_state.time to tcd->time on entry of EVERY call (:172), overwrites its tn / fn / mn
+// from a SYNC PDU only when the CRC is good (:257-266) and copies tcd->time back to t_phy_state.time for every SB1 (:268).  So:
+//   every frame the LOCKED receiver consumes      t_phy_state.time += one timeslot (tetra_burst_sync.c:113, before the callback)
+//   a SYNC burst's SB1 block, good CRC            tcd <- colour code, mcc, mnc, scramb_init; the clock <- the PDU's tn (bits + 1), fn, mn
+//   a SYNC burst's SB1 block, bad CRC             the clock stays at its time on entry
+// Slots are taken 64 at a time, a slot per lane.  What a slot needs from its past is the last SYNC frame with a GOOD CRC before it
+// -- the clock was set there, and tcd holds that frame's fields -- and how many slots ago that was: the highest set bit below the
+// lane in the group's mask of good frames; the fields come from that lane; the clock k slots later is tdma_advance.
+
+// The tracker's state per channel: tetra_lmac_cell_state_t (include/tetra_lmac.h), member for member.
+struct TrackState {
+    uint32_t scramb_init, colour, mcc, mnc;
+    Tdma tcd;        // tn / fn / mn of the last SYNC PDU with a good CRC (zero before the first)
+    Tdma phy;        // t_phy_state.time
+};
+// What the rule gives for one slot.
+struct TrackSlot {
+    Tdma t_rx;       // t_phy_state.time on entry of tetra_burst_rx_cb
+    Tdma t_after;    // ... after the slot's SB1 (every later block of the burst is handled under it; the next slot's step starts from it)
+    Tdma tcd;        // the last good SYNC PDU's time up to and including this slot
+    uint32_t colour, mcc, mnc, scramb;      // tcd's fields after the slot, the scrambling code in force for the slot's other blocks
+};
+// highest set bit of m at or below position `upto` (-1: none; upto = -1: none)
+LM_FN int last_set_upto(unsigned long long m, int upto) {
+    if (upto < 0) return -1;
+    const unsigned long long x = m & (upto >= 63 ? ~0ull : ((2ull << upto) - 1ull));
+    return x ? 63 - __builtin_clzll(x) : -1;
+}
+// The two words a lane keeps of a SYNC PDU with a good CRC: a = colour << 2 | tn << 8 | fn << 11 | mn << 16, b = mcc | mnc << 10.
+// word(k) = bytes 4k .. 4k+3 of the decoded SB1 row (a bit per byte), little endian.
+template <class Word>
+LM_FN void sync_pdu_words(Word word, uint32_t& a, uint32_t& b) {
+    uint64_t v = 0;                               // type-2 bits 0..55, first bit most significant
+#pragma unroll
+    for (int k = 0; k < 14; ++k) v |= (uint64_t)pack4(word(k) & 0x01010101u) << (60 - 4 * k);
+    const SyncPdu p = { v };
+    a = (p.colour() << 2) | (p.tn() << 8) | (p.fn() << 11) | (p.mn() << 16);
+    b = p.mcc() | (p.mnc() << 10);
+}
+// st: the state the 64-slot group starts from.  mv / mg: the group's masks of slots that hold a SYNC burst / one with a good CRC (bit =
+// lane).  words(h, a, b): the PDU words of lane h >= 0 (a lane shuffle on the device: every lane calls track_slot, none is masked off).
+// kStaleTcdOnBadCrc = true is NOT the reference's rule: it is the rule this tracker had before it was pinned to the reference's own
+// tp_sap_udata_ind -- an SB1 with a bad CRC throws the clock back to the time of the last good SYNC PDU -- kept so that the tests can
+// plant it and show that they notice (tests/test_sync_track.py); nothing in the library instantiates it.
+template <bool kStaleTcdOnBadCrc = false, class Words>
+LM_FN TrackSlot track_slot(const TrackState& st, unsigned long long mv, unsigned long long mg, int lane, Words words) {
+    // tcd as a slot sees it: the fields of good frame h, or what the group started with
+    auto tcd_of = [&](int h, uint32_t ah, uint32_t bh, uint32_t& colour, uint32_t& mcc, uint32_t& mnc) {
+        Tdma t = st.tcd;
+        colour = st.colour; mcc = st.mcc; mnc = st.mnc;
+        if (h >= 0) {
+            t = Tdma{ (ah >> 8) & 7u, (ah >> 11) & 0x1fu, (ah >> 16) & 0x3fu };
+            colour = (ah >> 2) & 0x3fu; mcc = bh & 0x3ffu; mnc = bh >> 10;
+        }
+        return t;
+    };
+    const int gp = last_set_upto(kStaleTcdOnBadCrc ? mv : mg, lane - 1);    // the last frame before this slot that set the clock
+    const int hp = gp >= 0 ? last_set_upto(mg, gp) : -1;                    // ... and the good one whose time it took (gp itself)
+    const int hs = last_set_upto(mg, lane);                                 // the good one tcd holds after this slot
+    uint32_t ap, bp, as, bs;
+    words(hp < 0 ? 0 : hp, ap, bp);
+    words(hs < 0 ? 0 : hs, as, bs);
+    TrackSlot o;
+    // time on entry: k slots after the clock was last set, or after the group's start
+    Tdma from = tcd_of(hp, ap, bp, o.colour, o.mcc, o.mnc);
+    if (gp < 0) from = st.phy;
+    o.t_rx = tdma_advance(from, (uint32_t)(lane - gp));
+    // after the slot's SB1: the PDU's time if its CRC is good, else unchanged
+    o.tcd = tcd_of(hs, as, bs, o.colour, o.mcc, o.mnc);
+    const bool sets_clock = ((kStaleTcdOnBadCrc ? mv : mg) >> lane) & 1ull;
+    o.t_after = sets_clock ? o.tcd : o.t_rx;
+    o.scramb = st.scramb_init;                                              // (an if, not ?:, compiles the list form to the same code
+    if (hs >= 0) o.scramb = scramb_code(o.colour, o.mcc, o.mnc);            //  as the formula written out in place)
+    return o;
+}
+// The state after a group = after its last live slot (the next group, and the next call, start from it).
+LM_FN void track_carry(TrackState& st, const TrackSlot& end) {
+    st.phy = end.t_after;
+    st.tcd = end.tcd;
+    st.colour = end.colour; st.mcc = end.mcc; st.mnc = end.mnc;
+    st.scramb_init = end.scramb;
+}
+
 }  // namespace tetra_lmac

@@ -397,20 +397,23 @@ __global__ __launch_bounds__(256) void k_lmac_bbk(const uint8_t* __restrict__ ty
     crc_ok[blk] = 1;
 }
 
-// The SB1 tracking rule, every entry point's: the SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) plus
-// the PHY's TDMA clock (tetra_burst_sync.c:113, tetra_tdma.c:28-78), per channel, frame slots in time order:
+// The SB1 tracking rule, every entry point's: the SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275, with the
+// copy of the PHY time into tcd->time at :172) plus the PHY's TDMA clock (tetra_burst_sync.c:113, tetra_tdma.c:28-78), per channel,
+// frame slots in time order:
 //   every frame the LOCKED receiver consumes      t_phy_state.time += one timeslot (tetra_tdma_time_add_tn, before the callback)
-//   a SYNC burst's SB1 block, good CRC            tcd-> colour code, time (tn = bits + 1, fn, mn), mcc, mnc, scramb_init
-//   a SYNC burst's SB1 block, any CRC             t_phy_state.time = tcd->time   (:268-269: copied whatever the CRC said)
+//   a SYNC burst's SB1 block, good CRC            tcd-> colour code, mcc, mnc, scramb_init; tcd->time (tn = bits + 1, fn, mn) -> t_phy_state.time
+//   a SYNC burst's SB1 block, bad CRC             t_phy_state.time stays at its time on entry (tcd->time IS that time since :172, and
+//                                                 :268 copies it back unchanged)
 // Outputs per frame slot: the scrambling code in force for the slot's other blocks, the TDMA time tetra_burst_rx_cb sees on
 // entry (t_display_st->curr_multiframe / curr_frame, tetra_burst.c:349-350) and the time after the slot's SB1 (what every
 // later block of the burst and the next slot's increment start from).  Times are packed tn | fn << 8 | mn << 16 (tdma_pack).
 //
 // No walk over the slots: one wavefront per channel, 64 frame slots at a time, a slot per lane.  What a slot needs from its past is
-// (1) the last SYNC frame before it -- the PHY clock was set to tcd's time there -- and how many slots ago that was, (2) the last
-// SYNC frame with a good CRC up to there / up to the slot itself -- that is what tcd holds.  Both are "highest set bit below my
-// lane" of two ballots; the fields travel with two lane shuffles; and the clock k slots after a reset is tdma_advance.  Nothing is
-// serial but the carry from one 64-slot group to the next.  (A walk on the scalar unit: 2577 scalar instructions per wave, 29 us.)
+// the last SYNC frame with a GOOD CRC before it -- the PHY clock was set to the PDU's time there, and tcd holds its fields -- and how
+// many slots ago that was: "highest set bit below my lane" of the ballot of good frames; the fields travel with lane shuffles; and the
+// clock k slots after it was set is tdma_advance.  Nothing is serial but the carry from one 64-slot group to the next.  The rule itself
+// (track_slot, track_carry) lives in lmac_core.hpp, where the host emulation runs it too.  (A walk on the scalar unit: 2577 scalar
+// instructions per wave, 29 us.)
 //
 // Two compile-time choices:
 //   ROWS   kRowsList: the SB1 rows are compact, one per SYNC-list entry (tetra_lmac_track_sync_lists_device): a slot holds a SYNC
@@ -420,20 +423,21 @@ __global__ __launch_bounds__(256) void k_lmac_bbk(const uint8_t* __restrict__ ty
 //                     one where `present` (d_valid) is non-zero, read as bytes (any stride, any row alignment)
 //   State  tetra_lmac_cell_state_t (both times, labels) or uint32_t (tetra_lmac_track_scramb_device: the code alone, every slot live)
 enum { kRowsList, kRowsSlot };
-__device__ __forceinline__ tetra_lmac_cell_state_t load_state(const tetra_lmac_cell_state_t& s) { return s; }
-__device__ __forceinline__ tetra_lmac_cell_state_t load_state(uint32_t code) {
-    tetra_lmac_cell_state_t s = {};
+static_assert(sizeof(TrackState) == sizeof(tetra_lmac_cell_state_t), "TrackState is tetra_lmac_cell_state_t member for member");
+__device__ __forceinline__ TrackState load_state(const tetra_lmac_cell_state_t& s) {
+    return TrackState{ s.scramb_init, s.colour_code, s.mcc, s.mnc, Tdma{ s.tcd_tn, s.tcd_fn, s.tcd_mn }, Tdma{ s.phy_tn, s.phy_fn, s.phy_mn } };
+}
+__device__ __forceinline__ TrackState load_state(uint32_t code) {
+    TrackState s = {};
     s.scramb_init = code;
     return s;
 }
-__device__ __forceinline__ void store_state(tetra_lmac_cell_state_t& d, const tetra_lmac_cell_state_t& s) { d = s; }
-__device__ __forceinline__ void store_state(uint32_t& d, const tetra_lmac_cell_state_t& s) { d = s.scramb_init; }
-// highest set bit of m at or below position `upto` (-1: none; upto = -1: none)
-__device__ __forceinline__ int last_set_upto(unsigned long long m, int upto) {
-    if (upto < 0) return -1;
-    const unsigned long long x = m & (upto >= 63 ? ~0ull : ((2ull << upto) - 1ull));
-    return x ? 63 - __clzll((long long)x) : -1;
+__device__ __forceinline__ void store_state(tetra_lmac_cell_state_t& d, const TrackState& s) {
+    d = tetra_lmac_cell_state_t{ s.scramb_init, s.colour, s.mcc, s.mnc, s.tcd.tn, s.tcd.fn, s.tcd.mn, s.phy.tn, s.phy.fn, s.phy.mn };
 }
+__device__ __forceinline__ void store_state(uint32_t& d, const TrackState& s) { d = s.scramb_init; }
+__device__ __forceinline__ uint32_t shfl_u32(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src); }
+__device__ __forceinline__ Tdma shfl_tdma(const Tdma& t, int src) { return Tdma{ shfl_u32(t.tn, src), shfl_u32(t.fn, src), shfl_u32(t.mn, src) }; }
 template <int ROWS, class State>
 __global__ __launch_bounds__(kLanes) void k_track(const uint8_t* __restrict__ sb1, int stride, const int* __restrict__ crc_ok,
                                                   const int* __restrict__ present, const int* __restrict__ n_frames,
@@ -445,7 +449,7 @@ __global__ __launch_bounds__(kLanes) void k_track(const uint8_t* __restrict__ sb
     const int c = blockIdx.x, lane = threadIdx.x;
     const int nf = n_frames ? min(n_frames[c], frames) : frames;
     int base = ROWS == kRowsList ? chan_first[c] : 0;
-    tetra_lmac_cell_state_t st = load_state(state[c]);    // wave-uniform; carried from group to group
+    TrackState st = load_state(state[c]);    // wave-uniform; carried from group to group
     for (int f0 = 0; f0 < frames; f0 += kLanes) {
         const int f = f0 + lane;
         const size_t r = (size_t)c * frames + f;
@@ -453,63 +457,32 @@ __global__ __launch_bounds__(kLanes) void k_track(const uint8_t* __restrict__ sb
         const unsigned long long m = __ballot(is_sync);
         const Row j = ROWS == kRowsList ? (Row)(base + __popcll(m & ((1ull << lane) - 1ull))) : (Row)r;      // the slot's SB1 row
         base += __popcll(m);
-        // a: colour << 2, tn << 8, fn << 11, mn << 16;  b: mcc | mnc << 10  (of a SYNC frame with a good CRC)
+        // a, b: the PDU words of a SYNC frame with a good CRC (sync_pdu_words)
         const bool valid = is_sync && f < nf;
         bool good = false;
         uint32_t a = 0, b = 0;
         if (valid && crc_ok[j]) {
             good = true;
             const uint8_t* t2 = sb1 + (size_t)j * stride;
-            auto word = [&](int k) -> uint32_t {                 // bytes 4k .. 4k+3 of the row, little endian
+            sync_pdu_words([&](int k) -> uint32_t {              // bytes 4k .. 4k+3 of the row, little endian
                 if (ROWS == kRowsList) return reinterpret_cast<const uint32_t*>(t2)[k];
                 return t2[4 * k] | (t2[4 * k + 1] << 8) | (t2[4 * k + 2] << 16) | ((uint32_t)t2[4 * k + 3] << 24);
-            };
-            uint64_t v = 0;                               // type-2 bits 0..55, first bit most significant
-#pragma unroll
-            for (int k = 0; k < 14; ++k) v |= (uint64_t)pack4(word(k) & 0x01010101u) << (60 - 4 * k);
-            const SyncPdu p = { v };
-            a = (p.colour() << 2) | (p.tn() << 8) | (p.fn() << 11) | (p.mn() << 16);
-            b = p.mcc() | (p.mnc() << 10);
+            }, a, b);
         }
         const unsigned long long mv = __ballot(valid), mg = __ballot(good);
-        // tcd as a slot sees it: the fields of good frame h (ah, bh = its words, fetched by every lane: a shuffle reads active lanes
-        // only), or what the group started with
-        auto tcd_of = [&](int h, uint32_t ah, uint32_t bh, uint32_t& colour, uint32_t& mcc, uint32_t& mnc) {
-            Tdma t = { st.tcd_tn, st.tcd_fn, st.tcd_mn };
-            colour = st.colour_code; mcc = st.mcc; mnc = st.mnc;
-            if (h >= 0) {
-                t = Tdma{ (ah >> 8) & 7u, (ah >> 11) & 0x1fu, (ah >> 16) & 0x3fu };
-                colour = (ah >> 2) & 0x3fu; mcc = bh & 0x3ffu; mnc = bh >> 10;
-            }
-            return t;
-        };
-        const int gp = last_set_upto(mv, lane - 1);                          // the last SYNC frame before this slot
-        const int hp = gp >= 0 ? last_set_upto(mg, gp) : -1;                 // ... and the good one tcd held there
-        const int hs = last_set_upto(mg, lane);                              // the good one tcd holds after this slot
-        const uint32_t ap = (uint32_t)__shfl((int)a, hp < 0 ? 0 : hp), bp = (uint32_t)__shfl((int)b, hp < 0 ? 0 : hp);
-        const uint32_t as = (uint32_t)__shfl((int)a, hs < 0 ? 0 : hs), bs = (uint32_t)__shfl((int)b, hs < 0 ? 0 : hs);
-        uint32_t cc, mcc, mnc;
-        // time on entry: k slots after the last SYNC frame before this one (the clock was set to tcd's time there), or after the group's start
-        Tdma from = tcd_of(hp, ap, bp, cc, mcc, mnc);
-        if (gp < 0) from = Tdma{ st.phy_tn, st.phy_fn, st.phy_mn };
-        const Tdma t_rx = tdma_advance(from, (uint32_t)(lane - gp));
-        // after the slot's SB1: tcd as of this slot if it is a SYNC frame, else unchanged
-        const Tdma tcd_now = tcd_of(hs, as, bs, cc, mcc, mnc);
-        const Tdma t_after = valid ? tcd_now : t_rx;
-        uint32_t scramb = st.scramb_init;                                     // (an if, not ?:, compiles the list form to the same code
-        if (hs >= 0) scramb = scramb_code(cc, mcc, mnc);                     //  as the formula written out in place)
+        // the rule (every lane: a shuffle reads active lanes only)
+        const TrackSlot me = track_slot(st, mv, mg, lane, [&](int h, uint32_t& ah, uint32_t& bh) { ah = shfl_u32(a, h); bh = shfl_u32(b, h); });
         const bool live = f < nf;
         // the group's last live slot is the state the next group (and the next call) starts from; slots past the channel's frame
         // count carry the code in force at its end
         const int last_live = min(nf - f0, kLanes) - 1;                       // < 0: no live slot in this group
         const int src = last_live < 0 ? 0 : last_live;
-        const uint32_t code_end = last_live < 0 ? st.scramb_init : (uint32_t)__shfl((int)scramb, src);
-        const Tdma end_phy = { (uint32_t)__shfl((int)t_after.tn, src), (uint32_t)__shfl((int)t_after.fn, src), (uint32_t)__shfl((int)t_after.mn, src) };
-        const Tdma end_tcd = { (uint32_t)__shfl((int)tcd_now.tn, src), (uint32_t)__shfl((int)tcd_now.fn, src), (uint32_t)__shfl((int)tcd_now.mn, src) };
-        const uint32_t end_cc = (uint32_t)__shfl((int)cc, src), end_mcc = (uint32_t)__shfl((int)mcc, src), end_mnc = (uint32_t)__shfl((int)mnc, src);
+        const TrackSlot end = { shfl_tdma(me.t_rx, src), shfl_tdma(me.t_after, src), shfl_tdma(me.tcd, src),
+                                shfl_u32(me.colour, src), shfl_u32(me.mcc, src), shfl_u32(me.mnc, src), shfl_u32(me.scramb, src) };
+        const uint32_t code_end = last_live < 0 ? st.scramb_init : end.scramb;
         if (f < frames) {
-            const uint32_t o_rx = live ? tdma_pack(t_rx) : 0u, o_t = live ? tdma_pack(t_after) : 0u;
-            row_scramb[r] = live ? scramb : code_end;
+            const uint32_t o_rx = live ? tdma_pack(me.t_rx) : 0u, o_t = live ? tdma_pack(me.t_after) : 0u;
+            row_scramb[r] = live ? me.scramb : code_end;
             if (row_time_rx) row_time_rx[r] = o_rx;
             if (row_time) row_time[r] = o_t;
             if (labels && valid) {
@@ -523,12 +496,7 @@ __global__ __launch_bounds__(kLanes) void k_track(const uint8_t* __restrict__ sb
                 labels[j] = lb;
             }
         }
-        if (last_live >= 0) {
-            st.phy_tn = end_phy.tn; st.phy_fn = end_phy.fn; st.phy_mn = end_phy.mn;
-            st.tcd_tn = end_tcd.tn; st.tcd_fn = end_tcd.fn; st.tcd_mn = end_tcd.mn;
-            st.colour_code = end_cc; st.mcc = end_mcc; st.mnc = end_mnc;
-            st.scramb_init = code_end;
-        }
+        if (last_live >= 0) track_carry(st, end);
     }
     if (lane == 0) store_state(state[c], st);
 }

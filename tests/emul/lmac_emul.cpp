@@ -146,3 +146,48 @@ extern "C" void lmac_emul_tdma_advance(const uint32_t* start, int n, int kmax, u
         for (int k = 1; k <= kmax; ++k)
             out[(size_t)i * kmax + k - 1] = tdma_pack(tdma_advance(Tdma{ start[3 * i], start[3 * i + 1], start[3 * i + 2] }, (uint32_t)k));
 }
+
+// k_track's loop on the host, slot layout (tetra_lmac_track_sync_device): the SAME track_slot / track_carry / sync_pdu_words the kernel
+// calls, with arrays where the kernel has ballots and lane shuffles.  cell [n_channels][10] = tetra_lmac_cell_state_t, in / out.
+// stale_tcd_on_bad_crc != 0 plants the rule the tracker had before it was pinned to the reference (lmac_core.hpp: kStaleTcdOnBadCrc).
+extern "C" void lmac_emul_track(const uint8_t* sb1, int stride, const int32_t* crc_ok, const int32_t* valid_in, const int32_t* n_frames, int n_channels,
+                                int frames, uint32_t* cell, uint32_t* row_scramb, uint32_t* row_time_rx, uint32_t* row_time, int stale_tcd_on_bad_crc) {
+    constexpr int kLanes = 64;
+    for (int c = 0; c < n_channels; ++c) {
+        const int nf = n_frames ? (n_frames[c] < frames ? n_frames[c] : frames) : frames;
+        uint32_t* cs = cell + (size_t)c * 10;
+        TrackState st = { cs[0], cs[1], cs[2], cs[3], Tdma{ cs[4], cs[5], cs[6] }, Tdma{ cs[7], cs[8], cs[9] } };
+        for (int f0 = 0; f0 < frames; f0 += kLanes) {
+            uint32_t a[kLanes] = {}, b[kLanes] = {};
+            unsigned long long mv = 0, mg = 0;
+            for (int lane = 0; lane < kLanes; ++lane) {
+                const int f = f0 + lane;
+                const size_t r = (size_t)c * frames + f;
+                const bool valid = f < frames && valid_in[r] != 0 && f < nf;
+                if (valid) mv |= 1ull << lane;
+                if (valid && crc_ok[r]) {
+                    mg |= 1ull << lane;
+                    const uint8_t* t2 = sb1 + r * stride;
+                    sync_pdu_words([&](int k) -> uint32_t { return t2[4 * k] | (t2[4 * k + 1] << 8) | (t2[4 * k + 2] << 16) | ((uint32_t)t2[4 * k + 3] << 24); },
+                                   a[lane], b[lane]);
+                }
+            }
+            auto words = [&](int h, uint32_t& ah, uint32_t& bh) { ah = a[h]; bh = b[h]; };
+            TrackSlot slot[kLanes];
+            for (int lane = 0; lane < kLanes; ++lane)
+                slot[lane] = stale_tcd_on_bad_crc ? track_slot<true>(st, mv, mg, lane, words) : track_slot<false>(st, mv, mg, lane, words);
+            const int last_live = (nf - f0 < kLanes ? nf - f0 : kLanes) - 1;
+            const uint32_t code_end = last_live < 0 ? st.scramb_init : slot[last_live].scramb;
+            for (int lane = 0; lane < kLanes && f0 + lane < frames; ++lane) {
+                const size_t r = (size_t)c * frames + f0 + lane;
+                const bool live = f0 + lane < nf;
+                row_scramb[r] = live ? slot[lane].scramb : code_end;
+                row_time_rx[r] = live ? tdma_pack(slot[lane].t_rx) : 0u;
+                row_time[r] = live ? tdma_pack(slot[lane].t_after) : 0u;
+            }
+            if (last_live >= 0) track_carry(st, slot[last_live]);
+        }
+        const uint32_t out[10] = { st.scramb_init, st.colour, st.mcc, st.mnc, st.tcd.tn, st.tcd.fn, st.tcd.mn, st.phy.tn, st.phy.fn, st.phy.mn };
+        std::memcpy(cs, out, sizeof(out));
+    }
+}

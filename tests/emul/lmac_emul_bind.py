@@ -73,3 +73,26 @@ def tdma_advance(start, kmax):
     vp = C.c_void_p
     _lib.lmac_emul_tdma_advance(st.ctypes.data_as(vp), len(st), int(kmax), out.ctypes.data_as(vp))
     return out
+
+
+def track(sb1_type2, crc_ok, valid, n_frames, cell, stale_tcd_on_bad_crc=False):
+    """k_track's rule (lmac_core.hpp track_slot / track_carry) built for the host, slot layout: sb1_type2 [n_channels * F][stride] decoded
+    SB1 rows, crc_ok / valid per frame slot, n_frames [n_channels] consumed frames (None: all), cell [n_channels][10] uint32
+    (tetra_lmac_cell_state_t) updated in place -> (code, time on entry, time after the SB1) per frame slot.  stale_tcd_on_bad_crc plants
+    the tracker's earlier rule (a bad-CRC SB1 sets the clock to the last good SYNC PDU's time): for tests that show they would notice."""
+    global _lib
+    if _lib is None:
+        build()
+        _lib = C.CDLL(LIB)
+    rows = np.ascontiguousarray(sb1_type2, np.uint8)
+    n_ch = len(cell)
+    F = rows.shape[0] // n_ch
+    assert cell.dtype == np.uint32 and cell.flags.c_contiguous and cell.shape == (n_ch, 10) and rows.shape[1] >= 56
+    ok, va = np.ascontiguousarray(crc_ok, np.int32), np.ascontiguousarray(valid, np.int32)
+    nf = None if n_frames is None else np.ascontiguousarray(n_frames, np.int32)
+    outs = [np.zeros(n_ch * F, np.uint32) for _ in range(3)]
+    vp = C.c_void_p
+    _lib.lmac_emul_track(rows.ctypes.data_as(vp), int(rows.shape[1]), ok.ctypes.data_as(vp), va.ctypes.data_as(vp),
+                         None if nf is None else nf.ctypes.data_as(vp), n_ch, F, cell.ctypes.data_as(vp), *(o.ctypes.data_as(vp) for o in outs),
+                         int(bool(stale_tcd_on_bad_crc)))
+    return tuple(outs)

@@ -391,9 +391,12 @@ def walk_slots(lref, cell, t2, ok, valid, nfr=None):
     """The SB1 tracking rule walked on the host, per channel in frame-slot order, with the REFERENCE'S OWN tetra_tdma_time_add_tn
     and tetra_scramb_get_init: tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275) + the LOCKED receiver's clock
     (tetra_burst_sync.c:113).  Every consumed frame (slot f < nfr[c]; nfr None: all) advances the PHY time by one timeslot; a valid
-    SB1 with a good CRC sets colour code / TN / FN / MN / MCC / MNC and the scrambling code; the PHY time takes tcd's after EVERY
-    valid SB1, good CRC or not.  cell [C][10] uint32 (tetra_lmac_cell_state_t) is updated in place; t2 / ok / valid are per frame
-    slot [C * F].  Returns the slot outputs (code, time on entry, time after the SB1), as the tracker packs them."""
+    SB1 with a good CRC sets colour code / TN / FN / MN / MCC / MNC and the scrambling code, and the PHY time takes the PDU's.  A valid
+    SB1 with a bad CRC leaves the PHY time where it was: tcd->time is the PHY time on entry of every tp_sap_udata_ind call (:172), only a
+    good CRC overwrites it (:257-266), and :268 copies it back.  The cell's tcd tn / fn / mn are the time of the last SYNC PDU with a
+    good CRC.  Pinned to the reference's own tp_sap_udata_ind by tests/test_sync_track.py.  cell [C][10] uint32
+    (tetra_lmac_cell_state_t) is updated in place; t2 / ok / valid are per frame slot [C * F].  Returns the slot outputs (code, time on
+    entry, time after the SB1), as the tracker packs them."""
     import ctypes as C
     add_tn = _ref_add_tn(lref)
     n_ch = len(cell)
@@ -409,12 +412,11 @@ def walk_slots(lref, cell, t2, ok, valid, nfr=None):
             if f < nf:
                 add_tn(C.byref(phy), 1)
                 t_rx[r] = pack(phy)
-                if valid[r]:
-                    if ok[r]:
-                        val = lambda a, n: int("".join(str(int(x)) for x in t2[r][a:a + n]), 2)
-                        cc, mcc, mnc = val(4, 6), val(31, 10), val(41, 14)
-                        tcd = [val(10, 2) + 1, val(12, 5), val(17, 6)]
-                        code = lref.scramb_get_init(mcc, mnc, cc)
+                if valid[r] and ok[r]:
+                    val = lambda a, n: int("".join(str(int(x)) for x in t2[r][a:a + n]), 2)
+                    cc, mcc, mnc = val(4, 6), val(31, 10), val(41, 14)
+                    tcd = [val(10, 2) + 1, val(12, 5), val(17, 6)]
+                    code = lref.scramb_get_init(mcc, mnc, cc)
                     phy.tn, phy.fn, phy.mn = tcd
                 t_af[r] = pack(phy)
             scr[r] = code
