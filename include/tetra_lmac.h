@@ -11,7 +11,8 @@
  *             K=5 rate-1/4 code of EN 300 392-2 8.2.3.1.1, CONV_TERM_FLUSH)--> type2
  *           --crc16_ccitt_bits(type2, type1_bits+16) == TETRA_CRC_OK (lower_mac/crc_simple.c:103, tetra_common.h:330)--> crc_ok
  * with the block parameters of tetra_blk_param[] (tetra_lower_mac.c:58-105).  TPSAP_T_BBK follows the reference's
- * pass-through (:231-236: descramble only, crc_ok = 1; its Reed-Muller decode is a FIXME there).
+ * pass-through (:231-236: descramble only, crc_ok = 1; its Reed-Muller decode is a FIXME there).  The Reed-Muller decoding itself is
+ * opt-in and declared in tetra_aach.h; nothing in this header changes without it.
  *
  * Bit-exact with the reference for ANY input bytes, including its treatment of non-0/1 bytes (after descrambling a byte
  * 0 is a strong 0, 0xff is an erasure, anything else a strong 1 -- viterbi.c:12-23), the decoder's tie-breaks
@@ -108,6 +109,9 @@ int tetra_lmac_debug_force_byte_route(int on);
  *         d_frame_scramb [n_frames]: the scrambling code per FRAME SLOT (tetra_lmac_track_sync_device's d_row_scramb; NULL for
  *         TETRA_TPSAP_T_SB1, which always uses SCRAMB_INIT).  d_type2 [max_rows][out_stride] (8-byte aligned, out_stride a multiple
  *         of 8 and >= type2_bits; TETRA_TPSAP_T_BBK: 30 descrambled bits + 2 zero bytes, out_stride >= 32), d_crc_ok [max_rows].
+ *         A BBK job whose type carries TETRA_LMAC_JOB_RM3014 (tetra_aach.h) is decoded with the RM(30,14) code instead: the corrected
+ *         codeword (or, beyond 3 bit errors, the descrambled bits), the distance in byte 30, and crc_ok = 0 for an undecodable row --
+ *         which departs from the reference: it reports crc_ok = 1 for every AACH.
  *         d_labels [max_rows], may be NULL: (channel, frame slot, bit number, TDMA times, crc_ok) per row -- needs src's label arrays.
  * Jobs run in the order given; put the long kinds first (SCH/F before SB2 / NDB before BBK).  At most TETRA_LMAC_MAX_JOBS.
  */

@@ -45,7 +45,10 @@ extern "C" {
  * (SB1, BBK, SB2); a NORM_1 burst carries SCH/F + BBK, a NORM_2 burst NDB blk 1 + blk 2 + BBK. */
 enum {
     TETRA_RX_KIND_SB1 = 0,     /* TPSAP_T_SB1, BLK_1: BSCH, the SYNC PDU (60 type-1 bits) */
-    TETRA_RX_KIND_BBK = 1,     /* TPSAP_T_BBK: AACH, 30 descrambled bits (pass-through like the reference, tetra_lower_mac.c:231-236) */
+    TETRA_RX_KIND_BBK = 1,     /* TPSAP_T_BBK: AACH, 30 descrambled bits, crc_ok = 1 (pass-through like the reference, tetra_lower_mac.c:231-236).
+                                  With TETRA_RX_FLAG_AACH_RM3014: the 30 bits of the RM(30,14) codeword within 3 bit errors and crc_ok = 1,
+                                  or the descrambled bits and crc_ok = 0 where there is none -- a verdict the reference, which always
+                                  reports 1, does not give (tetra_aach.h) */
     TETRA_RX_KIND_SB2 = 2,     /* TPSAP_T_SB2, BLK_2 (124 type-1 bits) */
     TETRA_RX_KIND_NDB1 = 3,    /* TPSAP_T_NDB, BLK_1 (124) */
     TETRA_RX_KIND_NDB2 = 4,    /* TPSAP_T_NDB, BLK_2 (124) */
@@ -54,7 +57,8 @@ enum {
 };
 
 enum {
-    TETRA_RX_FLAG_ONE_STREAM = 1   /* run the tail on the caller's stream behind the demodulator (no overlap between calls); A/B, tests */
+    TETRA_RX_FLAG_ONE_STREAM = 1,  /* run the tail on the caller's stream behind the demodulator (no overlap between calls); A/B, tests */
+    TETRA_RX_FLAG_AACH_RM3014 = 2  /* decode the AACH with its Reed-Muller code: up to 3 bit errors corrected, crc_ok = 0 beyond (tetra_aach.h) */
 };
 
 typedef struct tetra_rx_config {

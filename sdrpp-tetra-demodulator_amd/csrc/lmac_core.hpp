@@ -189,7 +189,8 @@ LM_FN void extract_block(const uint32_t fw[kFrameWords], int off0, int len0, int
 }
 
 // where a kind's bits sit in its burst (demux_core::pieces_for), as literal layouts so that every shift is a constant
-enum { kLayoutSb1 = 0, kLayoutSb2, kLayoutNdb1, kLayoutNdb2, kLayoutSchF, kLayoutBbk, kLayoutNone };
+enum { kLayoutSb1 = 0, kLayoutSb2, kLayoutNdb1, kLayoutNdb2, kLayoutSchF, kLayoutBbk, kLayoutNone,
+       kLayoutBbkRm };      // the AACH decoded with its Reed-Muller code (only the kernel's RM instantiation meets it)
 template <int TRAIN, int TPSAP, int BLK>
 LM_FN void cut(const uint32_t fw[kFrameWords], int frame_type, uint32_t xb[kSeqWords]) {
     const demux_core::Pieces p = demux_core::pieces_for(TRAIN, TPSAP, BLK);
@@ -588,6 +589,55 @@ LM_FN void track_carry(TrackState& st, const TrackSlot& end) {
     st.tcd = end.tcd;
     st.colour = end.colour; st.mcc = end.mcc; st.mnc = end.mnc;
     st.scramb_init = end.scramb;
+}
+
+// ---- AACH: the shortened (30,14) Reed-Muller code of EN 300 392-2 8.2.3.2 (include/tetra_aach.h) ----------------------------------------
+// A word holds the block's 30 bits, first bit on air at bit 29: the 14 information bits in bits 29..16, the 16 parity bits in bits
+// 15..0 -- the value format of the reference's tetra_rm3014_compute (lower_mac/tetra_rm3014.c), whose decoder is a stub ("Maybe
+// correct it in the future") and whose caller (tetra_lower_mac.c:230-236, "FIXME: RM3014-decode") never calls it.  The code is
+// systematic, G = [I | P]; row i of P (the parity bits information bit i sets, i = 0 the first bit on air) is a constant of the
+// standard like the training sequences.  Minimum distance 8: the 4526 error patterns of weight <= 3 have 4526 distinct syndromes, so
+// up to three bit errors are corrected and every fourth is detected (tests/test_aach_rm.py checks both exhaustively).
+constexpr int kRm3014Radius = 3;
+constexpr uint32_t kRm3014Undecodable = 0xffu;            // `dist` of a word no codeword lies within the radius of
+constexpr uint32_t kRm3014TableEntries = 1u << 16;        // one per syndrome: 256 KB
+constexpr uint32_t kRm3014NoPattern = 0xffffffffu;        // table entry of a syndrome no pattern of weight <= 3 has
+// the 16 parity bits of 14 information bits (first bit at bit 13): 14 x (extract, AND, XOR) on constants
+LM_HD uint32_t rm3014_parity(uint32_t info) {
+    constexpr uint32_t rows[14] = { 0x9b60u, 0x2de0u, 0xfc20u, 0xe03cu, 0x983au, 0x5436u, 0x2c2eu,
+                                    0xffdfu, 0x8339u, 0x42b5u, 0x21adu, 0x1273u, 0x096bu, 0x04e7u };
+    uint32_t p = 0;
+#pragma unroll
+    for (int i = 0; i < 14; ++i) p ^= rows[i] & (0u - ((info >> (13 - i)) & 1u));
+    return p;
+}
+LM_HD uint32_t rm3014_encode(uint32_t info) { return ((info & 0x3fffu) << 16) | rm3014_parity(info & 0x3fffu); }
+// H w for H = [P^T | I]: zero exactly for codewords, and the syndrome of (codeword ^ e) is that of e
+LM_HD uint32_t rm3014_syndrome(uint32_t word) { return rm3014_parity((word >> 16) & 0x3fffu) ^ (word & 0xffffu); }
+// Syndrome -> the one error pattern of weight <= 3 that has it (kRm3014NoPattern where there is none), from the generator alone:
+// host code, run once per device (tetra_lmac.hip) and by the host emulation.
+inline void rm3014_correction_table(uint32_t* tab) {      // [kRm3014TableEntries]
+    for (uint32_t s = 0; s < kRm3014TableEntries; ++s) tab[s] = kRm3014NoPattern;
+    tab[0] = 0;
+    for (int a = 0; a < 30; ++a) {
+        const uint32_t ea = 1u << a;
+        tab[rm3014_syndrome(ea)] = ea;
+        for (int b = a + 1; b < 30; ++b) {
+            const uint32_t eb = ea | (1u << b);
+            tab[rm3014_syndrome(eb)] = eb;
+            for (int c = b + 1; c < 30; ++c) tab[rm3014_syndrome(eb | (1u << c))] = eb | (1u << c);
+        }
+    }
+}
+// Bounded-distance decoding with radius 3: the codeword within Hamming distance <= 3 of `word` (unique: d = 8) and that distance,
+// else the word unchanged and kRm3014Undecodable.  tab(s) = entry s of rm3014_correction_table; one look-up, no search.
+struct Rm3014Word { uint32_t word, dist; };
+template <class Tab>
+LM_HD Rm3014Word rm3014_decode(uint32_t word, Tab tab) {
+    word &= 0x3fffffffu;
+    const uint32_t e = tab(rm3014_syndrome(word));
+    const bool found = (e >> 30) == 0u;
+    return Rm3014Word{ found ? word ^ e : word, found ? (uint32_t)__builtin_popcount(e) : kRm3014Undecodable };
 }
 
 }  // namespace tetra_lmac

@@ -45,6 +45,7 @@ struct tetra_rx {
     int device = 0, last_hip = 0;
     int C = 0, F = 0, rows = 0, stride = 0, kinds = 0;
     bool one_stream = false;
+    bool aach_rm = false;                 // TETRA_RX_FLAG_AACH_RM3014: the BBK job decodes with the AACH's Reed-Muller code (tetra_aach.h)
     Handle<tetra_demod_t*, tetra_demod_destroy> dem;
     Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
     Stream tail;

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/tetra_aach.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "hip_host.hpp"
@@ -257,8 +258,11 @@ struct JobTable {
 // (backward CRC table) = 4608 B <= 5120: LDS never caps the kernel below 8 waves per SIMD -- which matters beside the demodulator:
 // the compiler sizes a kernel's register allocation for the occupancy its LDS allows (6992 B -> 6 waves -> 80 registers where 54 are
 // used), and next to k_fused's 199-register waves every 8 registers decide how many of this kernel's waves fit a SIMD.
+// RM: the instantiation that also knows kLayoutBbkRm -- the AACH's 30 descrambled bits through rm3014_decode (one syndrome, one look-up
+// in rm_tab), a lane per block like the pass-through.  Launched only when a job asks for it; <false> is the kernel as it was.
+template <bool RM>
 __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint32_t* __restrict__ dec_scratch,
-                                                        const uint32_t* __restrict__ seq_tab) {
+                                                        const uint32_t* __restrict__ seq_tab, const uint32_t* __restrict__ rm_tab) {
     __shared__ union {
         uint32_t cls[kSeqWords][kLanes];
         OutW outw;
@@ -294,16 +298,24 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
         }
     }
     bool good = true;
-    if (J.layout == kLayoutBbk) {
+    const bool bbk = J.layout == kLayoutBbk || (RM && J.layout == kLayoutBbkRm);
+    if (bbk) {
         // TPSAP_T_BBK: the reference only descrambles (tetra_lower_mac.c:231-236): 30 bits -> 30 bytes (+ 2 zero bytes), a row per lane
         const uint32_t x = bbk_bits(fw, ft);
         const uint32_t seq = seq_tab[((size_t)0 * 256 + (code & 0xffu)) * kSeqStride] ^ seq_tab[((size_t)1 * 256 + ((code >> 8) & 0xffu)) * kSeqStride] ^
                              seq_tab[((size_t)2 * 256 + ((code >> 16) & 0xffu)) * kSeqStride] ^ seq_tab[((size_t)3 * 256 + (code >> 24)) * kSeqStride];
-        const uint32_t y = (x ^ seq) & 0xfffffffcu;          // 30 bits, first bit most significant
+        uint32_t y = (x ^ seq) & 0xfffffffcu;                // 30 bits, first bit most significant
+        uint32_t tail = 0;                                   // row bytes 30, 31
+        if (RM && J.layout == kLayoutBbkRm) {
+            const Rm3014Word r = rm3014_decode(y >> 2, [&](uint32_t s) { return rm_tab[s]; });
+            y = r.word << 2;
+            tail = r.dist << 16;
+            good = r.dist <= (uint32_t)kRm3014Radius;
+        }
         if (blk < n_blocks) {
             demux_core::U2* dst = reinterpret_cast<demux_core::U2*>(J.out + (size_t)blk * J.out_stride);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) dst[k] = demux_core::U2{ bbk_bytes(y, 2 * k), bbk_bytes(y, 2 * k + 1) };
+            for (int k = 0; k < 4; ++k) dst[k] = demux_core::U2{ bbk_bytes(y, 2 * k), bbk_bytes(y, 2 * k + 1) | (k == 3 ? tail : 0u) };
         }
     } else {
         uint32_t xb[kSeqWords];
@@ -328,7 +340,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
             J.labels[blk] = lb;
         }
     }
-    if (J.layout != kLayoutBbk) {
+    if (!bbk) {
         __syncthreads();
         write_rows(outw, lane, rows_here, J.type2, J.out + (size_t)blk0 * J.out_stride, J.out_stride);
     }
@@ -358,6 +370,29 @@ const uint32_t* seq_table() {
     return g_seq_tab[dev];
 }
 
+// Per-device constant of the AACH's Reed-Muller decoding (tetra_aach.h): syndrome -> error pattern, 2^16 entries = 256 KB, built on the
+// host from the generator on first use (the lock makes that safe for concurrent handles: one per GPU in a multi-GPU bank) and kept,
+// like the scrambling table above, for the life of the process.
+std::mutex g_rm_mu;
+uint32_t* g_rm_tab[64] = {};
+const uint32_t* rm3014_table() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    std::lock_guard<std::mutex> g(g_rm_mu);
+    if (!g_rm_tab[dev]) {
+        std::vector<uint32_t> host(kRm3014TableEntries);
+        rm3014_correction_table(host.data());
+        DevMem<uint32_t> d_tab;
+        if (d_tab.reserve(sizeof(uint32_t) * host.size()) != hipSuccess ||
+            hipMemcpy(d_tab, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        g_rm_tab[dev] = d_tab.release();
+    }
+    return g_rm_tab[dev];
+}
+
 // The decoder's decision scratch (up to 200 MB for a second of 4096 channels' SCH/F slots) comes from a stream-ordered pool of this
 // library's own, one per device, that KEEPS what is freed into it (release threshold = everything).  The device's default pool hands
 // unused memory back to the driver at synchronisation points; the next call then maps 200 MB again and takes milliseconds instead of
@@ -384,17 +419,51 @@ hipMemPool_t scratch_pool() {
 }
 
 // TPSAP_T_BBK: the reference only descrambles (tetra_lower_mac.c:231-236); 30 bits per block, one lane per block.
+// RM (tetra_lmac_decode_aach_rm3014_device): the descrambled bytes are also gathered into the 30-bit word (a byte other than 0 is a 1),
+// rm3014_decode runs on it, a decodable row is rewritten with the codeword's bits, byte 30 takes the distance and byte 31 a zero
+// (rows of at least 32 bytes).  The table is a trailing parameter pack -- one pointer for RM, none otherwise -- so that the instantiation
+// without the option has the argument block, and with it the instruction stream, it had before the option existed.
+template <class T> __device__ __forceinline__ T only_of(T t) { return t; }
+template <bool RM, class... Tab>
 __global__ __launch_bounds__(256) void k_lmac_bbk(const uint8_t* __restrict__ type5, int n_blocks, int in_stride,
                                                   const uint32_t* __restrict__ scramb_init, int nbits,
                                                   uint8_t* __restrict__ out, int out_stride, int* __restrict__ crc_ok,
-                                                  const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index) {
+                                                  const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index,
+                                                  Tab... rm_tab_pack) {
     const int blk = blockIdx.x * blockDim.x + threadIdx.x;
     if (blk >= n_blocks || (n_blocks_dev && blk >= *n_blocks_dev)) return;
     uint32_t lfsr = scramb_init[init_index ? init_index[blk] : blk];
     const uint8_t* src = type5 + (size_t)blk * in_stride;
     uint8_t* dst = out + (size_t)blk * out_stride;
-    for (int j = 0; j < nbits; ++j) dst[j] = src[j] ^ (uint8_t)lfsr_next(lfsr);
-    crc_ok[blk] = 1;
+    if constexpr (!RM) {
+        for (int j = 0; j < nbits; ++j) dst[j] = src[j] ^ (uint8_t)lfsr_next(lfsr);
+        crc_ok[blk] = 1;
+    } else {
+        const uint32_t* __restrict__ rm_tab = only_of(rm_tab_pack...);
+        uint32_t word = 0;
+        for (int j = 0; j < 30; ++j) {
+            const uint8_t v = src[j] ^ (uint8_t)lfsr_next(lfsr);
+            dst[j] = v;
+            word = (word << 1) | (v ? 1u : 0u);
+        }
+        const Rm3014Word r = rm3014_decode(word, [&](uint32_t s) { return rm_tab[s]; });
+        const bool good = r.dist <= (uint32_t)kRm3014Radius;
+        if (good)
+            for (int j = 0; j < 30; ++j) dst[j] = (uint8_t)((r.word >> (29 - j)) & 1u);
+        dst[30] = (uint8_t)r.dist;
+        dst[31] = 0;
+        crc_ok[blk] = good;
+    }
+}
+
+// the bare primitive (tetra_lmac_rm3014_decode_device): a lane per 30-bit word
+__global__ __launch_bounds__(256) void k_rm3014(const uint32_t* __restrict__ words, int n, uint32_t* __restrict__ out_words,
+                                                uint8_t* __restrict__ dist, const uint32_t* __restrict__ rm_tab) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Rm3014Word r = rm3014_decode(words[i], [&](uint32_t s) { return rm_tab[s]; });
+    out_words[i] = r.word;
+    dist[i] = (uint8_t)r.dist;
 }
 
 // The SB1 tracking rule, every entry point's: the SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275, with the
@@ -544,7 +613,7 @@ int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blo
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const BlkParam& p = kBlk[type];
     if (type == TETRA_TPSAP_T_BBK) {
-        hipLaunchKernelGGL(k_lmac_bbk, dim3((n_blocks + 255) / 256), dim3(256), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
+        hipLaunchKernelGGL(k_lmac_bbk<false>, dim3((n_blocks + 255) / 256), dim3(256), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
                            p.type345, d_type2, out_stride, d_crc_ok, d_n_blocks, d_init_index);
     } else {
         // decision scratch: (type2 + 4) steps x 64 lanes x u16 per workgroup, from the library's keeping pool (scratch_pool():
@@ -579,8 +648,11 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
     tab.src = DevFrames{ src->d_frames, src->d_frame_type, src->d_frame_bitnum, src->d_time_rx, src->d_time, src->frames_per_channel, src->n_frames };
     long long groups_total = 0, scratch_words = 0;
     int n = 0, max_pairs = 0;
+    bool any_rm = false;
     for (int i = 0; i < n_jobs; ++i) {
-        const tetra_lmac_job_t& j = jobs[i];
+        tetra_lmac_job_t j = jobs[i];
+        const bool rm = j.type == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014);       // (the flag on any other type: refused below)
+        if (rm) j.type = TETRA_TPSAP_T_BBK;
         if (j.type < 0 || j.type > 5 || j.max_rows < 0) return TETRA_ERR_ARG;
         if (j.max_rows == 0) continue;
         if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok) return TETRA_ERR_ARG;
@@ -591,13 +663,15 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
             case TETRA_TPSAP_T_SB1: layout = j.blk_num == 1 ? kLayoutSb1 : kLayoutNone; break;
             case TETRA_TPSAP_T_SB2: layout = j.blk_num == 2 ? kLayoutSb2 : kLayoutNone; break;
             case TETRA_TPSAP_T_NDB: layout = j.blk_num == 1 ? kLayoutNdb1 : j.blk_num == 2 ? kLayoutNdb2 : kLayoutNone; break;
-            case TETRA_TPSAP_T_BBK: layout = kLayoutBbk; break;
+            case TETRA_TPSAP_T_BBK: layout = rm ? kLayoutBbkRm : kLayoutBbk; break;
             case TETRA_TPSAP_T_SCH_F: layout = kLayoutSchF; break;
             default: break;                                    // SCH/HU: an uplink block, no downlink burst carries it
         }
         if (layout == kLayoutNone) return TETRA_ERR_ARG;       // no burst type carries this (kind, block number)
         const BlkParam& p = kBlk[j.type];
-        if (j.out_stride < (layout == kLayoutBbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
+        const bool bbk = layout == kLayoutBbk || layout == kLayoutBbkRm;
+        any_rm = any_rm || rm;
+        if (j.out_stride < (bbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
         if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
         DevJob& d = tab.job[n++];
         d.row_frame = j.d_row_frame;
@@ -610,7 +684,7 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
         d.out_stride = j.out_stride;
         d.layout = layout;
         d.type345 = p.type345; d.type2 = p.type2; d.a = p.a;
-        d.dec_pairs = layout == kLayoutBbk ? 0 : (p.type2 + kFlush) / 2;
+        d.dec_pairs = bbk ? 0 : (p.type2 + kFlush) / 2;
         max_pairs = d.dec_pairs > max_pairs ? d.dec_pairs : max_pairs;
         const long long groups = ((long long)j.max_rows + kLanes - 1) / kLanes;
         d.first_group = (int)groups_total;
@@ -640,7 +714,13 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
             pooled = true;
         }
     }
-    hipLaunchKernelGGL(k_lmac_frames, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq);
+    if (any_rm) {
+        const uint32_t* rm_tab = rm3014_table();
+        if (!rm_tab) { if (pooled) (void)hipFreeAsync(scratch, s); return TETRA_ERR_NOMEM; }
+        hipLaunchKernelGGL(k_lmac_frames<true>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq, rm_tab);
+    } else {
+        hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq, nullptr);
+    }
     const hipError_t launch = hipGetLastError();
     if ((pooled && hipFreeAsync(scratch, s) != hipSuccess) || launch != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
@@ -655,6 +735,30 @@ size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, in
         words += (size_t)(((long long)j.max_rows + kLanes - 1) / kLanes) * ((kBlk[j.type].type2 + kFlush) / 2) * kLanes;
     }
     return words * sizeof(uint32_t);
+}
+
+int tetra_lmac_rm3014_decode_device(const uint32_t* d_words, int n, uint32_t* d_out_words, uint8_t* d_dist, void* hip_stream) {
+    if (n < 0) return TETRA_ERR_ARG;
+    if (n == 0) return TETRA_OK;
+    if (!d_words || !d_out_words || !d_dist) return TETRA_ERR_ARG;
+    if (((uintptr_t)d_words & 3) || ((uintptr_t)d_out_words & 3)) return TETRA_ERR_ALIGN;
+    const uint32_t* rm_tab = rm3014_table();
+    if (!rm_tab) return TETRA_ERR_NOMEM;
+    hipLaunchKernelGGL(k_rm3014, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_words, n, d_out_words, d_dist,
+                       rm_tab);
+    return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
+}
+
+int tetra_lmac_decode_aach_rm3014_device(const uint8_t* d_type5, int n_blocks, int in_stride, const uint32_t* d_scramb_init,
+                                         uint8_t* d_type2, int out_stride, int32_t* d_crc_ok, void* hip_stream) {
+    const int rc = check_args(TETRA_TPSAP_T_BBK, d_type5, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_crc_ok, true);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    if (out_stride < 32) return TETRA_ERR_ARG;                 // bytes 30 and 31 of a row
+    const uint32_t* rm_tab = rm3014_table();
+    if (!rm_tab) return TETRA_ERR_NOMEM;
+    hipLaunchKernelGGL((k_lmac_bbk<true, const uint32_t*>), dim3((n_blocks + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_type5, n_blocks,
+                       in_stride, d_scramb_init, 30, d_type2, out_stride, d_crc_ok, nullptr, nullptr, rm_tab);
+    return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
 int tetra_lmac_debug_force_byte_route(int on) {

@@ -21,6 +21,7 @@
 #include <memory>
 #include <new>
 
+#include "../../include/tetra_aach.h"
 #include "../../include/tetra_rx.h"
 #include "rx_handle.hpp"
 
@@ -33,6 +34,12 @@ __global__ __launch_bounds__(256) void k_rx_pack_type1(const uint8_t* __restrict
     if (i >= (long long)n * half) return;
     const int j = (int)(i / half), u = (int)(i - (long long)j * half);
     reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(t2 + (size_t)j * in_stride)[u];
+}
+
+// byte `at` of the first n rows, packed (tetra_rx_fetch_aach_dist)
+__global__ __launch_bounds__(256) void k_rx_pack_byte(const uint8_t* __restrict__ t2, int in_stride, int at, int n, uint8_t* __restrict__ out) {
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j < n) out[j] = t2[(size_t)j * in_stride + at];
 }
 
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
@@ -65,7 +72,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         const KindInfo& ki = kKinds[k];
         const KindBufs& r = h->res[b][k];
         tetra_lmac_job_t j = {};
-        j.type = ki.tpsap;
+        j.type = ki.tpsap | (k == TETRA_RX_KIND_BBK && h->aach_rm ? TETRA_LMAC_JOB_RM3014 : 0);
         j.blk_num = ki.blk;
         j.d_row_frame = r.row_frame;
         j.d_n_rows = r.n_rows;
@@ -118,13 +125,15 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~TETRA_RX_FLAG_ONE_STREAM)) return TETRA_ERR_ARG;
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014)))
+        return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
     h->cfg = *cfg;
     h->cfg.demod.rrc_taps = h->cfg.demod.bandedge_taps = h->cfg.demod.interp_bank = nullptr;
     h->kinds = (cfg->kinds ? cfg->kinds : (1 << TETRA_RX_N_KINDS) - 1) | (1 << TETRA_RX_KIND_SB1);
     h->one_stream = (cfg->flags & TETRA_RX_FLAG_ONE_STREAM) != 0;
+    h->aach_rm = (cfg->flags & TETRA_RX_FLAG_AACH_RM3014) != 0;
     TETRA_TRY(tetra_demod_create(&cfg->demod, h->dem.put()));
     h->C = cfg->demod.n_channels;
     int dev = cfg->demod.device;
@@ -296,6 +305,35 @@ int tetra_rx_fetch(tetra_rx_t* h, int which, int kind, tetra_rx_block_t* blocks,
             HIP_TRY(h, hipMemcpy2D(type1, (size_t)type1_stride, r.t2, (size_t)kKinds[kind].out_stride, (size_t)nb, (size_t)n, hipMemcpyDeviceToHost));
         }
     }
+    return TETRA_OK;
+}
+
+int tetra_rx_fetch_aach_dist(tetra_rx_t* h, int which, uint8_t* dist, int capacity, int* n_rows) {
+    if (!h || !n_rows || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
+    if (!h->aach_rm || !(h->kinds & (1 << TETRA_RX_KIND_BBK))) return TETRA_ERR_UNSUPPORTED;
+    *n_rows = 0;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
+    const KindBufs& r = h->res[b][TETRA_RX_KIND_BBK];
+    int32_t n = 0;
+    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
+    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
+    *n_rows = n;
+    if (n > capacity) return dist ? TETRA_ERR_SIZE : TETRA_OK;
+    if (n == 0 || !dist) return TETRA_OK;
+    // packed on the device, one copy (see tetra_rx_fetch)
+    if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
+        (void)hipGetLastError();
+        return TETRA_ERR_NOMEM;
+    }
+    hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[TETRA_RX_KIND_BBK].out_stride, 30, n,
+                       h->fetch_stage);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(dist, h->fetch_stage, (size_t)n, hipMemcpyDeviceToHost, h->fetch_s));
+    HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
     return TETRA_OK;
 }
 

@@ -9,6 +9,10 @@ LMAC_EXPORTS = ["tetra_lmac_blk_param", "tetra_lmac_scramb_init", "tetra_lmac_de
                 "tetra_lmac_track_scramb_device", "tetra_lmac_decode_counted_device", "tetra_lmac_track_sync_device",
                 "tetra_lmac_debug_force_byte_route", "tetra_lmac_decode_frames_device", "tetra_lmac_track_sync_lists_device",
                 "tetra_lmac_decode_frames_workspace_bytes"]
+# include/tetra_aach.h: the lower MAC's share (the receive chain's is in rx_binding.RX_AACH_EXPORTS)
+AACH_EXPORTS = ["tetra_lmac_rm3014_decode_device", "tetra_lmac_decode_aach_rm3014_device"]
+JOB_RM3014 = 0x100            # TETRA_LMAC_JOB_RM3014: OR into a BBK job's type for decode_frames_device
+AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 # enum tp_sap_data_type (src/decoder/src/phy/tetra_burst.h:9-16)
 TPSAP_T_SB1, TPSAP_T_SB2, TPSAP_T_NDB, TPSAP_T_BBK, TPSAP_T_SCH_HU, TPSAP_T_SCH_F = range(6)
 
@@ -216,3 +220,30 @@ def track_sync_lists_device(d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d
                                               _ptr(d_row_time_rx), _ptr(d_row_time), _ptr(d_frame_bitnum), _ptr(d_sb1_labels), s)
     if rc:
         raise TetraDemodError(rc, "tetra_lmac_track_sync_lists_device")
+
+
+def _stream(stream):
+    return None if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+
+
+def rm3014_decode_device(d_words, n, d_out_words, d_dist, stream=None):
+    """tetra_lmac_rm3014_decode_device (include/tetra_aach.h): torch tensors on the GPU -- int32 / uint32 [n] 30-bit words in and out,
+    uint8 [n] distances (0..3, or AACH_UNDECODABLE and the word unchanged)."""
+    L = _lib()
+    L.tetra_lmac_rm3014_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tetra_lmac_rm3014_decode_device.restype = C.c_int
+    rc = L.tetra_lmac_rm3014_decode_device(_ptr(d_words), int(n), _ptr(d_out_words), _ptr(d_dist), _stream(stream))
+    if rc:
+        raise TetraDemodError(rc, "tetra_lmac_rm3014_decode_device")
+
+
+def decode_aach_rm3014_device(d_type5, n_blocks, in_stride, d_scramb, d_type2, out_stride, d_crc_ok, stream=None):
+    """tetra_lmac_decode_aach_rm3014_device: decode_batch_device for TPSAP_T_BBK rows with the RM(30,14) decoding behind the
+    descrambler; rows of >= 32 bytes out (30 bits, the distance, a zero)."""
+    L = _lib()
+    L.tetra_lmac_decode_aach_rm3014_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.tetra_lmac_decode_aach_rm3014_device.restype = C.c_int
+    rc = L.tetra_lmac_decode_aach_rm3014_device(_ptr(d_type5), int(n_blocks), int(in_stride), _ptr(d_scramb), _ptr(d_type2), int(out_stride),
+                                                _ptr(d_crc_ok), _stream(stream))
+    if rc:
+        raise TetraDemodError(rc, "tetra_lmac_decode_aach_rm3014_device")

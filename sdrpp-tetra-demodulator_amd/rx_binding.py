@@ -12,9 +12,13 @@ RX_EXPORTS = ["tetra_rx_default_config", "tetra_rx_create", "tetra_rx_destroy", 
               "tetra_rx_get_cell", "tetra_rx_get_sync_state", "tetra_rx_bits_device", "tetra_rx_demod", "tetra_rx_stage_ms"]
 # include/tetra_retune.h (resets of single channels while the stream runs): the chain's share
 RX_RETUNE_EXPORTS = ["tetra_rx_reset_channels_device"]
+# include/tetra_aach.h (the AACH decoded with its Reed-Muller code): the chain's share
+RX_AACH_EXPORTS = ["tetra_rx_fetch_aach_dist"]
 KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
 N_KINDS = 6
 FLAG_ONE_STREAM = 1
+FLAG_AACH_RM3014 = 2          # TETRA_RX_FLAG_AACH_RM3014
+AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
 
 class RxConfig(C.Structure):
@@ -66,6 +70,9 @@ def _lib():
         if hasattr(L, "tetra_rx_reset_channels_device"):       # (a TETRA_DEMOD_LIB override may be an older build without it)
             L.tetra_rx_reset_channels_device.argtypes = [vp, vp, i32, vp]
             L.tetra_rx_reset_channels_device.restype = i32
+        if hasattr(L, "tetra_rx_fetch_aach_dist"):
+            L.tetra_rx_fetch_aach_dist.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+            L.tetra_rx_fetch_aach_dist.restype = i32
         _ready = True
     return L
 
@@ -158,6 +165,17 @@ class RxChain:
         self._chk(self._lib.tetra_rx_fetch(self._h, which, kind, blocks.ctypes.data_as(C.c_void_p), t1.ctypes.data_as(C.c_void_p), nb,
                                            max(n, 1), C.byref(got)), "tetra_rx_fetch")
         return blocks[:got.value], t1[:got.value]
+
+    def fetch_aach_dist(self, which=0):
+        """tetra_rx_fetch_aach_dist: uint8 [n], byte 30 of every BBK row in fetch(KIND_BBK)'s order -- the Hamming distance 0..3 the
+        RM(30,14) decoder corrected, or AACH_UNDECODABLE.  Needs a handle created with FLAG_AACH_RM3014."""
+        n = C.c_int(0)
+        self._chk(self._lib.tetra_rx_fetch_aach_dist(self._h, which, None, 0, C.byref(n)), "tetra_rx_fetch_aach_dist")
+        dist = np.zeros(max(n.value, 1), np.uint8)
+        got = C.c_int(0)
+        self._chk(self._lib.tetra_rx_fetch_aach_dist(self._h, which, dist.ctypes.data_as(C.c_void_p), max(n.value, 1), C.byref(got)),
+                  "tetra_rx_fetch_aach_dist")
+        return dist[:got.value]
 
     def cells(self, first=0, count=None):
         count = self.n_channels - first if count is None else count

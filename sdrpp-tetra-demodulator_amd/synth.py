@@ -266,7 +266,7 @@ def tdma_time_of_slot(s):
     return s % 4 + 1, (s // 4) % 18 + 1, (s // 72) % 60 + 1
 
 
-def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0):
+def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None):
     """A coded continuous downlink of one cell: slot s (absolute s + slot0) carries
          s % 4 == 0   SYNC burst: SB1 = SYNC PDU (60 type-1 bits: the cell's colour code at bits 4..9, the slot's TN-1 / FN / MN at
                       10..11 / 12..16 / 17..22, MCC at 31..40, MNC at 41..54 -- the fields tetra_lower_mac.c:246-275 reads --, the rest
@@ -274,7 +274,9 @@ def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0):
          s % 4 == 2   normal burst with two logical channels: NDB block 1 + block 2 (124 random type-1 bits each), AACH
          otherwise    normal burst with one logical channel: SCH/F (268 random type-1 bits), AACH
     everything but SB1 scrambled with the cell's code.  Returns (bits uint8 [n_slots * 510], sent) with sent = {kind: [(slot,
-    type-1 bits)]} for kind in sb1 / sb2 / ndb1 / ndb2 / schf / bbk (bbk: the 30 descrambled AACH bits)."""
+    type-1 bits)]} for kind in sb1 / sb2 / ndb1 / ndb2 / schf / bbk (bbk: the 30 descrambled AACH bits).
+    aach: uint8 [n_slots][30], the AACH's 30 bits per slot before scrambling (e.g. RM(30,14) codewords, with or without bit errors)
+    in place of the seeded random bits; everything else of the stream is the same with and without it."""
     rng = np.random.default_rng(seed)
     mcc, mnc, cc = cell
     code = tx_scramb_code(mcc, mnc, cc)
@@ -291,6 +293,8 @@ def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0):
     t1 = {"sb1": pdu, "sb2": rng.integers(0, 2, (len(s_sync), 124), dtype=np.uint8),
           "ndb1": rng.integers(0, 2, (len(s_ndb), 124), dtype=np.uint8), "ndb2": rng.integers(0, 2, (len(s_ndb), 124), dtype=np.uint8),
           "schf": rng.integers(0, 2, (len(s_schf), 268), dtype=np.uint8), "bbk": rng.integers(0, 2, (n_slots, 30), dtype=np.uint8)}
+    if aach is not None:
+        t1["bbk"] = np.ascontiguousarray(aach, np.uint8).reshape(n_slots, 30) & 1
     t5 = {k: tx_encode({"ndb1": "ndb", "ndb2": "ndb"}.get(k, k), v, np.full(len(v), code, np.uint32)) for k, v in t1.items() if k != "bbk"}
     bb = t1["bbk"] ^ tx_scramb_seq([code], 30)[0][None, :]
     out = np.zeros((n_slots, 510), np.uint8)
