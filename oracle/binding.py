@@ -6,12 +6,12 @@ bench.py's cpu_baseline leg -- never by the product package.  PARITY UNPINNED
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from . import hostlib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "libtetra_oracle.so")
 
 MAX_TAPS = 129
 PHASES = 128
@@ -65,15 +65,15 @@ class Tables(C.Structure):
     ]
 
 
+def _make(target, deps, extra="", force=False):
+    """A library of oracle/Makefile, kept current by hostlib (the Makefile holds the compile commands and is a dependency)."""
+    return hostlib.build(os.path.join(_HERE, target), ["make", "-B", target, "OUT=" + hostlib.OUT],
+                         [os.path.join(_HERE, f) for f in deps + ["Makefile"]], extra, force)
+
+
 def build(force=False):
-    """Compile the oracle with gcc if the .so is missing or older than its sources."""
-    srcs = [os.path.join(_HERE, f) for f in ("tetra_oracle.c", "tetra_oracle.h", "Makefile")]
-    stale = force or not os.path.exists(_LIB_PATH) or any(
-        os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
-    if stale:
-        subprocess.run(["make", "-C", _HERE, "-B", "libtetra_oracle.so"], check=True,
-                       stdout=subprocess.DEVNULL)
-    return _LIB_PATH
+    """Compile the oracle with gcc if the .so is missing or was built from other sources than the tree holds."""
+    return _make("libtetra_oracle.so", ["tetra_oracle.c", "tetra_oracle.h"], force=force)
 
 
 _lib = None
@@ -82,34 +82,22 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        build()
-        L = C.CDLL(_LIB_PATH)
-        L.tetra_oracle_default_cfg.argtypes = [C.POINTER(Cfg)]
-        L.tetra_oracle_default_cfg.restype = None
-        L.tetra_oracle_design.argtypes = [C.POINTER(Cfg), C.POINTER(Tables)]
-        L.tetra_oracle_design.restype = C.c_int
-        L.tetra_oracle_reset.argtypes = [C.POINTER(Tables), C.POINTER(State)]
-        L.tetra_oracle_reset.restype = None
-        L.tetra_oracle_reset_reference.argtypes = [C.POINTER(Tables), C.POINTER(State)]
-        L.tetra_oracle_reset_reference.restype = None
-        L.tetra_oracle_reset_timing.argtypes = [C.POINTER(Tables), C.POINTER(State)]
-        L.tetra_oracle_reset_timing.restype = None
-        L.tetra_oracle_set_param.argtypes = [C.POINTER(Tables), C.c_int, C.c_double, C.c_int]
-        L.tetra_oracle_set_param.restype = C.c_int
-        L.tetra_oracle_sincosf.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.tetra_oracle_sincosf.restype = None
-        vp = C.c_void_p
-        L.tetra_oracle_process.argtypes = [C.POINTER(Tables), C.POINTER(State), C.c_int, vp, vp, vp, vp, vp, vp]
-        L.tetra_oracle_process.restype = C.c_int
-        L.tetra_oracle_process_mode.argtypes = [C.POINTER(Tables), C.POINTER(State), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
-        L.tetra_oracle_process_mode.restype = C.c_int
-        L.tetra_oracle_process_batch.argtypes = [C.POINTER(Tables), C.POINTER(State), C.c_int, C.c_int,
-                                                 C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]
-        L.tetra_oracle_process_batch.restype = C.c_int
-        L.tetra_oracle_max_threads.restype = C.c_int
-        L.tetra_oracle_fmaf_chain_matmul.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
-        L.tetra_oracle_fmaf_chain_matmul.restype = None
-        _lib = L
+        vp, i32, T, S = C.c_void_p, C.c_int, C.POINTER(Tables), C.POINTER(State)
+        _lib = hostlib.load(build(), {
+            "tetra_oracle_default_cfg": (None, [C.POINTER(Cfg)]),
+            "tetra_oracle_design": (i32, [C.POINTER(Cfg), T]),
+            "tetra_oracle_reset": (None, [T, S]),
+            "tetra_oracle_reset_reference": (None, [T, S]),
+            "tetra_oracle_reset_timing": (None, [T, S]),
+            "tetra_oracle_set_param": (i32, [T, i32, C.c_double, i32]),
+            "tetra_oracle_rrc_taps_grown": (None, [S, i32]),
+            "tetra_oracle_sincosf": (None, [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+            "tetra_oracle_process": (i32, [T, S, i32, vp, vp, vp, vp, vp, vp]),
+            "tetra_oracle_process_mode": (i32, [T, S, i32, i32, vp, vp, vp, vp, vp, vp]),
+            "tetra_oracle_process_batch": (i32, [T, S, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+            "tetra_oracle_max_threads": (i32, []),
+            "tetra_oracle_fmaf_chain_matmul": (None, [vp, vp, i32, i32, i32, vp]),
+        })
     return _lib
 
 
@@ -235,7 +223,6 @@ def process_batch(iq, cfg=None, chunk=0, threads=0, want_sym=False, states=None,
     return bits, nb, sym, states
 
 
-_FAST_LIB_PATH = os.path.join(_HERE, "libtetra_fast.so")
 _fast = None
 
 
@@ -244,21 +231,10 @@ def fast_lib():
     THAT RUNS IT (a prebuilt file from another machine is rebuilt: its instruction set may not match)."""
     global _fast
     if _fast is None:
-        src = os.path.join(_HERE, "tetra_fast.c")
-        stamp = _FAST_LIB_PATH + ".host"
         host = open("/proc/cpuinfo").read().split("flags", 1)[-1].split("\n", 1)[0] if os.path.exists("/proc/cpuinfo") else ""
-        fresh = (os.path.exists(_FAST_LIB_PATH) and os.path.getmtime(src) <= os.path.getmtime(_FAST_LIB_PATH) and
-                 os.path.exists(stamp) and open(stamp).read() == host)
-        if not fresh:
-            subprocess.run(["make", "-C", _HERE, "-B", "libtetra_fast.so"], check=True, stdout=subprocess.DEVNULL)
-            with open(stamp, "w") as f:
-                f.write(host)
-        L = C.CDLL(_FAST_LIB_PATH)
-        vp = C.c_void_p
-        L.tetra_fast_process_batch.argtypes = [C.POINTER(Tables), C.POINTER(State), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
-                                               C.c_int, vp]
-        L.tetra_fast_process_batch.restype = C.c_int
-        _fast = L
+        i32, vp = C.c_int, C.c_void_p
+        _fast = hostlib.load(_make("libtetra_fast.so", ["tetra_fast.c", "tetra_oracle.h"], extra=host), {
+            "tetra_fast_process_batch": (i32, [C.POINTER(Tables), C.POINTER(State), i32, i32, i32, i32, vp, vp, i32, vp])})
     return _fast
 
 
@@ -348,32 +324,20 @@ def max_threads():
 # ---------------------------------------------------------------------------------------------------------
 # Channeliser front-end definition (oracle/chan_oracle.c) -- test infrastructure, like everything in here.
 # ---------------------------------------------------------------------------------------------------------
-_CHAN_LIB_PATH = os.path.join(_HERE, "libchan_oracle.so")
 _chan = None
 
 
 def chan_lib():
     global _chan
     if _chan is None:
-        src = os.path.join(_HERE, "chan_oracle.c")
-        if not os.path.exists(_CHAN_LIB_PATH) or os.path.getmtime(src) > os.path.getmtime(_CHAN_LIB_PATH):
-            subprocess.run(["make", "-C", _HERE, "-B", "libchan_oracle.so"], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(_CHAN_LIB_PATH)
-        vp = C.c_void_p
-        L.chan_oracle_prototype.argtypes = [C.c_int, C.c_int, C.c_double, vp]
-        L.chan_oracle_prototype.restype = None
-        L.chan_oracle_process.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
-                                          C.c_int, vp, vp]
-        L.chan_oracle_process.restype = C.c_int
-        L.chan_oracle_process_channels.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
-                                                   C.c_int, vp, vp, C.c_int, vp]
-        L.chan_oracle_process_channels.restype = C.c_int
-        L.resamp_oracle_prototype.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]
-        L.resamp_oracle_prototype.restype = None
-        L.resamp_oracle_process.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                            C.c_int, vp, vp]
-        L.resamp_oracle_process.restype = C.c_int
-        _chan = L
+        vp, i32, f64, pi32, pi64 = C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        _chan = hostlib.load(_make("libchan_oracle.so", ["chan_oracle.c"]), {
+            "chan_oracle_prototype": (None, [i32, i32, f64, vp]),
+            "chan_oracle_process": (i32, [i32, i32, i32, vp, vp, pi32, pi64, i32, vp, vp]),
+            "chan_oracle_process_channels": (i32, [i32, i32, i32, vp, vp, pi32, pi64, i32, vp, vp, i32, vp]),
+            "resamp_oracle_prototype": (None, [i32, i32, i32, f64, f64, vp]),
+            "resamp_oracle_process": (i32, [i32, i32, i32, vp, i32, vp, pi64, pi64, i32, vp, vp]),
+        })
     return _chan
 
 
@@ -433,7 +397,6 @@ class ResampOracle:
 # ---------------------------------------------------------------------------------------------------------------------
 # Burst synchroniser + burst demultiplexer restatement (oracle/burst_sync_oracle.c)
 # ---------------------------------------------------------------------------------------------------------------------
-_BSYNC_LIB_PATH = os.path.join(_HERE, "libbsync_oracle.so")
 _bsync = None
 RX_S_UNLOCKED, RX_S_KNOW_FSTART, RX_S_LOCKED = 0, 1, 2
 
@@ -441,25 +404,16 @@ RX_S_UNLOCKED, RX_S_KNOW_FSTART, RX_S_LOCKED = 0, 1, 2
 def bsync_lib():
     global _bsync
     if _bsync is None:
-        src = os.path.join(_HERE, "burst_sync_oracle.c")
-        if not os.path.exists(_BSYNC_LIB_PATH) or os.path.getmtime(src) > os.path.getmtime(_BSYNC_LIB_PATH):
-            subprocess.run(["make", "-C", _HERE, "-B", "libbsync_oracle.so"], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(_BSYNC_LIB_PATH)
-        vp = C.c_void_p
-        L.bs_oracle_find_train_seq.argtypes = [vp, C.c_uint, C.c_uint32, C.POINTER(C.c_uint)]
-        L.bs_oracle_find_train_seq.restype = C.c_int
-        L.bs_oracle_reset.argtypes = [vp]
-        L.bs_oracle_reset.restype = None
-        L.bs_oracle_feed.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
-        L.bs_oracle_feed.restype = C.c_int
-        L.bs_oracle_demux.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
-        L.bs_oracle_demux.restype = C.c_int
-        L.bs_oracle_state_size.restype = C.c_int
-        L.ts_indicator_init.argtypes = [vp]
-        L.ts_indicator_init.restype = None
-        L.ts_indicator_feed.argtypes = [vp, vp, C.c_int]
-        L.ts_indicator_feed.restype = None
-        _bsync = L
+        vp, i32 = C.c_void_p, C.c_int
+        _bsync = hostlib.load(_make("libbsync_oracle.so", ["burst_sync_oracle.c"]), {
+            "bs_oracle_find_train_seq": (i32, [vp, C.c_uint, C.c_uint32, C.POINTER(C.c_uint)]),
+            "bs_oracle_reset": (None, [vp]),
+            "bs_oracle_feed": (i32, [vp, vp, i32, i32, vp, vp, vp, i32]),
+            "bs_oracle_demux": (i32, [vp, i32, i32, i32, vp]),
+            "bs_oracle_state_size": (i32, []),
+            "ts_indicator_init": (None, [vp]),
+            "ts_indicator_feed": (None, [vp, vp, i32]),
+        })
     return _bsync
 
 

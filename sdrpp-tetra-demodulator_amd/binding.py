@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from . import build as _build
+from ._ffi import P, TetraDemodError, call, check, declare, f64, i32, ptr, size_t, stream_ptr, vp  # noqa: F401
 
 LAYOUT_CHANNEL_MAJOR = 0
 LAYOUT_TIME_MAJOR = 1
@@ -27,17 +28,6 @@ FLAG_GENERIC_KERNEL = 128        # filters of 73 .. 129 taps / loops below 0.27 
 PARAMS = dict(symbolrate=0, samplerate=1, rrc_tap_count=2, rrc_beta=3, agc_rate=4, costas_bandwidth=5,
               fll_bandwidth=6, omega_gain=7, mu_gain=8, omega_rel_limit=9)
 
-EXPORTS = [
-    "tetra_demod_default_config", "tetra_demod_device_count", "tetra_demod_create", "tetra_demod_destroy",
-    "tetra_demod_bits_stride", "tetra_demod_process_device", "tetra_demod_process", "tetra_demod_reset",
-    "tetra_demod_set_param", "tetra_demod_get_state", "tetra_demod_set_state", "tetra_demod_get_tables",
-    "tetra_demod_debug_read_rrc_out", "tetra_demod_last_kernel_ms", "tetra_demod_strerror",
-    "tetra_demod_last_hip_error", "tetra_demod_abi_version", "tetra_demod_debug_selftest", "tetra_demod_kernel_ms_history", "tetra_demod_get_quality",
-    "tetra_demod_bandedge_tap_count", "tetra_demod_process_async", "tetra_demod_wait", "tetra_demod_host_alloc",
-    "tetra_demod_host_free", "tetra_demod_device_info", "tetra_demod_bits_stride_for", "tetra_demod_get_overruns",
-    "tetra_demod_set_rrc_params", "tetra_demod_process_resident", "tetra_demod_debug_mfma_selftest", "tetra_demod_build_id",
-    "tetra_demod_set_tables", "tetra_demod_get_constellation",
-]
 ERR_OVERRUN = -8
 IQ_CF32, IQ_CS16, IQ_CS8 = 0, 1, 2
 
@@ -64,15 +54,44 @@ class ChannelState(C.Structure):
     ]
 
 
-class TetraDemodError(RuntimeError):
-    def __init__(self, status, what, hip=0):
-        self.status = status
-        self.hip = hip
-        msg = "%s failed: %d (%s)" % (what, status, _strerror(status))
-        if hip:
-            msg += " [hipError %d]" % hip
-        super().__init__(msg)
-
+# include/tetra_demod.h
+SIGNATURES = {
+    "tetra_demod_default_config": (i32, [P(Config)]),
+    "tetra_demod_device_count": (i32, []),
+    "tetra_demod_create": (i32, [P(Config), P(vp)]),
+    "tetra_demod_destroy": (i32, [vp]),
+    "tetra_demod_bits_stride_for": (i32, [vp, i32]),
+    "tetra_demod_bits_stride": (i32, [i32]),
+    "tetra_demod_process_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp]),
+    "tetra_demod_process": (i32, [vp, vp, i32, vp, i32, vp, vp]),
+    "tetra_demod_process_resident": (i32, [vp, vp, i32, vp, i32, vp, vp]),
+    "tetra_demod_get_overruns": (i32, [vp, P(C.c_longlong)]),
+    "tetra_demod_process_async": (i32, [vp, vp, i32, i32, vp, i32, vp]),
+    "tetra_demod_wait": (i32, [vp]),
+    "tetra_demod_host_alloc": (vp, [size_t]),
+    "tetra_demod_host_free": (None, [vp]),
+    "tetra_demod_reset": (i32, [vp, i32]),
+    "tetra_demod_set_param": (i32, [vp, i32, f64]),
+    "tetra_demod_set_rrc_params": (i32, [vp, i32, f64]),
+    "tetra_demod_set_tables": (i32, [vp, vp, i32, vp, i32, vp]),
+    "tetra_demod_get_state": (i32, [vp, i32, P(ChannelState)]),
+    "tetra_demod_set_state": (i32, [vp, i32, P(ChannelState)]),
+    "tetra_demod_get_tables": (i32, [vp, P(i32), vp, P(i32), vp, vp, vp]),
+    "tetra_demod_bandedge_tap_count": (i32, [vp]),
+    "tetra_demod_get_quality": (i32, [vp, vp, vp]),
+    "tetra_demod_get_constellation": (i32, [vp, i32, i32, vp, vp]),
+    "tetra_demod_debug_read_rrc_out": (i32, [vp, vp, i32]),
+    "tetra_demod_last_kernel_ms": (i32, [vp, P(C.c_float)]),
+    "tetra_demod_kernel_ms_history": (i32, [vp, i32, vp]),
+    "tetra_demod_debug_selftest": (i32, [vp, vp, vp]),
+    "tetra_demod_debug_mfma_selftest": (i32, [vp, i32, i32, vp, vp, vp]),
+    "tetra_demod_strerror": (C.c_char_p, [i32]),
+    "tetra_demod_last_hip_error": (i32, [vp]),
+    "tetra_demod_abi_version": (i32, []),
+    "tetra_demod_build_id": (C.c_char_p, []),
+    "tetra_demod_device_info": (i32, [i32, P(i32), P(i32)]),
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -96,75 +115,21 @@ def load_library(rebuild_if_stale=True):
         # never run (or measure) a library built from other sources than the tree holds
         raise RuntimeError("HIP library %s was built from other sources than this tree holds (build id %s, sources %s); run "
                            "__graft_entry__.build()" % (path, _build.lib_build_id(path), _build.source_hash()))
-    L = C.CDLL(path)
-    vp, i32 = C.c_void_p, C.c_int
-    if hasattr(L, "tetra_demod_build_id"):          # (an override may be an older experimental build without it)
-        L.tetra_demod_build_id.argtypes = []
-        L.tetra_demod_build_id.restype = C.c_char_p
-    L.tetra_demod_default_config.argtypes = [C.POINTER(Config)]
-    L.tetra_demod_device_count.argtypes = []
-    L.tetra_demod_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.tetra_demod_destroy.argtypes = [vp]
-    L.tetra_demod_bits_stride.argtypes = [i32]
-    L.tetra_demod_process_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
-    L.tetra_demod_process.argtypes = [vp, vp, i32, vp, i32, vp, vp]
-    L.tetra_demod_reset.argtypes = [vp, i32]
-    L.tetra_demod_set_param.argtypes = [vp, i32, C.c_double]
-    L.tetra_demod_get_state.argtypes = [vp, i32, C.POINTER(ChannelState)]
-    L.tetra_demod_set_state.argtypes = [vp, i32, C.POINTER(ChannelState)]
-    L.tetra_demod_get_tables.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(i32), vp, vp, vp]
-    L.tetra_demod_bits_stride_for.argtypes = [vp, i32]
-    L.tetra_demod_get_overruns.argtypes = [vp, C.POINTER(C.c_longlong)]
-    L.tetra_demod_set_rrc_params.argtypes = [vp, i32, C.c_double]
-    L.tetra_demod_process_resident.argtypes = [vp, vp, i32, vp, i32, vp, vp]
-    L.tetra_demod_set_tables.argtypes = [vp, vp, i32, vp, i32, vp]
-    L.tetra_demod_debug_mfma_selftest.argtypes = [vp, i32, i32, vp, vp, vp]
-    L.tetra_demod_bandedge_tap_count.argtypes = [vp]
-    L.tetra_demod_debug_read_rrc_out.argtypes = [vp, vp, i32]
-    L.tetra_demod_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    L.tetra_demod_strerror.argtypes = [i32]
-    L.tetra_demod_strerror.restype = C.c_char_p
-    L.tetra_demod_last_hip_error.argtypes = [vp]
-    L.tetra_demod_abi_version.argtypes = []
-    L.tetra_demod_debug_selftest.argtypes = [vp, vp, vp]
-    L.tetra_demod_kernel_ms_history.argtypes = [vp, i32, vp]
-    L.tetra_demod_get_quality.argtypes = [vp, vp, vp]
-    L.tetra_demod_get_constellation.argtypes = [vp, i32, i32, vp, vp]
-    L.tetra_demod_process_async.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    L.tetra_demod_wait.argtypes = [vp]
-    L.tetra_demod_device_info.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
-    L.tetra_demod_host_alloc.argtypes = [C.c_size_t]
-    L.tetra_demod_host_free.argtypes = [vp]
-    for name in EXPORTS:
-        if name not in ("tetra_demod_strerror", "tetra_demod_host_alloc", "tetra_demod_host_free", "tetra_demod_build_id"):
-            getattr(L, name).restype = i32
-    L.tetra_demod_host_alloc.restype = vp
-    L.tetra_demod_host_free.restype = None
-    _lib = L
-    return L
-
-
-def _strerror(status):
-    try:
-        return load_library(False).tetra_demod_strerror(status).decode()
-    except Exception:  # pragma: no cover
-        return "?"
+    # (an override may be an older experimental build without the build id)
+    _lib = declare(C.CDLL(path), SIGNATURES, optional=("tetra_demod_build_id",))
+    return _lib
 
 
 def device_info(device=0):
     """(shader clock in kHz, compute units) of a device."""
     clk, cus = C.c_int32(0), C.c_int32(0)
-    rc = load_library().tetra_demod_device_info(int(device), C.byref(clk), C.byref(cus))
-    if rc != 0:
-        raise TetraDemodError(rc, "tetra_demod_device_info")
+    call(load_library().tetra_demod_device_info, int(device), C.byref(clk), C.byref(cus))
     return int(clk.value), int(cus.value)
 
 
 def default_config():
     cfg = Config()
-    rc = load_library().tetra_demod_default_config(C.byref(cfg))
-    if rc:
-        raise TetraDemodError(rc, "tetra_demod_default_config")
+    call(load_library().tetra_demod_default_config, C.byref(cfg))
     return cfg
 
 
@@ -176,10 +141,6 @@ def bits_stride(n_samples):
     """Handle-free row length: covers every handle at ~2 samples per symbol (tetra_demod_bits_stride); Demodulator.bits_stride
     is the one for a particular handle's rates."""
     return int(load_library().tetra_demod_bits_stride(int(n_samples)))
-
-
-def _np_ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class Demodulator:
@@ -209,26 +170,30 @@ class Demodulator:
         self.max_samples = max_samples
         self.layout = layout
         h = C.c_void_p()
-        rc = self._lib.tetra_demod_create(C.byref(cfg), C.byref(h))
-        if rc:
-            raise TetraDemodError(rc, "tetra_demod_create")
+        call(self._lib.tetra_demod_create, C.byref(cfg), C.byref(h))
         self._h = h
 
-    def _check(self, rc, what):
+    def _check(self, rc, fn):
         if rc:
-            raise TetraDemodError(rc, what, self._lib.tetra_demod_last_hip_error(self._h))
+            check(rc, fn, self._lib.tetra_demod_last_hip_error(self._h))
+
+    def _call(self, fn, *args):
+        """fn(handle, *args); a non-zero status raises with the handle's last HIP error."""
+        rc = fn(self._h, *args)
+        if rc:
+            check(rc, fn, self._lib.tetra_demod_last_hip_error(self._h))
 
     def bits_stride(self, n_samples):
         """tetra_demod_bits_stride_for: the row length this handle's timing loop needs for calls of n_samples."""
         rc = int(self._lib.tetra_demod_bits_stride_for(self._h, int(n_samples)))
         if rc < 0:
-            raise TetraDemodError(rc, "tetra_demod_bits_stride_for")
+            check(rc, self._lib.tetra_demod_bits_stride_for)
         return rc
 
     def overruns(self):
         """(channel, launch) events cut off at the row capacity since create (tetra_demod_get_overruns)."""
         v = C.c_longlong(0)
-        self._check(self._lib.tetra_demod_get_overruns(self._h, C.byref(v)), "tetra_demod_get_overruns")
+        self._call(self._lib.tetra_demod_get_overruns, C.byref(v))
         return int(v.value)
 
     def close(self):
@@ -258,54 +223,40 @@ class Demodulator:
         bits = np.zeros((self.n_channels, stride), np.uint8)
         nb = np.zeros(self.n_channels, np.int32)
         sym = np.zeros((self.n_channels, stride // 2), np.complex64) if want_sym else None
-        rc = self._lib.tetra_demod_process(self._h, _np_ptr(iq), n, _np_ptr(bits), stride, _np_ptr(nb), _np_ptr(sym))
+        rc = self._lib.tetra_demod_process(self._h, ptr(iq), n, ptr(bits), stride, ptr(nb), ptr(sym))
         self.last_status = rc
         if not (allow_overrun and rc == ERR_OVERRUN):
-            self._check(rc, "tetra_demod_process")
+            self._check(rc, self._lib.tetra_demod_process)
         return bits, nb, sym
 
     def process_async(self, iq_ptr, iq_format, n_samples, bits_ptr, bits_stride_, n_bits_ptr):
         """tetra_demod_process_async on raw host addresses (page-locked buffers, e.g. torch pinned tensors' data_ptr() or
         host_alloc()); the buffers must stay alive and untouched until wait()."""
-        rc = self._lib.tetra_demod_process_async(self._h, C.c_void_p(int(iq_ptr)), int(iq_format), int(n_samples),
-                                                 C.c_void_p(int(bits_ptr)), int(bits_stride_), C.c_void_p(int(n_bits_ptr)))
-        self._check(rc, "tetra_demod_process_async")
+        self._call(self._lib.tetra_demod_process_async, int(iq_ptr), int(iq_format), int(n_samples), int(bits_ptr), int(bits_stride_),
+                   int(n_bits_ptr))
 
     def wait(self):
-        self._check(self._lib.tetra_demod_wait(self._h), "tetra_demod_wait")
+        self._call(self._lib.tetra_demod_wait)
 
     def process_resident(self, d_iq, n_samples, d_bits, bits_stride_, d_n_bits, d_sym=None):
         """tetra_demod_process_resident: device buffers, the handle's own stream, returns when the launch is done."""
-        def p(x):
-            if x is None:
-                return None
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self._lib.tetra_demod_process_resident(self._h, p(d_iq), int(n_samples), p(d_bits), int(bits_stride_),
-                                                           p(d_n_bits), p(d_sym)), "tetra_demod_process_resident")
+        self._call(self._lib.tetra_demod_process_resident, ptr(d_iq), int(n_samples), ptr(d_bits), int(bits_stride_), ptr(d_n_bits), ptr(d_sym))
 
     def process_device(self, d_iq, n_samples, d_bits, bits_stride_, d_n_bits, d_sym=None, stream=None):
         """Device path: arguments are objects with .data_ptr() (torch tensors on this GPU) or ints."""
-        def p(x):
-            if x is None:
-                return None
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        s = None
-        if stream is not None:
-            s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-        rc = self._lib.tetra_demod_process_device(self._h, p(d_iq), int(n_samples), p(d_bits), int(bits_stride_),
-                                                  p(d_n_bits), p(d_sym), s)
-        self._check(rc, "tetra_demod_process_device")
+        self._call(self._lib.tetra_demod_process_device, ptr(d_iq), int(n_samples), ptr(d_bits), int(bits_stride_), ptr(d_n_bits), ptr(d_sym),
+                   stream_ptr(stream))
 
     # --- PI4DQPSK::reset and the setters -----------------------------------------------------------
     def reset(self, channel=-1):
-        self._check(self._lib.tetra_demod_reset(self._h, channel), "tetra_demod_reset")
+        self._call(self._lib.tetra_demod_reset, channel)
 
     def set_param(self, name, value):
-        self._check(self._lib.tetra_demod_set_param(self._h, PARAMS[name], float(value)), "tetra_demod_set_param")
+        self._call(self._lib.tetra_demod_set_param, PARAMS[name], float(value))
 
     def set_rrc_params(self, rrc_tap_count, rrc_beta):
         """PI4DQPSK::setRRCParams: both in one re-design."""
-        self._check(self._lib.tetra_demod_set_rrc_params(self._h, int(rrc_tap_count), float(rrc_beta)), "tetra_demod_set_rrc_params")
+        self._call(self._lib.tetra_demod_set_rrc_params, int(rrc_tap_count), float(rrc_beta))
 
     def set_tables(self, rrc_taps=None, bandedge_taps=None, interp_bank=None):
         """tetra_demod_set_tables: FIR::setTaps with caller-designed tables (rrc [n]; band-edge [2][n_be] = re, im of the lower
@@ -313,16 +264,15 @@ class Demodulator:
         r = None if rrc_taps is None else np.ascontiguousarray(rrc_taps, np.float32)
         b = None if bandedge_taps is None else np.ascontiguousarray(bandedge_taps, np.float32).reshape(2, -1)
         k = None if interp_bank is None else np.ascontiguousarray(interp_bank, np.float32).reshape(128, 8)
-        self._check(self._lib.tetra_demod_set_tables(self._h, _np_ptr(r), 0 if r is None else r.size, _np_ptr(b),
-                                                     0 if b is None else b.shape[1], _np_ptr(k)), "tetra_demod_set_tables")
+        self._call(self._lib.tetra_demod_set_tables, ptr(r), 0 if r is None else r.size, ptr(b), 0 if b is None else b.shape[1], ptr(k))
 
     def get_state(self, channel):
         st = ChannelState()
-        self._check(self._lib.tetra_demod_get_state(self._h, channel, C.byref(st)), "tetra_demod_get_state")
+        self._call(self._lib.tetra_demod_get_state, channel, C.byref(st))
         return st
 
     def set_state(self, channel, st):
-        self._check(self._lib.tetra_demod_set_state(self._h, channel, C.byref(st)), "tetra_demod_set_state")
+        self._call(self._lib.tetra_demod_set_state, channel, C.byref(st))
 
     def tables(self):
         nt, nbe = C.c_int(0), C.c_int(0)
@@ -330,22 +280,20 @@ class Demodulator:
         re = np.zeros(129, np.float32)
         im = np.zeros(129, np.float32)
         bank = np.zeros((128, 8), np.float32)
-        self._check(self._lib.tetra_demod_get_tables(self._h, C.byref(nt), _np_ptr(rrc), C.byref(nbe), _np_ptr(re), _np_ptr(im),
-                                                     _np_ptr(bank)), "tetra_demod_get_tables")
+        self._call(self._lib.tetra_demod_get_tables, C.byref(nt), ptr(rrc), C.byref(nbe), ptr(re), ptr(im), ptr(bank))
         assert nbe.value == self._lib.tetra_demod_bandedge_tap_count(self._h)
         return dict(rrc=rrc[:nt.value].copy(), be_re=re[:nbe.value].copy(), be_im=im[:nbe.value].copy(), bank=bank)
 
     def read_rrc_out(self, n_samples):
         y = np.zeros((self.n_channels, n_samples), np.complex64)
-        self._check(self._lib.tetra_demod_debug_read_rrc_out(self._h, _np_ptr(y), n_samples),
-                    "tetra_demod_debug_read_rrc_out")
+        self._call(self._lib.tetra_demod_debug_read_rrc_out, ptr(y), n_samples)
         return y
 
     def selftest(self, in128):
         a = np.ascontiguousarray(in128, np.float32)
         assert a.shape == (128,)
         out = np.zeros(320, np.float32)
-        self._check(self._lib.tetra_demod_debug_selftest(self._h, _np_ptr(a), _np_ptr(out)), "tetra_demod_debug_selftest")
+        self._call(self._lib.tetra_demod_debug_selftest, ptr(a), ptr(out))
         return out.reshape(5, 64)
 
     def mfma_selftest(self, a, b):
@@ -355,15 +303,14 @@ class Demodulator:
         m, k = a.shape
         assert b.shape == (k, m)
         d = np.zeros((m, m), np.float32)
-        self._check(self._lib.tetra_demod_debug_mfma_selftest(self._h, m, k, _np_ptr(a), _np_ptr(b), _np_ptr(d)),
-                    "tetra_demod_debug_mfma_selftest")
+        self._call(self._lib.tetra_demod_debug_mfma_selftest, m, k, ptr(a), ptr(b), ptr(d))
         return d
 
     def quality(self):
         """(standarderr float32[C], sync bool[C]) -- DQPSKSymbolExtractor's public members per channel."""
         err = np.zeros(self.n_channels, np.float32)
         sync = np.zeros(self.n_channels, np.uint8)
-        self._check(self._lib.tetra_demod_get_quality(self._h, _np_ptr(err), _np_ptr(sync)), "tetra_demod_get_quality")
+        self._call(self._lib.tetra_demod_get_quality, ptr(err), ptr(sync))
         return err, sync.astype(bool)
 
     def constellation(self, first=0, count=None):
@@ -372,17 +319,16 @@ class Demodulator:
         count = self.n_channels - first if count is None else count
         blk = np.zeros((max(count, 0), CONSTELLATION_SYMBOLS), np.complex64)
         nb = np.zeros(max(count, 0), np.int32)
-        self._check(self._lib.tetra_demod_get_constellation(self._h, first, count, _np_ptr(blk), _np_ptr(nb)),
-                    "tetra_demod_get_constellation")
+        self._call(self._lib.tetra_demod_get_constellation, first, count, ptr(blk), ptr(nb))
         return blk, nb
 
     def kernel_ms_history(self, n):
         """GPU ms of the n most recent process calls' launches, oldest first (HIP events on each call's stream)."""
         ms = np.zeros(n, np.float32)
-        self._check(self._lib.tetra_demod_kernel_ms_history(self._h, n, _np_ptr(ms)), "tetra_demod_kernel_ms_history")
+        self._call(self._lib.tetra_demod_kernel_ms_history, n, ptr(ms))
         return ms
 
     def last_kernel_ms(self):
         a = C.c_float(0)
-        self._check(self._lib.tetra_demod_last_kernel_ms(self._h, C.byref(a)), "tetra_demod_last_kernel_ms")
+        self._call(self._lib.tetra_demod_last_kernel_ms, C.byref(a))
         return a.value

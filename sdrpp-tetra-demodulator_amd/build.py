@@ -7,10 +7,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtetra_demod_hip.so")
 SOURCES = ["tetra_demod.hip", "tetra_chan.hip", "tetra_resamp.hip", "tetra_burst_scan.hip", "tetra_lmac.hip", "tetra_burst_sync.hip", "tetra_rx.hip", "tetra_rx_out.hip", "tetra_wbrx.hip", "tetra_retune.hip"]
-DEPS = ["tetra_retune.hip", os.path.join("..", "..", "include", "tetra_retune.h"), "retune_core.hpp", "retune_impl.hpp", "retune_list.hpp", "wbrx_handle.hpp",
-        "tetra_wbrx.hip", os.path.join("..", "..", "include", "tetra_wbrx.h"), os.path.join("..", "..", "include", "tetra_shift.h"), "resamp_handle.hpp", "tetra_rx.hip", os.path.join("..", "..", "include", "tetra_rx.h"), "rx_handle.hpp", "tetra_rx_out.hip", "rx_out_core.hpp",
-        os.path.join("..", "..", "include", "tetra_rx_out.h"), "tetra_burst_sync.hip", "bsync_core.hpp", "demux_core.hpp", os.path.join("..", "..", "include", "tetra_burst_sync.h"), "tetra_demod.hip", "tetra_chan.hip", "chan_fft_core.hpp", "tetra_resamp.hip", "resamp_core.hpp", "tetra_burst_scan.hip", "tetra_lmac.hip", "lmac_core.hpp", os.path.join("..", "..", "include", "tetra_lmac.h"), os.path.join("..", "..", "include", "tetra_aach.h"), os.path.join("..", "..", "include", "tetra_burst_scan.h"), "demod_core.hpp", "constellation_core.hpp", "design.hpp", "launch_plan.hpp", "kernel_fused.hpp", "kernel_generic.hpp", "fll_asm.inc", "fll4_asm.inc", "fll16_asm.inc", "fll16l_asm.inc", "fll8l_asm.inc", "gen_fll_asm.py", "hip_host.hpp",
-        os.path.join("..", "..", "include", "tetra_demod.h"), os.path.join("..", "..", "include", "tetra_chan.h")]
+# Every regular file in csrc/ and every public header, as paths relative to csrc/, sorted: what the build id is taken over.  Read from
+# the tree, so that a new header cannot be forgotten and leave a stale library looking current.
+DEPS = sorted([f for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))] +
+              [os.path.join("..", "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include")) if f.endswith(".h")])
 
 # -ffp-contract=off + correctly rounded sqrt: the arithmetic contract shared with the oracle.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",

@@ -1,18 +1,11 @@
 """ctypes binding of the channeliser front-end C ABI (include/tetra_chan.h)."""
 import ctypes as C
+import functools
 
 import numpy as np
 
-from .binding import TetraDemodError, load_library
-
-CHAN_EXPORTS = ["tetra_chan_default_config", "tetra_chan_create", "tetra_chan_destroy", "tetra_chan_frames_for",
-                "tetra_chan_process_device", "tetra_chan_process", "tetra_chan_reset", "tetra_chan_get_prototype",
-                "tetra_chan_last_kernel_ms", "tetra_chan_process_device_cs16", "tetra_chan_process_device_cs8"]
-# include/tetra_shift.h (the frequency-shifted bank): the channeliser's share
-CHAN_SHIFT_EXPORTS = ["tetra_chan_set_shift", "tetra_chan_get_shift", "tetra_chan_shift_from_hz"]
-RESAMP_EXPORTS = ["tetra_resamp_default_config", "tetra_resamp_create", "tetra_resamp_destroy", "tetra_resamp_frames_for",
-                  "tetra_resamp_process_device", "tetra_resamp_process", "tetra_resamp_reset", "tetra_resamp_get_prototype",
-                  "tetra_resamp_last_kernel_ms"]
+from ._ffi import P, call, declare, f64, i32, ptr, stream_ptr, u32, vp
+from .binding import load_library
 
 
 class ChanConfig(C.Structure):
@@ -27,45 +20,44 @@ class ResampConfig(C.Structure):
                 ("cutoff_rel", C.c_double), ("kaiser_beta", C.c_double), ("prototype", C.c_void_p)]
 
 
-_ready = False
+# include/tetra_chan.h
+SIGNATURES = {
+    "tetra_chan_default_config": (i32, [P(ChanConfig)]),
+    "tetra_chan_create": (i32, [P(ChanConfig), P(vp)]),
+    "tetra_chan_destroy": (i32, [vp]),
+    "tetra_chan_frames_for": (i32, [vp, i32]),
+    "tetra_chan_process_device": (i32, [vp, vp, i32, vp, P(i32), vp]),
+    "tetra_chan_process_device_cs16": (i32, [vp, vp, i32, vp, P(i32), vp]),
+    "tetra_chan_process_device_cs8": (i32, [vp, vp, i32, vp, P(i32), vp]),
+    "tetra_chan_process": (i32, [vp, vp, i32, vp, P(i32)]),
+    "tetra_chan_reset": (i32, [vp]),
+    "tetra_chan_get_prototype": (i32, [vp, vp]),
+    "tetra_chan_last_kernel_ms": (i32, [vp, P(C.c_float)]),
+    "tetra_resamp_default_config": (i32, [P(ResampConfig)]),
+    "tetra_resamp_create": (i32, [P(ResampConfig), P(vp)]),
+    "tetra_resamp_destroy": (i32, [vp]),
+    "tetra_resamp_frames_for": (i32, [vp, i32]),
+    "tetra_resamp_process_device": (i32, [vp, vp, i32, vp, P(i32), vp]),
+    "tetra_resamp_process": (i32, [vp, vp, i32, vp, P(i32)]),
+    "tetra_resamp_reset": (i32, [vp]),
+    "tetra_resamp_get_prototype": (i32, [vp, vp]),
+    "tetra_resamp_last_kernel_ms": (i32, [vp, P(C.c_float)]),
+}
+# include/tetra_shift.h (the frequency-shifted bank): the channeliser's share
+SHIFT_SIGNATURES = {
+    "tetra_chan_set_shift": (i32, [vp, u32]),
+    "tetra_chan_get_shift": (i32, [vp, P(u32)]),
+    "tetra_chan_shift_from_hz": (u32, [f64, f64]),
+}
+CHAN_EXPORTS = [n for n in SIGNATURES if n.startswith("tetra_chan_")]
+RESAMP_EXPORTS = [n for n in SIGNATURES if n.startswith("tetra_resamp_")]
+CHAN_SHIFT_EXPORTS = list(SHIFT_SIGNATURES)
 
 
+@functools.lru_cache(None)
 def _lib():
-    global _ready
-    L = load_library()
-    if not _ready:
-        vp, i32 = C.c_void_p, C.c_int
-        L.tetra_chan_default_config.argtypes = [C.POINTER(ChanConfig)]
-        L.tetra_chan_create.argtypes = [C.POINTER(ChanConfig), C.POINTER(vp)]
-        L.tetra_chan_destroy.argtypes = [vp]
-        L.tetra_chan_frames_for.argtypes = [vp, i32]
-        L.tetra_chan_process_device.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp]
-        L.tetra_chan_process.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
-        L.tetra_chan_process_device_cs16.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp]
-        L.tetra_chan_process_device_cs8.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp]
-        L.tetra_chan_reset.argtypes = [vp]
-        L.tetra_chan_get_prototype.argtypes = [vp, vp]
-        L.tetra_chan_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.tetra_resamp_default_config.argtypes = [C.POINTER(ResampConfig)]
-        L.tetra_resamp_create.argtypes = [C.POINTER(ResampConfig), C.POINTER(vp)]
-        L.tetra_resamp_destroy.argtypes = [vp]
-        L.tetra_resamp_frames_for.argtypes = [vp, i32]
-        L.tetra_resamp_process_device.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp]
-        L.tetra_resamp_process.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
-        L.tetra_resamp_reset.argtypes = [vp]
-        L.tetra_resamp_get_prototype.argtypes = [vp, vp]
-        L.tetra_resamp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        for n in CHAN_EXPORTS + RESAMP_EXPORTS:
-            getattr(L, n).restype = i32
-        if hasattr(L, "tetra_chan_set_shift"):       # (a TETRA_DEMOD_LIB override may be an older build without the shift)
-            L.tetra_chan_set_shift.argtypes = [vp, C.c_uint32]
-            L.tetra_chan_set_shift.restype = i32
-            L.tetra_chan_get_shift.argtypes = [vp, C.POINTER(C.c_uint32)]
-            L.tetra_chan_get_shift.restype = i32
-            L.tetra_chan_shift_from_hz.argtypes = [C.c_double, C.c_double]
-            L.tetra_chan_shift_from_hz.restype = C.c_uint32
-        _ready = True
-    return L
+    # (a TETRA_DEMOD_LIB override may be an older build without the shift)
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES}, optional=CHAN_SHIFT_EXPORTS)
 
 
 def shift_from_hz(shift_hz, sample_rate_hz):
@@ -98,24 +90,18 @@ class Channeliser:
             cfg.prototype = keep.ctypes.data
         self.M, self.P, self.D = n_channels, taps_per_channel, cfg.decimation
         h = C.c_void_p()
-        rc = self._lib.tetra_chan_create(C.byref(cfg), C.byref(h))
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_create")
+        call(self._lib.tetra_chan_create, C.byref(cfg), C.byref(h))
         self._h = h
         if shift:
             self.set_shift(shift)
 
     def set_shift(self, inc):
         """tetra_chan_set_shift: between process calls; takes effect from the next call's first frame, keeps the phase reference."""
-        rc = self._lib.tetra_chan_set_shift(self._h, int(inc) & 0xffffffff)
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_set_shift")
+        call(self._lib.tetra_chan_set_shift, self._h, int(inc) & 0xffffffff)
 
     def get_shift(self):
         v = C.c_uint32(0)
-        rc = self._lib.tetra_chan_get_shift(self._h, C.byref(v))
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_get_shift")
+        call(self._lib.tetra_chan_get_shift, self._h, C.byref(v))
         return int(v.value)
 
     def close(self):
@@ -137,42 +123,28 @@ class Channeliser:
         nf = self.frames_for(x.shape[0])
         out = np.zeros((max(nf, 1), self.M), np.complex64)
         got = C.c_int(0)
-        rc = self._lib.tetra_chan_process(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0],
-                                          out.ctypes.data_as(C.c_void_p), C.byref(got))
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_process")
+        call(self._lib.tetra_chan_process, self._h, ptr(x), x.shape[0], ptr(out), C.byref(got))
         return out[: got.value]
 
     def process_device(self, d_x, n_in, d_out, stream=None):
-        def p(t):
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        s = None
-        if stream is not None:
-            s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
         got = C.c_int(0)
         # the input format follows the tensor: complex64, or interleaved I / Q pairs [n][2] int16 / int8 (tetra_chan_process_device_cs16 / _cs8)
         name = {"torch.int16": "tetra_chan_process_device_cs16", "torch.int8": "tetra_chan_process_device_cs8"}.get(str(getattr(d_x, "dtype", "")),
                                                                                                                   "tetra_chan_process_device")
-        rc = getattr(self._lib, name)(self._h, p(d_x), int(n_in), p(d_out), C.byref(got), s)
-        if rc:
-            raise TetraDemodError(rc, name)
+        call(getattr(self._lib, name), self._h, ptr(d_x), int(n_in), ptr(d_out), C.byref(got), stream_ptr(stream))
         return got.value
 
     def reset(self):
-        rc = self._lib.tetra_chan_reset(self._h)
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_reset")
+        call(self._lib.tetra_chan_reset, self._h)
 
     def prototype(self):
         h = np.zeros(self.M * self.P, np.float32)
-        self._lib.tetra_chan_get_prototype(self._h, h.ctypes.data_as(C.c_void_p))
+        self._lib.tetra_chan_get_prototype(self._h, ptr(h))
         return h
 
     def last_kernel_ms(self):
         v = C.c_float(0)
-        rc = self._lib.tetra_chan_last_kernel_ms(self._h, C.byref(v))
-        if rc:
-            raise TetraDemodError(rc, "tetra_chan_last_kernel_ms")
+        call(self._lib.tetra_chan_last_kernel_ms, self._h, C.byref(v))
         return v.value
 
 
@@ -198,9 +170,7 @@ class Resampler:
             cfg.prototype = keep.ctypes.data
         self.C, self.I, self.DN, self.T = n_channels, interp, decim, taps_per_phase
         h = C.c_void_p()
-        rc = self._lib.tetra_resamp_create(C.byref(cfg), C.byref(h))
-        if rc:
-            raise TetraDemodError(rc, "tetra_resamp_create")
+        call(self._lib.tetra_resamp_create, C.byref(cfg), C.byref(h))
         self._h = h
 
     def close(self):
@@ -222,36 +192,23 @@ class Resampler:
         nf = self.frames_for(x.shape[0])
         out = np.zeros((max(nf, 1), self.C), np.complex64)
         got = C.c_int(0)
-        rc = self._lib.tetra_resamp_process(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], out.ctypes.data_as(C.c_void_p), C.byref(got))
-        if rc:
-            raise TetraDemodError(rc, "tetra_resamp_process")
+        call(self._lib.tetra_resamp_process, self._h, ptr(x), x.shape[0], ptr(out), C.byref(got))
         return out[: got.value]
 
     def process_device(self, d_in, n_in, d_out, stream=None):
-        def p(t):
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        s = None
-        if stream is not None:
-            s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
         got = C.c_int(0)
-        rc = self._lib.tetra_resamp_process_device(self._h, p(d_in), int(n_in), p(d_out), C.byref(got), s)
-        if rc:
-            raise TetraDemodError(rc, "tetra_resamp_process_device")
+        call(self._lib.tetra_resamp_process_device, self._h, ptr(d_in), int(n_in), ptr(d_out), C.byref(got), stream_ptr(stream))
         return got.value
 
     def reset(self):
-        rc = self._lib.tetra_resamp_reset(self._h)
-        if rc:
-            raise TetraDemodError(rc, "tetra_resamp_reset")
+        call(self._lib.tetra_resamp_reset, self._h)
 
     def prototype(self):
         h = np.zeros(self.I * self.T, np.float32)
-        self._lib.tetra_resamp_get_prototype(self._h, h.ctypes.data_as(C.c_void_p))
+        self._lib.tetra_resamp_get_prototype(self._h, ptr(h))
         return h
 
     def last_kernel_ms(self):
         v = C.c_float(0)
-        rc = self._lib.tetra_resamp_last_kernel_ms(self._h, C.byref(v))
-        if rc:
-            raise TetraDemodError(rc, "tetra_resamp_last_kernel_ms")
+        call(self._lib.tetra_resamp_last_kernel_ms, self._h, C.byref(v))
         return v.value

@@ -1,16 +1,12 @@
 """ctypes binding of the batched lower-MAC channel decoding (include/tetra_lmac.h)."""
 import ctypes as C
+import functools
 
 import numpy as np
 
-from .binding import TetraDemodError, load_library
+from ._ffi import P, call, declare, i32, ptr, size_t, stream_ptr, u32, vp
+from .binding import load_library
 
-LMAC_EXPORTS = ["tetra_lmac_blk_param", "tetra_lmac_scramb_init", "tetra_lmac_decode_batch_device", "tetra_lmac_decode_batch",
-                "tetra_lmac_track_scramb_device", "tetra_lmac_decode_counted_device", "tetra_lmac_track_sync_device",
-                "tetra_lmac_debug_force_byte_route", "tetra_lmac_decode_frames_device", "tetra_lmac_track_sync_lists_device",
-                "tetra_lmac_decode_frames_workspace_bytes"]
-# include/tetra_aach.h: the lower MAC's share (the receive chain's is in rx_binding.RX_AACH_EXPORTS)
-AACH_EXPORTS = ["tetra_lmac_rm3014_decode_device", "tetra_lmac_decode_aach_rm3014_device"]
 JOB_RM3014 = 0x100            # TETRA_LMAC_JOB_RM3014: OR into a BBK job's type for decode_frames_device
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 # enum tp_sap_data_type (src/decoder/src/phy/tetra_burst.h:9-16)
@@ -41,43 +37,42 @@ class BlkParam(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("type345_bits", "type2_bits", "type1_bits", "interleave_a", "have_crc16")]
 
 
-_ready = False
+# include/tetra_lmac.h
+SIGNATURES = {
+    "tetra_lmac_blk_param": (i32, [i32, P(BlkParam)]),
+    "tetra_lmac_scramb_init": (u32, [C.c_uint16, C.c_uint16, C.c_uint8]),
+    "tetra_lmac_decode_batch_device": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, vp]),
+    "tetra_lmac_decode_counted_device": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
+    "tetra_lmac_debug_force_byte_route": (i32, [i32]),
+    "tetra_lmac_decode_frames_device": (i32, [P(Frames), P(Job), i32, vp]),
+    "tetra_lmac_decode_frames_workspace_bytes": (size_t, [P(Job), i32]),
+    "tetra_lmac_decode_batch": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32]),
+    "tetra_lmac_track_scramb_device": (i32, [vp, i32, vp, vp, i32, i32, vp, vp, vp]),
+    "tetra_lmac_track_sync_device": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "tetra_lmac_track_sync_lists_device": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+}
+# include/tetra_aach.h: the lower MAC's share (the receive chain's is in rx_binding.AACH_SIGNATURES)
+AACH_SIGNATURES = {
+    "tetra_lmac_rm3014_decode_device": (i32, [vp, i32, vp, vp, vp]),
+    "tetra_lmac_decode_aach_rm3014_device": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
+}
+LMAC_EXPORTS, AACH_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES)
 
 
+@functools.lru_cache(None)
 def _lib():
-    global _ready
-    L = load_library()
-    if not _ready:
-        vp, i32 = C.c_void_p, C.c_int
-        L.tetra_lmac_blk_param.argtypes = [i32, C.POINTER(BlkParam)]
-        L.tetra_lmac_blk_param.restype = i32
-        L.tetra_lmac_scramb_init.argtypes = [C.c_uint16, C.c_uint16, C.c_uint8]
-        L.tetra_lmac_scramb_init.restype = C.c_uint32
-        L.tetra_lmac_decode_batch_device.argtypes = [i32, vp, i32, i32, vp, vp, i32, vp, vp]
-        L.tetra_lmac_decode_batch_device.restype = i32
-        L.tetra_lmac_decode_counted_device.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]
-        L.tetra_lmac_decode_counted_device.restype = i32
-        L.tetra_lmac_decode_batch.argtypes = [i32, vp, i32, i32, vp, vp, i32, vp, i32]
-        L.tetra_lmac_decode_batch.restype = i32
-        L.tetra_lmac_track_scramb_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp]
-        L.tetra_lmac_track_scramb_device.restype = i32
-        _ready = True
-    return L
+    # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES}, optional=AACH_EXPORTS)
 
 
 def force_byte_route(on):
     """tetra_lmac_debug_force_byte_route: every row through the decoder's byte route (process-wide).  Returns the old setting."""
-    L = _lib()
-    L.tetra_lmac_debug_force_byte_route.argtypes = [C.c_int]
-    L.tetra_lmac_debug_force_byte_route.restype = C.c_int
-    return bool(L.tetra_lmac_debug_force_byte_route(int(bool(on))))
+    return bool(_lib().tetra_lmac_debug_force_byte_route(int(bool(on))))
 
 
 def blk_param(blk_type):
     p = BlkParam()
-    rc = _lib().tetra_lmac_blk_param(int(blk_type), C.byref(p))
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_blk_param")
+    call(_lib().tetra_lmac_blk_param, int(blk_type), C.byref(p))
     return p
 
 
@@ -98,152 +93,75 @@ def decode_batch(blk_type, type5, scramb=None, device=-1):
     out = np.zeros((n, ost), np.uint8)
     ok = np.zeros(n, np.int32)
     si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
-    rc = _lib().tetra_lmac_decode_batch(int(blk_type), rows.ctypes.data_as(C.c_void_p), n, in_stride,
-                                        None if si is None else si.ctypes.data_as(C.c_void_p),
-                                        out.ctypes.data_as(C.c_void_p), ost, ok.ctypes.data_as(C.c_void_p), device)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_decode_batch")
+    call(_lib().tetra_lmac_decode_batch, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), device)
     return out, ok
 
 
 def decode_batch_device(blk_type, d_type5, n_blocks, in_stride, d_scramb, d_type2, out_stride, d_crc_ok, stream=None):
     """torch tensors already on the GPU; enqueues on `stream` (torch stream or raw handle), no synchronisation."""
-    s = None
-    if stream is not None:
-        s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    rc = _lib().tetra_lmac_decode_batch_device(int(blk_type), C.c_void_p(d_type5.data_ptr()), int(n_blocks), int(in_stride),
-                                               None if d_scramb is None else C.c_void_p(d_scramb.data_ptr()),
-                                               C.c_void_p(d_type2.data_ptr()), int(out_stride), C.c_void_p(d_crc_ok.data_ptr()), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_decode_batch_device")
+    call(_lib().tetra_lmac_decode_batch_device, int(blk_type), ptr(d_type5), int(n_blocks), int(in_stride), ptr(d_scramb), ptr(d_type2),
+         int(out_stride), ptr(d_crc_ok), stream_ptr(stream))
 
 
 def decode_counted_device(blk_type, d_type5, capacity, d_n_blocks, in_stride, d_scramb, d_init_index, d_type2, out_stride, d_crc_ok,
                           stream=None):
     """Rows from the compacting demultiplexer: count and scrambling-code index are read on the device."""
-    s = None
-    if stream is not None:
-        s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    vp = C.c_void_p
-    rc = _lib().tetra_lmac_decode_counted_device(int(blk_type), vp(d_type5.data_ptr()), int(capacity),
-                                                 None if d_n_blocks is None else vp(d_n_blocks.data_ptr()), int(in_stride),
-                                                 None if d_scramb is None else vp(d_scramb.data_ptr()),
-                                                 None if d_init_index is None else vp(d_init_index.data_ptr()),
-                                                 vp(d_type2.data_ptr()), int(out_stride), vp(d_crc_ok.data_ptr()), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_decode_counted_device")
+    call(_lib().tetra_lmac_decode_counted_device, int(blk_type), ptr(d_type5), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
+         ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), stream_ptr(stream))
 
 
 def track_scramb_device(d_sb1_type2, type2_stride, d_crc_ok, d_valid, n_channels, frames_per_channel, d_chan_scramb, d_row_scramb,
                         stream=None):
-    s = None
-    if stream is not None:
-        s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    vp = C.c_void_p
-    rc = _lib().tetra_lmac_track_scramb_device(vp(d_sb1_type2.data_ptr()), int(type2_stride), vp(d_crc_ok.data_ptr()),
-                                               vp(d_valid.data_ptr()), int(n_channels), int(frames_per_channel),
-                                               vp(d_chan_scramb.data_ptr()), vp(d_row_scramb.data_ptr()), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_track_scramb_device")
+    call(_lib().tetra_lmac_track_scramb_device, ptr(d_sb1_type2), int(type2_stride), ptr(d_crc_ok), ptr(d_valid), int(n_channels),
+         int(frames_per_channel), ptr(d_chan_scramb), ptr(d_row_scramb), stream_ptr(stream))
 
 
 def track_sync_device(d_sb1_type2, type2_stride, d_crc_ok, d_valid, d_n_frames, n_channels, frames_per_channel, d_cell, d_row_scramb,
                       d_row_time_rx=None, d_row_time=None, stream=None):
     """tetra_lmac_track_sync_device: d_cell = torch int32 / uint32 tensor [n_channels][10] (tetra_lmac_cell_state_t: scramb_init,
     colour_code, mcc, mnc, tcd tn / fn / mn, phy tn / fn / mn)."""
-    s = None
-    if stream is not None:
-        s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    vp = C.c_void_p
-
-    def p(t):
-        return vp(t.data_ptr()) if t is not None else None
-    L = _lib()
-    L.tetra_lmac_track_sync_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    L.tetra_lmac_track_sync_device.restype = C.c_int
-    rc = L.tetra_lmac_track_sync_device(p(d_sb1_type2), int(type2_stride), p(d_crc_ok), p(d_valid), p(d_n_frames), int(n_channels),
-                                        int(frames_per_channel), p(d_cell), p(d_row_scramb), p(d_row_time_rx), p(d_row_time), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_track_sync_device")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    call(_lib().tetra_lmac_track_sync_device, ptr(d_sb1_type2), int(type2_stride), ptr(d_crc_ok), ptr(d_valid), ptr(d_n_frames),
+         int(n_channels), int(frames_per_channel), ptr(d_cell), ptr(d_row_scramb), ptr(d_row_time_rx), ptr(d_row_time), stream_ptr(stream))
 
 
 def _job_array(jobs):
     arr = (Job * max(1, len(jobs)))()
     for i, j in enumerate(jobs):
-        arr[i] = Job(int(j["type"]), int(j.get("blk_num", 0)), _ptr(j.get("row_frame")), _ptr(j.get("n_rows")), int(j["max_rows"]),
-                     int(j.get("out_stride", 0)), _ptr(j.get("frame_scramb")), _ptr(j.get("type2")), _ptr(j.get("crc_ok")), _ptr(j.get("labels")))
+        arr[i] = Job(int(j["type"]), int(j.get("blk_num", 0)), ptr(j.get("row_frame")), ptr(j.get("n_rows")), int(j["max_rows"]),
+                     int(j.get("out_stride", 0)), ptr(j.get("frame_scramb")), ptr(j.get("type2")), ptr(j.get("crc_ok")), ptr(j.get("labels")))
     return arr
 
 
 def decode_frames_workspace_bytes(jobs):
     """tetra_lmac_decode_frames_workspace_bytes (jobs as for decode_frames_device; only type and max_rows matter)."""
-    L = _lib()
-    L.tetra_lmac_decode_frames_workspace_bytes.argtypes = [C.POINTER(Job), C.c_int]
-    L.tetra_lmac_decode_frames_workspace_bytes.restype = C.c_size_t
-    return int(L.tetra_lmac_decode_frames_workspace_bytes(_job_array(jobs), len(jobs)))
+    return int(_lib().tetra_lmac_decode_frames_workspace_bytes(_job_array(jobs), len(jobs)))
 
 
 def decode_frames_device(d_frames, d_frame_type, jobs, frames_per_channel=0, d_frame_bitnum=None, d_time_rx=None, d_time=None, stream=None,
                          d_workspace=None):
     """tetra_lmac_decode_frames_device.  jobs: dicts with type, blk_num, row_frame, n_rows (tensor or None), max_rows, out_stride,
     frame_scramb (tensor or None), type2, crc_ok, labels (int32 tensor [rows][6] or None); d_workspace: uint8 tensor or None (pool)."""
-    L = _lib()
-    L.tetra_lmac_decode_frames_device.argtypes = [C.POINTER(Frames), C.POINTER(Job), C.c_int, C.c_void_p]
-    L.tetra_lmac_decode_frames_device.restype = C.c_int
-    src = Frames(_ptr(d_frames), _ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), _ptr(d_frame_bitnum), _ptr(d_time_rx),
-                 _ptr(d_time), _ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
-    arr = _job_array(jobs)
-    s = None
-    if stream is not None:
-        s = C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    rc = L.tetra_lmac_decode_frames_device(C.byref(src), arr, len(jobs), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_decode_frames_device")
+    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
+                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    call(_lib().tetra_lmac_decode_frames_device, C.byref(src), _job_array(jobs), len(jobs), stream_ptr(stream))
 
 
 def track_sync_lists_device(d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync, n_channels, frames_per_channel,
                             d_cell, d_row_scramb, d_row_time_rx=None, d_row_time=None, d_frame_bitnum=None, d_sb1_labels=None, stream=None):
     """tetra_lmac_track_sync_lists_device (compact SB1 rows = the SYNC list's)."""
-    vp = C.c_void_p
-    L = _lib()
-    L.tetra_lmac_track_sync_lists_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.tetra_lmac_track_sync_lists_device.restype = C.c_int
-    s = None
-    if stream is not None:
-        s = vp(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
-    rc = L.tetra_lmac_track_sync_lists_device(_ptr(d_sb1_type2), int(type2_stride), _ptr(d_crc_ok), _ptr(d_frame_type), _ptr(d_n_frames),
-                                              _ptr(d_chan_first_sync), int(n_channels), int(frames_per_channel), _ptr(d_cell), _ptr(d_row_scramb),
-                                              _ptr(d_row_time_rx), _ptr(d_row_time), _ptr(d_frame_bitnum), _ptr(d_sb1_labels), s)
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_track_sync_lists_device")
-
-
-def _stream(stream):
-    return None if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+    call(_lib().tetra_lmac_track_sync_lists_device, ptr(d_sb1_type2), int(type2_stride), ptr(d_crc_ok), ptr(d_frame_type), ptr(d_n_frames),
+         ptr(d_chan_first_sync), int(n_channels), int(frames_per_channel), ptr(d_cell), ptr(d_row_scramb), ptr(d_row_time_rx),
+         ptr(d_row_time), ptr(d_frame_bitnum), ptr(d_sb1_labels), stream_ptr(stream))
 
 
 def rm3014_decode_device(d_words, n, d_out_words, d_dist, stream=None):
     """tetra_lmac_rm3014_decode_device (include/tetra_aach.h): torch tensors on the GPU -- int32 / uint32 [n] 30-bit words in and out,
     uint8 [n] distances (0..3, or AACH_UNDECODABLE and the word unchanged)."""
-    L = _lib()
-    L.tetra_lmac_rm3014_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tetra_lmac_rm3014_decode_device.restype = C.c_int
-    rc = L.tetra_lmac_rm3014_decode_device(_ptr(d_words), int(n), _ptr(d_out_words), _ptr(d_dist), _stream(stream))
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_rm3014_decode_device")
+    call(_lib().tetra_lmac_rm3014_decode_device, ptr(d_words), int(n), ptr(d_out_words), ptr(d_dist), stream_ptr(stream))
 
 
 def decode_aach_rm3014_device(d_type5, n_blocks, in_stride, d_scramb, d_type2, out_stride, d_crc_ok, stream=None):
     """tetra_lmac_decode_aach_rm3014_device: decode_batch_device for TPSAP_T_BBK rows with the RM(30,14) decoding behind the
     descrambler; rows of >= 32 bytes out (30 bits, the distance, a zero)."""
-    L = _lib()
-    L.tetra_lmac_decode_aach_rm3014_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.tetra_lmac_decode_aach_rm3014_device.restype = C.c_int
-    rc = L.tetra_lmac_decode_aach_rm3014_device(_ptr(d_type5), int(n_blocks), int(in_stride), _ptr(d_scramb), _ptr(d_type2), int(out_stride),
-                                                _ptr(d_crc_ok), _stream(stream))
-    if rc:
-        raise TetraDemodError(rc, "tetra_lmac_decode_aach_rm3014_device")
+    call(_lib().tetra_lmac_decode_aach_rm3014_device, ptr(d_type5), int(n_blocks), int(in_stride), ptr(d_scramb), ptr(d_type2),
+         int(out_stride), ptr(d_crc_ok), stream_ptr(stream))

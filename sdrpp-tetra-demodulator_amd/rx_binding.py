@@ -1,19 +1,14 @@
 """ctypes binding of the receive chain behind one handle (include/tetra_rx.h)."""
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import binding as B
-from .binding import TetraDemodError, load_library
+from ._ffi import P, TetraDemodError, call, check, declare, i32, i64, ptr, size_t, stream_ptr, u64, vp
+from .binding import load_library
 from .bsync_binding import BsyncState
 
-RX_EXPORTS = ["tetra_rx_default_config", "tetra_rx_create", "tetra_rx_destroy", "tetra_rx_reset", "tetra_rx_process_device",
-              "tetra_rx_process", "tetra_rx_wait", "tetra_rx_max_rows", "tetra_rx_type1_bits", "tetra_rx_fetch", "tetra_rx_rows_device",
-              "tetra_rx_get_cell", "tetra_rx_get_sync_state", "tetra_rx_bits_device", "tetra_rx_demod", "tetra_rx_stage_ms"]
-# include/tetra_retune.h (resets of single channels while the stream runs): the chain's share
-RX_RETUNE_EXPORTS = ["tetra_rx_reset_channels_device"]
-# include/tetra_aach.h (the AACH decoded with its Reed-Muller code): the chain's share
-RX_AACH_EXPORTS = ["tetra_rx_fetch_aach_dist"]
 KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
 N_KINDS = 6
 FLAG_ONE_STREAM = 1
@@ -39,52 +34,53 @@ class CellState(C.Structure):
                                           "phy_mn")]
 
 
-_ready = False
+# include/tetra_rx.h
+SIGNATURES = {
+    "tetra_rx_default_config": (i32, [P(RxConfig)]),
+    "tetra_rx_create": (i32, [P(RxConfig), P(vp)]),
+    "tetra_rx_destroy": (i32, [vp]),
+    "tetra_rx_reset": (i32, [vp]),
+    "tetra_rx_process_device": (i32, [vp, vp, i32, vp]),
+    "tetra_rx_process": (i32, [vp, vp, i32]),
+    "tetra_rx_wait": (i32, [vp]),
+    "tetra_rx_max_rows": (i32, [vp]),
+    "tetra_rx_type1_bits": (i32, [i32]),
+    "tetra_rx_fetch": (i32, [vp, i32, i32, vp, vp, i32, i32, P(i32)]),
+    "tetra_rx_rows_device": (i32, [vp, i32, i32, P(vp), P(i32), P(vp), P(vp), vp]),
+    "tetra_rx_get_cell": (i32, [vp, i32, i32, P(CellState)]),
+    "tetra_rx_get_sync_state": (i32, [vp, i32, i32, P(BsyncState)]),
+    "tetra_rx_bits_device": (i32, [vp, i32, P(vp), P(i32), P(vp), vp]),
+    "tetra_rx_demod": (vp, [vp]),
+    "tetra_rx_stage_ms": (i32, [vp, P(C.c_float * 4)]),
+}
+# include/tetra_rx_out.h (the one-step hand-off of a call's blocks)
+OUT_SIGNATURES = {
+    "tetra_rx_out_bound": (i32, [vp, i32, i32, P(u64)]),
+    "tetra_rx_out_enqueue": (i32, [vp, i32, i32, i32, vp, u64, P(i64)]),
+    "tetra_rx_out_query": (i32, [vp, i64]),
+    "tetra_rx_out_wait": (i32, [vp, i64]),
+    "tetra_rx_out_host_alloc": (vp, [size_t]),
+    "tetra_rx_out_host_free": (None, [vp]),
+    "tetra_rx_out_view": (i32, [vp, u64, i32, P(vp), P(vp), P(i32), P(i32)]),
+    "tetra_rx_unpack_bits": (i32, [vp, i32, i32, i32, vp, i32]),
+}
+# include/tetra_retune.h (resets of single channels while the stream runs): the chain's share
+RETUNE_SIGNATURES = {"tetra_rx_reset_channels_device": (i32, [vp, vp, i32, vp])}
+# include/tetra_aach.h (the AACH decoded with its Reed-Muller code): the chain's share
+AACH_SIGNATURES = {"tetra_rx_fetch_aach_dist": (i32, [vp, i32, vp, i32, P(i32)])}
+RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
+RX_RETUNE_EXPORTS, RX_AACH_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES)
 
 
+@functools.lru_cache(None)
 def _lib():
-    global _ready
-    L = load_library()
-    if not _ready:
-        vp, i32 = C.c_void_p, C.c_int
-        L.tetra_rx_default_config.argtypes = [C.POINTER(RxConfig)]
-        L.tetra_rx_create.argtypes = [C.POINTER(RxConfig), C.POINTER(vp)]
-        L.tetra_rx_destroy.argtypes = [vp]
-        L.tetra_rx_reset.argtypes = [vp]
-        L.tetra_rx_process_device.argtypes = [vp, vp, i32, vp]
-        L.tetra_rx_process.argtypes = [vp, vp, i32]
-        L.tetra_rx_wait.argtypes = [vp]
-        L.tetra_rx_max_rows.argtypes = [vp]
-        L.tetra_rx_type1_bits.argtypes = [i32]
-        L.tetra_rx_fetch.argtypes = [vp, i32, i32, vp, vp, i32, i32, C.POINTER(i32)]
-        L.tetra_rx_rows_device.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), vp]
-        L.tetra_rx_get_cell.argtypes = [vp, i32, i32, vp]
-        L.tetra_rx_get_sync_state.argtypes = [vp, i32, i32, vp]
-        L.tetra_rx_bits_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), vp]
-        L.tetra_rx_demod.argtypes = [vp]
-        L.tetra_rx_demod.restype = vp
-        L.tetra_rx_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 4)]
-        for n in RX_EXPORTS:
-            if n != "tetra_rx_demod":
-                getattr(L, n).restype = i32
-        if hasattr(L, "tetra_rx_reset_channels_device"):       # (a TETRA_DEMOD_LIB override may be an older build without it)
-            L.tetra_rx_reset_channels_device.argtypes = [vp, vp, i32, vp]
-            L.tetra_rx_reset_channels_device.restype = i32
-        if hasattr(L, "tetra_rx_fetch_aach_dist"):
-            L.tetra_rx_fetch_aach_dist.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
-            L.tetra_rx_fetch_aach_dist.restype = i32
-        _ready = True
-    return L
+    # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
+    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES},
+                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS)
 
 
 def type1_bits(kind):
     return int(_lib().tetra_rx_type1_bits(int(kind)))
-
-
-def _stream_ptr(stream):
-    if stream is None:
-        return None
-    return C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
 
 
 class RxChain:
@@ -94,9 +90,7 @@ class RxChain:
     def __init__(self, n_channels=1, max_samples=36000, layout=B.LAYOUT_CHANNEL_MAJOR, device=-1, kinds=0, flags=0, demod_flags=0, **params):
         self._lib = _lib()
         cfg = RxConfig()
-        rc = self._lib.tetra_rx_default_config(C.byref(cfg))
-        if rc:
-            raise TetraDemodError(rc, "tetra_rx_default_config")
+        call(self._lib.tetra_rx_default_config, C.byref(cfg))
         cfg.demod.n_channels, cfg.demod.max_samples, cfg.demod.layout, cfg.demod.device = n_channels, max_samples, layout, device
         cfg.demod.flags = demod_flags
         for k, v in params.items():
@@ -106,9 +100,7 @@ class RxChain:
         cfg.kinds, cfg.flags = kinds, flags
         self.n_channels, self.max_samples = n_channels, max_samples
         h = C.c_void_p()
-        rc = self._lib.tetra_rx_create(C.byref(cfg), C.byref(h))
-        if rc:
-            raise TetraDemodError(rc, "tetra_rx_create")
+        call(self._lib.tetra_rx_create, C.byref(cfg), C.byref(h))
         self._h = h
         self.max_rows = int(self._lib.tetra_rx_max_rows(h))
 
@@ -124,35 +116,29 @@ class RxChain:
         except Exception:
             pass
 
-    def _chk(self, rc, what):
-        if rc:
-            raise TetraDemodError(rc, what)
-
     def reset(self):
-        self._chk(self._lib.tetra_rx_reset(self._h), "tetra_rx_reset")
+        call(self._lib.tetra_rx_reset, self._h)
 
     def reset_channels(self, channels, stream=None):
         """tetra_rx_reset_channels_device: the listed channels start afresh from the next process call on, everything else stays;
         enqueued on `stream`, not waited for."""
         ch = np.ascontiguousarray(np.asarray(channels, np.int64).astype(np.int32).reshape(-1))
-        self._chk(self._lib.tetra_rx_reset_channels_device(self._h, ch.ctypes.data_as(C.c_void_p) if ch.size else None, int(ch.size),
-                                                           _stream_ptr(stream)), "tetra_rx_reset_channels_device")
+        call(self._lib.tetra_rx_reset_channels_device, self._h, ptr(ch) if ch.size else None, int(ch.size), stream_ptr(stream))
 
     def process(self, iq):
         iq = np.ascontiguousarray(iq, np.complex64)
         n = iq.size // self.n_channels
-        self._chk(self._lib.tetra_rx_process(self._h, iq.ctypes.data_as(C.c_void_p), int(n)), "tetra_rx_process")
+        call(self._lib.tetra_rx_process, self._h, ptr(iq), int(n))
 
     def process_device(self, d_iq, n_samples, stream=None):
-        p = C.c_void_p(d_iq.data_ptr() if hasattr(d_iq, "data_ptr") else int(d_iq))
-        self._chk(self._lib.tetra_rx_process_device(self._h, p, int(n_samples), _stream_ptr(stream)), "tetra_rx_process_device")
+        call(self._lib.tetra_rx_process_device, self._h, ptr(d_iq), int(n_samples), stream_ptr(stream))
 
     def wait(self):
-        self._chk(self._lib.tetra_rx_wait(self._h), "tetra_rx_wait")
+        call(self._lib.tetra_rx_wait, self._h)
 
     def count(self, kind, which=0):
         n = C.c_int(0)
-        self._chk(self._lib.tetra_rx_fetch(self._h, which, kind, None, None, 0, 0, C.byref(n)), "tetra_rx_fetch")
+        call(self._lib.tetra_rx_fetch, self._h, which, kind, None, None, 0, 0, C.byref(n))
         return n.value
 
     def fetch(self, kind, which=0):
@@ -162,49 +148,45 @@ class RxChain:
         blocks = np.zeros(max(n, 1), BLOCK_DTYPE)
         t1 = np.zeros((max(n, 1), nb), np.uint8)
         got = C.c_int(0)
-        self._chk(self._lib.tetra_rx_fetch(self._h, which, kind, blocks.ctypes.data_as(C.c_void_p), t1.ctypes.data_as(C.c_void_p), nb,
-                                           max(n, 1), C.byref(got)), "tetra_rx_fetch")
+        call(self._lib.tetra_rx_fetch, self._h, which, kind, ptr(blocks), ptr(t1), nb, max(n, 1), C.byref(got))
         return blocks[:got.value], t1[:got.value]
 
     def fetch_aach_dist(self, which=0):
         """tetra_rx_fetch_aach_dist: uint8 [n], byte 30 of every BBK row in fetch(KIND_BBK)'s order -- the Hamming distance 0..3 the
         RM(30,14) decoder corrected, or AACH_UNDECODABLE.  Needs a handle created with FLAG_AACH_RM3014."""
         n = C.c_int(0)
-        self._chk(self._lib.tetra_rx_fetch_aach_dist(self._h, which, None, 0, C.byref(n)), "tetra_rx_fetch_aach_dist")
+        call(self._lib.tetra_rx_fetch_aach_dist, self._h, which, None, 0, C.byref(n))
         dist = np.zeros(max(n.value, 1), np.uint8)
         got = C.c_int(0)
-        self._chk(self._lib.tetra_rx_fetch_aach_dist(self._h, which, dist.ctypes.data_as(C.c_void_p), max(n.value, 1), C.byref(got)),
-                  "tetra_rx_fetch_aach_dist")
+        call(self._lib.tetra_rx_fetch_aach_dist, self._h, which, ptr(dist), max(n.value, 1), C.byref(got))
         return dist[:got.value]
 
     def cells(self, first=0, count=None):
         count = self.n_channels - first if count is None else count
         arr = (CellState * max(count, 1))()
-        self._chk(self._lib.tetra_rx_get_cell(self._h, first, count, arr), "tetra_rx_get_cell")
+        call(self._lib.tetra_rx_get_cell, self._h, first, count, arr)
         return [arr[i] for i in range(count)]
 
     def sync_states(self, first=0, count=None):
         count = self.n_channels - first if count is None else count
         arr = (BsyncState * max(count, 1))()
-        self._chk(self._lib.tetra_rx_get_sync_state(self._h, first, count, arr), "tetra_rx_get_sync_state")
+        call(self._lib.tetra_rx_get_sync_state, self._h, first, count, arr)
         return [(arr[i].state, arr[i].bits_in_buf, arr[i].bitbuf_start_bitnum, arr[i].next_frame_start_bitnum) for i in range(count)]
 
     def stage_ms(self):
         ms = (C.c_float * 4)()
-        self._chk(self._lib.tetra_rx_stage_ms(self._h, C.byref(ms)), "tetra_rx_stage_ms")
+        call(self._lib.tetra_rx_stage_ms, self._h, C.byref(ms))
         return [float(v) for v in ms]
 
     def rows_device(self, kind, which=0, stream=None):
         """-> (d_type2 pointer, type2_stride, d_blocks pointer, d_n_rows pointer): raw device addresses."""
         t2, blk, nr, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-        self._chk(self._lib.tetra_rx_rows_device(self._h, which, kind, C.byref(t2), C.byref(st), C.byref(blk), C.byref(nr), _stream_ptr(stream)),
-                  "tetra_rx_rows_device")
+        call(self._lib.tetra_rx_rows_device, self._h, which, kind, C.byref(t2), C.byref(st), C.byref(blk), C.byref(nr), stream_ptr(stream))
         return t2.value, st.value, blk.value, nr.value
 
     def bits_device(self, which=0, stream=None):
         bits, nb, st = C.c_void_p(), C.c_void_p(), C.c_int(0)
-        self._chk(self._lib.tetra_rx_bits_device(self._h, which, C.byref(bits), C.byref(st), C.byref(nb), _stream_ptr(stream)),
-                  "tetra_rx_bits_device")
+        call(self._lib.tetra_rx_bits_device, self._h, which, C.byref(bits), C.byref(st), C.byref(nb), stream_ptr(stream))
         return bits.value, st.value, nb.value
 
     def demod_handle(self):
@@ -215,29 +197,28 @@ class RxChain:
         and return a Delivery without waiting.  buf = None: the next of two page-locked buffers of this handle (sized for the worst case),
         so the arrays a Delivery returns stay valid until the second delivery after it is enqueued; else a HostBuffer, a torch tensor on
         the handle's GPU, or any object with a .ctypes pointer (pageable memory is refused: TETRA_ERR_ARG)."""
-        self._out = _out_lib()
         flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
         if buf is None:
             if getattr(self, "_pool", None) is None:
                 nb = C.c_uint64(0)
-                self._chk(self._out.tetra_rx_out_bound(self._h, 0, 0, C.byref(nb)), "tetra_rx_out_bound")
+                call(self._lib.tetra_rx_out_bound, self._h, 0, 0, C.byref(nb))
                 self._pool, self._pool_next = [HostBuffer(nb.value) for _ in range(2)], 0
             buf = self._pool[self._pool_next]
             self._pool_next ^= 1
         if isinstance(buf, HostBuffer):
-            ptr, cap = buf.ptr, buf.nbytes
+            dst, cap = buf.ptr, buf.nbytes
         elif hasattr(buf, "data_ptr"):
-            ptr, cap = buf.data_ptr(), buf.numel() * buf.element_size()
+            dst, cap = buf.data_ptr(), buf.numel() * buf.element_size()
         else:
-            ptr, cap = buf.ctypes.data, buf.nbytes
-        call = C.c_int64(-1)
-        self._chk(self._out.tetra_rx_out_enqueue(self._h, which, kinds, flags, C.c_void_p(ptr), cap, C.byref(call)), "tetra_rx_out_enqueue")
-        return Delivery(self, call.value, buf, cap)
+            dst, cap = buf.ctypes.data, buf.nbytes
+        ticket = C.c_int64(-1)
+        call(self._lib.tetra_rx_out_enqueue, self._h, which, kinds, flags, dst, cap, C.byref(ticket))
+        return Delivery(self, ticket.value, buf, cap)
 
     def out_bound(self, kinds=0, packed=False, crc_good_only=False):
         nb = C.c_uint64(0)
         flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
-        self._chk(_out_lib().tetra_rx_out_bound(self._h, kinds, flags, C.byref(nb)), "tetra_rx_out_bound")
+        call(_lib().tetra_rx_out_bound, self._h, kinds, flags, C.byref(nb))
         return nb.value
 
     def _close_pool(self):
@@ -248,8 +229,6 @@ class RxChain:
 
 # ---- one-step hand-off of a call's blocks (include/tetra_rx_out.h) ----
 
-RX_OUT_EXPORTS = ["tetra_rx_out_bound", "tetra_rx_out_enqueue", "tetra_rx_out_query", "tetra_rx_out_wait", "tetra_rx_out_host_alloc",
-                  "tetra_rx_out_host_free", "tetra_rx_out_view", "tetra_rx_unpack_bits"]
 OUT_PACKED, OUT_CRC_GOOD = 1, 2
 OUT_MAGIC = 0x4f585254
 
@@ -264,40 +243,15 @@ class OutHeader(C.Structure):
                 ("bytes", C.c_uint64), ("kinds", OutKind * N_KINDS)]
 
 
-_out_ready = False
-
-
-def _out_lib():
-    global _out_ready
-    L = _lib()
-    if not _out_ready:
-        vp, i32 = C.c_void_p, C.c_int
-        L.tetra_rx_out_bound.argtypes = [vp, i32, i32, C.POINTER(C.c_uint64)]
-        L.tetra_rx_out_enqueue.argtypes = [vp, i32, i32, i32, vp, C.c_uint64, C.POINTER(C.c_int64)]
-        L.tetra_rx_out_query.argtypes = [vp, C.c_int64]
-        L.tetra_rx_out_wait.argtypes = [vp, C.c_int64]
-        L.tetra_rx_out_host_alloc.argtypes = [C.c_size_t]
-        L.tetra_rx_out_host_alloc.restype = vp
-        L.tetra_rx_out_host_free.argtypes = [vp]
-        L.tetra_rx_out_host_free.restype = None
-        L.tetra_rx_out_view.argtypes = [vp, C.c_uint64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
-        L.tetra_rx_unpack_bits.argtypes = [vp, i32, i32, i32, vp, i32]
-        for n in ("tetra_rx_out_bound", "tetra_rx_out_enqueue", "tetra_rx_out_query", "tetra_rx_out_wait", "tetra_rx_out_view",
-                  "tetra_rx_unpack_bits"):
-            getattr(L, n).restype = i32
-        _out_ready = True
-    return L
-
-
 class HostBuffer:
     """Page-locked, coherent host memory mapped for the GPUs (tetra_rx_out_host_alloc); .array is a uint8 numpy view of it."""
 
     def __init__(self, nbytes):
-        self._lib = _out_lib()
+        self._lib = _lib()
         self.nbytes = int(nbytes)
         self.ptr = self._lib.tetra_rx_out_host_alloc(self.nbytes)
         if not self.ptr:
-            raise TetraDemodError(-5, "tetra_rx_out_host_alloc")
+            check(-5, self._lib.tetra_rx_out_host_alloc)
         self.array = np.ctypeslib.as_array((C.c_uint8 * self.nbytes).from_address(self.ptr))
 
     def close(self):
@@ -316,7 +270,7 @@ class HostBuffer:
 def view_delivery(buf, nbytes=None):
     """A completed delivery in host memory (numpy uint8 array, or HostBuffer) -> (header, {kind: (blocks, type1)}): numpy views into
     the buffer; type1 is [n][row_bytes] (packed rows when the header's flags say so).  A header status other than TETRA_OK raises."""
-    L = _out_lib()
+    L = _lib()
     arr = buf.array if isinstance(buf, HostBuffer) else buf
     nbytes = arr.nbytes if nbytes is None else int(nbytes)
     base = arr.ctypes.data
@@ -325,9 +279,7 @@ def view_delivery(buf, nbytes=None):
     for i in range(max(0, min(hd.n_kinds, N_KINDS))):
         k = hd.kinds[i].kind
         pb, pt, n, rb = C.c_void_p(), C.c_void_p(), C.c_int(0), C.c_int(0)
-        rc = L.tetra_rx_out_view(C.c_void_p(base), nbytes, k, C.byref(pb), C.byref(pt), C.byref(n), C.byref(rb))
-        if rc:
-            raise TetraDemodError(rc, "tetra_rx_out_view")
+        call(L.tetra_rx_out_view, base, nbytes, k, C.byref(pb), C.byref(pt), C.byref(n), C.byref(rb))
         ob, ot = pb.value - base, pt.value - base
         blocks = arr[ob: ob + n.value * BLOCK_DTYPE.itemsize].view(BLOCK_DTYPE)
         out[k] = (blocks, arr[ot: ot + n.value * rb.value].reshape(n.value, rb.value))
@@ -339,9 +291,7 @@ def unpack_bits(packed, n_bits):
     packed = np.ascontiguousarray(packed, np.uint8)
     n, rb = packed.shape
     out = np.zeros((n, n_bits), np.uint8)
-    rc = _out_lib().tetra_rx_unpack_bits(packed.ctypes.data_as(C.c_void_p), n, rb, n_bits, out.ctypes.data_as(C.c_void_p), n_bits)
-    if rc:
-        raise TetraDemodError(rc, "tetra_rx_unpack_bits")
+    call(_lib().tetra_rx_unpack_bits, ptr(packed), n, rb, n_bits, ptr(out), n_bits)
     return out
 
 
@@ -353,13 +303,13 @@ class Delivery:
         self.header = None
 
     def ready(self):
-        rc = self.chain._out.tetra_rx_out_query(self.chain._h, self.call)
+        rc = self.chain._lib.tetra_rx_out_query(self.chain._h, self.call)
         if rc < 0:
-            raise TetraDemodError(rc, "tetra_rx_out_query")
+            check(rc, self.chain._lib.tetra_rx_out_query)
         return rc == 0
 
     def wait(self):
-        self.chain._chk(self.chain._out.tetra_rx_out_wait(self.chain._h, self.call), "tetra_rx_out_wait")
+        call(self.chain._lib.tetra_rx_out_wait, self.chain._h, self.call)
         buf = self.buf
         if hasattr(buf, "data_ptr"):              # a device tensor: the header says how much to bring over
             head = buf[:C.sizeof(OutHeader)].cpu().numpy()

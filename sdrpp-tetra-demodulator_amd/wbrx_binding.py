@@ -1,21 +1,15 @@
 """ctypes binding of the wideband receiver (include/tetra_wbrx.h): one SDR capture in, the receive chain's blocks per carrier out."""
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import binding as B
-from .binding import TetraDemodError, load_library
+from ._ffi import P, call, declare, i32, i64, ptr, stream_ptr, u32, vp
+from .binding import load_library
 from .chan_binding import ChanConfig
-from .rx_binding import RxChain, RxConfig, _stream_ptr
+from .rx_binding import RxChain, RxConfig
 from .rx_binding import _lib as _rx_lib
-
-WBRX_EXPORTS = ["tetra_wbrx_default_config", "tetra_wbrx_create", "tetra_wbrx_destroy", "tetra_wbrx_reset", "tetra_wbrx_process_device",
-                "tetra_wbrx_process_device_cs16", "tetra_wbrx_process_device_cs8", "tetra_wbrx_process", "tetra_wbrx_process_cs16",
-                "tetra_wbrx_rx", "tetra_wbrx_bins", "tetra_wbrx_frames_device", "tetra_wbrx_bin_power", "tetra_wbrx_stage_ms"]
-# include/tetra_shift.h (the frequency-shifted bank): the wideband receiver's share
-WBRX_SHIFT_EXPORTS = ["tetra_wbrx_set_shift", "tetra_wbrx_get_shift"]
-# include/tetra_retune.h (carrier slots that move while the stream runs): the wideband receiver's share
-WBRX_RETUNE_EXPORTS = ["tetra_wbrx_retune", "tetra_wbrx_retune_count"]
 
 
 class WbrxConfig(C.Structure):
@@ -23,50 +17,45 @@ class WbrxConfig(C.Structure):
                 ("resamp_cutoff_rel", C.c_double), ("resamp_kaiser_beta", C.c_double), ("bins", C.c_void_p), ("rx", RxConfig)]
 
 
-_ready = False
+# include/tetra_wbrx.h
+SIGNATURES = {
+    "tetra_wbrx_default_config": (i32, [P(WbrxConfig)]),
+    "tetra_wbrx_create": (i32, [P(WbrxConfig), P(vp)]),
+    "tetra_wbrx_destroy": (i32, [vp]),
+    "tetra_wbrx_reset": (i32, [vp]),
+    "tetra_wbrx_process_device": (i32, [vp, vp, i32, vp]),
+    "tetra_wbrx_process_device_cs16": (i32, [vp, vp, i32, vp]),
+    "tetra_wbrx_process_device_cs8": (i32, [vp, vp, i32, vp]),
+    "tetra_wbrx_process": (i32, [vp, vp, i32]),
+    "tetra_wbrx_process_cs16": (i32, [vp, vp, i32]),
+    "tetra_wbrx_rx": (vp, [vp]),
+    "tetra_wbrx_bins": (i32, [vp, vp]),
+    "tetra_wbrx_frames_device": (i32, [vp, i32, P(vp), P(i32), vp]),
+    "tetra_wbrx_bin_power": (i32, [vp, vp]),
+    "tetra_wbrx_stage_ms": (i32, [vp, P(C.c_float * 2)]),
+}
+# include/tetra_shift.h (the frequency-shifted bank): the wideband receiver's share
+SHIFT_SIGNATURES = {
+    "tetra_wbrx_set_shift": (i32, [vp, u32]),
+    "tetra_wbrx_get_shift": (i32, [vp, P(u32)]),
+}
+# include/tetra_retune.h (carrier slots that move while the stream runs): the wideband receiver's share
+RETUNE_SIGNATURES = {
+    "tetra_wbrx_retune": (i32, [vp, vp, vp]),
+    "tetra_wbrx_retune_count": (i32, [vp, P(i64), P(i64)]),
+}
+WBRX_EXPORTS, WBRX_SHIFT_EXPORTS, WBRX_RETUNE_EXPORTS = list(SIGNATURES), list(SHIFT_SIGNATURES), list(RETUNE_SIGNATURES)
 
 
+@functools.lru_cache(None)
 def _lib():
-    global _ready
-    L = load_library()
-    if not _ready:
-        vp, i32 = C.c_void_p, C.c_int
-        L.tetra_wbrx_default_config.argtypes = [C.POINTER(WbrxConfig)]
-        L.tetra_wbrx_create.argtypes = [C.POINTER(WbrxConfig), C.POINTER(vp)]
-        L.tetra_wbrx_destroy.argtypes = [vp]
-        L.tetra_wbrx_reset.argtypes = [vp]
-        for n in ("tetra_wbrx_process_device", "tetra_wbrx_process_device_cs16", "tetra_wbrx_process_device_cs8"):
-            getattr(L, n).argtypes = [vp, vp, i32, vp]
-        L.tetra_wbrx_process.argtypes = [vp, vp, i32]
-        L.tetra_wbrx_process_cs16.argtypes = [vp, vp, i32]
-        L.tetra_wbrx_rx.argtypes = [vp]
-        L.tetra_wbrx_rx.restype = vp
-        L.tetra_wbrx_bins.argtypes = [vp, vp]
-        L.tetra_wbrx_frames_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), vp]
-        L.tetra_wbrx_bin_power.argtypes = [vp, vp]
-        L.tetra_wbrx_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 2)]
-        for n in WBRX_EXPORTS:
-            if n != "tetra_wbrx_rx":
-                getattr(L, n).restype = i32
-        if hasattr(L, "tetra_wbrx_set_shift"):       # (a TETRA_DEMOD_LIB override may be an older build without the shift)
-            L.tetra_wbrx_set_shift.argtypes = [vp, C.c_uint32]
-            L.tetra_wbrx_set_shift.restype = i32
-            L.tetra_wbrx_get_shift.argtypes = [vp, C.POINTER(C.c_uint32)]
-            L.tetra_wbrx_get_shift.restype = i32
-        if hasattr(L, "tetra_wbrx_retune"):
-            L.tetra_wbrx_retune.argtypes = [vp, vp, vp]
-            L.tetra_wbrx_retune.restype = i32
-            L.tetra_wbrx_retune_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-            L.tetra_wbrx_retune_count.restype = i32
-        _ready = True
-    return L
+    # (a TETRA_DEMOD_LIB override may be an older build without the shift and the retune)
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES}, optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS)
 
 
 def default_config():
     cfg = WbrxConfig()
-    rc = _lib().tetra_wbrx_default_config(C.byref(cfg))
-    if rc:
-        raise TetraDemodError(rc, "tetra_wbrx_default_config")
+    call(_lib().tetra_wbrx_default_config, C.byref(cfg))
     return cfg
 
 
@@ -130,9 +119,7 @@ class WidebandRx:
             setattr(cfg.rx.demod, k, v)
         self.M, self.D, self.max_in, self.n_bins = n_channels, cfg.chan.decimation, max_in, int(keep.size)
         h = C.c_void_p()
-        rc = self._lib.tetra_wbrx_create(C.byref(cfg), C.byref(h))
-        if rc:
-            raise TetraDemodError(rc, "tetra_wbrx_create")
+        call(self._lib.tetra_wbrx_create, C.byref(cfg), C.byref(h))
         self._h = h
         max_samples = int(((self.D - 1 + max_in) // self.D) * interp // decim + 1)
         self.rx = _ChainView(self._lib.tetra_wbrx_rx(h), self.n_bins, max_samples)
@@ -141,11 +128,11 @@ class WidebandRx:
 
     def set_shift(self, inc):
         """tetra_wbrx_set_shift: forwards to the channeliser; between process calls, from the next call's first frame."""
-        self._chk(self._lib.tetra_wbrx_set_shift(self._h, int(inc) & 0xffffffff), "tetra_wbrx_set_shift")
+        call(self._lib.tetra_wbrx_set_shift, self._h, int(inc) & 0xffffffff)
 
     def get_shift(self):
         v = C.c_uint32(0)
-        self._chk(self._lib.tetra_wbrx_get_shift(self._h, C.byref(v)), "tetra_wbrx_get_shift")
+        call(self._lib.tetra_wbrx_get_shift, self._h, C.byref(v))
         return int(v.value)
 
     def retune(self, bins, stream=None):
@@ -154,12 +141,12 @@ class WidebandRx:
         new = np.ascontiguousarray(np.asarray(bins, np.int64).astype(np.int32).reshape(-1))
         if new.size != self.n_bins:
             raise ValueError("retune takes exactly %d bins" % self.n_bins)
-        self._chk(self._lib.tetra_wbrx_retune(self._h, new.ctypes.data_as(C.c_void_p), _stream_ptr(stream)), "tetra_wbrx_retune")
+        call(self._lib.tetra_wbrx_retune, self._h, ptr(new), stream_ptr(stream))
 
     def retune_count(self):
         """-> (accepted retunes, slots they moved) since create."""
         a, b = C.c_int64(0), C.c_int64(0)
-        self._chk(self._lib.tetra_wbrx_retune_count(self._h, C.byref(a), C.byref(b)), "tetra_wbrx_retune_count")
+        call(self._lib.tetra_wbrx_retune_count, self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def close(self):
@@ -175,22 +162,18 @@ class WidebandRx:
         except Exception:
             pass
 
-    def _chk(self, rc, what):
-        if rc:
-            raise TetraDemodError(rc, what)
-
     def reset(self):
-        self._chk(self._lib.tetra_wbrx_reset(self._h), "tetra_wbrx_reset")
+        call(self._lib.tetra_wbrx_reset, self._h)
 
     def process(self, x):
         """Host capture: complex64 [n], or int16 interleaved I / Q ([n][2] or [2 n]) -> tetra_wbrx_process / _process_cs16."""
         x = np.asarray(x)
         if x.dtype == np.int16:
             x = np.ascontiguousarray(x).reshape(-1)
-            self._chk(self._lib.tetra_wbrx_process_cs16(self._h, x.ctypes.data_as(C.c_void_p), x.size // 2), "tetra_wbrx_process_cs16")
+            call(self._lib.tetra_wbrx_process_cs16, self._h, ptr(x), x.size // 2)
         else:
             x = np.ascontiguousarray(x, np.complex64).reshape(-1)
-            self._chk(self._lib.tetra_wbrx_process(self._h, x.ctypes.data_as(C.c_void_p), x.size), "tetra_wbrx_process")
+            call(self._lib.tetra_wbrx_process, self._h, ptr(x), x.size)
 
     def process_device(self, d_x, n_in=None, stream=None):
         """Device capture: the entry point follows the tensor's dtype (complex64, or interleaved I / Q pairs int16 / int8, as
@@ -199,18 +182,17 @@ class WidebandRx:
         name = {"torch.int16": "tetra_wbrx_process_device_cs16", "torch.int8": "tetra_wbrx_process_device_cs8"}.get(dt, "tetra_wbrx_process_device")
         if n_in is None:
             n_in = d_x.numel() // 2 if name != "tetra_wbrx_process_device" else d_x.numel()
-        p = C.c_void_p(d_x.data_ptr() if hasattr(d_x, "data_ptr") else int(d_x))
-        self._chk(getattr(self._lib, name)(self._h, p, int(n_in), _stream_ptr(stream)), name)
+        call(getattr(self._lib, name), self._h, ptr(d_x), int(n_in), stream_ptr(stream))
 
     def bins(self):
         out = np.zeros(max(self.n_bins, 1), np.int32)
-        self._chk(self._lib.tetra_wbrx_bins(self._h, out.ctypes.data_as(C.c_void_p)), "tetra_wbrx_bins")
+        call(self._lib.tetra_wbrx_bins, self._h, ptr(out))
         return out[:self.n_bins]
 
     def frames_device(self, which=0, stream=None):
         """-> (device pointer, n_frames) of the resampled carrier IQ [n_frames][n_bins] complex64 of the latest (0) / previous (1) call."""
         p, n = C.c_void_p(), C.c_int(0)
-        self._chk(self._lib.tetra_wbrx_frames_device(self._h, int(which), C.byref(p), C.byref(n), _stream_ptr(stream)), "tetra_wbrx_frames_device")
+        call(self._lib.tetra_wbrx_frames_device, self._h, int(which), C.byref(p), C.byref(n), stream_ptr(stream))
         return p.value, n.value
 
     def frames(self, which=0, stream=None):
@@ -225,10 +207,10 @@ class WidebandRx:
 
     def bin_power(self):
         out = np.zeros(self.M, np.float32)
-        self._chk(self._lib.tetra_wbrx_bin_power(self._h, out.ctypes.data_as(C.c_void_p)), "tetra_wbrx_bin_power")
+        call(self._lib.tetra_wbrx_bin_power, self._h, ptr(out))
         return out
 
     def stage_ms(self):
         ms = (C.c_float * 2)()
-        self._chk(self._lib.tetra_wbrx_stage_ms(self._h, C.byref(ms)), "tetra_wbrx_stage_ms")
+        call(self._lib.tetra_wbrx_stage_ms, self._h, C.byref(ms))
         return [float(v) for v in ms]

@@ -1,9 +1,10 @@
 """Builds and binds tests/emul/bsync_emul.cpp (host build of the burst synchroniser's logic, csrc/bsync_core.hpp)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import hostlib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -15,10 +16,19 @@ _lib = None
 
 
 def build(force=False):
-    stale = force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in DEPS)
-    if stale:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", LIB, os.path.join(HERE, "bsync_emul.cpp")], check=True)
-    return LIB
+    return hostlib.build(LIB, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", hostlib.OUT, "bsync_emul.cpp"], DEPS, force=force)
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "bsync_emul_process": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32]),
+            "bsync_emul_demux": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp]),
+            "bsync_emul_demux_compact": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp]),
+        })
+    return _lib
 
 
 class Emul:
@@ -27,11 +37,6 @@ class Emul:
     def __init__(self, batch=True):
         """batch: LOCKED steady state evaluated frame-parallel like the kernel does (run()'s batch hook) or event by event."""
         self.batch = 1 if batch else 0
-        global _lib
-        if _lib is None:
-            build()
-            _lib = C.CDLL(LIB)
-            _lib.bsync_emul_process.restype = C.c_int
         self.st = np.zeros(4, np.uint32)
         self.carry = np.zeros(4096, np.uint8)
 
@@ -46,19 +51,10 @@ class Emul:
         ty = np.zeros(cap, np.int32)
         bn = np.zeros(cap, np.uint32)
         vp = C.c_void_p
-        n = _lib.bsync_emul_process(self.st.ctypes.data_as(vp), self.carry.ctypes.data_as(vp), b.ctypes.data_as(vp), b.size,
+        n = lib().bsync_emul_process(self.st.ctypes.data_as(vp), self.carry.ctypes.data_as(vp), b.ctypes.data_as(vp), b.size,
                                     fr.ctypes.data_as(vp), ty.ctypes.data_as(vp), bn.ctypes.data_as(vp), cap, self.batch)
         assert n >= 0
         return fr[:n, :510].copy(), ty[:n].copy(), bn[:n].copy()
-
-
-def _lib_demux():
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
-        _lib.bsync_emul_process.restype = C.c_int
-    return _lib
 
 
 def pack_frames(frames):
@@ -75,7 +71,7 @@ def demux(frames, frame_type, tpsap, blk_num, row_stride, packed=False, fill=9):
     rows = np.full((n, row_stride), fill, np.uint8)
     valid = np.full(n, fill, np.int32)
     vp = C.c_void_p
-    rc = _lib_demux().bsync_emul_demux(src.ctypes.data_as(vp), int(packed), ft.ctypes.data_as(vp), n, tpsap, blk_num, rows.ctypes.data_as(vp),
+    rc = lib().bsync_emul_demux(src.ctypes.data_as(vp), int(packed), ft.ctypes.data_as(vp), n, tpsap, blk_num, rows.ctypes.data_as(vp),
                                        row_stride, valid.ctypes.data_as(vp))
     if rc:
         raise ValueError("refused")
@@ -91,7 +87,7 @@ def demux_compact(frames, frame_type, tpsap, blk_num, row_stride, packed=False, 
     row_frame = np.full(n, -1, np.int32)
     cnt = np.zeros(1, np.int32)
     vp = C.c_void_p
-    rc = _lib_demux().bsync_emul_demux_compact(src.ctypes.data_as(vp), int(packed), ft.ctypes.data_as(vp), n, tpsap, blk_num,
+    rc = lib().bsync_emul_demux_compact(src.ctypes.data_as(vp), int(packed), ft.ctypes.data_as(vp), n, tpsap, blk_num,
                                                rows.ctypes.data_as(vp), row_stride, row_frame.ctypes.data_as(vp), cnt.ctypes.data_as(vp))
     if rc:
         raise ValueError("refused")

@@ -2,9 +2,10 @@
 Compiles on first use."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import hostlib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
@@ -13,23 +14,18 @@ _lib = None
 
 
 def build():
-    deps = [os.path.join(_HERE, "chan_shift_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "chan_fft_core.hpp")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        tmp = _SO + ".tmp.%d" % os.getpid()
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", deps[0], "-o", tmp], check=True)
-        os.replace(tmp, _SO)
-    return _SO
+    return hostlib.build(_SO, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "chan_shift_emul.cpp", "-o", hostlib.OUT],
+                         [os.path.join(_HERE, "chan_shift_emul.cpp")] + [os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", f) for f in ("chan_fft_core.hpp",)])
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
-        L.chan_fft_shift_emul_fmt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_uint,
-                                              C.c_int, C.c_void_p]
-        L.chan_fft_shift_emul_fmt.restype = C.c_int
-        L.chan_shift_phasor.argtypes = [C.c_uint, C.c_void_p]
-        _lib = L
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "chan_fft_shift_emul_fmt": (i32, [vp, vp, i32, i32, i32, i32, C.c_longlong, vp, C.c_uint, i32, vp]),
+            "chan_shift_phasor": (None, [C.c_uint, vp]),
+        })
     return _lib
 
 

@@ -1,7 +1,6 @@
 """Builds and binds tests/emul/emul.cpp (host emulation of the kernels' lane-level code)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,6 +16,7 @@ DEPS = [os.path.join(HERE, "emul.cpp"),
 
 sys.path.insert(0, ROOT)
 import tetra_amd  # noqa: E402
+from oracle import hostlib  # noqa: E402
 
 Config = tetra_amd.pkg.binding.Config
 ChannelState = tetra_amd.pkg.binding.ChannelState
@@ -38,39 +38,28 @@ class Tables(C.Structure):
 
 
 def build(force=False):
-    stale = force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in DEPS)
-    if stale:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-mavx2", "-DTETRA_HOST_EMUL",
-                        "-shared", "-fPIC", "-o", LIB, os.path.join(HERE, "emul.cpp")], check=True)
-    return LIB
+    return hostlib.build(LIB, ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-mavx2", "-DTETRA_HOST_EMUL", "-shared", "-fPIC",
+                               "-o", hostlib.OUT, "emul.cpp"], DEPS, force=force)
 
 
 _lib = None
+_FUSED = [C.POINTER(Tables), C.POINTER(ChannelState), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 
 
 def lib():
     global _lib
     if _lib is None:
-        build()
-        L = C.CDLL(LIB)
-        vp = C.c_void_p
-        L.emul_design.argtypes = [C.POINTER(Config), C.POINTER(Tables)]
-        L.emul_design.restype = C.c_int
-        L.emul_default_cfg.argtypes = [C.POINTER(Config)]
-        L.emul_default_cfg.restype = None
-        L.emul_reset_state.argtypes = [C.POINTER(Tables), C.POINTER(ChannelState)]
-        L.emul_reset_state.restype = None
-        L.emul_fused.argtypes = [C.POINTER(Tables), C.POINTER(ChannelState), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
-        L.emul_fused.restype = C.c_int
-        L.emul_fused_shape.argtypes = L.emul_fused.argtypes + [C.c_int]
-        L.emul_fused_shape.restype = C.c_int
-        L.emul_bits_stride_for.argtypes = [C.POINTER(Config), C.c_longlong]
-        L.emul_bits_stride_for.restype = C.c_longlong
-        L.emul_quality_distance.argtypes = [C.c_int, vp, vp]
-        L.emul_quality_distance.restype = None
-        L.emul_constellation.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int]
-        L.emul_constellation.restype = None
-        _lib = L
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "emul_design": (i32, [C.POINTER(Config), C.POINTER(Tables)]),
+            "emul_default_cfg": (None, [C.POINTER(Config)]),
+            "emul_reset_state": (None, [C.POINTER(Tables), C.POINTER(ChannelState)]),
+            "emul_fused": (i32, _FUSED),
+            "emul_fused_shape": (i32, _FUSED + [i32]),
+            "emul_bits_stride_for": (C.c_longlong, [C.POINTER(Config), C.c_longlong]),
+            "emul_quality_distance": (None, [i32, vp, vp]),
+            "emul_constellation": (None, [i32, vp, vp, vp, vp, vp, i32]),
+        })
     return _lib
 
 

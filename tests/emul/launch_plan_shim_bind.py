@@ -1,7 +1,8 @@
 """ctypes binding of tests/emul/launch_plan_shim.cpp (the product's launch plan, csrc/launch_plan.hpp, built for the host; TEST TOOL)."""
 import ctypes as C
 import os
-import subprocess
+
+from oracle import hostlib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
@@ -11,19 +12,15 @@ _lib = None
 
 
 def build():
-    deps = [os.path.join(_HERE, "launch_plan_shim.cpp")] + [os.path.join(_CSRC, f) for f in ("launch_plan.hpp", "design.hpp", "demod_core.hpp")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", deps[0], "-o", _SO], check=True)
-    return _SO
+    return hostlib.build(_SO, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "launch_plan_shim.cpp", "-o", hostlib.OUT],
+                         [os.path.join(_HERE, "launch_plan_shim.cpp")] + [os.path.join(_CSRC, f) for f in ("launch_plan.hpp", "design.hpp", "demod_core.hpp")])
 
 
 def plan(n_channels, cus, flags, samplerate=-1.0, rrc_tap_count=-1):
     """host::plan_launch for a fresh handle of these parameters: dict(generic, n_wide, rest_ch, deep, long_rows, lanes), None if refused."""
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.launch_plan_shim.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)]
-        _lib.launch_plan_shim.restype = C.c_int
+        _lib = hostlib.load(build(), {"launch_plan_shim": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)])})
     out = (C.c_int * 6)()
     if _lib.launch_plan_shim(n_channels, cus, flags, samplerate, rrc_tap_count, out) != 0:
         return None

@@ -1,9 +1,10 @@
 """Builds and binds tests/emul/lmac_emul.cpp (host build of the lower-MAC decoder's lane-level code)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import hostlib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -18,17 +19,24 @@ _lib = None
 
 
 def build(force=False):
-    stale = force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in DEPS)
-    if stale:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", LIB, os.path.join(HERE, "lmac_emul.cpp")], check=True)
-    return LIB
+    return hostlib.build(LIB, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", hostlib.OUT, "lmac_emul.cpp"], DEPS, force=force)
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "lmac_emul_decode_route": (i32, [i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, i32, C.POINTER(C.c_int32)]),
+            "lmac_emul_decode": (i32, [i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp]),
+            "lmac_emul_decode_frames": (i32, [i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]),
+            "lmac_emul_tdma_advance": (None, [vp, i32, i32, vp]),
+            "lmac_emul_track": (None, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32]),
+        })
+    return _lib
 
 
 def decode_batch(blk_type, type5, scramb):
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
     n345, n2, n1, a = BLK_PARAM[blk_type]
     rows = np.ascontiguousarray(type5, np.uint8)
     n, stride = rows.shape
@@ -36,7 +44,7 @@ def decode_batch(blk_type, type5, scramb):
     out = np.zeros((n, n2), np.uint8)
     ok = np.zeros(n, np.int32)
     vp = C.c_void_p
-    rc = _lib.lmac_emul_decode(n345, n2, n1, a, rows.ctypes.data_as(vp), n, stride, si.ctypes.data_as(vp), out.ctypes.data_as(vp), n2,
+    rc = lib().lmac_emul_decode(n345, n2, n1, a, rows.ctypes.data_as(vp), n, stride, si.ctypes.data_as(vp), out.ctypes.data_as(vp), n2,
                                ok.ctypes.data_as(vp))
     assert rc == 0
     return out, ok
@@ -44,10 +52,6 @@ def decode_batch(blk_type, type5, scramb):
 
 def decode_frames(tpsap, blk_num, frames_packed, frame_type, row_frame, frame_scramb, out_stride):
     """The lane code of k_lmac_frames (tetra_lmac_decode_frames_device, one job) for the listed frames: (rows [n][out_stride], crc_ok)."""
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
     fr = np.ascontiguousarray(frames_packed, np.uint32)
     ft = np.ascontiguousarray(frame_type, np.int32)
     rf = np.ascontiguousarray(row_frame, np.int32)
@@ -55,7 +59,7 @@ def decode_frames(tpsap, blk_num, frames_packed, frame_type, row_frame, frame_sc
     out = np.zeros((rf.size, out_stride), np.uint8)
     ok = np.zeros(rf.size, np.int32)
     vp = C.c_void_p
-    rc = _lib.lmac_emul_decode_frames(int(tpsap), int(blk_num), fr.ctypes.data_as(vp), ft.ctypes.data_as(vp), rf.ctypes.data_as(vp), rf.size,
+    rc = lib().lmac_emul_decode_frames(int(tpsap), int(blk_num), fr.ctypes.data_as(vp), ft.ctypes.data_as(vp), rf.ctypes.data_as(vp), rf.size,
                                       None if sc is None else sc.ctypes.data_as(vp), out.ctypes.data_as(vp), out_stride, ok.ctypes.data_as(vp))
     if rc:
         raise ValueError("refused")
@@ -64,14 +68,10 @@ def decode_frames(tpsap, blk_num, frames_packed, frame_type, row_frame, frame_sc
 
 def tdma_advance(start, kmax):
     """tdma_advance (lmac_core.hpp) built for the host: start [n][3] (tn, fn, mn) -> [n][kmax] packed times after k = 1..kmax steps."""
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
     st = np.ascontiguousarray(start, np.uint32)
     out = np.zeros((len(st), kmax), np.uint32)
     vp = C.c_void_p
-    _lib.lmac_emul_tdma_advance(st.ctypes.data_as(vp), len(st), int(kmax), out.ctypes.data_as(vp))
+    lib().lmac_emul_tdma_advance(st.ctypes.data_as(vp), len(st), int(kmax), out.ctypes.data_as(vp))
     return out
 
 
@@ -80,10 +80,6 @@ def track(sb1_type2, crc_ok, valid, n_frames, cell, stale_tcd_on_bad_crc=False):
     SB1 rows, crc_ok / valid per frame slot, n_frames [n_channels] consumed frames (None: all), cell [n_channels][10] uint32
     (tetra_lmac_cell_state_t) updated in place -> (code, time on entry, time after the SB1) per frame slot.  stale_tcd_on_bad_crc plants
     the tracker's earlier rule (a bad-CRC SB1 sets the clock to the last good SYNC PDU's time): for tests that show they would notice."""
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
     rows = np.ascontiguousarray(sb1_type2, np.uint8)
     n_ch = len(cell)
     F = rows.shape[0] // n_ch
@@ -92,7 +88,7 @@ def track(sb1_type2, crc_ok, valid, n_frames, cell, stale_tcd_on_bad_crc=False):
     nf = None if n_frames is None else np.ascontiguousarray(n_frames, np.int32)
     outs = [np.zeros(n_ch * F, np.uint32) for _ in range(3)]
     vp = C.c_void_p
-    _lib.lmac_emul_track(rows.ctypes.data_as(vp), int(rows.shape[1]), ok.ctypes.data_as(vp), va.ctypes.data_as(vp),
+    lib().lmac_emul_track(rows.ctypes.data_as(vp), int(rows.shape[1]), ok.ctypes.data_as(vp), va.ctypes.data_as(vp),
                          None if nf is None else nf.ctypes.data_as(vp), n_ch, F, cell.ctypes.data_as(vp), *(o.ctypes.data_as(vp) for o in outs),
                          int(bool(stale_tcd_on_bad_crc)))
     return tuple(outs)

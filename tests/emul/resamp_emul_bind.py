@@ -1,9 +1,10 @@
 """ctypes binding of tests/emul/resamp_emul.cpp (host emulation of the rational resampler's kernels; TEST TOOL)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import hostlib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
@@ -12,20 +13,15 @@ _lib = None
 
 
 def build():
-    deps = [os.path.join(_HERE, "resamp_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "resamp_core.hpp")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", deps[0], "-o", _SO], check=True)
-    return _SO
+    return hostlib.build(_SO, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "resamp_emul.cpp", "-o", hostlib.OUT],
+                         [os.path.join(_HERE, "resamp_emul.cpp")] + [os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", f) for f in ("resamp_core.hpp",)])
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
-        vp = C.c_void_p
-        L.resamp_emul.argtypes = [C.c_int] * 6 + [vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong, vp]
-        L.resamp_emul.restype = C.c_int
-        _lib = L
+        vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
+        _lib = hostlib.load(build(), {"resamp_emul": (i32, [i32] * 6 + [vp, vp, vp, i32, i64, i64, vp])})
     return _lib
 
 

@@ -1,7 +1,8 @@
 """ctypes binding of tests/emul/retune_emul.cpp (host build of csrc/retune_core.hpp, the retune lane code; TEST TOOL)."""
 import ctypes as C
 import os
-import subprocess
+
+from oracle import hostlib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
@@ -23,26 +24,20 @@ class DemodView(C.Structure):
 
 
 def build():
-    deps = [os.path.join(_HERE, "retune_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "retune_core.hpp")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror", deps[0], "-o", _SO], check=True)
-    return _SO
+    return hostlib.build(_SO, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror", "retune_emul.cpp", "-o", hostlib.OUT],
+                         [os.path.join(_HERE, "retune_emul.cpp"), os.path.join(_ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "retune_core.hpp")])
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
         vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
-        L.retune_emul_view_bytes.restype = i32
-        L.retune_emul_reset_demod.argtypes = [C.POINTER(DemodView), vp, i32, i32]
-        L.retune_emul_reset_demod.restype = None
-        L.retune_emul_reset_tail.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32]
-        L.retune_emul_reset_tail.restype = None
-        L.retune_emul_keep.argtypes = [vp, i32, i64, i32, i32, vp]
-        L.retune_emul_keep.restype = None
-        L.retune_emul_rebuild.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp]
-        L.retune_emul_rebuild.restype = None
-        assert L.retune_emul_view_bytes() == C.sizeof(DemodView)
-        _lib = L
+        _lib = hostlib.load(build(), {
+            "retune_emul_view_bytes": (i32, []),
+            "retune_emul_reset_demod": (None, [C.POINTER(DemodView), vp, i32, i32]),
+            "retune_emul_reset_tail": (None, [vp, i32, vp, i32, vp, i32, vp, i32, i32]),
+            "retune_emul_keep": (None, [vp, i32, i64, i32, i32, vp]),
+            "retune_emul_rebuild": (None, [vp, i32, i32, i64, vp, vp, i32, i32, vp]),
+        })
+        assert _lib.retune_emul_view_bytes() == C.sizeof(DemodView)
     return _lib

@@ -1,9 +1,10 @@
 """Builds and binds tests/emul/rm3014_emul.cpp (host build of the AACH's Reed-Muller lane code in lmac_core.hpp)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import hostlib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -15,17 +16,19 @@ _lib = None
 
 
 def build(force=False):
-    stale = force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in DEPS)
-    if stale:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", LIB, os.path.join(HERE, "rm3014_emul.cpp")], check=True)
-    return LIB
+    return hostlib.build(LIB, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", hostlib.OUT, "rm3014_emul.cpp"], DEPS, force=force)
 
 
 def _load():
     global _lib
     if _lib is None:
-        build()
-        _lib = C.CDLL(LIB)
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "rm3014_emul_encode": (None, [vp, i32, vp]),
+            "rm3014_emul_syndrome": (None, [vp, i32, vp]),
+            "rm3014_emul_decode": (None, [vp, i32, vp, vp]),
+            "rm3014_emul_table": (i32, [vp]),
+        })
     return _lib
 
 

@@ -27,6 +27,80 @@ def test_header_symbols_all_exported(pkg):
     assert L.tetra_demod_build_id().decode() == pkg.build.source_hash() == pkg.build.lib_build_id()
 
 
+def _declarations():
+    """(header, return type, name, [parameter declarations]) of every function declared in include/*.h."""
+    import glob
+    out = []
+    for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        src = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        src = re.sub(r"//[^\n]*", "", src)
+        src = "\n".join(line for line in src.split("\n") if not line.lstrip().startswith("#"))
+        for m in re.finditer(r"([A-Za-z_][\w\s\*]*?[\s\*])(\w+)\s*\(([^()]*)\)\s*;", src):
+            args = " ".join(m.group(3).split())
+            out.append((os.path.basename(h), " ".join(m.group(1).split()), m.group(2),
+                        [] if args in ("", "void") else [a.strip() for a in args.split(",")]))
+    return out
+
+
+def test_signatures_agree_with_the_headers(pkg):
+    """Every function an include/*.h declares has an entry in some binding module's signature table: as many parameters, a
+    restype that fits the declared return type, and a ctypes type of the declared width for every 64-bit / size_t / double
+    parameter (a c_int there corrupts the arguments silently)."""
+    tables = {}
+    for mod in (pkg.binding, pkg.chan_binding, pkg.scan_binding, pkg.lmac_binding, pkg.bsync_binding, pkg.rx_binding, pkg.wbrx_binding):
+        for attr in dir(mod):
+            if attr == "SIGNATURES" or attr.endswith("_SIGNATURES"):
+                for name, sig in getattr(mod, attr).items():
+                    assert name not in tables, name
+                    tables[name] = sig
+    decls = _declarations()
+    assert len(decls) == 134 and len(set(d[0] for d in decls)) == 11 and len(set(d[2] for d in decls)) == 134
+    assert set(tables) == set(d[2] for d in decls)
+    restypes = {"int": (C.c_int,), "uint32_t": (C.c_uint32,), "size_t": (C.c_size_t,), "void": (None,)}
+    wide = {"size_t": C.c_size_t, "uint64_t": C.c_uint64, "int64_t": C.c_int64, "long long": C.c_longlong, "double": C.c_double}
+    L = pkg.load_library()
+    for m in ("chan", "scan", "lmac", "bsync", "rx", "wbrx"):
+        assert getattr(pkg, m + "_binding")._lib() is L
+    for hdr, ret, name, params in decls:
+        restype, argtypes = tables[name]
+        assert len(argtypes) == len(params), (hdr, name)
+        assert restype in (restypes[ret] if "*" not in ret else (C.c_void_p, C.c_char_p)), (hdr, name, ret)
+        for decl, ct in zip(params, argtypes):
+            ctype = decl.rsplit(" ", 1)[0].replace("const ", "").strip()
+            if ctype in wide:
+                assert ct is not C.c_int and C.sizeof(ct) == C.sizeof(wide[ctype]), (hdr, name, decl)
+                assert (ct is C.c_double) == (ctype == "double"), (hdr, name, decl)
+            elif "*" in decl or "[" in decl:
+                assert C.sizeof(ct) == C.sizeof(C.c_void_p) and ct not in (C.c_int64, C.c_uint64, C.c_size_t), (hdr, name, decl)
+        fn = getattr(L, name)          # what the tables say is what the loaded library's functions carry
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_missing_symbols_are_named_at_load(pkg):
+    """_ffi.declare: a name the library lacks raises with the name, unless the table's caller lists it as optional."""
+    L = C.CDLL(pkg.load_library()._name)
+    ffi = pkg._ffi
+    ffi.declare(L, {"tetra_demod_no_such_entry": (C.c_int, [])}, optional=("tetra_demod_no_such_entry",))
+    with pytest.raises(RuntimeError, match="tetra_demod_no_such_entry"):
+        ffi.declare(L, {"tetra_demod_abi_version": (C.c_int, []), "tetra_demod_no_such_entry": (C.c_int, [])})
+    a = np.zeros(3, np.float32)
+    assert ffi.ptr(None) is None and ffi.ptr(a) == a.ctypes.data and ffi.ptr(12345) == 12345 and ffi.stream_ptr(None) is None
+    with pytest.raises(pkg.TetraDemodError, match="tetra_demod_abi_version failed: -2") as e:
+        ffi.check(-2, L.tetra_demod_abi_version, hip=7)
+    assert (e.value.status, e.value.hip) == (-2, 7)
+
+
+def test_build_deps_cover_the_tree(pkg):
+    """build.DEPS, what the build id is taken over, is every file of csrc/ and every public header."""
+    import glob
+    pk = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc")
+    want = [f for f in glob.glob(os.path.join(pk, "*")) if os.path.isfile(f)] + glob.glob(os.path.join(ROOT, "include", "*.h"))
+    got = [os.path.normpath(os.path.join(pk, d)) for d in pkg.build.DEPS]
+    assert len(got) == len(set(got)) and set(got) == set(want) and len(want) >= 46
+    assert pkg.build.DEPS == sorted(pkg.build.DEPS)
+    assert pkg.load_library().tetra_demod_build_id().decode() == pkg.build.source_hash() == pkg.build.lib_build_id()
+
+
 def test_channeliser_header_symbols_all_exported(pkg):
     src = open(os.path.join(ROOT, "include", "tetra_chan.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)

@@ -94,8 +94,7 @@ def test_lane_code_packed_route_equals_byte_route(lref):
     taken for the clean rows, gives the byte route's output bit for bit, and both equal the reference."""
     import ctypes as C
     from tests.emul import lmac_emul_bind
-    lmac_emul_bind.decode_batch(0, np.zeros((1, 120), np.uint8), np.zeros(1, np.uint32))          # builds / loads the library
-    L = lmac_emul_bind._lib
+    L = lmac_emul_bind.lib()
     vp = C.c_void_p
     for t in CODED:
         n345, n2, n1, a, _ = lref.BLK_PARAM[t]
