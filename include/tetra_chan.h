@@ -30,9 +30,11 @@ extern "C" {
 #endif
 
 typedef struct tetra_chan_config {
-    int32_t n_channels;        /* M: must factor as N1*N2 with N1, N2 <= 64 (e.g. 800 = 25*32, 32 = 4*8) */
+    int32_t n_channels;        /* M >= 2: must factor as N1*N2 with N1, N2 <= 64 (e.g. 800 = 25*32, 32 = 4*8; a factor of 1 is fine: 2, 61;
+                                  largest 4096 = 64*64), else TETRA_ERR_UNSUPPORTED (67, 4097, 64*67) */
     int32_t taps_per_channel;  /* P: prototype length L = P*M (1..32) */
-    int32_t decimation;        /* D >= 1 */
+    int32_t decimation;        /* D >= 1: need not divide M and may exceed it (D = 1: a frame per sample; D > M: samples between
+                                  frames are skipped).  The whole domain M x P x D is held to the tolerance on the GPU: tests/test_chan.py */
     int32_t max_in;            /* largest n_in of one process call */
     int32_t device;            /* HIP device ordinal, -1 = current */
     int32_t reserved;          /* flags: TETRA_CHAN_FLAG_* (0 = default); any other bit: TETRA_ERR_ARG */

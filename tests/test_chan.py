@@ -69,6 +69,127 @@ def test_oracle_memoised_phasors_are_the_definition(oracle):
             assert abs(y[m, k] - acc) < 1e-6 * (1 + abs(acc))
 
 
+def test_oracle_is_the_definition_where_frames_skip_samples_and_at_every_sample(oracle):
+    """The same check where the GPU sweep below leans on the oracle outside D <= M, D | M: D > M (samples between two frames that
+    no frame's newest tap touches, a history carry longer than a frame step) and D = 1 (a frame per sample) -- two calls each, so
+    the carried history and phase are part of it."""
+    for M, P, D, nf, cut in ((12, 2, 17, 5, 40), (6, 2, 1, 40, 13)):
+        co = oracle.ChanOracle(M, P, D)
+        rng = np.random.default_rng(M + D)
+        x = (rng.standard_normal(nf * D + D // 2) + 1j * rng.standard_normal(nf * D + D // 2)).astype(np.complex64)
+        y = np.concatenate([co.process(x[:cut]), co.process(x[cut:])])
+        assert y.shape == (nf, M)
+        L = M * P
+        xp = np.concatenate([np.zeros(L - 1, np.complex128), x.astype(np.complex128)])
+        for m in range(nf):
+            n_m = (m + 1) * D - 1
+            for k in range(M):
+                acc = 0j
+                for l in range(L):
+                    n = n_m - l
+                    acc += float(co.h[l]) * xp[L - 1 + n] * np.exp(-2j * np.pi * ((k * n) % M) / M)
+                assert abs(y[m, k] - acc) < 1e-6 * (1 + abs(acc)), (M, P, D, m, k)
+
+
+ERR_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE = -1, -2, -3
+
+
+def _create_status(pkg, **fields):
+    """tetra_chan_create on the default configuration with `fields` replaced -> (status, handle); *out starts as a non-NULL value."""
+    import ctypes as C
+    cb = pkg.chan_binding
+    L = cb._lib()
+    cfg = cb.ChanConfig()
+    assert L.tetra_chan_default_config(C.byref(cfg)) == 0
+    cfg.max_in = 64
+    for name, value in fields.items():
+        setattr(cfg, name, value)
+    h = C.c_void_p(0x1234)
+    return L.tetra_chan_create(C.byref(cfg), C.byref(h)), h
+
+
+@pytest.mark.parametrize("fields,status", [(dict(n_channels=67), ERR_UNSUPPORTED),            # a prime > 64
+                                           (dict(n_channels=4097), ERR_UNSUPPORTED),          # 17 x 241
+                                           (dict(n_channels=64 * 67), ERR_UNSUPPORTED),
+                                           (dict(n_channels=1), ERR_ARG), (dict(taps_per_channel=0), ERR_ARG),
+                                           (dict(taps_per_channel=33), ERR_ARG), (dict(decimation=0), ERR_ARG),
+                                           (dict(cutoff_rel=0.0), ERR_ARG), (dict(reserved=4), ERR_ARG), (dict(reserved=0x100), ERR_ARG)])
+def test_create_refuses_what_the_header_does_not_promise(pkg, fields, status):
+    """include/tetra_chan.h: M = N1 N2 with N1, N2 <= 64, P = 1 .. 32, D >= 1, a positive cutoff, the two documented flags.  The
+    arguments and the factorisation are checked before the device is looked for, so this needs none; *out is NULL afterwards."""
+    rc, h = _create_status(pkg, **fields)
+    assert rc == status and not h.value
+
+
+@pytest.mark.parametrize("fields", [dict(n_channels=4096, taps_per_channel=2), dict(n_channels=4032, taps_per_channel=1), dict(n_channels=2),
+                                    dict(n_channels=61), dict(n_channels=32, taps_per_channel=32), dict(n_channels=32, taps_per_channel=1, decimation=1)])
+def test_create_takes_the_ends_of_the_documented_domain(pkg, fields):
+    """The other side of the limits: the largest factors, a factor of 1, P = 1 and P = 32, D = 1 pass the argument checks -- without
+    a device the status is TETRA_ERR_NO_DEVICE, with one a handle comes back."""
+    rc, h = _create_status(pkg, **fields)
+    assert rc in (0, ERR_NO_DEVICE) and (rc == 0) == bool(h.value)
+    if h.value:
+        assert pkg.chan_binding._lib().tetra_chan_destroy(h) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------- geometry sweep
+# (M, P, D, n_in): the documented domain of include/tetra_chan.h where the geometries above never go, each for one thing --
+SWEEP = [(60, 4, 7, 7 * 300 + 3), (32, 8, 5, 5 * 300 + 2), (12, 3, 5, 5 * 300 + 1),      # D does not divide M: n_abs mod M runs through many residues
+         (32, 4, 48, 48 * 200 + 5), (60, 2, 61, 61 * 200 + 7),                           # D > M: samples skipped between frames
+         (32, 4, 1, 700),                                                                # D = 1: a frame per sample
+         (32, 1, 16, 16 * 300 + 3), (60, 1, 7, 7 * 300 + 4),                             # P = 1: L = M
+         (32, 32, 16, 16 * 300 + 9),                                                     # P = 32: the documented maximum
+         (2, 4, 1, 300), (61, 2, 30, 30 * 200 + 11),                                     # a factor of 1 (1 x 2, 1 x 61)
+         (4096, 2, 2048, 2048 * 20 + 5), (4032, 1, 1000, 1000 * 30 + 17),                # the largest factors (64 x 64, 63 x 64) and LDS footprint
+         (800, 8, 300, 300 * 80 + 13), (800, 6, 7, 7 * 760 + 2), (800, 4, 1200, 1200 * 40 + 7),      # the matrix kernel off D = M / 2
+         (800, 5, 400, 400 * 40 + 3), (800, 1, 333, 333 * 60 + 5)]                       # M = 800 with a P the matrix kernel does not take
+SWEEP_NIN = {(M, P, D): nin for M, P, D, nin in SWEEP}
+
+
+def _sweep_cuts(M, P, D, nin):
+    """Call boundaries of the sweep: an empty call, 1 sample, a call that stays short of the first frame (D > 2), a call shorter
+    than the delay line L - 1 (the carry overlaps), one of exactly L - 1, one that ends a sample before a frame boundary, the
+    1 sample that completes that frame, the rest."""
+    L = M * P
+    lens = [0, 1]
+    if D > 2:
+        lens.append((D - 1) // 2)
+    lens += [min((L - 1) // 2, 5 * D + 2), L - 1]
+    lens.append((D - 1 - sum(lens)) % D + 2 * D)
+    lens.append(1)
+    assert sum(lens) < nin
+    lens.append(nin - sum(lens))
+    return [0] + [int(c) for c in np.cumsum(lens)]
+
+
+@pytest.mark.parametrize("M,P,D,nin", SWEEP)
+def test_sweep_chunking_holds_the_calls_it_names(M, P, D, nin):
+    cuts = _sweep_cuts(M, P, D, nin)
+    lens = [b - a for a, b in zip(cuts, cuts[1:])]
+    L = M * P
+    assert cuts[-1] == nin and lens[0] == 0 and lens[1] == 1 and min(lens[1:]) >= 1
+    if D > 2:
+        assert cuts[3] < D                                  # no frame yet
+    i = lens.index(L - 1)
+    assert 1 <= lens[i - 1] < L - 1
+    assert cuts[i + 2] % D == D - 1 and lens[i + 2] == 1 and lens[i + 1] >= D
+
+
+def _sweep_check(M, P, D, cuts, frames_for, process, definition, count):
+    """One stream through `process` and `definition` call by call: frames_for before the call, the definition's count and the
+    returned count agree; -> the largest error of a call relative to that call's largest output magnitude."""
+    worst = 0.0
+    for a, b in zip(cuts, cuts[1:]):
+        want = count(b - a)
+        assert frames_for(b - a) == want, (a, b)
+        yg, yo = process(a, b), definition(a, b)
+        assert yg.shape == yo.shape == (want, M), (a, b, yg.shape, yo.shape)
+        if want:
+            assert np.isfinite(yg).all(), (a, b)
+            worst = max(worst, np.abs(yg - yo).max() / (np.abs(yo).max() + 1e-12))
+    return worst
+
+
 def test_fft_kernel_lane_code_on_the_host_matches_the_definition(oracle):
     """Round 5: M = 800 at D = 400 runs as a 32 x 5 x 5 mixed-radix FFT (csrc/chan_fft_core.hpp).  The kernel's lane-level source --
     fold with its slot / class maps, 32-point FFT, transposed LDS block, twiddle, 5 x 5 DFT, store map -- compiled for the host and run
@@ -185,6 +306,59 @@ def test_gpu_matches_definition(pkg, oracle, M, P, D, nin, flags):
             scale = np.abs(yo).max() + 1e-12
             assert np.abs(yg - yo).max() / scale < 2e-5, (a, b, np.abs(yg - yo).max() / scale)   # float32 DFT vs double definition
     ch.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,P,D,nin", SWEEP)
+def test_gpu_geometry_sweep_matches_definition(pkg, oracle, M, P, D, nin):
+    """The documented geometry domain outside D | M, D <= M, P >= 4 (SWEEP above): white noise through k_channelise (every case
+    but three) and k_channelise_mfma (M = 800 with P = 8, 6, 4), chunked as _sweep_cuts says, call by call against the
+    double-precision definition, 2e-5 of the call's largest output (where the measured values are
+    tabulated); frames_for, the definition's count and the returned count agree before every call."""
+    rng = np.random.default_rng(1000 * M + 40 * D + P)
+    x = (rng.standard_normal(nin) + 1j * rng.standard_normal(nin)).astype(np.complex64)
+    ch = pkg.Channeliser(M, P, D, max_in=nin)
+    co = oracle.ChanOracle(M, P, D)
+    assert np.array_equal(ch.prototype(), co.h)
+    err = _sweep_check(M, P, D, _sweep_cuts(M, P, D, nin), ch.frames_for, lambda a, b: ch.process(x[a:b]), lambda a, b: co.process(x[a:b]),
+                       lambda n: (co.phase.value + n) // D)
+    ch.close()
+    print("chan_sweep_error M %d P %d D %d nin %d: e %.3e" % (M, P, D, nin, err))
+    assert err < 2e-5, err
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["int16", "int8"])
+@pytest.mark.parametrize("M,P,D", [(60, 4, 7), (32, 4, 48), (800, 8, 300)])
+def test_gpu_geometry_sweep_integer_input(pkg, oracle, M, P, D, dtype):
+    """Integer captures at three of the sweep's geometries (D does not divide M; D > M; the matrix kernel): these go through
+    k_chan_convert into the staging buffer behind the delay line.  Against the definition on the quantised samples (2e-5) and bit
+    for bit the complex64 entry point on the converted samples; the sweep's chunking, one call of the integer handle in complex64."""
+    import torch
+    dev = torch.device("cuda", 0)
+    nin = SWEEP_NIN[M, P, D]
+    rng = np.random.default_rng(M + P + D)
+    q, xq = _quantise(rng.standard_normal(nin) + 1j * rng.standard_normal(nin), np.int16 if dtype == "int16" else np.int8)
+    ch_i, ch_f = pkg.Channeliser(M, P, D, max_in=nin), pkg.Channeliser(M, P, D, max_in=nin)
+    co = oracle.ChanOracle(M, P, D)
+    d_q, d_x = torch.from_numpy(q).to(dev), torch.from_numpy(xq).to(dev)
+    cuts = _sweep_cuts(M, P, D, nin)
+    as_float = (cuts[-4], cuts[-3])          # the call that ends a sample before a frame boundary
+
+    def process(a, b):
+        out_i = torch.zeros((max(1, ch_i.frames_for(b - a)), M), dtype=torch.complex64, device=dev)
+        out_f = torch.zeros_like(out_i)
+        n_i = ch_i.process_device(d_x[a:b] if (a, b) == as_float else d_q[a:b], b - a, out_i)
+        n_f = ch_f.process_device(d_x[a:b], b - a, out_f)
+        torch.cuda.synchronize()
+        assert n_i == n_f and torch.equal(out_i[:n_i], out_f[:n_f]), (a, b)
+        return out_i[:n_i].cpu().numpy()
+
+    err = _sweep_check(M, P, D, cuts, ch_i.frames_for, process, lambda a, b: co.process(xq[a:b]), lambda n: (co.phase.value + n) // D)
+    ch_i.close()
+    ch_f.close()
+    print("chan_sweep_error %s M %d P %d D %d nin %d: e %.3e" % (dtype, M, P, D, nin, err))
+    assert err < 2e-5, err
 
 
 @pytest.mark.gpu

@@ -11,6 +11,8 @@ import re
 import numpy as np
 import pytest
 
+from tests.test_chan import SWEEP, _sweep_check, _sweep_cuts
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
 TWO32 = 1 << 32
@@ -242,6 +244,33 @@ def test_gpu_shifted_matches_definition(pkg, oracle, M, P, D, nin, flags):
     assert e0 < 2e-5, e0
     ch.close()
     ch0.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,P,D,nin", SWEEP)
+def test_gpu_shifted_geometry_sweep_matches_definition(pkg, oracle, M, P, D, nin):
+    """test_chan.py's geometry sweep (D not dividing M, D > M, D = 1, P = 1 and 32, a factor of 1, the largest factors, M = 800 off
+    the FFT kernel's geometry) under half a bin of shift from the first sample and ODD_LARGE from the call that ends a sample before
+    a frame boundary on: the phasor inc n_m mod 2^32 and the modulated taps hang on the same per-frame indices as the fold.  Same
+    chunking, same bound (2e-5 of the call's largest output, DESIGN.md section 8.8 with the measured values), same agreement of
+    frames_for, the definition's count and the returned count."""
+    rng = np.random.default_rng(1000 * M + 40 * D + P)
+    x = _noise(rng, nin)
+    half = TWO32 // (2 * M)
+    ch = pkg.Channeliser(M, P, D, max_in=nin, shift=half)
+    d = ShiftedBankDefinition(M, P, D, ch.prototype(), half)
+    cuts = _sweep_cuts(M, P, D, nin)
+
+    def process(a, b):
+        if (a, b) == (cuts[-4], cuts[-3]):
+            ch.set_shift(ODD_LARGE), d.set_shift(ODD_LARGE)
+        return ch.process(x[a:b])
+
+    err = _sweep_check(M, P, D, cuts, ch.frames_for, process, lambda a, b: d.process(x[a:b]),
+                       lambda n: (d.buf.size - (d.L - 1) + n) // D - d.m)
+    ch.close()
+    print("chan_shift_sweep_error M %d P %d D %d nin %d: e1 %.3e" % (M, P, D, nin, err))
+    assert err < 2e-5, err
 
 
 @pytest.mark.gpu

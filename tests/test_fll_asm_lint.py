@@ -1,4 +1,4 @@
-"""Independent lint of the generated FLL assembly (csrc/fll_asm.inc, fll4_asm.inc): the gfx950 hazards the hardware does not
+"""Independent lint of the generated FLL assembly (csrc/fll_asm.inc, fll4_asm.inc, fll16_asm.inc and the two long-row files fll16l_asm.inc, fll8l_asm.inc): the gfx950 hazards the hardware does not
 interlock must be covered by distance in the instruction stream.  The generator enforces them while it schedules
 (gen_fll_asm.py, Emitter._need); this test re-derives them from the emitted TEXT alone, so a scheduling bug cannot hide
 behind the generator's own bookkeeping.  Rules (LLVM GCNHazardRecognizer for gfx940/gfx950):
@@ -81,7 +81,8 @@ def _check(seq, where):
     return bad
 
 
-@pytest.mark.parametrize("fname,macro", [("fll_asm.inc", "FLL_WAVE"), ("fll4_asm.inc", "FLL4_WAVE"), ("fll16_asm.inc", "FLL16_WAVE")])
+@pytest.mark.parametrize("fname,macro", [("fll_asm.inc", "FLL_WAVE"), ("fll4_asm.inc", "FLL4_WAVE"), ("fll16_asm.inc", "FLL16_WAVE"),
+                                         ("fll16l_asm.inc", "FLL16L_WAVE"), ("fll8l_asm.inc", "FLL8L_WAVE")])
 def test_generated_assembly_respects_the_hazard_distances(fname, macro):
     items = _parse(os.path.join(CSRC, fname), macro)
     instrs = [it for it in items if it[0] != "label"]

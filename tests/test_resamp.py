@@ -6,7 +6,7 @@ float32 tolerance, and wideband -> channeliser -> resampler -> demodulator with 
 import numpy as np
 import pytest
 
-TOL = 2e-5          # float32 sums of <= 24 products against double sums, relative to the peak
+TOL = 2e-5          # float32 sums of <= 64 products (taps_per_phase 2 .. 64) against double sums, relative to the peak
 
 
 def _frames(rng, n, C):
@@ -57,27 +57,39 @@ def test_oracle_chunk_invariance(oracle):
 @pytest.mark.parametrize("I,DN,T,C,generic,W", [(18, 25, 16, 10, False, 4), (18, 25, 16, 10, False, 2), (18, 25, 16, 7, False, 2),
                                                 (18, 25, 8, 4, False, 4), (18, 25, 12, 6, False, 4), (18, 25, 24, 2, False, 4),
                                                 (2, 3, 8, 4, False, 4), (3, 2, 8, 3, False, 2), (1, 2, 8, 8, False, 4),
-                                                (18, 25, 16, 10, True, 4), (5, 7, 11, 3, True, 2), (4, 1, 3, 2, True, 4)])
+                                                (18, 25, 16, 10, True, 4), (5, 7, 11, 3, True, 2), (4, 1, 3, 2, True, 4),
+                                                # the ends of the documented domain: the shortest and the longest filter (generic by
+                                                # necessity), one channel (units = 1) on two specialised kernels and upsampling with
+                                                # the longest filter, the identity ratio, the largest ratio create accepts
+                                                (18, 25, 2, 3, True, 2), (18, 25, 64, 2, True, 4), (2, 3, 8, 1, False, 2),
+                                                (18, 25, 16, 1, False, 2), (7, 3, 64, 1, True, 2), (1, 1, 2, 2, True, 4),
+                                                (4096, 4095, 2, 2, True, 4)])
 def test_kernel_thread_code_on_the_host_matches_the_definition(oracle, I, DN, T, C, generic, W):
     """The resampler kernels' thread-level source (csrc/resamp_core.hpp) compiled for the host and run over exactly the thread range
     the C ABI launches (tests/emul/resamp_emul.cpp), with the carried delay line and positions, against the definition: ragged calls
-    (0 / 1 / 2 frames, calls shorter than the delay line, calls that end inside a group of I outputs), every stored element written
-    (the output buffer is NaN-poisoned and exactly sized), for the specialised kernels, both lane-unit widths, and the generic one."""
+    (0 / 1 / 2 frames, calls shorter than the delay line -- one of T - 2 frames behind the stream's bulk --, calls that end inside a
+    group of I outputs), every stored element written (the output buffer is NaN-poisoned and exactly sized), for the specialised
+    kernels, both lane-unit widths, and the generic one."""
     from tests.emul import resamp_emul_bind as re_
     ro = oracle.ResampOracle(C, I, DN, T)
     em = re_.ResampEmul(C, I, DN, T, ro.h, generic=generic, W=W)
     rng = np.random.default_rng(I + 7 * DN + T)
-    n = 40 * DN + 13
-    x = _frames(rng, n, C)
+    n = 40 * DN + 13 if DN <= 25 else 413          # (a few hundred frames at the largest ratio)
+    x = _frames(rng, n + T, C)
     cuts = [0, 0, 1, 3, 4, T - 1 + 4, 3 * DN, 3 * DN + 1, 7 * DN + 5, 7 * DN + 6, 30 * DN, n]
-    cuts = sorted(set(cuts)) + [n]
+    cuts = sorted(set(c for c in cuts if c <= n)) + [n]
     cuts = [0] + cuts          # an empty first call
+    cuts += [n + T - 2, n + T]  # a call of T - 2 frames (shorter than the delay line; T = 2: empty), and two frames behind it
+    worst = 0.0
     for a, b in zip(cuts, cuts[1:]):
         yo, ye = ro.process(x[a:b]), em.process(x[a:b])
         assert yo.shape == ye.shape, (a, b)
         if len(yo):
             assert np.isfinite(ye).all(), (a, b)
+            worst = max(worst, np.abs(yo - ye).max() / np.abs(yo).max())
             assert np.abs(yo - ye).max() / np.abs(yo).max() < 2e-6, (a, b)
+    if T == 64:
+        print("resamp_emul_error I %d DN %d T %d C %d: %.3e" % (I, DN, T, C, worst))
 
 
 def test_resampler_header_symbols_all_exported(pkg):
@@ -92,26 +104,63 @@ def test_resampler_header_symbols_all_exported(pkg):
         assert hasattr(L, n), n
 
 
+@pytest.mark.parametrize("fields,status", [(dict(taps_per_phase=1), -1), (dict(taps_per_phase=65), -1), (dict(interp=4097), -1),
+                                           (dict(decim=4097), -1), (dict(reserved=1), -1),
+                                           (dict(max_in=0x7fffffff, interp=2, decim=1), -6),         # 2^32 - 2 outputs of one call
+                                           (dict(max_in=0x7fffffff, interp=1, decim=1), -6),         # 2^31 - 1 + the two of slack
+                                           (dict(taps_per_phase=2, interp=4096, decim=4096), -3),    # inside the limits: goes on to the device
+                                           (dict(taps_per_phase=64, max_in=0x7fffffff, interp=1, decim=2), -3)])
+def test_create_limits_precede_the_device_lookup(pkg, fields, status):
+    """tetra_resamp_create at the edges of include/tetra_chan.h's domain: T = 2 .. 64, I and DN <= 4096, reserved = 0 (TETRA_ERR_ARG),
+    a max_in whose output count does not fit 32 bits (TETRA_ERR_SIZE) -- all checked before the device is looked for, *out left NULL.
+    The configurations just inside pass those checks: TETRA_ERR_NO_DEVICE where there is no device, a handle on one."""
+    import ctypes as C
+    cb = pkg.chan_binding
+    L = cb._lib()
+    cfg = cb.ResampConfig()
+    assert L.tetra_resamp_default_config(C.byref(cfg)) == 0
+    cfg.n_channels, cfg.max_in = 2, 64
+    for name, value in fields.items():
+        setattr(cfg, name, value)
+    h = C.c_void_p(0x1234)
+    rc = L.tetra_resamp_create(C.byref(cfg), C.byref(h))
+    if status == -3:
+        assert rc in (0, -3) and (rc == 0) == bool(h.value)
+        if h.value:
+            assert L.tetra_resamp_destroy(h) == 0
+    else:
+        assert rc == status and not h.value
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("I,DN,T,C,nin,flags", [(18, 25, 16, 800, 2500, 0), (18, 25, 16, 800, 2500, 2), (18, 25, 16, 800, 700, 1),
                                                 (18, 25, 8, 64, 999, 0), (18, 25, 12, 30, 999, 0), (18, 25, 24, 800, 1201, 0),
                                                 (18, 25, 16, 7, 1500, 0), (2, 3, 8, 32, 1000, 0), (3, 2, 8, 5, 1000, 0),
-                                                (1, 2, 8, 16, 1000, 0), (5, 7, 11, 12, 800, 0), (160, 147, 10, 4, 600, 0)])
+                                                (1, 2, 8, 16, 1000, 0), (5, 7, 11, 12, 800, 0), (160, 147, 10, 4, 600, 0),
+                                                (18, 25, 2, 3, 999, 0), (18, 25, 64, 2, 999, 0), (2, 3, 8, 1, 1000, 0),
+                                                (18, 25, 16, 1, 1500, 0), (7, 3, 64, 1, 500, 0), (1, 1, 2, 2, 300, 0),
+                                                (4096, 4095, 2, 2, 400, 0)])
 def test_gpu_matches_definition(pkg, oracle, I, DN, T, C, nin, flags):
     """Specialised kernels (16-byte and 8-byte lane units), the generic kernel forced and by necessity (5 / 7, 160 / 147), an odd
-    channel count; ragged calls with carried delay line and position; against the double-precision definition."""
+    channel count; the ends of the documented domain (T = 2 and T = 64, one channel on a specialised kernel and with the longest
+    filter, the identity ratio, 4096 / 4095); ragged calls with carried delay line and position, an empty one and one of T - 2
+    frames among them; against the double-precision definition."""
     rng = np.random.default_rng(I * 31 + C)
-    x = _frames(rng, nin, C)
+    x = _frames(rng, nin + T, C)
     rs = pkg.Resampler(C, I, DN, T, max_in=nin, flags=flags)
     ro = oracle.ResampOracle(C, I, DN, T)
     assert np.array_equal(rs.prototype(), ro.h)
-    cuts = sorted(set([0, 1, 3, T + 2, nin // 3, nin // 3 + 1, nin]))
+    cuts = [0] + sorted(set([0, 1, 3, T + 2, nin // 3, nin // 3 + 1, nin])) + [nin + T - 2, nin + T]
+    worst = 0.0
     for a, b in zip(cuts, cuts[1:]):
         assert rs.frames_for(b - a) == ro.frames_for(b - a)
         yg, yo = rs.process(x[a:b]), ro.process(x[a:b])
         assert yg.shape == yo.shape
         if len(yo):
+            worst = max(worst, np.abs(yg - yo).max() / (np.abs(yo).max() + 1e-12))
             assert np.abs(yg - yo).max() / (np.abs(yo).max() + 1e-12) < TOL, (a, b)
+    if T == 64:
+        print("resamp_error I %d DN %d T %d C %d: %.3e" % (I, DN, T, C, worst))
     rs.reset()
     ro2 = oracle.ResampOracle(C, I, DN, T)
     yg, yo = rs.process(x[:50]), ro2.process(x[:50])
