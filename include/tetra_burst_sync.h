@@ -128,8 +128,9 @@ int tetra_burst_demux_compact_packed_device(const uint32_t* d_frames_packed, con
 /*
  * The frame lists of a call in one pass (round 6): which frame slots hold a SYNC / NORM_1 / NORM_2 burst, and which any of the
  * three, each in frame order -- the d_row_frame of every block kind tetra_burst_rx_cb hands on (SYNC: SB1, SB2; NORM_1: SCH/F;
- * NORM_2: NDB blk 1 + 2; any: BBK), for tetra_lmac_decode_frames_device.  Replaces the count / scan / index passes the compacting
- * demultiplexer runs per kind (18 launches for the six kinds of a downlink) by three launches.
+ * NORM_2: NDB blk 1 + 2; any: BBK), for tetra_lmac_decode_frames_device.  The same three compaction launches (count per 256 frames,
+ * scan of the counts, list write: csrc/compact_core.hpp) that the compacting demultiplexer runs for its one list per kind -- 18
+ * launches for the six kinds of a downlink -- run here once for all four lists.
  *   d_lists       [TETRA_N_LISTS][n] int32 out: list k holds indices into d_frame_type, ascending; entries past its count unspecified
  *   d_counts      [TETRA_N_LISTS] int32 out
  *   d_chan_first  [TETRA_N_LISTS][n / frames_per_channel] int32 out, may be NULL: position in list k of channel c's first entry

@@ -5,7 +5,9 @@ stream every stage is enqueued on): IQ [4096 channels x 36000 samples = 1 s of s
 channels; the chain is run over three consecutive seconds of signal with state carried and the third -- demodulator
 converged, synchroniser LOCKED on every channel -- is the one timed.
 `python profiles/measure_pipeline.py packed` (round 5) hands the frames on PACKED (16 words per frame instead of 512 bytes:
-tetra_bsync_process_packed_device -> tetra_burst_demux_packed_device); without the argument the byte-per-bit frames of round 4."""
+tetra_bsync_process_packed_device -> tetra_burst_demux_packed_device); without the argument the byte-per-bit frames of round 4.
+With `compact` the four kinds then also go through the compacting demultiplexer (tetra_burst_demux_compact[_packed]_device: count,
+scan and list passes + gather per kind), timed as `ms_demux_compact_x4` behind the other stages."""
 import json
 import os
 import sys
@@ -21,6 +23,7 @@ lb, bb = pkg.lmac_binding, pkg.bsync_binding
 dev = torch.device("cuda", 0)
 C, N, SEC, DISTINCT = 4096, 36000, 3, 64
 PACKED = "packed" in sys.argv[1:]
+COMPACT = "compact" in sys.argv[1:]
 stride = pkg.binding.bits_stride(N)
 n_slots = SEC * N // 510 + 2
 iq_all = np.stack([pkg.synth.gen_channel(SEC * N, 4000 + c, bits=pkg.synth.gen_slot_bits(n_slots, c))[0] for c in range(DISTINCT)])
@@ -39,6 +42,8 @@ kinds = (("SB1", lb.TPSAP_T_SB1, 1, 120, 80), ("SB2", lb.TPSAP_T_SB2, 2, 216, 14
          ("BBK", lb.TPSAP_T_BBK, 0, 32, 32))
 bufs = {k[0]: (torch.zeros((C * F, k[3]), dtype=torch.uint8, device=dev), torch.zeros(C * F, dtype=torch.int32, device=dev),
                torch.zeros((C * F, k[4]), dtype=torch.uint8, device=dev), torch.zeros(C * F, dtype=torch.int32, device=dev)) for k in kinds}
+d_row_frame = torch.zeros(C * F, dtype=torch.int32, device=dev)
+d_n_rows = torch.zeros(1, dtype=torch.int32, device=dev)
 
 
 def ev():
@@ -62,6 +67,10 @@ for sec in range(SEC):
         rows, valid, t2, ok = bufs[name]
         lb.decode_batch_device(tpsap, rows, C * F, rs, d_scr, t2, os_, ok, s)
     marks.append(ev()); marks[-1].record(s)
+    if COMPACT:          # (last: the compacted rows overwrite the slot layout's)
+        for name, tpsap, blk, rs, os_ in kinds:
+            bb.demux_compact_device(d_frames, d_ft, C * F, tpsap, blk, bufs[name][0], rs, d_row_frame, d_n_rows, s, packed=PACKED)
+        marks.append(ev()); marks[-1].record(s)
     torch.cuda.synchronize()
     t = [marks[i].elapsed_time(marks[i + 1]) for i in range(4)]
     locked = sum(1 for st in bs.states() if st[0] == bb.RX_S_LOCKED)
@@ -88,7 +97,8 @@ for sec in range(SEC):
     roof["lmac_x4"]["valu_wave_instr_per_s"] = round(wave_instr / (t[3] * 1e-3) / 1e9, 1)
     roof["lmac_x4"]["frac_valu_issue_614G"] = round(wave_instr / (t[3] * 1e-3) / 614.4e9, 4)
     roof["lmac_x4"]["bound"] = "valu-issue (integer add-compare-select)"
+    extra = {"ms_demux_compact_x4": round(marks[4].elapsed_time(marks[5]), 4)} if COMPACT else {}
     print(json.dumps({"second": sec, "frames_packed": PACKED, "channels": C, "samples_per_channel": N, "ms_demod": round(t[0], 3), "ms_burst_sync": round(t[1], 3),
-                      "ms_demux_x4": round(t[2], 3), "ms_lmac_x4": round(t[3], 3), "ms_total": round(sum(t), 3),
+                      "ms_demux_x4": round(t[2], 3), "ms_lmac_x4": round(t[3], 3), "ms_total": round(sum(t), 3), **extra,
                       "x_real_time": round(1000.0 / sum(t), 1), "channels_locked": locked, "frames": int(nf.sum()),
                       "bursts_with_callback": int((ft >= 0).sum()), "frame_slots_decoded_per_kind": C * F, "roofline": roof}))

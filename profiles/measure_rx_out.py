@@ -9,6 +9,9 @@ call k).  Variants, alternated in one process:
                     later (the way a consumer thread would)
   deliver_bytes   the same, one byte per bit
 
+--crc-good: the deliveries keep the CRC-good rows only (count and scan launches before the write).  `delivery_alone_ms`: one delivery
+enqueued behind a finished call and waited for, nothing beside it (best of the rounds).
+
 Prints one JSON object: ms per second of signal per variant (best of the rounds), bytes per delivery.  The delivery kernels' own
 time comes from a separate run under `rocprofv3 --kernel-trace --stats` (--calls N: just N delivered calls, no timing)."""
 import argparse
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--seconds", type=int, default=4)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--crc-good", action="store_true", help="deliveries of the CRC-good rows only")
     ap.add_argument("--calls", type=int, default=0, help="profile mode: only N calls with a packed delivery each, no timing")
     a = ap.parse_args()
     import torch
@@ -88,7 +92,7 @@ def main():
     if a.calls:
         for i in range(a.calls):
             call()
-            rx.deliver(1, packed=True, buf=bufs[i % 2]).wait()
+            rx.deliver(1, packed=True, crc_good_only=a.crc_good, buf=bufs[i % 2]).wait()
         rx.close()
         print(json.dumps({"profiled_calls": a.calls}))
         return
@@ -103,7 +107,7 @@ def main():
                 for kind in range(R.N_KINDS):
                     rx.fetch(kind, which=1)
             elif variant.startswith("deliver"):
-                d = rx.deliver(1, packed=variant == "deliver_packed", buf=bufs[i % 2])
+                d = rx.deliver(1, packed=variant == "deliver_packed", crc_good_only=a.crc_good, buf=bufs[i % 2])
                 if pend is not None:
                     pend.wait()
                 pend = d
@@ -112,10 +116,20 @@ def main():
         rx.wait()
         return (time.perf_counter() - t0) * 1e3 / a.reps, pend
 
+    def alone(packed):
+        call()
+        rx.wait()
+        t0 = time.perf_counter()
+        rx.deliver(0, packed=packed, crc_good_only=a.crc_good, buf=bufs[0]).wait()
+        return (time.perf_counter() - t0) * 1e3
+
     variants = ["none", "fetch", "deliver_packed", "deliver_bytes"]
     best = {v: float("inf") for v in variants}
+    solo = {"packed": float("inf"), "bytes": float("inf")}
     sizes = {}
     for _ in range(a.rounds):
+        for nm in solo:
+            solo[nm] = min([solo[nm]] + [alone(nm == "packed") for _ in range(a.reps)])
         for v in variants:
             ms, d = run(v)
             best[v] = min(best[v], ms)
@@ -123,7 +137,8 @@ def main():
                 sizes[v] = int(d.header.bytes)
                 rows = {int(e.kind): int(e.n_rows) for e in d.header.kinds[:d.header.n_kinds]}
     res = {"channels": C, "samples_per_channel": N, "reps": a.reps, "rounds": a.rounds,
-           "ms_per_second_two_streams": {v: round(best[v], 3) for v in variants},
+           "crc_good_only": a.crc_good, "ms_per_second_two_streams": {v: round(best[v], 3) for v in variants},
+           "delivery_alone_ms": {nm: round(v, 3) for nm, v in solo.items()},
            "delivery_bytes": sizes, "rows_per_kind": rows,
            "fetch_bytes": int(sum(n * (24 + R.type1_bits(kk)) for kk, n in rows.items()))}
     rx.close()

@@ -78,7 +78,7 @@ struct tetra_rx {
     static constexpr int kOutRing = 8;    // the latest deliveries, for tetra_rx_out_query / _wait (created on first use)
     Event ring_ev[kOutRing];
     long long ring_call[kOutRing] = { -1, -1, -1, -1, -1, -1, -1, -1 }, ring_seq[kOutRing] = {}, out_seq = 0;
-    DevMem<int32_t> out_tiles;            // [2][TETRA_RX_N_KINDS][tiles]: kept rows per tile, then their first output row
+    DevMem<int32_t> out_tiles;            // [TETRA_RX_N_KINDS][tiles]: kept rows per tile, scanned in place to their first output row
     DevMem<uint8_t> out_layout;           // the layout the write launch reads (rx_out::Layout)
     // resets of single channels (include/tetra_retune.h, tetra_retune.hip)
     ListRing to_device;                       // the channel lists on their way to the device

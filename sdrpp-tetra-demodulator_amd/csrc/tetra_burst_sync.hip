@@ -16,6 +16,7 @@
 
 #include "../../include/tetra_burst_sync.h"
 #include "bsync_core.hpp"
+#include "compact_core.hpp"
 #include "demux_core.hpp"
 #include "hip_host.hpp"
 #include "retune_impl.hpp"
@@ -187,49 +188,59 @@ template <bool PACKED, bool WIDE> __global__ __launch_bounds__(256) void k_burst
     demux_core::demux_thread<PACKED, WIDE>(blockIdx.x, threadIdx.x, frames, frame_type, n, tpsap, blk_num, rows, row_stride, valid);
 }
 
-// ---- compacting form of the demultiplexer: only frames that carry the block kind produce a row, in frame order ----
-// 1. per block of 256 frames: how many carry it
-__global__ __launch_bounds__(256) void k_demux_count(const int* __restrict__ frame_type, int n, int tpsap, int blk_num,
-                                                     int* __restrict__ block_count) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const bool has = r < n && pieces_for(frame_type[r], tpsap, blk_num).len0 > 0;
-    const int c = __syncthreads_count(has ? 1 : 0);
-    if (threadIdx.x == 0) block_count[blockIdx.x] = c;
+// ---- compaction (compact_core.hpp): list k of a call = the frames r whose mask(r) has bit k set, in frame order ----
+// The compacting form of the demultiplexer is K = 1 (CarriesKind: only frames that carry the block kind produce a row), the frame
+// lists of tetra_burst_index_device K = TETRA_N_LISTS (ListMask).
+constexpr int kRows = 256;            // frames per workgroup of k_list_count / k_list_write
+// 1. entries per kRows frames and list
+template <int K, class Mask> __global__ __launch_bounds__(kRows) void k_list_count(const Mask mask, int n, int nblocks, int* __restrict__ work) {
+    const int r = blockIdx.x * kRows + threadIdx.x;
+    compact_core::block_count<K>(r < n ? mask(r) : 0u, work, nblocks, blockIdx.x);
 }
-// 2. exclusive scan of the block counts (one workgroup; nblocks is a few thousand), total -> *n_rows
-__global__ __launch_bounds__(1024) void k_demux_scan(int* __restrict__ block_count, int nblocks, int* __restrict__ n_rows) {
-    __shared__ int part[1024];
-    const int per = (nblocks + 1023) / 1024;
-    const int lo = threadIdx.x * per, hi = min(nblocks, lo + per);
-    int sum = 0;
-    for (int i = lo; i < hi; ++i) sum += block_count[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                       // Hillis-Steele inclusive scan
-        const int v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
+// 2. exclusive scan of each list's block counts, totals -> counts
+template <int K> __global__ __launch_bounds__(compact_core::kScanThreads) void k_list_scan(int* __restrict__ work, int nblocks, int* __restrict__ counts) {
+    int len[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) len[k] = nblocks;
+    compact_core::scan_counts<K>(work, nblocks, len, counts);
+}
+// 3. the lists themselves [K][n], and (the frame lists only: chan_first != null) per channel the position of its first entry
+template <int K, class Mask> __global__ __launch_bounds__(kRows) void k_list_write(const Mask mask, int n, int nblocks, int frames_per_channel,
+                                                                                  const int* __restrict__ work, int* __restrict__ lists, int* __restrict__ chan_first) {
+    const int r = blockIdx.x * kRows + threadIdx.x;
+    const unsigned m = r < n ? mask(r) : 0u;
+    int at[K];
+    compact_core::block_rank<K, kRows>(m, at);
+    const bool first_of_channel = chan_first && r < n && r % frames_per_channel == 0;
+    const int chans = first_of_channel ? n / frames_per_channel : 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        at[k] += work[k * nblocks + blockIdx.x];
+        if ((m >> k) & 1u) lists[(size_t)k * n + at[k]] = r;
+        if (first_of_channel) chan_first[(size_t)k * chans + r / frames_per_channel] = at[k];
     }
-    int run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-    for (int i = lo; i < hi; ++i) { const int c = block_count[i]; block_count[i] = run; run += c; }
-    if (threadIdx.x == 1023) *n_rows = part[1023];
 }
-// 3. row j <- frame index, frame order kept
-__global__ __launch_bounds__(256) void k_demux_index(const int* __restrict__ frame_type, int n, int tpsap, int blk_num,
-                                                     const int* __restrict__ block_off, int* __restrict__ row_frame) {
-    __shared__ int wave_cnt[4];
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const bool has = r < n && pieces_for(frame_type[r], tpsap, blk_num).len0 > 0;
-    const unsigned long long m = __ballot(has);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) wave_cnt[w] = __popcll(m);
-    __syncthreads();
-    int base = block_off[blockIdx.x];
-    for (int i = 0; i < w; ++i) base += wave_cnt[i];
-    if (has) row_frame[base + __popcll(m & ((1ull << lane) - 1ull))] = r;
+template <int K, class Mask> void lists_launch(const Mask& mask, int n, int frames_per_channel, int* work, int* lists, int* counts, int* chan_first, hipStream_t s) {
+    const int nblocks = (n + kRows - 1) / kRows;
+    hipLaunchKernelGGL((k_list_count<K, Mask>), dim3(nblocks), dim3(kRows), 0, s, mask, n, nblocks, work);
+    hipLaunchKernelGGL(k_list_scan<K>, dim3(1), dim3(compact_core::kScanThreads), 0, s, work, nblocks, counts);
+    hipLaunchKernelGGL((k_list_write<K, Mask>), dim3(nblocks), dim3(kRows), 0, s, mask, n, nblocks, frames_per_channel, work, lists, chan_first);
 }
-// 4. the gather itself, one thread per output dword of the worst case; rows past *n_rows do not exist
+struct CarriesKind {      // the compacting demultiplexer's one list
+    const int* frame_type; int tpsap, blk_num;
+    __device__ unsigned operator()(int r) const { return pieces_for(frame_type[r], tpsap, blk_num).len0 > 0; }
+};
+struct ListMask {         // the frame lists of a call (tetra_burst_index_device): SYNC / NORM_1 / NORM_2 / any
+    const int* frame_type;
+    __device__ unsigned operator()(int r) const {
+        const int t = frame_type[r];
+        return t == TETRA_TRAIN_SYNC ? (1u << TETRA_LIST_SYNC) | (1u << TETRA_LIST_ANY)
+             : t == TETRA_TRAIN_NORM_1 ? (1u << TETRA_LIST_NORM_1) | (1u << TETRA_LIST_ANY)
+             : t == TETRA_TRAIN_NORM_2 ? (1u << TETRA_LIST_NORM_2) | (1u << TETRA_LIST_ANY) : 0u;
+    }
+};
+
+// the gather itself, one thread per output dword of the worst case; rows past *n_rows do not exist
 template <bool PACKED, bool WIDE> __global__ __launch_bounds__(256) void k_demux_gather(const uint8_t* __restrict__ frames, const int* __restrict__ frame_type,
                                                       const int* __restrict__ row_frame, const int* __restrict__ n_rows, int n,
                                                       int tpsap, int blk_num, uint8_t* __restrict__ rows, int row_stride) {
@@ -243,81 +254,6 @@ template <bool GATHER> __global__ __launch_bounds__(256) void k_demux_rows(const
                                                                          uint8_t* __restrict__ rows, int* __restrict__ valid) {
     const long long have = GATHER ? (long long)*n_rows : (long long)n;
     demux_core::rows_thread<GATHER>(blockIdx.x, threadIdx.x, frames, frame_type, row_frame, have, lut, row_u, rows_per_wave, inv_row_u, rows, valid);
-}
-
-// ---- the frame lists of a call (tetra_burst_index_device): SYNC / NORM_1 / NORM_2 / any, frame order ----------------------------
-__device__ __forceinline__ unsigned list_mask(int t) {      // bit k set <=> a frame of type t belongs to list k
-    return t == TETRA_TRAIN_SYNC ? (1u << TETRA_LIST_SYNC) | (1u << TETRA_LIST_ANY)
-         : t == TETRA_TRAIN_NORM_1 ? (1u << TETRA_LIST_NORM_1) | (1u << TETRA_LIST_ANY)
-         : t == TETRA_TRAIN_NORM_2 ? (1u << TETRA_LIST_NORM_2) | (1u << TETRA_LIST_ANY) : 0u;
-}
-// 1. entries per 256 frames and list
-__global__ __launch_bounds__(256) void k_index_count(const int* __restrict__ frame_type, int n, int nblocks, int* __restrict__ work) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const unsigned m = r < n ? list_mask(frame_type[r]) : 0u;
-#pragma unroll
-    for (int k = 0; k < TETRA_N_LISTS; ++k) {
-        const int c = __syncthreads_count((m >> k) & 1u);
-        if (threadIdx.x == 0) work[k * nblocks + blockIdx.x] = c;
-    }
-}
-// 2. exclusive scan of each list's block counts, totals -> counts.  One workgroup of FOUR wavefronts (a run of blocks per thread,
-//    shuffles within a wavefront, one exchange between the four): a workgroup has to find ONE compute unit with room for all its
-//    waves, and beside the demodulator -- whose 199-register waves leave 112 registers on two of a CU's four SIMDs -- the
-//    1024-thread form of this kernel (four waves of 32 registers per SIMD) found none until the demodulator's launch was over: the
-//    tail of the receive chain then ran BEHIND the demodulator it was meant to overlap (two-stream chain 4.17 instead of 3.98 ms).
-constexpr int kScanThreads = 256;
-__global__ __launch_bounds__(kScanThreads) void k_index_scan(int* __restrict__ work, int nblocks, int* __restrict__ counts) {
-    __shared__ int wave_sum[TETRA_N_LISTS][kScanThreads / 64];
-    const int per = (nblocks + kScanThreads - 1) / kScanThreads;
-    const int lo = threadIdx.x * per, hi = min(nblocks, lo + per);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int sum[TETRA_N_LISTS], inc[TETRA_N_LISTS];
-#pragma unroll
-    for (int k = 0; k < TETRA_N_LISTS; ++k) {
-        sum[k] = 0;
-        for (int i = lo; i < hi; ++i) sum[k] += work[k * nblocks + i];
-        inc[k] = sum[k];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(inc[k], d);
-            inc[k] += lane >= d ? v : 0;
-        }
-        if (lane == 63) wave_sum[k][w] = inc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TETRA_N_LISTS; ++k) {
-        int run = inc[k] - sum[k];
-        for (int i = 0; i < w; ++i) run += wave_sum[k][i];
-        for (int i = lo; i < hi; ++i) { const int c = work[k * nblocks + i]; work[k * nblocks + i] = run; run += c; }
-        if (threadIdx.x == kScanThreads - 1) counts[k] = run;
-    }
-}
-// 3. the lists themselves, and per channel the position of its first entry
-__global__ __launch_bounds__(256) void k_index_write(const int* __restrict__ frame_type, int n, int nblocks, int frames_per_channel,
-                                                     const int* __restrict__ work, int* __restrict__ lists, int* __restrict__ chan_first) {
-    __shared__ int wave_cnt[TETRA_N_LISTS][4];
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const unsigned m = r < n ? list_mask(frame_type[r]) : 0u;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long b[TETRA_N_LISTS];
-#pragma unroll
-    for (int k = 0; k < TETRA_N_LISTS; ++k) {
-        b[k] = __ballot((m >> k) & 1u);
-        if (lane == 0) wave_cnt[k][w] = __popcll(b[k]);
-    }
-    __syncthreads();
-    const bool first_of_channel = chan_first && r < n && r % frames_per_channel == 0;
-    const int chans = first_of_channel ? n / frames_per_channel : 0;
-#pragma unroll
-    for (int k = 0; k < TETRA_N_LISTS; ++k) {
-        int at = work[k * nblocks + blockIdx.x];
-        for (int i = 0; i < w; ++i) at += wave_cnt[k][i];
-        at += __popcll(b[k] & ((1ull << lane) - 1ull));
-        if ((m >> k) & 1u) lists[(size_t)k * n + at] = r;
-        if (first_of_channel) chan_first[(size_t)k * chans + r / frames_per_channel] = at;
-    }
 }
 
 size_t lds_bytes(int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * 5 * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
@@ -455,20 +391,26 @@ int tetra_bsync_get_state(tetra_bsync_t* h, int first, int count, tetra_bsync_st
 }  // extern "C"
 
 namespace {
+// the argument rules of both demultiplexers behind their null / range checks: the longest block of the kind fits a row; alignment
+template <bool PACKED> int demux_check(const uint8_t* d_frames, int tpsap, int blk_num, const uint8_t* d_rows, int row_stride) {
+    int longest = 0;
+    for (int t : { TETRA_TRAIN_SYNC, TETRA_TRAIN_NORM_1, TETRA_TRAIN_NORM_2 }) {
+        const Pieces p = pieces_for(t, tpsap, blk_num);
+        longest = p.len0 + p.len1 > longest ? p.len0 + p.len1 : longest;
+    }
+    if (longest == 0) return TETRA_ERR_ARG;                      // no burst type carries (tpsap, blk_num)
+    if (row_stride < longest) return TETRA_ERR_SIZE;
+    if ((row_stride & 3) || ((uintptr_t)d_rows & 3)) return TETRA_ERR_ALIGN;
+    if (PACKED && ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;          // packed frames are read as 32-bit words
+    return TETRA_OK;
+}
+
 template <bool PACKED> int demux_launch(const void* d_frames_v, const int32_t* d_frame_type, int n, int tpsap, int blk_num, uint8_t* d_rows,
                                         int row_stride, int32_t* d_valid, void* hip_stream) {
     const uint8_t* d_frames = static_cast<const uint8_t*>(d_frames_v);
     if (!d_frames || !d_frame_type || !d_rows || !d_valid || n < 0 || tpsap < 0 || tpsap > 5) return TETRA_ERR_ARG;
     if (n == 0) return TETRA_OK;
-    // the longest block this kind can have must fit the row
-    const Pieces longest = tpsap == TETRA_TPSAP_T_SCH_F ? pieces_for(TETRA_TRAIN_NORM_1, tpsap, blk_num)
-                           : tpsap == TETRA_TPSAP_T_NDB ? pieces_for(TETRA_TRAIN_NORM_2, tpsap, blk_num)
-                           : tpsap == TETRA_TPSAP_T_BBK ? pieces_for(TETRA_TRAIN_NORM_1, tpsap, blk_num)
-                                                        : pieces_for(TETRA_TRAIN_SYNC, tpsap, blk_num);
-    if (longest.len0 == 0) return TETRA_ERR_ARG;                      // no burst type carries (tpsap, blk_num)
-    if (row_stride < longest.len0 + longest.len1) return TETRA_ERR_SIZE;
-    if ((row_stride & 3) || ((uintptr_t)d_rows & 3)) return TETRA_ERR_ALIGN;
-    if (PACKED && ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;
+    TETRA_TRY(demux_check<PACKED>(d_frames, tpsap, blk_num, d_rows, row_stride));
     const bool wide = !(row_stride & 7) && !((uintptr_t)d_rows & 7);
     if (demux_core::use_rows_kernel(PACKED, wide, row_stride)) {           // whole rows per wavefront (k_demux_rows)
         const int row_u = row_stride >> 3, rpw = 64 / row_u;
@@ -491,24 +433,12 @@ template <bool PACKED> int demux_compact_launch(const void* d_frames_v, const in
     if (tpsap < 0 || tpsap > 5) return TETRA_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (n == 0) return hipMemsetAsync(d_n_rows, 0, sizeof(int32_t), s) == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
-    // same argument rules as tetra_burst_demux_device
-    const Pieces any[3] = { pieces_for(TETRA_TRAIN_SYNC, tpsap, blk_num), pieces_for(TETRA_TRAIN_NORM_1, tpsap, blk_num),
-                            pieces_for(TETRA_TRAIN_NORM_2, tpsap, blk_num) };
-    int longest = 0;
-    for (const Pieces& p : any) longest = p.len0 + p.len1 > longest ? p.len0 + p.len1 : longest;
-    if (longest == 0) return TETRA_ERR_ARG;                      // no burst type carries this (kind, block number)
-    if (row_stride < longest) return TETRA_ERR_SIZE;
-    if ((row_stride & 3) || ((uintptr_t)d_rows & 3)) return TETRA_ERR_ALIGN;
-    if (PACKED && ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;          // packed frames are read as 32-bit words (as demux_launch<true> checks)
-    const int nblocks = (n + 255) / 256;
-    // the per-block counts / offsets of steps 1-3 live in the head of the row buffer itself (4 bytes per 256 frames of a buffer that
-    // holds at least 30 bytes per frame; 4-byte aligned): the gather, which overwrites it, runs after their last reader in stream
-    // order.  (Until round 5 a stream-ordered allocation per call: every so often the pool gave its memory back in between and one
-    // call took milliseconds.)
-    int* off = reinterpret_cast<int*>(d_rows);
-    hipLaunchKernelGGL(k_demux_count, dim3(nblocks), dim3(256), 0, s, d_frame_type, n, tpsap, blk_num, off);
-    hipLaunchKernelGGL(k_demux_scan, dim3(1), dim3(1024), 0, s, off, nblocks, d_n_rows);
-    hipLaunchKernelGGL(k_demux_index, dim3(nblocks), dim3(256), 0, s, d_frame_type, n, tpsap, blk_num, off, d_row_frame);
+    TETRA_TRY(demux_check<PACKED>(d_frames, tpsap, blk_num, d_rows, row_stride));
+    // the per-block counts / offsets of the three list passes live in the head of the row buffer itself (4 bytes per 256 frames of a
+    // buffer that holds at least 30 bytes per frame; 4-byte aligned): the gather, which overwrites it, runs after their last reader in
+    // stream order.  (Until round 5 a stream-ordered allocation per call: every so often the pool gave its memory back in between and
+    // one call took milliseconds.)
+    lists_launch<1>(CarriesKind{ d_frame_type, tpsap, blk_num }, n, 1, reinterpret_cast<int*>(d_rows), d_row_frame, d_n_rows, nullptr, s);
     const bool wide = !(row_stride & 7) && !((uintptr_t)d_rows & 7);
     const dim3 grid((unsigned)demux_core::units_grid(n, row_stride, wide));
     if (demux_core::use_rows_kernel(PACKED, wide, row_stride)) {           // whole rows per wavefront (k_demux_rows), sized for the worst case of n rows
@@ -549,11 +479,7 @@ int tetra_burst_index_device(const int32_t* d_frame_type, int n, int frames_per_
     if (n == 0) return hipMemsetAsync(d_counts, 0, sizeof(int32_t) * TETRA_N_LISTS, s) == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;      // (no frames: nothing else is touched)
     if (!d_frame_type || !d_lists || !d_work) return TETRA_ERR_ARG;
     if (d_chan_first && (frames_per_channel < 1 || n % frames_per_channel)) return TETRA_ERR_ARG;
-    const int nblocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_index_count, dim3(nblocks), dim3(256), 0, s, d_frame_type, n, nblocks, d_work);
-    hipLaunchKernelGGL(k_index_scan, dim3(1), dim3(kScanThreads), 0, s, d_work, nblocks, d_counts);
-    hipLaunchKernelGGL(k_index_write, dim3(nblocks), dim3(256), 0, s, d_frame_type, n, nblocks, d_chan_first ? frames_per_channel : 1, d_work,
-                       d_lists, d_chan_first);
+    lists_launch<TETRA_N_LISTS>(ListMask{ d_frame_type }, n, d_chan_first ? frames_per_channel : 1, d_work, d_lists, d_counts, d_chan_first, s);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 

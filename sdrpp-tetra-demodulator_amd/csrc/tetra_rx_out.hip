@@ -5,9 +5,10 @@
 // the tail of the call it reads:
 //
 //   k_out_count   (CRC-good only)  per kind and tile of kTile rows: the rows with crc_ok != 0
-//   k_out_layout  ONE workgroup: per kind the tiles' first output rows (a scan of the counts), the layout, the header -> dst
+//   k_out_layout  ONE workgroup: per kind the tiles' first output rows (a scan of the counts, in place), the layout, the header -> dst
 //   k_out_write   per kind and tile: the kept rows' labels and type-1 rows (byte per bit or packed), compacted in LDS so that
 //                 the tile's output is two contiguous runs, then written with 16-byte stores
+// The count, the scan and the ranking of a tile's kept rows are the chain's one compaction (compact_core.hpp).
 //
 // No workgroup reads what another workgroup of the same launch writes (the per-XCD L2s are not coherent); every hand-over is a
 // kernel boundary on one stream.  Nothing is written outside [dst, dst + capacity): the layout launch checks the size first, and a
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tetra_rx_out.h"
+#include "compact_core.hpp"
 #include "rx_handle.hpp"
 #include "rx_out_core.hpp"
 
@@ -52,40 +54,25 @@ __global__ __launch_bounds__(kTile) void k_out_count(const OutArgs a, int32_t* _
     const int t0 = (int)blockIdx.x * kTile;
     if (t0 >= n) return;
     const int i = t0 + (int)threadIdx.x;
-    const int c = __syncthreads_count(i < n && k.ok[i] != 0);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.y * a.tiles + blockIdx.x] = c;
+    compact_core::block_count<1>(i < n && k.ok[i] != 0, tile_cnt + blockIdx.y * a.tiles, a.tiles, blockIdx.x);
 }
 
-// one workgroup: tile offsets, layout, header
-__global__ __launch_bounds__(1024) void k_out_layout(const OutArgs a, const int32_t* __restrict__ tile_cnt, int32_t* __restrict__ tile_off,
-                                                     Layout* __restrict__ lay, uint8_t* __restrict__ dst, uint64_t capacity, long long call) {
-    __shared__ int scan[1024];
+// one workgroup: tile counts -> tile offsets, layout, header
+__global__ __launch_bounds__(compact_core::kScanThreads) void k_out_layout(const OutArgs a, int32_t* __restrict__ tile_off, Layout* __restrict__ lay,
+                                                                           uint8_t* __restrict__ dst, uint64_t capacity, long long call) {
     __shared__ int kept[TETRA_RX_N_KINDS], dec[TETRA_RX_N_KINDS];
     __shared__ __attribute__((aligned(16))) tetra_rx_out_header_t hd;
     const int t = (int)threadIdx.x;
-    for (int s = 0; s < a.nsel; s++) {
-        const int n = rows_of(a.k[s], a.max_rows);
-        if (!(a.flags & TETRA_RX_OUT_CRC_GOOD)) {
-            if (t == 0) kept[s] = dec[s] = n;
-            continue;
-        }
-        const int tiles = (n + kTile - 1) / kTile;
-        int carry = 0;
-        for (int c0 = 0; c0 < tiles; c0 += 1024) {         // exclusive scan of the tile counts, 1024 at a time
-            const int v = c0 + t < tiles ? tile_cnt[s * a.tiles + c0 + t] : 0;
-            scan[t] = v;
-            __syncthreads();
-            for (int d = 1; d < 1024; d <<= 1) {
-                const int add = t >= d ? scan[t - d] : 0;
-                __syncthreads();
-                scan[t] += add;
-                __syncthreads();
-            }
-            if (c0 + t < tiles) tile_off[s * a.tiles + c0 + t] = carry + scan[t] - v;
-            carry += scan[1023];
-            __syncthreads();
-        }
-        if (t == 0) { kept[s] = carry; dec[s] = n; }
+    int tiles[TETRA_RX_N_KINDS];                           // each kind's own tile count; a kind not selected has none
+#pragma unroll
+    for (int s = 0; s < TETRA_RX_N_KINDS; s++) {
+        const int n = s < a.nsel ? rows_of(a.k[s], a.max_rows) : 0;
+        tiles[s] = (n + kTile - 1) / kTile;
+        if (t == 0) kept[s] = dec[s] = n;
+    }
+    if (a.flags & TETRA_RX_OUT_CRC_GOOD) {
+        __syncthreads();                                   // (kept[] is written twice)
+        compact_core::scan_counts<TETRA_RX_N_KINDS>(tile_off, a.tiles, tiles, kept);
     }
     __syncthreads();
     if (t == 0) {
@@ -114,7 +101,6 @@ __global__ __launch_bounds__(256) void k_out_write(const OutArgs a, const int32_
     __shared__ __attribute__((aligned(16))) uint8_t sbits[16 + kTile * kMaxRowBytes];
     __shared__ __attribute__((aligned(16))) uint64_t slab[2 + kTile * 3];
     __shared__ uint8_t src[kTile];
-    __shared__ int wave_cnt[kTile / 64];
     if (lay->status != TETRA_OK) return;
     const int s = (int)blockIdx.y;
     const OutKind& k = a.k[s];
@@ -125,16 +111,10 @@ __global__ __launch_bounds__(256) void k_out_write(const OutArgs a, const int32_
     const bool crc = (a.flags & TETRA_RX_OUT_CRC_GOOD) != 0;
     const int base = crc ? tile_off[s * a.tiles + blockIdx.x] : t0;      // first output row of the tile
     // compaction of the tile's kept rows (waves 0 and 1 hold one row per lane)
-    const int lane = t & 63, w = t >> 6;
     const bool keep = t < kTile && t0 + t < n && (!crc || k.ok[t0 + t] != 0);
-    const unsigned long long m = __ballot(keep);
-    if (t < kTile && lane == 0) wave_cnt[w] = __popcll(m);
-    __syncthreads();
-    int before = 0;
-    for (int v = 0; v < w && v < kTile / 64; v++) before += wave_cnt[v];
-    if (keep) src[before + __popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)t;
-    int cnt = 0;
-    for (int v = 0; v < kTile / 64; v++) cnt += wave_cnt[v];
+    int at[1], cnt;
+    compact_core::block_rank<1, kTile>(keep, at, &cnt);
+    if (keep) src[at[0]] = (uint8_t)t;
     __syncthreads();
     if (cnt == 0) return;
     // labels: 3 words per row; slab[lshift + 3 r + j] holds output word (first word + 3 r + j), lshift = that word's parity, so
@@ -266,7 +246,7 @@ int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* d
     }
     if (reinterpret_cast<uintptr_t>(d) & 15) return TETRA_ERR_ALIGN;
     const int tiles = (h->rows + kTile - 1) / kTile;
-    if (h->out_tiles.reserve(sizeof(int32_t) * 2 * TETRA_RX_N_KINDS * (size_t)tiles) != hipSuccess ||
+    if (h->out_tiles.reserve(sizeof(int32_t) * TETRA_RX_N_KINDS * (size_t)tiles) != hipSuccess ||
         h->out_layout.reserve(sizeof(Layout)) != hipSuccess) {
         (void)hipGetLastError();
         return TETRA_ERR_NOMEM;
@@ -288,16 +268,15 @@ int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* d
     a.flags = flags;
     a.tiles = tiles;
     a.max_rows = h->rows;
-    int32_t* tile_cnt = h->out_tiles;
-    int32_t* tile_off = tile_cnt + (size_t)TETRA_RX_N_KINDS * tiles;
+    int32_t* tile_off = h->out_tiles;                      // [kind][tile]: k_out_count's counts, scanned in place by k_out_layout
     for (auto& e : h->ring_ev)
         if (!e) HIP_TRY(h, hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
     Layout* lay = reinterpret_cast<Layout*>(h->out_layout.get());
     const long long c = h->calls - 1 - which;
     hipStream_t s = h->fetch_s;
     HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[b], 0));
-    if (flags & TETRA_RX_OUT_CRC_GOOD) hipLaunchKernelGGL(k_out_count, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(kTile), 0, s, a, tile_cnt);
-    hipLaunchKernelGGL(k_out_layout, dim3(1), dim3(1024), 0, s, a, tile_cnt, tile_off, lay, d, capacity, c);
+    if (flags & TETRA_RX_OUT_CRC_GOOD) hipLaunchKernelGGL(k_out_count, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(kTile), 0, s, a, tile_off);
+    hipLaunchKernelGGL(k_out_layout, dim3(1), dim3(compact_core::kScanThreads), 0, s, a, tile_off, lay, d, capacity, c);
     hipLaunchKernelGGL(k_out_write, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(256), 0, s, a, tile_off, lay, d);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->ev_out[b], s));

@@ -79,7 +79,7 @@ extern "C" int bsync_emul_demux(const uint8_t* frames, int packed, const int32_t
     return 0;
 }
 
-// the compacting form: row_frame / n_rows as k_demux_count / _scan / _index leave them (frame order), then the gather
+// the compacting form: row_frame / n_rows as the list passes (k_list_count / _scan / _write with CarriesKind) leave them (frame order), then the gather
 extern "C" int bsync_emul_demux_compact(const uint8_t* frames, int packed, const int32_t* frame_type, int n, int tpsap, int blk_num,
                                         uint8_t* rows, int row_stride, int32_t* row_frame, int32_t* n_rows) {
     using namespace demux_core;

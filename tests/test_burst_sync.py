@@ -531,6 +531,39 @@ def test_gpu_compacting_demux_and_counted_decoder_equal_the_slot_layout(pkg, ref
     assert int(cnt.cpu().numpy()[0]) == 0
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,packed", ((65537, True), (257, False)))
+def test_gpu_compacting_demux_at_the_scan_boundaries(pkg, n, packed):
+    """The compacting demultiplexer where its scan of the block counts changes shape (csrc/compact_core.hpp: 256 scanning threads;
+    65537 frames = 257 blocks, the first size at which a thread owns two; 257 frames = a second block of one frame): the count and
+    the kept frames equal numpy's, and the rows are those of the non-compacting demultiplexer at the kept frames -- for SB1 (only
+    SYNC frames kept) and the BBK (every frame with a training sequence)."""
+    import torch
+    lb, bb_ = pkg.lmac_binding, pkg.bsync_binding
+    rng = np.random.default_rng(n)
+    types = rng.choice(np.array([3, 0, 1, -1], np.int32), n)
+    if packed:
+        frames = rng.integers(0, 2 ** 32, (n, 16), dtype=np.uint64).astype(np.uint32).view(np.int32)
+    else:
+        frames = np.zeros((n, 512), np.uint8)
+        frames[:, :510] = rng.integers(0, 2, (n, 510))
+    dev = torch.device("cuda", 0)
+    d_frames, d_types = torch.from_numpy(frames).to(dev), torch.from_numpy(types).to(dev)
+    for tpsap, blk, rs, kept in ((lb.TPSAP_T_SB1, 1, 120, np.flatnonzero(types == 3)), (lb.TPSAP_T_BBK, 0, 32, np.flatnonzero(types >= 0))):
+        rows = torch.full((n, rs), 7, dtype=torch.uint8, device=dev)
+        valid = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        crow = torch.full((n, rs), 9, dtype=torch.uint8, device=dev)
+        cidx = torch.full((n + 64,), -1, dtype=torch.int32, device=dev)
+        cnt = torch.full((1 + 64,), -1, dtype=torch.int32, device=dev)
+        bb_.demux_device(d_frames, d_types, n, tpsap, blk, rows, rs, valid, packed=packed)
+        bb_.demux_compact_device(d_frames, d_types, n, tpsap, blk, crow, rs, cidx, cnt, packed=packed)
+        torch.cuda.synchronize()
+        idx, c = cidx.cpu().numpy(), cnt.cpu().numpy()
+        assert c[0] == kept.size and (c[1:] == -1).all() and (idx[n:] == -1).all(), (tpsap, c[0], kept.size)
+        assert np.array_equal(idx[:kept.size], kept) and np.array_equal(np.flatnonzero(valid.cpu().numpy()), kept)
+        assert np.array_equal(crow.cpu().numpy()[:kept.size], rows.cpu().numpy()[kept])
+
+
 def _uint_bits(v, n):
     return [(v >> (n - 1 - i)) & 1 for i in range(n)]
 

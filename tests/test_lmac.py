@@ -620,6 +620,46 @@ def test_gpu_decode_frames_all_kinds_in_one_launch(pkg, lref, oracle):
     torch.cuda.synchronize()
 
 
+# frames -> blocks of 256 for the one-workgroup scan of 256 threads (csrc/compact_core.hpp): 1, 1, 1, 2 blocks; 256 = one block per
+# scanning thread; 257 = the first size at which a thread owns two; 258 = runs of two that leave the trailing threads with none
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", (1, 255, 256, 257, 65281, 65536, 65537, 66000))
+def test_gpu_frame_lists_at_the_scan_and_rank_boundaries(pkg, n):
+    """tetra_burst_index_device at the sizes where the block count, the scan of the block counts and the rank inside a block change
+    shape: lists, counts (and at n = 66000 the channels' first entries, 48 frames per channel: no multiple of the block) equal numpy's
+    for random types, all SYNC (every list it belongs to full) and no training sequence at all; nothing is written outside
+    d_lists [4][n], entries at and beyond a count are untouched or in range, and d_work is exactly the documented size."""
+    import torch
+    bb = pkg.bsync_binding
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(1000 + n)
+    F = 48 if n == 66000 else 0
+    G, S = 64, -7                                # guard words on either side, sentinel
+    nwork = 4 * ((n + 255) // 256)
+    for types in (rng.choice(np.array([3, 0, 1, -1], np.int32), n), np.full(n, 3, np.int32), np.full(n, -1, np.int32)):
+        want = [np.flatnonzero(types == 3), np.flatnonzero(types == 0), np.flatnonzero(types == 1), np.flatnonzero(types >= 0)]
+        d_ft = torch.from_numpy(types).to(dev)
+        lists_buf = torch.full((G + 4 * n + G,), S, dtype=torch.int32, device=dev)
+        work_buf = torch.full((G + nwork + G,), S, dtype=torch.int32, device=dev)
+        counts = torch.full((4 + G,), S, dtype=torch.int32, device=dev)
+        chan_first = torch.full((4 * (n // F) + G,), S, dtype=torch.int32, device=dev) if F else None
+        bb.index_device(d_ft, F or 1, lists_buf[G:G + 4 * n].view(4, n), counts, chan_first, d_work=work_buf[G:G + nwork])
+        torch.cuda.synchronize()
+        lists_all, work_all, cnt = lists_buf.cpu().numpy(), work_buf.cpu().numpy(), counts.cpu().numpy()
+        assert (lists_all[:G] == S).all() and (lists_all[G + 4 * n:] == S).all() and (cnt[4:] == S).all()
+        assert (work_all[:G] == S).all() and (work_all[G + nwork:] == S).all()
+        lists = lists_all[G:G + 4 * n].reshape(4, n)
+        for k in range(4):
+            assert cnt[k] == want[k].size and np.array_equal(lists[k, :cnt[k]], want[k]), (n, k)
+            rest = lists[k, cnt[k]:]
+            assert ((rest == S) | ((rest >= 0) & (rest < n))).all(), (n, k)
+        if F:
+            cf = chan_first.cpu().numpy()
+            assert (cf[4 * (n // F):] == S).all()
+            for k in range(4):
+                assert np.array_equal(cf[k * (n // F):(k + 1) * (n // F)], np.searchsorted(want[k], np.arange(0, n, F))), k
+
+
 @pytest.mark.gpu
 def test_gpu_track_sync_lists_equals_the_slot_layout_tracker(pkg, lref):
     """tetra_lmac_track_sync_lists_device (compact SB1 rows) == the host walk (walk_slots) on the same frames in the slot layout, and

@@ -200,6 +200,7 @@ def test_gpu_rx_out_equals_fetch(pkg, synth):
     want = {w: _fetched(rx, w) for w in (0, 1)}
     assert sum(len(b) for b, _ in want[0].values()) > 500
     assert sum(int((b["crc_ok"] == 0).sum()) for b, _ in want[0].values()) > 0          # bad CRCs exist
+    assert any(len(b) > 128 and len(b) % 128 for b, _ in want[0].values())              # a kind of several tiles, the last one partial
     for which in (0, 1):
         for packed in (False, True):
             for crc in (False, True):
