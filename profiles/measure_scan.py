@@ -1,5 +1,6 @@
-"""Times k_find_train_seq on demodulator-sized rows (4096 channels x 36864 bits) with HIP events (torch.cuda.Event on the
-stream the kernel is launched on) and prints achieved HBM GB/s: algorithmic bytes = one byte per scanned position."""
+"""Times k_find_train_seq, then k_ts_indicator, on demodulator-sized rows (4096 channels x 36864 bits) with HIP events
+(torch.cuda.Event on the stream the kernel is launched on) and prints achieved HBM GB/s: algorithmic bytes = one byte per scanned
+position."""
 import json
 import os
 import sys
@@ -35,3 +36,22 @@ for mask, name in ((0x00, "full scan (no sequence enabled: every row is read to 
     print(json.dumps({"kernel": "k_find_train_seq", "case": name, "channels": C, "bits_per_channel": n, "ms": round(ms, 4),
                       "achieved_GBps": round(C * n / ms / 1e6, 1), "frac_of_8TBps": round(C * n / ms / 1e6 / 8000, 4),
                       "found": int((t >= 0).sum())}))
+
+# the indicator on the same rows, every bit of a row in one call (state carried from launch to launch, as in use)
+nb = torch.full((C,), n, dtype=torch.int32, device=dev)
+found = torch.zeros(C, dtype=torch.uint8, device=dev)
+expire = torch.zeros(C, dtype=torch.int32, device=dev)
+ind = pkg.scan_binding.TsIndicator(C)
+for _ in range(3):
+    ind.process_device(bits, stride, nb, found, expire, s)
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+e0.record(s)
+for _ in range(reps):
+    ind.process_device(bits, stride, nb, found, expire, s)
+e1.record(s)
+torch.cuda.synchronize()
+ms = e0.elapsed_time(e1) / reps
+print(json.dumps({"kernel": "k_ts_indicator", "case": "one call per row", "channels": C, "bits_per_channel": n, "ms": round(ms, 4),
+                  "achieved_GBps": round(C * n / ms / 1e6, 1), "frac_of_8TBps": round(C * n / ms / 1e6 / 8000, 4),
+                  "found": int(found.sum())}))
+ind.close()
