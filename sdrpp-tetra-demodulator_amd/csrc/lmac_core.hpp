@@ -340,13 +340,14 @@ LM_FN int interleave_next(int& pos, int a, int K) {
 // (type-4 bits at three consecutive interleaver positions) and returns what make(raw) needs to turn them into branch metrics;
 // st(u, word) receives decision_word of steps 2u, 2u + 1.  The loads of pair u + 1 are issued BEFORE the add-compare-select of pair
 // u and consumed after it (software pipelining by one round): a wavefront that has its SIMD to itself -- the last long blocks of a
-// launch, every wave of a small one -- does not wait for LDS.  n2 is even for every block kind.
+// launch, every wave of a small one -- does not wait for LDS.  n2 is even for every block kind.  s0 = the start metric of state 0,
+// 127 * N * K in the units of the branch metrics: 20 for classes in units of 127, 2540 for raw soft values (soft_core.hpp).
 template <class Fetch, class Make, class St>
-LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st) {
+LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st, int s0 = 4 * 5) {
     PathMetrics pm;
 #pragma unroll
     for (int i = 0; i < 8; ++i) pm.R[i] = pk_make(0, 0);
-    pm.R[0] = pk_make(4 * 5, 0);       // S[0] = 127 * N * K in units of 127
+    pm.R[0] = pk_make(s0, 0);
     auto raw = fetch();
     for (int u = 0; u < n2 / 2; ++u) {
         const Bm m = make(raw);

@@ -42,6 +42,13 @@ struct CellView {
     int32_t cell_words;
 };
 
+struct SoftView {                             // TETRA_RX_FLAG_SOFT (rx_handle.hpp; all null without the flag)
+    float* prev;                              // [2][C][2]: a channel's previous symbol, both parities
+    uint32_t* bits;                           // [2][C]: its absolute bit count
+    int32_t n_channels;
+    float fresh_prev;                         // both components of a fresh channel's previous symbol
+};
+
 RT_HD void zero_f32(float* p, long long n, int lane, int lanes) {
     for (long long i = lane; i < n; i += lanes) p[i] = 0.0f;
 }
@@ -83,6 +90,16 @@ RT_HD void reset_demod_channel(const DemodView& v, int c, int lane, int lanes) {
     zero_f32(v.ybuf + (long long)c * 2 * v.n_ybuf, 2LL * v.n_ybuf, lane, lanes);
     if (v.q_ring) zero_f32(v.q_ring + (long long)c * v.n_q_ring, v.n_q_ring, lane, lanes);
     if (v.cd_blk) zero_f32(v.cd_blk + (long long)c * 2 * v.n_cd, 2LL * v.n_cd, lane, lanes);
+}
+
+// the soft-decision quantiser's carried state of channel c: bit numbering from 0 like the synchroniser's, no previous symbol
+RT_HD void reset_soft_channel(const SoftView& v, int c, int lane, int lanes) {
+    (void)lanes;
+    if (!v.prev || lane >= 2) return;
+    const long long at = (long long)lane * v.n_channels + c;      // lane = parity
+    v.prev[2 * at] = v.fresh_prev;
+    v.prev[2 * at + 1] = v.fresh_prev;
+    v.bits[at] = 0u;
 }
 
 // tetra_bsync_reset for channel c: UNLOCKED, no bits, bit numbering from 0

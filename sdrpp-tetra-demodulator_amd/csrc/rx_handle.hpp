@@ -46,6 +46,14 @@ struct tetra_rx {
     int C = 0, F = 0, rows = 0, stride = 0, kinds = 0;
     bool one_stream = false;
     bool aach_rm = false;                 // TETRA_RX_FLAG_AACH_RM3014: the BBK job decodes with the AACH's Reed-Muller code (tetra_aach.h)
+    // TETRA_RX_FLAG_SOFT (soft_core.hpp): the coded kinds decode from soft values.  All of it lives on the demodulator's stream.
+    bool soft = false;
+    uint32_t soft_R = 0;                  // bits per channel's ring
+    int soft_par = 0;                     // which half of soft_prev / soft_bits the next call reads (it writes the other)
+    DevMem<float> sym;                    // [C][stride / 2] complex64: the call's symbols (one buffer: k_soft reads it behind the demodulator)
+    DevMem<int8_t> soft_ring;             // [C][soft_R]
+    DevMem<float> soft_prev;              // [2][C] complex64: a channel's last symbol
+    DevMem<uint32_t> soft_bits;           // [2][C]: its absolute bit count = the synchroniser's numbering
     Handle<tetra_demod_t*, tetra_demod_destroy> dem;
     Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
     Stream tail;

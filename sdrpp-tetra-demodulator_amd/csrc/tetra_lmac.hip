@@ -32,6 +32,8 @@
 #include "demux_core.hpp"
 #include "hip_host.hpp"
 #include "lmac_core.hpp"
+#include "lmac_impl.hpp"
+#include "soft_core.hpp"
 
 namespace {
 
@@ -254,6 +256,39 @@ struct JobTable {
     DevFrames src;
     int n;
 };
+// a row's verdict and, where the job asks for them, its label
+__device__ __forceinline__ void write_verdict(const DevJob& J, const DevFrames& src, int blk, int f, bool good) {
+    J.crc_ok[blk] = good;
+    if (J.labels) {
+        tetra_lmac_label_t lb;
+        lb.channel = f / src.frames_per_channel;
+        lb.frame_slot = f - lb.channel * src.frames_per_channel;
+        lb.bitnum = src.bitnum[f];
+        lb.tdma_time_rx = src.time_rx[f];
+        lb.tdma_time = src.time[f];
+        lb.crc_ok = good;
+        J.labels[blk] = lb;
+    }
+}
+// the lane's scrambling sequence, words 0 .. (type345 + 31) / 32 (four rows of the table XORed, 16-byte loads; the rest zero)
+__device__ __forceinline__ void lane_sequence(int type345, uint32_t code, const uint32_t* __restrict__ seq_tab, uint32_t seq[kSeqWords]) {
+    const uint4* r0 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)0 * 256 + (code & 0xffu)) * kSeqStride);
+    const uint4* r1 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)1 * 256 + ((code >> 8) & 0xffu)) * kSeqStride);
+    const uint4* r2 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)2 * 256 + ((code >> 16) & 0xffu)) * kSeqStride);
+    const uint4* r3 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)3 * 256 + (code >> 24)) * kSeqStride);
+#pragma unroll
+    for (int g = 0; g < (kSeqWords + 3) / 4; ++g) {
+        uint4 s = make_uint4(0u, 0u, 0u, 0u);
+        if (128 * g < type345) {
+            const uint4 s0 = r0[g], s1 = r1[g], s2 = r2[g], s3 = r3[g];
+            s = make_uint4(s0.x ^ s1.x ^ s2.x ^ s3.x, s0.y ^ s1.y ^ s2.y ^ s3.y, s0.z ^ s1.z ^ s2.z ^ s3.z, s0.w ^ s1.w ^ s2.w ^ s3.w);
+        }
+        const uint32_t w[4] = { s.x, s.y, s.z, s.w };
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * g + k < kSeqWords) seq[4 * g + k] = w[k];
+    }
+}
 // LDS per workgroup: 3584 (type-4 bits; the decoded halves reuse the space once the forward recursion is through with them) + 1024
 // (backward CRC table) = 4608 B <= 5120: LDS never caps the kernel below 8 waves per SIMD -- which matters beside the demodulator:
 // the compiler sizes a kernel's register allocation for the occupancy its LDS allows (6992 B -> 6 waves -> 80 registers where 54 are
@@ -327,23 +362,58 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
         good = decode_core<true>(cls, outw, crc_inv, lane, J.type345, J.type2, J.a, [&](int u, uint32_t w) { dec[u * kLanes] = w; },
                                  [&](int u) { return dec[u * kLanes]; });
     }
-    if (blk < n_blocks) {
-        J.crc_ok[blk] = good;
-        if (J.labels) {
-            tetra_lmac_label_t lb;
-            lb.channel = f / tab.src.frames_per_channel;
-            lb.frame_slot = f - lb.channel * tab.src.frames_per_channel;
-            lb.bitnum = tab.src.bitnum[f];
-            lb.tdma_time_rx = tab.src.time_rx[f];
-            lb.tdma_time = tab.src.time[f];
-            lb.crc_ok = good;
-            J.labels[blk] = lb;
-        }
-    }
+    if (blk < n_blocks) write_verdict(J, tab.src, blk, f, good);
     if (!bbk) {
         __syncthreads();
         write_rows(outw, lane, rows_here, J.type2, J.out + (size_t)blk0 * J.out_stride, J.out_stride);
     }
+}
+
+// ---- the coded kinds from SOFT values (lmac_impl::decode_frames_soft: the receive chain's TETRA_RX_FLAG_SOFT) -----------------------
+// k_lmac_frames with another front end: where that kernel cuts a block's bits out of the packed frame, this one reads the block's soft
+// values from the chain's ring at the frame's absolute bit number, descrambles them by sign and stages them in LDS as bytes
+// (soft_core.hpp); the forward recursion takes its branch metrics from those bytes; traceback, backward CRC, verdict, label and row
+// write-back are the hard route's, unchanged.
+// LDS per workgroup: 27648 (432 staged bytes per lane; the decoded halves reuse the space) + 1024 (backward CRC table) = 28672 B: five
+// workgroups = five waves per CU where the hard kernel's 4608 B allow 32, so beside k_fused this launch keeps at most five decoder waves
+// on a CU and hides the latency of its ring loads with its own unrolled loads rather than with other waves.
+__global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab, uint32_t* __restrict__ dec_scratch, const uint32_t* __restrict__ seq_tab,
+                                                             const uint32_t* __restrict__ ring, uint32_t ring_words) {
+    using namespace tetra_soft;
+    __shared__ union {
+        uint32_t soft[kSoftWords][kLanes];
+        OutW outw;
+    } sm;
+    __shared__ uint32_t crc_inv[256];
+    const int lane = threadIdx.x;
+    int ji = 0;
+    for (int i = 1; i < tab.n; ++i) ji = (int)blockIdx.x >= tab.job[i].first_group ? i : ji;
+    const DevJob& J = tab.job[ji];
+    const int group = (int)blockIdx.x - J.first_group;
+    const int blk0 = group * kLanes, blk = blk0 + lane;
+    int n_blocks = J.n_rows;
+    if (J.n_rows_dev) {
+        const int have = *J.n_rows_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
+    }
+    if (blk0 >= n_blocks) return;
+    const int rows_here = min(kLanes, n_blocks - blk0);
+    const int f = min(max(J.row_frame[blk < n_blocks ? blk : blk0], 0), tab.src.n_frames - 1);
+    const uint32_t code = J.frame_scramb ? J.frame_scramb[f] : kScrambInitSb1;
+    const uint32_t* chan = ring + (size_t)(f / tab.src.frames_per_channel) * ring_words;
+    uint32_t seq[kSeqWords];
+    lane_sequence(J.type345, code, seq_tab, seq);
+    stage_block(J.layout, tab.src.bitnum[f], tab.src.frame_type[f], [&](uint32_t w) { return chan[w]; }, 4u * ring_words - 1u, seq,
+                [&](int g, uint32_t word) { sm.soft[g][lane] = word; });
+    load_crc_inv(crc_inv, lane);
+    __syncthreads();
+    uint32_t* dec = dec_scratch + J.scratch_base + (size_t)group * J.dec_pairs * kLanes + lane;
+    forward(J.type345, J.type2, J.a, [&](int w) { return sm.soft[w][lane]; }, [&](int u, uint32_t w) { dec[u * kLanes] = w; });
+    const bool good = viterbi_traceback(J.type2, [&](int u) { return dec[u * kLanes]; }, [&](int h, uint32_t half) { sm.outw[h][lane] = (uint16_t)half; },
+                                        [&](uint32_t off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(crc_inv) + off); });
+    if (blk < n_blocks) write_verdict(J, tab.src, blk, f, good);
+    __syncthreads();
+    write_rows(sm.outw, lane, rows_here, J.type2, J.out + (size_t)blk0 * J.out_stride, J.out_stride);
 }
 
 // Per-device constant of the decoder's packed route: the scrambling-sequence table (64 KB), built on the host once per device and
@@ -638,7 +708,8 @@ int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blo
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
-int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
+// tetra_lmac_decode_frames_device, and with `soft` lmac_impl::decode_frames_soft: the same job table, the soft kernel
+static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const lmac_impl::SoftRing* soft, void* hip_stream) {
     if (!src || !jobs || n_jobs < 0 || n_jobs > TETRA_LMAC_MAX_JOBS) return TETRA_ERR_ARG;
     if (n_jobs == 0) return TETRA_OK;
     if (!src->d_frames || !src->d_frame_type || src->n_frames < 0) return TETRA_ERR_ARG;
@@ -670,6 +741,7 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
         if (layout == kLayoutNone) return TETRA_ERR_ARG;       // no burst type carries this (kind, block number)
         const BlkParam& p = kBlk[j.type];
         const bool bbk = layout == kLayoutBbk || layout == kLayoutBbkRm;
+        if (soft && bbk) return TETRA_ERR_ARG;                 // the AACH has no soft route
         any_rm = any_rm || rm;
         if (j.out_stride < (bbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
         if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
@@ -714,7 +786,10 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
             pooled = true;
         }
     }
-    if (any_rm) {
+    if (soft) {
+        hipLaunchKernelGGL(k_lmac_frames_soft, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq,
+                           reinterpret_cast<const uint32_t*>(soft->d_ring), soft->size / 4u);
+    } else if (any_rm) {
         const uint32_t* rm_tab = rm3014_table();
         if (!rm_tab) { if (pooled) (void)hipFreeAsync(scratch, s); return TETRA_ERR_NOMEM; }
         hipLaunchKernelGGL(k_lmac_frames<true>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq, rm_tab);
@@ -724,6 +799,10 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
     const hipError_t launch = hipGetLastError();
     if ((pooled && hipFreeAsync(scratch, s) != hipSuccess) || launch != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
+}
+
+int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
+    return decode_frames(src, jobs, n_jobs, nullptr, hip_stream);
 }
 
 size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {
@@ -839,3 +918,10 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
 }
 
 }  // extern "C"
+
+int lmac_impl::decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream) {
+    // a ring of whole aligned words, a power of two in size; the frames' bit numbers and channels
+    if (!ring.d_ring || ring.size < 4 || (ring.size & (ring.size - 1)) || ((uintptr_t)ring.d_ring & 3)) return TETRA_ERR_ARG;
+    if (src && (!src->d_frame_bitnum || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
+    return decode_frames(src, jobs, n_jobs, &ring, hip_stream);
+}

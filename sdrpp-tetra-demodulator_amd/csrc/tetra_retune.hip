@@ -22,16 +22,18 @@
 #include "retune_core.hpp"
 #include "retune_impl.hpp"
 #include "rx_handle.hpp"
+#include "soft_core.hpp"
 #include "wbrx_handle.hpp"
 
 namespace {
 
 constexpr int kLanes = 64;
 
-__global__ __launch_bounds__(kLanes) void k_reset_demod(retune::DemodView v, const int32_t* __restrict__ channels, int n_channels) {
+__global__ __launch_bounds__(kLanes) void k_reset_demod(retune::DemodView v, retune::SoftView soft, const int32_t* __restrict__ channels, int n_channels) {
     const int c = channels[blockIdx.x];
     if (c < 0 || c >= n_channels) return;          // (the host has checked the list)
     retune::reset_demod_channel(v, c, threadIdx.x, kLanes);
+    retune::reset_soft_channel(soft, c, threadIdx.x, kLanes);
 }
 
 __global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retune::CellView cell, const int32_t* __restrict__ channels, int n_channels) {
@@ -84,9 +86,12 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     if (h->reset_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_reset, 0));        // an earlier reset, possibly given another stream
     if (h->calls > 0) {
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_demod[last], 0));
-        if (h->one_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[last], 0));
+        // (soft decisions: a reset channel's bit numbering restarts, so the next call's soft values land anywhere in its ring -- where the
+        //  last call's tail may still be reading: the reset, and with it that call, waits for the tail)
+        if (h->one_stream || h->soft) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[last], 0));
     }
-    hipLaunchKernelGGL(k_reset_demod, dim3((unsigned)n), dim3(kLanes), 0, s, dv, d_channels, h->C);
+    const retune::SoftView sv = { h->soft_prev.get(), h->soft_bits.get(), h->C, tetra_soft::kFreshPrev };
+    hipLaunchKernelGGL(k_reset_demod, dim3((unsigned)n), dim3(kLanes), 0, s, dv, sv, d_channels, h->C);
     HIP_TRY(h, hipGetLastError());
     if (!h->one_stream) {
         HIP_TRY(h, hipEventRecord(h->ev_reset, s));

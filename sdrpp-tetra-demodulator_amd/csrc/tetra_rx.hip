@@ -13,6 +13,9 @@
 //                           per-slot codes and labels every row (channel, slot, bit number, times, crc)            (event T_k)
 //
 // so the demodulator of call k+1 runs beside the tail of call k; results and bit rows are double buffered by call parity.
+// With TETRA_RX_FLAG_SOFT the demodulator also writes its symbols, k_soft (below) follows it on the caller's stream in front of D_k and
+// leaves the call's soft values in the channels' rings, and the tail decodes SB1 and the other coded kinds from those rings
+// (lmac_impl::decode_frames_soft) with the AACH in a launch of its own: 9 launches (soft_core.hpp).
 // (Until round 6: per kind a compacting demultiplexer into byte rows (4 launches), a counted decode and a label kernel -- 40 launches
 // and 0.36 GB of byte rows per second of 4096 channels; now 7 launches and no byte rows.)
 #include <hip/hip_runtime.h>
@@ -20,12 +23,39 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "../../include/tetra_aach.h"
 #include "../../include/tetra_rx.h"
+#include "lmac_impl.hpp"
 #include "rx_handle.hpp"
+#include "soft_core.hpp"
 
 namespace {
+
+// TETRA_RX_FLAG_SOFT: the call's symbols -> soft values in the channels' rings (soft_core.hpp), a thread per symbol.  A channel's
+// carried state (previous symbol, absolute bit count) is read at `in` and written at `out`, the other parity: one launch, and no
+// workgroup reads what another one writes.  The demodulator delivers whole symbols, so a channel's bit count is even and a symbol's two
+// soft values are one aligned 2-byte store.
+__global__ __launch_bounds__(256) void k_soft(const float2* __restrict__ sym, int sym_stride, const int32_t* __restrict__ n_bits,
+                                              const float2* __restrict__ prev_in, const uint32_t* __restrict__ bits_in, float2* __restrict__ prev_out,
+                                              uint32_t* __restrict__ bits_out, int8_t* __restrict__ ring, uint32_t ring_size) {
+    const int c = blockIdx.y, k = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const float2* z = sym + (size_t)c * sym_stride;
+    const int n = min(max(n_bits[c] >> 1, 0), sym_stride);
+    const uint32_t count = bits_in[c];
+    const float2 pv = prev_in[c];
+    if (k == 0) {
+        bits_out[c] = count + 2u * (uint32_t)n;
+        prev_out[c] = n > 0 ? z[n - 1] : pv;
+    }
+    if (k >= n) return;
+    const float2 s = z[k], p = k > 0 ? z[k - 1] : pv;
+    int q0, q1;
+    tetra_soft::soft_pair(s.x, s.y, p.x, p.y, q0, q1);
+    const uint32_t at = (count + 2u * (uint32_t)k) & (ring_size - 1u) & ~1u;
+    *reinterpret_cast<uint16_t*>(ring + (size_t)c * ring_size + at) = (uint16_t)((q0 & 0xff) | ((q1 & 0xff) << 8));
+}
 
 // the type-1 bits of the first n rows, packed: out[j][0 .. nb) = t2[j][0 .. nb) (two bytes per thread: every kind's count is even)
 __global__ __launch_bounds__(256) void k_rx_pack_type1(const uint8_t* __restrict__ t2, int in_stride, int nb, int n, uint8_t* __restrict__ out) {
@@ -48,6 +78,11 @@ int zero_results(tetra_rx* h) {
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->counts[b], 0, sizeof(int32_t) * TETRA_N_LISTS));
     HIP_TRY(h, hipMemset(h->cell, 0, sizeof(tetra_lmac_cell_state_t) * (size_t)h->C));
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->nbits[b], 0, sizeof(int32_t) * (size_t)h->C));
+    if (h->soft) {      // fresh channels: previous symbol (1,1)/sqrt(2), bit count 0 (both parities: the next call reads either)
+        const std::vector<float> prev((size_t)4 * h->C, tetra_soft::kFreshPrev);
+        HIP_TRY(h, hipMemcpy(h->soft_prev, prev.data(), sizeof(float) * prev.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemset(h->soft_bits, 0, sizeof(uint32_t) * 2 * (size_t)h->C));
+    }
     return TETRA_OK;
 }
 
@@ -68,6 +103,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     src.d_time = h->row_time;
     src.d_workspace = h->lmac_ws;
     src.workspace_bytes = h->lmac_ws.bytes();
+    const lmac_impl::SoftRing ring = { h->soft_ring, h->soft_R };
     auto job_of = [&](int k, bool labels) {
         const KindInfo& ki = kKinds[k];
         const KindBufs& r = h->res[b][k];
@@ -87,7 +123,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     {   // SB1 first: its SYNC PDUs set the code and the clock for everything else in the same burst (tetra_lower_mac.c:246-275)
         const KindBufs& r = h->res[b][TETRA_RX_KIND_SB1];
         const tetra_lmac_job_t j = job_of(TETRA_RX_KIND_SB1, false);
-        TETRA_TRY(tetra_lmac_decode_frames_device(&src, &j, 1, s));
+        TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s) : tetra_lmac_decode_frames_device(&src, &j, 1, s));
         TETRA_TRY(tetra_lmac_track_sync_lists_device(r.t2, kKinds[TETRA_RX_KIND_SB1].out_stride, r.ok, h->ft, h->nf,
                                                  h->chan_first + (size_t)TETRA_LIST_SYNC * h->C, h->C, h->F, h->cell, h->row_scramb, h->row_time_rx,
                                                  h->row_time, h->fb, reinterpret_cast<tetra_lmac_label_t*>(r.blocks.get()), s));
@@ -96,7 +132,12 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     tetra_lmac_job_t jobs[TETRA_RX_N_KINDS];
     int nj = 0;
     for (int k : kJobOrder)
-        if (h->kinds & (1 << k)) jobs[nj++] = job_of(k, true);
+        if ((h->kinds & (1 << k)) && !(h->soft && k == TETRA_RX_KIND_BBK)) jobs[nj++] = job_of(k, true);
+    if (h->soft) {      // the coded kinds from the ring; the AACH from the packed frames as ever, a launch of its own
+        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s));
+        nj = 0;
+        if (h->kinds & (1 << TETRA_RX_KIND_BBK)) jobs[nj++] = job_of(TETRA_RX_KIND_BBK, true);
+    }
     TETRA_TRY(tetra_lmac_decode_frames_device(&src, jobs, nj, s));
     HIP_TRY(h, hipEventRecord(h->ev_stage[3], s));
     return TETRA_OK;
@@ -125,7 +166,7 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014)))
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT)))
         return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
@@ -134,6 +175,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     h->kinds = (cfg->kinds ? cfg->kinds : (1 << TETRA_RX_N_KINDS) - 1) | (1 << TETRA_RX_KIND_SB1);
     h->one_stream = (cfg->flags & TETRA_RX_FLAG_ONE_STREAM) != 0;
     h->aach_rm = (cfg->flags & TETRA_RX_FLAG_AACH_RM3014) != 0;
+    h->soft = (cfg->flags & TETRA_RX_FLAG_SOFT) != 0;
     TETRA_TRY(tetra_demod_create(&cfg->demod, h->dem.put()));
     h->C = cfg->demod.n_channels;
     int dev = cfg->demod.device;
@@ -168,6 +210,11 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
          dalloc(h->chan_first, (size_t)TETRA_N_LISTS * h->C) && dalloc(h->index_work, (size_t)TETRA_N_LISTS * ((n + 255) / 256)) &&
          dalloc(h->row_scramb, n) && dalloc(h->row_time_rx, n) && dalloc(h->row_time, n) && dalloc(h->cell, (size_t)h->C);
     for (auto& e : h->ev_stage) ok = ok && hipEventCreate(e.put()) == hipSuccess;
+    if (ok && h->soft) {
+        h->soft_R = tetra_soft::ring_size(h->stride);
+        ok = dalloc(h->sym, (size_t)h->C * h->stride) && dalloc(h->soft_ring, (size_t)h->C * h->soft_R) && dalloc(h->soft_prev, (size_t)4 * h->C) &&
+             dalloc(h->soft_bits, (size_t)2 * h->C) && hipMemset(h->soft_ring, 0, (size_t)h->C * h->soft_R) == hipSuccess;
+    }
     if (ok) {      // the decision scratch of the two decode launches (they run one after the other), sized for the worst case (every frame slot a row of every kind)
         tetra_lmac_job_t jobs[TETRA_RX_N_KINDS] = {};
         int nj = 0;
@@ -202,6 +249,7 @@ int tetra_rx_reset(tetra_rx_t* h) {
     TETRA_TRY(tetra_bsync_reset(h->bs));
     TETRA_TRY(zero_results(h));
     h->calls = 0;
+    h->soft_par = 0;
     h->stage_valid = false;
     for (bool& p : h->out_pending) p = false;          // (the device is idle: every delivery has completed)
     for (long long& c : h->ring_call) c = -1;
@@ -223,7 +271,16 @@ int tetra_rx_process_device(tetra_rx_t* h, const float* d_iq, int n_samples, voi
         HIP_TRY(h, hipStreamWaitEvent(sa, h->ev_reset, 0));
         h->reset_pending = false;
     }
-    TETRA_TRY(tetra_demod_process_device(h->dem, d_iq, n_samples, h->bits[b], h->stride, h->nbits[b], nullptr, sa));
+    TETRA_TRY(tetra_demod_process_device(h->dem, d_iq, n_samples, h->bits[b], h->stride, h->nbits[b], h->soft ? h->sym.get() : nullptr, sa));
+    if (h->soft) {      // behind the demodulator, in front of ev_demod: the tail finds the call's soft values in the ring
+        const int p = h->soft_par, sym_stride = h->stride / 2;
+        hipLaunchKernelGGL(k_soft, dim3((unsigned)((sym_stride + 255) / 256), (unsigned)h->C), dim3(256), 0, sa, reinterpret_cast<const float2*>(h->sym.get()),
+                           sym_stride, h->nbits[b].get(), reinterpret_cast<const float2*>(h->soft_prev.get()) + (size_t)p * h->C, h->soft_bits + (size_t)p * h->C,
+                           reinterpret_cast<float2*>(h->soft_prev.get()) + (size_t)(p ^ 1) * h->C, h->soft_bits + (size_t)(p ^ 1) * h->C, h->soft_ring.get(),
+                           h->soft_R);
+        HIP_TRY(h, hipGetLastError());
+        h->soft_par = p ^ 1;
+    }
     HIP_TRY(h, hipEventRecord(h->ev_demod[b], sa));
     if (!h->one_stream) HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_demod[b], 0));
     h->calls++;                     // the call exists from here on: a failing tail leaves its rows undefined, not the bookkeeping

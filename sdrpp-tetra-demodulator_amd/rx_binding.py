@@ -13,6 +13,7 @@ KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
 N_KINDS = 6
 FLAG_ONE_STREAM = 1
 FLAG_AACH_RM3014 = 2          # TETRA_RX_FLAG_AACH_RM3014
+FLAG_SOFT = 8                 # TETRA_RX_FLAG_SOFT: the coded kinds decoded from soft values (4 is no flag)
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
 
