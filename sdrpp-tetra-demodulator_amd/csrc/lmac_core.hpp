@@ -1,8 +1,12 @@
 // lmac_core.hpp -- lane-level code of the batched lower-MAC channel decoder (include/tetra_lmac.h).
 //
-// One lane decodes one block.  The same source is compiled twice: by hipcc into the gfx950 kernel (tetra_lmac.hip, the
-// accessors hit LDS) and by g++ (-DTETRA_HOST_EMUL) into tests/emul, where it is checked against the reference-built
-// primitives without a GPU.  Everything is integer work, so "same source" means "same results".
+// One lane decodes one block.  The same source is compiled twice: by hipcc into the gfx950 kernels (tetra_lmac.hip, the
+// accessors hit LDS and global memory) and by g++ (-DTETRA_HOST_EMUL) into tests/emul, where it is checked against the
+// reference-built primitives without a GPU.  Everything is integer work, so "same source" means "same results".  What the
+// kernels share with the emulation: the block table and layout map (blk_param, layout_for), the cooperative front end of byte
+// rows (needs_byte_route, pack_units, staged_row) and its byte route (descramble_chunk), the scrambling sequence (lane_sequence,
+// descramble_words), the blocks cut from packed frames (frame_block, bbk_bits), forward recursion + traceback + CRC
+// (decode_hard; soft_core.hpp's decode_soft ends in the same traceback) and the write-back of both row widths (write_rows).
 //
 // Restated from the reference (src/decoder/src/lower_mac/), not copied:
 //   * scrambler        tetra_scramb.c:34-51 (Fibonacci LFSR, taps 32 26 23 22 16 12 11 10 8 7 5 4 2 1, shifts right, new
@@ -50,6 +54,18 @@ constexpr uint32_t kCrcOk = 0x1d0f;      // TETRA_CRC_OK, tetra_common.h:330
 constexpr int kFlush = 4;                // K - 1
 constexpr int kMaxType345 = 432;
 constexpr int kMaxType2 = 288;
+
+// tetra_blk_param[], tetra_lower_mac.c:58-105 (values of EN 300 392-2 table 8.x / 8.2.4.1), by TETRA_TPSAP_T_*
+struct BlkParam { int type345, type2, type1, a, crc; };
+constexpr BlkParam kBlkParam[6] = {
+    { 120, 80, 60, 11, 1 },     // SB1
+    { 216, 144, 124, 101, 1 },  // SB2
+    { 216, 144, 124, 101, 1 },  // NDB
+    { 30, 30, 14, 0, 0 },       // BBK
+    { 168, 112, 92, 13, 1 },    // SCH/HU
+    { 432, 288, 268, 103, 1 },  // SCH/F
+};
+constexpr const BlkParam& blk_param(int type) { return kBlkParam[type]; }
 
 LM_FN uint32_t lfsr_next(uint32_t& lfsr) {
     const uint32_t bit = (uint32_t)__builtin_popcount(lfsr & kScrambTaps) & 1u;
@@ -132,33 +148,70 @@ inline void scramb_sequence_table(uint32_t* tab) {       // [4][256][kSeqStride]
 LM_FN uint32_t pack4(uint32_t v) { return (v * 0x08040201u) >> 24; }
 
 struct U2 { uint32_t x, y; };
-// Packs the lane's own row, bytes -> bits; ld8(i) returns bytes 8i..8i+7 of the row.  Returns non-zero if any byte of the row is
-// not 0 / 1 (then the byte route has to decode the row).  type345 is a multiple of 8 for every coded block kind.
-template <class Ld8>
-LM_FN uint32_t pack_row_bits(int type345, Ld8 ld8, uint32_t xb[kSeqWords]) {
+struct U4 { uint32_t x, y, z, w; };
+constexpr int kLanes = 64;                 // a workgroup is one wavefront, a block per lane
+constexpr int kChunkDwords = 16;           // 64 type-5 bits per row per staging chunk
+constexpr int kStageWords = kChunkDwords + 1;      // a staged row; odd: conflict-free column reads
+constexpr int kClsWords = (kMaxType345 + 15) / 16;     // 27: a block as soft classes, 16 per word (descramble_chunk)
+
+// q = i / units by a multiply and a shift, for the flattened (row, unit) index spaces of the front end and the write-back.  Exact for
+// every units <= 64 and i < 64 * units (tests/test_lmac.py checks that whole domain against the division).
+LM_FN uint32_t unit_inverse(int units) { return ((1u << 20) + (uint32_t)units - 1u) / (uint32_t)units; }
+LM_FN int unit_row(int i, uint32_t inv) { return (int)(((uint32_t)i * inv) >> 20); }
+// rows that 8-byte accesses can address
+LM_FN bool rows_wide(const void* p, int stride) { return !(stride & 7) && !((uintptr_t)p & 7); }
+// The packed front end is not for this launch: no sequence table (the byte route forced), rows that are not 8-byte aligned, or rows that
+// do not fit the unit -> row map (64 units).
+LM_FN bool needs_byte_route(const void* seq_tab, const void* p, int stride) { return seq_tab == nullptr || (stride & 7) || ((uintptr_t)p & 7) || stride > 512; }
+
+// The cooperative front end, the lane's share.  The workgroup's rows_here rows are one contiguous run of rows_here * in_stride bytes:
+// it is read ONCE, 8 bytes per lane and 512 contiguous bytes per load instruction (ld8(u) = bytes 8u .. 8u+7 of the run); each unit's
+// 8 bytes become 8 bits, dropped as one byte into the row's packed words (st(at, byte): byte `at` of the staged words
+// [kLanes][kStageWords]).  Returns non-zero if any byte the lane met is not 0 / 1: then the whole workgroup has to take the byte route.
+template <class Ld8, class St>
+LM_FN uint32_t pack_units(int lane, int rows_here, int in_stride, int type345, Ld8 ld8, St st) {
+    const int units_per_row = in_stride >> 3, total_units = rows_here * units_per_row;
+    const uint32_t inv = unit_inverse(units_per_row);
     uint32_t dirty = 0;
-#pragma unroll
-    for (int w = 0; w < kSeqWords; ++w) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (32 * w + 8 * q < type345) {
-                const U2 d = ld8(4 * w + q);
-                dirty |= (d.x | d.y) & 0xfefefefeu;
-                v |= ((pack4(d.x) << 4) | pack4(d.y)) << (24 - 8 * q);
-            }
+    for (int u = lane; u < total_units; u += kLanes) {
+        const int r = unit_row(u, inv), j = u - r * units_per_row;      // row, byte of its packed bits
+        if (8 * j < type345) {
+            const U2 d = ld8(u);
+            dirty |= (d.x | d.y) & 0xfefefefeu;
+            // type-5 bits 8j .. 8j+7, first bit most significant; byte j of the row's bit string sits in word j / 4 at bits 31 - 8 (j % 4) ..
+            st((size_t)r * (4 * kStageWords) + (j & ~3) + (3 - (j & 3)), (uint8_t)((pack4(d.x) << 4) | pack4(d.y)));
         }
-        xb[w] = v;
     }
     return dirty;
 }
-// Descrambles the packed row: seq(t, byte, w) = seq_tab[t][byte][w]; st(w, word) = type-4 bits 32w..32w+31.
-template <class Seq, class St>
-LM_FN void descramble_bits(int type345, uint32_t code, const uint32_t xb[kSeqWords], Seq seq, St st) {
+// ... then every lane picks up its own row: ld(w) = staged word w of the lane's row (bytes behind the row's last bit were never written)
+template <class Ld>
+LM_FN void staged_row(int type345, Ld ld, uint32_t xb[kSeqWords]) {
 #pragma unroll
-    for (int w = 0; w < kSeqWords; ++w)
-        if (32 * w < type345)
-            st(w, xb[w] ^ seq(0, code & 0xffu, w) ^ seq(1, (code >> 8) & 0xffu, w) ^ seq(2, (code >> 16) & 0xffu, w) ^ seq(3, code >> 24, w));
+    for (int w = 0; w < kSeqWords; ++w) xb[w] = 32 * w < type345 ? ld(w) : 0u;
+    if (type345 & 31) xb[type345 >> 5] &= ~(0xffffffffu >> (type345 & 31));
+}
+// The lane's scrambling sequence: the four table rows the code's bytes select, XORed.  rows(t, byte)[g] = words 4g .. 4g+3 of
+// seq_tab[t][byte] as .x .y .z .w (one 16-byte load on the device); st(w, word) receives every word of the groups the block reaches,
+// a group that no bit of it reaches is not loaded.
+template <class Rows, class St>
+LM_FN void lane_sequence(int type345, uint32_t code, Rows rows, St st) {
+    const auto r0 = rows(0, code & 0xffu), r1 = rows(1, (code >> 8) & 0xffu), r2 = rows(2, (code >> 16) & 0xffu), r3 = rows(3, code >> 24);
+#pragma unroll
+    for (int g = 0; g < (kSeqWords + 3) / 4; ++g) {
+        if (128 * g < type345) {
+            const auto s0 = r0[g], s1 = r1[g], s2 = r2[g], s3 = r3[g];
+            const uint32_t w[4] = { s0.x ^ s1.x ^ s2.x ^ s3.x, s0.y ^ s1.y ^ s2.y ^ s3.y, s0.z ^ s1.z ^ s2.z ^ s3.z, s0.w ^ s1.w ^ s2.w ^ s3.w };
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < kSeqWords) st(4 * g + k, w[k]);
+        }
+    }
+}
+// the packed rows' descrambling: st(w, word) = type-4 bits 32w .. 32w+31, for the words the block reaches
+template <class Rows, class St>
+LM_FN void descramble_words(int type345, uint32_t code, const uint32_t xb[kSeqWords], Rows rows, St st) {
+    lane_sequence(type345, code, rows, [&](int w, uint32_t word) { if (32 * w < type345) st(w, xb[w] ^ word); });
 }
 
 // ---- blocks straight from the burst synchroniser's packed frames (16 words, first bit most significant) ---------------------------
@@ -191,6 +244,18 @@ LM_FN void extract_block(const uint32_t fw[kFrameWords], int off0, int len0, int
 // where a kind's bits sit in its burst (demux_core::pieces_for), as literal layouts so that every shift is a constant
 enum { kLayoutSb1 = 0, kLayoutSb2, kLayoutNdb1, kLayoutNdb2, kLayoutSchF, kLayoutBbk, kLayoutNone,
        kLayoutBbkRm };      // the AACH decoded with its Reed-Muller code (only the kernel's RM instantiation meets it)
+// the layout of block blk_num of a kind in the downlink burst that carries it; kLayoutNone: no burst carries this (kind, block number)
+// (SCH/HU is an uplink block)
+constexpr int layout_for(int tpsap, int blk_num, bool rm) {
+    switch (tpsap) {
+        case TETRA_TPSAP_T_SB1: return blk_num == 1 ? kLayoutSb1 : kLayoutNone;
+        case TETRA_TPSAP_T_SB2: return blk_num == 2 ? kLayoutSb2 : kLayoutNone;
+        case TETRA_TPSAP_T_NDB: return blk_num == 1 ? kLayoutNdb1 : blk_num == 2 ? kLayoutNdb2 : kLayoutNone;
+        case TETRA_TPSAP_T_BBK: return rm ? kLayoutBbkRm : kLayoutBbk;
+        case TETRA_TPSAP_T_SCH_F: return kLayoutSchF;
+        default: return kLayoutNone;
+    }
+}
 template <int TRAIN, int TPSAP, int BLK>
 LM_FN void cut(const uint32_t fw[kFrameWords], int frame_type, uint32_t xb[kSeqWords]) {
     const demux_core::Pieces p = demux_core::pieces_for(TRAIN, TPSAP, BLK);
@@ -452,6 +517,63 @@ LM_FN bool viterbi_traceback(int n2, Ld ld, St st, Tinv tinv) {
 
 // 4 decoded bits -> 4 bytes (one bit per byte, little endian)
 LM_FN uint32_t spread4(uint32_t nib) { return (nib * 0x00204081u) & 0x01010101u; }
+
+// Steps 2-3 for a lane whose type-4 bits (BITS: bit i at bit 31 - (i & 31) of word i >> 5) or soft classes (16 per word, descramble_chunk)
+// are behind cls(word).  io = the lane's other memory: dec_st(u, word) / dec_ld(u) its decision word of step pair u, out_st(h, half)
+// its decoded bits 16h .. 16h+15, tinv(off) the backward CRC table.  Returns the lane's CRC verdict.
+template <class Io>
+LM_FN bool traceback(int type2, Io& io) {        // (own lane's data only: program order is enough)
+    return viterbi_traceback(type2, [&](int u) { return io.dec_ld(u); }, [&](int h, uint32_t half) { io.out_st(h, half); },
+                             [&](uint32_t off) { return io.tinv(off); });
+}
+template <bool BITS, class Cls, class Io>
+LM_FN bool decode_hard(int type345, int type2, int a, Cls cls, Io& io) {
+    int pos = a;                       // (a * i) % K for i = 1
+    auto fetch = [&] {
+        Raw3 r;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int p = interleave_next(pos, a, type345);
+            r.w[k] = cls(BITS ? p >> 5 : p >> 4);
+            r.at[k] = BITS ? 31u - (uint32_t)(p & 31) : (uint32_t)(30 - 2 * (p & 15));
+        }
+        return r;
+    };
+    auto dec_st = [&](int u, uint32_t w) { io.dec_st(u, w); };
+    if (BITS) {
+        viterbi_forward(type2, fetch,
+                        [&](const Raw3& r) { return bm_from_masks(bfe_mask(r.w[0], r.at[0]), bfe_mask(r.w[1], r.at[1]), bfe_mask(r.w[2], r.at[2])); },
+                        dec_st);
+    } else {
+        viterbi_forward(type2, fetch,
+                        [&](const Raw3& r) { return bm_from_classes((int)(r.w[0] << r.at[0]) >> 30, (int)(r.w[1] << r.at[1]) >> 30, (int)(r.w[2] << r.at[2]) >> 30); },
+                        dec_st);
+    }
+    return traceback(type2, io);
+}
+
+// Step 4: the workgroup's decoded rows -> memory, the lane's share; half(h, q) = decoded bits 16h .. 16h+15 of row q.  WIDE (rows_wide):
+// 8 bits -> 8 bytes per store, st8(q, d, v) = bytes 8d .. 8d+7 of row q, the (row, unit) index space flattened so that every lane
+// stores in every round; otherwise st4(q, d, v) = bytes 4d .. 4d+3, row by row.
+template <class Half, class St8, class St4>
+LM_FN void write_rows(int lane, int rows_here, int type2, bool wide, Half half, St8 st8, St4 st4) {
+    if (wide) {
+        const int units = type2 >> 3, total = rows_here * units;
+        const uint32_t inv = unit_inverse(units);
+        for (int i = lane; i < total; i += kLanes) {
+            const int q = unit_row(i, inv), d = i - q * units;
+            const uint32_t byte = ((uint32_t)half(d >> 1, q) >> (8 * (d & 1))) & 0xffu;
+            demux_core::U2 v;
+            v.x = spread4(byte & 0xfu);
+            v.y = spread4(byte >> 4);
+            st8(q, d, v);
+        }
+    } else {
+        const int out_dw = type2 >> 2;
+        for (int q = 0; q < rows_here; ++q)
+            for (int d = lane; d < out_dw; d += kLanes) st4(q, d, spread4(((uint32_t)half(d >> 2, q) >> (4 * (d & 3))) & 0xfu));
+    }
+}
 
 // ---- SB1 tracking (tetra_lmac_track_*_device): the SYNC PDU, the scrambling code and the TDMA clock -------------------------------
 // Host and device: tetra_lmac_scramb_init and the tracker kernel use the same source.

@@ -128,5 +128,11 @@ LM_FN void forward(int type345, int type2, int a, Ld ld, DecSt dec_st) {
                     },
                     dec_st, kStartMetric);
 }
+// steps 2-3 of the soft route: the forward recursion above, then the hard route's traceback (io: as decode_hard's)
+template <class Ld, class Io>
+LM_FN bool decode_soft(int type345, int type2, int a, Ld ld, Io& io) {
+    forward(type345, type2, a, ld, [&](int u, uint32_t w) { io.dec_st(u, w); });
+    return traceback(type2, io);
+}
 
 }  // namespace tetra_soft

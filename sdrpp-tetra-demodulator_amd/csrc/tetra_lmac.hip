@@ -1,7 +1,10 @@
 // tetra_lmac.hip -- batched lower-MAC channel decoding (include/tetra_lmac.h), bit-exact with the reference's
 // tp_sap_udata_ind() decoding chain (src/decoder/src/lower_mac/tetra_lower_mac.c:181-236).
 //
-// One 64-lane workgroup (one wavefront) decodes 64 blocks, one block per lane (lane-level code: lmac_core.hpp):
+// One 64-lane workgroup (one wavefront) decodes 64 blocks, one block per lane.  Everything a lane computes is lane-level code in
+// lmac_core.hpp (soft_core.hpp for the soft front end) -- pack_units / staged_row, descramble_chunk, lane_sequence / descramble_words,
+// decode_hard / decode_soft, write_rows -- where tests/emul runs the same source on the host; this file holds the kernels' LDS and
+// global-memory accessors, the barriers, and the host side.
 //   1. front end -> the descrambled type-4 bits of the lane's block as packed words in LDS, [word][lane]:
 //      * from PACKED FRAMES (k_lmac_frames, round 6): the lane reads its frame (four 16-byte loads), cuts the kind's one or two bit
 //        ranges out with funnel shifts and XORs whole words of its scrambling sequence (linear in the code: four rows of a 64 KB
@@ -39,57 +42,25 @@ namespace {
 
 using namespace tetra_lmac;
 
-constexpr int kLanes = 64;
-constexpr int kChunkDwords = 16;                       // 64 type-5 bits per row per staging chunk
-constexpr int kSteps = kMaxType2 + kFlush;             // 292
-constexpr int kClsWords = (kMaxType345 + 15) / 16;     // 27
 constexpr int kOutHalves = kMaxType2 / 16;             // 18
 constexpr int kOutPad = 2;                             // outw rows of 66 ushorts = 33 banks: the write-back's column reads do not collide
 bool g_force_byte_route = false;                       // tests / A-B: tetra_lmac_debug_force_byte_route
 __constant__ CrcInvTable kCrcInvDev = make_crc_inv_table();      // the traceback's backward CRC table; every workgroup copies it to LDS
 
-struct BlkParam { int type345, type2, type1, a, crc; };
-// tetra_blk_param[], tetra_lower_mac.c:58-105 (values of EN 300 392-2 table 8.x / 8.2.4.1)
-const BlkParam kBlk[6] = {
-    { 120, 80, 60, 11, 1 },     // SB1
-    { 216, 144, 124, 101, 1 },  // SB2
-    { 216, 144, 124, 101, 1 },  // NDB
-    { 30, 30, 14, 0, 0 },       // BBK
-    { 168, 112, 92, 13, 1 },    // SCH/HU
-    { 432, 288, 268, 103, 1 },  // SCH/F
-};
-
 typedef uint16_t OutW[kOutHalves][kLanes + kOutPad];
 
-// steps 2-3 for a workgroup whose type-4 bits (BITS) or soft classes are in `cls`; dec_st(u, word) / dec_ld(u) = the lane's decision
-// word of step pair u (global scratch, or LDS for a launch of short blocks); returns the lane's CRC verdict
-template <bool BITS, class DecSt, class DecLd>
-__device__ __forceinline__ bool decode_core(const uint32_t (*cls)[kLanes], OutW& outw, const uint32_t* crc_inv, int lane, int type345, int type2,
-                                            int a, DecSt dec_st, DecLd dec_ld) {
-    int pos = a;                       // (a * i) % K for i = 1
-    auto fetch = [&] {
-        Raw3 r;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int p = interleave_next(pos, a, type345);
-            r.w[k] = cls[BITS ? p >> 5 : p >> 4][lane];
-            r.at[k] = BITS ? 31u - (uint32_t)(p & 31) : (uint32_t)(30 - 2 * (p & 15));
-        }
-        return r;
-    };
-    if (BITS) {
-        viterbi_forward(type2, fetch,
-                        [&](const Raw3& r) { return bm_from_masks(bfe_mask(r.w[0], r.at[0]), bfe_mask(r.w[1], r.at[1]), bfe_mask(r.w[2], r.at[2])); },
-                        dec_st);
-    } else {
-        viterbi_forward(type2, fetch,
-                        [&](const Raw3& r) { return bm_from_classes((int)(r.w[0] << r.at[0]) >> 30, (int)(r.w[1] << r.at[1]) >> 30, (int)(r.w[2] << r.at[2]) >> 30); },
-                        dec_st);
-    }
-    // traceback + CRC (own lane's data only: program order is enough)
-    return viterbi_traceback(type2, dec_ld, [&](int h, uint32_t half) { outw[h][lane] = (uint16_t)half; },
-                             [&](uint32_t off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(crc_inv) + off); });
-}
+// What steps 2-3 (decode_hard, decode_soft) touch besides the lane's type-4 bits: its column of the decoded halves and the backward CRC
+// table in LDS, and its decision words in the global scratch, laid out [step pair][lane]
+struct LaneIo {
+    OutW& outw;
+    const uint32_t* crc_inv;
+    uint32_t* dec;
+    int lane;
+    __device__ __forceinline__ void dec_st(int u, uint32_t w) const { dec[u * kLanes] = w; }
+    __device__ __forceinline__ uint32_t dec_ld(int u) const { return dec[u * kLanes]; }
+    __device__ __forceinline__ void out_st(int h, uint32_t half) const { outw[h][lane] = (uint16_t)half; }
+    __device__ __forceinline__ uint32_t tinv(uint32_t off) const { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(crc_inv) + off); }
+};
 
 // the backward CRC table into LDS (4 entries per lane); the caller's next barrier makes it visible
 __device__ __forceinline__ void load_crc_inv(uint32_t* crc_inv, int lane) {
@@ -97,46 +68,16 @@ __device__ __forceinline__ void load_crc_inv(uint32_t* crc_inv, int lane) {
     for (int k = 0; k < 256 / kLanes; ++k) crc_inv[k * kLanes + lane] = kCrcInvDev.t[k * kLanes + lane];
 }
 
-// step 4: decoded rows -> HBM.  WIDE: rows a multiple of 8 bytes and 8-byte aligned -- 8 bits -> 8 bytes per lane, the (row, unit)
-// index space flattened so that every lane stores in every round (q = i / units by a multiply: exact for i < 64 * 36).
+// step 4 (lmac_core.hpp write_rows) from LDS to the workgroup's rows in HBM
 __device__ __forceinline__ void write_rows(const OutW& outw, int lane, int rows_here, int type2, uint8_t* __restrict__ out0, int out_stride) {
-    if (!(out_stride & 7) && !((uintptr_t)out0 & 7)) {
-        const int units = type2 >> 3, total = rows_here * units;
-        const uint32_t inv = ((1u << 20) + (uint32_t)units - 1u) / (uint32_t)units;
-        for (int i = lane; i < total; i += kLanes) {
-            const int q = (int)(((uint32_t)i * inv) >> 20), d = i - q * units;
-            const uint32_t byte = ((uint32_t)outw[d >> 1][q] >> (8 * (d & 1))) & 0xffu;
-            demux_core::U2 v;
-            v.x = spread4(byte & 0xfu);
-            v.y = spread4(byte >> 4);
-            reinterpret_cast<demux_core::U2*>(out0 + (size_t)q * out_stride)[d] = v;
-        }
-    } else {
-        const int out_dw = type2 >> 2;
-        for (int q = 0; q < rows_here; ++q) {
-            uint32_t* dst = reinterpret_cast<uint32_t*>(out0 + (size_t)q * out_stride);
-            for (int d = lane; d < out_dw; d += kLanes) dst[d] = spread4(((uint32_t)outw[d >> 2][q] >> (4 * (d & 3))) & 0xfu);
-        }
-    }
+    tetra_lmac::write_rows(lane, rows_here, type2, rows_wide(out0, out_stride), [&](int h, int q) { return outw[h][q]; },
+               [&](int q, int d, demux_core::U2 v) { reinterpret_cast<demux_core::U2*>(out0 + (size_t)q * out_stride)[d] = v; },
+               [&](int q, int d, uint32_t v) { reinterpret_cast<uint32_t*>(out0 + (size_t)q * out_stride)[d] = v; });
 }
 
-// the lane's scrambling sequence words XORed onto its packed row, result to LDS (sequence rows as 16-byte loads)
-__device__ __forceinline__ void descramble_to_lds(int type345, uint32_t code, const uint32_t xb[kSeqWords], const uint32_t* __restrict__ seq_tab,
-                                                  uint32_t (*cls)[kLanes], int lane) {
-    const uint4* r0 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)0 * 256 + (code & 0xffu)) * kSeqStride);
-    const uint4* r1 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)1 * 256 + ((code >> 8) & 0xffu)) * kSeqStride);
-    const uint4* r2 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)2 * 256 + ((code >> 16) & 0xffu)) * kSeqStride);
-    const uint4* r3 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)3 * 256 + (code >> 24)) * kSeqStride);
-#pragma unroll
-    for (int g = 0; g < (kSeqWords + 3) / 4; ++g) {
-        if (128 * g < type345) {
-            const uint4 s0 = r0[g], s1 = r1[g], s2 = r2[g], s3 = r3[g];
-            const uint32_t w[4] = { s0.x ^ s1.x ^ s2.x ^ s3.x, s0.y ^ s1.y ^ s2.y ^ s3.y, s0.z ^ s1.z ^ s2.z ^ s3.z, s0.w ^ s1.w ^ s2.w ^ s3.w };
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * g + k < kSeqWords && 32 * (4 * g + k) < type345) cls[4 * g + k][lane] = xb[4 * g + k] ^ w[k];
-        }
-    }
+// lane_sequence's rows of the device's sequence table: 16-byte loads
+__device__ __forceinline__ auto seq_rows(const uint32_t* __restrict__ seq_tab) {
+    return [=](int t, uint32_t byte) { return reinterpret_cast<const uint4*>(seq_tab + ((size_t)t * 256 + byte) * kSeqStride); };
 }
 
 __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restrict__ type5, int n_blocks, int in_stride,
@@ -146,7 +87,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restric
                                                         uint32_t* __restrict__ dec_scratch, int dec_pairs,
                                                         const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index,
                                                         const uint32_t* __restrict__ seq_tab) {
-    __shared__ uint32_t stage[kLanes][kChunkDwords + 1];     // +1: odd row stride, conflict-free column reads
+    __shared__ uint32_t stage[kLanes][kStageWords];
     __shared__ uint32_t cls[kClsWords + 1][kLanes];
     __shared__ OutW outw;
     __shared__ uint32_t crc_inv[256];
@@ -166,42 +107,29 @@ __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restric
     // 1. front end.  Rows of plain bits: each lane packs its own row (8-byte loads), descrambles whole words and leaves the type-4
     //    bits in LDS (cls rows 0..13 as [word][lane]); the workgroup falls back to the byte route if any of its rows holds another
     //    byte value, or if the rows are not 8-byte aligned.
-    bool byte_route = seq_tab == nullptr || (in_stride & 7) || ((uintptr_t)type5 & 7) || in_stride > 512;      // (512: the unit -> row map below)
+    bool byte_route = needs_byte_route(seq_tab, type5, in_stride);
+    LaneIo io{ outw, crc_inv, dec, lane };
     if (!byte_route) {
-        // The workgroup's rows_here rows are one contiguous run of rows_here * in_stride bytes: read it ONCE, 8 bytes per lane and
-        // 512 contiguous bytes per load instruction, pack each unit's 8 bytes to 8 bits and drop them as one byte into the row's
-        // packed words in LDS (`stage`, 17 words per row); then every lane picks up its own row's words.  (Until late in round 6 every
-        // lane read its own row with strided 8-byte loads: 64 cache lines per instruction, and with a few waves per CU the lines were
-        // evicted before their other 120 bytes were used.)
-        const int units_per_row = in_stride >> 3, total_units = rows_here * units_per_row;
-        const uint32_t inv = ((1u << 20) + (uint32_t)units_per_row - 1u) / (uint32_t)units_per_row;      // exact for u < 64 * 64
+        // pack_units: the workgroup reads its rows as one contiguous run.  (Until late in round 6 every lane read its own row with strided
+        // 8-byte loads: 64 cache lines per instruction, and with a few waves per CU the lines were evicted before their other 120 bytes
+        // were used.)
         const U2* base = reinterpret_cast<const U2*>(type5 + (size_t)blk0 * in_stride);
         uint8_t* sb = reinterpret_cast<uint8_t*>(&stage[0][0]);
-        uint32_t dirty = 0;
-        for (int u = lane; u < total_units; u += kLanes) {
-            const int r = (int)(((uint32_t)u * inv) >> 20), j = u - r * units_per_row;      // row, byte of its packed bits
-            if (8 * j < type345) {
-                const U2 d = base[u];
-                dirty |= (d.x | d.y) & 0xfefefefeu;
-                // type-5 bits 8j .. 8j+7, first bit most significant; byte j of the row's bit string sits in word j / 4 at bits 31 - 8 (j % 4) ..
-                sb[(size_t)r * (4 * (kChunkDwords + 1)) + (j & ~3) + (3 - (j & 3))] = (uint8_t)((pack4(d.x) << 4) | pack4(d.y));
-            }
-        }
+        const uint32_t dirty = pack_units(lane, rows_here, in_stride, type345, [&](int u) { return base[u]; },
+                                          [&](size_t at, uint8_t byte) { sb[at] = byte; });
         byte_route = __builtin_amdgcn_ballot_w64(dirty != 0) != 0;          // wave-uniform
         __syncthreads();
         if (!byte_route) {
             uint32_t xb[kSeqWords];
-#pragma unroll
-            for (int w = 0; w < kSeqWords; ++w) xb[w] = 32 * w < type345 ? stage[lane][w] : 0u;
-            if (type345 & 31) xb[type345 >> 5] &= ~(0xffffffffu >> (type345 & 31));      // (bytes behind the row's last bit were never written)
-            descramble_to_lds(type345, code, xb, seq_tab, cls, lane);
+            const uint32_t* mine = stage[lane];
+            staged_row(type345, [&](int w) { return mine[w]; }, xb);
+            descramble_words(type345, code, xb, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
         }
     }
     bool good;
     if (!byte_route) {
         __syncthreads();
-        good = decode_core<true>(cls, outw, crc_inv, lane, type345, type2, a, [&](int u, uint32_t w) { dec[u * kLanes] = w; },
-                                 [&](int u) { return dec[u * kLanes]; });
+        good = decode_hard<true>(type345, type2, a, [&](int w) { return cls[w][lane]; }, io);
     } else {
         // rows -> LDS in chunks of 64 bits per row (coalesced 64-byte segments, 4 rows per load instruction), each lane
         // descrambles its own row chunk by chunk (its LFSR carried in a register) and packs the soft classes
@@ -221,8 +149,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restric
                                     [&](int w, uint32_t word) { cls[c0 / 4 + w][lane] = word; });
             __syncthreads();
         }
-        good = decode_core<false>(cls, outw, crc_inv, lane, type345, type2, a, [&](int u, uint32_t w) { dec[u * kLanes] = w; },
-                                  [&](int u) { return dec[u * kLanes]; });
+        good = decode_hard<false>(type345, type2, a, [&](int w) { return cls[w][lane]; }, io);
     }
     if (blk < n_blocks) crc_ok[blk] = good;
     __syncthreads();
@@ -270,24 +197,31 @@ __device__ __forceinline__ void write_verdict(const DevJob& J, const DevFrames& 
         J.labels[blk] = lb;
     }
 }
-// the lane's scrambling sequence, words 0 .. (type345 + 31) / 32 (four rows of the table XORed, 16-byte loads; the rest zero)
-__device__ __forceinline__ void lane_sequence(int type345, uint32_t code, const uint32_t* __restrict__ seq_tab, uint32_t seq[kSeqWords]) {
-    const uint4* r0 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)0 * 256 + (code & 0xffu)) * kSeqStride);
-    const uint4* r1 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)1 * 256 + ((code >> 8) & 0xffu)) * kSeqStride);
-    const uint4* r2 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)2 * 256 + ((code >> 16) & 0xffu)) * kSeqStride);
-    const uint4* r3 = reinterpret_cast<const uint4*>(seq_tab + ((size_t)3 * 256 + (code >> 24)) * kSeqStride);
-#pragma unroll
-    for (int g = 0; g < (kSeqWords + 3) / 4; ++g) {
-        uint4 s = make_uint4(0u, 0u, 0u, 0u);
-        if (128 * g < type345) {
-            const uint4 s0 = r0[g], s1 = r1[g], s2 = r2[g], s3 = r3[g];
-            s = make_uint4(s0.x ^ s1.x ^ s2.x ^ s3.x, s0.y ^ s1.y ^ s2.y ^ s3.y, s0.z ^ s1.z ^ s2.z ^ s3.z, s0.w ^ s1.w ^ s2.w ^ s3.w);
-        }
-        const uint32_t w[4] = { s.x, s.y, s.z, s.w };
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (4 * g + k < kSeqWords) seq[4 * g + k] = w[k];
+// The frame kernels' prologue, in two halves around the kernel's own `if (L.blk0 >= L.n_blocks) return;` (as one function that also says
+// "nothing to do" it compiles to a materialised predicate and a dozen more instructions per kernel): frame_group finds the workgroup's
+// job and rows, frame_of the lane's frame and its scrambling code.
+struct FrameLane {
+    const DevJob& J;
+    int group, blk0, blk, n_blocks, rows_here;
+    int f;
+    uint32_t code;
+};
+__device__ __forceinline__ FrameLane frame_group(const JobTable& tab, int lane) {
+    int ji = 0;
+    for (int i = 1; i < tab.n; ++i) ji = (int)blockIdx.x >= tab.job[i].first_group ? i : ji;
+    const DevJob& J = tab.job[ji];
+    const int group = (int)blockIdx.x - J.first_group, blk0 = group * kLanes;
+    int n_blocks = J.n_rows;
+    if (J.n_rows_dev) {           // counted rows: a device-side result (the frame lists)
+        const int have = *J.n_rows_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
     }
+    return FrameLane{ J, group, blk0, blk0 + lane, n_blocks, min(kLanes, n_blocks - blk0), 0, 0u };
+}
+__device__ __forceinline__ void frame_of(const JobTable& tab, FrameLane& L) {
+    // (a list entry outside [0, n_frames) -- a caller's slip -- reads the nearest frame instead of memory that is not there)
+    L.f = min(max(L.J.row_frame[L.blk < L.n_blocks ? L.blk : L.blk0], 0), tab.src.n_frames - 1);
+    L.code = L.J.frame_scramb ? L.J.frame_scramb[L.f] : kScrambInitSb1;
 }
 // LDS per workgroup: 3584 (type-4 bits; the decoded halves reuse the space once the forward recursion is through with them) + 1024
 // (backward CRC table) = 4608 B <= 5120: LDS never caps the kernel below 8 waves per SIMD -- which matters beside the demodulator:
@@ -307,25 +241,14 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
     OutW& outw = sm.outw;
     __shared__ uint32_t crc_inv[256];
     const int lane = threadIdx.x;
-    int ji = 0;
-    for (int i = 1; i < tab.n; ++i) ji = (int)blockIdx.x >= tab.job[i].first_group ? i : ji;
-    const DevJob& J = tab.job[ji];
-    const int group = (int)blockIdx.x - J.first_group;
-    const int blk0 = group * kLanes, blk = blk0 + lane;
-    int n_blocks = J.n_rows;
-    if (J.n_rows_dev) {
-        const int have = *J.n_rows_dev;
-        n_blocks = have < n_blocks ? have : n_blocks;
-    }
-    if (blk0 >= n_blocks) return;
-    const int rows_here = min(kLanes, n_blocks - blk0);
-    // (a list entry outside [0, n_frames) -- a caller's slip -- reads the nearest frame instead of memory that is not there)
-    const int f = min(max(J.row_frame[blk < n_blocks ? blk : blk0], 0), tab.src.n_frames - 1);
-    const uint32_t code = J.frame_scramb ? J.frame_scramb[f] : kScrambInitSb1;
-    const int ft = tab.src.frame_type[f];
+    FrameLane L = frame_group(tab, lane);
+    if (L.blk0 >= L.n_blocks) return;
+    frame_of(tab, L);
+    const DevJob& J = L.J;
+    const int ft = tab.src.frame_type[L.f];
     uint32_t fw[kFrameWords];
     {
-        const uint4* src = reinterpret_cast<const uint4*>(tab.src.frames + (size_t)f * kFrameWords);
+        const uint4* src = reinterpret_cast<const uint4*>(tab.src.frames + (size_t)L.f * kFrameWords);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const uint4 v = src[g];
@@ -337,8 +260,8 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
     if (bbk) {
         // TPSAP_T_BBK: the reference only descrambles (tetra_lower_mac.c:231-236): 30 bits -> 30 bytes (+ 2 zero bytes), a row per lane
         const uint32_t x = bbk_bits(fw, ft);
-        const uint32_t seq = seq_tab[((size_t)0 * 256 + (code & 0xffu)) * kSeqStride] ^ seq_tab[((size_t)1 * 256 + ((code >> 8) & 0xffu)) * kSeqStride] ^
-                             seq_tab[((size_t)2 * 256 + ((code >> 16) & 0xffu)) * kSeqStride] ^ seq_tab[((size_t)3 * 256 + (code >> 24)) * kSeqStride];
+        uint32_t seq = 0;
+        lane_sequence(30, L.code, seq_rows(seq_tab), [&](int w, uint32_t word) { seq = w == 0 ? word : seq; });
         uint32_t y = (x ^ seq) & 0xfffffffcu;                // 30 bits, first bit most significant
         uint32_t tail = 0;                                   // row bytes 30, 31
         if (RM && J.layout == kLayoutBbkRm) {
@@ -347,25 +270,24 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
             tail = r.dist << 16;
             good = r.dist <= (uint32_t)kRm3014Radius;
         }
-        if (blk < n_blocks) {
-            demux_core::U2* dst = reinterpret_cast<demux_core::U2*>(J.out + (size_t)blk * J.out_stride);
+        if (L.blk < L.n_blocks) {
+            demux_core::U2* dst = reinterpret_cast<demux_core::U2*>(J.out + (size_t)L.blk * J.out_stride);
 #pragma unroll
             for (int k = 0; k < 4; ++k) dst[k] = demux_core::U2{ bbk_bytes(y, 2 * k), bbk_bytes(y, 2 * k + 1) | (k == 3 ? tail : 0u) };
         }
     } else {
         uint32_t xb[kSeqWords];
         frame_block(J.layout, fw, ft, xb);
-        descramble_to_lds(J.type345, code, xb, seq_tab, cls, lane);
+        descramble_words(J.type345, L.code, xb, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
         load_crc_inv(crc_inv, lane);
         __syncthreads();
-        uint32_t* dec = dec_scratch + J.scratch_base + (size_t)group * J.dec_pairs * kLanes + lane;
-        good = decode_core<true>(cls, outw, crc_inv, lane, J.type345, J.type2, J.a, [&](int u, uint32_t w) { dec[u * kLanes] = w; },
-                                 [&](int u) { return dec[u * kLanes]; });
+        LaneIo io{ outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
+        good = decode_hard<true>(J.type345, J.type2, J.a, [&](int w) { return cls[w][lane]; }, io);
     }
-    if (blk < n_blocks) write_verdict(J, tab.src, blk, f, good);
+    if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, good);
     if (!bbk) {
         __syncthreads();
-        write_rows(outw, lane, rows_here, J.type2, J.out + (size_t)blk0 * J.out_stride, J.out_stride);
+        write_rows(outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
     }
 }
 
@@ -386,94 +308,69 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
     } sm;
     __shared__ uint32_t crc_inv[256];
     const int lane = threadIdx.x;
-    int ji = 0;
-    for (int i = 1; i < tab.n; ++i) ji = (int)blockIdx.x >= tab.job[i].first_group ? i : ji;
-    const DevJob& J = tab.job[ji];
-    const int group = (int)blockIdx.x - J.first_group;
-    const int blk0 = group * kLanes, blk = blk0 + lane;
-    int n_blocks = J.n_rows;
-    if (J.n_rows_dev) {
-        const int have = *J.n_rows_dev;
-        n_blocks = have < n_blocks ? have : n_blocks;
-    }
-    if (blk0 >= n_blocks) return;
-    const int rows_here = min(kLanes, n_blocks - blk0);
-    const int f = min(max(J.row_frame[blk < n_blocks ? blk : blk0], 0), tab.src.n_frames - 1);
-    const uint32_t code = J.frame_scramb ? J.frame_scramb[f] : kScrambInitSb1;
-    const uint32_t* chan = ring + (size_t)(f / tab.src.frames_per_channel) * ring_words;
-    uint32_t seq[kSeqWords];
-    lane_sequence(J.type345, code, seq_tab, seq);
-    stage_block(J.layout, tab.src.bitnum[f], tab.src.frame_type[f], [&](uint32_t w) { return chan[w]; }, 4u * ring_words - 1u, seq,
+    FrameLane L = frame_group(tab, lane);
+    if (L.blk0 >= L.n_blocks) return;
+    frame_of(tab, L);
+    const DevJob& J = L.J;
+    const uint32_t* chan = ring + (size_t)(L.f / tab.src.frames_per_channel) * ring_words;
+    uint32_t seq[kSeqWords] = {};
+    lane_sequence(J.type345, L.code, seq_rows(seq_tab), [&](int w, uint32_t word) { seq[w] = word; });
+    stage_block(J.layout, tab.src.bitnum[L.f], tab.src.frame_type[L.f], [&](uint32_t w) { return chan[w]; }, 4u * ring_words - 1u, seq,
                 [&](int g, uint32_t word) { sm.soft[g][lane] = word; });
     load_crc_inv(crc_inv, lane);
     __syncthreads();
-    uint32_t* dec = dec_scratch + J.scratch_base + (size_t)group * J.dec_pairs * kLanes + lane;
-    forward(J.type345, J.type2, J.a, [&](int w) { return sm.soft[w][lane]; }, [&](int u, uint32_t w) { dec[u * kLanes] = w; });
-    const bool good = viterbi_traceback(J.type2, [&](int u) { return dec[u * kLanes]; }, [&](int h, uint32_t half) { sm.outw[h][lane] = (uint16_t)half; },
-                                        [&](uint32_t off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(crc_inv) + off); });
-    if (blk < n_blocks) write_verdict(J, tab.src, blk, f, good);
+    LaneIo io{ sm.outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
+    const bool good = decode_soft(J.type345, J.type2, J.a, [&](int w) { return sm.soft[w][lane]; }, io);
+    if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, good);
     __syncthreads();
-    write_rows(sm.outw, lane, rows_here, J.type2, J.out + (size_t)blk0 * J.out_stride, J.out_stride);
+    write_rows(sm.outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
 }
 
-// Per-device constant of the decoder's packed route: the scrambling-sequence table (64 KB), built on the host once per device and
-// kept for the life of the process.
-std::mutex g_tab_mu;
-uint32_t* g_seq_tab[64] = {};
-// nullptr if the table cannot be set up (out of memory): the caller reports TETRA_ERR_NOMEM
+// One value per device, built on first use under a lock (safe for concurrent handles: one per GPU in a multi-GPU bank) and kept for the
+// life of the process.  make(dev) returns the value, or a null one if it cannot be set up: get() then returns null, and tries again
+// next time.
+template <class T>
+struct PerDevice {
+    std::mutex mu;
+    T v[64] = {};
+    template <class Make>
+    T get(Make make) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return T{};
+        std::lock_guard<std::mutex> g(mu);
+        if (!v[dev]) v[dev] = make(dev);
+        return v[dev];
+    }
+};
+// a table of `words` words filled on the host, on the current device (nullptr: out of memory, the caller reports TETRA_ERR_NOMEM)
+uint32_t* upload_table(size_t words, void (*fill)(uint32_t*)) {
+    std::vector<uint32_t> host(words);
+    fill(host.data());
+    DevMem<uint32_t> d_tab;
+    if (d_tab.reserve(sizeof(uint32_t) * words) != hipSuccess || hipMemcpy(d_tab, host.data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return d_tab.release();
+}
+// the packed route's scrambling-sequence table (64 KB)
 const uint32_t* seq_table() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> g(g_tab_mu);
-    if (!g_seq_tab[dev]) {
-        const size_t seq_words = (size_t)4 * 256 * kSeqStride;
-        std::vector<uint32_t> host(seq_words);
-        scramb_sequence_table(host.data());
-        DevMem<uint32_t> d_seq;
-        if (d_seq.reserve(sizeof(uint32_t) * seq_words) != hipSuccess ||
-            hipMemcpy(d_seq, host.data(), sizeof(uint32_t) * seq_words, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        g_seq_tab[dev] = d_seq.release();
-    }
-    return g_seq_tab[dev];
+    static PerDevice<uint32_t*> tab;
+    return tab.get([](int) { return upload_table((size_t)4 * 256 * kSeqStride, scramb_sequence_table); });
 }
-
-// Per-device constant of the AACH's Reed-Muller decoding (tetra_aach.h): syndrome -> error pattern, 2^16 entries = 256 KB, built on the
-// host from the generator on first use (the lock makes that safe for concurrent handles: one per GPU in a multi-GPU bank) and kept,
-// like the scrambling table above, for the life of the process.
-std::mutex g_rm_mu;
-uint32_t* g_rm_tab[64] = {};
+// the AACH's Reed-Muller decoding (tetra_aach.h): syndrome -> error pattern, 2^16 entries = 256 KB, from the generator
 const uint32_t* rm3014_table() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> g(g_rm_mu);
-    if (!g_rm_tab[dev]) {
-        std::vector<uint32_t> host(kRm3014TableEntries);
-        rm3014_correction_table(host.data());
-        DevMem<uint32_t> d_tab;
-        if (d_tab.reserve(sizeof(uint32_t) * host.size()) != hipSuccess ||
-            hipMemcpy(d_tab, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        g_rm_tab[dev] = d_tab.release();
-    }
-    return g_rm_tab[dev];
+    static PerDevice<uint32_t*> tab;
+    return tab.get([](int) { return upload_table(kRm3014TableEntries, rm3014_correction_table); });
 }
 
 // The decoder's decision scratch (up to 200 MB for a second of 4096 channels' SCH/F slots) comes from a stream-ordered pool of this
 // library's own, one per device, that KEEPS what is freed into it (release threshold = everything).  The device's default pool hands
 // unused memory back to the driver at synchronisation points; the next call then maps 200 MB again and takes milliseconds instead of
 // microseconds -- seen as one call in five at 20 ms in the two-stream chain (profiles/r05/README.md).
-std::mutex g_pool_mu;
-hipMemPool_t g_pool[64] = {};
 hipMemPool_t scratch_pool() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> g(g_pool_mu);
-    if (!g_pool[dev]) {
+    static PerDevice<hipMemPool_t> pool;
+    return pool.get([](int dev) -> hipMemPool_t {
         hipMemPoolProps props = {};
         props.allocType = hipMemAllocationTypePinned;
         props.handleTypes = hipMemHandleTypeNone;
@@ -483,10 +380,37 @@ hipMemPool_t scratch_pool() {
         if (hipMemPoolCreate(&p, &props) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         uint64_t keep = ~0ull;
         (void)hipMemPoolSetAttribute(p, hipMemPoolAttrReleaseThreshold, &keep);
-        g_pool[dev] = p;
-    }
-    return g_pool[dev];
+        return p;
+    });
 }
+// One launch's lease of decision scratch: the caller's workspace if it gave one, else `bytes` from the keeping pool (after the first
+// call a free-list hit; the device's default pool if the keeping pool could not be made), handed back in stream order right behind
+// the kernel.
+struct ScratchLease {
+    uint32_t* p = nullptr;
+    hipStream_t s = nullptr;
+    bool pooled = false;
+    int take(size_t bytes, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+        s = stream;
+        if (workspace) {
+            if (workspace_bytes < bytes) return TETRA_ERR_SIZE;
+            if ((uintptr_t)workspace & 3) return TETRA_ERR_ALIGN;
+            p = static_cast<uint32_t*>(workspace);
+            return TETRA_OK;
+        }
+        hipMemPool_t pool = scratch_pool();
+        const hipError_t got = pool ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&p), bytes, pool, s) : hipMallocAsync(reinterpret_cast<void**>(&p), bytes, s);
+        if (got != hipSuccess) { (void)hipGetLastError(); return TETRA_ERR_NOMEM; }
+        pooled = true;
+        return TETRA_OK;
+    }
+    bool give_back() { return !pooled || hipFreeAsync(p, s) == hipSuccess; }
+    // behind the launch: its status and the hand-back's
+    int launched() {
+        const hipError_t launch = hipGetLastError();
+        return !give_back() || launch != hipSuccess ? TETRA_ERR_HIP : TETRA_OK;
+    }
+};
 
 // TPSAP_T_BBK: the reference only descrambles (tetra_lower_mac.c:231-236); 30 bits per block, one lane per block.
 // RM (tetra_lmac_decode_aach_rm3014_device): the descrambled bytes are also gathered into the 30-bit word (a byte other than 0 is a 1),
@@ -646,7 +570,7 @@ int check_args(int type, const void* in, int n_blocks, int in_stride, const void
     if (n_blocks == 0) return TETRA_OK;
     if (!in || !out || !ok) return TETRA_ERR_ARG;
     if (type != TETRA_TPSAP_T_SB1 && !init) return TETRA_ERR_ARG;
-    const BlkParam& p = kBlk[type];
+    const BlkParam& p = blk_param(type);
     if (in_stride < p.type345 || out_stride < p.type2) return TETRA_ERR_ARG;
     if ((in_stride & 3) || (out_stride & 3)) return TETRA_ERR_ALIGN;
     if (device_ptrs && (((uintptr_t)in & 3) || ((uintptr_t)out & 3))) return TETRA_ERR_ALIGN;
@@ -659,11 +583,12 @@ extern "C" {
 
 int tetra_lmac_blk_param(int type, tetra_lmac_blk_param_t* out) {
     if (type < 0 || type > 5 || !out) return TETRA_ERR_ARG;
-    out->type345_bits = kBlk[type].type345;
-    out->type2_bits = kBlk[type].type2;
-    out->type1_bits = kBlk[type].type1;
-    out->interleave_a = kBlk[type].a;
-    out->have_crc16 = kBlk[type].crc;
+    const BlkParam& p = blk_param(type);
+    out->type345_bits = p.type345;
+    out->type2_bits = p.type2;
+    out->type1_bits = p.type1;
+    out->interleave_a = p.a;
+    out->have_crc16 = p.crc;
     return TETRA_OK;
 }
 
@@ -681,29 +606,23 @@ int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blo
     const int rc = check_args(type, d_type5, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_crc_ok, true);
     if (rc != TETRA_OK || n_blocks == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const BlkParam& p = kBlk[type];
+    const BlkParam& p = blk_param(type);
     if (type == TETRA_TPSAP_T_BBK) {
         hipLaunchKernelGGL(k_lmac_bbk<false>, dim3((n_blocks + 255) / 256), dim3(256), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
                            p.type345, d_type2, out_stride, d_crc_ok, d_n_blocks, d_init_index);
     } else {
-        // decision scratch: (type2 + 4) steps x 64 lanes x u16 per workgroup, from the library's keeping pool (scratch_pool():
-        // after the first call a free-list hit), released in stream order right behind the kernel
+        // decision scratch: (type2 + 4) steps x 64 lanes x u16 per workgroup
         const int groups = (n_blocks + kLanes - 1) / kLanes;
         const int dec_pairs = (p.type2 + kFlush) / 2;
         const size_t bytes = (size_t)groups * dec_pairs * kLanes * sizeof(uint32_t);
         const uint32_t* seq = seq_table();
         if (!seq) return TETRA_ERR_NOMEM;
-        uint32_t* scratch = nullptr;
-        hipMemPool_t pool = scratch_pool();
-        const hipError_t got = pool ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), bytes, pool, s)
-                                    : hipMallocAsync(reinterpret_cast<void**>(&scratch), bytes, s);
-        if (got != hipSuccess) { (void)hipGetLastError(); return TETRA_ERR_NOMEM; }
+        ScratchLease scratch;
+        if (const int err = scratch.take(bytes, nullptr, 0, s)) return err;
         hipLaunchKernelGGL(k_lmac_decode, dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
                            type == TETRA_TPSAP_T_SB1 ? 1 : 0, p.type345, p.type2, p.type1, p.a, d_type2, out_stride, d_crc_ok,
-                           scratch, dec_pairs, d_n_blocks, d_init_index, g_force_byte_route ? nullptr : seq);
-        const hipError_t launch = hipGetLastError();
-        if (hipFreeAsync(scratch, s) != hipSuccess || launch != hipSuccess) return TETRA_ERR_HIP;
-        return TETRA_OK;
+                           scratch.p, dec_pairs, d_n_blocks, d_init_index, g_force_byte_route ? nullptr : seq);
+        return scratch.launched();
     }
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
@@ -729,17 +648,9 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok) return TETRA_ERR_ARG;
         if (j.type != TETRA_TPSAP_T_SB1 && !j.d_frame_scramb) return TETRA_ERR_ARG;
         if (j.d_labels && (!src->d_frame_bitnum || !src->d_time_rx || !src->d_time || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
-        int layout = kLayoutNone;
-        switch (j.type) {
-            case TETRA_TPSAP_T_SB1: layout = j.blk_num == 1 ? kLayoutSb1 : kLayoutNone; break;
-            case TETRA_TPSAP_T_SB2: layout = j.blk_num == 2 ? kLayoutSb2 : kLayoutNone; break;
-            case TETRA_TPSAP_T_NDB: layout = j.blk_num == 1 ? kLayoutNdb1 : j.blk_num == 2 ? kLayoutNdb2 : kLayoutNone; break;
-            case TETRA_TPSAP_T_BBK: layout = rm ? kLayoutBbkRm : kLayoutBbk; break;
-            case TETRA_TPSAP_T_SCH_F: layout = kLayoutSchF; break;
-            default: break;                                    // SCH/HU: an uplink block, no downlink burst carries it
-        }
+        const int layout = layout_for(j.type, j.blk_num, rm);
         if (layout == kLayoutNone) return TETRA_ERR_ARG;       // no burst type carries this (kind, block number)
-        const BlkParam& p = kBlk[j.type];
+        const BlkParam& p = blk_param(j.type);
         const bool bbk = layout == kLayoutBbk || layout == kLayoutBbkRm;
         if (soft && bbk) return TETRA_ERR_ARG;                 // the AACH has no soft route
         any_rm = any_rm || rm;
@@ -771,34 +682,19 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
     const uint32_t* seq = seq_table();
     if (!seq) return TETRA_ERR_NOMEM;
     const size_t bytes = (size_t)scratch_words * sizeof(uint32_t);
-    uint32_t* scratch = nullptr;
-    bool pooled = false;
-    if (scratch_words) {
-        if (src->d_workspace) {
-            if (src->workspace_bytes < bytes) return TETRA_ERR_SIZE;
-            if ((uintptr_t)src->d_workspace & 3) return TETRA_ERR_ALIGN;
-            scratch = static_cast<uint32_t*>(src->d_workspace);
-        } else {
-            hipMemPool_t pool = scratch_pool();
-            const hipError_t got = pool ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), bytes, pool, s)
-                                        : hipMallocAsync(reinterpret_cast<void**>(&scratch), bytes, s);
-            if (got != hipSuccess) { (void)hipGetLastError(); return TETRA_ERR_NOMEM; }
-            pooled = true;
-        }
-    }
+    ScratchLease scratch;
+    if (const int err = scratch_words ? scratch.take(bytes, src->d_workspace, src->workspace_bytes, s) : TETRA_OK) return err;
     if (soft) {
-        hipLaunchKernelGGL(k_lmac_frames_soft, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq,
+        hipLaunchKernelGGL(k_lmac_frames_soft, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq,
                            reinterpret_cast<const uint32_t*>(soft->d_ring), soft->size / 4u);
     } else if (any_rm) {
         const uint32_t* rm_tab = rm3014_table();
-        if (!rm_tab) { if (pooled) (void)hipFreeAsync(scratch, s); return TETRA_ERR_NOMEM; }
-        hipLaunchKernelGGL(k_lmac_frames<true>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq, rm_tab);
+        if (!rm_tab) { (void)scratch.give_back(); return TETRA_ERR_NOMEM; }
+        hipLaunchKernelGGL(k_lmac_frames<true>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, rm_tab);
     } else {
-        hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch, seq, nullptr);
+        hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, nullptr);
     }
-    const hipError_t launch = hipGetLastError();
-    if ((pooled && hipFreeAsync(scratch, s) != hipSuccess) || launch != hipSuccess) return TETRA_ERR_HIP;
-    return TETRA_OK;
+    return scratch.launched();
 }
 
 int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
@@ -811,7 +707,7 @@ size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, in
     for (int i = 0; i < n_jobs; ++i) {
         const tetra_lmac_job_t& j = jobs[i];
         if (j.type < 0 || j.type > 5 || j.type == TETRA_TPSAP_T_BBK || j.max_rows <= 0) continue;
-        words += (size_t)(((long long)j.max_rows + kLanes - 1) / kLanes) * ((kBlk[j.type].type2 + kFlush) / 2) * kLanes;
+        words += (size_t)(((long long)j.max_rows + kLanes - 1) / kLanes) * ((blk_param(j.type).type2 + kFlush) / 2) * kLanes;
     }
     return words * sizeof(uint32_t);
 }
@@ -910,8 +806,9 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
     if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
     // only the type2_bits columns: the caller's row padding is left alone
     // (rows without padding: one contiguous copy -- a strided device-to-host copy of many narrow rows crawls)
-    if (out_stride == kBlk[type].type2 ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
-                                       : hipMemcpy2D(type2, out_stride, d_out, out_stride, kBlk[type].type2, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
+    const int row = blk_param(type).type2;
+    if (out_stride == row ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
+                          : hipMemcpy2D(type2, out_stride, d_out, out_stride, row, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
         return TETRA_ERR_HIP;
     if (hipMemcpy(crc_ok, d_ok, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;

@@ -1,140 +1,134 @@
-// Host build of the lower-MAC decoder's lane-level code (sdrpp-tetra-demodulator_amd/csrc/lmac_core.hpp), one block at
-// a time with plain arrays behind the accessors the kernel puts on LDS.  Test infrastructure: lets the CPU suite check
-// the exact kernel source against the reference-built primitives (oracle/_ref) without a GPU.
+// Host build of the lower-MAC decoder's lane-level code (sdrpp-tetra-demodulator_amd/csrc/lmac_core.hpp), one 64-row workgroup
+// at a time with plain arrays behind the accessors the kernels put on LDS (lmac_lane_io.hpp).  Test infrastructure: lets the CPU suite
+// check the exact kernel source against the reference-built primitives (oracle/_ref) without a GPU.
 #define TETRA_HOST_EMUL 1
-#include <cstdint>
-#include <cstring>
+#include "lmac_lane_io.hpp"
 
-#include "../../sdrpp-tetra-demodulator_amd/csrc/lmac_core.hpp"
-
-using namespace tetra_lmac;
+using namespace lane_emul;
 
 namespace {
-const uint32_t* seq_table() {
-    static uint32_t* tab = nullptr;
-    if (!tab) {
-        tab = new uint32_t[(size_t)4 * 256 * kSeqStride];
-        scramb_sequence_table(tab);
-    }
-    return tab;
+// k_lmac_decode's cooperative front end for one workgroup: rows_here rows from `rows` on, type5 / in_stride the whole batch's.  True: the
+// packed route is taken and xb[lane] holds the lane's packed row; false: the whole workgroup has to take the byte route.  The staging
+// array starts out as all ones: the kernel's LDS is not cleared, and what staged_row lets through of that must not matter.
+bool stage_workgroup(const uint32_t* seq_tab, int type345, const uint8_t* type5, const uint8_t* rows, int rows_here, int in_stride,
+                     uint32_t xb[kLanes][kSeqWords]) {
+    if (needs_byte_route(seq_tab, type5, in_stride)) return false;
+    uint32_t stage[kLanes][kStageWords];
+    std::memset(stage, 0xff, sizeof(stage));
+    uint8_t* sb = reinterpret_cast<uint8_t*>(&stage[0][0]);
+    uint32_t dirty = 0;                                           // the kernel's ballot
+    for (int lane = 0; lane < kLanes; ++lane)
+        dirty |= pack_units(lane, rows_here, in_stride, type345, [&](int u) { U2 d; std::memcpy(&d, rows + (size_t)8 * u, 8); return d; },
+                            [&](size_t at, uint8_t byte) { sb[at] = byte; });
+    if (dirty) return false;
+    for (int lane = 0; lane < rows_here; ++lane) staged_row(type345, [&](int w) { return stage[lane][w]; }, xb[lane]);
+    return true;
 }
 }  // namespace
 
-// route: 0 = like the kernel (rows of plain bits take the packed route, any other row the byte route), 1 = byte route always
+// k_lmac_decode, a 64-row workgroup at a time.  route: 0 = like the kernel (a workgroup whose rows are all plain bits, 8-byte aligned
+// and at most 512 bytes apart takes the packed route, any other the byte route), 1 = byte route always (tetra_lmac_debug_force_byte_route).
+// fast_rows: the rows of the workgroups that took the packed route.
 extern "C" int lmac_emul_decode_route(int type345, int type2, int type1, int a, const uint8_t* type5, int n_blocks, int in_stride,
                                       const uint32_t* scramb_init, uint8_t* out, int out_stride, int32_t* crc_ok, int route, int32_t* fast_rows) {
     if (type345 > kMaxType345 || type2 > kMaxType2 || (type345 & 7) || (type2 & 15) || (in_stride & 3)) return -1;
-    static const CrcInvTable crci = make_crc_inv_table();
     (void)type1;                  // n2 = type1 + 16 + 4 for every coded kind: the traceback derives the CRC span from n2
-    const uint32_t* tab = seq_table();
+    const uint32_t* seq_tab = route == 0 ? seq_table() : nullptr;
     int fast = 0;
-    for (int blk = 0; blk < n_blocks; ++blk) {
-        const uint8_t* row = type5 + (size_t)blk * in_stride;
-        uint32_t cls[(kMaxType345 + 15) / 16 + 1];
-        uint32_t dec[(kMaxType2 + kFlush) / 2];
-        uint16_t outw[kMaxType2 / 16];
-        uint32_t xb[kSeqWords];
-        const uint32_t dirty = pack_row_bits(type345, [&](int i) { U2 d; std::memcpy(&d, row + 8 * i, 8); return d; }, xb);
-        int pos = a;
-        const bool bits_route = route == 0 && !dirty;
-        if (bits_route) {
-            ++fast;
-            descramble_bits(type345, scramb_init[blk], xb, [&](int t, uint32_t byte, int w) { return tab[((size_t)t * 256 + byte) * kSeqStride + w]; },
-                            [&](int w, uint32_t word) { cls[w] = word; });
-        } else {
-            uint32_t lfsr = scramb_init[blk];
-            for (int c0 = 0; c0 < type345 / 4; c0 += 16)      // the kernel's 64-bit staging chunks
-                lfsr = descramble_chunk(type345 - 4 * c0, lfsr,
-                                        [&](int d) { uint32_t v; std::memcpy(&v, row + 4 * (c0 + d), 4); return v; },
-                                        [&](int w, uint32_t word) { cls[c0 / 4 + w] = word; });
-        }
-        auto fetch = [&] {                                    // as decode_core in tetra_lmac.hip
-            Raw3 r;
-            for (int k = 0; k < 3; ++k) {
-                const int p = interleave_next(pos, a, type345);
-                r.w[k] = cls[bits_route ? p >> 5 : p >> 4];
-                r.at[k] = bits_route ? 31u - (uint32_t)(p & 31) : (uint32_t)(30 - 2 * (p & 15));
+    for (int blk0 = 0; blk0 < n_blocks; blk0 += kLanes) {
+        const int rows_here = n_blocks - blk0 < kLanes ? n_blocks - blk0 : kLanes;
+        const uint8_t* rows = type5 + (size_t)blk0 * in_stride;
+        uint32_t xb[kLanes][kSeqWords];
+        OutW outw;
+        const bool packed = stage_workgroup(seq_tab, type345, type5, rows, rows_here, in_stride, xb);
+        if (packed) fast += rows_here;
+        for (int lane = 0; lane < rows_here; ++lane) {
+            const uint32_t code = scramb_init[blk0 + lane];
+            uint32_t cls[kClsWords + 1];
+            LaneIo io{ outw, lane, {} };
+            if (packed) {
+                descramble_words(type345, code, xb[lane], seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w] = word; });
+                crc_ok[blk0 + lane] = decode_hard<true>(type345, type2, a, [&](int w) { return cls[w]; }, io);
+            } else {
+                const uint8_t* row = rows + (size_t)lane * in_stride;
+                uint32_t lfsr = code;
+                for (int c0 = 0; c0 < type345 / 4; c0 += kChunkDwords)      // the kernel's 64-bit staging chunks
+                    lfsr = descramble_chunk(type345 - 4 * c0, lfsr,
+                                            [&](int d) { uint32_t v; std::memcpy(&v, row + 4 * (c0 + d), 4); return v; },
+                                            [&](int w, uint32_t word) { cls[c0 / 4 + w] = word; });
+                crc_ok[blk0 + lane] = decode_hard<false>(type345, type2, a, [&](int w) { return cls[w]; }, io);
             }
-            return r;
-        };
-        auto dec_st = [&](int u, uint32_t word) { dec[u] = word; };
-        if (bits_route)
-            viterbi_forward(type2, fetch,
-                            [&](const Raw3& r) { return bm_from_masks(bfe_mask(r.w[0], r.at[0]), bfe_mask(r.w[1], r.at[1]), bfe_mask(r.w[2], r.at[2])); }, dec_st);
-        else
-            viterbi_forward(type2, fetch,
-                            [&](const Raw3& r) { return bm_from_classes((int)(r.w[0] << r.at[0]) >> 30, (int)(r.w[1] << r.at[1]) >> 30, (int)(r.w[2] << r.at[2]) >> 30); },
-                            dec_st);
-        crc_ok[blk] = viterbi_traceback(type2, [&](int u) { return dec[u]; }, [&](int h, uint32_t half) { outw[h] = (uint16_t)half; },
-                                        [&](uint32_t off) { return crci.t[off >> 2]; });
-        for (int t4 = 0; t4 < type2 / 4; ++t4) {
-            const uint32_t v = spread4((outw[t4 >> 2] >> (4 * (t4 & 3))) & 0xfu);
-            std::memcpy(out + (size_t)blk * out_stride + 4 * t4, &v, 4);
         }
+        write_rows(outw, rows_here, type2, out + (size_t)blk0 * out_stride, out_stride);
     }
     if (fast_rows) *fast_rows = fast;
     return 0;
 }
 
-extern "C" int lmac_emul_decode(int type345, int type2, int type1, int a, const uint8_t* type5, int n_blocks, int in_stride,
-                                const uint32_t* scramb_init, uint8_t* out, int out_stride, int32_t* crc_ok) {
-    return lmac_emul_decode_route(type345, type2, type1, a, type5, n_blocks, in_stride, scramb_init, out, out_stride, crc_ok, 0, nullptr);
+// the front end alone: the packed words (xb [n_blocks][kSeqWords]) of every row of the workgroups that take the packed route, took[blk] =
+// whether row blk's workgroup did
+extern "C" void lmac_emul_stage(int type345, const uint8_t* type5, int n_blocks, int in_stride, uint32_t* xb_out, int32_t* took) {
+    for (int blk0 = 0; blk0 < n_blocks; blk0 += kLanes) {
+        const int rows_here = n_blocks - blk0 < kLanes ? n_blocks - blk0 : kLanes;
+        uint32_t xb[kLanes][kSeqWords] = {};
+        const bool packed = stage_workgroup(seq_table(), type345, type5, type5 + (size_t)blk0 * in_stride, rows_here, in_stride, xb);
+        for (int lane = 0; lane < rows_here; ++lane) {
+            took[blk0 + lane] = packed;
+            std::memcpy(xb_out + (size_t)(blk0 + lane) * kSeqWords, xb[lane], sizeof(xb[lane]));
+        }
+    }
+}
+// lane_sequence alone: the words it hands out for a block of type345 bits under `code` (words [kSeqWords]); returns the mask of the
+// words it handed out
+extern "C" uint32_t lmac_emul_sequence(int type345, uint32_t code, uint32_t* words) {
+    uint32_t mask = 0;
+    lane_sequence(type345, code, seq_rows(seq_table()), [&](int w, uint32_t word) { words[w] = word; mask |= 1u << w; });
+    return mask;
+}
+// unit_row (the multiply-shift row index of the front end and the write-back) for i = 0 .. n - 1
+extern "C" void lmac_emul_unit_row(int units, int n, int32_t* out) {
+    const uint32_t inv = unit_inverse(units);
+    for (int i = 0; i < n; ++i) out[i] = unit_row(i, inv);
+}
+// blk_param(type) as type345, type2, type1, a, crc
+extern "C" int lmac_emul_blk_param(int type, int32_t* out) {
+    if (type < 0 || type > 5) return -1;
+    const BlkParam& p = blk_param(type);
+    const int32_t v[5] = { p.type345, p.type2, p.type1, p.a, p.crc };
+    std::memcpy(out, v, sizeof(v));
+    return 0;
 }
 
-// tetra_lmac_decode_frames_device, one job: the lane code of k_lmac_frames for every listed frame.  frames [n_frames][16] packed,
-// frame_scramb per frame slot (NULL: SCRAMB_INIT).  out rows: type2 bits (BBK: 30 bits + 2 zero bytes).
+// tetra_lmac_decode_frames_device, one job: the lane code of k_lmac_frames for every listed frame, a 64-row workgroup at a time.
+// frames [n_frames][16] packed, frame_scramb per frame slot (NULL: SCRAMB_INIT).  out rows: type2 bits (BBK: 30 bits + 2 zero bytes).
 extern "C" int lmac_emul_decode_frames(int tpsap, int blk_num, const uint32_t* frames, const int32_t* frame_type, const int32_t* row_frame,
                                        int n_rows, const uint32_t* frame_scramb, uint8_t* out, int out_stride, int32_t* crc_ok) {
-    int layout = kLayoutNone, type345 = 0, type2 = 0, type1 = 0, a = 0;
-    switch (tpsap) {
-        case TETRA_TPSAP_T_SB1: layout = blk_num == 1 ? kLayoutSb1 : kLayoutNone; type345 = 120; type2 = 80; type1 = 60; a = 11; break;
-        case TETRA_TPSAP_T_SB2: layout = blk_num == 2 ? kLayoutSb2 : kLayoutNone; type345 = 216; type2 = 144; type1 = 124; a = 101; break;
-        case TETRA_TPSAP_T_NDB: layout = blk_num == 1 ? kLayoutNdb1 : blk_num == 2 ? kLayoutNdb2 : kLayoutNone; type345 = 216; type2 = 144; type1 = 124; a = 101; break;
-        case TETRA_TPSAP_T_BBK: layout = kLayoutBbk; break;
-        case TETRA_TPSAP_T_SCH_F: layout = kLayoutSchF; type345 = 432; type2 = 288; type1 = 268; a = 103; break;
-        default: break;
-    }
+    const int layout = tpsap < 0 || tpsap > 5 ? kLayoutNone : layout_for(tpsap, blk_num, false);
     if (layout == kLayoutNone) return -1;
-    static const CrcInvTable crci = make_crc_inv_table();
-    const uint32_t* tab = seq_table();
-    auto seq = [&](int t, uint32_t byte, int w) { return tab[((size_t)t * 256 + byte) * kSeqStride + w]; };
-    for (int blk = 0; blk < n_rows; ++blk) {
-        const int f = row_frame[blk];
-        const uint32_t code = frame_scramb && tpsap != TETRA_TPSAP_T_SB1 ? frame_scramb[f] : kScrambInitSb1;
-        const uint32_t* fw = frames + (size_t)f * kFrameWords;
-        uint8_t* row = out + (size_t)blk * out_stride;
-        if (layout == kLayoutBbk) {
-            const uint32_t x = bbk_bits(fw, frame_type[f]);
-            const uint32_t sw = seq(0, code & 0xffu, 0) ^ seq(1, (code >> 8) & 0xffu, 0) ^ seq(2, (code >> 16) & 0xffu, 0) ^ seq(3, code >> 24, 0);
-            const uint32_t y = (x ^ sw) & 0xfffffffcu;
-            for (int k = 0; k < 8; ++k) { const uint32_t v = bbk_bytes(y, k); std::memcpy(row + 4 * k, &v, 4); }
-            crc_ok[blk] = 1;
-            continue;
-        }
-        uint32_t xb[kSeqWords], cls[kSeqWords], dec[(kMaxType2 + kFlush) / 2];
-        uint16_t outw[kMaxType2 / 16];
-        frame_block(layout, fw, frame_type[f], xb);
-        descramble_bits(type345, code, xb, seq, [&](int w, uint32_t word) { cls[w] = word; });
-        int pos = a;
-        auto fetch = [&] {
-            Raw3 r;
-            for (int k = 0; k < 3; ++k) {
-                const int p = interleave_next(pos, a, type345);
-                r.w[k] = cls[p >> 5];
-                r.at[k] = 31u - (uint32_t)(p & 31);
+    const BlkParam& p = blk_param(tpsap);
+    const uint32_t* seq_tab = seq_table();
+    for (int blk0 = 0; blk0 < n_rows; blk0 += kLanes) {
+        const int rows_here = n_rows - blk0 < kLanes ? n_rows - blk0 : kLanes;
+        OutW outw;
+        for (int lane = 0; lane < rows_here; ++lane) {
+            const int blk = blk0 + lane, f = row_frame[blk];
+            const uint32_t code = frame_scramb && tpsap != TETRA_TPSAP_T_SB1 ? frame_scramb[f] : kScrambInitSb1;
+            const uint32_t* fw = frames + (size_t)f * kFrameWords;
+            if (layout == kLayoutBbk) {
+                uint32_t seq = 0;
+                lane_sequence(30, code, seq_rows(seq_tab), [&](int w, uint32_t word) { seq = w == 0 ? word : seq; });
+                const uint32_t y = (bbk_bits(fw, frame_type[f]) ^ seq) & 0xfffffffcu;
+                for (int k = 0; k < 8; ++k) { const uint32_t v = bbk_bytes(y, k); std::memcpy(out + (size_t)blk * out_stride + 4 * k, &v, 4); }
+                crc_ok[blk] = 1;
+                continue;
             }
-            return r;
-        };
-        viterbi_forward(type2, fetch,
-                        [&](const Raw3& r) { return bm_from_masks(bfe_mask(r.w[0], r.at[0]), bfe_mask(r.w[1], r.at[1]), bfe_mask(r.w[2], r.at[2])); },
-                        [&](int u, uint32_t word) { dec[u] = word; });
-        (void)type1;
-        crc_ok[blk] = viterbi_traceback(type2, [&](int u) { return dec[u]; }, [&](int h, uint32_t half) { outw[h] = (uint16_t)half; },
-                                        [&](uint32_t off) { return crci.t[off >> 2]; });
-        for (int t4 = 0; t4 < type2 / 4; ++t4) {
-            const uint32_t v = spread4((outw[t4 >> 2] >> (4 * (t4 & 3))) & 0xfu);
-            std::memcpy(row + 4 * t4, &v, 4);
+            uint32_t xb[kSeqWords], cls[kSeqWords];
+            frame_block(layout, fw, frame_type[f], xb);
+            descramble_words(p.type345, code, xb, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w] = word; });
+            LaneIo io{ outw, lane, {} };
+            crc_ok[blk] = decode_hard<true>(p.type345, p.type2, p.a, [&](int w) { return cls[w]; }, io);
         }
+        if (layout != kLayoutBbk) write_rows(outw, rows_here, p.type2, out + (size_t)blk0 * out_stride, out_stride);
     }
     return 0;
 }
@@ -152,7 +146,6 @@ extern "C" void lmac_emul_tdma_advance(const uint32_t* start, int n, int kmax, u
 // stale_tcd_on_bad_crc != 0 plants the rule the tracker had before it was pinned to the reference (lmac_core.hpp: kStaleTcdOnBadCrc).
 extern "C" void lmac_emul_track(const uint8_t* sb1, int stride, const int32_t* crc_ok, const int32_t* valid_in, const int32_t* n_frames, int n_channels,
                                 int frames, uint32_t* cell, uint32_t* row_scramb, uint32_t* row_time_rx, uint32_t* row_time, int stale_tcd_on_bad_crc) {
-    constexpr int kLanes = 64;
     for (int c = 0; c < n_channels; ++c) {
         const int nf = n_frames ? (n_frames[c] < frames ? n_frames[c] : frames) : frames;
         uint32_t* cs = cell + (size_t)c * 10;

@@ -1,13 +1,12 @@
-// Host build of the soft-decision option's lane-level code (sdrpp-tetra-demodulator_amd/csrc/soft_core.hpp + the traceback of
-// lmac_core.hpp): the quantiser of k_soft and one lane of k_lmac_frames_soft with plain arrays where the kernels have global memory
-// and LDS.  Test infrastructure: lets the CPU suite hold the exact kernel source against the reference's conv_cch_decode.
+// Host build of the soft-decision option's lane-level code (sdrpp-tetra-demodulator_amd/csrc/soft_core.hpp + the sequence, traceback
+// and write-back of lmac_core.hpp): the quantiser of k_soft and the workgroups of k_lmac_frames_soft with plain arrays where the kernels
+// have global memory and LDS (lmac_lane_io.hpp).  Test infrastructure: lets the CPU suite hold the exact kernel source against the reference's conv_cch_decode.
 #define TETRA_HOST_EMUL 1
-#include <cstdint>
-#include <cstring>
-
 #include "../../sdrpp-tetra-demodulator_amd/csrc/soft_core.hpp"
+#include "lmac_lane_io.hpp"
 
 using namespace tetra_soft;
+using namespace lane_emul;
 
 extern "C" int soft_emul_q(void) { return kQ; }
 extern "C" float soft_emul_g(void) { return kG; }
@@ -29,34 +28,27 @@ extern "C" void soft_emul_quantise(const float* sym, int n, float* prev, int8_t*
     prev[1] = pi;
 }
 
-// One lane of k_lmac_frames_soft per row: row j's frame starts at absolute bit bitnum[j] of ring j (rings [n_rows][ring_size] int8,
-// 4-byte aligned, ring_size a power of two), has burst type frame_type[j] and is descrambled with scramb[j] (NULL: SCRAMB_INIT).
-// out rows: type-2 bits, one per byte.
+// k_lmac_frames_soft, a lane per row and a 64-row workgroup at a time: row j's frame starts at absolute bit bitnum[j] of ring j (rings
+// [n_rows][ring_size] int8, 4-byte aligned, ring_size a power of two), has burst type frame_type[j] and is descrambled with scramb[j]
+// (NULL: SCRAMB_INIT).  out rows: type-2 bits, one per byte.
 extern "C" int soft_emul_decode(int tpsap, int blk_num, const int8_t* rings, uint32_t ring_size, const uint32_t* bitnum, const int32_t* frame_type,
                                 int n_rows, const uint32_t* scramb, uint8_t* out, int out_stride, int32_t* crc_ok) {
-    int layout = kLayoutNone, type345 = 0, type2 = 0, a = 0;
-    switch (tpsap) {
-        case TETRA_TPSAP_T_SB1: layout = blk_num == 1 ? kLayoutSb1 : kLayoutNone; type345 = 120; type2 = 80; a = 11; break;
-        case TETRA_TPSAP_T_SB2: layout = blk_num == 2 ? kLayoutSb2 : kLayoutNone; type345 = 216; type2 = 144; a = 101; break;
-        case TETRA_TPSAP_T_NDB: layout = blk_num == 1 ? kLayoutNdb1 : blk_num == 2 ? kLayoutNdb2 : kLayoutNone; type345 = 216; type2 = 144; a = 101; break;
-        case TETRA_TPSAP_T_SCH_F: layout = kLayoutSchF; type345 = 432; type2 = 288; a = 103; break;
-        default: break;
-    }
+    const int layout = tpsap < 0 || tpsap > 5 || tpsap == TETRA_TPSAP_T_BBK ? kLayoutNone : layout_for(tpsap, blk_num, false);
     if (layout == kLayoutNone || ring_size < 4 || (ring_size & (ring_size - 1))) return -1;
-    static const CrcInvTable crci = make_crc_inv_table();
-    for (int j = 0; j < n_rows; ++j) {
-        const uint32_t* ring = reinterpret_cast<const uint32_t*>(rings + (size_t)j * ring_size);
-        uint32_t seq[kSeqWords], soft[kSoftWords] = {}, dec[(kMaxType2 + kFlush) / 2];
-        uint16_t outw[kMaxType2 / 16];
-        scramb_sequence_words(scramb ? scramb[j] : kScrambInitSb1, seq);
-        stage_block(layout, bitnum[j], frame_type[j], [&](uint32_t w) { return ring[w]; }, ring_size - 1u, seq, [&](int g, uint32_t word) { soft[g] = word; });
-        forward(type345, type2, a, [&](int w) { return soft[w]; }, [&](int u, uint32_t word) { dec[u] = word; });
-        crc_ok[j] = viterbi_traceback(type2, [&](int u) { return dec[u]; }, [&](int h, uint32_t half) { outw[h] = (uint16_t)half; },
-                                      [&](uint32_t off) { return crci.t[off >> 2]; });
-        for (int t4 = 0; t4 < type2 / 4; ++t4) {
-            const uint32_t v = spread4((outw[t4 >> 2] >> (4 * (t4 & 3))) & 0xfu);
-            std::memcpy(out + (size_t)j * out_stride + 4 * t4, &v, 4);
+    const BlkParam& p = blk_param(tpsap);
+    for (int blk0 = 0; blk0 < n_rows; blk0 += kLanes) {
+        const int rows_here = n_rows - blk0 < kLanes ? n_rows - blk0 : kLanes;
+        OutW outw;
+        for (int lane = 0; lane < rows_here; ++lane) {
+            const int j = blk0 + lane;
+            const uint32_t* ring = reinterpret_cast<const uint32_t*>(rings + (size_t)j * ring_size);
+            uint32_t seq[kSeqWords] = {}, soft[kSoftWords] = {};
+            lane_sequence(p.type345, scramb ? scramb[j] : kScrambInitSb1, seq_rows(seq_table()), [&](int w, uint32_t word) { seq[w] = word; });
+            stage_block(layout, bitnum[j], frame_type[j], [&](uint32_t w) { return ring[w]; }, ring_size - 1u, seq, [&](int g, uint32_t word) { soft[g] = word; });
+            LaneIo io{ outw, lane, {} };
+            crc_ok[j] = decode_soft(p.type345, p.type2, p.a, [&](int w) { return soft[w]; }, io);
         }
+        write_rows(outw, rows_here, p.type2, out + (size_t)blk0 * out_stride, out_stride);
     }
     return 0;
 }

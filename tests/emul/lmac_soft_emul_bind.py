@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "liblmac_soft_emul.so")
 CSRC = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc")
-DEPS = [os.path.join(HERE, "lmac_soft_emul.cpp")] + [os.path.join(CSRC, f) for f in ("soft_core.hpp", "lmac_core.hpp", "demux_core.hpp")]
+DEPS = [os.path.join(HERE, "lmac_soft_emul.cpp"), os.path.join(HERE, "lmac_lane_io.hpp")] + [os.path.join(CSRC, f) for f in ("soft_core.hpp", "lmac_core.hpp", "demux_core.hpp")]
 
 # where a kind's type-5 bits sit in its 510-bit burst (tetra_burst.c:343-393): (tpsap, blk_num, burst type, pieces (offset, length))
 KINDS = {

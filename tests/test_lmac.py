@@ -87,29 +87,148 @@ def test_lane_code_equals_reference(lref):
         assert 0 < want_ok.sum() < len(rows)
 
 
+def packed_rows_by_the_kernels_rule(rows, n345):
+    """fast_rows as k_lmac_decode decides it, workgroup-wide: the 64 rows of a workgroup take the packed route together when the rows
+    are 8-byte aligned and at most 512 bytes apart and every one of their type-5 bytes is 0 / 1; one other byte anywhere in the
+    workgroup sends all of its rows down the byte route."""
+    if rows.shape[1] % 8 or rows.shape[1] > 512 or rows.ctypes.data % 8:
+        return 0
+    clean = ((rows[:, :n345] & 0xfe) == 0).all(1)
+    return sum(min(64, len(rows) - g) for g in range(0, len(rows), 64) if clean[g:g + 64].all())
+
+
 def test_lane_code_packed_route_equals_byte_route(lref):
     """Round 6: rows of plain bits (every byte 0 / 1) take a packed route through the decoder's front end (bytes -> bits, whole
     words of the scrambling sequence from a table that is linear in the code, bit spreading to classes); any other row the byte
-    route (an LFSR step and a three-way classification per byte).  Same lane code as the kernel, on the host: the packed route IS
-    taken for the clean rows, gives the byte route's output bit for bit, and both equal the reference."""
-    import ctypes as C
+    route (an LFSR step and a three-way classification per byte).  Same lane code as the kernel, on the host, a 64-row workgroup at
+    a time: the packed route IS taken by exactly the workgroups the kernel's rule sends there (three clean ones, then one with clean
+    and other rows mixed and one without a clean row), gives the byte route's output bit for bit, and both equal the reference."""
     from tests.emul import lmac_emul_bind
-    L = lmac_emul_bind.lib()
-    vp = C.c_void_p
     for t in CODED:
         n345, n2, n1, a, _ = lref.BLK_PARAM[t]
-        rows, si, _ = make_rows(lref, t, 200, 300 + t)
-        outs = []
-        for route in (0, 1):
-            out, ok, fast = np.zeros((len(rows), n2), np.uint8), np.zeros(len(rows), np.int32), C.c_int32(-1)
-            assert L.lmac_emul_decode_route(n345, n2, n1, a, rows.ctypes.data_as(vp), len(rows), rows.shape[1], si.ctypes.data_as(vp),
-                                            out.ctypes.data_as(vp), n2, ok.ctypes.data_as(vp), route, C.byref(fast)) == 0
-            outs.append((out, ok, fast.value))
-        clean = int(((rows[:, :n345] & 0xfe) == 0).all(1).sum())
-        assert outs[0][2] == clean >= 150 and outs[1][2] == 0
+        rows, si, _ = make_rows(lref, t, 320, 300 + t)
+        first = np.argsort(~((rows[:, :n345] & 0xfe) == 0).all(1), kind="stable")      # the rows of plain bits first
+        rows = np.ascontiguousarray(np.concatenate([rows, rows[:, :4]], axis=1)[first])  # (436 bytes apart: not 8-byte aligned; 440 are)
+        si = si[first]
+        outs = [lmac_emul_bind.decode_route(t, rows, si, route) for route in (0, 1)]
+        assert outs[0][2] == packed_rows_by_the_kernels_rule(rows, n345) == 192 >= 150 and outs[1][2] == 0
         assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
         want, want_ok = ref_decode_rows(lref, t, rows, si)
         assert np.array_equal(outs[0][0], want) and np.array_equal(outs[0][1], want_ok)
+
+
+@pytest.fixture(scope="module")
+def bit_rows(lref):
+    """Per coded kind, 128 blocks of plain bits (even rows: encoded blocks, a good CRC; odd rows: random bits), their scrambling codes and
+    the reference's decoding of them; shared by the tests below, which lay them into rows of their own strides."""
+    rng = np.random.default_rng(612)
+    pool = {}
+    for t in CODED:
+        n345, n2, n1, a, _ = lref.BLK_PARAM[t]
+        si = rng.integers(0, 2 ** 32, 128, dtype=np.uint64).astype(np.uint32)
+        if t == lref.TPSAP_T_SB1:
+            si[:] = lref.SCRAMB_INIT
+        bits = rng.integers(0, 2, (128, n345), dtype=np.uint8)
+        for b in range(0, 128, 2):
+            bits[b] = lref.lmac_encode(t, rng.integers(0, 2, n1).astype(np.uint8), int(si[b]))
+        want, want_ok = ref_decode_rows(lref, t, bits, si)
+        assert want_ok[::2].all()
+        for arr in (bits, si, want, want_ok):
+            arr.flags.writeable = False
+        pool[t] = (bits, si, want, want_ok)
+    return pool
+
+
+def in_rows(bits, stride, seed):
+    """the blocks as rows `stride` bytes apart, garbage behind each block"""
+    rows = np.random.default_rng(seed).integers(0, 256, (len(bits), stride), dtype=np.uint8)
+    rows[:, :bits.shape[1]] = bits
+    return rows
+
+
+def test_emulated_workgroup_front_end_over_its_whole_domain(lref, bit_rows):
+    """k_lmac_decode's cooperative front end as the emulation runs it (pack_units, staged_row, descramble_words of lmac_core.hpp, the
+    kernel's own functions): workgroups of 1, 2, 63 and 64 rows of the shortest and the longest kind at every row stride from 8 to
+    512 bytes in steps of 8 that holds the block.  All rows take the packed route; the staged words are the rows' bits, first bit
+    most significant, and zero behind the last one although the staging array starts out as all ones; the output is the byte
+    route's and the reference's.  Rows further apart than 512 bytes do not fit the unit -> row map: the byte route.  The map itself
+    -- i // units as a multiply and a shift -- equals the division for every units-per-row from 1 to 64 and every index below
+    64 * units: the front end's whole domain, and the write-back's (10, 14, 18, 36 units)."""
+    from tests.emul import lmac_emul_bind as E
+    for units in range(1, 65):
+        assert np.array_equal(E.unit_row(units, 64 * units), np.arange(64 * units) // units), units
+    for t in (lref.TPSAP_T_SB1, lref.TPSAP_T_SCH_F):
+        n345 = lref.BLK_PARAM[t][0]
+        bits, si, want, want_ok = bit_rows[t]
+        words = np.zeros((len(bits), 14 * 32), np.uint8)
+        words[:, :n345] = bits
+        words = np.packbits(words, axis=1).view(">u4").astype(np.uint32)
+        strides = [s for s in range(8, 513, 8) if s >= n345]
+        assert strides[-1] == 512 and len(strides) == (50 if t == lref.TPSAP_T_SB1 else 11)
+        for stride in strides + [520]:
+            for n in (1, 2, 63, 64):
+                rows = in_rows(bits[:n], stride, stride + n)
+                xb, took = E.stage(t, rows)
+                got, ok, fast = E.decode_route(t, rows, si[:n])
+                if stride > 512:
+                    assert fast == 0 and not took.any(), (t, stride, n)
+                else:
+                    assert fast == n and took.all() and np.array_equal(xb, words[:n]), (t, stride, n)
+                byte, byte_ok, byte_fast = E.decode_route(t, rows, si[:n], route=1)
+                assert byte_fast == 0 and np.array_equal(got, byte) and np.array_equal(ok, byte_ok), (t, stride, n)
+                assert np.array_equal(got, want[:n]) and np.array_equal(ok, want_ok[:n]), (t, stride, n)
+
+
+def test_emulated_scrambling_sequence_reaches_exactly_its_groups(lref):
+    """lane_sequence (lmac_core.hpp; the packed row route, the frame route, the AACH word and the soft route all call it): for every
+    block length from 8 to 432 bits in steps of 8 -- 128, 256 and 384, where a group of four words ends on the block's last bit,
+    among them -- and the AACH's 30, it hands out the words of exactly the 128-bit groups the block reaches, none of a group no bit
+    of it lies in, and they are the reference's sequence (tetra_scramb_bits over zeros), first bit most significant."""
+    from tests.emul import lmac_emul_bind as E
+    L = lref.lmac_lib()
+    rng = np.random.default_rng(3)
+    for code in [lref.SCRAMB_INIT, 0xffffffff] + [int(c) for c in rng.integers(1, 2 ** 32, 6, dtype=np.uint64)]:
+        seq = np.zeros(14 * 32, np.uint8)
+        L.tetra_scramb_bits(code, seq.ctypes.data, seq.size)
+        want = np.packbits(seq).view(">u4").astype(np.uint32)
+        for type345 in [30] + list(range(8, 433, 8)):
+            words, mask = E.sequence(type345, code)
+            reached = min(14, 4 * ((type345 + 127) // 128))
+            assert mask == (1 << reached) - 1, (type345, hex(mask))
+            assert np.array_equal(words[:reached], want[:reached]) and not words[reached:].any(), (hex(code), type345)
+
+
+def test_emulated_write_back_routes_agree(lref, bit_rows):
+    """write_rows (lmac_core.hpp) as the emulation runs it: output rows that are a multiple of 8 bytes apart take the wide route (8
+    bytes per store, the (row, unit) index space flattened), rows type2 + 4 bytes apart the narrow one (4 bytes per store, row by
+    row).  Every coded kind, workgroups of 1, 63 and 64 rows: both equal the reference, and the bytes behind a row's type2 bits keep
+    the 0xA5 they were filled with."""
+    from tests.emul import lmac_emul_bind as E
+    for t in CODED:
+        n345, n2 = lref.BLK_PARAM[t][:2]
+        bits, si, want, want_ok = bit_rows[t]
+        assert n2 % 8 == 0
+        for n in (1, 63, 64):
+            for out_stride in (n2 + 8, n2 + 4):
+                got, ok, fast = E.decode_route(t, in_rows(bits[:n], n345, n), si[:n], out_stride=out_stride, fill=0xA5)
+                assert fast == n and np.array_equal(ok, want_ok[:n]), (t, n, out_stride)
+                assert np.array_equal(got[:, :n2], want[:n]) and (got[:, n2:] == 0xA5).all(), (t, n, out_stride)
+
+
+def test_emulated_mixed_workgroup_falls_back_as_a_whole(lref, bit_rows):
+    """One erasure byte in row 5 of a 64-row workgroup sends the whole workgroup down the byte route, as in the kernel; the next
+    workgroup, all plain bits, takes the packed route: fast_rows is 64, and both workgroups equal the reference."""
+    from tests.emul import lmac_emul_bind as E
+    for t in CODED:
+        n345 = lref.BLK_PARAM[t][0]
+        bits, si, _, _ = bit_rows[t]
+        rows = in_rows(bits, n345 + 8, 77)
+        rows[5, 7] = 0xff
+        got, ok, fast = E.decode_route(t, rows, si)
+        want, want_ok = ref_decode_rows(lref, t, rows, si)
+        assert fast == 64 == packed_rows_by_the_kernels_rule(rows, n345)
+        assert np.array_equal(got, want) and np.array_equal(ok, want_ok)
+        assert not E.stage(t, rows)[1][:64].any() and E.stage(t, rows)[1][64:].all()
 
 
 FRAME_KINDS = ((0, 1, 3), (1, 2, 3), (2, 1, 1), (2, 2, 1), (5, 0, 0), (3, 0, None))      # (tpsap, blk_num, carrying burst type)
@@ -341,6 +460,28 @@ def test_gpu_lmac_device_entry_with_wide_output_rows_on_a_side_stream(pkg, lref)
     for d_out, d_ok in outs:
         out, ok = d_out.cpu().numpy(), d_ok.cpu().numpy()
         assert np.array_equal(out[:, :288], want) and (out[:, 288:] == 7).all() and np.array_equal(ok, want_ok)
+
+
+@pytest.mark.gpu
+def test_gpu_lmac_narrow_output_rows(pkg, lref, bit_rows):
+    """tetra_lmac_decode_batch_device with output rows type2 + 4 bytes apart: not a multiple of 8, so the write-back stores 4 bytes at
+    a time, row by row.  65 blocks (a full workgroup and one of a single row) of the shortest and the longest kind: the rows equal the
+    reference, and the four bytes behind each keep the 0xA5 they were filled with."""
+    import torch
+    dev = torch.device("cuda", 0)
+    for t in (lref.TPSAP_T_SB1, lref.TPSAP_T_SCH_F):
+        n345, n2 = lref.BLK_PARAM[t][:2]
+        bits, si, want, want_ok = bit_rows[t]
+        n = 65
+        d_rows = torch.from_numpy(bits[:n].copy()).to(dev)
+        d_si = torch.from_numpy(si[:n].view(np.int32).copy()).to(dev)
+        d_out = torch.full((n, n2 + 4), 0xA5, dtype=torch.uint8, device=dev)
+        d_ok = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        pkg.lmac_binding.decode_batch_device(t, d_rows, n, n345, d_si, d_out, n2 + 4, d_ok)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        assert np.array_equal(out[:, :n2], want[:n]) and (out[:, n2:] == 0xA5).all(), t
+        assert np.array_equal(d_ok.cpu().numpy(), want_ok[:n]), t
 
 
 @pytest.mark.gpu
