@@ -60,6 +60,10 @@ enum {
     TETRA_RX_FLAG_ONE_STREAM = 1,  /* run the tail on the caller's stream behind the demodulator (no overlap between calls); A/B, tests */
     TETRA_RX_FLAG_AACH_RM3014 = 2, /* decode the AACH with its Reed-Muller code: up to 3 bit errors corrected, crc_ok = 0 beyond (tetra_aach.h) */
     /* 4 is not a flag and stays TETRA_ERR_ARG: callers and tests rely on it as the example of an unknown bit. */
+    TETRA_RX_FLAG_BITERR = 32,     /* channel bit-error counts: every coded block (SB1, SB2, NDB 1 / 2, SCH/F) also gets the distance from the
+                                      received block to its decoded codeword, and every channel running link figures (tetra_biterr.h:
+                                      tetra_rx_fetch_biterr, tetra_rx_get_link).  Composes with every other flag; blocks, rows, labels and
+                                      every fetch / delivery entry are unchanged.  16 and 64 are not flags either (tests hold them refused). */
     TETRA_RX_FLAG_SOFT = 8         /* soft decisions: SB1, SB2, NDB 1 / 2 and SCH/F are decoded from the demodulator's symbols -- per bit a
                                       6-bit soft value of the differential phase, kept per channel in a ring indexed by `bitnum` -- where
                                       the default slices every symbol to two hard bits first.  Same decoder as the reference's
@@ -108,7 +112,8 @@ int tetra_rx_wait(tetra_rx_t* h);
  * frames, the two bit-row buffers): 1.4 GB for 4096 channels x 36000 samples per call.  TETRA_RX_FLAG_SOFT adds, per CHANNEL with
  * S = the bit-row stride (about 1.05 bits per sample of max_samples): 4 S bytes for the call's symbols and a ring of one byte per bit of
  * R = the power of two >= 4096 + 2 S bytes (the synchroniser's 4096-bit buffer plus two calls in flight, csrc/soft_core.hpp), at least
- * 8192: 283 KB per channel, 1.16 GB for 4096 channels, at 36000 samples per call. */
+ * 8192: 283 KB per channel, 1.16 GB for 4096 channels, at 36000 samples per call.
+ * TETRA_RX_FLAG_BITERR adds 4 bytes per row and coded kind (two calls: 40 bytes per row with all five) and 24 bytes per channel. */
 int tetra_rx_max_rows(tetra_rx_t* h);
 /* type-1 bits per block of a kind (60 / 30 / 124 / 124 / 124 / 268); < 0: TETRA_ERR_ARG. */
 int tetra_rx_type1_bits(int kind);

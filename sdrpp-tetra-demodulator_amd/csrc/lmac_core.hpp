@@ -6,7 +6,8 @@
 // kernels share with the emulation: the block table and layout map (blk_param, layout_for), the cooperative front end of byte
 // rows (needs_byte_route, pack_units, staged_row) and its byte route (descramble_chunk), the scrambling sequence (lane_sequence,
 // descramble_words), the blocks cut from packed frames (frame_block, bbk_bits), forward recursion + traceback + CRC
-// (decode_hard; soft_core.hpp's decode_soft ends in the same traceback) and the write-back of both row widths (write_rows).
+// (decode_hard; soft_core.hpp's decode_soft ends in the same traceback), the channel bit-error count of a decoded block
+// (reencode_errors, opt-in: include/ext/tetra_biterr.h) and the write-back of both row widths (write_rows).
 //
 // Restated from the reference (src/decoder/src/lower_mac/), not copied:
 //   * scrambler        tetra_scramb.c:34-51 (Fibonacci LFSR, taps 32 26 23 22 16 12 11 10 8 7 5 4 2 1, shifts right, new
@@ -550,6 +551,51 @@ LM_FN bool decode_hard(int type345, int type2, int a, Cls cls, Io& io) {
                         dec_st);
     }
     return traceback(type2, io);
+}
+
+// ---- channel bit errors of a decoded block (include/ext/tetra_biterr.h) ------------------------------------------------------------------
+// The decoded type-2 bits d[0 .. type2) -- all of them, the four tail positions included -- are encoded again as a transmitter would
+// (tetra_conv_enc.c:45-60 from the all-zero state, punct_2_3, tetra_interleave.c:36-39) and held against what was received: the
+// Hamming distance from the received word to the decoded codeword over the positions that carry a decision.  The scrambler is a
+// bijection on bits, so the comparison is made on the descrambled side, where the lane's staged data already is.
+//   half(h)  = decoded bits 16h .. 16h+15, bit 16h + b at bit b (what viterbi_traceback hands to its st)
+//   rx(p)    = type-4 position p as received: bit 0 = the position carries a decision, bit 1 = its hard bit
+// Sixteen trellis steps at a time: with D = d[16h - 4 .. 16h + 15] (d[t] at bit t - 16h + 4, zeros before the block) the generators
+// g1 = 1 + D + D^4 and g2 = 1 + D^2 + D^3 + D^4 of all sixteen steps are three and four shifted XORs.  Rate 2/3 sends g1 and g2 of
+// every even step and g1 of every odd one (see the depuncturer above), in that order, and type-3 bit j sits at type-4 position
+// (a (j + 1)) % K: the received bits are gathered with the decoder's running index into words that line up with g1 (every step) and
+// g2 (even steps), and one XOR, AND and population count each give the group's share.  Returns errors | compared << 16.
+template <class Half, class Rx>
+LM_FN uint32_t reencode_errors(int type345, int type2, int a, Half half, Rx rx) {
+    int pos = a;
+    uint32_t prev = 0, errors = 0, compared = 0;
+    for (int h = 0; h < type2 / 16; ++h) {
+        const uint32_t D = ((uint32_t)half(h) << 4) | prev;
+        prev = D >> 16;
+        const uint32_t g1 = (D >> 4) ^ (D >> 3) ^ D, g2 = (D >> 4) ^ (D >> 2) ^ (D >> 1) ^ D;      // bit b: step 16h + b
+        uint32_t r1 = 0, v1 = 0, r2 = 0, v2 = 0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const uint32_t xa = rx(interleave_next(pos, a, type345));
+            const uint32_t xb = rx(interleave_next(pos, a, type345));
+            const uint32_t xc = rx(interleave_next(pos, a, type345));
+            v1 |= ((xa & 1u) << (2 * u)) | ((xc & 1u) << (2 * u + 1));
+            r1 |= ((xa >> 1) << (2 * u)) | ((xc >> 1) << (2 * u + 1));
+            v2 |= (xb & 1u) << (2 * u);
+            r2 |= (xb >> 1) << (2 * u);
+        }
+        errors += (uint32_t)__builtin_popcount((r1 ^ g1) & v1) + (uint32_t)__builtin_popcount((r2 ^ g2) & v2);
+        compared += (uint32_t)__builtin_popcount(v1) + (uint32_t)__builtin_popcount(v2);
+    }
+    return errors | (compared << 16);
+}
+// ... for the hard routes: cls as decode_hard's.  A packed bit always carries a decision; a class is +1 (0b01: a 0), 0 (erasure) or -1
+// (0b11: a 1), so its low bit says whether it counts and its high bit is the hard bit.
+template <bool BITS, class Half, class Cls>
+LM_FN uint32_t bit_errors_hard(int type345, int type2, int a, Half half, Cls cls) {
+    return reencode_errors(type345, type2, a, half, [&](int p) -> uint32_t {
+        return BITS ? 1u | (bfe_u(cls(p >> 5), 31u - (uint32_t)(p & 31), 1u) << 1) : bfe_u(cls(p >> 4), 2u * (uint32_t)(p & 15), 2u);
+    });
 }
 
 // Step 4: the workgroup's decoded rows -> memory, the lane's share; half(h, q) = decoded bits 16h .. 16h+15 of row q.  WIDE (rows_wide):

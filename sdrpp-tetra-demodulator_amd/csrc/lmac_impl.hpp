@@ -21,7 +21,9 @@ struct SoftRing {
 
 // tetra_lmac_decode_frames_device for the coded kinds (SB1, SB2, NDB, SCH/F; a BBK job is TETRA_ERR_ARG: the AACH stays on the packed
 // frames), the block's bits read as soft values from the ring at the frame's bit number (src->d_frame_bitnum, required) and
-// src->frames_per_channel >= 1.  Same jobs, rows, verdicts, labels and workspace as the entry point it mirrors.
-TETRA_HIDDEN int decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream);
+// src->frames_per_channel >= 1.  Same jobs, rows, verdicts, labels and workspace as the entry point it mirrors.  d_biterr: as
+// tetra_lmac_decode_frames_biterr_device's (tetra_biterr.h), the counts taken on the soft values.
+TETRA_HIDDEN int decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream,
+                                    uint32_t* const* d_biterr = nullptr);
 
 }  // namespace lmac_impl

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_rx.h"
 #include "hip_host.hpp"
 #include "retune_list.hpp"
@@ -31,6 +32,7 @@ struct KindBufs {                 // one parity's results of one kind
     DevMem<uint8_t> t2;           // [rows][out_stride]
     DevMem<int32_t> ok;           // [rows]
     DevMem<tetra_rx_block_t> blocks;      // [rows]
+    DevMem<uint32_t> biterr;              // [rows] errors | compared << 16 (TETRA_RX_FLAG_BITERR, coded kinds only)
     // into the parity's frame lists (not owned): the kind's rows are the frames row_frame[0 .. *n_rows)
     const int32_t* row_frame = nullptr;
     const int32_t* n_rows = nullptr;
@@ -54,6 +56,9 @@ struct tetra_rx {
     DevMem<int8_t> soft_ring;             // [C][soft_R]
     DevMem<float> soft_prev;              // [2][C] complex64: a channel's last symbol
     DevMem<uint32_t> soft_bits;           // [2][C]: its absolute bit count = the synchroniser's numbering
+    // TETRA_RX_FLAG_BITERR (tetra_biterr.h): the decode launches count channel bit errors per row, a kernel behind them sums them per channel
+    bool biterr = false;
+    DevMem<tetra_rx_link_t> link;         // [C], accumulated by the tails (one at a time, on one stream), zeroed by the resets
     Handle<tetra_demod_t*, tetra_demod_destroy> dem;
     Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
     Stream tail;

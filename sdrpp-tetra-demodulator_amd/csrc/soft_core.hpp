@@ -135,4 +135,14 @@ LM_FN bool decode_soft(int type345, int type2, int a, Ld ld, Io& io) {
     return traceback(type2, io);
 }
 
+// reencode_errors (lmac_core.hpp) on the staged block: a soft value of zero carries no decision, a negative one is a 1.  half: as
+// there; ld: as decode_soft's.
+template <class Half, class Ld>
+LM_FN uint32_t bit_errors_soft(int type345, int type2, int a, Half half, Ld ld) {
+    return reencode_errors(type345, type2, a, half, [&](int p) -> uint32_t {
+        const uint32_t y = bfe_u(ld(p >> 2), 8u * (uint32_t)(p & 3), 8);      // soft value + 128
+        return (y != 128u ? 1u : 0u) | (y < 128u ? 2u : 0u);
+    });
+}
+
 }  // namespace tetra_soft

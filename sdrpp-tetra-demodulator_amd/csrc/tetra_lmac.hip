@@ -23,6 +23,8 @@
 //      pipeline) with the CRC16 folded in (affine in the message: one AND + XOR per bit with a wave-uniform constant), decoded bits
 //      packed 16 per ushort into LDS [half][lane];
 //   4. the 64 decoded rows are written back with coalesced 8-byte stores, 8 bits -> 8 bytes per lane.
+// A launch that is asked for channel bit-error counts (include/ext/tetra_biterr.h) runs the COUNT instantiation of its kernel: between 3 and
+// 4 each lane encodes its decoded bits again and holds them against its block, both still in LDS (lmac_core.hpp reencode_errors).
 // The work is integer add / compare / select: bound by vector issue.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,7 @@
 #include <vector>
 
 #include "../../include/tetra_aach.h"
+#include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "hip_host.hpp"
@@ -80,13 +83,19 @@ __device__ __forceinline__ auto seq_rows(const uint32_t* __restrict__ seq_tab) {
     return [=](int t, uint32_t byte) { return reinterpret_cast<const uint4*>(seq_tab + ((size_t)t * 256 + byte) * kSeqStride); };
 }
 
+// The channel bit-error counts (tetra_biterr.h) are an instantiation of each decode kernel: COUNT = true takes where the counts go as a
+// trailing parameter pack -- one argument, none otherwise, as k_lmac_bbk takes its table -- so that the instantiation without the option
+// has the argument block and the instruction stream it had before the option existed.
+template <class T> __device__ __forceinline__ T only_of(T t) { return t; }
+
+template <bool COUNT, class... Biterr>
 __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restrict__ type5, int n_blocks, int in_stride,
                                                         const uint32_t* __restrict__ scramb_init, int fixed_init,
                                                         int type345, int type2, int type1, int a,
                                                         uint8_t* __restrict__ out, int out_stride, int* __restrict__ crc_ok,
                                                         uint32_t* __restrict__ dec_scratch, int dec_pairs,
                                                         const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index,
-                                                        const uint32_t* __restrict__ seq_tab) {
+                                                        const uint32_t* __restrict__ seq_tab, Biterr... biterr_pack) {
     __shared__ uint32_t stage[kLanes][kStageWords];
     __shared__ uint32_t cls[kClsWords + 1][kLanes];
     __shared__ OutW outw;
@@ -127,9 +136,13 @@ __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restric
         }
     }
     bool good;
+    uint32_t biterr = 0;                      // COUNT: errors | compared << 16 of the lane's block, from its decoded halves and its staged bits
+    auto half = [&](int h) { return outw[h][lane]; };
+    auto staged = [&](int w) { return cls[w][lane]; };
     if (!byte_route) {
         __syncthreads();
-        good = decode_hard<true>(type345, type2, a, [&](int w) { return cls[w][lane]; }, io);
+        good = decode_hard<true>(type345, type2, a, staged, io);
+        if constexpr (COUNT) biterr = bit_errors_hard<true>(type345, type2, a, half, staged);
     } else {
         // rows -> LDS in chunks of 64 bits per row (coalesced 64-byte segments, 4 rows per load instruction), each lane
         // descrambles its own row chunk by chunk (its LFSR carried in a register) and packs the soft classes
@@ -149,9 +162,13 @@ __global__ __launch_bounds__(kLanes) void k_lmac_decode(const uint8_t* __restric
                                     [&](int w, uint32_t word) { cls[c0 / 4 + w][lane] = word; });
             __syncthreads();
         }
-        good = decode_hard<false>(type345, type2, a, [&](int w) { return cls[w][lane]; }, io);
+        good = decode_hard<false>(type345, type2, a, staged, io);
+        if constexpr (COUNT) biterr = bit_errors_hard<false>(type345, type2, a, half, staged);
     }
     if (blk < n_blocks) crc_ok[blk] = good;
+    if constexpr (COUNT) {
+        if (blk < n_blocks) only_of(biterr_pack...)[blk] = biterr;
+    }
     __syncthreads();
     write_rows(outw, lane, rows_here, type2, out + (size_t)blk0 * out_stride, out_stride);
 }
@@ -223,21 +240,34 @@ __device__ __forceinline__ void frame_of(const JobTable& tab, FrameLane& L) {
     L.f = min(max(L.J.row_frame[L.blk < L.n_blocks ? L.blk : L.blk0], 0), tab.src.n_frames - 1);
     L.code = L.J.frame_scramb ? L.J.frame_scramb[L.f] : kScrambInitSb1;
 }
+// Where the counts of a frame launch go: per job of the table, NULL = the job does not count (tetra_lmac_decode_frames_biterr_device).
+struct BiterrTable { uint32_t* out[TETRA_LMAC_MAX_JOBS]; };
+// the workgroup's entry, found as frame_group finds its job (selects over the argument block: indexing it would put it in scratch)
+__device__ __forceinline__ uint32_t* job_counts(const JobTable& tab, const BiterrTable& bt) {
+    uint32_t* c = bt.out[0];
+#pragma unroll
+    for (int i = 1; i < TETRA_LMAC_MAX_JOBS; ++i) c = i < tab.n && (int)blockIdx.x >= tab.job[i].first_group ? bt.out[i] : c;
+    return c;
+}
+// A frame kernel's staged block and its decoded halves.  Without counts the halves reuse the block's space once the forward recursion is
+// through with it; the counting instantiations hold the decoded block against the staged one, so they keep both.
+template <class Staged, bool KEEP> struct BlockLds { union { Staged in; OutW outw; }; };
+template <class Staged> struct BlockLds<Staged, true> { Staged in; OutW outw; };
 // LDS per workgroup: 3584 (type-4 bits; the decoded halves reuse the space once the forward recursion is through with them) + 1024
 // (backward CRC table) = 4608 B <= 5120: LDS never caps the kernel below 8 waves per SIMD -- which matters beside the demodulator:
 // the compiler sizes a kernel's register allocation for the occupancy its LDS allows (6992 B -> 6 waves -> 80 registers where 54 are
 // used), and next to k_fused's 199-register waves every 8 registers decide how many of this kernel's waves fit a SIMD.
 // RM: the instantiation that also knows kLayoutBbkRm -- the AACH's 30 descrambled bits through rm3014_decode (one syndrome, one look-up
 // in rm_tab), a lane per block like the pass-through.  Launched only when a job asks for it; <false> is the kernel as it was.
-template <bool RM>
+// COUNT: + 2376 (the decoded halves beside the type-4 bits, rounded up to 8) = 6992 B, 23 workgroups per CU; the counting instantiations
+// still allocate 50 to 54 registers (the 80 above was a build of its time, not a rule).
+template <bool RM, bool COUNT = false, class... Biterr>
 __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint32_t* __restrict__ dec_scratch,
-                                                        const uint32_t* __restrict__ seq_tab, const uint32_t* __restrict__ rm_tab) {
-    __shared__ union {
-        uint32_t cls[kSeqWords][kLanes];
-        OutW outw;
-    } sm;
-    static_assert(sizeof(OutW) <= sizeof(uint32_t) * kSeqWords * kLanes, "the decoded halves fit the type-4 words' space");
-    uint32_t (&cls)[kSeqWords][kLanes] = sm.cls;
+                                                        const uint32_t* __restrict__ seq_tab, const uint32_t* __restrict__ rm_tab, Biterr... biterr_pack) {
+    typedef uint32_t Cls[kSeqWords][kLanes];
+    __shared__ BlockLds<Cls, COUNT> sm;
+    static_assert(sizeof(OutW) <= sizeof(Cls), "the decoded halves fit the type-4 words' space");
+    Cls& cls = sm.in;
     OutW& outw = sm.outw;
     __shared__ uint32_t crc_inv[256];
     const int lane = threadIdx.x;
@@ -283,6 +313,13 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
         __syncthreads();
         LaneIo io{ outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
         good = decode_hard<true>(J.type345, J.type2, J.a, [&](int w) { return cls[w][lane]; }, io);
+        if constexpr (COUNT) {
+            uint32_t* counts = job_counts(tab, only_of(biterr_pack...));            // (workgroup-uniform: a workgroup has one job)
+            if (counts) {
+                const uint32_t biterr = bit_errors_hard<true>(J.type345, J.type2, J.a, [&](int h) { return outw[h][lane]; }, [&](int w) { return cls[w][lane]; });
+                if (L.blk < L.n_blocks) counts[L.blk] = biterr;
+            }
+        }
     }
     if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, good);
     if (!bbk) {
@@ -299,13 +336,13 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
 // LDS per workgroup: 27648 (432 staged bytes per lane; the decoded halves reuse the space) + 1024 (backward CRC table) = 28672 B: five
 // workgroups = five waves per CU where the hard kernel's 4608 B allow 32, so beside k_fused this launch keeps at most five decoder waves
 // on a CU and hides the latency of its ring loads with its own unrolled loads rather than with other waves.
+// COUNT: + 2376 (rounded up to 8) = 31056 B, still five workgroups per CU.
+template <bool COUNT, class... Biterr>
 __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab, uint32_t* __restrict__ dec_scratch, const uint32_t* __restrict__ seq_tab,
-                                                             const uint32_t* __restrict__ ring, uint32_t ring_words) {
+                                                             const uint32_t* __restrict__ ring, uint32_t ring_words, Biterr... biterr_pack) {
     using namespace tetra_soft;
-    __shared__ union {
-        uint32_t soft[kSoftWords][kLanes];
-        OutW outw;
-    } sm;
+    typedef uint32_t Soft[kSoftWords][kLanes];
+    __shared__ BlockLds<Soft, COUNT> sm;
     __shared__ uint32_t crc_inv[256];
     const int lane = threadIdx.x;
     FrameLane L = frame_group(tab, lane);
@@ -316,11 +353,18 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
     uint32_t seq[kSeqWords] = {};
     lane_sequence(J.type345, L.code, seq_rows(seq_tab), [&](int w, uint32_t word) { seq[w] = word; });
     stage_block(J.layout, tab.src.bitnum[L.f], tab.src.frame_type[L.f], [&](uint32_t w) { return chan[w]; }, 4u * ring_words - 1u, seq,
-                [&](int g, uint32_t word) { sm.soft[g][lane] = word; });
+                [&](int g, uint32_t word) { sm.in[g][lane] = word; });
     load_crc_inv(crc_inv, lane);
     __syncthreads();
     LaneIo io{ sm.outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
-    const bool good = decode_soft(J.type345, J.type2, J.a, [&](int w) { return sm.soft[w][lane]; }, io);
+    const bool good = decode_soft(J.type345, J.type2, J.a, [&](int w) { return sm.in[w][lane]; }, io);
+    if constexpr (COUNT) {
+        uint32_t* counts = job_counts(tab, only_of(biterr_pack...));
+        if (counts) {
+            const uint32_t biterr = bit_errors_soft(J.type345, J.type2, J.a, [&](int h) { return sm.outw[h][lane]; }, [&](int w) { return sm.in[w][lane]; });
+            if (L.blk < L.n_blocks) counts[L.blk] = biterr;
+        }
+    }
     if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, good);
     __syncthreads();
     write_rows(sm.outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
@@ -417,7 +461,6 @@ struct ScratchLease {
 // rm3014_decode runs on it, a decodable row is rewritten with the codeword's bits, byte 30 takes the distance and byte 31 a zero
 // (rows of at least 32 bytes).  The table is a trailing parameter pack -- one pointer for RM, none otherwise -- so that the instantiation
 // without the option has the argument block, and with it the instruction stream, it had before the option existed.
-template <class T> __device__ __forceinline__ T only_of(T t) { return t; }
 template <bool RM, class... Tab>
 __global__ __launch_bounds__(256) void k_lmac_bbk(const uint8_t* __restrict__ type5, int n_blocks, int in_stride,
                                                   const uint32_t* __restrict__ scramb_init, int nbits,
@@ -603,8 +646,18 @@ int tetra_lmac_decode_batch_device(int type, const uint8_t* d_type5, int n_block
 int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
                                      const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
                                      int32_t* d_crc_ok, void* hip_stream) {
+    return tetra_lmac_decode_counted_biterr_device(type, d_type5, n_blocks, d_n_blocks, in_stride, d_scramb_init, d_init_index, d_type2, out_stride,
+                                                   d_crc_ok, nullptr, hip_stream);
+}
+
+int tetra_lmac_decode_counted_biterr_device(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                                            const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                                            int32_t* d_crc_ok, uint32_t* d_biterr, void* hip_stream) {
     const int rc = check_args(type, d_type5, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_crc_ok, true);
-    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    if (rc != TETRA_OK) return rc;
+    if (d_biterr && type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;           // the AACH is not convolutionally coded: tetra_aach.h has its distance
+    if ((uintptr_t)d_biterr & 3) return TETRA_ERR_ALIGN;
+    if (n_blocks == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const BlkParam& p = blk_param(type);
     if (type == TETRA_TPSAP_T_BBK) {
@@ -619,21 +672,31 @@ int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blo
         if (!seq) return TETRA_ERR_NOMEM;
         ScratchLease scratch;
         if (const int err = scratch.take(bytes, nullptr, 0, s)) return err;
-        hipLaunchKernelGGL(k_lmac_decode, dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
-                           type == TETRA_TPSAP_T_SB1 ? 1 : 0, p.type345, p.type2, p.type1, p.a, d_type2, out_stride, d_crc_ok,
-                           scratch.p, dec_pairs, d_n_blocks, d_init_index, g_force_byte_route ? nullptr : seq);
+        const uint32_t* seq_or_bytes = g_force_byte_route ? nullptr : seq;
+        if (d_biterr)
+            hipLaunchKernelGGL((k_lmac_decode<true, uint32_t*>), dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
+                               type == TETRA_TPSAP_T_SB1 ? 1 : 0, p.type345, p.type2, p.type1, p.a, d_type2, out_stride, d_crc_ok,
+                               scratch.p, dec_pairs, d_n_blocks, d_init_index, seq_or_bytes, d_biterr);
+        else
+            hipLaunchKernelGGL(k_lmac_decode<false>, dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
+                               type == TETRA_TPSAP_T_SB1 ? 1 : 0, p.type345, p.type2, p.type1, p.a, d_type2, out_stride, d_crc_ok,
+                               scratch.p, dec_pairs, d_n_blocks, d_init_index, seq_or_bytes);
         return scratch.launched();
     }
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
 // tetra_lmac_decode_frames_device, and with `soft` lmac_impl::decode_frames_soft: the same job table, the soft kernel
-static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const lmac_impl::SoftRing* soft, void* hip_stream) {
+// d_biterr: NULL, or per job where its counts go (tetra_lmac_decode_frames_biterr_device)
+static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const lmac_impl::SoftRing* soft,
+                         uint32_t* const* d_biterr, void* hip_stream) {
     if (!src || !jobs || n_jobs < 0 || n_jobs > TETRA_LMAC_MAX_JOBS) return TETRA_ERR_ARG;
     if (n_jobs == 0) return TETRA_OK;
     if (!src->d_frames || !src->d_frame_type || src->n_frames < 0) return TETRA_ERR_ARG;
     if ((uintptr_t)src->d_frames & 15) return TETRA_ERR_ALIGN;
     JobTable tab = {};
+    BiterrTable counts = {};
+    bool any_counts = false;
     if (src->n_frames == 0) return TETRA_OK;              // no frames: no row can exist
     tab.src = DevFrames{ src->d_frames, src->d_frame_type, src->d_frame_bitnum, src->d_time_rx, src->d_time, src->frames_per_channel, src->n_frames };
     long long groups_total = 0, scratch_words = 0;
@@ -644,6 +707,9 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         const bool rm = j.type == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014);       // (the flag on any other type: refused below)
         if (rm) j.type = TETRA_TPSAP_T_BBK;
         if (j.type < 0 || j.type > 5 || j.max_rows < 0) return TETRA_ERR_ARG;
+        uint32_t* const job_counts = d_biterr ? d_biterr[i] : nullptr;
+        if (job_counts && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;       // the AACH is not convolutionally coded
+        if ((uintptr_t)job_counts & 3) return TETRA_ERR_ALIGN;
         if (j.max_rows == 0) continue;
         if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok) return TETRA_ERR_ARG;
         if (j.type != TETRA_TPSAP_T_SB1 && !j.d_frame_scramb) return TETRA_ERR_ARG;
@@ -656,6 +722,8 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         any_rm = any_rm || rm;
         if (j.out_stride < (bbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
         if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
+        counts.out[n] = job_counts;
+        any_counts = any_counts || job_counts;
         DevJob& d = tab.job[n++];
         d.row_frame = j.d_row_frame;
         d.n_rows_dev = j.d_n_rows;
@@ -684,13 +752,19 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
     const size_t bytes = (size_t)scratch_words * sizeof(uint32_t);
     ScratchLease scratch;
     if (const int err = scratch_words ? scratch.take(bytes, src->d_workspace, src->workspace_bytes, s) : TETRA_OK) return err;
+    // a launch that counts is an instantiation of its own; every other launch is the kernel it was
+    const dim3 grid((unsigned)groups_total), block(kLanes);
     if (soft) {
-        hipLaunchKernelGGL(k_lmac_frames_soft, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq,
-                           reinterpret_cast<const uint32_t*>(soft->d_ring), soft->size / 4u);
+        const uint32_t* ring = reinterpret_cast<const uint32_t*>(soft->d_ring);
+        if (any_counts) hipLaunchKernelGGL((k_lmac_frames_soft<true, BiterrTable>), grid, block, 0, s, tab, scratch.p, seq, ring, soft->size / 4u, counts);
+        else hipLaunchKernelGGL(k_lmac_frames_soft<false>, grid, block, 0, s, tab, scratch.p, seq, ring, soft->size / 4u);
     } else if (any_rm) {
         const uint32_t* rm_tab = rm3014_table();
         if (!rm_tab) { (void)scratch.give_back(); return TETRA_ERR_NOMEM; }
-        hipLaunchKernelGGL(k_lmac_frames<true>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, rm_tab);
+        if (any_counts) hipLaunchKernelGGL((k_lmac_frames<true, true, BiterrTable>), grid, block, 0, s, tab, scratch.p, seq, rm_tab, counts);
+        else hipLaunchKernelGGL(k_lmac_frames<true>, grid, block, 0, s, tab, scratch.p, seq, rm_tab);
+    } else if (any_counts) {
+        hipLaunchKernelGGL((k_lmac_frames<false, true, BiterrTable>), grid, block, 0, s, tab, scratch.p, seq, nullptr, counts);
     } else {
         hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, nullptr);
     }
@@ -698,7 +772,12 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
 }
 
 int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
-    return decode_frames(src, jobs, n_jobs, nullptr, hip_stream);
+    return decode_frames(src, jobs, n_jobs, nullptr, nullptr, hip_stream);
+}
+
+int tetra_lmac_decode_frames_biterr_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, uint32_t* const* d_biterr,
+                                           void* hip_stream) {
+    return decode_frames(src, jobs, n_jobs, nullptr, d_biterr, hip_stream);
 }
 
 size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {
@@ -784,7 +863,13 @@ int tetra_lmac_track_sync_lists_device(const uint8_t* d_sb1_type2, int type2_str
 
 int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
                             uint8_t* type2, int out_stride, int32_t* crc_ok, int device) {
+    return tetra_lmac_decode_batch_biterr(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, nullptr, device);
+}
+
+int tetra_lmac_decode_batch_biterr(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                                   uint8_t* type2, int out_stride, int32_t* crc_ok, uint32_t* biterr, int device) {
     int rc = check_args(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, false);
+    if (rc == TETRA_OK && biterr && type == TETRA_TPSAP_T_BBK) rc = TETRA_ERR_ARG;
     if (rc != TETRA_OK || n_blocks == 0) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
@@ -793,6 +878,8 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
     DevMem<uint8_t> d_in, d_out;
     DevMem<uint32_t> d_init;
     DevMem<int32_t> d_ok;
+    DevMem<uint32_t> d_biterr;
+    if (biterr && d_biterr.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess) return TETRA_ERR_NOMEM;
     const size_t in_bytes = (size_t)n_blocks * in_stride, out_bytes = (size_t)n_blocks * out_stride;
     if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_ok.reserve(sizeof(int32_t) * n_blocks) != hipSuccess)
         return TETRA_ERR_NOMEM;
@@ -801,7 +888,8 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
         if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
     }
     if (hipMemcpy(d_in, type5, in_bytes, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
-    rc = tetra_lmac_decode_batch_device(type, d_in, n_blocks, in_stride, d_init, d_out, out_stride, d_ok, nullptr);
+    rc = tetra_lmac_decode_counted_biterr_device(type, d_in, n_blocks, nullptr, in_stride, d_init, nullptr, d_out, out_stride, d_ok,
+                                                 biterr ? (uint32_t*)d_biterr : nullptr, nullptr);
     if (rc != TETRA_OK) return rc;
     if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
     // only the type2_bits columns: the caller's row padding is left alone
@@ -811,14 +899,16 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
                           : hipMemcpy2D(type2, out_stride, d_out, out_stride, row, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
         return TETRA_ERR_HIP;
     if (hipMemcpy(crc_ok, d_ok, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
 }
 
 }  // extern "C"
 
-int lmac_impl::decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream) {
+int lmac_impl::decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream,
+                                  uint32_t* const* d_biterr) {
     // a ring of whole aligned words, a power of two in size; the frames' bit numbers and channels
     if (!ring.d_ring || ring.size < 4 || (ring.size & (ring.size - 1)) || ((uintptr_t)ring.d_ring & 3)) return TETRA_ERR_ARG;
     if (src && (!src->d_frame_bitnum || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
-    return decode_frames(src, jobs, n_jobs, &ring, hip_stream);
+    return decode_frames(src, jobs, n_jobs, &ring, d_biterr, hip_stream);
 }

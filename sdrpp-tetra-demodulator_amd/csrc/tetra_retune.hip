@@ -36,11 +36,14 @@ __global__ __launch_bounds__(kLanes) void k_reset_demod(retune::DemodView v, ret
     retune::reset_soft_channel(soft, c, threadIdx.x, kLanes);
 }
 
-__global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retune::CellView cell, const int32_t* __restrict__ channels, int n_channels) {
+// link: the channels' link figures as words (tetra_rx_link_t, TETRA_RX_FLAG_BITERR; no words without the flag), zeroed like the cell state
+__global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retune::CellView cell, retune::CellView link, const int32_t* __restrict__ channels,
+                                                       int n_channels) {
     const int c = channels[blockIdx.x];
     if (c < 0 || c >= n_channels) return;
     retune::reset_bsync_channel(b, c, threadIdx.x, kLanes);
     retune::reset_cell_channel(cell, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(link, c, threadIdx.x, kLanes);
 }
 
 // list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
@@ -80,6 +83,8 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     TETRA_TRY(retune_impl::bsync_view(h->bs, &bv));
     static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0, "reset in 32-bit words");
     retune::CellView cv = { reinterpret_cast<uint32_t*>(h->cell.get()), (int32_t)(sizeof(tetra_lmac_cell_state_t) / 4) };
+    static_assert(sizeof(tetra_rx_link_t) % 4 == 0, "reset in 32-bit words");
+    const retune::CellView lv = { reinterpret_cast<uint32_t*>(h->link.get()), h->biterr ? (int32_t)(sizeof(tetra_rx_link_t) / 4) : 0 };
     if (!h->ev_reset) HIP_TRY(h, hipEventCreateWithFlags(h->ev_reset.put(), hipEventDisableTiming));
     const int last = (int)((h->calls - 1) & 1);
     hipStream_t st = h->one_stream ? s : static_cast<hipStream_t>(h->tail);
@@ -97,7 +102,7 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
         HIP_TRY(h, hipEventRecord(h->ev_reset, s));
         HIP_TRY(h, hipStreamWaitEvent(st, h->ev_reset, 0));
     }
-    hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, d_channels, h->C);
+    hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
     HIP_TRY(h, hipGetLastError());
     if (h->one_stream) HIP_TRY(h, hipEventRecord(h->ev_reset, s));
     h->reset_pending = true;

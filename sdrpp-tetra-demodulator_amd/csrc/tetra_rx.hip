@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/tetra_aach.h"
+#include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_rx.h"
 #include "lmac_impl.hpp"
 #include "rx_handle.hpp"
@@ -72,11 +73,59 @@ __global__ __launch_bounds__(256) void k_rx_pack_byte(const uint8_t* __restrict_
     if (j < n) out[j] = t2[(size_t)j * in_stride + at];
 }
 
+// TETRA_RX_FLAG_BITERR: a call's coded rows into the channels' link figures (tetra_rx_link_t).  The rows of a kind are in (channel, frame)
+// order and chan_first says where a channel's begin in each frame list, so a wavefront takes one channel, walks its rows of every coded
+// kind, reduces across its lanes and adds to the channel's figures: no two wavefronts share a channel and tails run one after the other,
+// so plain stores do.
+struct LinkKind {
+    const int32_t* ok;            // the kind's verdicts and counts, per row
+    const uint32_t* biterr;
+    int list;                     // the frame list its rows come from
+};
+struct LinkTable {
+    LinkKind kind[TETRA_RX_N_KINDS];
+    int n;
+};
+__global__ __launch_bounds__(64) void k_rx_link(const LinkTable tab, const int32_t* __restrict__ chan_first, const int32_t* __restrict__ counts, int C,
+                                                tetra_rx_link_t* __restrict__ link) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    uint32_t bits = 0, errors = 0, blocks = 0, bad = 0;          // (a call's share of one channel: far below 2^32)
+    for (int k = 0; k < tab.n; ++k) {
+        const LinkKind K = tab.kind[k];
+        const int first = chan_first[(size_t)K.list * C + c];
+        const int end = c + 1 < C ? chan_first[(size_t)K.list * C + c + 1] : counts[K.list];
+        for (int j = first + lane; j < end; j += 64) {
+            const bool good = K.ok[j] != 0;
+            const uint32_t v = K.biterr[j];
+            blocks += 1u;
+            bad += good ? 0u : 1u;
+            bits += good ? v >> 16 : 0u;
+            errors += good ? v & 0xffffu : 0u;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        bits += (uint32_t)__shfl_xor((int)bits, d);
+        errors += (uint32_t)__shfl_xor((int)errors, d);
+        blocks += (uint32_t)__shfl_xor((int)blocks, d);
+        bad += (uint32_t)__shfl_xor((int)bad, d);
+    }
+    if (lane == 0) {
+        tetra_rx_link_t l = link[c];
+        l.bits += bits;
+        l.bit_errors += errors;
+        l.blocks += blocks;
+        l.blocks_crc_bad += bad;
+        link[c] = l;
+    }
+}
+
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
 
 int zero_results(tetra_rx* h) {
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->counts[b], 0, sizeof(int32_t) * TETRA_N_LISTS));
     HIP_TRY(h, hipMemset(h->cell, 0, sizeof(tetra_lmac_cell_state_t) * (size_t)h->C));
+    if (h->biterr) HIP_TRY(h, hipMemset(h->link, 0, sizeof(tetra_rx_link_t) * (size_t)h->C));
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->nbits[b], 0, sizeof(int32_t) * (size_t)h->C));
     if (h->soft) {      // fresh channels: previous symbol (1,1)/sqrt(2), bit count 0 (both parities: the next call reads either)
         const std::vector<float> prev((size_t)4 * h->C, tetra_soft::kFreshPrev);
@@ -123,22 +172,38 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     {   // SB1 first: its SYNC PDUs set the code and the clock for everything else in the same burst (tetra_lower_mac.c:246-275)
         const KindBufs& r = h->res[b][TETRA_RX_KIND_SB1];
         const tetra_lmac_job_t j = job_of(TETRA_RX_KIND_SB1, false);
-        TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s) : tetra_lmac_decode_frames_device(&src, &j, 1, s));
+        uint32_t* const counts = h->biterr ? r.biterr.get() : nullptr;          // (without the flag: the launches as they were)
+        TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr)
+                          : tetra_lmac_decode_frames_biterr_device(&src, &j, 1, h->biterr ? &counts : nullptr, s));
         TETRA_TRY(tetra_lmac_track_sync_lists_device(r.t2, kKinds[TETRA_RX_KIND_SB1].out_stride, r.ok, h->ft, h->nf,
                                                  h->chan_first + (size_t)TETRA_LIST_SYNC * h->C, h->C, h->F, h->cell, h->row_scramb, h->row_time_rx,
                                                  h->row_time, h->fb, reinterpret_cast<tetra_lmac_label_t*>(r.blocks.get()), s));
     }
     HIP_TRY(h, hipEventRecord(h->ev_stage[2], s));
     tetra_lmac_job_t jobs[TETRA_RX_N_KINDS];
+    uint32_t* counts[TETRA_RX_N_KINDS];          // per job where its bit-error counts go (NULL: the AACH)
     int nj = 0;
     for (int k : kJobOrder)
-        if ((h->kinds & (1 << k)) && !(h->soft && k == TETRA_RX_KIND_BBK)) jobs[nj++] = job_of(k, true);
+        if ((h->kinds & (1 << k)) && !(h->soft && k == TETRA_RX_KIND_BBK)) {
+            counts[nj] = h->res[b][k].biterr;
+            jobs[nj++] = job_of(k, true);
+        }
     if (h->soft) {      // the coded kinds from the ring; the AACH from the packed frames as ever, a launch of its own
-        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s));
+        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s, h->biterr ? counts : nullptr));
         nj = 0;
-        if (h->kinds & (1 << TETRA_RX_KIND_BBK)) jobs[nj++] = job_of(TETRA_RX_KIND_BBK, true);
+        if (h->kinds & (1 << TETRA_RX_KIND_BBK)) {
+            counts[nj] = nullptr;
+            jobs[nj++] = job_of(TETRA_RX_KIND_BBK, true);
+        }
     }
-    TETRA_TRY(tetra_lmac_decode_frames_device(&src, jobs, nj, s));
+    TETRA_TRY(tetra_lmac_decode_frames_biterr_device(&src, jobs, nj, h->biterr ? counts : nullptr, s));
+    if (h->biterr) {
+        LinkTable tab = {};
+        for (int k = 0; k < TETRA_RX_N_KINDS; ++k)
+            if ((h->kinds & (1 << k)) && k != TETRA_RX_KIND_BBK) tab.kind[tab.n++] = LinkKind{ h->res[b][k].ok, h->res[b][k].biterr, kKinds[k].list };
+        hipLaunchKernelGGL(k_rx_link, dim3((unsigned)h->C), dim3(64), 0, s, tab, h->chan_first.get(), h->counts[b].get(), h->C, h->link.get());
+        HIP_TRY(h, hipGetLastError());
+    }
     HIP_TRY(h, hipEventRecord(h->ev_stage[3], s));
     return TETRA_OK;
 }
@@ -166,7 +231,7 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT)))
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR)))
         return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
@@ -176,6 +241,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     h->one_stream = (cfg->flags & TETRA_RX_FLAG_ONE_STREAM) != 0;
     h->aach_rm = (cfg->flags & TETRA_RX_FLAG_AACH_RM3014) != 0;
     h->soft = (cfg->flags & TETRA_RX_FLAG_SOFT) != 0;
+    h->biterr = (cfg->flags & TETRA_RX_FLAG_BITERR) != 0;
     TETRA_TRY(tetra_demod_create(&cfg->demod, h->dem.put()));
     h->C = cfg->demod.n_channels;
     int dev = cfg->demod.device;
@@ -201,7 +267,8 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
         for (int k = 0; k < TETRA_RX_N_KINDS && ok; k++) {
             if (!(h->kinds & (1 << k))) continue;
             KindBufs& r = h->res[b][k];
-            ok = dalloc(r.t2, n * kKinds[k].out_stride) && dalloc(r.ok, n) && dalloc(r.blocks, n);
+            ok = dalloc(r.t2, n * kKinds[k].out_stride) && dalloc(r.ok, n) && dalloc(r.blocks, n) &&
+                 (!h->biterr || k == TETRA_RX_KIND_BBK || dalloc(r.biterr, n));
             r.row_frame = h->lists[b] + (size_t)kKinds[k].list * n;
             r.n_rows = h->counts[b] + kKinds[k].list;
         }
@@ -210,6 +277,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
          dalloc(h->chan_first, (size_t)TETRA_N_LISTS * h->C) && dalloc(h->index_work, (size_t)TETRA_N_LISTS * ((n + 255) / 256)) &&
          dalloc(h->row_scramb, n) && dalloc(h->row_time_rx, n) && dalloc(h->row_time, n) && dalloc(h->cell, (size_t)h->C);
     for (auto& e : h->ev_stage) ok = ok && hipEventCreate(e.put()) == hipSuccess;
+    if (ok && h->biterr) ok = dalloc(h->link, (size_t)h->C);
     if (ok && h->soft) {
         h->soft_R = tetra_soft::ring_size(h->stride);
         ok = dalloc(h->sym, (size_t)h->C * h->stride) && dalloc(h->soft_ring, (size_t)h->C * h->soft_R) && dalloc(h->soft_prev, (size_t)4 * h->C) &&
@@ -391,6 +459,51 @@ int tetra_rx_fetch_aach_dist(tetra_rx_t* h, int which, uint8_t* dist, int capaci
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(dist, h->fetch_stage, (size_t)n, hipMemcpyDeviceToHost, h->fetch_s));
     HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
+    return TETRA_OK;
+}
+
+// the chain's share of tetra_biterr.h
+static bool counts_kind(const tetra_rx* h, int kind) { return h->biterr && kind != TETRA_RX_KIND_BBK && (h->kinds & (1 << kind)); }
+
+int tetra_rx_fetch_biterr(tetra_rx_t* h, int which, int kind, uint32_t* out, int capacity, int* n_rows) {
+    if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
+    if (!counts_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
+    *n_rows = 0;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
+    const KindBufs& r = h->res[b][kind];
+    int32_t n = 0;
+    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
+    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
+    *n_rows = n;
+    if (n > capacity) return out ? TETRA_ERR_SIZE : TETRA_OK;
+    if (n == 0 || !out) return TETRA_OK;
+    HIP_TRY(h, hipMemcpy(out, r.biterr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return TETRA_OK;
+}
+
+int tetra_rx_biterr_device(tetra_rx_t* h, int which, int kind, const uint32_t** d_biterr, void* hip_stream) {
+    if (!h || !d_biterr || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1) return TETRA_ERR_ARG;
+    if (!counts_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
+    *d_biterr = h->res[b][kind].biterr;
+    return TETRA_OK;
+}
+
+int tetra_rx_get_link(tetra_rx_t* h, int first, int count, tetra_rx_link_t* out) {
+    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
+    if (!h->biterr) return TETRA_ERR_UNSUPPORTED;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    if (count) HIP_TRY(h, hipMemcpy(out, h->link + first, sizeof(tetra_rx_link_t) * (size_t)count, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
 

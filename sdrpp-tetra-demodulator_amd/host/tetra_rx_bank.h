@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "ext/tetra_biterr.h"
 #include "tetra_rx.h"
 #include "tetra_rx_out.h"
 
@@ -119,6 +120,20 @@ public:
     int cells(std::vector<tetra_lmac_cell_state_t>& out) {
         out.resize((size_t)channels_);
         return tetra_rx_get_cell(h_, 0, channels_, out.data());
+    }
+    // TETRA_RX_FLAG_BITERR (tetra_biterr.h): errors | compared << 16 of a coded kind's rows, in fetch()'s order -- an estimate of the
+    // channel's bit errors that is meaningful for rows with a good CRC ...
+    int fetchBitErrors(int kind, std::vector<uint32_t>& out, int which = 0) {
+        int n = 0;
+        const int rc = tetra_rx_fetch_biterr(h_, which, kind, nullptr, 0, &n);
+        if (rc != TETRA_OK) return rc;
+        out.resize((size_t)n);
+        return n ? tetra_rx_fetch_biterr(h_, which, kind, out.data(), n, &n) : TETRA_OK;
+    }
+    // ... and every channel's link figures since the last reset
+    int links(std::vector<tetra_rx_link_t>& out) {
+        out.resize((size_t)channels_);
+        return tetra_rx_get_link(h_, 0, channels_, out.data());
     }
     int syncStates(std::vector<tetra_bsync_state_t>& out) {
         out.resize((size_t)channels_);
@@ -241,6 +256,27 @@ public:
         std::vector<tetra_lmac_cell_state_t> part;
         for (auto& s : shards_) {
             const int rc = s->bank.cells(part);
+            if (rc != TETRA_OK) return rc;
+            out.insert(out.end(), part.begin(), part.end());
+        }
+        return TETRA_OK;
+    }
+    // the shards' counts and link figures one after the other: fetch()'s row order, cells()'s channel order
+    int fetchBitErrors(int kind, std::vector<uint32_t>& out, int which = 0) {
+        out.clear();
+        std::vector<uint32_t> part;
+        for (auto& s : shards_) {
+            const int rc = s->bank.fetchBitErrors(kind, part, which);
+            if (rc != TETRA_OK) return rc;
+            out.insert(out.end(), part.begin(), part.end());
+        }
+        return TETRA_OK;
+    }
+    int links(std::vector<tetra_rx_link_t>& out) {
+        out.clear();
+        std::vector<tetra_rx_link_t> part;
+        for (auto& s : shards_) {
+            const int rc = s->bank.links(part);
             if (rc != TETRA_OK) return rc;
             out.insert(out.end(), part.begin(), part.end());
         }

@@ -56,13 +56,19 @@ AACH_SIGNATURES = {
     "tetra_lmac_rm3014_decode_device": (i32, [vp, i32, vp, vp, vp]),
     "tetra_lmac_decode_aach_rm3014_device": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
 }
-LMAC_EXPORTS, AACH_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES)
+# include/ext/tetra_biterr.h: the lower MAC's share (the receive chain's is in rx_binding.BITERR_ABI)
+BITERR_ABI = {
+    "tetra_lmac_decode_counted_biterr_device": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
+    "tetra_lmac_decode_batch_biterr": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, vp, i32]),
+    "tetra_lmac_decode_frames_biterr_device": (i32, [P(Frames), P(Job), i32, P(vp), vp]),
+}
+LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES}, optional=AACH_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI}, optional=AACH_EXPORTS + BITERR_EXPORTS)
 
 
 def force_byte_route(on):
@@ -110,6 +116,30 @@ def decode_counted_device(blk_type, d_type5, capacity, d_n_blocks, in_stride, d_
          ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), stream_ptr(stream))
 
 
+def split_biterr(biterr):
+    """errors | compared << 16 (include/ext/tetra_biterr.h) -> (errors, compared) as int arrays."""
+    v = np.asarray(biterr).astype(np.int64) & 0xffffffff          # (an int32 view of the words included)
+    return v & 0xffff, v >> 16
+
+
+def decode_batch_biterr(blk_type, type5, scramb=None, device=-1):
+    """tetra_lmac_decode_batch_biterr: decode_batch plus the channel bit-error counts -> (type2, crc_ok, biterr uint32 [n])."""
+    rows = np.ascontiguousarray(type5, np.uint8)
+    n, in_stride = rows.shape
+    ost = out_stride_for(blk_type)
+    out, ok, be = np.zeros((n, ost), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
+    call(_lib().tetra_lmac_decode_batch_biterr, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), ptr(be), device)
+    return out, ok, be
+
+
+def decode_counted_biterr_device(blk_type, d_type5, capacity, d_n_blocks, in_stride, d_scramb, d_init_index, d_type2, out_stride, d_crc_ok,
+                                 d_biterr, stream=None):
+    """tetra_lmac_decode_counted_biterr_device: decode_counted_device plus d_biterr (int32 / uint32 tensor [capacity], or None)."""
+    call(_lib().tetra_lmac_decode_counted_biterr_device, int(blk_type), ptr(d_type5), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
+         ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), ptr(d_biterr), stream_ptr(stream))
+
+
 def track_scramb_device(d_sb1_type2, type2_stride, d_crc_ok, d_valid, n_channels, frames_per_channel, d_chan_scramb, d_row_scramb,
                         stream=None):
     call(_lib().tetra_lmac_track_scramb_device, ptr(d_sb1_type2), int(type2_stride), ptr(d_crc_ok), ptr(d_valid), int(n_channels),
@@ -144,6 +174,16 @@ def decode_frames_device(d_frames, d_frame_type, jobs, frames_per_channel=0, d_f
     src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
                  ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
     call(_lib().tetra_lmac_decode_frames_device, C.byref(src), _job_array(jobs), len(jobs), stream_ptr(stream))
+
+
+def decode_frames_biterr_device(d_frames, d_frame_type, jobs, frames_per_channel=0, d_frame_bitnum=None, d_time_rx=None, d_time=None, stream=None,
+                                d_workspace=None, counted=True):
+    """tetra_lmac_decode_frames_biterr_device: decode_frames_device whose jobs may carry `biterr` (int32 / uint32 tensor [max_rows], or
+    None / absent: the job does not count).  counted=False hands in no array at all."""
+    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
+                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    arr = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
+    call(_lib().tetra_lmac_decode_frames_biterr_device, C.byref(src), _job_array(jobs), len(jobs), arr if counted else None, stream_ptr(stream))
 
 
 def track_sync_lists_device(d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync, n_channels, frames_per_channel,

@@ -14,6 +14,7 @@ N_KINDS = 6
 FLAG_ONE_STREAM = 1
 FLAG_AACH_RM3014 = 2          # TETRA_RX_FLAG_AACH_RM3014
 FLAG_SOFT = 8                 # TETRA_RX_FLAG_SOFT: the coded kinds decoded from soft values (4 is no flag)
+FLAG_BITERR = 32              # TETRA_RX_FLAG_BITERR: channel bit-error counts per coded block, link figures per channel (tetra_biterr.h)
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
 
@@ -33,6 +34,11 @@ BLOCK_DTYPE = np.dtype([("channel", "<i4"), ("frame_slot", "<i4"), ("bitnum", "<
 class CellState(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("scramb_init", "colour_code", "mcc", "mnc", "tcd_tn", "tcd_fn", "tcd_mn", "phy_tn", "phy_fn",
                                           "phy_mn")]
+
+
+class Link(C.Structure):
+    """tetra_rx_link_t."""
+    _fields_ = [("bits", C.c_uint64), ("bit_errors", C.c_uint64), ("blocks", C.c_uint32), ("blocks_crc_bad", C.c_uint32)]
 
 
 # include/tetra_rx.h
@@ -69,15 +75,21 @@ OUT_SIGNATURES = {
 RETUNE_SIGNATURES = {"tetra_rx_reset_channels_device": (i32, [vp, vp, i32, vp])}
 # include/tetra_aach.h (the AACH decoded with its Reed-Muller code): the chain's share
 AACH_SIGNATURES = {"tetra_rx_fetch_aach_dist": (i32, [vp, i32, vp, i32, P(i32)])}
+# include/ext/tetra_biterr.h (channel bit-error counts): the chain's share
+BITERR_ABI = {
+    "tetra_rx_fetch_biterr": (i32, [vp, i32, i32, vp, i32, P(i32)]),
+    "tetra_rx_biterr_device": (i32, [vp, i32, i32, P(vp), vp]),
+    "tetra_rx_get_link": (i32, [vp, i32, i32, P(Link)]),
+}
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
-RX_RETUNE_EXPORTS, RX_AACH_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES)
+RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
-    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES},
-                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI},
+                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS)
 
 
 def type1_bits(kind):
@@ -161,6 +173,32 @@ class RxChain:
         got = C.c_int(0)
         call(self._lib.tetra_rx_fetch_aach_dist, self._h, which, ptr(dist), max(n.value, 1), C.byref(got))
         return dist[:got.value]
+
+    def fetch_biterr(self, kind, which=0):
+        """tetra_rx_fetch_biterr: (errors, compared) int arrays [n] of a coded kind's rows, in fetch(kind)'s order -- the distance from
+        the received block to the decoded codeword and the positions it was taken over; an estimate of the channel's bit errors that
+        is meaningful for rows with a good CRC.  Needs a handle created with FLAG_BITERR."""
+        n = C.c_int(0)
+        call(self._lib.tetra_rx_fetch_biterr, self._h, which, kind, None, 0, C.byref(n))
+        v = np.zeros(max(n.value, 1), np.uint32)
+        got = C.c_int(0)
+        call(self._lib.tetra_rx_fetch_biterr, self._h, which, kind, ptr(v), max(n.value, 1), C.byref(got))
+        v = v[:got.value].astype(np.int64)
+        return v & 0xffff, v >> 16
+
+    def biterr_device(self, kind, which=0, stream=None):
+        """tetra_rx_biterr_device -> the raw device address of the kind's counts (uint32 per row of rows_device)."""
+        d = C.c_void_p()
+        call(self._lib.tetra_rx_biterr_device, self._h, which, kind, C.byref(d), stream_ptr(stream))
+        return d.value
+
+    def links(self, first=0, count=None):
+        """tetra_rx_get_link: per channel a dict bits / bit_errors (summed over the coded blocks with a good CRC since the last reset)
+        and blocks / blocks_crc_bad (every coded block)."""
+        count = self.n_channels - first if count is None else count
+        arr = (Link * max(count, 1))()
+        call(self._lib.tetra_rx_get_link, self._h, first, count, arr)
+        return [dict(bits=int(a.bits), bit_errors=int(a.bit_errors), blocks=int(a.blocks), blocks_crc_bad=int(a.blocks_crc_bad)) for a in arr[:count]]
 
     def cells(self, first=0, count=None):
         count = self.n_channels - first if count is None else count

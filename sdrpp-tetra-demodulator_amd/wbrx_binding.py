@@ -205,6 +205,10 @@ class WidebandRx:
             return torch.zeros((0, self.n_bins), dtype=torch.complex64, device=stream.device)
         return torch.as_tensor(_DeviceArray(p, (n, self.n_bins), "<c8"), device=stream.device)
 
+    def links(self, first=0, count=None):
+        """The carrier slots' link figures (RxChain.links of the chain; needs FLAG_BITERR in `flags`).  A retune zeroes a moved slot's."""
+        return self.rx.links(first, count)
+
     def bin_power(self):
         out = np.zeros(self.M, np.float32)
         call(self._lib.tetra_wbrx_bin_power, self._h, ptr(out))
