@@ -64,6 +64,10 @@ enum {
                                       received block to its decoded codeword, and every channel running link figures (tetra_biterr.h:
                                       tetra_rx_fetch_biterr, tetra_rx_get_link).  Composes with every other flag; blocks, rows, labels and
                                       every fetch / delivery entry are unchanged.  16 and 64 are not flags either (tests hold them refused). */
+    TETRA_RX_FLAG_SYNC_TOLERANT = 128, /* the burst synchroniser's tolerant lock with its defaults {3, 5, 16} (ext/tetra_sync_tol.h): in LOCKED a
+                                      training sequence is looked for at the expected position only and may carry a few bit errors, and lock is
+                                      dropped only behind several consecutive misses.  DEPARTS FROM THE REFERENCE (more frames at low Es/N0);
+                                      composes with every other flag; row formats, labels and every fetch / delivery entry are unchanged */
     TETRA_RX_FLAG_SOFT = 8         /* soft decisions: SB1, SB2, NDB 1 / 2 and SCH/F are decoded from the demodulator's symbols -- per bit a
                                       6-bit soft value of the differential phase, kept per channel in a ring indexed by `bitnum` -- where
                                       the default slices every symbol to two hard bits first.  Same decoder as the reference's

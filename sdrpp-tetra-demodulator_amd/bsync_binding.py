@@ -37,9 +37,28 @@ SIGNATURES = {
 BSYNC_EXPORTS = list(SIGNATURES)
 
 
+class BsyncTolerance(C.Structure):
+    """tetra_bsync_tolerance_t."""
+    _fields_ = [("tol_norm", C.c_int32), ("tol_sync", C.c_int32), ("max_miss", C.c_int32)]
+
+
+# include/ext/tetra_sync_tol.h (the tolerant lock): the synchroniser's share
+SYNC_TOL_ABI = {
+    "tetra_bsync_set_tolerance": (i32, [vp, P(BsyncTolerance)]),
+    "tetra_bsync_get_misses": (i32, [vp, i32, i32, vp]),
+}
+SYNC_TOL_DEFAULT = (3, 5, 16)
+
+
+def tolerance_arg(tol):
+    """None -> NULL (the reference's rule); (tol_norm, tol_sync, max_miss) -> a tetra_bsync_tolerance_t."""
+    return None if tol is None else C.byref(BsyncTolerance(*[int(v) for v in tol]))
+
+
 @functools.lru_cache(None)
 def _lib():
-    return declare(load_library(), SIGNATURES)
+    # (a TETRA_DEMOD_LIB override may be an older build without the tolerant lock)
+    return declare(load_library(), {**SIGNATURES, **SYNC_TOL_ABI}, optional=list(SYNC_TOL_ABI))
 
 
 class BurstSync:
@@ -87,6 +106,17 @@ class BurstSync:
         """Frames as [C][max_frames][16] int32 / uint32 words (first bit = most significant) instead of [C][max_frames][512] bytes."""
         call(_lib().tetra_bsync_process_packed_device, self._h, ptr(d_bits), int(bits_stride), ptr(d_n_bits), ptr(d_frames_packed),
              ptr(d_frame_type), ptr(d_frame_bitnum), ptr(d_n_frames), stream_ptr(stream))
+
+    def set_tolerance(self, tol):
+        """tetra_bsync_set_tolerance: (tol_norm, tol_sync, max_miss) from the next process call on, None = the reference's rule."""
+        call(_lib().tetra_bsync_set_tolerance, self._h, tolerance_arg(tol))
+
+    def misses(self, first=0, count=None):
+        """tetra_bsync_get_misses: int32 [count], the channels' consecutive LOCKED frames without a training sequence."""
+        count = self.n_channels - first if count is None else count
+        out = np.zeros(max(count, 1), np.int32)
+        call(_lib().tetra_bsync_get_misses, self._h, int(first), int(count), ptr(out))
+        return out[:count]
 
     def states(self, first=0, count=None):
         count = self.n_channels - first if count is None else count

@@ -23,6 +23,11 @@
 //                of {sync, normal 1, normal 2}; sync at 214 / normal at 244 -> burst reported with its type; sync
 //                elsewhere or nothing found -> UNLOCKED; normal elsewhere -> frame dropped, still LOCKED.
 // All bit numbers are uint32 and wrap like the reference's unsigned ints.
+//
+// Tolerant lock (include/ext/tetra_sync_tol.h; opt-in, a departure from the reference): UNLOCKED and KNOW_FSTART as above, but a LOCKED
+// call looks only at the expected positions of the frame -- sync at 214, normal 1 / 2 at 244 --, accepts up to tol_sync / tol_norm bit
+// errors there (tolerant_frame_eval) and falls back to UNLOCKED only behind max_miss consecutive frames without a candidate
+// (first_unlock).  Only the sync bitmap is needed then.  run_tolerant() is that policy; run() is the reference's rule.
 #pragma once
 
 #include <stdint.h>
@@ -115,6 +120,19 @@ BS_FN void match_word(const uint32_t* s, int w, int x0, int xe, uint32_t& m_sync
     m_n2 = bit_reverse(ap) & range_mask(w, x0, xe - 22 + 1);
 }
 
+// match_word's sync bitmap alone (the tolerant lock needs no other)
+BS_FN uint32_t match_word_sync(const uint32_t* s, int w, int x0, int xe) {
+    const uint32_t w0 = s[w], w1 = s[w + 1], w2 = s[w + 2];
+    uint32_t ay = 0xffffffffu;
+    constexpr uint64_t seq_y = ((uint64_t)kHeadY << 16) | kTailY;
+#pragma unroll
+    for (int k = 0; k < 38; ++k) {
+        const uint32_t v = shifted_word(w0, w1, w2, k);
+        ay &= ((seq_y >> (37 - k)) & 1u) ? v : ~v;
+    }
+    return bit_reverse(ay) & range_mask(w, x0, xe - 38 + 1);
+}
+
 // first set bit of bitmap m (bit x at word x>>5, bit x&31) in [a, b), or -1
 BS_FN int first_set(const uint32_t* m, int a, int b) {
     if (a >= b) return -1;
@@ -192,6 +210,68 @@ BS_FN FrameEval locked_frame_eval(const uint32_t* s, const uint32_t* m_sync, con
     return e;
 }
 
+// ---- tolerant lock --------------------------------------------------------------------------------------------------------------------
+struct Tolerance {                  // tetra_bsync_tolerance_t
+    int32_t tol_norm;               // 0..4 bit errors accepted in a normal training sequence at 244
+    int32_t tol_sync;               // 0..6 in the sync training sequence at 214
+    int32_t max_miss;               // 1..255 consecutive frames without a candidate before the receiver unlocks
+};
+constexpr int kTolNormMax = 4, kTolSyncMax = 6, kMaxMissMax = 255;
+constexpr bool tolerance_valid(const Tolerance& t) {           // (constexpr: host and device)
+    return t.tol_norm >= 0 && t.tol_norm <= kTolNormMax && t.tol_sync >= 0 && t.tol_sync <= kTolSyncMax && t.max_miss >= 1 && t.max_miss <= kMaxMissMax;
+}
+
+// One tolerant LOCKED call on the frame [bx, bx + 510): Hamming distances of the three windows to y / n / p, the candidate with the
+// smallest distance (ties: sync, normal 1, normal 2), or -1.  Nothing else of the buffer is looked at.
+BS_FN int tolerant_frame_eval(const uint32_t* s, int bx, const Tolerance& t) {
+    const int ds = __builtin_popcount(window(s, bx + 214, 22) ^ kHeadY) + __builtin_popcount(window(s, bx + 236, 16) ^ kTailY);
+    const int d1 = __builtin_popcount(window(s, bx + 244, 22) ^ kHeadN);
+    const int d2 = __builtin_popcount(window(s, bx + 244, 22) ^ kHeadP);
+    int type = -1, best = 0;
+    if (ds <= t.tol_sync) { type = kSync; best = ds; }
+    if (d1 <= t.tol_norm && (type < 0 || d1 < best)) { type = kNorm1; best = d1; }
+    if (d2 <= t.tol_norm && (type < 0 || d2 < best)) { type = kNorm2; best = d2; }
+    return type;
+}
+
+// The consecutive-miss rule over n <= 64 frames evaluated side by side: bit k of pass_mask = frame k was reported.  The miss counter
+// enters with misses_in (< max_miss).  index: the first frame at which the counter reaches max_miss (the receiver unlocks behind it and
+// the frames after it are not LOCKED calls), or -1; misses: the counter behind frame `index` (0) or, without one, behind frame n - 1.
+struct Unlock { int index; int misses; };
+// the definition, frame by frame
+BS_FN Unlock first_unlock(uint64_t pass_mask, int n, int misses_in, int max_miss) {
+    int m = misses_in;
+    for (int k = 0; k < n; ++k) {
+        m = ((pass_mask >> k) & 1u) ? 0 : m + 1;
+        if (m >= max_miss) return Unlock{ k, 0 };
+    }
+    return Unlock{ -1, m };
+}
+// the same with bit operations (the kernel's: pass_mask is a ballot).  A run that reaches max_miss either started in the carried counter
+// -- then frames 0 .. max_miss - misses_in - 1 all miss -- or lies inside the mask: max_miss consecutive miss bits, found by and-ing the
+// mask with shifted copies of itself, doubling the covered length.  The first kind ends no later than any of the second.
+BS_FN Unlock first_unlock_bits(uint64_t pass_mask, int n, int misses_in, int max_miss) {
+    if (n <= 0) return Unlock{ -1, misses_in };
+    const uint64_t all = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+    const uint64_t pass = pass_mask & all, miss = ~pass_mask & all;
+    const int need = max_miss - misses_in;                      // frames still to miss for the carried run (>= 1)
+    if (need <= n) {
+        const uint64_t head = need >= 64 ? ~0ull : ((1ull << need) - 1ull);
+        if ((miss & head) == head) return Unlock{ need - 1, 0 };
+    }
+    if (max_miss <= n) {
+        uint64_t x = miss;                                      // bit j: frames j .. j + have - 1 all miss
+        for (int have = 1; have < max_miss;) {
+            const int sh = have < max_miss - have ? have : max_miss - have;
+            x &= x >> sh;
+            have += sh;
+        }
+        if (x) return Unlock{ __builtin_ctzll(x) + max_miss - 1, 0 };
+    }
+    if (!pass) return Unlock{ -1, misses_in + n };
+    return Unlock{ -1, n - 1 - (63 - __builtin_clzll(pass)) };  // the misses behind the last reported frame
+}
+
 // Runs the state machine over the new bits.  emit(f, bx, type, bitnum) is called for the f-th consumed frame (buffer
 // coordinate of its first bit, the reference's rx_cb type or -1, absolute bit number of its first bit).  On return
 // st holds the new state and carry_x the coordinate of the first bit that stays buffered ([carry_x, xe) = the new bitbuf).
@@ -237,6 +317,99 @@ BS_FN int run(State& st, const uint32_t* s, const uint32_t* m_sync, const uint32
                 a = a1;
                 bx = bx1;
                 if (rc >= 0) { nfs = abs_of(bx) + (uint32_t)offs + 296u; state = kKnowFstart; }
+                continue;
+            }
+            const int p = first(m_sync, bx1 + 21, xe - 38 + 1);
+            if (p < 0) { a = xe; break; }
+            a = (p + 38 > a1) ? p + 38 : a1;
+            bx = (a - kBuf > bx) ? a - kBuf : bx;
+            nfs = abs_of(p) + 296u;
+            state = kKnowFstart;
+        } else if (state == kKnowFstart) {
+            const int nfs_x = x0 + (int)(int32_t)(nfs - abs0);
+            const int at = (a + 1 > nfs_x) ? a + 1 : nfs_x;
+            if (at > xe) { a = xe; break; }
+            a = at;
+            bx = nfs_x;
+            nfs += kTs;
+            state = kLocked;
+            locked_call();
+        } else {
+            if (a == bx && xe - bx >= 2 * kTs) {
+                bool unlocked = false;
+                const int done = batch(bx, (xe - bx) / kTs, frames, abs_of(bx), unlocked);
+                if (done > 0) {                                 // `done` LOCKED calls of exactly one frame each, a = bx + 510 after every one
+                    frames += done;
+                    bx += kTs * done;
+                    nfs += (uint32_t)(kTs * done);
+                    a = bx;
+                    if (unlocked) state = kUnlocked;
+                    continue;
+                }
+            }
+            const int an = (a + 1 > bx + kTs) ? a + 1 : bx + kTs;
+            if (an > xe) { a = xe; break; }
+            a = an;
+            bx = (a - kBuf > bx) ? a - kBuf : bx;
+            locked_call();
+        }
+    }
+    bx = (a - kBuf > bx) ? a - kBuf : bx;                       // make_bitbuf_space of the calls skipped at the end
+    st.state = state;
+    st.bits_in_buf = (uint32_t)(xe - bx);
+    st.bitbuf_start_bitnum = abs_of(bx);
+    st.next_frame_start_bitnum = nfs;
+    carry_x = bx;
+    return frames;
+}
+
+// The tolerant lock.  The same walk over the events with the tolerant LOCKED call and ONE shortcut in UNLOCKED that gives the same result
+// (the literal calls on a buffer whose start does not move, below); `misses` is the channel's miss counter, carried from
+// call to call.  batch() evaluates its frames with tolerant_frame_eval, applies first_unlock to them with the same counter and leaves
+// it as the rule does.  Only the sync bitmap is read.  (A copy of run(), not a parameter of it: the reference rule's kernels are held
+// instruction for instruction to what they were, and the compiler schedules run() differently as soon as it carries a second policy.)
+template <class First, class Emit, class Batch>
+BS_FN int run_tolerant(State& st, const uint32_t* s, const uint32_t* m_sync, int n_new, int& carry_x, First first, Emit emit, Batch batch,
+                       const Tolerance& tol, int& misses) {
+    const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
+    const uint32_t abs0 = st.bitbuf_start_bitnum;               // absolute bit number of coordinate x0
+    auto abs_of = [&](int x) { return abs0 + (uint32_t)(x - x0); };
+    int state = st.state, bx = x0, a = kOff, frames = 0;
+    uint32_t nfs = st.next_frame_start_bitnum;
+
+    auto locked_call = [&]() {                                  // the tolerant LOCKED call on the first 510 bits of the buffer [bx, a)
+        if (a - bx < kTs) return;
+        const int reported = tolerant_frame_eval(s, bx, tol);
+        misses = reported >= 0 ? 0 : misses + 1;
+        if (misses >= tol.max_miss) { state = kUnlocked; misses = 0; }
+        emit(frames++, bx, reported, abs_of(bx));
+        bx += kTs;
+        nfs += kTs;
+    };
+
+    while (a < xe) {
+        if (state == kUnlocked) {
+            const int a1 = (a + 1 > bx + 2 * kTs) ? a + 1 : bx + 2 * kTs;
+            if (a1 > xe) { a = xe; break; }
+            const int bx1 = (a1 - kBuf > bx) ? a1 - kBuf : bx;
+            if (first(m_sync, bx1, bx1 + 21) >= 0) {        // a true match in the misaligned-filter zone: literal calls
+                // Until the buffer is full its start stays bx1, and the calls a1, a1 + 1, ... search the same positions plus one more each:
+                // what an earlier call rejected stays rejected, so the first call that finds anything finds the first position p that
+                // passes anywhere in [bx1, lim), and it is the call a = max(a1, p + 38).  One literal search over the whole stretch
+                // stands for all of them, with the same result.  (run() evaluates such a buffer call by call -- up to 3076 literal searches
+                // of up to 4096 positions each on one wavefront, where this is one.  A flywheel that unlocks 16 frames late lands on such a
+                // buffer whenever the timing has jumped by about 300 bits; run() has the same path and is left as it is.)
+                const int lim = xe < bx1 + kBuf ? xe : bx1 + kBuf;
+                int offs = 0;
+                const int rc = literal_find(s, bx1, lim - bx1, 1u << kSync, offs);
+                bx = bx1;
+                if (rc >= 0) {
+                    a = (bx1 + offs + 38 > a1) ? bx1 + offs + 38 : a1;
+                    nfs = abs_of(bx) + (uint32_t)offs + 296u;
+                    state = kKnowFstart;
+                } else {
+                    a = lim > a1 ? lim : a1;
+                }
                 continue;
             }
             const int p = first(m_sync, bx1 + 21, xe - 38 + 1);

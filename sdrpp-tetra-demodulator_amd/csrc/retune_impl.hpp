@@ -15,6 +15,7 @@ namespace retune_impl {
 TETRA_HIDDEN int demod_view(tetra_demod_t* h, retune::DemodView* out);
 // tetra_burst_sync.hip
 TETRA_HIDDEN int bsync_view(tetra_bsync_t* h, retune::BsyncView* out);
+TETRA_HIDDEN int bsync_miss_view(tetra_bsync_t* h, retune::CellView* out);
 // tetra_resamp.hip: a handle that runs all its channels in place (16-byte lane units) becomes one that picks columns (8-byte units,
 // what TETRA_RESAMP_FLAG_NARROW_UNITS gives at create).  Same floats; the delay line's layout does not depend on the unit width.
 TETRA_HIDDEN int resamp_narrow_units(tetra_resamp_t* h);

@@ -14,6 +14,7 @@
 // k_burst_demux: one thread per output dword; a gather with the offsets of tetra_burst_rx_cb().
 #include <hip/hip_runtime.h>
 
+#include "../../include/ext/tetra_sync_tol.h"
 #include "../../include/tetra_burst_sync.h"
 #include "bsync_core.hpp"
 #include "compact_core.hpp"
@@ -175,6 +176,148 @@ template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_syn
     }
 }
 
+// k_burst_sync under the tolerant lock (include/ext/tetra_sync_tol.h): steps 1 and 4 as above; step 2 builds the sync bitmap only (LDS:
+// stream, one bitmap, frame list); in step 3 the LOCKED batch evaluates the three windows of its frame per lane (tolerant_frame_eval)
+// and the consecutive-miss rule runs over the ballot of the reported frames (first_unlock_bits).  miss [C]: the channels' miss
+// counters beside their State.  A kernel of its own: the reference rule's kernel above is held instruction for instruction.
+template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync_tol(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
+                                                       int max_bits, int max_frames, State* __restrict__ states,
+                                                       uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
+                                                       int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
+                                                       int* __restrict__ n_frames, const Tolerance tol, int32_t* __restrict__ miss) {
+    extern __shared__ uint32_t lds[];
+    __shared__ int sh_nframes, sh_carry_x;
+    __shared__ State sh_state;
+    const int words = stream_words(max_bits);
+    uint32_t* s = lds;
+    uint32_t* m_sync = s + words;
+    FrameRec* rec = reinterpret_cast<FrameRec*>(m_sync + words);
+
+    const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & (kLanes - 1);
+    const uint8_t* in = bits + (size_t)ch * bits_stride;
+    uint8_t* cbuf = carry + (size_t)ch * kBuf;
+    State st = states[ch];
+    int n_new = n_bits[ch];
+    n_new = n_new < 0 ? 0 : (n_new > max_bits ? max_bits : n_new);
+    n_new = n_new > bits_stride ? bits_stride : n_new;         // a poisoned count never reads into the next channel's row
+    const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
+
+    // 1. pack the stream
+    for (int w = tid; w < words; w += kThreadsBS) {
+        uint32_t v = 0;
+        const int xb = 32 * w;
+        if (xb + 32 > x0 && xb < kOff) {                         // carried bits: byte by byte (at most 128 words)
+            for (int b = 0; b < 32; ++b) {
+                const int x = xb + b;
+                if (x >= x0 && x < kOff) v |= (uint32_t)(cbuf[x - x0] & 1u) << (31 - b);
+            }
+        } else if (xb >= kOff && xb < xe) {
+            const int j = xb - kOff;
+            if (j + 32 <= n_new && (((uintptr_t)(in + j)) & 15) == 0) {
+                const uint4 lo = *reinterpret_cast<const uint4*>(in + j);
+                const uint4 hi = *reinterpret_cast<const uint4*>(in + j + 16);
+                const unsigned long long q[4] = { ((unsigned long long)lo.y << 32) | lo.x, ((unsigned long long)lo.w << 32) | lo.z,
+                                                  ((unsigned long long)hi.y << 32) | hi.x, ((unsigned long long)hi.w << 32) | hi.z };
+#pragma unroll
+                for (int z = 0; z < 4; ++z)      // 8 bytes -> 8 bits, first byte = MSB: byte i of x * 0x8040201008040201 reaches bit 63 - i
+                    v |= (uint32_t)(((q[z] & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56) << (24 - 8 * z);
+            } else {
+                for (int b = 0; b < 32; ++b)
+                    if (j + b < n_new) v |= (uint32_t)(in[j + b] & 1u) << (31 - b);
+            }
+        }
+        s[w] = v;
+    }
+    __syncthreads();
+
+    // 2. the sync bitmap
+    for (int w = tid; w < words; w += kThreadsBS) {
+        m_sync[w] = (w + 2 < words && 32 * w + 32 > x0 && 32 * w < xe) ? match_word_sync(s, w, x0, xe) : 0u;
+    }
+    __syncthreads();
+
+    // 3. state machine: all lanes in lock step (uniform control flow); the bitmap searches are wave-cooperative
+    auto first_wave = [&](const uint32_t* m, int a, int b) -> int {
+        if (a >= b) return -1;
+        const int w0 = a >> 5, w1 = (b - 1) >> 5;
+        for (int base = w0; base <= w1; base += kLanes) {
+            const int w = base + lane;
+            uint32_t v = (w <= w1) ? m[w] : 0u;
+            if (w == w0) v &= 0xffffffffu << (a & 31);
+            if (w == w1 && (b & 31) != 0) v &= (1u << (b & 31)) - 1u;
+            const unsigned long long hit = __ballot(v != 0u);
+            if (hit) {
+                const int l = __builtin_ctzll(hit);
+                return 32 * (base + l) + __builtin_ctz(__shfl(v, l));
+            }
+        }
+        return -1;
+    };
+    if (tid < kLanes) {      // (one wavefront walks the events; the other three join again for the byte work behind the barrier)
+        int carry_x = 0;
+        auto emit = [&](int f, int bx, int type, uint32_t bitnum) {
+            if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
+        };
+        int misses = miss[ch];
+        // LOCKED steady state: one frame per lane, 64 per round; the ballot of the reported frames decides where the consecutive-miss rule unlocks
+        auto batch = [&](int bx, int K, int f0, uint32_t abs_bx, bool& unlocked) -> int {
+            int done = 0;
+            while (done < K) {
+                const int k = done + lane, here = K - done < kLanes ? K - done : kLanes;
+                int reported = -1;
+                if (lane < here) reported = tolerant_frame_eval(s, bx + kTs * k, tol);
+                const Unlock u = first_unlock_bits(__ballot(reported >= 0), here, misses, tol.max_miss);
+                const int take = u.index >= 0 ? u.index + 1 : here;
+                if (lane < take && f0 + k < max_frames) rec[f0 + k] = FrameRec{ bx + kTs * k, reported, abs_bx + (uint32_t)(kTs * k) };
+                misses = u.misses;
+                done += take;
+                if (u.index >= 0) { unlocked = true; break; }
+            }
+            return done;
+        };
+        const int nrun = run_tolerant(st, s, m_sync, n_new, carry_x, first_wave, emit, batch, tol, misses);
+        if (lane == 0) {
+            miss[ch] = misses;
+            sh_nframes = nrun < max_frames ? nrun : max_frames;
+            sh_carry_x = carry_x;
+            sh_state = st;
+        }
+    }
+    __syncthreads();
+
+    // 4. frames, carry, state
+    const int nf = sh_nframes;
+    if (PACKED) {
+        uint32_t* pout = reinterpret_cast<uint32_t*>(frames) + (size_t)ch * max_frames * TETRA_FRAME_WORDS;
+        for (int i = tid; i < nf * TETRA_FRAME_WORDS; i += kThreadsBS) {
+            const int f = i / TETRA_FRAME_WORDS, w = i % TETRA_FRAME_WORDS;
+            uint32_t v = window(s, rec[f].bx + 32 * w, 32);
+            if (w == TETRA_FRAME_WORDS - 1) v &= 0xfffffffcu;              // bits 510, 511 of the row are not the frame's
+            pout[i] = v;
+        }
+    }
+    uint8_t* fout = frames + (size_t)ch * max_frames * TETRA_FRAME_STRIDE;
+    for (int f = 0; !PACKED && f < nf; ++f) {
+        const int bx = rec[f].bx;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(fout + (size_t)f * TETRA_FRAME_STRIDE);
+        for (int d = tid; d < TETRA_FRAME_STRIDE / 4; d += kThreadsBS) {
+            uint32_t nib = window(s, bx + 4 * d, 4);                       // first bit = MSB
+            if (4 * d + 4 > kTs) nib &= (4 * d >= kTs) ? 0u : (0xfu << (4 * d + 4 - kTs)) & 0xfu;
+            dst[d] = ((nib >> 3) & 1u) | (((nib >> 2) & 1u) << 8) | (((nib >> 1) & 1u) << 16) | ((nib & 1u) << 24);
+        }
+    }
+    for (int f = tid; f < max_frames; f += kThreadsBS) {
+        frame_type[(size_t)ch * max_frames + f] = f < nf ? rec[f].type : TETRA_FRAME_NONE;
+        frame_bitnum[(size_t)ch * max_frames + f] = f < nf ? rec[f].bitnum : 0u;
+    }
+    const int cx = sh_carry_x, nc = xe - cx;
+    for (int i = tid; i < nc; i += kThreadsBS) cbuf[i] = (uint8_t)get_bit(s, cx + i);
+    if (tid == 0) {
+        states[ch] = sh_state;
+        n_frames[ch] = nf;
+    }
+}
+
 using demux_core::Pieces;
 using demux_core::PiecesLut;
 using demux_core::pieces_for;
@@ -257,6 +400,8 @@ template <bool GATHER> __global__ __launch_bounds__(256) void k_demux_rows(const
 }
 
 size_t lds_bytes(int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * 5 * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
+// the tolerant lock: stream and sync bitmap only
+size_t lds_bytes_tol(int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * 2 * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
 
 }  // namespace
 
@@ -264,6 +409,10 @@ struct tetra_bsync {
     int n_channels, max_bits, max_frames, device;
     DevMem<State> d_state;
     DevMem<uint8_t> d_carry;
+    // the tolerant lock (include/ext/tetra_sync_tol.h): off = the reference's rule and its kernels
+    bool tolerant = false;
+    Tolerance tol = { 0, 0, 1 };
+    DevMem<int32_t> d_miss;           // [C] consecutive LOCKED frames without a candidate (allocated by the first switch to the tolerant rule)
 };
 
 extern "C" {
@@ -287,6 +436,10 @@ int tetra_bsync_create(int n_channels, int max_bits, int device, tetra_bsync_t**
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 64) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024 - 64) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync_tol<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024 - 64) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync_tol<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024 - 64) != hipSuccess) {
         delete h;
         return TETRA_ERR_HIP;
@@ -306,8 +459,36 @@ int tetra_bsync_reset(tetra_bsync_t* h) {
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_HIP;
     if (hipMemset(h->d_state, 0, sizeof(State) * h->n_channels) != hipSuccess ||
-        hipMemset(h->d_carry, 0, (size_t)kBuf * h->n_channels) != hipSuccess)
+        hipMemset(h->d_carry, 0, (size_t)kBuf * h->n_channels) != hipSuccess ||
+        (h->d_miss.get() && hipMemset(h->d_miss, 0, sizeof(int32_t) * h->n_channels) != hipSuccess))
         return TETRA_ERR_HIP;
+    return TETRA_OK;
+}
+
+int tetra_bsync_set_tolerance(tetra_bsync_t* h, const tetra_bsync_tolerance_t* tol) {
+    if (!h) return TETRA_ERR_ARG;
+    const Tolerance t = tol ? Tolerance{ tol->tol_norm, tol->tol_sync, tol->max_miss } : Tolerance{ 0, 0, 1 };
+    if (!tolerance_valid(t)) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok || hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    // the counters exist from the first switch to the tolerant rule on: a handle that never leaves the reference's rule allocates what it
+    // always did
+    if (tol && !h->d_miss.get() && h->d_miss.reserve(sizeof(int32_t) * h->n_channels) != hipSuccess) return TETRA_ERR_NOMEM;
+    if (h->d_miss.get() && hipMemset(h->d_miss, 0, sizeof(int32_t) * h->n_channels) != hipSuccess) return TETRA_ERR_HIP;
+    h->tolerant = tol != nullptr;
+    h->tol = t;
+    return TETRA_OK;
+}
+
+int tetra_bsync_get_misses(tetra_bsync_t* h, int first, int count, int32_t* out) {
+    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->n_channels) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok || hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    if (!h->d_miss.get()) {          // never tolerant: nothing was ever counted
+        for (int i = 0; i < count; i++) out[i] = 0;
+        return TETRA_OK;
+    }
+    if (count && hipMemcpy(out, h->d_miss + first, sizeof(int32_t) * count, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
 }
 
@@ -323,6 +504,12 @@ int retune_impl::bsync_view(tetra_bsync_t* h, retune::BsyncView* v) {
     v->carry = reinterpret_cast<uint32_t*>(h->d_carry.get()); v->carry_words = kBuf / 4;
     return TETRA_OK;
 }
+// ... and the miss counters of the tolerant lock, one word per channel (no words while the handle runs the reference's rule)
+int retune_impl::bsync_miss_view(tetra_bsync_t* h, retune::CellView* v) {
+    if (!h || !v) return TETRA_ERR_ARG;
+    v->cell = reinterpret_cast<uint32_t*>(h->d_miss.get()); v->cell_words = h->tolerant ? 1 : 0;
+    return TETRA_OK;
+}
 
 namespace {
 template <bool PACKED> int bsync_launch(tetra_bsync_t* h, const uint8_t* d_bits, int bits_stride, const int32_t* d_n_bits, void* d_frames,
@@ -331,9 +518,14 @@ template <bool PACKED> int bsync_launch(tetra_bsync_t* h, const uint8_t* d_bits,
     if (bits_stride < 4) return TETRA_ERR_ARG;
     if (bits_stride < h->max_bits) return TETRA_ERR_SIZE;      // rows must be able to hold the max_bits the handle was sized for
     if ((bits_stride & 3) || ((uintptr_t)d_bits & 3) || ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;
-    hipLaunchKernelGGL(k_burst_sync<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(h->max_bits, h->max_frames),
-                       static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
-                       h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames);
+    if (h->tolerant)
+        hipLaunchKernelGGL(k_burst_sync_tol<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes_tol(h->max_bits, h->max_frames),
+                           static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
+                           h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames, h->tol, h->d_miss);
+    else
+        hipLaunchKernelGGL(k_burst_sync<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(h->max_bits, h->max_frames),
+                           static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
+                           h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 }  // namespace

@@ -46,6 +46,14 @@ __global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retu
     retune::reset_cell_channel(link, c, threadIdx.x, kLanes);
 }
 
+// the synchroniser's miss counters under the tolerant lock (tetra_sync_tol.h), one word per channel: a launch of its own behind
+// k_reset_tail, made only for a chain that runs that rule
+__global__ __launch_bounds__(kLanes) void k_reset_miss(retune::CellView miss, const int32_t* __restrict__ channels, int n_channels) {
+    const int c = channels[blockIdx.x];
+    if (c < 0 || c >= n_channels) return;
+    retune::reset_cell_channel(miss, c, threadIdx.x, kLanes);
+}
+
 // list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
 // history ring [hist][M] (a sibling of tetra_resamp.hip's k_pick_rows: same rows, one column each, out of the ring)
 __global__ __launch_bounds__(256) void k_retune_columns(const float* __restrict__ ring, int M, int hist, long long n_total, const int32_t* __restrict__ list,
@@ -104,6 +112,12 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     }
     hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
     HIP_TRY(h, hipGetLastError());
+    retune::CellView mv;
+    TETRA_TRY(retune_impl::bsync_miss_view(h->bs, &mv));
+    if (mv.cell_words > 0) {
+        hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, mv, d_channels, h->C);
+        HIP_TRY(h, hipGetLastError());
+    }
     if (h->one_stream) HIP_TRY(h, hipEventRecord(h->ev_reset, s));
     h->reset_pending = true;
     if (h->calls > 0) {      // who waits for the last call waits for the reset too

@@ -27,6 +27,7 @@
 
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
+#include "../../include/ext/tetra_sync_tol.h"
 #include "../../include/tetra_rx.h"
 #include "lmac_impl.hpp"
 #include "rx_handle.hpp"
@@ -231,7 +232,7 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR)))
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR | TETRA_RX_FLAG_SYNC_TOLERANT)))
         return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
@@ -253,6 +254,10 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (h->stride < 0) return h->stride;
     TETRA_TRY(tetra_bsync_create(h->C, h->stride, dev, h->bs.put()));
     h->F = tetra_bsync_max_frames(h->bs);
+    if (cfg->flags & TETRA_RX_FLAG_SYNC_TOLERANT) {
+        const tetra_bsync_tolerance_t tol = { TETRA_SYNC_TOL_DEFAULT_NORM, TETRA_SYNC_TOL_DEFAULT_SYNC, TETRA_SYNC_TOL_DEFAULT_MISS };
+        TETRA_TRY(tetra_bsync_set_tolerance(h->bs, &tol));
+    }
     const long long rows = (long long)h->C * h->F;
     if (rows > 0x7fffffffLL / 512) return TETRA_ERR_SIZE;      // 32-bit row / byte indices downstream
     h->rows = (int)rows;
@@ -539,6 +544,23 @@ int tetra_rx_get_sync_state(tetra_rx_t* h, int first, int count, tetra_bsync_sta
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
     return count ? tetra_bsync_get_state(h->bs, first, count, out) : TETRA_OK;
+}
+
+// the chain's share of tetra_sync_tol.h
+int tetra_rx_set_sync_tolerance(tetra_rx_t* h, const tetra_bsync_tolerance_t* tol) {
+    if (!h) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));      // (the synchroniser's own entry waits for the device)
+    return tetra_bsync_set_tolerance(h->bs, tol);
+}
+
+int tetra_rx_get_sync_misses(tetra_rx_t* h, int first, int count, int32_t* out) {
+    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    return count ? tetra_bsync_get_misses(h->bs, first, count, out) : TETRA_OK;
 }
 
 int tetra_rx_bits_device(tetra_rx_t* h, int which, const uint8_t** d_bits, int* bits_stride, const int32_t** d_n_bits, void* hip_stream) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ext/tetra_biterr.h"
+#include "ext/tetra_sync_tol.h"
 #include "tetra_rx.h"
 #include "tetra_rx_out.h"
 
@@ -138,6 +139,14 @@ public:
     int syncStates(std::vector<tetra_bsync_state_t>& out) {
         out.resize((size_t)channels_);
         return tetra_rx_get_sync_state(h_, 0, channels_, out.data());
+    }
+    // The synchroniser's tolerant lock (ext/tetra_sync_tol.h; TETRA_RX_FLAG_SYNC_TOLERANT creates the chain with {3, 5, 16}): tol = null
+    // returns to the reference's rule.  Between process calls; waits for the tail in flight.
+    int setSyncTolerance(const tetra_bsync_tolerance_t* tol) { return tetra_rx_set_sync_tolerance(h_, tol); }
+    // every channel's count of consecutive LOCKED frames without a training sequence
+    int syncMisses(std::vector<int32_t>& out) {
+        out.resize((size_t)channels_);
+        return tetra_rx_get_sync_misses(h_, 0, channels_, out.data());
     }
     // the PI4DQPSK setters of the demodulators inside (tetra_demod_set_param ids); waits for work in flight first
     int setParam(int paramId, double value) {

@@ -7,7 +7,7 @@ import numpy as np
 from . import binding as B
 from ._ffi import P, TetraDemodError, call, check, declare, i32, i64, ptr, size_t, stream_ptr, u64, vp
 from .binding import load_library
-from .bsync_binding import BsyncState
+from .bsync_binding import BsyncState, BsyncTolerance, tolerance_arg
 
 KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
 N_KINDS = 6
@@ -15,6 +15,7 @@ FLAG_ONE_STREAM = 1
 FLAG_AACH_RM3014 = 2          # TETRA_RX_FLAG_AACH_RM3014
 FLAG_SOFT = 8                 # TETRA_RX_FLAG_SOFT: the coded kinds decoded from soft values (4 is no flag)
 FLAG_BITERR = 32              # TETRA_RX_FLAG_BITERR: channel bit-error counts per coded block, link figures per channel (tetra_biterr.h)
+FLAG_SYNC_TOLERANT = 128      # TETRA_RX_FLAG_SYNC_TOLERANT: the synchroniser's tolerant lock with {3, 5, 16} (ext/tetra_sync_tol.h)
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
 
@@ -81,6 +82,11 @@ BITERR_ABI = {
     "tetra_rx_biterr_device": (i32, [vp, i32, i32, P(vp), vp]),
     "tetra_rx_get_link": (i32, [vp, i32, i32, P(Link)]),
 }
+# include/ext/tetra_sync_tol.h (the synchroniser's tolerant lock): the chain's share
+SYNC_TOL_ABI = {
+    "tetra_rx_set_sync_tolerance": (i32, [vp, P(BsyncTolerance)]),
+    "tetra_rx_get_sync_misses": (i32, [vp, i32, i32, vp]),
+}
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 
@@ -88,8 +94,8 @@ RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES),
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
-    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI},
-                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI},
+                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI))
 
 
 def type1_bits(kind):
@@ -211,6 +217,18 @@ class RxChain:
         arr = (BsyncState * max(count, 1))()
         call(self._lib.tetra_rx_get_sync_state, self._h, first, count, arr)
         return [(arr[i].state, arr[i].bits_in_buf, arr[i].bitbuf_start_bitnum, arr[i].next_frame_start_bitnum) for i in range(count)]
+
+    def set_sync_tolerance(self, tol):
+        """tetra_rx_set_sync_tolerance: (tol_norm, tol_sync, max_miss) for the synchroniser's tolerant lock from the next call on, None =
+        the reference's rule.  Between process calls; waits for the tail in flight."""
+        call(self._lib.tetra_rx_set_sync_tolerance, self._h, tolerance_arg(tol))
+
+    def sync_misses(self, first=0, count=None):
+        """tetra_rx_get_sync_misses: int32 [count], per channel the consecutive LOCKED frames without a training sequence."""
+        count = self.n_channels - first if count is None else count
+        out = np.zeros(max(count, 1), np.int32)
+        call(self._lib.tetra_rx_get_sync_misses, self._h, int(first), int(count), ptr(out))
+        return out[:count]
 
     def stage_ms(self):
         ms = (C.c_float * 4)()

@@ -209,6 +209,14 @@ class WidebandRx:
         """The carrier slots' link figures (RxChain.links of the chain; needs FLAG_BITERR in `flags`).  A retune zeroes a moved slot's."""
         return self.rx.links(first, count)
 
+    def set_sync_tolerance(self, tol):
+        """The tolerant lock of the carrier slots' synchroniser (RxChain.set_sync_tolerance of the chain); between process calls."""
+        self.rx.set_sync_tolerance(tol)
+
+    def sync_misses(self, first=0, count=None):
+        """The carrier slots' miss counters (RxChain.sync_misses of the chain).  A retune zeroes a moved slot's."""
+        return self.rx.sync_misses(first, count)
+
     def bin_power(self):
         out = np.zeros(self.M, np.float32)
         call(self._lib.tetra_wbrx_bin_power, self._h, ptr(out))

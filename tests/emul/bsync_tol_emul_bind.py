@@ -1,0 +1,89 @@
+"""Builds and binds tests/emul/bsync_tol_emul.cpp (host build of the burst synchroniser's tolerant lock, csrc/bsync_core.hpp)."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from oracle import hostlib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+LIB = os.path.join(HERE, "libbsync_tol_emul.so")
+DEPS = [os.path.join(HERE, "bsync_tol_emul.cpp"), os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "bsync_core.hpp")]
+
+_lib = None
+
+
+def build(force=False):
+    return hostlib.build(LIB, ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", hostlib.OUT, "bsync_tol_emul.cpp"], DEPS, force=force)
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        vp, i32 = C.c_void_p, C.c_int
+        _lib = hostlib.load(build(), {
+            "bsync_tol_emul_process": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32]),
+            "bsync_tol_emul_first_unlock": (None, [C.c_uint64, i32, i32, i32, i32, vp]),
+            "bsync_tol_emul_first_unlock_many": (None, [vp, vp, vp, vp, i32, i32, vp]),
+            "bsync_tol_emul_frame_eval": (i32, [vp, vp]),
+        })
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class Emul:
+    """One channel under the tolerant lock: oracle.binding.BurstSyncOracle's interface plus the miss counter.
+    mode: 0 event path only, 1 batch with the loop form of the consecutive-miss rule, 2 batch with the kernel's bit operations."""
+
+    def __init__(self, tol, mode=2):
+        self.tol = np.array(tol, np.int32)
+        self.mode = int(mode)
+        self.st = np.zeros(4, np.uint32)
+        self.miss = np.zeros(1, np.int32)
+        self.carry = np.zeros(4096, np.uint8)
+
+    @property
+    def state(self):
+        return int(self.st[0]), int(self.st[1]), int(self.st[2]), int(self.st[3])
+
+    @property
+    def misses(self):
+        return int(self.miss[0])
+
+    def bitbuf(self):
+        return self.carry[: int(self.st[1])].copy()
+
+    def feed(self, bits):
+        b = np.ascontiguousarray(bits, np.uint8)
+        cap = (4096 + b.size) // 510 + 4
+        fr = np.zeros((cap, 512), np.uint8)
+        ty = np.zeros(cap, np.int32)
+        bn = np.zeros(cap, np.uint32)
+        n = lib().bsync_tol_emul_process(_p(self.st), _p(self.miss), _p(self.carry), _p(b), b.size, _p(self.tol), _p(fr), _p(ty), _p(bn), cap, self.mode)
+        assert n >= 0, n
+        return fr[:n, :510].copy(), ty[:n].copy(), bn[:n].copy()
+
+
+def first_unlock(pass_mask, n, misses_in, max_miss, bits):
+    out = np.zeros(2, np.int32)
+    lib().bsync_tol_emul_first_unlock(int(pass_mask), int(n), int(misses_in), int(max_miss), int(bits), _p(out))
+    return int(out[0]), int(out[1])
+
+
+def first_unlock_many(pass_mask, n, misses_in, max_miss, bits):
+    pm = np.ascontiguousarray(pass_mask, np.uint64)
+    a, b, c = (np.ascontiguousarray(v, np.int32) for v in (n, misses_in, max_miss))
+    out = np.zeros((pm.size, 2), np.int32)
+    lib().bsync_tol_emul_first_unlock_many(_p(pm), _p(a), _p(b), _p(c), pm.size, int(bits), _p(out))
+    return out
+
+
+def frame_eval(frame, tol):
+    f = np.ascontiguousarray(frame, np.uint8)
+    assert f.size >= 510
+    t = np.array(tol, np.int32)
+    return int(lib().bsync_tol_emul_frame_eval(_p(f), _p(t)))

@@ -1,0 +1,924 @@
+"""The burst synchroniser's tolerant training-sequence match in lock (include/ext/tetra_sync_tol.h; lane code csrc/bsync_core.hpp).
+
+CPU: a plain Python restatement of the rule, fed one bit per call -- its UNLOCKED search is the reference's own tetra_find_train_seq
+(oracle/_ref), its LOCKED call byte loops -- against the host build of the lane code (tests/emul/bsync_tol_emul.cpp) in every frame,
+state field, buffered bit and miss counter, however the stream is cut; agreement with the reference's synchroniser where the two must
+agree; the window edges; the consecutive-miss rule exhaustively; and the operating point (11 dB, tests/test_rx_soft.py's stream), whose
+counts and rows are the fixture tests/golden/sync_tol_golden.npz (written by `python -m tests.test_sync_tol --write-golden`).
+GPU: the kernels against the host build, setting and clearing, and the chain with TETRA_RX_FLAG_SYNC_TOLERANT against the fixture."""
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+
+from tests import soft_pipeline as sp
+from tests.test_burst_sync import make_stream
+from tests.test_rx_soft import OP_CHANNELS, OP_SAMPLES, OP_SEED, OP_SLOTS, rows_to_arrays
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "sync_tol_golden.npz")
+
+UNLOCKED, KNOW_FSTART, LOCKED = 0, 1, 2
+NORM_1, NORM_2, SYNC = 0, 1, 3
+DEFAULT = (3, 5, 16)
+PARAM_SETS = ((0, 0, 1), DEFAULT, (4, 6, 255), (2, 2, 2))
+CUT_SIZES = (1, 509, 510, 511, 1019, 4096, 33661)
+OP_ESN0 = (9.0, 11.0, 13.0, 25.0)
+REFERENCE_FRAMES_11DB = 224                 # the reference rule at the operating point: the rows behind DESIGN.md 8.3 (50 SB1 + 56 NDB + 118 SCH/F)
+
+
+def _seq(name):
+    with open(os.path.join(ROOT, "tests", "golden", "etsi_training_sequences.json")) as f:
+        return bytes(json.load(f)[name])
+
+
+SEQ_Y, SEQ_N, SEQ_P = _seq("sync"), _seq("normal_1"), _seq("normal_2")
+
+
+# ---- the restatement -------------------------------------------------------------------------------------------------------------------
+
+class Restatement:
+    """The tolerant rule as a plain state machine, one bit per call.  The bit buffer is the latest bits of the stream, so it is kept as the
+    stream position of its first bit (= bitbuf_start_bitnum: numbering starts at 0).  history[i] = (state, bits_in_buf,
+    bitbuf_start_bitnum, next_frame_start_bitnum, misses) after i bits."""
+
+    def __init__(self, ref, tol):
+        self.ref, self.tol = ref, tuple(tol)
+        self.bits = bytearray()
+        self.st, self.start, self.nfs, self.miss = UNLOCKED, 0, 0, 0
+        self.history = [(UNLOCKED, 0, 0, 0, 0)]
+
+    def _in(self, arr, end):
+        """tetra_burst_sync_in for the bit that makes the stream `end` bits long (arr: the stream + slack for the search's look-ahead)"""
+        if end - self.start > 4096:                                # make_bitbuf_space
+            self.start = end - 4096
+        if self.st == UNLOCKED:
+            if end - self.start < 2 * 510:
+                return None
+            t, offs = self.ref.find_train_seq(arr[self.start:], end - self.start, 1 << SYNC)
+            if t >= 0:
+                self.st, self.nfs = KNOW_FSTART, self.start + offs + 296
+            return None
+        if self.st == KNOW_FSTART:
+            if end < self.nfs:
+                return None
+            self.start = self.nfs
+            self.nfs += 510
+            self.st = LOCKED                                       # and fall through
+        if end - self.start < 510:
+            return None
+        f = self.bits[self.start:self.start + 510]
+        tol_norm, tol_sync, max_miss = self.tol
+        d_s = sum(f[214 + k] != SEQ_Y[k] for k in range(38))
+        d_1 = sum(f[244 + k] != SEQ_N[k] for k in range(22))
+        d_2 = sum(f[244 + k] != SEQ_P[k] for k in range(22))
+        cands = [(d, order, t) for d, order, t, tol in ((d_s, 0, SYNC, tol_sync), (d_1, 1, NORM_1, tol_norm), (d_2, 2, NORM_2, tol_norm)) if d <= tol]
+        if cands:
+            reported, self.miss = min(cands)[2], 0
+        else:
+            reported, self.miss = -1, self.miss + 1
+            if self.miss >= max_miss:
+                self.st, self.miss = UNLOCKED, 0
+        out = (self.start, reported)
+        self.start += 510
+        self.nfs += 510
+        return out
+
+    def feed(self, bits, chunk=1):
+        """oracle.BurstSyncOracle.feed's interface"""
+        b = np.ascontiguousarray(bits, np.uint8)
+        n0 = len(self.bits)
+        self.bits += b.tobytes()
+        arr = np.concatenate([np.frombuffer(bytes(self.bits), np.uint8), np.zeros(64, np.uint8)])
+        out = []
+        for end in range(n0 + 1, n0 + b.size + 1):
+            r = self._in(arr, end)
+            if r is not None:
+                out.append(r)
+            self.history.append((self.st, end - self.start, self.start, self.nfs, self.miss))
+        frames = np.array([arr[s:s + 510] for s, _ in out], np.uint8).reshape(-1, 510)
+        return frames, np.array([t for _, t in out], np.int32), np.array([s for s, _ in out], np.uint32)
+
+    @property
+    def state(self):
+        return self.history[-1][:4]
+
+
+@pytest.fixture(scope="module")
+def tolemul():
+    from tests.emul import bsync_tol_emul_bind
+    bsync_tol_emul_bind.build()
+    return bsync_tol_emul_bind
+
+
+def cut_patterns(n, rng):
+    """Call sizes over a stream of n bits: every size of CUT_SIZES uniformly (1-bit calls over a stretch only, they are slow to drive
+    from Python), and a mix of all of them with empty calls in between."""
+    pats = []
+    for size in CUT_SIZES:
+        if size == 1:
+            lead = int(rng.integers(0, max(n - 3000, 1)))
+            sizes = [lead] + [1] * min(3000, n - lead) + [4096] * (n // 4096 + 1)
+        else:
+            sizes = [size] * (n // size + 1)
+        pats.append(sizes)
+    pats.append([int(v) for v in rng.choice(CUT_SIZES[1:] + (0, 0, 1, 1, 7), n // 300 + 8)])
+    return pats
+
+
+def check_against_restatement(tolemul, bits, tol, r, sizes, mode, tag):
+    """the host build fed `sizes` bits per call == the restatement r (already fed the whole stream): frames, and after every call the
+    state fields, the buffered bits and the miss counter"""
+    fr, ty, bn = r.frames
+    e = tolemul.Emul(tol, mode)
+    pos, got = 0, ([], [], [])
+    for size in sizes:
+        out = e.feed(bits[pos:pos + size])
+        pos = min(pos + size, len(bits))
+        for g, o in zip(got, out):
+            g.append(o)
+        st, nbuf, start, nfs, miss = r.history[pos]
+        assert e.state == (st, nbuf, start & 0xffffffff, nfs & 0xffffffff) and e.misses == miss, (tag, pos, size, e.state, e.misses, r.history[pos])
+        assert np.array_equal(e.bitbuf(), bits[start:pos]), (tag, pos)
+        if pos == len(bits):
+            break
+    assert pos == len(bits)
+    assert np.array_equal(np.concatenate(got[1]), ty) and np.array_equal(np.concatenate(got[2]), bn), tag
+    assert np.array_equal(np.concatenate(got[0]), fr), tag
+
+
+def restated(ref, bits, tol):
+    r = Restatement(ref, tol)
+    r.frames = r.feed(bits)
+    return r
+
+
+def check_stream(ref, tolemul, bits, tol, rng, tag):
+    r = restated(ref, bits, tol)
+    for i, sizes in enumerate(cut_patterns(len(bits), rng)):
+        for mode in ((0, 1, 2) if max(sizes) >= 1019 else (2,)):
+            check_against_restatement(tolemul, bits, tol, r, sizes, mode, (tag, tol, i, mode))
+    return r
+
+
+# ---- streams ----------------------------------------------------------------------------------------------------------------------------
+
+def op_iq(synth, esn0_db):
+    """tests/test_rx_soft.py's operating point at another Es/N0 (11 dB is that test's stream)"""
+    cells = [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(OP_CHANNELS)]
+    tx = [synth.gen_downlink(OP_SLOTS, OP_SEED + c, cell=cells[c]) for c in range(OP_CHANNELS)]
+    iq = np.stack([synth.gen_channel(OP_SAMPLES, OP_SEED + 100 + c, bits=tx[c][0], esn0_db=esn0_db)[0] for c in range(OP_CHANNELS)])
+    return iq, [t[0] for t in tx]
+
+
+_op_cache = {}
+
+
+def op_bits(synth, oracle, esn0_db):
+    """-> (iq, [demodulated bits per channel], [transmitted bits per channel]) of the oracle demodulator, computed once"""
+    if esn0_db not in _op_cache:
+        iq, tx = op_iq(synth, esn0_db)
+        bits, nb = oracle.process_batch(iq)[:2]
+        _op_cache[esn0_db] = (iq, [bits[c][:nb[c]].copy() for c in range(OP_CHANNELS)], tx)
+    return _op_cache[esn0_db]
+
+
+def sent_kind(tx, at):
+    """the burst type transmitted in the slot that starts at tx[at] (a multiple of 510), read off its training sequence"""
+    if at < 0 or at % 510 or at + 510 > len(tx):
+        return None
+    f = tx[at:at + 510].tobytes()
+    return SYNC if f[214:252] == SEQ_Y else NORM_1 if f[244:266] == SEQ_N else NORM_2 if f[244:266] == SEQ_P else None
+
+
+def typed_wrongly(synth, rx, tx, types, bitnums):
+    """reported frames whose type is not the transmitted slot's (a frame off the slot grid counts)"""
+    lag = synth.align_and_count_errors(rx, tx, skip=4000, window=6000)[0]          # rx[i] == tx[i - lag]
+    return sum(1 for t, b in zip(types, bitnums) if t >= 0 and sent_kind(tx, int(b) - lag) != t)
+
+
+# ---- 1. the restatement against the host build -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("tol", PARAM_SETS)
+def test_host_build_equals_restatement_on_adversarial_streams(ref, tolemul, tol):
+    rng = np.random.default_rng(11)
+    reported = unlocks = 0
+    for seed in range(20):
+        bits = make_stream(ref, seed)
+        r = check_stream(ref, tolemul, bits, tol, rng, ("adversarial", seed))
+        reported += int((r.frames[1] >= 0).sum())
+        unlocks += sum(1 for a, b in zip(r.history, r.history[1:]) if a[0] == LOCKED and b[0] == UNLOCKED)
+    # (a guard that the streams exercise LOCKED at all: 20 streams of at least 20 slots each; behind a bit slip a receiver that needs 255
+    #  misses to unlock reports next to nothing, hence the low floor)
+    assert reported > 100 and (unlocks > 0 or tol[2] > 2)
+
+
+@pytest.mark.parametrize("tol", PARAM_SETS)
+def test_host_build_equals_restatement_on_clean_and_noisy_downlinks(ref, oracle, synth, tolemul, tol):
+    rng = np.random.default_rng(12)
+    for seed in range(3):
+        bits, _ = synth.gen_downlink(40, 900 + seed)
+        bits = np.concatenate([rng.integers(0, 2, int(rng.integers(0, 700))).astype(np.uint8), bits])
+        r = check_stream(ref, tolemul, bits, tol, rng, ("clean", seed))
+        assert (r.frames[1] >= 0).sum() >= 37
+    for esn0 in (9.0, 11.0, 13.0):
+        for c, rx in enumerate(op_bits(synth, oracle, esn0)[1]):
+            if esn0 != 11.0 and c >= 2:          # (every channel at the operating point, two beside it)
+                break
+            check_stream(ref, tolemul, rx, tol, rng, ("noisy", esn0, c))
+
+
+# ---- 2. agreement with the reference where they must agree ------------------------------------------------------------------------------
+
+# clean coded downlinks, seeds 900 .. 911 with a random lead-in: with {0, 0, 1} the tolerant rule is the reference's wherever no payload
+# imitates a training sequence ahead of the expected offset.  No seed of these had to be passed over.
+AGREEMENT_SEEDS = tuple(range(900, 912))
+
+
+def test_exact_parameters_equal_the_reference_on_clean_downlinks(ref, oracle, synth, tolemul):
+    rng = np.random.default_rng(13)
+    for seed in AGREEMENT_SEEDS:
+        bits, _ = synth.gen_downlink(40, seed)
+        bits = np.concatenate([rng.integers(0, 2, int(rng.integers(0, 700))).astype(np.uint8), bits])
+        o = oracle.BurstSyncOracle()
+        want = o.feed(bits, chunk=1)
+        e = tolemul.Emul((0, 0, 1))
+        got = e.feed(bits)
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)) and len(want[1]) >= 37, seed
+        assert e.state == o.state and e.misses == 0, seed
+
+
+# ---- 3. window edges ---------------------------------------------------------------------------------------------------------------------
+
+def _frame(rng, kind):
+    f = rng.integers(0, 2, 510).astype(np.uint8)
+    f[200:300] = 0                                  # nothing near the windows resembles a sequence by accident
+    if kind == SYNC:
+        f[214:252] = np.frombuffer(SEQ_Y, np.uint8)
+    else:
+        f[244:266] = np.frombuffer(SEQ_N if kind == NORM_1 else SEQ_P, np.uint8)
+    return f
+
+
+def _flip(f, positions):
+    g = f.copy()
+    g[list(positions)] ^= 1
+    return g
+
+
+def test_window_edges_and_ties(tolemul):
+    rng = np.random.default_rng(14)
+    ev = tolemul.frame_eval
+    for tol in PARAM_SETS:
+        tol_norm, tol_sync, _ = tol
+        for kind, lo, hi, t in ((SYNC, 214, 251, tol_sync), (NORM_1, 244, 265, tol_norm), (NORM_2, 244, 265, tol_norm)):
+            f = _frame(rng, kind)
+            assert ev(f, tol) == kind
+            assert ev(_flip(f, (lo - 1, hi + 1)), tol) == kind                    # 213 / 252, 243 / 266 do not count
+            inner = [lo + 2 + 3 * k for k in range(8)]
+            for n_err, want in ((t, kind), (t + 1, -1)):
+                if n_err == 0:
+                    continue
+                edges = ([lo, hi] + inner)[:n_err] if n_err >= 2 else [lo]
+                assert ev(_flip(f, edges), tol) == want, (tol, kind, n_err)
+                assert ev(_flip(f, [hi] + inner[:n_err - 1]), tol) == want
+                assert ev(_flip(f, edges + [lo - 1, hi + 1]), tol) == want            # ... and still do not
+    # SYNC and a normal candidate at equal distance.  The windows overlap in 244 .. 251, where y differs from n in 6 and from p in 4
+    # positions: a frame that follows the normal sequence in half of those and y in the other half is equally far from both
+    y, n, p = (np.frombuffer(s, np.uint8) for s in (SEQ_Y, SEQ_N, SEQ_P))
+    for seq, kind, n_diff in ((n, NORM_1, 6), (p, NORM_2, 4)):
+        diff = [k for k in range(8) if y[30 + k] != seq[k]]
+        assert len(diff) == n_diff
+        f = np.zeros(510, np.uint8)
+        f[214:252] = y
+        f[252:266] = seq[8:22]
+        for k in diff[:n_diff // 2]:
+            f[244 + k] = seq[k]
+        d = n_diff // 2
+        assert int((f[214:252] != y).sum()) == d == int((f[244:266] != seq).sum())
+        assert ev(f, (4, 6, 1)) == SYNC                              # the tie goes to SYNC
+        assert ev(_flip(f, [214]), (4, 6, 1)) == kind                # one more error in the sync window alone: the normal sequence is nearer
+        assert ev(_flip(f, [265]), (4, 6, 1)) == SYNC                # one more in the normal window alone
+        assert ev(f, (d - 1, 6, 1)) == SYNC and ev(f, (4, d - 1, 1)) == kind and ev(f, (d - 1, d - 1, 1)) == -1
+    # both normal candidates in range: n and p differ in 11 of 22 bits, so d1 + d2 >= 11 and tol_norm <= 4 admits at most one
+    assert int((n != p).sum()) == 11
+    best = min(max(int((w != n).sum()), int((w != p).sum())) for w in (np.where(np.arange(22) < k, n, p) for k in range(23)))
+    assert best == 6 > 4                                # the most even split of the 11 differing bits leaves one of them 6 away
+    for k in range(23):
+        w = np.zeros(510, np.uint8)
+        w[244:266] = np.where(np.arange(22) < k, n, p)
+        d = (int((w[244:266] != n).sum()), int((w[244:266] != p).sum()))
+        want = NORM_1 if d[0] <= 4 else NORM_2 if d[1] <= 4 else -1
+        assert not (d[0] <= 4 and d[1] <= 4) and ev(w, (4, 0, 1)) == want, k
+    # equal distances of the two normal sequences cannot be in range either; the order NORM_1 before NORM_2 is what the rule says
+
+
+# ---- 4. first_unlock ------------------------------------------------------------------------------------------------------------------------
+
+def _first_unlock_loop(mask, n, misses_in, max_miss):
+    m = misses_in
+    for k in range(n):
+        m = 0 if (mask >> k) & 1 else m + 1
+        if m >= max_miss:
+            return k, 0
+    return -1, m
+
+
+def test_first_unlock_exhaustive_and_random(tolemul):
+    cases = [(mask, n, mi, mm) for n in range(13) for mask in range(1 << n) for mm in range(1, 7) for mi in range(min(6, mm))]
+    cases += [(mask | (5 << n), n, mi, mm) for n in (0, 3, 12) for mask in (0, 1) for mm in (2, 6) for mi in (0, 1)]      # bits past n are ignored
+    rng = np.random.default_rng(15)
+    for _ in range(60000):
+        n = int(rng.choice([64, 64, 63, 33, int(rng.integers(0, 65))]))
+        dens = rng.choice([0.02, 0.1, 0.5, 0.9])
+        mask = int(np.packbits(rng.random(64) < dens).view(">u8")[0])
+        mm = int(rng.choice([int(rng.integers(1, 256)), int(rng.integers(1, 20)), 64, 65, 255]))
+        cases.append((mask, n, int(rng.integers(0, mm)), mm))
+    arr = np.array([(c[0] & 0xffffffffffffffff,) + c[1:] for c in cases], dtype=object)
+    want = np.array([_first_unlock_loop(*c) for c in cases], np.int32)
+    for bits in (0, 1):
+        got = tolemul.first_unlock_many(np.array([c[0] for c in cases], np.uint64), arr[:, 1].astype(np.int32), arr[:, 2].astype(np.int32),
+                                        arr[:, 3].astype(np.int32), bits)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, (bits, cases[bad[0]], got[bad[0]], want[bad[0]])
+    assert (want[:, 0] >= 0).sum() > 10000 and (want[:, 0] < 0).sum() > 10000
+
+
+# ---- 5. the operating point -----------------------------------------------------------------------------------------------------------------
+
+def tolerant_rows(lref, oracle, iq, tol, use_soft):
+    """tests/soft_pipeline.py's stream_rows with the restatement where it runs the reference's synchroniser"""
+    shim = types.SimpleNamespace(process_batch=oracle.process_batch, BurstSyncOracle=lambda: Restatement(lref, tol))
+    return sp.stream_rows(lref, shim, iq, use_soft)
+
+
+def operating_table(ref, oracle, synth, esn0_db):
+    """[frames the reference rule reports, frames {3, 5, 16} reports, of those typed wrongly] over the five channels"""
+    _, rx, tx = op_bits(synth, oracle, esn0_db)
+    row = [0, 0, 0]
+    for c in range(OP_CHANNELS):
+        row[0] += int((oracle.BurstSyncOracle().feed(rx[c], chunk=1)[1] >= 0).sum())
+        _, ty, bn = Restatement(ref, DEFAULT).feed(rx[c])
+        row[1] += int((ty >= 0).sum())
+        row[2] += typed_wrongly(synth, rx[c], tx[c], ty, bn)
+    return row
+
+
+def golden():
+    return np.load(GOLDEN)
+
+
+def golden_rows(name):
+    g = golden()
+    return {k: [tuple(int(x) for x in lab) + (t1.tobytes(),) for lab, t1 in zip(g["%s_%d_label" % (name, k)], g["%s_%d_type1" % (name, k)])]
+            for k in range(6)}
+
+
+@pytest.fixture(scope="module")
+def lref(ref):
+    if not ref.lmac_available():
+        pytest.skip("oracle/_ref/libtetra_lmac_ref.so not available")
+    return ref
+
+
+def test_operating_point_frames_and_rows_are_the_fixture(lref, oracle, synth):
+    g = golden()
+    row = operating_table(lref, oracle, synth, 11.0)
+    print("11 dB: reference rule %d frames, tolerant %d, typed wrongly %d" % tuple(row))
+    assert row[0] == REFERENCE_FRAMES_11DB
+    assert row == [int(v) for v in g["table"][list(g["table_esn0"]).index(11.0)]]
+    assert row[1] > REFERENCE_FRAMES_11DB and row[2] == 0
+    iq = op_bits(synth, oracle, 11.0)[0]
+    for name, use_soft in (("hard", False), ("soft", True)):
+        rows = tolerant_rows(lref, oracle, iq, DEFAULT, use_soft)
+        counts = [[len(rows[k]), sum(r[2] for r in rows[k])] for k in range(6)]
+        print(name, "rows / CRC-good rows per kind:", counts)
+        assert counts == [[int(a), int(b)] for a, b in g[name + "_counts"]]
+        assert rows == golden_rows(name)
+
+
+def test_operating_table_beside_the_operating_point(ref, oracle, synth):
+    """the other rows of DESIGN.md 8.4's table"""
+    g = golden()
+    for esn0 in (9.0, 13.0, 25.0):
+        row = operating_table(ref, oracle, synth, esn0)
+        print("%g dB: reference rule %d frames, tolerant %d, typed wrongly %d" % ((esn0,) + tuple(row)))
+        assert row == [int(v) for v in g["table"][list(g["table_esn0"]).index(esn0)]]
+        assert row[1] > row[0] and row[2] == 0
+
+
+def test_flag_value_header_and_bindings(pkg):
+    src = open(os.path.join(ROOT, "include", "tetra_rx.h")).read()
+    assert "TETRA_RX_FLAG_SYNC_TOLERANT = 128" in src and pkg.rx_binding.FLAG_SYNC_TOLERANT == 128
+    hdr = open(os.path.join(ROOT, "include", "ext", "tetra_sync_tol.h")).read()
+    L = pkg.load_library()
+    for name in list(pkg.bsync_binding.SYNC_TOL_ABI) + list(pkg.rx_binding.SYNC_TOL_ABI):
+        assert name + "(" in hdr and hasattr(L, name), name
+    assert pkg.bsync_binding.SYNC_TOL_DEFAULT == DEFAULT
+    assert all("TETRA_SYNC_TOL_DEFAULT_%s %d" % (n, v) in hdr for n, v in zip(("NORM", "SYNC", "MISS"), DEFAULT))
+
+
+# ---- 6. sanitizers ---------------------------------------------------------------------------------------------------------------------------
+
+def test_host_build_under_sanitizers(ref, tmp_path):
+    """tests/san/san_sync_tol.cpp: a stand-alone program that runs the host build over the adversarial streams, cut into calls of every
+    size of CUT_SIZES, compiled with -fsanitize=address,undefined; it prints a checksum of what the unsanitised build reports too."""
+    import subprocess
+    streams = tmp_path / "streams.bin"
+    with open(streams, "wb") as f:
+        for seed in range(10):
+            b = make_stream(ref, seed)
+            f.write(np.array([b.size], np.int32).tobytes() + b.tobytes())
+    exe = str(tmp_path / "san_sync_tol")
+    src = os.path.join(ROOT, "tests", "san", "san_sync_tol.cpp")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([exe, str(streams)], check=True, capture_output=True, text=True, env=env).stdout
+    assert "san_sync_tol ok" in out and "frames=" in out, out
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------------------
+
+def _gpu_call(torch, bs, rows, nb, packed, stream=None):
+    """one process call through the device entry points -> (frames uint8 [C][F][510], types, bit numbers, counts) on the host"""
+    dev = torch.device("cuda", 0)
+    Cn, F = bs.n_channels, bs.max_frames
+    d_rows, d_nb = torch.from_numpy(rows).to(dev), torch.from_numpy(nb).to(dev)
+    d_ft = torch.full((Cn, F), 99, dtype=torch.int32, device=dev)
+    d_fb = torch.zeros((Cn, F), dtype=torch.int32, device=dev)
+    d_nf = torch.full((Cn,), -1, dtype=torch.int32, device=dev)
+    d_fr = torch.zeros((Cn, F, 16), dtype=torch.int32, device=dev) if packed else torch.zeros((Cn, F, 512), dtype=torch.uint8, device=dev)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    (bs.process_packed_device if packed else bs.process_device)(d_rows, rows.shape[1], d_nb, d_fr, d_ft, d_fb, d_nf, stream)
+    torch.cuda.synchronize()
+    fr = d_fr.cpu().numpy()
+    if packed:
+        fr = np.unpackbits(fr.view(np.uint32).astype(">u4").view(np.uint8).reshape(Cn, F, 64), axis=2)
+        assert not fr[:, :, 510:].any()
+    return fr[:, :, :510], d_ft.cpu().numpy(), d_fb.cpu().numpy().view(np.uint32), d_nf.cpu().numpy()
+
+
+def _run_calls_against_emul(torch, pkg, tolemul, streams, tol, sizes_per_call, max_bits, packed, stream=None, emuls=None, bs=None):
+    """every channel's stream through one handle, call k = sizes_per_call[k][c] bits of channel c, against one host build per channel:
+    frames, types, bit numbers, counts, states and miss counters after every call.  Returns (handle, emuls, per-call results)."""
+    Cn = len(streams)
+    if bs is None:
+        bs = pkg.bsync_binding.BurstSync(Cn, max_bits)
+        bs.set_tolerance(tol)
+    emuls = emuls or [tolemul.Emul(tol, mode=1) for _ in range(Cn)]
+    stride = (max_bits + 15) & ~15
+    rng = np.random.default_rng(5)
+    pos = getattr(bs, "_pos", np.zeros(Cn, np.int64))
+    log = []
+    for call, sizes in enumerate(sizes_per_call):
+        rows = rng.integers(0, 2, (Cn, stride), dtype=np.uint8)              # garbage behind n_bits must be ignored
+        nb = np.zeros(Cn, np.int32)
+        for c in range(Cn):
+            nb[c] = max(0, min(int(sizes[c]), streams[c].size - pos[c]))
+            rows[c, :nb[c]] = streams[c][pos[c]:pos[c] + nb[c]]
+        fr, ft, fb, nf = _gpu_call(torch, bs, rows, nb, packed, stream)
+        st, miss = bs.states(), bs.misses()
+        want = []
+        for c in range(Cn):
+            w = emuls[c].feed(streams[c][pos[c]:pos[c] + nb[c]])
+            pos[c] += nb[c]
+            assert nf[c] == len(w[1]), (call, c, nf[c], len(w[1]))
+            assert np.array_equal(ft[c, :nf[c]], w[1]) and (ft[c, nf[c]:] == pkg.bsync_binding.FRAME_NONE).all(), (call, c)
+            assert np.array_equal(fb[c, :nf[c]], w[2]) and np.array_equal(fr[c, :nf[c]], w[0]), (call, c)
+            assert st[c] == emuls[c].state and miss[c] == emuls[c].misses, (call, c, st[c], emuls[c].state, miss[c], emuls[c].misses)
+            want.append(w)
+        log.append((want, st, miss.copy()))
+    bs._pos = pos
+    return bs, emuls, log
+
+
+def _long_adversarial(ref, seed, n):
+    parts, k = [], 0
+    while sum(p.size for p in parts) < n:
+        parts.append(make_stream(ref, seed + 100 * k))
+        k += 1
+    return np.concatenate(parts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("packed,tol,side", ((False, DEFAULT, False), (True, DEFAULT, True), (True, (2, 2, 2), False)))
+def test_gpu_tolerant_kernels_equal_the_host_build(pkg, ref, oracle, synth, tolemul, packed, tol, side):
+    """adversarial and 11 dB streams on 8 channels; calls of 66 frames' worth of bits (the LOCKED batch takes a second 64-lane round),
+    ragged counts including 0, on the null stream and on a side stream"""
+    import torch
+    rx11 = op_bits(synth, oracle, 11.0)[1]
+    streams = [_long_adversarial(ref, 3000 + c, 80000) for c in range(5)] + [np.concatenate([rx11[0], rx11[1]]), np.concatenate([rx11[2], rx11[3]]), rx11[4]]
+    rng = np.random.default_rng(21)
+    big = 33661
+    calls = [[4096] * 8, [big] * 8, [int(v) for v in rng.choice([0, 1, 509, 510, 1019, 4096, big], 8)], [big] * 8,
+             [0, 1, 511, big, 0, 4096, big, 1019], [big] * 8]
+    s = torch.cuda.Stream(torch.device("cuda", 0)) if side else None
+    bs, emuls, log = _run_calls_against_emul(torch, pkg, tolemul, streams, tol, calls, big, packed, s)
+    bs.close()
+    n_frames = sum(len(w[1]) for want, _, _ in log for w in want)
+    n_rep = sum(int((w[1] >= 0).sum()) for want, _, _ in log for w in want)
+    assert n_frames > 600 and n_rep > 300 and max(len(w[1]) for w in log[1][0]) == 66          # 64 lanes and two more: a second round
+
+
+def _destroy(bits, frame_start):
+    """no candidate in the frame that starts at bits[frame_start]: both windows inverted"""
+    bits[frame_start + 214:frame_start + 266] ^= 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("packed", (False, True))
+def test_gpu_consecutive_miss_runs_across_lanes_rounds_and_calls(pkg, synth, tolemul, packed):
+    """max_miss = 4.  Clean downlinks with destroyed training sequences placed so that the run of four misses ends on lanes 62, 63, 64 and
+    65 of the second call's LOCKED batch (the last two in its second round), starts in the counter carried over from the first call
+    (two and one misses carried), and is one short of four at the first call's end."""
+    import torch
+    tol, big, n1 = (3, 5, 4), 33661, 5609
+    base, _ = synth.gen_downlink(150, 4242)
+    # where the frames lie: the clean stream through the host build
+    e = tolemul.Emul(tol)
+    e.feed(base[:n1])
+    state, r, start, _ = e.state
+    assert state == LOCKED and r == 509 and e.misses == 0
+    # call 2 begins with 509 buffered bits and holds 67 frames: its first frame goes through the event path, the batch's lane l (of 66, in
+    # two rounds) is the call's frame l + 1
+    frame2 = lambda j: start + 510 * j                       # the call's j-th frame
+    last1 = lambda k: start - 510 * (k + 1)                  # the k-th last frame of call 1
+    plans = []
+    for lane in (62, 63, 64, 65):
+        plans.append(([frame2(lane + 1 - k) for k in range(4)], lane + 1))            # (frames to destroy, the call-2 frame that unlocks)
+    plans.append(([last1(0), last1(1), frame2(0), frame2(1)], 1))                     # two carried: unlocks at lane 0
+    plans.append(([last1(0), frame2(0), frame2(1), frame2(2)], 2))                    # one carried: lane 1
+    plans.append(([last1(0), last1(1), last1(2)], None))                              # three at the call's end, then a good frame
+    plans.append(([], None))
+    streams = []
+    for destroy, _ in plans:
+        b = base.copy()
+        for at in destroy:
+            _destroy(b, at)
+        streams.append(b)
+    bs, emuls, log = _run_calls_against_emul(torch, pkg, tolemul, streams, tol, [[n1] * 8, [big] * 8, [big] * 8], big, packed)
+    bs.close()
+    (w1, st1, miss1), (w2, st2, miss2) = log[0], log[1]
+    assert list(miss1) == [0, 0, 0, 0, 2, 1, 3, 0] and all(s[0] == LOCKED for s in st1)
+    for c, (destroy, unlock_at) in enumerate(plans):
+        types = w2[c][1]
+        if unlock_at is None:
+            assert len(types) == 67 and (types >= 0).all() and st2[c][0] == LOCKED and miss2[c] == 0, c
+        else:
+            # the frame that unlocks is the last LOCKED call before the 1020-bit wait: the next frame, if any, does not follow at 510 bits
+            assert types[unlock_at] == -1 and w2[c][2][unlock_at] == frame2(unlock_at), c
+            assert len(types) == unlock_at + 1 or w2[c][2][unlock_at + 1] - w2[c][2][unlock_at] > 510, (c, len(types))
+            assert miss2[c] == 0, c
+
+
+@pytest.mark.gpu
+def test_gpu_setting_and_clearing_the_tolerance(pkg, ref, oracle, tolemul):
+    import torch
+    bb = pkg.bsync_binding
+    Cn, max_bits = 6, 9000
+    streams = [_long_adversarial(ref, 7000 + c, 6 * max_bits) for c in range(Cn)]
+    bs = bb.BurstSync(Cn, max_bits)
+    oracles = [oracle.BurstSyncOracle() for _ in range(Cn)]
+    stride = (max_bits + 15) & ~15
+
+    def reference_call(pos):
+        rows = np.zeros((Cn, stride), np.uint8)
+        for c in range(Cn):
+            rows[c, :max_bits] = streams[c][pos:pos + max_bits]
+        fr, ft, fb, nf = _gpu_call(torch, bs, rows, np.full(Cn, max_bits, np.int32), False)
+        for c in range(Cn):
+            w = oracles[c].feed(streams[c][pos:pos + max_bits], 1)
+            assert nf[c] == len(w[1]) and np.array_equal(ft[c, :nf[c]], w[1]) and np.array_equal(fb[c, :nf[c]], w[2]), c
+            assert np.array_equal(fr[c, :nf[c]], w[0]) and bs.states()[c] == oracles[c].state, c
+        assert not bs.misses().any()
+
+    reference_call(0)                                             # the default: the reference's rule
+    bs.set_tolerance(DEFAULT)                                     # from the next call on
+    emuls = []
+    for c in range(Cn):
+        e = tolemul.Emul(DEFAULT, mode=1)
+        e.st[:] = oracles[c].state
+        e.carry[:e.st[1]] = oracles[c]._st[16:16 + e.st[1]]
+        emuls.append(e)
+    bs._pos = np.full(Cn, max_bits, np.int64)
+    _, _, log = _run_calls_against_emul(torch, pkg, tolemul, streams, DEFAULT, [[max_bits] * Cn], max_bits, False, emuls=emuls, bs=bs)
+    assert any(len(w[1]) for w in log[0][0])
+    bs.set_tolerance((4, 6, 255))
+    assert not bs.misses().any()                                  # setting zeroes the counters
+    for e in emuls:
+        e.tol[:] = (4, 6, 255)
+        e.miss[:] = 0
+    _run_calls_against_emul(torch, pkg, tolemul, streams, None, [[max_bits] * Cn], max_bits, False, emuls=emuls, bs=bs)
+    bs.set_tolerance(None)                                        # back to the reference's rule, from the state the handle is in
+    for c in range(Cn):
+        v = oracles[c]._st[:16].view(np.uint32)
+        v[:] = emuls[c].st
+        oracles[c]._st[16:16 + v[1]] = emuls[c].carry[:v[1]]
+    reference_call(3 * max_bits)
+    # statuses
+    for bad in ((5, 0, 1), (0, 7, 1), (0, 0, 0), (0, 0, 256), (-1, 0, 1), (0, -1, 1)):
+        with pytest.raises(pkg.TetraDemodError) as err:
+            bs.set_tolerance(bad)
+        assert err.value.status == -1
+    reference_call(4 * max_bits)                                  # a refused setting changes nothing
+    L = bb._lib()
+    assert L.tetra_bsync_set_tolerance(None, None) == -1 and L.tetra_bsync_get_misses(None, 0, 0, None) == -1
+    out = np.zeros(Cn, np.int32)
+    assert L.tetra_bsync_get_misses(bs._h, 0, Cn + 1, out.ctypes.data) == -1 and L.tetra_bsync_get_misses(bs._h, -1, 1, out.ctypes.data) == -1
+    bs.close()
+
+
+@pytest.fixture(scope="module")
+def op11(synth):
+    return op_iq(synth, 11.0)[0]
+
+
+def _rx_soft():
+    from tests import test_rx_soft
+    return test_rx_soft
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("one_stream", [False, True])
+def test_gpu_tolerant_chain_equals_the_fixture(pkg, op11, one_stream):
+    """flag 128 at the operating point, the stream cut as 9000, 180, 1, 0, 4000, ... samples: row for row the reference-only pipeline
+    behind the restatement's frames"""
+    R, T = pkg.rx_binding, _rx_soft()
+    want = golden_rows("hard")
+    got = T.run_stream(pkg, op11, T.ragged_cuts(OP_SAMPLES), flags=R.FLAG_SYNC_TOLERANT | (R.FLAG_ONE_STREAM if one_stream else 0))
+    for k in range(R.N_KINDS):
+        assert sorted(got[k]) == sorted(want[k]), (k, len(got[k]), len(want[k]))
+
+
+@pytest.mark.gpu
+def test_gpu_tolerant_chain_beside_the_other_flags_and_through_the_delivery(pkg, op11):
+    R, T = pkg.rx_binding, _rx_soft()
+    cuts = [0, 16000, 32000, OP_SAMPLES]
+    soft = T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_SOFT)
+    want = golden_rows("soft")
+    for k in range(R.N_KINDS):
+        assert sorted(soft[k]) == sorted(want[k]), k
+    # every flag at once: the coded kinds are the soft rows, the AACH rows are as many
+    rx = pkg.RxChain(OP_CHANNELS, OP_SAMPLES, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_SOFT | R.FLAG_BITERR | R.FLAG_AACH_RM3014)
+    rx.process(op11)
+    rx.wait()
+    got = T._collect(rx, R)
+    for k in range(R.N_KINDS):
+        if k != R.KIND_BBK:
+            assert got[k] == want[k], k
+    assert len(got[R.KIND_BBK]) == len(want[R.KIND_BBK]) == int(golden()["table"][1][1])
+    errors, compared = rx.fetch_biterr(R.KIND_SCH_F)
+    assert len(errors) == len(want[R.KIND_SCH_F]) and 0 < compared.min() and compared.max() <= 432 and (errors <= compared).all()
+    assert rx.sync_misses().shape == (OP_CHANNELS,)
+    # the one-step delivery: the rows of every kind as fetch gives them
+    dl = rx.deliver().wait()
+    for k in range(R.N_KINDS):
+        blocks, t1 = rx.fetch(k)
+        assert np.array_equal(dl[k][0], blocks) and np.array_equal(dl[k][1][:, :t1.shape[1]], t1), k
+    rx.close()
+    # the flag alone and 4 / 16 / 64 beside it
+    for flags in (R.FLAG_SYNC_TOLERANT | 4, R.FLAG_SYNC_TOLERANT | 16, R.FLAG_SYNC_TOLERANT | 64, 256):
+        with pytest.raises(pkg.TetraDemodError) as e:
+            pkg.RxChain(2, 2000, flags=flags)
+        assert e.value.status == -1
+
+
+@pytest.mark.gpu
+def test_gpu_chain_tolerance_is_settable_between_calls(pkg, op11):
+    """a chain created without the flag and switched with tetra_rx_set_sync_tolerance before its first call is the flag's chain; switched
+    back to NULL it is the default chain"""
+    R, T = pkg.rx_binding, _rx_soft()
+    for tol, name in ((DEFAULT, "hard"), (None, None)):
+        rx = pkg.RxChain(OP_CHANNELS, OP_SAMPLES, flags=0 if tol else R.FLAG_SYNC_TOLERANT)
+        rx.set_sync_tolerance(tol)
+        rx.process(op11)
+        rx.wait()
+        got = T._collect(rx, R)
+        want = golden_rows(name) if name else T.golden_rows("hard")
+        for k in range(R.N_KINDS):
+            assert got[k] == want[k], (tol, k)
+        with pytest.raises(pkg.TetraDemodError):
+            rx.set_sync_tolerance((9, 9, 9))
+        rx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_tolerant_through_the_wideband_handle(pkg, synth):
+    """32 bins, 3 carriers at 25 dB: cfg.rx carries the flag to the wideband handle's chain -- every frame of the default handle is there
+    (channel, bit number), every block the default handle passes is passed with the same bits (the clock labels may differ: the clock
+    steps with every frame consumed), and the chain's entry points work on tetra_wbrx_rx(h)"""
+    import torch
+    from tests.test_wbrx import _capture, _rows
+    R = pkg.rx_binding
+    x, cells, tx = _capture(torch, synth, 32, {1: 11, 7: 12, 20: 13}, 40)
+    runs = {}
+    for flags in (0, R.FLAG_SYNC_TOLERANT):
+        wb = pkg.WidebandRx([1, 7, 20], n_channels=32, decimation=16, max_in=x.shape[0], flags=flags)
+        wb.process_device(x)
+        runs[flags] = _rows(wb.rx, R)
+        assert wb.sync_misses().shape == (3,)
+        if flags:
+            wb.set_sync_tolerance((2, 2, 2))
+            assert not wb.sync_misses().any()
+            wb.set_sync_tolerance(None)
+        wb.close()
+    hard, tol = runs[0], runs[R.FLAG_SYNC_TOLERANT]
+    for k in range(R.N_KINDS):
+        by_frame = {r[:2]: r for r in tol[k]}
+        assert all(r[:2] in by_frame for r in hard[k]) and len(tol[k]) >= len(hard[k]) >= (8 if k != R.KIND_BBK else 30), k
+        good = [r for r in hard[k] if r[2] and k != R.KIND_BBK]          # (the AACH passes as it is, descrambled with the code of the moment)
+        assert k == R.KIND_BBK or len(good) >= 5 and all(by_frame[r[:2]][2] == 1 and by_frame[r[:2]][5] == r[5] for r in good), k
+    with pytest.raises(pkg.TetraDemodError):
+        pkg.WidebandRx([1, 7, 20], n_channels=32, decimation=16, max_in=1 << 16, flags=R.FLAG_SYNC_TOLERANT | 4)
+
+
+@pytest.mark.gpu
+def test_gpu_reset_of_one_channel_zeroes_its_miss_counter(pkg, op11):
+    """channel 1 of 3 loses its signal from sample 9000 to 12000, so at the call boundary at 12000 samples its miss counter stands above
+    0; tetra_rx_reset_channels_device on it there zeroes that counter in stream order and leaves the other channels' rows the fixture's"""
+    R, T = pkg.rx_binding, _rx_soft()
+    iq = op11[:3].copy()
+    g = np.random.default_rng(99)
+    iq[1, 9000:12000] = (0.05 * (g.standard_normal(3000) + 1j * g.standard_normal(3000))).astype(np.complex64)
+    step, at = 6000, 2
+    cuts = list(range(0, OP_SAMPLES + 1, step))
+    seen = {}
+
+    def between(rx, i, s):
+        if i == at - 1:
+            seen["before"] = rx.sync_misses().copy()
+            rx.reset_channels([1], s)
+            seen["after"] = rx.sync_misses().copy()
+            seen["state"] = rx.sync_states()[1]
+
+    got = T.run_stream(pkg, iq, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=step, between=between)
+    assert 0 < seen["before"][1] < 16 and seen["after"][1] == 0 and seen["state"] == (0, 0, 0, 0), seen
+    assert np.array_equal(seen["before"][[0, 2]], seen["after"][[0, 2]])
+    want = golden_rows("hard")
+    for k in range(R.N_KINDS):
+        for c in (0, 2):
+            assert sorted(r for r in got[k] if r[0] == c) == sorted(r for r in want[k] if r[0] == c), (k, c)
+    assert len([r for r in got[R.KIND_BBK] if r[0] == 1]) > 10            # and channel 1 locks again behind the reset
+
+
+@pytest.mark.gpu
+def test_gpu_tolerant_lock_delivers_more_blocks(pkg, op11):
+    """THE GAIN: at 11 dB the flag yields more SCH/F rows and more CRC-good SCH/F rows than the default chain; the counts are the
+    fixture's (147 / 112 against the reference rule's 118 / 97)"""
+    R, T = pkg.rx_binding, _rx_soft()
+    cuts = [0, 16000, 32000, OP_SAMPLES]
+    off, on = T.run_stream(pkg, op11, cuts, flags=0), T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT)
+    n = {name: (len(rows[R.KIND_SCH_F]), sum(r[2] for r in rows[R.KIND_SCH_F])) for name, rows in (("off", off), ("on", on))}
+    print("SCH/F rows / CRC-good rows: flag off %s, flag on %s" % (n["off"], n["on"]))
+    assert n["off"] == T.OP_SCHF["hard"] and n["on"] == tuple(int(v) for v in golden()["hard_counts"][R.KIND_SCH_F])
+    assert n["on"][0] > n["off"][0] and n["on"][1] > n["off"][1]
+    assert sum(len(v) for k, v in on.items() if k in (R.KIND_SB1, R.KIND_NDB1, R.KIND_SCH_F)) == int(golden()["table"][1][1]) > REFERENCE_FRAMES_11DB
+
+
+@pytest.mark.gpu
+def test_gpu_resets_zero_the_miss_counters(pkg, synth, op11):
+    """tetra_bsync_reset and tetra_rx_reset: counters that stand above 0 are 0 afterwards, with the state"""
+    import torch
+    tol, n1 = (3, 5, 4), 5609
+    base, _ = synth.gen_downlink(150, 4242)                # (the stream of the miss-run test: LOCKED with 509 bits buffered after 5609)
+    streams = []
+    for k in (2, 3, 0):                                    # the last k frames of the call destroyed (the call ends 509 bits behind a frame)
+        b = base.copy()
+        for j in range(k):
+            _destroy(b, 5100 - 510 * (j + 1))
+        streams.append(b)
+    bs = pkg.bsync_binding.BurstSync(3, n1)
+    assert not bs.misses().any()                           # (a handle that never was tolerant: zeros)
+    bs.set_tolerance(tol)
+    rows = np.zeros((3, (n1 + 15) & ~15), np.uint8)
+    for c in range(3):
+        rows[c, :n1] = streams[c][:n1]
+    _gpu_call(torch, bs, rows, np.full(3, n1, np.int32), True)
+    assert list(bs.misses()) == [2, 3, 0] and all(s[0] == LOCKED for s in bs.states())
+    bs.reset()
+    assert not bs.misses().any() and bs.states() == [(0, 0, 0, 0)] * 3
+    bs.close()
+    # the chain: channel 1 loses its signal before the end of the call
+    R = pkg.rx_binding
+    iq = op11[:3, :12000].copy()
+    g = np.random.default_rng(99)
+    iq[1, 9000:12000] = (0.05 * (g.standard_normal(3000) + 1j * g.standard_normal(3000))).astype(np.complex64)
+    rx = pkg.RxChain(3, 12000, flags=R.FLAG_SYNC_TOLERANT)
+    rx.process(iq)
+    rx.wait()
+    before = rx.sync_misses()
+    assert 0 < before[1] < 16
+    rx.reset()
+    assert not rx.sync_misses().any() and rx.sync_states() == [(0, 0, 0, 0)] * 3
+    rx.process(iq)                                         # and the chain runs on under the tolerant rule
+    rx.wait()
+    assert np.array_equal(rx.sync_misses(), before)
+    rx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_chain_tolerance_set_with_a_tail_in_flight(pkg, op11):
+    """tetra_rx_set_sync_tolerance right behind a process call, without waiting: it waits for that call's tail itself, so the rows are
+    those of a chain that waited first -- the first call under the reference's rule, the others under {3, 5, 16}"""
+    import torch
+    R, T = pkg.rx_binding, _rx_soft()
+    cuts = [0, 12000, 24000, OP_SAMPLES]
+    runs = []
+    for wait_first in (True, False):
+        def between(rx, i, s, wait_first=wait_first):
+            if i == 0:
+                if wait_first:
+                    rx.wait()
+                rx.set_sync_tolerance(DEFAULT)
+                assert not rx.sync_misses().any()
+        runs.append(T.run_stream(pkg, op11, cuts, flags=0, max_samples=12000, between=between))
+    plain, tolerant = T.run_stream(pkg, op11, cuts, flags=0, max_samples=12000), T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=12000)
+    first_call_bits = 11000                                # (every frame below this bit number ended inside the first call)
+    for k in range(R.N_KINDS):
+        assert runs[0][k] == runs[1][k], k
+        head = [r for r in runs[1][k] if r[1] + 510 < first_call_bits]
+        assert head == [r for r in plain[k] if r[1] + 510 < first_call_bits], k
+    print("SCH/F rows: reference rule %d, switched behind the first call %d, tolerant from the start %d" % tuple(len(r[R.KIND_SCH_F]) for r in (plain, runs[1], tolerant)))
+
+
+@pytest.mark.gpu
+def test_gpu_wideband_retune_zeroes_the_moved_slots_counter(pkg, synth):
+    """the carriers vanish in a second capture, so every locked slot counts misses; tetra_wbrx_retune of slot 2 zeroes its counter in stream
+    order and leaves the others'"""
+    import torch
+    from tests.test_wbrx import BINS_SMALL, CARRIERS_SMALL, D_SMALL, M_SMALL, _capture
+    R = pkg.rx_binding
+    x, _, _ = _capture(torch, synth, M_SMALL, CARRIERS_SMALL, 24)
+    g = torch.Generator(device=x.device)
+    g.manual_seed(5)
+    quiet = (1e-3 * torch.view_as_complex(torch.randn((x.shape[0] // 4, 2), device=x.device, generator=g))).to(torch.complex64).contiguous()
+    wb = pkg.WidebandRx(BINS_SMALL, n_channels=M_SMALL, decimation=D_SMALL, max_in=x.shape[0], flags=R.FLAG_SYNC_TOLERANT)
+    try:
+        s = torch.cuda.current_stream()
+        wb.set_sync_tolerance((3, 5, 255))                 # (no unlock however long the silence)
+        wb.process_device(x, x.shape[0], s)
+        assert all(st[0] == LOCKED for st in wb.rx.sync_states())
+        wb.process_device(quiet, quiet.shape[0], s)
+        before = wb.sync_misses()
+        assert (before > 0).all(), before
+        moved = list(BINS_SMALL)
+        moved[2] = 9
+        wb.retune(moved, s)
+        after = wb.sync_misses()
+        assert after[2] == 0 and wb.rx.sync_states()[2] == (0, 0, 0, 0)
+        assert [after[c] for c in range(len(BINS_SMALL)) if c != 2] == [before[c] for c in range(len(BINS_SMALL)) if c != 2]
+    finally:
+        wb.close()
+
+
+@pytest.mark.gpu
+def test_gpu_host_bank_sets_the_tolerance_and_reads_the_counters(pkg, synth, tmp_path):
+    """TetraRxBank::setSyncTolerance / syncMisses (host/tetra_rx_bank.h) from a plain C++ driver (tests/host/test_sync_tol_bank.cpp): a bank
+    switched with setSyncTolerance is the bank created with the flag, row for row and counter for counter"""
+    import subprocess
+    from tests.test_rx_out import _noisy_batch
+    pk = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
+    pkg.build.build()
+    exe = str(tmp_path / "test_sync_tol_bank")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(pk, "host"),
+                    os.path.join(ROOT, "tests", "host", "test_sync_tol_bank.cpp"), "-L", pk, "-ltetra_demod_hip", "-Wl,-rpath," + pk, "-o", exe], check=True)
+    Cn, calls, nslots = 5, 2, 32
+    N = nslots * 510 // calls
+    _, _, iq = _noisy_batch(synth, Cn, nslots, N * calls, 8950)
+    f = tmp_path / "iq.bin"
+    with open(f, "wb") as fh:
+        for k in range(calls):
+            fh.write(np.ascontiguousarray(iq[:, k * N:(k + 1) * N]).astype(np.complex64).tobytes())
+    r = subprocess.run([exe, str(Cn), str(N), str(calls), str(f)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "test_sync_tol_bank: ok" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
+    assert int(r.stdout.split()[2]) > 100
+
+
+# ---- the fixture's generator ---------------------------------------------------------------------------------------------------------------
+
+def write_golden():
+    """python -m tests.test_sync_tol --write-golden: the operating table and the operating point's rows, from the reference-only pipeline
+    behind the restatement's frames"""
+    import tetra_amd
+    from oracle import binding as oracle, ref_binding as ref
+    synth = tetra_amd.pkg.synth
+    oracle.build()
+    out = dict(table_esn0=np.array(OP_ESN0), table=np.array([operating_table(ref, oracle, synth, e) for e in OP_ESN0], np.int64))
+    iq = op_bits(synth, oracle, 11.0)[0]
+    for name, use_soft in (("hard", False), ("soft", True)):
+        rows = tolerant_rows(ref, oracle, iq, DEFAULT, use_soft)
+        out[name + "_counts"] = np.array([[len(rows[k]), sum(r[2] for r in rows[k])] for k in range(6)], np.int64)
+        for k in range(6):
+            a = rows_to_arrays(rows[k], sp.TYPE1_BITS[k])
+            out["%s_%d_label" % (name, k)], out["%s_%d_type1" % (name, k)] = a["label"], a["type1"]
+    np.savez_compressed(GOLDEN, **out)
+    print(out["table_esn0"], out["table"], out["hard_counts"], out["soft_counts"], sep="\n")
+
+
+if __name__ == "__main__":
+    import sys
+    if "--write-golden" in sys.argv:
+        write_golden()
