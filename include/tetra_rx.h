@@ -68,6 +68,13 @@ enum {
                                       training sequence is looked for at the expected position only and may carry a few bit errors, and lock is
                                       dropped only behind several consecutive misses.  DEPARTS FROM THE REFERENCE (more frames at low Es/N0);
                                       composes with every other flag; row formats, labels and every fetch / delivery entry are unchanged */
+    /* 256 is not a flag either (tests hold it refused). */
+    TETRA_RX_FLAG_LIST = 512,      /* CRC-aided list decoding (ext/tetra_list.h): a coded block (SB1, SB2, NDB 1 / 2, SCH/F) whose decoded path
+                                      fails its CRC is decoded again along the few next-best paths (tetra_rx_set_list_candidates, default 4) and
+                                      takes the first whose CRC is good; tetra_rx_fetch_list_rank says which rows were rescued.  SB1 is rescued
+                                      in front of the SYNC tracker.  DEPARTS FROM THE REFERENCE (more CRC-good blocks at low Es/N0, at up to T x
+                                      2^-16 false accepts per failed block); composes with every other flag; row formats, labels and every
+                                      fetch / delivery entry are unchanged */
     TETRA_RX_FLAG_SOFT = 8         /* soft decisions: SB1, SB2, NDB 1 / 2 and SCH/F are decoded from the demodulator's symbols -- per bit a
                                       6-bit soft value of the differential phase, kept per channel in a ring indexed by `bitnum` -- where
                                       the default slices every symbol to two hard bits first.  Same decoder as the reference's

@@ -43,6 +43,12 @@
 #else
 #define LM_FN static inline
 #endif
+// (member functions of the defaulted hooks below)
+#if defined(__HIPCC__) && !defined(TETRA_HOST_EMUL)
+#define LM_MEM __device__ __forceinline__
+#else
+#define LM_MEM inline
+#endif
 
 namespace tetra_lmac {
 
@@ -408,8 +414,11 @@ LM_FN int interleave_next(int& pos, int a, int K) {
 // u and consumed after it (software pipelining by one round): a wavefront that has its SIMD to itself -- the last long blocks of a
 // launch, every wave of a small one -- does not wait for LDS.  n2 is even for every block kind.  s0 = the start metric of state 0,
 // 127 * N * K in the units of the branch metrics: 20 for classes in units of 127, 2540 for raw soft values (soft_core.hpp).
-template <class Fetch, class Make, class St>
-LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st, int s0 = 4 * 5) {
+// probe(u, De, Do) sees the differences of steps 2u, 2u + 1 -- every pair, the flush steps included -- as acs_step left them: the list
+// decoder (list_core.hpp) collects its margins there; the default sees nothing and costs nothing.
+struct NoProbe { LM_MEM void operator()(int, const Pk*, const Pk*) const {} };
+template <class Fetch, class Make, class St, class Probe = NoProbe>
+LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st, int s0 = 4 * 5, Probe probe = Probe()) {
     PathMetrics pm;
 #pragma unroll
     for (int i = 0; i < 8; ++i) pm.R[i] = pk_make(0, 0);
@@ -424,6 +433,7 @@ LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st, int s0 = 4 * 5
         const Pk Mo[8] = { m.C, m.C, m.C, m.C, pk_swap(m.C), pk_swap(m.C), pk_swap(m.C), pk_swap(m.C) };
         acs_step(pm, Mo, Do);
         st(u, decision_word(De, Do));
+        probe(u, De, Do);
     }
 #pragma unroll
     for (int f = 0; f < kFlush / 2; ++f) {
@@ -433,6 +443,7 @@ LM_FN void viterbi_forward(int n2, Fetch fetch, Make make, St st, int s0 = 4 * 5
         acs_step(pm, Mz, De);
         acs_step(pm, Mz, Do);
         st(n2 / 2 + f, decision_word(De, Do));
+        probe(n2 / 2 + f, De, Do);
     }
 }
 // what fetch() hands to make(): the three LDS words that hold a step pair's soft values and where in them
@@ -472,16 +483,19 @@ constexpr CrcInvTable make_crc_inv_table() {
 // shifts, so after the 16 steps of group h bits 4..31 of ~y are the decoded bits 16h .. 16h+27: the CRC bytes, which end 4 bits
 // before a group boundary, are cut from there -- bits 16h+12..16h+19 (not in the top group: tail bits) and 16h+4..16h+11; the four
 // bits 0..3 left at the end take four single steps.
-template <class Ld, class St, class Tinv>
-LM_FN bool viterbi_traceback(int n2, Ld ld, St st, Tinv tinv) {
+// flip(step) = all ones where the decision met at that step is to be inverted, else 0 (one XOR on the extracted -d): a candidate path
+// of the list decoder (list_core.hpp); the default inverts nothing and costs nothing.
+struct NoFlip { LM_MEM uint32_t operator()(int) const { return 0u; } };
+template <class Ld, class St, class Tinv, class Flip = NoFlip>
+LM_FN bool viterbi_traceback(int n2, Ld ld, St st, Tinv tinv, Flip flip = Flip()) {
     uint32_t y = 15u;
 #pragma unroll
     for (int f = kFlush / 2 - 1; f >= 0; --f) {
         const uint32_t w = ld(n2 / 2 + f);
         uint32_t t = y << 1;
-        y = t + 1u + bfe_mask(w, t);
+        y = t + 1u + (bfe_mask(w, t) ^ flip(n2 + 2 * f + 1));
         t = (y << 1) | 1u;
-        y = t + bfe_mask(w, t);
+        y = t + (bfe_mask(w, t) ^ flip(n2 + 2 * f));
     }
     uint32_t r4 = kCrcOk << 2;
     const int top = n2 / 16 - 1;
@@ -498,9 +512,9 @@ LM_FN bool viterbi_traceback(int n2, Ld ld, St st, Tinv tinv) {
         for (int b2 = 7; b2 >= 0; --b2) {
             const uint32_t w = cur[b2];
             uint32_t t = y << 1;
-            y = t + 1u + bfe_mask(w, t);
+            y = t + 1u + (bfe_mask(w, t) ^ flip(16 * h + 2 * b2 + 1));
             t = (y << 1) | 1u;
-            y = t + bfe_mask(w, t);
+            y = t + (bfe_mask(w, t) ^ flip(16 * h + 2 * b2));
         }
         const uint32_t bits = ~y;
         st(h, (bits >> 4) & 0xffffu);
@@ -522,13 +536,14 @@ LM_FN uint32_t spread4(uint32_t nib) { return (nib * 0x00204081u) & 0x01010101u;
 // Steps 2-3 for a lane whose type-4 bits (BITS: bit i at bit 31 - (i & 31) of word i >> 5) or soft classes (16 per word, descramble_chunk)
 // are behind cls(word).  io = the lane's other memory: dec_st(u, word) / dec_ld(u) its decision word of step pair u, out_st(h, half)
 // its decoded bits 16h .. 16h+15, tinv(off) the backward CRC table.  Returns the lane's CRC verdict.
-template <class Io>
-LM_FN bool traceback(int type2, Io& io) {        // (own lane's data only: program order is enough)
+template <class Io, class Flip = NoFlip>
+LM_FN bool traceback(int type2, Io& io, Flip flip = Flip()) {        // (own lane's data only: program order is enough)
     return viterbi_traceback(type2, [&](int u) { return io.dec_ld(u); }, [&](int h, uint32_t half) { io.out_st(h, half); },
-                             [&](uint32_t off) { return io.tinv(off); });
+                             [&](uint32_t off) { return io.tinv(off); }, flip);
 }
-template <bool BITS, class Cls, class Io>
-LM_FN bool decode_hard(int type345, int type2, int a, Cls cls, Io& io) {
+// step 2 alone: dec_st(u, word) as viterbi_forward's st, probe as there
+template <bool BITS, class Cls, class DecSt, class Probe = NoProbe>
+LM_FN void forward_hard(int type345, int type2, int a, Cls cls, DecSt dec_st, Probe probe = Probe()) {
     int pos = a;                       // (a * i) % K for i = 1
     auto fetch = [&] {
         Raw3 r;
@@ -540,16 +555,19 @@ LM_FN bool decode_hard(int type345, int type2, int a, Cls cls, Io& io) {
         }
         return r;
     };
-    auto dec_st = [&](int u, uint32_t w) { io.dec_st(u, w); };
     if (BITS) {
         viterbi_forward(type2, fetch,
                         [&](const Raw3& r) { return bm_from_masks(bfe_mask(r.w[0], r.at[0]), bfe_mask(r.w[1], r.at[1]), bfe_mask(r.w[2], r.at[2])); },
-                        dec_st);
+                        dec_st, 4 * 5, probe);
     } else {
         viterbi_forward(type2, fetch,
                         [&](const Raw3& r) { return bm_from_classes((int)(r.w[0] << r.at[0]) >> 30, (int)(r.w[1] << r.at[1]) >> 30, (int)(r.w[2] << r.at[2]) >> 30); },
-                        dec_st);
+                        dec_st, 4 * 5, probe);
     }
+}
+template <bool BITS, class Cls, class Io>
+LM_FN bool decode_hard(int type345, int type2, int a, Cls cls, Io& io) {
+    forward_hard<BITS>(type345, type2, a, cls, [&](int u, uint32_t w) { io.dec_st(u, w); });
     return traceback(type2, io);
 }
 

@@ -33,6 +33,7 @@ struct KindBufs {                 // one parity's results of one kind
     DevMem<int32_t> ok;           // [rows]
     DevMem<tetra_rx_block_t> blocks;      // [rows]
     DevMem<uint32_t> biterr;              // [rows] errors | compared << 16 (TETRA_RX_FLAG_BITERR, coded kinds only)
+    DevMem<int32_t> rank;                 // [rows] 0 / rank / -1 (TETRA_RX_FLAG_LIST, coded kinds only)
     // into the parity's frame lists (not owned): the kind's rows are the frames row_frame[0 .. *n_rows)
     const int32_t* row_frame = nullptr;
     const int32_t* n_rows = nullptr;
@@ -59,6 +60,10 @@ struct tetra_rx {
     // TETRA_RX_FLAG_BITERR (tetra_biterr.h): the decode launches count channel bit errors per row, a kernel behind them sums them per channel
     bool biterr = false;
     DevMem<tetra_rx_link_t> link;         // [C], accumulated by the tails (one at a time, on one stream), zeroed by the resets
+    // TETRA_RX_FLAG_LIST (tetra_list.h): the decode launches are followed by the rescue of their CRC-failed rows
+    bool list = false;
+    int list_T = 4;                       // tetra_rx_set_list_candidates
+    DevMem<void> list_ws;                 // the list launches' compaction words (lmac_impl::list_work_bytes of the larger decode launch)
     Handle<tetra_demod_t*, tetra_demod_destroy> dem;
     Handle<tetra_bsync_t*, tetra_bsync_destroy> bs;
     Stream tail;

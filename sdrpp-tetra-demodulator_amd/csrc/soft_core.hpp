@@ -109,8 +109,9 @@ LM_FN void stage_block(int layout, uint32_t bitnum, int frame_type, Ring ring, u
 
 // The forward recursion on the staged block: ld(w) = the lane's staged word w.  Deinterleaving and depuncturing are by address as
 // on the hard routes (a punctured position never enters a branch metric: it is the reference's 0); dec_st as viterbi_forward's st.
-template <class Ld, class DecSt>
-LM_FN void forward(int type345, int type2, int a, Ld ld, DecSt dec_st) {
+// probe: as viterbi_forward's.
+template <class Ld, class DecSt, class Probe = NoProbe>
+LM_FN void forward(int type345, int type2, int a, Ld ld, DecSt dec_st, Probe probe = Probe()) {
     int pos = a;
     viterbi_forward(type2,
                     [&] {
@@ -126,7 +127,7 @@ LM_FN void forward(int type345, int type2, int a, Ld ld, DecSt dec_st) {
                     [&](const Raw3& r) {
                         return bm_from_classes((int)bfe_u(r.w[0], r.at[0], 8) - 128, (int)bfe_u(r.w[1], r.at[1], 8) - 128, (int)bfe_u(r.w[2], r.at[2], 8) - 128);
                     },
-                    dec_st, kStartMetric);
+                    dec_st, kStartMetric, probe);
 }
 // steps 2-3 of the soft route: the forward recursion above, then the hard route's traceback (io: as decode_hard's)
 template <class Ld, class Io>

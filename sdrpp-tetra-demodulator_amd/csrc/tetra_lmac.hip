@@ -34,9 +34,12 @@
 
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
+#include "../../include/ext/tetra_list.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
+#include "compact_core.hpp"
 #include "hip_host.hpp"
+#include "list_core.hpp"
 #include "lmac_core.hpp"
 #include "lmac_impl.hpp"
 #include "soft_core.hpp"
@@ -370,6 +373,178 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
     write_rows(sm.outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
 }
 
+// ---- list decoding of the rows whose CRC failed (include/ext/tetra_list.h; lane code: list_core.hpp) ------------------------------------------
+// Four launches BEHIND a decode launch that was asked for ranks, on its stream, for ALL its jobs together, none otherwise.  The rows of
+// the jobs with ranks form one index space, a job's rows rounded up to whole tiles of 256, so that a tile belongs to one job:
+// k_list_count, k_list_scan and k_list_fill (compact_core.hpp's three steps over crc_ok == 0; the fill also writes every row's default
+// rank, 0 for a good row and -1 for a failed one) leave ONE list of failed rows, job after job, and the scanned tile offsets say where
+// a job's part of it begins.  k_list_rescue is a small persistent grid: a workgroup takes 64 failed rows of one job at a time, a row per
+// lane, whichever workgroup decoded them, and strides over the list; with no failed row every workgroup reads a handful of words and
+// leaves.  The cost is that of the failed rows.
+// A lane stages its block again through the front end its decode launch used (FRONT), reads the decoder's decision words of its row
+// from the launch's scratch -- which the host therefore hands back only behind this kernel --, and runs list_core.hpp's rescue.  The
+// winner's row, verdict, label verdict, rank and (where the launch counts) channel bit errors are written by the lane itself: plain
+// 4-byte stores to one row.
+// Beside k_fused (compact_core.hpp's note): workgroups of 256 (compaction) and 64 threads.
+constexpr int kListTile = 256;
+constexpr int kRescueGroups = 512;         // the persistent grid (two per compute unit)
+enum { kFrontBytes, kFrontFrames, kFrontSoft };
+struct RescueJob {
+    // the rows of a job of the decode launch
+    const int* n_dev;
+    int n;
+    int first_tile;                    // of the launch's tiles, the job's first
+    int* crc_ok;
+    uint8_t* out;
+    int out_stride;
+    tetra_lmac_label_t* labels;
+    uint32_t* counts;
+    int32_t* rank;
+    const uint32_t* dec;               // the rows' decision scratch, [workgroup][pair][lane]
+    int dec_pairs;
+    int type345, type2, a;
+    // front ends: byte rows
+    const uint8_t* type5;
+    int in_stride, fixed_init;
+    const uint32_t* scramb_init;
+    const int* init_index;
+    // ... frames and soft values
+    const int* row_frame;
+    const uint32_t* frame_scramb;
+    int layout;
+};
+struct RescueTable {
+    RescueJob job[TETRA_LMAC_MAX_JOBS];
+    int n, tiles, T;
+    // the compacted failed rows
+    int* work;                         // [tiles]: failed rows per tile, scanned in place to the tile's first list position
+    int* total;
+    int* list;                         // [sum of the jobs' rows]: the failed rows' numbers within their job
+    DevFrames src;
+    const uint32_t* seq_tab;
+    const uint32_t* ring;
+    uint32_t ring_words;
+};
+__device__ __forceinline__ int list_rows(const RescueJob& J) {
+    int n = J.n;
+    if (J.n_dev) {
+        const int have = *J.n_dev;
+        n = have < n ? have : n;
+    }
+    return n;
+}
+__device__ __forceinline__ int job_of_tile(const RescueTable& tab, int tile) {
+    int j = 0;
+    for (int i = 1; i < tab.n; ++i) j = tile >= tab.job[i].first_tile ? i : j;
+    return j;
+}
+__global__ __launch_bounds__(kListTile) void k_list_count(const RescueTable tab) {
+    const int tile = (int)blockIdx.x;
+    const RescueJob& J = tab.job[job_of_tile(tab, tile)];
+    const int n = list_rows(J), t0 = (tile - J.first_tile) * kListTile;
+    if (t0 >= n) {
+        if (threadIdx.x == 0) tab.work[tile] = 0;
+        return;
+    }
+    const int i = t0 + (int)threadIdx.x;
+    compact_core::block_count<1>(i < n && J.crc_ok[i] == 0, tab.work, tab.tiles, tile);
+}
+__global__ __launch_bounds__(compact_core::kScanThreads) void k_list_scan(const RescueTable tab) {
+    const int len[1] = { tab.tiles };
+    compact_core::scan_counts<1>(tab.work, tab.tiles, len, tab.total);
+}
+__global__ __launch_bounds__(kListTile) void k_list_fill(const RescueTable tab) {
+    const int tile = (int)blockIdx.x;
+    const RescueJob& J = tab.job[job_of_tile(tab, tile)];
+    const int n = list_rows(J), t0 = (tile - J.first_tile) * kListTile;
+    if (t0 >= n) return;
+    const int i = t0 + (int)threadIdx.x;
+    const bool failed = i < n && J.crc_ok[i] == 0;
+    int at[1];
+    compact_core::block_rank<1, kListTile>(failed, at);
+    if (failed) tab.list[tab.work[tile] + at[0]] = i;
+    if (i < n) J.rank[i] = failed ? -1 : 0;
+}
+// LDS per workgroup: the staged block (byte rows 7168 B of soft classes, frames 3584 B of bits, soft values 27648 B) + 2376 (decoded
+// halves) + 1024 (backward CRC table).  Every array but the table is a column per lane, so the rounds of the persistent loop need no
+// barrier between them.
+template <int FRONT>
+__global__ __launch_bounds__(kLanes) void k_list_rescue(const RescueTable tab) {
+    typedef uint32_t Staged[FRONT == kFrontSoft ? tetra_soft::kSoftWords : (FRONT == kFrontFrames ? kSeqWords : kClsWords + 1)][kLanes];
+    __shared__ Staged in;
+    __shared__ OutW outw;
+    __shared__ uint32_t crc_inv[256];
+    const int lane = threadIdx.x;
+    const int total = *tab.total;
+    if (total == 0) return;
+    load_crc_inv(crc_inv, lane);
+    __syncthreads();
+    auto staged = [&](int w) { return in[w][lane]; };
+    auto half = [&](int h) { return outw[h][lane]; };
+    for (int v = (int)blockIdx.x;; v += (int)gridDim.x) {
+        // group v of 64 failed rows, counted job after job (all of this is workgroup-uniform)
+        int j = 0, u = v, first = 0, cnt = 0;
+        for (; j < tab.n; ++j) {
+            first = tab.work[tab.job[j].first_tile];
+            cnt = (j + 1 < tab.n ? tab.work[tab.job[j + 1].first_tile] : total) - first;
+            const int groups = (cnt + kLanes - 1) / kLanes;
+            if (u < groups) break;
+            u -= groups;
+        }
+        if (j >= tab.n) return;
+        const RescueJob& a = tab.job[j];
+        const int blk0 = u * kLanes;
+        const bool live = blk0 + lane < cnt;
+        const int row = tab.list[first + (live ? blk0 + lane : blk0)];     // (a lane without a row repeats the first one's work and writes nothing)
+        LaneIo io{ outw, crc_inv, const_cast<uint32_t*>(a.dec) + (size_t)(row / kLanes) * a.dec_pairs * kLanes + row % kLanes, lane };
+        int rank;
+        uint32_t biterr = 0;
+        if constexpr (FRONT == kFrontBytes) {
+            // the byte route of k_lmac_decode, the lane reading its own row: classes of plain bits are the packed route's bits
+            const uint32_t* rowp = reinterpret_cast<const uint32_t*>(a.type5 + (size_t)row * a.in_stride);
+            uint32_t lfsr = a.fixed_init ? kScrambInitSb1 : a.scramb_init[a.init_index ? a.init_index[row] : row];
+            for (int c0 = 0; c0 < a.type345 >> 2; c0 += kChunkDwords)
+                lfsr = descramble_chunk(a.type345 - 4 * c0, lfsr, [&](int d) { return rowp[c0 + d]; }, [&](int w, uint32_t word) { in[c0 / 4 + w][lane] = word; });
+            rank = tetra_list::rescue_hard<false>(a.type345, a.type2, a.a, tab.T, staged, io, half);
+            if (a.counts && rank > 0) biterr = bit_errors_hard<false>(a.type345, a.type2, a.a, half, staged);
+        } else {
+            const int f = min(max(a.row_frame[row], 0), tab.src.n_frames - 1);
+            const uint32_t code = a.frame_scramb ? a.frame_scramb[f] : kScrambInitSb1;
+            if constexpr (FRONT == kFrontFrames) {
+                uint32_t fw[kFrameWords], xb[kSeqWords];
+                const uint4* src = reinterpret_cast<const uint4*>(tab.src.frames + (size_t)f * kFrameWords);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const uint4 w4 = src[g];
+                    fw[4 * g] = w4.x; fw[4 * g + 1] = w4.y; fw[4 * g + 2] = w4.z; fw[4 * g + 3] = w4.w;
+                }
+                frame_block(a.layout, fw, tab.src.frame_type[f], xb);
+                descramble_words(a.type345, code, xb, seq_rows(tab.seq_tab), [&](int w, uint32_t word) { in[w][lane] = word; });
+                rank = tetra_list::rescue_hard<true>(a.type345, a.type2, a.a, tab.T, staged, io, half);
+                if (a.counts && rank > 0) biterr = bit_errors_hard<true>(a.type345, a.type2, a.a, half, staged);
+            } else {
+                const uint32_t* chan = tab.ring + (size_t)(f / tab.src.frames_per_channel) * tab.ring_words;
+                uint32_t seq[kSeqWords] = {};
+                lane_sequence(a.type345, code, seq_rows(tab.seq_tab), [&](int w, uint32_t word) { seq[w] = word; });
+                tetra_soft::stage_block(a.layout, tab.src.bitnum[f], tab.src.frame_type[f], [&](uint32_t w) { return chan[w]; }, 4u * tab.ring_words - 1u, seq,
+                                        [&](int g, uint32_t word) { in[g][lane] = word; });
+                rank = tetra_list::rescue_soft(a.type345, a.type2, a.a, tab.T, staged, io, half);
+                if (a.counts && rank > 0) biterr = tetra_soft::bit_errors_soft(a.type345, a.type2, a.a, half, staged);
+            }
+        }
+        if (live) {
+            a.rank[row] = rank;
+            if (rank > 0) {
+                uint32_t* dst = reinterpret_cast<uint32_t*>(a.out + (size_t)row * a.out_stride);
+                for (int d = 0; d < a.type2 >> 2; ++d) dst[d] = spread4(((uint32_t)outw[d >> 2][lane] >> (4 * (d & 3))) & 0xfu);
+                a.crc_ok[row] = 1;
+                if (a.labels) a.labels[row].crc_ok = 1;
+                if (a.counts) a.counts[row] = biterr;
+            }
+        }
+    }
+}
+
 // One value per device, built on first use under a lock (safe for concurrent handles: one per GPU in a multi-GPU bank) and kept for the
 // life of the process.  make(dev) returns the value, or a null one if it cannot be set up: get() then returns null, and tries again
 // next time.
@@ -455,6 +630,42 @@ struct ScratchLease {
         return !give_back() || launch != hipSuccess ? TETRA_ERR_HIP : TETRA_OK;
     }
 };
+
+// The list launches behind a decode launch on stream s.  tab: the jobs with ranks (n of them, everything but first_tile) and what they
+// share; the compaction's own words come from the caller's workspace `ws` if it gave one (the chain's handle), else from the keeping pool,
+// handed back in stream order behind the rescue kernel.
+size_t list_words(long long tiles, long long rows) { return (size_t)tiles + 1 + (size_t)rows; }
+int launch_list(int front, RescueTable& tab, hipStream_t s, void* ws, size_t ws_bytes) {
+    long long tiles = 0, rows = 0, groups = 0;
+    for (int k = 0; k < tab.n; ++k) {
+        tab.job[k].first_tile = (int)tiles;
+        tiles += (tab.job[k].n + kListTile - 1) / kListTile;
+        rows += tab.job[k].n;
+        groups += (tab.job[k].n + kLanes - 1) / kLanes;
+    }
+    if (tab.n == 0) return TETRA_OK;
+    if (tiles > 0x7fffffffLL) return TETRA_ERR_SIZE;
+    tab.tiles = (int)tiles;
+    ScratchLease w;
+    if (const int err = w.take(sizeof(int) * list_words(tiles, rows), ws, ws_bytes, s)) return err;
+    tab.work = reinterpret_cast<int*>(w.p);
+    tab.total = tab.work + tab.tiles;
+    tab.list = tab.total + 1;
+    const dim3 grid((unsigned)(groups < kRescueGroups ? groups : kRescueGroups));
+    hipLaunchKernelGGL(k_list_count, dim3(tab.tiles), dim3(kListTile), 0, s, tab);
+    hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(compact_core::kScanThreads), 0, s, tab);
+    hipLaunchKernelGGL(k_list_fill, dim3(tab.tiles), dim3(kListTile), 0, s, tab);
+    if (front == kFrontBytes) hipLaunchKernelGGL(k_list_rescue<kFrontBytes>, grid, dim3(kLanes), 0, s, tab);
+    else if (front == kFrontFrames) hipLaunchKernelGGL(k_list_rescue<kFrontFrames>, grid, dim3(kLanes), 0, s, tab);
+    else hipLaunchKernelGGL(k_list_rescue<kFrontSoft>, grid, dim3(kLanes), 0, s, tab);
+    return w.launched();
+}
+// a rank array and its T (tetra_list.h): none, or a 4-byte aligned array with T in 1..8
+int check_list(const void* d_rank, int max_candidates) {
+    if (!d_rank) return TETRA_OK;
+    if (max_candidates < 1 || max_candidates > tetra_list::kMaxCandidates) return TETRA_ERR_ARG;
+    return ((uintptr_t)d_rank & 3) ? TETRA_ERR_ALIGN : TETRA_OK;
+}
 
 // TPSAP_T_BBK: the reference only descrambles (tetra_lower_mac.c:231-236); 30 bits per block, one lane per block.
 // RM (tetra_lmac_decode_aach_rm3014_device): the descrambled bytes are also gathered into the 30-bit word (a byte other than 0 is a 1),
@@ -650,9 +861,30 @@ int tetra_lmac_decode_counted_device(int type, const uint8_t* d_type5, int n_blo
                                                    d_crc_ok, nullptr, hip_stream);
 }
 
+static int decode_counted(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                          const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                          int32_t* d_crc_ok, uint32_t* d_biterr, int max_candidates, int32_t* d_rank, void* hip_stream);
+
 int tetra_lmac_decode_counted_biterr_device(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
                                             const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
                                             int32_t* d_crc_ok, uint32_t* d_biterr, void* hip_stream) {
+    return decode_counted(type, d_type5, n_blocks, d_n_blocks, in_stride, d_scramb_init, d_init_index, d_type2, out_stride, d_crc_ok, d_biterr, 0, nullptr,
+                          hip_stream);
+}
+
+int tetra_lmac_decode_counted_list_device(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                                          const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                                          int32_t* d_crc_ok, int max_candidates, int32_t* d_rank, void* hip_stream) {
+    return decode_counted(type, d_type5, n_blocks, d_n_blocks, in_stride, d_scramb_init, d_init_index, d_type2, out_stride, d_crc_ok, nullptr,
+                          max_candidates, d_rank, hip_stream);
+}
+
+// every byte-row entry point; d_rank NULL: the launches they always made, nothing else
+static int decode_counted(int type, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                          const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                          int32_t* d_crc_ok, uint32_t* d_biterr, int max_candidates, int32_t* d_rank, void* hip_stream) {
+    if (d_rank && type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;              // the AACH has no CRC to aim at
+    if (const int bad = check_list(d_rank, max_candidates)) return bad;
     const int rc = check_args(type, d_type5, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_crc_ok, true);
     if (rc != TETRA_OK) return rc;
     if (d_biterr && type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;           // the AACH is not convolutionally coded: tetra_aach.h has its distance
@@ -681,21 +913,35 @@ int tetra_lmac_decode_counted_biterr_device(int type, const uint8_t* d_type5, in
             hipLaunchKernelGGL(k_lmac_decode<false>, dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init,
                                type == TETRA_TPSAP_T_SB1 ? 1 : 0, p.type345, p.type2, p.type1, p.a, d_type2, out_stride, d_crc_ok,
                                scratch.p, dec_pairs, d_n_blocks, d_init_index, seq_or_bytes);
-        return scratch.launched();
+        int list_rc = TETRA_OK;
+        if (d_rank) {               // behind the decode launch, in front of the scratch's hand-back
+            RescueTable rt = {};
+            RescueJob& a = rt.job[rt.n++];
+            a.n_dev = d_n_blocks; a.n = n_blocks; a.crc_ok = d_crc_ok; a.out = d_type2; a.out_stride = out_stride; a.counts = d_biterr; a.rank = d_rank;
+            a.dec = scratch.p; a.dec_pairs = dec_pairs; a.type345 = p.type345; a.type2 = p.type2; a.a = p.a;
+            a.type5 = d_type5; a.in_stride = in_stride; a.fixed_init = type == TETRA_TPSAP_T_SB1 ? 1 : 0; a.scramb_init = d_scramb_init; a.init_index = d_init_index;
+            rt.T = max_candidates;
+            list_rc = launch_list(kFrontBytes, rt, s, nullptr, 0);
+        }
+        const int launch_rc = scratch.launched();
+        return list_rc != TETRA_OK ? list_rc : launch_rc;
     }
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
 // tetra_lmac_decode_frames_device, and with `soft` lmac_impl::decode_frames_soft: the same job table, the soft kernel
 // d_biterr: NULL, or per job where its counts go (tetra_lmac_decode_frames_biterr_device)
+// d_rank: NULL, or per job where its ranks go (tetra_lmac_decode_frames_list_device); max_candidates: their T
 static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const lmac_impl::SoftRing* soft,
-                         uint32_t* const* d_biterr, void* hip_stream) {
+                         uint32_t* const* d_biterr, void* hip_stream, int max_candidates = 0, int32_t* const* d_rank = nullptr,
+                         lmac_impl::ListWork list_work = lmac_impl::ListWork()) {
     if (!src || !jobs || n_jobs < 0 || n_jobs > TETRA_LMAC_MAX_JOBS) return TETRA_ERR_ARG;
     if (n_jobs == 0) return TETRA_OK;
     if (!src->d_frames || !src->d_frame_type || src->n_frames < 0) return TETRA_ERR_ARG;
     if ((uintptr_t)src->d_frames & 15) return TETRA_ERR_ALIGN;
     JobTable tab = {};
     BiterrTable counts = {};
+    int32_t* ranks[TETRA_LMAC_MAX_JOBS] = {};
     bool any_counts = false;
     if (src->n_frames == 0) return TETRA_OK;              // no frames: no row can exist
     tab.src = DevFrames{ src->d_frames, src->d_frame_type, src->d_frame_bitnum, src->d_time_rx, src->d_time, src->frames_per_channel, src->n_frames };
@@ -710,6 +956,9 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         uint32_t* const job_counts = d_biterr ? d_biterr[i] : nullptr;
         if (job_counts && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;       // the AACH is not convolutionally coded
         if ((uintptr_t)job_counts & 3) return TETRA_ERR_ALIGN;
+        int32_t* const job_rank = d_rank ? d_rank[i] : nullptr;
+        if (job_rank && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;         // the AACH has no CRC to aim at
+        if (const int bad = check_list(job_rank, max_candidates)) return bad;
         if (j.max_rows == 0) continue;
         if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok) return TETRA_ERR_ARG;
         if (j.type != TETRA_TPSAP_T_SB1 && !j.d_frame_scramb) return TETRA_ERR_ARG;
@@ -723,6 +972,7 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         if (j.out_stride < (bbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
         if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
         counts.out[n] = job_counts;
+        ranks[n] = job_rank;
         any_counts = any_counts || job_counts;
         DevJob& d = tab.job[n++];
         d.row_frame = j.d_row_frame;
@@ -768,7 +1018,27 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
     } else {
         hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, nullptr);
     }
-    return scratch.launched();
+    // the jobs with ranks, all in one set of list launches: behind the decode launch, in front of the scratch's hand-back
+    RescueTable rt = {};
+    for (int k = 0; k < n; ++k) {
+        if (!ranks[k]) continue;
+        const DevJob& d = tab.job[k];
+        RescueJob& a = rt.job[rt.n++];
+        a.n_dev = d.n_rows_dev; a.n = d.n_rows; a.crc_ok = d.crc_ok; a.out = d.out; a.out_stride = d.out_stride; a.labels = d.labels;
+        a.counts = counts.out[k]; a.rank = ranks[k];
+        a.dec = scratch.p + d.scratch_base; a.dec_pairs = d.dec_pairs; a.type345 = d.type345; a.type2 = d.type2; a.a = d.a;
+        a.row_frame = d.row_frame; a.frame_scramb = d.frame_scramb; a.layout = d.layout;
+    }
+    rt.T = max_candidates; rt.src = tab.src; rt.seq_tab = seq;
+    if (soft) { rt.ring = reinterpret_cast<const uint32_t*>(soft->d_ring); rt.ring_words = soft->size / 4u; }
+    const int list_rc = launch_list(soft ? kFrontSoft : kFrontFrames, rt, s, list_work.d_work, list_work.bytes);
+    const int launch_rc = scratch.launched();
+    return list_rc != TETRA_OK ? list_rc : launch_rc;
+}
+
+int tetra_lmac_decode_frames_list_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, int max_candidates,
+                                         int32_t* const* d_rank, void* hip_stream) {
+    return decode_frames(src, jobs, n_jobs, nullptr, nullptr, hip_stream, max_candidates, d_rank);
 }
 
 int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
@@ -866,10 +1136,24 @@ int tetra_lmac_decode_batch(int type, const uint8_t* type5, int n_blocks, int in
     return tetra_lmac_decode_batch_biterr(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, nullptr, device);
 }
 
+static int decode_batch(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                        uint8_t* type2, int out_stride, int32_t* crc_ok, uint32_t* biterr, int max_candidates, int32_t* rank, int device);
+
 int tetra_lmac_decode_batch_biterr(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
                                    uint8_t* type2, int out_stride, int32_t* crc_ok, uint32_t* biterr, int device) {
+    return decode_batch(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, biterr, 0, nullptr, device);
+}
+
+int tetra_lmac_decode_batch_list(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                                 uint8_t* type2, int out_stride, int32_t* crc_ok, int max_candidates, int32_t* rank, int device) {
+    return decode_batch(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, nullptr, max_candidates, rank, device);
+}
+
+static int decode_batch(int type, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                        uint8_t* type2, int out_stride, int32_t* crc_ok, uint32_t* biterr, int max_candidates, int32_t* rank, int device) {
     int rc = check_args(type, type5, n_blocks, in_stride, scramb_init, type2, out_stride, crc_ok, false);
-    if (rc == TETRA_OK && biterr && type == TETRA_TPSAP_T_BBK) rc = TETRA_ERR_ARG;
+    if (rc == TETRA_OK && (biterr || rank) && type == TETRA_TPSAP_T_BBK) rc = TETRA_ERR_ARG;
+    if (rc == TETRA_OK && rank && (max_candidates < 1 || max_candidates > tetra_list::kMaxCandidates)) rc = TETRA_ERR_ARG;
     if (rc != TETRA_OK || n_blocks == 0) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
@@ -879,7 +1163,9 @@ int tetra_lmac_decode_batch_biterr(int type, const uint8_t* type5, int n_blocks,
     DevMem<uint32_t> d_init;
     DevMem<int32_t> d_ok;
     DevMem<uint32_t> d_biterr;
+    DevMem<int32_t> d_rank;
     if (biterr && d_biterr.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess) return TETRA_ERR_NOMEM;
+    if (rank && d_rank.reserve(sizeof(int32_t) * n_blocks) != hipSuccess) return TETRA_ERR_NOMEM;
     const size_t in_bytes = (size_t)n_blocks * in_stride, out_bytes = (size_t)n_blocks * out_stride;
     if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_ok.reserve(sizeof(int32_t) * n_blocks) != hipSuccess)
         return TETRA_ERR_NOMEM;
@@ -888,8 +1174,8 @@ int tetra_lmac_decode_batch_biterr(int type, const uint8_t* type5, int n_blocks,
         if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
     }
     if (hipMemcpy(d_in, type5, in_bytes, hipMemcpyHostToDevice) != hipSuccess) return TETRA_ERR_HIP;
-    rc = tetra_lmac_decode_counted_biterr_device(type, d_in, n_blocks, nullptr, in_stride, d_init, nullptr, d_out, out_stride, d_ok,
-                                                 biterr ? (uint32_t*)d_biterr : nullptr, nullptr);
+    rc = decode_counted(type, d_in, n_blocks, nullptr, in_stride, d_init, nullptr, d_out, out_stride, d_ok, biterr ? (uint32_t*)d_biterr : nullptr,
+                        max_candidates, rank ? (int32_t*)d_rank : nullptr, nullptr);
     if (rc != TETRA_OK) return rc;
     if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
     // only the type2_bits columns: the caller's row padding is left alone
@@ -900,15 +1186,31 @@ int tetra_lmac_decode_batch_biterr(int type, const uint8_t* type5, int n_blocks,
         return TETRA_ERR_HIP;
     if (hipMemcpy(crc_ok, d_ok, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    if (rank && hipMemcpy(rank, d_rank, sizeof(int32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
 }
 
 }  // extern "C"
 
 int lmac_impl::decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream,
-                                  uint32_t* const* d_biterr) {
+                                  uint32_t* const* d_biterr, int max_candidates, int32_t* const* d_rank, ListWork list_work) {
     // a ring of whole aligned words, a power of two in size; the frames' bit numbers and channels
     if (!ring.d_ring || ring.size < 4 || (ring.size & (ring.size - 1)) || ((uintptr_t)ring.d_ring & 3)) return TETRA_ERR_ARG;
     if (src && (!src->d_frame_bitnum || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
-    return decode_frames(src, jobs, n_jobs, &ring, d_biterr, hip_stream);
+    return decode_frames(src, jobs, n_jobs, &ring, d_biterr, hip_stream, max_candidates, d_rank, list_work);
+}
+
+int lmac_impl::decode_frames_list(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream, uint32_t* const* d_biterr,
+                                  int max_candidates, int32_t* const* d_rank, ListWork list_work) {
+    return decode_frames(src, jobs, n_jobs, nullptr, d_biterr, hip_stream, max_candidates, d_rank, list_work);
+}
+
+size_t lmac_impl::list_work_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {
+    long long tiles = 0, rows = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        if (jobs[i].max_rows <= 0 || (jobs[i].type & 0xff) == TETRA_TPSAP_T_BBK) continue;
+        tiles += (jobs[i].max_rows + kListTile - 1) / kListTile;
+        rows += jobs[i].max_rows;
+    }
+    return sizeof(int) * list_words(tiles, rows);
 }

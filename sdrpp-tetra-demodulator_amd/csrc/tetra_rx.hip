@@ -27,6 +27,7 @@
 
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
+#include "../../include/ext/tetra_list.h"
 #include "../../include/ext/tetra_sync_tol.h"
 #include "../../include/tetra_rx.h"
 #include "lmac_impl.hpp"
@@ -154,6 +155,9 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     src.d_workspace = h->lmac_ws;
     src.workspace_bytes = h->lmac_ws.bytes();
     const lmac_impl::SoftRing ring = { h->soft_ring, h->soft_R };
+    lmac_impl::ListWork list_work;              // the list launches' compaction words (one launch at a time on this stream)
+    list_work.d_work = h->list_ws;
+    list_work.bytes = h->list_ws.bytes();
     auto job_of = [&](int k, bool labels) {
         const KindInfo& ki = kKinds[k];
         const KindBufs& r = h->res[b][k];
@@ -174,8 +178,14 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         const KindBufs& r = h->res[b][TETRA_RX_KIND_SB1];
         const tetra_lmac_job_t j = job_of(TETRA_RX_KIND_SB1, false);
         uint32_t* const counts = h->biterr ? r.biterr.get() : nullptr;          // (without the flag: the launches as they were)
-        TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr)
-                          : tetra_lmac_decode_frames_biterr_device(&src, &j, 1, h->biterr ? &counts : nullptr, s));
+        int32_t* const rank = r.rank.get();
+        if (h->list) {      // the rescue in front of the tracker: a rescued SYNC PDU sets code and clock
+            TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr, h->list_T, &rank, list_work)
+                              : lmac_impl::decode_frames_list(&src, &j, 1, s, h->biterr ? &counts : nullptr, h->list_T, &rank, list_work));
+        } else {
+            TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr)
+                              : tetra_lmac_decode_frames_biterr_device(&src, &j, 1, h->biterr ? &counts : nullptr, s));
+        }
         TETRA_TRY(tetra_lmac_track_sync_lists_device(r.t2, kKinds[TETRA_RX_KIND_SB1].out_stride, r.ok, h->ft, h->nf,
                                                  h->chan_first + (size_t)TETRA_LIST_SYNC * h->C, h->C, h->F, h->cell, h->row_scramb, h->row_time_rx,
                                                  h->row_time, h->fb, reinterpret_cast<tetra_lmac_label_t*>(r.blocks.get()), s));
@@ -183,21 +193,29 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     HIP_TRY(h, hipEventRecord(h->ev_stage[2], s));
     tetra_lmac_job_t jobs[TETRA_RX_N_KINDS];
     uint32_t* counts[TETRA_RX_N_KINDS];          // per job where its bit-error counts go (NULL: the AACH)
+    int32_t* ranks[TETRA_RX_N_KINDS];            // ... and its ranks (TETRA_RX_FLAG_LIST; NULL: the AACH)
     int nj = 0;
     for (int k : kJobOrder)
         if ((h->kinds & (1 << k)) && !(h->soft && k == TETRA_RX_KIND_BBK)) {
             counts[nj] = h->res[b][k].biterr;
+            ranks[nj] = h->res[b][k].rank;
             jobs[nj++] = job_of(k, true);
         }
     if (h->soft) {      // the coded kinds from the ring; the AACH from the packed frames as ever, a launch of its own
-        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s, h->biterr ? counts : nullptr));
+        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s, h->biterr ? counts : nullptr, h->list_T, h->list ? ranks : nullptr, list_work));
         nj = 0;
         if (h->kinds & (1 << TETRA_RX_KIND_BBK)) {
             counts[nj] = nullptr;
+            ranks[nj] = nullptr;
             jobs[nj++] = job_of(TETRA_RX_KIND_BBK, true);
         }
     }
-    TETRA_TRY(tetra_lmac_decode_frames_biterr_device(&src, jobs, nj, h->biterr ? counts : nullptr, s));
+    // (the rescue of these kinds runs inside the call, behind its decode launch: in front of the link figures and of the tail's event)
+    if (h->list) {
+        TETRA_TRY(lmac_impl::decode_frames_list(&src, jobs, nj, s, h->biterr ? counts : nullptr, h->list_T, ranks, list_work));
+    } else {
+        TETRA_TRY(tetra_lmac_decode_frames_biterr_device(&src, jobs, nj, h->biterr ? counts : nullptr, s));
+    }
     if (h->biterr) {
         LinkTable tab = {};
         for (int k = 0; k < TETRA_RX_N_KINDS; ++k)
@@ -232,7 +250,7 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR | TETRA_RX_FLAG_SYNC_TOLERANT)))
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR | TETRA_RX_FLAG_SYNC_TOLERANT | TETRA_RX_FLAG_LIST)))
         return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
@@ -243,6 +261,8 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     h->aach_rm = (cfg->flags & TETRA_RX_FLAG_AACH_RM3014) != 0;
     h->soft = (cfg->flags & TETRA_RX_FLAG_SOFT) != 0;
     h->biterr = (cfg->flags & TETRA_RX_FLAG_BITERR) != 0;
+    h->list = (cfg->flags & TETRA_RX_FLAG_LIST) != 0;
+    h->list_T = TETRA_LIST_DEFAULT_CANDIDATES;
     TETRA_TRY(tetra_demod_create(&cfg->demod, h->dem.put()));
     h->C = cfg->demod.n_channels;
     int dev = cfg->demod.device;
@@ -273,7 +293,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
             if (!(h->kinds & (1 << k))) continue;
             KindBufs& r = h->res[b][k];
             ok = dalloc(r.t2, n * kKinds[k].out_stride) && dalloc(r.ok, n) && dalloc(r.blocks, n) &&
-                 (!h->biterr || k == TETRA_RX_KIND_BBK || dalloc(r.biterr, n));
+                 (!h->biterr || k == TETRA_RX_KIND_BBK || dalloc(r.biterr, n)) && (!h->list || k == TETRA_RX_KIND_BBK || dalloc(r.rank, n));
             r.row_frame = h->lists[b] + (size_t)kKinds[k].list * n;
             r.n_rows = h->counts[b] + kKinds[k].list;
         }
@@ -298,6 +318,10 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
         sb1.type = TETRA_TPSAP_T_SB1; sb1.blk_num = 1; sb1.max_rows = h->rows;
         const size_t sb1_bytes = tetra_lmac_decode_frames_workspace_bytes(&sb1, 1);
         ok = h->lmac_ws.reserve(sb1_bytes > ws_bytes ? sb1_bytes : ws_bytes) == hipSuccess;
+        if (ok && h->list) {
+            const size_t a = lmac_impl::list_work_bytes(jobs, nj), b1 = lmac_impl::list_work_bytes(&sb1, 1);
+            ok = h->list_ws.reserve(a > b1 ? a : b1) == hipSuccess;
+        }
     }
     if (!ok) return TETRA_ERR_NOMEM;
     TETRA_TRY(zero_results(h.get()));
@@ -499,6 +523,49 @@ int tetra_rx_biterr_device(tetra_rx_t* h, int which, int kind, const uint32_t** 
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
     *d_biterr = h->res[b][kind].biterr;
+    return TETRA_OK;
+}
+
+// the chain's share of tetra_list.h
+static bool ranks_kind(const tetra_rx* h, int kind) { return h->list && kind != TETRA_RX_KIND_BBK && (h->kinds & (1 << kind)); }
+
+int tetra_rx_set_list_candidates(tetra_rx_t* h, int max_candidates) {
+    if (!h) return TETRA_ERR_ARG;
+    if (!h->list) return TETRA_ERR_UNSUPPORTED;
+    if (max_candidates < 1 || max_candidates > TETRA_LIST_MAX_CANDIDATES) return TETRA_ERR_ARG;
+    h->list_T = max_candidates;
+    return TETRA_OK;
+}
+
+int tetra_rx_fetch_list_rank(tetra_rx_t* h, int which, int kind, int32_t* out, int capacity, int* n_rows) {
+    if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
+    if (!ranks_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
+    *n_rows = 0;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
+    const KindBufs& r = h->res[b][kind];
+    int32_t n = 0;
+    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
+    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
+    *n_rows = n;
+    if (n > capacity) return out ? TETRA_ERR_SIZE : TETRA_OK;
+    if (n == 0 || !out) return TETRA_OK;
+    HIP_TRY(h, hipMemcpy(out, r.rank, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return TETRA_OK;
+}
+
+int tetra_rx_list_rank_device(tetra_rx_t* h, int which, int kind, const int32_t** d_rank, void* hip_stream) {
+    if (!h || !d_rank || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1) return TETRA_ERR_ARG;
+    if (!ranks_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
+    *d_rank = h->res[b][kind].rank;
     return TETRA_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ext/tetra_biterr.h"
+#include "ext/tetra_list.h"
 #include "ext/tetra_sync_tol.h"
 #include "tetra_rx.h"
 #include "tetra_rx_out.h"
@@ -135,6 +136,17 @@ public:
     int links(std::vector<tetra_rx_link_t>& out) {
         out.resize((size_t)channels_);
         return tetra_rx_get_link(h_, 0, channels_, out.data());
+    }
+    // TETRA_RX_FLAG_LIST (tetra_list.h): how many next-best paths (1..8) a CRC-failed block is decoded along from the next call on ...
+    int setListCandidates(int maxCandidates) { return tetra_rx_set_list_candidates(h_, maxCandidates); }
+    // ... and the rank of a coded kind's rows, in fetch()'s order: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k,
+    // -1 = failed and not rescued
+    int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) {
+        int n = 0;
+        const int rc = tetra_rx_fetch_list_rank(h_, which, kind, nullptr, 0, &n);
+        if (rc != TETRA_OK) return rc;
+        out.resize((size_t)n);
+        return n ? tetra_rx_fetch_list_rank(h_, which, kind, out.data(), n, &n) : TETRA_OK;
     }
     int syncStates(std::vector<tetra_bsync_state_t>& out) {
         out.resize((size_t)channels_);
@@ -276,6 +288,20 @@ public:
         std::vector<uint32_t> part;
         for (auto& s : shards_) {
             const int rc = s->bank.fetchBitErrors(kind, part, which);
+            if (rc != TETRA_OK) return rc;
+            out.insert(out.end(), part.begin(), part.end());
+        }
+        return TETRA_OK;
+    }
+    int setListCandidates(int maxCandidates) {
+        for (auto& s : shards_) { const int rc = s->bank.setListCandidates(maxCandidates); if (rc != TETRA_OK) return rc; }
+        return TETRA_OK;
+    }
+    int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) {
+        out.clear();
+        std::vector<int32_t> part;
+        for (auto& s : shards_) {
+            const int rc = s->bank.fetchListRank(kind, part, which);
             if (rc != TETRA_OK) return rc;
             out.insert(out.end(), part.begin(), part.end());
         }

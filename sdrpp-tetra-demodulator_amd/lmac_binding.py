@@ -62,13 +62,20 @@ BITERR_ABI = {
     "tetra_lmac_decode_batch_biterr": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, vp, i32]),
     "tetra_lmac_decode_frames_biterr_device": (i32, [P(Frames), P(Job), i32, P(vp), vp]),
 }
-LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
+# include/ext/tetra_list.h: the lower MAC's share
+LIST_ABI = {
+    "tetra_lmac_decode_counted_list_device": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
+    "tetra_lmac_decode_batch_list": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]),
+    "tetra_lmac_decode_frames_list_device": (i32, [P(Frames), P(Job), i32, i32, P(vp), vp]),
+}
+LIST_MAX_CANDIDATES, LIST_DEFAULT_CANDIDATES = 8, 4            # TETRA_LIST_MAX_CANDIDATES, TETRA_LIST_DEFAULT_CANDIDATES
+LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI}, optional=AACH_EXPORTS + BITERR_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI}, optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS)
 
 
 def force_byte_route(on):
@@ -140,6 +147,25 @@ def decode_counted_biterr_device(blk_type, d_type5, capacity, d_n_blocks, in_str
          ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), ptr(d_biterr), stream_ptr(stream))
 
 
+def decode_batch_list(blk_type, type5, scramb=None, max_candidates=LIST_DEFAULT_CANDIDATES, device=-1):
+    """tetra_lmac_decode_batch_list (include/ext/tetra_list.h): decode_batch plus the CRC-aided rescue of the failed rows
+    -> (type2, crc_ok, rank int32 [n]: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k, -1 = not rescued)."""
+    rows = np.ascontiguousarray(type5, np.uint8)
+    n, in_stride = rows.shape
+    ost = out_stride_for(blk_type)
+    out, ok, rank = np.zeros((n, ost), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
+    call(_lib().tetra_lmac_decode_batch_list, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), int(max_candidates), ptr(rank), device)
+    return out, ok, rank
+
+
+def decode_counted_list_device(blk_type, d_type5, capacity, d_n_blocks, in_stride, d_scramb, d_init_index, d_type2, out_stride, d_crc_ok,
+                               max_candidates, d_rank, stream=None):
+    """tetra_lmac_decode_counted_list_device: decode_counted_device plus max_candidates and d_rank (int32 tensor [capacity], or None)."""
+    call(_lib().tetra_lmac_decode_counted_list_device, int(blk_type), ptr(d_type5), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
+         ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), int(max_candidates), ptr(d_rank), stream_ptr(stream))
+
+
 def track_scramb_device(d_sb1_type2, type2_stride, d_crc_ok, d_valid, n_channels, frames_per_channel, d_chan_scramb, d_row_scramb,
                         stream=None):
     call(_lib().tetra_lmac_track_scramb_device, ptr(d_sb1_type2), int(type2_stride), ptr(d_crc_ok), ptr(d_valid), int(n_channels),
@@ -184,6 +210,17 @@ def decode_frames_biterr_device(d_frames, d_frame_type, jobs, frames_per_channel
                  ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
     arr = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
     call(_lib().tetra_lmac_decode_frames_biterr_device, C.byref(src), _job_array(jobs), len(jobs), arr if counted else None, stream_ptr(stream))
+
+
+def decode_frames_list_device(d_frames, d_frame_type, jobs, max_candidates=LIST_DEFAULT_CANDIDATES, frames_per_channel=0, d_frame_bitnum=None,
+                              d_time_rx=None, d_time=None, stream=None, d_workspace=None, ranked=True):
+    """tetra_lmac_decode_frames_list_device: decode_frames_device whose jobs may carry `rank` (int32 tensor [max_rows], or None / absent:
+    the job is not rescued).  ranked=False hands in no array at all."""
+    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
+                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    arr = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
+    call(_lib().tetra_lmac_decode_frames_list_device, C.byref(src), _job_array(jobs), len(jobs), int(max_candidates), arr if ranked else None,
+         stream_ptr(stream))
 
 
 def track_sync_lists_device(d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync, n_channels, frames_per_channel,

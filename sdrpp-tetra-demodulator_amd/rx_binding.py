@@ -15,6 +15,7 @@ FLAG_ONE_STREAM = 1
 FLAG_AACH_RM3014 = 2          # TETRA_RX_FLAG_AACH_RM3014
 FLAG_SOFT = 8                 # TETRA_RX_FLAG_SOFT: the coded kinds decoded from soft values (4 is no flag)
 FLAG_BITERR = 32              # TETRA_RX_FLAG_BITERR: channel bit-error counts per coded block, link figures per channel (tetra_biterr.h)
+FLAG_LIST = 512               # TETRA_RX_FLAG_LIST: CRC-aided list decoding of the CRC-failed coded blocks (ext/tetra_list.h)
 FLAG_SYNC_TOLERANT = 128      # TETRA_RX_FLAG_SYNC_TOLERANT: the synchroniser's tolerant lock with {3, 5, 16} (ext/tetra_sync_tol.h)
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
@@ -87,6 +88,12 @@ SYNC_TOL_ABI = {
     "tetra_rx_set_sync_tolerance": (i32, [vp, P(BsyncTolerance)]),
     "tetra_rx_get_sync_misses": (i32, [vp, i32, i32, vp]),
 }
+# include/ext/tetra_list.h (CRC-aided list decoding): the chain's share
+LIST_ABI = {
+    "tetra_rx_set_list_candidates": (i32, [vp, i32]),
+    "tetra_rx_fetch_list_rank": (i32, [vp, i32, i32, vp, i32, P(i32)]),
+    "tetra_rx_list_rank_device": (i32, [vp, i32, i32, P(vp), vp]),
+}
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 
@@ -94,8 +101,8 @@ RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES),
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
-    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI},
-                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI))
+    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI},
+                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI))
 
 
 def type1_bits(kind):
@@ -196,6 +203,27 @@ class RxChain:
         """tetra_rx_biterr_device -> the raw device address of the kind's counts (uint32 per row of rows_device)."""
         d = C.c_void_p()
         call(self._lib.tetra_rx_biterr_device, self._h, which, kind, C.byref(d), stream_ptr(stream))
+        return d.value
+
+    def set_list_candidates(self, max_candidates):
+        """tetra_rx_set_list_candidates: how many next-best paths (1..8) the calls that follow try on a CRC-failed block.  Needs a handle
+        created with FLAG_LIST."""
+        call(self._lib.tetra_rx_set_list_candidates, self._h, int(max_candidates))
+
+    def fetch_list_rank(self, kind, which=0):
+        """tetra_rx_fetch_list_rank: int32 [n] of a coded kind's rows, in fetch(kind)'s order -- 0: the decoder's own path passed the CRC,
+        k >= 1: rescued by candidate k, -1: failed and not rescued.  Needs a handle created with FLAG_LIST."""
+        n = C.c_int(0)
+        call(self._lib.tetra_rx_fetch_list_rank, self._h, which, kind, None, 0, C.byref(n))
+        v = np.zeros(max(n.value, 1), np.int32)
+        got = C.c_int(0)
+        call(self._lib.tetra_rx_fetch_list_rank, self._h, which, kind, ptr(v), max(n.value, 1), C.byref(got))
+        return v[:got.value]
+
+    def list_rank_device(self, kind, which=0, stream=None):
+        """tetra_rx_list_rank_device -> the raw device address of the kind's ranks (int32 per row of rows_device)."""
+        d = C.c_void_p()
+        call(self._lib.tetra_rx_list_rank_device, self._h, which, kind, C.byref(d), stream_ptr(stream))
         return d.value
 
     def links(self, first=0, count=None):
