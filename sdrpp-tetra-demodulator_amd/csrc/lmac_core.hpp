@@ -5,7 +5,8 @@
 // reference-built primitives without a GPU.  Everything is integer work, so "same source" means "same results".  What the
 // kernels share with the emulation: the block table and layout map (blk_param, layout_for), the cooperative front end of byte
 // rows (needs_byte_route, pack_units, staged_row) and its byte route (descramble_chunk), the scrambling sequence (lane_sequence,
-// descramble_words), the blocks cut from packed frames (frame_block, bbk_bits), forward recursion + traceback + CRC
+// descramble_words), the blocks cut from packed frames (frame_block, bbk_bits), the block front ends composed of those, one per source
+// (frame_lookup, load_frame, frame_hard_block, byte_row_block; soft_core.hpp's soft_block), forward recursion + traceback + CRC
 // (decode_hard; soft_core.hpp's decode_soft ends in the same traceback), the channel bit-error count of a decoded block
 // (reencode_errors, opt-in: include/ext/tetra_biterr.h) and the write-back of both row widths (write_rows).
 //
@@ -305,6 +306,45 @@ LM_FN uint32_t rev32(uint32_t x) {
 LM_FN uint32_t spread4(uint32_t nib);
 // bits 4k..4k+3 of a first-bit-most-significant word as four bytes, first bit in the low byte
 LM_FN uint32_t bbk_bytes(uint32_t y, int k) { return spread4(rev32(y << (4 * k)) & 0xfu); }
+
+// ---- block front ends: how a lane turns its source into the descrambled type-4 block, one function per source ------------------------
+// Every decode kernel, the rescue behind it (which has to stage a block exactly as its decode launch did: tetra_list.h) and the host
+// emulation call these; none of them composes the steps above itself.  (The soft source is soft_core.hpp's soft_block; k_lmac_decode's
+// cooperative route stages its chunks through LDS between barriers and keeps its own loop around descramble_chunk.)
+// A listed row's frame and scrambling code: a list entry outside [0, n_frames) -- a caller's slip -- reads the nearest frame instead of
+// memory that is not there; frame_scramb NULL: SB1's fixed code.
+struct FrameRef { int f; uint32_t code; };
+LM_FN FrameRef frame_lookup(int listed, int n_frames, const uint32_t* frame_scramb) {
+    const int lo = listed > 0 ? listed : 0, f = lo < n_frames - 1 ? lo : n_frames - 1;
+    return FrameRef{ f, frame_scramb ? frame_scramb[f] : kScrambInitSb1 };
+}
+// the lane's packed frame: ld16(g) = words 4g .. 4g+3 of the frame as .x .y .z .w (one 16-byte load on the device)
+template <class Ld16>
+LM_FN void load_frame(Ld16 ld16, uint32_t fw[kFrameWords]) {
+#pragma unroll
+    for (int g = 0; g < kFrameWords / 4; ++g) {
+        const auto v = ld16(g);
+        fw[4 * g] = v.x; fw[4 * g + 1] = v.y; fw[4 * g + 2] = v.z; fw[4 * g + 3] = v.w;
+    }
+}
+// Hard block from a packed frame: the layout's bit ranges, descrambled; st(w, word) as descramble_words'.  J: the job, anything with
+// .layout and .type345 (an entry of a kernel's job table, or a BlockKind); frame_type(): the frame's burst type.  A pointer and an
+// accessor so that each of these loads happens where its value is used: a reference parameter tells the compiler that the whole job
+// can be read at once, it then hoists and merges the job's loads, and every frame kernel's schedule changes.
+struct BlockKind { int layout, type345; };
+template <class Job, class FrameType, class Rows, class St>
+LM_FN void frame_hard_block(const Job* J, uint32_t code, const uint32_t fw[kFrameWords], FrameType frame_type, Rows rows, St st) {
+    uint32_t xb[kSeqWords];
+    frame_block(J->layout, fw, frame_type(), xb);
+    descramble_words(J->type345, code, xb, rows, st);
+}
+// byte row read by its own lane, any byte values: ld4(d) = bytes 4d .. 4d+3 of the row; st(w, word) = soft classes of bits 16w .. 16w+15
+template <class Job, class Ld4, class St>
+LM_FN void byte_row_block(const Job* J, uint32_t code, Ld4 ld4, St st) {
+    uint32_t lfsr = code;
+    for (int c0 = 0; c0 < J->type345 >> 2; c0 += kChunkDwords)      // the cooperative route's 64-bit staging chunks
+        lfsr = descramble_chunk(J->type345 - 4 * c0, lfsr, [&](int d) { return ld4(c0 + d); }, [&](int w, uint32_t word) { st(c0 / 4 + w, word); });
+}
 
 // ---- packed 16-bit lanes: two path metrics per 32-bit register (v_pk_add_i16 / v_pk_sub_i16 / v_pk_max_i16) --------
 // In units of 127 a path metric never leaves [-2*292, 20 + 2*292], so int16 needs no renormalisation at all.

@@ -1,7 +1,11 @@
-// lmac_impl.hpp -- what the receive chain (tetra_rx.hip) needs from the frame decoder (tetra_lmac.hip) beyond include/tetra_lmac.h:
-// the soft-decision launch behind TETRA_RX_FLAG_SOFT.  Host-side, hidden from the C ABI.
+// lmac_impl.hpp -- the frame decoder (tetra_lmac.hip) as its callers inside the library see it: ONE function, decode_frames, that takes
+// every option of a frame launch as a FrameOpts.  The three frame entry points of the C ABI (tetra_lmac_decode_frames_device,
+// _biterr_device, _list_device) are it with the options their signatures can express; the receive chain (tetra_rx.hip) builds the
+// options from its handle's flags -- soft values from the chain's ring, bit-error counts, ranks, where the list launches keep their work --
+// and calls it directly.  Host-side, hidden from the C ABI.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/tetra_lmac.h"
@@ -27,18 +31,20 @@ struct ListWork {
 };
 TETRA_HIDDEN size_t list_work_bytes(const tetra_lmac_job_t* jobs, int n_jobs);
 
-// tetra_lmac_decode_frames_device for the coded kinds (SB1, SB2, NDB, SCH/F; a BBK job is TETRA_ERR_ARG: the AACH stays on the packed
-// frames), the block's bits read as soft values from the ring at the frame's bit number (src->d_frame_bitnum, required) and
-// src->frames_per_channel >= 1.  Same jobs, rows, verdicts, labels and workspace as the entry point it mirrors.  d_biterr: as
-// tetra_lmac_decode_frames_biterr_device's (tetra_biterr.h), the counts taken on the soft values.  max_candidates, d_rank: as
-// tetra_lmac_decode_frames_list_device's (tetra_list.h), the margins taken on the soft values.
-TETRA_HIDDEN int decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream,
-                                    uint32_t* const* d_biterr = nullptr, int max_candidates = 0, int32_t* const* d_rank = nullptr,
-                                    ListWork list_work = ListWork());
+// The options of a frame launch; the defaults are tetra_lmac_decode_frames_device.
+struct FrameOpts {
+    // NULL: the blocks' bits from the packed frames.  Else the coded kinds (SB1, SB2, NDB, SCH/F; a BBK job is TETRA_ERR_ARG: the AACH
+    // stays on the packed frames) read as soft values from this ring at the frame's bit number: a ring of whole aligned words, and
+    // src->d_frame_bitnum and src->frames_per_channel >= 1 are required.  Counts and margins are then taken on the soft values.
+    const SoftRing* soft = nullptr;
+    uint32_t* const* d_biterr = nullptr;        // NULL, or per job where its counts go (NULL: the job does not count), tetra_biterr.h
+    int32_t* const* d_rank = nullptr;           // NULL, or per job where its ranks go (NULL: the job is not rescued), tetra_list.h
+    int max_candidates = 0;                     // the ranks' T; looked at only for a job with ranks
+    ListWork list_work;
+};
 
-// tetra_lmac_decode_frames_biterr_device and tetra_lmac_decode_frames_list_device in one: counts and ranks per job, either array may be
-// NULL (the chain with TETRA_RX_FLAG_LIST, with or without TETRA_RX_FLAG_BITERR).
-TETRA_HIDDEN int decode_frames_list(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream, uint32_t* const* d_biterr,
-                                    int max_candidates, int32_t* const* d_rank, ListWork list_work = ListWork());
+// tetra_lmac_decode_frames_device with options: same jobs, rows, verdicts, labels and workspace.  Launches on the stream: the decode
+// kernel, the list launches if any job has ranks, the hand-back of the decision scratch.
+TETRA_HIDDEN int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const FrameOpts& opts, void* hip_stream);
 
 }  // namespace lmac_impl

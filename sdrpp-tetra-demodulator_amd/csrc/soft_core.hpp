@@ -106,6 +106,15 @@ LM_FN void stage_block(int layout, uint32_t bitnum, int frame_type, Ring ring, u
         default: break;
     }
 }
+// The soft front end (beside lmac_core.hpp's, one per source): the lane's sequence, then the block staged from its channel's ring.
+// J: as frame_hard_block's; bitnum(), frame_type(): the frame's absolute bit number and burst type (accessors: loaded behind the
+// sequence, where they are used); rows: as lane_sequence's; ring: as ring_four's, of ring_words words (R / 4); st as stage_block's.
+template <class Job, class Bitnum, class FrameType, class Rows, class Ring, class St>
+LM_FN void soft_block(const Job* J, uint32_t code, Bitnum bitnum, FrameType frame_type, Rows rows, Ring ring, uint32_t ring_words, St st) {
+    uint32_t seq[kSeqWords] = {};
+    lane_sequence(J->type345, code, rows, [&](int w, uint32_t word) { seq[w] = word; });
+    stage_block(J->layout, bitnum(), frame_type(), ring, 4u * ring_words - 1u, seq, st);
+}
 
 // The forward recursion on the staged block: ld(w) = the lane's staged word w.  Deinterleaving and depuncturing are by address as
 // on the hard routes (a punctured position never enters a branch metric: it is the reference's 0); dec_st as viterbi_forward's st.

@@ -2,9 +2,11 @@
 // tp_sap_udata_ind() decoding chain (src/decoder/src/lower_mac/tetra_lower_mac.c:181-236).
 //
 // One 64-lane workgroup (one wavefront) decodes 64 blocks, one block per lane.  Everything a lane computes is lane-level code in
-// lmac_core.hpp (soft_core.hpp for the soft front end) -- pack_units / staged_row, descramble_chunk, lane_sequence / descramble_words,
-// decode_hard / decode_soft, write_rows -- where tests/emul runs the same source on the host; this file holds the kernels' LDS and
-// global-memory accessors, the barriers, and the host side.
+// lmac_core.hpp (soft_core.hpp for the soft front end) -- pack_units / staged_row, descramble_chunk, the block front ends (frame_lookup,
+// load_frame, frame_hard_block, byte_row_block, soft_block: one function per source, called by the decode kernel and by the rescue
+// behind it alike), decode_hard / decode_soft, write_rows -- where tests/emul runs the same source on the host; this file holds the
+// kernels' LDS and global-memory accessors, the barriers, and the host side: every frame entry point is lmac_impl::decode_frames
+// (lmac_impl.hpp) with the options its signature can express.
 //   1. front end -> the descrambled type-4 bits of the lane's block as packed words in LDS, [word][lane]:
 //      * from PACKED FRAMES (k_lmac_frames, round 6): the lane reads its frame (four 16-byte loads), cuts the kind's one or two bit
 //        ranges out with funnel shifts and XORs whole words of its scrambling sequence (linear in the code: four rows of a 64 KB
@@ -84,6 +86,17 @@ __device__ __forceinline__ void write_rows(const OutW& outw, int lane, int rows_
 // lane_sequence's rows of the device's sequence table: 16-byte loads
 __device__ __forceinline__ auto seq_rows(const uint32_t* __restrict__ seq_tab) {
     return [=](int t, uint32_t byte) { return reinterpret_cast<const uint4*>(seq_tab + ((size_t)t * 256 + byte) * kSeqStride); };
+}
+
+// load_frame's 16-byte rows of frame f
+__device__ __forceinline__ auto frame_rows(const uint32_t* frames, int f) {
+    const uint4* src = reinterpret_cast<const uint4*>(frames + (size_t)f * kFrameWords);
+    return [=](int g) { return src[g]; };
+}
+// soft_block's ring of one channel: aligned words
+__device__ __forceinline__ auto ring_of(const uint32_t* ring, uint32_t ring_words, int channel) {
+    const uint32_t* chan = ring + (size_t)channel * ring_words;
+    return [=](uint32_t w) { return chan[w]; };
 }
 
 // The channel bit-error counts (tetra_biterr.h) are an instantiation of each decode kernel: COUNT = true takes where the counts go as a
@@ -239,9 +252,9 @@ __device__ __forceinline__ FrameLane frame_group(const JobTable& tab, int lane) 
     return FrameLane{ J, group, blk0, blk0 + lane, n_blocks, min(kLanes, n_blocks - blk0), 0, 0u };
 }
 __device__ __forceinline__ void frame_of(const JobTable& tab, FrameLane& L) {
-    // (a list entry outside [0, n_frames) -- a caller's slip -- reads the nearest frame instead of memory that is not there)
-    L.f = min(max(L.J.row_frame[L.blk < L.n_blocks ? L.blk : L.blk0], 0), tab.src.n_frames - 1);
-    L.code = L.J.frame_scramb ? L.J.frame_scramb[L.f] : kScrambInitSb1;
+    const FrameRef r = frame_lookup(L.J.row_frame[L.blk < L.n_blocks ? L.blk : L.blk0], tab.src.n_frames, L.J.frame_scramb);
+    L.f = r.f;
+    L.code = r.code;
 }
 // Where the counts of a frame launch go: per job of the table, NULL = the job does not count (tetra_lmac_decode_frames_biterr_device).
 struct BiterrTable { uint32_t* out[TETRA_LMAC_MAX_JOBS]; };
@@ -280,14 +293,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
     const DevJob& J = L.J;
     const int ft = tab.src.frame_type[L.f];
     uint32_t fw[kFrameWords];
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(tab.src.frames + (size_t)L.f * kFrameWords);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const uint4 v = src[g];
-            fw[4 * g] = v.x; fw[4 * g + 1] = v.y; fw[4 * g + 2] = v.z; fw[4 * g + 3] = v.w;
-        }
-    }
+    load_frame(frame_rows(tab.src.frames, L.f), fw);
     bool good = true;
     const bool bbk = J.layout == kLayoutBbk || (RM && J.layout == kLayoutBbkRm);
     if (bbk) {
@@ -309,9 +315,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
             for (int k = 0; k < 4; ++k) dst[k] = demux_core::U2{ bbk_bytes(y, 2 * k), bbk_bytes(y, 2 * k + 1) | (k == 3 ? tail : 0u) };
         }
     } else {
-        uint32_t xb[kSeqWords];
-        frame_block(J.layout, fw, ft, xb);
-        descramble_words(J.type345, L.code, xb, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
+        frame_hard_block(&J, L.code, fw, [&] { return ft; }, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
         load_crc_inv(crc_inv, lane);
         __syncthreads();
         LaneIo io{ outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
@@ -331,7 +335,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames(const JobTable tab, uint
     }
 }
 
-// ---- the coded kinds from SOFT values (lmac_impl::decode_frames_soft: the receive chain's TETRA_RX_FLAG_SOFT) -----------------------
+// ---- the coded kinds from SOFT values (lmac_impl::FrameOpts::soft: the receive chain's TETRA_RX_FLAG_SOFT) --------------------------
 // k_lmac_frames with another front end: where that kernel cuts a block's bits out of the packed frame, this one reads the block's soft
 // values from the chain's ring at the frame's absolute bit number, descrambles them by sign and stages them in LDS as bytes
 // (soft_core.hpp); the forward recursion takes its branch metrics from those bytes; traceback, backward CRC, verdict, label and row
@@ -352,11 +356,8 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
     if (L.blk0 >= L.n_blocks) return;
     frame_of(tab, L);
     const DevJob& J = L.J;
-    const uint32_t* chan = ring + (size_t)(L.f / tab.src.frames_per_channel) * ring_words;
-    uint32_t seq[kSeqWords] = {};
-    lane_sequence(J.type345, L.code, seq_rows(seq_tab), [&](int w, uint32_t word) { seq[w] = word; });
-    stage_block(J.layout, tab.src.bitnum[L.f], tab.src.frame_type[L.f], [&](uint32_t w) { return chan[w]; }, 4u * ring_words - 1u, seq,
-                [&](int g, uint32_t word) { sm.in[g][lane] = word; });
+    soft_block(&J, L.code, [&] { return tab.src.bitnum[L.f]; }, [&] { return tab.src.frame_type[L.f]; }, seq_rows(seq_tab),
+               ring_of(ring, ring_words, L.f / tab.src.frames_per_channel), ring_words, [&](int g, uint32_t word) { sm.in[g][lane] = word; });
     load_crc_inv(crc_inv, lane);
     __syncthreads();
     LaneIo io{ sm.outw, crc_inv, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
 // a job's part of it begins.  k_list_rescue is a small persistent grid: a workgroup takes 64 failed rows of one job at a time, a row per
 // lane, whichever workgroup decoded them, and strides over the list; with no failed row every workgroup reads a handful of words and
 // leaves.  The cost is that of the failed rows.
-// A lane stages its block again through the front end its decode launch used (FRONT), reads the decoder's decision words of its row
+// A lane stages its block again through the front end its decode launch used (FRONT: the same lmac_core.hpp / soft_core.hpp function), reads the decoder's decision words of its row
 // from the launch's scratch -- which the host therefore hands back only behind this kernel --, and runs list_core.hpp's rescue.  The
 // winner's row, verdict, label verdict, rank and (where the launch counts) channel bit errors are written by the lane itself: plain
 // 4-byte stores to one row.
@@ -480,6 +481,7 @@ __global__ __launch_bounds__(kLanes) void k_list_rescue(const RescueTable tab) {
     load_crc_inv(crc_inv, lane);
     __syncthreads();
     auto staged = [&](int w) { return in[w][lane]; };
+    auto stage = [&](int w, uint32_t word) { in[w][lane] = word; };
     auto half = [&](int h) { return outw[h][lane]; };
     for (int v = (int)blockIdx.x;; v += (int)gridDim.x) {
         // group v of 64 failed rows, counted job after job (all of this is workgroup-uniform)
@@ -502,32 +504,21 @@ __global__ __launch_bounds__(kLanes) void k_list_rescue(const RescueTable tab) {
         if constexpr (FRONT == kFrontBytes) {
             // the byte route of k_lmac_decode, the lane reading its own row: classes of plain bits are the packed route's bits
             const uint32_t* rowp = reinterpret_cast<const uint32_t*>(a.type5 + (size_t)row * a.in_stride);
-            uint32_t lfsr = a.fixed_init ? kScrambInitSb1 : a.scramb_init[a.init_index ? a.init_index[row] : row];
-            for (int c0 = 0; c0 < a.type345 >> 2; c0 += kChunkDwords)
-                lfsr = descramble_chunk(a.type345 - 4 * c0, lfsr, [&](int d) { return rowp[c0 + d]; }, [&](int w, uint32_t word) { in[c0 / 4 + w][lane] = word; });
+            byte_row_block(&a, a.fixed_init ? kScrambInitSb1 : a.scramb_init[a.init_index ? a.init_index[row] : row], [&](int d) { return rowp[d]; }, stage);
             rank = tetra_list::rescue_hard<false>(a.type345, a.type2, a.a, tab.T, staged, io, half);
             if (a.counts && rank > 0) biterr = bit_errors_hard<false>(a.type345, a.type2, a.a, half, staged);
         } else {
-            const int f = min(max(a.row_frame[row], 0), tab.src.n_frames - 1);
-            const uint32_t code = a.frame_scramb ? a.frame_scramb[f] : kScrambInitSb1;
+            const FrameRef fr = frame_lookup(a.row_frame[row], tab.src.n_frames, a.frame_scramb);
+            const int f = fr.f;
             if constexpr (FRONT == kFrontFrames) {
-                uint32_t fw[kFrameWords], xb[kSeqWords];
-                const uint4* src = reinterpret_cast<const uint4*>(tab.src.frames + (size_t)f * kFrameWords);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const uint4 w4 = src[g];
-                    fw[4 * g] = w4.x; fw[4 * g + 1] = w4.y; fw[4 * g + 2] = w4.z; fw[4 * g + 3] = w4.w;
-                }
-                frame_block(a.layout, fw, tab.src.frame_type[f], xb);
-                descramble_words(a.type345, code, xb, seq_rows(tab.seq_tab), [&](int w, uint32_t word) { in[w][lane] = word; });
+                uint32_t fw[kFrameWords];
+                load_frame(frame_rows(tab.src.frames, f), fw);
+                frame_hard_block(&a, fr.code, fw, [&] { return tab.src.frame_type[f]; }, seq_rows(tab.seq_tab), stage);
                 rank = tetra_list::rescue_hard<true>(a.type345, a.type2, a.a, tab.T, staged, io, half);
                 if (a.counts && rank > 0) biterr = bit_errors_hard<true>(a.type345, a.type2, a.a, half, staged);
             } else {
-                const uint32_t* chan = tab.ring + (size_t)(f / tab.src.frames_per_channel) * tab.ring_words;
-                uint32_t seq[kSeqWords] = {};
-                lane_sequence(a.type345, code, seq_rows(tab.seq_tab), [&](int w, uint32_t word) { seq[w] = word; });
-                tetra_soft::stage_block(a.layout, tab.src.bitnum[f], tab.src.frame_type[f], [&](uint32_t w) { return chan[w]; }, 4u * tab.ring_words - 1u, seq,
-                                        [&](int g, uint32_t word) { in[g][lane] = word; });
+                tetra_soft::soft_block(&a, fr.code, [&] { return tab.src.bitnum[f]; }, [&] { return tab.src.frame_type[f]; }, seq_rows(tab.seq_tab),
+                                       ring_of(tab.ring, tab.ring_words, f / tab.src.frames_per_channel), tab.ring_words, stage);
                 rank = tetra_list::rescue_soft(a.type345, a.type2, a.a, tab.T, staged, io, half);
                 if (a.counts && rank > 0) biterr = tetra_soft::bit_errors_soft(a.type345, a.type2, a.a, half, staged);
             }
@@ -659,6 +650,15 @@ int launch_list(int front, RescueTable& tab, hipStream_t s, void* ws, size_t ws_
     else if (front == kFrontFrames) hipLaunchKernelGGL(k_list_rescue<kFrontFrames>, grid, dim3(kLanes), 0, s, tab);
     else hipLaunchKernelGGL(k_list_rescue<kFrontSoft>, grid, dim3(kLanes), 0, s, tab);
     return w.launched();
+}
+// The next job of a rescue table, what every front end's job holds filled in: the rows, where their results go, their decision scratch and
+// their kind.  The caller adds its front end's own fields.
+RescueJob& add_rescue_job(RescueTable& rt, const int* n_dev, int n, int* crc_ok, uint8_t* out, int out_stride, tetra_lmac_label_t* labels, uint32_t* counts,
+                          int32_t* rank, const uint32_t* dec, int dec_pairs, int type345, int type2, int a) {
+    RescueJob& j = rt.job[rt.n++];
+    j.n_dev = n_dev; j.n = n; j.crc_ok = crc_ok; j.out = out; j.out_stride = out_stride; j.labels = labels; j.counts = counts; j.rank = rank;
+    j.dec = dec; j.dec_pairs = dec_pairs; j.type345 = type345; j.type2 = type2; j.a = a;
+    return j;
 }
 // a rank array and its T (tetra_list.h): none, or a 4-byte aligned array with T in 1..8
 int check_list(const void* d_rank, int max_candidates) {
@@ -916,9 +916,7 @@ static int decode_counted(int type, const uint8_t* d_type5, int n_blocks, const 
         int list_rc = TETRA_OK;
         if (d_rank) {               // behind the decode launch, in front of the scratch's hand-back
             RescueTable rt = {};
-            RescueJob& a = rt.job[rt.n++];
-            a.n_dev = d_n_blocks; a.n = n_blocks; a.crc_ok = d_crc_ok; a.out = d_type2; a.out_stride = out_stride; a.counts = d_biterr; a.rank = d_rank;
-            a.dec = scratch.p; a.dec_pairs = dec_pairs; a.type345 = p.type345; a.type2 = p.type2; a.a = p.a;
+            RescueJob& a = add_rescue_job(rt, d_n_blocks, n_blocks, d_crc_ok, d_type2, out_stride, nullptr, d_biterr, d_rank, scratch.p, dec_pairs, p.type345, p.type2, p.a);
             a.type5 = d_type5; a.in_stride = in_stride; a.fixed_init = type == TETRA_TPSAP_T_SB1 ? 1 : 0; a.scramb_init = d_scramb_init; a.init_index = d_init_index;
             rt.T = max_candidates;
             list_rc = launch_list(kFrontBytes, rt, s, nullptr, 0);
@@ -929,12 +927,15 @@ static int decode_counted(int type, const uint8_t* d_type5, int n_blocks, const 
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
-// tetra_lmac_decode_frames_device, and with `soft` lmac_impl::decode_frames_soft: the same job table, the soft kernel
-// d_biterr: NULL, or per job where its counts go (tetra_lmac_decode_frames_biterr_device)
-// d_rank: NULL, or per job where its ranks go (tetra_lmac_decode_frames_list_device); max_candidates: their T
-static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const lmac_impl::SoftRing* soft,
-                         uint32_t* const* d_biterr, void* hip_stream, int max_candidates = 0, int32_t* const* d_rank = nullptr,
-                         lmac_impl::ListWork list_work = lmac_impl::ListWork()) {
+}  // extern "C"
+
+// Every frame entry point (lmac_impl.hpp): one job table, the kernel the options select, the list launches behind it for the jobs with ranks.
+int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const FrameOpts& opts, void* hip_stream) {
+    const SoftRing* const soft = opts.soft;
+    if (soft) {     // a ring of whole aligned words, a power of two in size; the frames' bit numbers and channels
+        if (!soft->d_ring || soft->size < 4 || (soft->size & (soft->size - 1)) || ((uintptr_t)soft->d_ring & 3)) return TETRA_ERR_ARG;
+        if (src && (!src->d_frame_bitnum || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
+    }
     if (!src || !jobs || n_jobs < 0 || n_jobs > TETRA_LMAC_MAX_JOBS) return TETRA_ERR_ARG;
     if (n_jobs == 0) return TETRA_OK;
     if (!src->d_frames || !src->d_frame_type || src->n_frames < 0) return TETRA_ERR_ARG;
@@ -953,12 +954,12 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
         const bool rm = j.type == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014);       // (the flag on any other type: refused below)
         if (rm) j.type = TETRA_TPSAP_T_BBK;
         if (j.type < 0 || j.type > 5 || j.max_rows < 0) return TETRA_ERR_ARG;
-        uint32_t* const job_counts = d_biterr ? d_biterr[i] : nullptr;
+        uint32_t* const job_counts = opts.d_biterr ? opts.d_biterr[i] : nullptr;
         if (job_counts && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;       // the AACH is not convolutionally coded
         if ((uintptr_t)job_counts & 3) return TETRA_ERR_ALIGN;
-        int32_t* const job_rank = d_rank ? d_rank[i] : nullptr;
+        int32_t* const job_rank = opts.d_rank ? opts.d_rank[i] : nullptr;
         if (job_rank && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;         // the AACH has no CRC to aim at
-        if (const int bad = check_list(job_rank, max_candidates)) return bad;
+        if (const int bad = check_list(job_rank, opts.max_candidates)) return bad;
         if (j.max_rows == 0) continue;
         if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok) return TETRA_ERR_ARG;
         if (j.type != TETRA_TPSAP_T_SB1 && !j.d_frame_scramb) return TETRA_ERR_ARG;
@@ -1023,31 +1024,31 @@ static int decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_job_t*
     for (int k = 0; k < n; ++k) {
         if (!ranks[k]) continue;
         const DevJob& d = tab.job[k];
-        RescueJob& a = rt.job[rt.n++];
-        a.n_dev = d.n_rows_dev; a.n = d.n_rows; a.crc_ok = d.crc_ok; a.out = d.out; a.out_stride = d.out_stride; a.labels = d.labels;
-        a.counts = counts.out[k]; a.rank = ranks[k];
-        a.dec = scratch.p + d.scratch_base; a.dec_pairs = d.dec_pairs; a.type345 = d.type345; a.type2 = d.type2; a.a = d.a;
+        RescueJob& a = add_rescue_job(rt, d.n_rows_dev, d.n_rows, d.crc_ok, d.out, d.out_stride, d.labels, counts.out[k], ranks[k], scratch.p + d.scratch_base,
+                                      d.dec_pairs, d.type345, d.type2, d.a);
         a.row_frame = d.row_frame; a.frame_scramb = d.frame_scramb; a.layout = d.layout;
     }
-    rt.T = max_candidates; rt.src = tab.src; rt.seq_tab = seq;
+    rt.T = opts.max_candidates; rt.src = tab.src; rt.seq_tab = seq;
     if (soft) { rt.ring = reinterpret_cast<const uint32_t*>(soft->d_ring); rt.ring_words = soft->size / 4u; }
-    const int list_rc = launch_list(soft ? kFrontSoft : kFrontFrames, rt, s, list_work.d_work, list_work.bytes);
+    const int list_rc = launch_list(soft ? kFrontSoft : kFrontFrames, rt, s, opts.list_work.d_work, opts.list_work.bytes);
     const int launch_rc = scratch.launched();
     return list_rc != TETRA_OK ? list_rc : launch_rc;
 }
 
+extern "C" {
+
 int tetra_lmac_decode_frames_list_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, int max_candidates,
                                          int32_t* const* d_rank, void* hip_stream) {
-    return decode_frames(src, jobs, n_jobs, nullptr, nullptr, hip_stream, max_candidates, d_rank);
+    return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{ nullptr, nullptr, d_rank, max_candidates, {} }, hip_stream);
 }
 
 int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream) {
-    return decode_frames(src, jobs, n_jobs, nullptr, nullptr, hip_stream);
+    return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{}, hip_stream);
 }
 
 int tetra_lmac_decode_frames_biterr_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, uint32_t* const* d_biterr,
                                            void* hip_stream) {
-    return decode_frames(src, jobs, n_jobs, nullptr, d_biterr, hip_stream);
+    return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{ nullptr, d_biterr, nullptr, 0, {} }, hip_stream);
 }
 
 size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {
@@ -1191,19 +1192,6 @@ static int decode_batch(int type, const uint8_t* type5, int n_blocks, int in_str
 }
 
 }  // extern "C"
-
-int lmac_impl::decode_frames_soft(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const SoftRing& ring, void* hip_stream,
-                                  uint32_t* const* d_biterr, int max_candidates, int32_t* const* d_rank, ListWork list_work) {
-    // a ring of whole aligned words, a power of two in size; the frames' bit numbers and channels
-    if (!ring.d_ring || ring.size < 4 || (ring.size & (ring.size - 1)) || ((uintptr_t)ring.d_ring & 3)) return TETRA_ERR_ARG;
-    if (src && (!src->d_frame_bitnum || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
-    return decode_frames(src, jobs, n_jobs, &ring, d_biterr, hip_stream, max_candidates, d_rank, list_work);
-}
-
-int lmac_impl::decode_frames_list(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, void* hip_stream, uint32_t* const* d_biterr,
-                                  int max_candidates, int32_t* const* d_rank, ListWork list_work) {
-    return decode_frames(src, jobs, n_jobs, nullptr, d_biterr, hip_stream, max_candidates, d_rank, list_work);
-}
 
 size_t lmac_impl::list_work_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {
     long long tiles = 0, rows = 0;

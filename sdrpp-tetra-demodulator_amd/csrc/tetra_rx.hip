@@ -15,7 +15,8 @@
 // so the demodulator of call k+1 runs beside the tail of call k; results and bit rows are double buffered by call parity.
 // With TETRA_RX_FLAG_SOFT the demodulator also writes its symbols, k_soft (below) follows it on the caller's stream in front of D_k and
 // leaves the call's soft values in the channels' rings, and the tail decodes SB1 and the other coded kinds from those rings
-// (lmac_impl::decode_frames_soft) with the AACH in a launch of its own: 9 launches (soft_core.hpp).
+// (lmac_impl::decode_frames with the ring among its options) with the AACH in a launch of its own: 9 launches (soft_core.hpp).
+// Every option of the decoder -- soft values, bit-error counts, ranks -- reaches it as one lmac_impl::FrameOpts built from the handle's flags.
 // (Until round 6: per kind a compacting demultiplexer into byte rows (4 launches), a counted decode and a label kernel -- 40 launches
 // and 0.36 GB of byte rows per second of 4096 channels; now 7 launches and no byte rows.)
 #include <hip/hip_runtime.h>
@@ -154,10 +155,17 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     src.d_time = h->row_time;
     src.d_workspace = h->lmac_ws;
     src.workspace_bytes = h->lmac_ws.bytes();
+    // the handle's flags as the decoder's options, once: without a flag its array is NULL and the launches are the ones they were
     const lmac_impl::SoftRing ring = { h->soft_ring, h->soft_R };
-    lmac_impl::ListWork list_work;              // the list launches' compaction words (one launch at a time on this stream)
-    list_work.d_work = h->list_ws;
-    list_work.bytes = h->list_ws.bytes();
+    uint32_t* counts[TETRA_RX_N_KINDS];          // per job where its bit-error counts go (NULL: the AACH)
+    int32_t* ranks[TETRA_RX_N_KINDS];            // ... and its ranks (NULL: the AACH)
+    lmac_impl::FrameOpts opts;
+    opts.soft = h->soft ? &ring : nullptr;
+    opts.d_biterr = h->biterr ? counts : nullptr;
+    opts.d_rank = h->list ? ranks : nullptr;
+    opts.max_candidates = h->list_T;
+    opts.list_work.d_work = h->list_ws;          // the list launches' compaction words (one launch at a time on this stream)
+    opts.list_work.bytes = h->list_ws.bytes();
     auto job_of = [&](int k, bool labels) {
         const KindInfo& ki = kKinds[k];
         const KindBufs& r = h->res[b][k];
@@ -177,23 +185,15 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     {   // SB1 first: its SYNC PDUs set the code and the clock for everything else in the same burst (tetra_lower_mac.c:246-275)
         const KindBufs& r = h->res[b][TETRA_RX_KIND_SB1];
         const tetra_lmac_job_t j = job_of(TETRA_RX_KIND_SB1, false);
-        uint32_t* const counts = h->biterr ? r.biterr.get() : nullptr;          // (without the flag: the launches as they were)
-        int32_t* const rank = r.rank.get();
-        if (h->list) {      // the rescue in front of the tracker: a rescued SYNC PDU sets code and clock
-            TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr, h->list_T, &rank, list_work)
-                              : lmac_impl::decode_frames_list(&src, &j, 1, s, h->biterr ? &counts : nullptr, h->list_T, &rank, list_work));
-        } else {
-            TETRA_TRY(h->soft ? lmac_impl::decode_frames_soft(&src, &j, 1, ring, s, h->biterr ? &counts : nullptr)
-                              : tetra_lmac_decode_frames_biterr_device(&src, &j, 1, h->biterr ? &counts : nullptr, s));
-        }
+        counts[0] = r.biterr;
+        ranks[0] = r.rank;
+        TETRA_TRY(lmac_impl::decode_frames(&src, &j, 1, opts, s));      // (with ranks the rescue runs in front of the tracker: a rescued SYNC PDU sets code and clock)
         TETRA_TRY(tetra_lmac_track_sync_lists_device(r.t2, kKinds[TETRA_RX_KIND_SB1].out_stride, r.ok, h->ft, h->nf,
                                                  h->chan_first + (size_t)TETRA_LIST_SYNC * h->C, h->C, h->F, h->cell, h->row_scramb, h->row_time_rx,
                                                  h->row_time, h->fb, reinterpret_cast<tetra_lmac_label_t*>(r.blocks.get()), s));
     }
     HIP_TRY(h, hipEventRecord(h->ev_stage[2], s));
     tetra_lmac_job_t jobs[TETRA_RX_N_KINDS];
-    uint32_t* counts[TETRA_RX_N_KINDS];          // per job where its bit-error counts go (NULL: the AACH)
-    int32_t* ranks[TETRA_RX_N_KINDS];            // ... and its ranks (TETRA_RX_FLAG_LIST; NULL: the AACH)
     int nj = 0;
     for (int k : kJobOrder)
         if ((h->kinds & (1 << k)) && !(h->soft && k == TETRA_RX_KIND_BBK)) {
@@ -202,7 +202,8 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
             jobs[nj++] = job_of(k, true);
         }
     if (h->soft) {      // the coded kinds from the ring; the AACH from the packed frames as ever, a launch of its own
-        TETRA_TRY(lmac_impl::decode_frames_soft(&src, jobs, nj, ring, s, h->biterr ? counts : nullptr, h->list_T, h->list ? ranks : nullptr, list_work));
+        TETRA_TRY(lmac_impl::decode_frames(&src, jobs, nj, opts, s));
+        opts.soft = nullptr;
         nj = 0;
         if (h->kinds & (1 << TETRA_RX_KIND_BBK)) {
             counts[nj] = nullptr;
@@ -211,11 +212,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         }
     }
     // (the rescue of these kinds runs inside the call, behind its decode launch: in front of the link figures and of the tail's event)
-    if (h->list) {
-        TETRA_TRY(lmac_impl::decode_frames_list(&src, jobs, nj, s, h->biterr ? counts : nullptr, h->list_T, ranks, list_work));
-    } else {
-        TETRA_TRY(tetra_lmac_decode_frames_biterr_device(&src, jobs, nj, h->biterr ? counts : nullptr, s));
-    }
+    TETRA_TRY(lmac_impl::decode_frames(&src, jobs, nj, opts, s));
     if (h->biterr) {
         LinkTable tab = {};
         for (int k = 0; k < TETRA_RX_N_KINDS; ++k)
@@ -231,6 +228,33 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
 int parity_of(const tetra_rx* h, int which) {
     if (which < 0 || which > 1 || h->calls <= which) return -1;
     return (int)((h->calls - 1 - which) & 1);
+}
+
+// The rows of `kind` of call `which` are ready: what every fetch does once its arguments are checked.  No such call yet: no rows,
+// TETRA_OK.  Else waits for that call's tail, reads and bounds the row count into *n_rows, and applies the capacity rule: more rows than
+// `capacity` is TETRA_ERR_SIZE only if the caller `wants` them (it handed in an output pointer), TETRA_OK for one who only counts.
+// copy(r, n) then brings n > 0 wanted rows over, with the handle's device still selected, and its status is the fetch's.
+template <class Copy>
+int fetch_rows(tetra_rx* h, int which, int kind, bool wants, int capacity, int* n_rows, Copy copy) {
+    *n_rows = 0;
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_OK;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
+    const KindBufs& r = h->res[b][kind];
+    int32_t n = 0;
+    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
+    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;          // (cannot happen: the demultiplexer counts at most `rows` frames)
+    *n_rows = n;
+    if (n > capacity) return wants ? TETRA_ERR_SIZE : TETRA_OK;
+    return n && wants ? copy(r, (int)n) : TETRA_OK;
+}
+
+// the latest call's tail is done: what the getters of per-channel state wait for
+int latest_tail_done(tetra_rx* h) {
+    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    return TETRA_OK;
 }
 
 }  // namespace
@@ -426,69 +450,47 @@ int tetra_rx_fetch(tetra_rx_t* h, int which, int kind, tetra_rx_block_t* blocks,
     if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
     if (!(h->kinds & (1 << kind))) return TETRA_ERR_UNSUPPORTED;
     if (type1 && type1_stride < kKinds[kind].type1_bits) return TETRA_ERR_SIZE;
-    *n_rows = 0;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
-    const KindBufs& r = h->res[b][kind];
-    int32_t n = 0;
-    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
-    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;          // (cannot happen: the demultiplexer counts at most `rows` frames)
-    *n_rows = n;
-    if (n > capacity) return (blocks || type1) ? TETRA_ERR_SIZE : TETRA_OK;
-    if (n == 0) return TETRA_OK;
-    if (blocks) HIP_TRY(h, hipMemcpy(blocks, r.blocks, sizeof(tetra_rx_block_t) * (size_t)n, hipMemcpyDeviceToHost));
-    if (type1) {
-        const int nb = kKinds[kind].type1_bits;
-        if (type1_stride == nb) {
-            // contiguous rows at the caller's: pack on the device, ONE copy (a strided device-to-host copy of 10^5 narrow rows moves
-            // ~50 MB/s: 1.9 s for a second of 4096 channels' blocks, measured; this way the link's rate)
-            if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
-                (void)hipGetLastError();
-                return TETRA_ERR_NOMEM;
+    return fetch_rows(h, which, kind, blocks || type1, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
+        if (blocks) HIP_TRY(h, hipMemcpy(blocks, r.blocks, sizeof(tetra_rx_block_t) * (size_t)n, hipMemcpyDeviceToHost));
+        if (type1) {
+            const int nb = kKinds[kind].type1_bits;
+            if (type1_stride == nb) {
+                // contiguous rows at the caller's: pack on the device, ONE copy (a strided device-to-host copy of 10^5 narrow rows moves
+                // ~50 MB/s: 1.9 s for a second of 4096 channels' blocks, measured; this way the link's rate)
+                if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return TETRA_ERR_NOMEM;
+                }
+                const long long units = (long long)n * (nb >> 1);
+                hipLaunchKernelGGL(k_rx_pack_type1, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[kind].out_stride, nb, n,
+                                   h->fetch_stage);
+                HIP_TRY(h, hipGetLastError());
+                HIP_TRY(h, hipMemcpyAsync(type1, h->fetch_stage, (size_t)n * nb, hipMemcpyDeviceToHost, h->fetch_s));
+                HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
+            } else {
+                HIP_TRY(h, hipMemcpy2D(type1, (size_t)type1_stride, r.t2, (size_t)kKinds[kind].out_stride, (size_t)nb, (size_t)n, hipMemcpyDeviceToHost));
             }
-            const long long units = (long long)n * (nb >> 1);
-            hipLaunchKernelGGL(k_rx_pack_type1, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[kind].out_stride, nb, n,
-                               h->fetch_stage);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipMemcpyAsync(type1, h->fetch_stage, (size_t)n * nb, hipMemcpyDeviceToHost, h->fetch_s));
-            HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
-        } else {
-            HIP_TRY(h, hipMemcpy2D(type1, (size_t)type1_stride, r.t2, (size_t)kKinds[kind].out_stride, (size_t)nb, (size_t)n, hipMemcpyDeviceToHost));
         }
-    }
-    return TETRA_OK;
+        return TETRA_OK;
+    });
 }
 
 int tetra_rx_fetch_aach_dist(tetra_rx_t* h, int which, uint8_t* dist, int capacity, int* n_rows) {
     if (!h || !n_rows || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
     if (!h->aach_rm || !(h->kinds & (1 << TETRA_RX_KIND_BBK))) return TETRA_ERR_UNSUPPORTED;
-    *n_rows = 0;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
-    const KindBufs& r = h->res[b][TETRA_RX_KIND_BBK];
-    int32_t n = 0;
-    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
-    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
-    *n_rows = n;
-    if (n > capacity) return dist ? TETRA_ERR_SIZE : TETRA_OK;
-    if (n == 0 || !dist) return TETRA_OK;
-    // packed on the device, one copy (see tetra_rx_fetch)
-    if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
-        (void)hipGetLastError();
-        return TETRA_ERR_NOMEM;
-    }
-    hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[TETRA_RX_KIND_BBK].out_stride, 30, n,
-                       h->fetch_stage);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(dist, h->fetch_stage, (size_t)n, hipMemcpyDeviceToHost, h->fetch_s));
-    HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
-    return TETRA_OK;
+    return fetch_rows(h, which, TETRA_RX_KIND_BBK, dist != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
+        // packed on the device, one copy (see tetra_rx_fetch)
+        if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
+            (void)hipGetLastError();
+            return TETRA_ERR_NOMEM;
+        }
+        hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[TETRA_RX_KIND_BBK].out_stride, 30, n,
+                           h->fetch_stage);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(dist, h->fetch_stage, (size_t)n, hipMemcpyDeviceToHost, h->fetch_s));
+        HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
+        return TETRA_OK;
+    });
 }
 
 // the chain's share of tetra_biterr.h
@@ -497,21 +499,10 @@ static bool counts_kind(const tetra_rx* h, int kind) { return h->biterr && kind 
 int tetra_rx_fetch_biterr(tetra_rx_t* h, int which, int kind, uint32_t* out, int capacity, int* n_rows) {
     if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
     if (!counts_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    *n_rows = 0;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
-    const KindBufs& r = h->res[b][kind];
-    int32_t n = 0;
-    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
-    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
-    *n_rows = n;
-    if (n > capacity) return out ? TETRA_ERR_SIZE : TETRA_OK;
-    if (n == 0 || !out) return TETRA_OK;
-    HIP_TRY(h, hipMemcpy(out, r.biterr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return TETRA_OK;
+    return fetch_rows(h, which, kind, out != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
+        HIP_TRY(h, hipMemcpy(out, r.biterr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        return TETRA_OK;
+    });
 }
 
 int tetra_rx_biterr_device(tetra_rx_t* h, int which, int kind, const uint32_t** d_biterr, void* hip_stream) {
@@ -540,21 +531,10 @@ int tetra_rx_set_list_candidates(tetra_rx_t* h, int max_candidates) {
 int tetra_rx_fetch_list_rank(tetra_rx_t* h, int which, int kind, int32_t* out, int capacity, int* n_rows) {
     if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
     if (!ranks_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    *n_rows = 0;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipEventSynchronize(h->ev_tail[b]));
-    const KindBufs& r = h->res[b][kind];
-    int32_t n = 0;
-    HIP_TRY(h, hipMemcpy(&n, r.n_rows, sizeof(n), hipMemcpyDeviceToHost));
-    if (n < 0 || n > h->rows) return TETRA_ERR_HIP;
-    *n_rows = n;
-    if (n > capacity) return out ? TETRA_ERR_SIZE : TETRA_OK;
-    if (n == 0 || !out) return TETRA_OK;
-    HIP_TRY(h, hipMemcpy(out, r.rank, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return TETRA_OK;
+    return fetch_rows(h, which, kind, out != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
+        HIP_TRY(h, hipMemcpy(out, r.rank, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        return TETRA_OK;
+    });
 }
 
 int tetra_rx_list_rank_device(tetra_rx_t* h, int which, int kind, const int32_t** d_rank, void* hip_stream) {
@@ -574,7 +554,7 @@ int tetra_rx_get_link(tetra_rx_t* h, int first, int count, tetra_rx_link_t* out)
     if (!h->biterr) return TETRA_ERR_UNSUPPORTED;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    TETRA_TRY(latest_tail_done(h));
     if (count) HIP_TRY(h, hipMemcpy(out, h->link + first, sizeof(tetra_rx_link_t) * (size_t)count, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
@@ -600,7 +580,7 @@ int tetra_rx_get_cell(tetra_rx_t* h, int first, int count, tetra_lmac_cell_state
     if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    TETRA_TRY(latest_tail_done(h));
     if (count) HIP_TRY(h, hipMemcpy(out, h->cell + first, sizeof(tetra_lmac_cell_state_t) * (size_t)count, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
@@ -609,7 +589,7 @@ int tetra_rx_get_sync_state(tetra_rx_t* h, int first, int count, tetra_bsync_sta
     if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    TETRA_TRY(latest_tail_done(h));
     return count ? tetra_bsync_get_state(h->bs, first, count, out) : TETRA_OK;
 }
 
@@ -618,7 +598,7 @@ int tetra_rx_set_sync_tolerance(tetra_rx_t* h, const tetra_bsync_tolerance_t* to
     if (!h) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));      // (the synchroniser's own entry waits for the device)
+    TETRA_TRY(latest_tail_done(h));      // (the synchroniser's own entry waits for the device)
     return tetra_bsync_set_tolerance(h->bs, tol);
 }
 
@@ -626,7 +606,7 @@ int tetra_rx_get_sync_misses(tetra_rx_t* h, int first, int count, int32_t* out) 
     if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    TETRA_TRY(latest_tail_done(h));
     return count ? tetra_bsync_get_misses(h->bs, first, count, out) : TETRA_OK;
 }
 

@@ -97,15 +97,20 @@ def out_stride_for(blk_type):
     return (blk_param(blk_type).type2_bits + 3) & ~3
 
 
-def decode_batch(blk_type, type5, scramb=None, device=-1):
-    """type5 uint8 [n][in_stride] (in_stride % 4 == 0), scramb uint32 [n] (None for SB1)
-    -> (type2 uint8 [n][type2_bits rounded up to 4], crc_ok int32 [n])."""
+def _host_batch(blk_type, type5, scramb):
+    """What every decode_batch* call hands over: the rows, their count and stride, the scrambling codes, the output rows with their
+    stride, and the verdicts."""
     rows = np.ascontiguousarray(type5, np.uint8)
     n, in_stride = rows.shape
     ost = out_stride_for(blk_type)
-    out = np.zeros((n, ost), np.uint8)
-    ok = np.zeros(n, np.int32)
     si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
+    return rows, n, in_stride, si, np.zeros((n, ost), np.uint8), ost, np.zeros(n, np.int32)
+
+
+def decode_batch(blk_type, type5, scramb=None, device=-1):
+    """type5 uint8 [n][in_stride] (in_stride % 4 == 0), scramb uint32 [n] (None for SB1)
+    -> (type2 uint8 [n][type2_bits rounded up to 4], crc_ok int32 [n])."""
+    rows, n, in_stride, si, out, ost, ok = _host_batch(blk_type, type5, scramb)
     call(_lib().tetra_lmac_decode_batch, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), device)
     return out, ok
 
@@ -131,11 +136,8 @@ def split_biterr(biterr):
 
 def decode_batch_biterr(blk_type, type5, scramb=None, device=-1):
     """tetra_lmac_decode_batch_biterr: decode_batch plus the channel bit-error counts -> (type2, crc_ok, biterr uint32 [n])."""
-    rows = np.ascontiguousarray(type5, np.uint8)
-    n, in_stride = rows.shape
-    ost = out_stride_for(blk_type)
-    out, ok, be = np.zeros((n, ost), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.uint32)
-    si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
+    rows, n, in_stride, si, out, ost, ok = _host_batch(blk_type, type5, scramb)
+    be = np.zeros(n, np.uint32)
     call(_lib().tetra_lmac_decode_batch_biterr, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), ptr(be), device)
     return out, ok, be
 
@@ -150,11 +152,8 @@ def decode_counted_biterr_device(blk_type, d_type5, capacity, d_n_blocks, in_str
 def decode_batch_list(blk_type, type5, scramb=None, max_candidates=LIST_DEFAULT_CANDIDATES, device=-1):
     """tetra_lmac_decode_batch_list (include/ext/tetra_list.h): decode_batch plus the CRC-aided rescue of the failed rows
     -> (type2, crc_ok, rank int32 [n]: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k, -1 = not rescued)."""
-    rows = np.ascontiguousarray(type5, np.uint8)
-    n, in_stride = rows.shape
-    ost = out_stride_for(blk_type)
-    out, ok, rank = np.zeros((n, ost), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
-    si = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
+    rows, n, in_stride, si, out, ost, ok = _host_batch(blk_type, type5, scramb)
+    rank = np.zeros(n, np.int32)
     call(_lib().tetra_lmac_decode_batch_list, int(blk_type), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(ok), int(max_candidates), ptr(rank), device)
     return out, ok, rank
 
@@ -193,12 +192,17 @@ def decode_frames_workspace_bytes(jobs):
     return int(_lib().tetra_lmac_decode_frames_workspace_bytes(_job_array(jobs), len(jobs)))
 
 
+def _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace):
+    """tetra_lmac_frames_t of torch tensors on the GPU (None: NULL)."""
+    return Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
+                  ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+
+
 def decode_frames_device(d_frames, d_frame_type, jobs, frames_per_channel=0, d_frame_bitnum=None, d_time_rx=None, d_time=None, stream=None,
                          d_workspace=None):
     """tetra_lmac_decode_frames_device.  jobs: dicts with type, blk_num, row_frame, n_rows (tensor or None), max_rows, out_stride,
     frame_scramb (tensor or None), type2, crc_ok, labels (int32 tensor [rows][6] or None); d_workspace: uint8 tensor or None (pool)."""
-    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
-                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    src = _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace)
     call(_lib().tetra_lmac_decode_frames_device, C.byref(src), _job_array(jobs), len(jobs), stream_ptr(stream))
 
 
@@ -206,8 +210,7 @@ def decode_frames_biterr_device(d_frames, d_frame_type, jobs, frames_per_channel
                                 d_workspace=None, counted=True):
     """tetra_lmac_decode_frames_biterr_device: decode_frames_device whose jobs may carry `biterr` (int32 / uint32 tensor [max_rows], or
     None / absent: the job does not count).  counted=False hands in no array at all."""
-    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
-                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    src = _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace)
     arr = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
     call(_lib().tetra_lmac_decode_frames_biterr_device, C.byref(src), _job_array(jobs), len(jobs), arr if counted else None, stream_ptr(stream))
 
@@ -216,8 +219,7 @@ def decode_frames_list_device(d_frames, d_frame_type, jobs, max_candidates=LIST_
                               d_time_rx=None, d_time=None, stream=None, d_workspace=None, ranked=True):
     """tetra_lmac_decode_frames_list_device: decode_frames_device whose jobs may carry `rank` (int32 tensor [max_rows], or None / absent:
     the job is not rescued).  ranked=False hands in no array at all."""
-    src = Frames(ptr(d_frames), ptr(d_frame_type), int(d_frame_type.numel()), int(frames_per_channel), ptr(d_frame_bitnum), ptr(d_time_rx),
-                 ptr(d_time), ptr(d_workspace), 0 if d_workspace is None else int(d_workspace.numel() * d_workspace.element_size()))
+    src = _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace)
     arr = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
     call(_lib().tetra_lmac_decode_frames_list_device, C.byref(src), _job_array(jobs), len(jobs), int(max_candidates), arr if ranked else None,
          stream_ptr(stream))

@@ -177,26 +177,25 @@ class RxChain:
         call(self._lib.tetra_rx_fetch, self._h, which, kind, ptr(blocks), ptr(t1), nb, max(n, 1), C.byref(got))
         return blocks[:got.value], t1[:got.value]
 
+    def _count_then_fetch(self, fn, dtype, which, *kind):
+        """A fetch entry point of the form fn(h, which, [kind,] out, capacity, &n_rows): asked for the row count, then for the rows."""
+        n = C.c_int(0)
+        call(fn, self._h, which, *kind, None, 0, C.byref(n))
+        v = np.zeros(max(n.value, 1), dtype)
+        got = C.c_int(0)
+        call(fn, self._h, which, *kind, ptr(v), max(n.value, 1), C.byref(got))
+        return v[:got.value]
+
     def fetch_aach_dist(self, which=0):
         """tetra_rx_fetch_aach_dist: uint8 [n], byte 30 of every BBK row in fetch(KIND_BBK)'s order -- the Hamming distance 0..3 the
         RM(30,14) decoder corrected, or AACH_UNDECODABLE.  Needs a handle created with FLAG_AACH_RM3014."""
-        n = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_aach_dist, self._h, which, None, 0, C.byref(n))
-        dist = np.zeros(max(n.value, 1), np.uint8)
-        got = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_aach_dist, self._h, which, ptr(dist), max(n.value, 1), C.byref(got))
-        return dist[:got.value]
+        return self._count_then_fetch(self._lib.tetra_rx_fetch_aach_dist, np.uint8, which)
 
     def fetch_biterr(self, kind, which=0):
         """tetra_rx_fetch_biterr: (errors, compared) int arrays [n] of a coded kind's rows, in fetch(kind)'s order -- the distance from
         the received block to the decoded codeword and the positions it was taken over; an estimate of the channel's bit errors that
         is meaningful for rows with a good CRC.  Needs a handle created with FLAG_BITERR."""
-        n = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_biterr, self._h, which, kind, None, 0, C.byref(n))
-        v = np.zeros(max(n.value, 1), np.uint32)
-        got = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_biterr, self._h, which, kind, ptr(v), max(n.value, 1), C.byref(got))
-        v = v[:got.value].astype(np.int64)
+        v = self._count_then_fetch(self._lib.tetra_rx_fetch_biterr, np.uint32, which, kind).astype(np.int64)
         return v & 0xffff, v >> 16
 
     def biterr_device(self, kind, which=0, stream=None):
@@ -213,12 +212,7 @@ class RxChain:
     def fetch_list_rank(self, kind, which=0):
         """tetra_rx_fetch_list_rank: int32 [n] of a coded kind's rows, in fetch(kind)'s order -- 0: the decoder's own path passed the CRC,
         k >= 1: rescued by candidate k, -1: failed and not rescued.  Needs a handle created with FLAG_LIST."""
-        n = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_list_rank, self._h, which, kind, None, 0, C.byref(n))
-        v = np.zeros(max(n.value, 1), np.int32)
-        got = C.c_int(0)
-        call(self._lib.tetra_rx_fetch_list_rank, self._h, which, kind, ptr(v), max(n.value, 1), C.byref(got))
-        return v[:got.value]
+        return self._count_then_fetch(self._lib.tetra_rx_fetch_list_rank, np.int32, which, kind)
 
     def list_rank_device(self, kind, which=0, stream=None):
         """tetra_rx_list_rank_device -> the raw device address of the kind's ranks (int32 per row of rows_device)."""

@@ -1,6 +1,7 @@
 // Host build of the soft-decision option's lane-level code (sdrpp-tetra-demodulator_amd/csrc/soft_core.hpp + the sequence, traceback
-// and write-back of lmac_core.hpp): the quantiser of k_soft and the workgroups of k_lmac_frames_soft with plain arrays where the kernels
-// have global memory and LDS (lmac_lane_io.hpp).  Test infrastructure: lets the CPU suite hold the exact kernel source against the reference's conv_cch_decode.
+// and write-back of lmac_core.hpp): the quantiser of k_soft and the workgroups of k_lmac_frames_soft -- soft_core.hpp's soft_block, the
+// front end the kernel calls, with lmac_lane_io.hpp's lane epilogue behind it and plain arrays where the kernels have global memory and
+// LDS.  Test infrastructure: lets the CPU suite hold the exact kernel source against the reference's conv_cch_decode.
 #define TETRA_HOST_EMUL 1
 #include "../../sdrpp-tetra-demodulator_amd/csrc/soft_core.hpp"
 #include "lmac_lane_io.hpp"
@@ -36,17 +37,17 @@ extern "C" int soft_emul_decode(int tpsap, int blk_num, const int8_t* rings, uin
     const int layout = tpsap < 0 || tpsap > 5 || tpsap == TETRA_TPSAP_T_BBK ? kLayoutNone : layout_for(tpsap, blk_num, false);
     if (layout == kLayoutNone || ring_size < 4 || (ring_size & (ring_size - 1))) return -1;
     const BlkParam& p = blk_param(tpsap);
+    const BlockKind kind{ layout, p.type345 };
     for (int blk0 = 0; blk0 < n_rows; blk0 += kLanes) {
         const int rows_here = n_rows - blk0 < kLanes ? n_rows - blk0 : kLanes;
         OutW outw;
         for (int lane = 0; lane < rows_here; ++lane) {
             const int j = blk0 + lane;
-            const uint32_t* ring = reinterpret_cast<const uint32_t*>(rings + (size_t)j * ring_size);
-            uint32_t seq[kSeqWords] = {}, soft[kSoftWords] = {};
-            lane_sequence(p.type345, scramb ? scramb[j] : kScrambInitSb1, seq_rows(seq_table()), [&](int w, uint32_t word) { seq[w] = word; });
-            stage_block(layout, bitnum[j], frame_type[j], [&](uint32_t w) { return ring[w]; }, ring_size - 1u, seq, [&](int g, uint32_t word) { soft[g] = word; });
-            LaneIo io{ outw, lane, {} };
-            crc_ok[j] = decode_soft(p.type345, p.type2, p.a, [&](int w) { return soft[w]; }, io);
+            uint32_t soft[kSoftWords] = {};
+            soft_block(&kind, scramb ? scramb[j] : kScrambInitSb1, [&] { return bitnum[j]; }, [&] { return frame_type[j]; }, seq_rows(seq_table()),
+                       ring_words(rings + (size_t)j * ring_size), ring_size / 4u, [&](int g, uint32_t word) { soft[g] = word; });
+            finish_lane(outw, lane, [&](LaneIo& io) { return decode_soft(p.type345, p.type2, p.a, [&](int w) { return soft[w]; }, io); },
+                        [](bool) { return 0u; }, NoRescue(), &crc_ok[j], nullptr, nullptr);
         }
         write_rows(outw, rows_here, p.type2, out + (size_t)blk0 * out_stride, out_stride);
     }
