@@ -5,9 +5,9 @@ ms[1]; the extra frames it delivers show in the decode stages ms[2] (SB1) and ms
 
     python profiles/measure_sync_tol.py                       # one process, this build: flag off / on
     python profiles/measure_sync_tol.py --ab PARENT_LIB [--rounds 2]
-        fresh processes in alternation -- a build of the parent commit, this build with the flag off, this build with the flag on --
-        with each one's medians per round, the parent's own round-to-round spread (the resolution of the comparison), the stages and
-        the rows delivered
+        fresh processes in alternation -- a build of the parent commit and this build with the flag off, then both with the flag on (the
+        parent's only where it has the tolerant lock) -- with each one's medians per round, the parent's own round-to-round spread (the
+        resolution of the comparison), the stages and the rows delivered
     python profiles/measure_sync_tol.py --ab PARENT_LIB --swap
         the same with this build (flag off) in front of the parent build in every round, recorded beside the first as builds_swapped:
         a difference that follows the build and not the position in the round is the build's
@@ -64,7 +64,7 @@ def child(lib, tolerant, a):
     return json.loads(p.stdout.strip().splitlines()[-1])
 
 
-CONFIGS = (("parent", True, 0), ("off", False, 0), ("on", False, 1))
+CONFIGS = (("parent", True, 0), ("off", False, 0), ("parent_on", True, 1), ("on", False, 1))
 
 
 def main():
@@ -78,6 +78,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--swap", action="store_true", help="this build with the flag off runs first in every round, the parent build second: tells a "
                     "difference between the builds from an effect of the position in the round; recorded under builds_swapped")
+    ap.add_argument("--parent-on", action="store_true", help="the parent build has the tolerant lock too: measure it with the flag on beside this build's")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -91,10 +92,11 @@ def main():
     if a.ab:
         rounds = []
         for _ in range(a.rounds):
-            order = (CONFIGS[1], CONFIGS[0], CONFIGS[2]) if a.swap else CONFIGS
+            order = (CONFIGS[1], CONFIGS[0], CONFIGS[3], CONFIGS[2]) if a.swap else CONFIGS
+            order = [c for c in order if a.parent_on or c[0] != "parent_on"]
             rounds.append({name: child(os.path.abspath(a.ab) if parent else None, tolerant, a) for name, parent, tolerant in order})
             print(json.dumps(rounds[-1]), flush=True)
-        names = [c[0] for c in CONFIGS]
+        names = [c[0] for c in CONFIGS if a.parent_on or c[0] != "parent_on"]
         s = {}
         for mode in ("two_stream", "one_stream"):
             med = {n: [r[n][mode]["ms_per_call_median"] for r in rounds] for n in names}
@@ -105,7 +107,13 @@ def main():
                        "flag_off_inside_parent_spread": bool(min(med["parent"]) <= mean["off"] <= max(med["parent"])),
                        "flag_off_not_above_parent_spread": bool(mean["off"] <= max(med["parent"])),
                        "flag_on_minus_flag_off_ms": round(mean["on"] - mean["off"], 4)}
+            if a.parent_on:                 # every median of this build against the parent's range, rule by rule
+                s[mode].update({"parent_on_round_to_round_spread_ms": round(max(med["parent_on"]) - min(med["parent_on"]), 4),
+                                "flag_on_minus_parent_on_ms": round(mean["on"] - mean["parent_on"], 4),
+                                "every_flag_off_median_not_above_parent_range": bool(max(med["off"]) <= max(med["parent"])),
+                                "every_flag_on_median_not_above_parent_on_range": bool(max(med["on"]) <= max(med["parent_on"]))})
         s["one_stream_stage_ms"] = {n: [r[n]["one_stream"]["stage_ms"] for r in rounds] for n in names}
+        s["synchroniser_stage_ms_per_round"] = {n: [r[n]["one_stream"]["stage_ms"][1] for r in rounds] for n in names}
         s["synchroniser_stage_ms"] = {n: round(statistics.mean(r[n]["one_stream"]["stage_ms"][1] for r in rounds), 4) for n in names}
         s["decode_stages_ms"] = {n: round(statistics.mean(r[n]["one_stream"]["stage_ms"][2] + r[n]["one_stream"]["stage_ms"][3] for r in rounds), 4) for n in names}
         s["rows_per_kind"] = {n: rounds[-1][n]["rows_per_kind"] for n in names}

@@ -1,5 +1,5 @@
 // bsync_core.hpp -- the burst synchroniser's logic (include/tetra_burst_sync.h), shared by the gfx950 kernel
-// (tetra_burst_sync.hip) and its host build (tests/emul/bsync_emul.cpp, -DTETRA_HOST_EMUL).
+// (tetra_burst_sync.hip) and its host builds (tests/emul/bsync_emul.cpp, bsync_tol_emul.cpp through bsync_lane_io.hpp, -DTETRA_HOST_EMUL).
 //
 // Contract: for one channel, one call over n_new bits leaves exactly the state, and reports exactly the frames, that the
 // reference's tetra_burst_sync_in() (src/decoder/src/phy/tetra_burst_sync.c:54-155) produces when it is handed the same
@@ -27,15 +27,22 @@
 // Tolerant lock (include/ext/tetra_sync_tol.h; opt-in, a departure from the reference): UNLOCKED and KNOW_FSTART as above, but a LOCKED
 // call looks only at the expected positions of the frame -- sync at 214, normal 1 / 2 at 244 --, accepts up to tol_sync / tol_norm bit
 // errors there (tolerant_frame_eval) and falls back to UNLOCKED only behind max_miss consecutive frames without a candidate
-// (first_unlock).  Only the sync bitmap is needed then.  run_tolerant() is that policy; run() is the reference's rule.
+// (first_unlock).  Only the sync bitmap is needed then.
+//
+// One walk over the events, walk(), serves both: the rule is a small policy object (RefLock, TolLock) that says what a LOCKED call
+// reports and how a literal call in UNLOCKED is answered; run() and run_tolerant() bind walk() to their rule.  Steps 1 and 4 of the kernel -- packing the stream, expanding the listed
+// frames, writing the carried buffer back -- are lane code here too (stage_thread, write_thread), so the host build runs the kernel's text.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__) && !defined(TETRA_HOST_EMUL)
 #define BS_FN __device__ __forceinline__
+#define BS_MFN __device__ __forceinline__
 #else
 #define BS_FN static inline
+#define BS_MFN inline               // (member functions: `static` would mean something else)
 #endif
 
 namespace bsync_core {
@@ -101,6 +108,8 @@ BS_FN uint32_t range_mask(int w, int lo, int hi) {
 // match bits of the 32 positions 32w .. 32w+31 (LSB = position 32w) for the three sequences; a position counts only if
 // the whole sequence lies inside [x0, xe).  Bit-sliced: for every offset k into the sequence, the 32 candidate windows'
 // k-th bits are one funnel-shifted word, AND-ed (or AND-NOT-ed) into the three running match words.
+// NORMAL = false: the sync bitmap alone; m_n1 / m_n2 are left as they are.
+template <bool NORMAL = true>
 BS_FN void match_word(const uint32_t* s, int w, int x0, int xe, uint32_t& m_sync, uint32_t& m_n1, uint32_t& m_n2) {
     const uint32_t w0 = s[w], w1 = s[w + 1], w2 = s[w + 2];
     uint32_t ay = 0xffffffffu, an = 0xffffffffu, ap = 0xffffffffu;
@@ -109,28 +118,24 @@ BS_FN void match_word(const uint32_t* s, int w, int x0, int xe, uint32_t& m_sync
     for (int k = 0; k < 38; ++k) {
         const uint32_t v = shifted_word(w0, w1, w2, k);
         ay &= ((seq_y >> (37 - k)) & 1u) ? v : ~v;
-        if (k < 22) {
+        if (NORMAL && k < 22) {
             an &= ((kHeadN >> (21 - k)) & 1u) ? v : ~v;
             ap &= ((kHeadP >> (21 - k)) & 1u) ? v : ~v;
         }
     }
     // ay/an/ap: bit 31 - b = position 32w + b  ->  bit b
     m_sync = bit_reverse(ay) & range_mask(w, x0, xe - 38 + 1);
-    m_n1 = bit_reverse(an) & range_mask(w, x0, xe - 22 + 1);
-    m_n2 = bit_reverse(ap) & range_mask(w, x0, xe - 22 + 1);
+    if (NORMAL) {
+        m_n1 = bit_reverse(an) & range_mask(w, x0, xe - 22 + 1);
+        m_n2 = bit_reverse(ap) & range_mask(w, x0, xe - 22 + 1);
+    }
 }
 
 // match_word's sync bitmap alone (the tolerant lock needs no other)
 BS_FN uint32_t match_word_sync(const uint32_t* s, int w, int x0, int xe) {
-    const uint32_t w0 = s[w], w1 = s[w + 1], w2 = s[w + 2];
-    uint32_t ay = 0xffffffffu;
-    constexpr uint64_t seq_y = ((uint64_t)kHeadY << 16) | kTailY;
-#pragma unroll
-    for (int k = 0; k < 38; ++k) {
-        const uint32_t v = shifted_word(w0, w1, w2, k);
-        ay &= ((seq_y >> (37 - k)) & 1u) ? v : ~v;
-    }
-    return bit_reverse(ay) & range_mask(w, x0, xe - 38 + 1);
+    uint32_t m_sync = 0, none = 0;
+    match_word<false>(s, w, x0, xe, m_sync, none, none);
+    return m_sync;
 }
 
 // first set bit of bitmap m (bit x at word x>>5, bit x&31) in [a, b), or -1
@@ -188,26 +193,6 @@ BS_FN int locked_find(const uint32_t* s, const uint32_t* m_sync, const uint32_t*
     if (p2 >= 0 && (best < 0 || p2 < best)) { best = p2; type = kNorm2; }
     if (best >= 0) offs = best - bx;
     return type;
-}
-
-// One LOCKED call on a buffer of exactly one frame, [bx, bx + 510): what tetra_burst_sync_in reports for it (the rx_cb type, or -1)
-// and whether the receiver falls back to UNLOCKED behind it (tetra_burst_sync.c:105-150).  A pure function of the bitmaps: frames in
-// LOCKED steady state can be evaluated side by side, one per lane (run()'s `batch`).
-struct FrameEval { int reported; bool unlocks; };
-BS_FN FrameEval locked_frame_eval(const uint32_t* s, const uint32_t* m_sync, const uint32_t* m_n1, const uint32_t* m_n2, const uint32_t* m_any,
-                                  int bx) {
-    int offs = 0;
-    const int rc = locked_find(s, m_sync, m_n1, m_n2, m_any, bx, kTs, offs, [](const uint32_t* m, int a, int b) { return first_set(m, a, b); });
-    FrameEval e = { -1, false };
-    if (rc == kSync) {
-        if (offs == 214) e.reported = rc;
-        else e.unlocks = true;
-    } else if (rc == kNorm1 || rc == kNorm2) {
-        if (offs == 244) e.reported = rc;
-    } else {
-        e.unlocks = true;
-    }
-    return e;
 }
 
 // ---- tolerant lock --------------------------------------------------------------------------------------------------------------------
@@ -272,36 +257,90 @@ BS_FN Unlock first_unlock_bits(uint64_t pass_mask, int n, int misses_in, int max
     return Unlock{ -1, n - 1 - (63 - __builtin_clzll(pass)) };  // the misses behind the last reported frame
 }
 
-// Runs the state machine over the new bits.  emit(f, bx, type, bitnum) is called for the f-th consumed frame (buffer
-// coordinate of its first bit, the reference's rx_cb type or -1, absolute bit number of its first bit).  On return
+// ---- the two lock rules -----------------------------------------------------------------------------------------------------------------
+// What a rule says to walk():
+//   locked(s, bx, n, first)   one LOCKED call on the buffer [bx, bx + n), n >= 510: what tetra_burst_sync_in reports for its first frame
+//                             (the rx_cb type, or -1) and whether the receiver falls back to UNLOCKED behind it;
+//   literal(s, bx1, a1, xe, offs, a)   UNLOCKED with a true sync match in the misaligned-filter zone of the buffer that starts at bx1, first
+//                             call a1: the literal search's result and offset, and in `a` the call that has been evaluated.
+struct FrameEval { int reported; bool unlocks; };
+
+// The reference's rule (tetra_burst_sync.c:105-150) on the three bitmaps and their union.  On a buffer of exactly one frame it is a
+// pure function of the bitmaps: frames in LOCKED steady state can be evaluated side by side, one per lane (walk()'s `batch`).
+struct RefLock {
+    const uint32_t *m_sync, *m_n1, *m_n2, *m_any;
+    template <class First> BS_MFN FrameEval locked(const uint32_t* s, int bx, int n, First first) const {
+        int offs = 0;
+        const int rc = locked_find(s, m_sync, m_n1, m_n2, m_any, bx, n, offs, first);
+        FrameEval e = { -1, false };
+        if (rc == kSync) {
+            if (offs == 214) e.reported = rc;
+            else e.unlocks = true;
+        } else if (rc == kNorm1 || rc == kNorm2) {
+            if (offs == 244) e.reported = rc;
+        } else {
+            e.unlocks = true;
+        }
+        return e;
+    }
+    BS_MFN int literal(const uint32_t* s, int bx1, int a1, int, int& offs, int& a) const {      // call by call
+        a = a1;
+        return literal_find(s, bx1, a1 - bx1, 1u << kSync, offs);
+    }
+};
+BS_FN FrameEval locked_frame_eval(const uint32_t* s, const uint32_t* m_sync, const uint32_t* m_n1, const uint32_t* m_n2, const uint32_t* m_any,
+                                  int bx) {
+    return RefLock{ m_sync, m_n1, m_n2, m_any }.locked(s, bx, kTs, [](const uint32_t* m, int a, int b) { return first_set(m, a, b); });
+}
+
+// The tolerant rule: tolerant_frame_eval on the first 510 bits of the buffer and the channel's miss counter `misses`, carried from call
+// to call.  A batch() evaluates its frames with tolerant_frame_eval, applies first_unlock to them with the same counter and leaves it
+// as locked() does.  Only the sync bitmap is read.
+struct TolLock {
+    Tolerance tol;
+    int& misses;
+    template <class First> BS_MFN FrameEval locked(const uint32_t* s, int bx, int, First) {
+        FrameEval e = { tolerant_frame_eval(s, bx, tol), false };
+        misses = e.reported >= 0 ? 0 : misses + 1;
+        if (misses >= tol.max_miss) { e.unlocks = true; misses = 0; }
+        return e;
+    }
+    // Until the buffer is full its start stays bx1, and the calls a1, a1 + 1, ... search the same positions plus one more each: what an
+    // earlier call rejected stays rejected, so the first call that finds anything finds the first position p that passes anywhere in
+    // [bx1, lim), and it is the call a = max(a1, p + 38).  One literal search over the whole stretch stands for all of them, with the
+    // same result.  (The reference's rule evaluates such a buffer call by call -- up to 3076 literal searches of up to 4096 positions
+    // each on one wavefront, where this is one.  A flywheel that unlocks 16 frames late lands on such a buffer whenever the timing has
+    // jumped by about 300 bits.)
+    BS_MFN int literal(const uint32_t* s, int bx1, int a1, int xe, int& offs, int& a) const {
+        const int lim = xe < bx1 + kBuf ? xe : bx1 + kBuf;
+        const int rc = literal_find(s, bx1, lim - bx1, 1u << kSync, offs);
+        if (rc >= 0) a = (bx1 + offs + 38 > a1) ? bx1 + offs + 38 : a1;
+        else a = lim > a1 ? lim : a1;
+        return rc;
+    }
+};
+
+// Runs the state machine over the new bits under the rule `lock`.  emit(f, bx, type, bitnum) is called for the f-th consumed frame
+// (buffer coordinate of its first bit, the reference's rx_cb type or -1, absolute bit number of its first bit).  On return
 // st holds the new state and carry_x the coordinate of the first bit that stays buffered ([carry_x, xe) = the new bitbuf).
 // batch(bx, K, f0, abs_bx, unlocked): LOCKED steady state (the fed position a equals the buffer start bx, so every call consumes
 // exactly the next 510 bits): evaluate up to K whole frames [bx + 510 k, bx + 510 (k + 1)) and emit them as frames f0, f0 + 1, ... up to
 // and including the first one that unlocks the receiver; returns how many it consumed (0 = not taken: the serial path runs).  The
 // kernel does this one frame per lane -- ~70 dependent event steps per second of signal become two -- the host emulation in a loop.
-template <class First, class Emit, class Batch>
-BS_FN int run(State& st, const uint32_t* s, const uint32_t* m_sync, const uint32_t* m_n1, const uint32_t* m_n2, const uint32_t* m_any,
-              int n_new, int& carry_x, First first, Emit emit, Batch batch) {
+template <class Lock, class First, class Emit, class Batch>
+BS_FN int walk(State& st, const uint32_t* s, const uint32_t* m_sync, int n_new, int& carry_x, First first, Emit emit, Batch batch, Lock& lock) {
     const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
     const uint32_t abs0 = st.bitbuf_start_bitnum;               // absolute bit number of coordinate x0
     auto abs_of = [&](int x) { return abs0 + (uint32_t)(x - x0); };
     int state = st.state, bx = x0, a = kOff, frames = 0;
     uint32_t nfs = st.next_frame_start_bitnum;
 
-    auto locked_call = [&]() {                                  // tetra_burst_sync.c:105-150, buffer [bx, a)
+    auto locked_call = [&]() {                                  // buffer [bx, a)
         const int n = a - bx;
         if (n < kTs) return;
-        int offs = 0, reported = -1;
-        const int rc = locked_find(s, m_sync, m_n1, m_n2, m_any, bx, n, offs, first);
-        if (rc == kSync) {
-            if (offs == 214) reported = rc;
-            else state = kUnlocked;
-        } else if (rc == kNorm1 || rc == kNorm2) {
-            if (offs == 244) reported = rc;
-        } else {
-            state = kUnlocked;
-        }
-        emit(frames++, bx, reported, abs_of(bx));
+        const FrameEval e = lock.locked(s, bx, n, first);
+        if (e.unlocks) state = kUnlocked;
+        emit(frames++, bx, e.reported, abs_of(bx));
         bx += kTs;
         nfs += kTs;
     };
@@ -311,10 +350,9 @@ BS_FN int run(State& st, const uint32_t* s, const uint32_t* m_sync, const uint32
             const int a1 = (a + 1 > bx + 2 * kTs) ? a + 1 : bx + 2 * kTs;
             if (a1 > xe) { a = xe; break; }
             const int bx1 = (a1 - kBuf > bx) ? a1 - kBuf : bx;
-            if (first(m_sync, bx1, bx1 + 21) >= 0) {        // a true match in the misaligned-filter zone: literal call
+            if (first(m_sync, bx1, bx1 + 21) >= 0) {        // a true match in the misaligned-filter zone: literal, as the rule has it
                 int offs = 0;
-                const int rc = literal_find(s, bx1, a1 - bx1, 1u << kSync, offs);
-                a = a1;
+                const int rc = lock.literal(s, bx1, a1, xe, offs, a);
                 bx = bx1;
                 if (rc >= 0) { nfs = abs_of(bx) + (uint32_t)offs + 296u; state = kKnowFstart; }
                 continue;
@@ -363,97 +401,97 @@ BS_FN int run(State& st, const uint32_t* s, const uint32_t* m_sync, const uint32
     return frames;
 }
 
-// The tolerant lock.  The same walk over the events with the tolerant LOCKED call and ONE shortcut in UNLOCKED that gives the same result
-// (the literal calls on a buffer whose start does not move, below); `misses` is the channel's miss counter, carried from
-// call to call.  batch() evaluates its frames with tolerant_frame_eval, applies first_unlock to them with the same counter and leaves
-// it as the rule does.  Only the sync bitmap is read.  (A copy of run(), not a parameter of it: the reference rule's kernels are held
-// instruction for instruction to what they were, and the compiler schedules run() differently as soon as it carries a second policy.)
+// walk() under the reference's rule, and under the tolerant one
+template <class First, class Emit, class Batch>
+BS_FN int run(State& st, const uint32_t* s, const uint32_t* m_sync, const uint32_t* m_n1, const uint32_t* m_n2, const uint32_t* m_any,
+              int n_new, int& carry_x, First first, Emit emit, Batch batch) {
+    RefLock lock{ m_sync, m_n1, m_n2, m_any };
+    return walk(st, s, m_sync, n_new, carry_x, first, emit, batch, lock);
+}
 template <class First, class Emit, class Batch>
 BS_FN int run_tolerant(State& st, const uint32_t* s, const uint32_t* m_sync, int n_new, int& carry_x, First first, Emit emit, Batch batch,
                        const Tolerance& tol, int& misses) {
-    const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
-    const uint32_t abs0 = st.bitbuf_start_bitnum;               // absolute bit number of coordinate x0
-    auto abs_of = [&](int x) { return abs0 + (uint32_t)(x - x0); };
-    int state = st.state, bx = x0, a = kOff, frames = 0;
-    uint32_t nfs = st.next_frame_start_bitnum;
+    TolLock lock{ tol, misses };
+    return walk(st, s, m_sync, n_new, carry_x, first, emit, batch, lock);
+}
 
-    auto locked_call = [&]() {                                  // the tolerant LOCKED call on the first 510 bits of the buffer [bx, a)
-        if (a - bx < kTs) return;
-        const int reported = tolerant_frame_eval(s, bx, tol);
-        misses = reported >= 0 ? 0 : misses + 1;
-        if (misses >= tol.max_miss) { state = kUnlocked; misses = 0; }
-        emit(frames++, bx, reported, abs_of(bx));
-        bx += kTs;
-        nfs += kTs;
-    };
+// ---- steps 1 and 4 of a channel's workgroup: the lane's share, thread tid of kThreads ----------------------------------------------------
+constexpr int kThreads = 256;       // four wavefronts per channel for the byte work, one of them walks the state machine
+constexpr int kFrameWords = 16, kFrameStride = 512;             // TETRA_FRAME_WORDS, TETRA_FRAME_STRIDE
+struct FrameRec { int bx; int type; uint32_t bitnum; };         // a consumed frame, as emit() gets it
 
-    while (a < xe) {
-        if (state == kUnlocked) {
-            const int a1 = (a + 1 > bx + 2 * kTs) ? a + 1 : bx + 2 * kTs;
-            if (a1 > xe) { a = xe; break; }
-            const int bx1 = (a1 - kBuf > bx) ? a1 - kBuf : bx;
-            if (first(m_sync, bx1, bx1 + 21) >= 0) {        // a true match in the misaligned-filter zone: literal calls
-                // Until the buffer is full its start stays bx1, and the calls a1, a1 + 1, ... search the same positions plus one more each:
-                // what an earlier call rejected stays rejected, so the first call that finds anything finds the first position p that
-                // passes anywhere in [bx1, lim), and it is the call a = max(a1, p + 38).  One literal search over the whole stretch
-                // stands for all of them, with the same result.  (run() evaluates such a buffer call by call -- up to 3076 literal searches
-                // of up to 4096 positions each on one wavefront, where this is one.  A flywheel that unlocks 16 frames late lands on such a
-                // buffer whenever the timing has jumped by about 300 bits; run() has the same path and is left as it is.)
-                const int lim = xe < bx1 + kBuf ? xe : bx1 + kBuf;
-                int offs = 0;
-                const int rc = literal_find(s, bx1, lim - bx1, 1u << kSync, offs);
-                bx = bx1;
-                if (rc >= 0) {
-                    a = (bx1 + offs + 38 > a1) ? bx1 + offs + 38 : a1;
-                    nfs = abs_of(bx) + (uint32_t)offs + 296u;
-                    state = kKnowFstart;
-                } else {
-                    a = lim > a1 ? lim : a1;
-                }
-                continue;
-            }
-            const int p = first(m_sync, bx1 + 21, xe - 38 + 1);
-            if (p < 0) { a = xe; break; }
-            a = (p + 38 > a1) ? p + 38 : a1;
-            bx = (a - kBuf > bx) ? a - kBuf : bx;
-            nfs = abs_of(p) + 296u;
-            state = kKnowFstart;
-        } else if (state == kKnowFstart) {
-            const int nfs_x = x0 + (int)(int32_t)(nfs - abs0);
-            const int at = (a + 1 > nfs_x) ? a + 1 : nfs_x;
-            if (at > xe) { a = xe; break; }
-            a = at;
-            bx = nfs_x;
-            nfs += kTs;
-            state = kLocked;
-            locked_call();
+struct alignas(16) U4 { uint32_t x, y, z, w; };
+BS_FN U4 load16(const uint8_t* p) {                             // p is 16-byte aligned
+#if defined(__HIPCC__) && !defined(TETRA_HOST_EMUL)
+    return *reinterpret_cast<const U4*>(p);
+#else
+    U4 v;
+    __builtin_memcpy(&v, __builtin_assume_aligned(p, 16), 16);
+    return v;
+#endif
+}
+
+// word w of the packed stream: the carried buffer cbuf (x0 .. kOff, one byte per bit) followed by n_new bytes of the row `in`; only bit
+// 0 of a byte counts.  The new bits start word-aligned: 32 bytes -> one word with two 16-byte loads where the row's address allows them
+// and one multiply per 8 bytes (the scan kernel's trick).
+BS_FN uint32_t stream_word(int w, int x0, int n_new, const uint8_t* cbuf, const uint8_t* in) {
+    uint32_t v = 0;
+    const int xb = 32 * w;
+    if (xb + 32 > x0 && xb < kOff) {                             // carried bits: byte by byte (at most 128 words)
+        for (int b = 0; b < 32; ++b) {
+            const int x = xb + b;
+            if (x >= x0 && x < kOff) v |= (uint32_t)(cbuf[x - x0] & 1u) << (31 - b);
+        }
+    } else if (xb >= kOff && xb < kOff + n_new) {
+        const int j = xb - kOff;
+        if (j + 32 <= n_new && (((uintptr_t)(in + j)) & 15) == 0) {
+            const U4 lo = load16(in + j), hi = load16(in + j + 16);
+            const unsigned long long q[4] = { ((unsigned long long)lo.y << 32) | lo.x, ((unsigned long long)lo.w << 32) | lo.z,
+                                              ((unsigned long long)hi.y << 32) | hi.x, ((unsigned long long)hi.w << 32) | hi.z };
+#pragma unroll
+            for (int z = 0; z < 4; ++z)      // 8 bytes -> 8 bits, first byte = MSB: byte i of x * 0x8040201008040201 reaches bit 63 - i
+                v |= (uint32_t)(((q[z] & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56) << (24 - 8 * z);
         } else {
-            if (a == bx && xe - bx >= 2 * kTs) {
-                bool unlocked = false;
-                const int done = batch(bx, (xe - bx) / kTs, frames, abs_of(bx), unlocked);
-                if (done > 0) {                                 // `done` LOCKED calls of exactly one frame each, a = bx + 510 after every one
-                    frames += done;
-                    bx += kTs * done;
-                    nfs += (uint32_t)(kTs * done);
-                    a = bx;
-                    if (unlocked) state = kUnlocked;
-                    continue;
-                }
-            }
-            const int an = (a + 1 > bx + kTs) ? a + 1 : bx + kTs;
-            if (an > xe) { a = xe; break; }
-            a = an;
-            bx = (a - kBuf > bx) ? a - kBuf : bx;
-            locked_call();
+            for (int b = 0; b < 32; ++b)
+                if (j + b < n_new) v |= (uint32_t)(in[j + b] & 1u) << (31 - b);
         }
     }
-    bx = (a - kBuf > bx) ? a - kBuf : bx;                       // make_bitbuf_space of the calls skipped at the end
-    st.state = state;
-    st.bits_in_buf = (uint32_t)(xe - bx);
-    st.bitbuf_start_bitnum = abs_of(bx);
-    st.next_frame_start_bitnum = nfs;
-    carry_x = bx;
-    return frames;
+    return v;
+}
+BS_FN void stage_thread(int tid, uint32_t* s, int words, int x0, int n_new, const uint8_t* cbuf, const uint8_t* in) {
+    for (int w = tid; w < words; w += kThreads) s[w] = stream_word(w, x0, n_new, cbuf, in);
+}
+
+// word w of the packed frame that starts at bx (first bit = most significant; word 15 holds bits 480 .. 509 in its top 30 bits)
+BS_FN uint32_t frame_word(const uint32_t* s, int bx, int w) {
+    const uint32_t v = window(s, bx + 32 * w, 32);
+    return w == kFrameWords - 1 ? v & 0xfffffffcu : v;          // bits 510, 511 of the row are not the frame's
+}
+// dword d of its byte form: four bits as four bytes, zero from bit 510 on
+BS_FN uint32_t frame_dword(const uint32_t* s, int bx, int d) {
+    uint32_t nib = window(s, bx + 4 * d, 4);                    // first bit = MSB
+    if (4 * d + 4 > kTs) nib &= (4 * d >= kTs) ? 0u : (0xfu << (4 * d + 4 - kTs)) & 0xfu;
+    return ((nib >> 3) & 1u) | (((nib >> 2) & 1u) << 8) | (((nib >> 1) & 1u) << 16) | ((nib & 1u) << 24);
+}
+// The channel's outputs from the frame list rec[0 .. nf) of the walk: frames ([max_frames][16] words, PACKED, or [max_frames][512]
+// bytes), types and bit numbers of all max_frames slots (none_type behind the list), and the new carried buffer [carry_x, xe).
+template <bool PACKED>
+BS_FN void write_thread(int tid, const uint32_t* s, const FrameRec* rec, int nf, int max_frames, int none_type, int carry_x, int xe,
+                        uint8_t* frames, int32_t* frame_type, uint32_t* frame_bitnum, uint8_t* cbuf) {
+    if (PACKED) {
+        uint32_t* pout = reinterpret_cast<uint32_t*>(frames);
+        for (int i = tid; i < nf * kFrameWords; i += kThreads) pout[i] = frame_word(s, rec[i / kFrameWords].bx, i % kFrameWords);
+    }
+    for (int f = 0; !PACKED && f < nf; ++f) {
+        const int bx = rec[f].bx;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(frames + (size_t)f * kFrameStride);
+        for (int d = tid; d < kFrameStride / 4; d += kThreads) dst[d] = frame_dword(s, bx, d);
+    }
+    for (int f = tid; f < max_frames; f += kThreads) {
+        frame_type[f] = f < nf ? rec[f].type : none_type;
+        frame_bitnum[f] = f < nf ? rec[f].bitnum : 0u;
+    }
+    for (int i = tid; i < xe - carry_x; i += kThreads) cbuf[i] = (uint8_t)get_bit(s, carry_x + i);
 }
 
 }  // namespace bsync_core

@@ -1,15 +1,19 @@
 // tetra_burst_sync.hip -- batched burst synchroniser + burst demultiplexer (include/tetra_burst_sync.h).
 //
-// k_burst_sync: one workgroup of four wavefronts per channel (the byte work of steps 1, 2 and 4 on all 256 lanes; step 3 on one wave).
+// k_burst_sync / k_burst_sync_tol (the reference's lock rule / the tolerant one, include/ext/tetra_sync_tol.h; one body,
+// burst_sync_workgroup, with the rule as a parameter): one workgroup of four wavefronts per channel (the byte work of steps 1, 2 and 4
+// on all 256 lanes; step 3 on one wave).
 //   1. the channel's stream of this call -- carried buffer (<= 4096 bits, one byte per bit in HBM) followed by the new
 //      bits -- is packed 32 bits per word into LDS; the new bits start word-aligned, 32 bytes -> one word per lane-step
 //      with 16-byte loads and one multiply per 8 bytes (the scan kernel's trick);
-//   2. three match bitmaps (sync / normal 1 / normal 2 training sequence present at x) are built 32 positions per lane-step;
+//   2. the rule's match bitmaps (sync / normal 1 / normal 2 training sequence present at x and their union, or sync alone) are built
+//      32 positions per lane-step;
 //   3. the wave walks the event-driven state machine of bsync_core.hpp (about 70 events per second of signal) in lock
 //      step; its "first set bit in [a, b)" searches over the bitmaps are wave-cooperative (one word per lane + ballot);
 //      the consumed frames are listed in LDS;
 //   4. all lanes expand the listed frames to one byte per bit with coalesced dword stores, and write the new carried
 //      buffer and the state.
+// Steps 1 and 4 and the walk are lane code in bsync_core.hpp, which the host emulation runs too.
 // Byte work: every input byte is read from HBM once, every output byte written once.
 // k_burst_demux: one thread per output dword; a gather with the offsets of tetra_burst_rx_cb().
 #include <hip/hip_runtime.h>
@@ -27,31 +31,91 @@ namespace {
 using namespace bsync_core;
 
 constexpr int kLanes = 64;
-constexpr int kThreadsBS = 256;       // k_burst_sync: four wavefronts per channel for the byte work, one of them walks the state machine
+constexpr int kThreadsBS = kThreads;  // k_burst_sync: four wavefronts per channel for the byte work, one of them walks the state machine
 constexpr int kMaxBitsLimit = 262144;
+static_assert(kFrameWords == TETRA_FRAME_WORDS && kFrameStride == TETRA_FRAME_STRIDE, "frame layout");
 
-struct FrameRec { int bx; int type; uint32_t bitnum; };
+// walk()'s `first` for a wavefront in lock step: one word per lane + ballot
+__device__ __forceinline__ int first_wave(const uint32_t* m, int a, int b, int lane) {
+    if (a >= b) return -1;
+    const int w0 = a >> 5, w1 = (b - 1) >> 5;
+    for (int base = w0; base <= w1; base += kLanes) {
+        const int w = base + lane;
+        uint32_t v = (w <= w1) ? m[w] : 0u;
+        if (w == w0) v &= 0xffffffffu << (a & 31);
+        if (w == w1 && (b & 31) != 0) v &= (1u << (b & 31)) - 1u;
+        const unsigned long long hit = __ballot(v != 0u);
+        if (hit) {
+            const int l = __builtin_ctzll(hit);
+            return 32 * (base + l) + __builtin_ctz(__shfl(v, l));
+        }
+    }
+    return -1;
+}
 
+// What a lock rule says to the workgroup: how many bitmaps lie behind the stream in LDS (m [kMaps][words], the sync bitmap first) and
+// how word w of them is built; where the channel's rule state is loaded and stored and its policy object for walk(); and one
+// round of the LOCKED batch -- the lane's frame [bx, bx + 510) evaluated if `active` (lanes 0 .. here - 1), -> what it reports, and
+// the index of the lane behind whose frame the receiver unlocks, or -1.
+struct RefRule {          // the reference's rule: sync / normal 1 / normal 2 bitmaps and their union
+    static constexpr int kMaps = 4;
+    __device__ void map_word(const uint32_t* s, uint32_t* m, int words, int w, bool inside, int x0, int xe) const {
+        uint32_t a = 0, b = 0, c = 0;
+        if (inside) match_word(s, w, x0, xe, a, b, c);
+        m[w] = a;
+        m[words + w] = b;
+        m[2 * words + w] = c;
+        m[3 * words + w] = a | b | c;
+    }
+    __device__ int load(int) const { return 0; }
+    __device__ void store(int, int) const {}
+    __device__ RefLock lock(const uint32_t* m, int words, int&) const { return RefLock{ m, m + words, m + 2 * words, m + 3 * words }; }
+    __device__ int round(RefLock& lock, const uint32_t* s, int bx, bool active, int, int& reported) const {
+        FrameEval e = { -1, false };
+        if (active) e = locked_frame_eval(s, lock.m_sync, lock.m_n1, lock.m_n2, lock.m_any, bx);
+        reported = e.reported;
+        const unsigned long long um = __ballot(e.unlocks);
+        return um ? __builtin_ctzll(um) : -1;
+    }
+};
+// The tolerant lock (include/ext/tetra_sync_tol.h): the sync bitmap only; a lane evaluates the three windows of its frame
+// (tolerant_frame_eval) and the consecutive-miss rule runs over the ballot of the reported frames (first_unlock_bits).  miss [C]: the
+// channels' miss counters beside their State.
+struct TolRule {
+    static constexpr int kMaps = 1;
+    Tolerance tol;
+    int32_t* miss;
+    __device__ void map_word(const uint32_t* s, uint32_t* m, int, int w, bool inside, int x0, int xe) const {
+        m[w] = inside ? match_word_sync(s, w, x0, xe) : 0u;
+    }
+    __device__ int load(int ch) const { return miss[ch]; }
+    __device__ void store(int ch, int misses) const { miss[ch] = misses; }
+    __device__ TolLock lock(const uint32_t*, int, int& misses) const { return TolLock{ tol, misses }; }
+    __device__ int round(TolLock& lock, const uint32_t* s, int bx, bool active, int here, int& reported) const {
+        reported = active ? tolerant_frame_eval(s, bx, lock.tol) : -1;
+        const Unlock u = first_unlock_bits(__ballot(reported >= 0), here, lock.misses, lock.tol.max_miss);
+        lock.misses = u.misses;
+        return u.index;
+    }
+};
+
+// One workgroup of four wavefronts per channel (steps 1 .. 4 of the head of this file).
 // PACKED: the consumed frames leave as 16 words of 32 bits (first bit = most significant; word 15 holds bits 480 .. 509 in its top 30
 // bits) instead of 512 bytes: an eighth of the bytes for the demultiplexer behind (tetra_bsync_process_packed_device).
-template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
-                                                       int max_bits, int max_frames, State* __restrict__ states,
-                                                       uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
-                                                       int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
-                                                       int* __restrict__ n_frames) {
+template <bool PACKED, class Rule>
+__device__ __forceinline__ void burst_sync_workgroup(const Rule rule, const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
+                                                     int max_bits, int max_frames, State* __restrict__ states, uint8_t* __restrict__ carry,
+                                                     uint8_t* __restrict__ frames, int* __restrict__ frame_type,
+                                                     uint32_t* __restrict__ frame_bitnum, int* __restrict__ n_frames) {
     extern __shared__ uint32_t lds[];
     const int words = stream_words(max_bits);
     uint32_t* s = lds;
-    uint32_t* m_sync = s + words;
-    uint32_t* m_n1 = m_sync + words;
-    uint32_t* m_n2 = m_n1 + words;
-    uint32_t* m_any = m_n2 + words;
-    FrameRec* rec = reinterpret_cast<FrameRec*>(m_any + words);
+    uint32_t* maps = s + words;
+    FrameRec* rec = reinterpret_cast<FrameRec*>(maps + Rule::kMaps * words);
     __shared__ int sh_nframes, sh_carry_x;
     __shared__ State sh_state;
 
     const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & (kLanes - 1);
-    const uint8_t* in = bits + (size_t)ch * bits_stride;
     uint8_t* cbuf = carry + (size_t)ch * kBuf;
     State st = states[ch];
     int n_new = n_bits[ch];
@@ -60,82 +124,38 @@ template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_syn
     const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
 
     // 1. pack the stream
-    for (int w = tid; w < words; w += kThreadsBS) {
-        uint32_t v = 0;
-        const int xb = 32 * w;
-        if (xb + 32 > x0 && xb < kOff) {                         // carried bits: byte by byte (at most 128 words)
-            for (int b = 0; b < 32; ++b) {
-                const int x = xb + b;
-                if (x >= x0 && x < kOff) v |= (uint32_t)(cbuf[x - x0] & 1u) << (31 - b);
-            }
-        } else if (xb >= kOff && xb < xe) {
-            const int j = xb - kOff;
-            if (j + 32 <= n_new && (((uintptr_t)(in + j)) & 15) == 0) {
-                const uint4 lo = *reinterpret_cast<const uint4*>(in + j);
-                const uint4 hi = *reinterpret_cast<const uint4*>(in + j + 16);
-                const unsigned long long q[4] = { ((unsigned long long)lo.y << 32) | lo.x, ((unsigned long long)lo.w << 32) | lo.z,
-                                                  ((unsigned long long)hi.y << 32) | hi.x, ((unsigned long long)hi.w << 32) | hi.z };
-#pragma unroll
-                for (int z = 0; z < 4; ++z)      // 8 bytes -> 8 bits, first byte = MSB: byte i of x * 0x8040201008040201 reaches bit 63 - i
-                    v |= (uint32_t)(((q[z] & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56) << (24 - 8 * z);
-            } else {
-                for (int b = 0; b < 32; ++b)
-                    if (j + b < n_new) v |= (uint32_t)(in[j + b] & 1u) << (31 - b);
-            }
-        }
-        s[w] = v;
-    }
+    stage_thread(tid, s, words, x0, n_new, cbuf, bits + (size_t)ch * bits_stride);
     __syncthreads();
 
     // 2. match bitmaps
-    for (int w = tid; w < words; w += kThreadsBS) {
-        uint32_t a = 0, b = 0, c = 0;
-        if (w + 2 < words && 32 * w + 32 > x0 && 32 * w < xe) match_word(s, w, x0, xe, a, b, c);
-        m_sync[w] = a;
-        m_n1[w] = b;
-        m_n2[w] = c;
-        m_any[w] = a | b | c;
-    }
+    for (int w = tid; w < words; w += kThreadsBS) rule.map_word(s, maps, words, w, w + 2 < words && 32 * w + 32 > x0 && 32 * w < xe, x0, xe);
     __syncthreads();
 
     // 3. state machine: all lanes in lock step (uniform control flow); the bitmap searches are wave-cooperative
-    auto first_wave = [&](const uint32_t* m, int a, int b) -> int {
-        if (a >= b) return -1;
-        const int w0 = a >> 5, w1 = (b - 1) >> 5;
-        for (int base = w0; base <= w1; base += kLanes) {
-            const int w = base + lane;
-            uint32_t v = (w <= w1) ? m[w] : 0u;
-            if (w == w0) v &= 0xffffffffu << (a & 31);
-            if (w == w1 && (b & 31) != 0) v &= (1u << (b & 31)) - 1u;
-            const unsigned long long hit = __ballot(v != 0u);
-            if (hit) {
-                const int l = __builtin_ctzll(hit);
-                return 32 * (base + l) + __builtin_ctz(__shfl(v, l));
-            }
-        }
-        return -1;
-    };
     if (tid < kLanes) {      // (one wavefront walks the events; the other three join again for the byte work behind the barrier)
         int carry_x = 0;
+        int rule_state = rule.load(ch);
+        auto lock = rule.lock(maps, words, rule_state);
         // LOCKED steady state: one frame per lane, 64 per round, up to and including the first frame that unlocks the receiver
         auto batch = [&](int bx, int K, int f0, uint32_t abs_bx, bool& unlocked) -> int {
             int done = 0;
             while (done < K) {
                 const int k = done + lane, here = K - done < kLanes ? K - done : kLanes;
-                FrameEval e = { -1, false };
-                if (lane < here) e = locked_frame_eval(s, m_sync, m_n1, m_n2, m_any, bx + kTs * k);
-                const unsigned long long um = __ballot(e.unlocks);
-                const int take = um ? __builtin_ctzll(um) + 1 : here;
-                if (lane < take && f0 + k < max_frames) rec[f0 + k] = FrameRec{ bx + kTs * k, e.reported, abs_bx + (uint32_t)(kTs * k) };
+                int reported;
+                const int stop = rule.round(lock, s, bx + kTs * k, lane < here, here, reported);
+                const int take = stop >= 0 ? stop + 1 : here;
+                if (lane < take && f0 + k < max_frames) rec[f0 + k] = FrameRec{ bx + kTs * k, reported, abs_bx + (uint32_t)(kTs * k) };
                 done += take;
-                if (um) { unlocked = true; break; }
+                if (stop >= 0) { unlocked = true; break; }
             }
             return done;
         };
-        const int nrun = run(st, s, m_sync, m_n1, m_n2, m_any, n_new, carry_x, first_wave, [&](int f, int bx, int type, uint32_t bitnum) {
-            if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
-        }, batch);
+        const int nrun = walk(st, s, maps, n_new, carry_x, [&](const uint32_t* m, int a, int b) { return first_wave(m, a, b, lane); },
+                              [&](int f, int bx, int type, uint32_t bitnum) {
+                                  if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
+                              }, batch, lock);
         if (lane == 0) {
+            rule.store(ch, rule_state);
             sh_nframes = nrun < max_frames ? nrun : max_frames;
             sh_carry_x = carry_x;
             sh_state = st;
@@ -145,177 +165,28 @@ template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_syn
 
     // 4. frames, carry, state
     const int nf = sh_nframes;
-    if (PACKED) {
-        uint32_t* pout = reinterpret_cast<uint32_t*>(frames) + (size_t)ch * max_frames * TETRA_FRAME_WORDS;
-        for (int i = tid; i < nf * TETRA_FRAME_WORDS; i += kThreadsBS) {
-            const int f = i / TETRA_FRAME_WORDS, w = i % TETRA_FRAME_WORDS;
-            uint32_t v = window(s, rec[f].bx + 32 * w, 32);
-            if (w == TETRA_FRAME_WORDS - 1) v &= 0xfffffffcu;              // bits 510, 511 of the row are not the frame's
-            pout[i] = v;
-        }
-    }
-    uint8_t* fout = frames + (size_t)ch * max_frames * TETRA_FRAME_STRIDE;
-    for (int f = 0; !PACKED && f < nf; ++f) {
-        const int bx = rec[f].bx;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(fout + (size_t)f * TETRA_FRAME_STRIDE);
-        for (int d = tid; d < TETRA_FRAME_STRIDE / 4; d += kThreadsBS) {
-            uint32_t nib = window(s, bx + 4 * d, 4);                       // first bit = MSB
-            if (4 * d + 4 > kTs) nib &= (4 * d >= kTs) ? 0u : (0xfu << (4 * d + 4 - kTs)) & 0xfu;
-            dst[d] = ((nib >> 3) & 1u) | (((nib >> 2) & 1u) << 8) | (((nib >> 1) & 1u) << 16) | ((nib & 1u) << 24);
-        }
-    }
-    for (int f = tid; f < max_frames; f += kThreadsBS) {
-        frame_type[(size_t)ch * max_frames + f] = f < nf ? rec[f].type : TETRA_FRAME_NONE;
-        frame_bitnum[(size_t)ch * max_frames + f] = f < nf ? rec[f].bitnum : 0u;
-    }
-    const int cx = sh_carry_x, nc = xe - cx;
-    for (int i = tid; i < nc; i += kThreadsBS) cbuf[i] = (uint8_t)get_bit(s, cx + i);
+    write_thread<PACKED>(tid, s, rec, nf, max_frames, TETRA_FRAME_NONE, sh_carry_x, xe,
+                         frames + (size_t)ch * max_frames * (PACKED ? TETRA_FRAME_WORDS * 4 : TETRA_FRAME_STRIDE),
+                         frame_type + (size_t)ch * max_frames, frame_bitnum + (size_t)ch * max_frames, cbuf);
     if (tid == 0) {
         states[ch] = sh_state;
         n_frames[ch] = nf;
     }
 }
 
-// k_burst_sync under the tolerant lock (include/ext/tetra_sync_tol.h): steps 1 and 4 as above; step 2 builds the sync bitmap only (LDS:
-// stream, one bitmap, frame list); in step 3 the LOCKED batch evaluates the three windows of its frame per lane (tolerant_frame_eval)
-// and the consecutive-miss rule runs over the ballot of the reported frames (first_unlock_bits).  miss [C]: the channels' miss
-// counters beside their State.  A kernel of its own: the reference rule's kernel above is held instruction for instruction.
+template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
+                                                       int max_bits, int max_frames, State* __restrict__ states,
+                                                       uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
+                                                       int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
+                                                       int* __restrict__ n_frames) {
+    burst_sync_workgroup<PACKED>(RefRule{}, bits, bits_stride, n_bits, max_bits, max_frames, states, carry, frames, frame_type, frame_bitnum, n_frames);
+}
 template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync_tol(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
                                                        int max_bits, int max_frames, State* __restrict__ states,
                                                        uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
                                                        int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
                                                        int* __restrict__ n_frames, const Tolerance tol, int32_t* __restrict__ miss) {
-    extern __shared__ uint32_t lds[];
-    __shared__ int sh_nframes, sh_carry_x;
-    __shared__ State sh_state;
-    const int words = stream_words(max_bits);
-    uint32_t* s = lds;
-    uint32_t* m_sync = s + words;
-    FrameRec* rec = reinterpret_cast<FrameRec*>(m_sync + words);
-
-    const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & (kLanes - 1);
-    const uint8_t* in = bits + (size_t)ch * bits_stride;
-    uint8_t* cbuf = carry + (size_t)ch * kBuf;
-    State st = states[ch];
-    int n_new = n_bits[ch];
-    n_new = n_new < 0 ? 0 : (n_new > max_bits ? max_bits : n_new);
-    n_new = n_new > bits_stride ? bits_stride : n_new;         // a poisoned count never reads into the next channel's row
-    const int x0 = kOff - (int)st.bits_in_buf, xe = kOff + n_new;
-
-    // 1. pack the stream
-    for (int w = tid; w < words; w += kThreadsBS) {
-        uint32_t v = 0;
-        const int xb = 32 * w;
-        if (xb + 32 > x0 && xb < kOff) {                         // carried bits: byte by byte (at most 128 words)
-            for (int b = 0; b < 32; ++b) {
-                const int x = xb + b;
-                if (x >= x0 && x < kOff) v |= (uint32_t)(cbuf[x - x0] & 1u) << (31 - b);
-            }
-        } else if (xb >= kOff && xb < xe) {
-            const int j = xb - kOff;
-            if (j + 32 <= n_new && (((uintptr_t)(in + j)) & 15) == 0) {
-                const uint4 lo = *reinterpret_cast<const uint4*>(in + j);
-                const uint4 hi = *reinterpret_cast<const uint4*>(in + j + 16);
-                const unsigned long long q[4] = { ((unsigned long long)lo.y << 32) | lo.x, ((unsigned long long)lo.w << 32) | lo.z,
-                                                  ((unsigned long long)hi.y << 32) | hi.x, ((unsigned long long)hi.w << 32) | hi.z };
-#pragma unroll
-                for (int z = 0; z < 4; ++z)      // 8 bytes -> 8 bits, first byte = MSB: byte i of x * 0x8040201008040201 reaches bit 63 - i
-                    v |= (uint32_t)(((q[z] & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56) << (24 - 8 * z);
-            } else {
-                for (int b = 0; b < 32; ++b)
-                    if (j + b < n_new) v |= (uint32_t)(in[j + b] & 1u) << (31 - b);
-            }
-        }
-        s[w] = v;
-    }
-    __syncthreads();
-
-    // 2. the sync bitmap
-    for (int w = tid; w < words; w += kThreadsBS) {
-        m_sync[w] = (w + 2 < words && 32 * w + 32 > x0 && 32 * w < xe) ? match_word_sync(s, w, x0, xe) : 0u;
-    }
-    __syncthreads();
-
-    // 3. state machine: all lanes in lock step (uniform control flow); the bitmap searches are wave-cooperative
-    auto first_wave = [&](const uint32_t* m, int a, int b) -> int {
-        if (a >= b) return -1;
-        const int w0 = a >> 5, w1 = (b - 1) >> 5;
-        for (int base = w0; base <= w1; base += kLanes) {
-            const int w = base + lane;
-            uint32_t v = (w <= w1) ? m[w] : 0u;
-            if (w == w0) v &= 0xffffffffu << (a & 31);
-            if (w == w1 && (b & 31) != 0) v &= (1u << (b & 31)) - 1u;
-            const unsigned long long hit = __ballot(v != 0u);
-            if (hit) {
-                const int l = __builtin_ctzll(hit);
-                return 32 * (base + l) + __builtin_ctz(__shfl(v, l));
-            }
-        }
-        return -1;
-    };
-    if (tid < kLanes) {      // (one wavefront walks the events; the other three join again for the byte work behind the barrier)
-        int carry_x = 0;
-        auto emit = [&](int f, int bx, int type, uint32_t bitnum) {
-            if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
-        };
-        int misses = miss[ch];
-        // LOCKED steady state: one frame per lane, 64 per round; the ballot of the reported frames decides where the consecutive-miss rule unlocks
-        auto batch = [&](int bx, int K, int f0, uint32_t abs_bx, bool& unlocked) -> int {
-            int done = 0;
-            while (done < K) {
-                const int k = done + lane, here = K - done < kLanes ? K - done : kLanes;
-                int reported = -1;
-                if (lane < here) reported = tolerant_frame_eval(s, bx + kTs * k, tol);
-                const Unlock u = first_unlock_bits(__ballot(reported >= 0), here, misses, tol.max_miss);
-                const int take = u.index >= 0 ? u.index + 1 : here;
-                if (lane < take && f0 + k < max_frames) rec[f0 + k] = FrameRec{ bx + kTs * k, reported, abs_bx + (uint32_t)(kTs * k) };
-                misses = u.misses;
-                done += take;
-                if (u.index >= 0) { unlocked = true; break; }
-            }
-            return done;
-        };
-        const int nrun = run_tolerant(st, s, m_sync, n_new, carry_x, first_wave, emit, batch, tol, misses);
-        if (lane == 0) {
-            miss[ch] = misses;
-            sh_nframes = nrun < max_frames ? nrun : max_frames;
-            sh_carry_x = carry_x;
-            sh_state = st;
-        }
-    }
-    __syncthreads();
-
-    // 4. frames, carry, state
-    const int nf = sh_nframes;
-    if (PACKED) {
-        uint32_t* pout = reinterpret_cast<uint32_t*>(frames) + (size_t)ch * max_frames * TETRA_FRAME_WORDS;
-        for (int i = tid; i < nf * TETRA_FRAME_WORDS; i += kThreadsBS) {
-            const int f = i / TETRA_FRAME_WORDS, w = i % TETRA_FRAME_WORDS;
-            uint32_t v = window(s, rec[f].bx + 32 * w, 32);
-            if (w == TETRA_FRAME_WORDS - 1) v &= 0xfffffffcu;              // bits 510, 511 of the row are not the frame's
-            pout[i] = v;
-        }
-    }
-    uint8_t* fout = frames + (size_t)ch * max_frames * TETRA_FRAME_STRIDE;
-    for (int f = 0; !PACKED && f < nf; ++f) {
-        const int bx = rec[f].bx;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(fout + (size_t)f * TETRA_FRAME_STRIDE);
-        for (int d = tid; d < TETRA_FRAME_STRIDE / 4; d += kThreadsBS) {
-            uint32_t nib = window(s, bx + 4 * d, 4);                       // first bit = MSB
-            if (4 * d + 4 > kTs) nib &= (4 * d >= kTs) ? 0u : (0xfu << (4 * d + 4 - kTs)) & 0xfu;
-            dst[d] = ((nib >> 3) & 1u) | (((nib >> 2) & 1u) << 8) | (((nib >> 1) & 1u) << 16) | ((nib & 1u) << 24);
-        }
-    }
-    for (int f = tid; f < max_frames; f += kThreadsBS) {
-        frame_type[(size_t)ch * max_frames + f] = f < nf ? rec[f].type : TETRA_FRAME_NONE;
-        frame_bitnum[(size_t)ch * max_frames + f] = f < nf ? rec[f].bitnum : 0u;
-    }
-    const int cx = sh_carry_x, nc = xe - cx;
-    for (int i = tid; i < nc; i += kThreadsBS) cbuf[i] = (uint8_t)get_bit(s, cx + i);
-    if (tid == 0) {
-        states[ch] = sh_state;
-        n_frames[ch] = nf;
-    }
+    burst_sync_workgroup<PACKED>(TolRule{ tol, miss }, bits, bits_stride, n_bits, max_bits, max_frames, states, carry, frames, frame_type, frame_bitnum, n_frames);
 }
 
 using demux_core::Pieces;
@@ -399,9 +270,8 @@ template <bool GATHER> __global__ __launch_bounds__(256) void k_demux_rows(const
     demux_core::rows_thread<GATHER>(blockIdx.x, threadIdx.x, frames, frame_type, row_frame, have, lut, row_u, rows_per_wave, inv_row_u, rows, valid);
 }
 
-size_t lds_bytes(int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * 5 * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
-// the tolerant lock: stream and sync bitmap only
-size_t lds_bytes_tol(int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * 2 * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
+// the stream, the rule's bitmaps (RefRule::kMaps / TolRule::kMaps) and the frame list
+size_t lds_bytes(int maps, int max_bits, int max_frames) { return (size_t)stream_words(max_bits) * (1 + maps) * sizeof(uint32_t) + (size_t)max_frames * sizeof(FrameRec); }
 
 }  // namespace
 
@@ -426,24 +296,19 @@ int tetra_bsync_create(int n_channels, int max_bits, int device, tetra_bsync_t**
     if (!g.ok) return TETRA_ERR_HIP;
     if (device < 0 && hipGetDevice(&device) != hipSuccess) return TETRA_ERR_HIP;
     tetra_bsync* h = new tetra_bsync{ n_channels, max_bits, (kBuf + max_bits) / kTs + 2, device };
-    if (lds_bytes(max_bits, h->max_frames) > 160 * 1024 - 64) { delete h; return TETRA_ERR_UNSUPPORTED; }
+    if (lds_bytes(RefRule::kMaps, max_bits, h->max_frames) > 160 * 1024 - 64) { delete h; return TETRA_ERR_UNSUPPORTED; }
     if (h->d_state.reserve(sizeof(State) * n_channels) != hipSuccess || h->d_carry.reserve((size_t)kBuf * n_channels) != hipSuccess) {
         delete h;
         return TETRA_ERR_NOMEM;
     }
     // the attribute belongs to the kernel, not to the handle: always raise it to the ceiling so that handles of different
     // sizes can coexist
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync_tol<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_burst_sync_tol<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024 - 64) != hipSuccess) {
-        delete h;
-        return TETRA_ERR_HIP;
-    }
+    for (const void* k : { reinterpret_cast<const void*>(k_burst_sync<false>), reinterpret_cast<const void*>(k_burst_sync<true>),
+                           reinterpret_cast<const void*>(k_burst_sync_tol<false>), reinterpret_cast<const void*>(k_burst_sync_tol<true>) })
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess) {
+            delete h;
+            return TETRA_ERR_HIP;
+        }
     *out = h;
     return tetra_bsync_reset(h);
 }
@@ -519,11 +384,11 @@ template <bool PACKED> int bsync_launch(tetra_bsync_t* h, const uint8_t* d_bits,
     if (bits_stride < h->max_bits) return TETRA_ERR_SIZE;      // rows must be able to hold the max_bits the handle was sized for
     if ((bits_stride & 3) || ((uintptr_t)d_bits & 3) || ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;
     if (h->tolerant)
-        hipLaunchKernelGGL(k_burst_sync_tol<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes_tol(h->max_bits, h->max_frames),
+        hipLaunchKernelGGL(k_burst_sync_tol<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(TolRule::kMaps, h->max_bits, h->max_frames),
                            static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
                            h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames, h->tol, h->d_miss);
     else
-        hipLaunchKernelGGL(k_burst_sync<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(h->max_bits, h->max_frames),
+        hipLaunchKernelGGL(k_burst_sync<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(RefRule::kMaps, h->max_bits, h->max_frames),
                            static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
                            h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;

@@ -6,41 +6,62 @@
 #include <cstring>
 #include <vector>
 
-#include "../../sdrpp-tetra-demodulator_amd/csrc/bsync_core.hpp"
+#include "bsync_lane_io.hpp"
 
 using namespace bsync_core;
 
-extern "C" int bsync_emul_process(State* st, uint8_t* carry, const uint8_t* bits, int n_new, uint8_t* frames, int32_t* types,
-                                  uint32_t* bitnums, int max_frames, int use_batch) {
-    const int words = stream_words(n_new);
-    std::vector<uint32_t> s(words, 0), ms(words, 0), m1(words, 0), m2(words, 0), ma(words, 0);
-    const int x0 = kOff - (int)st->bits_in_buf, xe = kOff + n_new;
-    for (int x = x0; x < kOff; ++x) s[x >> 5] |= (uint32_t)(carry[x - x0] & 1u) << (31 - (x & 31));
-    for (int j = 0; j < n_new; ++j) s[(kOff + j) >> 5] |= (uint32_t)(bits[j] & 1u) << (31 - ((kOff + j) & 31));
-    for (int w = x0 >> 5; w <= (xe - 1) >> 5 && w + 2 < words; ++w) { match_word(s.data(), w, x0, xe, ms[w], m1[w], m2[w]); ma[w] = ms[w] | m1[w] | m2[w]; }
-    int carry_x = 0, overflow = 0;
-    auto emit = [&](int f, int bx, int type, uint32_t bitnum) {
-        if (f >= max_frames) { overflow = 1; return; }
-        for (int i = 0; i < kTs; ++i) frames[(size_t)f * 512 + i] = (uint8_t)get_bit(s.data(), bx + i);
-        types[f] = type;
-        bitnums[f] = bitnum;
-    };
+namespace {
+int process(State* st, uint8_t* carry, const uint8_t* bits, int n_new, void* frames, int packed, int32_t* types, uint32_t* bitnums, int max_frames,
+            int use_batch) {
+    bsync_emul::Call call(*st, carry, bits, n_new, n_new, max_frames);
+    const int words = (int)call.s.size(), x0 = kOff - (int)st->bits_in_buf, xe = kOff + n_new;
+    const uint32_t* s = call.s.data();
+    std::vector<uint32_t> ms(words, 0), m1(words, 0), m2(words, 0), ma(words, 0);
+    for (int w = x0 >> 5; w <= (xe - 1) >> 5 && w + 2 < words; ++w) { match_word(s, w, x0, xe, ms[w], m1[w], m2[w]); ma[w] = ms[w] | m1[w] | m2[w]; }
     // the kernel's batch of LOCKED frames (one per lane, 64 per round, stopping behind the first frame that unlocks), frame by frame
     auto batch = [&](int bx, int K, int f0, uint32_t abs_bx, bool& unlocked) {
         if (!use_batch) return 0;
         int done = 0;
         while (done < K) {
-            const FrameEval e = locked_frame_eval(s.data(), ms.data(), m1.data(), m2.data(), ma.data(), bx + kTs * done);
-            emit(f0 + done, bx + kTs * done, e.reported, abs_bx + (uint32_t)(kTs * done));
+            const FrameEval e = locked_frame_eval(s, ms.data(), m1.data(), m2.data(), ma.data(), bx + kTs * done);
+            call.emit(f0 + done, bx + kTs * done, e.reported, abs_bx + (uint32_t)(kTs * done));
             done++;
             if (e.unlocks) { unlocked = true; break; }
         }
         return done;
     };
-    const int n = run(*st, s.data(), ms.data(), m1.data(), m2.data(), ma.data(), n_new, carry_x,
-                      [](const uint32_t* m, int a, int b) { return first_set(m, a, b); }, emit, batch);
-    for (int x = carry_x; x < xe; ++x) carry[x - carry_x] = (uint8_t)get_bit(s.data(), x);
-    return overflow ? -1 : n;
+    return call.finish([&](int& carry_x, auto first, auto emit) {
+        return run(*st, s, ms.data(), m1.data(), m2.data(), ma.data(), n_new, carry_x, first, emit, batch);
+    }, packed, carry, frames, types, bitnums);
+}
+}  // namespace
+
+// frames [max_frames][512] bytes
+extern "C" int bsync_emul_process(State* st, uint8_t* carry, const uint8_t* bits, int n_new, uint8_t* frames, int32_t* types,
+                                  uint32_t* bitnums, int max_frames, int use_batch) {
+    return process(st, carry, bits, n_new, frames, 0, types, bitnums, max_frames, use_batch);
+}
+// frames [max_frames][16] words
+extern "C" int bsync_emul_process_packed(State* st, uint8_t* carry, const uint8_t* bits, int n_new, uint32_t* frames, int32_t* types,
+                                         uint32_t* bitnums, int max_frames, int use_batch) {
+    return process(st, carry, bits, n_new, frames, 1, types, bitnums, max_frames, use_batch);
+}
+
+// steps 1 and 4 on their own (tests/test_burst_sync.py holds them against their definitions).
+// the packed stream of a call: stream_words(max_bits) words
+extern "C" int bsync_emul_stage(int bits_in_buf, const uint8_t* carry, const uint8_t* bits, int n_new, int max_bits, uint32_t* s_out) {
+    const State st = { 0, (uint32_t)bits_in_buf, 0, 0 };
+    const bsync_emul::Call call(st, carry, bits, n_new, max_bits, 0);
+    std::memcpy(s_out, call.s.data(), call.s.size() * sizeof(uint32_t));
+    return (int)call.s.size();
+}
+// the frames that start at bx[0 .. nf) of that stream, and the carried buffer from carry_x on
+extern "C" void bsync_emul_expand(int bits_in_buf, const uint8_t* carry_in, const uint8_t* bits, int n_new, int max_bits, const int32_t* bx, int nf,
+                                  int carry_x, int packed, void* frames, int32_t* types, uint32_t* bitnums, uint8_t* carry_out) {
+    const State st = { 0, (uint32_t)bits_in_buf, 0, 0 };
+    bsync_emul::Call call(st, carry_in, bits, n_new, max_bits, nf);
+    for (int f = 0; f < nf; ++f) call.emit(f, bx[f], f & 3, (uint32_t)bx[f]);
+    call.write(nf, carry_x, packed, carry_out, frames, types, bitnums, -2);
 }
 
 // ---- the demultiplexer kernels (csrc/demux_core.hpp): every (workgroup, thread) of the launch tetra_burst_sync.hip's launchers would

@@ -9,7 +9,7 @@ from oracle import hostlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libbsync_emul.so")
-DEPS = [os.path.join(HERE, "bsync_emul.cpp"), os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "bsync_core.hpp"),
+DEPS = [os.path.join(HERE, "bsync_emul.cpp"), os.path.join(HERE, "bsync_lane_io.hpp"), os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "bsync_core.hpp"),
         os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "demux_core.hpp"), os.path.join(ROOT, "include", "tetra_burst_sync.h")]
 
 _lib = None
@@ -25,6 +25,9 @@ def lib():
         vp, i32 = C.c_void_p, C.c_int
         _lib = hostlib.load(build(), {
             "bsync_emul_process": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32]),
+            "bsync_emul_process_packed": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32]),
+            "bsync_emul_stage": (i32, [i32, vp, vp, i32, i32, vp]),
+            "bsync_emul_expand": (None, [i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
             "bsync_emul_demux": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp]),
             "bsync_emul_demux_compact": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp]),
         })
@@ -34,9 +37,11 @@ def lib():
 class Emul:
     """One channel: same interface as oracle.binding.BurstSyncOracle."""
 
-    def __init__(self, batch=True):
-        """batch: LOCKED steady state evaluated frame-parallel like the kernel does (run()'s batch hook) or event by event."""
+    def __init__(self, batch=True, packed=False):
+        """batch: LOCKED steady state evaluated frame-parallel like the kernel does (walk()'s batch hook) or event by event.
+        packed: feed() returns the frames as [n][16] uint32 words (k_burst_sync<true>'s form) instead of [n][510] bytes."""
         self.batch = 1 if batch else 0
+        self.packed = bool(packed)
         self.st = np.zeros(4, np.uint32)
         self.carry = np.zeros(4096, np.uint8)
 
@@ -47,14 +52,45 @@ class Emul:
     def feed(self, bits):
         b = np.ascontiguousarray(bits, np.uint8)
         cap = (4096 + b.size) // 510 + 4
-        fr = np.zeros((cap, 512), np.uint8)
+        fr = np.zeros((cap, 16), np.uint32) if self.packed else np.zeros((cap, 512), np.uint8)
         ty = np.zeros(cap, np.int32)
         bn = np.zeros(cap, np.uint32)
         vp = C.c_void_p
-        n = lib().bsync_emul_process(self.st.ctypes.data_as(vp), self.carry.ctypes.data_as(vp), b.ctypes.data_as(vp), b.size,
-                                    fr.ctypes.data_as(vp), ty.ctypes.data_as(vp), bn.ctypes.data_as(vp), cap, self.batch)
+        fn = lib().bsync_emul_process_packed if self.packed else lib().bsync_emul_process
+        n = fn(self.st.ctypes.data_as(vp), self.carry.ctypes.data_as(vp), b.ctypes.data_as(vp), b.size,
+               fr.ctypes.data_as(vp), ty.ctypes.data_as(vp), bn.ctypes.data_as(vp), cap, self.batch)
         assert n >= 0
-        return fr[:n, :510].copy(), ty[:n].copy(), bn[:n].copy()
+        return (fr[:n] if self.packed else fr[:n, :510]).copy(), ty[:n].copy(), bn[:n].copy()
+
+
+def stage(carry, bits, max_bits=None):
+    """Step 1 of a call run for every thread of the workgroup (bsync_core.hpp: stage_thread): the packed stream, stream_words(max_bits)
+    uint32 words, of the carried buffer `carry` (its size is bits_in_buf) and the new bits (read where the array lies: its address
+    decides between the 16-byte loads and the byte-wise path)."""
+    assert carry.dtype == np.uint8 and bits.dtype == np.uint8 and bits.flags.c_contiguous
+    max_bits = bits.size if max_bits is None else max_bits
+    s = np.zeros((4096 + max_bits + 64 + 31) // 32 + 2, np.uint32)
+    cb = np.ascontiguousarray(carry)
+    vp = C.c_void_p
+    n = lib().bsync_emul_stage(cb.size, cb.ctypes.data_as(vp), bits.ctypes.data_as(vp), bits.size, max_bits, s.ctypes.data_as(vp))
+    assert n == s.size
+    return s
+
+
+def expand(carry, bits, starts, carry_x, packed):
+    """Step 4 run for every thread (write_thread) on the stream of stage(): the frames that start at the coordinates `starts` ([n][16]
+    uint32 or [n][512] uint8), their types (f & 3) and bit numbers (the coordinate) with one spare slot, the carried buffer from
+    carry_x on (4096 bytes, 9 where nothing was written)."""
+    bx = np.ascontiguousarray(starts, np.int32)
+    fr = np.full((bx.size + 1, 16), 0xa5a5a5a5, np.uint32) if packed else np.full((bx.size + 1, 512), 9, np.uint8)
+    ty = np.zeros(bx.size, np.int32)
+    bn = np.zeros(bx.size, np.uint32)
+    out = np.full(4096, 9, np.uint8)
+    cb = np.ascontiguousarray(carry)
+    vp = C.c_void_p
+    lib().bsync_emul_expand(cb.size, cb.ctypes.data_as(vp), bits.ctypes.data_as(vp), bits.size, bits.size, bx.ctypes.data_as(vp), bx.size, int(carry_x),
+                            int(packed), fr.ctypes.data_as(vp), ty.ctypes.data_as(vp), bn.ctypes.data_as(vp), out.ctypes.data_as(vp))
+    return fr, ty, bn, out
 
 
 def pack_frames(frames):

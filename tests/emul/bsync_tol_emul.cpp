@@ -7,30 +7,24 @@
 #include <cstring>
 #include <vector>
 
-#include "../../sdrpp-tetra-demodulator_amd/csrc/bsync_core.hpp"
+#include "bsync_lane_io.hpp"
 
 using namespace bsync_core;
 
 // mode 0: no batch (every LOCKED call through the event path); 1: batch, consecutive-miss rule by first_unlock (the loop);
 // 2: batch, first_unlock_bits (the kernel's).  tol3 = {tol_norm, tol_sync, max_miss}.  Returns the frame count, -1 on overflow, -2 for
 // a tolerance out of range.
-extern "C" int bsync_tol_emul_process(State* st, int32_t* misses, uint8_t* carry, const uint8_t* bits, int n_new, const int32_t* tol3, uint8_t* frames,
-                                      int32_t* types, uint32_t* bitnums, int max_frames, int mode) {
+namespace {
+int process(State* st, int32_t* misses, uint8_t* carry, const uint8_t* bits, int n_new, const int32_t* tol3, void* frames, int packed, int32_t* types,
+            uint32_t* bitnums, int max_frames, int mode) {
     const Tolerance tol = { tol3[0], tol3[1], tol3[2] };
     if (!tolerance_valid(tol)) return -2;
-    const int words = stream_words(n_new);
-    std::vector<uint32_t> s(words, 0), ms(words, 0);
-    const int x0 = kOff - (int)st->bits_in_buf, xe = kOff + n_new;
-    for (int x = x0; x < kOff; ++x) s[x >> 5] |= (uint32_t)(carry[x - x0] & 1u) << (31 - (x & 31));
-    for (int j = 0; j < n_new; ++j) s[(kOff + j) >> 5] |= (uint32_t)(bits[j] & 1u) << (31 - ((kOff + j) & 31));
-    for (int w = x0 >> 5; w <= (xe - 1) >> 5 && w + 2 < words; ++w) ms[w] = match_word_sync(s.data(), w, x0, xe);
-    int carry_x = 0, overflow = 0, m = *misses;
-    auto emit = [&](int f, int bx, int type, uint32_t bitnum) {
-        if (f >= max_frames) { overflow = 1; return; }
-        for (int i = 0; i < kTs; ++i) frames[(size_t)f * 512 + i] = (uint8_t)get_bit(s.data(), bx + i);
-        types[f] = type;
-        bitnums[f] = bitnum;
-    };
+    bsync_emul::Call call(*st, carry, bits, n_new, n_new, max_frames);
+    const int words = (int)call.s.size(), x0 = kOff - (int)st->bits_in_buf, xe = kOff + n_new;
+    const uint32_t* s = call.s.data();
+    std::vector<uint32_t> ms(words, 0);
+    for (int w = x0 >> 5; w <= (xe - 1) >> 5 && w + 2 < words; ++w) ms[w] = match_word_sync(s, w, x0, xe);
+    int m = *misses;
     auto batch = [&](int bx, int K, int f0, uint32_t abs_bx, bool& unlocked) {
         if (!mode) return 0;
         int done = 0;
@@ -39,22 +33,34 @@ extern "C" int bsync_tol_emul_process(State* st, int32_t* misses, uint8_t* carry
             int reported[64];
             uint64_t pass = 0;
             for (int lane = 0; lane < 64; ++lane) {              // (lanes past `here` report nothing, as in the kernel's ballot)
-                reported[lane] = lane < here ? tolerant_frame_eval(s.data(), bx + kTs * (done + lane), tol) : -1;
+                reported[lane] = lane < here ? tolerant_frame_eval(s, bx + kTs * (done + lane), tol) : -1;
                 if (reported[lane] >= 0) pass |= 1ull << lane;
             }
             const Unlock u = mode == 2 ? first_unlock_bits(pass, here, m, tol.max_miss) : first_unlock(pass, here, m, tol.max_miss);
             const int take = u.index >= 0 ? u.index + 1 : here;
-            for (int lane = 0; lane < take; ++lane) emit(f0 + done + lane, bx + kTs * (done + lane), reported[lane], abs_bx + (uint32_t)(kTs * (done + lane)));
+            for (int lane = 0; lane < take; ++lane) call.emit(f0 + done + lane, bx + kTs * (done + lane), reported[lane], abs_bx + (uint32_t)(kTs * (done + lane)));
             m = u.misses;
             done += take;
             if (u.index >= 0) { unlocked = true; break; }
         }
         return done;
     };
-    const int n = run_tolerant(*st, s.data(), ms.data(), n_new, carry_x, [](const uint32_t* mm, int a, int b) { return first_set(mm, a, b); }, emit, batch, tol, m);
-    for (int x = carry_x; x < xe; ++x) carry[x - carry_x] = (uint8_t)get_bit(s.data(), x);
+    const int n = call.finish([&](int& carry_x, auto first, auto emit) { return run_tolerant(*st, s, ms.data(), n_new, carry_x, first, emit, batch, tol, m); },
+                              packed, carry, frames, types, bitnums);
     *misses = m;
-    return overflow ? -1 : n;
+    return n;
+}
+}  // namespace
+
+// frames [max_frames][512] bytes
+extern "C" int bsync_tol_emul_process(State* st, int32_t* misses, uint8_t* carry, const uint8_t* bits, int n_new, const int32_t* tol3, uint8_t* frames,
+                                      int32_t* types, uint32_t* bitnums, int max_frames, int mode) {
+    return process(st, misses, carry, bits, n_new, tol3, frames, 0, types, bitnums, max_frames, mode);
+}
+// frames [max_frames][16] words
+extern "C" int bsync_tol_emul_process_packed(State* st, int32_t* misses, uint8_t* carry, const uint8_t* bits, int n_new, const int32_t* tol3,
+                                             uint32_t* frames, int32_t* types, uint32_t* bitnums, int max_frames, int mode) {
+    return process(st, misses, carry, bits, n_new, tol3, frames, 1, types, bitnums, max_frames, mode);
 }
 
 // out = {index, misses}

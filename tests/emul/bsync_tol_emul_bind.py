@@ -9,7 +9,7 @@ from oracle import hostlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libbsync_tol_emul.so")
-DEPS = [os.path.join(HERE, "bsync_tol_emul.cpp"), os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "bsync_core.hpp")]
+DEPS = [os.path.join(HERE, "bsync_tol_emul.cpp"), os.path.join(HERE, "bsync_lane_io.hpp"), os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc", "bsync_core.hpp")]
 
 _lib = None
 
@@ -24,6 +24,7 @@ def lib():
         vp, i32 = C.c_void_p, C.c_int
         _lib = hostlib.load(build(), {
             "bsync_tol_emul_process": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32]),
+            "bsync_tol_emul_process_packed": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32]),
             "bsync_tol_emul_first_unlock": (None, [C.c_uint64, i32, i32, i32, i32, vp]),
             "bsync_tol_emul_first_unlock_many": (None, [vp, vp, vp, vp, i32, i32, vp]),
             "bsync_tol_emul_frame_eval": (i32, [vp, vp]),
@@ -37,9 +38,11 @@ def _p(a):
 
 class Emul:
     """One channel under the tolerant lock: oracle.binding.BurstSyncOracle's interface plus the miss counter.
-    mode: 0 event path only, 1 batch with the loop form of the consecutive-miss rule, 2 batch with the kernel's bit operations."""
+    mode: 0 event path only, 1 batch with the loop form of the consecutive-miss rule, 2 batch with the kernel's bit operations.
+    packed: feed() returns the frames as [n][16] uint32 words (k_burst_sync_tol<true>'s form) instead of [n][510] bytes."""
 
-    def __init__(self, tol, mode=2):
+    def __init__(self, tol, mode=2, packed=False):
+        self.packed = bool(packed)
         self.tol = np.array(tol, np.int32)
         self.mode = int(mode)
         self.st = np.zeros(4, np.uint32)
@@ -60,12 +63,13 @@ class Emul:
     def feed(self, bits):
         b = np.ascontiguousarray(bits, np.uint8)
         cap = (4096 + b.size) // 510 + 4
-        fr = np.zeros((cap, 512), np.uint8)
+        fr = np.zeros((cap, 16), np.uint32) if self.packed else np.zeros((cap, 512), np.uint8)
         ty = np.zeros(cap, np.int32)
         bn = np.zeros(cap, np.uint32)
-        n = lib().bsync_tol_emul_process(_p(self.st), _p(self.miss), _p(self.carry), _p(b), b.size, _p(self.tol), _p(fr), _p(ty), _p(bn), cap, self.mode)
+        fn = lib().bsync_tol_emul_process_packed if self.packed else lib().bsync_tol_emul_process
+        n = fn(_p(self.st), _p(self.miss), _p(self.carry), _p(b), b.size, _p(self.tol), _p(fr), _p(ty), _p(bn), cap, self.mode)
         assert n >= 0, n
-        return fr[:n, :510].copy(), ty[:n].copy(), bn[:n].copy()
+        return (fr[:n] if self.packed else fr[:n, :510]).copy(), ty[:n].copy(), bn[:n].copy()
 
 
 def first_unlock(pass_mask, n, misses_in, max_miss, bits):

@@ -292,6 +292,58 @@ def test_kernel_logic_equals_literal_state_machine(ref, oracle):
     assert min(hist.get(k, 0) for k in (-1, 0, 1, 3)) > 50        # every outcome was exercised
 
 
+def aligned_bytes(n, align, fill):
+    """n bytes `fill` that lie `align` bytes behind a 16-byte boundary"""
+    buf = np.zeros(n + 32, np.uint8)
+    at = (-buf.ctypes.data) % 16 + align
+    buf[at:at + n] = fill
+    out = buf[at:at + n]
+    assert n == 0 or out.ctypes.data % 16 == align
+    return out
+
+
+def test_stream_staging_and_frame_expansion_equal_their_definitions():
+    """Steps 1 and 4 of k_burst_sync as the host build runs them (bsync_core.hpp: stage_thread / write_thread for every thread of the
+    workgroup).  The input row at every alignment (the two 16-byte loads, the byte-wise fall-back, the ragged tail), carried buffers and
+    call sizes around the word boundaries, bytes with high bits set: the packed stream is numpy.packbits of [carry | bits] at coordinate
+    4096 - bits_in_buf and zero elsewhere; frames at all 32 bit phases, byte form and packed form, and the carry written back are the
+    stream's bits."""
+    from tests.emul import bsync_emul_bind as E
+    rng = np.random.default_rng(2024)
+    n_frames_checked = 0
+    for n_new in (0, 1, 31, 32, 33, 63, 64, 65, 510, 1055):
+        for nbuf in (0, 1, 31, 32, 33, 4095, 4096):
+            x0, xe = 4096 - nbuf, 4096 + n_new
+            for align in range(16):
+                carry = rng.integers(0, 256, nbuf, dtype=np.uint8)
+                bits = aligned_bytes(n_new, align, rng.integers(0, 256, n_new, dtype=np.uint8))
+                s = E.stage(carry, bits)
+                want = np.zeros(32 * s.size, np.uint8)               # one byte per coordinate, the look-ahead words included
+                want[x0:4096] = carry & 1
+                want[4096:xe] = bits & 1
+                assert np.array_equal(s, np.packbits(want).view(">u4").astype(np.uint32)), (n_new, nbuf, align)
+                if align % 5:
+                    continue
+                # step 4 on that stream: frames from all 32 bit phases as far as the stream's words hold them (a frame may run into
+                # the zero look-ahead), one that ends with the stream; the carry from a start of any phase
+                starts = [x0 + p for p in range(32)] + ([xe - 510] if xe - 510 >= x0 else [])
+                starts = [b for b in starts if b + 510 <= 32 * (s.size - 1)]
+                carry_x = xe - int(rng.integers(0, min(xe - x0, 4096) + 1))
+                for packed in (False, True):
+                    fr, ty, bn, out = E.expand(carry, bits, starts, carry_x, packed)
+                    frames = np.array([want[b:b + 510] for b in starts], np.uint8).reshape(len(starts), 510)
+                    if packed:
+                        rows = np.concatenate([frames, np.zeros((len(starts), 2), np.uint8)], axis=1)
+                        assert np.array_equal(fr[:-1], np.packbits(rows, axis=1).view(">u4").astype(np.uint32)), (n_new, nbuf, align)
+                        assert not (fr[:-1, 15] & 3).any() and (fr[-1] == 0xa5a5a5a5).all()
+                    else:
+                        assert np.array_equal(fr[:-1, :510], frames) and not fr[:-1, 510:].any() and (fr[-1] == 9).all(), (n_new, nbuf, align)
+                    assert np.array_equal(ty, np.arange(len(starts)) & 3) and np.array_equal(bn, np.array(starts, np.uint32))
+                    assert np.array_equal(out[:xe - carry_x], want[carry_x:xe]) and (out[xe - carry_x:] == 9).all(), (n_new, nbuf, align, carry_x)
+                n_frames_checked += len(starts)
+    assert n_frames_checked >= 32 * 30 * 4          # the 30 (n_new, nbuf) pairs that hold a frame at every phase, four alignments each
+
+
 @pytest.mark.gpu
 def test_gpu_burst_sync_equals_literal_state_machine(pkg, ref, oracle):
     """48 channels with different adversarial streams, five calls with ragged per-channel bit counts."""

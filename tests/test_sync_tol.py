@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from tests import soft_pipeline as sp
-from tests.test_burst_sync import make_stream
+from tests.test_burst_sync import aligned_bytes, make_stream
 from tests.test_rx_soft import OP_CHANNELS, OP_SAMPLES, OP_SEED, OP_SLOTS, rows_to_arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -629,6 +629,77 @@ def test_gpu_setting_and_clearing_the_tolerance(pkg, ref, oracle, tolemul):
     out = np.zeros(Cn, np.int32)
     assert L.tetra_bsync_get_misses(bs._h, 0, Cn + 1, out.ctypes.data) == -1 and L.tetra_bsync_get_misses(bs._h, -1, 1, out.ctypes.data) == -1
     bs.close()
+
+
+def unaligned_streams(ref):
+    """four short streams that lock early: no lead-in, a sync sequence in the first buffer positions, noise lead-ins"""
+    return [make_stream(ref, seed)[:3 * 2052] for seed in (4, 1, 10, 14)]
+
+
+def unaligned_calls(streams, call):
+    """rows [4][2052] for call `call` -- bit 0 of a byte is the stream's bit, the other seven and everything behind n_bits are
+    garbage -- and the counts 2052, 2051, 1025, 0 rotated by one channel per call"""
+    rng = np.random.default_rng(300 + call)
+    rows = rng.integers(0, 256, (4, 2052), dtype=np.uint8)
+    nb = np.roll(np.array([2052, 2051, 1025, 0], np.int32), call)
+    pos = [int(sum(np.roll([2052, 2051, 1025, 0], k)[c] for k in range(call))) for c in range(4)]
+    for c in range(4):
+        rows[c, :nb[c]] = (rows[c, :nb[c]] & 0xfe) | streams[c][pos[c]:pos[c] + nb[c]]
+    return rows, nb, pos
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("packed", (False, True))
+@pytest.mark.parametrize("tol", (None, DEFAULT))
+def test_gpu_rows_off_the_16_byte_grid_equal_the_host_build(pkg, ref, tolemul, tol, packed):
+    """bits_stride = max_bits = 2052, a multiple of 4 and not of 16: the four channels' rows lie 0, 4, 8 and 12 bytes behind a 16-byte
+    boundary, so three of them take step 1's byte-wise path, and the counts 2051 and 1025 leave a ragged last word.  Three calls, both
+    rules: frames (in the kernel's own form, packed or bytes), types, bit numbers, counts, states and miss counters equal the host
+    build's after every call.  The carried buffer has no reader in the C ABI: it is held through the frames the next call cuts from
+    it and, behind the last call, through its length in the state."""
+    import torch
+    from tests.emul import bsync_emul_bind
+    dev = torch.device("cuda", 0)
+    Cn, max_bits = 4, 2052
+    streams = unaligned_streams(ref)
+    bs = pkg.bsync_binding.BurstSync(Cn, max_bits)
+    F = bs.max_frames
+    if tol is not None:
+        bs.set_tolerance(tol)
+    emuls = [tolemul.Emul(tol, mode=2, packed=packed) if tol is not None else bsync_emul_bind.Emul(packed=packed) for _ in range(Cn)]
+    n_frames = n_reported = from_carry = 0
+    for call in range(3):
+        rows, nb, pos = unaligned_calls(streams, call)
+        d_rows, d_nb = torch.from_numpy(rows).to(dev), torch.from_numpy(nb).to(dev)
+        assert d_rows.data_ptr() % 16 == 0 and d_rows.stride(0) == max_bits
+        d_fr = torch.full((Cn, F, 16), 0x5a5a5a5a, dtype=torch.int32, device=dev) if packed else torch.full((Cn, F, 512), 9, dtype=torch.uint8, device=dev)
+        d_ft = torch.full((Cn, F), 99, dtype=torch.int32, device=dev)
+        d_fb = torch.full((Cn, F), 99, dtype=torch.int32, device=dev)
+        d_nf = torch.full((Cn,), -1, dtype=torch.int32, device=dev)
+        (bs.process_packed_device if packed else bs.process_device)(d_rows, max_bits, d_nb, d_fr, d_ft, d_fb, d_nf)
+        torch.cuda.synchronize()
+        fr, ft, fb, nf = d_fr.cpu().numpy(), d_ft.cpu().numpy(), d_fb.cpu().numpy().view(np.uint32), d_nf.cpu().numpy()
+        st, miss = bs.states(), bs.misses()
+        for c in range(Cn):
+            before = emuls[c].state
+            w = emuls[c].feed(aligned_bytes(int(nb[c]), 4 * c, rows[c, :nb[c]]))
+            n = len(w[1])
+            assert nf[c] == n, (call, c, nf[c], n)
+            if packed:
+                assert np.array_equal(fr[c, :n].view(np.uint32), w[0]) and (fr[c, n:] == 0x5a5a5a5a).all(), (call, c)
+            else:
+                assert np.array_equal(fr[c, :n, :510], w[0]) and not fr[c, :n, 510:].any() and (fr[c, n:] == 9).all(), (call, c)
+            assert np.array_equal(ft[c, :n], w[1]) and (ft[c, n:] == pkg.bsync_binding.FRAME_NONE).all(), (call, c)
+            assert np.array_equal(fb[c, :n], w[2]) and not fb[c, n:].any(), (call, c)
+            assert st[c] == emuls[c].state, (call, c, st[c], emuls[c].state)
+            assert miss[c] == (emuls[c].misses if tol is not None else 0), (call, c)
+            n_frames += n
+            n_reported += int((w[1] >= 0).sum())
+            from_carry += int(sum(1 for b in w[2] if (int(b) - before[2]) % (1 << 32) < before[1]))       # frames that begin in the carried buffer
+    bs.close()
+    torch.cuda.synchronize()
+    # the run did what it is for: frames from every channel's stream, reported ones among them, frames cut from the carried buffer
+    assert n_frames >= 16 and n_reported >= 12 and from_carry >= 3, (n_frames, n_reported, from_carry)
 
 
 @pytest.fixture(scope="module")
