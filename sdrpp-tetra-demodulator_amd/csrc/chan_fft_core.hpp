@@ -21,6 +21,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define CHAN_HD __host__ __device__ __forceinline__
@@ -150,25 +151,27 @@ CHAN_HD void dft25(c32 x[25]) {
 // frames (4 new samples per slot and block; the rest is re-read from L1 / L2 by the next block).
 //   coef[0][q] = h[u + 800 q]                    (even frames)
 //   coef[1][q] = h[(u + 400) % 800 + 800 q]      (odd frames)
-template <int P> struct FoldCoef {
-    float c[2][P];
+// Tap = float for the bank on the bin grid, c32 for the frequency-shifted one (below): one fold, two tap types.
+template <int P, class Tap> struct FoldCoef {
+    Tap c[2][P];
 };
-// The prototype re-ordered for the fold (host side, once per handle): ht[u][parity][q], so that a slot's 2 P coefficients are 8 P
-// contiguous bytes and the lanes of a wave (consecutive u) read one contiguous run with 16-byte loads.
-inline void fold_transpose_prototype(const float* h, int P, float* ht) {
+// The prototype re-ordered for the fold (host side, once per handle and shift): ht[u][parity][q] = tap(l), so that a slot's 2 P
+// coefficients are contiguous (8 P or 16 P bytes) and the lanes of a wave (consecutive u) read one contiguous run with 16-byte loads.
+template <class Tap, class TapOf> inline void fold_transpose_prototype(int P, TapOf tap, Tap* ht) {
     for (int u = 0; u < kM; u++) {
         const int uo = u < kM / 2 ? u + kM / 2 : u - kM / 2;
         for (int q = 0; q < P; q++) {
-            ht[(2 * u + 0) * P + q] = h[u + kM * q];
-            ht[(2 * u + 1) * P + q] = h[uo + kM * q];
+            ht[(2 * u + 0) * P + q] = tap(u + kM * q);
+            ht[(2 * u + 1) * P + q] = tap(uo + kM * q);
         }
     }
 }
-template <int P> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoef<P>& k) {
+template <int P, class Tap> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoef<P, Tap>& k) {
+    const Tap* t = reinterpret_cast<const Tap*>(ht);
 #pragma unroll
     for (int q = 0; q < P; q++) {
-        k.c[0][q] = ht[(2 * u + 0) * P + q];
-        k.c[1][q] = ht[(2 * u + 1) * P + q];
+        k.c[0][q] = t[(2 * u + 0) * P + q];
+        k.c[1][q] = t[(2 * u + 1) * P + q];
     }
 }
 // ---- the frequency-shifted bank (tetra_chan_set_shift): complex taps and one phasor per frame ----------------------------
@@ -177,35 +180,13 @@ template <int P> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoef<P>
 // = the same fold with a complex (modulated) prototype, and one phasor per output frame that is the same for every bin.  Both
 // phases are taken in INTEGER arithmetic mod 2^32 (inc . l for the taps, inc . n_m for the frame, n_m = the absolute index of the
 // frame's newest sample): exact at any stream position, whatever the chunking.  Everything here is selected at compile time
-// (SHIFT = true); the SHIFT = false instantiations are the code above, untouched.
-template <int P> struct FoldCoefC {
-    c32 c[2][P];
-};
-// hc in double on the host, re-ordered like fold_transpose_prototype: htc[u][parity][q] complex (16 P bytes per slot)
-inline void fold_transpose_prototype_shifted(const float* h, int P, uint32_t inc, c32* htc) {
+// (SHIFT = true: Tap = c32); the SHIFT = false instantiations pay nothing for it.
+// hc[l], in double on the host: what every kernel's shifted taps are made of, in the fold layout above or as [L]
+inline c32 modulated_tap(const float* h, uint32_t inc, int l) {
     const double two_pi = 6.283185307179586476925286766559;
-    auto hc = [&](int l) {
-        const double a = two_pi * (double)(uint32_t)(inc * (uint32_t)l) / 4294967296.0;
-        return mk((float)((double)h[l] * std::cos(a)), (float)((double)h[l] * std::sin(a)));
-    };
-    for (int u = 0; u < kM; u++) {
-        const int uo = u < kM / 2 ? u + kM / 2 : u - kM / 2;
-        for (int q = 0; q < P; q++) {
-            htc[(2 * u + 0) * P + q] = hc(u + kM * q);
-            htc[(2 * u + 1) * P + q] = hc(uo + kM * q);
-        }
-    }
+    const double a = two_pi * (double)(uint32_t)(inc * (uint32_t)l) / 4294967296.0;
+    return mk((float)((double)h[l] * std::cos(a)), (float)((double)h[l] * std::sin(a)));
 }
-template <int P> CHAN_HD void fold_load_coef(const float* ht, int u, FoldCoefC<P>& k) {
-    const c32* htc = reinterpret_cast<const c32*>(ht);
-#pragma unroll
-    for (int q = 0; q < P; q++) {
-        k.c[0][q] = htc[(2 * u + 0) * P + q];
-        k.c[1][q] = htc[(2 * u + 1) * P + q];
-    }
-}
-template <int P, bool SHIFT> struct FoldCoefOf { typedef FoldCoef<P> type; };
-template <int P> struct FoldCoefOf<P, true> { typedef FoldCoefC<P> type; };
 // exp(-j 2 pi ph / 2^32).  The phase goes to binary32 as a signed fraction of a turn (24 significant bits: 1.9e-7 rad at worst).
 CHAN_HD c32 shift_phasor(uint32_t ph) {
     const float t = (float)(int32_t)ph * (1.0f / 2147483648.0f);      // half-turns in [-1, 1)
@@ -246,13 +227,13 @@ struct BlockCtx {
     const c32* hist;      // the L - 1 samples before them, oldest first (the handle's carried delay line)
     int n_in;
     c32* out;             // [frames][800]
-    const float* h;       // prototype, re-ordered for the fold: [800][2][P] (fold_transpose_prototype)
+    const float* h;       // prototype, re-ordered for the fold: [800][2][P] (fold_transpose_prototype); SHIFT: the complex taps, as c32
     const c32* tw;        // [25][32]: W800^(n1 k2)
     int frames;           // frames of this call
     int ph0;              // samples already consumed towards the call's first frame
     long long abs0;       // absolute time of the first new sample
     int L;                // 800 P
-    uint32_t inc;         // frequency shift in 2^-32 cycles per input sample (SHIFT instantiations only; h then holds the complex taps)
+    uint32_t inc;         // frequency shift in 2^-32 cycles per input sample (SHIFT instantiations only)
 };
 
 // Sample s of the stream, s counted from the call's first new sample.  Blocks in the middle of a call read only new samples and
@@ -270,7 +251,20 @@ CHAN_HD bool block_is_careful(const BlockCtx& c, long long newest0) {
     return newest0 < c.L - 1 || newest0 + (kBlockFrames - 1) * (kM / 2) > c.n_in - 1;
 }
 
-template <int P, int CLS, bool CAREFUL, int FMT> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoef<P>& k, c32 out[kBlockFrames]) {
+// one tap of the fold: acc += hv . x -- 2 fma for a real tap, 4 for a complex one
+CHAN_HD void fold_tap(float hv, c32 xv, float& ar, float& ai) {
+    CHAN_FP_FAST
+    ar += hv * xv.x;
+    ai += hv * xv.y;
+}
+CHAN_HD void fold_tap(c32 hv, c32 xv, float& ar, float& ai) {
+    CHAN_FP_FAST
+    ar += hv.x * xv.x;
+    ar -= hv.y * xv.y;
+    ai += hv.x * xv.y;
+    ai += hv.y * xv.x;
+}
+template <int P, int CLS, bool CAREFUL, int FMT, class Tap> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoef<P, Tap>& k, c32 out[kBlockFrames]) {
     CHAN_FP_FAST
     constexpr int kS = P + 3 + CLS;                   // class 0 frames reach sample m = 3, class 1 frames m = 4
     c32 S[kS];                                        // S[j] = sample m = j - (P - 1) = stream sample s0 + 800 m  (s0 = newest0 - u)
@@ -281,36 +275,7 @@ template <int P, int CLS, bool CAREFUL, int FMT> CHAN_HD void fold_slot(const Bl
         const int s = (t + CLS) >> 1;
         float ar = 0.f, ai = 0.f;
 #pragma unroll
-        for (int q = 0; q < P; q++) {
-            const c32 xv = S[s - q + (P - 1)];
-            const float hv = k.c[t & 1][q];
-            ar += hv * xv.x;
-            ai += hv * xv.y;
-        }
-        out[t] = mk(ar, ai);
-    }
-}
-
-// the same with complex taps: 4 fma per tap instead of 2
-template <int P, int CLS, bool CAREFUL, int FMT> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoefC<P>& k, c32 out[kBlockFrames]) {
-    CHAN_FP_FAST
-    constexpr int kS = P + 3 + CLS;
-    c32 S[kS];
-#pragma unroll
-    for (int j = 0; j < kS; j++) S[j] = sample_at<CAREFUL, FMT>(c, s0 + kM * (j - (P - 1)));
-#pragma unroll
-    for (int t = 0; t < kBlockFrames; t++) {
-        const int s = (t + CLS) >> 1;
-        float ar = 0.f, ai = 0.f;
-#pragma unroll
-        for (int q = 0; q < P; q++) {
-            const c32 xv = S[s - q + (P - 1)];
-            const c32 hv = k.c[t & 1][q];
-            ar += hv.x * xv.x;
-            ar -= hv.y * xv.y;
-            ai += hv.x * xv.y;
-            ai += hv.y * xv.x;
-        }
+        for (int q = 0; q < P; q++) fold_tap(k.c[t & 1][q], S[s - q + (P - 1)], ar, ai);
         out[t] = mk(ar, ai);
     }
 }
@@ -324,8 +289,8 @@ template <int P, bool CAREFUL, int FMT, bool SHIFT = false> CHAN_HD void phase_f
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int u = kFoldThreads * i + tid;
-        typename FoldCoefOf<P, SHIFT>::type k;
-        fold_load_coef<P>(c.h, u, k);
+        FoldCoef<P, typename std::conditional<SHIFT, c32, float>::type> k;
+        fold_load_coef(c.h, u, k);
         c32 v[kBlockFrames];
         if (i < 2) fold_slot<P, 0, CAREFUL, FMT>(c, newest0 - u, k, v);
         else fold_slot<P, 1, CAREFUL, FMT>(c, newest0 - u, k, v);

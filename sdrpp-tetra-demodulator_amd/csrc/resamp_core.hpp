@@ -18,7 +18,7 @@
 // column equals that column of the full resampler bit for bit.
 //
 // Compiles for the host as well (tests/emul/resamp_emul.cpp runs every thread of a launch against the double-precision definition,
-// tests/emul/resamp_select_emul.cpp the picking variant against the full one).
+// and the picking variant against the full one).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -175,6 +175,21 @@ template <int W, class Cols = AllColumns> RESAMP_HD void thread_generic(const Ct
 #pragma unroll
     for (int w = 0; w < W; w++) o.v[w] = acc[w];
     reinterpret_cast<V*>(c.out)[k * (long long)c.units + u] = o;
+}
+
+// The ratios and lengths with thread code specialised at compile time (thread_fixed): the one table.  tetra_resamp.hip picks its
+// kernels through it and the host emulation its thread code; any other (I, DN, T) runs thread_generic.
+template <int I_, int DN_, int T_> struct Ratio { static constexpr int I = I_, DN = DN_, T = T_; };
+template <class... R> struct RatioList {};
+using Ratios = RatioList<Ratio<18, 25, 8>, Ratio<18, 25, 12>, Ratio<18, 25, 16>, Ratio<18, 25, 24>, Ratio<2, 3, 8>, Ratio<3, 2, 8>, Ratio<1, 2, 8>>;
+template <class F, class... R> inline void for_each_ratio(RatioList<R...>, F&& f) { (f(R()), ...); }
+// f(Ratio<I, DN, T>()) if the triple is in the table; false ("none") otherwise
+template <class F> inline bool visit_ratio(int I, int DN, int T, F&& f) {
+    bool found = false;
+    for_each_ratio(Ratios(), [&](auto r) {
+        if (I == r.I && DN == r.DN && T == r.T) { f(r); found = true; }
+    });
+    return found;
 }
 
 // coef[i][j] = h[(DN i mod I) + I j]

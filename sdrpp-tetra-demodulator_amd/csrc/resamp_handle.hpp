@@ -22,8 +22,7 @@ struct tetra_resamp {
     fixed_kernel_t fixed = nullptr;
     pick_kernel_t pick = nullptr;     // the same ratio over picked columns (W = 2; resamp_impl::process_pick_device)
     DevMem<float> d_coef;        // [I][T] phase table (fixed kernel) or the prototype (generic)
-    DevMem<float> hist;          // [T - 1][2 C]: the frames before the next call's first
-    DevMem<float> halt;          // same size: receives the next call's delay line, then the two swap roles
+    DelayLine<float> hist;       // [T - 1][2 C]: the frames before the next call's first
     long long n_total = 0;       // frames consumed so far
     long long m_next = 0;        // outputs emitted so far
     DevMem<float> st_in;         // host-path staging

@@ -18,10 +18,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <utility>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tetra_shift.h"
+#include "chan_design.hpp"
 #include "chan_fft_core.hpp"
 #include "hip_host.hpp"
 
@@ -33,14 +34,13 @@ constexpr int kMaxFactor = 64;
 struct ChanParams {
     const float2* xbuf;    // [L-1 history][n_in new]
     float2* out;           // [frames][M]
-    const float* h;        // prototype [L]
+    const float* h;        // prototype [L]; SHIFT: the modulated prototype hc[l] = h[l] exp(+j 2 pi inc l / 2^32), [L] complex
     const float2* w1;      // exp(-j 2 pi i / N1), i < N1
     const float2* w2;      // exp(-j 2 pi i / N2), i < N2
     const float2* wm;      // exp(-j 2 pi i / M),  i < M
     int M, P, D, N1, N2;
     int ph0;               // samples already consumed towards the first frame of this call
     long long abs0;        // absolute index of xbuf[L-1] (the first new sample)
-    const float2* hc;      // SHIFT: the modulated prototype hc[l] = h[l] exp(+j 2 pi inc l / 2^32), [L]
     uint32_t inc;          // SHIFT: frequency shift in 2^-32 cycles per input sample (tetra_chan_set_shift)
 };
 
@@ -71,7 +71,7 @@ template <bool SHIFT> __global__ __launch_bounds__(kThreads) void k_channelise(C
         for (int q = 0; q < p.P; q++) {
             const int l = l0 + q * M;
             if (SHIFT) {
-                const float2 hv = p.hc[l];
+                const float2 hv = reinterpret_cast<const float2*>(p.h)[l];
                 const float2 xv = xn[-l];
                 acc.x = fmaf(-hv.y, xv.y, fmaf(hv.x, xv.x, acc.x));
                 acc.y = fmaf(hv.y, xv.x, fmaf(hv.x, xv.y, acc.y));
@@ -147,7 +147,7 @@ constexpr int kMBoStride = 36;                    // floats per Bo row (32 used)
 struct ChanMfmaParams {
     const float2* xbuf;
     float2* out;
-    const float* h;        // prototype [L]; SHIFT: the modulated prototype hc, [L] complex
+    const float* h;        // prototype [L]; SHIFT: the modulated prototype hc, [L] complex (as ChanParams::h)
     const float* bc;       // [4 kMK1][64] stage-1 constant operand
     const float* ac;       // [64][64]     stage-2 constant operand
     const float2* wm;      // exp(-j 2 pi i / M)
@@ -289,20 +289,20 @@ template <int P, bool SHIFT = false> __global__ __launch_bounds__(kThreads, SHIF
 //   stage 1    lane = n1 (25 of each 32; two frames per wave): 32-point FFT over n2 in registers, transposed in place in LDS
 //   stage 2    lane = k2 (all 32; two frames per wave): twiddle, 5 x 5 DFT over n1 in registers, then for every k1 the 32 lanes store
 //              32 consecutive bins: 256-byte runs of the [frame][channel] rows, two per store instruction
-// The lane-level code is chan_fft_core.hpp (also compiled for the host: tests/emul/chan_emul.cpp).
+// The lane-level code is chan_fft_core.hpp (also compiled for the host, shifted and un-shifted: tests/emul/chan_emul.cpp).
 // ---------------------------------------------------------------------------------------------------------------------
 struct ChanFftParams {
     const void* x;         // the call's new samples (the caller's buffer) in the kernel's sample format
     const float2* hist;    // the L - 1 samples before them
     float2* out;
-    const float* h;        // the prototype re-ordered for the fold [800][2][P]
+    const float* h;        // the prototype re-ordered for the fold [800][2][P]; SHIFT: the complex taps hc in that order
     const float2* tw;      // [25][32] exp(-j 2 pi n1 k2 / 800)
     int frames, blocks, n_in;
     int ph0;
     int xcd_span;          // blocks per XCD (ceil(blocks / 8)); 0 = no remap
     int exp;               // ablation switches (profiles/measure_chan_fft.py; compile-time variants of the P = 8 kernel): 1 = one store per lane, 2 = no inter-stage twiddles
     long long abs0;
-    uint32_t inc;          // frequency shift (tetra_chan_set_shift); read by the SHIFT instantiations only, for which h holds the complex taps [800][2][P]
+    uint32_t inc;          // frequency shift (tetra_chan_set_shift); read by the SHIFT instantiations only
 };
 
 // SHIFT = true: the frequency-shifted bank (complex taps in the fold, one phasor per frame in the store: chan_fft_core.hpp).  SHIFT =
@@ -367,8 +367,8 @@ struct tetra_chan {
     int device = 0, last_hip = 0;
     int M = 0, P = 0, D = 0, L = 0, N1 = 0, N2 = 0, max_in = 0;
     std::vector<float> proto;
-    DevMem<float2> xbuf;        // [L-1 + max_in]: [history | new samples] of the call in flight
-    DevMem<float2> xalt;        // same size: receives the next call's history (one copy, then the two swap roles)
+    DelayLine<float2> line;     // the L - 1 samples before the next call's first; the staged kernels' buffers hold the call's new
+                                // samples behind them: [L-1 + max_in] = [history | new samples] of the call in flight
     DevMem<float> d_h;
     DevMem<float2> d_w1, d_w2, d_wm;
     DevMem<float> d_bc, d_ac;   // matrix-pipe form: the two constant block-twiddle operands (k_channelise_mfma)
@@ -392,32 +392,9 @@ struct tetra_chan {
 
 namespace {
 
-double bessel_i0(double x) {
-    double s = 1.0, t = 1.0;
-    for (int k = 1; k < 60; k++) {
-        t *= (x / (2.0 * k)) * (x / (2.0 * k));
-        s += t;
-        if (t < 1e-18 * s) break;
-    }
-    return s;
-}
-
 // Kaiser(beta 9)-windowed sinc, cutoff fc = cutoff_rel / (2M) cycles/sample, unity DC gain.
 void design_prototype(int M, int P, double cutoff_rel, std::vector<float>& h) {
-    const int L = M * P;
-    const double pi = 3.14159265358979323846, fc = cutoff_rel / (2.0 * (double)M), beta = 9.0;
-    std::vector<double> t(L);
-    double sum = 0.0;
-    for (int l = 0; l < L; l++) {
-        const double u = (double)l - 0.5 * (double)(L - 1);
-        const double sinc = (u == 0.0) ? 2.0 * fc : std::sin(2.0 * pi * fc * u) / (pi * u);
-        const double r = 2.0 * u / (double)(L - 1);
-        const double w = bessel_i0(beta * std::sqrt(1.0 - r * r > 0 ? 1.0 - r * r : 0.0)) / bessel_i0(beta);
-        t[l] = sinc * w;
-        sum += t[l];
-    }
-    h.resize(L);
-    for (int l = 0; l < L; l++) h[l] = (float)(t[l] / sum);
+    chandesign::kaiser_sinc(M * P, cutoff_rel / (2.0 * (double)M), 9.0, 1.0, h);
 }
 
 bool factor(int M, int& n1, int& n2) {
@@ -454,7 +431,7 @@ int upload_twiddles(tetra_chan* h) {
             }
         HIP_TRY(h, hipMemcpy(h->d_tw, t.data(), sizeof(float2) * t.size(), hipMemcpyHostToDevice));
         std::vector<float> ht((size_t)2 * chanfft::kM * h->P);
-        chanfft::fold_transpose_prototype(h->proto.data(), h->P, ht.data());
+        chanfft::fold_transpose_prototype(h->P, [&](int l) { return h->proto[l]; }, ht.data());
         HIP_TRY(h, hipMemcpy(h->d_ht, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice));
     }
     if (h->mfma) {
@@ -533,9 +510,7 @@ int tetra_chan_create(const tetra_chan_config_t* cfg, tetra_chan_t** out) {
     DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     // (the FFT kernel reads the caller's samples in place: its handles keep only the L - 1 samples of delay line, twice)
-    const size_t xelems = (size_t)h->L - 1 + (h->fft ? 0 : (size_t)h->max_in);
-    bool ok = h->xbuf.reserve(sizeof(float2) * xelems) == hipSuccess &&
-              h->xalt.reserve(sizeof(float2) * xelems) == hipSuccess &&
+    bool ok = h->line.reserve((size_t)h->L - 1, 1, h->fft ? 0 : (size_t)h->max_in) == hipSuccess &&
               h->d_h.reserve(sizeof(float) * h->L) == hipSuccess &&
               h->d_w1.reserve(sizeof(float2) * h->N1) == hipSuccess &&
               h->d_w2.reserve(sizeof(float2) * h->N2) == hipSuccess &&
@@ -547,7 +522,7 @@ int tetra_chan_create(const tetra_chan_config_t* cfg, tetra_chan_t** out) {
               hipEventCreate(h->ev[0].put()) == hipSuccess && hipEventCreate(h->ev[1].put()) == hipSuccess;
     if (ok && hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) h->cus = 256;
     int rc = ok ? upload_twiddles(h) : TETRA_ERR_NOMEM;
-    if (rc == TETRA_OK && hipMemset(h->xbuf, 0, sizeof(float2) * ((size_t)h->L - 1)) != hipSuccess) rc = TETRA_ERR_HIP;
+    if (rc == TETRA_OK && h->line.reset() != hipSuccess) rc = TETRA_ERR_HIP;
     if (rc != TETRA_OK) { delete h; return rc; }
     *out = h;
     return TETRA_OK;
@@ -571,19 +546,31 @@ int tetra_chan_frames_for(tetra_chan_t* h, int n_in) {
 namespace {
 // bytes per sample of a format; copy `n` samples starting at `first` of the caller's buffer into a complex64 buffer
 constexpr int kFmtBytes[3] = { 8, 4, 2 };
-int copy_samples(tetra_chan* h, int fmt, const void* d_x, size_t first, size_t n, float2* dst, hipStream_t s) {
-    if (n == 0) return TETRA_OK;
-    if (fmt == chanfft::kFmtC32) {
-        HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
-        return TETRA_OK;
-    }
+hipError_t copy_samples(int fmt, const void* d_x, size_t first, size_t n, float2* dst, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (fmt == chanfft::kFmtC32) return hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s);
     const dim3 grid((unsigned)((n + 255) / 256));
     if (fmt == chanfft::kFmtCs16) hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs16>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
     else hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs8>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
-    HIP_TRY(h, hipGetLastError());
-    return TETRA_OK;
+    return hipGetLastError();
 }
-template <int FMT> void launch_fft(tetra_chan* h, const ChanFftParams& p, dim3 grid, hipStream_t s);
+// The one place that turns a handle's (taps per channel, sample format, shifted or not) into template arguments:
+// f(Int<P>, Int<FMT>, bool_constant<SHIFT>) for the three tap counts that have FFT and matrix kernels (p_ok in tetra_chan_create).
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> void with_variant(int P, int fmt, bool shift, F f) {
+    auto with_shift = [&](auto p, auto m) {
+        if (shift) f(p, m, std::true_type());
+        else f(p, m, std::false_type());
+    };
+    auto with_fmt = [&](auto p) {
+        if (fmt == chanfft::kFmtCs16) with_shift(p, Int<chanfft::kFmtCs16>());
+        else if (fmt == chanfft::kFmtCs8) with_shift(p, Int<chanfft::kFmtCs8>());
+        else with_shift(p, Int<chanfft::kFmtC32>());
+    };
+    if (P == 8) with_fmt(Int<8>());
+    else if (P == 6) with_fmt(Int<6>());
+    else with_fmt(Int<4>());
+}
 // complex elements of the modulated prototype: the FFT kernel's fold layout holds every tap twice ([800][2][P], as d_ht), the others [L]
 size_t hc_elems(const tetra_chan* h) { return h->fft ? (size_t)2 * chanfft::kM * h->P : (size_t)h->L; }
 
@@ -601,8 +588,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     // The FFT kernel reads the new samples where the caller left them (and the L - 1 before them from the handle's delay line): no
     // staging copy -- every sample crosses HBM once.  The other two kernels index one contiguous [history | new] buffer.
     if (n_in > 0 && !h->fft) {
-        const int rc = copy_samples(h, fmt, d_x, 0, (size_t)n_in, h->xbuf + hist, s);
-        if (rc != TETRA_OK) return rc;
+        HIP_TRY(h, copy_samples(fmt, d_x, 0, (size_t)n_in, h->line + hist, s));
     }
     // a new shift's taps go up here, in stream order behind everything enqueued before this call and ahead of its kernel
     if (h->hc_dirty) {
@@ -615,7 +601,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
     if (frames > 0 && h->fft) {
         ChanFftParams p;
-        p.x = d_x; p.hist = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.tw = h->d_tw;
+        p.x = d_x; p.hist = h->line; p.out = reinterpret_cast<float2*>(d_out); p.tw = h->d_tw;
         p.h = shift ? reinterpret_cast<const float*>(h->d_hc.get()) : h->d_ht.get();
         p.inc = h->inc;
         p.frames = frames; p.blocks = (frames + chanfft::kBlockFrames - 1) / chanfft::kBlockFrames; p.n_in = n_in;
@@ -637,34 +623,30 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         else if (fmt == chanfft::kFmtC32 && h->P == 8 && p.exp == 3) hipLaunchKernelGGL((k_channelise_fft<8, 3>), grid, dim3(kThreads), 0, s, p);
         else
 #endif
-        if (fmt == chanfft::kFmtCs16) launch_fft<chanfft::kFmtCs16>(h, p, grid, s);
-        else if (fmt == chanfft::kFmtCs8) launch_fft<chanfft::kFmtCs8>(h, p, grid, s);
-        else launch_fft<chanfft::kFmtC32>(h, p, grid, s);
+        with_variant(h->P, fmt, shift, [&](auto P, auto FMT, auto SHIFT) {
+            hipLaunchKernelGGL((k_channelise_fft<decltype(P)::value, 0, decltype(FMT)::value, decltype(SHIFT)::value>), grid, dim3(kThreads), 0, s, p);
+        });
         HIP_TRY(h, hipGetLastError());
     } else if (frames > 0 && h->mfma) {
         ChanMfmaParams p;
-        p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h; p.bc = h->d_bc; p.ac = h->d_ac; p.wm = h->d_wm;
+        p.xbuf = h->line; p.out = reinterpret_cast<float2*>(d_out); p.bc = h->d_bc; p.ac = h->d_ac; p.wm = h->d_wm;
+        p.h = shift ? reinterpret_cast<const float*>(h->d_hc.get()) : h->d_h.get();
         p.P = h->P; p.D = h->D; p.frames = frames; p.ph0 = h->phase; p.abs0 = h->consumed; p.inc = h->inc;
-        if (shift) p.h = reinterpret_cast<const float*>(h->d_hc.get());
         // workgroups loop over frames (the constant operands are loaded once per workgroup): a few per CU keep the matrix pipe,
         // the fold's loads and the stores of different frames overlapping
         const int per_cu = shift ? 2 : 3;                                 // workgroups that fit a CU (registers, LDS; the shifted form's complex taps double hs)
         const int grid = frames < per_cu * h->cus ? frames : per_cu * h->cus;      // each loops over its frames
-        if (shift) {
-            if (h->P == 8) hipLaunchKernelGGL((k_channelise_mfma<8, true>), dim3(grid), dim3(kThreads), 0, s, p);
-            else if (h->P == 6) hipLaunchKernelGGL((k_channelise_mfma<6, true>), dim3(grid), dim3(kThreads), 0, s, p);
-            else hipLaunchKernelGGL((k_channelise_mfma<4, true>), dim3(grid), dim3(kThreads), 0, s, p);
-        }
-        else if (h->P == 8) hipLaunchKernelGGL(k_channelise_mfma<8>, dim3(grid), dim3(kThreads), 0, s, p);
-        else if (h->P == 6) hipLaunchKernelGGL(k_channelise_mfma<6>, dim3(grid), dim3(kThreads), 0, s, p);
-        else hipLaunchKernelGGL(k_channelise_mfma<4>, dim3(grid), dim3(kThreads), 0, s, p);
+        with_variant(h->P, chanfft::kFmtC32, shift, [&](auto P, auto, auto SHIFT) {      // (reads the staged complex64 samples whatever the call's format)
+            hipLaunchKernelGGL((k_channelise_mfma<decltype(P)::value, decltype(SHIFT)::value>), dim3(grid), dim3(kThreads), 0, s, p);
+        });
         HIP_TRY(h, hipGetLastError());
     } else if (frames > 0) {
         ChanParams p;
-        p.xbuf = h->xbuf; p.out = reinterpret_cast<float2*>(d_out); p.h = h->d_h;
+        p.xbuf = h->line; p.out = reinterpret_cast<float2*>(d_out);
+        p.h = shift ? reinterpret_cast<const float*>(h->d_hc.get()) : h->d_h.get();
         p.w1 = h->d_w1; p.w2 = h->d_w2; p.wm = h->d_wm;
         p.M = h->M; p.P = h->P; p.D = h->D; p.N1 = h->N1; p.N2 = h->N2;
-        p.ph0 = h->phase; p.abs0 = h->consumed; p.hc = h->d_hc; p.inc = h->inc;
+        p.ph0 = h->phase; p.abs0 = h->consumed; p.inc = h->inc;
         const size_t lds_bytes = sizeof(float2) * ((size_t)h->M + (size_t)h->N1 * (h->N2 + 1));
         if (shift) hipLaunchKernelGGL(k_channelise<true>, dim3(frames), dim3(kThreads), lds_bytes + sizeof(float2), s, p);
         else hipLaunchKernelGGL(k_channelise<false>, dim3(frames), dim3(kThreads), lds_bytes, s, p);
@@ -672,34 +654,16 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     }
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     h->ev_valid = true;
-    // carry: the last L-1 samples of [history | new] become the next call's history -- ONE copy into the other buffer
-    // (whatever n_in is; an in-place move would overlap for n_in < L-1), then the buffers swap roles.  Stream order keeps the
-    // kernel above ahead of the copy and the copy ahead of the next call's writes.
-    if (n_in > 0 && h->fft) {
-        // the same from the two places the samples live in: what is left of the old delay line, then the tail of the caller's buffer
-        const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
-        if (keep) HIP_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * keep, hipMemcpyDeviceToDevice, s));
-        const int rc = copy_samples(h, fmt, d_x, (size_t)n_in - from_x, from_x, h->xalt + keep, s);
-        if (rc != TETRA_OK) return rc;
-        std::swap(h->xbuf, h->xalt);
-    } else if (n_in > 0) {
-        HIP_TRY(h, hipMemcpyAsync(h->xalt, h->xbuf + n_in, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
-        std::swap(h->xbuf, h->xalt);
+    // carry (DelayLine): the FFT route's new samples are still where the caller left them, in the call's format; the staged routes'
+    // lie behind the line already
+    if (h->fft) {
+        HIP_TRY(h, h->line.carry((size_t)n_in, s, [&](float2* dst, size_t from_x) { return copy_samples(fmt, d_x, (size_t)n_in - from_x, from_x, dst, s); }));
+    } else {
+        HIP_TRY(h, h->line.carry_staged((size_t)n_in, s));
     }
     h->phase = (h->phase + n_in) % h->D;
     h->consumed += n_in;
     return TETRA_OK;
-}
-template <int FMT> void launch_fft(tetra_chan* h, const ChanFftParams& p, dim3 grid, hipStream_t s) {
-    if (h->inc != 0) {
-        if (h->P == 8) hipLaunchKernelGGL((k_channelise_fft<8, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
-        else if (h->P == 6) hipLaunchKernelGGL((k_channelise_fft<6, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
-        else hipLaunchKernelGGL((k_channelise_fft<4, 0, FMT, true>), grid, dim3(kThreads), 0, s, p);
-        return;
-    }
-    if (h->P == 8) hipLaunchKernelGGL((k_channelise_fft<8, 0, FMT>), grid, dim3(kThreads), 0, s, p);
-    else if (h->P == 6) hipLaunchKernelGGL((k_channelise_fft<6, 0, FMT>), grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL((k_channelise_fft<4, 0, FMT>), grid, dim3(kThreads), 0, s, p);
 }
 }  // namespace
 
@@ -743,7 +707,7 @@ int tetra_chan_reset(tetra_chan_t* h) {
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemset(h->xbuf, 0, sizeof(float2) * ((size_t)h->L - 1)));
+    HIP_TRY(h, h->line.reset());
     h->phase = 0;
     h->consumed = 0;
     return TETRA_OK;
@@ -767,16 +731,11 @@ int tetra_chan_set_shift(tetra_chan_t* h, uint32_t inc) {
         HIP_TRY(h, hipEventSynchronize(h->ev_hc));
         h->hc_in_flight = false;
     }
-    // hc[l] = h[l] exp(+j 2 pi inc l / 2^32): the phase inc l mod 2^32 in integers, cos / sin in double
-    if (h->fft) {
-        chanfft::fold_transpose_prototype_shifted(h->proto.data(), h->P, inc, reinterpret_cast<chanfft::c32*>(h->hc_host.get()));
-    } else {
-        const double two_pi = 6.283185307179586476925286766559;
-        for (int l = 0; l < h->L; l++) {
-            const double a = two_pi * (double)(uint32_t)(inc * (uint32_t)l) / 4294967296.0;
-            h->hc_host.get()[l] = make_float2((float)((double)h->proto[l] * std::cos(a)), (float)((double)h->proto[l] * std::sin(a)));
-        }
-    }
+    // hc[l] (chanfft::modulated_tap), in the fold's order for the FFT kernel and as [L] for the other two
+    chanfft::c32* hc = reinterpret_cast<chanfft::c32*>(h->hc_host.get());
+    auto tap = [&](int l) { return chanfft::modulated_tap(h->proto.data(), inc, l); };
+    if (h->fft) chanfft::fold_transpose_prototype(h->P, tap, hc);
+    else for (int l = 0; l < h->L; l++) hc[l] = tap(l);
     h->inc = inc;
     h->hc_dirty = true;         // uploaded at the head of the next process call, on its stream
     return TETRA_OK;

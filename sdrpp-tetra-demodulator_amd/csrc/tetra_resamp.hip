@@ -9,10 +9,10 @@
 #include <cmath>
 #include <cstring>
 #include <new>
-#include <utility>
 #include <vector>
 
 #include "../../include/tetra_chan.h"
+#include "chan_design.hpp"
 #include "hip_host.hpp"
 #include "resamp_core.hpp"
 #include "resamp_handle.hpp"
@@ -29,31 +29,19 @@ __device__ __forceinline__ long long remapped_block(int span) {
     return (long long)(blockIdx.x & 7) * span + (long long)(blockIdx.x >> 3);
 }
 
-template <int I, int DN, int T, int W> __global__ __launch_bounds__(kThreads) void k_resample(resamp::Ctx c, int span, long long blocks) {
+// The two kernels, over every column in place (no Cols: resamp::AllColumns) or over picked columns (Cols = resamp::PickColumns, the
+// wideband receiver's carriers: one channel per lane unit, read from column cols.col[u] of the channeliser's rows).  The column map
+// keeps the place it has had in the argument list, so both forms keep their kernarg layout; Cols is always named, never deduced.
+template <int I, int DN, int T, int W, class... Cols> __global__ __launch_bounds__(kThreads) void k_resample(resamp::Ctx c, Cols... cols, int span, long long blocks) {
     const long long b = remapped_block(span);
     if (b >= blocks) return;
-    resamp::thread_fixed<I, DN, T, W>(c, b * kThreads + threadIdx.x);
+    resamp::thread_fixed<I, DN, T, W>(c, b * kThreads + threadIdx.x, cols...);
 }
 
-template <int W> __global__ __launch_bounds__(kThreads) void k_resample_generic(resamp::Ctx c, int span, long long blocks) {
+template <int W, class... Cols> __global__ __launch_bounds__(kThreads) void k_resample_generic(resamp::Ctx c, Cols... cols, int span, long long blocks) {
     const long long b = remapped_block(span);
     if (b >= blocks) return;
-    resamp::thread_generic<W>(c, b * kThreads + threadIdx.x);
-}
-
-// The same two kernels over picked columns (the wideband receiver's carriers): one channel per lane unit, read from column
-// cols.col[u] of the channeliser's rows.
-template <int I, int DN, int T> __global__ __launch_bounds__(kThreads) void k_resample_pick(resamp::Ctx c, resamp::PickColumns cols, int span,
-                                                                                         long long blocks) {
-    const long long b = remapped_block(span);
-    if (b >= blocks) return;
-    resamp::thread_fixed<I, DN, T, 2>(c, b * kThreads + threadIdx.x, cols);
-}
-
-__global__ __launch_bounds__(kThreads) void k_resample_pick_generic(resamp::Ctx c, resamp::PickColumns cols, int span, long long blocks) {
-    const long long b = remapped_block(span);
-    if (b >= blocks) return;
-    resamp::thread_generic<2>(c, b * kThreads + threadIdx.x, cols);
+    resamp::thread_generic<W>(c, b * kThreads + threadIdx.x, cols...);
 }
 
 // rows [first, first + rows) of frames [*][in_ch], columns cols[0 .. n) -> out [rows][n] (the picked delay line)
@@ -66,66 +54,34 @@ __global__ __launch_bounds__(256) void k_pick_rows(const float2* __restrict__ in
     out[i] = in[(first + r) * in_ch + cols[j]];
 }
 
-template <int I, int DN, int T> struct FullKernel {
-    static fixed_kernel_t get(int W) { return W == 4 ? (fixed_kernel_t)k_resample<I, DN, T, 4> : (fixed_kernel_t)k_resample<I, DN, T, 2>; }
-};
-template <int I, int DN, int T> struct PickKernel {
-    static pick_kernel_t get() { return (pick_kernel_t)k_resample_pick<I, DN, T>; }
-};
-
-// K<I, DN, T>::get(a...) for the ratios and lengths that have a kernel specialised at compile time, nullptr for any other
-template <template <int, int, int> class K, class... A> auto pick_ratio(int I, int DN, int T, A... a) -> decltype(K<18, 25, 8>::get(a...)) {
-    if (I == 18 && DN == 25) {
-        if (T == 8) return K<18, 25, 8>::get(a...);
-        if (T == 12) return K<18, 25, 12>::get(a...);
-        if (T == 16) return K<18, 25, 16>::get(a...);
-        if (T == 24) return K<18, 25, 24>::get(a...);
-    }
-    if (T == 8) {
-        if (I == 2 && DN == 3) return K<2, 3, 8>::get(a...);
-        if (I == 3 && DN == 2) return K<3, 2, 8>::get(a...);
-        if (I == 1 && DN == 2) return K<1, 2, 8>::get(a...);
-    }
-    return nullptr;
+// the kernels of a ratio in resamp_core.hpp's table, nullptr for any other
+fixed_kernel_t pick_fixed(int I, int DN, int T, int W) {
+    fixed_kernel_t k = nullptr;
+    resamp::visit_ratio(I, DN, T, [&](auto r) {
+        using R = decltype(r);
+        k = W == 4 ? (fixed_kernel_t)k_resample<R::I, R::DN, R::T, 4> : (fixed_kernel_t)k_resample<R::I, R::DN, R::T, 2>;
+    });
+    return k;
 }
-
-fixed_kernel_t pick_fixed(int I, int DN, int T, int W) { return pick_ratio<FullKernel>(I, DN, T, W); }
-
-double bessel_i0(double x) {
-    double s = 1.0, t = 1.0;
-    for (int k = 1; k < 60; k++) {
-        t *= (x / (2.0 * k)) * (x / (2.0 * k));
-        s += t;
-        if (t < 1e-18 * s) break;
-    }
-    return s;
+pick_kernel_t pick_picked(int I, int DN, int T) {
+    pick_kernel_t k = nullptr;
+    resamp::visit_ratio(I, DN, T, [&](auto r) {
+        using R = decltype(r);
+        k = (pick_kernel_t)k_resample<R::I, R::DN, R::T, 2, resamp::PickColumns>;
+    });
+    return k;
 }
 
 // Kaiser-windowed sinc at the zero-stuffed rate, cutoff fc = cutoff_rel / (2 max(I, DN)) cycles per sample there (= cutoff_rel x the
 // narrower of the input and output Nyquist bands), DC gain I.
 void design_prototype(int I, int DN, int T, double cutoff_rel, double beta, std::vector<float>& h) {
-    const int L = I * T;
-    const double pi = 3.14159265358979323846, fc = cutoff_rel / (2.0 * (double)(I > DN ? I : DN));
-    std::vector<double> t(L);
-    double sum = 0.0;
-    for (int l = 0; l < L; l++) {
-        const double u = (double)l - 0.5 * (double)(L - 1);
-        const double sinc = (u == 0.0) ? 2.0 * fc : std::sin(2.0 * pi * fc * u) / (pi * u);
-        const double r = L > 1 ? 2.0 * u / (double)(L - 1) : 0.0;
-        const double w = bessel_i0(beta * std::sqrt(1.0 - r * r > 0 ? 1.0 - r * r : 0.0)) / bessel_i0(beta);
-        t[l] = sinc * w;
-        sum += t[l];
-    }
-    h.resize(L);
-    for (int l = 0; l < L; l++) h[l] = (float)(t[l] / sum * (double)I);
+    chandesign::kaiser_sinc(I * T, cutoff_rel / (2.0 * (double)(I > DN ? I : DN)), beta, (double)I, h);
 }
 
 }  // namespace
 
 
 namespace {
-
-size_t hist_bytes(const tetra_resamp* h) { return sizeof(float) * 2 * (size_t)h->C * (size_t)(h->T - 1); }
 
 // One call's kernel and delay-line carry.  d_cols = nullptr: every column in place (in_ch = C); else the C picked columns of rows of
 // in_ch channels.  The arguments are checked by the caller.
@@ -150,7 +106,7 @@ int process_any(tetra_resamp* h, const int32_t* d_cols, int in_ch, const float* 
             resamp::PickColumns cols;
             cols.col = d_cols; cols.in_units = in_ch;
             if (h->pick) hipLaunchKernelGGL(h->pick, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
-            else hipLaunchKernelGGL(k_resample_pick_generic, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
+            else hipLaunchKernelGGL((k_resample_generic<2, resamp::PickColumns>), dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
         } else if (h->fixed) hipLaunchKernelGGL(h->fixed, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
         else if (h->W == 4) hipLaunchKernelGGL(k_resample_generic<4>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
         else hipLaunchKernelGGL(k_resample_generic<2>, dim3(8 * span), dim3(kThreads), 0, s, c, span, blocks);
@@ -158,23 +114,15 @@ int process_any(tetra_resamp* h, const int32_t* d_cols, int in_ch, const float* 
     }
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     h->ev_valid = true;
-    // carry: the last T - 1 frames of [delay line | new] (their picked columns) become the next call's delay line -- into the OTHER
-    // buffer (an in-place move would overlap for n_in < T - 1), then the two swap roles.  Stream order keeps the kernel ahead of the copies.
-    if (n_in > 0) {
-        const size_t row = sizeof(float) * 2 * (size_t)h->C, hist = (size_t)h->T - 1;
-        const size_t from_x = (size_t)n_in < hist ? (size_t)n_in : hist, keep = hist - from_x;
-        if (keep) HIP_TRY(h, hipMemcpyAsync(h->halt, (const char*)h->hist.get() + row * (size_t)n_in, row * keep, hipMemcpyDeviceToDevice, s));
-        if (d_cols) {
-            const long long n = (long long)from_x * h->C;
-            hipLaunchKernelGGL(k_pick_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float2*>(d_in), in_ch, d_cols, h->C,
-                               (long long)n_in - (long long)from_x, (int)from_x, reinterpret_cast<float2*>(h->halt.get() + 2 * (size_t)h->C * keep));
-            HIP_TRY(h, hipGetLastError());
-        } else {
-            HIP_TRY(h, hipMemcpyAsync((char*)h->halt.get() + row * keep, (const char*)d_in + row * ((size_t)n_in - from_x), row * from_x,
-                                     hipMemcpyDeviceToDevice, s));
-        }
-        std::swap(h->hist, h->halt);
-    }
+    // carry (DelayLine): the newest frames' rows as they are, or their picked columns
+    const size_t row = 2 * (size_t)h->C;
+    HIP_TRY(h, h->hist.carry((size_t)n_in, s, [&](float* dst, size_t from_x) {
+        if (!d_cols) return hipMemcpyAsync(dst, d_in + row * ((size_t)n_in - from_x), sizeof(float) * row * from_x, hipMemcpyDeviceToDevice, s);
+        const long long n = (long long)from_x * h->C;
+        hipLaunchKernelGGL(k_pick_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float2*>(d_in), in_ch, d_cols, h->C,
+                           (long long)n_in - (long long)from_x, (int)from_x, reinterpret_cast<float2*>(dst));
+        return hipGetLastError();
+    }));
     h->n_total += n_in;
     h->m_next = m1;
     return TETRA_OK;
@@ -243,18 +191,18 @@ int tetra_resamp_create(const tetra_resamp_config_t* cfg, tetra_resamp_t** out) 
     if (cfg->prototype) h->proto.assign(cfg->prototype, cfg->prototype + (size_t)h->I * h->T);
     else design_prototype(h->I, h->DN, h->T, cfg->cutoff_rel, cfg->kaiser_beta, h->proto);
     h->fixed = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_fixed(h->I, h->DN, h->T, h->W);
-    h->pick = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_ratio<PickKernel>(h->I, h->DN, h->T);
+    h->pick = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_picked(h->I, h->DN, h->T);
     DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     std::vector<float> coef((size_t)h->I * h->T);
     if (h->fixed) resamp::phase_table(h->proto.data(), h->I, h->DN, h->T, coef.data());
     else coef = h->proto;
     bool ok = h->d_coef.reserve(sizeof(float) * coef.size()) == hipSuccess &&
-              h->hist.reserve(hist_bytes(h)) == hipSuccess && h->halt.reserve(hist_bytes(h)) == hipSuccess &&
+              h->hist.reserve((size_t)h->T - 1, 2 * (size_t)h->C) == hipSuccess &&
               hipEventCreate(h->ev[0].put()) == hipSuccess && hipEventCreate(h->ev[1].put()) == hipSuccess;
     int rc = ok ? TETRA_OK : TETRA_ERR_NOMEM;
     if (rc == TETRA_OK && (hipMemcpy(h->d_coef, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                           hipMemset(h->hist, 0, hist_bytes(h)) != hipSuccess))
+                           h->hist.reset() != hipSuccess))
         rc = TETRA_ERR_HIP;
     if (rc != TETRA_OK) { delete h; return rc; }
     *out = h;
@@ -306,7 +254,7 @@ int tetra_resamp_reset(tetra_resamp_t* h) {
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemset(h->hist, 0, hist_bytes(h)));
+    HIP_TRY(h, h->hist.reset());
     h->n_total = 0;
     h->m_next = 0;
     return TETRA_OK;

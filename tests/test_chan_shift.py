@@ -3,7 +3,7 @@
 Expected values come from the DEFINITION, written out below in numpy complex128 (ShiftedBankDefinition): the un-shifted bank's sum
 with the modulated prototype hc[l] = h[l] exp(+j 2 pi inc l / 2^32) and the frame phasor exp(-j 2 pi (inc n_m mod 2^32) / 2^32), both
 phases in integer arithmetic -- cross-checked once against oracle.ChanOracle run on the premixed signal.  Against it: the FFT
-kernel's shifted lane code on the host (tests/emul/chan_shift_emul.cpp) and all three kernels on the GPU."""
+kernel's shifted lane code on the host (tests/emul/chan_emul.cpp) and all three kernels on the GPU."""
 import ctypes as C
 import os
 import re
@@ -99,7 +99,7 @@ def test_shifted_lane_code_on_the_host_matches_the_definition(oracle, P, inc):
     the output rows, so an unwritten or overwritten phasor slot shows as NaN.  Bound 3e-6 of the output's maximum: the un-shifted
     lane code is held to 2e-6 (test_chan.py); the shifted one adds two roundings per tap (re and im of hc, 2^-24 each, P-term sums),
     one complex multiply per output (2^-23) and the phasor's 2^-24 phase quantum (1.9e-7 rad) -- under 1e-6 together."""
-    from tests.emul import chan_shift_emul_bind as cs
+    from tests.emul import chan_emul_bind as cs
     rng = np.random.default_rng(100 * P + inc % 97)
     h = oracle.ChanOracle(800, P, 400).h
     nin = 400 * 19 + 123
@@ -121,7 +121,7 @@ def test_shifted_lane_code_on_the_host_matches_the_definition(oracle, P, inc):
 
 
 def test_set_shift_mid_stream_on_the_host_keeps_the_phase_reference(oracle):
-    from tests.emul import chan_shift_emul_bind as cs
+    from tests.emul import chan_emul_bind as cs
     rng = np.random.default_rng(8)
     h = oracle.ChanOracle(800, 8, 400).h
     x = _noise(rng, 400 * 30 + 77)
@@ -135,30 +135,43 @@ def test_set_shift_mid_stream_on_the_host_keeps_the_phase_reference(oracle):
         assert ye.shape == yd.shape and np.abs(ye - yd).max() / np.abs(yd).max() < 3e-6, i
 
 
-@pytest.mark.parametrize("dtype", [np.complex64, np.int16, np.int8])
-def test_shift_zero_through_the_new_emulation_equals_the_existing_emulation(oracle, dtype):
-    """inc = 0: the new emulation's dispatch (un-shifted instantiations, as the library's) equals tests/emul/chan_emul.cpp bit for
-    bit; and the SHIFT = true lane code itself at inc = 0 (taps (h, 0), phasor (1, -0)) gives the same numbers (x . 1 - y . 0 is
-    exact; only the sign of a zero can differ, hence array_equal on values)."""
-    from tests.emul import chan_emul_bind as ce
-    from tests.emul import chan_shift_emul_bind as cs
+SHIFT_ZERO_NIN = 400 * 17 + 55
+SHIFT_ZERO_CUTS = [0, 9, 9 + 399, SHIFT_ZERO_NIN // 2, SHIFT_ZERO_NIN]
+
+
+def shift_zero_inputs(dtype):
+    """(P, samples) of the shift-zero test, P = 4, 6, 8 off one generator (tests/golden/make_front_end_golden.py records from these)."""
     rng = np.random.default_rng(4)
     for P in (4, 6, 8):
+        x = _noise(rng, SHIFT_ZERO_NIN)
+        yield P, (x if dtype == np.complex64 else _quantise(x.astype(np.complex128), dtype)[0])
+
+
+@pytest.mark.parametrize("dtype", [np.complex64, np.int16, np.int8])
+def test_shift_zero_through_the_new_emulation_equals_the_existing_emulation(oracle, dtype):
+    """inc = 0: the emulation's dispatch (un-shifted instantiations, as the library's) equals, bit for bit, the rows that
+    tests/emul/chan_emul.cpp gave before the shifted emulation was folded into it (tests/golden/chan_emul_unshifted.npz: the first
+    and last frame of every call; no libm call on this path); and the SHIFT = true lane code itself at inc = 0 (taps (h, 0), phasor
+    (1, -0)) gives the same numbers (x . 1 - y . 0 is exact; only the sign of a zero can differ, hence array_equal on values)."""
+    from tests.emul import chan_emul_bind as ce
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "chan_emul_unshifted.npz"))
+    assert list(gold["cuts"]) == SHIFT_ZERO_CUTS
+    for P, x in shift_zero_inputs(dtype):
         h = oracle.ChanOracle(800, P, 400).h
-        nin = 400 * 17 + 55
-        x = _noise(rng, nin)
-        if dtype != np.complex64:
-            x = _quantise(x.astype(np.complex128), dtype)[0]
-        old, new, forced = ce.ChanFftEmul(P, h), cs.ChanFftShiftEmul(P, h, 0), cs.ChanFftShiftEmul(P, h, 0, force_shift_code=True)
-        cuts = [0, 9, 9 + 399, nin // 2, nin]
-        for a, b in zip(cuts, cuts[1:]):
-            yo, yn, yf = old.process(x[a:b]), new.process(x[a:b]), forced.process(x[a:b])
-            assert np.array_equal(yo.view(np.uint32), yn.view(np.uint32)), (P, a, b)
-            assert np.array_equal(yo, yf), (P, a, b)
+        plain, forced = ce.ChanFftShiftEmul(P, h, 0), ce.ChanFftShiftEmul(P, h, 0, force_shift_code=True)
+        first = ce.ChanFftEmul(P, h)
+        rows = []
+        for a, b in zip(SHIFT_ZERO_CUTS, SHIFT_ZERO_CUTS[1:]):
+            yn, yf = plain.process(x[a:b]), forced.process(x[a:b])
+            assert np.array_equal(yn.view(np.uint32), first.process(x[a:b]).view(np.uint32)), (P, a, b)
+            assert np.array_equal(yn, yf), (P, a, b)
+            rows.append(yn)
+        want = gold["%s_P%d" % (np.dtype(dtype).name, P)]
+        assert np.array_equal(np.concatenate(rows)[gold["keep"]].view(np.uint32), want.view(np.uint32)), P
 
 
 def test_host_phasor_is_the_integer_phase(oracle):
-    from tests.emul import chan_shift_emul_bind as cs
+    from tests.emul import chan_emul_bind as cs
     for ph in (0, 1, TWO32 // 4, TWO32 // 2, TWO32 - 1, ODD_LARGE, 0x12345678):
         assert abs(cs.phasor(ph) - np.exp(-2j * np.pi * ph / TWO32)) < 3e-7, ph
 

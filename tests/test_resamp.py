@@ -92,6 +92,25 @@ def test_kernel_thread_code_on_the_host_matches_the_definition(oracle, I, DN, T,
         print("resamp_emul_error I %d DN %d T %d C %d: %.3e" % (I, DN, T, C, worst))
 
 
+@pytest.mark.parametrize("name", ["full_w4", "full_w2", "full_generic_w4", "full_generic_w2", "pick", "pick_generic"])
+def test_emulation_equals_the_recorded_rows(name):
+    """One small case per kernel wrapper -- (18, 25, 16) on 10 channels with 16-byte and 8-byte lane units and over three picked
+    columns, the generic kernel at (5, 7, 11) likewise -- against the rows the emulation gave before the picking variant was folded
+    into it (tests/golden/resamp_emul.npz, written by tests/golden/make_front_end_golden.py: input, prototype and ragged cuts are in
+    the file; no libm call on this path): bit for bit."""
+    import os
+    from tests.emul import resamp_emul_bind as re_
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resamp_emul.npz"))
+    I, DN, T, W, generic = (int(v) for v in g[name + "_case"])
+    x, cuts = g["x"], list(g["cuts"])
+    if W:
+        em = re_.ResampEmul(x.shape[1], I, DN, T, g[name + "_proto"], generic=bool(generic), W=W)
+    else:
+        em = re_.ResampSelectEmul(x.shape[1], g["cols"], I, DN, T, g[name + "_proto"], generic=bool(generic))
+    got = np.concatenate([em.process(x[a:b]) for a, b in zip(cuts, cuts[1:])])
+    assert got.shape == g[name].shape and np.array_equal(got.view(np.uint32), g[name].view(np.uint32))
+
+
 def test_resampler_header_symbols_all_exported(pkg):
     import os
     import re

@@ -59,14 +59,24 @@ def test_wbrx_no_cpu_fallback(pkg):
     assert e.value.status == ERR_NO_DEVICE
 
 
-@pytest.mark.parametrize("M,I,DN,T,generic", [(32, 18, 25, 16, False), (800, 18, 25, 16, False), (32, 18, 25, 8, False),
-                                              (32, 2, 3, 8, False), (32, 18, 25, 16, True), (12, 5, 7, 11, True)])
+def _picking_cases():
+    """Every triple of the product's table of specialised ratios (read from it through the emulation library, resamp_core.hpp) at M
+    = 32, the default ratio on the 800 bins of config 5, and two generic cases."""
+    from tests.emul import resamp_emul_bind as re_
+    return [(32, I, DN, T, False) for I, DN, T in re_.ratios()] + [(800, 18, 25, 16, False), (32, 18, 25, 16, True), (12, 5, 7, 11, True)]
+
+
+def test_ratio_table_is_the_documented_seven():
+    from tests.emul import resamp_emul_bind as re_
+    assert sorted(re_.ratios()) == sorted([(18, 25, 8), (18, 25, 12), (18, 25, 16), (18, 25, 24), (2, 3, 8), (3, 2, 8), (1, 2, 8)])
+
+
+@pytest.mark.parametrize("M,I,DN,T,generic", _picking_cases())
 def test_picking_thread_code_equals_full_resampler_then_column_pick(oracle, M, I, DN, T, generic):
     """The selecting resampler's thread code (resamp_core.hpp, PickColumns) compiled for the host over a random [frames][M] input,
     random bin subsets in random order, ragged calls (empty ones, calls shorter than one group of DN frames and than the delay line)
     equals the full resampler's host build followed by the column pick, bit for bit."""
     from tests.emul import resamp_emul_bind as re_
-    from tests.emul import resamp_select_emul_bind as rs_
     proto = oracle.ResampOracle(M, I, DN, T).h
     rng = np.random.default_rng(M + I + T + int(generic))
     n = 12 * DN + 29 if M > 100 else 40 * DN + 13
@@ -74,7 +84,7 @@ def test_picking_thread_code_equals_full_resampler_then_column_pick(oracle, M, I
     for trial in range(3):
         cols = rng.permutation(M)[: int(rng.integers(1, min(M, 40) + 1))].astype(np.int32)
         full = re_.ResampEmul(M, I, DN, T, proto, generic=generic)
-        pick = rs_.ResampSelectEmul(M, cols, I, DN, T, proto, generic=generic)
+        pick = re_.ResampSelectEmul(M, cols, I, DN, T, proto, generic=generic)
         cuts = sorted(set([0, 0, 1, 3, DN - 1, DN + 2, T + 5, 3 * DN + 1, int(rng.integers(4 * DN, n)), n]))
         cuts = [0] + cuts + [n]
         for a, b in zip(cuts, cuts[1:]):
@@ -195,6 +205,40 @@ def test_gpu_wbrx_equals_the_hand_wired_composition(pkg, small_capture, fmt):
     assert len(ms) == 2 and all(v >= 0 for v in ms)
     wb.close()
     rx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [8, 24])
+def test_gpu_wbrx_picked_columns_for_other_tap_counts(pkg, small_capture, T):
+    """The picking kernels of the table's other two 18 / 25 lengths (the demodulator keeps its 36 ksps): tetra_wbrx_frames_device
+    equals Channeliser(32) -> Resampler(32, T) -> column pick bit for bit, over one call of a few thousand samples, a ragged one
+    that brings fewer frames than the picked delay line holds, and one behind it that reads that line."""
+    import torch
+    x = small_capture[0]
+    cuts = [0, 4099, 4099 + 37, 4099 + 37 + 1000]
+    max_in = 4099
+    wb = pkg.WidebandRx(BINS_SMALL, n_channels=M_SMALL, decimation=D_SMALL, max_in=max_in, taps_per_phase=T)
+    ch = pkg.Channeliser(M_SMALL, decimation=D_SMALL, max_in=max_in)
+    rs = pkg.Resampler(M_SMALL, taps_per_phase=T, max_in=(D_SMALL - 1 + max_in) // D_SMALL)
+    chan_buf = torch.zeros(((D_SMALL - 1 + max_in) // D_SMALL, M_SMALL), dtype=torch.complex64, device="cuda")
+    res_buf = torch.zeros((_small_max_samples(max_in), M_SMALL), dtype=torch.complex64, device="cuda")
+    cols = torch.tensor(BINS_SMALL, device="cuda")
+    s = torch.cuda.current_stream()
+    total = 0
+    for a, b in zip(cuts, cuts[1:]):
+        wb.process_device(x[a:b], b - a, s)
+        nf = ch.process_device(x[a:b], b - a, chan_buf, s)
+        nr = rs.process_device(chan_buf, nf, res_buf, s)
+        picked = res_buf[:nr][:, cols].contiguous()
+        got = wb.frames()
+        assert got.shape == picked.shape, (a, b)
+        assert torch.equal(torch.view_as_real(got).view(torch.int32), torch.view_as_real(picked).view(torch.int32)), (a, b)
+        total += nr
+        torch.cuda.synchronize()
+    assert total == (cuts[-1] // D_SMALL * 18 + 24) // 25
+    wb.close()
+    ch.close()
+    rs.close()
 
 
 def _assert_known_answer(pkg, synth, got, cell, cells, tx, nslots):
