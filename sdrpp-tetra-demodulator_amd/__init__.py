@@ -7,6 +7,6 @@ only builds it (build.py), binds it with ctypes (binding.py) and generates synth
 """
 from . import build, binding, chan_binding, scan_binding, lmac_binding, bsync_binding, rx_binding, wbrx_binding, synth, synth_gpu, shard  # noqa: F401
 from .binding import Demodulator, TetraDemodError, load_library  # noqa: F401
-from .chan_binding import Channeliser, Resampler  # noqa: F401
+from .chan_binding import Channeliser, Resampler, input_map_from_stats, iq_stats  # noqa: F401
 from .rx_binding import RxChain  # noqa: F401
 from .wbrx_binding import WidebandRx  # noqa: F401

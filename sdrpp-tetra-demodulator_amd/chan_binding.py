@@ -54,15 +54,83 @@ RESAMP_EXPORTS = [n for n in SIGNATURES if n.startswith("tetra_resamp_")]
 CHAN_SHIFT_EXPORTS = list(SHIFT_SIGNATURES)
 
 
+class IqMap(C.Structure):
+    """tetra_iq_map_t (include/ext/tetra_iqcond.h): (yr, yi) = (m00 xr + m01 xi + c0, m10 xr + m11 xi + c1)."""
+    _fields_ = [(n, C.c_float) for n in ("m00", "m01", "m10", "m11", "c0", "c1")]
+
+    def astuple(self):
+        return tuple(float(getattr(self, n)) for n, _ in self._fields_)
+
+
+class IqStats(C.Structure):
+    """tetra_iq_stats_t: the sums of n samples in the converted samples' unit."""
+    _fields_ = [("n", C.c_int64)] + [(n, C.c_double) for n in ("s_i", "s_q", "s_ii", "s_qq", "s_iq")]
+
+    def astuple(self):
+        return (int(self.n),) + tuple(float(getattr(self, n)) for n, _ in self._fields_[1:])
+
+
+# include/ext/tetra_iqcond.h (conditioning of the capture): the channeliser's share and the two handle-free entry points
+IQCOND_ABI = {
+    "tetra_chan_set_input_map": (i32, [vp, P(IqMap)]),
+    "tetra_chan_get_input_map": (i32, [vp, P(IqMap), P(i32)]),
+    "tetra_iq_stats_device": (i32, [vp, i32, C.c_longlong, P(IqStats), vp]),
+    "tetra_iq_map_from_stats": (i32, [P(IqStats), P(IqMap)]),
+}
+IQ_FMT_C64, IQ_FMT_CS16, IQ_FMT_CS8 = 0, 1, 2
+
+
 @functools.lru_cache(None)
 def _lib():
-    # (a TETRA_DEMOD_LIB override may be an older build without the shift)
-    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES}, optional=CHAN_SHIFT_EXPORTS)
+    # (a TETRA_DEMOD_LIB override may be an older build without the shift or the input map)
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **IQCOND_ABI}, optional=CHAN_SHIFT_EXPORTS + list(IQCOND_ABI))
 
 
 def shift_from_hz(shift_hz, sample_rate_hz):
     """tetra_chan_shift_from_hz: the increment (2^-32 cycles per input sample) of a shift in hertz; negative shifts wrap."""
     return int(_lib().tetra_chan_shift_from_hz(float(shift_hz), float(sample_rate_hz)))
+
+
+def as_iq_map(m):
+    """None stays None; an IqMap is passed through; six numbers (m00, m01, m10, m11, c0, c1) become one."""
+    if m is None or isinstance(m, IqMap):
+        return m
+    vals = [float(v) for v in m]
+    if len(vals) != 6:
+        raise ValueError("an input map has six coefficients: m00, m01, m10, m11, c0, c1")
+    return IqMap(*vals)
+
+
+def _set_input_map(fn, handle, m):
+    m = as_iq_map(m)
+    call(fn, handle, None if m is None else C.byref(m))
+
+
+def _get_input_map(fn, handle):
+    m, on = IqMap(), C.c_int(0)
+    call(fn, handle, C.byref(m), C.byref(on))
+    return m.astuple() if on.value else None
+
+
+def iq_stats(x, n=None, stream=None):
+    """tetra_iq_stats_device: the sums (IqStats) of a capture on the device -- a torch tensor, complex64 [n] or interleaved I / Q pairs
+    int16 / int8 [n][2] (as Channeliser.process_device); n: samples (default: all of the tensor)."""
+    dt = str(getattr(x, "dtype", ""))
+    fmt = {"torch.int16": IQ_FMT_CS16, "torch.int8": IQ_FMT_CS8}.get(dt, IQ_FMT_C64)
+    if n is None:
+        n = x.numel() // 2 if fmt != IQ_FMT_C64 else x.numel()
+    out = IqStats()
+    call(_lib().tetra_iq_stats_device, ptr(x) if n else None, fmt, int(n), C.byref(out), stream_ptr(stream))
+    return out
+
+
+def input_map_from_stats(stats):
+    """tetra_iq_map_from_stats (host only): the six coefficients that remove the DC offset and decorrelate and equalise I and Q."""
+    if not isinstance(stats, IqStats):
+        stats = IqStats(*stats)
+    m = IqMap()
+    call(_lib().tetra_iq_map_from_stats, C.byref(stats), C.byref(m))
+    return m.astuple()
 
 
 class Channeliser:
@@ -103,6 +171,15 @@ class Channeliser:
         v = C.c_uint32(0)
         call(self._lib.tetra_chan_get_shift, self._h, C.byref(v))
         return int(v.value)
+
+    def set_input_map(self, m):
+        """tetra_chan_set_input_map (include/ext/tetra_iqcond.h): six coefficients (m00, m01, m10, m11, c0, c1) or an IqMap; None returns
+        the handle to the un-conditioned kernels.  Between process calls; from the next call's first new sample."""
+        _set_input_map(self._lib.tetra_chan_set_input_map, self._h, m)
+
+    def get_input_map(self):
+        """The six coefficients in force, or None if no map is set."""
+        return _get_input_map(self._lib.tetra_chan_get_input_map, self._h)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "iqcond_core.hpp"
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define CHAN_HD __host__ __device__ __forceinline__
 #else
@@ -221,6 +223,15 @@ template <int FMT> CHAN_HD c32 load_sample(const void* x, long long s) {
     }
     return reinterpret_cast<const c32*>(x)[s];
 }
+// The conditioned form (include/ext/tetra_iqcond.h): the converted sample through the handle's input map.  Every load of a NEW sample of a
+// handle with a map set goes through this one function -- the FFT kernel's fold, the delay-line carry and the staging of the other two
+// kernels -- so the delay line holds conditioned samples and whoever reads it applies nothing.
+template <int FMT> CHAN_HD c32 load_sample(const void* x, long long s, const iqcond::Map& m) {
+    const c32 v = load_sample<FMT>(x, s);
+    c32 y;
+    iqcond::apply(m, v.x, v.y, y.x, y.y);
+    return y;
+}
 
 struct BlockCtx {
     const void* x;        // the call's n_in NEW samples in the format the kernel is compiled for, where the caller left them (read in place: no staging copy)
@@ -234,16 +245,19 @@ struct BlockCtx {
     long long abs0;       // absolute time of the first new sample
     int L;                // 800 P
     uint32_t inc;         // frequency shift in 2^-32 cycles per input sample (SHIFT instantiations only)
+    iqcond::Map map;      // the input map of the new samples (COND instantiations only)
 };
 
 // Sample s of the stream, s counted from the call's first new sample.  Blocks in the middle of a call read only new samples and
 // index the caller's buffer directly (CAREFUL = false).  The first two blocks reach back into the delay line (s < 0), and the last
 // block of a call whose frame count is not a multiple of 8 asks for samples past the call's end for the frames it does not store:
 // those read the last sample instead (any value would do: it only reaches results that are never stored).
-template <bool CAREFUL, int FMT> CHAN_HD c32 sample_at(const BlockCtx& c, long long s) {
-    if (!CAREFUL) return load_sample<FMT>(c.x, s);
-    if (s < 0) return c.hist[(c.L - 1) + s];
-    return load_sample<FMT>(c.x, s < c.n_in ? s : c.n_in - 1);
+// COND: the new samples go through the input map; the delay line holds conditioned samples already (the map of the call that delivered them).
+template <bool CAREFUL, int FMT, bool COND = false> CHAN_HD c32 sample_at(const BlockCtx& c, long long s) {
+    if (CAREFUL && s < 0) return c.hist[(c.L - 1) + s];
+    const long long at = !CAREFUL || s < c.n_in ? s : c.n_in - 1;
+    if (COND) return load_sample<FMT>(c.x, at, c.map);
+    return load_sample<FMT>(c.x, at);
 }
 // does a block with its first frame's newest sample at index newest0 need the careful accessor?  (it reads
 // [newest0 - (L - 1), newest0 + 7 * 400])
@@ -264,12 +278,12 @@ CHAN_HD void fold_tap(c32 hv, c32 xv, float& ar, float& ai) {
     ai += hv.x * xv.y;
     ai += hv.y * xv.x;
 }
-template <int P, int CLS, bool CAREFUL, int FMT, class Tap> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoef<P, Tap>& k, c32 out[kBlockFrames]) {
+template <int P, int CLS, bool CAREFUL, int FMT, bool COND = false, class Tap> CHAN_HD void fold_slot(const BlockCtx& c, long long s0, const FoldCoef<P, Tap>& k, c32 out[kBlockFrames]) {
     CHAN_FP_FAST
     constexpr int kS = P + 3 + CLS;                   // class 0 frames reach sample m = 3, class 1 frames m = 4
     c32 S[kS];                                        // S[j] = sample m = j - (P - 1) = stream sample s0 + 800 m  (s0 = newest0 - u)
 #pragma unroll
-    for (int j = 0; j < kS; j++) S[j] = sample_at<CAREFUL, FMT>(c, s0 + kM * (j - (P - 1)));
+    for (int j = 0; j < kS; j++) S[j] = sample_at<CAREFUL, FMT, COND>(c, s0 + kM * (j - (P - 1)));
 #pragma unroll
     for (int t = 0; t < kBlockFrames; t++) {
         const int s = (t + CLS) >> 1;
@@ -282,7 +296,7 @@ template <int P, int CLS, bool CAREFUL, int FMT, class Tap> CHAN_HD void fold_sl
 
 // phase 1 (threads < kFoldThreads): fold the block's 8 frames, v_t[r] -> lds[t][r].  Slot after slot: a slot's 2 P coefficients and
 // P + 4 samples live only while its 8 frames are summed.
-template <int P, bool CAREFUL, int FMT, bool SHIFT = false> CHAN_HD void phase_fold_t(const BlockCtx& c, int blk, int tid, c32* lds) {
+template <int P, bool CAREFUL, int FMT, bool SHIFT = false, bool COND = false> CHAN_HD void phase_fold_t(const BlockCtx& c, int blk, int tid, c32* lds) {
     if (tid >= kFoldThreads) return;
     const long long newest0 = (long long)(kBlockFrames * blk + 1) * (kM / 2) - 1 - c.ph0;     // index of the block's first frame's newest sample among the new samples
     const int a = (int)((c.abs0 + newest0) % kM);
@@ -292,8 +306,8 @@ template <int P, bool CAREFUL, int FMT, bool SHIFT = false> CHAN_HD void phase_f
         FoldCoef<P, typename std::conditional<SHIFT, c32, float>::type> k;
         fold_load_coef(c.h, u, k);
         c32 v[kBlockFrames];
-        if (i < 2) fold_slot<P, 0, CAREFUL, FMT>(c, newest0 - u, k, v);
-        else fold_slot<P, 1, CAREFUL, FMT>(c, newest0 - u, k, v);
+        if (i < 2) fold_slot<P, 0, CAREFUL, FMT, COND>(c, newest0 - u, k, v);
+        else fold_slot<P, 1, CAREFUL, FMT, COND>(c, newest0 - u, k, v);
         int r = a - u;
         r += r < 0 ? kM : 0;
 #pragma unroll
@@ -305,10 +319,10 @@ template <int P, bool CAREFUL, int FMT, bool SHIFT = false> CHAN_HD void phase_f
 #endif
     }
 }
-template <int P, int FMT = kFmtC32, bool SHIFT = false> CHAN_HD void phase_fold(const BlockCtx& c, int blk, int tid, c32* lds) {
+template <int P, int FMT = kFmtC32, bool SHIFT = false, bool COND = false> CHAN_HD void phase_fold(const BlockCtx& c, int blk, int tid, c32* lds) {
     const long long newest0 = (long long)(kBlockFrames * blk + 1) * (kM / 2) - 1 - c.ph0;
-    if (block_is_careful(c, newest0)) phase_fold_t<P, true, FMT, SHIFT>(c, blk, tid, lds);      // (uniform over the workgroup)
-    else phase_fold_t<P, false, FMT, SHIFT>(c, blk, tid, lds);
+    if (block_is_careful(c, newest0)) phase_fold_t<P, true, FMT, SHIFT, COND>(c, blk, tid, lds);      // (uniform over the workgroup)
+    else phase_fold_t<P, false, FMT, SHIFT, COND>(c, blk, tid, lds);
 }
 // phase 1, shifted bank only: the block's 8 frame phasors, ONE thread per frame (threads 200 .. 207: they fold nothing, though their wave 3 does for its first 8 lanes), into
 // kPhasorSlot of the frame's region; phase 3 reads them behind the two barriers.  Frame j of the call has its newest sample at

@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/ext/tetra_iqcond.h"
 #include "../../include/tetra_shift.h"
 #include "chan_design.hpp"
 #include "chan_fft_core.hpp"
@@ -303,11 +304,14 @@ struct ChanFftParams {
     int exp;               // ablation switches (profiles/measure_chan_fft.py; compile-time variants of the P = 8 kernel): 1 = one store per lane, 2 = no inter-stage twiddles
     long long abs0;
     uint32_t inc;          // frequency shift (tetra_chan_set_shift); read by the SHIFT instantiations only
+    iqcond::Map map;       // input map (tetra_chan_set_input_map); read by the COND instantiations only.  Behind every older member: their offsets stay
 };
 
 // SHIFT = true: the frequency-shifted bank (complex taps in the fold, one phasor per frame in the store: chan_fft_core.hpp).  SHIFT =
 // false is the kernel as it was: the shift is a template parameter so that it costs the un-shifted bank no instruction.
-template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false> __global__ __launch_bounds__(kThreads, 2) void k_channelise_fft(ChanFftParams p) {
+// COND = true: the fold's loads of NEW samples go through the input map (include/ext/tetra_iqcond.h; load_sample's conditioned form) --
+// four fma per loaded sample; the delay line is read as it is.  COND = false is the kernel as it was, in the same way.
+template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false, bool COND = false> __global__ __launch_bounds__(kThreads, 2) void k_channelise_fft(ChanFftParams p) {
     using namespace chanfft;
     __shared__ c32 lds[kBlockFrames * kFrameLds];          // 52.8 KB: three workgroups per CU
     const int tid = threadIdx.x;
@@ -321,6 +325,7 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false> __
     c.tw = reinterpret_cast<const c32*>(p.tw);
     c.frames = p.frames; c.ph0 = p.ph0; c.abs0 = p.abs0;
     c.inc = SHIFT ? p.inc : 0u;
+    if (COND) c.map = p.map;
     // One block of 8 frames per workgroup, no loop over blocks: nothing is carried from block to block, and a loop makes the compiler
     // keep the transforms' ~100 literal twiddles in VGPRs across it (256 VGPRs + spills instead of 147: three workgroups per CU).
     // Consecutive blocks share two thirds of their samples (a block reads 9600, 3200 of them new).  Workgroups are dealt to the 8 XCDs
@@ -332,7 +337,7 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false> __
         blk = (int)(blockIdx.x & 7) * p.xcd_span + (int)(blockIdx.x >> 3);
         if (blk >= p.blocks || (int)(blockIdx.x >> 3) >= p.xcd_span) return;
     }
-    phase_fold<P, FMT, SHIFT>(c, blk, tid, lds);
+    phase_fold<P, FMT, SHIFT, COND>(c, blk, tid, lds);
     if (SHIFT) phase_phasor(c, blk, tid, lds);
     __syncthreads();
     c32 tw[kN1 - 1];
@@ -353,10 +358,11 @@ template <int P, int EXP = 0, int FMT = chanfft::kFmtC32, bool SHIFT = false> __
 }
 
 // integer samples -> complex64 (the staging buffer of the kernels that read [history | new] contiguously, and the delay line)
-template <int FMT> __global__ __launch_bounds__(256) void k_chan_convert(const void* __restrict__ x, long long first, int n, float2* __restrict__ out) {
+// COND: through the handle's input map (complex64 samples too, then: in place of the plain copy); the map rides behind the older arguments
+template <int FMT, bool COND = false> __global__ __launch_bounds__(256) void k_chan_convert(const void* __restrict__ x, long long first, int n, float2* __restrict__ out, iqcond::Map m) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const chanfft::c32 v = chanfft::load_sample<FMT>(x, first + i);
+    const chanfft::c32 v = COND ? chanfft::load_sample<FMT>(x, first + i, m) : chanfft::load_sample<FMT>(x, first + i);
     out[i] = make_float2(v.x, v.y);
 }
 
@@ -384,6 +390,8 @@ struct tetra_chan {
     bool hc_dirty = false;      // hc_host is newer than d_hc
     Event ev_hc;                // behind the latest upload: set_shift waits for it before it rewrites hc_host
     bool hc_in_flight = false;
+    bool cond = false;          // an input map is set (tetra_chan_set_input_map): the COND instantiations run, with `map` as a kernel argument
+    iqcond::Map map = { 1.f, 0.f, 0.f, 1.f, 0.f, 0.f };
     int phase = 0;              // samples consumed towards the next frame
     long long consumed = 0;     // absolute index of the next input sample
     Event ev[2];
@@ -546,21 +554,34 @@ int tetra_chan_frames_for(tetra_chan_t* h, int n_in) {
 namespace {
 // bytes per sample of a format; copy `n` samples starting at `first` of the caller's buffer into a complex64 buffer
 constexpr int kFmtBytes[3] = { 8, 4, 2 };
-hipError_t copy_samples(int fmt, const void* d_x, size_t first, size_t n, float2* dst, hipStream_t s) {
+// map: the handle's input map, or null for none (then complex64 samples are a plain copy)
+hipError_t copy_samples(int fmt, const void* d_x, size_t first, size_t n, float2* dst, hipStream_t s, const iqcond::Map* map) {
     if (n == 0) return hipSuccess;
-    if (fmt == chanfft::kFmtC32) return hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s);
+    if (fmt == chanfft::kFmtC32 && !map) return hipMemcpyAsync(dst, static_cast<const float2*>(d_x) + first, sizeof(float2) * n, hipMemcpyDeviceToDevice, s);
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (fmt == chanfft::kFmtCs16) hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs16>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
-    else hipLaunchKernelGGL(k_chan_convert<chanfft::kFmtCs8>, grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst);
+    const iqcond::Map m = map ? *map : iqcond::Map();
+    auto launch = [&](auto FMT, auto COND) {
+        hipLaunchKernelGGL((k_chan_convert<decltype(FMT)::value, decltype(COND)::value>), grid, dim3(256), 0, s, d_x, (long long)first, (int)n, dst, m);
+    };
+    auto with_cond = [&](auto FMT) {
+        if (map) launch(FMT, std::true_type());
+        else launch(FMT, std::false_type());
+    };
+    if (fmt == chanfft::kFmtCs16) with_cond(std::integral_constant<int, chanfft::kFmtCs16>());
+    else if (fmt == chanfft::kFmtCs8) with_cond(std::integral_constant<int, chanfft::kFmtCs8>());
+    else launch(std::integral_constant<int, chanfft::kFmtC32>(), std::true_type());
     return hipGetLastError();
 }
-// The one place that turns a handle's (taps per channel, sample format, shifted or not) into template arguments:
-// f(Int<P>, Int<FMT>, bool_constant<SHIFT>) for the three tap counts that have FFT and matrix kernels (p_ok in tetra_chan_create).
+// The one place that turns a handle's (taps per channel, sample format, shifted or not, input map or not) into template arguments:
+// f(Int<P>, Int<FMT>, bool_constant<SHIFT>, bool_constant<COND>) for the three tap counts that have FFT and matrix kernels (p_ok in
+// tetra_chan_create).
 template <int V> using Int = std::integral_constant<int, V>;
-template <class F> void with_variant(int P, int fmt, bool shift, F f) {
+template <class F> void with_variant(int P, int fmt, bool shift, bool cond, F f) {
     auto with_shift = [&](auto p, auto m) {
-        if (shift) f(p, m, std::true_type());
-        else f(p, m, std::false_type());
+        if (shift && cond) f(p, m, std::true_type(), std::true_type());
+        else if (shift) f(p, m, std::true_type(), std::false_type());
+        else if (cond) f(p, m, std::false_type(), std::true_type());
+        else f(p, m, std::false_type(), std::false_type());
     };
     auto with_fmt = [&](auto p) {
         if (fmt == chanfft::kFmtCs16) with_shift(p, Int<chanfft::kFmtCs16>());
@@ -585,10 +606,11 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     const int frames = (h->phase + n_in) / h->D;
     *n_frames = frames;
     const size_t hist = (size_t)h->L - 1;
+    const iqcond::Map* map = h->cond ? &h->map : nullptr;      // the input map of THIS call's samples (include/ext/tetra_iqcond.h)
     // The FFT kernel reads the new samples where the caller left them (and the L - 1 before them from the handle's delay line): no
     // staging copy -- every sample crosses HBM once.  The other two kernels index one contiguous [history | new] buffer.
     if (n_in > 0 && !h->fft) {
-        HIP_TRY(h, copy_samples(fmt, d_x, 0, (size_t)n_in, h->line + hist, s));
+        HIP_TRY(h, copy_samples(fmt, d_x, 0, (size_t)n_in, h->line + hist, s, map));      // (with a map: the staged samples, and so the line, are conditioned)
     }
     // a new shift's taps go up here, in stream order behind everything enqueued before this call and ahead of its kernel
     if (h->hc_dirty) {
@@ -604,6 +626,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         p.x = d_x; p.hist = h->line; p.out = reinterpret_cast<float2*>(d_out); p.tw = h->d_tw;
         p.h = shift ? reinterpret_cast<const float*>(h->d_hc.get()) : h->d_ht.get();
         p.inc = h->inc;
+        p.map = h->map;
         p.frames = frames; p.blocks = (frames + chanfft::kBlockFrames - 1) / chanfft::kBlockFrames; p.n_in = n_in;
         p.ph0 = h->phase; p.abs0 = h->consumed;
         // one block of 8 frames per workgroup: the hardware hands the next block to whichever CU is through first
@@ -623,8 +646,8 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         else if (fmt == chanfft::kFmtC32 && h->P == 8 && p.exp == 3) hipLaunchKernelGGL((k_channelise_fft<8, 3>), grid, dim3(kThreads), 0, s, p);
         else
 #endif
-        with_variant(h->P, fmt, shift, [&](auto P, auto FMT, auto SHIFT) {
-            hipLaunchKernelGGL((k_channelise_fft<decltype(P)::value, 0, decltype(FMT)::value, decltype(SHIFT)::value>), grid, dim3(kThreads), 0, s, p);
+        with_variant(h->P, fmt, shift, h->cond, [&](auto P, auto FMT, auto SHIFT, auto COND) {
+            hipLaunchKernelGGL((k_channelise_fft<decltype(P)::value, 0, decltype(FMT)::value, decltype(SHIFT)::value, decltype(COND)::value>), grid, dim3(kThreads), 0, s, p);
         });
         HIP_TRY(h, hipGetLastError());
     } else if (frames > 0 && h->mfma) {
@@ -636,7 +659,7 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
         // the fold's loads and the stores of different frames overlapping
         const int per_cu = shift ? 2 : 3;                                 // workgroups that fit a CU (registers, LDS; the shifted form's complex taps double hs)
         const int grid = frames < per_cu * h->cus ? frames : per_cu * h->cus;      // each loops over its frames
-        with_variant(h->P, chanfft::kFmtC32, shift, [&](auto P, auto, auto SHIFT) {      // (reads the staged complex64 samples whatever the call's format)
+        with_variant(h->P, chanfft::kFmtC32, shift, false, [&](auto P, auto, auto SHIFT, auto) {      // (reads the staged complex64 samples, conditioned or not, whatever the call's format)
             hipLaunchKernelGGL((k_channelise_mfma<decltype(P)::value, decltype(SHIFT)::value>), dim3(grid), dim3(kThreads), 0, s, p);
         });
         HIP_TRY(h, hipGetLastError());
@@ -654,10 +677,10 @@ int process_any(tetra_chan_t* h, int fmt, const void* d_x, int n_in, float* d_ou
     }
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     h->ev_valid = true;
-    // carry (DelayLine): the FFT route's new samples are still where the caller left them, in the call's format; the staged routes'
-    // lie behind the line already
+    // carry (DelayLine): the FFT route's new samples are still where the caller left them, in the call's format (and raw: they enter the
+    // line through the call's input map, like the fold's loads); the staged routes' lie behind the line already
     if (h->fft) {
-        HIP_TRY(h, h->line.carry((size_t)n_in, s, [&](float2* dst, size_t from_x) { return copy_samples(fmt, d_x, (size_t)n_in - from_x, from_x, dst, s); }));
+        HIP_TRY(h, h->line.carry((size_t)n_in, s, [&](float2* dst, size_t from_x) { return copy_samples(fmt, d_x, (size_t)n_in - from_x, from_x, dst, s, map); }));
     } else {
         HIP_TRY(h, h->line.carry_staged((size_t)n_in, s));
     }
@@ -753,6 +776,28 @@ uint32_t tetra_chan_shift_from_hz(double shift_hz, double sample_rate_hz) {
     f -= std::floor(f);                                      // cycles per sample in [0, 1): negative shifts wrap
     const double v = std::nearbyint(f * 4294967296.0);       // (round to nearest; 2^32 itself wraps to 0)
     return (uint32_t)(unsigned long long)v;
+}
+
+int tetra_chan_set_input_map(tetra_chan_t* h, const tetra_iq_map_t* map) {
+    if (!h) return TETRA_ERR_ARG;
+    if (!map) {                 // back to the un-conditioned kernels; the line keeps what it holds
+        h->cond = false;
+        h->map = iqcond::Map{ 1.f, 0.f, 0.f, 1.f, 0.f, 0.f };
+        return TETRA_OK;
+    }
+    const iqcond::Map m = { map->m00, map->m01, map->m10, map->m11, map->c0, map->c1 };
+    if (!iqcond::finite(m)) return TETRA_ERR_ARG;
+    h->map = m;                 // host state only: the next process call passes it to its kernels by value
+    h->cond = true;
+    return TETRA_OK;
+}
+
+int tetra_chan_get_input_map(tetra_chan_t* h, tetra_iq_map_t* map, int* is_set) {
+    if (!h || !map) return TETRA_ERR_ARG;
+    const iqcond::Map& m = h->map;
+    map->m00 = m.m00; map->m01 = m.m01; map->m10 = m.m10; map->m11 = m.m11; map->c0 = m.c0; map->c1 = m.c1;
+    if (is_set) *is_set = h->cond ? 1 : 0;
+    return TETRA_OK;
 }
 
 int tetra_chan_get_prototype(tetra_chan_t* h, float* proto) {

@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/ext/tetra_iqcond.h"
 #include "../../include/tetra_shift.h"
 #include "hip_host.hpp"
 #include "resamp_handle.hpp"
@@ -295,6 +296,17 @@ int tetra_wbrx_set_shift(tetra_wbrx_t* h, uint32_t inc) {
 int tetra_wbrx_get_shift(tetra_wbrx_t* h, uint32_t* inc) {
     if (!h) return TETRA_ERR_ARG;
     return tetra_chan_get_shift(h->chan, inc);
+}
+
+// So is the input map (include/ext/tetra_iqcond.h): it acts on the capture's samples, in the channeliser's loads.
+int tetra_wbrx_set_input_map(tetra_wbrx_t* h, const tetra_iq_map_t* map) {
+    if (!h) return TETRA_ERR_ARG;
+    return tetra_chan_set_input_map(h->chan, map);
+}
+
+int tetra_wbrx_get_input_map(tetra_wbrx_t* h, tetra_iq_map_t* map, int* is_set) {
+    if (!h) return TETRA_ERR_ARG;
+    return tetra_chan_get_input_map(h->chan, map, is_set);
 }
 
 int tetra_wbrx_stage_ms(tetra_wbrx_t* h, float ms[2]) {

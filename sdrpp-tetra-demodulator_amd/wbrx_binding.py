@@ -7,7 +7,7 @@ import numpy as np
 from . import binding as B
 from ._ffi import P, call, declare, i32, i64, ptr, stream_ptr, u32, vp
 from .binding import load_library
-from .chan_binding import ChanConfig
+from .chan_binding import ChanConfig, IqMap, _get_input_map, _set_input_map, input_map_from_stats, iq_stats
 from .rx_binding import RxChain, RxConfig
 from .rx_binding import _lib as _rx_lib
 
@@ -44,13 +44,19 @@ RETUNE_SIGNATURES = {
     "tetra_wbrx_retune": (i32, [vp, vp, vp]),
     "tetra_wbrx_retune_count": (i32, [vp, P(i64), P(i64)]),
 }
+# include/ext/tetra_iqcond.h (conditioning of the capture): the wideband receiver's share
+IQCOND_ABI = {
+    "tetra_wbrx_set_input_map": (i32, [vp, P(IqMap)]),
+    "tetra_wbrx_get_input_map": (i32, [vp, P(IqMap), P(i32)]),
+}
 WBRX_EXPORTS, WBRX_SHIFT_EXPORTS, WBRX_RETUNE_EXPORTS = list(SIGNATURES), list(SHIFT_SIGNATURES), list(RETUNE_SIGNATURES)
 
 
 @functools.lru_cache(None)
 def _lib():
-    # (a TETRA_DEMOD_LIB override may be an older build without the shift and the retune)
-    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES}, optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS)
+    # (a TETRA_DEMOD_LIB override may be an older build without the shift, the retune and the input map)
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI},
+                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI))
 
 
 def default_config():
@@ -134,6 +140,23 @@ class WidebandRx:
         v = C.c_uint32(0)
         call(self._lib.tetra_wbrx_get_shift, self._h, C.byref(v))
         return int(v.value)
+
+    def set_input_map(self, m):
+        """tetra_wbrx_set_input_map (include/ext/tetra_iqcond.h): forwards to the channeliser -- six coefficients (m00, m01, m10, m11, c0, c1)
+        or None for the un-conditioned kernels; between process calls, from the next call's first new sample."""
+        _set_input_map(self._lib.tetra_wbrx_set_input_map, self._h, m)
+
+    def get_input_map(self):
+        """The six coefficients in force, or None if no map is set."""
+        return _get_input_map(self._lib.tetra_wbrx_get_input_map, self._h)
+
+    def estimate_input_map(self, x, n=None, stream=None):
+        """The blind estimate from a stretch of the capture on the device (iq_stats -> input_map_from_stats), set on this handle and
+        returned.  x: as process_device takes it; n: samples (default: all of the tensor).  The handle's map stays as it was if the
+        solver refuses the statistics."""
+        m = input_map_from_stats(iq_stats(x, n, stream))
+        self.set_input_map(m)
+        return m
 
     def retune(self, bins, stream=None):
         """tetra_wbrx_retune: slot j receives bins[j] from the next process call on.  Slots whose bin stays are untouched; every other
