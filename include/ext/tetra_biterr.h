@@ -70,8 +70,9 @@ int tetra_lmac_decode_frames_biterr_device(const tetra_lmac_frames_t* src, const
  * The receive chain: TETRA_RX_FLAG_BITERR in tetra_rx_config_t.flags (tetra_rx.h; through cfg.rx also for tetra_wbrx_create, whose chain
  * tetra_wbrx_rx hands out) makes the chain's decode launches count, with the packed frames or -- with TETRA_RX_FLAG_SOFT -- the soft
  * values as the received word.  The handle then keeps one uint32 per row for each coded kind it decodes, double buffered like the
- * results (4 bytes per row and kind), and the link figures below.  The tetra_rx_out.h delivery format is unchanged: the counts are not
- * delivered through it; fetch them here.
+ * results (4 bytes per row and kind), and the link figures below.  The tetra_rx_out.h delivery format is unchanged; the counts and the
+ * link figures come with a call's rows, without a host synchronisation, as a column and a per-channel table of an extended delivery
+ * (tetra_rx_out_ext.h: TETRA_RX_OUT_EXT_ROW_BITERR, TETRA_RX_OUT_EXT_CHAN_LINK), or through the blocking calls here.
  *
  * tetra_rx_fetch_biterr: errors | compared << 16 of every row of a coded kind of the latest (which = 0) or previous (1) call, in
  * tetra_rx_fetch's order.

@@ -77,8 +77,9 @@ int tetra_lmac_decode_frames_list_device(const tetra_lmac_frames_t* src, const t
  * soft values.  SB1 rows are rescued in front of the SYNC tracker, so a rescued SYNC PDU sets the scrambling code and the clock of its
  * burst and of what follows; the other coded kinds are rescued in front of the link figures (TETRA_RX_FLAG_BITERR: a rescued row's count is
  * taken again on the rescued codeword) and of the event that ends the tail.  Rows, labels (crc_ok = 1 for a rescued row) and the
- * tetra_rx_out.h delivery -- its TETRA_RX_OUT_CRC_GOOD selection included -- see rescued rows as good rows; the format is unchanged and the
- * ranks are not delivered through it: fetch them here.  The handle keeps one int32 per row for each coded kind it decodes, double buffered
+ * tetra_rx_out.h delivery -- its TETRA_RX_OUT_CRC_GOOD selection included -- see rescued rows as good rows; the format is unchanged, and the
+ * ranks come with the rows as a column of an extended delivery (tetra_rx_out_ext.h, TETRA_RX_OUT_EXT_ROW_LIST_RANK) -- which rows were
+ * rescued, beside the rows themselves -- or through the blocking fetch here.  The handle keeps one int32 per row for each coded kind it decodes, double buffered
  * like the results (8 bytes per row and kind).
  *
  * tetra_rx_set_list_candidates: T for the calls that follow (1..8, else TETRA_ERR_ARG; a new handle has TETRA_LIST_DEFAULT_CANDIDATES).

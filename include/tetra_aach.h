@@ -70,7 +70,8 @@ int tetra_lmac_decode_aach_rm3014_device(const uint8_t* d_type5, int n_blocks, i
  * The receive chain: TETRA_RX_FLAG_AACH_RM3014 in tetra_rx_config_t.flags (tetra_rx.h; through cfg.rx also for tetra_wbrx_create)
  * makes the chain's BBK job decode with the code.  tetra_rx_fetch(TETRA_RX_KIND_BBK) then returns the 30 corrected bits and the
  * verdict in crc_ok, tetra_rx_rows_device the rows as above, and the tetra_rx_out.h delivery with TETRA_RX_OUT_CRC_GOOD keeps only
- * the decodable AACH rows.
+ * the decodable AACH rows.  A delivery carries the 30 bits; the distance (byte 30) comes with them as a column of an extended
+ * delivery (ext/tetra_rx_out_ext.h, TETRA_RX_OUT_EXT_ROW_AACH_DIST), or through the blocking fetch below.
  *
  * tetra_rx_fetch_aach_dist: byte 30 of every BBK row of the latest (which = 0) or previous (1) call, in tetra_rx_fetch's order.
  *   dist     [capacity] uint8 host, may be NULL

@@ -98,6 +98,11 @@ struct tetra_rx {
     long long ring_call[kOutRing] = { -1, -1, -1, -1, -1, -1, -1, -1 }, ring_seq[kOutRing] = {}, out_seq = 0;
     DevMem<int32_t> out_tiles;            // [TETRA_RX_N_KINDS][tiles]: kept rows per tile, scanned in place to their first output row
     DevMem<uint8_t> out_layout;           // the layout the write launch reads (rx_out::Layout)
+    // the extension block (include/ext/tetra_rx_out_ext.h)
+    DevMem<uint8_t> out_ext_layout;       // what the extras' layout launch leaves for their write launch
+    int snap_mask = 0;                    // tetra_rx_out_set_snapshot: the channel extras every tail copies ...
+    DevMem<uint8_t> snap[2];              // ... into its parity's snapshot (rx_out::snap_offset; allocated when first armed)
+    int snap_taken[2] = { 0, 0 };         // the mask the latest tail of each parity ran with (0 again after a reset)
     // resets of single channels (include/tetra_retune.h, tetra_retune.hip)
     ListRing to_device;                       // the channel lists on their way to the device
     Event ev_reset;                       // the latest reset's work on the stream it was given ...

@@ -25,6 +25,7 @@
 #include "demux_core.hpp"
 #include "hip_host.hpp"
 #include "retune_impl.hpp"
+#include "rx_snap_impl.hpp"
 
 namespace {
 
@@ -373,6 +374,15 @@ int retune_impl::bsync_view(tetra_bsync_t* h, retune::BsyncView* v) {
 int retune_impl::bsync_miss_view(tetra_bsync_t* h, retune::CellView* v) {
     if (!h || !v) return TETRA_ERR_ARG;
     v->cell = reinterpret_cast<uint32_t*>(h->d_miss.get()); v->cell_words = h->tolerant ? 1 : 0;
+    return TETRA_OK;
+}
+
+// ... and both tables where they are, for the receive chain's per-call snapshot (tetra_rx.hip)
+int rx_snap_impl::bsync_tables(tetra_bsync_t* h, const tetra_bsync_state_t** state, const int32_t** miss) {
+    if (!h || !state || !miss) return TETRA_ERR_ARG;
+    static_assert(sizeof(State) == sizeof(tetra_bsync_state_t), "state layout");
+    *state = reinterpret_cast<const tetra_bsync_state_t*>(h->d_state.get());
+    *miss = h->d_miss.get();
     return TETRA_OK;
 }
 

@@ -33,6 +33,8 @@
 #include "../../include/tetra_rx.h"
 #include "lmac_impl.hpp"
 #include "rx_handle.hpp"
+#include "rx_out_core.hpp"
+#include "rx_snap_impl.hpp"
 #include "soft_core.hpp"
 
 namespace {
@@ -121,6 +123,24 @@ __global__ __launch_bounds__(64) void k_rx_link(const LinkTable tab, const int32
         l.blocks_crc_bad += bad;
         link[c] = l;
     }
+}
+
+// tetra_rx_out_set_snapshot (ext/tetra_rx_out_ext.h): the armed per-channel tables as this tail leaves them -> the parity's snapshot, in
+// 32-bit words (every table's element is a whole number of them), a thread per word of the longest table.  Reads what earlier kernels
+// of the tail wrote; nothing in the tail reads what it writes.
+struct SnapTable {
+    const uint32_t* src;
+    uint32_t* dst;
+    int words;                    // 0: not armed
+};
+struct SnapArgs {
+    SnapTable tab[rx_out::kChanTables];
+};
+__global__ __launch_bounds__(256) void k_rx_snapshot(const SnapArgs a) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+#pragma unroll
+    for (int t = 0; t < rx_out::kChanTables; ++t)
+        if (i < a.tab[t].words) a.tab[t].dst[i] = a.tab[t].src[i];
 }
 
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
@@ -221,6 +241,27 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipEventRecord(h->ev_stage[3], s));
+    h->snap_taken[b] = 0;
+    if (h->snap_mask) {      // behind the link figures and outside the stages' spans; in front of the tail's event, which a delivery waits for
+        const tetra_bsync_state_t* st = nullptr;
+        const int32_t* miss = nullptr;
+        TETRA_TRY(rx_snap_impl::bsync_tables(h->bs, &st, &miss));
+        const void* src[rx_out::kChanTables] = { h->cell.get(), st, miss, h->link.get() };
+        SnapArgs a = {};
+        int most = 0;
+        for (int t = 0; t < rx_out::kChanTables; ++t) {
+            if (!(h->snap_mask & rx_out::chan_extra(t)) || !src[t]) continue;
+            a.tab[t].src = static_cast<const uint32_t*>(src[t]);
+            a.tab[t].dst = reinterpret_cast<uint32_t*>(h->snap[b].get() + rx_out::snap_offset(t, h->C));
+            a.tab[t].words = rx_out::chan_elem_bytes(t) / 4 * h->C;
+            most = a.tab[t].words > most ? a.tab[t].words : most;
+            h->snap_taken[b] |= rx_out::chan_extra(t);
+        }
+        if (most > 0) {
+            hipLaunchKernelGGL(k_rx_snapshot, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, s, a);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
     return TETRA_OK;
 }
 
@@ -374,6 +415,7 @@ int tetra_rx_reset(tetra_rx_t* h) {
     h->stage_valid = false;
     for (bool& p : h->out_pending) p = false;          // (the device is idle: every delivery has completed)
     for (long long& c : h->ring_call) c = -1;
+    h->snap_taken[0] = h->snap_taken[1] = 0;           // (the mask stays armed: the next tails take snapshots again)
     h->reset_pending = false;
     return TETRA_OK;
 }

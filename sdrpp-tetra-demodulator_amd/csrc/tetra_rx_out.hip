@@ -12,13 +12,15 @@
 //
 // No workgroup reads what another workgroup of the same launch writes (the per-XCD L2s are not coherent); every hand-over is a
 // kernel boundary on one stream.  Nothing is written outside [dst, dst + capacity): the layout launch checks the size first, and a
-// delivery that does not fit gets only its header.
+// delivery that does not fit gets only its header.  The opt-in extension block (include/ext/tetra_rx_out_ext.h) adds two launches of
+// its own around k_out_write (see below); without extras the three kernels above are all that is launched.
 #include <hip/hip_runtime.h>
 
 #include "../../include/tetra_rx_out.h"
 #include "compact_core.hpp"
 #include "rx_handle.hpp"
 #include "rx_out_core.hpp"
+#include "rx_snap_impl.hpp"
 
 namespace {
 
@@ -168,6 +170,118 @@ __global__ __launch_bounds__(256) void k_out_write(const OutArgs a, const int32_
     }
 }
 
+// ---- the extension block (include/ext/tetra_rx_out_ext.h): two more launches around k_out_write, which stays what it is ----
+//
+//   k_out_count (CRC-good only), k_out_layout        as ever
+//   k_out_ext_layout  ONE workgroup behind k_out_layout: the kept rows per kind from the SAME scanned tile counts (a tile's first
+//                     output row, plus the last tile's own kept rows), the extension's layout and header -> dst; if classic part plus
+//                     extension do not fit, the status of the classic header in dst and of the Layout k_out_write reads becomes
+//                     TETRA_ERR_SIZE and bytes the total, so that nothing but the classic header is written
+//   k_out_write       as ever
+//   k_out_ext_write   per kind and tile: the kept rows' columns, ranked like the rows, staged in LDS and stored as contiguous runs
+//                     (rx_out::ext_stage / ext_store); one more row of workgroups copies the call's per-channel snapshot
+
+struct ExtKind {                      // one selected kind's columns of one parity (the distance is byte 30 of its type-2 row)
+    const uint32_t* biterr;
+    const int32_t* rank;
+};
+struct ExtArgs {
+    ExtKind k[TETRA_RX_N_KINDS];
+    const uint8_t* snap;              // the parity's snapshot (rx_out::snap_offset)
+    int extras, n_channels;
+};
+struct ExtLayout {                    // what k_out_ext_layout leaves for k_out_ext_write
+    int status;
+    int n_dec[TETRA_RX_N_KINDS];
+    uint64_t col[TETRA_RX_N_KINDS][rx_out::kRowCols];      // 0: the kind has no such column
+    uint64_t tab[rx_out::kChanTables];                     // 0: no such table
+};
+
+__global__ __launch_bounds__(kTile) void k_out_ext_layout(const OutArgs a, const ExtArgs x, const int32_t* __restrict__ tile_off, Layout* __restrict__ lay,
+                                                          ExtLayout* __restrict__ xl, uint8_t* __restrict__ dst, uint64_t capacity, long long call) {
+    __shared__ int kept[TETRA_RX_N_KINDS];
+    __shared__ tetra_rx_out_header_t hd;
+    __shared__ __attribute__((aligned(16))) tetra_rx_out_ext_header_t ex;
+    __shared__ int fits;
+    const int t = (int)threadIdx.x;
+    for (int s = 0; s < a.nsel; s++) {                     // (n is the same in every thread: the barriers are met by all)
+        const int n = lay->n_dec[s];
+        int k = n;
+        if ((a.flags & TETRA_RX_OUT_CRC_GOOD) && n > 0) {
+            const int last = (n - 1) / kTile, i = last * kTile + t;
+            k = tile_off[s * a.tiles + last] + __syncthreads_count(i < n && a.k[s].ok[i] != 0);
+        }
+        if (t == 0) kept[s] = k;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int kinds[TETRA_RX_N_KINDS], nk[TETRA_RX_N_KINDS], nd[TETRA_RX_N_KINDS];
+        for (int s = 0; s < a.nsel; s++) { kinds[s] = a.k[s].kind; nk[s] = kept[s]; nd[s] = lay->n_dec[s]; }
+        const uint64_t classic = rx_out::layout(&hd, kinds, nk, nd, a.nsel, a.flags);
+        const uint64_t total = rx_out::layout_ext(&ex, kinds, nk, a.nsel, classic, x.extras, x.n_channels);
+        ex.magic = TETRA_RX_OUT_EXT_MAGIC;
+        ex.call = call;
+        fits = total <= capacity;
+        if (!fits) {
+            lay->status = TETRA_ERR_SIZE;
+            reinterpret_cast<tetra_rx_out_header_t*>(dst)->status = TETRA_ERR_SIZE;
+            reinterpret_cast<tetra_rx_out_header_t*>(dst)->bytes = total;
+        }
+        xl->status = fits ? TETRA_OK : TETRA_ERR_SIZE;
+        for (int s = 0; s < TETRA_RX_N_KINDS; s++) {
+            xl->n_dec[s] = s < a.nsel ? nd[s] : 0;
+            xl->col[s][0] = ex.kinds[s].biterr_offset;
+            xl->col[s][1] = ex.kinds[s].rank_offset;
+            xl->col[s][2] = ex.kinds[s].aach_dist_offset;
+        }
+        xl->tab[0] = ex.cell_offset;
+        xl->tab[1] = ex.sync_state_offset;
+        xl->tab[2] = ex.sync_misses_offset;
+        xl->tab[3] = ex.link_offset;
+    }
+    __syncthreads();
+    constexpr int kWords = (int)(rx_out::kExtHeaderBytes / 16);
+    if (fits && t < kWords) reinterpret_cast<uint4*>(dst + rx_out::align16(hd.bytes))[t] = reinterpret_cast<const uint4*>(&ex)[t];
+}
+
+__global__ __launch_bounds__(kTile) void k_out_ext_write(const OutArgs a, const ExtArgs x, const int32_t* __restrict__ tile_off,
+                                                         const ExtLayout* __restrict__ xl, uint8_t* __restrict__ dst) {
+    __shared__ __attribute__((aligned(16))) uint8_t scol[rx_out::kRowCols][16 + kTile * 4];
+    __shared__ uint8_t src[kTile];
+    if (xl->status != TETRA_OK) return;
+    const int t = (int)threadIdx.x;
+    const int s = (int)blockIdx.y;
+    if (s == a.nsel) {                // the per-channel tables, 16 bytes per thread
+        for (int j = 0; j < rx_out::kChanTables; j++)
+            if (xl->tab[j])
+                rx_out::table_copy(dst + xl->tab[j], x.snap + rx_out::snap_offset(j, x.n_channels), (uint64_t)rx_out::chan_elem_bytes(j) * (uint64_t)x.n_channels,
+                                   (uint64_t)blockIdx.x * kTile + (uint64_t)t, (uint64_t)gridDim.x * kTile);
+        return;
+    }
+    const uint64_t* col = xl->col[s];
+    if (!(col[0] | col[1] | col[2])) return;
+    const OutKind& k = a.k[s];
+    const int n = xl->n_dec[s];
+    const int t0 = (int)blockIdx.x * kTile;
+    if (t0 >= n) return;
+    const bool crc = (a.flags & TETRA_RX_OUT_CRC_GOOD) != 0;
+    const int base = crc ? tile_off[s * a.tiles + blockIdx.x] : t0;      // first output row of the tile, as in k_out_write
+    const bool keep = t0 + t < n && (!crc || k.ok[t0 + t] != 0);
+    int at[1], cnt;
+    compact_core::block_rank<1, kTile>(keep, at, &cnt);
+    if (keep) src[at[0]] = (uint8_t)t;
+    __syncthreads();
+    if (cnt == 0) return;
+    const uint64_t b0 = col[0] + 4ull * (uint64_t)base, b1 = col[1] + 4ull * (uint64_t)base, b2 = col[2] + (uint64_t)base;
+    if (col[0]) rx_out::ext_stage<4>(scol[0], b0, reinterpret_cast<const uint8_t*>(x.k[s].biterr), 4, t0, src, cnt, t, kTile);
+    if (col[1]) rx_out::ext_stage<4>(scol[1], b1, reinterpret_cast<const uint8_t*>(x.k[s].rank), 4, t0, src, cnt, t, kTile);
+    if (col[2]) rx_out::ext_stage<1>(scol[2], b2, k.t2 + 30, (size_t)k.out_stride, t0, src, cnt, t, kTile);
+    __syncthreads();
+    if (col[0]) rx_out::ext_store<4>(dst, b0, scol[0], cnt, t, kTile);
+    if (col[1]) rx_out::ext_store<4>(dst, b1, scol[1], cnt, t, kTile);
+    if (col[2]) rx_out::ext_store<1>(dst, b2, scol[2], cnt, t, kTile);
+}
+
 // kinds (0 = every configured kind) -> the handle's selection; statuses as tetra_rx_out.h
 int select_kinds(const tetra_rx* h, int kinds, int* sel) {
     if (kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) return TETRA_ERR_ARG;
@@ -194,6 +308,22 @@ int ring_slot(const tetra_rx* h, int64_t call) {
     return oldest >= 0 && call < min_call ? oldest : -1;
 }
 
+// TETRA_ERR_UNSUPPORTED for an extra whose flag the handle was created without, as its blocking fetch answers
+int extras_supported(const tetra_rx* h, int extras) {
+    if ((extras & (TETRA_RX_OUT_EXT_ROW_BITERR | TETRA_RX_OUT_EXT_CHAN_LINK)) && !h->biterr) return TETRA_ERR_UNSUPPORTED;
+    if ((extras & TETRA_RX_OUT_EXT_ROW_LIST_RANK) && !h->list) return TETRA_ERR_UNSUPPORTED;
+    if ((extras & TETRA_RX_OUT_EXT_ROW_AACH_DIST) && (!h->aach_rm || !(h->kinds & (1 << TETRA_RX_KIND_BBK)))) return TETRA_ERR_UNSUPPORTED;
+    if (extras & TETRA_RX_OUT_EXT_CHAN_SYNC_MISSES) {      // the counters exist once a tolerance was set (TETRA_RX_FLAG_SYNC_TOLERANT sets one)
+        const tetra_bsync_state_t* st = nullptr;
+        const int32_t* miss = nullptr;
+        TETRA_TRY(rx_snap_impl::bsync_tables(h->bs, &st, &miss));
+        if (!miss) return TETRA_ERR_UNSUPPORTED;
+    }
+    return TETRA_OK;
+}
+
+int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst, uint64_t capacity, int64_t* call);
+
 }  // namespace
 
 extern "C" {
@@ -215,12 +345,78 @@ int tetra_rx_out_bound(tetra_rx_t* h, int kinds, int flags, uint64_t* bytes) {
     return TETRA_OK;
 }
 
+int tetra_rx_out_bound_ext(tetra_rx_t* h, int kinds, int flags, int extras, uint64_t* bytes) {
+    if (!h || !bytes || (flags & ~rx_out::kFlagsAll) || (extras & ~rx_out::kExtrasAll)) return TETRA_ERR_ARG;
+    int sel = 0;
+    TETRA_TRY(select_kinds(h, kinds, &sel));
+    TETRA_TRY(extras_supported(h, extras));
+    TETRA_TRY(tetra_rx_out_bound(h, kinds, flags, bytes));
+    if (!extras) return TETRA_OK;
+    // the same worst case: every frame slot one burst type; every section starts on its own 16 bytes
+    uint64_t worst = 0, pads = 16 + 16 * (uint64_t)rx_out::kChanTables;
+    for (int list : { TETRA_LIST_SYNC, TETRA_LIST_NORM_1, TETRA_LIST_NORM_2 }) {
+        uint64_t b = 0;
+        for (int k = 0; k < TETRA_RX_N_KINDS; k++)
+            if ((sel & (1 << k)) && (kKinds[k].list == list || kKinds[k].list == TETRA_LIST_ANY))
+                for (int c = 0; c < rx_out::kRowCols; c++)
+                    if ((extras & rx_out::row_extra(c)) && rx_out::kind_has(k, c)) b += (uint64_t)h->rows * (uint64_t)rx_out::row_elem_bytes(c);
+        worst = b > worst ? b : worst;
+    }
+    for (int t = 0; t < rx_out::kChanTables; t++)
+        if (extras & rx_out::chan_extra(t)) worst += (uint64_t)rx_out::chan_elem_bytes(t) * (uint64_t)h->C;
+    pads += 16 * (uint64_t)rx_out::kRowCols * (uint64_t)__builtin_popcount((unsigned)sel);
+    *bytes += rx_out::kExtHeaderBytes + worst + pads;
+    return TETRA_OK;
+}
+
+int tetra_rx_out_set_snapshot(tetra_rx_t* h, int chan_extras) {
+    if (!h || (chan_extras & ~rx_out::kExtrasChan)) return TETRA_ERR_ARG;
+    TETRA_TRY(extras_supported(h, chan_extras));
+    if (chan_extras) {
+        DeviceGuard g(h->device);
+        if (!g.ok) return TETRA_ERR_NO_DEVICE;
+        for (auto& s : h->snap)
+            if (s.reserve((size_t)rx_out::snap_bytes(h->C)) != hipSuccess) {
+                (void)hipGetLastError();
+                return TETRA_ERR_NOMEM;
+            }
+    }
+    h->snap_mask = chan_extras;
+    return TETRA_OK;
+}
+
 int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* dst, uint64_t capacity, int64_t* call) {
+    return enqueue(h, which, kinds, flags, 0, dst, capacity, call);
+}
+
+int tetra_rx_out_enqueue_ext(tetra_rx_t* h, int which, int kinds, int flags, int extras, void* dst, uint64_t capacity, int64_t* call) {
+    if (extras & ~rx_out::kExtrasAll) return TETRA_ERR_ARG;
+    return enqueue(h, which, kinds, flags, extras, dst, capacity, call);
+}
+
+int tetra_rx_out_view_ext(const void* buf, uint64_t bytes, int kind, const uint32_t** biterr, const int32_t** rank, const uint8_t** aach_dist,
+                          int* n_rows) {
+    return rx_out::view_ext(buf, bytes, kind, biterr, rank, aach_dist, n_rows);
+}
+
+int tetra_rx_out_view_channels(const void* buf, uint64_t bytes, const tetra_lmac_cell_state_t** cell, const tetra_bsync_state_t** sync,
+                               const int32_t** misses, const tetra_rx_link_t** link, int* n_channels) {
+    return rx_out::view_channels(buf, bytes, cell, sync, misses, link, n_channels);
+}
+
+}  // extern "C"
+
+namespace {
+
+// tetra_rx_out_enqueue (extras = 0: its launches and nothing else) and tetra_rx_out_enqueue_ext
+int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst, uint64_t capacity, int64_t* call) {
     if (!h || !dst || which < 0 || which > 1 || (flags & ~rx_out::kFlagsAll)) return TETRA_ERR_ARG;
     int sel = 0;
     TETRA_TRY(select_kinds(h, kinds, &sel));
+    TETRA_TRY(extras_supported(h, extras));
     if (h->calls <= which) return TETRA_ERR_ARG;
     const int b = (int)((h->calls - 1 - which) & 1);
+    if (extras & rx_out::kExtrasChan & ~h->snap_taken[b]) return TETRA_ERR_ARG;      // that call's tail took no such snapshot
     if (capacity < rx_out::kHeaderBytes) return TETRA_ERR_SIZE;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
@@ -268,7 +464,23 @@ int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* d
     a.flags = flags;
     a.tiles = tiles;
     a.max_rows = h->rows;
-    int32_t* tile_off = h->out_tiles;                      // [kind][tile]: k_out_count's counts, scanned in place by k_out_layout
+    ExtArgs x = {};
+    ExtLayout* xl = nullptr;
+    if (extras) {
+        if (h->out_ext_layout.reserve(sizeof(ExtLayout)) != hipSuccess) {
+            (void)hipGetLastError();
+            return TETRA_ERR_NOMEM;
+        }
+        xl = reinterpret_cast<ExtLayout*>(h->out_ext_layout.get());
+        for (int i = 0; i < a.nsel; i++) {
+            x.k[i].biterr = h->res[b][a.k[i].kind].biterr;
+            x.k[i].rank = h->res[b][a.k[i].kind].rank;
+        }
+        x.snap = h->snap[b];
+        x.extras = extras;
+        x.n_channels = h->C;
+    }
+    int32_t* tile_off = h->out_tiles;                     // [kind][tile]: k_out_count's counts, scanned in place by k_out_layout
     for (auto& e : h->ring_ev)
         if (!e) HIP_TRY(h, hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
     Layout* lay = reinterpret_cast<Layout*>(h->out_layout.get());
@@ -277,7 +489,9 @@ int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* d
     HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[b], 0));
     if (flags & TETRA_RX_OUT_CRC_GOOD) hipLaunchKernelGGL(k_out_count, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(kTile), 0, s, a, tile_off);
     hipLaunchKernelGGL(k_out_layout, dim3(1), dim3(compact_core::kScanThreads), 0, s, a, tile_off, lay, d, capacity, c);
+    if (extras) hipLaunchKernelGGL(k_out_ext_layout, dim3(1), dim3(kTile), 0, s, a, x, tile_off, lay, xl, d, capacity, c);
     hipLaunchKernelGGL(k_out_write, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(256), 0, s, a, tile_off, lay, d);
+    if (extras) hipLaunchKernelGGL(k_out_ext_write, dim3((unsigned)tiles, (unsigned)a.nsel + 1), dim3(kTile), 0, s, a, x, tile_off, xl, d);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->ev_out[b], s));
     h->out_pending[b] = true;
@@ -288,6 +502,10 @@ int tetra_rx_out_enqueue(tetra_rx_t* h, int which, int kinds, int flags, void* d
     if (call) *call = c;
     return TETRA_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int tetra_rx_out_query(tetra_rx_t* h, int64_t call) {
     if (!h) return TETRA_ERR_ARG;

@@ -11,6 +11,7 @@
 
 #include "ext/tetra_biterr.h"
 #include "ext/tetra_list.h"
+#include "ext/tetra_rx_out_ext.h"
 #include "ext/tetra_sync_tol.h"
 #include "tetra_rx.h"
 #include "tetra_rx_out.h"
@@ -25,6 +26,16 @@ public:
         std::vector<uint8_t> type1;       // [info.size()][bitsPerBlock], one bit per byte
         int bitsPerBlock = 0;
         const uint8_t* bits(size_t row) const { return type1.data() + row * (size_t)bitsPerBlock; }
+        // the opt-in columns of an extended delivery (ext/tetra_rx_out_ext.h), row for row beside info; empty where not delivered
+        std::vector<uint32_t> biterr;     // errors | compared << 16 (coded kinds)
+        std::vector<int32_t> rank;        // list-decoding rank (coded kinds)
+        std::vector<uint8_t> aachDist;    // Reed-Muller distance (BBK)
+    };
+    struct Channels {                     // the per-channel state of the delivered call; empty where not delivered
+        std::vector<tetra_lmac_cell_state_t> cell;
+        std::vector<tetra_bsync_state_t> sync;
+        std::vector<int32_t> misses;
+        std::vector<tetra_rx_link_t> link;
     };
 
     TetraRxBank() {}
@@ -69,27 +80,43 @@ public:
     // One-step hand-off (include/tetra_rx_out.h): every kind of `kinds` (0 = every configured kind) of the latest (which = 0) or
     // previous (1) call, gathered by the GPU into one of this bank's two page-locked buffers without waiting; *call names the delivered
     // call for collect(), which must come before the second deliver() after this one.  flags: TETRA_RX_OUT_*.
-    int deliver(int64_t* call, int which = 0, int kinds = 0, int flags = 0) {
+    // extras: TETRA_RX_OUT_EXT_* (ext/tetra_rx_out_ext.h) -- the rows' opt-in columns and, for the channel extras armed with
+    // setSnapshot() when that call was processed, the call's per-channel state, in the same step.
+    int deliver(int64_t* call, int which = 0, int kinds = 0, int flags = 0, int extras = 0) {
         if (!h_ || !call) return TETRA_ERR_ARG;
         // two buffers, taken in turn, each sized once for the largest delivery the handle can make (every kind, byte per bit); the
         // delivery stream runs them in order, so a buffer is only rewritten after the delivery before it has completed
         OutBuf& o = out_[next_];
-        if (!o.buf) {
-            uint64_t need = 0;
-            const int rc = tetra_rx_out_bound(h_, 0, 0, &need);
+        uint64_t need = o.bytes;
+        if (extras) {                     // (also checks the extras against the handle's flags)
+            const int rc = tetra_rx_out_bound_ext(h_, 0, 0, extras, &need);
             if (rc != TETRA_OK) return rc;
+        }
+        if (!o.buf || need > o.bytes) {
+            if (!o.buf && !extras) {
+                const int rc = tetra_rx_out_bound(h_, 0, 0, &need);
+                if (rc != TETRA_OK) return rc;
+            }
+            if (o.buf) {                  // a larger one: the delivery last enqueued into this one has to be over first
+                if (o.call >= 0) (void)tetra_rx_out_wait(h_, o.call);
+                tetra_rx_out_host_free(o.buf);
+                o = OutBuf();
+            }
             if (!(o.buf = tetra_rx_out_host_alloc((size_t)need))) return TETRA_ERR_NOMEM;
             o.bytes = need;
         }
-        const int rc = tetra_rx_out_enqueue(h_, which, kinds, flags, o.buf, o.bytes, call);
+        const int rc = extras ? tetra_rx_out_enqueue_ext(h_, which, kinds, flags, extras, o.buf, o.bytes, call)
+                              : tetra_rx_out_enqueue(h_, which, kinds, flags, o.buf, o.bytes, call);
         if (rc != TETRA_OK) return rc;
         o.call = *call;
+        o.extras = extras;
         next_ ^= 1;
         return TETRA_OK;
     }
     // Waits for the delivery of `call` and copies its blocks out: out[kind] for every kind it holds (type-1 rows one bit per byte,
-    // unpacked if the delivery was packed); the other entries are left empty.
-    int collect(int64_t call, Blocks out[TETRA_RX_N_KINDS]) {
+    // unpacked if the delivery was packed); the other entries are left empty.  For a delivery with extras the columns it holds come
+    // with the rows, and *chans (may be null) receives its per-channel tables.
+    int collect(int64_t call, Blocks out[TETRA_RX_N_KINDS], Channels* chans = nullptr) {
         if (!h_ || call < 0) return TETRA_ERR_ARG;
         int rc = tetra_rx_out_wait(h_, call);
         if (rc != TETRA_OK) return rc;
@@ -100,6 +127,9 @@ public:
             Blocks& b = out[k];
             b.info.clear();
             b.type1.clear();
+            b.biterr.clear();
+            b.rank.clear();
+            b.aachDist.clear();
             b.bitsPerBlock = tetra_rx_type1_bits(k);
             const tetra_rx_block_t* blk = nullptr;
             const uint8_t* bits = nullptr;
@@ -108,6 +138,16 @@ public:
             if (rc == TETRA_ERR_UNSUPPORTED) continue;             // a kind the delivery does not hold
             if (rc != TETRA_OK) return rc;
             b.info.assign(blk, blk + n);
+            if (o.extras) {
+                const uint32_t* be = nullptr;
+                const int32_t* rk = nullptr;
+                const uint8_t* ad = nullptr;
+                rc = tetra_rx_out_view_ext(o.buf, o.bytes, k, &be, &rk, &ad, nullptr);
+                if (rc != TETRA_OK) return rc;
+                if (be) b.biterr.assign(be, be + n);
+                if (rk) b.rank.assign(rk, rk + n);
+                if (ad) b.aachDist.assign(ad, ad + n);
+            }
             if (rb == b.bitsPerBlock) {
                 b.type1.assign(bits, bits + (size_t)n * (size_t)rb);
                 continue;
@@ -116,8 +156,26 @@ public:
             rc = tetra_rx_unpack_bits(bits, n, rb, b.bitsPerBlock, b.type1.data(), b.bitsPerBlock);
             if (rc != TETRA_OK) return rc;
         }
+        if (chans) {
+            *chans = Channels();
+            if (o.extras) {
+                const tetra_lmac_cell_state_t* cell = nullptr;
+                const tetra_bsync_state_t* sync = nullptr;
+                const int32_t* misses = nullptr;
+                const tetra_rx_link_t* link = nullptr;
+                int n = 0;
+                rc = tetra_rx_out_view_channels(o.buf, o.bytes, &cell, &sync, &misses, &link, &n);
+                if (rc != TETRA_OK) return rc;
+                if (cell) chans->cell.assign(cell, cell + n);
+                if (sync) chans->sync.assign(sync, sync + n);
+                if (misses) chans->misses.assign(misses, misses + n);
+                if (link) chans->link.assign(link, link + n);
+            }
+        }
         return TETRA_OK;
     }
+    // ext/tetra_rx_out_ext.h: the channel extras (TETRA_RX_OUT_EXT_CHAN_*) every tail from the next call on snapshots for deliver()
+    int setSnapshot(int chanExtras) { return tetra_rx_out_set_snapshot(h_, chanExtras); }
     // tcd / t_phy_state of every channel (tetra_lower_mac.c:116, tetra_burst_sync.c:34 -- one per channel here)
     int cells(std::vector<tetra_lmac_cell_state_t>& out) {
         out.resize((size_t)channels_);
@@ -174,6 +232,7 @@ private:
         void* buf = nullptr;
         uint64_t bytes = 0;
         int64_t call = -1;                // the call last delivered into it
+        int extras = 0;                   // ... and the extras it was asked for
     };
     tetra_rx_t* h_ = nullptr;
     int channels_ = 0;
@@ -253,22 +312,60 @@ public:
     // Every kind of `kinds` (0 = all configured) in one step per shard: every shard's delivery is enqueued first, then each is
     // collected, so the GPUs' transfers run side by side.  out[kind] as fetch() returns it (bank channel numbers, (channel, frame)
     // order, one bit per byte); kinds outside the delivery come back empty.
-    int fetchAll(TetraRxBank::Blocks out[TETRA_RX_N_KINDS], int which = 0, int kinds = 0, int flags = 0) {
-        for (int k = 0; k < TETRA_RX_N_KINDS; k++) { out[k].info.clear(); out[k].type1.clear(); out[k].bitsPerBlock = tetra_rx_type1_bits(k); }
+    // extras (ext/tetra_rx_out_ext.h): the shards' columns one after the other like their rows, and *chans (may be null) the per-channel
+    // tables in the bank's channel order; the channel extras need setSnapshot() armed when that call was processed.
+    int fetchAll(TetraRxBank::Blocks out[TETRA_RX_N_KINDS], int which = 0, int kinds = 0, int flags = 0, int extras = 0,
+                 TetraRxBank::Channels* chans = nullptr) {
+        for (int k = 0; k < TETRA_RX_N_KINDS; k++) { out[k] = TetraRxBank::Blocks(); out[k].bitsPerBlock = tetra_rx_type1_bits(k); }
+        if (chans) *chans = TetraRxBank::Channels();
         std::vector<int64_t> calls(shards_.size(), -1);
         for (size_t s = 0; s < shards_.size(); s++) {
-            const int rc = shards_[s]->bank.deliver(&calls[s], which, kinds, flags);
+            const int rc = shards_[s]->bank.deliver(&calls[s], which, kinds, flags, extras);
             if (rc != TETRA_OK) return rc;
         }
         TetraRxBank::Blocks part[TETRA_RX_N_KINDS];
+        TetraRxBank::Channels cpart;
         for (size_t s = 0; s < shards_.size(); s++) {
-            const int rc = shards_[s]->bank.collect(calls[s], part);
+            const int rc = shards_[s]->bank.collect(calls[s], part, chans ? &cpart : nullptr);
             if (rc != TETRA_OK) return rc;
             for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
                 for (auto& b : part[k].info) b.channel += shards_[s]->first;
                 out[k].info.insert(out[k].info.end(), part[k].info.begin(), part[k].info.end());
                 out[k].type1.insert(out[k].type1.end(), part[k].type1.begin(), part[k].type1.end());
+                out[k].biterr.insert(out[k].biterr.end(), part[k].biterr.begin(), part[k].biterr.end());
+                out[k].rank.insert(out[k].rank.end(), part[k].rank.begin(), part[k].rank.end());
+                out[k].aachDist.insert(out[k].aachDist.end(), part[k].aachDist.begin(), part[k].aachDist.end());
             }
+            if (chans) {
+                chans->cell.insert(chans->cell.end(), cpart.cell.begin(), cpart.cell.end());
+                chans->sync.insert(chans->sync.end(), cpart.sync.begin(), cpart.sync.end());
+                chans->misses.insert(chans->misses.end(), cpart.misses.begin(), cpart.misses.end());
+                chans->link.insert(chans->link.end(), cpart.link.begin(), cpart.link.end());
+            }
+        }
+        return TETRA_OK;
+    }
+    int setSnapshot(int chanExtras) {
+        for (auto& s : shards_) { const int rc = s->bank.setSnapshot(chanExtras); if (rc != TETRA_OK) return rc; }
+        return TETRA_OK;
+    }
+    int syncStates(std::vector<tetra_bsync_state_t>& out) {
+        out.clear();
+        std::vector<tetra_bsync_state_t> part;
+        for (auto& s : shards_) {
+            const int rc = s->bank.syncStates(part);
+            if (rc != TETRA_OK) return rc;
+            out.insert(out.end(), part.begin(), part.end());
+        }
+        return TETRA_OK;
+    }
+    int syncMisses(std::vector<int32_t>& out) {
+        out.clear();
+        std::vector<int32_t> part;
+        for (auto& s : shards_) {
+            const int rc = s->bank.syncMisses(part);
+            if (rc != TETRA_OK) return rc;
+            out.insert(out.end(), part.begin(), part.end());
         }
         return TETRA_OK;
     }

@@ -94,15 +94,26 @@ LIST_ABI = {
     "tetra_rx_fetch_list_rank": (i32, [vp, i32, i32, vp, i32, P(i32)]),
     "tetra_rx_list_rank_device": (i32, [vp, i32, i32, P(vp), vp]),
 }
+# include/ext/tetra_rx_out_ext.h (the opt-in row extras and per-channel state through the one-step hand-off)
+OUT_EXT_ABI = {
+    "tetra_rx_out_bound_ext": (i32, [vp, i32, i32, i32, P(u64)]),
+    "tetra_rx_out_enqueue_ext": (i32, [vp, i32, i32, i32, i32, vp, u64, P(i64)]),
+    "tetra_rx_out_set_snapshot": (i32, [vp, i32]),
+    "tetra_rx_out_view_ext": (i32, [vp, u64, i32, P(vp), P(vp), P(vp), P(i32)]),
+    "tetra_rx_out_view_channels": (i32, [vp, u64, P(vp), P(vp), P(vp), P(vp), P(i32)]),
+}
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
+RX_OUT_EXT_EXPORTS = list(OUT_EXT_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
-    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI},
-                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI))
+    return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
+                                    **OUT_EXT_ABI},
+                   optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
+                   RX_OUT_EXT_EXPORTS)
 
 
 def type1_bits(kind):
@@ -271,17 +282,28 @@ class RxChain:
     def demod_handle(self):
         return self._lib.tetra_rx_demod(self._h)
 
-    def deliver(self, which=0, kinds=0, packed=False, crc_good_only=False, buf=None):
+    def set_snapshot(self, chan_extras):
+        """tetra_rx_out_set_snapshot: the channel extras (EXT_CHAN_*) every tail from the next call on copies into its call's snapshot,
+        which deliver(extras=...) of that call then reads; 0 disarms."""
+        call(self._lib.tetra_rx_out_set_snapshot, self._h, int(chan_extras))
+
+    def deliver(self, which=0, kinds=0, packed=False, crc_good_only=False, buf=None, extras=0):
         """Enqueue a delivery of the latest (which = 0) or previous (1) call's blocks of `kinds` (bit mask, 0 = every configured kind)
         and return a Delivery without waiting.  buf = None: the next of two page-locked buffers of this handle (sized for the worst case),
         so the arrays a Delivery returns stay valid until the second delivery after it is enqueued; else a HostBuffer, a torch tensor on
-        the handle's GPU, or any object with a .ctypes pointer (pageable memory is refused: TETRA_ERR_ARG)."""
+        the handle's GPU, or any object with a .ctypes pointer (pageable memory is refused: TETRA_ERR_ARG).
+        extras (EXT_ROW_* | EXT_CHAN_*, include/ext/tetra_rx_out_ext.h): the rows' opt-in columns and the call's per-channel state in
+        the same buffer; the channel extras need set_snapshot armed with them when that call was processed."""
         flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
         if buf is None:
             if getattr(self, "_pool", None) is None:
-                nb = C.c_uint64(0)
-                call(self._lib.tetra_rx_out_bound, self._h, 0, 0, C.byref(nb))
-                self._pool, self._pool_next = [HostBuffer(nb.value) for _ in range(2)], 0
+                # sized once, for every extra this handle can ever deliver (the miss counters may be enabled later: counted by hand)
+                nb, can = C.c_uint64(0), 0
+                for bit in (EXT_ROW_BITERR, EXT_ROW_LIST_RANK, EXT_ROW_AACH_DIST, EXT_CHAN_CELL, EXT_CHAN_SYNC_STATE, EXT_CHAN_LINK):
+                    if self._lib.tetra_rx_out_bound_ext(self._h, 0, 0, bit, C.byref(nb)) == 0:
+                        can |= bit
+                call(self._lib.tetra_rx_out_bound_ext, self._h, 0, 0, can, C.byref(nb))
+                self._pool, self._pool_next = [HostBuffer(nb.value + 16 + 4 * self.n_channels) for _ in range(2)], 0
             buf = self._pool[self._pool_next]
             self._pool_next ^= 1
         if isinstance(buf, HostBuffer):
@@ -291,13 +313,19 @@ class RxChain:
         else:
             dst, cap = buf.ctypes.data, buf.nbytes
         ticket = C.c_int64(-1)
-        call(self._lib.tetra_rx_out_enqueue, self._h, which, kinds, flags, dst, cap, C.byref(ticket))
-        return Delivery(self, ticket.value, buf, cap)
+        if extras:
+            call(self._lib.tetra_rx_out_enqueue_ext, self._h, which, kinds, flags, int(extras), dst, cap, C.byref(ticket))
+        else:
+            call(self._lib.tetra_rx_out_enqueue, self._h, which, kinds, flags, dst, cap, C.byref(ticket))
+        return Delivery(self, ticket.value, buf, cap, extras)
 
-    def out_bound(self, kinds=0, packed=False, crc_good_only=False):
+    def out_bound(self, kinds=0, packed=False, crc_good_only=False, extras=0):
         nb = C.c_uint64(0)
         flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
-        call(_lib().tetra_rx_out_bound, self._h, kinds, flags, C.byref(nb))
+        if extras:
+            call(_lib().tetra_rx_out_bound_ext, self._h, kinds, flags, int(extras), C.byref(nb))
+        else:
+            call(_lib().tetra_rx_out_bound, self._h, kinds, flags, C.byref(nb))
         return nb.value
 
     def _close_pool(self):
@@ -320,6 +348,27 @@ class OutKind(C.Structure):
 class OutHeader(C.Structure):
     _fields_ = [("magic", C.c_uint32), ("status", C.c_int32), ("flags", C.c_int32), ("n_kinds", C.c_int32), ("call", C.c_int64),
                 ("bytes", C.c_uint64), ("kinds", OutKind * N_KINDS)]
+
+
+# the extension block (include/ext/tetra_rx_out_ext.h)
+EXT_ROW_BITERR, EXT_ROW_LIST_RANK, EXT_ROW_AACH_DIST = 1, 2, 4
+EXT_CHAN_CELL, EXT_CHAN_SYNC_STATE, EXT_CHAN_SYNC_MISSES, EXT_CHAN_LINK = 16, 32, 64, 128
+EXT_ROW_ALL, EXT_CHAN_ALL = 7, 240
+OUT_EXT_MAGIC = 0x58585254
+CELL_DTYPE = np.dtype([(n, "<u4") for n, _ in CellState._fields_])
+SYNC_STATE_DTYPE = np.dtype([("state", "<i4"), ("bits_in_buf", "<u4"), ("bitbuf_start_bitnum", "<u4"), ("next_frame_start_bitnum", "<u4")])
+LINK_DTYPE = np.dtype([("bits", "<u8"), ("bit_errors", "<u8"), ("blocks", "<u4"), ("blocks_crc_bad", "<u4")])
+
+
+class OutExtKind(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("biterr_offset", C.c_uint64), ("rank_offset", C.c_uint64),
+                ("aach_dist_offset", C.c_uint64)]
+
+
+class OutExtHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint32), ("extras", C.c_int32), ("call", C.c_int64), ("n_channels", C.c_int32), ("n_kinds", C.c_int32),
+                ("bytes", C.c_uint64), ("cell_offset", C.c_uint64), ("sync_state_offset", C.c_uint64), ("sync_misses_offset", C.c_uint64),
+                ("link_offset", C.c_uint64), ("kinds", OutExtKind * N_KINDS)]
 
 
 class HostBuffer:
@@ -365,6 +414,44 @@ def view_delivery(buf, nbytes=None):
     return hd, out
 
 
+def view_delivery_ext(buf, nbytes=None):
+    """The extension block of a completed extended delivery in host memory -> (extension header, {kind: {"biterr": uint32 [n] or None,
+    "rank": int32 [n] or None, "aach_dist": uint8 [n] or None}}, {"cell": CELL_DTYPE [C], "sync_state": SYNC_STATE_DTYPE [C],
+    "sync_misses": int32 [C], "link": LINK_DTYPE [C]} with None for a table the delivery does not hold): numpy views into the buffer
+    (tetra_rx_out_view_ext / tetra_rx_out_view_channels).  A buffer without an extension block raises (TETRA_ERR_UNSUPPORTED)."""
+    L = _lib()
+    arr = buf.array if isinstance(buf, HostBuffer) else buf
+    nbytes = arr.nbytes if nbytes is None else int(nbytes)
+    base = arr.ctypes.data
+    hd = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+
+    def at(p, n, dtype):
+        if not p.value:
+            return None
+        o = p.value - base
+        return arr[o: o + n * dtype.itemsize].view(dtype)
+
+    cols = {}
+    for i in range(max(0, min(hd.n_kinds, N_KINDS))):
+        k = hd.kinds[i].kind
+        pe, pr, pd, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        call(L.tetra_rx_out_view_ext, base, nbytes, k, C.byref(pe), C.byref(pr), C.byref(pd), C.byref(n))
+        cols[k] = dict(biterr=at(pe, n.value, np.dtype("<u4")), rank=at(pr, n.value, np.dtype("<i4")), aach_dist=at(pd, n.value, np.dtype("u1")))
+    pc, ps, pm, pl, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    call(L.tetra_rx_out_view_channels, base, nbytes, C.byref(pc), C.byref(ps), C.byref(pm), C.byref(pl), C.byref(nc))
+    chans = dict(cell=at(pc, nc.value, CELL_DTYPE), sync_state=at(ps, nc.value, SYNC_STATE_DTYPE), sync_misses=at(pm, nc.value, np.dtype("<i4")),
+                 link=at(pl, nc.value, LINK_DTYPE))
+    o = (int(hd.bytes) + 15) // 16 * 16
+    return OutExtHeader.from_buffer_copy(arr[o: o + C.sizeof(OutExtHeader)].tobytes()), cols, chans
+
+
+class DeliveryRows(dict):
+    """What Delivery.wait() returns: {kind: (blocks, type1)}, and for an extended delivery .columns = {kind: {"biterr", "rank",
+    "aach_dist"}} and .channels = {"cell", "sync_state", "sync_misses", "link"} (view_delivery_ext); both None otherwise."""
+    columns = None
+    channels = None
+
+
 def unpack_bits(packed, n_bits):
     """Packed rows [n][row_bytes] (first bit in bit 7) -> uint8 [n][n_bits], one bit per byte (tetra_rx_unpack_bits)."""
     packed = np.ascontiguousarray(packed, np.uint8)
@@ -377,9 +464,9 @@ def unpack_bits(packed, n_bits):
 class Delivery:
     """One enqueued delivery (RxChain.deliver).  ready() polls; wait() blocks and returns {kind: (blocks, type1)}."""
 
-    def __init__(self, chain, call, buf, capacity):
-        self.chain, self.call, self.buf, self.capacity = chain, call, buf, capacity
-        self.header = None
+    def __init__(self, chain, call, buf, capacity, extras=0):
+        self.chain, self.call, self.buf, self.capacity, self.extras = chain, call, buf, capacity, extras
+        self.header = self.ext_header = None
 
     def ready(self):
         rc = self.chain._lib.tetra_rx_out_query(self.chain._h, self.call)
@@ -392,12 +479,21 @@ class Delivery:
         buf = self.buf
         if hasattr(buf, "data_ptr"):              # a device tensor: the header says how much to bring over
             head = buf[:C.sizeof(OutHeader)].cpu().numpy()
-            need = int(OutHeader.from_buffer_copy(head.tobytes()).bytes)
+            hd = OutHeader.from_buffer_copy(head.tobytes())
+            need = int(hd.bytes)
+            if self.extras and hd.status == 0:      # the extension header behind the classic part says how long the whole is
+                o = (need + 15) // 16 * 16
+                if o + C.sizeof(OutExtHeader) <= self.capacity:
+                    ex = OutExtHeader.from_buffer_copy(buf[o: o + C.sizeof(OutExtHeader)].cpu().numpy().tobytes())
+                    need = int(ex.bytes) if ex.magic == OUT_EXT_MAGIC else need
             buf = buf[:min(need, self.capacity)].cpu().numpy() if need <= self.capacity else head
             self.host_copy = buf
         arr = buf.array if isinstance(buf, HostBuffer) else buf
         self.header = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
         if self.header.status:
             raise TetraDemodError(self.header.status, "tetra_rx delivery (needs %d bytes)" % self.header.bytes)
-        return view_delivery(buf, min(arr.nbytes, self.capacity))[1]
+        rows = DeliveryRows(view_delivery(buf, min(arr.nbytes, self.capacity))[1])
+        if self.extras:
+            self.ext_header, rows.columns, rows.channels = view_delivery_ext(buf, min(arr.nbytes, self.capacity))
+        return rows
 

@@ -103,7 +103,8 @@ class WidebandRx:
     """An SDR capture in, the decoded blocks of the carriers on `bins` out: channeliser (M bins) -> selecting 18 / 25 resampler ->
     receive chain on one GPU.  `.rx` is the chain (an RxChain view); a block's channel is the carrier's index into `bins`.  shift:
     the channeliser's frequency shift (include/tetra_shift.h, 2^-32 cycles per input sample) for carriers that share one offset from
-    the bins' centres, e.g. chan_binding.shift_from_hz(12500, 20e6) for half a bin."""
+    the bins' centres, e.g. chan_binding.shift_from_hz(12500, 20e6) for half a bin.  Extended deliveries (ext/tetra_rx_out_ext.h) need
+    nothing here: `.rx.set_snapshot(mask)` and `.rx.deliver(..., extras=mask)` work on the chain tetra_wbrx_rx hands out."""
 
     def __init__(self, bins, n_channels=800, taps_per_channel=8, decimation=None, max_in=1 << 20, device=-1, chan_cutoff_rel=1.2,
                  chan_flags=0, interp=18, decim=25, taps_per_phase=16, resamp_cutoff_rel=1.0, resamp_kaiser_beta=6.0, kinds=0, flags=0,
