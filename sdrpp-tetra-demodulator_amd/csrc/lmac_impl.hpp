@@ -1,6 +1,6 @@
 // lmac_impl.hpp -- the frame decoder (tetra_lmac.hip) as its callers inside the library see it: ONE function, decode_frames, that takes
-// every option of a frame launch as a FrameOpts.  The three frame entry points of the C ABI (tetra_lmac_decode_frames_device,
-// _biterr_device, _list_device) are it with the options their signatures can express; the receive chain (tetra_rx.hip) builds the
+// every option of a frame launch as a FrameOpts.  The four frame entry points of the C ABI (tetra_lmac_decode_frames_device,
+// _biterr_device, _list_device, _soft_device) are it with the options their signatures can express; the receive chain (tetra_rx.hip) builds the
 // options from its handle's flags -- soft values from the chain's ring, bit-error counts, ranks, where the list launches keep their work --
 // and calls it directly.  Host-side, hidden from the C ABI.
 #pragma once

@@ -37,6 +37,7 @@
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/ext/tetra_list.h"
+#include "../../include/ext/tetra_soft.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "compact_core.hpp"
@@ -1049,6 +1050,12 @@ int tetra_lmac_decode_frames_device(const tetra_lmac_frames_t* src, const tetra_
 int tetra_lmac_decode_frames_biterr_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, uint32_t* const* d_biterr,
                                            void* hip_stream) {
     return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{ nullptr, d_biterr, nullptr, 0, {} }, hip_stream);
+}
+
+int tetra_lmac_decode_frames_soft_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const int8_t* d_ring, uint32_t ring_size,
+                                         uint32_t* const* d_biterr, int32_t* const* d_rank, int max_candidates, void* hip_stream) {
+    const lmac_impl::SoftRing ring{ d_ring, ring_size };       // (a NULL ring is refused there: never "no ring", the hard route)
+    return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{ &ring, d_biterr, d_rank, max_candidates, {} }, hip_stream);
 }
 
 size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {

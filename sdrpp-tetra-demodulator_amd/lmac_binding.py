@@ -69,13 +69,19 @@ LIST_ABI = {
     "tetra_lmac_decode_frames_list_device": (i32, [P(Frames), P(Job), i32, i32, P(vp), vp]),
 }
 LIST_MAX_CANDIDATES, LIST_DEFAULT_CANDIDATES = 8, 4            # TETRA_LIST_MAX_CANDIDATES, TETRA_LIST_DEFAULT_CANDIDATES
+# include/ext/tetra_soft.h
+SOFT_ABI = {
+    "tetra_lmac_decode_frames_soft_device": (i32, [P(Frames), P(Job), i32, vp, u32, P(vp), P(vp), i32, vp]),
+}
 LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
+SOFT_EXPORTS = list(SOFT_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI}, optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI},
+                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS)
 
 
 def force_byte_route(on):
@@ -223,6 +229,18 @@ def decode_frames_list_device(d_frames, d_frame_type, jobs, max_candidates=LIST_
     arr = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
     call(_lib().tetra_lmac_decode_frames_list_device, C.byref(src), _job_array(jobs), len(jobs), int(max_candidates), arr if ranked else None,
          stream_ptr(stream))
+
+
+def decode_frames_soft(d_frames, d_frame_type, jobs, d_ring, ring_size, frames_per_channel, d_frame_bitnum, max_candidates=LIST_DEFAULT_CANDIDATES,
+                       d_time_rx=None, d_time=None, stream=None, d_workspace=None, counted=True, ranked=True):
+    """tetra_lmac_decode_frames_soft_device (include/ext/tetra_soft.h): decode_frames_device whose coded kinds read soft values from
+    d_ring (int8 tensor [channels][ring_size], or a raw device address) at the frames' bit numbers.  Jobs may carry `biterr` and `rank` as for
+    decode_frames_biterr_device / decode_frames_list_device; counted=False / ranked=False hand in no array at all."""
+    src = _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace)
+    counts = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
+    ranks = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
+    call(_lib().tetra_lmac_decode_frames_soft_device, C.byref(src), _job_array(jobs), len(jobs), ptr(d_ring), int(ring_size),
+         counts if counted else None, ranks if ranked else None, int(max_candidates), stream_ptr(stream))
 
 
 def track_sync_lists_device(d_sb1_type2, type2_stride, d_crc_ok, d_frame_type, d_n_frames, d_chan_first_sync, n_channels, frames_per_channel,

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from oracle import hostlib
-from tests.emul.lmac_soft_emul_bind import KINDS, TYPE2_BITS
+from tests.soft_pipeline import KINDS, TYPE2_BITS, lay_rings
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -73,14 +73,7 @@ def decode_soft_rows(kind, soft_rows, scramb, T, ring=1024, bitnum=None):
     tpsap, blk, train, pieces = KINDS[kind]
     rows = np.ascontiguousarray(soft_rows, np.int8)
     n = len(rows)
-    bn = (np.arange(n, dtype=np.uint64) * 37 + 0xfffffe00).astype(np.uint32) if bitnum is None else np.ascontiguousarray(bitnum, np.uint32)
-    rings = np.random.default_rng(5).integers(-31, 32, (n, ring)).astype(np.int8)
-    at = 0
-    for off, ln in pieces:
-        idx = (bn[:, None].astype(np.int64) + off + np.arange(ln)[None, :]) % ring
-        np.put_along_axis(rings, idx, rows[:, at:at + ln], axis=1)
-        at += ln
-    assert at == rows.shape[1]
+    rings, bn = lay_rings(kind, rows, ring, bitnum)
     ft = np.full(n, train, np.int32)
     sc = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
     n2 = TYPE2_BITS[kind]

@@ -5,22 +5,13 @@ import os
 import numpy as np
 
 from oracle import hostlib
+from tests.soft_pipeline import KINDS, TYPE2_BITS, lay_rings  # noqa: F401 (the kinds' tables: also imported from here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "liblmac_soft_emul.so")
 CSRC = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd", "csrc")
 DEPS = [os.path.join(HERE, "lmac_soft_emul.cpp"), os.path.join(HERE, "lmac_lane_io.hpp")] + [os.path.join(CSRC, f) for f in ("soft_core.hpp", "lmac_core.hpp", "demux_core.hpp")]
-
-# where a kind's type-5 bits sit in its 510-bit burst (tetra_burst.c:343-393): (tpsap, blk_num, burst type, pieces (offset, length))
-KINDS = {
-    "sb1": (0, 1, 3, ((94, 120),)),
-    "sb2": (1, 2, 3, ((282, 216),)),
-    "ndb1": (2, 1, 1, ((14, 216),)),
-    "ndb2": (2, 2, 1, ((282, 216),)),
-    "schf": (5, 0, 0, ((14, 216), (282, 216))),
-}
-TYPE2_BITS = {"sb1": 80, "sb2": 144, "ndb1": 144, "ndb2": 144, "schf": 288}
 
 _lib = None
 
@@ -82,14 +73,7 @@ def decode_rows(kind, soft_rows, scramb=None, ring=1024, bitnum=None):
     tpsap, blk, train, pieces = KINDS[kind]
     rows = np.ascontiguousarray(soft_rows, np.int8)
     n = len(rows)
-    bn = (np.arange(n, dtype=np.uint64) * 37 + 0xfffffe00).astype(np.uint32) if bitnum is None else np.ascontiguousarray(bitnum, np.uint32)
-    rings = np.random.default_rng(5).integers(-31, 32, (n, ring)).astype(np.int8)
-    at = 0
-    for off, ln in pieces:
-        idx = (bn[:, None].astype(np.int64) + off + np.arange(ln)[None, :]) % ring
-        np.put_along_axis(rings, idx, rows[:, at:at + ln], axis=1)
-        at += ln
-    assert at == rows.shape[1]
+    rings, bn = lay_rings(kind, rows, ring, bitnum)
     ft = np.full(n, train, np.int32)
     sc = None if scramb is None else np.ascontiguousarray(scramb, np.uint32)
     n2 = TYPE2_BITS[kind]

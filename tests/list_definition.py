@@ -126,10 +126,8 @@ def list_decode(t, v3, T, start, forced_first=None):
     return res
 
 
-def count_errors(t, row, code, type2, soft=False):
-    """(errors, compared) of include/ext/tetra_biterr.h for a received byte row and decoded type-2 bits: the bits encoded again from the
-    all-zero state (g1, g2 of every even step, g1 of every odd one), interleaved, and held against the descrambled row where it is
-    not an erasure."""
+def type4_of(t, type2):
+    """Type-2 bits (tail included) encoded from the all-zero state (g1, g2 of every even step, g1 of every odd one) and interleaved."""
     n345, n2, _, a = BLK[t]
     d = np.concatenate([np.zeros(4, np.int64), np.asarray(type2[:n2], np.int64)])
     k = np.arange(n2) + 4
@@ -139,6 +137,29 @@ def count_errors(t, row, code, type2, soft=False):
     type3[0::3], type3[1::3], type3[2::3] = g1[0::2], g2[0::2], g1[1::2]
     type4 = np.zeros(n345, np.int64)
     type4[(a * np.arange(1, n345 + 1)) % n345] = type3
+    return type4
+
+
+def encode(t, type1, code):
+    """A transmitter: type-1 bits -> type-5 bits uint8 [type345].  The CRC appended is the ones' complement of crc_good's register over
+    the type-1 bits, first bit most significant; then four zero tail bits, type4_of, and the scrambling sequence of the block's code."""
+    n345, n2, n1, _ = BLK[t]
+    r = 0xffff
+    for b in np.asarray(type1[:n1], np.int64):
+        r = ((r << 1) & 0xffff) ^ ((((r >> 15) & 1) ^ int(b)) * 0x1021)
+    type2 = np.zeros(n2, np.int64)
+    type2[:n1] = type1[:n1]
+    type2[n1:n1 + 16] = [((r ^ 0xffff) >> (15 - i)) & 1 for i in range(16)]
+    assert crc_good(type2[None, :n1 + 16])[0]
+    return (type4_of(t, type2) ^ scramb_seq(SCRAMB_INIT if t == 0 else code, n345)).astype(np.uint8)
+
+
+def count_errors(t, row, code, type2, soft=False):
+    """(errors, compared) of include/ext/tetra_biterr.h for a received byte row and decoded type-2 bits: the bits encoded again from the
+    all-zero state (g1, g2 of every even step, g1 of every odd one), interleaved, and held against the descrambled row where it is
+    not an erasure."""
+    n345 = BLK[t][0]
+    type4 = type4_of(t, type2)
     seq = scramb_seq(SCRAMB_INIT if t == 0 else code, n345)
     if soft:        # soft values as received (positive = 0): zero carries no decision, negative after descrambling is a 1
         v = np.where(seq != 0, -np.asarray(row[:n345], np.int64), np.asarray(row[:n345], np.int64))

@@ -23,6 +23,72 @@ PIECES = {
 BURST_KINDS = {TRAIN_SYNC: (KIND_SB1, KIND_BBK, KIND_SB2), TRAIN_NORM_2: (KIND_BBK, KIND_NDB1, KIND_NDB2), TRAIN_NORM_1: (KIND_BBK, KIND_SCH_F)}
 TYPE1_BITS = (60, 30, 124, 124, 124, 268)
 
+# ---- planted inputs of the soft frame decoder: shared by the host emulation's tests and the GPU tests -----------------------------------
+# where a kind's type-5 bits sit in its 510-bit burst (tetra_burst.c:343-393): (tpsap, blk_num, burst type, pieces (offset, length))
+KINDS = {
+    "sb1": (0, 1, 3, ((94, 120),)),
+    "sb2": (1, 2, 3, ((282, 216),)),
+    "ndb1": (2, 1, 1, ((14, 216),)),
+    "ndb2": (2, 2, 1, ((282, 216),)),
+    "schf": (5, 0, 0, ((14, 216), (282, 216))),
+}
+TYPE2_BITS = {"sb1": 80, "sb2": 144, "ndb1": 144, "ndb2": 144, "schf": 288}
+REF_TPSAP = {"sb1": 0, "sb2": 1, "ndb1": 2, "ndb2": 2, "schf": 5}
+
+
+def soft_rows_for(lref, kind, rng):
+    """int8 rows [n][type345] and their scrambling codes: clean codewords of the reference's encoder at several amplitudes, noisy
+    ones, uniform random values, the overflow bound's rows (all +Q, all -Q, alternating) and rows of ties (all zero, sparse)."""
+    tpsap = REF_TPSAP[kind]
+    n345, n2, n1, a, _ = lref.BLK_PARAM[tpsap]
+    rows, codes = [], []
+    for i in range(12):
+        code = int(rng.integers(0, 1 << 32))
+        t5 = lref.lmac_encode(tpsap, rng.integers(0, 2, n1).astype(np.uint8), code)
+        clean = (1 - 2 * t5.astype(np.int32))
+        amp = (Q, 16, 1, 5)[i % 4]
+        rows.append(clean * amp), codes.append(code)
+        for sigma in (6.0, 12.0, 20.0):
+            rows.append(np.clip(np.rint(clean * 16 + rng.normal(0, sigma, n345)), -Q, Q)), codes.append(code)
+    for i in range(24):
+        rows.append(rng.integers(-Q, Q + 1, n345)), codes.append(int(rng.integers(0, 1 << 32)))
+    alt = np.where(np.arange(n345) % 2 == 0, Q, -Q)
+    for r in (np.full(n345, Q), np.full(n345, -Q), alt, -alt, np.zeros(n345)):
+        for code in (0, 3, 0xffffffff, int(rng.integers(0, 1 << 32))):
+            rows.append(r), codes.append(code)
+    for i in range(8):                                     # mostly ties
+        r = np.zeros(n345)
+        r[rng.integers(0, n345, 6)] = rng.integers(-Q, Q + 1, 6)
+        rows.append(r), codes.append(int(rng.integers(0, 1 << 32)))
+    return np.array(rows, np.int8), np.array(codes, np.uint32)
+
+
+class DefinitionEncoder:
+    """soft_rows_for's `lref` where the reference is not built: its block parameters, and tests/list_definition.py's transmitter (which
+    tests/test_lmac_soft_gpu.py holds against the reference's lmac_encode where that is at hand)."""
+    BLK_PARAM = {0: (120, 80, 60, 11, 1), 1: (216, 144, 124, 101, 1), 2: (216, 144, 124, 101, 1), 5: (432, 288, 268, 103, 1)}
+
+    @staticmethod
+    def lmac_encode(tpsap, type1, code):
+        from tests import list_definition
+        return list_definition.encode(tpsap, type1, code)
+
+
+def lay_rings(kind, rows, ring=1024, bitnum=None):
+    """Every row laid into a ring of its own at the kind's burst positions behind bit number bitnum[j] (None: spread so that rows wrap
+    their ring at every offset), the rest of the ring filled with junk -> (rings int8 [n][ring], bit numbers uint32 [n])."""
+    tpsap, blk, train, pieces = KINDS[kind]
+    n = len(rows)
+    bn = (np.arange(n, dtype=np.uint64) * 37 + 0xfffffe00).astype(np.uint32) if bitnum is None else np.ascontiguousarray(bitnum, np.uint32)
+    rings = np.random.default_rng(5).integers(-31, 32, (n, ring)).astype(np.int8)
+    at = 0
+    for off, ln in pieces:
+        idx = (bn[:, None].astype(np.int64) + off + np.arange(ln)[None, :]) % ring
+        np.put_along_axis(rings, idx, rows[:, at:at + ln], axis=1)
+        at += ln
+    assert at == rows.shape[1]
+    return rings, bn
+
 
 def quantise_np(sym, prev=FRESH_PREV):
     """The quantiser restated in numpy binary32: sym complex64 [n] -> int8 [2n] (bit 2k: d.re + d.im, bit 2k+1: d.re - d.im of

@@ -21,7 +21,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "rx_soft_golden.npz")
 OP_CHANNELS, OP_SLOTS, OP_SAMPLES, OP_ESN0_DB, OP_SEED = 5, 71, 36000, 11.0, 9000
 OP_SCHF = {"hard": (118, 97), "soft": (118, 106)}            # (rows, CRC-good rows)
 KINDS = ("sb1", "sb2", "ndb1", "ndb2", "schf")
-REF_TPSAP = {"sb1": 0, "sb2": 1, "ndb1": 2, "ndb2": 2, "schf": 5}
+REF_TPSAP, soft_rows_for = sp.REF_TPSAP, sp.soft_rows_for
 
 
 def operating_point_iq(synth):
@@ -57,33 +57,6 @@ def semul():
 
 
 # ---- CPU: the lane code against the reference's soft decoder -----------------------------------------------------------------------
-
-def soft_rows_for(lref, kind, rng):
-    """int8 rows [n][type345] and their scrambling codes: clean codewords of the reference's encoder at several amplitudes, noisy
-    ones, uniform random values, the overflow bound's rows (all +Q, all -Q, alternating) and rows of ties (all zero, sparse)."""
-    tpsap = REF_TPSAP[kind]
-    n345, n2, n1, a, _ = lref.BLK_PARAM[tpsap]
-    rows, codes = [], []
-    for i in range(12):
-        code = int(rng.integers(0, 1 << 32))
-        t5 = lref.lmac_encode(tpsap, rng.integers(0, 2, n1).astype(np.uint8), code)
-        clean = (1 - 2 * t5.astype(np.int32))
-        amp = (sp.Q, 16, 1, 5)[i % 4]
-        rows.append(clean * amp), codes.append(code)
-        for sigma in (6.0, 12.0, 20.0):
-            rows.append(np.clip(np.rint(clean * 16 + rng.normal(0, sigma, n345)), -sp.Q, sp.Q)), codes.append(code)
-    for i in range(24):
-        rows.append(rng.integers(-sp.Q, sp.Q + 1, n345)), codes.append(int(rng.integers(0, 1 << 32)))
-    alt = np.where(np.arange(n345) % 2 == 0, sp.Q, -sp.Q)
-    for r in (np.full(n345, sp.Q), np.full(n345, -sp.Q), alt, -alt, np.zeros(n345)):
-        for code in (0, 3, 0xffffffff, int(rng.integers(0, 1 << 32))):
-            rows.append(r), codes.append(code)
-    for i in range(8):                                     # mostly ties
-        r = np.zeros(n345)
-        r[rng.integers(0, n345, 6)] = rng.integers(-sp.Q, sp.Q + 1, 6)
-        rows.append(r), codes.append(int(rng.integers(0, 1 << 32)))
-    return np.array(rows, np.int8), np.array(codes, np.uint32)
-
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_emulated_soft_decoder_equals_the_reference_chain(lref, semul, kind):
