@@ -1,5 +1,6 @@
-// retune_impl.hpp -- what tetra_retune.hip needs from the stages whose handles are private to their sources: views of their
-// per-channel state (retune_core.hpp) and the resampler's switch to picked columns.  Host-side, hidden from the C ABI.
+// retune_impl.hpp -- what tetra_retune.hip and the receive chain (rx_handle.hpp) need from the stages whose handles are private to
+// their sources: views of their per-channel state (retune_core.hpp), the synchroniser's per-channel tables where they are, and the
+// resampler's switch to picked columns.  Host-side, hidden from the C ABI.
 #pragma once
 
 #include "../../include/tetra_burst_sync.h"
@@ -15,7 +16,15 @@ namespace retune_impl {
 TETRA_HIDDEN int demod_view(tetra_demod_t* h, retune::DemodView* out);
 // tetra_burst_sync.hip
 TETRA_HIDDEN int bsync_view(tetra_bsync_t* h, retune::BsyncView* out);
-TETRA_HIDDEN int bsync_miss_view(tetra_bsync_t* h, retune::CellView* out);
+// ... and its per-channel tables on the device, [n_channels] each.  The miss counters exist from the first switch to the tolerant rule
+// (ext/tetra_sync_tol.h) on and stay when the handle returns to the reference's rule: `miss` says whether they exist, `tolerant`
+// whether they count.
+struct BsyncTables {
+    tetra_bsync_state_t* state;
+    int32_t* miss;
+    bool tolerant;
+};
+TETRA_HIDDEN int bsync_tables(tetra_bsync_t* h, BsyncTables* out);
 // tetra_resamp.hip: a handle that runs all its channels in place (16-byte lane units) becomes one that picks columns (8-byte units,
 // what TETRA_RESAMP_FLAG_NARROW_UNITS gives at create).  Same floats; the delay line's layout does not depend on the unit width.
 TETRA_HIDDEN int resamp_narrow_units(tetra_resamp_t* h);

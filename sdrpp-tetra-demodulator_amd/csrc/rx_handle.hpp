@@ -7,7 +7,9 @@
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_rx.h"
 #include "hip_host.hpp"
+#include "retune_impl.hpp"
 #include "retune_list.hpp"
+#include "rx_out_core.hpp"
 
 namespace tetra_rx_impl {
 
@@ -37,6 +39,18 @@ struct KindBufs {                 // one parity's results of one kind
     // into the parity's frame lists (not owned): the kind's rows are the frames row_frame[0 .. *n_rows)
     const int32_t* row_frame = nullptr;
     const int32_t* n_rows = nullptr;
+};
+
+// The opt-in row columns and the per-channel tables in rx_out's order (rx_out::kRowCols, kChanTables; row_extra / chan_extra are their
+// delivery bits, row_elem_bytes / chan_elem_bytes their element sizes, kind_has which kinds carry a column).  What this handle has
+// of them and where it lies is stated once, in row_col and chan_tab behind the handle below.
+enum { COL_BITERR, COL_RANK, COL_AACH_DIST };
+enum { TAB_CELL, TAB_SYNC_STATE, TAB_SYNC_MISSES, TAB_LINK };
+// the Reed-Muller distance of a BBK row (TETRA_RX_FLAG_AACH_RM3014): the byte behind its 30 type-1 bits (tetra_aach.h)
+constexpr int kAachDistByte = 30;
+struct ColSrc {                   // a column of one kind and parity on the device: element j at base + j * stride
+    const uint8_t* base;
+    size_t stride;
 };
 
 }  // namespace tetra_rx_impl
@@ -109,3 +123,58 @@ struct tetra_rx {
     bool reset_pending = false;           // ... which the next process call waits for on ITS stream
     bool owned = false;                   // inside a wideband handle (tetra_wbrx_rx): that handle restarts its channels, the entry point refuses
 };
+
+// A row column (COL_*) of this handle: every fetch, device view and delivery asks here whether it exists and where it lies.
+namespace row_col TETRA_HIDDEN {
+
+// TETRA_ERR_UNSUPPORTED without the column's flag, for a kind the handle does not decode, or for one that does not carry the column
+inline int status(const tetra_rx* h, int col, int kind) {
+    const bool flag = col == COL_BITERR ? h->biterr : col == COL_RANK ? h->list : h->aach_rm;
+    return flag && (h->kinds & (1 << kind)) && rx_out::kind_has(kind, col) ? TETRA_OK : TETRA_ERR_UNSUPPORTED;
+}
+// ... the same for a delivery or a bound, which name no kind: some kind of the handle has it
+inline int status(const tetra_rx* h, int col) {
+    for (int k = 0; k < TETRA_RX_N_KINDS; k++)
+        if (status(h, col, k) == TETRA_OK) return TETRA_OK;
+    return TETRA_ERR_UNSUPPORTED;
+}
+// where it lies: counts and ranks in buffers of their own, the distance inside the kind's rows (base is null where status is not TETRA_OK)
+inline ColSrc src(const tetra_rx* h, int parity, int kind, int col) {
+    const KindBufs& r = h->res[parity][kind];
+    if (col == COL_BITERR) return { reinterpret_cast<const uint8_t*>(r.biterr.get()), sizeof(uint32_t) };
+    if (col == COL_RANK) return { reinterpret_cast<const uint8_t*>(r.rank.get()), sizeof(int32_t) };
+    return { status(h, col, kind) == TETRA_OK ? r.t2.get() + kAachDistByte : nullptr, (size_t)kKinds[kind].out_stride };
+}
+// the buffers of n > 0 rows that src names, for the columns this kind has (tetra_rx_create)
+inline bool alloc(const tetra_rx* h, KindBufs& r, int kind, size_t n) {
+    return (status(h, COL_BITERR, kind) != TETRA_OK || r.biterr.reserve(sizeof(uint32_t) * n) == hipSuccess) &&
+           (status(h, COL_RANK, kind) != TETRA_OK || r.rank.reserve(sizeof(int32_t) * n) == hipSuccess);
+}
+
+}  // namespace row_col
+
+// A per-channel table (TAB_*) of this handle, [C] elements of rx_out::chan_elem_bytes: the getters, the snapshot, the deliveries and
+// the reset of single channels ask here.
+namespace chan_tab TETRA_HIDDEN {
+
+// the chain's own tables, which it zeroes and copies itself; the other two are the synchroniser's, read through its getters
+inline bool own(int tab) { return tab == TAB_CELL || tab == TAB_LINK; }
+// *p = the live table on the device, or null where the handle has none: link figures without TETRA_RX_FLAG_BITERR, miss counters
+// before a tolerance was first set (TETRA_RX_FLAG_SYNC_TOLERANT sets one).  The miss counters stay when the handle returns to the
+// reference's rule; *counting (may be null) is false then, which is what a reset of channels keys on -- the snapshot keys on the table.
+inline int live(const tetra_rx* h, int tab, void** p, bool* counting = nullptr) {
+    retune_impl::BsyncTables t = { nullptr, nullptr, true };
+    if (!own(tab)) TETRA_TRY(retune_impl::bsync_tables(h->bs, &t));
+    *p = tab == TAB_CELL ? (void*)h->cell.get() : tab == TAB_LINK ? (void*)h->link.get() : tab == TAB_SYNC_STATE ? (void*)t.state : (void*)t.miss;
+    if (counting) *counting = tab != TAB_SYNC_MISSES || t.tolerant;
+    return TETRA_OK;
+}
+// whether a snapshot can be armed with it and a delivery can carry it: TETRA_ERR_UNSUPPORTED for a table the handle does not have
+inline int status(const tetra_rx* h, int tab) {
+    if (tab == TAB_LINK) return h->biterr ? TETRA_OK : TETRA_ERR_UNSUPPORTED;      // (asked before the table is allocated, too)
+    void* p = nullptr;
+    TETRA_TRY(live(h, tab, &p));
+    return p ? TETRA_OK : TETRA_ERR_UNSUPPORTED;
+}
+
+}  // namespace chan_tab

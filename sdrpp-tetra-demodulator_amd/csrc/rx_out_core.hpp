@@ -136,7 +136,9 @@ RXO_FN int row_elem_bytes(int col) { return col == 2 ? 1 : 4; }
 // the coded kinds have the first two columns, the AACH the third
 RXO_FN bool kind_has(int kind, int col) { return (col == 2) == (kind == TETRA_RX_KIND_BBK); }
 RXO_FN int chan_extra(int tab) { return TETRA_RX_OUT_EXT_CHAN_CELL << tab; }
-RXO_FN int chan_elem_bytes(int tab) { return tab == 0 ? 40 : tab == 1 ? 16 : tab == 2 ? 4 : 24; }
+RXO_FN int chan_elem_bytes(int tab) {
+    return (int)(tab == 0 ? sizeof(tetra_lmac_cell_state_t) : tab == 1 ? sizeof(tetra_bsync_state_t) : tab == 2 ? sizeof(int32_t) : sizeof(tetra_rx_link_t));
+}
 // A handle's snapshot of one call: the four tables one after the other, each 16-byte aligned, whatever the armed mask
 RXO_FN uint64_t snap_offset(int tab, int n_channels) {
     uint64_t off = 0;

@@ -25,7 +25,6 @@
 #include "demux_core.hpp"
 #include "hip_host.hpp"
 #include "retune_impl.hpp"
-#include "rx_snap_impl.hpp"
 
 namespace {
 
@@ -370,19 +369,11 @@ int retune_impl::bsync_view(tetra_bsync_t* h, retune::BsyncView* v) {
     v->carry = reinterpret_cast<uint32_t*>(h->d_carry.get()); v->carry_words = kBuf / 4;
     return TETRA_OK;
 }
-// ... and the miss counters of the tolerant lock, one word per channel (no words while the handle runs the reference's rule)
-int retune_impl::bsync_miss_view(tetra_bsync_t* h, retune::CellView* v) {
-    if (!h || !v) return TETRA_ERR_ARG;
-    v->cell = reinterpret_cast<uint32_t*>(h->d_miss.get()); v->cell_words = h->tolerant ? 1 : 0;
-    return TETRA_OK;
-}
-
-// ... and both tables where they are, for the receive chain's per-call snapshot (tetra_rx.hip)
-int rx_snap_impl::bsync_tables(tetra_bsync_t* h, const tetra_bsync_state_t** state, const int32_t** miss) {
-    if (!h || !state || !miss) return TETRA_ERR_ARG;
+// ... and the per-channel tables where they are, for the receive chain's description of them (rx_handle.hpp)
+int retune_impl::bsync_tables(tetra_bsync_t* h, BsyncTables* t) {
+    if (!h || !t) return TETRA_ERR_ARG;
     static_assert(sizeof(State) == sizeof(tetra_bsync_state_t), "state layout");
-    *state = reinterpret_cast<const tetra_bsync_state_t*>(h->d_state.get());
-    *miss = h->d_miss.get();
+    *t = { reinterpret_cast<tetra_bsync_state_t*>(h->d_state.get()), h->d_miss.get(), h->tolerant };
     return TETRA_OK;
 }
 

@@ -89,10 +89,17 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     retune::BsyncView bv;
     TETRA_TRY(retune_impl::demod_view(h->dem, &dv));
     TETRA_TRY(retune_impl::bsync_view(h->bs, &bv));
-    static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0, "reset in 32-bit words");
-    retune::CellView cv = { reinterpret_cast<uint32_t*>(h->cell.get()), (int32_t)(sizeof(tetra_lmac_cell_state_t) / 4) };
-    static_assert(sizeof(tetra_rx_link_t) % 4 == 0, "reset in 32-bit words");
-    const retune::CellView lv = { reinterpret_cast<uint32_t*>(h->link.get()), h->biterr ? (int32_t)(sizeof(tetra_rx_link_t) / 4) : 0 };
+    static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0 && sizeof(tetra_rx_link_t) % 4 == 0, "reset in 32-bit words");
+    // the chain's per-channel tables in 32-bit words per channel: no words where the handle has no such table, nor for miss counters
+    // that the rule in force does not count
+    retune::CellView tv[rx_out::kChanTables];
+    for (int t = 0; t < rx_out::kChanTables; ++t) {
+        void* p = nullptr;
+        bool counting = true;
+        TETRA_TRY(chan_tab::live(h, t, &p, &counting));
+        tv[t] = { static_cast<uint32_t*>(p), p && counting ? (int32_t)(rx_out::chan_elem_bytes(t) / 4) : 0 };
+    }
+    const retune::CellView &cv = tv[TAB_CELL], &lv = tv[TAB_LINK], &mv = tv[TAB_SYNC_MISSES];
     if (!h->ev_reset) HIP_TRY(h, hipEventCreateWithFlags(h->ev_reset.put(), hipEventDisableTiming));
     const int last = (int)((h->calls - 1) & 1);
     hipStream_t st = h->one_stream ? s : static_cast<hipStream_t>(h->tail);
@@ -112,8 +119,6 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     }
     hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
     HIP_TRY(h, hipGetLastError());
-    retune::CellView mv;
-    TETRA_TRY(retune_impl::bsync_miss_view(h->bs, &mv));
     if (mv.cell_words > 0) {
         hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, mv, d_channels, h->C);
         HIP_TRY(h, hipGetLastError());

@@ -34,7 +34,6 @@
 #include "lmac_impl.hpp"
 #include "rx_handle.hpp"
 #include "rx_out_core.hpp"
-#include "rx_snap_impl.hpp"
 #include "soft_core.hpp"
 
 namespace {
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(256) void k_rx_pack_type1(const uint8_t* __restrict
     reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(t2 + (size_t)j * in_stride)[u];
 }
 
-// byte `at` of the first n rows, packed (tetra_rx_fetch_aach_dist)
+// byte `at` of the first n rows, packed (fetch_col: a column that lies inside the rows)
 __global__ __launch_bounds__(256) void k_rx_pack_byte(const uint8_t* __restrict__ t2, int in_stride, int at, int n, uint8_t* __restrict__ out) {
     const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (j < n) out[j] = t2[(size_t)j * in_stride + at];
@@ -147,8 +146,10 @@ template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve
 
 int zero_results(tetra_rx* h) {
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->counts[b], 0, sizeof(int32_t) * TETRA_N_LISTS));
-    HIP_TRY(h, hipMemset(h->cell, 0, sizeof(tetra_lmac_cell_state_t) * (size_t)h->C));
-    if (h->biterr) HIP_TRY(h, hipMemset(h->link, 0, sizeof(tetra_rx_link_t) * (size_t)h->C));
+    for (int t = 0; t < rx_out::kChanTables; ++t) {      // the chain's own tables (tetra_bsync_reset clears the synchroniser's)
+        void* p = nullptr;
+        if (chan_tab::own(t) && chan_tab::live(h, t, &p) == TETRA_OK && p) HIP_TRY(h, hipMemset(p, 0, (size_t)rx_out::chan_elem_bytes(t) * (size_t)h->C));
+    }
     for (int b = 0; b < 2; b++) HIP_TRY(h, hipMemset(h->nbits[b], 0, sizeof(int32_t) * (size_t)h->C));
     if (h->soft) {      // fresh channels: previous symbol (1,1)/sqrt(2), bit count 0 (both parities: the next call reads either)
         const std::vector<float> prev((size_t)4 * h->C, tetra_soft::kFreshPrev);
@@ -243,15 +244,13 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     HIP_TRY(h, hipEventRecord(h->ev_stage[3], s));
     h->snap_taken[b] = 0;
     if (h->snap_mask) {      // behind the link figures and outside the stages' spans; in front of the tail's event, which a delivery waits for
-        const tetra_bsync_state_t* st = nullptr;
-        const int32_t* miss = nullptr;
-        TETRA_TRY(rx_snap_impl::bsync_tables(h->bs, &st, &miss));
-        const void* src[rx_out::kChanTables] = { h->cell.get(), st, miss, h->link.get() };
         SnapArgs a = {};
         int most = 0;
         for (int t = 0; t < rx_out::kChanTables; ++t) {
-            if (!(h->snap_mask & rx_out::chan_extra(t)) || !src[t]) continue;
-            a.tab[t].src = static_cast<const uint32_t*>(src[t]);
+            void* src = nullptr;
+            TETRA_TRY(chan_tab::live(h, t, &src));
+            if (!(h->snap_mask & rx_out::chan_extra(t)) || !src) continue;
+            a.tab[t].src = static_cast<const uint32_t*>(src);
             a.tab[t].dst = reinterpret_cast<uint32_t*>(h->snap[b].get() + rx_out::snap_offset(t, h->C));
             a.tab[t].words = rx_out::chan_elem_bytes(t) / 4 * h->C;
             most = a.tab[t].words > most ? a.tab[t].words : most;
@@ -295,6 +294,70 @@ int fetch_rows(tetra_rx* h, int which, int kind, bool wants, int capacity, int* 
 // the latest call's tail is done: what the getters of per-channel state wait for
 int latest_tail_done(tetra_rx* h) {
     if (h->calls > 0) HIP_TRY(h, hipEventSynchronize(h->ev_tail[(h->calls - 1) & 1]));
+    return TETRA_OK;
+}
+
+// Rows that are not contiguous on the device: pack(stage) launches the kernel that packs them on the fetch stream, then ONE copy (a strided
+// device-to-host copy of 10^5 narrow rows moves ~50 MB/s: 1.9 s for a second of 4096 channels' blocks, measured; this way the link's rate)
+template <class Pack> int fetch_packed(tetra_rx* h, void* out, size_t bytes, Pack pack) {
+    if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
+        (void)hipGetLastError();
+        return TETRA_ERR_NOMEM;
+    }
+    pack(h->fetch_stage.get());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->fetch_stage, bytes, hipMemcpyDeviceToHost, h->fetch_s));
+    HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
+    return TETRA_OK;
+}
+
+// The blocking fetch of one row column (COL_*; tetra_biterr.h, tetra_list.h, tetra_aach.h): a column with a buffer of its own is one
+// copy, one that lies inside the rows (a byte wide) goes through fetch_packed.
+int fetch_col(tetra_rx* h, int which, int kind, int col, void* out, int capacity, int* n_rows) {
+    if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
+    TETRA_TRY(row_col::status(h, col, kind));
+    return fetch_rows(h, which, kind, out != nullptr, capacity, n_rows, [&](const KindBufs&, int n) -> int {
+        const ColSrc c = row_col::src(h, parity_of(h, which), kind, col);
+        const size_t elem = (size_t)rx_out::row_elem_bytes(col);
+        if (c.stride == elem) {
+            HIP_TRY(h, hipMemcpy(out, c.base, elem * (size_t)n, hipMemcpyDeviceToHost));
+            return TETRA_OK;
+        }
+        return fetch_packed(h, out, (size_t)n, [&](uint8_t* stage) {
+            hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, c.base, (int)c.stride, 0, n, stage);
+        });
+    });
+}
+
+// ... and the same column where it is: *d_col [rows] beside tetra_rx_rows_device's rows, hip_stream made to wait for the call's tail
+template <class T> int col_device(tetra_rx* h, int which, int kind, int col, const T** d_col, void* hip_stream) {
+    if (!h || !d_col || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1) return TETRA_ERR_ARG;
+    TETRA_TRY(row_col::status(h, col, kind));
+    const int b = parity_of(h, which);
+    if (b < 0) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
+    *d_col = reinterpret_cast<const T*>(row_col::src(h, b, kind, col).base);
+    return TETRA_OK;
+}
+
+// The getter of one per-channel table (TAB_*): channels [first, first + count) behind the latest call's tail.  The chain's own tables
+// are copied from where they live; the synchroniser's are answered by its getters, which wait for the whole device and answer zeros
+// for miss counters that were never allocated.
+int get_chan(tetra_rx* h, int tab, int first, int count, void* out) {
+    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
+    if (chan_tab::own(tab)) TETRA_TRY(chan_tab::status(h, tab));
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    TETRA_TRY(latest_tail_done(h));
+    if (!count) return TETRA_OK;
+    if (tab == TAB_SYNC_STATE) return tetra_bsync_get_state(h->bs, first, count, static_cast<tetra_bsync_state_t*>(out));
+    if (tab == TAB_SYNC_MISSES) return tetra_bsync_get_misses(h->bs, first, count, static_cast<int32_t*>(out));
+    void* live = nullptr;
+    TETRA_TRY(chan_tab::live(h, tab, &live));
+    const size_t elem = (size_t)rx_out::chan_elem_bytes(tab);
+    HIP_TRY(h, hipMemcpy(out, static_cast<const uint8_t*>(live) + elem * (size_t)first, elem * (size_t)count, hipMemcpyDeviceToHost));
     return TETRA_OK;
 }
 
@@ -357,8 +420,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
         for (int k = 0; k < TETRA_RX_N_KINDS && ok; k++) {
             if (!(h->kinds & (1 << k))) continue;
             KindBufs& r = h->res[b][k];
-            ok = dalloc(r.t2, n * kKinds[k].out_stride) && dalloc(r.ok, n) && dalloc(r.blocks, n) &&
-                 (!h->biterr || k == TETRA_RX_KIND_BBK || dalloc(r.biterr, n)) && (!h->list || k == TETRA_RX_KIND_BBK || dalloc(r.rank, n));
+            ok = dalloc(r.t2, n * kKinds[k].out_stride) && dalloc(r.ok, n) && dalloc(r.blocks, n) && row_col::alloc(h.get(), r, k, n ? n : 1);
             r.row_frame = h->lists[b] + (size_t)kKinds[k].list * n;
             r.n_rows = h->counts[b] + kKinds[k].list;
         }
@@ -367,7 +429,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
          dalloc(h->chan_first, (size_t)TETRA_N_LISTS * h->C) && dalloc(h->index_work, (size_t)TETRA_N_LISTS * ((n + 255) / 256)) &&
          dalloc(h->row_scramb, n) && dalloc(h->row_time_rx, n) && dalloc(h->row_time, n) && dalloc(h->cell, (size_t)h->C);
     for (auto& e : h->ev_stage) ok = ok && hipEventCreate(e.put()) == hipSuccess;
-    if (ok && h->biterr) ok = dalloc(h->link, (size_t)h->C);
+    if (ok && chan_tab::status(h.get(), TAB_LINK) == TETRA_OK) ok = dalloc(h->link, (size_t)h->C);
     if (ok && h->soft) {
         h->soft_R = tetra_soft::ring_size(h->stride);
         ok = dalloc(h->sym, (size_t)h->C * h->stride) && dalloc(h->soft_ring, (size_t)h->C * h->soft_R) && dalloc(h->soft_prev, (size_t)4 * h->C) &&
@@ -496,19 +558,11 @@ int tetra_rx_fetch(tetra_rx_t* h, int which, int kind, tetra_rx_block_t* blocks,
         if (blocks) HIP_TRY(h, hipMemcpy(blocks, r.blocks, sizeof(tetra_rx_block_t) * (size_t)n, hipMemcpyDeviceToHost));
         if (type1) {
             const int nb = kKinds[kind].type1_bits;
-            if (type1_stride == nb) {
-                // contiguous rows at the caller's: pack on the device, ONE copy (a strided device-to-host copy of 10^5 narrow rows moves
-                // ~50 MB/s: 1.9 s for a second of 4096 channels' blocks, measured; this way the link's rate)
-                if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return TETRA_ERR_NOMEM;
-                }
+            if (type1_stride == nb) {      // contiguous rows at the caller's
                 const long long units = (long long)n * (nb >> 1);
-                hipLaunchKernelGGL(k_rx_pack_type1, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[kind].out_stride, nb, n,
-                                   h->fetch_stage);
-                HIP_TRY(h, hipGetLastError());
-                HIP_TRY(h, hipMemcpyAsync(type1, h->fetch_stage, (size_t)n * nb, hipMemcpyDeviceToHost, h->fetch_s));
-                HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
+                TETRA_TRY(fetch_packed(h, type1, (size_t)n * nb, [&](uint8_t* stage) {
+                    hipLaunchKernelGGL(k_rx_pack_type1, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2.get(), kKinds[kind].out_stride, nb, n, stage);
+                }));
             } else {
                 HIP_TRY(h, hipMemcpy2D(type1, (size_t)type1_stride, r.t2, (size_t)kKinds[kind].out_stride, (size_t)nb, (size_t)n, hipMemcpyDeviceToHost));
             }
@@ -518,50 +572,21 @@ int tetra_rx_fetch(tetra_rx_t* h, int which, int kind, tetra_rx_block_t* blocks,
 }
 
 int tetra_rx_fetch_aach_dist(tetra_rx_t* h, int which, uint8_t* dist, int capacity, int* n_rows) {
-    if (!h || !n_rows || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
-    if (!h->aach_rm || !(h->kinds & (1 << TETRA_RX_KIND_BBK))) return TETRA_ERR_UNSUPPORTED;
-    return fetch_rows(h, which, TETRA_RX_KIND_BBK, dist != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
-        // packed on the device, one copy (see tetra_rx_fetch)
-        if (h->fetch_stage.reserve((size_t)h->rows * 268) != hipSuccess) {
-            (void)hipGetLastError();
-            return TETRA_ERR_NOMEM;
-        }
-        hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2, kKinds[TETRA_RX_KIND_BBK].out_stride, 30, n,
-                           h->fetch_stage);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(dist, h->fetch_stage, (size_t)n, hipMemcpyDeviceToHost, h->fetch_s));
-        HIP_TRY(h, hipStreamSynchronize(h->fetch_s));
-        return TETRA_OK;
-    });
+    return fetch_col(h, which, TETRA_RX_KIND_BBK, COL_AACH_DIST, dist, capacity, n_rows);
 }
 
 // the chain's share of tetra_biterr.h
-static bool counts_kind(const tetra_rx* h, int kind) { return h->biterr && kind != TETRA_RX_KIND_BBK && (h->kinds & (1 << kind)); }
-
 int tetra_rx_fetch_biterr(tetra_rx_t* h, int which, int kind, uint32_t* out, int capacity, int* n_rows) {
-    if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
-    if (!counts_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    return fetch_rows(h, which, kind, out != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
-        HIP_TRY(h, hipMemcpy(out, r.biterr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-        return TETRA_OK;
-    });
+    return fetch_col(h, which, kind, COL_BITERR, out, capacity, n_rows);
 }
 
 int tetra_rx_biterr_device(tetra_rx_t* h, int which, int kind, const uint32_t** d_biterr, void* hip_stream) {
-    if (!h || !d_biterr || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1) return TETRA_ERR_ARG;
-    if (!counts_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_ERR_ARG;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
-    *d_biterr = h->res[b][kind].biterr;
-    return TETRA_OK;
+    return col_device(h, which, kind, COL_BITERR, d_biterr, hip_stream);
 }
 
-// the chain's share of tetra_list.h
-static bool ranks_kind(const tetra_rx* h, int kind) { return h->list && kind != TETRA_RX_KIND_BBK && (h->kinds & (1 << kind)); }
+int tetra_rx_get_link(tetra_rx_t* h, int first, int count, tetra_rx_link_t* out) { return get_chan(h, TAB_LINK, first, count, out); }
 
+// the chain's share of tetra_list.h
 int tetra_rx_set_list_candidates(tetra_rx_t* h, int max_candidates) {
     if (!h) return TETRA_ERR_ARG;
     if (!h->list) return TETRA_ERR_UNSUPPORTED;
@@ -571,34 +596,11 @@ int tetra_rx_set_list_candidates(tetra_rx_t* h, int max_candidates) {
 }
 
 int tetra_rx_fetch_list_rank(tetra_rx_t* h, int which, int kind, int32_t* out, int capacity, int* n_rows) {
-    if (!h || !n_rows || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
-    if (!ranks_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    return fetch_rows(h, which, kind, out != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
-        HIP_TRY(h, hipMemcpy(out, r.rank, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-        return TETRA_OK;
-    });
+    return fetch_col(h, which, kind, COL_RANK, out, capacity, n_rows);
 }
 
 int tetra_rx_list_rank_device(tetra_rx_t* h, int which, int kind, const int32_t** d_rank, void* hip_stream) {
-    if (!h || !d_rank || kind < 0 || kind >= TETRA_RX_N_KINDS || which < 0 || which > 1) return TETRA_ERR_ARG;
-    if (!ranks_kind(h, kind)) return TETRA_ERR_UNSUPPORTED;
-    const int b = parity_of(h, which);
-    if (b < 0) return TETRA_ERR_ARG;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_tail[b], 0));
-    *d_rank = h->res[b][kind].rank;
-    return TETRA_OK;
-}
-
-int tetra_rx_get_link(tetra_rx_t* h, int first, int count, tetra_rx_link_t* out) {
-    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
-    if (!h->biterr) return TETRA_ERR_UNSUPPORTED;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    TETRA_TRY(latest_tail_done(h));
-    if (count) HIP_TRY(h, hipMemcpy(out, h->link + first, sizeof(tetra_rx_link_t) * (size_t)count, hipMemcpyDeviceToHost));
-    return TETRA_OK;
+    return col_device(h, which, kind, COL_RANK, d_rank, hip_stream);
 }
 
 int tetra_rx_rows_device(tetra_rx_t* h, int which, int kind, const uint8_t** d_type2, int* type2_stride, const tetra_rx_block_t** d_blocks,
@@ -618,22 +620,9 @@ int tetra_rx_rows_device(tetra_rx_t* h, int which, int kind, const uint8_t** d_t
     return TETRA_OK;
 }
 
-int tetra_rx_get_cell(tetra_rx_t* h, int first, int count, tetra_lmac_cell_state_t* out) {
-    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    TETRA_TRY(latest_tail_done(h));
-    if (count) HIP_TRY(h, hipMemcpy(out, h->cell + first, sizeof(tetra_lmac_cell_state_t) * (size_t)count, hipMemcpyDeviceToHost));
-    return TETRA_OK;
-}
+int tetra_rx_get_cell(tetra_rx_t* h, int first, int count, tetra_lmac_cell_state_t* out) { return get_chan(h, TAB_CELL, first, count, out); }
 
-int tetra_rx_get_sync_state(tetra_rx_t* h, int first, int count, tetra_bsync_state_t* out) {
-    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    TETRA_TRY(latest_tail_done(h));
-    return count ? tetra_bsync_get_state(h->bs, first, count, out) : TETRA_OK;
-}
+int tetra_rx_get_sync_state(tetra_rx_t* h, int first, int count, tetra_bsync_state_t* out) { return get_chan(h, TAB_SYNC_STATE, first, count, out); }
 
 // the chain's share of tetra_sync_tol.h
 int tetra_rx_set_sync_tolerance(tetra_rx_t* h, const tetra_bsync_tolerance_t* tol) {
@@ -644,13 +633,7 @@ int tetra_rx_set_sync_tolerance(tetra_rx_t* h, const tetra_bsync_tolerance_t* to
     return tetra_bsync_set_tolerance(h->bs, tol);
 }
 
-int tetra_rx_get_sync_misses(tetra_rx_t* h, int first, int count, int32_t* out) {
-    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
-    DeviceGuard g(h->device);
-    if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    TETRA_TRY(latest_tail_done(h));
-    return count ? tetra_bsync_get_misses(h->bs, first, count, out) : TETRA_OK;
-}
+int tetra_rx_get_sync_misses(tetra_rx_t* h, int first, int count, int32_t* out) { return get_chan(h, TAB_SYNC_MISSES, first, count, out); }
 
 int tetra_rx_bits_device(tetra_rx_t* h, int which, const uint8_t** d_bits, int* bits_stride, const int32_t** d_n_bits, void* hip_stream) {
     if (!h || which < 0 || which > 1) return TETRA_ERR_ARG;

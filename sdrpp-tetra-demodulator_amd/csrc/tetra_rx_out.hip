@@ -20,7 +20,6 @@
 #include "compact_core.hpp"
 #include "rx_handle.hpp"
 #include "rx_out_core.hpp"
-#include "rx_snap_impl.hpp"
 
 namespace {
 
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(256) void k_out_write(const OutArgs a, const int32_
 //   k_out_ext_write   per kind and tile: the kept rows' columns, ranked like the rows, staged in LDS and stored as contiguous runs
 //                     (rx_out::ext_stage / ext_store); one more row of workgroups copies the call's per-channel snapshot
 
-struct ExtKind {                      // one selected kind's columns of one parity (the distance is byte 30 of its type-2 row)
+struct ExtKind {                      // one selected kind's columns of one parity (the distance lies in its type-2 rows: kAachDistByte)
     const uint32_t* biterr;
     const int32_t* rank;
 };
@@ -275,7 +274,7 @@ __global__ __launch_bounds__(kTile) void k_out_ext_write(const OutArgs a, const 
     const uint64_t b0 = col[0] + 4ull * (uint64_t)base, b1 = col[1] + 4ull * (uint64_t)base, b2 = col[2] + (uint64_t)base;
     if (col[0]) rx_out::ext_stage<4>(scol[0], b0, reinterpret_cast<const uint8_t*>(x.k[s].biterr), 4, t0, src, cnt, t, kTile);
     if (col[1]) rx_out::ext_stage<4>(scol[1], b1, reinterpret_cast<const uint8_t*>(x.k[s].rank), 4, t0, src, cnt, t, kTile);
-    if (col[2]) rx_out::ext_stage<1>(scol[2], b2, k.t2 + 30, (size_t)k.out_stride, t0, src, cnt, t, kTile);
+    if (col[2]) rx_out::ext_stage<1>(scol[2], b2, k.t2 + kAachDistByte, (size_t)k.out_stride, t0, src, cnt, t, kTile);
     __syncthreads();
     if (col[0]) rx_out::ext_store<4>(dst, b0, scol[0], cnt, t, kTile);
     if (col[1]) rx_out::ext_store<4>(dst, b1, scol[1], cnt, t, kTile);
@@ -310,15 +309,10 @@ int ring_slot(const tetra_rx* h, int64_t call) {
 
 // TETRA_ERR_UNSUPPORTED for an extra whose flag the handle was created without, as its blocking fetch answers
 int extras_supported(const tetra_rx* h, int extras) {
-    if ((extras & (TETRA_RX_OUT_EXT_ROW_BITERR | TETRA_RX_OUT_EXT_CHAN_LINK)) && !h->biterr) return TETRA_ERR_UNSUPPORTED;
-    if ((extras & TETRA_RX_OUT_EXT_ROW_LIST_RANK) && !h->list) return TETRA_ERR_UNSUPPORTED;
-    if ((extras & TETRA_RX_OUT_EXT_ROW_AACH_DIST) && (!h->aach_rm || !(h->kinds & (1 << TETRA_RX_KIND_BBK)))) return TETRA_ERR_UNSUPPORTED;
-    if (extras & TETRA_RX_OUT_EXT_CHAN_SYNC_MISSES) {      // the counters exist once a tolerance was set (TETRA_RX_FLAG_SYNC_TOLERANT sets one)
-        const tetra_bsync_state_t* st = nullptr;
-        const int32_t* miss = nullptr;
-        TETRA_TRY(rx_snap_impl::bsync_tables(h->bs, &st, &miss));
-        if (!miss) return TETRA_ERR_UNSUPPORTED;
-    }
+    for (int c = 0; c < rx_out::kRowCols; c++)
+        if (extras & rx_out::row_extra(c)) TETRA_TRY(row_col::status(h, c));
+    for (int t = 0; t < rx_out::kChanTables; t++)
+        if (extras & rx_out::chan_extra(t)) TETRA_TRY(chan_tab::status(h, t));
     return TETRA_OK;
 }
 
@@ -359,7 +353,7 @@ int tetra_rx_out_bound_ext(tetra_rx_t* h, int kinds, int flags, int extras, uint
         for (int k = 0; k < TETRA_RX_N_KINDS; k++)
             if ((sel & (1 << k)) && (kKinds[k].list == list || kKinds[k].list == TETRA_LIST_ANY))
                 for (int c = 0; c < rx_out::kRowCols; c++)
-                    if ((extras & rx_out::row_extra(c)) && rx_out::kind_has(k, c)) b += (uint64_t)h->rows * (uint64_t)rx_out::row_elem_bytes(c);
+                    if ((extras & rx_out::row_extra(c)) && row_col::status(h, c, k) == TETRA_OK) b += (uint64_t)h->rows * (uint64_t)rx_out::row_elem_bytes(c);
         worst = b > worst ? b : worst;
     }
     for (int t = 0; t < rx_out::kChanTables; t++)
@@ -473,8 +467,8 @@ int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst,
         }
         xl = reinterpret_cast<ExtLayout*>(h->out_ext_layout.get());
         for (int i = 0; i < a.nsel; i++) {
-            x.k[i].biterr = h->res[b][a.k[i].kind].biterr;
-            x.k[i].rank = h->res[b][a.k[i].kind].rank;
+            x.k[i].biterr = reinterpret_cast<const uint32_t*>(row_col::src(h, b, a.k[i].kind, COL_BITERR).base);
+            x.k[i].rank = reinterpret_cast<const int32_t*>(row_col::src(h, b, a.k[i].kind, COL_RANK).base);
         }
         x.snap = h->snap[b];
         x.extras = extras;

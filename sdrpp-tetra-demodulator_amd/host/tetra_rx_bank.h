@@ -30,12 +30,32 @@ public:
         std::vector<uint32_t> biterr;     // errors | compared << 16 (coded kinds)
         std::vector<int32_t> rank;        // list-decoding rank (coded kinds)
         std::vector<uint8_t> aachDist;    // Reed-Muller distance (BBK)
+        void clear() { info.clear(); type1.clear(); biterr.clear(); rank.clear(); aachDist.clear(); }
+        // o's rows and columns behind these, its channels numbered from channelOffset on (a shard's share of a bank's)
+        void append(const Blocks& o, int channelOffset) {
+            bitsPerBlock = o.bitsPerBlock;
+            const size_t at = info.size();
+            info.insert(info.end(), o.info.begin(), o.info.end());
+            for (size_t i = at; i < info.size(); i++) info[i].channel += channelOffset;
+            type1.insert(type1.end(), o.type1.begin(), o.type1.end());
+            biterr.insert(biterr.end(), o.biterr.begin(), o.biterr.end());
+            rank.insert(rank.end(), o.rank.begin(), o.rank.end());
+            aachDist.insert(aachDist.end(), o.aachDist.begin(), o.aachDist.end());
+        }
     };
     struct Channels {                     // the per-channel state of the delivered call; empty where not delivered
         std::vector<tetra_lmac_cell_state_t> cell;
         std::vector<tetra_bsync_state_t> sync;
         std::vector<int32_t> misses;
         std::vector<tetra_rx_link_t> link;
+        void clear() { cell.clear(); sync.clear(); misses.clear(); link.clear(); }
+        // o's channels behind these (tables carry no channel numbers: the offset is their position)
+        void append(const Channels& o, int /*channelOffset*/) {
+            cell.insert(cell.end(), o.cell.begin(), o.cell.end());
+            sync.insert(sync.end(), o.sync.begin(), o.sync.end());
+            misses.insert(misses.end(), o.misses.begin(), o.misses.end());
+            link.insert(link.end(), o.link.begin(), o.link.end());
+        }
     };
 
     TetraRxBank() {}
@@ -125,11 +145,7 @@ public:
         const OutBuf& o = *ob;
         for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
             Blocks& b = out[k];
-            b.info.clear();
-            b.type1.clear();
-            b.biterr.clear();
-            b.rank.clear();
-            b.aachDist.clear();
+            b.clear();
             b.bitsPerBlock = tetra_rx_type1_bits(k);
             const tetra_rx_block_t* blk = nullptr;
             const uint8_t* bits = nullptr;
@@ -157,7 +173,7 @@ public:
             if (rc != TETRA_OK) return rc;
         }
         if (chans) {
-            *chans = Channels();
+            chans->clear();
             if (o.extras) {
                 const tetra_lmac_cell_state_t* cell = nullptr;
                 const tetra_bsync_state_t* sync = nullptr;
@@ -177,47 +193,23 @@ public:
     // ext/tetra_rx_out_ext.h: the channel extras (TETRA_RX_OUT_EXT_CHAN_*) every tail from the next call on snapshots for deliver()
     int setSnapshot(int chanExtras) { return tetra_rx_out_set_snapshot(h_, chanExtras); }
     // tcd / t_phy_state of every channel (tetra_lower_mac.c:116, tetra_burst_sync.c:34 -- one per channel here)
-    int cells(std::vector<tetra_lmac_cell_state_t>& out) {
-        out.resize((size_t)channels_);
-        return tetra_rx_get_cell(h_, 0, channels_, out.data());
-    }
+    int cells(std::vector<tetra_lmac_cell_state_t>& out) { return table(tetra_rx_get_cell, out); }
     // TETRA_RX_FLAG_BITERR (tetra_biterr.h): errors | compared << 16 of a coded kind's rows, in fetch()'s order -- an estimate of the
     // channel's bit errors that is meaningful for rows with a good CRC ...
-    int fetchBitErrors(int kind, std::vector<uint32_t>& out, int which = 0) {
-        int n = 0;
-        const int rc = tetra_rx_fetch_biterr(h_, which, kind, nullptr, 0, &n);
-        if (rc != TETRA_OK) return rc;
-        out.resize((size_t)n);
-        return n ? tetra_rx_fetch_biterr(h_, which, kind, out.data(), n, &n) : TETRA_OK;
-    }
+    int fetchBitErrors(int kind, std::vector<uint32_t>& out, int which = 0) { return column(tetra_rx_fetch_biterr, kind, out, which); }
     // ... and every channel's link figures since the last reset
-    int links(std::vector<tetra_rx_link_t>& out) {
-        out.resize((size_t)channels_);
-        return tetra_rx_get_link(h_, 0, channels_, out.data());
-    }
+    int links(std::vector<tetra_rx_link_t>& out) { return table(tetra_rx_get_link, out); }
     // TETRA_RX_FLAG_LIST (tetra_list.h): how many next-best paths (1..8) a CRC-failed block is decoded along from the next call on ...
     int setListCandidates(int maxCandidates) { return tetra_rx_set_list_candidates(h_, maxCandidates); }
     // ... and the rank of a coded kind's rows, in fetch()'s order: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k,
     // -1 = failed and not rescued
-    int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) {
-        int n = 0;
-        const int rc = tetra_rx_fetch_list_rank(h_, which, kind, nullptr, 0, &n);
-        if (rc != TETRA_OK) return rc;
-        out.resize((size_t)n);
-        return n ? tetra_rx_fetch_list_rank(h_, which, kind, out.data(), n, &n) : TETRA_OK;
-    }
-    int syncStates(std::vector<tetra_bsync_state_t>& out) {
-        out.resize((size_t)channels_);
-        return tetra_rx_get_sync_state(h_, 0, channels_, out.data());
-    }
+    int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) { return column(tetra_rx_fetch_list_rank, kind, out, which); }
+    int syncStates(std::vector<tetra_bsync_state_t>& out) { return table(tetra_rx_get_sync_state, out); }
     // The synchroniser's tolerant lock (ext/tetra_sync_tol.h; TETRA_RX_FLAG_SYNC_TOLERANT creates the chain with {3, 5, 16}): tol = null
     // returns to the reference's rule.  Between process calls; waits for the tail in flight.
     int setSyncTolerance(const tetra_bsync_tolerance_t* tol) { return tetra_rx_set_sync_tolerance(h_, tol); }
     // every channel's count of consecutive LOCKED frames without a training sequence
-    int syncMisses(std::vector<int32_t>& out) {
-        out.resize((size_t)channels_);
-        return tetra_rx_get_sync_misses(h_, 0, channels_, out.data());
-    }
+    int syncMisses(std::vector<int32_t>& out) { return table(tetra_rx_get_sync_misses, out); }
     // the PI4DQPSK setters of the demodulators inside (tetra_demod_set_param ids); waits for work in flight first
     int setParam(int paramId, double value) {
         const int rc = tetra_rx_wait(h_);
@@ -228,6 +220,19 @@ public:
     tetra_rx_t* handle() { return h_; }
 
 private:
+    // a row column's blocking fetch (fetch(h, which, kind, out, capacity, &n_rows)): asked for the row count, sized, asked for the rows
+    template <class T, class Fetch> int column(Fetch fetch, int kind, std::vector<T>& out, int which) {
+        int n = 0;
+        const int rc = fetch(h_, which, kind, nullptr, 0, &n);
+        if (rc != TETRA_OK) return rc;
+        out.resize((size_t)n);
+        return n ? fetch(h_, which, kind, out.data(), n, &n) : TETRA_OK;
+    }
+    // a per-channel getter (get(h, first, count, out)) for every channel
+    template <class T, class Get> int table(Get get, std::vector<T>& out) {
+        out.resize((size_t)channels_);
+        return get(h_, 0, channels_, out.data());
+    }
     struct OutBuf {
         void* buf = nullptr;
         uint64_t bytes = 0;
@@ -281,33 +286,22 @@ public:
     }
     // Host samples, channel major [n_channels][count] complex64: every shard copies its rows in and enqueues its chain.
     int process(int count, const float* iq) {
-        for (auto& s : shards_) {
-            const int rc = s->bank.process(count, iq + (size_t)2 * (size_t)s->first * (size_t)count);
-            if (rc != TETRA_OK) return rc;
-        }
-        return TETRA_OK;
+        return each([&](Shard& s) { return s.bank.process(count, iq + (size_t)2 * (size_t)s.first * (size_t)count); });
     }
     int wait() {
         int first = TETRA_OK;
         for (auto& s : shards_) { const int rc = s->bank.wait(); if (first == TETRA_OK) first = rc; }
         return first;
     }
-    int reset() {
-        for (auto& s : shards_) { const int rc = s->bank.reset(); if (rc != TETRA_OK) return rc; }
-        return TETRA_OK;
-    }
+    int reset() { return each([](Shard& s) { return s.bank.reset(); }); }
     int fetch(int kind, TetraRxBank::Blocks& out, int which = 0) {
-        out.info.clear(); out.type1.clear();
+        out.clear();
         TetraRxBank::Blocks part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.fetch(kind, part, which);
-            if (rc != TETRA_OK) return rc;
-            out.bitsPerBlock = part.bitsPerBlock;
-            for (auto& b : part.info) b.channel += s->first;
-            out.info.insert(out.info.end(), part.info.begin(), part.info.end());
-            out.type1.insert(out.type1.end(), part.type1.begin(), part.type1.end());
-        }
-        return TETRA_OK;
+        return each([&](Shard& s) {
+            const int rc = s.bank.fetch(kind, part, which);
+            if (rc == TETRA_OK) out.append(part, s.first);
+            return rc;
+        });
     }
     // Every kind of `kinds` (0 = all configured) in one step per shard: every shard's delivery is enqueued first, then each is
     // collected, so the GPUs' transfers run side by side.  out[kind] as fetch() returns it (bank channel numbers, (channel, frame)
@@ -316,8 +310,8 @@ public:
     // tables in the bank's channel order; the channel extras need setSnapshot() armed when that call was processed.
     int fetchAll(TetraRxBank::Blocks out[TETRA_RX_N_KINDS], int which = 0, int kinds = 0, int flags = 0, int extras = 0,
                  TetraRxBank::Channels* chans = nullptr) {
-        for (int k = 0; k < TETRA_RX_N_KINDS; k++) { out[k] = TetraRxBank::Blocks(); out[k].bitsPerBlock = tetra_rx_type1_bits(k); }
-        if (chans) *chans = TetraRxBank::Channels();
+        for (int k = 0; k < TETRA_RX_N_KINDS; k++) { out[k].clear(); out[k].bitsPerBlock = tetra_rx_type1_bits(k); }
+        if (chans) chans->clear();
         std::vector<int64_t> calls(shards_.size(), -1);
         for (size_t s = 0; s < shards_.size(); s++) {
             const int rc = shards_[s]->bank.deliver(&calls[s], which, kinds, flags, extras);
@@ -328,92 +322,24 @@ public:
         for (size_t s = 0; s < shards_.size(); s++) {
             const int rc = shards_[s]->bank.collect(calls[s], part, chans ? &cpart : nullptr);
             if (rc != TETRA_OK) return rc;
-            for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
-                for (auto& b : part[k].info) b.channel += shards_[s]->first;
-                out[k].info.insert(out[k].info.end(), part[k].info.begin(), part[k].info.end());
-                out[k].type1.insert(out[k].type1.end(), part[k].type1.begin(), part[k].type1.end());
-                out[k].biterr.insert(out[k].biterr.end(), part[k].biterr.begin(), part[k].biterr.end());
-                out[k].rank.insert(out[k].rank.end(), part[k].rank.begin(), part[k].rank.end());
-                out[k].aachDist.insert(out[k].aachDist.end(), part[k].aachDist.begin(), part[k].aachDist.end());
-            }
-            if (chans) {
-                chans->cell.insert(chans->cell.end(), cpart.cell.begin(), cpart.cell.end());
-                chans->sync.insert(chans->sync.end(), cpart.sync.begin(), cpart.sync.end());
-                chans->misses.insert(chans->misses.end(), cpart.misses.begin(), cpart.misses.end());
-                chans->link.insert(chans->link.end(), cpart.link.begin(), cpart.link.end());
-            }
+            for (int k = 0; k < TETRA_RX_N_KINDS; k++) out[k].append(part[k], shards_[s]->first);
+            if (chans) chans->append(cpart, shards_[s]->first);
         }
         return TETRA_OK;
     }
-    int setSnapshot(int chanExtras) {
-        for (auto& s : shards_) { const int rc = s->bank.setSnapshot(chanExtras); if (rc != TETRA_OK) return rc; }
-        return TETRA_OK;
-    }
-    int syncStates(std::vector<tetra_bsync_state_t>& out) {
-        out.clear();
-        std::vector<tetra_bsync_state_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.syncStates(part);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
-    }
-    int syncMisses(std::vector<int32_t>& out) {
-        out.clear();
-        std::vector<int32_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.syncMisses(part);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
-    }
-    int cells(std::vector<tetra_lmac_cell_state_t>& out) {
-        out.clear();
-        std::vector<tetra_lmac_cell_state_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.cells(part);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
-    }
+    int setSnapshot(int chanExtras) { return each([&](Shard& s) { return s.bank.setSnapshot(chanExtras); }); }
+    int syncStates(std::vector<tetra_bsync_state_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.syncStates(part); }); }
+    int syncMisses(std::vector<int32_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.syncMisses(part); }); }
+    int cells(std::vector<tetra_lmac_cell_state_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.cells(part); }); }
     // the shards' counts and link figures one after the other: fetch()'s row order, cells()'s channel order
     int fetchBitErrors(int kind, std::vector<uint32_t>& out, int which = 0) {
-        out.clear();
-        std::vector<uint32_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.fetchBitErrors(kind, part, which);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
+        return gather(out, [&](TetraRxBank& b, auto& part) { return b.fetchBitErrors(kind, part, which); });
     }
-    int setListCandidates(int maxCandidates) {
-        for (auto& s : shards_) { const int rc = s->bank.setListCandidates(maxCandidates); if (rc != TETRA_OK) return rc; }
-        return TETRA_OK;
-    }
+    int setListCandidates(int maxCandidates) { return each([&](Shard& s) { return s.bank.setListCandidates(maxCandidates); }); }
     int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) {
-        out.clear();
-        std::vector<int32_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.fetchListRank(kind, part, which);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
+        return gather(out, [&](TetraRxBank& b, auto& part) { return b.fetchListRank(kind, part, which); });
     }
-    int links(std::vector<tetra_rx_link_t>& out) {
-        out.clear();
-        std::vector<tetra_rx_link_t> part;
-        for (auto& s : shards_) {
-            const int rc = s->bank.links(part);
-            if (rc != TETRA_OK) return rc;
-            out.insert(out.end(), part.begin(), part.end());
-        }
-        return TETRA_OK;
-    }
+    int links(std::vector<tetra_rx_link_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.links(part); }); }
     int channels() const { return channels_; }
     int shards() const { return (int)shards_.size(); }
     void shardInfo(int shard, int& first, int& count) const { first = shards_[(size_t)shard]->first; count = shards_[(size_t)shard]->count; }
@@ -424,6 +350,24 @@ private:
         TetraRxBank bank;
         int first = 0, count = 0;
     };
+    // tell every shard in turn: the first failure ends the round and is the result
+    template <class Tell> int each(Tell tell) {
+        for (auto& s : shards_) {
+            const int rc = tell(*s);
+            if (rc != TETRA_OK) return rc;
+        }
+        return TETRA_OK;
+    }
+    // ask every shard (ask(bank, part)) and put the answers one after the other: the shards' rows, or their channels, in the bank's order
+    template <class T, class Ask> int gather(std::vector<T>& out, Ask ask) {
+        out.clear();
+        std::vector<T> part;
+        return each([&](Shard& s) {
+            const int rc = ask(s.bank, part);
+            if (rc == TETRA_OK) out.insert(out.end(), part.begin(), part.end());
+            return rc;
+        });
+    }
     std::vector<std::unique_ptr<Shard>> shards_;
     int channels_ = 0;
 };

@@ -211,8 +211,12 @@ class RxChain:
 
     def biterr_device(self, kind, which=0, stream=None):
         """tetra_rx_biterr_device -> the raw device address of the kind's counts (uint32 per row of rows_device)."""
+        return self._column_device(self._lib.tetra_rx_biterr_device, kind, which, stream)
+
+    def _column_device(self, fn, kind, which, stream):
+        """A device view of the form fn(h, which, kind, &d_column, stream) -> the raw device address."""
         d = C.c_void_p()
-        call(self._lib.tetra_rx_biterr_device, self._h, which, kind, C.byref(d), stream_ptr(stream))
+        call(fn, self._h, which, kind, C.byref(d), stream_ptr(stream))
         return d.value
 
     def set_list_candidates(self, max_candidates):
@@ -227,29 +231,27 @@ class RxChain:
 
     def list_rank_device(self, kind, which=0, stream=None):
         """tetra_rx_list_rank_device -> the raw device address of the kind's ranks (int32 per row of rows_device)."""
-        d = C.c_void_p()
-        call(self._lib.tetra_rx_list_rank_device, self._h, which, kind, C.byref(d), stream_ptr(stream))
-        return d.value
+        return self._column_device(self._lib.tetra_rx_list_rank_device, kind, which, stream)
 
     def links(self, first=0, count=None):
         """tetra_rx_get_link: per channel a dict bits / bit_errors (summed over the coded blocks with a good CRC since the last reset)
         and blocks / blocks_crc_bad (every coded block)."""
-        count = self.n_channels - first if count is None else count
-        arr = (Link * max(count, 1))()
-        call(self._lib.tetra_rx_get_link, self._h, first, count, arr)
-        return [dict(bits=int(a.bits), bit_errors=int(a.bit_errors), blocks=int(a.blocks), blocks_crc_bad=int(a.blocks_crc_bad)) for a in arr[:count]]
+        return [dict(bits=int(a.bits), bit_errors=int(a.bit_errors), blocks=int(a.blocks), blocks_crc_bad=int(a.blocks_crc_bad))
+                for a in self._channel_table(self._lib.tetra_rx_get_link, Link, first, count)]
 
-    def cells(self, first=0, count=None):
+    def _channel_table(self, fn, elem, first, count):
+        """A per-channel getter of the form fn(h, first, count, out) -> [elem] of channels first .. first + count - 1 (None: to the last)."""
         count = self.n_channels - first if count is None else count
-        arr = (CellState * max(count, 1))()
-        call(self._lib.tetra_rx_get_cell, self._h, first, count, arr)
+        arr = (elem * max(count, 1))()
+        call(fn, self._h, int(first), int(count), arr)
         return [arr[i] for i in range(count)]
 
+    def cells(self, first=0, count=None):
+        return self._channel_table(self._lib.tetra_rx_get_cell, CellState, first, count)
+
     def sync_states(self, first=0, count=None):
-        count = self.n_channels - first if count is None else count
-        arr = (BsyncState * max(count, 1))()
-        call(self._lib.tetra_rx_get_sync_state, self._h, first, count, arr)
-        return [(arr[i].state, arr[i].bits_in_buf, arr[i].bitbuf_start_bitnum, arr[i].next_frame_start_bitnum) for i in range(count)]
+        return [(a.state, a.bits_in_buf, a.bitbuf_start_bitnum, a.next_frame_start_bitnum)
+                for a in self._channel_table(self._lib.tetra_rx_get_sync_state, BsyncState, first, count)]
 
     def set_sync_tolerance(self, tol):
         """tetra_rx_set_sync_tolerance: (tol_norm, tol_sync, max_miss) for the synchroniser's tolerant lock from the next call on, None =
@@ -258,10 +260,7 @@ class RxChain:
 
     def sync_misses(self, first=0, count=None):
         """tetra_rx_get_sync_misses: int32 [count], per channel the consecutive LOCKED frames without a training sequence."""
-        count = self.n_channels - first if count is None else count
-        out = np.zeros(max(count, 1), np.int32)
-        call(self._lib.tetra_rx_get_sync_misses, self._h, int(first), int(count), ptr(out))
-        return out[:count]
+        return np.array(self._channel_table(self._lib.tetra_rx_get_sync_misses, C.c_int32, first, count), np.int32)
 
     def stage_ms(self):
         ms = (C.c_float * 4)()
@@ -299,11 +298,12 @@ class RxChain:
             if getattr(self, "_pool", None) is None:
                 # sized once, for every extra this handle can ever deliver (the miss counters may be enabled later: counted by hand)
                 nb, can = C.c_uint64(0), 0
-                for bit in (EXT_ROW_BITERR, EXT_ROW_LIST_RANK, EXT_ROW_AACH_DIST, EXT_CHAN_CELL, EXT_CHAN_SYNC_STATE, EXT_CHAN_LINK):
-                    if self._lib.tetra_rx_out_bound_ext(self._h, 0, 0, bit, C.byref(nb)) == 0:
+                for _, bit, _ in ROW_COLUMNS + CHAN_TABLES:
+                    if bit != EXT_CHAN_SYNC_MISSES and self._lib.tetra_rx_out_bound_ext(self._h, 0, 0, bit, C.byref(nb)) == 0:
                         can |= bit
                 call(self._lib.tetra_rx_out_bound_ext, self._h, 0, 0, can, C.byref(nb))
-                self._pool, self._pool_next = [HostBuffer(nb.value + 16 + 4 * self.n_channels) for _ in range(2)], 0
+                misses = next(dtype for _, bit, dtype in CHAN_TABLES if bit == EXT_CHAN_SYNC_MISSES)
+                self._pool, self._pool_next = [HostBuffer(nb.value + 16 + misses.itemsize * self.n_channels) for _ in range(2)], 0
             buf = self._pool[self._pool_next]
             self._pool_next ^= 1
         if isinstance(buf, HostBuffer):
@@ -358,17 +358,20 @@ OUT_EXT_MAGIC = 0x58585254
 CELL_DTYPE = np.dtype([(n, "<u4") for n, _ in CellState._fields_])
 SYNC_STATE_DTYPE = np.dtype([("state", "<i4"), ("bits_in_buf", "<u4"), ("bitbuf_start_bitnum", "<u4"), ("next_frame_start_bitnum", "<u4")])
 LINK_DTYPE = np.dtype([("bits", "<u8"), ("bit_errors", "<u8"), ("blocks", "<u4"), ("blocks_crc_bad", "<u4")])
+# The extension block's row columns and per-channel tables, in its order, as (name, EXT_* bit, element dtype): what view_delivery_ext
+# returns under these names, what DeliveryRows documents, and what RxChain.deliver sizes its pool for.
+ROW_COLUMNS = (("biterr", EXT_ROW_BITERR, np.dtype("<u4")), ("rank", EXT_ROW_LIST_RANK, np.dtype("<i4")), ("aach_dist", EXT_ROW_AACH_DIST, np.dtype("u1")))
+CHAN_TABLES = (("cell", EXT_CHAN_CELL, CELL_DTYPE), ("sync_state", EXT_CHAN_SYNC_STATE, SYNC_STATE_DTYPE),
+               ("sync_misses", EXT_CHAN_SYNC_MISSES, np.dtype("<i4")), ("link", EXT_CHAN_LINK, LINK_DTYPE))
 
 
 class OutExtKind(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("biterr_offset", C.c_uint64), ("rank_offset", C.c_uint64),
-                ("aach_dist_offset", C.c_uint64)]
+    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32)] + [(name + "_offset", C.c_uint64) for name, _, _ in ROW_COLUMNS]
 
 
 class OutExtHeader(C.Structure):
     _fields_ = [("magic", C.c_uint32), ("extras", C.c_int32), ("call", C.c_int64), ("n_channels", C.c_int32), ("n_kinds", C.c_int32),
-                ("bytes", C.c_uint64), ("cell_offset", C.c_uint64), ("sync_state_offset", C.c_uint64), ("sync_misses_offset", C.c_uint64),
-                ("link_offset", C.c_uint64), ("kinds", OutExtKind * N_KINDS)]
+                ("bytes", C.c_uint64)] + [(name + "_offset", C.c_uint64) for name, _, _ in CHAN_TABLES] + [("kinds", OutExtKind * N_KINDS)]
 
 
 class HostBuffer:
@@ -395,14 +398,16 @@ class HostBuffer:
             pass
 
 
+def _open_delivery(buf, nbytes):
+    """-> (library, uint8 array, its bytes, its address, classic header) of a delivery in host memory"""
+    arr = buf.array if isinstance(buf, HostBuffer) else buf
+    return _lib(), arr, arr.nbytes if nbytes is None else int(nbytes), arr.ctypes.data, OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+
+
 def view_delivery(buf, nbytes=None):
     """A completed delivery in host memory (numpy uint8 array, or HostBuffer) -> (header, {kind: (blocks, type1)}): numpy views into
     the buffer; type1 is [n][row_bytes] (packed rows when the header's flags say so).  A header status other than TETRA_OK raises."""
-    L = _lib()
-    arr = buf.array if isinstance(buf, HostBuffer) else buf
-    nbytes = arr.nbytes if nbytes is None else int(nbytes)
-    base = arr.ctypes.data
-    hd = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+    L, arr, nbytes, base, hd = _open_delivery(buf, nbytes)
     out = {}
     for i in range(max(0, min(hd.n_kinds, N_KINDS))):
         k = hd.kinds[i].kind
@@ -415,15 +420,11 @@ def view_delivery(buf, nbytes=None):
 
 
 def view_delivery_ext(buf, nbytes=None):
-    """The extension block of a completed extended delivery in host memory -> (extension header, {kind: {"biterr": uint32 [n] or None,
-    "rank": int32 [n] or None, "aach_dist": uint8 [n] or None}}, {"cell": CELL_DTYPE [C], "sync_state": SYNC_STATE_DTYPE [C],
-    "sync_misses": int32 [C], "link": LINK_DTYPE [C]} with None for a table the delivery does not hold): numpy views into the buffer
-    (tetra_rx_out_view_ext / tetra_rx_out_view_channels).  A buffer without an extension block raises (TETRA_ERR_UNSUPPORTED)."""
-    L = _lib()
-    arr = buf.array if isinstance(buf, HostBuffer) else buf
-    nbytes = arr.nbytes if nbytes is None else int(nbytes)
-    base = arr.ctypes.data
-    hd = OutHeader.from_buffer_copy(arr[:C.sizeof(OutHeader)].tobytes())
+    """The extension block of a completed extended delivery in host memory -> (extension header, {kind: {column: [n] or None}} for the
+    columns of ROW_COLUMNS, {table: [C] or None} for the tables of CHAN_TABLES, each with the dtype given there and None where the
+    delivery does not hold it): numpy views into the buffer (tetra_rx_out_view_ext / tetra_rx_out_view_channels).  A buffer without an
+    extension block raises (TETRA_ERR_UNSUPPORTED)."""
+    L, arr, nbytes, base, hd = _open_delivery(buf, nbytes)
 
     def at(p, n, dtype):
         if not p.value:
@@ -434,20 +435,20 @@ def view_delivery_ext(buf, nbytes=None):
     cols = {}
     for i in range(max(0, min(hd.n_kinds, N_KINDS))):
         k = hd.kinds[i].kind
-        pe, pr, pd, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-        call(L.tetra_rx_out_view_ext, base, nbytes, k, C.byref(pe), C.byref(pr), C.byref(pd), C.byref(n))
-        cols[k] = dict(biterr=at(pe, n.value, np.dtype("<u4")), rank=at(pr, n.value, np.dtype("<i4")), aach_dist=at(pd, n.value, np.dtype("u1")))
-    pc, ps, pm, pl, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    call(L.tetra_rx_out_view_channels, base, nbytes, C.byref(pc), C.byref(ps), C.byref(pm), C.byref(pl), C.byref(nc))
-    chans = dict(cell=at(pc, nc.value, CELL_DTYPE), sync_state=at(ps, nc.value, SYNC_STATE_DTYPE), sync_misses=at(pm, nc.value, np.dtype("<i4")),
-                 link=at(pl, nc.value, LINK_DTYPE))
+        ps, n = [C.c_void_p() for _ in ROW_COLUMNS], C.c_int(0)
+        call(L.tetra_rx_out_view_ext, base, nbytes, k, *[C.byref(p) for p in ps], C.byref(n))
+        cols[k] = {name: at(p, n.value, dtype) for (name, _, dtype), p in zip(ROW_COLUMNS, ps)}
+    ps, nc = [C.c_void_p() for _ in CHAN_TABLES], C.c_int(0)
+    call(L.tetra_rx_out_view_channels, base, nbytes, *[C.byref(p) for p in ps], C.byref(nc))
+    chans = {name: at(p, nc.value, dtype) for (name, _, dtype), p in zip(CHAN_TABLES, ps)}
     o = (int(hd.bytes) + 15) // 16 * 16
     return OutExtHeader.from_buffer_copy(arr[o: o + C.sizeof(OutExtHeader)].tobytes()), cols, chans
 
 
 class DeliveryRows(dict):
-    """What Delivery.wait() returns: {kind: (blocks, type1)}, and for an extended delivery .columns = {kind: {"biterr", "rank",
-    "aach_dist"}} and .channels = {"cell", "sync_state", "sync_misses", "link"} (view_delivery_ext); both None otherwise."""
+    __doc__ = ("""What Delivery.wait() returns: {kind: (blocks, type1)}, and for an extended delivery .columns = {kind: {%s}} and
+    .channels = {%s} (view_delivery_ext); both None otherwise.""" %
+               tuple(", ".join('"%s"' % name for name, _, _ in t) for t in (ROW_COLUMNS, CHAN_TABLES)))
     columns = None
     channels = None
 
