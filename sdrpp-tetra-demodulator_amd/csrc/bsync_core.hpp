@@ -29,6 +29,10 @@
 // errors there (tolerant_frame_eval) and falls back to UNLOCKED only behind max_miss consecutive frames without a candidate
 // (first_unlock).  Only the sync bitmap is needed then.
 //
+// Hand-over (include/ext/tetra_handover.h; opt-in, a departure from the reference): a fourth state, kAssist, in which the channel looks
+// for a training sequence only around the frame start it inherited from a donor; its fields (Assist) live beside State.  A third policy,
+// AssistLock, wraps the handle's rule and adds that state to walk(); RefLock and TolLock compile walk() without it.
+//
 // One walk over the events, walk(), serves both: the rule is a small policy object (RefLock, TolLock) that says what a LOCKED call
 // reports and how a literal call in UNLOCKED is answered; run() and run_tolerant() bind walk() to their rule.  Steps 1 and 4 of the kernel -- packing the stream, expanding the listed
 // frames, writing the carried buffer back -- are lane code here too (stage_thread, write_thread), so the host build runs the kernel's text.
@@ -52,6 +56,7 @@ constexpr int kBuf = 4096;
 constexpr int kTs = 510;            // TETRA_BITS_PER_TS
 constexpr int kLook = 64;           // zero bits kept past the end of the stream for window reads
 enum { kUnlocked = 0, kKnowFstart = 1, kLocked = 2 };                   // enum rx_state, tetra_burst_sync.h:6-10
+constexpr int kAssist = 3;          // ... and the hand-over's state beside them (include/ext/tetra_handover.h): not the reference's
 enum { kNorm1 = 0, kNorm2 = 1, kNorm3 = 2, kSync = 3, kExt = 4 };       // enum tetra_train_seq, tetra_burst.h:26-32
 
 struct State {                      // struct tetra_rx_state without its bitbuf (kept separately, one byte per bit)
@@ -268,6 +273,7 @@ struct FrameEval { int reported; bool unlocks; };
 // The reference's rule (tetra_burst_sync.c:105-150) on the three bitmaps and their union.  On a buffer of exactly one frame it is a
 // pure function of the bitmaps: frames in LOCKED steady state can be evaluated side by side, one per lane (walk()'s `batch`).
 struct RefLock {
+    static constexpr bool kAssists = false;
     const uint32_t *m_sync, *m_n1, *m_n2, *m_any;
     template <class First> BS_MFN FrameEval locked(const uint32_t* s, int bx, int n, First first) const {
         int offs = 0;
@@ -297,6 +303,7 @@ BS_FN FrameEval locked_frame_eval(const uint32_t* s, const uint32_t* m_sync, con
 // to call.  A batch() evaluates its frames with tolerant_frame_eval, applies first_unlock to them with the same counter and leaves it
 // as locked() does.  Only the sync bitmap is read.
 struct TolLock {
+    static constexpr bool kAssists = false;
     Tolerance tol;
     int& misses;
     template <class First> BS_MFN FrameEval locked(const uint32_t* s, int bx, int, First) {
@@ -318,6 +325,48 @@ struct TolLock {
         else a = lim > a1 ? lim : a1;
         return rc;
     }
+};
+
+// ---- hand-over (include/ext/tetra_handover.h; opt-in, a departure from the reference) ------------------------------------------------------
+// A channel that inherited its frame timing from a donor is in the state kAssist: it knows where its next frame should start (`expect`, an
+// absolute bit number) and looks for a training sequence only there, `window` bits either side, once per slot period, for at most
+// `slots_left` periods.  The fields live beside State, one Assist per channel; its first three words are tetra_handover_status_t.
+enum { kHoNone = 0, kHoPending = 1, kHoLocked = 2, kHoExpired = 3, kHoRefused = 4 };       // TETRA_HANDOVER_*
+struct Assist {
+    int32_t status;                 // kHo*
+    int32_t waited;                 // slot periods ASSIST has advanced
+    int32_t offset;                 // found frame start - expected frame start, in bits (once locked)
+    uint32_t expect;                // absolute bit number of the expected frame start
+    int32_t window;                 // W: 0..127
+    int32_t slots_left;
+    int32_t result;                 // for the apply kernel, which clears it: 1 + waited on the lock, -1 on expiry, 0 nothing
+    int32_t reserved;
+};
+constexpr int kAssistWords = (int)(sizeof(Assist) / 4);
+constexpr int kWindowMax = 127, kAssistSlotsMax = 255;
+
+// a frame that starts at x carries the sync sequence exactly at 214, or normal sequence 1 or 2 exactly at 244
+BS_FN bool assist_match(const uint32_t* s, int x) {
+    const uint32_t n = window(s, x + 244, 22);
+    return n == kHeadN || n == kHeadP || (window(s, x + 214, 22) == kHeadY && window(s, x + 236, 16) == kTailY);
+}
+// The candidates ex + d in the order d = 0, +1, -1, ..., +w, -w, none in front of the buffer's start bx: the first that matches, or -1.
+// All of [ex - w, ex + w + 510) lies in the stream.
+BS_FN int assist_find(const uint32_t* s, int bx, int ex, int w) {
+    for (int i = 0; i <= 2 * w; ++i) {
+        const int d = (i & 1) ? (i + 1) / 2 : -(i / 2);
+        if (ex + d >= bx && assist_match(s, ex + d)) return ex + d;
+    }
+    return -1;
+}
+// The third policy of walk(): the handle's own lock rule (RefLock, TolLock) for everything LOCKED and UNLOCKED, and the channel's Assist
+// for the state kAssist.
+template <class Inner> struct AssistLock {
+    static constexpr bool kAssists = true;
+    Inner& inner;
+    Assist& as;
+    template <class First> BS_MFN FrameEval locked(const uint32_t* s, int bx, int n, First first) { return inner.locked(s, bx, n, first); }
+    BS_MFN int literal(const uint32_t* s, int bx1, int a1, int xe, int& offs, int& a) const { return inner.literal(s, bx1, a1, xe, offs, a); }
 };
 
 // Runs the state machine over the new bits under the rule `lock`.  emit(f, bx, type, bitnum) is called for the f-th consumed frame
@@ -346,6 +395,39 @@ BS_FN int walk(State& st, const uint32_t* s, const uint32_t* m_sync, int n_new, 
     };
 
     while (a < xe) {
+        if constexpr (Lock::kAssists) {
+            // kAssist: nothing happens until the call that has fed expect + W + 510 bits; that call tries the window.  A match moves the
+            // buffer's start to the frame's and is LOCKED at once, the matched frame consumed in the same call like KNOW_FSTART's; a miss
+            // moves on by one slot period and drops what lies in front of the next window; the last miss is UNLOCKED on what is buffered.
+            if (state == kAssist) {
+                Assist& as = lock.as;
+                const int ex = x0 + (int)(int32_t)(as.expect - abs0);
+                const int at = ex + as.window + kTs;
+                if (at > xe) { a = xe; break; }
+                a = at > a ? at : a;
+                const int sx = assist_find(s, bx, ex, as.window);
+                if (sx >= 0) {
+                    bx = sx;
+                    nfs = abs_of(bx) + (uint32_t)kTs;
+                    state = kLocked;
+                    as.status = kHoLocked;
+                    as.offset = sx - ex;
+                    as.result = 1 + as.waited;
+                    locked_call();
+                } else {
+                    as.expect += (uint32_t)kTs;
+                    as.waited += 1;
+                    as.slots_left -= 1;
+                    bx = (ex + kTs - as.window > bx) ? ex + kTs - as.window : bx;
+                    if (as.slots_left <= 0) {
+                        state = kUnlocked;
+                        as.status = kHoExpired;
+                        as.result = -1;
+                    }
+                }
+                continue;
+            }
+        }
         if (state == kUnlocked) {
             const int a1 = (a + 1 > bx + 2 * kTs) ? a + 1 : bx + 2 * kTs;
             if (a1 > xe) { a = xe; break; }

@@ -19,12 +19,17 @@ TETRA_HIDDEN int bsync_view(tetra_bsync_t* h, retune::BsyncView* out);
 // ... and its per-channel tables on the device, [n_channels] each.  The miss counters exist from the first switch to the tolerant rule
 // (ext/tetra_sync_tol.h) on and stay when the handle returns to the reference's rule: `miss` says whether they exist, `tolerant`
 // whether they count.
+// `assist`: the hand-over's fields (bsync_core::Assist; ext/tetra_handover.h), null until the handle's first hand-over.
 struct BsyncTables {
     tetra_bsync_state_t* state;
     int32_t* miss;
     bool tolerant;
+    void* assist;
 };
 TETRA_HIDDEN int bsync_tables(tetra_bsync_t* h, BsyncTables* out);
+// ... the hand-over's fields, allocated and zeroed on the first call (which waits for the device, once); from then on the handle
+// launches its ASSIST-capable kernels
+TETRA_HIDDEN int bsync_assist(tetra_bsync_t* h, void** out);
 // tetra_resamp.hip: a handle that runs all its channels in place (16-byte lane units) becomes one that picks columns (8-byte units,
 // what TETRA_RESAMP_FLAG_NARROW_UNITS gives at create).  Same floats; the delay line's layout does not depend on the unit width.
 TETRA_HIDDEN int resamp_narrow_units(tetra_resamp_t* h);

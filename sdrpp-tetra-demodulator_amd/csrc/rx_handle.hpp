@@ -6,6 +6,7 @@
 
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_rx.h"
+#include "bsync_core.hpp"
 #include "hip_host.hpp"
 #include "retune_impl.hpp"
 #include "retune_list.hpp"
@@ -46,6 +47,9 @@ struct KindBufs {                 // one parity's results of one kind
 // of them and where it lies is stated once, in row_col and chan_tab behind the handle below.
 enum { COL_BITERR, COL_RANK, COL_AACH_DIST };
 enum { TAB_CELL, TAB_SYNC_STATE, TAB_SYNC_MISSES, TAB_LINK };
+// ... and one more per-channel table behind rx_out's four, which no delivery or snapshot carries: the hand-over's fields
+// (bsync_core::Assist, ext/tetra_handover.h), the synchroniser's like the two above
+constexpr int TAB_HANDOVER = rx_out::kChanTables, kChanTablesAll = rx_out::kChanTables + 1;
 // the Reed-Muller distance of a BBK row (TETRA_RX_FLAG_AACH_RM3014): the byte behind its 30 type-1 bits (tetra_aach.h)
 constexpr int kAachDistByte = 30;
 struct ColSrc {                   // a column of one kind and parity on the device: element j at base + j * stride
@@ -159,13 +163,16 @@ namespace chan_tab TETRA_HIDDEN {
 
 // the chain's own tables, which it zeroes and copies itself; the other two are the synchroniser's, read through its getters
 inline bool own(int tab) { return tab == TAB_CELL || tab == TAB_LINK; }
+// a table's element size: rx_out's for its four
+inline int elem_bytes(int tab) { return tab == TAB_HANDOVER ? (int)sizeof(bsync_core::Assist) : rx_out::chan_elem_bytes(tab); }
 // *p = the live table on the device, or null where the handle has none: link figures without TETRA_RX_FLAG_BITERR, miss counters
-// before a tolerance was first set (TETRA_RX_FLAG_SYNC_TOLERANT sets one).  The miss counters stay when the handle returns to the
+// before a tolerance was first set (TETRA_RX_FLAG_SYNC_TOLERANT sets one), the hand-over's fields before the first hand-over.  The miss counters stay when the handle returns to the
 // reference's rule; *counting (may be null) is false then, which is what a reset of channels keys on -- the snapshot keys on the table.
 inline int live(const tetra_rx* h, int tab, void** p, bool* counting = nullptr) {
-    retune_impl::BsyncTables t = { nullptr, nullptr, true };
+    retune_impl::BsyncTables t = { nullptr, nullptr, true, nullptr };
     if (!own(tab)) TETRA_TRY(retune_impl::bsync_tables(h->bs, &t));
-    *p = tab == TAB_CELL ? (void*)h->cell.get() : tab == TAB_LINK ? (void*)h->link.get() : tab == TAB_SYNC_STATE ? (void*)t.state : (void*)t.miss;
+    *p = tab == TAB_CELL ? (void*)h->cell.get() : tab == TAB_LINK ? (void*)h->link.get() : tab == TAB_SYNC_STATE ? (void*)t.state
+       : tab == TAB_SYNC_MISSES ? (void*)t.miss : t.assist;
     if (counting) *counting = tab != TAB_SYNC_MISSES || t.tolerant;
     return TETRA_OK;
 }

@@ -15,8 +15,12 @@
 //      buffer and the state.
 // Steps 1 and 4 and the walk are lane code in bsync_core.hpp, which the host emulation runs too.
 // Byte work: every input byte is read from HBM once, every output byte written once.
+// k_burst_sync_assist / k_burst_sync_tol_assist: the same body with the hand-over's state ASSIST beside the rule (bsync_core.hpp:
+// AssistLock; include/ext/tetra_handover.h), launched instead of the two above once a handle has handed over.
 // k_burst_demux: one thread per output dword; a gather with the offsets of tetra_burst_rx_cb().
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #include "../../include/ext/tetra_sync_tol.h"
 #include "../../include/tetra_burst_sync.h"
@@ -102,11 +106,13 @@ struct TolRule {
 // One workgroup of four wavefronts per channel (steps 1 .. 4 of the head of this file).
 // PACKED: the consumed frames leave as 16 words of 32 bits (first bit = most significant; word 15 holds bits 480 .. 509 in its top 30
 // bits) instead of 512 bytes: an eighth of the bytes for the demultiplexer behind (tetra_bsync_process_packed_device).
-template <bool PACKED, class Rule>
+// ASSIST: the hand-over's state beside the rule's (include/ext/tetra_handover.h): the channel's Assist is loaded, walk() runs under
+// AssistLock around the rule's policy, and lane 0 stores it back.  The kernels of a handle that never handed over are compiled without.
+template <bool PACKED, class Rule, bool ASSIST = false>
 __device__ __forceinline__ void burst_sync_workgroup(const Rule rule, const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
                                                      int max_bits, int max_frames, State* __restrict__ states, uint8_t* __restrict__ carry,
                                                      uint8_t* __restrict__ frames, int* __restrict__ frame_type,
-                                                     uint32_t* __restrict__ frame_bitnum, int* __restrict__ n_frames) {
+                                                     uint32_t* __restrict__ frame_bitnum, int* __restrict__ n_frames, Assist* __restrict__ assist = nullptr) {
     extern __shared__ uint32_t lds[];
     const int words = stream_words(max_bits);
     uint32_t* s = lds;
@@ -150,10 +156,19 @@ __device__ __forceinline__ void burst_sync_workgroup(const Rule rule, const uint
             }
             return done;
         };
-        const int nrun = walk(st, s, maps, n_new, carry_x, [&](const uint32_t* m, int a, int b) { return first_wave(m, a, b, lane); },
-                              [&](int f, int bx, int type, uint32_t bitnum) {
-                                  if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
-                              }, batch, lock);
+        auto first = [&](const uint32_t* m, int a, int b) { return first_wave(m, a, b, lane); };
+        auto emit = [&](int f, int bx, int type, uint32_t bitnum) {
+            if (lane == 0 && f < max_frames) rec[f] = FrameRec{ bx, type, bitnum };
+        };
+        int nrun;
+        if constexpr (ASSIST) {
+            Assist as = assist[ch];
+            AssistLock<decltype(lock)> with_assist{ lock, as };
+            nrun = walk(st, s, maps, n_new, carry_x, first, emit, batch, with_assist);
+            if (lane == 0) assist[ch] = as;
+        } else {
+            nrun = walk(st, s, maps, n_new, carry_x, first, emit, batch, lock);
+        }
         if (lane == 0) {
             rule.store(ch, rule_state);
             sh_nframes = nrun < max_frames ? nrun : max_frames;
@@ -187,6 +202,22 @@ template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_syn
                                                        int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
                                                        int* __restrict__ n_frames, const Tolerance tol, int32_t* __restrict__ miss) {
     burst_sync_workgroup<PACKED>(TolRule{ tol, miss }, bits, bits_stride, n_bits, max_bits, max_frames, states, carry, frames, frame_type, frame_bitnum, n_frames);
+}
+
+// ... and the same two for a handle that has handed over (include/ext/tetra_handover.h): assist [C] beside the states
+template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync_assist(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
+                                                       int max_bits, int max_frames, State* __restrict__ states,
+                                                       uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
+                                                       int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
+                                                       int* __restrict__ n_frames, Assist* __restrict__ assist) {
+    burst_sync_workgroup<PACKED, RefRule, true>(RefRule{}, bits, bits_stride, n_bits, max_bits, max_frames, states, carry, frames, frame_type, frame_bitnum, n_frames, assist);
+}
+template <bool PACKED> __global__ __launch_bounds__(kThreadsBS) void k_burst_sync_tol_assist(const uint8_t* __restrict__ bits, int bits_stride, const int* __restrict__ n_bits,
+                                                       int max_bits, int max_frames, State* __restrict__ states,
+                                                       uint8_t* __restrict__ carry, uint8_t* __restrict__ frames,
+                                                       int* __restrict__ frame_type, uint32_t* __restrict__ frame_bitnum,
+                                                       int* __restrict__ n_frames, const Tolerance tol, int32_t* __restrict__ miss, Assist* __restrict__ assist) {
+    burst_sync_workgroup<PACKED, TolRule, true>(TolRule{ tol, miss }, bits, bits_stride, n_bits, max_bits, max_frames, states, carry, frames, frame_type, frame_bitnum, n_frames, assist);
 }
 
 using demux_core::Pieces;
@@ -283,6 +314,8 @@ struct tetra_bsync {
     bool tolerant = false;
     Tolerance tol = { 0, 0, 1 };
     DevMem<int32_t> d_miss;           // [C] consecutive LOCKED frames without a candidate (allocated by the first switch to the tolerant rule)
+    // the hand-over (include/ext/tetra_handover.h): with the fields, the ASSIST-capable kernels
+    DevMem<Assist> d_assist;          // [C] (allocated by the handle's first hand-over, retune_impl::bsync_assist)
 };
 
 extern "C" {
@@ -325,7 +358,8 @@ int tetra_bsync_reset(tetra_bsync_t* h) {
     if (!g.ok) return TETRA_ERR_HIP;
     if (hipMemset(h->d_state, 0, sizeof(State) * h->n_channels) != hipSuccess ||
         hipMemset(h->d_carry, 0, (size_t)kBuf * h->n_channels) != hipSuccess ||
-        (h->d_miss.get() && hipMemset(h->d_miss, 0, sizeof(int32_t) * h->n_channels) != hipSuccess))
+        (h->d_miss.get() && hipMemset(h->d_miss, 0, sizeof(int32_t) * h->n_channels) != hipSuccess) ||
+        (h->d_assist.get() && hipMemset(h->d_assist, 0, sizeof(Assist) * h->n_channels) != hipSuccess))
         return TETRA_ERR_HIP;
     return TETRA_OK;
 }
@@ -373,7 +407,24 @@ int retune_impl::bsync_view(tetra_bsync_t* h, retune::BsyncView* v) {
 int retune_impl::bsync_tables(tetra_bsync_t* h, BsyncTables* t) {
     if (!h || !t) return TETRA_ERR_ARG;
     static_assert(sizeof(State) == sizeof(tetra_bsync_state_t), "state layout");
-    *t = { reinterpret_cast<tetra_bsync_state_t*>(h->d_state.get()), h->d_miss.get(), h->tolerant };
+    *t = { reinterpret_cast<tetra_bsync_state_t*>(h->d_state.get()), h->d_miss.get(), h->tolerant, h->d_assist.get() };
+    return TETRA_OK;
+}
+
+// The hand-over's per-channel fields: allocated and zeroed by the first call (which waits for the device, once), and from then on the
+// handle launches the ASSIST-capable kernels.
+int retune_impl::bsync_assist(tetra_bsync_t* h, void** out) {
+    if (!h || !out) return TETRA_ERR_ARG;
+    if (!h->d_assist.get()) {
+        DevMem<Assist> mem;
+        if (mem.reserve(sizeof(Assist) * h->n_channels) != hipSuccess) return TETRA_ERR_NOMEM;
+        for (const void* k : { reinterpret_cast<const void*>(k_burst_sync_assist<false>), reinterpret_cast<const void*>(k_burst_sync_assist<true>),
+                               reinterpret_cast<const void*>(k_burst_sync_tol_assist<false>), reinterpret_cast<const void*>(k_burst_sync_tol_assist<true>) })
+            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess) return TETRA_ERR_HIP;
+        if (hipMemset(mem, 0, sizeof(Assist) * h->n_channels) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+        h->d_assist = std::move(mem);
+    }
+    *out = h->d_assist.get();
     return TETRA_OK;
 }
 
@@ -384,7 +435,15 @@ template <bool PACKED> int bsync_launch(tetra_bsync_t* h, const uint8_t* d_bits,
     if (bits_stride < 4) return TETRA_ERR_ARG;
     if (bits_stride < h->max_bits) return TETRA_ERR_SIZE;      // rows must be able to hold the max_bits the handle was sized for
     if ((bits_stride & 3) || ((uintptr_t)d_bits & 3) || ((uintptr_t)d_frames & 3)) return TETRA_ERR_ALIGN;
-    if (h->tolerant)
+    if (h->d_assist.get() && h->tolerant)
+        hipLaunchKernelGGL(k_burst_sync_tol_assist<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(TolRule::kMaps, h->max_bits, h->max_frames),
+                           static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
+                           h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames, h->tol, h->d_miss, h->d_assist);
+    else if (h->d_assist.get())
+        hipLaunchKernelGGL(k_burst_sync_assist<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(RefRule::kMaps, h->max_bits, h->max_frames),
+                           static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
+                           h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames, h->d_assist);
+    else if (h->tolerant)
         hipLaunchKernelGGL(k_burst_sync_tol<PACKED>, dim3(h->n_channels), dim3(kThreadsBS), lds_bytes(TolRule::kMaps, h->max_bits, h->max_frames),
                            static_cast<hipStream_t>(hip_stream), d_bits, bits_stride, d_n_bits, h->max_bits, h->max_frames, h->d_state,
                            h->d_carry, static_cast<uint8_t*>(d_frames), d_frame_type, d_frame_bitnum, d_n_frames, h->tol, h->d_miss);

@@ -12,11 +12,15 @@
 // the state readers, the call after next -- also waits for the reset.  Call k's results are not touched: they stay fetchable.
 //
 // The kernels are a launch of one 64-lane workgroup per listed channel (lane code: retune_core.hpp): not a hot path.
+// A reset with donors (include/ext/tetra_handover.h) is the same reset with one more kernel behind k_reset_tail on the tail stream,
+// k_handover_plant (lane code: handover_core.hpp), which reads the donors' state as the last tail left it.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
+#include "../../include/ext/tetra_handover.h"
 #include "../../include/tetra_retune.h"
+#include "handover_core.hpp"
 #include "hip_host.hpp"
 #include "resamp_handle.hpp"
 #include "retune_core.hpp"
@@ -54,6 +58,17 @@ __global__ __launch_bounds__(kLanes) void k_reset_miss(retune::CellView miss, co
     retune::reset_cell_channel(miss, c, threadIdx.x, kLanes);
 }
 
+// The hand-over's planting (include/ext/tetra_handover.h; lane code: handover_core.hpp), behind k_reset_tail and the reset of the listed
+// channels' Assist: a thread per entry, heirs[i] from donors[i] (-1: a plain restart).  The host has checked that no donor is an heir.
+__global__ __launch_bounds__(kLanes) void k_handover_plant(handover::View v, const int32_t* __restrict__ heirs, const int32_t* __restrict__ donors, int n,
+                                                           int n_channels, int32_t window, int32_t max_slots) {
+    const int i = (int)blockIdx.x * kLanes + (int)threadIdx.x;
+    if (i >= n) return;
+    const int c = heirs[i], d = donors[i];
+    if (c < 0 || c >= n_channels || d < 0 || d >= n_channels) return;
+    handover::plant_channel(v, c, d, window, max_slots);
+}
+
 // list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
 // history ring [hist][M] (a sibling of tetra_resamp.hip's k_pick_rows: same rows, one column each, out of the ring)
 __global__ __launch_bounds__(256) void k_retune_columns(const float* __restrict__ ring, int M, int hist, long long n_total, const int32_t* __restrict__ list,
@@ -82,9 +97,17 @@ bool distinct_in_range(const int32_t* v, int n, int limit) {
     return true;
 }
 
+// a hand-over's parameters, or the defaults; false: out of range
+bool handover_params(const tetra_handover_params_t* p, tetra_handover_params_t* out) {
+    *out = p ? *p : tetra_handover_params_t{ TETRA_HANDOVER_DEFAULT_WINDOW, TETRA_HANDOVER_DEFAULT_MAX_SLOTS };
+    return out->window >= 0 && out->window <= bsync_core::kWindowMax && out->max_slots >= 1 && out->max_slots <= bsync_core::kAssistSlotsMax;
+}
+
 // The chain's part, for n > 0 channels listed on the device at d_channels (uploaded on s).  The caller marks the list's readers:
 // s, and *tail_reader (the tail stream when the chain has one of its own, else null).
-int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader) {
+// d_donors (may be null: a plain reset): per listed channel its donor or -1, planted behind the reset with the parameters *p.
+int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader, const int32_t* d_donors = nullptr,
+                  const tetra_handover_params_t* p = nullptr) {
     retune::DemodView dv;
     retune::BsyncView bv;
     TETRA_TRY(retune_impl::demod_view(h->dem, &dv));
@@ -92,14 +115,14 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0 && sizeof(tetra_rx_link_t) % 4 == 0, "reset in 32-bit words");
     // the chain's per-channel tables in 32-bit words per channel: no words where the handle has no such table, nor for miss counters
     // that the rule in force does not count
-    retune::CellView tv[rx_out::kChanTables];
-    for (int t = 0; t < rx_out::kChanTables; ++t) {
-        void* p = nullptr;
+    retune::CellView tv[kChanTablesAll];
+    for (int t = 0; t < kChanTablesAll; ++t) {
+        void* at = nullptr;
         bool counting = true;
-        TETRA_TRY(chan_tab::live(h, t, &p, &counting));
-        tv[t] = { static_cast<uint32_t*>(p), p && counting ? (int32_t)(rx_out::chan_elem_bytes(t) / 4) : 0 };
+        TETRA_TRY(chan_tab::live(h, t, &at, &counting));
+        tv[t] = { static_cast<uint32_t*>(at), at && counting ? (int32_t)(chan_tab::elem_bytes(t) / 4) : 0 };
     }
-    const retune::CellView &cv = tv[TAB_CELL], &lv = tv[TAB_LINK], &mv = tv[TAB_SYNC_MISSES];
+    const retune::CellView &cv = tv[TAB_CELL], &lv = tv[TAB_LINK], &mv = tv[TAB_SYNC_MISSES], &av = tv[TAB_HANDOVER];
     if (!h->ev_reset) HIP_TRY(h, hipEventCreateWithFlags(h->ev_reset.put(), hipEventDisableTiming));
     const int last = (int)((h->calls - 1) & 1);
     hipStream_t st = h->one_stream ? s : static_cast<hipStream_t>(h->tail);
@@ -123,6 +146,19 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
         hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, mv, d_channels, h->C);
         HIP_TRY(h, hipGetLastError());
     }
+    if (av.cell_words > 0) {      // a handle that has handed over: the listed channels' hand-over fields, like the miss counters ...
+        hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, av, d_channels, h->C);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (d_donors) {      // ... and behind all of it the planting
+        retune::BsyncView bsv;
+        TETRA_TRY(retune_impl::bsync_view(h->bs, &bsv));
+        const handover::View hv = { reinterpret_cast<bsync_core::State*>(bsv.state), reinterpret_cast<bsync_core::Assist*>(av.cell),
+                                          reinterpret_cast<tetra_lmac::TrackState*>(cv.cell) };
+        hipLaunchKernelGGL(k_handover_plant, dim3((unsigned)((n + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, hv, d_channels, d_donors, n, h->C, p->window,
+                           p->max_slots);
+        HIP_TRY(h, hipGetLastError());
+    }
     if (h->one_stream) HIP_TRY(h, hipEventRecord(h->ev_reset, s));
     h->reset_pending = true;
     if (h->calls > 0) {      // who waits for the last call waits for the reset too
@@ -133,40 +169,46 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     return TETRA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int tetra_rx_reset_channels_device(tetra_rx_t* h, const int32_t* channels, int n, void* hip_stream) {
-    if (no_device()) return TETRA_ERR_NO_DEVICE;
-    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
-    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune restarts its slots
-    if (!distinct_in_range(channels, n, h->C)) return TETRA_ERR_ARG;
+// tetra_rx_reset_channels_device, and with donors [n] and checked parameters tetra_rx_handover_channels_device: the list travels as
+// [n channels] or [n channels | n donors]
+int reset_channels(tetra_rx* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p, void* hip_stream) {
     if (n == 0) return TETRA_OK;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    std::vector<int32_t> both;
+    void* fields = nullptr;      // the handle's first hand-over allocates them; from here on its tails run the ASSIST-capable kernels
+    if (donors) TETRA_TRY(retune_impl::bsync_assist(h->bs, &fields));
+    if (donors) {
+        both.assign(channels, channels + n);
+        both.insert(both.end(), donors, donors + n);
+    }
     int32_t* d_list = nullptr;
     hipError_t e = hipSuccess;
-    const int k = h->to_device.push(channels, n, h->C, s, &d_list, &e);
+    const int k = donors ? h->to_device.push(both.data(), 2 * n, 2 * h->C, s, &d_list, &e) : h->to_device.push(channels, n, h->C, s, &d_list, &e);
     if (k < 0) HIP_TRY(h, e);
     hipStream_t tail = nullptr;
-    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail));
+    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail, donors ? d_list + n : nullptr, p));
     HIP_TRY(h, h->to_device.done(k, 0, s));
     if (tail) HIP_TRY(h, h->to_device.done(k, 1, tail));
     return TETRA_OK;
 }
 
-int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
-    if (no_device()) return TETRA_ERR_NO_DEVICE;
+// The wideband receiver's retune: bins [S], and -- donors != null -- per slot a donor or -1, with checked parameters
+int wbrx_retune(tetra_wbrx* h, const int32_t* bins, const int32_t* donors, const tetra_handover_params_t* p, void* hip_stream) {
     if (!h || !bins) return TETRA_ERR_ARG;
     const int S = h->n_bins;
     if (!distinct_in_range(bins, S, h->M)) return TETRA_ERR_ARG;
-    std::vector<int32_t> list;               // [n slots | n bins] of the slots that move
+    std::vector<int32_t> list;               // [n slots | n bins] of the slots that move, and with donors [| n donors]
     for (int j = 0; j < S; j++)
         if (bins[j] != h->bins[(size_t)j]) list.push_back(j);
     const int n = (int)list.size();
     for (int i = 0; i < n; i++) list.push_back(bins[list[(size_t)i]]);
+    for (int i = 0; donors && i < n; i++) {      // a moving slot's donor: -1, or a slot whose bin stays
+        const int32_t d = donors[list[(size_t)i]];
+        if (d < -1 || d >= S || (d >= 0 && bins[d] != h->bins[(size_t)d])) return TETRA_ERR_ARG;
+        list.push_back(d);
+    }
     if (n == 0) {
         h->retunes++;
         return TETRA_OK;
@@ -176,11 +218,13 @@ int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     tetra_resamp* rs = h->rs;
     tetra_rx* rx = h->rx;
+    void* fields = nullptr;      // the chain's first hand-over allocates them (reset_channels)
+    if (donors) TETRA_TRY(retune_impl::bsync_assist(rx->bs, &fields));
     // chan_out's rows are in the ring and the delay line is the last call's once that call's work on its stream is through
     if (h->done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
     int32_t* d_list = nullptr;
     hipError_t e = hipSuccess;
-    const int k = h->to_device.push(list.data(), 2 * n, 2 * S, s, &d_list, &e);
+    const int k = h->to_device.push(list.data(), (int)list.size(), (donors ? 3 : 2) * S, s, &d_list, &e);
     if (k < 0) HIP_TRY(h, e);
     const int hist = rs->T - 1, cells = hist * n;      // (the delay line's layout does not depend on the resampler's lane-unit width)
     hipLaunchKernelGGL(k_retune_columns, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->ring.get(), h->M, hist, rs->n_total, d_list, n, rs->C,
@@ -198,7 +242,7 @@ int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
     h->retunes++;
     h->slots_changed += n;
     hipStream_t tail = nullptr;
-    int rc = reset_enqueue(rx, d_list, n, s, &tail);
+    int rc = reset_enqueue(rx, d_list, n, s, &tail, donors ? d_list + 2 * n : nullptr, p);
     hipError_t late = h->to_device.done(k, 0, s);
     if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
     if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
@@ -208,6 +252,44 @@ int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
         rc = TETRA_ERR_HIP;
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tetra_rx_reset_channels_device(tetra_rx_t* h, const int32_t* channels, int n, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
+    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune restarts its slots
+    if (!distinct_in_range(channels, n, h->C)) return TETRA_ERR_ARG;
+    return reset_channels(h, channels, nullptr, n, nullptr, hip_stream);
+}
+
+int tetra_rx_handover_channels_device(tetra_rx_t* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p,
+                                      void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || n < 0 || n > h->C || ((!channels || !donors) && n > 0)) return TETRA_ERR_ARG;
+    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune_from hands its slots over
+    tetra_handover_params_t prm;
+    if (!distinct_in_range(channels, n, h->C) || !handover_params(p, &prm)) return TETRA_ERR_ARG;
+    std::vector<char> heir((size_t)h->C, 0);
+    for (int i = 0; i < n; i++) heir[(size_t)channels[i]] = 1;
+    for (int i = 0; i < n; i++)
+        if (donors[i] < -1 || donors[i] >= h->C || (donors[i] >= 0 && heir[(size_t)donors[i]])) return TETRA_ERR_ARG;
+    return reset_channels(h, channels, donors, n, &prm, hip_stream);
+}
+
+int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    return wbrx_retune(h, bins, nullptr, nullptr, hip_stream);
+}
+
+int tetra_wbrx_retune_from(tetra_wbrx_t* h, const int32_t* bins, const int32_t* donors, const tetra_handover_params_t* p, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    tetra_handover_params_t prm;
+    if (!handover_params(p, &prm)) return TETRA_ERR_ARG;
+    return wbrx_retune(h, bins, donors, &prm, hip_stream);
 }
 
 int tetra_wbrx_retune_count(tetra_wbrx_t* h, int64_t* retunes, int64_t* slots_changed) {

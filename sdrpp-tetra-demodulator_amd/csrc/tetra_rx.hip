@@ -28,9 +28,11 @@
 
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
+#include "../../include/ext/tetra_handover.h"
 #include "../../include/ext/tetra_list.h"
 #include "../../include/ext/tetra_sync_tol.h"
 #include "../../include/tetra_rx.h"
+#include "handover_core.hpp"
 #include "lmac_impl.hpp"
 #include "rx_handle.hpp"
 #include "rx_out_core.hpp"
@@ -142,6 +144,14 @@ __global__ __launch_bounds__(256) void k_rx_snapshot(const SnapArgs a) {
         if (i < a.tab[t].words) a.tab[t].dst[i] = a.tab[t].src[i];
 }
 
+// The hand-over's apply step (include/ext/tetra_handover.h; lane code: handover_core.hpp) between the synchroniser and the tracker, a
+// thread per channel: the synchroniser's result word advances the channel's PHY time or zeroes its cell.  Only on a handle that has
+// ever handed over.
+__global__ __launch_bounds__(64) void k_handover_apply(handover::View v, int n_channels) {
+    const int c = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (c < n_channels) handover::apply_channel(v, c);
+}
+
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
 
 int zero_results(tetra_rx* h) {
@@ -166,6 +176,13 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
     TETRA_TRY(tetra_bsync_process_packed_device(h->bs, h->bits[b], h->stride, h->nbits[b], h->frames, h->ft, h->fb, h->nf, s));
     HIP_TRY(h, hipEventRecord(h->ev_stage[1], s));
     TETRA_TRY(tetra_burst_index_device(h->ft, n, h->F, h->lists[b], h->counts[b], h->chan_first, h->index_work, s));
+    void* assist = nullptr;
+    TETRA_TRY(chan_tab::live(h, TAB_HANDOVER, &assist));
+    if (assist) {      // a handle that has handed over: the synchroniser's results of this call, in front of the tracker
+        const handover::View hv = { nullptr, static_cast<bsync_core::Assist*>(assist), reinterpret_cast<tetra_lmac::TrackState*>(h->cell.get()) };
+        hipLaunchKernelGGL(k_handover_apply, dim3((unsigned)((h->C + 63) / 64)), dim3(64), 0, s, hv, h->C);
+        HIP_TRY(h, hipGetLastError());
+    }
     tetra_lmac_frames_t src = {};
     src.d_frames = h->frames;
     src.d_frame_type = h->ft;
@@ -623,6 +640,24 @@ int tetra_rx_rows_device(tetra_rx_t* h, int which, int kind, const uint8_t** d_t
 int tetra_rx_get_cell(tetra_rx_t* h, int first, int count, tetra_lmac_cell_state_t* out) { return get_chan(h, TAB_CELL, first, count, out); }
 
 int tetra_rx_get_sync_state(tetra_rx_t* h, int first, int count, tetra_bsync_state_t* out) { return get_chan(h, TAB_SYNC_STATE, first, count, out); }
+
+// the chain's share of tetra_handover.h: the first three words of every channel's hand-over fields; all zero on a handle without them
+int tetra_rx_get_handover(tetra_rx_t* h, int first, int count, tetra_handover_status_t* out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
+    if (!h || !out || first < 0 || count < 0 || first + (long long)count > h->C) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    TETRA_TRY(latest_tail_done(h));
+    if (h->calls == 0) HIP_TRY(h, hipDeviceSynchronize());      // (no tail yet whose event a hand-over would have been recorded behind)
+    void* live = nullptr;
+    TETRA_TRY(chan_tab::live(h, TAB_HANDOVER, &live));
+    std::vector<bsync_core::Assist> fields((size_t)count, bsync_core::Assist{});
+    if (live && count)
+        HIP_TRY(h, hipMemcpy(fields.data(), static_cast<const bsync_core::Assist*>(live) + first, sizeof(bsync_core::Assist) * (size_t)count, hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; i++) out[i] = { fields[(size_t)i].status, fields[(size_t)i].waited, fields[(size_t)i].offset };
+    return TETRA_OK;
+}
 
 // the chain's share of tetra_sync_tol.h
 int tetra_rx_set_sync_tolerance(tetra_rx_t* h, const tetra_bsync_tolerance_t* tol) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ext/tetra_biterr.h"
+#include "ext/tetra_handover.h"
 #include "ext/tetra_list.h"
 #include "ext/tetra_rx_out_ext.h"
 #include "ext/tetra_sync_tol.h"
@@ -210,6 +211,15 @@ public:
     int setSyncTolerance(const tetra_bsync_tolerance_t* tol) { return tetra_rx_set_sync_tolerance(h_, tol); }
     // every channel's count of consecutive LOCKED frames without a training sequence
     int syncMisses(std::vector<int32_t>& out) { return table(tetra_rx_get_sync_misses, out); }
+    // Retune with a donor (ext/tetra_handover.h): the listed channels restart, and channels[i] inherits frame timing, cell and TDMA clock
+    // from donors[i] (-1: a plain restart); p = null: the header's defaults.  Enqueued on hipStream, not waited for.
+    int handOver(const std::vector<int32_t>& channels, const std::vector<int32_t>& donors, const tetra_handover_params_t* p = nullptr,
+                 void* hipStream = nullptr) {
+        if (channels.size() != donors.size()) return TETRA_ERR_ARG;
+        return tetra_rx_handover_channels_device(h_, channels.data(), donors.data(), (int)channels.size(), p, hipStream);
+    }
+    // ... and every channel's hand-over status
+    int handoverStatus(std::vector<tetra_handover_status_t>& out) { return table(tetra_rx_get_handover, out); }
     // the PI4DQPSK setters of the demodulators inside (tetra_demod_set_param ids); waits for work in flight first
     int setParam(int paramId, double value) {
         const int rc = tetra_rx_wait(h_);
@@ -340,6 +350,33 @@ public:
         return gather(out, [&](TetraRxBank& b, auto& part) { return b.fetchListRank(kind, part, which); });
     }
     int links(std::vector<tetra_rx_link_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.links(part); }); }
+    // Retune with a donor (ext/tetra_handover.h), in the bank's channel numbers: every shard is told its own entries.  Nothing crosses
+    // between the GPUs, so a donor must lie in its heir's shard: TETRA_ERR_ARG otherwise (and for a channel outside the bank), nothing
+    // enqueued on any shard.  streams[s]: a HIP stream of shard s's device (streams = null: the null streams).
+    int handOver(const std::vector<int32_t>& channels, const std::vector<int32_t>& donors, const tetra_handover_params_t* p = nullptr,
+                 void* const* streams = nullptr) {
+        if (channels.size() != donors.size()) return TETRA_ERR_ARG;
+        if (p && (p->window < 0 || p->window > 127 || p->max_slots < 1 || p->max_slots > 255)) return TETRA_ERR_ARG;
+        // everything a shard would refuse is refused here, before the first shard is told anything
+        std::vector<char> heir((size_t)channels_, 0);
+        for (int32_t c : channels) {
+            if (c < 0 || c >= channels_ || heir[(size_t)c]) return TETRA_ERR_ARG;
+            heir[(size_t)c] = 1;
+        }
+        std::vector<std::vector<int32_t>> ch(shards_.size()), dn(shards_.size());
+        for (size_t i = 0; i < channels.size(); i++) {
+            const int s = shardOf(channels[i]);
+            if (donors[i] != -1 && (shardOf(donors[i]) != s || heir[(size_t)donors[i]])) return TETRA_ERR_ARG;
+            ch[(size_t)s].push_back(channels[i] - shards_[(size_t)s]->first);
+            dn[(size_t)s].push_back(donors[i] == -1 ? -1 : donors[i] - shards_[(size_t)s]->first);
+        }
+        for (size_t s = 0; s < shards_.size(); s++) {
+            const int rc = shards_[s]->bank.handOver(ch[s], dn[s], p, streams ? streams[s] : nullptr);
+            if (rc != TETRA_OK) return rc;
+        }
+        return TETRA_OK;
+    }
+    int handoverStatus(std::vector<tetra_handover_status_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.handoverStatus(part); }); }
     int channels() const { return channels_; }
     int shards() const { return (int)shards_.size(); }
     void shardInfo(int shard, int& first, int& count) const { first = shards_[(size_t)shard]->first; count = shards_[(size_t)shard]->count; }
@@ -350,6 +387,12 @@ private:
         TetraRxBank bank;
         int first = 0, count = 0;
     };
+    // the shard that holds channel c of the bank, or -1
+    int shardOf(int c) const {
+        for (size_t s = 0; s < shards_.size(); s++)
+            if (c >= shards_[s]->first && c < shards_[s]->first + shards_[s]->count) return (int)s;
+        return -1;
+    }
     // tell every shard in turn: the first failure ends the round and is the result
     template <class Tell> int each(Tell tell) {
         for (auto& s : shards_) {

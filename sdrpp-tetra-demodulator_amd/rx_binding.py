@@ -94,6 +94,32 @@ LIST_ABI = {
     "tetra_rx_fetch_list_rank": (i32, [vp, i32, i32, vp, i32, P(i32)]),
     "tetra_rx_list_rank_device": (i32, [vp, i32, i32, P(vp), vp]),
 }
+# include/ext/tetra_handover.h (a restarted channel inherits frame timing, cell and clock from a donor): the chain's share
+class HandoverParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("max_slots", C.c_int32)]
+
+
+class HandoverStatus(C.Structure):
+    _fields_ = [("state", C.c_int32), ("slots_waited", C.c_int32), ("offset", C.c_int32)]
+
+
+HANDOVER_NONE, HANDOVER_PENDING, HANDOVER_LOCKED, HANDOVER_EXPIRED, HANDOVER_REFUSED = range(5)
+HANDOVER_DEFAULT_WINDOW, HANDOVER_DEFAULT_MAX_SLOTS = 8, 72
+SYNC_STATE_ASSIST = 3         # TETRA_BSYNC_STATE_ASSIST
+HANDOVER_ABI = {
+    "tetra_rx_handover_channels_device": (i32, [vp, vp, vp, i32, P(HandoverParams), vp]),
+    "tetra_rx_get_handover": (i32, [vp, i32, i32, P(HandoverStatus)]),
+}
+
+
+def handover_params_arg(window, max_slots):
+    """None, None -> NULL (the header's defaults); else the struct with the default for whichever is None."""
+    if window is None and max_slots is None:
+        return None
+    return C.byref(HandoverParams(HANDOVER_DEFAULT_WINDOW if window is None else int(window),
+                                  HANDOVER_DEFAULT_MAX_SLOTS if max_slots is None else int(max_slots)))
+
+
 # include/ext/tetra_rx_out_ext.h (the opt-in row extras and per-channel state through the one-step hand-off)
 OUT_EXT_ABI = {
     "tetra_rx_out_bound_ext": (i32, [vp, i32, i32, i32, P(u64)]),
@@ -105,15 +131,16 @@ OUT_EXT_ABI = {
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 RX_OUT_EXT_EXPORTS = list(OUT_EXT_ABI)
+RX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
     return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
-                                    **OUT_EXT_ABI},
+                                    **OUT_EXT_ABI, **HANDOVER_ABI},
                    optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
-                   RX_OUT_EXT_EXPORTS)
+                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS)
 
 
 def type1_bits(kind):
@@ -161,6 +188,21 @@ class RxChain:
         enqueued on `stream`, not waited for."""
         ch = np.ascontiguousarray(np.asarray(channels, np.int64).astype(np.int32).reshape(-1))
         call(self._lib.tetra_rx_reset_channels_device, self._h, ptr(ch) if ch.size else None, int(ch.size), stream_ptr(stream))
+
+    def handover_channels(self, channels, donors, window=None, max_slots=None, stream=None):
+        """tetra_rx_handover_channels_device: reset_channels, and every listed channel with a donor (donors[i] >= 0; -1: a plain restart)
+        inherits that channel's frame timing, cell and TDMA clock and looks for its first burst `window` bits either side of where the
+        donor's frames start, for at most `max_slots` slot periods (None: the header's defaults).  Enqueued, not waited for."""
+        ch = np.ascontiguousarray(np.asarray(channels, np.int64).astype(np.int32).reshape(-1))
+        dn = np.ascontiguousarray(np.asarray(donors, np.int64).astype(np.int32).reshape(-1))
+        if dn.size != ch.size:
+            raise ValueError("handover_channels takes a donor (or -1) per channel")
+        call(self._lib.tetra_rx_handover_channels_device, self._h, ptr(ch) if ch.size else None, ptr(dn) if dn.size else None, int(ch.size),
+             handover_params_arg(window, max_slots), stream_ptr(stream))
+
+    def handover_status(self, first=0, count=None):
+        """tetra_rx_get_handover: per channel (state HANDOVER_*, slot periods waited, found - expected frame start in bits)."""
+        return [(a.state, a.slots_waited, a.offset) for a in self._channel_table(self._lib.tetra_rx_get_handover, HandoverStatus, first, count)]
 
     def process(self, iq):
         iq = np.ascontiguousarray(iq, np.complex64)

@@ -8,7 +8,7 @@ from . import binding as B
 from ._ffi import P, call, declare, i32, i64, ptr, stream_ptr, u32, vp
 from .binding import load_library
 from .chan_binding import ChanConfig, IqMap, _get_input_map, _set_input_map, input_map_from_stats, iq_stats
-from .rx_binding import RxChain, RxConfig
+from .rx_binding import HandoverParams, RxChain, RxConfig, handover_params_arg
 from .rx_binding import _lib as _rx_lib
 
 
@@ -49,14 +49,17 @@ IQCOND_ABI = {
     "tetra_wbrx_set_input_map": (i32, [vp, P(IqMap)]),
     "tetra_wbrx_get_input_map": (i32, [vp, P(IqMap), P(i32)]),
 }
+# include/ext/tetra_handover.h (a moved slot inherits frame timing, cell and clock from a donor slot): the wideband receiver's share
+HANDOVER_ABI = {"tetra_wbrx_retune_from": (i32, [vp, vp, vp, P(HandoverParams), vp])}
 WBRX_EXPORTS, WBRX_SHIFT_EXPORTS, WBRX_RETUNE_EXPORTS = list(SIGNATURES), list(SHIFT_SIGNATURES), list(RETUNE_SIGNATURES)
+WBRX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the shift, the retune and the input map)
-    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI},
-                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI))
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI, **HANDOVER_ABI},
+                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI) + WBRX_HANDOVER_EXPORTS)
 
 
 def default_config():
@@ -85,6 +88,9 @@ class _ChainView(RxChain):
 
     def reset_channels(self, channels, stream=None):
         raise TypeError("the wideband receiver's slots are restarted through WidebandRx.retune()")
+
+    def handover_channels(self, channels, donors, window=None, max_slots=None, stream=None):
+        raise TypeError("the wideband receiver's slots are handed over through WidebandRx.retune(bins, donors=...)")
 
     def process(self, iq):
         raise TypeError("the wideband receiver's chain is fed through WidebandRx.process*()")
@@ -159,13 +165,25 @@ class WidebandRx:
         self.set_input_map(m)
         return m
 
-    def retune(self, bins, stream=None):
+    def retune(self, bins, stream=None, donors=None, window=None, max_slots=None):
         """tetra_wbrx_retune: slot j receives bins[j] from the next process call on.  Slots whose bin stays are untouched; every other
-        slot starts afresh on its new bin.  Enqueued on `stream` (the one the process calls use), not waited for."""
+        slot starts afresh on its new bin.  Enqueued on `stream` (the one the process calls use), not waited for.
+        donors (tetra_wbrx_retune_from, include/ext/tetra_handover.h): per slot a donor slot whose bin stays, or -1 -- a moving slot with
+        a donor inherits its frame timing, cell and TDMA clock (window / max_slots: None = the header's defaults)."""
         new = np.ascontiguousarray(np.asarray(bins, np.int64).astype(np.int32).reshape(-1))
         if new.size != self.n_bins:
             raise ValueError("retune takes exactly %d bins" % self.n_bins)
-        call(self._lib.tetra_wbrx_retune, self._h, ptr(new), stream_ptr(stream))
+        if donors is None:
+            call(self._lib.tetra_wbrx_retune, self._h, ptr(new), stream_ptr(stream))
+            return
+        dn = np.ascontiguousarray(np.asarray(donors, np.int64).astype(np.int32).reshape(-1))
+        if dn.size != self.n_bins:
+            raise ValueError("retune takes a donor (or -1) per slot")
+        call(self._lib.tetra_wbrx_retune_from, self._h, ptr(new), ptr(dn), handover_params_arg(window, max_slots), stream_ptr(stream))
+
+    def handover_status(self, first=0, count=None):
+        """The carrier slots' hand-over status (RxChain.handover_status of the chain)."""
+        return self.rx.handover_status(first, count)
 
     def retune_count(self):
         """-> (accepted retunes, slots they moved) since create."""
