@@ -16,6 +16,7 @@
 // its own around k_out_write (see below); without extras the three kernels above are all that is launched.
 #include <hip/hip_runtime.h>
 
+#include "../../include/ext/tetra_rx_out_rows.h"
 #include "../../include/tetra_rx_out.h"
 #include "compact_core.hpp"
 #include "rx_handle.hpp"
@@ -316,6 +317,70 @@ int extras_supported(const tetra_rx* h, int extras) {
     return TETRA_OK;
 }
 
+// where the kernels write: device memory on GPU `device`, or page-locked host memory through its device address; 16-byte aligned
+int resolve_dst(void* dst, int device, uint8_t** out) {
+    hipPointerAttribute_t at = {};
+    if (hipPointerGetAttributes(&at, dst) != hipSuccess) {
+        (void)hipGetLastError();
+        return TETRA_ERR_ARG;
+    }
+    uint8_t* d = nullptr;
+    if (at.type == hipMemoryTypeDevice) {
+        if (at.device != device) return TETRA_ERR_ARG;
+        d = static_cast<uint8_t*>(dst);
+    } else if (at.type == hipMemoryTypeHost) {
+        void* p = nullptr;
+        if (hipHostGetDevicePointer(&p, dst, 0) != hipSuccess || !p) {
+            (void)hipGetLastError();
+            return TETRA_ERR_ARG;
+        }
+        d = static_cast<uint8_t*>(p);
+    } else {
+        return TETRA_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d) & 15) return TETRA_ERR_ALIGN;
+    *out = d;
+    return TETRA_OK;
+}
+
+// The launches of one delivery on s, for the chain's rows (enqueue) and a caller's (tetra_rx_out_write_rows_device) alike.
+// x.extras = 0: count (CRC-good only), layout, write, and nothing else; xl is not looked at then.
+// tile_off [TETRA_RX_N_KINDS][a.tiles]: k_out_count's counts, scanned in place by k_out_layout
+void launch(const OutArgs& a, const ExtArgs& x, uint8_t* d, uint64_t capacity, long long c, int32_t* tile_off, Layout* lay, ExtLayout* xl,
+            hipStream_t s) {
+    const unsigned tiles = (unsigned)a.tiles;
+    if (a.flags & TETRA_RX_OUT_CRC_GOOD) hipLaunchKernelGGL(k_out_count, dim3(tiles, (unsigned)a.nsel), dim3(kTile), 0, s, a, tile_off);
+    hipLaunchKernelGGL(k_out_layout, dim3(1), dim3(compact_core::kScanThreads), 0, s, a, tile_off, lay, d, capacity, c);
+    if (x.extras) hipLaunchKernelGGL(k_out_ext_layout, dim3(1), dim3(kTile), 0, s, a, x, tile_off, lay, xl, d, capacity, c);
+    hipLaunchKernelGGL(k_out_write, dim3(tiles, (unsigned)a.nsel), dim3(256), 0, s, a, tile_off, lay, d);
+    if (x.extras) hipLaunchKernelGGL(k_out_ext_write, dim3(tiles, (unsigned)a.nsel + 1), dim3(kTile), 0, s, a, x, tile_off, xl, d);
+}
+
+// one selected kind of a launch
+OutKind out_kind(int kind, const uint8_t* t2, int stride, const int32_t* ok, const tetra_rx_block_t* blocks, const int32_t* n_rows, int flags) {
+    OutKind o = {};
+    o.t2 = t2;
+    o.ok = ok;
+    o.blocks = blocks;
+    o.n_rows = n_rows;
+    o.kind = kind;
+    o.out_stride = stride;
+    o.nb = kKinds[kind].type1_bits;
+    o.rb = rx_out::row_bytes(kind, flags);
+    return o;
+}
+
+// the caller's workspace (tetra_rx_out_rows.h): the tile counts, the layout, the extension's layout, each on its own 16 bytes
+struct RowsWork {
+    size_t lay, xl, bytes;
+    explicit RowsWork(int max_rows) {
+        const size_t tiles = ((size_t)max_rows + kTile - 1) / kTile;
+        lay = (size_t)rx_out::align16(sizeof(int32_t) * TETRA_RX_N_KINDS * tiles);
+        xl = lay + (size_t)rx_out::align16(sizeof(Layout));
+        bytes = xl + (size_t)rx_out::align16(sizeof(ExtLayout));
+    }
+};
+
 int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst, uint64_t capacity, int64_t* call);
 
 }  // namespace
@@ -414,27 +479,8 @@ int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst,
     if (capacity < rx_out::kHeaderBytes) return TETRA_ERR_SIZE;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
-    // where the kernels write: device memory on this GPU, or page-locked host memory through its device address
-    hipPointerAttribute_t at = {};
-    if (hipPointerGetAttributes(&at, dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return TETRA_ERR_ARG;
-    }
     uint8_t* d = nullptr;
-    if (at.type == hipMemoryTypeDevice) {
-        if (at.device != h->device) return TETRA_ERR_ARG;
-        d = static_cast<uint8_t*>(dst);
-    } else if (at.type == hipMemoryTypeHost) {
-        void* p = nullptr;
-        if (hipHostGetDevicePointer(&p, dst, 0) != hipSuccess || !p) {
-            (void)hipGetLastError();
-            return TETRA_ERR_ARG;
-        }
-        d = static_cast<uint8_t*>(p);
-    } else {
-        return TETRA_ERR_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(d) & 15) return TETRA_ERR_ALIGN;
+    TETRA_TRY(resolve_dst(dst, h->device, &d));
     const int tiles = (h->rows + kTile - 1) / kTile;
     if (h->out_tiles.reserve(sizeof(int32_t) * TETRA_RX_N_KINDS * (size_t)tiles) != hipSuccess ||
         h->out_layout.reserve(sizeof(Layout)) != hipSuccess) {
@@ -445,15 +491,7 @@ int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst,
     for (int k = 0; k < TETRA_RX_N_KINDS; k++) {
         if (!(sel & (1 << k))) continue;
         const KindBufs& r = h->res[b][k];
-        OutKind& o = a.k[a.nsel++];
-        o.t2 = r.t2;
-        o.ok = r.ok;
-        o.blocks = r.blocks;
-        o.n_rows = r.n_rows;
-        o.kind = k;
-        o.out_stride = kKinds[k].out_stride;
-        o.nb = kKinds[k].type1_bits;
-        o.rb = rx_out::row_bytes(k, flags);
+        a.k[a.nsel++] = out_kind(k, r.t2, kKinds[k].out_stride, r.ok, r.blocks, r.n_rows, flags);
     }
     a.flags = flags;
     a.tiles = tiles;
@@ -474,18 +512,14 @@ int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst,
         x.extras = extras;
         x.n_channels = h->C;
     }
-    int32_t* tile_off = h->out_tiles;                     // [kind][tile]: k_out_count's counts, scanned in place by k_out_layout
+    int32_t* tile_off = h->out_tiles;
     for (auto& e : h->ring_ev)
         if (!e) HIP_TRY(h, hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
     Layout* lay = reinterpret_cast<Layout*>(h->out_layout.get());
     const long long c = h->calls - 1 - which;
     hipStream_t s = h->fetch_s;
     HIP_TRY(h, hipStreamWaitEvent(s, h->ev_tail[b], 0));
-    if (flags & TETRA_RX_OUT_CRC_GOOD) hipLaunchKernelGGL(k_out_count, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(kTile), 0, s, a, tile_off);
-    hipLaunchKernelGGL(k_out_layout, dim3(1), dim3(compact_core::kScanThreads), 0, s, a, tile_off, lay, d, capacity, c);
-    if (extras) hipLaunchKernelGGL(k_out_ext_layout, dim3(1), dim3(kTile), 0, s, a, x, tile_off, lay, xl, d, capacity, c);
-    hipLaunchKernelGGL(k_out_write, dim3((unsigned)tiles, (unsigned)a.nsel), dim3(256), 0, s, a, tile_off, lay, d);
-    if (extras) hipLaunchKernelGGL(k_out_ext_write, dim3((unsigned)tiles, (unsigned)a.nsel + 1), dim3(kTile), 0, s, a, x, tile_off, xl, d);
+    launch(a, x, d, capacity, c, tile_off, lay, xl, s);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->ev_out[b], s));
     h->out_pending[b] = true;
@@ -500,6 +534,52 @@ int enqueue(tetra_rx* h, int which, int kinds, int flags, int extras, void* dst,
 }  // namespace
 
 extern "C" {
+
+size_t tetra_rx_out_rows_workspace_bytes(int max_rows) { return max_rows < 1 ? 0 : RowsWork(max_rows).bytes; }
+
+int tetra_rx_out_write_rows_device(const tetra_rx_out_rows_t* kinds, int n_kinds, int max_rows, int flags, int row_extras, int64_t call, void* dst,
+                                   uint64_t capacity, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!kinds || !dst || !d_workspace || n_kinds < 1 || n_kinds > TETRA_RX_N_KINDS || max_rows < 1 || (flags & ~rx_out::kFlagsAll) ||
+        (row_extras & ~rx_out::kExtrasRow))
+        return TETRA_ERR_ARG;
+    const auto off_grid = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; };
+    OutArgs a = {};
+    ExtArgs x = {};
+    bool misaligned = off_grid(d_workspace, 16);
+    for (int i = 0; i < n_kinds; i++) {
+        const tetra_rx_out_rows_t& r = kinds[i];
+        if (r.kind < 0 || r.kind >= TETRA_RX_N_KINDS || (i > 0 && r.kind <= kinds[i - 1].kind)) return TETRA_ERR_ARG;
+        if (!r.d_type2 || !r.d_crc_ok || !r.d_blocks || !r.d_n_rows) return TETRA_ERR_ARG;
+        if (r.type2_stride < 8 * ((kKinds[r.kind].type1_bits + 7) / 8)) return TETRA_ERR_ARG;
+        const bool coded = rx_out::kind_has(r.kind, COL_BITERR);
+        if (coded && (((row_extras & TETRA_RX_OUT_EXT_ROW_BITERR) && !r.d_biterr) || ((row_extras & TETRA_RX_OUT_EXT_ROW_LIST_RANK) && !r.d_rank)))
+            return TETRA_ERR_ARG;
+        misaligned = misaligned || (r.type2_stride & 7) || off_grid(r.d_type2, 8) || off_grid(r.d_blocks, 8) || off_grid(r.d_crc_ok, 4) ||
+                     off_grid(r.d_n_rows, 4) || off_grid(r.d_biterr, 4) || off_grid(r.d_rank, 4);
+        a.k[a.nsel++] = out_kind(r.kind, r.d_type2, r.type2_stride, r.d_crc_ok, r.d_blocks, r.d_n_rows, flags);
+        x.k[i].biterr = r.d_biterr;
+        x.k[i].rank = r.d_rank;
+    }
+    const RowsWork w(max_rows);
+    if (capacity < rx_out::kHeaderBytes || workspace_bytes < w.bytes) return TETRA_ERR_SIZE;
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) {
+        (void)hipGetLastError();
+        return TETRA_ERR_NO_DEVICE;
+    }
+    uint8_t* d = nullptr;
+    const int rc = resolve_dst(dst, device, &d);
+    if (rc != TETRA_OK && rc != TETRA_ERR_ALIGN) return rc;
+    if (misaligned || rc == TETRA_ERR_ALIGN) return TETRA_ERR_ALIGN;
+    a.flags = flags;
+    a.tiles = (int)(((size_t)max_rows + kTile - 1) / kTile);
+    a.max_rows = max_rows;
+    x.extras = row_extras;      // (no snapshot, no channels: the tables are a handle's)
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    launch(a, x, d, capacity, call, reinterpret_cast<int32_t*>(ws), reinterpret_cast<Layout*>(ws + w.lay), reinterpret_cast<ExtLayout*>(ws + w.xl),
+           static_cast<hipStream_t>(hip_stream));
+    return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
+}
 
 int tetra_rx_out_query(tetra_rx_t* h, int64_t call) {
     if (!h) return TETRA_ERR_ARG;

@@ -128,6 +128,18 @@ OUT_EXT_ABI = {
     "tetra_rx_out_view_ext": (i32, [vp, u64, i32, P(vp), P(vp), P(vp), P(i32)]),
     "tetra_rx_out_view_channels": (i32, [vp, u64, P(vp), P(vp), P(vp), P(vp), P(i32)]),
 }
+# include/ext/tetra_rx_out_rows.h (the delivery's launches over rows the caller provides)
+class OutRows(C.Structure):
+    """tetra_rx_out_rows_t."""
+    _fields_ = [("kind", C.c_int32), ("type2_stride", C.c_int32), ("d_type2", vp), ("d_crc_ok", vp), ("d_blocks", vp), ("d_n_rows", vp),
+                ("d_biterr", vp), ("d_rank", vp)]
+
+
+OUT_ROWS_ABI = {
+    "tetra_rx_out_rows_workspace_bytes": (size_t, [i32]),
+    "tetra_rx_out_write_rows_device": (i32, [P(OutRows), i32, i32, i32, i32, i64, vp, u64, vp, size_t, vp]),
+}
+RX_OUT_ROWS_EXPORTS = list(OUT_ROWS_ABI)
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 RX_OUT_EXT_EXPORTS = list(OUT_EXT_ABI)
@@ -138,9 +150,9 @@ RX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
     return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
-                                    **OUT_EXT_ABI, **HANDOVER_ABI},
+                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI},
                    optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
-                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS)
+                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS)
 
 
 def type1_bits(kind):
@@ -502,6 +514,40 @@ def unpack_bits(packed, n_bits):
     out = np.zeros((n, n_bits), np.uint8)
     call(_lib().tetra_rx_unpack_bits, ptr(packed), n, rb, n_bits, ptr(out), n_bits)
     return out
+
+
+def out_rows_workspace_bytes(max_rows):
+    """tetra_rx_out_rows_workspace_bytes: device scratch for out_write_rows over up to max_rows rows per kind."""
+    return int(_lib().tetra_rx_out_rows_workspace_bytes(int(max_rows)))
+
+
+def out_rows_arg(kinds):
+    """[dict(kind, type2, crc_ok, blocks, n_rows[, stride, biterr, rank])] -> the tetra_rx_out_rows_t array.  Every array is a torch
+    tensor on the GPU or a raw device address (ptr's rule); stride defaults to type2's row length in bytes, which a raw address lacks."""
+    arr = (OutRows * max(len(kinds), 1))()
+    for o, k in zip(arr, kinds):
+        t2 = k["type2"]
+        stride = k.get("stride")
+        o.kind, o.type2_stride = int(k["kind"]), int(t2.stride(0) * t2.element_size() if stride is None else stride)
+        o.d_type2, o.d_crc_ok, o.d_blocks, o.d_n_rows = ptr(t2), ptr(k["crc_ok"]), ptr(k["blocks"]), ptr(k["n_rows"])
+        o.d_biterr, o.d_rank = ptr(k.get("biterr")), ptr(k.get("rank"))
+    return arr
+
+
+def out_write_rows(kinds, max_rows, dst, workspace, packed=False, crc_good_only=False, row_extras=0, call_index=0, capacity=None, stream=None):
+    """tetra_rx_out_write_rows_device (include/ext/tetra_rx_out_rows.h): the delivery's launches over the caller's rows `kinds`
+    (out_rows_arg's list, ascending kinds), enqueued on `stream` and not waited for.  dst: a HostBuffer, a uint8 torch tensor on the
+    GPU or an object with a .ctypes pointer into page-locked memory (capacity: its size unless given); workspace: a uint8 torch tensor of out_rows_workspace_bytes(max_rows) bytes on the GPU.  Read
+    the result with view_delivery / view_delivery_ext once the stream's work is done."""
+    flags = (OUT_PACKED if packed else 0) | (OUT_CRC_GOOD if crc_good_only else 0)
+    if isinstance(dst, HostBuffer):
+        d, cap = dst.ptr, dst.nbytes
+    elif hasattr(dst, "data_ptr"):
+        d, cap = dst.data_ptr(), dst.numel() * dst.element_size()
+    else:
+        d, cap = dst.ctypes.data, dst.nbytes
+    call(_lib().tetra_rx_out_write_rows_device, out_rows_arg(kinds), len(kinds), int(max_rows), flags, int(row_extras), int(call_index), d,
+         cap if capacity is None else int(capacity), ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr(stream))
 
 
 class Delivery:

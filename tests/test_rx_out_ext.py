@@ -10,19 +10,15 @@ import tempfile
 import numpy as np
 import pytest
 
-from tests.test_rx_out import PACKED_BYTES, TYPE1, _build_delivery, _downlink_batch, _noisy_batch
+from tests.rx_out_reference import CHAN_BYTES, a16 as _a16, build_ext_delivery as _build_ext_delivery, keep_patterns as _keep_patterns
+from tests.test_rx_out import _build_delivery, _downlink_batch, _noisy_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PK = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
 SAN = os.path.join(ROOT, "tests", "san")
 HDR = os.path.join(ROOT, "include", "ext", "tetra_rx_out_ext.h")
-CHAN_BYTES = [40, 16, 4, 24]
 ROW_BYTES = [4, 4, 1]
 ARG, UNSUPPORTED, SIZE = -1, -2, -6
-
-
-def _a16(x):
-    return (x + 15) // 16 * 16
 
 
 # ---------------------------------------------------------------------------------------------------------------- ABI
@@ -78,52 +74,6 @@ def test_rx_out_ext_struct_layouts_match_header(pkg):
 
 
 # ---------------------------------------------------------------------------------------------------------------- layout and readers
-
-def _build_ext_delivery(R, rows, flags, extras, n_channels, rng):
-    """An extended delivery laid out by hand as include/ext/tetra_rx_out_ext.h documents it, behind test_rx_out's classic one ->
-    (buffer, classic rows, {kind: [biterr, rank, dist] (None = absent)}, [cell, sync, misses, link] as bytes (None = absent),
-    section boundaries)."""
-    classic, want = _build_delivery(R, rows, flags, rng)
-    kinds = sorted(rows)
-    ex = R.OutExtHeader()
-    ex.magic, ex.call, ex.n_channels, ex.n_kinds = R.OUT_EXT_MAGIC, 41, n_channels, len(kinds)
-    at = _a16(len(classic))
-    end = at + C.sizeof(R.OutExtHeader)
-    got, cols, parts, bounds = extras & R.EXT_CHAN_ALL, {}, [], [len(classic), at, end]
-    for i, k in enumerate(kinds):
-        n = rows[k]
-        e = ex.kinds[i]
-        e.kind, e.n_rows = k, n
-        cols[k] = [None, None, None]
-        for c, (field, dtype, hi) in enumerate((("biterr_offset", "<u4", 2 ** 32), ("rank_offset", "<i4", 9), ("aach_dist_offset", "u1", 256))):
-            if not extras & (1 << c) or (c == 2) != (k == R.KIND_BBK):
-                continue
-            off = _a16(end)
-            setattr(e, field, off)
-            v = rng.integers(-1 if c == 1 else 0, hi, n).astype(dtype)
-            cols[k][c] = v
-            parts.append((off, v.tobytes()))
-            end = off + v.nbytes
-            bounds.append(end)
-            got |= 1 << c
-    tabs = [None] * 4
-    for t, field in enumerate(("cell_offset", "sync_state_offset", "sync_misses_offset", "link_offset")):
-        if not extras & (R.EXT_CHAN_CELL << t):
-            continue
-        off = _a16(end)
-        setattr(ex, field, off)
-        tabs[t] = rng.integers(0, 256, CHAN_BYTES[t] * n_channels).astype(np.uint8).tobytes()
-        parts.append((off, tabs[t]))
-        end = off + len(tabs[t])
-        bounds.append(end)
-    ex.extras, ex.bytes = got, end
-    buf = np.zeros(end, np.uint8)
-    buf[:len(classic)] = classic
-    buf[at: at + C.sizeof(R.OutExtHeader)] = np.frombuffer(bytes(ex), np.uint8)
-    for off, b in parts:
-        buf[off: off + len(b)] = np.frombuffer(b, np.uint8)
-    return buf, want, cols, tabs, sorted(set(bounds))
-
 
 def _view_ext_rc(L, buf, nbytes, kind):
     return L.tetra_rx_out_view_ext(buf.ctypes.data_as(C.c_void_p), nbytes, kind, None, None, None, None)
@@ -207,15 +157,6 @@ def test_rx_out_ext_host_side_is_clean_under_asan_and_ubsan():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the writer's lane code
-
-def _keep_patterns(n):
-    last_of_tile = np.zeros(n, np.int32)
-    last_of_tile[127::128] = 1
-    if n:
-        last_of_tile[n - 1] = 1
-    every_second = (np.arange(n) % 2).astype(np.int32)
-    return {"all": np.ones(n, np.int32), "none": np.zeros(n, np.int32), "every second": every_second, "last of a tile": last_of_tile}
-
 
 def test_rx_out_ext_lane_code_writes_column_of_keep():
     """The columns the tiles write (host build of the lane code, tests/emul/rx_out_ext_emul.cpp) are numpy's column[keep], at every
