@@ -32,8 +32,9 @@ extern "C" {
  *   src             d_frame_bitnum [n_frames] is REQUIRED (the absolute bit number of each frame's first bit) and
  *                   frames_per_channel >= 1, with or without labels.  d_frames is not read for the coded kinds, but must be given and
  *                   aligned as for tetra_lmac_decode_frames_device; d_frame_type says which kinds a frame carries.
- *   jobs            SB1, SB2, NDB and SCH/F.  A BBK job (with or without TETRA_LMAC_JOB_RM3014) is TETRA_ERR_ARG: the AACH has no soft
- *                   route, decode it from the packed frames.  A listed frame of another burst type decodes as a block of erasures
+ *   jobs            SB1, SB2, NDB and SCH/F.  A BBK job (with or without TETRA_LMAC_JOB_RM3014) is TETRA_ERR_ARG: the AACH's hard bits are
+ *                   not in the ring, decode them from the packed frames.  The AACH's soft route is a job flag of its own,
+ *                   TETRA_LMAC_JOB_RM3014_SOFT of ext/tetra_aach_soft.h, which this entry point alone accepts.  A listed frame of another burst type decodes as a block of erasures
  *                   (all soft values zero) under that frame's scrambling code.
  *   d_biterr        NULL, or [n_jobs] device pointers as for tetra_lmac_decode_frames_biterr_device (tetra_biterr.h); an entry may be
  *                   NULL.  The counts are taken on the soft values: compared = the positions whose value is not 0, errors = those
@@ -44,7 +45,7 @@ extern "C" {
  *                   the rescued codeword.
  *   max_candidates  the ranks' T, 1..TETRA_LIST_MAX_CANDIDATES (else TETRA_ERR_ARG for a job with ranks); not looked at otherwise.
  * TETRA_ERR_ARG, before anything is launched or written: d_ring NULL or off the 4-byte grid, ring_size 0 / below 4 / no power of two,
- * src->d_frame_bitnum NULL, src->frames_per_channel < 1, a BBK job.
+ * src->d_frame_bitnum NULL, src->frames_per_channel < 1, a BBK job without TETRA_LMAC_JOB_RM3014_SOFT.
  */
 int tetra_lmac_decode_frames_soft_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs,
                                          const int8_t* d_ring, uint32_t ring_size,

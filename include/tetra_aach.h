@@ -22,6 +22,8 @@
  *     byte 30       dist (0..3, or 0xFF)
  *     byte 31       0
  * The first 14 bytes are the type-1 bits (the ACCESS-ASSIGN PDU; parsing it is upper MAC and stays with the caller).
+ * Decoding the same code from SOFT values, by exact maximum likelihood over its 16384 codewords, is ext/tetra_aach_soft.h
+ * (TETRA_LMAC_JOB_RM3014_SOFT, TETRA_RX_FLAG_AACH_SOFT): an option of its own that excludes the ones declared here.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */
 #ifndef TETRA_AACH_H

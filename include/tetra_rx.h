@@ -48,7 +48,8 @@ enum {
     TETRA_RX_KIND_BBK = 1,     /* TPSAP_T_BBK: AACH, 30 descrambled bits, crc_ok = 1 (pass-through like the reference, tetra_lower_mac.c:231-236).
                                   With TETRA_RX_FLAG_AACH_RM3014: the 30 bits of the RM(30,14) codeword within 3 bit errors and crc_ok = 1,
                                   or the descrambled bits and crc_ok = 0 where there is none -- a verdict the reference, which always
-                                  reports 1, does not give (tetra_aach.h) */
+                                  reports 1, does not give (tetra_aach.h).  With TETRA_RX_FLAG_AACH_SOFT: the
+                                  maximum-likelihood codeword on the soft values, and a verdict from its margin (ext/tetra_aach_soft.h) */
     TETRA_RX_KIND_SB2 = 2,     /* TPSAP_T_SB2, BLK_2 (124 type-1 bits) */
     TETRA_RX_KIND_NDB1 = 3,    /* TPSAP_T_NDB, BLK_1 (124) */
     TETRA_RX_KIND_NDB2 = 4,    /* TPSAP_T_NDB, BLK_2 (124) */
@@ -75,6 +76,12 @@ enum {
                                       in front of the SYNC tracker.  DEPARTS FROM THE REFERENCE (more CRC-good blocks at low Es/N0, at up to T x
                                       2^-16 false accepts per failed block); composes with every other flag; row formats, labels and every
                                       fetch / delivery entry are unchanged */
+    TETRA_RX_FLAG_AACH_SOFT = 1024, /* 1024 is taken: the AACH decoded from the soft ring too, by exact maximum likelihood over the RM(30,14)
+                                      code's 16384 codewords (ext/tetra_aach_soft.h): BBK rows always carry the best codeword's 30 bits, byte
+                                      30 the disagreeing soft values, byte 31 the margin to the runner-up, crc_ok = margin >= min_margin
+                                      (tetra_rx_set_aach_min_margin, default 1).  NEEDS TETRA_RX_FLAG_SOFT and REFUSES
+                                      TETRA_RX_FLAG_AACH_RM3014 (TETRA_ERR_ARG at create); composes with every other flag.  DEPARTS FROM
+                                      THE REFERENCE as the Reed-Muller flag does; every other kind is decoded as without it */
     TETRA_RX_FLAG_SOFT = 8         /* soft decisions: SB1, SB2, NDB 1 / 2 and SCH/F are decoded from the demodulator's symbols -- per bit a
                                       6-bit soft value of the differential phase, kept per channel in a ring indexed by `bitnum` -- where
                                       the default slices every symbol to two hard bits first.  Same decoder as the reference's

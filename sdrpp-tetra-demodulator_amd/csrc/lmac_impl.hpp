@@ -33,8 +33,8 @@ TETRA_HIDDEN size_t list_work_bytes(const tetra_lmac_job_t* jobs, int n_jobs);
 
 // The options of a frame launch; the defaults are tetra_lmac_decode_frames_device.
 struct FrameOpts {
-    // NULL: the blocks' bits from the packed frames.  Else the coded kinds (SB1, SB2, NDB, SCH/F; a BBK job is TETRA_ERR_ARG: the AACH
-    // stays on the packed frames) read as soft values from this ring at the frame's bit number: a ring of whole aligned words, and
+    // NULL: the blocks' bits from the packed frames.  Else the coded kinds (SB1, SB2, NDB, SCH/F; a BBK job is TETRA_ERR_ARG unless it
+    // carries TETRA_LMAC_JOB_RM3014_SOFT, tetra_aach_soft.h: the AACH by maximum likelihood, launches of its own behind the decode launch) read as soft values from this ring at the frame's bit number: a ring of whole aligned words, and
     // src->d_frame_bitnum and src->frames_per_channel >= 1 are required.  Counts and margins are then taken on the soft values.
     const SoftRing* soft = nullptr;
     uint32_t* const* d_biterr = nullptr;        // NULL, or per job where its counts go (NULL: the job does not count), tetra_biterr.h

@@ -51,7 +51,8 @@ enum { TAB_CELL, TAB_SYNC_STATE, TAB_SYNC_MISSES, TAB_LINK };
 // (bsync_core::Assist, ext/tetra_handover.h), the synchroniser's like the two above
 constexpr int TAB_HANDOVER = rx_out::kChanTables, kChanTablesAll = rx_out::kChanTables + 1;
 // the Reed-Muller distance of a BBK row (TETRA_RX_FLAG_AACH_RM3014): the byte behind its 30 type-1 bits (tetra_aach.h)
-constexpr int kAachDistByte = 30;
+// (TETRA_RX_FLAG_AACH_SOFT: the disagreeing soft values there, and the margin in the byte behind it, ext/tetra_aach_soft.h)
+constexpr int kAachDistByte = 30, kAachMarginByte = 31;
 struct ColSrc {                   // a column of one kind and parity on the device: element j at base + j * stride
     const uint8_t* base;
     size_t stride;
@@ -69,6 +70,8 @@ struct tetra_rx {
     bool aach_rm = false;                 // TETRA_RX_FLAG_AACH_RM3014: the BBK job decodes with the AACH's Reed-Muller code (tetra_aach.h)
     // TETRA_RX_FLAG_SOFT (soft_core.hpp): the coded kinds decode from soft values.  All of it lives on the demodulator's stream.
     bool soft = false;
+    bool aach_soft = false;               // TETRA_RX_FLAG_AACH_SOFT: the BBK job under `soft` is the maximum-likelihood one (ext/tetra_aach_soft.h)
+    int aach_min_margin = 1;              // tetra_rx_set_aach_min_margin
     uint32_t soft_R = 0;                  // bits per channel's ring
     int soft_par = 0;                     // which half of soft_prev / soft_bits the next call reads (it writes the other)
     DevMem<float> sym;                    // [C][stride / 2] complex64: the call's symbols (one buffer: k_soft reads it behind the demodulator)
@@ -133,7 +136,7 @@ namespace row_col TETRA_HIDDEN {
 
 // TETRA_ERR_UNSUPPORTED without the column's flag, for a kind the handle does not decode, or for one that does not carry the column
 inline int status(const tetra_rx* h, int col, int kind) {
-    const bool flag = col == COL_BITERR ? h->biterr : col == COL_RANK ? h->list : h->aach_rm;
+    const bool flag = col == COL_BITERR ? h->biterr : col == COL_RANK ? h->list : (h->aach_rm || h->aach_soft);
     return flag && (h->kinds & (1 << kind)) && rx_out::kind_has(kind, col) ? TETRA_OK : TETRA_ERR_UNSUPPORTED;
 }
 // ... the same for a delivery or a bound, which name no kind: some kind of the handle has it

@@ -155,4 +155,87 @@ LM_FN uint32_t bit_errors_soft(int type345, int type2, int a, Half half, Ld ld) 
     });
 }
 
+// ---- the AACH from soft values: exact maximum-likelihood decoding over the RM(30,14) code's 16384 codewords (ext/tetra_aach_soft.h) ------
+// A staged AACH row is 32 plain signed bytes in 8 words: the block's 30 soft values descrambled by sign, then two zeros.  The search
+// itself (k_aach_soft in tetra_lmac.hip) is a dense int8 product on the matrix cores; what it shares with the host emulation is here:
+// the staging, the key that carries the tie rule, the running best two, and the read-out.
+constexpr int kAachWords = 8;
+constexpr int kAachMaxMargin = 930;                    // 30 values of magnitude Q: |corr| <= 930, and so is the margin
+
+// four plain signed bytes (|x| <= Q), negated where `neg` has 0xff
+LM_FN uint32_t flip_signed(uint32_t four, uint32_t neg) { return bias_and_flip(four, neg) ^ 0x80808080u; }
+// The AACH's bits of a TRAIN burst (demux_core::pieces_for: SYNC one piece, the normal bursts 14 + 16) from the ring.  The pieces are no
+// multiples of four, so a word may take its first bytes from the end of piece 0 and the rest from the start of piece 1: two reads, the
+// second placed so that its bytes fall into the same byte lanes.  seq: the scrambling sequence's first word (bit i at bit 31 - i).
+template <int TRAIN, class Ring>
+LM_FN void stage_aach_pieces(uint32_t bitnum, Ring ring, uint32_t mask, uint32_t seq, uint32_t y[kAachWords]) {
+    const demux_core::Pieces p = demux_core::pieces_for(TRAIN, TETRA_TPSAP_T_BBK, 0);
+#pragma unroll
+    for (int g = 0; g < kAachWords; ++g) {
+        const int i = 4 * g;
+        uint32_t four;
+        if (i + 4 <= p.len0 || p.len1 == 0) four = ring_four(ring, bitnum + (uint32_t)(p.off0 + i), mask);
+        else if (i >= p.len0) four = ring_four(ring, bitnum + (uint32_t)(p.off1 + i - p.len0), mask);
+        else {
+            const uint32_t first = 0xffffffffu >> (8 * (4 - (p.len0 - i)));          // the bytes piece 0 still has
+            four = (ring_four(ring, bitnum + (uint32_t)(p.off0 + i), mask) & first) | (ring_four(ring, bitnum + (uint32_t)(p.off1 + i - p.len0), mask) & ~first);
+        }
+        y[g] = flip_signed(four, nibble_mask((seq >> (28 - 4 * g)) & 0xfu));
+    }
+    y[kAachWords - 1] &= 0x0000ffffu;                  // values 30, 31: not the block's
+}
+// The AACH front end on soft values: the frame's 30 ring positions descrambled by sign with `code`; a frame of another burst type is 30
+// erasures.  bitnum(), frame_type(), rows, ring, ring_words: as soft_block's.
+template <class Bitnum, class FrameType, class Rows, class Ring>
+LM_FN void aach_soft_block(uint32_t code, Bitnum bitnum, FrameType frame_type, Rows rows, Ring ring, uint32_t ring_words, uint32_t y[kAachWords]) {
+    uint32_t seq = 0;
+    lane_sequence(30, code, rows, [&](int w, uint32_t word) { seq = w == 0 ? word : seq; });
+    const uint32_t bn = bitnum(), mask = 4u * ring_words - 1u;
+    const int ft = frame_type();
+#pragma unroll
+    for (int g = 0; g < kAachWords; ++g) y[g] = 0u;
+    if (ft == TETRA_TRAIN_SYNC) stage_aach_pieces<TETRA_TRAIN_SYNC>(bn, ring, mask, seq, y);
+    else if (ft == TETRA_TRAIN_NORM_1 || ft == TETRA_TRAIN_NORM_2) stage_aach_pieces<TETRA_TRAIN_NORM_1>(bn, ring, mask, seq, y);
+}
+// soft value k of a staged row
+LM_FN int aach_value(const uint32_t y[kAachWords], int k) { return (int)(int8_t)(y[k >> 2] >> (8 * (k & 3))); }
+
+// corr and info in one int32 that orders codewords as the definition does: larger corr first, then the smaller info (|corr| <= 930)
+LM_FN int aach_key(int corr, uint32_t info) { return corr * 16384 + (int)(16383u - info); }
+// the two largest keys seen (best >= second): the new second is the median of (best, second, key)
+struct Top2 { int best, second; };
+constexpr int kTop2None = -0x7fffffff - 1;
+LM_FN void top2_insert(Top2& t, int key) {
+#if defined(__HIPCC__) && !defined(TETRA_HOST_EMUL)
+    int m;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(m) : "v"(t.best), "v"(t.second), "v"(key));
+    t.second = m;
+#else
+    const int lo = t.best < key ? t.best : key;
+    t.second = t.second > lo ? t.second : lo;
+#endif
+    t.best = t.best > key ? t.best : key;
+}
+// The read-out: best's information bits and codeword (word format of lmac_core.hpp's rm3014_encode), the margin to the runner-up
+// (0 = a tie) and the number of non-zero values whose sign disagrees with best.
+struct AachSoft { uint32_t info, word, dist, margin; };
+LM_FN AachSoft aach_soft_finish(const Top2& t, const uint32_t y[kAachWords]) {
+    AachSoft r;
+    r.info = 16383u - ((uint32_t)t.best & 16383u);
+    r.margin = (uint32_t)((t.best >> 14) - (t.second >> 14)) >> 1;
+    r.word = rm3014_encode(r.info);
+    uint32_t neg = 0, nz = 0;                           // value k at bit 29 - k, as the codeword's bits
+#pragma unroll
+    for (int k = 0; k < 30; ++k) {
+        const int v = aach_value(y, k);
+        neg |= (v < 0 ? 1u : 0u) << (29 - k);
+        nz |= (v != 0 ? 1u : 0u) << (29 - k);
+    }
+    r.dist = (uint32_t)__builtin_popcount((neg ^ r.word) & nz);
+    return r;
+}
+// bytes 30 and 31 of a row (dist, the margin saturated at a byte) as the top half of its last word, and the verdict
+LM_FN uint32_t aach_soft_tail(const AachSoft& r) { return (r.dist << 16) | ((r.margin < 255u ? r.margin : 255u) << 24); }
+LM_FN bool aach_soft_good(const AachSoft& r, int min_margin) { return (int)r.margin >= (min_margin < 1 ? 1 : min_margin); }
+
 }  // namespace tetra_soft

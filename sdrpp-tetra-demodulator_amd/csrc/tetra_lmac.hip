@@ -37,6 +37,7 @@
 #include "../../include/tetra_aach.h"
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/ext/tetra_list.h"
+#include "../../include/ext/tetra_aach_soft.h"
 #include "../../include/ext/tetra_soft.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
@@ -715,6 +716,133 @@ __global__ __launch_bounds__(256) void k_rm3014(const uint32_t* __restrict__ wor
     dist[i] = (uint8_t)r.dist;
 }
 
+// ---- the AACH from soft values: exact maximum-likelihood decoding (include/ext/tetra_aach_soft.h; lane code: soft_core.hpp) --------------
+// corr[codeword][block] = sum over k of (+-1)[codeword][k] * y[k][block] is a 16384 x 32 (30 padded) by 32 x blocks integer product:
+// v_mfma_i32_32x32x32_i8, a wavefront per 32 blocks, 512 steps of 32 codewords each.  Operand A holds the codewords (a row of the result
+// = a codeword of the step), operand B the blocks (a column = a block), so a lane's 16 result registers are 16 codewords of ONE block,
+// its own (column = lane & 31; rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)), and the running best two need no lane crossing until the
+// end, where the two lanes of a block merge.  Both operands give lane (r, h = lane >> 5) element j the same k = 16 h + j of their row r,
+// so the products pair up whichever k the hardware gives that element.
+// The +-1 matrix is never in memory.  The code is linear: codeword(32 t + r) = codeword(32 t) ^ codeword(r), and in bytes of +-1 (0x01 /
+// 0xff) a flipped sign is an XOR with 0xfe.  A lane keeps the 16 bytes of codeword(r) and XORs step t's 16 flip bytes of its half onto
+// them: `flip` [512][2] x 16 B = 16 KB of LDS, which the workgroup fills from the generator on entry.
+// Per product the epilogue is three vector instructions: key = corr << 14 + 32 (511 - t) (the step's share of 16383 - info, a scalar),
+// second = med3(best, second, key), best = max(best, key), one (best, second) pair per result register; the row's share of the key, 31 - row, is
+// added once behind the loop.  The next step's MFMA is issued in front of a step's epilogue.
+// A workgroup is four wavefronts = 128 blocks sharing the flip table: 16 KB of LDS and four wave slots, which is what k_fused leaves on a
+// compute unit.
+typedef int AachV4 __attribute__((ext_vector_type(4)));
+typedef int AachV16 __attribute__((ext_vector_type(16)));
+constexpr int kAachWaveRows = 32;
+constexpr int kAachGroupThreads = 256;
+constexpr int kAachGroupRows = kAachWaveRows * kAachGroupThreads / kLanes;          // 128: the kernel's row tile
+constexpr int kAachSteps = 16384 / 32;
+typedef uint4 AachFlip[kAachSteps][2];
+
+// the +-1 bytes' flip masks of a codeword's bits 16 h .. 16 h + 15 (cw: first bit on air at bit 31); bits 30, 31 are no part of it
+__device__ __forceinline__ uint4 aach_flip_bytes(uint32_t cw, int h) {
+    const uint32_t half = (cw << (16 * h)) >> 16;
+    return uint4{ tetra_soft::nibble_mask((half >> 12) & 0xfu) & 0xfefefefeu, tetra_soft::nibble_mask((half >> 8) & 0xfu) & 0xfefefefeu,
+                  tetra_soft::nibble_mask((half >> 4) & 0xfu) & 0xfefefefeu, tetra_soft::nibble_mask(half & 0xfu) & 0xfefefefeu };
+}
+__device__ __forceinline__ void aach_fill_flip(AachFlip& flip) {
+    for (int e = (int)threadIdx.x; e < 2 * kAachSteps; e += kAachGroupThreads)
+        flip[e >> 1][e & 1] = aach_flip_bytes(rm3014_encode(32u * (uint32_t)(e >> 1)) << 2, e & 1);
+}
+__device__ __forceinline__ AachV16 aach_step(const uint4& a0, const uint4& m, const AachV4& b) {
+    const AachV4 a = { (int)(a0.x ^ m.x), (int)(a0.y ^ m.y), (int)(a0.z ^ m.z), (int)(a0.w ^ m.w) };
+    const AachV16 zero = {};
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, zero, 0, 0, 0);
+}
+// the best two keys (soft_core.hpp aach_key) of the lane's block, lane & 31 of the wavefront's 32, over all codewords; y: its staged row
+__device__ __forceinline__ tetra_soft::Top2 aach_search(const uint32_t y[tetra_soft::kAachWords], const AachFlip& flip) {
+    using namespace tetra_soft;
+    const int lane = (int)threadIdx.x & (kLanes - 1), h = lane >> 5;
+    const uint4 f0 = aach_flip_bytes(rm3014_encode((uint32_t)(lane & 31)) << 2, h);
+    const uint4 a0 = { f0.x ^ 0x01010101u, f0.y ^ 0x01010101u, f0.z ^ 0x01010101u, f0.w ^ 0x01010101u };
+    const AachV4 b = { (int)y[4 * h], (int)y[4 * h + 1], (int)y[4 * h + 2], (int)y[4 * h + 3] };
+    Top2 slot[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) slot[r] = Top2{ kTop2None, kTop2None };
+    AachV16 acc = aach_step(a0, flip[0][h], b);
+#pragma unroll 2
+    for (int t = 0; t < kAachSteps; ++t) {
+        const AachV16 next = aach_step(a0, flip[t + 1 < kAachSteps ? t + 1 : t][h], b);       // (the last one is not used)
+        const int step_key = 32 * (kAachSteps - 1 - t);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) top2_insert(slot[r], (int)(((uint32_t)acc[r] << 14) + (uint32_t)step_key));
+        acc = next;
+    }
+    Top2 top{ kTop2None, kTop2None };
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row_key = 31 - ((r & 3) + 8 * (r >> 2) + 4 * h);
+        top2_insert(top, slot[r].best + row_key);
+        top2_insert(top, slot[r].second + row_key);          // (same register: same row)
+    }
+    const int ob = __shfl_xor(top.best, 32), os = __shfl_xor(top.second, 32);
+    top2_insert(top, ob);
+    top2_insert(top, os);
+    return top;
+}
+
+// the bare primitive (tetra_lmac_rm3014_soft_decode_device)
+__global__ __launch_bounds__(kAachGroupThreads) void k_aach_soft(const int8_t* __restrict__ soft, int n, int soft_stride, uint32_t* __restrict__ out_words,
+                                                                 uint8_t* __restrict__ dist, uint16_t* __restrict__ margin) {
+    using namespace tetra_soft;
+    __shared__ AachFlip flip;
+    aach_fill_flip(flip);
+    __syncthreads();
+    const int lane = (int)threadIdx.x & (kLanes - 1);
+    const int blk0 = ((int)blockIdx.x * (kAachGroupThreads / kLanes) + (int)threadIdx.x / kLanes) * kAachWaveRows;
+    if (blk0 >= n) return;
+    const int blk = blk0 + (lane & 31);
+    uint32_t y[kAachWords];
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(soft + (size_t)(blk < n ? blk : blk0) * soft_stride);
+#pragma unroll
+    for (int g = 0; g < kAachWords; ++g) y[g] = row[g];
+    y[kAachWords - 1] &= 0x0000ffffu;
+    const Top2 top = aach_search(y, flip);
+    if (lane < kAachWaveRows && blk < n) {
+        const AachSoft r = aach_soft_finish(top, y);
+        if (out_words) out_words[blk] = r.word;
+        if (dist) dist[blk] = (uint8_t)r.dist;
+        if (margin) margin[blk] = (uint16_t)r.margin;
+    }
+}
+
+// a soft BBK job of the frame decoder (TETRA_LMAC_JOB_RM3014_SOFT): the staging of soft_core.hpp's aach_soft_block in front of the search,
+// rows, verdicts and labels behind it as k_lmac_frames writes a BBK job's
+__global__ __launch_bounds__(kAachGroupThreads) void k_aach_soft_frames(const DevJob J, const DevFrames src, const uint32_t* __restrict__ seq_tab,
+                                                                        const uint32_t* __restrict__ ring, uint32_t ring_words, int min_margin) {
+    using namespace tetra_soft;
+    __shared__ AachFlip flip;
+    aach_fill_flip(flip);
+    __syncthreads();
+    const int lane = (int)threadIdx.x & (kLanes - 1);
+    const int blk0 = ((int)blockIdx.x * (kAachGroupThreads / kLanes) + (int)threadIdx.x / kLanes) * kAachWaveRows;
+    int n = J.n_rows;
+    if (J.n_rows_dev) {
+        const int have = *J.n_rows_dev;
+        n = have < n ? have : n;
+    }
+    if (blk0 >= n) return;
+    const int blk = blk0 + (lane & 31);
+    const FrameRef fr = frame_lookup(J.row_frame[blk < n ? blk : blk0], src.n_frames, J.frame_scramb);
+    uint32_t y[kAachWords];
+    aach_soft_block(fr.code, [&] { return src.bitnum[fr.f]; }, [&] { return src.frame_type[fr.f]; }, seq_rows(seq_tab),
+                    ring_of(ring, ring_words, fr.f / src.frames_per_channel), ring_words, y);
+    const Top2 top = aach_search(y, flip);
+    if (lane < kAachWaveRows && blk < n) {
+        const AachSoft r = aach_soft_finish(top, y);
+        const uint32_t bits = r.word << 2, tail = aach_soft_tail(r);
+        demux_core::U2* dst = reinterpret_cast<demux_core::U2*>(J.out + (size_t)blk * J.out_stride);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dst[k] = demux_core::U2{ bbk_bytes(bits, 2 * k), bbk_bytes(bits, 2 * k + 1) | (k == 3 ? tail : 0u) };
+        write_verdict(J, src, blk, fr.f, aach_soft_good(r, min_margin));
+    }
+}
+
 // The SB1 tracking rule, every entry point's: the SYNC-PDU read-out of tp_sap_udata_ind's SB1 case (tetra_lower_mac.c:246-275, with the
 // copy of the PHY time into tcd->time at :172) plus the PHY's TDMA clock (tetra_burst_sync.c:113, tetra_tdma.c:28-78), per channel,
 // frame slots in time order:
@@ -950,10 +1078,16 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     long long groups_total = 0, scratch_words = 0;
     int n = 0, max_pairs = 0;
     bool any_rm = false;
+    DevJob aach[TETRA_LMAC_MAX_JOBS];
+    int aach_min_margin[TETRA_LMAC_MAX_JOBS], n_aach = 0;
     for (int i = 0; i < n_jobs; ++i) {
         tetra_lmac_job_t j = jobs[i];
         const bool rm = j.type == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014);       // (the flag on any other type: refused below)
-        if (rm) j.type = TETRA_TPSAP_T_BBK;
+        // the AACH by maximum likelihood on the ring's values (tetra_aach_soft.h): the soft entry point's alone, min_margin in bits 16..25
+        const bool ml = j.type >= 0 && (j.type & ~TETRA_LMAC_JOB_AACH_MIN_MARGIN(0x3ff)) == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014_SOFT);
+        const int min_margin = ml ? (j.type >> 16) & 0x3ff : 0;
+        if (ml && (!soft || min_margin > TETRA_AACH_SOFT_MAX_MARGIN)) return TETRA_ERR_ARG;
+        if (rm || ml) j.type = TETRA_TPSAP_T_BBK;
         if (j.type < 0 || j.type > 5 || j.max_rows < 0) return TETRA_ERR_ARG;
         uint32_t* const job_counts = opts.d_biterr ? opts.d_biterr[i] : nullptr;
         if (job_counts && j.type == TETRA_TPSAP_T_BBK) return TETRA_ERR_ARG;       // the AACH is not convolutionally coded
@@ -969,10 +1103,18 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
         if (layout == kLayoutNone) return TETRA_ERR_ARG;       // no burst type carries this (kind, block number)
         const BlkParam& p = blk_param(j.type);
         const bool bbk = layout == kLayoutBbk || layout == kLayoutBbkRm;
-        if (soft && bbk) return TETRA_ERR_ARG;                 // the AACH has no soft route
+        if (soft && bbk && !ml) return TETRA_ERR_ARG;          // the AACH's hard bits are not in the ring: its soft route is the flag above
         any_rm = any_rm || rm;
         if (j.out_stride < (bbk ? 32 : p.type2)) return TETRA_ERR_SIZE;
         if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
+        if (ml) {                                              // a launch of its own behind the decode launch: not in the job table
+            DevJob& d = aach[n_aach];
+            d = DevJob{};
+            d.row_frame = j.d_row_frame; d.n_rows_dev = j.d_n_rows; d.frame_scramb = j.d_frame_scramb; d.out = j.d_type2; d.crc_ok = j.d_crc_ok;
+            d.labels = j.d_labels; d.n_rows = j.max_rows; d.out_stride = j.out_stride; d.layout = kLayoutBbk;
+            aach_min_margin[n_aach++] = min_margin;
+            continue;
+        }
         counts.out[n] = job_counts;
         ranks[n] = job_rank;
         any_counts = any_counts || job_counts;
@@ -997,10 +1139,18 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
         if (groups_total > 0x7fffffffLL) return TETRA_ERR_SIZE;
     }
     tab.n = n;
-    if (n == 0) return TETRA_OK;
+    if (n == 0 && n_aach == 0) return TETRA_OK;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const uint32_t* seq = seq_table();
     if (!seq) return TETRA_ERR_NOMEM;
+    // the soft AACH jobs, each a launch of its own (they are queued behind the decode launch: see the end of the function)
+    auto launch_aach = [&]() -> int {
+        for (int k = 0; k < n_aach; ++k)
+            hipLaunchKernelGGL(k_aach_soft_frames, dim3((unsigned)(((long long)aach[k].n_rows + kAachGroupRows - 1) / kAachGroupRows)), dim3(kAachGroupThreads), 0, s,
+                               aach[k], tab.src, seq, reinterpret_cast<const uint32_t*>(soft->d_ring), soft->size / 4u, aach_min_margin[k]);
+        return n_aach && hipGetLastError() != hipSuccess ? TETRA_ERR_HIP : TETRA_OK;
+    };
+    if (n == 0) return launch_aach();
     const size_t bytes = (size_t)scratch_words * sizeof(uint32_t);
     ScratchLease scratch;
     if (const int err = scratch_words ? scratch.take(bytes, src->d_workspace, src->workspace_bytes, s) : TETRA_OK) return err;
@@ -1033,7 +1183,8 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     if (soft) { rt.ring = reinterpret_cast<const uint32_t*>(soft->d_ring); rt.ring_words = soft->size / 4u; }
     const int list_rc = launch_list(soft ? kFrontSoft : kFrontFrames, rt, s, opts.list_work.d_work, opts.list_work.bytes);
     const int launch_rc = scratch.launched();
-    return list_rc != TETRA_OK ? list_rc : launch_rc;
+    const int aach_rc = launch_aach();
+    return list_rc != TETRA_OK ? list_rc : launch_rc != TETRA_OK ? launch_rc : aach_rc;
 }
 
 extern "C" {
@@ -1078,6 +1229,17 @@ int tetra_lmac_rm3014_decode_device(const uint32_t* d_words, int n, uint32_t* d_
     if (!rm_tab) return TETRA_ERR_NOMEM;
     hipLaunchKernelGGL(k_rm3014, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_words, n, d_out_words, d_dist,
                        rm_tab);
+    return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
+}
+
+int tetra_lmac_rm3014_soft_decode_device(const int8_t* d_soft, int n, int soft_stride, uint32_t* d_out_words, uint8_t* d_dist, uint16_t* d_margin,
+                                         void* hip_stream) {
+    if (n < 0) return TETRA_ERR_ARG;
+    if (n == 0) return TETRA_OK;
+    if (!d_soft || soft_stride < 32) return TETRA_ERR_ARG;
+    if (((uintptr_t)d_soft & 3) || (soft_stride & 3) || ((uintptr_t)d_out_words & 3) || ((uintptr_t)d_margin & 1)) return TETRA_ERR_ALIGN;
+    hipLaunchKernelGGL(k_aach_soft, dim3((unsigned)(((long long)n + kAachGroupRows - 1) / kAachGroupRows)), dim3(kAachGroupThreads), 0,
+                       static_cast<hipStream_t>(hip_stream), d_soft, n, soft_stride, d_out_words, d_dist, d_margin);
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/tetra_aach.h"
+#include "../../include/ext/tetra_aach_soft.h"
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/ext/tetra_handover.h"
 #include "../../include/ext/tetra_list.h"
@@ -209,6 +210,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         const KindBufs& r = h->res[b][k];
         tetra_lmac_job_t j = {};
         j.type = ki.tpsap | (k == TETRA_RX_KIND_BBK && h->aach_rm ? TETRA_LMAC_JOB_RM3014 : 0);
+        if (k == TETRA_RX_KIND_BBK && h->aach_soft) j.type |= TETRA_LMAC_JOB_RM3014_SOFT | TETRA_LMAC_JOB_AACH_MIN_MARGIN(h->aach_min_margin);
         j.blk_num = ki.blk;
         j.d_row_frame = r.row_frame;
         j.d_n_rows = r.n_rows;
@@ -239,9 +241,9 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
             ranks[nj] = h->res[b][k].rank;
             jobs[nj++] = job_of(k, true);
         }
-    if (h->soft) {      // the coded kinds from the ring; the AACH from the packed frames as ever, a launch of its own
+    if (h->soft) {      // the coded kinds from the ring; the AACH in a launch of its own: from the packed frames as ever, or -- TETRA_RX_FLAG_AACH_SOFT -- from the ring too
         TETRA_TRY(lmac_impl::decode_frames(&src, jobs, nj, opts, s));
-        opts.soft = nullptr;
+        if (!h->aach_soft) opts.soft = nullptr;
         nj = 0;
         if (h->kinds & (1 << TETRA_RX_KIND_BBK)) {
             counts[nj] = nullptr;
@@ -395,8 +397,10 @@ int tetra_rx_type1_bits(int kind) {
 int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     if (!cfg || !out) return TETRA_ERR_ARG;
     *out = nullptr;
-    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR | TETRA_RX_FLAG_SYNC_TOLERANT | TETRA_RX_FLAG_LIST)))
+    if ((cfg->kinds & ~((1 << TETRA_RX_N_KINDS) - 1)) || (cfg->flags & ~(TETRA_RX_FLAG_ONE_STREAM | TETRA_RX_FLAG_AACH_RM3014 | TETRA_RX_FLAG_SOFT | TETRA_RX_FLAG_BITERR | TETRA_RX_FLAG_SYNC_TOLERANT | TETRA_RX_FLAG_LIST | TETRA_RX_FLAG_AACH_SOFT)))
         return TETRA_ERR_ARG;
+    // the AACH's soft decoding reads the soft ring, and a BBK row is decoded one way
+    if ((cfg->flags & TETRA_RX_FLAG_AACH_SOFT) && (!(cfg->flags & TETRA_RX_FLAG_SOFT) || (cfg->flags & TETRA_RX_FLAG_AACH_RM3014))) return TETRA_ERR_ARG;
     std::unique_ptr<tetra_rx> h(new (std::nothrow) tetra_rx());      // everything it holds is released on every failure below
     if (!h) return TETRA_ERR_NOMEM;
     h->cfg = *cfg;
@@ -405,6 +409,7 @@ int tetra_rx_create(const tetra_rx_config_t* cfg, tetra_rx_t** out) {
     h->one_stream = (cfg->flags & TETRA_RX_FLAG_ONE_STREAM) != 0;
     h->aach_rm = (cfg->flags & TETRA_RX_FLAG_AACH_RM3014) != 0;
     h->soft = (cfg->flags & TETRA_RX_FLAG_SOFT) != 0;
+    h->aach_soft = (cfg->flags & TETRA_RX_FLAG_AACH_SOFT) != 0;
     h->biterr = (cfg->flags & TETRA_RX_FLAG_BITERR) != 0;
     h->list = (cfg->flags & TETRA_RX_FLAG_LIST) != 0;
     h->list_T = TETRA_LIST_DEFAULT_CANDIDATES;
@@ -590,6 +595,31 @@ int tetra_rx_fetch(tetra_rx_t* h, int which, int kind, tetra_rx_block_t* blocks,
 
 int tetra_rx_fetch_aach_dist(tetra_rx_t* h, int which, uint8_t* dist, int capacity, int* n_rows) {
     return fetch_col(h, which, TETRA_RX_KIND_BBK, COL_AACH_DIST, dist, capacity, n_rows);
+}
+
+// the chain's share of ext/tetra_aach_soft.h
+int tetra_rx_set_aach_min_margin(tetra_rx_t* h, int min_margin) {
+    if (!h) return TETRA_ERR_ARG;
+    if (!h->aach_soft) return TETRA_ERR_UNSUPPORTED;
+    if (min_margin < 1 || min_margin > TETRA_AACH_SOFT_MAX_MARGIN) return TETRA_ERR_ARG;
+    h->aach_min_margin = min_margin;
+    return TETRA_OK;
+}
+
+// byte 31 of the BBK rows, packed on the device as the distance is and widened on the host
+int tetra_rx_fetch_aach_margin(tetra_rx_t* h, int which, uint16_t* margin, int capacity, int* n_rows) {
+    if (!h || !n_rows || which < 0 || which > 1 || capacity < 0) return TETRA_ERR_ARG;
+    if (!h->aach_soft) return TETRA_ERR_UNSUPPORTED;
+    TETRA_TRY(row_col::status(h, COL_AACH_DIST, TETRA_RX_KIND_BBK));
+    return fetch_rows(h, which, TETRA_RX_KIND_BBK, margin != nullptr, capacity, n_rows, [&](const KindBufs& r, int n) -> int {
+        std::vector<uint8_t> bytes((size_t)n);
+        TETRA_TRY(fetch_packed(h, bytes.data(), (size_t)n, [&](uint8_t* stage) {
+            hipLaunchKernelGGL(k_rx_pack_byte, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->fetch_s, r.t2.get(), kKinds[TETRA_RX_KIND_BBK].out_stride,
+                               kAachMarginByte, n, stage);
+        }));
+        for (int j = 0; j < n; ++j) margin[j] = bytes[(size_t)j];
+        return TETRA_OK;
+    });
 }
 
 // the chain's share of tetra_biterr.h

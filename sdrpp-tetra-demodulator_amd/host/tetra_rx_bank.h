@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "ext/tetra_aach_soft.h"
 #include "ext/tetra_biterr.h"
 #include "ext/tetra_handover.h"
 #include "ext/tetra_list.h"
@@ -205,6 +206,17 @@ public:
     // ... and the rank of a coded kind's rows, in fetch()'s order: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k,
     // -1 = failed and not rescued
     int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) { return column(tetra_rx_fetch_list_rank, kind, out, which); }
+    // TETRA_RX_FLAG_AACH_SOFT (ext/tetra_aach_soft.h): the margin (1..930) from which a maximum-likelihood AACH row is accepted, from the
+    // next call on ...
+    int setAachMinMargin(int minMargin) { return tetra_rx_set_aach_min_margin(h_, minMargin); }
+    // ... and the margin of every BBK row (saturated at 255; 0 = a tie), in fetch()'s order
+    int fetchAachMargin(std::vector<uint16_t>& out, int which = 0) {
+        int n = 0;
+        const int rc = tetra_rx_fetch_aach_margin(h_, which, nullptr, 0, &n);
+        if (rc != TETRA_OK) return rc;
+        out.resize((size_t)n);
+        return n ? tetra_rx_fetch_aach_margin(h_, which, out.data(), n, &n) : TETRA_OK;
+    }
     int syncStates(std::vector<tetra_bsync_state_t>& out) { return table(tetra_rx_get_sync_state, out); }
     // The synchroniser's tolerant lock (ext/tetra_sync_tol.h; TETRA_RX_FLAG_SYNC_TOLERANT creates the chain with {3, 5, 16}): tol = null
     // returns to the reference's rule.  Between process calls; waits for the tail in flight.
@@ -348,6 +360,10 @@ public:
     int setListCandidates(int maxCandidates) { return each([&](Shard& s) { return s.bank.setListCandidates(maxCandidates); }); }
     int fetchListRank(int kind, std::vector<int32_t>& out, int which = 0) {
         return gather(out, [&](TetraRxBank& b, auto& part) { return b.fetchListRank(kind, part, which); });
+    }
+    int setAachMinMargin(int minMargin) { return each([&](Shard& s) { return s.bank.setAachMinMargin(minMargin); }); }
+    int fetchAachMargin(std::vector<uint16_t>& out, int which = 0) {
+        return gather(out, [&](TetraRxBank& b, auto& part) { return b.fetchAachMargin(part, which); });
     }
     int links(std::vector<tetra_rx_link_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.links(part); }); }
     // Retune with a donor (ext/tetra_handover.h), in the bank's channel numbers: every shard is told its own entries.  Nothing crosses

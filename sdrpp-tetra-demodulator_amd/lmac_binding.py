@@ -9,6 +9,8 @@ from .binding import load_library
 
 JOB_RM3014 = 0x100            # TETRA_LMAC_JOB_RM3014: OR into a BBK job's type for decode_frames_device
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
+JOB_RM3014_SOFT = 0x200       # TETRA_LMAC_JOB_RM3014_SOFT: OR into a BBK job's type for decode_frames_soft (include/ext/tetra_aach_soft.h)
+AACH_SOFT_MAX_MARGIN = 930    # TETRA_AACH_SOFT_MAX_MARGIN
 # enum tp_sap_data_type (src/decoder/src/phy/tetra_burst.h:9-16)
 TPSAP_T_SB1, TPSAP_T_SB2, TPSAP_T_NDB, TPSAP_T_BBK, TPSAP_T_SCH_HU, TPSAP_T_SCH_F = range(6)
 
@@ -73,15 +75,20 @@ LIST_MAX_CANDIDATES, LIST_DEFAULT_CANDIDATES = 8, 4            # TETRA_LIST_MAX_
 SOFT_ABI = {
     "tetra_lmac_decode_frames_soft_device": (i32, [P(Frames), P(Job), i32, vp, u32, P(vp), P(vp), i32, vp]),
 }
+# include/ext/tetra_aach_soft.h: the lower MAC's share (the receive chain's is in rx_binding.AACH_SOFT_ABI)
+AACH_SOFT_ABI = {
+    "tetra_lmac_rm3014_soft_decode_device": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+}
 LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
 SOFT_EXPORTS = list(SOFT_ABI)
+AACH_SOFT_EXPORTS = list(AACH_SOFT_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI},
-                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI},
+                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS)
 
 
 def force_byte_route(on):
@@ -262,3 +269,16 @@ def decode_aach_rm3014_device(d_type5, n_blocks, in_stride, d_scramb, d_type2, o
     descrambler; rows of >= 32 bytes out (30 bits, the distance, a zero)."""
     call(_lib().tetra_lmac_decode_aach_rm3014_device, ptr(d_type5), int(n_blocks), int(in_stride), ptr(d_scramb), ptr(d_type2),
          int(out_stride), ptr(d_crc_ok), stream_ptr(stream))
+
+
+def job_aach_min_margin(m):
+    """TETRA_LMAC_JOB_AACH_MIN_MARGIN(m): OR into the type of a TPSAP_T_BBK | JOB_RM3014_SOFT job; min_margin 1..930, 0 = absent = 1."""
+    return (int(m) & 0x3ff) << 16
+
+
+def rm3014_soft_decode(d_soft, n, soft_stride, d_out_words=None, d_dist=None, d_margin=None, stream=None):
+    """tetra_lmac_rm3014_soft_decode_device (include/ext/tetra_aach_soft.h): torch tensors on the GPU -- int8 [n][soft_stride] soft values
+    (30 of a row used, soft_stride >= 32) in; the maximum-likelihood codeword (int32 / uint32 [n]), the number of disagreeing non-zero
+    values (uint8 [n]) and the margin to the runner-up (int16 / uint16 [n]) out, any of them None."""
+    call(_lib().tetra_lmac_rm3014_soft_decode_device, ptr(d_soft), int(n), int(soft_stride), ptr(d_out_words), ptr(d_dist), ptr(d_margin),
+         stream_ptr(stream))

@@ -17,6 +17,7 @@ FLAG_SOFT = 8                 # TETRA_RX_FLAG_SOFT: the coded kinds decoded from
 FLAG_BITERR = 32              # TETRA_RX_FLAG_BITERR: channel bit-error counts per coded block, link figures per channel (tetra_biterr.h)
 FLAG_LIST = 512               # TETRA_RX_FLAG_LIST: CRC-aided list decoding of the CRC-failed coded blocks (ext/tetra_list.h)
 FLAG_SYNC_TOLERANT = 128      # TETRA_RX_FLAG_SYNC_TOLERANT: the synchroniser's tolerant lock with {3, 5, 16} (ext/tetra_sync_tol.h)
+FLAG_AACH_SOFT = 1024         # TETRA_RX_FLAG_AACH_SOFT: the AACH by maximum likelihood on the soft values (ext/tetra_aach_soft.h); needs FLAG_SOFT
 AACH_UNDECODABLE = 0xFF       # TETRA_AACH_UNDECODABLE
 
 
@@ -94,6 +95,11 @@ LIST_ABI = {
     "tetra_rx_fetch_list_rank": (i32, [vp, i32, i32, vp, i32, P(i32)]),
     "tetra_rx_list_rank_device": (i32, [vp, i32, i32, P(vp), vp]),
 }
+# include/ext/tetra_aach_soft.h (the AACH by maximum likelihood on the soft values): the chain's share
+AACH_SOFT_ABI = {
+    "tetra_rx_set_aach_min_margin": (i32, [vp, i32]),
+    "tetra_rx_fetch_aach_margin": (i32, [vp, i32, vp, i32, P(i32)]),
+}
 # include/ext/tetra_handover.h (a restarted channel inherits frame timing, cell and clock from a donor): the chain's share
 class HandoverParams(C.Structure):
     _fields_ = [("window", C.c_int32), ("max_slots", C.c_int32)]
@@ -150,9 +156,9 @@ RX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
     return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
-                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI},
+                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI, **AACH_SOFT_ABI},
                    optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
-                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS)
+                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS + list(AACH_SOFT_ABI))
 
 
 def type1_bits(kind):
@@ -253,8 +259,19 @@ class RxChain:
 
     def fetch_aach_dist(self, which=0):
         """tetra_rx_fetch_aach_dist: uint8 [n], byte 30 of every BBK row in fetch(KIND_BBK)'s order -- the Hamming distance 0..3 the
-        RM(30,14) decoder corrected, or AACH_UNDECODABLE.  Needs a handle created with FLAG_AACH_RM3014."""
+        RM(30,14) decoder corrected, or AACH_UNDECODABLE; with FLAG_AACH_SOFT the non-zero soft values that disagree with the
+        maximum-likelihood codeword.  Needs a handle created with FLAG_AACH_RM3014 or FLAG_AACH_SOFT."""
         return self._count_then_fetch(self._lib.tetra_rx_fetch_aach_dist, np.uint8, which)
+
+    def set_aach_min_margin(self, min_margin):
+        """tetra_rx_set_aach_min_margin: the margin (1..930) from which the calls that follow accept a maximum-likelihood AACH row.
+        Needs a handle created with FLAG_AACH_SOFT."""
+        call(self._lib.tetra_rx_set_aach_min_margin, self._h, int(min_margin))
+
+    def fetch_aach_margin(self, which=0):
+        """tetra_rx_fetch_aach_margin: uint16 [n], byte 31 of every BBK row in fetch(KIND_BBK)'s order -- the margin of the
+        maximum-likelihood codeword to the runner-up, saturated at 255 (0: a tie).  Needs a handle created with FLAG_AACH_SOFT."""
+        return self._count_then_fetch(self._lib.tetra_rx_fetch_aach_margin, np.uint16, which)
 
     def fetch_biterr(self, kind, which=0):
         """tetra_rx_fetch_biterr: (errors, compared) int arrays [n] of a coded kind's rows, in fetch(kind)'s order -- the distance from

@@ -259,6 +259,15 @@ class WidebandRx:
         """The carrier slots' miss counters (RxChain.sync_misses of the chain).  A retune zeroes a moved slot's."""
         return self.rx.sync_misses(first, count)
 
+    def set_aach_min_margin(self, min_margin):
+        """The margin from which the carrier slots' maximum-likelihood AACH rows are accepted (RxChain.set_aach_min_margin of the chain;
+        needs FLAG_SOFT | FLAG_AACH_SOFT in `flags`)."""
+        self.rx.set_aach_min_margin(min_margin)
+
+    def fetch_aach_margin(self, which=0):
+        """The AACH rows' margins (RxChain.fetch_aach_margin of the chain)."""
+        return self.rx.fetch_aach_margin(which)
+
     def bin_power(self):
         out = np.zeros(self.M, np.float32)
         call(self._lib.tetra_wbrx_bin_power, self._h, ptr(out))
