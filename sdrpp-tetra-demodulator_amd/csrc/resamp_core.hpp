@@ -17,9 +17,15 @@
 // (PickColumns below): every output float is the same fma chain over the same coefficients as the full resampler's, so a picked
 // column equals that column of the full resampler bit for bit.
 //
+// A carrier that lies off its bin's centre is mixed down in the same pass (MixColumns below, include/ext/tetra_carrier_offset.h):
+// each row is rotated once, as it is loaded, by a phasor whose phase is formed in integer arithmetic.
+//
 // Compiles for the host as well (tests/emul/resamp_emul.cpp runs every thread of a launch against the double-precision definition,
-// and the picking variant against the full one).
+// and the picking variant against the full one; tests/emul/resamp_mix_emul.cpp does the same for the mixing variant).
 #pragma once
+
+#include <cmath>
+#include <cstddef>
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define RESAMP_HD __host__ __device__ __forceinline__
@@ -68,12 +74,17 @@ template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row_at(const 
 }
 
 // Which input column a lane unit reads.  A column map hands each lane a `lane` object whose row() reads the lane's unit of a row.
+// A lane may also rotate what it reads: phasor(a0) is what it keeps for a run of rows that starts at absolute frame a0, mixed(v, p, k)
+// the row k frames behind a0 as it enters the sums.  AllColumns and PickedLane rotate nothing (NoPhasor: no state, no instruction).
+struct NoPhasor {};
 // AllColumns (the resampler, tetra_resamp.hip): unit u of rows of c.units units, in the new frames, the delay line and the output.
 struct AllColumns {
     RESAMP_HD AllColumns lane(const Ctx&, int) const { return *this; }
     template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row(const Ctx& c, long long rel, int u, int T) const {
         return row_at<W, CAREFUL>(c, rel, u, T);
     }
+    RESAMP_HD NoPhasor phasor(long long) const { return NoPhasor(); }
+    template <class V> RESAMP_HD V mixed(const V& v, NoPhasor, int) const { return v; }
 };
 // PickColumns (the wideband receiver, tetra_wbrx.hip): the new frames are a channeliser's rows of in_units units, of which unit u
 // reads column col[u] (one channel per unit: W = 2); the delay line and the output hold the picked columns only (rows of c.units =
@@ -90,11 +101,64 @@ struct PickedLane {
         }
         return reinterpret_cast<const V*>(c.x)[(rel < c.n_in ? rel : c.n_in - 1) * stride + col];
     }
+    RESAMP_HD NoPhasor phasor(long long) const { return NoPhasor(); }
+    template <class V> RESAMP_HD V mixed(const V& v, NoPhasor, int) const { return v; }
 };
 struct PickColumns {
     const int* col;        // [c.units], each in [0, in_units)
     int in_units;
     RESAMP_HD PickedLane lane(const Ctx&, int u) const { return PickedLane{(long long)in_units, col[u]}; }
+};
+
+// MixColumns (the wideband receiver's per-carrier offsets, include/ext/tetra_carrier_offset.h): PickColumns whose unit u is rotated by
+// exp(-j 2 pi (inc[u] n mod 2^32) / 2^32), n = the row's absolute frame index, before it enters the sums -- the delay line and the
+// new frames hold un-rotated rows.  No phase is carried from row to row or from call to call: a run of rows (a group's kRows, a
+// generic output's T) takes ONE phasor from the exact integer phase of its first row a0, (inc a0) mod 2^32, and row a0 + k is
+// rotated by that phasor times step[k] = exp(-j 2 pi (inc k mod 2^32) / 2^32), a table per slot that the host fills in double when
+// the offsets are set (step_table).  The coefficients stay wave-uniform scalars; phasor, steps and products are the lane's own.
+struct Phasor { float re, im; };
+// exp(-j 2 pi ph / 2^32): the quadrant is taken off in integers (exact), the rest, at most an eighth of a turn either way, goes
+// through two short polynomials (Cephes' sinf / cosf kernels; 1.2e-7 at worst with the float32 roundings around them).  ph = 0 gives exactly (1, 0).
+RESAMP_HD Phasor phasor_of(unsigned ph) {
+    RESAMP_FP_FAST
+    const unsigned q = (ph + 0x20000000u) >> 30;
+    const int d = (int)(ph - (q << 30));                          // [-2^29, 2^29)
+    const float t = (float)d * 1.4629180792671596e-9f;            // 2 pi / 2^32
+    const float z = t * t;
+    const float s = t + t * z * (-1.6666654611e-1f + z * (8.3321608736e-3f + z * -1.9515295891e-4f));
+    const float c = 1.0f - 0.5f * z + z * z * (4.166664568298827e-2f + z * (-1.388731625493765e-3f + z * 2.443315711809948e-5f));
+    // (cos, sin) of q quarter turns + t, then the conjugate
+    const float co = (q & 1) ? ((q & 2) ? s : -s) : ((q & 2) ? -c : c);
+    const float si = (q & 1) ? ((q & 2) ? -c : c) : ((q & 2) ? -s : s);
+    return Phasor{co, -si};
+}
+struct MixedLane {
+    PickedLane pick;
+    unsigned inc;          // the slot's offset, 2^-32 cycles per frame
+    const f2* step;        // the slot's step phasors: step[k * units]
+    long long units;
+    template <int W, bool CAREFUL> RESAMP_HD typename unit_of<W>::type row(const Ctx& c, long long rel, int u, int T) const {
+        return pick.template row<W, CAREFUL>(c, rel, u, T);
+    }
+    RESAMP_HD Phasor phasor(long long a0) const { return phasor_of(inc * (unsigned)(unsigned long long)a0); }
+    RESAMP_HD f2 mixed(const f2& v, const Phasor& p, int k) const {
+        RESAMP_FP_FAST
+        const f2 s = step[k * units];
+        const float re = p.re * s.v[0] - p.im * s.v[1], im = p.re * s.v[1] + p.im * s.v[0];
+        f2 o;
+        o.v[0] = v.v[0] * re - v.v[1] * im;
+        o.v[1] = v.v[0] * im + v.v[1] * re;
+        return o;
+    }
+};
+struct MixColumns {
+    const int* col;        // [c.units], each in [0, in_units)
+    int in_units;
+    const unsigned* inc;   // [c.units]
+    const f2* step;        // [mix_rows(I, DN, T)][c.units]
+    RESAMP_HD MixedLane lane(const Ctx& c, int u) const {
+        return MixedLane{PickedLane{(long long)in_units, col[u]}, inc[u], step + u, (long long)c.units};
+    }
 };
 
 // One group of I outputs (absolute group G, i.e. outputs I G .. I G + I - 1) for lane unit u.
@@ -104,9 +168,10 @@ template <int I, int DN, int T, int W, bool CAREFUL, class Lane> RESAMP_HD void 
     constexpr int kQmax = (DN * (I - 1)) / I;            // newest row the group's last output reads
     constexpr int kRows = kQmax + T;                      // rows -(T - 1) .. kQmax relative to row DN G
     const long long base = (long long)DN * G - c.n0;      // row DN G counted from the call's first new frame
+    const auto ph = lane.phasor((long long)DN * G - (T - 1));      // (a mixing lane's; nothing for the others)
     V rows[kRows];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) rows[k] = lane.template row<W, CAREFUL>(c, base + (k - (T - 1)), u, T);
+    for (int k = 0; k < kRows; k++) rows[k] = lane.mixed(lane.template row<W, CAREFUL>(c, base + (k - (T - 1)), u, T), ph, k);
     V* const out = reinterpret_cast<V*>(c.out);
 #pragma unroll
     for (int i = 0; i < I; i++) {
@@ -162,12 +227,13 @@ template <int W, class Cols = AllColumns> RESAMP_HD void thread_generic(const Ct
     const long long q = ((long long)c.DN * m) / c.I;
     const int r = (int)((long long)c.DN * m - q * c.I);
     const auto lane = cols.lane(c, u);
+    const auto ph = lane.phasor(q - (c.T - 1));
     float acc[W];
 #pragma unroll
     for (int w = 0; w < W; w++) acc[w] = 0.f;
     for (int j = c.T - 1; j >= 0; j--) {
         const float h = c.coef[r + c.I * j];
-        const V xv = lane.template row<W, true>(c, q - j - c.n0, u, c.T);
+        const V xv = lane.mixed(lane.template row<W, true>(c, q - j - c.n0, u, c.T), ph, c.T - 1 - j);
 #pragma unroll
         for (int w = 0; w < W; w++) acc[w] += h * xv.v[w];
     }
@@ -196,6 +262,18 @@ template <class F> inline bool visit_ratio(int I, int DN, int T, F&& f) {
 inline void phase_table(const float* h, int I, int DN, int T, float* coef) {
     for (int i = 0; i < I; i++)
         for (int j = 0; j < T; j++) coef[i * T + j] = h[(DN * i) % I + I * j];
+}
+
+// The mixing lanes' step phasors.  Rows of the table: the longest run of rows one phasor serves, a group's kRows (>= T, the generic
+// kernel's run).  step[k][u] = exp(-j 2 pi (inc[u] k mod 2^32) / 2^32), in double, rounded once.
+inline int mix_rows(int I, int DN, int T) { return (int)(((long long)DN * (I - 1)) / I) + T; }
+inline void step_table(const unsigned* inc, int units, int rows, float* step) {
+    for (int k = 0; k < rows; k++)
+        for (int u = 0; u < units; u++) {
+            const double th = 6.283185307179586476925286766559 * (double)(unsigned)(inc[u] * (unsigned)k) / 4294967296.0;
+            step[2 * ((size_t)k * units + u)] = (float)std::cos(th);
+            step[2 * ((size_t)k * units + u) + 1] = (float)-std::sin(th);
+        }
 }
 
 // outputs that exist once n frames have arrived: m with floor(DN m / I) <= n - 1

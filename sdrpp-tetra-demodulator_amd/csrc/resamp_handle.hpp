@@ -13,6 +13,7 @@
 
 typedef void (*fixed_kernel_t)(resamp::Ctx, int, long long);
 typedef void (*pick_kernel_t)(resamp::Ctx, resamp::PickColumns, int, long long);
+typedef void (*mix_kernel_t)(resamp::Ctx, resamp::MixColumns, int, long long);
 
 struct tetra_resamp {
     tetra_resamp_config_t cfg;
@@ -21,6 +22,11 @@ struct tetra_resamp {
     std::vector<float> proto;
     fixed_kernel_t fixed = nullptr;
     pick_kernel_t pick = nullptr;     // the same ratio over picked columns (W = 2; resamp_impl::process_pick_device)
+    mix_kernel_t pick_mix = nullptr;  // ... and rotated by the columns' offsets (resamp_impl::set_mix)
+    // per-column offsets (include/ext/tetra_carrier_offset.h): empty until the first list that is not all zero
+    std::vector<uint32_t> inc;   // [C] the offsets in force, 2^-32 cycles per frame
+    bool mixing = false;         // some offset is non-zero: process_pick_device launches the mixing kernels
+    DevMem<uint32_t> d_mix;      // [mix_rows][C] complex64 step phasors | [C] offsets (resamp_core.hpp, MixColumns)
     DevMem<float> d_coef;        // [I][T] phase table (fixed kernel) or the prototype (generic)
     DelayLine<float> hist;       // [T - 1][2 C]: the frames before the next call's first
     long long n_total = 0;       // frames consumed so far
@@ -39,5 +45,14 @@ namespace resamp_impl {
 // device int32, each in [0, in_ch).  Same statuses and stream rules as tetra_resamp_process_device.
 __attribute__((visibility("hidden"))) int process_pick_device(tetra_resamp_t* h, const int32_t* d_cols, int in_ch, const float* d_in, int n_in,
                                                             float* d_out, int* n_out, hipStream_t s);
+
+// The per-column offsets of process_pick_device (resamp_core.hpp, MixColumns).  mix_words: 32-bit words of the device tables for C
+// columns.  mix_fill: the tables of inc [C] into words [mix_words], the step phasors in double.  set_mix: takes inc [C] as the
+// offsets in force; d_tables (device, [mix_words], filled from mix_fill's words) is copied into the handle's own tables on s -- the
+// caller orders s behind the last process call and the next one behind s.  d_tables may be null for a list that is all zero: then
+// the un-mixed kernels run again and the tables are not read.
+__attribute__((visibility("hidden"))) size_t mix_words(const tetra_resamp_t* h);
+__attribute__((visibility("hidden"))) void mix_fill(const tetra_resamp_t* h, const uint32_t* inc, int32_t* words);
+__attribute__((visibility("hidden"))) int set_mix(tetra_resamp_t* h, const uint32_t* inc, const int32_t* d_tables, hipStream_t s);
 
 }  // namespace resamp_impl

@@ -4,6 +4,8 @@
 // VFO_SAMPLERATE 36000, 2 samples per symbol (/root/reference/src/main.cpp:35,75,84).  Bound by its HBM traffic: per input frame of C
 // channels 8 C bytes are read and 8 C I / DN written (config 5, a quarter second: 80 MB + 57.6 MB); the arithmetic (2 T flop per
 // output float) is a tenth of what the vector pipes do in that time.  Thread-level code: resamp_core.hpp.
+// Picked columns may carry an offset each (include/ext/tetra_carrier_offset.h): the mixing kernels (Cols = resamp::MixColumns) are
+// launched only while some offset is non-zero; without one the launches are the ones of a handle that knows no offsets.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -71,6 +73,14 @@ pick_kernel_t pick_picked(int I, int DN, int T) {
     });
     return k;
 }
+mix_kernel_t pick_mixed(int I, int DN, int T) {
+    mix_kernel_t k = nullptr;
+    resamp::visit_ratio(I, DN, T, [&](auto r) {
+        using R = decltype(r);
+        k = (mix_kernel_t)k_resample<R::I, R::DN, R::T, 2, resamp::MixColumns>;
+    });
+    return k;
+}
 
 // Kaiser-windowed sinc at the zero-stuffed rate, cutoff fc = cutoff_rel / (2 max(I, DN)) cycles per sample there (= cutoff_rel x the
 // narrower of the input and output Nyquist bands), DC gain I.
@@ -102,7 +112,14 @@ int process_any(tetra_resamp* h, const int32_t* d_cols, int in_ch, const float* 
         else threads = n_new * (long long)h->units;
         const long long blocks = (threads + kThreads - 1) / kThreads;
         const int span = (int)((blocks + 7) / 8);
-        if (d_cols) {
+        if (d_cols && h->mixing) {
+            resamp::MixColumns cols;
+            cols.col = d_cols; cols.in_units = in_ch;
+            cols.step = reinterpret_cast<const resamp::f2*>(h->d_mix.get());
+            cols.inc = h->d_mix.get() + resamp_impl::mix_words(h) - (size_t)h->C;
+            if (h->pick_mix) hipLaunchKernelGGL(h->pick_mix, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
+            else hipLaunchKernelGGL((k_resample_generic<2, resamp::MixColumns>), dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
+        } else if (d_cols) {
             resamp::PickColumns cols;
             cols.col = d_cols; cols.in_units = in_ch;
             if (h->pick) hipLaunchKernelGGL(h->pick, dim3(8 * span), dim3(kThreads), 0, s, c, cols, span, blocks);
@@ -137,6 +154,31 @@ int process_pick_device(tetra_resamp_t* h, const int32_t* d_cols, int in_ch, con
     if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
     if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 7)) return TETRA_ERR_ALIGN;
     return process_any(h, d_cols, in_ch, d_in, n_in, d_out, n_out, s);
+}
+
+size_t mix_words(const tetra_resamp_t* h) { return (size_t)h->C * (1 + 2 * (size_t)resamp::mix_rows(h->I, h->DN, h->T)); }
+
+void mix_fill(const tetra_resamp_t* h, const uint32_t* inc, int32_t* words) {
+    const int rows = resamp::mix_rows(h->I, h->DN, h->T);
+    resamp::step_table(inc, h->C, rows, reinterpret_cast<float*>(words));
+    std::memcpy(words + 2 * (size_t)rows * h->C, inc, sizeof(uint32_t) * (size_t)h->C);
+}
+
+int set_mix(tetra_resamp_t* h, const uint32_t* inc, const int32_t* d_tables, hipStream_t s) {
+    if (!h || !inc || h->W != 2) return TETRA_ERR_ARG;
+    bool any = false;
+    for (int j = 0; j < h->C; j++) any = any || inc[j] != 0;
+    if (any && !d_tables) return TETRA_ERR_ARG;
+    if (d_tables) {
+        DeviceGuard g(h->device);
+        if (!g.ok) return TETRA_ERR_NO_DEVICE;
+        const size_t bytes = sizeof(int32_t) * mix_words(h);
+        HIP_TRY(h, h->d_mix.reserve(bytes));      // (one size for the handle's life: never grown while a kernel reads it)
+        HIP_TRY(h, hipMemcpyAsync(h->d_mix, d_tables, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    h->inc.assign(inc, inc + h->C);
+    h->mixing = any;
+    return TETRA_OK;
 }
 
 }  // namespace resamp_impl
@@ -192,6 +234,7 @@ int tetra_resamp_create(const tetra_resamp_config_t* cfg, tetra_resamp_t** out) 
     else design_prototype(h->I, h->DN, h->T, cfg->cutoff_rel, cfg->kaiser_beta, h->proto);
     h->fixed = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_fixed(h->I, h->DN, h->T, h->W);
     h->pick = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_picked(h->I, h->DN, h->T);
+    h->pick_mix = (cfg->flags & TETRA_RESAMP_FLAG_GENERIC) ? nullptr : pick_mixed(h->I, h->DN, h->T);
     DeviceGuard g(dev);
     if (!g.ok) { delete h; return TETRA_ERR_NO_DEVICE; }
     std::vector<float> coef((size_t)h->I * h->T);

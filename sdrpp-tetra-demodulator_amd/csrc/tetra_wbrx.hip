@@ -9,6 +9,9 @@
 // one channel per lane unit; resamp_impl::process_pick_device runs its kernels over picked columns (resamp_core.hpp, PickColumns).
 // A bin list 0 .. M - 1 in order runs the resampler in place on the full rows instead.  The resampled frames are double buffered by
 // call parity like the chain's bit rows, so tetra_wbrx_frames_device can hand out the previous call's too.
+//
+// Per-carrier offsets (include/ext/tetra_carrier_offset.h) are the selecting resampler's: with a non-zero one in force it rotates each
+// carrier's column as it loads it (resamp_core.hpp, MixColumns).  chan_out, the delay line and the retune ring stay un-rotated.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -16,11 +19,13 @@
 #include <new>
 #include <vector>
 
+#include "../../include/ext/tetra_carrier_offset.h"
 #include "../../include/ext/tetra_iqcond.h"
 #include "../../include/tetra_shift.h"
 #include "hip_host.hpp"
 #include "resamp_handle.hpp"
 #include "retune_core.hpp"
+#include "retune_impl.hpp"
 #include "rx_handle.hpp"
 #include "wbrx_handle.hpp"
 
@@ -55,6 +60,11 @@ __global__ __launch_bounds__(256) void k_bin_power_sum(const double* __restrict_
 __global__ __launch_bounds__(256) void k_keep_rows(const float* __restrict__ x, int M, long long n0, int n_in, int rows, int hist, float* __restrict__ ring) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < (long long)rows * M) retune::keep_element(x, M, n0, n_in, rows, hist, i, ring);
+}
+
+bool no_device() {
+    int n = 0;
+    return hipGetDeviceCount(&n) != hipSuccess || n <= 0;
 }
 
 template <typename T> bool dalloc(DevMem<T>& p, size_t count) { return p.reserve(sizeof(T) * (count ? count : 1)) == hipSuccess; }
@@ -307,6 +317,58 @@ int tetra_wbrx_set_input_map(tetra_wbrx_t* h, const tetra_iq_map_t* map) {
 int tetra_wbrx_get_input_map(tetra_wbrx_t* h, tetra_iq_map_t* map, int* is_set) {
     if (!h) return TETRA_ERR_ARG;
     return tetra_chan_get_input_map(h->chan, map, is_set);
+}
+
+// The carriers' own offsets (include/ext/tetra_carrier_offset.h) are the selecting resampler's.  Like a retune, the setter works on the
+// caller's stream between two process calls: behind the last call (ev_done), and the next call behind it (ev_done again).
+int tetra_wbrx_set_carrier_offsets(tetra_wbrx_t* h, const uint32_t* inc, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || !inc) return TETRA_ERR_ARG;
+    tetra_resamp* rs = h->rs;
+    bool same = true, any = false;
+    for (int j = 0; j < h->n_bins; j++) {
+        same = same && inc[j] == (rs->inc.empty() ? 0u : rs->inc[(size_t)j]);
+        any = any || inc[j] != 0;
+    }
+    if (same) return TETRA_OK;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (!any) return resamp_impl::set_mix(rs, inc, nullptr, s);      // the un-mixed kernels again: nothing to upload
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    std::vector<int32_t> words(resamp_impl::mix_words(rs));
+    resamp_impl::mix_fill(rs, inc, words.data());
+    // the tables in force are read by the last call's resampler: the new ones go in behind that call
+    if (h->done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+    int32_t* d_words = nullptr;
+    hipError_t e = hipSuccess;
+    const int k = h->mix_to_device.push(words.data(), (int)words.size(), (int)words.size(), s, &d_words, &e);
+    if (k < 0) HIP_TRY(h, e);
+    if (h->all) {      // from now on the selecting resampler, as after a first retune: the delay line already holds every bin in order
+        (void)retune_impl::resamp_narrow_units(rs);
+        h->all = false;
+    }
+    const int rc = resamp_impl::set_mix(rs, inc, d_words, s);
+    if (rc == TETRA_ERR_HIP) h->last_hip = rs->last_hip;
+    hipError_t late = h->mix_to_device.done(k, 0, s);
+    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
+    if (late == hipSuccess) h->done_recorded = true;
+    if (rc != TETRA_OK) return rc;
+    HIP_TRY(h, late);
+    return TETRA_OK;
+}
+
+int tetra_wbrx_get_carrier_offsets(tetra_wbrx_t* h, uint32_t* inc) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || !inc) return TETRA_ERR_ARG;
+    const tetra_resamp* rs = h->rs;
+    for (int j = 0; j < h->n_bins; j++) inc[j] = rs->inc.empty() ? 0u : rs->inc[(size_t)j];
+    return TETRA_OK;
+}
+
+// round(offset_hz . decimation / sample_rate_hz . 2^32) mod 2^32, by tetra_chan_shift_from_hz's rules
+uint32_t tetra_wbrx_carrier_offset_from_hz(double offset_hz, double sample_rate_hz, int decimation) {
+    if (decimation < 1) return 0;
+    return tetra_chan_shift_from_hz(offset_hz * (double)decimation, sample_rate_hz);
 }
 
 int tetra_wbrx_stage_ms(tetra_wbrx_t* h, float ms[2]) {

@@ -36,4 +36,6 @@ struct tetra_wbrx {
     DevMem<float> ring;                     // [T - 1][M] complex64: the channeliser's newest T - 1 frames of ALL bins, frame a in row a mod (T - 1)
     ListRing to_device;                     // a retune's moved slots and their new bins on their way to the device
     long long retunes = 0, slots_changed = 0;
+    // per-carrier offsets (include/ext/tetra_carrier_offset.h): the resampler handle holds the list in force and its device tables
+    ListRing mix_to_device;                 // a new list's tables on their way to the device
 };

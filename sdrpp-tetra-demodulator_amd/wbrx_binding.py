@@ -5,7 +5,7 @@ import functools
 import numpy as np
 
 from . import binding as B
-from ._ffi import P, call, declare, i32, i64, ptr, stream_ptr, u32, vp
+from ._ffi import P, call, declare, f64, i32, i64, ptr, stream_ptr, u32, vp
 from .binding import load_library
 from .chan_binding import ChanConfig, IqMap, _get_input_map, _set_input_map, input_map_from_stats, iq_stats
 from .rx_binding import HandoverParams, RxChain, RxConfig, handover_params_arg
@@ -51,6 +51,12 @@ IQCOND_ABI = {
 }
 # include/ext/tetra_handover.h (a moved slot inherits frame timing, cell and clock from a donor slot): the wideband receiver's share
 HANDOVER_ABI = {"tetra_wbrx_retune_from": (i32, [vp, vp, vp, P(HandoverParams), vp])}
+# include/ext/tetra_carrier_offset.h (an offset per carrier slot, mixed out in the selecting resampler)
+CARRIER_OFFSET_ABI = {
+    "tetra_wbrx_set_carrier_offsets": (i32, [vp, vp, vp]),
+    "tetra_wbrx_get_carrier_offsets": (i32, [vp, vp]),
+    "tetra_wbrx_carrier_offset_from_hz": (u32, [f64, f64, i32]),
+}
 WBRX_EXPORTS, WBRX_SHIFT_EXPORTS, WBRX_RETUNE_EXPORTS = list(SIGNATURES), list(SHIFT_SIGNATURES), list(RETUNE_SIGNATURES)
 WBRX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 
@@ -58,8 +64,14 @@ WBRX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the shift, the retune and the input map)
-    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI, **HANDOVER_ABI},
-                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI) + WBRX_HANDOVER_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI, **HANDOVER_ABI, **CARRIER_OFFSET_ABI},
+                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI) + WBRX_HANDOVER_EXPORTS + list(CARRIER_OFFSET_ABI))
+
+
+def carrier_offset_from_hz(offset_hz, sample_rate_hz, decimation):
+    """tetra_wbrx_carrier_offset_from_hz: the increment (2^-32 cycles per channeliser frame) of a carrier `offset_hz` above its bin's
+    centre; negative offsets wrap."""
+    return int(_lib().tetra_wbrx_carrier_offset_from_hz(float(offset_hz), float(sample_rate_hz), int(decimation)))
 
 
 def default_config():
@@ -110,11 +122,13 @@ class WidebandRx:
     receive chain on one GPU.  `.rx` is the chain (an RxChain view); a block's channel is the carrier's index into `bins`.  shift:
     the channeliser's frequency shift (include/tetra_shift.h, 2^-32 cycles per input sample) for carriers that share one offset from
     the bins' centres, e.g. chan_binding.shift_from_hz(12500, 20e6) for half a bin.  Extended deliveries (ext/tetra_rx_out_ext.h) need
-    nothing here: `.rx.set_snapshot(mask)` and `.rx.deliver(..., extras=mask)` work on the chain tetra_wbrx_rx hands out."""
+    nothing here: `.rx.set_snapshot(mask)` and `.rx.deliver(..., extras=mask)` work on the chain tetra_wbrx_rx hands out.
+    offsets_hz: per slot the carrier's own offset from its (shifted) bin centre in hertz at the capture rate n_channels x 25 kHz
+    (include/ext/tetra_carrier_offset.h); set_offsets takes increments or hertz later."""
 
     def __init__(self, bins, n_channels=800, taps_per_channel=8, decimation=None, max_in=1 << 20, device=-1, chan_cutoff_rel=1.2,
                  chan_flags=0, interp=18, decim=25, taps_per_phase=16, resamp_cutoff_rel=1.0, resamp_kaiser_beta=6.0, kinds=0, flags=0,
-                 demod_flags=0, shift=0, **params):
+                 demod_flags=0, shift=0, offsets_hz=None, **params):
         self._lib = _lib()
         cfg = default_config()
         cfg.chan.n_channels, cfg.chan.taps_per_channel = n_channels, taps_per_channel
@@ -138,6 +152,27 @@ class WidebandRx:
         self.rx = _ChainView(self._lib.tetra_wbrx_rx(h), self.n_bins, max_samples)
         if shift:
             self.set_shift(shift)
+        if offsets_hz is not None:
+            self.set_offsets(hz=offsets_hz)
+
+    def set_offsets(self, inc=None, hz=None, stream=None):
+        """tetra_wbrx_set_carrier_offsets: per slot an offset `inc` (2^-32 cycles per channeliser frame) or `hz` (hertz, at the capture rate
+        n_channels x 25 kHz); between process calls, enqueued on `stream`, from the next call on.  Neither: all zero (the default)."""
+        if inc is not None and hz is not None:
+            raise ValueError("offsets are given as increments or in hertz, not both")
+        if hz is not None:
+            hz = np.asarray(hz, np.float64).reshape(-1)
+            inc = [carrier_offset_from_hz(f, self.M * 25000.0, self.D) for f in hz]
+        new = np.zeros(self.n_bins, np.uint32) if inc is None else np.ascontiguousarray(np.asarray(inc, np.int64).reshape(-1) & 0xffffffff).astype(np.uint32)
+        if new.size != self.n_bins:
+            raise ValueError("set_offsets takes exactly %d offsets" % self.n_bins)
+        call(self._lib.tetra_wbrx_set_carrier_offsets, self._h, ptr(new), stream_ptr(stream))
+
+    def offsets(self):
+        """The offsets in force (tetra_wbrx_get_carrier_offsets), uint32 [n_bins]."""
+        out = np.zeros(max(self.n_bins, 1), np.uint32)
+        call(self._lib.tetra_wbrx_get_carrier_offsets, self._h, ptr(out))
+        return out[:self.n_bins]
 
     def set_shift(self, inc):
         """tetra_wbrx_set_shift: forwards to the channeliser; between process calls, from the next call's first frame."""
@@ -165,14 +200,17 @@ class WidebandRx:
         self.set_input_map(m)
         return m
 
-    def retune(self, bins, stream=None, donors=None, window=None, max_slots=None):
+    def retune(self, bins, stream=None, donors=None, window=None, max_slots=None, offsets=None):
         """tetra_wbrx_retune: slot j receives bins[j] from the next process call on.  Slots whose bin stays are untouched; every other
         slot starts afresh on its new bin.  Enqueued on `stream` (the one the process calls use), not waited for.
         donors (tetra_wbrx_retune_from, include/ext/tetra_handover.h): per slot a donor slot whose bin stays, or -1 -- a moving slot with
-        a donor inherits its frame timing, cell and TDMA clock (window / max_slots: None = the header's defaults)."""
+        a donor inherits its frame timing, cell and TDMA clock (window / max_slots: None = the header's defaults).
+        offsets: the slots' new offsets (set_offsets' increments), set on the same stream ahead of the retune; None keeps every slot's."""
         new = np.ascontiguousarray(np.asarray(bins, np.int64).astype(np.int32).reshape(-1))
         if new.size != self.n_bins:
             raise ValueError("retune takes exactly %d bins" % self.n_bins)
+        if offsets is not None:
+            self.set_offsets(offsets, stream=stream)
         if donors is None:
             call(self._lib.tetra_wbrx_retune, self._h, ptr(new), stream_ptr(stream))
             return
