@@ -3,21 +3,16 @@ tests/test_aach_soft_gpu.py, beside tests/soft_pipeline.py and in its way: oracl
 AACH's 30 ring positions descrambled by sign under the reference's clock and scrambling codes -> the numpy definition
 (tests/aach_soft_definition.py).  The coded kinds go through the reference's soft decoder as in soft_pipeline (an SB1 with a good CRC sets
 the code the burst's AACH is descrambled with).  Nothing of the product's code runs here.  Needs oracle/_ref."""
-import ctypes as C
-
 import numpy as np
 
 from tests import aach_soft_definition as A
+from tests import chain_host as ch
 from tests import soft_pipeline as sp
 
-# The stream of tests/golden/aach_soft_golden.npz: the size of tests/test_rx_soft.py's operating point, RM-coded AACHs, and a level chosen
+# The stream of tests/golden/aach_soft_golden.npz: the size of tests/chain_host.py's operating point, RM-coded AACHs, and a level chosen
 # on the CPU (see test_aach_soft_gpu.py's constants) at which the hard rule loses rows that maximum likelihood keeps.
 CHANNELS, SLOTS, SAMPLES, SEED = 5, 71, 36000, 9401
 ESN0_DB = 9.5
-
-
-def cells():
-    return [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(CHANNELS)]
 
 
 def sent_info():
@@ -26,9 +21,7 @@ def sent_info():
 
 
 def stream_iq(synth):
-    info = sent_info()
-    tx = [synth.gen_downlink(SLOTS, SEED + c, cell=cells()[c], aach=A.code_bits()[info[c]]) for c in range(CHANNELS)]
-    return np.stack([synth.gen_channel(SAMPLES, SEED + 100 + c, bits=tx[c][0], esn0_db=ESN0_DB)[0] for c in range(CHANNELS)])
+    return ch.downlink_batch(synth, CHANNELS, SLOTS, SAMPLES, SEED, ESN0_DB, aach=A.code_bits()[sent_info()])[2]
 
 
 def slot_of_time(t):
@@ -53,43 +46,27 @@ def slots_of(label, n_slots=SLOTS):
 
 def channel_aach(ref, oracle, bits, soft, channel):
     """One channel's stream -> per frame, in frame order: label (channel, bitnum, time on entry, time), the AACH's 30 hard bits
-    descrambled, its 30 soft values descrambled by sign.  tests/soft_pipeline.channel_rows' walk with soft decisions: the clock steps
-    per frame, a SYNC burst's SB1 is decoded first and a good CRC sets clock and code for the burst's other blocks."""
-    add_tn = ref.lib().tetra_tdma_time_add_tn
-    add_tn.argtypes = [C.POINTER(sp._TdmaTime), C.c_uint32]
-    add_tn.restype = None
+    descrambled, its 30 soft values descrambled by sign.  tests/chain_host.walk under the reference's clock and scrambling codes, the
+    SB1 through the reference's soft decoder: a good CRC sets clock and code for the burst's AACH."""
     frames, types, bitnums = oracle.BurstSyncOracle().feed(bits, chunk=1)
     labels, hard, values = [], [], []
-    code, phy = 0, sp._TdmaTime()
-    pack = lambda t: t.tn | (t.fn << 8) | (t.mn << 16)
-    for fr, ft, bn in zip(frames, types, bitnums):
-        add_tn(C.byref(phy), 1)
-        t_rx = t_af = pack(phy)
-        if int(ft) not in sp.BURST_KINDS:
+    sb1 = lambda f: sp.ref_soft_decode(ref, 0, ch.cut(soft, int(bitnums[f]), ch.BLOCK[(ch.TRAIN_SYNC, ch.KIND_SB1)].pieces), 0)
+    for f, (code, t_rx, t_af, _) in enumerate(ch.walk(types, ch.ref_clock(ref), sb1, ref.scramb_get_init)):
+        if int(types[f]) not in ch.BURST_KINDS:
             continue
-        if int(ft) == sp.TRAIN_SYNC:
-            tpsap, pieces = sp.PIECES[(int(ft), sp.KIND_SB1)]
-            soft5 = np.concatenate([soft[int(bn) + o:int(bn) + o + n] for o, n in pieces])
-            t2, ok = sp.ref_soft_decode(ref, tpsap, soft5, code)
-            if ok:
-                code = ref.scramb_get_init(sp._bits_val(t2, 31, 10), sp._bits_val(t2, 41, 14), sp._bits_val(t2, 4, 6))
-                phy.tn, phy.fn, phy.mn = sp._bits_val(t2, 10, 2) + 1, sp._bits_val(t2, 12, 5), sp._bits_val(t2, 17, 6)
-                t_af = pack(phy)
-        _, pieces = sp.PIECES[(int(ft), sp.KIND_BBK)]
+        pieces = ch.BLOCK[(int(types[f]), ch.KIND_BBK)].pieces
         seq = sp.scramb_seq(ref, code, 30)
-        labels.append((channel, int(bn), t_rx, t_af))
-        hard.append(np.concatenate([fr[o:o + n] for o, n in pieces]) ^ seq)
-        values.append(A.descramble(np.concatenate([soft[int(bn) + o:int(bn) + o + n] for o, n in pieces]), seq))
+        labels.append((channel, int(bitnums[f]), t_rx, t_af))
+        hard.append(ch.cut(frames[f], 0, pieces) ^ seq)
+        values.append(A.descramble(ch.cut(soft, int(bitnums[f]), pieces), seq))
     return labels, hard, values
 
 
 def stream_aach(ref, oracle, iq):
     """iq complex64 [C][N] -> dict: label int64 [n][4], hard uint8 [n][30], soft int8 [n][30]; all channels, channel-major"""
-    bits, nb, sym, _ = oracle.process_batch(iq, want_sym=True)
     labels, hard, values = [], [], []
-    for c in range(len(iq)):
-        soft = sp.quantise_np(sym[c][:nb[c] // 2])
-        l, h, v = channel_aach(ref, oracle, bits[c][:nb[c]], soft, c)
+    for c, (bits, soft) in enumerate(zip(*sp.oracle_streams(oracle, iq))):
+        l, h, v = channel_aach(ref, oracle, bits, soft, c)
         labels += l
         hard += h
         values += v

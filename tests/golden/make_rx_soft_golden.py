@@ -15,17 +15,17 @@ sys.path.insert(0, ROOT)
 def main():
     import tetra_amd
     from oracle import binding as ob, ref_binding as ref
+    from tests import chain_host as ch
     from tests import soft_pipeline as sp
-    from tests.test_rx_soft import GOLDEN, operating_point_iq, rows_to_arrays
-    iq = operating_point_iq(tetra_amd.pkg.synth)
+    iq = ch.operating_point(tetra_amd.pkg.synth, 11.0)[2]
     out = {}
     for name, use_soft in (("hard", False), ("soft", True)):
         rows = sp.stream_rows(ref, ob, iq, use_soft)
         for k, v in rows.items():
-            for field, arr in rows_to_arrays(v, sp.TYPE1_BITS[k]).items():
+            for field, arr in ch.rows_to_arrays(v, ch.TYPE1_BITS[k]).items():
                 out["%s_%d_%s" % (name, k, field)] = arr
         print(name, {k: (len(v), sum(r[2] for r in v)) for k, v in rows.items()})
-    np.savez_compressed(GOLDEN, **out)
+    np.savez_compressed(ch.RX_SOFT_GOLDEN, **out)
 
 
 if __name__ == "__main__":

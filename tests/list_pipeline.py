@@ -5,23 +5,10 @@ code and the clock; the clock steps one timeslot per frame) -- and the other kin
 T = 0 is the chain without the flag."""
 import numpy as np
 
+from tests import chain_host as ch
 from tests import list_definition as D
-from tests import soft_pipeline as sp
 
-CODED_KINDS = (sp.KIND_SB1, sp.KIND_SB2, sp.KIND_NDB1, sp.KIND_NDB2, sp.KIND_SCH_F)
-TYPE1 = {sp.KIND_SB1: 60, sp.KIND_SB2: 124, sp.KIND_NDB1: 124, sp.KIND_NDB2: 124, sp.KIND_SCH_F: 268}
-
-
-def _val(bits, a, n):
-    return int("".join(str(int(x)) for x in bits[a:a + n]), 2)
-
-
-def add_tn(t):
-    """One timeslot on [tn, fn, mn], in place: the host build of the tracker's clock (tests/emul/lmac_emul_bind.tdma_advance), which
-    tests/test_lmac.py pins to the reference's tetra_tdma_time_add_tn over the whole state space."""
-    from tests.emul import lmac_emul_bind
-    p = int(lmac_emul_bind.tdma_advance(np.array([t], np.uint32), 1)[0][0])
-    t[0], t[1], t[2] = p & 0xff, (p >> 8) & 0xff, p >> 16
+CODED_KINDS = ch.CODED_KINDS
 
 
 def scramb_code(colour, mcc, mnc):
@@ -40,53 +27,36 @@ def _decode(tpsap, rows, codes, T, soft):
 def channel_rows(oracle, bits, channel, T, soft=None):
     """-> {(kind, channel, bitnum): (crc_ok, time on entry, time, type-1 bytes, rank, (errors, compared) of tetra_biterr.h on the row's
     final bits)} for the coded kinds of one channel's stream.
-    soft: the quantiser's value per bit (same numbering) for the soft route, else None."""
+    soft: the quantiser's value per bit (same numbering) for the soft route, else None.  The SB1s are decoded as one batch ahead of
+    tests/chain_host.walk (they need no code), which runs under the host build of the tracker's clock and the numpy scramb_code."""
     frames, types, bitnums = oracle.BurstSyncOracle().feed(bits, chunk=1)
     nfr = len(frames)
 
     def cut(kind, which):
-        rows = []
-        for f in which:
-            _, pieces = sp.PIECES[(int(types[f]), kind)]
-            src, at = (frames[f], 0) if soft is None else (soft, int(bitnums[f]))
-            rows.append(np.concatenate([src[at + o:at + o + n] for o, n in pieces]))
-        return np.array(rows)
+        if soft is None:
+            return np.array([ch.cut(frames[f], 0, ch.BLOCK[(int(types[f]), kind)].pieces) for f in which])
+        return np.array([ch.cut(soft, int(bitnums[f]), ch.BLOCK[(int(types[f]), kind)].pieces) for f in which])
 
-    sync = [f for f in range(nfr) if int(types[f]) == sp.TRAIN_SYNC]
-    sb1, sb1_ok, sb1_rank = _decode(0, cut(sp.KIND_SB1, sync), np.zeros(len(sync), np.uint32), T, soft is not None)
+    sync = [f for f in range(nfr) if int(types[f]) == ch.TRAIN_SYNC]
+    sb1, sb1_ok, sb1_rank = _decode(0, cut(ch.KIND_SB1, sync), np.zeros(len(sync), np.uint32), T, soft is not None)
     at_sync = {f: j for j, f in enumerate(sync)}
-    code, phy = 0, [0, 0, 0]
-    codes, t_rx, t_af = np.zeros(nfr, np.uint32), np.zeros(nfr, np.int64), np.zeros(nfr, np.int64)
-    pack = lambda t: t[0] | (t[1] << 8) | (t[2] << 16)
-    for f in range(nfr):
-        add_tn(phy)
-        t_rx[f] = t_af[f] = pack(phy)
-        j = at_sync.get(f)
-        if j is not None and sb1_ok[j]:
-            b = sb1[j]
-            code = scramb_code(_val(b, 4, 6), _val(b, 31, 10), _val(b, 41, 14))
-            phy = [_val(b, 10, 2) + 1, _val(b, 12, 5), _val(b, 17, 6)]
-            t_af[f] = pack(phy)
-        codes[f] = code
+    steps = list(ch.walk(types, ch.host_clock, lambda f: (sb1[at_sync[f]], sb1_ok[at_sync[f]]), lambda mcc, mnc, colour: scramb_code(colour, mcc, mnc)))
+    codes, t_rx, t_af = (np.array([s[i] for s in steps], dt) for i, dt in enumerate((np.uint32, np.int64, np.int64)))
     out = {}
     for kind in CODED_KINDS:
-        which = [f for f in range(nfr) if kind in sp.BURST_KINDS.get(int(types[f]), ())]
-        if kind == sp.KIND_SB1:
-            tpsap, rx, t2, ok, rank = 0, cut(kind, which), sb1, sb1_ok, sb1_rank
-        else:
-            tpsap = sp.PIECES[(int(types[which[0]]), kind)][0] if which else 0
-            rx = cut(kind, which)
-            t2, ok, rank = _decode(tpsap, rx, codes[which], T, soft is not None)
+        which = [f for f in range(nfr) if kind in ch.BURST_KINDS.get(int(types[f]), ())]
+        tpsap, rx = ch.BY_KIND[kind].tpsap, cut(kind, which)
+        t2, ok, rank = (sb1, sb1_ok, sb1_rank) if kind == ch.KIND_SB1 else _decode(tpsap, rx, codes[which], T, soft is not None)
         for j, f in enumerate(which):
             count = D.count_errors(tpsap, rx[j], int(codes[f]), t2[j], soft is not None)
-            out[(kind, channel, int(bitnums[f]))] = (int(ok[j]), int(t_rx[f]), int(t_af[f]), t2[j][:TYPE1[kind]].tobytes(), int(rank[j]), count)
+            out[(kind, channel, int(bitnums[f]))] = (int(ok[j]), int(t_rx[f]), int(t_af[f]), t2[j][:ch.TYPE1_BITS[kind]].tobytes(), int(rank[j]), count)
     return out
 
 
 def rescued_sb1_matters(with_list, without):
     """a block of another kind that lies behind a rescued SB1 and has another verdict, other bits or another time than without the rescue"""
-    rescued = [(c, bn) for (k, c, bn), v in with_list.items() if k == sp.KIND_SB1 and v[4] > 0]
+    rescued = [(c, bn) for (k, c, bn), v in with_list.items() if k == ch.KIND_SB1 and v[4] > 0]
     for (k, c, bn), v in with_list.items():
-        if k != sp.KIND_SB1 and v[:4] != without[(k, c, bn)][:4] and any(rc == c and rbn <= bn for rc, rbn in rescued):
+        if k != ch.KIND_SB1 and v[:4] != without[(k, c, bn)][:4] and any(rc == c and rbn <= bn for rc, rbn in rescued):
             return True
     return False

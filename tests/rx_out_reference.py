@@ -5,9 +5,9 @@ import ctypes as C
 
 import numpy as np
 
-TYPE1 = [60, 30, 124, 124, 124, 268]             # type-1 bits per kind
-PACKED_BYTES = [8, 4, 16, 16, 16, 34]
-STRIDE = [80, 32, 144, 144, 144, 288]            # the chain's type-2 row strides
+from tests.chain_host import PACKED_BYTES, TYPE1_BITS as TYPE1          # per kind: type-1 bits, and the bytes they pack into
+
+STRIDE = [80, 32, 144, 144, 144, 288]            # the chain's type-2 row strides (tetra_rx_rows_device)
 CHAN_BYTES = [40, 16, 4, 24]
 SENTINEL = 0xA5
 TILE = 128                                       # rows per workgroup of the delivery kernels

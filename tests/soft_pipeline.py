@@ -10,30 +10,18 @@ import ctypes as C
 
 import numpy as np
 
+from tests import chain_host as ch
+from tests import list_definition
+
 Q, G = 31, np.float32(16.0)                     # csrc/soft_core.hpp
 FRESH_PREV = np.complex64(complex(np.float32(0.70710678), np.float32(0.70710678)))
-TRAIN_NORM_1, TRAIN_NORM_2, TRAIN_SYNC = 0, 1, 3
-# chain kind (TETRA_RX_KIND_*) -> (tpsap, pieces of the burst); per burst type the kinds in tetra_burst_rx_cb's order
-KIND_SB1, KIND_BBK, KIND_SB2, KIND_NDB1, KIND_NDB2, KIND_SCH_F = range(6)
-PIECES = {
-    (TRAIN_SYNC, KIND_SB1): (0, ((94, 120),)), (TRAIN_SYNC, KIND_BBK): (3, ((252, 30),)), (TRAIN_SYNC, KIND_SB2): (1, ((282, 216),)),
-    (TRAIN_NORM_2, KIND_BBK): (3, ((230, 14), (266, 16))), (TRAIN_NORM_2, KIND_NDB1): (2, ((14, 216),)), (TRAIN_NORM_2, KIND_NDB2): (2, ((282, 216),)),
-    (TRAIN_NORM_1, KIND_BBK): (3, ((230, 14), (266, 16))), (TRAIN_NORM_1, KIND_SCH_F): (5, ((14, 216), (282, 216))),
-}
-BURST_KINDS = {TRAIN_SYNC: (KIND_SB1, KIND_BBK, KIND_SB2), TRAIN_NORM_2: (KIND_BBK, KIND_NDB1, KIND_NDB2), TRAIN_NORM_1: (KIND_BBK, KIND_SCH_F)}
-TYPE1_BITS = (60, 30, 124, 124, 124, 268)
 
 # ---- planted inputs of the soft frame decoder: shared by the host emulation's tests and the GPU tests -----------------------------------
-# where a kind's type-5 bits sit in its 510-bit burst (tetra_burst.c:343-393): (tpsap, blk_num, burst type, pieces (offset, length))
-KINDS = {
-    "sb1": (0, 1, 3, ((94, 120),)),
-    "sb2": (1, 2, 3, ((282, 216),)),
-    "ndb1": (2, 1, 1, ((14, 216),)),
-    "ndb2": (2, 2, 1, ((282, 216),)),
-    "schf": (5, 0, 0, ((14, 216), (282, 216))),
-}
-TYPE2_BITS = {"sb1": 80, "sb2": 144, "ndb1": 144, "ndb2": 144, "schf": 288}
-REF_TPSAP = {"sb1": 0, "sb2": 1, "ndb1": 2, "ndb2": 2, "schf": 5}
+# the coded kinds of tests/chain_host.py's table by name: (tpsap, blk_num, burst type, pieces (offset, length)), type-2 bits, block type
+_CODED = [b for b in ch.BLOCKS if b.kind != ch.KIND_BBK]
+KINDS = {b.name: (b.tpsap, b.blk, b.train, b.pieces) for b in _CODED}
+TYPE2_BITS = {b.name: b.type2 for b in _CODED}
+REF_TPSAP = {b.name: b.tpsap for b in _CODED}
 
 
 def soft_rows_for(lref, kind, rng):
@@ -66,11 +54,10 @@ def soft_rows_for(lref, kind, rng):
 class DefinitionEncoder:
     """soft_rows_for's `lref` where the reference is not built: its block parameters, and tests/list_definition.py's transmitter (which
     tests/test_lmac_soft_gpu.py holds against the reference's lmac_encode where that is at hand)."""
-    BLK_PARAM = {0: (120, 80, 60, 11, 1), 1: (216, 144, 124, 101, 1), 2: (216, 144, 124, 101, 1), 5: (432, 288, 268, 103, 1)}
+    BLK_PARAM = {b.tpsap: (b.type5, b.type2, b.type1, list_definition.BLK[b.tpsap][3], 1) for b in _CODED}         # [3]: the interleaver's a
 
     @staticmethod
     def lmac_encode(tpsap, type1, code):
-        from tests import list_definition
         return list_definition.encode(tpsap, type1, code)
 
 
@@ -135,59 +122,40 @@ def ref_soft_decode(ref, blk_type, soft5, code):
     return t2[:n2].copy(), int(L.crc16_ccitt_bits(_p(t2), n1 + 16) == ref.TETRA_CRC_OK)
 
 
-class _TdmaTime(C.Structure):
-    """struct tetra_tdma_time (src/decoder/src/tetra_tdma.h:6-12)"""
-    _fields_ = [("hn", C.c_uint16), ("sn", C.c_uint32), ("tn", C.c_uint32), ("fn", C.c_uint32), ("mn", C.c_uint32)]
-
-
-def _bits_val(t2, a, n):
-    return int("".join(str(int(x)) for x in t2[a:a + n]), 2)
-
-
-def channel_rows(ref, oracle, bits, soft, channel, use_soft):
+def channel_rows(ref, oracle, bits, soft, channel, use_soft, sync=None):
     """One channel's whole stream -> {kind: [(channel, bitnum, crc_ok, time on entry, time, type-1 bytes)]} in frame order.  bits: the
-    oracle demodulator's bits; soft: the quantiser's value per bit (same numbering).  Frames: the burst-synchroniser oracle a bit per
-    call; per frame the clock steps (tetra_tdma_time_add_tn, the reference's), SB1 first: a good CRC sets the clock and the
-    scrambling code (tetra_scramb_get_init) every other block of the burst and every later one is descrambled with."""
-    add_tn = ref.lib().tetra_tdma_time_add_tn
-    add_tn.argtypes = [C.POINTER(_TdmaTime), C.c_uint32]
-    add_tn.restype = None
-    frames, types, bitnums = oracle.BurstSyncOracle().feed(bits, chunk=1)
+    oracle demodulator's bits; soft: the quantiser's value per bit (same numbering).  Frames: the synchroniser (sync(); default the
+    burst-synchroniser oracle) a bit per call; tests/chain_host.walk under the reference's clock (tetra_tdma_time_add_tn) and scrambling
+    codes (tetra_scramb_get_init).  Every block of a frame carries the time on entry and the time after the SB1."""
+    frames, types, bitnums = (sync or oracle.BurstSyncOracle)().feed(bits, chunk=1)
+
+    def decode(f, kind, code):
+        b = ch.BLOCK[(int(types[f]), kind)]
+        if kind == ch.KIND_BBK or not use_soft:
+            return ref.lmac_decode(b.tpsap, ch.cut(frames[f], 0, b.pieces), code)
+        return ref_soft_decode(ref, b.tpsap, ch.cut(soft, int(bitnums[f]), b.pieces), code)
+
     rows = {k: [] for k in range(6)}
-    code, phy = 0, _TdmaTime()
-    pack = lambda t: t.tn | (t.fn << 8) | (t.mn << 16)
-    for fr, ft, bn in zip(frames, types, bitnums):
-        add_tn(C.byref(phy), 1)
-        t_rx = t_af = pack(phy)
-        pending = []
-        for kind in BURST_KINDS.get(int(ft), ()):
-            tpsap, pieces = PIECES[(int(ft), kind)]
-            hard5 = np.concatenate([fr[o:o + n] for o, n in pieces])
-            if kind == KIND_BBK or not use_soft:
-                t2, ok = ref.lmac_decode(tpsap, hard5, code)
-            else:
-                soft5 = np.concatenate([soft[int(bn) + o:int(bn) + o + n] for o, n in pieces])
-                t2, ok = ref_soft_decode(ref, tpsap, soft5, code)
-            if kind == KIND_SB1 and ok:                  # tetra_lower_mac.c:246-275
-                code = ref.scramb_get_init(_bits_val(t2, 31, 10), _bits_val(t2, 41, 14), _bits_val(t2, 4, 6))
-                phy.tn, phy.fn, phy.mn = _bits_val(t2, 10, 2) + 1, _bits_val(t2, 12, 5), _bits_val(t2, 17, 6)
-                t_af = pack(phy)
-            pending.append((kind, ok, t2[:TYPE1_BITS[kind]].tobytes()))
-        # (a SYNC burst's SB1 comes first: its AACH and SB2 are handled under ITS code.)  Every block of the frame carries the time on
-        # entry and the time after the SB1
-        for kind, ok, t1 in pending:
-            rows[kind].append((channel, int(bn), int(ok), t_rx, t_af, t1))
+    steps = ch.walk(types, ch.ref_clock(ref), lambda f: decode(f, ch.KIND_SB1, 0), ref.scramb_get_init)
+    for f, (code, t_rx, t_af, sb1) in enumerate(steps):
+        for kind in ch.BURST_KINDS.get(int(types[f]), ()):
+            t2, ok = sb1 if kind == ch.KIND_SB1 else decode(f, kind, code)
+            rows[kind].append((channel, int(bitnums[f]), int(ok), t_rx, t_af, t2[:ch.TYPE1_BITS[kind]].tobytes()))
     return rows
 
 
-def stream_rows(ref, oracle, iq, use_soft):
-    """iq complex64 [C][N] -> rows of every kind as tests/test_rx.py's _collect gives them (all channels, channel-major), from the oracle
-    demodulator's bits and symbols."""
+def oracle_streams(oracle, iq):
+    """iq complex64 [C][N] -> per channel the oracle demodulator's bits, and the quantiser's value per bit of its symbols"""
     bits, nb, sym, _ = oracle.process_batch(iq, want_sym=True)
+    return [bits[c][:nb[c]] for c in range(len(iq))], [quantise_np(sym[c][:nb[c] // 2]) for c in range(len(iq))]
+
+
+def stream_rows(ref, oracle, iq, use_soft, sync=None):
+    """iq complex64 [C][N] -> rows of every kind as tests/chain_gpu.py's collect gives them (all channels, channel-major), from the oracle
+    demodulator's bits and symbols."""
     out = {k: [] for k in range(6)}
-    for c in range(len(iq)):
-        soft = quantise_np(sym[c][:nb[c] // 2])
-        rows = channel_rows(ref, oracle, bits[c][:nb[c]], soft, c, use_soft)
+    for c, (bits, soft) in enumerate(zip(*oracle_streams(oracle, iq))):
+        rows = channel_rows(ref, oracle, bits, soft, c, use_soft, sync)
         for k in out:
             out[k] += rows[k]
     return out

@@ -15,6 +15,7 @@ from tests import aach_soft_pipeline as P
 from tests import list_definition as D
 from tests import soft_pipeline as sp
 from tests import test_aach_soft as T
+from tests.chain_gpu import ragged_cuts, run_stream
 from tests.golden import make_aach_soft_golden as GA
 from tests.golden import make_lmac_soft_golden as G
 
@@ -262,7 +263,7 @@ def test_gpu_soft_bbk_job_refusals_write_nothing(pkg):
 
 # ---- GPU: the receive chain -------------------------------------------------------------------------------------------------------------
 def expected_bbk(g, min_margin=1):
-    """the fixture as tests/test_rx_soft.py's _collect gives a kind's rows"""
+    """the fixture as tests/chain_gpu.py's collect gives a kind's rows"""
     rows, ok = A.rows(g["soft"], min_margin)
     return [(int(l[0]), int(l[1]), int(o), int(l[2]), int(l[3]), r[:30].tobytes()) for l, o, r in zip(g["label"], ok, rows)]
 
@@ -277,7 +278,6 @@ def chain_iq(synth):
 def test_gpu_chain_equals_the_host_pipeline_under_ragged_cuts(pkg, chain_iq, one_stream):
     """SOFT | AACH_SOFT: the BBK rows are the fixture's, row for row, however the stream is cut, on two streams and on one; every other
     kind is what the chain with SOFT alone gives."""
-    from tests.test_rx_soft import ragged_cuts, run_stream
     R = pkg.rx_binding
     base = R.FLAG_SOFT | (R.FLAG_ONE_STREAM if one_stream else 0)
     cuts = ragged_cuts(P.SAMPLES)

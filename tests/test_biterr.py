@@ -7,7 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import chain_host as ch
 from tests import soft_pipeline as sp
+from tests.chain_gpu import device_bytes as _device_bytes, run_calls
 
 CODED = (0, 1, 2, 4, 5)                   # SB1, SB2, NDB, SCH/HU, SCH/F
 RATES = (0.0, 0.02, 0.05, 0.5)
@@ -454,7 +456,7 @@ def test_gpu_frames_count_like_the_byte_rows(pkg, lref, oracle):
 # ---- GPU: the receive chain (TETRA_RX_FLAG_BITERR) ---------------------------------------------------------------------------------------
 CH_SAMPLES, CH_CUT, CH_SLOTS = 18000, 9000, 36
 CH_ESN0 = (None, 11.0, 11.5)                   # three coded downlinks: a clean one and two near 11 dB; channel 3 is noise only
-CODED_KINDS = (sp.KIND_SB1, sp.KIND_SB2, sp.KIND_NDB1, sp.KIND_NDB2, sp.KIND_SCH_F)
+CODED_KINDS = ch.CODED_KINDS
 ERR_UNSUPPORTED = -2                           # include/tetra_demod.h
 
 
@@ -474,72 +476,57 @@ def chain_iq(synth):
 def _run_chain(pkg, iq, flags, after=None):
     """the stream in two calls through one handle -> per call {kind: (blocks, type1)}, the channels' bits of both calls, and after(rx)"""
     import torch
-    from tests.test_wbrx import _device_bytes
     R = pkg.rx_binding
-    dev = torch.device("cuda", 0)
-    d_iq = torch.from_numpy(np.array(iq)).to(dev)
-    rx = pkg.RxChain(iq.shape[0], CH_CUT, flags=flags)
-    s = torch.cuda.current_stream(dev)
-    calls, bits, extra = [], [b""] * iq.shape[0], None
-    try:
-        for i, (a, b) in enumerate(((0, CH_CUT), (CH_CUT, CH_SAMPLES))):
-            rx.process_device(d_iq[:, a:b].contiguous(), b - a, s)
-            if i == 0 and flags & R.FLAG_BITERR:
-                assert all(len(rx.fetch_biterr(k, which=1)[0]) == 0 for k in CODED_KINDS)          # no previous call yet
-            calls.append({k: rx.fetch(k) for k in range(R.N_KINDS)})
-            if flags & R.FLAG_BITERR:
-                calls[-1]["biterr"] = {k: rx.fetch_biterr(k) for k in CODED_KINDS}
-                for k in CODED_KINDS:          # the same rows where they are, beside rows_device's; and a buffer that is too small
-                    n = len(calls[-1][k][0])
-                    if n:
-                        words = _device_bytes(torch, rx.biterr_device(k, 0, s), (n,), "<i4").cpu().numpy().astype(np.int64) & 0xffffffff
-                        assert np.array_equal(words & 0xffff, calls[-1]["biterr"][k][0]) and np.array_equal(words >> 16, calls[-1]["biterr"][k][1])
-                        _, _, _, pn_rows = rx.rows_device(k, 0, s)
-                        assert int(_device_bytes(torch, pn_rows, (1,), "<i4").cpu().numpy()[0]) == n
-                        got, small = C.c_int(0), np.zeros(max(n - 1, 1), np.uint32)
-                        assert rx._lib.tetra_rx_fetch_biterr(rx._h, 0, k, small.ctypes.data, n - 1, C.byref(got)) == -6 and got.value == n      # TETRA_ERR_SIZE
-            p, stride, pn = rx.bits_device(0, s)
-            nb = _device_bytes(torch, pn, (iq.shape[0],), "<i4").cpu().numpy()
-            rows = _device_bytes(torch, p, (iq.shape[0], stride), "|u1").cpu().numpy()
-            bits = [bits[c] + rows[c, :nb[c]].tobytes() for c in range(iq.shape[0])]
-        cells = [bytes(c) for c in rx.cells()]
-        if after:
-            extra = after(rx)
-        rx.wait()
-    finally:
-        rx.close()
-    return calls, [np.frombuffer(b, np.uint8) for b in bits], cells, extra
+    calls = []
+
+    def per_call(rx, i, s):
+        if i == 0 and flags & R.FLAG_BITERR:
+            assert all(len(rx.fetch_biterr(k, which=1)[0]) == 0 for k in CODED_KINDS)          # no previous call yet
+        calls.append({k: rx.fetch(k) for k in range(R.N_KINDS)})
+        if flags & R.FLAG_BITERR:
+            calls[-1]["biterr"] = {k: rx.fetch_biterr(k) for k in CODED_KINDS}
+            for k in CODED_KINDS:          # the same rows where they are, beside rows_device's; and a buffer that is too small
+                n = len(calls[-1][k][0])
+                if n:
+                    words = _device_bytes(torch, rx.biterr_device(k, 0, s), (n,), "<i4").cpu().numpy().astype(np.int64) & 0xffffffff
+                    assert np.array_equal(words & 0xffff, calls[-1]["biterr"][k][0]) and np.array_equal(words >> 16, calls[-1]["biterr"][k][1])
+                    _, _, _, pn_rows = rx.rows_device(k, 0, s)
+                    assert int(_device_bytes(torch, pn_rows, (1,), "<i4").cpu().numpy()[0]) == n
+                    got, small = C.c_int(0), np.zeros(max(n - 1, 1), np.uint32)
+                    assert rx._lib.tetra_rx_fetch_biterr(rx._h, 0, k, small.ctypes.data, n - 1, C.byref(got)) == -6 and got.value == n      # TETRA_ERR_SIZE
+
+    bits, cells, extra = run_calls(pkg, iq, (0, CH_CUT, CH_SAMPLES), flags, per_call, after=after)
+    return calls, bits, cells, extra
 
 
 def _codes_in_force(ref, calls, n_channels):
     """per channel the (bit number, scrambling code) of every SB1 with a good CRC, in stream order: what tp_sap_udata_ind's SB1 case sets"""
     out = [[] for _ in range(n_channels)]
     for call in calls:
-        blocks, t1 = call[sp.KIND_SB1]
+        blocks, t1 = call[ch.KIND_SB1]
         for b, t in zip(blocks, t1):
             if b["crc_ok"]:
-                out[int(b["channel"])].append((int(b["bitnum"]), ref.scramb_get_init(sp._bits_val(t, 31, 10), sp._bits_val(t, 41, 14), sp._bits_val(t, 4, 6))))
+                out[int(b["channel"])].append((int(b["bitnum"]), ref.scramb_get_init(*ch.sync_pdu_fields(t)[:3])))
     return out
 
 
 def _expected_counts(ref, calls, bits, soft=None):
     """The definition on every coded row of both calls, from the chain's own bits (soft = None) or from soft values per channel: the
-    row's type-5 block is cut at its label's bit number with soft_pipeline.PIECES, decoded by the reference under the code in force, and
+    row's type-5 block is cut at its label's bit number with chain_host's pieces, decoded by the reference under the code in force, and
     counted.  -> per call {kind: (errors, compared)}; the reference's type-1 bits and verdicts are checked on the way."""
     codes = _codes_in_force(ref, calls, len(bits))
-    train = {sp.KIND_SB1: sp.TRAIN_SYNC, sp.KIND_SB2: sp.TRAIN_SYNC, sp.KIND_NDB1: sp.TRAIN_NORM_2, sp.KIND_NDB2: sp.TRAIN_NORM_2, sp.KIND_SCH_F: sp.TRAIN_NORM_1}
     out = []
     for call in calls:
         want = {}
         for k in CODED_KINDS:
-            tpsap, pieces = sp.PIECES[(train[k], k)]
+            tpsap, pieces = ch.BY_KIND[k].tpsap, ch.BY_KIND[k].pieces
             blocks, t1 = call[k]
             v = np.zeros((len(blocks), 2), np.int64)
             for j, b in enumerate(blocks):
                 c, bn = int(b["channel"]), int(b["bitnum"])
                 code = ([0] + [cd for at, cd in codes[c] if at <= bn])[-1]
                 src = bits[c] if soft is None else soft[c]
-                t5 = np.concatenate([src[bn + o:bn + o + n] for o, n in pieces])
+                t5 = ch.cut(src, bn, pieces)
                 if soft is None:
                     t2, ok = ref.lmac_decode(tpsap, t5, code)
                     v[j] = count_hard(ref, tpsap, t5, code, t2)
@@ -677,7 +664,7 @@ def test_gpu_host_banks_fetch_bit_errors_and_links(pkg, synth, tmp_path):
     C++ driver (tests/host/test_biterr_bank.cpp)."""
     import os
     import subprocess
-    from tests.test_rx_out import _noisy_batch
+    from tests.chain_host import noisy_batch as _noisy_batch
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pk = os.path.join(root, "sdrpp-tetra-demodulator_amd")
     pkg.build.build()

@@ -10,8 +10,9 @@ import math
 import numpy as np
 import pytest
 
+from tests.chain_gpu import bit_rows as _bit_rows
 from tests.test_carrier_offset import ODD_LARGE, TOL, definition
-from tests.test_wbrx import BINS_SMALL, CARRIERS_SMALL, D_SMALL, M_SMALL, _assert_known_answer, _bit_rows, _rows, _run_collect
+from tests.test_wbrx import BINS_SMALL, CARRIERS_SMALL, D_SMALL, M_SMALL, _assert_known_answer, _rows, _run_collect
 
 NSLOTS = 80
 FS = M_SMALL * 25000.0

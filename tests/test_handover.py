@@ -91,7 +91,7 @@ def _tdma_reference(starts, ks):
     built, else from the recording of exactly that (tests/golden/handover_tdma.json)."""
     from oracle import ref_binding
     if ref_binding.available():
-        from tests.test_lmac import _TdmaTime, _ref_add_tn
+        from tests.chain_host import TdmaTime as _TdmaTime, ref_add_tn as _ref_add_tn
         add_tn = _ref_add_tn(ref_binding)
         out = {}
         for tn, fn, mn in starts:
@@ -367,7 +367,7 @@ def test_gpu_chain_handover_equals_the_host_emulation(pkg, synth, em, slots2, to
     the inherited scrambling code.  Donor and bystander equal a chain that saw no hand-over, byte for byte."""
     import torch
     from tests.test_retune import _chain_snap
-    from tests.test_wbrx import _bit_rows
+    from tests.chain_gpu import bit_rows as _bit_rows
     R = pkg.rx_binding
     slots1, cell = 16, (262, 1, 5)
     n = slots1 + slots2

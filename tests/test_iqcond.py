@@ -479,7 +479,8 @@ def test_gpu_no_map_ever_and_null_after_a_map_equal_a_handle_that_never_heard_of
     and one that processes the first cuts WITH a map on a side stream of calls and is then reset, against a plain handle -- resampled
     frames, rows and bit rows equal after every call; the plain handle itself is pinned to the hand-wired composition by that test."""
     import torch
-    from tests.test_wbrx import BINS_SMALL, D_SMALL, M_SMALL, _bit_rows, _cs16, _rows
+    from tests.chain_gpu import bit_rows as _bit_rows
+    from tests.test_wbrx import BINS_SMALL, D_SMALL, M_SMALL, _cs16, _rows
     R = pkg.rx_binding
     x = small_capture[0]
     xin = x if fmt == "c64" else _cs16(torch, x)

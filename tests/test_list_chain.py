@@ -4,8 +4,10 @@ first and feeding the tracker's walk.  Four downlinks at Es/N0 = 11 dB from the 
 import numpy as np
 import pytest
 
+from tests import chain_host as ch
 from tests import list_pipeline as LP
 from tests import soft_pipeline as sp
+from tests.chain_gpu import device_bytes as _device_bytes, run_calls
 
 SAMPLES, CUT, SLOTS, ESN0 = 18000, 9000, 36, 11.0
 SEEDS = (214, 186, 259, 56)            # chosen so that rescued SB1s change later blocks (test_the_chosen_input_... checks it on the CPU)
@@ -26,8 +28,7 @@ def iq(synth):
 @pytest.fixture(scope="module")
 def oracle_stream(oracle, iq):
     """the oracle demodulator's bits and quantised soft values per channel"""
-    bits, nb, sym, _ = oracle.process_batch(np.array(iq), want_sym=True)
-    return [bits[c][:nb[c]] for c in range(len(iq))], [sp.quantise_np(sym[c][:nb[c] // 2]) for c in range(len(iq))]
+    return sp.oracle_streams(oracle, np.array(iq))
 
 
 def expected(oracle, bits, T, soft=None):
@@ -45,7 +46,7 @@ def test_the_chosen_input_holds_rescued_rows_and_a_rescued_sb1_that_matters(orac
         w, wo = expected(oracle, bits, 4, sv), expected(oracle, bits, 0, sv)
         assert set(w) == set(wo) and len(w) >= 80
         assert all(w[k][0] >= wo[k][0] for k in w) and all(v[4] == (0 if v[0] else -1) for v in wo.values())
-        assert sum(v[4] > 0 for v in w.values()) >= 3 and any(k[0] == sp.KIND_SB1 and v[4] > 0 for k, v in w.items())
+        assert sum(v[4] > 0 for v in w.values()) >= 3 and any(k[0] == ch.KIND_SB1 and v[4] > 0 for k, v in w.items())
         assert any(v[4] == -1 for v in w.values())
         assert LP.rescued_sb1_matters(w, wo)
 
@@ -54,49 +55,38 @@ def run_chain(pkg, iq, flags, T=None):
     """the stream in two calls through one handle -> {(kind, channel, bitnum): (crc_ok, time on entry, time, type-1 bytes, rank, counts)}
     (rank None without FLAG_LIST, counts None without FLAG_BITERR), the AACH rows, the channels' bits, the cells"""
     import torch
-    from tests.test_wbrx import _device_bytes
     R = pkg.rx_binding
-    dev = torch.device("cuda", 0)
-    d_iq = torch.from_numpy(np.array(iq)).to(dev)
-    rx = pkg.RxChain(iq.shape[0], CUT, flags=flags)
-    s = torch.cuda.current_stream(dev)
-    rows, aach, bits, ranks = {}, [], [b""] * iq.shape[0], []
-    try:
-        if T is not None:
-            rx.set_list_candidates(T)
-        for a, b in ((0, CUT), (CUT, SAMPLES)):
-            rx.process_device(d_iq[:, a:b].contiguous(), b - a, s)
-            for k in LP.CODED_KINDS:
-                blocks, t1 = rx.fetch(k)
-                rank = rx.fetch_list_rank(k) if flags & R.FLAG_LIST else [None] * len(blocks)
-                err, cmp_ = rx.fetch_biterr(k) if flags & R.FLAG_BITERR else ([None] * len(blocks), [None] * len(blocks))
-                assert len(rank) == len(blocks)
-                ranks.append(rank)
-                if flags & R.FLAG_LIST and len(blocks):
-                    dr = _device_bytes(torch, rx.list_rank_device(k, 0, s), (len(blocks),), "<i4").cpu().numpy()
-                    assert np.array_equal(dr, rank)
-                for j, blk in enumerate(blocks):
-                    key = (k, int(blk["channel"]), int(blk["bitnum"]))
-                    assert key not in rows
-                    rows[key] = (int(blk["crc_ok"]), int(blk["tdma_time_rx"]), int(blk["tdma_time"]), t1[j].tobytes(),
-                                 None if rank[j] is None else int(rank[j]), None if err[j] is None else (int(err[j]), int(cmp_[j])))
-            blocks, t1 = rx.fetch(R.KIND_BBK)
-            aach.append((blocks.tobytes(), t1.tobytes()))
-            p, stride, pn = rx.bits_device(0, s)
-            nb = _device_bytes(torch, pn, (iq.shape[0],), "<i4").cpu().numpy()
-            got = _device_bytes(torch, p, (iq.shape[0], stride), "|u1").cpu().numpy()
-            bits = [bits[c] + got[c, :nb[c]].tobytes() for c in range(iq.shape[0])]
+    rows, aach, ranks = {}, [], []
+
+    def per_call(rx, i, s):
+        for k in LP.CODED_KINDS:
+            blocks, t1 = rx.fetch(k)
+            rank = rx.fetch_list_rank(k) if flags & R.FLAG_LIST else [None] * len(blocks)
+            err, cmp_ = rx.fetch_biterr(k) if flags & R.FLAG_BITERR else ([None] * len(blocks), [None] * len(blocks))
+            assert len(rank) == len(blocks)
+            ranks.append(rank)
+            if flags & R.FLAG_LIST and len(blocks):
+                dr = _device_bytes(torch, rx.list_rank_device(k, 0, s), (len(blocks),), "<i4").cpu().numpy()
+                assert np.array_equal(dr, rank)
+            for j, blk in enumerate(blocks):
+                key = (k, int(blk["channel"]), int(blk["bitnum"]))
+                assert key not in rows
+                rows[key] = (int(blk["crc_ok"]), int(blk["tdma_time_rx"]), int(blk["tdma_time"]), t1[j].tobytes(),
+                             None if rank[j] is None else int(rank[j]), None if err[j] is None else (int(err[j]), int(cmp_[j])))
+        blocks, t1 = rx.fetch(R.KIND_BBK)
+        aach.append((blocks.tobytes(), t1.tobytes()))
+
+    def after(rx):
         if flags & R.FLAG_LIST:        # the rank buffers are double buffered like the results: which = 1 is the first call's
+            s = torch.cuda.current_stream()
             for j, k in enumerate(LP.CODED_KINDS):
                 first, second = ranks[j], ranks[len(LP.CODED_KINDS) + j]
                 assert np.array_equal(rx.fetch_list_rank(k, which=1), first) and np.array_equal(rx.fetch_list_rank(k, which=0), second)
                 if len(first):
                     assert np.array_equal(_device_bytes(torch, rx.list_rank_device(k, 1, s), (len(first),), "<i4").cpu().numpy(), first)
-        cells = [bytes(c) for c in rx.cells()]
-        rx.wait()
-    finally:
-        rx.close()
-    return rows, aach, [np.frombuffer(b, np.uint8) for b in bits], cells
+
+    bits, cells, _ = run_calls(pkg, iq, (0, CUT, SAMPLES), flags, per_call, None if T is None else lambda rx: rx.set_list_candidates(T), after)
+    return rows, aach, bits, cells
 
 
 @pytest.mark.gpu
@@ -123,7 +113,7 @@ def test_gpu_chain_equals_the_pipeline_on_every_row(pkg, oracle, oracle_stream, 
             if base & R.FLAG_BITERR:
                 assert rows[k][5] == want[k][5] and plain[k][5] == want0[k][5], (route, k)
         rescued = [k for k in rows if rows[k][4] > 0]
-        assert len(rescued) >= 3 and any(k[0] == sp.KIND_SB1 for k in rescued)
+        assert len(rescued) >= 3 and any(k[0] == ch.KIND_SB1 for k in rescued)
         assert all(rows[k][0] >= plain[k][0] for k in rows)
         assert LP.rescued_sb1_matters(rows, plain)
         if base & R.FLAG_BITERR:
@@ -196,7 +186,7 @@ def test_gpu_host_banks_fetch_ranks(pkg, synth, tmp_path):
     against one bank of all channels and a bank without the flag: a plain C++ driver (tests/host/test_list_bank.cpp)."""
     import os
     import subprocess
-    from tests.test_rx_out import _noisy_batch
+    from tests.chain_host import noisy_batch as _noisy_batch
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pk = os.path.join(root, "sdrpp-tetra-demodulator_amd")
     pkg.build.build()

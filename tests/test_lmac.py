@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.chain_host import TdmaTime as _TdmaTime, ref_add_tn as _ref_add_tn
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CODED = (0, 1, 2, 4, 5)     # SB1, SB2, NDB, SCH/HU, SCH/F
 STRIDE = 436                # a row stride that is not the row length
@@ -510,21 +512,6 @@ def test_gpu_lmac_full_size_round_trip(pkg, lref):
     for r in check:                                              # uncorrectable blocks and a random sample: == reference
         t2, okr = lref.lmac_decode(t, rows[r], si_d[pick[r]])
         assert np.array_equal(out[r, :288], t2) and okr == ok[r]
-
-
-class _TdmaTime(__import__("ctypes").Structure):
-    """struct tetra_tdma_time (src/decoder/src/tetra_tdma.h:6-12)"""
-    import ctypes as _C
-    _fields_ = [("hn", _C.c_uint16), ("sn", _C.c_uint32), ("tn", _C.c_uint32), ("fn", _C.c_uint32), ("mn", _C.c_uint32)]
-
-
-def _ref_add_tn(ref):
-    """The reference's own tetra_tdma_time_add_tn (oracle/_ref: src/decoder/src/tetra_tdma.c compiled where it lies)."""
-    import ctypes as C
-    add_tn = ref.lib().tetra_tdma_time_add_tn
-    add_tn.argtypes = [C.POINTER(_TdmaTime), C.c_uint32]
-    add_tn.restype = None
-    return add_tn
 
 
 def walk_slots(lref, cell, t2, ok, valid, nfr=None):

@@ -12,6 +12,9 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests.chain_gpu import collect as _collect, enqueue, rows as _rows
+from tests.chain_host import KIND_NAMES, downlink_batch as _downlink_batch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -108,22 +111,6 @@ def test_gpu_rx_iq_to_type1_blocks_through_one_handle(pkg, ref, synth):
     rx.close()
 
 
-def _downlink_batch(synth, Cn, nslots, N, seed):
-    cells = [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(Cn)]
-    tx = [synth.gen_downlink(nslots, seed + c, cell=cells[c]) for c in range(Cn)]
-    iq = np.stack([synth.gen_channel(N, seed + 100 + c, bits=tx[c][0])[0] for c in range(Cn)])
-    return cells, tx, iq
-
-
-def _collect(rx, R, which=0):
-    got = {}
-    for k in range(R.N_KINDS):
-        blocks, t1 = rx.fetch(k, which)
-        got[k] = [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), t1[j].tobytes())
-                  for j, b in enumerate(blocks)]
-    return got
-
-
 @pytest.mark.gpu
 def test_gpu_rx_all_kinds_cell_and_clock(pkg, synth, ref):
     """A coded downlink with every block kind (synth.gen_downlink: SYNC bursts with SB1 + AACH + SB2, two-channel normal bursts with
@@ -140,7 +127,7 @@ def test_gpu_rx_all_kinds_cell_and_clock(pkg, synth, ref):
     rx.wait()
     got = _collect(rx, R)
     cell = rx.cells()
-    names = {R.KIND_SB1: "sb1", R.KIND_BBK: "bbk", R.KIND_SB2: "sb2", R.KIND_NDB1: "ndb1", R.KIND_NDB2: "ndb2", R.KIND_SCH_F: "schf"}
+    names = KIND_NAMES
     for c in range(Cn):
         assert (cell[c].mcc, cell[c].mnc, cell[c].colour_code) == cells[c]
         assert cell[c].scramb_init == synth.tx_scramb_code(*cells[c])
@@ -245,14 +232,11 @@ def test_gpu_rx_streaming_calls_overlap_and_equal_one_call(pkg, synth):
         s = torch.cuda.Stream(dev)
         got = {k: [] for k in range(R.N_KINDS)}
         for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
-            chunk = d_iq[:, a:b].contiguous()
-            s.wait_stream(torch.cuda.current_stream(dev))
-            rx.process_device(chunk, b - a, s)
+            enqueue(torch, rx, d_iq, a, b, s)
             if i >= 1:                                   # the previous call's results while this one runs
                 prev = _collect(rx, R, which=1)
                 for k in got:
                     got[k] += prev[k]
-            chunk.record_stream(s)
         last = _collect(rx, R, which=0)
         for k in got:
             got[k] += last[k]
@@ -265,7 +249,7 @@ def test_gpu_rx_streaming_calls_overlap_and_equal_one_call(pkg, synth):
         rx.close()
     rx = pkg.RxChain(Cn, N, kinds=1 << R.KIND_SCH_F)
     rx.process(iq)
-    assert _collect_kind(rx, R, R.KIND_SCH_F) == want[R.KIND_SCH_F] and _collect_kind(rx, R, R.KIND_SB1) == want[R.KIND_SB1]
+    assert _rows(*rx.fetch(R.KIND_SCH_F)) == want[R.KIND_SCH_F] and _rows(*rx.fetch(R.KIND_SB1)) == want[R.KIND_SB1]
     with pytest.raises(pkg.TetraDemodError) as e:
         rx.fetch(R.KIND_SB2)
     assert e.value.status == -2          # TETRA_ERR_UNSUPPORTED
@@ -299,12 +283,6 @@ def test_gpu_rx_time_major_frames_equal_channel_major(pkg, synth):
         assert got[k] == want[k], k
     assert [tuple(getattr(c, f) for f, _ in R.CellState._fields_) for c in b.cells()] == want_cell
     b.close()
-
-
-def _collect_kind(rx, R, k):
-    blocks, t1 = rx.fetch(k)
-    return [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), t1[j].tobytes())
-            for j, b in enumerate(blocks)]
 
 
 @pytest.mark.gpu

@@ -10,11 +10,12 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests.chain_gpu import enqueue, rows as _rows
+from tests.chain_host import PACKED_BYTES, TYPE1_BITS as TYPE1, downlink_batch as _downlink_batch, noisy_batch as _noisy_batch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PK = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
 SAN = os.path.join(ROOT, "tests", "san")
-TYPE1 = [60, 30, 124, 124, 124, 268]
-PACKED_BYTES = [8, 4, 16, 16, 16, 34]
 
 
 def test_rx_out_header_symbols_all_exported(pkg):
@@ -142,30 +143,6 @@ def test_rx_out_host_side_is_clean_under_asan_and_ubsan():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 
-def _downlink_batch(synth, Cn, nslots, N, seed):
-    """tests/test_rx.py's recipe: coded downlinks with every block kind, a different cell per channel."""
-    cells = [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(Cn)]
-    tx = [synth.gen_downlink(nslots, seed + c, cell=cells[c]) for c in range(Cn)]
-    iq = np.stack([synth.gen_channel(N, seed + 100 + c, bits=tx[c][0])[0] for c in range(Cn)])
-    return cells, tx, iq
-
-
-def _noisy_batch(synth, Cn, nslots, N, seed):
-    """The same, with the last two channels at low Es/N0 so that some blocks fail their CRC."""
-    cells, tx, iq = _downlink_batch(synth, Cn, nslots, N, seed)
-    rng = np.random.default_rng(seed)
-    for c in (Cn - 2, Cn - 1):
-        sigma = np.sqrt(np.mean(np.abs(iq[c]) ** 2) / 10 ** (6.0 / 10) / 2)
-        iq[c] = iq[c] + (sigma * (rng.standard_normal(N) + 1j * rng.standard_normal(N))).astype(np.complex64)
-    return cells, tx, iq
-
-
-def _rows(blocks, type1):
-    """rows as tests/test_rx.py's _collect compares them (frame_slot counts frames within one call, so it is left out)"""
-    return [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), type1[j].tobytes())
-            for j, b in enumerate(blocks)]
-
-
 def _fetched(rx, which=0, kinds=range(6)):
     return {k: rx.fetch(k, which) for k in kinds}
 
@@ -253,10 +230,7 @@ def test_gpu_rx_out_streaming_deliveries_equal_one_call(pkg, synth):
                     got[k] += _rows(b, np.unpackbits(t, axis=1)[:, :TYPE1[k]])
 
         for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
-            chunk = d_iq[:, a:b].contiguous()
-            s.wait_stream(torch.cuda.current_stream(dev))
-            rx.process_device(chunk, b - a, s)
-            chunk.record_stream(s)
+            enqueue(torch, rx, d_iq, a, b, s)
             pending.append((i + 2, rx.deliver(0, packed=True, buf=bufs[i % 3])))
             drain(i)                      # call k's delivery is read once calls k + 1 and k + 2 are enqueued
         drain(len(cuts))

@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 from tests.rx_out_reference import CHAN_BYTES, a16 as _a16, build_ext_delivery as _build_ext_delivery, keep_patterns as _keep_patterns
-from tests.test_rx_out import _build_delivery, _downlink_batch, _noisy_batch
+from tests.chain_gpu import enqueue
+from tests.chain_host import downlink_batch as _downlink_batch, noisy_batch as _noisy_batch
+from tests.test_rx_out import _build_delivery
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PK = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
@@ -376,10 +378,7 @@ def test_gpu_rx_out_ext_snapshot_is_the_delivered_calls_state(pkg, synth):
         s = torch.cuda.Stream(dev)
         pending, got = [], []
         for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
-            chunk = d_iq[:, a:b].contiguous()
-            s.wait_stream(torch.cuda.current_stream(dev))
-            rx.process_device(chunk, b - a, s)
-            chunk.record_stream(s)
+            enqueue(torch, rx, d_iq, a, b, s)
             pending.append((i + 2, rx.deliver(0, packed=True, buf=bufs[i % 3], extras=ALL_CHAN)))
             while pending and pending[0][0] <= i:           # call k's delivery is read once calls k + 1 and k + 2 are enqueued
                 got.append({k: v.copy() for k, v in pending.pop(0)[1].wait().channels.items()})

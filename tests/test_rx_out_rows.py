@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from tests import rx_out_reference as X
-from tests.test_rx_out import _noisy_batch
+from tests.chain_host import noisy_batch as _noisy_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "ext", "tetra_rx_out_rows.h")

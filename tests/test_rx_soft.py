@@ -11,35 +11,16 @@ import os
 import numpy as np
 import pytest
 
+from tests import chain_host as ch
 from tests import soft_pipeline as sp
+from tests.chain_gpu import collect, ragged_cuts, run_stream
+from tests.chain_host import OP_CHANNELS, OP_SAMPLES, OP_SCHF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "rx_soft_golden.npz")
-
-# The operating point: one second of five coded downlinks at Es/N0 = 11 dB.  Chosen on the CPU from the reference-only
-# pipeline: hard decisions leave 21 of 118 SCH/F blocks CRC-bad, soft decisions 12.
-OP_CHANNELS, OP_SLOTS, OP_SAMPLES, OP_ESN0_DB, OP_SEED = 5, 71, 36000, 11.0, 9000
-OP_SCHF = {"hard": (118, 97), "soft": (118, 106)}            # (rows, CRC-good rows)
+GOLDEN = ch.RX_SOFT_GOLDEN
+OP_ESN0_DB = 11.0                                            # tests/chain_host.py's operating point at the level DESIGN.md 8.3 chose
 KINDS = ("sb1", "sb2", "ndb1", "ndb2", "schf")
 REF_TPSAP, soft_rows_for = sp.REF_TPSAP, sp.soft_rows_for
-
-
-def operating_point_iq(synth):
-    cells = [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(OP_CHANNELS)]
-    tx = [synth.gen_downlink(OP_SLOTS, OP_SEED + c, cell=cells[c]) for c in range(OP_CHANNELS)]
-    return np.stack([synth.gen_channel(OP_SAMPLES, OP_SEED + 100 + c, bits=tx[c][0], esn0_db=OP_ESN0_DB)[0] for c in range(OP_CHANNELS)])
-
-
-def rows_to_arrays(rows, n1):
-    return dict(label=np.array([r[:5] for r in rows], np.int64).reshape(-1, 5),
-                type1=np.frombuffer(b"".join(r[5] for r in rows), np.uint8).reshape(-1, n1))
-
-
-def golden_rows(name):
-    """{kind: rows} of the fixture, as tests/soft_pipeline.py's stream_rows returns them"""
-    g = np.load(GOLDEN)
-    return {k: [tuple(int(x) for x in lab) + (t1.tobytes(),) for lab, t1 in zip(g["%s_%d_label" % (name, k)], g["%s_%d_type1" % (name, k)])]
-            for k in range(6)}
 
 
 @pytest.fixture(scope="module")
@@ -116,12 +97,12 @@ def test_ring_size_covers_the_synchronisers_buffer_and_two_calls(semul):
 def test_operating_point_reference_pipeline_gains_and_matches_the_fixture(lref, oracle, synth):
     """The reference-only host pipeline on the GPU gain test's stream: hard decisions leave a clear share of the SCH/F blocks CRC-bad,
     soft decisions recover strictly more; the rows are the committed fixture."""
-    iq = operating_point_iq(synth)
+    iq = ch.operating_point(synth, OP_ESN0_DB)[2]
     for name, use_soft in (("hard", False), ("soft", True)):
         rows = sp.stream_rows(lref, oracle, iq, use_soft)
-        schf = rows[sp.KIND_SCH_F]
+        schf = rows[ch.KIND_SCH_F]
         assert (len(schf), sum(r[2] for r in schf)) == OP_SCHF[name]
-        assert rows == golden_rows(name)
+        assert rows == ch.golden_rows(GOLDEN, name)
     assert OP_SCHF["hard"][1] < 0.9 * OP_SCHF["hard"][0] and OP_SCHF["soft"][1] > OP_SCHF["hard"][1]
 
 
@@ -132,54 +113,9 @@ def test_flag_value_and_binding(pkg):
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------------
 
-def _collect(rx, R, which=0):
-    got = {}
-    for k in range(R.N_KINDS):
-        blocks, t1 = rx.fetch(k, which)
-        got[k] = [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), t1[j].tobytes())
-                  for j, b in enumerate(blocks)]
-    return got
-
-
-def run_stream(pkg, iq, cuts, flags=0, max_samples=16000, between=None):
-    """the stream through one handle, call k = samples [cuts[k], cuts[k+1]), results fetched one call late -> {kind: rows in call order};
-    between(rx, k) runs after call k is enqueued"""
-    import torch
-    R = pkg.rx_binding
-    dev = torch.device("cuda", 0)
-    d_iq = torch.from_numpy(iq).to(dev)
-    rx = pkg.RxChain(iq.shape[0], max_samples, flags=flags)
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    got = {k: [] for k in range(R.N_KINDS)}
-    for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
-        chunk = d_iq[:, a:b].contiguous() if b > a else d_iq[:, :1].contiguous()
-        s.wait_stream(torch.cuda.current_stream(dev))
-        rx.process_device(chunk, b - a, s)
-        chunk.record_stream(s)
-        if i >= 1:
-            for k, v in _collect(rx, R, which=1).items():
-                got[k] += v
-        if between:
-            between(rx, i, s)
-    for k, v in _collect(rx, R, which=0).items():
-        got[k] += v
-    rx.wait()
-    rx.close()
-    return got
-
-
-def ragged_cuts(n):
-    cuts, sizes, i = [0], (9000, 180, 1, 0, 4000), 0
-    while cuts[-1] < n:
-        cuts.append(min(n, cuts[-1] + sizes[i % len(sizes)]))
-        i += 1
-    return cuts
-
-
 @pytest.fixture(scope="module")
 def op_iq(synth):
-    return operating_point_iq(synth)
+    return ch.operating_point(synth, OP_ESN0_DB)[2]
 
 
 @pytest.mark.gpu
@@ -200,7 +136,7 @@ def test_gpu_flag_8_creates_a_chain(pkg):
 def test_gpu_soft_chain_equals_the_host_pipeline(pkg, op_iq, one_stream):
     """row for row: type-1 bits, crc_ok, bitnum, both TDMA times, every kind; the second cut as 9000, 180, 1, 0, 4000, ... samples"""
     R = pkg.rx_binding
-    want = golden_rows("soft")
+    want = ch.golden_rows(GOLDEN, "soft")
     got = run_stream(pkg, op_iq, ragged_cuts(OP_SAMPLES), flags=R.FLAG_SOFT | (R.FLAG_ONE_STREAM if one_stream else 0))
     for k in range(R.N_KINDS):
         assert sorted(got[k]) == sorted(want[k]), (k, len(got[k]), len(want[k]))
@@ -216,7 +152,7 @@ def test_gpu_soft_ring_of_minimum_size_wraps(pkg, op_iq, semul):
     cuts = list(range(0, OP_SAMPLES, small)) + [OP_SAMPLES]
     a = run_stream(pkg, op_iq, cuts, flags=R.FLAG_SOFT, max_samples=small)
     b = run_stream(pkg, op_iq, [0, 16000, 32000, OP_SAMPLES], flags=R.FLAG_SOFT, max_samples=16000)
-    want = golden_rows("soft")
+    want = ch.golden_rows(GOLDEN, "soft")
     for k in range(R.N_KINDS):
         assert sorted(a[k]) == sorted(b[k]) == sorted(want[k]), k
 
@@ -226,7 +162,7 @@ def test_gpu_soft_recovers_more_blocks_than_hard(pkg, op_iq):
     R = pkg.rx_binding
     cuts = [0, 16000, 32000, OP_SAMPLES]
     hard, soft = run_stream(pkg, op_iq, cuts, flags=0), run_stream(pkg, op_iq, cuts, flags=R.FLAG_SOFT)
-    want = golden_rows("hard")
+    want = ch.golden_rows(GOLDEN, "hard")
     for k in range(R.N_KINDS):
         assert sorted(hard[k]) == sorted(want[k]), k          # the flag-off chain: the hard path's host walk, as ever
     n = {name: sum(r[2] for r in rows[R.KIND_SCH_F]) for name, rows in (("hard", hard), ("soft", soft))}
@@ -238,11 +174,11 @@ def test_gpu_soft_recovers_more_blocks_than_hard(pkg, op_iq):
 def test_gpu_soft_beside_the_aach_option_and_through_the_delivery(pkg, op_iq):
     from tests.emul import rm3014_emul_bind
     R = pkg.rx_binding
-    want = golden_rows("soft")
+    want = ch.golden_rows(GOLDEN, "soft")
     rx = pkg.RxChain(OP_CHANNELS, OP_SAMPLES, flags=R.FLAG_SOFT | R.FLAG_AACH_RM3014)
     rx.process(op_iq)
     rx.wait()
-    got = _collect(rx, R)
+    got = collect(rx, R)
     for k in range(R.N_KINDS):
         if k != R.KIND_BBK:
             assert got[k] == want[k], k
@@ -299,7 +235,7 @@ def test_gpu_soft_reset_of_one_channel_mid_stream(pkg, op_iq):
 
     got = run_stream(pkg, iq, cuts, flags=R.FLAG_SOFT, max_samples=step, between=between)
     fresh = run_stream(pkg, np.ascontiguousarray(iq[:, at * step:]), cuts[:len(cuts) - at], flags=R.FLAG_SOFT, max_samples=step)
-    want = golden_rows("soft")
+    want = ch.golden_rows(GOLDEN, "soft")
     for k in range(R.N_KINDS):
         for c in (0, 2):
             assert sorted(r for r in got[k] if r[0] == c) == sorted(r for r in want[k] if r[0] == c), (k, c)

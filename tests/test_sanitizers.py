@@ -100,7 +100,7 @@ def test_rx_bank_streams_like_rx_chain_under_asan_and_ubsan(pkg, synth, tmp_path
     every block of every kind (labels + type-1 bits) and the cell states equal what the Python RxChain returns for the same stream,
     and the sanitizers stay silent (ROCm's own allocations suppressed by library name)."""
     import numpy as np
-    from tests.test_rx import _downlink_batch
+    from tests.chain_host import downlink_batch as _downlink_batch
     R = pkg.rx_binding
     Cn, calls, nslots = 5, 3, 36
     N = nslots * 510 // calls

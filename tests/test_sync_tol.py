@@ -8,14 +8,15 @@ counts and rows are the fixture tests/golden/sync_tol_golden.npz (written by `py
 GPU: the kernels against the host build, setting and clearing, and the chain with TETRA_RX_FLAG_SYNC_TOLERANT against the fixture."""
 import json
 import os
-import types
 
 import numpy as np
 import pytest
 
+from tests import chain_host as ch
 from tests import soft_pipeline as sp
+from tests.chain_gpu import collect, ragged_cuts, run_stream
+from tests.chain_host import OP_CHANNELS, OP_SAMPLES
 from tests.test_burst_sync import aligned_bytes, make_stream
-from tests.test_rx_soft import OP_CHANNELS, OP_SAMPLES, OP_SEED, OP_SLOTS, rows_to_arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sync_tol_golden.npz")
@@ -165,23 +166,16 @@ def check_stream(ref, tolemul, bits, tol, rng, tag):
 
 # ---- streams ----------------------------------------------------------------------------------------------------------------------------
 
-def op_iq(synth, esn0_db):
-    """tests/test_rx_soft.py's operating point at another Es/N0 (11 dB is that test's stream)"""
-    cells = [(100 + 7 * c, 1000 + 13 * c, (5 + 3 * c) % 64) for c in range(OP_CHANNELS)]
-    tx = [synth.gen_downlink(OP_SLOTS, OP_SEED + c, cell=cells[c]) for c in range(OP_CHANNELS)]
-    iq = np.stack([synth.gen_channel(OP_SAMPLES, OP_SEED + 100 + c, bits=tx[c][0], esn0_db=esn0_db)[0] for c in range(OP_CHANNELS)])
-    return iq, [t[0] for t in tx]
-
-
 _op_cache = {}
 
 
 def op_bits(synth, oracle, esn0_db):
-    """-> (iq, [demodulated bits per channel], [transmitted bits per channel]) of the oracle demodulator, computed once"""
+    """tests/chain_host.py's operating point at a given Es/N0 (11 dB is tests/test_rx_soft.py's stream) -> (iq, [demodulated bits per
+    channel], [transmitted bits per channel]) of the oracle demodulator, computed once"""
     if esn0_db not in _op_cache:
-        iq, tx = op_iq(synth, esn0_db)
+        _, tx, iq = ch.operating_point(synth, esn0_db)
         bits, nb = oracle.process_batch(iq)[:2]
-        _op_cache[esn0_db] = (iq, [bits[c][:nb[c]].copy() for c in range(OP_CHANNELS)], tx)
+        _op_cache[esn0_db] = (iq, [bits[c][:nb[c]].copy() for c in range(OP_CHANNELS)], [t[0] for t in tx])
     return _op_cache[esn0_db]
 
 
@@ -350,8 +344,7 @@ def test_first_unlock_exhaustive_and_random(tolemul):
 
 def tolerant_rows(lref, oracle, iq, tol, use_soft):
     """tests/soft_pipeline.py's stream_rows with the restatement where it runs the reference's synchroniser"""
-    shim = types.SimpleNamespace(process_batch=oracle.process_batch, BurstSyncOracle=lambda: Restatement(lref, tol))
-    return sp.stream_rows(lref, shim, iq, use_soft)
+    return sp.stream_rows(lref, oracle, iq, use_soft, sync=lambda: Restatement(lref, tol))
 
 
 def operating_table(ref, oracle, synth, esn0_db):
@@ -368,12 +361,6 @@ def operating_table(ref, oracle, synth, esn0_db):
 
 def golden():
     return np.load(GOLDEN)
-
-
-def golden_rows(name):
-    g = golden()
-    return {k: [tuple(int(x) for x in lab) + (t1.tobytes(),) for lab, t1 in zip(g["%s_%d_label" % (name, k)], g["%s_%d_type1" % (name, k)])]
-            for k in range(6)}
 
 
 @pytest.fixture(scope="module")
@@ -396,7 +383,7 @@ def test_operating_point_frames_and_rows_are_the_fixture(lref, oracle, synth):
         counts = [[len(rows[k]), sum(r[2] for r in rows[k])] for k in range(6)]
         print(name, "rows / CRC-good rows per kind:", counts)
         assert counts == [[int(a), int(b)] for a, b in g[name + "_counts"]]
-        assert rows == golden_rows(name)
+        assert rows == ch.golden_rows(GOLDEN, name)
 
 
 def test_operating_table_beside_the_operating_point(ref, oracle, synth):
@@ -704,12 +691,7 @@ def test_gpu_rows_off_the_16_byte_grid_equal_the_host_build(pkg, ref, tolemul, t
 
 @pytest.fixture(scope="module")
 def op11(synth):
-    return op_iq(synth, 11.0)[0]
-
-
-def _rx_soft():
-    from tests import test_rx_soft
-    return test_rx_soft
+    return ch.operating_point(synth, 11.0)[2]
 
 
 @pytest.mark.gpu
@@ -717,26 +699,26 @@ def _rx_soft():
 def test_gpu_tolerant_chain_equals_the_fixture(pkg, op11, one_stream):
     """flag 128 at the operating point, the stream cut as 9000, 180, 1, 0, 4000, ... samples: row for row the reference-only pipeline
     behind the restatement's frames"""
-    R, T = pkg.rx_binding, _rx_soft()
-    want = golden_rows("hard")
-    got = T.run_stream(pkg, op11, T.ragged_cuts(OP_SAMPLES), flags=R.FLAG_SYNC_TOLERANT | (R.FLAG_ONE_STREAM if one_stream else 0))
+    R = pkg.rx_binding
+    want = ch.golden_rows(GOLDEN, "hard")
+    got = run_stream(pkg, op11, ragged_cuts(OP_SAMPLES), flags=R.FLAG_SYNC_TOLERANT | (R.FLAG_ONE_STREAM if one_stream else 0))
     for k in range(R.N_KINDS):
         assert sorted(got[k]) == sorted(want[k]), (k, len(got[k]), len(want[k]))
 
 
 @pytest.mark.gpu
 def test_gpu_tolerant_chain_beside_the_other_flags_and_through_the_delivery(pkg, op11):
-    R, T = pkg.rx_binding, _rx_soft()
+    R = pkg.rx_binding
     cuts = [0, 16000, 32000, OP_SAMPLES]
-    soft = T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_SOFT)
-    want = golden_rows("soft")
+    soft = run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_SOFT)
+    want = ch.golden_rows(GOLDEN, "soft")
     for k in range(R.N_KINDS):
         assert sorted(soft[k]) == sorted(want[k]), k
     # every flag at once: the coded kinds are the soft rows, the AACH rows are as many
     rx = pkg.RxChain(OP_CHANNELS, OP_SAMPLES, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_SOFT | R.FLAG_BITERR | R.FLAG_AACH_RM3014)
     rx.process(op11)
     rx.wait()
-    got = T._collect(rx, R)
+    got = collect(rx, R)
     for k in range(R.N_KINDS):
         if k != R.KIND_BBK:
             assert got[k] == want[k], k
@@ -761,14 +743,14 @@ def test_gpu_tolerant_chain_beside_the_other_flags_and_through_the_delivery(pkg,
 def test_gpu_chain_tolerance_is_settable_between_calls(pkg, op11):
     """a chain created without the flag and switched with tetra_rx_set_sync_tolerance before its first call is the flag's chain; switched
     back to NULL it is the default chain"""
-    R, T = pkg.rx_binding, _rx_soft()
+    R = pkg.rx_binding
     for tol, name in ((DEFAULT, "hard"), (None, None)):
         rx = pkg.RxChain(OP_CHANNELS, OP_SAMPLES, flags=0 if tol else R.FLAG_SYNC_TOLERANT)
         rx.set_sync_tolerance(tol)
         rx.process(op11)
         rx.wait()
-        got = T._collect(rx, R)
-        want = golden_rows(name) if name else T.golden_rows("hard")
+        got = collect(rx, R)
+        want = ch.golden_rows(GOLDEN, name) if name else ch.golden_rows(ch.RX_SOFT_GOLDEN, "hard")
         for k in range(R.N_KINDS):
             assert got[k] == want[k], (tol, k)
         with pytest.raises(pkg.TetraDemodError):
@@ -810,7 +792,7 @@ def test_gpu_tolerant_through_the_wideband_handle(pkg, synth):
 def test_gpu_reset_of_one_channel_zeroes_its_miss_counter(pkg, op11):
     """channel 1 of 3 loses its signal from sample 9000 to 12000, so at the call boundary at 12000 samples its miss counter stands above
     0; tetra_rx_reset_channels_device on it there zeroes that counter in stream order and leaves the other channels' rows the fixture's"""
-    R, T = pkg.rx_binding, _rx_soft()
+    R = pkg.rx_binding
     iq = op11[:3].copy()
     g = np.random.default_rng(99)
     iq[1, 9000:12000] = (0.05 * (g.standard_normal(3000) + 1j * g.standard_normal(3000))).astype(np.complex64)
@@ -825,10 +807,10 @@ def test_gpu_reset_of_one_channel_zeroes_its_miss_counter(pkg, op11):
             seen["after"] = rx.sync_misses().copy()
             seen["state"] = rx.sync_states()[1]
 
-    got = T.run_stream(pkg, iq, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=step, between=between)
+    got = run_stream(pkg, iq, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=step, between=between)
     assert 0 < seen["before"][1] < 16 and seen["after"][1] == 0 and seen["state"] == (0, 0, 0, 0), seen
     assert np.array_equal(seen["before"][[0, 2]], seen["after"][[0, 2]])
-    want = golden_rows("hard")
+    want = ch.golden_rows(GOLDEN, "hard")
     for k in range(R.N_KINDS):
         for c in (0, 2):
             assert sorted(r for r in got[k] if r[0] == c) == sorted(r for r in want[k] if r[0] == c), (k, c)
@@ -839,12 +821,12 @@ def test_gpu_reset_of_one_channel_zeroes_its_miss_counter(pkg, op11):
 def test_gpu_tolerant_lock_delivers_more_blocks(pkg, op11):
     """THE GAIN: at 11 dB the flag yields more SCH/F rows and more CRC-good SCH/F rows than the default chain; the counts are the
     fixture's (147 / 112 against the reference rule's 118 / 97)"""
-    R, T = pkg.rx_binding, _rx_soft()
+    R = pkg.rx_binding
     cuts = [0, 16000, 32000, OP_SAMPLES]
-    off, on = T.run_stream(pkg, op11, cuts, flags=0), T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT)
+    off, on = run_stream(pkg, op11, cuts, flags=0), run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT)
     n = {name: (len(rows[R.KIND_SCH_F]), sum(r[2] for r in rows[R.KIND_SCH_F])) for name, rows in (("off", off), ("on", on))}
     print("SCH/F rows / CRC-good rows: flag off %s, flag on %s" % (n["off"], n["on"]))
-    assert n["off"] == T.OP_SCHF["hard"] and n["on"] == tuple(int(v) for v in golden()["hard_counts"][R.KIND_SCH_F])
+    assert n["off"] == ch.OP_SCHF["hard"] and n["on"] == tuple(int(v) for v in golden()["hard_counts"][R.KIND_SCH_F])
     assert n["on"][0] > n["off"][0] and n["on"][1] > n["off"][1]
     assert sum(len(v) for k, v in on.items() if k in (R.KIND_SB1, R.KIND_NDB1, R.KIND_SCH_F)) == int(golden()["table"][1][1]) > REFERENCE_FRAMES_11DB
 
@@ -895,7 +877,7 @@ def test_gpu_chain_tolerance_set_with_a_tail_in_flight(pkg, op11):
     """tetra_rx_set_sync_tolerance right behind a process call, without waiting: it waits for that call's tail itself, so the rows are
     those of a chain that waited first -- the first call under the reference's rule, the others under {3, 5, 16}"""
     import torch
-    R, T = pkg.rx_binding, _rx_soft()
+    R = pkg.rx_binding
     cuts = [0, 12000, 24000, OP_SAMPLES]
     runs = []
     for wait_first in (True, False):
@@ -905,8 +887,8 @@ def test_gpu_chain_tolerance_set_with_a_tail_in_flight(pkg, op11):
                     rx.wait()
                 rx.set_sync_tolerance(DEFAULT)
                 assert not rx.sync_misses().any()
-        runs.append(T.run_stream(pkg, op11, cuts, flags=0, max_samples=12000, between=between))
-    plain, tolerant = T.run_stream(pkg, op11, cuts, flags=0, max_samples=12000), T.run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=12000)
+        runs.append(run_stream(pkg, op11, cuts, flags=0, max_samples=12000, between=between))
+    plain, tolerant = run_stream(pkg, op11, cuts, flags=0, max_samples=12000), run_stream(pkg, op11, cuts, flags=R.FLAG_SYNC_TOLERANT, max_samples=12000)
     first_call_bits = 11000                                # (every frame below this bit number ended inside the first call)
     for k in range(R.N_KINDS):
         assert runs[0][k] == runs[1][k], k
@@ -950,7 +932,7 @@ def test_gpu_host_bank_sets_the_tolerance_and_reads_the_counters(pkg, synth, tmp
     """TetraRxBank::setSyncTolerance / syncMisses (host/tetra_rx_bank.h) from a plain C++ driver (tests/host/test_sync_tol_bank.cpp): a bank
     switched with setSyncTolerance is the bank created with the flag, row for row and counter for counter"""
     import subprocess
-    from tests.test_rx_out import _noisy_batch
+    from tests.chain_host import noisy_batch as _noisy_batch
     pk = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
     pkg.build.build()
     exe = str(tmp_path / "test_sync_tol_bank")
@@ -983,7 +965,7 @@ def write_golden():
         rows = tolerant_rows(ref, oracle, iq, DEFAULT, use_soft)
         out[name + "_counts"] = np.array([[len(rows[k]), sum(r[2] for r in rows[k])] for k in range(6)], np.int64)
         for k in range(6):
-            a = rows_to_arrays(rows[k], sp.TYPE1_BITS[k])
+            a = ch.rows_to_arrays(rows[k], ch.TYPE1_BITS[k])
             out["%s_%d_label" % (name, k)], out["%s_%d_type1" % (name, k)] = a["label"], a["type1"]
     np.savez_compressed(GOLDEN, **out)
     print(out["table_esn0"], out["table"], out["hard_counts"], out["soft_counts"], sep="\n")

@@ -409,7 +409,7 @@ def reference_rows(ref, bits):
     bits), in the reference's order.  The time on entry of tetra_burst_rx_cb is the PHY time before the frame plus one
     tetra_tdma_time_add_tn (the reference's own), cross-checked against curr_frame / curr_multiframe, which tetra_burst.c:349-350 store on
     entry.  facts: per SB1 (bitnum, crc_ok, tup time, PHY time after, PHY time on entry) and the receiver's state after every frame."""
-    from tests.test_lmac import _TdmaTime, _ref_add_tn
+    from tests.chain_host import TdmaTime as _TdmaTime, ref_add_tn as _ref_add_tn
     import ctypes as C
     add_tn = _ref_add_tn(ref)
     rx = ref.ReferenceRxChain()
@@ -476,7 +476,7 @@ def test_gpu_rx_chain_equals_the_reference_chain_on_a_stream_with_failures(pkg, 
     indication -- kind, bit number, crc_ok, type-1 bits, tdma_time (tup->tdma_time), tdma_time_rx (the PHY time on entry of
     tetra_burst_rx_cb) -- and there is a row for every indication.  Both sides consume identical bits: nothing is excluded."""
     import torch
-    from tests.test_wbrx import _bit_rows
+    from tests.chain_gpu import bit_rows as _bit_rows
     R = pkg.rx_binding
     Cn = len(FAIL_CELLS)
     N = FAIL_SLOTS * 510 - 100

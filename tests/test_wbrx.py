@@ -13,6 +13,8 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests.chain_gpu import bit_rows as _bit_rows
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_NO_DEVICE, ERR_SIZE, ERR_ALIGN = -1, -3, -6, -7
 
@@ -138,18 +140,6 @@ def _rows(rx, R, which=0):
         got[k] = [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), t1[j].tobytes())
                   for j, b in enumerate(blocks)]
     return got
-
-
-def _device_bytes(torch, ptr, shape, typestr):
-    import tetra_amd
-    return torch.as_tensor(tetra_amd.pkg.wbrx_binding._DeviceArray(ptr, shape, typestr), device="cuda")
-
-
-def _bit_rows(torch, rx, n_ch):
-    p, stride, pn = rx.bits_device(0, torch.cuda.current_stream())
-    nb = _device_bytes(torch, pn, (n_ch,), "<i4").cpu().numpy()
-    bits = _device_bytes(torch, p, (n_ch, stride), "|u1").cpu().numpy()
-    return [bits[c, : nb[c]].tobytes() for c in range(n_ch)]
 
 
 M_SMALL, D_SMALL, BINS_SMALL = 32, 16, [1, 7, 20, 31]
