@@ -1,6 +1,7 @@
 // handover_core.hpp -- lane code of the hand-over's two steps outside the synchroniser (include/ext/tetra_handover.h): the planting of
 // an heir from its donor (tetra_retune.hip: k_handover_plant, behind the plain reset of the heir) and the apply step that carries the
-// synchroniser's result word into the heir's cell (tetra_rx.hip: k_handover_apply, in front of the tracker).  The ASSIST state itself is
+// synchroniser's result word into the heir's cell (tetra_rx.hip: k_handover_apply, in front of the tracker), and of a stream gap
+// (include/ext/tetra_gap.h; tetra_retune.hip: k_resume_tail), in which a channel is its own donor.  The ASSIST state itself is
 // bsync_core.hpp's.  Host- and device-callable (tests/emul/handover_emul.cpp runs it on the host); plain stores only; one lane per channel.
 //
 // A header of its own beside retune_core.hpp: it works on the synchroniser's State and Assist and on the tracker's state and clock step
@@ -52,6 +53,59 @@ HO_HD void plant_channel(const View& v, int c, int donor, int32_t window, int32_
         as.slots_left = max_slots;
         tetra_lmac::TrackState hc = dc;
         hc.phy = tdma_steps(dc.phy, m);
+        v.cell[c] = hc;
+        v.state[c].state = bsync_core::kAssist;
+    }
+    v.assist[c] = as;
+}
+// ---- stream gaps (include/ext/tetra_gap.h): a channel restarts as its own heir after `elapsed` bits that never arrived ----------------------
+// The anchor of a channel: a frame at bit number a + 510 j is given the time q + j + 1 by the tracker; d = received bits - a.  LOCKED:
+// a = bitbuf_start_bitnum, q = the PHY time; ASSIST with the status PENDING: a = expect, q = the PHY time advanced by the slot periods
+// ASSIST has waited.  Anything else, or no scrambling code: not ok.  cell: the channel's cell with phy = q.
+struct Anchor {
+    int32_t ok;
+    int32_t d;
+    tetra_lmac::TrackState cell;
+};
+// the clock's period: 4 slots x 18 frames x 60 multiframes
+constexpr int32_t kTdmaPeriod = 4320;
+// Read before the channel is restarted.
+HO_HD Anchor gap_anchor(const View& v, int c) {
+    const bsync_core::State s = v.state[c];
+    const bsync_core::Assist as = v.assist[c];
+    Anchor an = { 0, 0, v.cell[c] };
+    const uint32_t rcv = s.bitbuf_start_bitnum + s.bits_in_buf;
+    if (an.cell.scramb_init == 0u) return an;
+    if (s.state == bsync_core::kLocked) {
+        an.ok = 1;
+        an.d = (int32_t)(rcv - s.bitbuf_start_bitnum);
+    } else if (s.state == bsync_core::kAssist && as.status == bsync_core::kHoPending) {
+        an.ok = 1;
+        an.d = (int32_t)(rcv - as.expect);
+        an.cell.phy = tdma_steps(an.cell.phy, as.waited);
+    }
+    return an;
+}
+// expect = 510 m - (d + elapsed) with the smallest m >= 0 for which expect >= W; 0 <= elapsed <= 2^31 - 1.  With elapsed = 0 on a LOCKED
+// channel (d = bits_in_buf) this is plant_expect.
+HO_HD int32_t gap_expect(int32_t d, uint32_t elapsed, int32_t window, int32_t& m) {
+    const long long need = (long long)d + (long long)elapsed + window;     // 510 m >= need
+    const long long mm = need <= 0 ? 0 : (need + bsync_core::kTs - 1) / bsync_core::kTs;
+    m = (int32_t)mm;
+    return (int32_t)(bsync_core::kTs * mm - ((long long)d + (long long)elapsed));
+}
+// Channel c behind its plain reset (State, bit buffer, cell and Assist all zero), from its own anchor: ASSIST around the frame start the
+// anchor's grid gives after the gap, the clock advanced by the slots that passed (m mod the clock's period steps: the same time).
+HO_HD void resume_channel(const View& v, int c, const Anchor& an, uint32_t elapsed, int32_t window, int32_t max_slots) {
+    bsync_core::Assist as = { bsync_core::kHoRefused, 0, 0, 0u, 0, 0, 0, 0 };
+    if (an.ok) {
+        int32_t m = 0;
+        as.status = bsync_core::kHoPending;
+        as.expect = (uint32_t)gap_expect(an.d, elapsed, window, m);
+        as.window = window;
+        as.slots_left = max_slots;
+        tetra_lmac::TrackState hc = an.cell;
+        hc.phy = tdma_steps(an.cell.phy, m % kTdmaPeriod);
         v.cell[c] = hc;
         v.state[c].state = bsync_core::kAssist;
     }

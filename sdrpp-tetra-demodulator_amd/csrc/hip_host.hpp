@@ -117,6 +117,8 @@ public:
         return e != hipSuccess ? e : alt_.reserve(sizeof(T) * (rows * row_elems + tail_elems));
     }
     hipError_t reset() { return hipMemset(cur_, 0, sizeof(T) * rows_ * row_); }
+    // the same on the stage's stream, behind the calls enqueued there and ahead of the next
+    hipError_t reset_on(hipStream_t s) { return hipMemsetAsync(cur_, 0, sizeof(T) * rows_ * row_, s); }
     operator T*() const { return cur_; }
     T* get() const { return cur_.get(); }
     // copy_new(dst, from_x) copies the from_x newest input rows to dst and returns its hipError_t.

@@ -30,6 +30,9 @@ TETRA_HIDDEN int bsync_tables(tetra_bsync_t* h, BsyncTables* out);
 // ... the hand-over's fields, allocated and zeroed on the first call (which waits for the device, once); from then on the handle
 // launches its ASSIST-capable kernels
 TETRA_HIDDEN int bsync_assist(tetra_bsync_t* h, void** out);
+// tetra_chan.hip: what tetra_chan_reset leaves -- delay line and carry cleared, the shift's phase reference at the next sample --,
+// enqueued on `stream` (the one the process calls use) with no host synchronisation (ext/tetra_gap.h)
+TETRA_HIDDEN int chan_restart(tetra_chan_t* h, void* stream);
 // tetra_resamp.hip: a handle that runs all its channels in place (16-byte lane units) becomes one that picks columns (8-byte units,
 // what TETRA_RESAMP_FLAG_NARROW_UNITS gives at create).  Same floats; the delay line's layout does not depend on the unit width.
 TETRA_HIDDEN int resamp_narrow_units(tetra_resamp_t* h);

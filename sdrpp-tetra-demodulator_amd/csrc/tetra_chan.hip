@@ -26,6 +26,7 @@
 #include "chan_design.hpp"
 #include "chan_fft_core.hpp"
 #include "hip_host.hpp"
+#include "retune_impl.hpp"
 
 namespace {
 
@@ -816,3 +817,15 @@ int tetra_chan_last_kernel_ms(tetra_chan_t* h, float* ms) {
 }
 
 }  // extern "C"
+
+// tetra_chan_reset's state without its host synchronisation (retune_impl.hpp; include/ext/tetra_gap.h): the clearing goes to the stream
+// the process calls use, behind the last call's carry and ahead of the next call's reads.
+int retune_impl::chan_restart(tetra_chan_t* h, void* stream) {
+    if (!h) return TETRA_ERR_ARG;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    HIP_TRY(h, h->line.reset_on(static_cast<hipStream_t>(stream)));
+    h->phase = 0;
+    h->consumed = 0;
+    return TETRA_OK;
+}

@@ -14,10 +14,15 @@
 // The kernels are a launch of one 64-lane workgroup per listed channel (lane code: retune_core.hpp): not a hot path.
 // A reset with donors (include/ext/tetra_handover.h) is the same reset with one more kernel behind k_reset_tail on the tail stream,
 // k_handover_plant (lane code: handover_core.hpp), which reads the donors' state as the last tail left it.
+// A stream gap (include/ext/tetra_gap.h) is the same reset with k_resume_tail in place of k_reset_tail: each listed channel reads its own
+// state before it clears it and resumes as its own heir.  The wideband handle's gap puts the front end's restart in front, on the
+// caller's stream: what tetra_wbrx_reset leaves, without its host synchronisation.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <vector>
 
+#include "../../include/ext/tetra_gap.h"
 #include "../../include/ext/tetra_handover.h"
 #include "../../include/tetra_retune.h"
 #include "handover_core.hpp"
@@ -69,6 +74,27 @@ __global__ __launch_bounds__(kLanes) void k_handover_plant(handover::View v, con
     handover::plant_channel(v, c, d, window, max_slots);
 }
 
+// A stream gap (include/ext/tetra_gap.h; lane code: handover_core.hpp): the tail part of a listed channel's restart as its own heir, in
+// one launch in place of k_reset_tail and the resets behind it.  Every lane reads the channel's anchor before any lane clears the
+// channel; lane 0 plants behind the clearing.  miss: zero words where the rule in force counts none.
+__global__ __launch_bounds__(kLanes) void k_resume_tail(retune::BsyncView b, retune::CellView cell, retune::CellView link, retune::CellView miss,
+                                                        retune::CellView assist, const int32_t* __restrict__ channels, int n_channels, uint32_t elapsed,
+                                                        int32_t window, int32_t max_slots) {
+    const int c = channels[blockIdx.x];
+    if (c < 0 || c >= n_channels) return;
+    const handover::View v = { reinterpret_cast<bsync_core::State*>(b.state), reinterpret_cast<bsync_core::Assist*>(assist.cell),
+                               reinterpret_cast<tetra_lmac::TrackState*>(cell.cell) };
+    const handover::Anchor an = handover::gap_anchor(v, c);
+    __syncthreads();
+    retune::reset_bsync_channel(b, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(cell, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(link, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(miss, c, threadIdx.x, kLanes);
+    retune::reset_cell_channel(assist, c, threadIdx.x, kLanes);
+    __syncthreads();
+    if (threadIdx.x == 0) handover::resume_channel(v, c, an, elapsed, window, max_slots);
+}
+
 // list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
 // history ring [hist][M] (a sibling of tetra_resamp.hip's k_pick_rows: same rows, one column each, out of the ring)
 __global__ __launch_bounds__(256) void k_retune_columns(const float* __restrict__ ring, int M, int hist, long long n_total, const int32_t* __restrict__ list,
@@ -103,11 +129,18 @@ bool handover_params(const tetra_handover_params_t* p, tetra_handover_params_t* 
     return out->window >= 0 && out->window <= bsync_core::kWindowMax && out->max_slots >= 1 && out->max_slots <= bsync_core::kAssistSlotsMax;
 }
 
+// a gap's parameters, or its header's defaults; false: out of range
+bool gap_params(const tetra_handover_params_t* p, tetra_handover_params_t* out) {
+    const tetra_handover_params_t def = { TETRA_GAP_DEFAULT_WINDOW, TETRA_GAP_DEFAULT_MAX_SLOTS };
+    return handover_params(p ? p : &def, out);
+}
+
 // The chain's part, for n > 0 channels listed on the device at d_channels (uploaded on s).  The caller marks the list's readers:
 // s, and *tail_reader (the tail stream when the chain has one of its own, else null).
 // d_donors (may be null: a plain reset): per listed channel its donor or -1, planted behind the reset with the parameters *p.
+// elapsed (may be null; never with donors): a stream gap of *elapsed bits -- every listed channel resumes as its own heir with *p.
 int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader, const int32_t* d_donors = nullptr,
-                  const tetra_handover_params_t* p = nullptr) {
+                  const tetra_handover_params_t* p = nullptr, const uint32_t* elapsed = nullptr) {
     retune::DemodView dv;
     retune::BsyncView bv;
     TETRA_TRY(retune_impl::demod_view(h->dem, &dv));
@@ -140,13 +173,18 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
         HIP_TRY(h, hipEventRecord(h->ev_reset, s));
         HIP_TRY(h, hipStreamWaitEvent(st, h->ev_reset, 0));
     }
-    hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
-    HIP_TRY(h, hipGetLastError());
-    if (mv.cell_words > 0) {
+    if (elapsed) {      // the whole tail part in one launch: the channel's own state is read before it is cleared
+        hipLaunchKernelGGL(k_resume_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, mv, av, d_channels, h->C, *elapsed, p->window, p->max_slots);
+        HIP_TRY(h, hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (!elapsed && mv.cell_words > 0) {
         hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, mv, d_channels, h->C);
         HIP_TRY(h, hipGetLastError());
     }
-    if (av.cell_words > 0) {      // a handle that has handed over: the listed channels' hand-over fields, like the miss counters ...
+    if (!elapsed && av.cell_words > 0) {      // a handle that has handed over: the listed channels' hand-over fields, like the miss counters ...
         hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, av, d_channels, h->C);
         HIP_TRY(h, hipGetLastError());
     }
@@ -170,15 +208,16 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
 }
 
 // tetra_rx_reset_channels_device, and with donors [n] and checked parameters tetra_rx_handover_channels_device: the list travels as
-// [n channels] or [n channels | n donors]
-int reset_channels(tetra_rx* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p, void* hip_stream) {
+// [n channels] or [n channels | n donors].  elapsed != null (and no donors): tetra_rx_resume_channels_device.
+int reset_channels(tetra_rx* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p, void* hip_stream,
+                   const uint32_t* elapsed = nullptr) {
     if (n == 0) return TETRA_OK;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     std::vector<int32_t> both;
     void* fields = nullptr;      // the handle's first hand-over allocates them; from here on its tails run the ASSIST-capable kernels
-    if (donors) TETRA_TRY(retune_impl::bsync_assist(h->bs, &fields));
+    if (donors || elapsed) TETRA_TRY(retune_impl::bsync_assist(h->bs, &fields));
     if (donors) {
         both.assign(channels, channels + n);
         both.insert(both.end(), donors, donors + n);
@@ -188,7 +227,7 @@ int reset_channels(tetra_rx* h, const int32_t* channels, const int32_t* donors, 
     const int k = donors ? h->to_device.push(both.data(), 2 * n, 2 * h->C, s, &d_list, &e) : h->to_device.push(channels, n, h->C, s, &d_list, &e);
     if (k < 0) HIP_TRY(h, e);
     hipStream_t tail = nullptr;
-    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail, donors ? d_list + n : nullptr, p));
+    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail, donors ? d_list + n : nullptr, p, elapsed));
     HIP_TRY(h, h->to_device.done(k, 0, s));
     if (tail) HIP_TRY(h, h->to_device.done(k, 1, tail));
     return TETRA_OK;
@@ -254,6 +293,48 @@ int wbrx_retune(tetra_wbrx* h, const int32_t* bins, const int32_t* donors, const
     return rc;
 }
 
+// A stream gap of a wideband handle (include/ext/tetra_gap.h), all on the caller's stream behind the last call: the front end as
+// tetra_wbrx_reset leaves it, then every slot resumed as its own heir after the bits the lost samples would have become.
+int wbrx_gap(tetra_wbrx* h, int64_t n_lost, const tetra_handover_params_t* p, int64_t* elapsed_bits_out, void* hip_stream) {
+    tetra_resamp* rs = h->rs;
+    tetra_rx* rx = h->rx;
+    const tetra_demod_config_t& dc = rx->cfg.demod;
+    const double bits = std::floor((double)n_lost * (double)rs->I * 2.0 * dc.symbolrate / ((double)rs->DN * (double)h->cfg.chan.decimation * dc.samplerate) + 0.5);
+    if (!(bits >= 0.0 && bits <= (double)TETRA_GAP_MAX_ELAPSED_BITS)) return TETRA_ERR_ARG;
+    const uint32_t elapsed = (uint32_t)bits;
+    DeviceGuard g(h->device);
+    if (!g.ok) return TETRA_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    void* fields = nullptr;      // the chain's first gap or hand-over allocates them
+    TETRA_TRY(retune_impl::bsync_assist(rx->bs, &fields));
+    const int S = h->n_bins;
+    std::vector<int32_t> list((size_t)S);
+    for (int j = 0; j < S; j++) list[(size_t)j] = j;
+    if (h->done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+    int32_t* d_list = nullptr;
+    hipError_t e = hipSuccess;
+    const int k = h->to_device.push(list.data(), S, 3 * S, s, &d_list, &e);      // (the ring's blocks at the size the retunes use)
+    if (k < 0) HIP_TRY(h, e);
+    // From here on the handle is committed to the gap; a failure below is reported and leaves the stream undefined until tetra_wbrx_reset.
+    int rc = retune_impl::chan_restart(h->chan, s);
+    hipError_t late = rs->hist.reset_on(s);
+    rs->n_total = 0;
+    rs->m_next = 0;
+    if (late == hipSuccess) late = hipMemsetAsync(h->ring.get(), 0, h->ring.bytes(), s);
+    hipStream_t tail = nullptr;
+    if (rc == TETRA_OK && late == hipSuccess) rc = reset_enqueue(rx, d_list, S, s, &tail, nullptr, p, &elapsed);
+    if (late == hipSuccess) late = h->to_device.done(k, 0, s);
+    if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
+    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
+    if (late == hipSuccess) h->done_recorded = true;
+    else if (rc == TETRA_OK) {
+        h->last_hip = (int)late;
+        rc = TETRA_ERR_HIP;
+    }
+    if (rc == TETRA_OK && elapsed_bits_out) *elapsed_bits_out = (int64_t)elapsed;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,6 +359,24 @@ int tetra_rx_handover_channels_device(tetra_rx_t* h, const int32_t* channels, co
     for (int i = 0; i < n; i++)
         if (donors[i] < -1 || donors[i] >= h->C || (donors[i] >= 0 && heir[(size_t)donors[i]])) return TETRA_ERR_ARG;
     return reset_channels(h, channels, donors, n, &prm, hip_stream);
+}
+
+int tetra_rx_resume_channels_device(tetra_rx_t* h, const int32_t* channels, int n, int64_t elapsed_bits, const tetra_handover_params_t* p,
+                                    void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
+    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_gap resumes its slots
+    tetra_handover_params_t prm;
+    if (!distinct_in_range(channels, n, h->C) || !gap_params(p, &prm) || elapsed_bits < 0 || elapsed_bits > TETRA_GAP_MAX_ELAPSED_BITS) return TETRA_ERR_ARG;
+    const uint32_t elapsed = (uint32_t)elapsed_bits;
+    return reset_channels(h, channels, nullptr, n, &prm, hip_stream, &elapsed);
+}
+
+int tetra_wbrx_gap(tetra_wbrx_t* h, int64_t n_lost, const tetra_handover_params_t* p, int64_t* elapsed_bits_out, void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    tetra_handover_params_t prm;
+    if (!h || n_lost < 0 || !gap_params(p, &prm)) return TETRA_ERR_ARG;
+    return wbrx_gap(h, n_lost, &prm, elapsed_bits_out, hip_stream);
 }
 
 int tetra_wbrx_retune(tetra_wbrx_t* h, const int32_t* bins, void* hip_stream) {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ext/tetra_carrier_offset.h"
+#include "../../include/ext/tetra_gap.h"
 #include "../../include/ext/tetra_iqcond.h"
 #include "../../include/tetra_shift.h"
 #include "hip_host.hpp"
@@ -233,6 +234,7 @@ int tetra_wbrx_reset(tetra_wbrx_t* h) {
     h->calls = 0;
     h->n_chan = 0;
     h->n_res[0] = h->n_res[1] = 0;
+    h->at_origin = false;
     return TETRA_OK;
 }
 
@@ -245,6 +247,24 @@ int tetra_wbrx_process_device_cs16(tetra_wbrx_t* h, const int16_t* d_x, int n_in
 int tetra_wbrx_process_device_cs8(tetra_wbrx_t* h, const int8_t* d_x, int n_in, void* hip_stream) {
     return process_any(h, kFmtCs8, d_x, n_in, hip_stream);
 }
+// The process call for a buffer with the driver's sample index (include/ext/tetra_gap.h): a jump forward is a gap, reported to
+// tetra_wbrx_gap ahead of the call; everything either of the two refuses is refused here, before anything is enqueued.
+int tetra_wbrx_process_device_at(tetra_wbrx_t* h, const void* d_x, int fmt, int n_in, int64_t first_index, const tetra_handover_params_t* p,
+                                 void* hip_stream) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    static_assert(kFmtC32 == TETRA_IQ_FMT_C64 && kFmtCs16 == TETRA_IQ_FMT_CS16 && kFmtCs8 == TETRA_IQ_FMT_CS8, "process_any's formats are the header's");
+    if (!h || fmt < 0 || fmt > kFmtCs8 || (!d_x && n_in > 0)) return TETRA_ERR_ARG;
+    if (n_in < 0 || n_in > h->max_in) return TETRA_ERR_SIZE;
+    if ((uintptr_t)d_x & (kFmtBytes[fmt] - 1)) return TETRA_ERR_ALIGN;
+    if (h->at_origin && first_index < h->at_next) return TETRA_ERR_ARG;          // an overlap
+    if (h->at_origin && first_index > h->at_next) TETRA_TRY(tetra_wbrx_gap(h, first_index - h->at_next, p, nullptr, hip_stream));
+    h->at_origin = true;
+    h->at_next = first_index;          // (a gap has been taken: a process call that fails behind it does not take it twice)
+    TETRA_TRY(process_any(h, fmt, d_x, n_in, hip_stream));
+    h->at_next = first_index + n_in;
+    return TETRA_OK;
+}
+
 int tetra_wbrx_process(tetra_wbrx_t* h, const float* x, int n_in) { return process_host(h, kFmtC32, x, n_in); }
 int tetra_wbrx_process_cs16(tetra_wbrx_t* h, const int16_t* x, int n_in) { return process_host(h, kFmtCs16, x, n_in); }
 

@@ -38,4 +38,7 @@ struct tetra_wbrx {
     long long retunes = 0, slots_changed = 0;
     // per-carrier offsets (include/ext/tetra_carrier_offset.h): the resampler handle holds the list in force and its device tables
     ListRing mix_to_device;                 // a new list's tables on their way to the device
+    // stream gaps (include/ext/tetra_gap.h)
+    bool at_origin = false;                 // tetra_wbrx_process_device_at has set the stream's origin (forgotten by tetra_wbrx_reset)
+    long long at_next = 0;                  // ... and expects this sample index next
 };

@@ -11,6 +11,7 @@
 
 #include "ext/tetra_aach_soft.h"
 #include "ext/tetra_biterr.h"
+#include "ext/tetra_gap.h"
 #include "ext/tetra_handover.h"
 #include "ext/tetra_list.h"
 #include "ext/tetra_rx_out_ext.h"
@@ -230,6 +231,12 @@ public:
         if (channels.size() != donors.size()) return TETRA_ERR_ARG;
         return tetra_rx_handover_channels_device(h_, channels.data(), donors.data(), (int)channels.size(), p, hipStream);
     }
+    // A stream gap (ext/tetra_gap.h): the listed channels restart as their own heirs after elapsedBits bits that never arrived -- a channel
+    // that was locked keeps its scrambling code and its TDMA clock, advanced by the slots that passed; p = null: the header's defaults.
+    // Enqueued on hipStream, not waited for.
+    int resume(const std::vector<int32_t>& channels, int64_t elapsedBits, const tetra_handover_params_t* p = nullptr, void* hipStream = nullptr) {
+        return tetra_rx_resume_channels_device(h_, channels.data(), (int)channels.size(), elapsedBits, p, hipStream);
+    }
     // ... and every channel's hand-over status
     int handoverStatus(std::vector<tetra_handover_status_t>& out) { return table(tetra_rx_get_handover, out); }
     // the PI4DQPSK setters of the demodulators inside (tetra_demod_set_param ids); waits for work in flight first
@@ -388,6 +395,25 @@ public:
         }
         for (size_t s = 0; s < shards_.size(); s++) {
             const int rc = shards_[s]->bank.handOver(ch[s], dn[s], p, streams ? streams[s] : nullptr);
+            if (rc != TETRA_OK) return rc;
+        }
+        return TETRA_OK;
+    }
+    // A stream gap (ext/tetra_gap.h), in the bank's channel numbers: every shard is told its own entries.  Everything a shard would refuse
+    // is refused here (TETRA_ERR_ARG), before the first shard is told anything.  streams as for handOver.
+    int resume(const std::vector<int32_t>& channels, int64_t elapsedBits, const tetra_handover_params_t* p = nullptr, void* const* streams = nullptr) {
+        if (elapsedBits < 0 || elapsedBits > TETRA_GAP_MAX_ELAPSED_BITS) return TETRA_ERR_ARG;
+        if (p && (p->window < 0 || p->window > 127 || p->max_slots < 1 || p->max_slots > 255)) return TETRA_ERR_ARG;
+        std::vector<char> seen((size_t)channels_, 0);
+        std::vector<std::vector<int32_t>> ch(shards_.size());
+        for (int32_t c : channels) {
+            if (c < 0 || c >= channels_ || seen[(size_t)c]) return TETRA_ERR_ARG;
+            seen[(size_t)c] = 1;
+            const int s = shardOf(c);
+            ch[(size_t)s].push_back(c - shards_[(size_t)s]->first);
+        }
+        for (size_t s = 0; s < shards_.size(); s++) {
+            const int rc = shards_[s]->bank.resume(ch[s], elapsedBits, p, streams ? streams[s] : nullptr);
             if (rc != TETRA_OK) return rc;
         }
         return TETRA_OK;

@@ -126,6 +126,18 @@ def handover_params_arg(window, max_slots):
                                   HANDOVER_DEFAULT_MAX_SLOTS if max_slots is None else int(max_slots)))
 
 
+# include/ext/tetra_gap.h (channels restarted after missing samples keep frame timing, cell and clock): the chain's share
+GAP_DEFAULT_WINDOW, GAP_DEFAULT_MAX_SLOTS, GAP_MAX_ELAPSED_BITS = 8, 72, (1 << 31) - 1
+GAP_ABI = {"tetra_rx_resume_channels_device": (i32, [vp, vp, i32, i64, P(HandoverParams), vp])}
+
+
+def gap_params_arg(window, max_slots):
+    """handover_params_arg with the gap header's defaults."""
+    if window is None and max_slots is None:
+        return None
+    return C.byref(HandoverParams(GAP_DEFAULT_WINDOW if window is None else int(window), GAP_DEFAULT_MAX_SLOTS if max_slots is None else int(max_slots)))
+
+
 # include/ext/tetra_rx_out_ext.h (the opt-in row extras and per-channel state through the one-step hand-off)
 OUT_EXT_ABI = {
     "tetra_rx_out_bound_ext": (i32, [vp, i32, i32, i32, P(u64)]),
@@ -150,15 +162,16 @@ RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 RX_OUT_EXT_EXPORTS = list(OUT_EXT_ABI)
 RX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
+RX_GAP_EXPORTS = list(GAP_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
     return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
-                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI, **AACH_SOFT_ABI},
+                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI, **AACH_SOFT_ABI, **GAP_ABI},
                    optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
-                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS + list(AACH_SOFT_ABI))
+                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS + list(AACH_SOFT_ABI) + RX_GAP_EXPORTS)
 
 
 def type1_bits(kind):
@@ -217,6 +230,15 @@ class RxChain:
             raise ValueError("handover_channels takes a donor (or -1) per channel")
         call(self._lib.tetra_rx_handover_channels_device, self._h, ptr(ch) if ch.size else None, ptr(dn) if dn.size else None, int(ch.size),
              handover_params_arg(window, max_slots), stream_ptr(stream))
+
+    def resume(self, elapsed_bits, channels=None, window=None, max_slots=None, stream=None):
+        """tetra_rx_resume_channels_device (include/ext/tetra_gap.h): the listed channels (None: all) restart as reset_channels restarts
+        them, after `elapsed_bits` bits that never arrived, and a channel that was locked keeps its scrambling code, its TDMA clock
+        advanced by the slots that passed, and looks for its first burst `window` bits either side of where its own frame grid puts it.
+        handover_status() says what became of each.  Enqueued, not waited for."""
+        ch = np.arange(self.n_channels, dtype=np.int32) if channels is None else np.ascontiguousarray(np.asarray(channels, np.int64).astype(np.int32).reshape(-1))
+        call(self._lib.tetra_rx_resume_channels_device, self._h, ptr(ch) if ch.size else None, int(ch.size), int(elapsed_bits),
+             gap_params_arg(window, max_slots), stream_ptr(stream))
 
     def handover_status(self, first=0, count=None):
         """tetra_rx_get_handover: per channel (state HANDOVER_*, slot periods waited, found - expected frame start in bits)."""

@@ -8,7 +8,7 @@ from . import binding as B
 from ._ffi import P, call, declare, f64, i32, i64, ptr, stream_ptr, u32, vp
 from .binding import load_library
 from .chan_binding import ChanConfig, IqMap, _get_input_map, _set_input_map, input_map_from_stats, iq_stats
-from .rx_binding import HandoverParams, RxChain, RxConfig, handover_params_arg
+from .rx_binding import HandoverParams, RxChain, RxConfig, gap_params_arg, handover_params_arg
 from .rx_binding import _lib as _rx_lib
 
 
@@ -59,13 +59,20 @@ CARRIER_OFFSET_ABI = {
 }
 WBRX_EXPORTS, WBRX_SHIFT_EXPORTS, WBRX_RETUNE_EXPORTS = list(SIGNATURES), list(SHIFT_SIGNATURES), list(RETUNE_SIGNATURES)
 WBRX_HANDOVER_EXPORTS = list(HANDOVER_ABI)
+# include/ext/tetra_gap.h (missing capture samples: the slots keep frame timing, cell and clock): the wideband receiver's share
+GAP_ABI = {
+    "tetra_wbrx_gap": (i32, [vp, i64, P(HandoverParams), P(i64), vp]),
+    "tetra_wbrx_process_device_at": (i32, [vp, vp, i32, i32, i64, P(HandoverParams), vp]),
+}
+WBRX_GAP_EXPORTS = list(GAP_ABI)
+IQ_FMT_C64, IQ_FMT_CS16, IQ_FMT_CS8 = range(3)          # TETRA_IQ_FMT_* (include/ext/tetra_iqcond.h)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the shift, the retune and the input map)
-    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI, **HANDOVER_ABI, **CARRIER_OFFSET_ABI},
-                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI) + WBRX_HANDOVER_EXPORTS + list(CARRIER_OFFSET_ABI))
+    return declare(load_library(), {**SIGNATURES, **SHIFT_SIGNATURES, **RETUNE_SIGNATURES, **IQCOND_ABI, **HANDOVER_ABI, **CARRIER_OFFSET_ABI, **GAP_ABI},
+                   optional=WBRX_SHIFT_EXPORTS + WBRX_RETUNE_EXPORTS + list(IQCOND_ABI) + WBRX_HANDOVER_EXPORTS + list(CARRIER_OFFSET_ABI) + WBRX_GAP_EXPORTS)
 
 
 def carrier_offset_from_hz(offset_hz, sample_rate_hz, decimation):
@@ -103,6 +110,9 @@ class _ChainView(RxChain):
 
     def handover_channels(self, channels, donors, window=None, max_slots=None, stream=None):
         raise TypeError("the wideband receiver's slots are handed over through WidebandRx.retune(bins, donors=...)")
+
+    def resume(self, elapsed_bits, channels=None, window=None, max_slots=None, stream=None):
+        raise TypeError("the wideband receiver's slots resume through WidebandRx.gap() or process_device_at()")
 
     def process(self, iq):
         raise TypeError("the wideband receiver's chain is fed through WidebandRx.process*()")
@@ -263,6 +273,24 @@ class WidebandRx:
         if n_in is None:
             n_in = d_x.numel() // 2 if name != "tetra_wbrx_process_device" else d_x.numel()
         call(getattr(self._lib, name), self._h, ptr(d_x), int(n_in), stream_ptr(stream))
+
+    def gap(self, n_lost, window=None, max_slots=None, stream=None):
+        """tetra_wbrx_gap (include/ext/tetra_gap.h): `n_lost` capture samples are missing between the last process call and the next.  The
+        front end restarts as after reset() -- with no host synchronisation, and keeping bins, shift, offsets and input map -- and every
+        slot that was locked keeps its scrambling code and its TDMA clock, advanced by the slots that passed.  Enqueued on `stream` (the
+        one the process calls use).  -> the elapsed bits the lost samples stand for; handover_status() says what became of each slot."""
+        g = C.c_int64(0)
+        call(self._lib.tetra_wbrx_gap, self._h, int(n_lost), gap_params_arg(window, max_slots), C.byref(g), stream_ptr(stream))
+        return int(g.value)
+
+    def process_device_at(self, d_x, first_index, n_in=None, window=None, max_slots=None, stream=None):
+        """tetra_wbrx_process_device_at: process_device for a buffer whose first sample has the driver's sample index `first_index`.  The
+        first call sets the origin; an index ahead of the expected one is a gap() of the difference, one behind it is refused."""
+        dt = str(getattr(d_x, "dtype", ""))
+        fmt = {"torch.int16": IQ_FMT_CS16, "torch.int8": IQ_FMT_CS8}.get(dt, IQ_FMT_C64)
+        if n_in is None:
+            n_in = d_x.numel() // 2 if fmt != IQ_FMT_C64 else d_x.numel()
+        call(self._lib.tetra_wbrx_process_device_at, self._h, ptr(d_x), fmt, int(n_in), int(first_index), gap_params_arg(window, max_slots), stream_ptr(stream))
 
     def bins(self):
         out = np.zeros(max(self.n_bins, 1), np.int32)
