@@ -1,7 +1,7 @@
 """How far the frame start a resumed slot finds lies from the one the gap rule expects: the number the gap's default window
 (include/ext/tetra_gap.h, TETRA_GAP_DEFAULT_WINDOW) rests on, and the time of the gap call.  Needs a GPU: the wideband handle itself.
 
-Per Es/N0 (11, 20, 25 dB per carrier): tests/test_handover.py's band (32 bins at 800 kHz; a control carrier, a traffic carrier, a carrier of
+Per Es/N0 (11, 20, 25 dB per carrier): tests/restart_gpu.py's band (32 bins at 800 kHz; a control carrier, a traffic carrier, a carrier of
 another cell, all frame-synchronous) is fed up to the first call boundary (17.6 slots); then a random number of samples is left out --
 drawn uniformly from what the capture leaves room for, 0 .. 48 slot periods, so that the elapsed bits G = n_lost * 0.045 fall anywhere
 between two bits and the channeliser's frame grid (16 samples) and the resampler's phase restart anywhere --, tetra_wbrx_gap is told, and
@@ -34,7 +34,7 @@ def main():
     import torch
     import tetra_amd
     pkg = tetra_amd.pkg
-    from tests.test_handover import BIN_A, BIN_B, BIN_C, BIN_EMPTY, CALL, D_BAND, M_BAND, _band_capture
+    from tests.restart_gpu import BIN_A, BIN_B, BIN_C, BIN_EMPTY, CALL, D_BAND, M_BAND, band_capture as _band_capture
     bins = [BIN_A, BIN_B, BIN_C, BIN_EMPTY]
     result = {"trials": args.trials, "bits_per_sample": 0.045, "by_esn0": {}}
     largest = 0

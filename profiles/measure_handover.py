@@ -1,6 +1,6 @@
 """What the retune with a donor (include/ext/tetra_handover.h) gains and costs.
 
-  --first-block   tests/test_handover.py's band (one base station on 32 bins: control carrier A, traffic carrier B with one SYNC burst per
+  --first-block   tests/restart_gpu.py's band (one base station on 32 bins: control carrier A, traffic carrier B with one SYNC burst per
                   multiframe, 0.25 s calls, slot 1 moved onto B just behind B's SYNC burst) at Es/N0 25, 20 and 11 dB: slot periods from the
                   move to the moved slot's first CRC-good NDB or SCH/F block with a donor, its hand-over status, and the same for the plain
                   retune (B's next SYNC burst is 70.4 slot periods after the move; the capture ends 78 after it)
@@ -25,16 +25,18 @@ OUT = os.path.join(ROOT, "profiles", "r21", "handover.json")
 
 
 def first_block(pkg, torch):
-    from tests import test_handover as T
+    from tests import restart_gpu as T
     R = pkg.rx_binding
+    moved = [T.BIN_A, T.BIN_B2, T.BIN_B]
     traffic = (R.KIND_NDB1, R.KIND_NDB2, R.KIND_SCH_F)
     move_bit = T.CALL * 36000 // 800000
     out = {"move_at_slot": round(move_bit / 510, 2), "next_sync_burst_of_B_at_slot": T.B_SYNC_SLOTS[2], "capture_slots": T.N_SLOTS, "by_esn0": {}}
     for esn0 in (25.0, 20.0, 11.0):
-        xs = T._band_capture(torch, pkg.synth, esn0_db=esn0)
+        xs = T.band_capture(torch, pkg.synth, esn0_db=esn0)
         row = {}
         for name, donors in (("with_donor", [-1, 0, -1]), ("plain", None)):
-            snaps, status, wb = T._band_run(pkg, torch, xs, [T.BIN_A, T.BIN_EMPTY, T.BIN_B], move=[T.BIN_A, T.BIN_B2, T.BIN_B], donors=donors)
+            wb = pkg.WidebandRx([T.BIN_A, T.BIN_EMPTY, T.BIN_B], n_channels=T.M_BAND, decimation=T.D_BAND, max_in=T.CALL)
+            snaps, status = T.drive(pkg, torch, wb, xs, T.band_calls(xs.shape[0]), {1: lambda w: w.retune(moved, donors=donors)})
             rows = [(r[1], k) for s in snaps[1:] for k in traffic for r in s[1]["rows"][k] if r[2]]
             all_rows = sum(len(s[1]["rows"][k]) for s in snaps[1:] for k in traffic)
             wit = sum(1 for s in snaps[1:] for k in traffic for r in s[2]["rows"][k] if r[2])

@@ -75,7 +75,7 @@ def measure(pkg, torch, xs, mode, n_blocks, warmup, reps):
 def rocprof_rows(db):
     """The retune's own launches and the per-block kernels next to them (rocpd `top_kernels` view, durations in us)."""
     import sqlite3
-    keep = ("k_keep_rows", "k_retune_columns", "k_reset_demod", "k_reset_tail", "resample", "pick_rows", "channelise", "k_fused", "k_burst_sync")
+    keep = ("k_keep_rows", "k_retune_columns", "k_reset_demod", "k_restart_tail", "resample", "pick_rows", "channelise", "k_fused", "k_burst_sync")
     cur = sqlite3.connect(db).cursor()
     rows = cur.execute("select name, total_calls, total_duration, average, percentage from top_kernels").fetchall()
     return [{"kernel": n, "calls": int(c), "total_us": round(t, 1), "avg_us": round(a, 2), "percent": round(p, 2)}

@@ -113,6 +113,25 @@ RT_HD void reset_cell_channel(const CellView& v, int c, int lane, int lanes) {
     zero_u32(v.cell + (long long)c * v.cell_words, v.cell_words, lane, lanes);
 }
 
+// The tail's per-channel tables, all of them: what a restart of a channel clears behind the demodulator.  A table the handle does not
+// keep, or miss counters that the rule in force does not count, has zero words and is skipped.
+struct TailView {
+    BsyncView sync;                           // the synchroniser's State and bit buffer
+    CellView cell;                            // tetra_lmac_cell_state_t
+    CellView link;                            // tetra_rx_link_t (TETRA_RX_FLAG_BITERR)
+    CellView miss;                            // the tolerant lock's miss counter (tetra_sync_tol.h)
+    CellView assist;                          // the hand-over fields (bsync_core.hpp: Assist), from a handle's first hand-over or gap on
+};
+
+// Every table of TailView for channel c.  The list of tables exists here and nowhere else: the kernel and the host emulations call this.
+RT_HD void reset_tail_channel(const TailView& v, int c, int lane, int lanes) {
+    reset_bsync_channel(v.sync, c, lane, lanes);
+    reset_cell_channel(v.cell, c, lane, lanes);
+    reset_cell_channel(v.link, c, lane, lanes);
+    reset_cell_channel(v.miss, c, lane, lanes);
+    reset_cell_channel(v.assist, c, lane, lanes);
+}
+
 // The wideband receiver's history ring: the channeliser's newest `hist` frames of all M bins, frame a (counted from the stream's
 // start) in row a mod hist.  keep_row: element i of the `rows` newest frames of a call that brought n_in frames after n0 earlier ones.
 RT_HD void keep_element(const float* x, int M, long long n0, int n_in, int rows, int hist, long long i, float* ring) {

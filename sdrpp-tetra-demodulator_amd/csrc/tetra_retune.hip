@@ -5,18 +5,17 @@
 // reset between call k and call k + 1 is split by stream:
 //
 //   caller's stream  [wait: demodulator k]  (wideband: bin list, delay-line columns)  k_reset_demod           (event ev_reset)
-//   tail stream      [behind tail k, wait ev_reset]  k_reset_tail: synchroniser state + bit buffer, cell state
+//   tail stream      [behind tail k, wait ev_reset]  k_restart_tail: the tail's per-channel tables, and the planting
 //
 // and call k + 1 is ordered behind both: its demodulator waits for ev_reset, its tail runs on the tail stream.  The events of call k
 // (ev_demod, ev_tail, the wideband ev_done) are recorded again behind the reset, so whoever waits for that call -- tetra_rx_wait,
 // the state readers, the call after next -- also waits for the reset.  Call k's results are not touched: they stay fetchable.
 //
 // The kernels are a launch of one 64-lane workgroup per listed channel (lane code: retune_core.hpp): not a hot path.
-// A reset with donors (include/ext/tetra_handover.h) is the same reset with one more kernel behind k_reset_tail on the tail stream,
-// k_handover_plant (lane code: handover_core.hpp), which reads the donors' state as the last tail left it.
-// A stream gap (include/ext/tetra_gap.h) is the same reset with k_resume_tail in place of k_reset_tail: each listed channel reads its own
-// state before it clears it and resumes as its own heir.  The wideband handle's gap puts the front end's restart in front, on the
-// caller's stream: what tetra_wbrx_reset leaves, without its host synchronisation.
+// A reset with donors (include/ext/tetra_handover.h) and a stream gap (include/ext/tetra_gap.h) are the same two launches: k_restart_tail
+// reads the anchor of the channel's source -- its donor as the last tail left it, or the channel itself -- before it clears the channel,
+// and plants behind the clearing (lane code: handover_core.hpp).  The wideband handle's gap puts the front end's restart in front, on
+// the caller's stream: what tetra_wbrx_reset leaves, without its host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -45,54 +44,24 @@ __global__ __launch_bounds__(kLanes) void k_reset_demod(retune::DemodView v, ret
     retune::reset_soft_channel(soft, c, threadIdx.x, kLanes);
 }
 
-// link: the channels' link figures as words (tetra_rx_link_t, TETRA_RX_FLAG_BITERR; no words without the flag), zeroed like the cell state
-__global__ __launch_bounds__(kLanes) void k_reset_tail(retune::BsyncView b, retune::CellView cell, retune::CellView link, const int32_t* __restrict__ channels,
-                                                       int n_channels) {
+// The tail part of every restart -- plain reset, hand-over, stream gap -- of listed channel c: the anchor of its source is read, then
+// all lanes clear the tail's tables of c (retune_core.hpp: reset_tail_channel), then lane 0 plants (handover_core.hpp).  The source is
+// c itself (own), donors[i], or none: a plain reset (donors null) or a hand-over entry with donor -1, where nothing is planted and the
+// hand-over fields stay zero (status NONE).  A donor is never an heir -- the host has checked it --, so no workgroup clears what
+// another reads; a channel that is its own source is read and cleared by one workgroup, the barrier between.
+__global__ __launch_bounds__(kLanes) void k_restart_tail(retune::TailView t, const int32_t* __restrict__ channels, const int32_t* __restrict__ donors, int own,
+                                                         int n_channels, uint32_t elapsed, int32_t window, int32_t max_slots) {
     const int c = channels[blockIdx.x];
-    if (c < 0 || c >= n_channels) return;
-    retune::reset_bsync_channel(b, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(cell, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(link, c, threadIdx.x, kLanes);
-}
-
-// the synchroniser's miss counters under the tolerant lock (tetra_sync_tol.h), one word per channel: a launch of its own behind
-// k_reset_tail, made only for a chain that runs that rule
-__global__ __launch_bounds__(kLanes) void k_reset_miss(retune::CellView miss, const int32_t* __restrict__ channels, int n_channels) {
-    const int c = channels[blockIdx.x];
-    if (c < 0 || c >= n_channels) return;
-    retune::reset_cell_channel(miss, c, threadIdx.x, kLanes);
-}
-
-// The hand-over's planting (include/ext/tetra_handover.h; lane code: handover_core.hpp), behind k_reset_tail and the reset of the listed
-// channels' Assist: a thread per entry, heirs[i] from donors[i] (-1: a plain restart).  The host has checked that no donor is an heir.
-__global__ __launch_bounds__(kLanes) void k_handover_plant(handover::View v, const int32_t* __restrict__ heirs, const int32_t* __restrict__ donors, int n,
-                                                           int n_channels, int32_t window, int32_t max_slots) {
-    const int i = (int)blockIdx.x * kLanes + (int)threadIdx.x;
-    if (i >= n) return;
-    const int c = heirs[i], d = donors[i];
-    if (c < 0 || c >= n_channels || d < 0 || d >= n_channels) return;
-    handover::plant_channel(v, c, d, window, max_slots);
-}
-
-// A stream gap (include/ext/tetra_gap.h; lane code: handover_core.hpp): the tail part of a listed channel's restart as its own heir, in
-// one launch in place of k_reset_tail and the resets behind it.  Every lane reads the channel's anchor before any lane clears the
-// channel; lane 0 plants behind the clearing.  miss: zero words where the rule in force counts none.
-__global__ __launch_bounds__(kLanes) void k_resume_tail(retune::BsyncView b, retune::CellView cell, retune::CellView link, retune::CellView miss,
-                                                        retune::CellView assist, const int32_t* __restrict__ channels, int n_channels, uint32_t elapsed,
-                                                        int32_t window, int32_t max_slots) {
-    const int c = channels[blockIdx.x];
-    if (c < 0 || c >= n_channels) return;
-    const handover::View v = { reinterpret_cast<bsync_core::State*>(b.state), reinterpret_cast<bsync_core::Assist*>(assist.cell),
-                               reinterpret_cast<tetra_lmac::TrackState*>(cell.cell) };
-    const handover::Anchor an = handover::gap_anchor(v, c);
+    if (c < 0 || c >= n_channels) return;          // (the host has checked the lists)
+    int src = own ? c : donors ? donors[blockIdx.x] : -1;
+    if (src >= n_channels) src = -1;
+    const handover::View v = handover::view_of(t);
+    handover::Anchor an = {};
+    if (src >= 0) an = handover::anchor_of(v, src, own != 0);
     __syncthreads();
-    retune::reset_bsync_channel(b, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(cell, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(link, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(miss, c, threadIdx.x, kLanes);
-    retune::reset_cell_channel(assist, c, threadIdx.x, kLanes);
+    retune::reset_tail_channel(t, c, threadIdx.x, kLanes);
     __syncthreads();
-    if (threadIdx.x == 0) handover::resume_channel(v, c, an, elapsed, window, max_slots);
+    if (src >= 0 && threadIdx.x == 0) handover::plant(v, c, an, elapsed, window, max_slots);
 }
 
 // list = [n slots | n bins]: bins[slot_i] = bin_i, and the slot's column of the resampler's delay line line [hist][C] from the
@@ -135,12 +104,22 @@ bool gap_params(const tetra_handover_params_t* p, tetra_handover_params_t* out) 
     return handover_params(p ? p : &def, out);
 }
 
-// The chain's part, for n > 0 channels listed on the device at d_channels (uploaded on s).  The caller marks the list's readers:
-// s, and *tail_reader (the tail stream when the chain has one of its own, else null).
-// d_donors (may be null: a plain reset): per listed channel its donor or -1, planted behind the reset with the parameters *p.
-// elapsed (may be null; never with donors): a stream gap of *elapsed bits -- every listed channel resumes as its own heir with *p.
-int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader, const int32_t* d_donors = nullptr,
-                  const tetra_handover_params_t* p = nullptr, const uint32_t* elapsed = nullptr) {
+// What the listed channels restart from, made by one of the three functions: a plain reset, a hand-over (per listed channel its donor
+// or -1, with checked parameters), or a stream gap of `elapsed` bits in which every listed channel is its own heir.
+struct Restart {
+    enum Kind { kPlain, kFromDonors, kOwnHeir } kind;
+    const int32_t* donors;               // kFromDonors: [n], the caller's list on the way in, the device's at the launch
+    tetra_handover_params_t p;           // kFromDonors, kOwnHeir
+    uint32_t elapsed;                    // kOwnHeir
+    static Restart plain() { return { kPlain, nullptr, { 0, 0 }, 0u }; }
+    static Restart from_donors(const int32_t* donors, const tetra_handover_params_t& p) { return { kFromDonors, donors, p, 0u }; }
+    static Restart own_heir(const tetra_handover_params_t& p, uint32_t elapsed) { return { kOwnHeir, nullptr, p, elapsed }; }
+    bool plants() const { return kind != kPlain; }
+};
+
+// The chain's part, for n > 0 channels listed on the device at d_channels (uploaded on s; r.donors on the device too).  The caller marks
+// the list's readers: s, and *tail_reader (the tail stream when the chain has one of its own, else null).
+int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, hipStream_t* tail_reader, const Restart& r) {
     retune::DemodView dv;
     retune::BsyncView bv;
     TETRA_TRY(retune_impl::demod_view(h->dem, &dv));
@@ -148,14 +127,14 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     static_assert(sizeof(tetra_lmac_cell_state_t) % 4 == 0 && sizeof(tetra_rx_link_t) % 4 == 0, "reset in 32-bit words");
     // the chain's per-channel tables in 32-bit words per channel: no words where the handle has no such table, nor for miss counters
     // that the rule in force does not count
-    retune::CellView tv[kChanTablesAll];
+    retune::CellView tab[kChanTablesAll];
     for (int t = 0; t < kChanTablesAll; ++t) {
         void* at = nullptr;
         bool counting = true;
         TETRA_TRY(chan_tab::live(h, t, &at, &counting));
-        tv[t] = { static_cast<uint32_t*>(at), at && counting ? (int32_t)(chan_tab::elem_bytes(t) / 4) : 0 };
+        tab[t] = { static_cast<uint32_t*>(at), at && counting ? (int32_t)(chan_tab::elem_bytes(t) / 4) : 0 };
     }
-    const retune::CellView &cv = tv[TAB_CELL], &lv = tv[TAB_LINK], &mv = tv[TAB_SYNC_MISSES], &av = tv[TAB_HANDOVER];
+    const retune::TailView tv = { bv, tab[TAB_CELL], tab[TAB_LINK], tab[TAB_SYNC_MISSES], tab[TAB_HANDOVER] };
     if (!h->ev_reset) HIP_TRY(h, hipEventCreateWithFlags(h->ev_reset.put(), hipEventDisableTiming));
     const int last = (int)((h->calls - 1) & 1);
     hipStream_t st = h->one_stream ? s : static_cast<hipStream_t>(h->tail);
@@ -173,30 +152,9 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
         HIP_TRY(h, hipEventRecord(h->ev_reset, s));
         HIP_TRY(h, hipStreamWaitEvent(st, h->ev_reset, 0));
     }
-    if (elapsed) {      // the whole tail part in one launch: the channel's own state is read before it is cleared
-        hipLaunchKernelGGL(k_resume_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, mv, av, d_channels, h->C, *elapsed, p->window, p->max_slots);
-        HIP_TRY(h, hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(k_reset_tail, dim3((unsigned)n), dim3(kLanes), 0, st, bv, cv, lv, d_channels, h->C);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (!elapsed && mv.cell_words > 0) {
-        hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, mv, d_channels, h->C);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (!elapsed && av.cell_words > 0) {      // a handle that has handed over: the listed channels' hand-over fields, like the miss counters ...
-        hipLaunchKernelGGL(k_reset_miss, dim3((unsigned)n), dim3(kLanes), 0, st, av, d_channels, h->C);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (d_donors) {      // ... and behind all of it the planting
-        retune::BsyncView bsv;
-        TETRA_TRY(retune_impl::bsync_view(h->bs, &bsv));
-        const handover::View hv = { reinterpret_cast<bsync_core::State*>(bsv.state), reinterpret_cast<bsync_core::Assist*>(av.cell),
-                                          reinterpret_cast<tetra_lmac::TrackState*>(cv.cell) };
-        hipLaunchKernelGGL(k_handover_plant, dim3((unsigned)((n + kLanes - 1) / kLanes)), dim3(kLanes), 0, st, hv, d_channels, d_donors, n, h->C, p->window,
-                           p->max_slots);
-        HIP_TRY(h, hipGetLastError());
-    }
+    hipLaunchKernelGGL(k_restart_tail, dim3((unsigned)n), dim3(kLanes), 0, st, tv, d_channels, r.donors, r.kind == Restart::kOwnHeir ? 1 : 0, h->C, r.elapsed,
+                       r.p.window, r.p.max_slots);
+    HIP_TRY(h, hipGetLastError());
     if (h->one_stream) HIP_TRY(h, hipEventRecord(h->ev_reset, s));
     h->reset_pending = true;
     if (h->calls > 0) {      // who waits for the last call waits for the reset too
@@ -207,30 +165,53 @@ int reset_enqueue(tetra_rx* h, const int32_t* d_channels, int n, hipStream_t s, 
     return TETRA_OK;
 }
 
-// tetra_rx_reset_channels_device, and with donors [n] and checked parameters tetra_rx_handover_channels_device: the list travels as
-// [n channels] or [n channels | n donors].  elapsed != null (and no donors): tetra_rx_resume_channels_device.
-int reset_channels(tetra_rx* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p, void* hip_stream,
-                   const uint32_t* elapsed = nullptr) {
+// The three tetra_rx_*_channels_device entries behind their argument checks: the list travels as [n channels], with donors as
+// [n channels | n donors].
+int reset_channels(tetra_rx* h, const int32_t* channels, int n, const Restart& r, void* hip_stream) {
     if (n == 0) return TETRA_OK;
     DeviceGuard g(h->device);
     if (!g.ok) return TETRA_ERR_NO_DEVICE;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    std::vector<int32_t> both;
-    void* fields = nullptr;      // the handle's first hand-over allocates them; from here on its tails run the ASSIST-capable kernels
-    if (donors || elapsed) TETRA_TRY(retune_impl::bsync_assist(h->bs, &fields));
-    if (donors) {
-        both.assign(channels, channels + n);
-        both.insert(both.end(), donors, donors + n);
-    }
+    std::vector<int32_t> list(channels, channels + n);
+    void* fields = nullptr;      // the handle's first hand-over or gap allocates them; from here on its tails run the ASSIST-capable kernels
+    if (r.plants()) TETRA_TRY(retune_impl::bsync_assist(h->bs, &fields));
+    if (r.donors) list.insert(list.end(), r.donors, r.donors + n);
     int32_t* d_list = nullptr;
     hipError_t e = hipSuccess;
-    const int k = donors ? h->to_device.push(both.data(), 2 * n, 2 * h->C, s, &d_list, &e) : h->to_device.push(channels, n, h->C, s, &d_list, &e);
+    const int k = h->to_device.push(list.data(), (int)list.size(), (r.donors ? 2 : 1) * h->C, s, &d_list, &e);
     if (k < 0) HIP_TRY(h, e);
+    Restart on_device = r;
+    if (r.donors) on_device.donors = d_list + n;
     hipStream_t tail = nullptr;
-    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail, donors ? d_list + n : nullptr, p, elapsed));
+    TETRA_TRY(reset_enqueue(h, d_list, n, s, &tail, on_device));
     HIP_TRY(h, h->to_device.done(k, 0, s));
     if (tail) HIP_TRY(h, h->to_device.done(k, 1, tail));
     return TETRA_OK;
+}
+
+// What the three tetra_rx_*_channels_device entries check alike, in their order; lists_given: every list the entry takes is non-null
+int channel_list_status(const tetra_rx* h, const int32_t* channels, int n, bool lists_given) {
+    if (no_device()) return TETRA_ERR_NO_DEVICE;
+    if (!h || n < 0 || n > h->C || (!lists_given && n > 0)) return TETRA_ERR_ARG;
+    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune, _retune_from and _gap restart its slots
+    return distinct_in_range(channels, n, h->C) ? TETRA_OK : TETRA_ERR_ARG;
+}
+
+// The end that tetra_wbrx_retune and tetra_wbrx_gap share, behind the point from which the host state is committed: the chain's
+// restart of the n slots listed at d_list (unless rc or late says that the front end's part has failed already), the readers of block k
+// of the upload ring marked, ev_done recorded behind it all, and a late HIP error folded into the return code.
+int wbrx_commit(tetra_wbrx* h, int k, const int32_t* d_list, int n, hipStream_t s, const Restart& r, int rc, hipError_t late) {
+    hipStream_t tail = nullptr;
+    if (rc == TETRA_OK && late == hipSuccess) rc = reset_enqueue(h->rx, d_list, n, s, &tail, r);
+    if (late == hipSuccess) late = h->to_device.done(k, 0, s);
+    if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
+    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
+    if (late == hipSuccess) h->done_recorded = true;
+    else if (rc == TETRA_OK) {
+        h->last_hip = (int)late;
+        rc = TETRA_ERR_HIP;
+    }
+    return rc;
 }
 
 // The wideband receiver's retune: bins [S], and -- donors != null -- per slot a donor or -1, with checked parameters
@@ -280,17 +261,7 @@ int wbrx_retune(tetra_wbrx* h, const int32_t* bins, const int32_t* donors, const
     for (int i = 0; i < n; i++) h->bins[(size_t)list[(size_t)i]] = list[(size_t)(n + i)];
     h->retunes++;
     h->slots_changed += n;
-    hipStream_t tail = nullptr;
-    int rc = reset_enqueue(rx, d_list, n, s, &tail, donors ? d_list + 2 * n : nullptr, p);
-    hipError_t late = h->to_device.done(k, 0, s);
-    if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
-    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
-    if (late == hipSuccess) h->done_recorded = true;
-    else if (rc == TETRA_OK) {
-        h->last_hip = (int)late;
-        rc = TETRA_ERR_HIP;
-    }
-    return rc;
+    return wbrx_commit(h, k, d_list, n, s, donors ? Restart::from_donors(d_list + 2 * n, *p) : Restart::plain(), TETRA_OK, hipSuccess);
 }
 
 // A stream gap of a wideband handle (include/ext/tetra_gap.h), all on the caller's stream behind the last call: the front end as
@@ -321,16 +292,7 @@ int wbrx_gap(tetra_wbrx* h, int64_t n_lost, const tetra_handover_params_t* p, in
     rs->n_total = 0;
     rs->m_next = 0;
     if (late == hipSuccess) late = hipMemsetAsync(h->ring.get(), 0, h->ring.bytes(), s);
-    hipStream_t tail = nullptr;
-    if (rc == TETRA_OK && late == hipSuccess) rc = reset_enqueue(rx, d_list, S, s, &tail, nullptr, p, &elapsed);
-    if (late == hipSuccess) late = h->to_device.done(k, 0, s);
-    if (late == hipSuccess && tail) late = h->to_device.done(k, 1, tail);
-    if (late == hipSuccess) late = hipEventRecord(h->ev_done, s);
-    if (late == hipSuccess) h->done_recorded = true;
-    else if (rc == TETRA_OK) {
-        h->last_hip = (int)late;
-        rc = TETRA_ERR_HIP;
-    }
+    rc = wbrx_commit(h, k, d_list, S, s, Restart::own_heir(*p, elapsed), rc, late);
     if (rc == TETRA_OK && elapsed_bits_out) *elapsed_bits_out = (int64_t)elapsed;
     return rc;
 }
@@ -340,36 +302,30 @@ int wbrx_gap(tetra_wbrx* h, int64_t n_lost, const tetra_handover_params_t* p, in
 extern "C" {
 
 int tetra_rx_reset_channels_device(tetra_rx_t* h, const int32_t* channels, int n, void* hip_stream) {
-    if (no_device()) return TETRA_ERR_NO_DEVICE;
-    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
-    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune restarts its slots
-    if (!distinct_in_range(channels, n, h->C)) return TETRA_ERR_ARG;
-    return reset_channels(h, channels, nullptr, n, nullptr, hip_stream);
+    const int rc = channel_list_status(h, channels, n, channels != nullptr);
+    return rc != TETRA_OK ? rc : reset_channels(h, channels, n, Restart::plain(), hip_stream);
 }
 
 int tetra_rx_handover_channels_device(tetra_rx_t* h, const int32_t* channels, const int32_t* donors, int n, const tetra_handover_params_t* p,
                                       void* hip_stream) {
-    if (no_device()) return TETRA_ERR_NO_DEVICE;
-    if (!h || n < 0 || n > h->C || ((!channels || !donors) && n > 0)) return TETRA_ERR_ARG;
-    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_retune_from hands its slots over
+    const int rc = channel_list_status(h, channels, n, channels && donors);
+    if (rc != TETRA_OK) return rc;
     tetra_handover_params_t prm;
-    if (!distinct_in_range(channels, n, h->C) || !handover_params(p, &prm)) return TETRA_ERR_ARG;
+    if (!handover_params(p, &prm)) return TETRA_ERR_ARG;
     std::vector<char> heir((size_t)h->C, 0);
     for (int i = 0; i < n; i++) heir[(size_t)channels[i]] = 1;
-    for (int i = 0; i < n; i++)
+    for (int i = 0; i < n; i++)      // a donor is never an heir: k_restart_tail relies on it
         if (donors[i] < -1 || donors[i] >= h->C || (donors[i] >= 0 && heir[(size_t)donors[i]])) return TETRA_ERR_ARG;
-    return reset_channels(h, channels, donors, n, &prm, hip_stream);
+    return reset_channels(h, channels, n, Restart::from_donors(donors, prm), hip_stream);
 }
 
 int tetra_rx_resume_channels_device(tetra_rx_t* h, const int32_t* channels, int n, int64_t elapsed_bits, const tetra_handover_params_t* p,
                                     void* hip_stream) {
-    if (no_device()) return TETRA_ERR_NO_DEVICE;
-    if (!h || n < 0 || n > h->C || (!channels && n > 0)) return TETRA_ERR_ARG;
-    if (h->owned) return TETRA_ERR_UNSUPPORTED;          // a wideband handle's chain: tetra_wbrx_gap resumes its slots
+    const int rc = channel_list_status(h, channels, n, channels != nullptr);
+    if (rc != TETRA_OK) return rc;
     tetra_handover_params_t prm;
-    if (!distinct_in_range(channels, n, h->C) || !gap_params(p, &prm) || elapsed_bits < 0 || elapsed_bits > TETRA_GAP_MAX_ELAPSED_BITS) return TETRA_ERR_ARG;
-    const uint32_t elapsed = (uint32_t)elapsed_bits;
-    return reset_channels(h, channels, nullptr, n, &prm, hip_stream, &elapsed);
+    if (!gap_params(p, &prm) || elapsed_bits < 0 || elapsed_bits > TETRA_GAP_MAX_ELAPSED_BITS) return TETRA_ERR_ARG;
+    return reset_channels(h, channels, n, Restart::own_heir(prm, (uint32_t)elapsed_bits), hip_stream);
 }
 
 int tetra_wbrx_gap(tetra_wbrx_t* h, int64_t n_lost, const tetra_handover_params_t* p, int64_t* elapsed_bits_out, void* hip_stream) {

@@ -378,21 +378,8 @@ public:
     // enqueued on any shard.  streams[s]: a HIP stream of shard s's device (streams = null: the null streams).
     int handOver(const std::vector<int32_t>& channels, const std::vector<int32_t>& donors, const tetra_handover_params_t* p = nullptr,
                  void* const* streams = nullptr) {
-        if (channels.size() != donors.size()) return TETRA_ERR_ARG;
-        if (p && (p->window < 0 || p->window > 127 || p->max_slots < 1 || p->max_slots > 255)) return TETRA_ERR_ARG;
-        // everything a shard would refuse is refused here, before the first shard is told anything
-        std::vector<char> heir((size_t)channels_, 0);
-        for (int32_t c : channels) {
-            if (c < 0 || c >= channels_ || heir[(size_t)c]) return TETRA_ERR_ARG;
-            heir[(size_t)c] = 1;
-        }
-        std::vector<std::vector<int32_t>> ch(shards_.size()), dn(shards_.size());
-        for (size_t i = 0; i < channels.size(); i++) {
-            const int s = shardOf(channels[i]);
-            if (donors[i] != -1 && (shardOf(donors[i]) != s || heir[(size_t)donors[i]])) return TETRA_ERR_ARG;
-            ch[(size_t)s].push_back(channels[i] - shards_[(size_t)s]->first);
-            dn[(size_t)s].push_back(donors[i] == -1 ? -1 : donors[i] - shards_[(size_t)s]->first);
-        }
+        PerShard ch, dn;
+        if (channels.size() != donors.size() || !split(channels, &donors, p, ch, dn)) return TETRA_ERR_ARG;
         for (size_t s = 0; s < shards_.size(); s++) {
             const int rc = shards_[s]->bank.handOver(ch[s], dn[s], p, streams ? streams[s] : nullptr);
             if (rc != TETRA_OK) return rc;
@@ -402,16 +389,8 @@ public:
     // A stream gap (ext/tetra_gap.h), in the bank's channel numbers: every shard is told its own entries.  Everything a shard would refuse
     // is refused here (TETRA_ERR_ARG), before the first shard is told anything.  streams as for handOver.
     int resume(const std::vector<int32_t>& channels, int64_t elapsedBits, const tetra_handover_params_t* p = nullptr, void* const* streams = nullptr) {
-        if (elapsedBits < 0 || elapsedBits > TETRA_GAP_MAX_ELAPSED_BITS) return TETRA_ERR_ARG;
-        if (p && (p->window < 0 || p->window > 127 || p->max_slots < 1 || p->max_slots > 255)) return TETRA_ERR_ARG;
-        std::vector<char> seen((size_t)channels_, 0);
-        std::vector<std::vector<int32_t>> ch(shards_.size());
-        for (int32_t c : channels) {
-            if (c < 0 || c >= channels_ || seen[(size_t)c]) return TETRA_ERR_ARG;
-            seen[(size_t)c] = 1;
-            const int s = shardOf(c);
-            ch[(size_t)s].push_back(c - shards_[(size_t)s]->first);
-        }
+        PerShard ch, dn;
+        if (elapsedBits < 0 || elapsedBits > TETRA_GAP_MAX_ELAPSED_BITS || !split(channels, nullptr, p, ch, dn)) return TETRA_ERR_ARG;
         for (size_t s = 0; s < shards_.size(); s++) {
             const int rc = shards_[s]->bank.resume(ch[s], elapsedBits, p, streams ? streams[s] : nullptr);
             if (rc != TETRA_OK) return rc;
@@ -434,6 +413,31 @@ private:
         for (size_t s = 0; s < shards_.size(); s++)
             if (c >= shards_[s]->first && c < shards_[s]->first + shards_[s]->count) return (int)s;
         return -1;
+    }
+    // the bounds of tetra_handover_params_t, which the public headers state in words only (csrc/bsync_core.hpp: kWindowMax, kAssistSlotsMax)
+    enum { kWindowMax = 127, kMaxSlotsMax = 255 };
+    typedef std::vector<std::vector<int32_t>> PerShard;
+    // A restart's list in the bank's channel numbers, checked and split: ch[s] = shard s's entries in its own numbering, and with donors
+    // (-1: none) dn[s] beside it.  false: something a shard would refuse -- a channel outside the bank or listed twice, a donor outside
+    // its heir's shard or itself an heir, parameters out of range -- so that it is refused before any shard is told anything.
+    bool split(const std::vector<int32_t>& channels, const std::vector<int32_t>* donors, const tetra_handover_params_t* p, PerShard& ch, PerShard& dn) const {
+        if (p && (p->window < 0 || p->window > kWindowMax || p->max_slots < 1 || p->max_slots > kMaxSlotsMax)) return false;
+        std::vector<char> listed((size_t)channels_, 0);
+        for (int32_t c : channels) {
+            if (c < 0 || c >= channels_ || listed[(size_t)c]) return false;
+            listed[(size_t)c] = 1;
+        }
+        ch.assign(shards_.size(), {});
+        dn.assign(shards_.size(), {});
+        for (size_t i = 0; i < channels.size(); i++) {
+            const int s = shardOf(channels[i]), first = shards_[(size_t)s]->first;
+            ch[(size_t)s].push_back(channels[i] - first);
+            if (!donors) continue;
+            const int32_t d = (*donors)[i];
+            if (d != -1 && (shardOf(d) != s || listed[(size_t)d])) return false;
+            dn[(size_t)s].push_back(d == -1 ? -1 : d - first);
+        }
+        return true;
     }
     // tell every shard in turn: the first failure ends the round and is the result
     template <class Tell> int each(Tell tell) {

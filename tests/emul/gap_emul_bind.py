@@ -1,6 +1,6 @@
-"""Builds and binds tests/emul/gap_emul.cpp: the host build of the stream gap's lane code (csrc/handover_core.hpp's anchor, planting
-arithmetic and resume around csrc/retune_core.hpp's reset; include/ext/tetra_gap.h).  The ASSIST state a resumed channel runs in is
-handover_emul_bind's: Bank here is that module's with resume() beside plant().  TEST TOOL."""
+"""Builds and binds tests/emul/gap_emul.cpp: the host build of the stream gap's arithmetic (csrc/handover_core.hpp's anchor and planting
+rule; include/ext/tetra_gap.h).  The restart and the ASSIST state a resumed channel runs in are handover_emul_bind's: Bank here is that
+module's with anchor() beside resume().  TEST TOOL."""
 import ctypes as C
 import os
 
@@ -9,7 +9,7 @@ import numpy as np
 from oracle import hostlib
 from tests.emul import handover_emul_bind as H
 from tests.emul.handover_emul_bind import (ASSIST_FIELDS, CELL_FIELDS, EXPIRED, LOCKED, NONE, PENDING, REFUSED, ST_ASSIST, ST_KNOW_FSTART,  # noqa: F401
-                                           ST_LOCKED, ST_UNLOCKED, tdma_steps)
+                                           ST_LOCKED, ST_UNLOCKED, own_donor_vs_resume, tdma_steps)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -34,7 +34,6 @@ def lib():
             "gap_emul_tdma_period": (i32, []),
             "gap_emul_expect": (i32, [C.c_int32, C.c_uint32, i32, vp]),
             "gap_emul_anchor": (i32, [vp, vp, vp, i32, vp, vp]),
-            "gap_emul_resume": (None, [vp, vp, vp, vp, vp, i32, C.c_uint32, i32, i32]),
         })
     return _lib
 
@@ -55,13 +54,10 @@ def expect(d, elapsed, window):
 
 
 class Bank(H.Bank):
-    """handover_emul_bind.Bank with the gap: resume() is what tetra_retune.hip's k_resume_tail does to one channel."""
+    """handover_emul_bind.Bank with the anchor a resume() plants from."""
 
     def anchor(self, c):
         """-> (ok, d, (tn, fn, mn))"""
         d, q = np.zeros(1, np.int32), np.zeros(3, np.uint32)
         ok = lib().gap_emul_anchor(_p(self.st), _p(self.assist), _p(self.cell), int(c), _p(d), _p(q))
         return int(ok), int(d[0]), tuple(int(x) for x in q)
-
-    def resume(self, c, elapsed, window, max_slots):
-        lib().gap_emul_resume(_p(self.st), _p(self.assist), _p(self.cell), _p(self.carry), _p(self.miss), int(c), int(elapsed), int(window), int(max_slots))

@@ -1,12 +1,14 @@
 // Host build of the hand-over's lane code (include/ext/tetra_handover.h): the ASSIST state of the burst synchroniser's walk under both
 // lock rules (sdrpp-tetra-demodulator_amd/csrc/bsync_core.hpp: AssistLock around RefLock / TolLock), and the planting and apply steps
-// (csrc/handover_core.hpp), with the kernels' parallel phases done sequentially as in bsync_emul.cpp / bsync_tol_emul.cpp.  TEST TOOL.
+// (csrc/handover_core.hpp) around the restart of a channel (restart_lanes.hpp), with the kernels' parallel phases done sequentially as in
+// bsync_emul.cpp / bsync_tol_emul.cpp.  TEST TOOL.
 #define TETRA_HOST_EMUL 1
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
-#include "../../sdrpp-tetra-demodulator_amd/csrc/handover_core.hpp"
 #include "bsync_lane_io.hpp"
+#include "restart_lanes.hpp"
 
 using namespace bsync_core;
 
@@ -79,7 +81,7 @@ int handover_emul_process(State* st, Assist* as, int32_t* misses, uint8_t* carry
 }
 
 // expect and m of the planting for a donor with bits_in_buf buffered bits
-int handover_emul_expect(uint32_t bits_in_buf, int window, int32_t* m) { return handover::plant_expect(bits_in_buf, window, *m); }
+int handover_emul_expect(uint32_t bits_in_buf, int window, int32_t* m) { return handover::expect((int32_t)bits_in_buf, 0u, window, *m); }
 
 // k tetra_tdma_time_add_tn steps on t = {tn, fn, mn}, in place
 void handover_emul_tdma_steps(uint32_t* t, int k) {
@@ -87,9 +89,42 @@ void handover_emul_tdma_steps(uint32_t* t, int k) {
     t[0] = r.tn; t[1] = r.fn; t[2] = r.mn;
 }
 
-// states [C][4 words], assist [C][8], cell [C][10]: heir c planted from `donor` (behind its plain reset, which the caller has done)
-void handover_emul_plant(State* states, Assist* assist, tetra_lmac::TrackState* cell, int c, int donor, int window, int max_slots) {
-    handover::plant_channel(handover::View{ states, assist, cell }, c, donor, window, max_slots);
+// The tail part of channel c's restart over the tables of restart_lanes.hpp's tail_view.  src < 0: a plain reset; else c is planted from
+// src's anchor -- a donor (accept_pending = 0, elapsed = 0), or c itself after a gap of `elapsed` bits (accept_pending = 1).
+void handover_emul_restart(State* states, uint8_t* carry, tetra_lmac::TrackState* cell, uint32_t* link, int link_words, int32_t* miss, Assist* assist, int c,
+                           int src, int accept_pending, uint32_t elapsed, int window, int max_slots) {
+    restart_emul::restart_channel(restart_emul::tail_view(states, carry, cell, link, link_words, miss, assist), c, src, accept_pending, elapsed, window, max_slots);
+}
+
+// The identity the single restart rests on, over every bits_in_buf 0 .. max_bits x window 0 .. max_window x the listed max_slots: a LOCKED
+// channel with the cell cell10 (its bit buffer left out: nothing here reads it) restarted by two routes, as an heir of itself taken as a
+// donor, and as its own heir after a gap of 0 bits.  Returns the number of cases in which State, Assist or cell differ between the two
+// (first3: the first such case); *planted counts the cases in which both read ASSIST with the status PENDING.
+long long handover_emul_own_donor_vs_resume(const uint32_t* cell10, int max_bits, int max_window, const int32_t* max_slots, int n_max_slots,
+                                            long long* planted, int32_t* first3) {
+    long long differing = 0;
+    *planted = 0;
+    for (int b = 0; b <= max_bits; ++b)
+        for (int w = 0; w <= max_window; ++w)
+            for (int k = 0; k < n_max_slots; ++k) {
+                State st[2];
+                Assist as[2];
+                tetra_lmac::TrackState cell[2];
+                int32_t miss[2] = { 3, 3 };
+                for (int r = 0; r < 2; ++r) {
+                    const uint32_t words[4] = { (uint32_t)kLocked, (uint32_t)b, 51000u, 51000u + (uint32_t)kTs };
+                    std::memcpy(&st[r], words, sizeof words);
+                    std::memset(&as[r], 0, sizeof as[r]);
+                    std::memcpy(&cell[r], cell10, sizeof cell[r]);
+                    restart_emul::restart_channel(restart_emul::tail_view(&st[r], nullptr, &cell[r], nullptr, 0, &miss[r], &as[r]), 0, 0, r, 0u, w, max_slots[k]);
+                }
+                if (st[0].state == (uint32_t)kAssist && as[0].status == kHoPending && st[1].state == (uint32_t)kAssist && as[1].status == kHoPending) ++*planted;
+                if (std::memcmp(&st[0], &st[1], sizeof st[0]) || std::memcmp(&as[0], &as[1], sizeof as[0]) || std::memcmp(&cell[0], &cell[1], sizeof cell[0])) {
+                    if (!differing) { first3[0] = b; first3[1] = w; first3[2] = max_slots[k]; }
+                    ++differing;
+                }
+            }
+    return differing;
 }
 
 void handover_emul_apply(Assist* assist, tetra_lmac::TrackState* cell, int n_channels) {

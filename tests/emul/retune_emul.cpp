@@ -15,13 +15,10 @@ void retune_emul_reset_demod(const retune::DemodView* v, const int32_t* channels
 
 void retune_emul_reset_tail(uint32_t* state, int state_words, uint32_t* carry, int carry_words, uint32_t* cell, int cell_words,
                             const int32_t* channels, int n, int lanes) {
-    const retune::BsyncView bv = { state, carry, state_words, carry_words };
-    const retune::CellView cv = { cell, cell_words };
+    const retune::CellView none = { nullptr, 0 };          // a chain without link figures, miss counters and hand-over fields
+    const retune::TailView tv = { { state, carry, state_words, carry_words }, { cell, cell_words }, none, none, none };
     for (int b = 0; b < n; b++)
-        for (int lane = lanes - 1; lane >= 0; lane--) {
-            retune::reset_bsync_channel(bv, channels[b], lane, lanes);
-            retune::reset_cell_channel(cv, channels[b], lane, lanes);
-        }
+        for (int lane = lanes - 1; lane >= 0; lane--) retune::reset_tail_channel(tv, channels[b], lane, lanes);
 }
 
 // one call's share of the ring: x [n_in][M] complex64 after n0 earlier frames

@@ -1,20 +1,22 @@
 """Stream gaps (include/ext/tetra_gap.h): channels restarted after missing samples keep frame timing, cell and TDMA clock.
 
-CPU: the lane code on the host (tests/emul/gap_emul.cpp: handover_core.hpp's anchor, planting arithmetic and resume around retune_core.hpp's
-reset; the ASSIST state through tests/emul/handover_emul.cpp) against the rule written out, the reference's own tetra_tdma_time_add_tn and
+CPU: the lane code on the host (tests/emul/gap_emul.cpp: handover_core.hpp's anchor and planting arithmetic; the restart in the kernel's
+order and the ASSIST state through tests/emul/handover_emul.cpp) against the rule written out, the reference's own tetra_tdma_time_add_tn and
 the hand-over's planting.  GPU: the chain against that emulation fed the chain's own demodulated bits, against a handle that saw the
-uninterrupted IQ and against one that was fed the cut stream without being told; the wideband handle on tests/test_handover.py's band
+uninterrupted IQ and against one that was fed the cut stream without being told; the wideband handle on tests/restart_gpu.py's band
 against a fresh handle, the uninterrupted run and the run that was not told."""
 import ctypes as C
-import json
 import os
 import re
 
 import numpy as np
 import pytest
 
-from tests.test_handover import (B_SYNC_SLOTS, BIN_A, BIN_B, BIN_C, BIN_EMPTY, CALL, CUTS, D_BAND, DONOR_CELL, M_BAND, NORM_1, NORM_2, SYNC, TS,
-                                 _band_capture, _blocks_by_time, _burst, _count_seqs, _downlink_bits, _filler, _slot_index, _traffic_downlink)
+from tests.restart_gpu import (BIN_A, BIN_B, BIN_C, BIN_EMPTY, B_SYNC_SLOTS, CALL, CUTS, DONOR_CELL, D_BAND, M_BAND, NORM_1, NORM_2, SYNC, TS,
+                               assert_exported_and_bound, band_calls, band_capture, blocks_by_time as _blocks_by_time, build_and_run_bank_driver,
+                               chain_snap as _chain_snap, count_seqs as _count_seqs, downlink_bits as _downlink_bits, drive, filler as _filler,
+                               has_gpu as _has_gpu, in_flight_and_waited, reference_clock, rows_by_time, slot_index as _slot_index, snap as _snap,
+                               traffic_downlink as _traffic_downlink)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "gap_tdma.json")
@@ -28,11 +30,6 @@ def _header_int(name):
 
 
 GAP_WINDOW, GAP_MAX_SLOTS = _header_int("TETRA_GAP_DEFAULT_WINDOW"), _header_int("TETRA_GAP_DEFAULT_MAX_SLOTS")
-
-
-def _has_gpu():
-    import torch
-    return torch.cuda.is_available()
 
 
 @pytest.fixture(scope="module")
@@ -57,24 +54,6 @@ def _rule(d, G, W):
     return TS * m - (d + G), m
 
 
-def _reference_steps(cases):
-    """{(tn, fn, mn, k): the time after k tetra_tdma_time_add_tn(t, 1)} for the (start, k) in `cases`, from the reference's own function
-    (oracle/_ref) where it is built, else from the recording of exactly that (tests/golden/gap_tdma.json)."""
-    from oracle import ref_binding
-    if ref_binding.available():
-        from tests.chain_host import TdmaTime, ref_add_tn
-        add_tn = ref_add_tn(ref_binding)
-        out = {}
-        for (tn, fn, mn), k in cases:
-            t = TdmaTime(tn=tn, fn=fn, mn=mn)
-            for _ in range(k):
-                add_tn(C.byref(t), 1)
-            out[(tn, fn, mn, k)] = (int(t.tn), int(t.fn), int(t.mn))
-        return out
-    rec = json.load(open(GOLDEN))
-    return {tuple(r[:4]): tuple(r[4:]) for r in rec["rows"]}
-
-
 def _locked_bank(em, bits_in_buf, phy, n=1, F=51000, tol=None, use_batch=True):
     """Channel 0 LOCKED with bits_in_buf buffered bits, DONOR_CELL's code and the PHY time phy, as a tail would have left it; its bit
     buffer and miss counter hold what a running channel's hold (anything)."""
@@ -96,7 +75,7 @@ def test_planting_arithmetic_equals_the_rule_and_the_reference_clock(em):
     times, which the lane code's own clock taken m times agrees with, the reference's clock having the period 4320 --, and G = 0 equals the
     hand-over's planting from a donor with the same state."""
     assert em.tdma_period() == PERIOD
-    ref_clock = _reference_steps(_planting_cases())
+    ref_clock = reference_clock(_planting_cases(), GOLDEN)
     for phy in PHYS:
         assert ref_clock[phy + (PERIOD,)] == phy and em.tdma_steps(phy, PERIOD) == phy
     for b in BITS_IN_BUF:
@@ -121,6 +100,24 @@ def test_planting_arithmetic_equals_the_rule_and_the_reference_clock(em):
                 own.resume(0, 0, W, 72)
                 other.plant(1, 0, W, 72)
                 assert own.state(0) == other.state(1) and tuple(own.assist[0]) == tuple(other.assist[1]) and tuple(own.cell[0]) == tuple(other.cell[1])
+
+
+def test_a_locked_channel_as_its_own_donor_equals_its_resume_after_no_gap(em):
+    """Exhaustively, for bits_in_buf 0 .. 4096 x window 0 .. 127 x max_slots in {1, 72, 255}: a LOCKED channel restarted as the heir of
+    itself taken as a donor (the hand-over's route: a source that must be LOCKED, no elapsed bits) and as its own heir after a gap of 0
+    bits (the gap's route) ends with identical State, hand-over fields and cell, planted in every case.  The one restart of
+    tetra_retune.hip rests on this identity; the loop runs in the emulation (tests/emul/handover_emul.cpp)."""
+    for phy in PHYS:
+        differing, planted, first = em.own_donor_vs_resume(DONOR_CELL[:7] + phy, 4096, 127, (1, 72, 255))
+        assert (differing, planted) == (0, 4097 * 128 * 3), (phy, differing, planted, first)
+    # (the comparison sees a difference where there is one: PENDING is accepted on one route only, a refused source leaves no planting)
+    bank = em.Bank(1)
+    bank.st[0], bank.cell[0], bank.assist[0] = (em.ST_ASSIST, 100, 0, 0), DONOR_CELL, (em.PENDING, 2, 0, 600, 8, 70, 0, 0)
+    as_donor, as_own = em.Bank(1), em.Bank(1)
+    for b, accept in ((as_donor, False), (as_own, True)):
+        b.st[:], b.cell[:], b.assist[:] = bank.st, bank.cell, bank.assist
+        b.restart(0, 0, accept, 0, 8, 72)
+    assert as_donor.status(0) == (em.REFUSED, 0, 0) and as_own.status(0) == (em.PENDING, 0, 0)
 
 
 @pytest.mark.parametrize("tol", [None, (3, 5, 16)])
@@ -200,7 +197,7 @@ def test_refused_channels_are_plainly_reset(em):
 @pytest.mark.parametrize("tol", [None, (3, 5, 16)])
 @pytest.mark.parametrize("case", ["lock_late", "expire", "lock_at_edge"])
 def test_cut_independence_after_a_resume(em, synth, case, tol):
-    """The stream behind a resume in tests/test_handover.py's cuts (1, 509, 510, 511, 1020 bits and ragged sizes), with and without the
+    """The stream behind a resume in tests/restart_gpu.py's cuts (1, 509, 510, 511, 1020 bits and ragged sizes), with and without the
     LOCKED batch, under both lock rules: frames, types, bit numbers, the result words in their order, the final State, hand-over fields,
     cell, bit buffer and miss counter are those of one single call."""
     rng = np.random.default_rng({"lock_late": 11, "expire": 12, "lock_at_edge": 13}[case])
@@ -218,20 +215,7 @@ def test_cut_independence_after_a_resume(em, synth, case, tol):
     def run(cut, use_batch):
         bank = _locked_bank(em, 137, (2, 9, 3), tol=tol, use_batch=use_batch)
         bank.resume(0, G, W, max_slots)
-        r = np.random.default_rng(99)
-        at, frames, types, nums, results = 0, [], [], [], []
-        while at < stream.size:
-            n = int(r.choice((1, 3, 200, 509, 511, 777, 2040))) if cut == "ragged" else cut
-            fr, ty, bn = bank.feed(0, stream[at:at + n])
-            at += n
-            frames += [f.tobytes() for f in fr]
-            types += list(ty)
-            nums += list(bn)
-            if bank.field(0, "result"):
-                results.append(bank.field(0, "result"))
-            bank.apply()
-        n_buf = bank.state(0)[1]
-        return frames, types, nums, results, bank.state(0), tuple(bank.assist[0]), tuple(bank.cell[0]), bank.carry[0][:n_buf].tobytes(), int(bank.miss[0])
+        return bank.feed_in_cuts(0, stream, cut)
 
     whole = run(stream.size, True)
     assert len(whole[1]) >= (5 if case == "expire" else 16)
@@ -242,26 +226,16 @@ def test_cut_independence_after_a_resume(em, synth, case, tol):
 
 
 def test_gap_header_symbols_all_exported_and_bound(pkg):
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(tetra_[a-z0-9_]+)\s*\(", src)))
     R, Wb = pkg.rx_binding, pkg.wbrx_binding
-    assert names == sorted(R.RX_GAP_EXPORTS + Wb.WBRX_GAP_EXPORTS) and len(names) == 3
-    L = pkg.load_library()
-    for n in names:
-        assert hasattr(L, n), n
-    R._lib(), Wb._lib()
-    for n in names:
-        assert getattr(L, n).argtypes is not None and getattr(L, n).restype is C.c_int, n
+    names = R.RX_GAP_EXPORTS + Wb.WBRX_GAP_EXPORTS
+    # (the pinned headers did not grow, and neither did RX_EXPORTS)
+    assert_exported_and_bound(pkg, os.path.join("ext", "tetra_gap.h"), names, (("tetra_wbrx.h", "tetra_wbrx_", 14), ("tetra_rx.h", "tetra_rx_", len(R.RX_EXPORTS)),
+                                                                              ("tetra_retune.h", "tetra_", 3), (os.path.join("ext", "tetra_handover.h"), "tetra_", 3)))
     assert callable(pkg.RxChain.resume) and callable(pkg.WidebandRx.gap) and callable(pkg.WidebandRx.process_device_at)
     assert (R.GAP_DEFAULT_WINDOW, R.GAP_DEFAULT_MAX_SLOTS, R.GAP_MAX_ELAPSED_BITS) == (GAP_WINDOW, GAP_MAX_SLOTS, _header_int("TETRA_GAP_MAX_ELAPSED_BITS"))
     assert R.GAP_MAX_ELAPSED_BITS == 2 ** 31 - 1 and GAP_WINDOW % 8 == 0 and GAP_WINDOW >= 8
     iq = open(os.path.join(ROOT, "include", "ext", "tetra_iqcond.h")).read()
     assert all(("#define TETRA_IQ_FMT_%s %d" % (n, v)) in iq for n, v in (("C64", Wb.IQ_FMT_C64), ("CS16", Wb.IQ_FMT_CS16), ("CS8", Wb.IQ_FMT_CS8)))
-    # the pinned headers did not grow, and neither did RX_EXPORTS
-    for hdr, prefix, count in (("tetra_wbrx.h", "tetra_wbrx_", 14), ("tetra_rx.h", "tetra_rx_", len(R.RX_EXPORTS)), ("tetra_retune.h", "tetra_", 3),
-                               (os.path.join("ext", "tetra_handover.h"), "tetra_", 3)):
-        s = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hdr)).read(), flags=re.S)
-        assert len(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, s))) == count, hdr
     assert len(R.RX_EXPORTS) == 16 and not set(names) & set(R.RX_EXPORTS + R.RX_HANDOVER_EXPORTS + Wb.WBRX_EXPORTS + Wb.WBRX_HANDOVER_EXPORTS)
 
 
@@ -315,11 +289,8 @@ def _three_channels(synth, removed, tolerant, seeds=(1, 3)):
 
 def _by_time(rows_by_kind):
     """{(channel, kind, tdma_time_rx): (crc_ok, tdma_time, type-1 bits)}; every key must be there once"""
-    out = {}
-    for k, rows in rows_by_kind.items():
-        for r in rows:
-            assert (r[0], k, r[3]) not in out
-            out[(r[0], k, r[3])] = (r[2], r[4], r[5])
+    out, order = rows_by_time([rows_by_kind])
+    assert len(out) == len(order)
     return out
 
 
@@ -426,12 +397,81 @@ def test_gpu_two_gaps_the_second_while_pending(pkg, synth):
 
 
 @pytest.mark.gpu
+def test_gpu_the_three_restarts_leave_what_the_host_emulation_leaves(pkg, synth, em):
+    """One plain chain of 4 channels at a sample per bit under TETRA_RX_FLAG_SYNC_TOLERANT | TETRA_RX_FLAG_BITERR, so that the tail keeps
+    all its tables: two carriers that fall silent for the last three of 16 slots (LOCKED, misses counted, link figures gathered) and two
+    noise channels.  Four handles see the same call; then one gets reset_channels([1, 3]), one handover_channels([2, 3], [0, -1]), one
+    resume(137, channels=[0, 2]), one nothing.  After each restart the listed channels' synchroniser state, cell, link figures, miss
+    counter and hand-over status equal the host emulation's (tests/emul/restart_lanes.hpp) started from the handle's own tables, and the
+    channels not listed equal the handle that was never restarted.  Last, the resumed handle hands channel 3 over from channel 0, which
+    is PENDING now: a donor must be LOCKED, so the heir reads REFUSED.  A table that the single kernel forgot, or a planting from the
+    wrong source, shows here."""
+    import copy
+    import torch
+    from tests.chain_gpu import bit_rows
+    R = pkg.rx_binding
+    n, quiet = SLOTS_1 * TS, 3 * TS
+    rng = np.random.default_rng(17)
+    noise = lambda k: (0.1 * (rng.standard_normal(k) + 1j * rng.standard_normal(k))).astype(np.complex64)
+    iq = np.concatenate([_three_channels(synth, 0, True)[:, :n], noise(n)[None, :]])
+    iq[0, n - quiet:], iq[1, n - quiet:] = noise(quiet), noise(quiet)
+    iq = np.ascontiguousarray(iq)
+    plain, heirs, own, never = (pkg.RxChain(4, 16000, flags=R.FLAG_SYNC_TOLERANT | R.FLAG_BITERR) for _ in range(4))
+    for h in (plain, heirs, own, never):
+        h.process(iq)
+
+    def link_words(h):
+        return np.array([(v["bits"], v["bit_errors"], v["blocks"], v["blocks_crc_bad"]) for v in h.links()], R.LINK_DTYPE).view(np.uint32).reshape(4, -1)
+
+    def tables(h):
+        """per channel (sync state, cell, link figures as words, miss counter, hand-over status)"""
+        cells, link, miss, status = h.cells(), link_words(h), h.sync_misses(), h.handover_status()
+        return [(sync, [getattr(cells[c], f) for f in em.CELL_FIELDS], [int(v) for v in link[c]], int(miss[c]), status[c]) for c, sync in enumerate(h.sync_states())]
+
+    def bank_tables(b):
+        return [(b.state(c), [int(v) for v in b.cell[c]], [int(v) for v in b.link[c]], int(b.miss[c]), b.status(c)) for c in range(4)]
+
+    bank = em.Bank(4, tol=(3, 5, 16))
+    for c, b in enumerate(bit_rows(torch, never, 4)):
+        bank.feed(c, np.frombuffer(b, np.uint8))
+    before = tables(never)
+    assert [t[0] for t in before] == [bank.state(c) for c in range(4)]
+    assert [t[0][0] == em.ST_LOCKED for t in before] == [True, True, False, False] and all(before[c][1][0] for c in (0, 1))
+    assert all(before[c][3] > 0 and before[c][2][4] > 0 for c in (0, 1)), before          # misses and coded blocks counted: their clearing shows
+    for c in range(4):          # the emulation goes on from the handle's own tables
+        bank.cell[c], bank.link[c], bank.miss[c] = before[c][1], before[c][2], before[c][3]
+    assert bank_tables(bank) == before and all(tables(h) == before for h in (plain, heirs, own))
+    W, K = R.HANDOVER_DEFAULT_WINDOW, R.HANDOVER_DEFAULT_MAX_SLOTS
+    cases = ((plain, [1, 3], lambda h: h.reset_channels([1, 3]), lambda b: (b.reset(1), b.reset(3)), {}),
+             (heirs, [2, 3], lambda h: h.handover_channels([2, 3], [0, -1]), lambda b: (b.plant(2, 0, W, K), b.reset(3)), {2: em.PENDING, 3: em.NONE}),
+             (own, [0, 2], lambda h: h.resume(137, channels=[0, 2]), lambda b: (b.resume(0, 137, GAP_WINDOW, GAP_MAX_SLOTS), b.resume(2, 137, GAP_WINDOW, GAP_MAX_SLOTS)),
+              {0: em.PENDING, 2: em.REFUSED}))
+    for h, listed, restart, emulate, status in cases:
+        b = copy.deepcopy(bank)
+        restart(h)
+        emulate(b)
+        got, want = tables(h), bank_tables(b)
+        for c in range(4):
+            assert got[c] == (want[c] if c in listed else before[c]), (listed, c, got[c], want[c], before[c])
+        for c in listed:
+            assert got[c][2] == [0] * 6 and got[c][3] == 0 and got[c][4][0] == status.get(c, em.NONE), (listed, c, got[c])
+    # a donor must be LOCKED: channel 0 of `own` is its own heir now, ASSIST with the status PENDING, and gives nothing
+    pending = tables(own)
+    own.handover_channels([3], [0])
+    b.plant(3, 0, W, K)
+    got, want = tables(own), bank_tables(b)
+    assert got[3] == want[3] and got[3][4] == (em.REFUSED, 0, 0) and got[3][0] == (em.ST_UNLOCKED, 0, 0, 0) and got[:3] == pending[:3], (got, want)
+    assert tables(never) == before
+    for h in (plain, heirs, own, never):
+        h.close()
+
+
+@pytest.mark.gpu
 def test_gpu_refused_arguments_change_nothing_and_a_handle_without_gaps_is_untouched(pkg, synth):
     """Every refusal of the three entry points: nothing is enqueued, the hand-over status reads NONE (the per-channel fields are not even
     allocated, so the handle still launches the kernels it always did), and every later snapshot -- rows, cell, sync and demodulator state
     -- equals that of a handle that never saw any of the calls.  A wideband handle's chain refuses the chain's entry point."""
     import torch
-    from tests.test_retune import _chain_snap, _snap
     R, Wb = pkg.rx_binding, pkg.wbrx_binding
     L = R._lib()
     iq = _three_channels(synth, 0, False)
@@ -490,7 +530,7 @@ INDEX_0 = 123456789012                             # a driver's sample index of 
 @pytest.fixture(scope="module")
 def band(pkg, synth):
     import torch
-    return _band_capture(torch, synth)
+    return band_capture(torch, synth)
 
 
 def _gap_run(pkg, torch, xs, mode, stream=None, wait=False, flags=0):
@@ -498,41 +538,26 @@ def _gap_run(pkg, torch, xs, mode, stream=None, wait=False, flags=0):
     same stream, nobody told; "at": the same through process_device_at with the driver's indices, and an overlapping call refused on
     the way; "fresh": the two calls behind the gap, on a new handle.
     -> (per call the per-slot snapshots with the call's demodulated bits, per call the hand-over status, the handle, gap()'s value)"""
-    from tests.chain_gpu import bit_rows
-    from tests.test_retune import _snap
     wb = pkg.WidebandRx(BINS, n_channels=M_BAND, decimation=D_BAND, max_in=CALL, flags=flags)
-    L = xs.shape[0]
     first = [] if mode == "fresh" else [(0, CALL)]
-    start = CALL if mode == "whole" else CALL + N_LOST
-    calls = first + [(a, min(a + CALL, L)) for a in range(start, L, CALL)][:2 if mode == "fresh" else None]
-    snaps, status, elapsed = [], [], None
-    for i, (a, b) in enumerate(calls):
-        if mode == "gap" and i == 1:
-            if wait:
-                wb.rx.wait()
-            elapsed = wb.gap(N_LOST, stream=stream)
-            if wait:
-                wb.rx.wait()
-        if mode == "at":
-            if i == 3:
-                with pytest.raises(pkg.binding.TetraDemodError) as err:
-                    wb.process_device_at(xs[a - 1:b - 1], INDEX_0 + a - 1, stream=stream)
-                assert err.value.status == ERR_ARG
-            wb.process_device_at(xs[a:b], INDEX_0 + a, stream=stream)
-        else:
-            wb.process_device(xs[a:b], b - a, stream)
-        if stream is None or wait:
-            s = _snap(pkg, torch, wb)
-            for c, bits in enumerate(bit_rows(torch, wb.rx, wb.n_bins)):
-                s[c]["bits"] = bits
-            snaps.append(s)
-            status.append(wb.handover_status())
-    return snaps, status, wb, elapsed
+    calls = first + band_calls(xs.shape[0], CALL if mode == "whole" else CALL + N_LOST)[:2 if mode == "fresh" else None]
+    elapsed = []
+    before = {1: lambda w: elapsed.append(w.gap(N_LOST, stream=stream))} if mode == "gap" else None
+
+    def at(w, i, a, b):
+        if i == 3:
+            with pytest.raises(pkg.binding.TetraDemodError) as err:
+                w.process_device_at(xs[a - 1:b - 1], INDEX_0 + a - 1, stream=stream)
+            assert err.value.status == ERR_ARG
+        w.process_device_at(xs[a:b], INDEX_0 + a, stream=stream)
+
+    snaps, status = drive(pkg, torch, wb, xs, calls, before, stream, wait, feed=at if mode == "at" else None, bits=True)
+    return snaps, status, wb, elapsed[0] if elapsed else None
 
 
 @pytest.mark.gpu
 def test_gpu_wideband_gap_keeps_code_and_clock(pkg, synth, band):
-    """tests/test_handover.py's band (A control, B traffic with SYNC bursts in slots 8, 16 and 88, C another cell, one empty bin), N_LOST
+    """tests/restart_gpu.py's band (A control, B traffic with SYNC bursts in slots 8, 16 and 88, C another cell, one empty bin), N_LOST
     samples dropped at the first call boundary, just behind B's SYNC burst.
       (a) the resampled IQ and the demodulated bits of every slot behind gap() equal a fresh handle's fed the capture behind the gap;
       (b) every row of A, B and C behind the gap equals the uninterrupted run's row of the same kind and TDMA time;
@@ -562,13 +587,13 @@ def test_gpu_wideband_gap_keeps_code_and_clock(pkg, synth, band):
     assert all(s[3] == (4, 0, 0) for s in status[1:])
     next_sync = B_SYNC_SLOTS[2]
     for slot in range(3):                                                                  # (b)
-        want, _ = _blocks_by_time(pkg, whole, slot)
-        got, order = _blocks_by_time(pkg, told, slot, first_call=1)
+        want, _ = _blocks_by_time(whole, slot)
+        got, order = _blocks_by_time(told, slot, first_call=1)
         assert len(got) == len(order) >= 150, (slot, len(got), len(order))
         for key, val in got.items():
             assert want.get(key) == val, (slot, key, val[:2], want.get(key, (None, None))[:2])
         assert told[-1][slot]["cell"] == whole[-1][slot]["cell"]
-    _, order_b = _blocks_by_time(pkg, told, 1, first_call=1)
+    _, order_b = _blocks_by_time(told, 1, first_call=1)
     first_good = min(_slot_index(t) for k, t, ok, ta, bits in order_b if k in TRAFFIC and ok)
     whole_b = {(k, r[5]): r[3] for s in whole for k in TRAFFIC for r in s[1]["rows"][k] if r[2]}
     stale = [(k, r[3], whole_b[(k, r[5])]) for s in untold[1:] for k in TRAFFIC for r in s[1]["rows"][k] if r[2] and (k, r[5]) in whole_b]
@@ -589,15 +614,8 @@ def test_gpu_gap_with_calls_in_flight(pkg, synth, band, one_stream):
     TETRA_RX_FLAG_ONE_STREAM) leaves the latest and the previous call's results, frames, all state and the hand-over status equal to the
     same sequence with tetra_rx_wait before and after the gap."""
     import torch
-    from tests.test_retune import _snap
     fl = pkg.rx_binding.FLAG_ONE_STREAM if one_stream else 0
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    _, _, fast, e1 = _gap_run(pkg, torch, band, "gap", stream=side, flags=fl)
-    _, slow_status, slow, e2 = _gap_run(pkg, torch, band, "gap", stream=side, flags=fl, wait=True)
-    with torch.cuda.stream(side):
-        for which in (0, 1):
-            assert _snap(pkg, torch, fast, which) == _snap(pkg, torch, slow, which), which
+    (_, _, fast, e1), (_, slow_status, slow, e2) = in_flight_and_waited(pkg, torch, lambda stream, wait: _gap_run(pkg, torch, band, "gap", stream=stream, wait=wait, flags=fl))
     assert e1 == e2 == 1734 and fast.handover_status() == slow.handover_status() == slow_status[-1] and [s[0] for s in slow_status[-1]] == [2, 2, 2, 4]
     fast.rx.wait()
     fast.close(), slow.close()
@@ -608,11 +626,5 @@ def test_gpu_host_banks_resume_per_shard(pkg):
     """TetraRxBank::resume and the TetraRxMultiBank forwarding (host/tetra_rx_bank.h), 2 shards on one GPU: entries go to the shard that
     holds them in its own numbering, what a shard would refuse is TETRA_ERR_ARG with nothing enqueued on any, the status comes back in the
     bank's channel order.  A plain C++ driver (tests/host/test_gap_bank.cpp)."""
-    import subprocess
-    pk = os.path.join(ROOT, "sdrpp-tetra-demodulator_amd")
-    pkg.build.build()
-    exe = os.path.join(ROOT, "tests", "host", "test_gap_bank")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(pk, "host"),
-                    os.path.join(ROOT, "tests", "host", "test_gap_bank.cpp"), "-L", pk, "-ltetra_demod_hip", "-Wl,-rpath," + pk, "-o", exe], check=True)
-    r = subprocess.run([exe, "7", "2"], capture_output=True, text=True, timeout=120)
+    r = build_and_run_bank_driver(pkg, "test_gap_bank", [7, 2])
     assert r.returncode == 0 and "test_gap_bank: ok" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])

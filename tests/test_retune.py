@@ -6,38 +6,23 @@ channeliser -> full resampler composition on all bins (a moved slot's IQ), a sep
 moved slot's blocks and state).  The per-channel resets and the history ring are also run on the host, lane by lane."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests.restart_gpu import assert_exported_and_bound, chain_snap as _chain_snap, drive, has_gpu as _has_gpu, frames_i32 as _frames_i32, snap as _snap
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE = -1, -2, -3
-
-
-def _has_gpu():
-    import torch
-    return torch.cuda.is_available()
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CPU
 
 
 def test_retune_header_symbols_all_exported_and_bound(pkg):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tetra_retune.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(tetra_[a-z0-9_]+)\s*\(", src)))
-    assert names == sorted(pkg.rx_binding.RX_RETUNE_EXPORTS + pkg.wbrx_binding.WBRX_RETUNE_EXPORTS) and len(names) == 3
-    L = pkg.load_library()
-    for n in names:
-        assert hasattr(L, n), n
-    pkg.rx_binding._lib(), pkg.wbrx_binding._lib()
-    for n in names:
-        assert getattr(L, n).argtypes is not None and getattr(L, n).restype is C.c_int, n
+    assert_exported_and_bound(pkg, "tetra_retune.h", pkg.rx_binding.RX_RETUNE_EXPORTS + pkg.wbrx_binding.WBRX_RETUNE_EXPORTS,
+                              (("tetra_wbrx.h", "tetra_wbrx_", 14), ("tetra_rx.h", "tetra_rx_", len(pkg.rx_binding.RX_EXPORTS))))          # the pinned headers did not grow
     assert callable(pkg.WidebandRx.retune) and callable(pkg.WidebandRx.retune_count) and callable(pkg.RxChain.reset_channels)
-    # the pinned headers did not grow
-    for hdr, prefix, count in (("tetra_wbrx.h", "tetra_wbrx_", 14), ("tetra_rx.h", "tetra_rx_", len(pkg.rx_binding.RX_EXPORTS))):
-        s = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hdr)).read(), flags=re.S)
-        assert len(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, s))) == count, hdr
 
 
 def test_retune_entry_points_without_a_gpu_return_no_device(pkg):
@@ -161,9 +146,9 @@ D = 400
 @pytest.fixture(scope="module")
 def band(pkg, synth):
     import torch
-    from tests.test_wbrx import _capture, _cs16
-    x, cells, tx = _capture(torch, synth, 800, CARRIERS16, NSLOTS)
-    xs = _cs16(torch, x)
+    from tests.wideband_gpu import capture, cs16
+    x, cells, tx = capture(torch, synth, 800, CARRIERS16, NSLOTS)
+    xs = cs16(torch, x)
     del x
     torch.cuda.empty_cache()
     return xs, cells
@@ -177,54 +162,9 @@ def _ragged(L, seed, sizes=(150, 399, 400, 401, 9000, 250000, 777777, 1500000)):
     return cuts
 
 
-def _demod_states(pkg, rx, n):
-    L = pkg.binding.load_library()
-    out = []
-    for c in range(n):
-        st = pkg.binding.ChannelState()
-        assert L.tetra_demod_get_state(C.c_void_p(rx.demod_handle()), c, C.byref(st)) == 0
-        out.append(bytes(st))
-    return out
-
-
-def _chain_snap(pkg, rx, n, which=0):
-    """What a call leaves in a chain, per channel: every kind's rows (labels + type-1 bits), cell, sync and demodulator state."""
-    from tests.test_wbrx import _rows
-    rows = _rows(rx, pkg.rx_binding, which)
-    cells, sync, dem = [bytes(c) for c in rx.cells()], rx.sync_states(), _demod_states(pkg, rx, n)
-    return [dict(rows={k: [r for r in v if r[0] == c] for k, v in rows.items()}, cell=cells[c], sync=sync[c], demod=dem[c]) for c in range(n)]
-
-
-def _frames_i32(torch, wb, which=0):
-    p, n = wb.frames_device(which, torch.cuda.current_stream())
-    if n == 0:
-        return np.zeros((0, wb.n_bins, 2), np.int32)
-    t = torch.as_tensor(wb_array(p, (n, wb.n_bins, 2)), device="cuda")
-    return t.cpu().numpy().copy()
-
-
-def wb_array(ptr, shape):
-    import tetra_amd
-    return tetra_amd.pkg.wbrx_binding._DeviceArray(ptr, shape, "<i4")
-
-
-def _snap(pkg, torch, wb, which=0):
-    s = _chain_snap(pkg, wb.rx, wb.n_bins, which)
-    fr = _frames_i32(torch, wb, which)
-    for c in range(wb.n_bins):
-        s[c]["frames"] = fr[:, c].tobytes()
-    return s
-
-
-def _run(pkg, torch, wb, xs, cuts, retunes, stream=None):
+def _run(pkg, torch, wb, xs, cuts, retunes):
     """Feed the cuts, retune before call i where retunes has i; -> per call the per-slot snapshots."""
-    out = []
-    for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
-        if i in retunes:
-            wb.retune(retunes[i], stream)
-        wb.process_device(xs[a:b], b - a, stream)
-        out.append(_snap(pkg, torch, wb))
-    return out
+    return drive(pkg, torch, wb, xs, list(zip(cuts, cuts[1:])), {i: (lambda w, bins=bins: w.retune(bins)) for i, bins in retunes.items()})[0]
 
 
 def _good_sb1(snap_slot, pkg):

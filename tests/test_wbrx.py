@@ -4,7 +4,6 @@ It is the composition of pinned stages -- channeliser (tetra_chan.h), resampler 
 one new kernel, the resampler over picked columns.  The tests hold the handle bit for bit against the hand-wired composition of the
 existing handles, and the picking thread code against the full resampler's on the host."""
 import ctypes as C
-import math
 import os
 import re
 import subprocess
@@ -13,7 +12,8 @@ import tempfile
 import numpy as np
 import pytest
 
-from tests.chain_gpu import bit_rows as _bit_rows
+from tests.chain_gpu import bit_rows as _bit_rows, collect
+from tests.wideband_gpu import capture as _capture, cs16 as _cs16  # noqa: F401  (other test modules take them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_NO_DEVICE, ERR_SIZE, ERR_ALIGN = -1, -3, -6, -7
@@ -96,50 +96,10 @@ def test_picking_thread_code_equals_full_resampler_then_column_pick(oracle, M, I
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
-#
-# Test signal: per carrier a coded downlink (synth.gen_downlink, its own cell) modulated at 36 ksps (synth.gen_channel), raised to the
-# capture rate by band-limited interpolation (zero-padding in frequency, float64), shifted to the centre of its bin; the carriers
-# summed over a noise floor.
-
-
-def _capture(torch, synth, M, carriers, nslots, seed=1, noise=1e-3):
-    """carriers {bin: seed} at Fs = M x 25 kHz -> (x complex64 [n] on cuda, cells {bin: (mcc, mnc, cc)}, tx {bin: gen_downlink})."""
-    dev = torch.device("cuda")
-    fs = M * 25000.0
-    N = (nslots * 510 - 100) // 9 * 9             # 36 ksps samples; Fs / 36 kHz = M 25 / 36 is a multiple of 1/9
-    L = int(round(N * fs / 36000.0))
-    x = torch.zeros(L, dtype=torch.complex128, device=dev)
-    n = torch.arange(L, dtype=torch.float64, device=dev)
-    cells, tx = {}, {}
-    for k, sd in carriers.items():
-        cells[k] = (100 + 7 * sd % 900, 1000 + 13 * sd, (5 + 3 * sd) % 64)
-        tx[k] = synth.gen_downlink(nslots, sd, cell=cells[k])
-        s = torch.from_numpy(synth.gen_channel(N, sd + 100, bits=tx[k][0], amp=1.0)[0].astype(np.complex128)).to(dev)
-        S = torch.fft.fft(s)
-        Y = torch.zeros(L, dtype=torch.complex128, device=dev)
-        Y[: N // 2] = S[: N // 2]
-        Y[L - (N - N // 2):] = S[N // 2:]
-        y = torch.fft.ifft(Y) * (L / N)
-        kc = k if k < M // 2 else k - M
-        x += y * torch.polar(torch.ones_like(n), 2.0 * math.pi * kc / M * n)
-    g = torch.Generator(device=dev)
-    g.manual_seed(seed)
-    x += noise * torch.view_as_complex(torch.randn((L, 2), device=dev, generator=g, dtype=torch.float64))
-    x *= 0.25 / float(x.abs().max())
-    return x.to(torch.complex64).contiguous(), cells, tx
-
-
-def _cs16(torch, x):
-    return torch.view_as_real(x).mul(32768.0).round().clamp(-32768, 32767).to(torch.int16).contiguous()
 
 
 def _rows(rx, R, which=0):
-    got = {}
-    for k in range(R.N_KINDS):
-        blocks, t1 = rx.fetch(k, which)
-        got[k] = [(int(b["channel"]), int(b["bitnum"]), int(b["crc_ok"]), int(b["tdma_time_rx"]), int(b["tdma_time"]), t1[j].tobytes())
-                  for j, b in enumerate(blocks)]
-    return got
+    return collect(rx, R, which)
 
 
 M_SMALL, D_SMALL, BINS_SMALL = 32, 16, [1, 7, 20, 31]
