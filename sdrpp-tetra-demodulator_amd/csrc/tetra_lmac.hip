@@ -39,6 +39,7 @@
 #include "../../include/ext/tetra_list.h"
 #include "../../include/ext/tetra_aach_soft.h"
 #include "../../include/ext/tetra_soft.h"
+#include "../../include/ext/tetra_tch.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "compact_core.hpp"
@@ -47,6 +48,7 @@
 #include "lmac_core.hpp"
 #include "lmac_impl.hpp"
 #include "soft_core.hpp"
+#include "tch_core.hpp"
 
 namespace {
 
@@ -374,6 +376,136 @@ __global__ __launch_bounds__(kLanes) void k_lmac_frames_soft(const JobTable tab,
     if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, good);
     __syncthreads();
     write_rows(sm.outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
+}
+
+// ---- circuit-mode data channels TCH/7.2, TCH/4.8, TCH/2.4 (include/ext/tetra_tch.h; lane code: tch_core.hpp) ---------------------------
+// Kernels of their own, so that the kernels above are the code objects they were: the workgroup shape (one wavefront, a block per lane),
+// the front ends, the decision scratch [workgroup][step pair][lane] and the row write-back are k_lmac_decode's and k_lmac_frames'; the
+// forward recursion takes its branch metrics from up to three generators per step by the kind's schedule, the traceback has no CRC
+// beside it, and a launch that counts encodes the decoded bits again with the same schedule.  The kind (generators per step, ng) is
+// workgroup-uniform; TCH/7.2 (ng = 0) is descrambling alone: a lane fetches its row's scrambling sequence, the workgroup XORs it onto
+// the rows four bytes at a time.
+typedef uint16_t TchOutW[tetra_tch::kOutHalves][kLanes + kOutPad];
+struct TchIo {
+    TchOutW& outw;
+    uint32_t* dec;
+    int lane;
+    __device__ __forceinline__ void dec_st(int u, uint32_t w) const { dec[u * kLanes] = w; }
+    __device__ __forceinline__ uint32_t dec_ld(int u) const { return dec[u * kLanes]; }
+    __device__ __forceinline__ void out_st(int h, uint32_t half) const { outw[h][lane] = (uint16_t)half; }
+    __device__ __forceinline__ uint32_t out_ld(int h) const { return outw[h][lane]; }
+};
+__device__ __forceinline__ void tch_write_rows(const TchOutW& outw, int lane, int rows_here, int type2, uint8_t* __restrict__ out0, int out_stride) {
+    tetra_tch::write_rows(lane, rows_here, type2, rows_wide(out0, out_stride), [&](int h, int q) { return outw[h][q]; },
+                          [&](int q, int d, demux_core::U2 v) { reinterpret_cast<demux_core::U2*>(out0 + (size_t)q * out_stride)[d] = v; },
+                          [&](int q, int d, uint32_t v) { reinterpret_cast<uint32_t*>(out0 + (size_t)q * out_stride)[d] = v; });
+}
+// LDS per workgroup: 4352 (staging) + 7168 (the block as bits or soft classes) + 2508 (decoded halves) = 14028 B.
+// packed_ok = 0: every row through the byte route (tetra_lmac_debug_force_byte_route); biterr_out NULL: no counts.
+__global__ __launch_bounds__(kLanes) void k_tch_rows(const uint8_t* __restrict__ type5, int n_blocks, int in_stride,
+                                                     const uint32_t* __restrict__ scramb_init, int ng, int type2,
+                                                     uint8_t* __restrict__ out, int out_stride,
+                                                     uint32_t* __restrict__ dec_scratch, int dec_pairs,
+                                                     const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index,
+                                                     const uint32_t* __restrict__ seq_tab, int packed_ok, uint32_t* __restrict__ biterr_out) {
+    __shared__ uint32_t stage[kLanes][kStageWords];
+    __shared__ uint32_t cls[kClsWords + 1][kLanes];
+    __shared__ TchOutW outw;
+    const int lane = threadIdx.x;
+    const int blk0 = blockIdx.x * kLanes;
+    const int blk = blk0 + lane;
+    if (n_blocks_dev) {
+        const int have = *n_blocks_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
+        if (blk0 >= n_blocks) return;
+    }
+    const int rows_here = min(kLanes, n_blocks - blk0);
+    const uint32_t code = blk >= n_blocks ? kScrambInitSb1 : scramb_init[init_index ? init_index[blk] : blk];
+    constexpr int type345 = tetra_tch::kType345;
+    if (ng == 0) {
+        lane_sequence(type345, code, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
+        __syncthreads();
+        tetra_tch::passthrough_rows(lane, rows_here, [&](int w, int q) { return cls[w][q]; },
+                                    [&](int q, int d) { return reinterpret_cast<const uint32_t*>(type5 + (size_t)(blk0 + q) * in_stride)[d]; },
+                                    [&](int q, int d, uint32_t v) { reinterpret_cast<uint32_t*>(out + (size_t)(blk0 + q) * out_stride)[d] = v; });
+        return;
+    }
+    // the front end of k_lmac_decode
+    bool byte_route = needs_byte_route(packed_ok ? seq_tab : nullptr, type5, in_stride);
+    if (!byte_route) {
+        const U2* base = reinterpret_cast<const U2*>(type5 + (size_t)blk0 * in_stride);
+        uint8_t* sb = reinterpret_cast<uint8_t*>(&stage[0][0]);
+        const uint32_t dirty = pack_units(lane, rows_here, in_stride, type345, [&](int u) { return base[u]; },
+                                          [&](size_t at, uint8_t byte) { sb[at] = byte; });
+        byte_route = __builtin_amdgcn_ballot_w64(dirty != 0) != 0;          // wave-uniform
+        __syncthreads();
+        if (!byte_route) {
+            uint32_t xb[kSeqWords];
+            const uint32_t* mine = stage[lane];
+            staged_row(type345, [&](int w) { return mine[w]; }, xb);
+            descramble_words(type345, code, xb, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
+        }
+    }
+    TchIo io{ outw, dec_scratch + (size_t)blockIdx.x * dec_pairs * kLanes + lane, lane };
+    auto staged = [&](int w) { return cls[w][lane]; };
+    uint32_t biterr;
+    if (!byte_route) {
+        __syncthreads();
+        biterr = tetra_tch::decode_lane<true>(ng, type2, biterr_out != nullptr, staged, io);
+    } else {
+        uint32_t lfsr = code;
+        const int row_dw = type345 >> 2;
+        for (int c0 = 0; c0 < row_dw; c0 += kChunkDwords) {
+#pragma unroll 4
+            for (int it = 0; it < kLanes * kChunkDwords / kLanes; ++it) {
+                const int q = it * (kLanes / kChunkDwords) + lane / kChunkDwords, d = lane % kChunkDwords;
+                uint32_t v = 0;
+                if (q < rows_here && c0 + d < row_dw)
+                    v = reinterpret_cast<const uint32_t*>(type5 + (size_t)(blk0 + q) * in_stride)[c0 + d];
+                stage[q][d] = v;
+            }
+            __syncthreads();
+            lfsr = descramble_chunk(type345 - 4 * c0, lfsr, [&](int d) { return stage[lane][d]; },
+                                    [&](int w, uint32_t word) { cls[c0 / 4 + w][lane] = word; });
+            __syncthreads();
+        }
+        biterr = tetra_tch::decode_lane<false>(ng, type2, biterr_out != nullptr, staged, io);
+    }
+    if (biterr_out && blk < n_blocks) biterr_out[blk] = biterr;
+    __syncthreads();
+    tch_write_rows(outw, lane, rows_here, type2, out + (size_t)blk0 * out_stride, out_stride);
+}
+
+// The TCH jobs of a frame launch: k_lmac_frames' prologue, the SCH/F cut of the frame, verdict 1 and the label; counts.out[job] NULL: the
+// job does not count.  LDS per workgroup: 3584 (type-4 bits) + 2508 (decoded halves) = 6092 B.
+__global__ __launch_bounds__(kLanes) void k_tch_frames(const JobTable tab, uint32_t* __restrict__ dec_scratch, const uint32_t* __restrict__ seq_tab,
+                                                       const BiterrTable counts_tab) {
+    __shared__ uint32_t cls[kSeqWords][kLanes];
+    __shared__ TchOutW outw;
+    const int lane = threadIdx.x;
+    FrameLane L = frame_group(tab, lane);
+    if (L.blk0 >= L.n_blocks) return;
+    frame_of(tab, L);
+    const DevJob& J = L.J;
+    const int ft = tab.src.frame_type[L.f];
+    uint32_t fw[kFrameWords];
+    load_frame(frame_rows(tab.src.frames, L.f), fw);
+    frame_hard_block(&J, L.code, fw, [&] { return ft; }, seq_rows(seq_tab), [&](int w, uint32_t word) { cls[w][lane] = word; });
+    if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, true);
+    const int ng = tetra_tch::ng_of_type2(J.type2);
+    uint8_t* out0 = J.out + (size_t)L.blk0 * J.out_stride;
+    __syncthreads();
+    if (ng == 0) {
+        tetra_tch::passthrough_rows(lane, L.rows_here, [&](int w, int q) { return cls[w][q]; }, [&](int, int) { return 0u; },
+                                    [&](int q, int d, uint32_t v) { reinterpret_cast<uint32_t*>(out0 + (size_t)q * J.out_stride)[d] = v; });
+        return;
+    }
+    TchIo io{ outw, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
+    uint32_t* counts = job_counts(tab, counts_tab);            // (workgroup-uniform: a workgroup has one job)
+    const uint32_t biterr = tetra_tch::decode_lane<true>(ng, J.type2, counts != nullptr, [&](int w) { return cls[w][lane]; }, io);
+    if (counts && L.blk < L.n_blocks) counts[L.blk] = biterr;
+    __syncthreads();
+    tch_write_rows(outw, lane, L.rows_here, J.type2, out0, J.out_stride);
 }
 
 // ---- list decoding of the rows whose CRC failed (include/ext/tetra_list.h; lane code: list_core.hpp) ------------------------------------------
@@ -1056,6 +1188,80 @@ static int decode_counted(int type, const uint8_t* d_type5, int n_blocks, const 
     return hipGetLastError() == hipSuccess ? TETRA_OK : TETRA_ERR_HIP;
 }
 
+// ---- include/ext/tetra_tch.h: byte rows ----------------------------------------------------------------------------------------------
+int tetra_lmac_tch_blk_param(int kind, tetra_lmac_blk_param_t* out) {
+    if (!tetra_tch::is_tch(kind) || !out) return TETRA_ERR_ARG;
+    const tetra_tch::Kind k = tetra_tch::kind_of(kind);
+    out->type345_bits = tetra_tch::kType345;
+    out->type2_bits = k.type2;
+    out->type1_bits = k.type1;
+    out->interleave_a = k.ng ? tetra_tch::kInterleaveA : 0;
+    out->have_crc16 = 0;
+    return TETRA_OK;
+}
+
+// check_args for a TCH kind (no verdicts; counts only for the coded kinds)
+static int tch_check_args(int kind, const void* in, int n_blocks, int in_stride, const void* init, const void* out, int out_stride,
+                          const void* biterr, bool device_ptrs) {
+    if (!tetra_tch::is_tch(kind) || n_blocks < 0) return TETRA_ERR_ARG;
+    if (biterr && kind == TETRA_LMAC_T_TCH_7_2) return TETRA_ERR_ARG;           // not coded: nothing to encode again
+    if (n_blocks == 0) return TETRA_OK;
+    if (!in || !out || !init) return TETRA_ERR_ARG;
+    if (in_stride < tetra_tch::kType345 || out_stride < tetra_tch::kind_of(kind).type2) return TETRA_ERR_ARG;
+    if ((in_stride & 3) || (out_stride & 3)) return TETRA_ERR_ALIGN;
+    if (device_ptrs && (((uintptr_t)in & 3) || ((uintptr_t)out & 3) || ((uintptr_t)biterr & 3))) return TETRA_ERR_ALIGN;
+    return TETRA_OK;
+}
+
+int tetra_lmac_decode_tch_counted_device(int kind, const uint8_t* d_type5, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                                         const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                                         uint32_t* d_biterr, void* hip_stream) {
+    const int rc = tch_check_args(kind, d_type5, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_biterr, true);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const tetra_tch::Kind k = tetra_tch::kind_of(kind);
+    const uint32_t* seq = seq_table();
+    if (!seq) return TETRA_ERR_NOMEM;
+    const int groups = (n_blocks + kLanes - 1) / kLanes;
+    const int dec_pairs = k.ng ? (k.type2 + kFlush) / 2 : 0;
+    ScratchLease scratch;
+    if (dec_pairs)
+        if (const int err = scratch.take((size_t)groups * dec_pairs * kLanes * sizeof(uint32_t), nullptr, 0, s)) return err;
+    hipLaunchKernelGGL(k_tch_rows, dim3(groups), dim3(kLanes), 0, s, d_type5, n_blocks, in_stride, d_scramb_init, k.ng, k.type2, d_type2, out_stride,
+                       scratch.p, dec_pairs, d_n_blocks, d_init_index, seq, g_force_byte_route ? 0 : 1, d_biterr);
+    return scratch.launched();
+}
+
+int tetra_lmac_decode_tch_batch(int kind, const uint8_t* type5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                                uint8_t* type2, int out_stride, uint32_t* biterr, int device) {
+    const int rc = tch_check_args(kind, type5, n_blocks, in_stride, scramb_init, type2, out_stride, biterr, false);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_HIP;
+    DevMem<uint8_t> d_in, d_out;
+    DevMem<uint32_t> d_init, d_biterr;
+    const size_t in_bytes = (size_t)n_blocks * in_stride, out_bytes = (size_t)n_blocks * out_stride;
+    if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_init.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess ||
+        (biterr && d_biterr.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess))
+        return TETRA_ERR_NOMEM;
+    if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_in, type5, in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int drc = tetra_lmac_decode_tch_counted_device(kind, d_in, n_blocks, nullptr, in_stride, d_init, nullptr, d_out, out_stride,
+                                                         biterr ? (uint32_t*)d_biterr : nullptr, nullptr);
+    if (drc != TETRA_OK) return drc;
+    if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    // only the type2 columns: the caller's row padding is left alone
+    const int row = tetra_tch::kind_of(kind).type2;
+    if (out_stride == row ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
+                          : hipMemcpy2D(type2, out_stride, d_out, out_stride, row, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    return TETRA_OK;
+}
+
 }  // extern "C"
 
 // Every frame entry point (lmac_impl.hpp): one job table, the kernel the options select, the list launches behind it for the jobs with ranks.
@@ -1080,8 +1286,37 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     bool any_rm = false;
     DevJob aach[TETRA_LMAC_MAX_JOBS];
     int aach_min_margin[TETRA_LMAC_MAX_JOBS], n_aach = 0;
+    // the TCH jobs (tetra_tch.h): a table and a launch of their own behind the others, their scratch behind the others' in the one lease
+    JobTable tch = {};
+    BiterrTable tch_counts = {};
+    long long tch_groups_total = 0;
     for (int i = 0; i < n_jobs; ++i) {
         tetra_lmac_job_t j = jobs[i];
+        if (tetra_tch::is_tch(j.type)) {
+            if (soft || opts.d_rank) return TETRA_ERR_ARG;         // no soft-decision TCH; no CRC for a list decoder to aim at
+            const tetra_tch::Kind k = tetra_tch::kind_of(j.type);
+            uint32_t* const job_counts = opts.d_biterr ? opts.d_biterr[i] : nullptr;
+            if (j.max_rows < 0 || (job_counts && !k.ng)) return TETRA_ERR_ARG;
+            if ((uintptr_t)job_counts & 3) return TETRA_ERR_ALIGN;
+            if (j.max_rows == 0) continue;
+            if (!j.d_row_frame || !j.d_type2 || !j.d_crc_ok || !j.d_frame_scramb) return TETRA_ERR_ARG;
+            if (j.d_labels && (!src->d_frame_bitnum || !src->d_time_rx || !src->d_time || src->frames_per_channel < 1)) return TETRA_ERR_ARG;
+            if (j.out_stride < k.type2) return TETRA_ERR_SIZE;
+            if ((j.out_stride & 7) || ((uintptr_t)j.d_type2 & 7)) return TETRA_ERR_ALIGN;
+            tch_counts.out[tch.n] = job_counts;
+            DevJob& d = tch.job[tch.n++];
+            d.row_frame = j.d_row_frame; d.n_rows_dev = j.d_n_rows; d.frame_scramb = j.d_frame_scramb; d.out = j.d_type2; d.crc_ok = j.d_crc_ok;
+            d.labels = j.d_labels; d.n_rows = j.max_rows; d.out_stride = j.out_stride; d.layout = kLayoutSchF;
+            d.type345 = tetra_tch::kType345; d.type2 = k.type2; d.a = tetra_tch::kInterleaveA;
+            d.dec_pairs = k.ng ? (k.type2 + kFlush) / 2 : 0;
+            const long long groups = ((long long)j.max_rows + kLanes - 1) / kLanes;
+            d.first_group = (int)tch_groups_total;
+            d.scratch_base = scratch_words;
+            tch_groups_total += groups;
+            scratch_words += groups * d.dec_pairs * kLanes;
+            if (tch_groups_total > 0x7fffffffLL) return TETRA_ERR_SIZE;
+            continue;
+        }
         const bool rm = j.type == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014);       // (the flag on any other type: refused below)
         // the AACH by maximum likelihood on the ring's values (tetra_aach_soft.h): the soft entry point's alone, min_margin in bits 16..25
         const bool ml = j.type >= 0 && (j.type & ~TETRA_LMAC_JOB_AACH_MIN_MARGIN(0x3ff)) == (TETRA_TPSAP_T_BBK | TETRA_LMAC_JOB_RM3014_SOFT);
@@ -1139,7 +1374,7 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
         if (groups_total > 0x7fffffffLL) return TETRA_ERR_SIZE;
     }
     tab.n = n;
-    if (n == 0 && n_aach == 0) return TETRA_OK;
+    if (n == 0 && n_aach == 0 && tch.n == 0) return TETRA_OK;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const uint32_t* seq = seq_table();
     if (!seq) return TETRA_ERR_NOMEM;
@@ -1150,13 +1385,16 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
                                aach[k], tab.src, seq, reinterpret_cast<const uint32_t*>(soft->d_ring), soft->size / 4u, aach_min_margin[k]);
         return n_aach && hipGetLastError() != hipSuccess ? TETRA_ERR_HIP : TETRA_OK;
     };
-    if (n == 0) return launch_aach();
+    if (n == 0 && tch.n == 0) return launch_aach();
+    tch.src = tab.src;
     const size_t bytes = (size_t)scratch_words * sizeof(uint32_t);
     ScratchLease scratch;
     if (const int err = scratch_words ? scratch.take(bytes, src->d_workspace, src->workspace_bytes, s) : TETRA_OK) return err;
     // a launch that counts is an instantiation of its own; every other launch is the kernel it was
     const dim3 grid((unsigned)groups_total), block(kLanes);
-    if (soft) {
+    if (n == 0) {
+        // TCH jobs alone
+    } else if (soft) {
         const uint32_t* ring = reinterpret_cast<const uint32_t*>(soft->d_ring);
         if (any_counts) hipLaunchKernelGGL((k_lmac_frames_soft<true, BiterrTable>), grid, block, 0, s, tab, scratch.p, seq, ring, soft->size / 4u, counts);
         else hipLaunchKernelGGL(k_lmac_frames_soft<false>, grid, block, 0, s, tab, scratch.p, seq, ring, soft->size / 4u);
@@ -1170,6 +1408,7 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     } else {
         hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, nullptr);
     }
+    if (tch.n) hipLaunchKernelGGL(k_tch_frames, dim3((unsigned)tch_groups_total), block, 0, s, tch, scratch.p, seq, tch_counts);
     // the jobs with ranks, all in one set of list launches: behind the decode launch, in front of the scratch's hand-back
     RescueTable rt = {};
     for (int k = 0; k < n; ++k) {
@@ -1214,6 +1453,11 @@ size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, in
     size_t words = 0;
     for (int i = 0; i < n_jobs; ++i) {
         const tetra_lmac_job_t& j = jobs[i];
+        if (tetra_tch::is_tch(j.type) && j.max_rows > 0) {         // tetra_tch.h; TCH/7.2 has no trellis
+            const tetra_tch::Kind k = tetra_tch::kind_of(j.type);
+            words += (size_t)(((long long)j.max_rows + kLanes - 1) / kLanes) * (k.ng ? (k.type2 + kFlush) / 2 : 0) * kLanes;
+            continue;
+        }
         if (j.type < 0 || j.type > 5 || j.type == TETRA_TPSAP_T_BBK || j.max_rows <= 0) continue;
         words += (size_t)(((long long)j.max_rows + kLanes - 1) / kLanes) * ((blk_param(j.type).type2 + kFlush) / 2) * kLanes;
     }

@@ -79,16 +79,24 @@ SOFT_ABI = {
 AACH_SOFT_ABI = {
     "tetra_lmac_rm3014_soft_decode_device": (i32, [vp, i32, i32, vp, vp, vp, vp]),
 }
+# include/ext/tetra_tch.h: the circuit-mode data channels; the kinds go where a TPSAP_T_* goes in decode_frames_device's job list
+TCH_ABI = {
+    "tetra_lmac_tch_blk_param": (i32, [i32, P(BlkParam)]),
+    "tetra_lmac_decode_tch_counted_device": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
+    "tetra_lmac_decode_tch_batch": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32]),
+}
+T_TCH_7_2, T_TCH_4_8, T_TCH_2_4 = 8, 9, 10          # TETRA_LMAC_T_TCH_*
 LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
 SOFT_EXPORTS = list(SOFT_ABI)
 AACH_SOFT_EXPORTS = list(AACH_SOFT_ABI)
+TCH_EXPORTS = list(TCH_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI},
-                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI, **TCH_ABI},
+                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS + TCH_EXPORTS)
 
 
 def force_byte_route(on):
@@ -160,6 +168,32 @@ def decode_counted_biterr_device(blk_type, d_type5, capacity, d_n_blocks, in_str
     """tetra_lmac_decode_counted_biterr_device: decode_counted_device plus d_biterr (int32 / uint32 tensor [capacity], or None)."""
     call(_lib().tetra_lmac_decode_counted_biterr_device, int(blk_type), ptr(d_type5), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
          ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_crc_ok), ptr(d_biterr), stream_ptr(stream))
+
+
+def tch_blk_param(kind):
+    """tetra_lmac_tch_blk_param (include/ext/tetra_tch.h): the block parameters of T_TCH_7_2 / T_TCH_4_8 / T_TCH_2_4."""
+    p = BlkParam()
+    call(_lib().tetra_lmac_tch_blk_param, int(kind), C.byref(p))
+    return p
+
+
+def decode_tch(kind, type5, scramb_init, biterr=False, device=-1):
+    """tetra_lmac_decode_tch_batch: type5 uint8 [n][in_stride] (in_stride % 4 == 0, >= 432), scramb_init uint32 [n]
+    -> type2 uint8 [n][type2_bits], and with biterr=True also the channel bit-error words uint32 [n] (split_biterr; not for T_TCH_7_2)."""
+    rows = np.ascontiguousarray(type5, np.uint8)
+    n, in_stride = rows.shape
+    ost = tch_blk_param(kind).type2_bits
+    si = np.ascontiguousarray(scramb_init, np.uint32)
+    out = np.zeros((n, ost), np.uint8)
+    be = np.zeros(n, np.uint32) if biterr else None
+    call(_lib().tetra_lmac_decode_tch_batch, int(kind), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(be), device)
+    return (out, be) if biterr else out
+
+
+def decode_tch_counted_device(kind, d_type5, capacity, d_n_blocks, in_stride, d_scramb, d_init_index, d_type2, out_stride, d_biterr=None, stream=None):
+    """tetra_lmac_decode_tch_counted_device: torch tensors on the GPU; d_n_blocks, d_init_index and d_biterr may be None."""
+    call(_lib().tetra_lmac_decode_tch_counted_device, int(kind), ptr(d_type5), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
+         ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
 
 
 def decode_batch_list(blk_type, type5, scramb=None, max_candidates=LIST_DEFAULT_CANDIDATES, device=-1):
