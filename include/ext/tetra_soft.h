@@ -7,6 +7,8 @@
  * soft values of its own: the frames say WHERE a block lies (burst type, bit number, channel), the ring holds WHAT was received there.
  * The decoder is the reference's conv_cch_decode on those values -- descrambled by sign, deinterleaved, depunctured onto zeros -- bit
  * for bit, with the CRC verdict on top; the receive chain keeps calling the decoder directly, nothing about it changes.
+ * Limits.  The circuit-mode data channels (tetra_tch.h) are not among the kinds of this entry point: a TCH job is TETRA_ERR_ARG here.
+ * tetra_tch_soft.h declares the entry that takes TCH/4.8 and TCH/2.4 jobs beside these kinds, and the int8 byte-row entries.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */
 #ifndef TETRA_SOFT_H

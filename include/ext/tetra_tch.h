@@ -22,7 +22,8 @@
  *
  * Limits.  Interleaving over N = 4 or 8 blocks (EN 300 392-2 8.2.4.2) is NOT built: only N = 1.  tetra_rx / tetra_wbrx do not route
  * traffic slots: which (carrier, timeslot) carries circuit-mode data, and at which rate, is upper-MAC knowledge that stays on the host,
- * which lists those slots' frames and hands them to a TCH job.  No soft-decision TCH; no speech (TCH/S).
+ * which lists those slots' frames and hands them to a TCH job.  No speech (TCH/S).  Soft-decision decoding of TCH/4.8
+ * and TCH/2.4 is tetra_tch_soft.h's, with entry points of its own; the ones declared here read hard bits.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */
 #ifndef TETRA_TCH_H
@@ -77,8 +78,8 @@ int tetra_lmac_decode_tch_batch(int kind, const uint8_t* type5, int n_blocks, in
  * out_stride follow the rules of any job (8-byte aligned, out_stride a multiple of 8 and >= type2), d_crc_ok[row] = 1 (there is nothing
  * to check, as the reference reports for the AACH), d_labels as for any job, counts as tetra_biterr.h (not for TCH/7.2).  TCH jobs and
  * the kinds of tetra_lmac.h may be mixed in one call: the TCH jobs run in a launch of their own behind the others on the same stream,
- * so the kernel that decodes the signalling kinds is the kernel it was.  The soft frame decoder (tetra_soft.h) and the list decoder
- * (tetra_list.h) return TETRA_ERR_ARG for a TCH job; the entry points of tetra_lmac.h that take one kind per call return for the values
+ * so the kernel that decodes the signalling kinds is the kernel it was.  The soft frame decoder (tetra_soft.h; tetra_tch_soft.h declares the entry
+ * that takes TCH jobs on soft values) and the list decoder (tetra_list.h) return TETRA_ERR_ARG for a TCH job; the entry points of tetra_lmac.h that take one kind per call return for the values
  * 8..10 what they always returned.
  */
 

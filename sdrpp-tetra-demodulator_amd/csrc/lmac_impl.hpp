@@ -1,6 +1,6 @@
 // lmac_impl.hpp -- the frame decoder (tetra_lmac.hip) as its callers inside the library see it: ONE function, decode_frames, that takes
-// every option of a frame launch as a FrameOpts.  The four frame entry points of the C ABI (tetra_lmac_decode_frames_device,
-// _biterr_device, _list_device, _soft_device) are it with the options their signatures can express; the receive chain (tetra_rx.hip) builds the
+// every option of a frame launch as a FrameOpts.  The frame entry points of the C ABI (tetra_lmac_decode_frames_device,
+// _biterr_device, _list_device, _soft_device, _soft_tch_device) are it with the options their signatures can express; the receive chain (tetra_rx.hip) builds the
 // options from its handle's flags -- soft values from the chain's ring, bit-error counts, ranks, where the list launches keep their work --
 // and calls it directly.  Host-side, hidden from the C ABI.
 #pragma once
@@ -41,6 +41,7 @@ struct FrameOpts {
     int32_t* const* d_rank = nullptr;           // NULL, or per job where its ranks go (NULL: the job is not rescued), tetra_list.h
     int max_candidates = 0;                     // the ranks' T; looked at only for a job with ranks
     ListWork list_work;
+    bool soft_tch = false;                      // with soft: TCH/4.8 and TCH/2.4 jobs are accepted and read the ring too (tetra_tch_soft.h)
 };
 
 // tetra_lmac_decode_frames_device with options: same jobs, rows, verdicts, labels and workspace.  Launches on the stream: the decode

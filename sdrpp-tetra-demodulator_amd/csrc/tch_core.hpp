@@ -52,12 +52,23 @@ constexpr uint32_t pair_pattern(int ng, int u) {
 // the values of a step pair as the forward recursion fetches them: LDS words and where in them; keep = 0 where the last one is absent
 template <int VALS> struct RawPair { uint32_t w[VALS]; uint32_t at[VALS]; uint32_t keep; };
 
-// (s, -s) of the value k of a fetched pair: from a packed bit (0 -> +1, 1 -> -1) or a 2-bit signed class
-template <bool BITS, int VALS>
+// What a lane's descrambled block is made of: soft classes (2 bits, 16 per word), packed bits (32 per word), or the staged bytes of
+// soft_core.hpp (soft value + 128, four per word: tch_soft_core.hpp).  kSrcClasses / kSrcBits are the BITS = false / true of decode_lane.
+enum { kSrcClasses = 0, kSrcBits = 1, kSrcSoft = 2 };
+template <int SRC> LM_FN uint32_t src_word(int p) { return (uint32_t)(SRC == kSrcBits ? p >> 5 : SRC == kSrcSoft ? p >> 2 : p >> 4); }
+template <int SRC> LM_FN uint32_t src_at(int p) {
+    return SRC == kSrcBits ? 31u - (uint32_t)(p & 31) : SRC == kSrcSoft ? 8u * (uint32_t)(p & 3) : (uint32_t)(30 - 2 * (p & 15));
+}
+
+// (s, -s) of the value k of a fetched pair: from a packed bit (0 -> +1, 1 -> -1), a 2-bit signed class or a staged byte (raw soft value)
+template <int SRC, int VALS>
 LM_FN Pk pair_value(const RawPair<VALS>& r, int k) {
     Pk v;
-    if (BITS) v = pk_from_bits(0xffff0001u ^ (bfe_mask(r.w[k], r.at[k]) & 0xfffefffeu));
-    else {
+    if (SRC == kSrcBits) v = pk_from_bits(0xffff0001u ^ (bfe_mask(r.w[k], r.at[k]) & 0xfffefffeu));
+    else if (SRC == kSrcSoft) {
+        const int c = (int)bfe_u(r.w[k], r.at[k], 8) - 128;
+        v = pk_make(c, -c);
+    } else {
         const int c = (int)(r.w[k] << r.at[k]) >> 30;
         v = pk_make(c, -c);
     }
@@ -72,10 +83,11 @@ LM_FN void step_metrics(Pk A, Pk B, Pk G, Pk Mm[8]) {
 }
 
 // Forward recursion over n2 + 4 steps, two per round, software-pipelined by one round like viterbi_forward.  cls(word): the lane's
-// descrambled block (BITS: bit i at bit 31 - (i & 31) of word i >> 5; else soft classes, 16 per word); st(u, word): decision_word of
-// steps 2u, 2u + 1.  The schedule runs as a countdown to the next short pair: wave-uniform, no division.
-template <int NG, bool BITS, class Cls, class St>
-LM_FN void forward(int n2, Cls cls, St st) {
+// descrambled block (kSrcBits: bit i at bit 31 - (i & 31) of word i >> 5; kSrcClasses: soft classes, 16 per word; kSrcSoft: staged
+// bytes, four per word); st(u, word): decision_word of steps 2u, 2u + 1; s0: the start metric of state 0 in the values' units, as
+// viterbi_forward's.  The schedule runs as a countdown to the next short pair: wave-uniform, no division.
+template <int NG, int SRC, class Cls, class St>
+LM_FN void forward(int n2, Cls cls, St st, int s0 = 4 * 5) {
     constexpr int VALS = NG == 2 ? 3 : 6, PERIOD = NG == 2 ? 22 : 6;
     int pos = kInterleaveA, left = PERIOD;
     auto fetch = [&] {
@@ -87,25 +99,25 @@ LM_FN void forward(int n2, Cls cls, St st) {
         for (int k = 0; k < VALS; ++k) {
             int p = pos;
             if (k < VALS - 1 || !is_short) p = interleave_next(pos, kInterleaveA, kType345);      // (an absent value reads a live word and is masked)
-            r.w[k] = cls(BITS ? p >> 5 : p >> 4);
-            r.at[k] = BITS ? 31u - (uint32_t)(p & 31) : (uint32_t)(30 - 2 * (p & 15));
+            r.w[k] = cls((int)src_word<SRC>(p));
+            r.at[k] = src_at<SRC>(p);
         }
         return r;
     };
     PathMetrics pm;
 #pragma unroll
     for (int i = 0; i < 8; ++i) pm.R[i] = pk_make(0, 0);
-    pm.R[0] = pk_make(4 * 5, 0);
+    pm.R[0] = pk_make(s0, 0);
     const Pk z = pk_make(0, 0);
     auto raw = fetch();
     for (int u = 0; u < n2 / 2; ++u) {
         Pk Me[8], Mo[8], De[8], Do[8];
         if (NG == 2) {
-            step_metrics(pair_value<BITS>(raw, 0), pair_value<BITS>(raw, 1), z, Me);
-            step_metrics(pair_value<BITS>(raw, 2), z, z, Mo);
+            step_metrics(pair_value<SRC>(raw, 0), pair_value<SRC>(raw, 1), z, Me);
+            step_metrics(pair_value<SRC>(raw, 2), z, z, Mo);
         } else {
-            step_metrics(pair_value<BITS>(raw, 0), pair_value<BITS>(raw, 1), pair_value<BITS>(raw, 2), Me);
-            step_metrics(pair_value<BITS>(raw, 3), pair_value<BITS>(raw, 4), pair_value<BITS>(raw, VALS - 1), Mo);
+            step_metrics(pair_value<SRC>(raw, 0), pair_value<SRC>(raw, 1), pair_value<SRC>(raw, 2), Me);
+            step_metrics(pair_value<SRC>(raw, 3), pair_value<SRC>(raw, 4), pair_value<SRC>(raw, VALS - 1), Mo);
         }
         if (u + 1 < n2 / 2) raw = fetch();
         acs_step(pm, Me, De);
@@ -198,7 +210,7 @@ LM_FN uint32_t reencode_errors(int n2, Half half, Rx rx) {
 // of the decoded halves.  count: also the channel bit errors (else 0).
 template <int NG, bool BITS, class Cls, class Io>
 LM_FN uint32_t decode_kind(int n2, bool count, Cls cls, Io& io) {
-    forward<NG, BITS>(n2, cls, [&](int u, uint32_t w) { io.dec_st(u, w); });
+    forward<NG, BITS ? kSrcBits : kSrcClasses>(n2, cls, [&](int u, uint32_t w) { io.dec_st(u, w); });
     traceback(n2, [&](int u) { return io.dec_ld(u); }, [&](int h, uint32_t half) { io.out_st(h, half); });
     if (!count) return 0u;
     return reencode_errors<NG>(n2, [&](int h) { return io.out_ld(h); }, [&](int p) -> uint32_t {

@@ -40,6 +40,7 @@
 #include "../../include/ext/tetra_aach_soft.h"
 #include "../../include/ext/tetra_soft.h"
 #include "../../include/ext/tetra_tch.h"
+#include "../../include/ext/tetra_tch_soft.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "compact_core.hpp"
@@ -49,6 +50,7 @@
 #include "lmac_impl.hpp"
 #include "soft_core.hpp"
 #include "tch_core.hpp"
+#include "tch_soft_core.hpp"
 
 namespace {
 
@@ -506,6 +508,78 @@ __global__ __launch_bounds__(kLanes) void k_tch_frames(const JobTable tab, uint3
     if (counts && L.blk < L.n_blocks) counts[L.blk] = biterr;
     __syncthreads();
     tch_write_rows(outw, lane, L.rows_here, J.type2, out0, J.out_stride);
+}
+
+// ---- the coded data channels from SOFT values (include/ext/tetra_tch_soft.h; lane code: tch_soft_core.hpp) ----------------------------------
+// The two kernels above with the soft front end of k_lmac_frames_soft: a lane's block is 432 staged bytes in LDS, the forward recursion
+// takes raw soft values by the kind's schedule; traceback, counts, scratch [workgroup][step pair][lane] and row write-back are the hard
+// siblings'.  One wavefront per workgroup, a block per lane; ng (2 or 3) is workgroup-uniform.
+// LDS per workgroup, k_tch_rows_soft: 28080 (108 staged words x 65: the rows arrive transposed, see below) + 2508 (decoded halves) =
+// 30588 B; k_tch_frames_soft: 27648 + 2508 = 30156 B.  Either way five workgroups = five waves per CU of 160 KB, as k_lmac_frames_soft
+// has (beside k_fused the decoder's launches fill what LDS is left, 64-thread workgroups).  Letting the halves reuse the staging
+// space would save 2508 B and still give five, so they keep a space of their own and the counts need no second instantiation.
+typedef uint32_t TchSoftRows[tetra_tch_soft::kSoftWords][kLanes + 1];
+typedef uint32_t TchSoftCols[tetra_tch_soft::kSoftWords][kLanes];
+
+// int8 byte rows.  The workgroup copies its rows into LDS as they lie in memory, a row per iteration and a dword per lane (coalesced:
+// 256 bytes an instruction, where a lane reading its own row would touch 64 cache lines an instruction), transposed into [word][row]; the
+// odd pitch of 65 words keeps both the transposing writes (bank 65 d + q) and the lanes' column reads (bank q) free of conflicts.  Each lane then
+// descrambles its own column in place.  Rows past rows_here are staged as zeros.  biterr_out NULL: no counts.
+__global__ __launch_bounds__(kLanes) void k_tch_rows_soft(const int8_t* __restrict__ soft5, int n_blocks, int in_stride,
+                                                          const uint32_t* __restrict__ scramb_init, int ng, int type2,
+                                                          uint8_t* __restrict__ out, int out_stride,
+                                                          uint32_t* __restrict__ dec_scratch, int dec_pairs,
+                                                          const int* __restrict__ n_blocks_dev, const int* __restrict__ init_index,
+                                                          const uint32_t* __restrict__ seq_tab, uint32_t* __restrict__ biterr_out) {
+    using namespace tetra_tch_soft;
+    __shared__ TchSoftRows in;
+    __shared__ TchOutW outw;
+    const int lane = threadIdx.x;
+    const int blk0 = blockIdx.x * kLanes;
+    const int blk = blk0 + lane;
+    if (n_blocks_dev) {
+        const int have = *n_blocks_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
+    }
+    if (blk0 >= n_blocks) return;
+    const int rows_here = min(kLanes, n_blocks - blk0);
+    const uint32_t code = blk >= n_blocks ? kScrambInitSb1 : scramb_init[init_index ? init_index[blk] : blk];
+#pragma unroll 4
+    for (int q = 0; q < kLanes; ++q) {
+        const uint32_t* row = reinterpret_cast<const uint32_t*>(soft5 + (size_t)(blk0 + q) * in_stride);
+#pragma unroll
+        for (int d = lane; d < kSoftWords; d += kLanes) in[d][q] = q < rows_here ? row[d] : 0u;
+    }
+    __syncthreads();
+    stage_row(code, seq_rows(seq_tab), [&](int g) { return in[g][lane]; }, [&](int g, uint32_t word) { in[g][lane] = word; });
+    TchIo io{ outw, dec_scratch + (size_t)blockIdx.x * dec_pairs * kLanes + lane, lane };
+    const uint32_t biterr = decode_lane(ng, type2, biterr_out != nullptr, [&](int w) { return in[w][lane]; }, io);
+    if (biterr_out && blk < n_blocks) biterr_out[blk] = biterr;
+    __syncthreads();
+    tch_write_rows(outw, lane, rows_here, type2, out + (size_t)blk0 * out_stride, out_stride);
+}
+
+// The TCH jobs of a soft frame launch: k_lmac_frames_soft's prologue and ring front end with the SCH/F layout, verdict 1 and the label;
+// counts_tab.out[job] NULL: the job does not count.  The staged words lie [word][lane].
+__global__ __launch_bounds__(kLanes) void k_tch_frames_soft(const JobTable tab, uint32_t* __restrict__ dec_scratch, const uint32_t* __restrict__ seq_tab,
+                                                            const uint32_t* __restrict__ ring, uint32_t ring_words, const BiterrTable counts_tab) {
+    using namespace tetra_tch_soft;
+    __shared__ TchSoftCols in;
+    __shared__ TchOutW outw;
+    const int lane = threadIdx.x;
+    FrameLane L = frame_group(tab, lane);
+    if (L.blk0 >= L.n_blocks) return;
+    frame_of(tab, L);
+    const DevJob& J = L.J;
+    frame_block(L.code, [&] { return tab.src.bitnum[L.f]; }, [&] { return tab.src.frame_type[L.f]; }, seq_rows(seq_tab),
+                ring_of(ring, ring_words, L.f / tab.src.frames_per_channel), ring_words, [&](int g, uint32_t word) { in[g][lane] = word; });
+    if (L.blk < L.n_blocks) write_verdict(J, tab.src, L.blk, L.f, true);
+    TchIo io{ outw, dec_scratch + J.scratch_base + (size_t)L.group * J.dec_pairs * kLanes + lane, lane };
+    uint32_t* counts = job_counts(tab, counts_tab);            // (workgroup-uniform: a workgroup has one job)
+    const uint32_t biterr = decode_lane(tetra_tch::ng_of_type2(J.type2), J.type2, counts != nullptr, [&](int w) { return in[w][lane]; }, io);
+    if (counts && L.blk < L.n_blocks) counts[L.blk] = biterr;
+    __syncthreads();
+    tch_write_rows(outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
 }
 
 // ---- list decoding of the rows whose CRC failed (include/ext/tetra_list.h; lane code: list_core.hpp) ------------------------------------------
@@ -1262,6 +1336,58 @@ int tetra_lmac_decode_tch_batch(int kind, const uint8_t* type5, int n_blocks, in
     return TETRA_OK;
 }
 
+// ---- include/ext/tetra_tch_soft.h: int8 byte rows -------------------------------------------------------------------------------------
+int tetra_lmac_decode_tch_soft_counted_device(int kind, const int8_t* d_soft, int n_blocks, const int32_t* d_n_blocks, int in_stride,
+                                              const uint32_t* d_scramb_init, const int32_t* d_init_index, uint8_t* d_type2, int out_stride,
+                                              uint32_t* d_biterr, void* hip_stream) {
+    if (kind == TETRA_LMAC_T_TCH_7_2) return TETRA_ERR_ARG;                    // not coded: nothing to gain from soft values
+    const int rc = tch_check_args(kind, d_soft, n_blocks, in_stride, d_scramb_init, d_type2, out_stride, d_biterr, true);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const tetra_tch::Kind k = tetra_tch::kind_of(kind);
+    const uint32_t* seq = seq_table();
+    if (!seq) return TETRA_ERR_NOMEM;
+    const int groups = (n_blocks + kLanes - 1) / kLanes;
+    const int dec_pairs = (k.type2 + kFlush) / 2;
+    ScratchLease scratch;
+    if (const int err = scratch.take((size_t)groups * dec_pairs * kLanes * sizeof(uint32_t), nullptr, 0, s)) return err;
+    hipLaunchKernelGGL(k_tch_rows_soft, dim3(groups), dim3(kLanes), 0, s, d_soft, n_blocks, in_stride, d_scramb_init, k.ng, k.type2, d_type2, out_stride,
+                       scratch.p, dec_pairs, d_n_blocks, d_init_index, seq, d_biterr);
+    return scratch.launched();
+}
+
+int tetra_lmac_decode_tch_soft_batch(int kind, const int8_t* soft5, int n_blocks, int in_stride, const uint32_t* scramb_init,
+                                     uint8_t* type2, int out_stride, uint32_t* biterr, int device) {
+    if (kind == TETRA_LMAC_T_TCH_7_2) return TETRA_ERR_ARG;
+    const int rc = tch_check_args(kind, soft5, n_blocks, in_stride, scramb_init, type2, out_stride, biterr, false);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_HIP;
+    DevMem<int8_t> d_in;
+    DevMem<uint8_t> d_out;
+    DevMem<uint32_t> d_init, d_biterr;
+    const size_t in_bytes = (size_t)n_blocks * in_stride, out_bytes = (size_t)n_blocks * out_stride;
+    if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_init.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess ||
+        (biterr && d_biterr.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess))
+        return TETRA_ERR_NOMEM;
+    if (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_in, soft5, in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int drc = tetra_lmac_decode_tch_soft_counted_device(kind, d_in, n_blocks, nullptr, in_stride, d_init, nullptr, d_out, out_stride,
+                                                              biterr ? (uint32_t*)d_biterr : nullptr, nullptr);
+    if (drc != TETRA_OK) return drc;
+    if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    // only the type2 columns: the caller's row padding is left alone
+    const int row = tetra_tch::kind_of(kind).type2;
+    if (out_stride == row ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
+                          : hipMemcpy2D(type2, out_stride, d_out, out_stride, row, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    return TETRA_OK;
+}
+
 }  // extern "C"
 
 // Every frame entry point (lmac_impl.hpp): one job table, the kernel the options select, the list launches behind it for the jobs with ranks.
@@ -1293,8 +1419,11 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     for (int i = 0; i < n_jobs; ++i) {
         tetra_lmac_job_t j = jobs[i];
         if (tetra_tch::is_tch(j.type)) {
-            if (soft || opts.d_rank) return TETRA_ERR_ARG;         // no soft-decision TCH; no CRC for a list decoder to aim at
+            // soft-decision TCH is tetra_tch_soft.h's entry point alone; no CRC for a list decoder to aim at (there a job is refused for a
+            // rank entry of its own, so that the signalling jobs beside it may be rescued; elsewhere for the array, as ever)
+            if (soft ? !opts.soft_tch || (opts.d_rank && opts.d_rank[i]) : opts.d_rank != nullptr) return TETRA_ERR_ARG;
             const tetra_tch::Kind k = tetra_tch::kind_of(j.type);
+            if (soft && !k.ng) return TETRA_ERR_ARG;               // TCH/7.2 is not coded: from the packed frames
             uint32_t* const job_counts = opts.d_biterr ? opts.d_biterr[i] : nullptr;
             if (j.max_rows < 0 || (job_counts && !k.ng)) return TETRA_ERR_ARG;
             if ((uintptr_t)job_counts & 3) return TETRA_ERR_ALIGN;
@@ -1408,7 +1537,10 @@ int lmac_impl::decode_frames(const tetra_lmac_frames_t* src, const tetra_lmac_jo
     } else {
         hipLaunchKernelGGL(k_lmac_frames<false>, dim3((unsigned)groups_total), dim3(kLanes), 0, s, tab, scratch.p, seq, nullptr);
     }
-    if (tch.n) hipLaunchKernelGGL(k_tch_frames, dim3((unsigned)tch_groups_total), block, 0, s, tch, scratch.p, seq, tch_counts);
+    if (tch.n && soft)
+        hipLaunchKernelGGL(k_tch_frames_soft, dim3((unsigned)tch_groups_total), block, 0, s, tch, scratch.p, seq, reinterpret_cast<const uint32_t*>(soft->d_ring),
+                           soft->size / 4u, tch_counts);
+    else if (tch.n) hipLaunchKernelGGL(k_tch_frames, dim3((unsigned)tch_groups_total), block, 0, s, tch, scratch.p, seq, tch_counts);
     // the jobs with ranks, all in one set of list launches: behind the decode launch, in front of the scratch's hand-back
     RescueTable rt = {};
     for (int k = 0; k < n; ++k) {
@@ -1446,6 +1578,14 @@ int tetra_lmac_decode_frames_soft_device(const tetra_lmac_frames_t* src, const t
                                          uint32_t* const* d_biterr, int32_t* const* d_rank, int max_candidates, void* hip_stream) {
     const lmac_impl::SoftRing ring{ d_ring, ring_size };       // (a NULL ring is refused there: never "no ring", the hard route)
     return lmac_impl::decode_frames(src, jobs, n_jobs, lmac_impl::FrameOpts{ &ring, d_biterr, d_rank, max_candidates, {} }, hip_stream);
+}
+
+int tetra_lmac_decode_frames_soft_tch_device(const tetra_lmac_frames_t* src, const tetra_lmac_job_t* jobs, int n_jobs, const int8_t* d_ring, uint32_t ring_size,
+                                             uint32_t* const* d_biterr, int32_t* const* d_rank, int max_candidates, void* hip_stream) {
+    const lmac_impl::SoftRing ring{ d_ring, ring_size };
+    lmac_impl::FrameOpts opts{ &ring, d_biterr, d_rank, max_candidates, {} };
+    opts.soft_tch = true;
+    return lmac_impl::decode_frames(src, jobs, n_jobs, opts, hip_stream);
 }
 
 size_t tetra_lmac_decode_frames_workspace_bytes(const tetra_lmac_job_t* jobs, int n_jobs) {

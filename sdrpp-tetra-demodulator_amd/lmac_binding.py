@@ -86,17 +86,24 @@ TCH_ABI = {
     "tetra_lmac_decode_tch_batch": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32]),
 }
 T_TCH_7_2, T_TCH_4_8, T_TCH_2_4 = 8, 9, 10          # TETRA_LMAC_T_TCH_*
+# include/ext/tetra_tch_soft.h: TCH/4.8 and TCH/2.4 from soft values
+TCH_SOFT_ABI = {
+    "tetra_lmac_decode_tch_soft_counted_device": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
+    "tetra_lmac_decode_tch_soft_batch": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32]),
+    "tetra_lmac_decode_frames_soft_tch_device": (i32, [P(Frames), P(Job), i32, vp, u32, P(vp), P(vp), i32, vp]),
+}
 LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
 SOFT_EXPORTS = list(SOFT_ABI)
 AACH_SOFT_EXPORTS = list(AACH_SOFT_ABI)
 TCH_EXPORTS = list(TCH_ABI)
+TCH_SOFT_EXPORTS = list(TCH_SOFT_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI, **TCH_ABI},
-                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS + TCH_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI, **TCH_ABI, **TCH_SOFT_ABI},
+                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS + TCH_EXPORTS + TCH_SOFT_EXPORTS)
 
 
 def force_byte_route(on):
@@ -196,6 +203,26 @@ def decode_tch_counted_device(kind, d_type5, capacity, d_n_blocks, in_stride, d_
          ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
 
 
+def decode_tch_soft(kind, soft5, scramb_init, biterr=False, device=-1):
+    """tetra_lmac_decode_tch_soft_batch (include/ext/tetra_tch_soft.h): soft5 int8 [n][in_stride] (in_stride % 4 == 0, >= 432; positive =
+    bit 0, |value| <= 31), scramb_init uint32 [n] -> type2 uint8 [n][type2_bits], and with biterr=True also the channel bit-error words
+    uint32 [n] (split_biterr).  T_TCH_4_8 / T_TCH_2_4 only."""
+    rows = np.ascontiguousarray(soft5, np.int8)
+    n, in_stride = rows.shape
+    ost = tch_blk_param(kind).type2_bits
+    si = np.ascontiguousarray(scramb_init, np.uint32)
+    out = np.zeros((n, ost), np.uint8)
+    be = np.zeros(n, np.uint32) if biterr else None
+    call(_lib().tetra_lmac_decode_tch_soft_batch, int(kind), ptr(rows), n, in_stride, ptr(si), ptr(out), ost, ptr(be), device)
+    return (out, be) if biterr else out
+
+
+def decode_tch_soft_counted_device(kind, d_soft, capacity, d_n_blocks, in_stride, d_scramb, d_init_index, d_type2, out_stride, d_biterr=None, stream=None):
+    """tetra_lmac_decode_tch_soft_counted_device: torch tensors on the GPU (d_soft int8); d_n_blocks, d_init_index and d_biterr may be None."""
+    call(_lib().tetra_lmac_decode_tch_soft_counted_device, int(kind), ptr(d_soft), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
+         ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
+
+
 def decode_batch_list(blk_type, type5, scramb=None, max_candidates=LIST_DEFAULT_CANDIDATES, device=-1):
     """tetra_lmac_decode_batch_list (include/ext/tetra_list.h): decode_batch plus the CRC-aided rescue of the failed rows
     -> (type2, crc_ok, rank int32 [n]: 0 = the decoder's own path passed, k >= 1 = rescued by candidate k, -1 = not rescued)."""
@@ -281,6 +308,17 @@ def decode_frames_soft(d_frames, d_frame_type, jobs, d_ring, ring_size, frames_p
     counts = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
     ranks = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
     call(_lib().tetra_lmac_decode_frames_soft_device, C.byref(src), _job_array(jobs), len(jobs), ptr(d_ring), int(ring_size),
+         counts if counted else None, ranks if ranked else None, int(max_candidates), stream_ptr(stream))
+
+
+def decode_frames_soft_tch(d_frames, d_frame_type, jobs, d_ring, ring_size, frames_per_channel, d_frame_bitnum, max_candidates=LIST_DEFAULT_CANDIDATES,
+                           d_time_rx=None, d_time=None, stream=None, d_workspace=None, counted=True, ranked=True):
+    """tetra_lmac_decode_frames_soft_tch_device (include/ext/tetra_tch_soft.h): decode_frames_soft whose jobs may also be of type T_TCH_4_8 /
+    T_TCH_2_4 (no `rank` on those)."""
+    src = _frames(d_frames, d_frame_type, frames_per_channel, d_frame_bitnum, d_time_rx, d_time, d_workspace)
+    counts = (vp * max(1, len(jobs)))(*[ptr(j.get("biterr")) for j in jobs])
+    ranks = (vp * max(1, len(jobs)))(*[ptr(j.get("rank")) for j in jobs])
+    call(_lib().tetra_lmac_decode_frames_soft_tch_device, C.byref(src), _job_array(jobs), len(jobs), ptr(d_ring), int(ring_size),
          counts if counted else None, ranks if ranked else None, int(max_candidates), stream_ptr(stream))
 
 
