@@ -20,7 +20,8 @@
  * TCH/7.2 is not coded and gains nothing from soft values: every entry point here returns TETRA_ERR_ARG for it; decode it from the
  * packed frames or from byte rows of hard bits (tetra_tch.h).
  *
- * Limits.  NOT built: interleaving over N = 4 or 8 blocks (only N = 1); speech (TCH/S); list decoding of TCH (there is no CRC to aim
+ * Limits.  The entry points declared here decode N = 1 only: interleaving over N = 4 or 8 blocks is tetra_tch_nblk.h's, for soft values
+ * as for hard bits.  NOT built: speech (TCH/S); list decoding of TCH (there is no CRC to aim
  * at); routing inside tetra_rx / tetra_wbrx -- the chain's ring and frames are not exposed to callers, so this serves a caller with a ring
  * of its own, as tetra_soft.h does.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.

@@ -41,6 +41,7 @@
 #include "../../include/ext/tetra_soft.h"
 #include "../../include/ext/tetra_tch.h"
 #include "../../include/ext/tetra_tch_soft.h"
+#include "../../include/ext/tetra_tch_nblk.h"
 #include "../../include/tetra_lmac.h"
 #include "demux_core.hpp"
 #include "compact_core.hpp"
@@ -51,6 +52,7 @@
 #include "soft_core.hpp"
 #include "tch_core.hpp"
 #include "tch_soft_core.hpp"
+#include "tch_nblk_core.hpp"
 
 namespace {
 
@@ -580,6 +582,110 @@ __global__ __launch_bounds__(kLanes) void k_tch_frames_soft(const JobTable tab, 
     if (counts && L.blk < L.n_blocks) counts[L.blk] = biterr;
     __syncthreads();
     tch_write_rows(outw, lane, L.rows_here, J.type2, J.out + (size_t)L.blk0 * J.out_stride, J.out_stride);
+}
+
+// ---- the coded data channels interleaved over N = 1, 4 or 8 blocks (include/ext/tetra_tch_nblk.h; lane code: tch_nblk_core.hpp) --------------
+// Kernels of their own behind a front end of their own; forward pass, traceback, counts, scratch [workgroup][step pair][lane] and row
+// write-back are the siblings' above.  One wavefront per workgroup, an OUTPUT block per lane; ng and N are workgroup-uniform.
+// How the rows reach the lanes: each lane gathers its own 432 positions from the pool, a byte a load.  The window table puts no bound
+// on a workgroup's distinct rows (64 N of them, 221 KB at N = 8, when nothing slides), so staging rows through LDS would need a second
+// route for tables that do not slide; a pre-pass that descrambles the pool once needs a pool-sized scratch and a second launch.  The
+// (432, 103) permutation scatters every read by bytes whichever way the rows are held, and a sliding workgroup's 64 + N - 1 rows
+// (30.7 KB) are read N times out of the vector cache and L2, not out of memory: the gather costs its 432 load instructions a lane, each
+// touching 64 cache lines, not its bytes, at N = 1 as at N = 8, and much the same with 27 loads in flight as with 4
+// (DESIGN.md 8.3 has the measurement and what staging the sliding case through LDS would cost).  A lane touches only its own column
+// of every LDS array below.
+// LDS per workgroup, k_tch_nblk: 3584 (one scrambling sequence a lane) + 7168 (the block as classes, then bits) + 2508 (decoded halves) =
+// 13260 B, twelve workgroups per CU of 160 KB; k_tch_nblk_soft: 27648 (staged bytes) + 3584 (the sequence, and behind the gather the
+// decoded halves in the same space) = 31232 B, five workgroups per CU as k_tch_rows_soft has.
+struct NblkArgs {
+    const void* pool;                  // [n_rows][in_stride] received bursts
+    int n_rows, in_stride;
+    const uint32_t* scramb_init;
+    const int* init_index;             // of the pool's rows, or NULL
+    const int* windows;                // [n_blocks][n]
+    int n, n_blocks;
+    const int* n_blocks_dev;
+    int ng, type2;
+    uint8_t* out;
+    int out_stride;
+    uint32_t* dec_scratch;
+    int dec_pairs;
+    const uint32_t* seq_tab;
+    uint32_t* biterr_out;
+};
+// packed_ok = 0: every workgroup through the class route (tetra_lmac_debug_force_byte_route)
+__global__ __launch_bounds__(kLanes) void k_tch_nblk(const NblkArgs a, int packed_ok) {
+    using namespace tetra_tch_nblk;
+    __shared__ uint32_t seq[kSeqWords][kLanes];
+    __shared__ uint32_t cls[kClsWords + 1][kLanes];
+    __shared__ TchOutW outw;
+    const int lane = threadIdx.x;
+    const int blk0 = blockIdx.x * kLanes;
+    const int blk = blk0 + lane;
+    int n_blocks = a.n_blocks;
+    if (a.n_blocks_dev) {
+        const int have = *a.n_blocks_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
+    }
+    if (blk0 >= n_blocks) return;
+    const int rows_here = min(kLanes, n_blocks - blk0);
+    const bool live = blk < n_blocks;
+    const uint8_t* pool = static_cast<const uint8_t*>(a.pool);
+#pragma unroll
+    for (int w = 0; w <= kClsWords; ++w) cls[w][lane] = 0u;
+    // (a lane past the last block gathers nothing and does not speak for the route)
+    const uint32_t dirty = gather_hard(live ? a.n : 0, a.n_rows, [&](int j) { return a.windows[(size_t)blk * a.n + j]; },
+                                       [&](int r) { return a.scramb_init[a.init_index ? a.init_index[r] : r]; }, seq_rows(a.seq_tab),
+                                       [&](int w, uint32_t word) { seq[w][lane] = word; }, [&](int w) { return seq[w][lane]; },
+                                       [&](int r, int t) -> uint32_t { return pool[(size_t)r * a.in_stride + t]; },
+                                       [&](int w, uint32_t bits) { cls[w][lane] |= bits; });
+    const bool class_route = !packed_ok || __builtin_amdgcn_ballot_w64(dirty != 0) != 0;          // wave-uniform
+    TchIo io{ outw, a.dec_scratch + (size_t)blockIdx.x * a.dec_pairs * kLanes + lane, lane };
+    auto staged = [&](int w) { return cls[w][lane]; };
+    uint32_t biterr;
+    if (!class_route) {
+        classes_to_bits(staged, [&](int w, uint32_t word) { cls[w][lane] = word; });
+        biterr = tetra_tch::decode_lane<true>(a.ng, a.type2, a.biterr_out != nullptr, staged, io);
+    } else {
+        biterr = tetra_tch::decode_lane<false>(a.ng, a.type2, a.biterr_out != nullptr, staged, io);
+    }
+    if (a.biterr_out && live) a.biterr_out[blk] = biterr;
+    __syncthreads();
+    tch_write_rows(outw, lane, rows_here, a.type2, a.out + (size_t)blk0 * a.out_stride, a.out_stride);
+}
+
+__global__ __launch_bounds__(kLanes) void k_tch_nblk_soft(const NblkArgs a) {
+    using namespace tetra_tch_nblk;
+    __shared__ TchSoftCols in;
+    __shared__ union { uint32_t seq[kSeqWords][kLanes]; TchOutW outw; } u;           // the sequence only while gathering
+    static_assert(sizeof(TchOutW) <= sizeof(uint32_t) * kSeqWords * kLanes, "the decoded halves fit the sequence's space");
+    const int lane = threadIdx.x;
+    const int blk0 = blockIdx.x * kLanes;
+    const int blk = blk0 + lane;
+    int n_blocks = a.n_blocks;
+    if (a.n_blocks_dev) {
+        const int have = *a.n_blocks_dev;
+        n_blocks = have < n_blocks ? have : n_blocks;
+    }
+    if (blk0 >= n_blocks) return;
+    const int rows_here = min(kLanes, n_blocks - blk0);
+    const bool live = blk < n_blocks;
+    const uint8_t* pool = static_cast<const uint8_t*>(a.pool);
+#pragma unroll
+    for (int g = 0; g < kSoftWords; ++g) in[g][lane] = 0x80808080u;
+    uint8_t* mine = reinterpret_cast<uint8_t*>(&in[0][lane]);
+    gather_soft(live ? a.n : 0, a.n_rows, [&](int j) { return a.windows[(size_t)blk * a.n + j]; },
+                [&](int r) { return a.scramb_init[a.init_index ? a.init_index[r] : r]; }, seq_rows(a.seq_tab),
+                [&](int w, uint32_t word) { u.seq[w][lane] = word; }, [&](int w) { return u.seq[w][lane]; },
+                [&](int r, int t) -> uint32_t { return pool[(size_t)r * a.in_stride + t]; },
+                [&](int q, uint32_t y) { mine[(size_t)(q >> 2) * (4 * kLanes) + (q & 3)] = (uint8_t)y; });
+    __syncthreads();                    // the sequence's space becomes the decoded halves'
+    TchIo io{ u.outw, a.dec_scratch + (size_t)blockIdx.x * a.dec_pairs * kLanes + lane, lane };
+    const uint32_t biterr = decode_lane(a.ng, a.type2, a.biterr_out != nullptr, [&](int w) { return in[w][lane]; }, io);
+    if (a.biterr_out && live) a.biterr_out[blk] = biterr;
+    __syncthreads();
+    tch_write_rows(u.outw, lane, rows_here, a.type2, a.out + (size_t)blk0 * a.out_stride, a.out_stride);
 }
 
 // ---- list decoding of the rows whose CRC failed (include/ext/tetra_list.h; lane code: list_core.hpp) ------------------------------------------
@@ -1386,6 +1492,98 @@ int tetra_lmac_decode_tch_soft_batch(int kind, const int8_t* soft5, int n_blocks
         return TETRA_ERR_HIP;
     if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
     return TETRA_OK;
+}
+
+// ---- include/ext/tetra_tch_nblk.h ------------------------------------------------------------------------------------------------------
+// tch_check_args for a coded kind behind the checks of N, the pool and the window table
+static int nblk_check_args(int kind, int n, const void* in, int n_rows, int in_stride, const void* init, const void* index, const void* windows,
+                           int n_blocks, const void* out, int out_stride, const void* biterr, bool device_ptrs) {
+    if (kind != TETRA_LMAC_T_TCH_4_8 && kind != TETRA_LMAC_T_TCH_2_4) return TETRA_ERR_ARG;
+    if (!tetra_tch_nblk::valid_n(n) || n_rows < 0) return TETRA_ERR_ARG;
+    if (n_blocks > 0 && !windows) return TETRA_ERR_ARG;
+    const int rc = tch_check_args(kind, in, n_blocks, in_stride, init, out, out_stride, biterr, device_ptrs);
+    if (rc != TETRA_OK) return rc;
+    if (device_ptrs && (((uintptr_t)windows & 3) || ((uintptr_t)init & 3) || ((uintptr_t)index & 3))) return TETRA_ERR_ALIGN;
+    return TETRA_OK;
+}
+
+static int nblk_launch(bool soft, int kind, int n, const void* d_pool, int n_rows, int in_stride, const uint32_t* d_scramb_init,
+                       const int32_t* d_init_index, const int32_t* d_windows, int n_blocks, const int32_t* d_n_blocks, uint8_t* d_type2, int out_stride,
+                       uint32_t* d_biterr, void* hip_stream) {
+    const int rc = nblk_check_args(kind, n, d_pool, n_rows, in_stride, d_scramb_init, d_init_index, d_windows, n_blocks, d_type2, out_stride, d_biterr, true);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const tetra_tch::Kind k = tetra_tch::kind_of(kind);
+    const uint32_t* seq = seq_table();
+    if (!seq) return TETRA_ERR_NOMEM;
+    const int groups = (n_blocks + kLanes - 1) / kLanes;
+    const int dec_pairs = (k.type2 + kFlush) / 2;
+    ScratchLease scratch;
+    if (const int err = scratch.take((size_t)groups * dec_pairs * kLanes * sizeof(uint32_t), nullptr, 0, s)) return err;
+    const NblkArgs a{ d_pool, n_rows, in_stride, d_scramb_init, d_init_index, d_windows, n, n_blocks, d_n_blocks, k.ng, k.type2, d_type2, out_stride,
+                      scratch.p, dec_pairs, seq, d_biterr };
+    if (soft) hipLaunchKernelGGL(k_tch_nblk_soft, dim3(groups), dim3(kLanes), 0, s, a);
+    else hipLaunchKernelGGL(k_tch_nblk, dim3(groups), dim3(kLanes), 0, s, a, g_force_byte_route ? 0 : 1);
+    return scratch.launched();
+}
+
+int tetra_lmac_decode_tch_nblk_device(int kind, int n_interleave, const uint8_t* d_type5, int n_rows, int in_stride,
+                                      const uint32_t* d_scramb_init, const int32_t* d_init_index, const int32_t* d_windows, int n_blocks,
+                                      const int32_t* d_n_blocks, uint8_t* d_type2, int out_stride, uint32_t* d_biterr, void* hip_stream) {
+    return nblk_launch(false, kind, n_interleave, d_type5, n_rows, in_stride, d_scramb_init, d_init_index, d_windows, n_blocks, d_n_blocks, d_type2,
+                       out_stride, d_biterr, hip_stream);
+}
+
+int tetra_lmac_decode_tch_nblk_soft_device(int kind, int n_interleave, const int8_t* d_soft, int n_rows, int in_stride,
+                                           const uint32_t* d_scramb_init, const int32_t* d_init_index, const int32_t* d_windows, int n_blocks,
+                                           const int32_t* d_n_blocks, uint8_t* d_type2, int out_stride, uint32_t* d_biterr, void* hip_stream) {
+    return nblk_launch(true, kind, n_interleave, d_soft, n_rows, in_stride, d_scramb_init, d_init_index, d_windows, n_blocks, d_n_blocks, d_type2,
+                       out_stride, d_biterr, hip_stream);
+}
+
+// both host-pointer variants: the pool, its codes and the window table in, the type2 columns and the counts out
+static int nblk_batch(bool soft, int kind, int n, const void* pool, int n_rows, int in_stride, const uint32_t* scramb_init, const int32_t* windows,
+                      int n_blocks, uint8_t* type2, int out_stride, uint32_t* biterr, int device) {
+    const int rc = nblk_check_args(kind, n, pool, n_rows, in_stride, scramb_init, nullptr, windows, n_blocks, type2, out_stride, biterr, false);
+    if (rc != TETRA_OK || n_blocks == 0) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TETRA_ERR_NO_DEVICE;
+    DeviceGuard g(device);
+    if (!g.ok) return TETRA_ERR_HIP;
+    DevMem<uint8_t> d_in, d_out;
+    DevMem<uint32_t> d_init, d_biterr;
+    DevMem<int32_t> d_win;
+    // (an empty pool is allowed: every window is then lost; the device side never reads it)
+    const size_t in_bytes = (size_t)(n_rows ? n_rows : 1) * in_stride, out_bytes = (size_t)n_blocks * out_stride;
+    const size_t init_bytes = sizeof(uint32_t) * (n_rows ? n_rows : 1), win_bytes = sizeof(int32_t) * (size_t)n_blocks * n;
+    if (d_in.reserve(in_bytes) != hipSuccess || d_out.reserve(out_bytes) != hipSuccess || d_init.reserve(init_bytes) != hipSuccess ||
+        d_win.reserve(win_bytes) != hipSuccess || (biterr && d_biterr.reserve(sizeof(uint32_t) * n_blocks) != hipSuccess))
+        return TETRA_ERR_NOMEM;
+    if ((n_rows && (hipMemcpy(d_init, scramb_init, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(d_in, pool, (size_t)n_rows * in_stride, hipMemcpyHostToDevice) != hipSuccess)) ||
+        hipMemcpy(d_win, windows, win_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return TETRA_ERR_HIP;
+    const int drc = nblk_launch(soft, kind, n, d_in, n_rows, in_stride, d_init, nullptr, d_win, n_blocks, nullptr, d_out, out_stride,
+                                biterr ? (uint32_t*)d_biterr : nullptr, nullptr);
+    if (drc != TETRA_OK) return drc;
+    if (hipDeviceSynchronize() != hipSuccess) return TETRA_ERR_HIP;
+    // only the type2 columns: the caller's row padding is left alone
+    const int row = tetra_tch::kind_of(kind).type2;
+    if (out_stride == row ? hipMemcpy(type2, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess
+                          : hipMemcpy2D(type2, out_stride, d_out, out_stride, row, n_blocks, hipMemcpyDeviceToHost) != hipSuccess)
+        return TETRA_ERR_HIP;
+    if (biterr && hipMemcpy(biterr, d_biterr, sizeof(uint32_t) * n_blocks, hipMemcpyDeviceToHost) != hipSuccess) return TETRA_ERR_HIP;
+    return TETRA_OK;
+}
+
+int tetra_lmac_decode_tch_nblk_batch(int kind, int n_interleave, const uint8_t* type5, int n_rows, int in_stride, const uint32_t* scramb_init,
+                                     const int32_t* windows, int n_blocks, uint8_t* type2, int out_stride, uint32_t* biterr, int device) {
+    return nblk_batch(false, kind, n_interleave, type5, n_rows, in_stride, scramb_init, windows, n_blocks, type2, out_stride, biterr, device);
+}
+
+int tetra_lmac_decode_tch_nblk_soft_batch(int kind, int n_interleave, const int8_t* soft5, int n_rows, int in_stride, const uint32_t* scramb_init,
+                                          const int32_t* windows, int n_blocks, uint8_t* type2, int out_stride, uint32_t* biterr, int device) {
+    return nblk_batch(true, kind, n_interleave, soft5, n_rows, in_stride, scramb_init, windows, n_blocks, type2, out_stride, biterr, device);
 }
 
 }  // extern "C"

@@ -92,18 +92,28 @@ TCH_SOFT_ABI = {
     "tetra_lmac_decode_tch_soft_batch": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32]),
     "tetra_lmac_decode_frames_soft_tch_device": (i32, [P(Frames), P(Job), i32, vp, u32, P(vp), P(vp), i32, vp]),
 }
+# include/ext/tetra_tch_nblk.h: TCH/4.8 and TCH/2.4 interleaved over N = 1, 4 or 8 blocks, hard bits and soft values
+TCH_NBLK_ABI = {
+    "tetra_lmac_decode_tch_nblk_device": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "tetra_lmac_decode_tch_nblk_soft_device": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "tetra_lmac_decode_tch_nblk_batch": (i32, [i32, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]),
+    "tetra_lmac_decode_tch_nblk_soft_batch": (i32, [i32, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]),
+}
 LMAC_EXPORTS, AACH_EXPORTS, BITERR_EXPORTS, LIST_EXPORTS = list(SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI), list(LIST_ABI)
 SOFT_EXPORTS = list(SOFT_ABI)
 AACH_SOFT_EXPORTS = list(AACH_SOFT_ABI)
 TCH_EXPORTS = list(TCH_ABI)
 TCH_SOFT_EXPORTS = list(TCH_SOFT_ABI)
+TCH_NBLK_EXPORTS = list(TCH_NBLK_ABI)
 
 
 @functools.lru_cache(None)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the Reed-Muller decoder)
-    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI, **TCH_ABI, **TCH_SOFT_ABI},
-                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS + TCH_EXPORTS + TCH_SOFT_EXPORTS)
+    return declare(load_library(), {**SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **LIST_ABI, **SOFT_ABI, **AACH_SOFT_ABI, **TCH_ABI, **TCH_SOFT_ABI,
+                                     **TCH_NBLK_ABI},
+                   optional=AACH_EXPORTS + BITERR_EXPORTS + LIST_EXPORTS + SOFT_EXPORTS + AACH_SOFT_EXPORTS + TCH_EXPORTS + TCH_SOFT_EXPORTS +
+                   TCH_NBLK_EXPORTS)
 
 
 def force_byte_route(on):
@@ -221,6 +231,61 @@ def decode_tch_soft_counted_device(kind, d_soft, capacity, d_n_blocks, in_stride
     """tetra_lmac_decode_tch_soft_counted_device: torch tensors on the GPU (d_soft int8); d_n_blocks, d_init_index and d_biterr may be None."""
     call(_lib().tetra_lmac_decode_tch_soft_counted_device, int(kind), ptr(d_soft), int(capacity), ptr(d_n_blocks), int(in_stride), ptr(d_scramb),
          ptr(d_init_index), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
+
+
+def tch_windows(stream_lengths, n, lost=()):
+    """The sliding-window table of include/ext/tetra_tch_nblk.h for streams laid end to end in the pool: a stream of L received rows gives
+    L - n + 1 output blocks (none if L < n), block b of it the rows b .. b + n - 1 of the stream; every listed pool row in `lost` is marked -1.
+    -> int32 [n_blocks][n].  Pure: needs no library."""
+    n = int(n)
+    if n not in (1, 4, 8):
+        raise ValueError("n must be 1, 4 or 8")
+    rows, at = [], 0
+    for length in stream_lengths:
+        length = int(length)
+        if length < 0:
+            raise ValueError("a stream length is negative")
+        rows += [np.arange(at + b, at + b + n) for b in range(length - n + 1)]
+        at += length
+    w = np.array(rows, np.int32).reshape(-1, n)
+    gone = np.asarray(list(lost), np.int64)
+    w[np.isin(w, gone)] = -1
+    return w
+
+
+def decode_tch_nblk(kind, n, rows, windows, scramb_init, soft=False, biterr=False, device=-1):
+    """tetra_lmac_decode_tch_nblk_batch / _soft_batch (include/ext/tetra_tch_nblk.h): rows uint8 (soft: int8) [n_rows][in_stride], the pool
+    of received bursts (in_stride % 4 == 0, >= 432); windows int32 [n_blocks][n] (tch_windows; an entry outside the pool = a lost burst);
+    scramb_init uint32 [n_rows] -> type2 uint8 [n_blocks][type2_bits], and with biterr=True also the channel bit-error words uint32
+    [n_blocks] (split_biterr).  T_TCH_4_8 / T_TCH_2_4, n in (1, 4, 8)."""
+    pool = np.ascontiguousarray(rows, np.int8 if soft else np.uint8)
+    n_rows, in_stride = pool.shape
+    win = np.ascontiguousarray(windows, np.int32)
+    if win.ndim != 2 or win.shape[1] != int(n):
+        raise ValueError("windows must be [n_blocks][n]")
+    ost = tch_blk_param(kind).type2_bits
+    si = np.ascontiguousarray(scramb_init, np.uint32)
+    if len(si) != n_rows:
+        raise ValueError("scramb_init must have a code per pool row")
+    out = np.zeros((len(win), ost), np.uint8)
+    be = np.zeros(len(win), np.uint32) if biterr else None
+    fn = _lib().tetra_lmac_decode_tch_nblk_soft_batch if soft else _lib().tetra_lmac_decode_tch_nblk_batch
+    call(fn, int(kind), int(n), ptr(pool), n_rows, in_stride, ptr(si), ptr(win), len(win), ptr(out), ost, ptr(be), device)
+    return (out, be) if biterr else out
+
+
+def decode_tch_nblk_device(kind, n, d_type5, n_rows, in_stride, d_scramb, d_init_index, d_windows, n_blocks, d_n_blocks, d_type2, out_stride,
+                           d_biterr=None, stream=None):
+    """tetra_lmac_decode_tch_nblk_device: torch tensors on the GPU; d_init_index, d_n_blocks and d_biterr may be None."""
+    call(_lib().tetra_lmac_decode_tch_nblk_device, int(kind), int(n), ptr(d_type5), int(n_rows), int(in_stride), ptr(d_scramb), ptr(d_init_index),
+         ptr(d_windows), int(n_blocks), ptr(d_n_blocks), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
+
+
+def decode_tch_nblk_soft_device(kind, n, d_soft, n_rows, in_stride, d_scramb, d_init_index, d_windows, n_blocks, d_n_blocks, d_type2, out_stride,
+                                d_biterr=None, stream=None):
+    """tetra_lmac_decode_tch_nblk_soft_device: decode_tch_nblk_device on int8 soft values."""
+    call(_lib().tetra_lmac_decode_tch_nblk_soft_device, int(kind), int(n), ptr(d_soft), int(n_rows), int(in_stride), ptr(d_scramb), ptr(d_init_index),
+         ptr(d_windows), int(n_blocks), ptr(d_n_blocks), ptr(d_type2), int(out_stride), ptr(d_biterr), stream_ptr(stream))
 
 
 def decode_batch_list(blk_type, type5, scramb=None, max_candidates=LIST_DEFAULT_CANDIDATES, device=-1):
