@@ -24,12 +24,19 @@ def _decode(tpsap, rows, codes, T, soft):
     return d["out"], d["ok"], d["rank"]
 
 
-def channel_rows(oracle, bits, channel, T, soft=None):
+def channel_rows(oracle, bits, channel, T, soft=None, sync=None):
     """-> {(kind, channel, bitnum): (crc_ok, time on entry, time, type-1 bytes, rank, (errors, compared) of tetra_biterr.h on the row's
     final bits)} for the coded kinds of one channel's stream.
-    soft: the quantiser's value per bit (same numbering) for the soft route, else None.  The SB1s are decoded as one batch ahead of
+    soft: the quantiser's value per bit (same numbering) for the soft route, else None.  sync: the synchroniser (sync(); default the
+    burst-synchroniser oracle), as tests/soft_pipeline.channel_rows takes it.  The SB1s are decoded as one batch ahead of
     tests/chain_host.walk (they need no code), which runs under the host build of the tracker's clock and the numpy scramb_code."""
-    frames, types, bitnums = oracle.BurstSyncOracle().feed(bits, chunk=1)
+    return channel_walk(oracle, bits, channel, T, soft, sync)[0]
+
+
+def channel_walk(oracle, bits, channel, T, soft=None, sync=None):
+    """channel_rows, and the walk behind it -> (the rows, dict: frames uint8 [n][510], types, bitnums, and per frame the scrambling code in
+    force behind its SB1, the packed time on entry and after the SB1, and the SB1's answer (type-2 bits, crc_ok) or None)."""
+    frames, types, bitnums = (sync or oracle.BurstSyncOracle)().feed(bits, chunk=1)
     nfr = len(frames)
 
     def cut(kind, which):
@@ -50,7 +57,7 @@ def channel_rows(oracle, bits, channel, T, soft=None):
         for j, f in enumerate(which):
             count = D.count_errors(tpsap, rx[j], int(codes[f]), t2[j], soft is not None)
             out[(kind, channel, int(bitnums[f]))] = (int(ok[j]), int(t_rx[f]), int(t_af[f]), t2[j][:ch.TYPE1_BITS[kind]].tobytes(), int(rank[j]), count)
-    return out
+    return out, dict(frames=frames, types=types, bitnums=bitnums, codes=codes, t_rx=t_rx, t_af=t_af, sb1=[s[3] for s in steps])
 
 
 def rescued_sb1_matters(with_list, without):
