@@ -21,9 +21,9 @@
  * channel error can already lose a TCH/4.8 block: that is the code, and it is reproduced, not mended.
  *
  * Limits.  The entry points declared here decode N = 1 only; interleaving over N = 4 or 8 blocks (EN 300 392-2 8.2.4.2) is
- * tetra_tch_nblk.h's, with entry points of its own over a pool of received bursts and a window table.  tetra_rx / tetra_wbrx do not route
- * traffic slots: which (carrier, timeslot) carries circuit-mode data, and at which rate, is upper-MAC knowledge that stays on the host,
- * which lists those slots' frames and hands them to a TCH job.  No speech (TCH/S).  Soft-decision decoding of TCH/4.8
+ * tetra_tch_nblk.h's, with entry points of its own over a pool of received bursts and a window table.  Which (carrier, timeslot) carries circuit-mode
+ * data, and at which rate, is upper-MAC knowledge that stays on the host: it lists those slots' frames and hands them to a TCH job, or
+ * names the timeslots to tetra_rx / tetra_wbrx, which then route them to these jobs themselves (tetra_traffic.h).  No speech (TCH/S).  Soft-decision decoding of TCH/4.8
  * and TCH/2.4 is tetra_tch_soft.h's, with entry points of its own; the ones declared here read hard bits.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */

@@ -35,8 +35,9 @@
  * different length share a launch.  The caller keeps its pool of received bursts and only lists windows; there is no device state and
  * no handle.
  *
- * Limits.  NOT built: window jobs of the frame decoders (a call's frame array does not hold earlier calls' bursts); routing inside
- * tetra_rx / tetra_wbrx; speech (TCH/S); an encoder.  TCH/7.2 is not coded and not interleaved: TETRA_ERR_ARG.
+ * Limits.  NOT built: window jobs of the frame decoders (a call's frame array does not hold earlier calls' bursts), and so
+ * no N = 4 / 8 inside tetra_rx / tetra_wbrx either, whose routing of the traffic slots the host names is N = 1 (tetra_traffic.h); speech
+ * (TCH/S); an encoder.  TCH/7.2 is not coded and not interleaved: TETRA_ERR_ARG.
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */
 #ifndef TETRA_TCH_NBLK_H

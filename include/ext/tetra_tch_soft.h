@@ -22,8 +22,8 @@
  *
  * Limits.  The entry points declared here decode N = 1 only: interleaving over N = 4 or 8 blocks is tetra_tch_nblk.h's, for soft values
  * as for hard bits.  NOT built: speech (TCH/S); list decoding of TCH (there is no CRC to aim
- * at); routing inside tetra_rx / tetra_wbrx -- the chain's ring and frames are not exposed to callers, so this serves a caller with a ring
- * of its own, as tetra_soft.h does.
+ * at).  The chain's ring and frames are not exposed to callers, so these entry points serve a caller with a ring of its own, as
+ * tetra_soft.h does; inside tetra_rx / tetra_wbrx the chain's own ring feeds the same jobs for the timeslots the host names (tetra_traffic.h).
  * Same conventions as tetra_lmac.h: extern "C", int status (TETRA_OK / TETRA_ERR_*), no exceptions, GPU only.
  */
 #ifndef TETRA_TCH_SOFT_H

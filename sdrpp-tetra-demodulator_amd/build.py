@@ -6,7 +6,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtetra_demod_hip.so")
-SOURCES = ["tetra_demod.hip", "tetra_chan.hip", "tetra_resamp.hip", "tetra_burst_scan.hip", "tetra_lmac.hip", "tetra_burst_sync.hip", "tetra_rx.hip", "tetra_rx_out.hip", "tetra_wbrx.hip", "tetra_retune.hip", "tetra_iqcond.hip"]
+SOURCES = ["tetra_demod.hip", "tetra_chan.hip", "tetra_resamp.hip", "tetra_burst_scan.hip", "tetra_lmac.hip", "tetra_burst_sync.hip", "tetra_rx.hip", "tetra_rx_out.hip", "tetra_rx_traffic.hip", "tetra_wbrx.hip", "tetra_retune.hip", "tetra_iqcond.hip"]
 # Every regular file in csrc/ and every public header, as paths relative to csrc/, sorted: what the build id is taken over.  Read from
 # the tree, so that a new header cannot be forgotten and leave a stale library looking current.
 DEPS = sorted([f for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))] +

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "../../include/ext/tetra_biterr.h"
 #include "../../include/tetra_rx.h"
 #include "bsync_core.hpp"
@@ -56,6 +58,28 @@ constexpr int kAachDistByte = 30, kAachMarginByte = 31;
 struct ColSrc {                   // a column of one kind and parity on the device: element j at base + j * stride
     const uint8_t* base;
     size_t stride;
+};
+
+// ext/tetra_traffic.h (tetra_rx_traffic.hip): what tetra_rx_traffic_enable allocates.  List k holds TETRA_LMAC_T_TCH_7_2 + k.
+constexpr int kTrafficKinds = 3;
+struct TrafficBufs {              // one parity's rows of one TCH kind
+    DevMem<uint8_t> t2;           // [max_rows][stride]
+    DevMem<int32_t> ok;           // [max_rows] (all 1: the decoder's verdict for a block without a CRC)
+    DevMem<tetra_rx_block_t> blocks;      // [max_rows]
+    DevMem<uint32_t> biterr;              // [max_rows] (TETRA_RX_FLAG_BITERR, the two coded kinds)
+};
+struct TrafficState {
+    int max_rows = 0;
+    TrafficBufs res[2][kTrafficKinds];
+    DevMem<int32_t> lists[2];             // [kTrafficKinds][max_rows] routed frames
+    DevMem<int32_t> counts[2];            // [kTrafficKinds][3] routed, kept, dropped
+    DevMem<int32_t> work;                 // [kTrafficKinds][blocks of 256 entries] the compaction's words
+    DevMem<uint8_t> table;                // [C][4] tetra_rx_traffic_slot_t
+    DevMem<void> ws;                      // the TCH decode launch's decision scratch
+    ListRing to_device;                   // table entries on their way to the device
+    Event ev_set;                         // the latest tetra_rx_set_traffic's copy into the table ...
+    bool set_pending = false;             // ... which the next tail waits for on its stream
+    bool ever_set = false;
 };
 
 }  // namespace tetra_rx_impl
@@ -129,7 +153,13 @@ struct tetra_rx {
     Event ev_reset;                       // the latest reset's work on the stream it was given ...
     bool reset_pending = false;           // ... which the next process call waits for on ITS stream
     bool owned = false;                   // inside a wideband handle (tetra_wbrx_rx): that handle restarts its channels, the entry point refuses
+    std::unique_ptr<TrafficState> traffic;    // ext/tetra_traffic.h: null until tetra_rx_traffic_enable
 };
+
+// tetra_rx_traffic.hip: the routing and the TCH decode of call parity b behind the tail's other launches on s (a handle with `traffic`)
+namespace traffic_impl {
+TETRA_HIDDEN int enqueue(tetra_rx* h, int b, hipStream_t s);
+}
 
 // A row column (COL_*) of this handle: every fetch, device view and delivery asks here whether it exists and where it lies.
 namespace row_col TETRA_HIDDEN {

@@ -261,6 +261,7 @@ int enqueue_tail(tetra_rx* h, int b, hipStream_t s) {
         HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipEventRecord(h->ev_stage[3], s));
+    if (h->traffic) TETRA_TRY(traffic_impl::enqueue(h, b, s));      // ext/tetra_traffic.h: outside the stages' spans, in front of the tail's event
     h->snap_taken[b] = 0;
     if (h->snap_mask) {      // behind the link figures and outside the stages' spans; in front of the tail's event, which a delivery waits for
         SnapArgs a = {};
@@ -536,6 +537,11 @@ int tetra_rx_process_device(tetra_rx_t* h, const float* d_iq, int n_samples, voi
     if (h->out_pending[b]) {
         HIP_TRY(h, hipStreamWaitEvent(sb, h->ev_out[b], 0));
         h->out_pending[b] = false;
+    }
+    // a table change since the last call (ext/tetra_traffic.h): this tail and every later one read the new table
+    if (h->traffic && h->traffic->set_pending) {
+        HIP_TRY(h, hipStreamWaitEvent(sb, h->traffic->ev_set, 0));
+        h->traffic->set_pending = false;
     }
     TETRA_TRY(enqueue_tail(h, b, sb));
     HIP_TRY(h, hipEventRecord(h->ev_tail[b], sb));

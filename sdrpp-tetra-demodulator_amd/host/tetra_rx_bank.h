@@ -5,6 +5,7 @@
 // verdict, TDMA time and channel, plus the per-channel cell state (tcd / t_phy_state).  Header-only; links libtetra_demod_hip.so.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "ext/tetra_list.h"
 #include "ext/tetra_rx_out_ext.h"
 #include "ext/tetra_sync_tol.h"
+#include "ext/tetra_traffic.h"
 #include "tetra_rx.h"
 #include "tetra_rx_out.h"
 
@@ -239,6 +241,32 @@ public:
     }
     // ... and every channel's hand-over status
     int handoverStatus(std::vector<tetra_handover_status_t>& out) { return table(tetra_rx_get_handover, out); }
+    // Traffic slots (ext/tetra_traffic.h): once per bank, at most maxRows rows per TCH kind and call (0: the handle's most) ...
+    int enableTraffic(int maxRows = 0) { return tetra_rx_traffic_enable(h_, maxRows > 0 ? maxRows : tetra_rx_max_rows(h_)); }
+    // ... the table entries of channels first .. first + slots.size() / 4 - 1, four per channel (timeslots 1..4), from the next call on;
+    // enqueued on hipStream, not waited for ...
+    int setTraffic(int first, const std::vector<tetra_rx_traffic_slot_t>& slots, void* hipStream = nullptr) {
+        if (slots.size() % 4) return TETRA_ERR_ARG;
+        return tetra_rx_set_traffic(h_, first, (int)(slots.size() / 4), slots.data(), hipStream);
+    }
+    // ... and the rows of one TCH kind (TETRA_LMAC_T_TCH_*) of the latest call (which = 0) or the one before it (1): type1 holds the
+    // kind's type-2 bits (432 / 292 / 148 per row, the type-1 bits first), biterr the count words where the handle counts (the coded
+    // kinds under TETRA_RX_FLAG_BITERR); *dropped (may be null): the rows routed beyond maxRows
+    int fetchTraffic(int tchKind, Blocks& out, int* dropped = nullptr, int which = 0) {
+        int n = 0;
+        int rc = tetra_rx_fetch_traffic(h_, which, tchKind, nullptr, nullptr, 0, 0, nullptr, &n, dropped);
+        if (rc != TETRA_OK) return rc;
+        out.clear();
+        out.bitsPerBlock = tchKind == TETRA_LMAC_T_TCH_7_2 ? 432 : tchKind == TETRA_LMAC_T_TCH_4_8 ? 292 : 148;
+        out.info.resize((size_t)n);
+        out.type1.resize((size_t)n * (size_t)out.bitsPerBlock);
+        if (n == 0) return TETRA_OK;
+        out.biterr.resize((size_t)n);
+        rc = tetra_rx_fetch_traffic(h_, which, tchKind, out.info.data(), out.type1.data(), out.bitsPerBlock, n, out.biterr.data(), &n, dropped);
+        if (rc != TETRA_ERR_UNSUPPORTED) return rc;
+        out.biterr.clear();                  // no counts on this handle or for this kind
+        return tetra_rx_fetch_traffic(h_, which, tchKind, out.info.data(), out.type1.data(), out.bitsPerBlock, n, nullptr, &n, dropped);
+    }
     // the PI4DQPSK setters of the demodulators inside (tetra_demod_set_param ids); waits for work in flight first
     int setParam(int paramId, double value) {
         const int rc = tetra_rx_wait(h_);
@@ -398,6 +426,35 @@ public:
         return TETRA_OK;
     }
     int handoverStatus(std::vector<tetra_handover_status_t>& out) { return gather(out, [](TetraRxBank& b, auto& part) { return b.handoverStatus(part); }); }
+    // Traffic slots (ext/tetra_traffic.h): every shard keeps up to maxRows rows per kind and call (0: its most) ...
+    int enableTraffic(int maxRows = 0) { return each([&](Shard& s) { return s.bank.enableTraffic(maxRows); }); }
+    // ... the table entries of the bank's channels first .. first + slots.size() / 4 - 1, every shard told its own; a range outside the
+    // bank is TETRA_ERR_ARG with no shard told anything (an entry a shard refuses leaves the shards before it changed) ...
+    int setTraffic(int first, const std::vector<tetra_rx_traffic_slot_t>& slots, void* const* streams = nullptr) {
+        const long long count = (long long)(slots.size() / 4);
+        if (slots.size() % 4 || first < 0 || first + count > channels_) return TETRA_ERR_ARG;
+        for (size_t s = 0; s < shards_.size(); s++) {
+            const long long lo = std::max<long long>(first, shards_[s]->first), hi = std::min<long long>(first + count, shards_[s]->first + shards_[s]->count);
+            if (lo >= hi) continue;
+            const std::vector<tetra_rx_traffic_slot_t> part(slots.begin() + (lo - first) * 4, slots.begin() + (hi - first) * 4);
+            const int rc = shards_[s]->bank.setTraffic((int)(lo - shards_[s]->first), part, streams ? streams[s] : nullptr);
+            if (rc != TETRA_OK) return rc;
+        }
+        return TETRA_OK;
+    }
+    // ... and the shards' rows one after the other: bank channel numbers, (channel, frame) order; *dropped: summed over the shards
+    int fetchTraffic(int tchKind, TetraRxBank::Blocks& out, int* dropped = nullptr, int which = 0) {
+        out.clear();
+        if (dropped) *dropped = 0;
+        TetraRxBank::Blocks part;
+        return each([&](Shard& s) {
+            int d = 0;
+            const int rc = s.bank.fetchTraffic(tchKind, part, &d, which);
+            if (rc == TETRA_OK) out.append(part, s.first);
+            if (dropped) *dropped += d;
+            return rc;
+        });
+    }
     int channels() const { return channels_; }
     int shards() const { return (int)shards_.size(); }
     void shardInfo(int shard, int& first, int& count) const { first = shards_[(size_t)shard]->first; count = shards_[(size_t)shard]->count; }

@@ -158,6 +158,37 @@ OUT_ROWS_ABI = {
     "tetra_rx_out_write_rows_device": (i32, [P(OutRows), i32, i32, i32, i32, i64, vp, u64, vp, size_t, vp]),
 }
 RX_OUT_ROWS_EXPORTS = list(OUT_ROWS_ABI)
+# include/ext/tetra_traffic.h (the traffic slots the host names, decoded as TCH blocks)
+TCH_7_2, TCH_4_8, TCH_2_4 = 8, 9, 10          # TETRA_LMAC_T_TCH_*
+TRAFFIC_TYPE2_BITS = {TCH_7_2: 432, TCH_4_8: 292, TCH_2_4: 148}
+TRAFFIC_TYPE1_BITS = {TCH_7_2: 432, TCH_4_8: 288, TCH_2_4: 144}
+TRAFFIC_STRIDE = {TCH_7_2: 432, TCH_4_8: 296, TCH_2_4: 152}
+TRAFFIC_SLOT_DTYPE = np.dtype([("kind", "u1"), ("usage", "u1"), ("pad", "u1", (2,))])          # tetra_rx_traffic_slot_t
+TRAFFIC_ABI = {
+    "tetra_rx_traffic_enable": (i32, [vp, i32]),
+    "tetra_rx_set_traffic": (i32, [vp, i32, i32, vp, vp]),
+    "tetra_rx_get_traffic": (i32, [vp, i32, i32, vp]),
+    "tetra_rx_fetch_traffic": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, P(i32), P(i32)]),
+    "tetra_rx_traffic_rows_device": (i32, [vp, i32, i32, P(vp), P(i32), P(vp), P(vp), P(vp), vp]),
+}
+RX_TRAFFIC_EXPORTS = list(TRAFFIC_ABI)
+
+
+def traffic_table_arg(table):
+    """A traffic table as tetra_rx_set_traffic takes it: a TRAFFIC_SLOT_DTYPE array [n][4] as it is; else per channel {tn: kind} or
+    {tn: (kind, usage)} for the timeslots 1..4 that carry traffic (None or {}: none)."""
+    if isinstance(table, np.ndarray) and table.dtype == TRAFFIC_SLOT_DTYPE:
+        return np.ascontiguousarray(table).reshape(-1, 4)
+    t = np.zeros((len(table), 4), TRAFFIC_SLOT_DTYPE)
+    for c, slots in enumerate(table):
+        for tn, v in (slots or {}).items():
+            if not 1 <= int(tn) <= 4:
+                raise ValueError("timeslots are 1..4")
+            kind, usage = v if isinstance(v, tuple) else (v, 0)
+            t[c, int(tn) - 1]["kind"], t[c, int(tn) - 1]["usage"] = int(kind), int(usage)
+    return t
+
+
 RX_EXPORTS, RX_OUT_EXPORTS = list(SIGNATURES), list(OUT_SIGNATURES)
 RX_RETUNE_EXPORTS, RX_AACH_EXPORTS, RX_BITERR_EXPORTS = list(RETUNE_SIGNATURES), list(AACH_SIGNATURES), list(BITERR_ABI)
 RX_OUT_EXT_EXPORTS = list(OUT_EXT_ABI)
@@ -169,9 +200,9 @@ RX_GAP_EXPORTS = list(GAP_ABI)
 def _lib():
     # (a TETRA_DEMOD_LIB override may be an older build without the hand-off, retune and AACH additions)
     return declare(load_library(), {**SIGNATURES, **OUT_SIGNATURES, **RETUNE_SIGNATURES, **AACH_SIGNATURES, **BITERR_ABI, **SYNC_TOL_ABI, **LIST_ABI,
-                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI, **AACH_SOFT_ABI, **GAP_ABI},
+                                    **OUT_EXT_ABI, **HANDOVER_ABI, **OUT_ROWS_ABI, **AACH_SOFT_ABI, **GAP_ABI, **TRAFFIC_ABI},
                    optional=RX_OUT_EXPORTS + RX_RETUNE_EXPORTS + RX_AACH_EXPORTS + RX_BITERR_EXPORTS + list(SYNC_TOL_ABI) + list(LIST_ABI) +
-                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS + list(AACH_SOFT_ABI) + RX_GAP_EXPORTS)
+                   RX_OUT_EXT_EXPORTS + RX_HANDOVER_EXPORTS + RX_OUT_ROWS_EXPORTS + list(AACH_SOFT_ABI) + RX_GAP_EXPORTS + RX_TRAFFIC_EXPORTS)
 
 
 def type1_bits(kind):
@@ -373,6 +404,45 @@ class RxChain:
 
     def demod_handle(self):
         return self._lib.tetra_rx_demod(self._h)
+
+    # ---- include/ext/tetra_traffic.h ----
+    def enable_traffic(self, max_rows=None):
+        """tetra_rx_traffic_enable: once per handle, synchronises; max_rows (None: the handle's max_rows) rows per TCH kind and call are
+        kept.  Until then every traffic method raises TETRA_ERR_UNSUPPORTED."""
+        call(self._lib.tetra_rx_traffic_enable, self._h, int(self.max_rows if max_rows is None else max_rows))
+
+    def set_traffic(self, table, first=0, stream=None):
+        """tetra_rx_set_traffic: the entries of channels first .. first + len(table) - 1 (traffic_table_arg: per channel {tn: kind} or
+        {tn: (kind, usage)}, or a TRAFFIC_SLOT_DTYPE array [n][4]), from the next process call on; enqueued on `stream`, not waited for."""
+        t = traffic_table_arg(table)
+        call(self._lib.tetra_rx_set_traffic, self._h, int(first), int(t.shape[0]), ptr(t) if t.size else None, stream_ptr(stream))
+
+    def traffic(self, first=0, count=None):
+        """tetra_rx_get_traffic -> TRAFFIC_SLOT_DTYPE array [count][4], the table on the device."""
+        count = self.n_channels - first if count is None else count
+        t = np.zeros((max(count, 1), 4), TRAFFIC_SLOT_DTYPE)
+        call(self._lib.tetra_rx_get_traffic, self._h, int(first), int(count), ptr(t))
+        return t[:count]
+
+    def fetch_traffic(self, tch_kind, which=0, biterr=False):
+        """tetra_rx_fetch_traffic -> (blocks [n] of BLOCK_DTYPE, type2 uint8 [n][TRAFFIC_TYPE2_BITS[tch_kind]], rows dropped beyond
+        max_rows) and, with biterr (FLAG_BITERR, the coded kinds), the uint32 words errors | compared << 16 [n] as a fourth."""
+        n, dropped = C.c_int(0), C.c_int(0)
+        call(self._lib.tetra_rx_fetch_traffic, self._h, which, int(tch_kind), None, None, 0, 0, None, C.byref(n), C.byref(dropped))
+        cap, nb = max(n.value, 1), TRAFFIC_TYPE2_BITS[int(tch_kind)]
+        blocks, t2, be = np.zeros(cap, BLOCK_DTYPE), np.zeros((cap, nb), np.uint8), np.zeros(cap, np.uint32)
+        call(self._lib.tetra_rx_fetch_traffic, self._h, which, int(tch_kind), ptr(blocks), ptr(t2), nb, cap, ptr(be) if biterr else None, C.byref(n),
+             C.byref(dropped))
+        out = (blocks[:n.value], t2[:n.value], dropped.value)
+        return out + (be[:n.value],) if biterr else out
+
+    def traffic_rows_device(self, tch_kind, which=0, stream=None):
+        """tetra_rx_traffic_rows_device -> (d_type2, type2_stride, d_blocks, d_counts [routed, kept, dropped], d_biterr or None): raw
+        device addresses."""
+        t2, blk, cnt, be, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        call(self._lib.tetra_rx_traffic_rows_device, self._h, which, int(tch_kind), C.byref(t2), C.byref(st), C.byref(blk), C.byref(cnt), C.byref(be),
+             stream_ptr(stream))
+        return t2.value, st.value, blk.value, cnt.value, be.value
 
     def set_snapshot(self, chan_extras):
         """tetra_rx_out_set_snapshot: the channel extras (EXT_CHAN_*) every tail from the next call on copies into its call's snapshot,

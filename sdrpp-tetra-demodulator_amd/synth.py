@@ -231,7 +231,41 @@ def tx_encode(kind, type1, codes):
     return t4 ^ tx_scramb_seq(uniq, n345)[inv]
 
 
-_PHASE_OF_DIBIT = np.array([1, 3, -1, -3])               # dibit value (first bit << 1 | second) -> phase step in pi/4 (EN 300 392-2 5.5.2.3 = PHASE_STEP)
+# The circuit-mode data channels (EN 300 392-2 8.2.3.1.5 / .6, 8.3.1; include/ext/tetra_tch.h): kind -> (type2 bits, type1 bits, the
+# puncturer's t, its P and the divisor of i = j + (j - 1) // d); TCH/7.2 (kind 8) is scrambled only.
+TX_TCH = {9: (292, 288, 3, (0, 1, 2, 5), 65), 10: (148, 144, 6, (0, 1, 2, 3, 5, 6, 7), 35)}
+TX_TCH_TYPE1 = {8: 432, 9: 288, 10: 144}
+
+
+def tx_encode_tch(kind, type1, codes):
+    """type-1 bits uint8 [m][432 / 288 / 144] of TCH/7.2 / 4.8 / 2.4 (kind 8 / 9 / 10) + scrambling codes uint32 [m] -> type-5 bits uint8
+    [m][432]: four zero tail bits, the rate-1/4 mother code, the 292/432 or 148/432 puncturer, the (432, 103) block interleaver,
+    scrambling.  No CRC.  tests/test_rx_traffic.py holds it against the reference's own encoder chain."""
+    t1 = np.asarray(type1, np.uint8).reshape(-1, TX_TCH_TYPE1[kind])
+    m = t1.shape[0]
+    if kind == 8:
+        t4 = t1.copy()
+    else:
+        n2, n1, t, P, d = TX_TCH[kind]
+        t2 = np.zeros((m, n2 + 4), np.uint8)              # 4 leading zeros = the encoder's initial state, 4 zero tail bits
+        t2[:, 4:4 + n1] = t1
+        b, d1, d2, d3, d4 = t2[:, 4:], t2[:, 3:-1], t2[:, 2:-2], t2[:, 1:-3], t2[:, :-4]
+        mother = np.empty((m, 4 * n2), np.uint8)
+        mother[:, 0::4] = b ^ d1 ^ d4
+        mother[:, 1::4] = b ^ d2 ^ d3 ^ d4
+        mother[:, 2::4] = b ^ d1 ^ d2 ^ d4
+        mother[:, 3::4] = b ^ d1 ^ d3 ^ d4
+        j = np.arange(1, 433)
+        i = j + (j - 1) // d
+        k = 8 * ((i - 1) // t) + np.array(P)[i - t * ((i - 1) // t)]               # (P is indexed 1..t)
+        t3 = mother[:, k - 1]
+        t4 = np.empty_like(t3)
+        t4[:, (103 * j) % 432] = t3
+    uniq, inv = np.unique(np.asarray(codes, np.uint32).reshape(m), return_inverse=True)
+    return t4 ^ tx_scramb_seq(uniq, 432)[inv]
+
+
+_PHASE_OF_DIBIT = np.array([1, 3, -1, -3])             # dibit value (first bit << 1 | second) -> phase step in pi/4 (EN 300 392-2 5.5.2.3 = PHASE_STEP)
 
 
 def _phase_adj(burst, n1, n2):
@@ -266,7 +300,7 @@ def tdma_time_of_slot(s):
     return s % 4 + 1, (s // 4) % 18 + 1, (s // 72) % 60 + 1
 
 
-def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None):
+def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None, traffic=None, aach_codewords=None):
     """A coded continuous downlink of one cell: slot s (absolute s + slot0) carries
          s % 4 == 0   SYNC burst: SB1 = SYNC PDU (60 type-1 bits: the cell's colour code at bits 4..9, the slot's TN-1 / FN / MN at
                       10..11 / 12..16 / 17..22, MCC at 31..40, MNC at 41..54 -- the fields tetra_lower_mac.c:246-275 reads --, the rest
@@ -276,7 +310,12 @@ def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None):
     everything but SB1 scrambled with the cell's code.  Returns (bits uint8 [n_slots * 510], sent) with sent = {kind: [(slot,
     type-1 bits)]} for kind in sb1 / sb2 / ndb1 / ndb2 / schf / bbk (bbk: the 30 descrambled AACH bits).
     aach: uint8 [n_slots][30], the AACH's 30 bits per slot before scrambling (e.g. RM(30,14) codewords, with or without bit errors)
-    in place of the seeded random bits; everything else of the stream is the same with and without it."""
+    in place of the seeded random bits; everything else of the stream is the same with and without it.
+    traffic: {tn: (kind, usage)} -- the one-channel normal bursts of these timeslots (only tn 2 and 4 carry them) outside frame 18 carry
+    a TCH block (kind 8 / 9 / 10 = TCH/7.2 / 4.8 / 2.4, tx_encode_tch) with a payload seeded apart from the rest of the stream in place
+    of SCH/F, and, for a usage other than 0, the RM(30,14) codeword of header 1, field 1 = usage, field 2 = 0 as their AACH --
+    aach_codewords: uint32 [16384], the code's word per 14-bit information word, first bit on air at bit 29.  sent gains "tch":
+    [(slot, kind, type-1 bits)] and loses those slots' "schf" entries; without the option the stream is what it is without it."""
     rng = np.random.default_rng(seed)
     mcc, mnc, cc = cell
     code = tx_scramb_code(mcc, mnc, cc)
@@ -296,6 +335,20 @@ def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None):
     if aach is not None:
         t1["bbk"] = np.ascontiguousarray(aach, np.uint8).reshape(n_slots, 30) & 1
     t5 = {k: tx_encode({"ndb1": "ndb", "ndb2": "ndb"}.get(k, k), v, np.full(len(v), code, np.uint32)) for k, v in t1.items() if k != "bbk"}
+    tch = {}                                               # row of s_schf -> (kind, type-1 bits)
+    if traffic:
+        trng = np.random.default_rng([int(seed), 0x7c4])
+        for r, s in enumerate(s_schf):
+            tn, fn, _ = tdma_time_of_slot(int(s) + slot0)
+            if tn not in traffic or fn == 18:
+                continue
+            kind, usage = traffic[tn]
+            pay = trng.integers(0, 2, TX_TCH_TYPE1[kind], dtype=np.uint8)
+            tch[r] = (kind, pay)
+            t5["schf"][r] = tx_encode_tch(kind, pay, [code])[0]
+            if usage:
+                word = int(np.asarray(aach_codewords)[1 << 12 | (usage & 0x3f) << 6])
+                t1["bbk"][s] = [(word >> (29 - i)) & 1 for i in range(30)]
     bb = t1["bbk"] ^ tx_scramb_seq([code], 30)[0][None, :]
     out = np.zeros((n_slots, 510), np.uint8)
     for r, s in enumerate(s_sync):
@@ -307,6 +360,9 @@ def gen_downlink(n_slots, seed, cell=(262, 1, 5), slot0=0, aach=None):
     sent = {"sb1": list(zip(s_sync.tolist(), t1["sb1"])), "sb2": list(zip(s_sync.tolist(), t1["sb2"])),
             "ndb1": list(zip(s_ndb.tolist(), t1["ndb1"])), "ndb2": list(zip(s_ndb.tolist(), t1["ndb2"])),
             "schf": list(zip(s_schf.tolist(), t1["schf"])), "bbk": list(zip(slots.tolist(), t1["bbk"]))}
+    if traffic:
+        sent["schf"] = [e for r, e in enumerate(sent["schf"]) if r not in tch]
+        sent["tch"] = [(int(s_schf[r]), k, pay) for r, (k, pay) in sorted(tch.items())]
     return out.reshape(-1), sent
 
 

@@ -334,6 +334,22 @@ class WidebandRx:
         """The AACH rows' margins (RxChain.fetch_aach_margin of the chain)."""
         return self.rx.fetch_aach_margin(which)
 
+    # include/ext/tetra_traffic.h by carrier slot: RxChain's methods of the chain (a retune leaves a slot's table entries as they are)
+    def enable_traffic(self, max_rows=None):
+        self.rx.enable_traffic(max_rows)
+
+    def set_traffic(self, table, first=0, stream=None):
+        self.rx.set_traffic(table, first, stream)
+
+    def traffic(self, first=0, count=None):
+        return self.rx.traffic(first, count)
+
+    def fetch_traffic(self, tch_kind, which=0, biterr=False):
+        return self.rx.fetch_traffic(tch_kind, which, biterr)
+
+    def traffic_rows_device(self, tch_kind, which=0, stream=None):
+        return self.rx.traffic_rows_device(tch_kind, which, stream)
+
     def bin_power(self):
         out = np.zeros(self.M, np.float32)
         call(self._lib.tetra_wbrx_bin_power, self._h, ptr(out))
